@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline bench: output megapixels/s of RealESRGAN_x2plus x2 upscaling on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up for W steps, times exactly K steps and prints one JSON line: `value` (output MP/s),
+`ms_per_step` (wall time of one timed step) and the `roofline` object measured on that same timed region.
+`--dump-outputs DIR` then writes what the last timed step computed as DIR/output.npy (float32; an output larger than
+64 MB is replaced by a fixed, seeded sample of its elements).  Everything that takes runs of its own -- the objects
+listed below, `frames_in_flight` and the host-to-host `enhance()` rate -- is measured only with `--full`.
 
 N > 1 may be started plainly (this process then spawns `python -m torch.distributed.run --nproc-per-node N` on
 127.0.0.1 before it touches a GPU, and relays rank 0's JSON line) or under torch.distributed.run as the driver does
@@ -12,10 +18,10 @@ input already resident in HBM as the NCHW float tensor RealESRGANer.process() ha
 boundary).  Frames are independent units, so N GPUs run their own frames with no data-path
 collective ("scaling": "weak").  `value` is one frame at a time per GPU -- the reference's batch-1 call
 (standalone/direct_esrgan.py:148), whose dense blocks run as rdb_f16x2_kernel -- and the `roofline` object describes that same
-timed region and kernel.  `frames_in_flight` is the extra: THROUGHPUT with 4 independent frames per GPU, each on its own HIP stream
+timed region and kernel.  `frames_in_flight` (--full) is the extra: THROUGHPUT with 4 independent frames per GPU, each on its own HIP stream
 and context replica (per-layer kernels: the persistent kernel wants the device to itself), timed right after.
 
-The line also carries
+With --full the line also carries
   strict_f32   the same frame on the f32 matrix cores (Winograd F(2x2,3x3) and direct implicit GEMM): ms, MP/s,
                fraction of the 157.3 TFLOP/s f32 MFMA peak, max abs vs the CPU oracle -- the default `dtype` is f32 in /
                out / accumulate with operands carried as f16 (hi, lo) pairs, so the strict forms are timed beside it;
@@ -114,6 +120,29 @@ def pmc_traffic(key):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 4 << 20           # elements kept of an output above the limit (seeded, so the same ones on every run)
+
+
+def dump_outputs(dirname, arrays):
+    """Writes each array (torch tensor on any device, or numpy) as DIR/<name>.npy in float32, for comparing two builds
+    output for output.  An array of more than DUMP_LIMIT_BYTES / len(arrays) bytes as float32 is reduced to the elements at
+    a fixed set of flat indices (numpy seed 0, sorted, drawn from its element count), saved 1-D."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    per_array = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        t = torch.from_numpy(np.ascontiguousarray(a)) if isinstance(a, np.ndarray) else a.detach()
+        if t.numel() * 4 > per_array:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=min(DUMP_SAMPLE, per_array // 4)))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            log(f"dump: {name} has {a.numel() if hasattr(a, 'numel') else a.size} elements; kept a seeded sample of {t.numel()}")
+        path = os.path.join(dirname, f"{name}.npy")
+        np.save(path, t.float().cpu().numpy())
+        log(f"dump: wrote {path} {tuple(t.shape)} float32")
+
+
 def net_input(frame_bgr_u8, crop=None):
     """HWC uint8 BGR -> [1,3,H,W] float32 RGB in [0,1] (numpy's correctly rounded /255, as enhance() computes it)."""
     import numpy as np
@@ -207,12 +236,17 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-crop", type=int, default=512, help="side of the crop the CPU oracle is timed on (0 = skip)")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the strict_f32 / c3 / c3_stream objects of the default c2 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: frames_in_flight, the host-to-host enhance() rate, the CPU "
+                         "oracle baseline and parity, and (c2) the strict_f32 / c3 / c3_stream / c4_stream objects")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/output.npy (float32, at most 64 MB)")
+    ap.add_argument("--cpu-crop", type=int, default=512, help="--full: side of the crop the CPU oracle is timed on (0 = skip)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the CPU oracle baseline and parity")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the strict_f32 / c3 / c3_stream objects of the c2 line")
     ap.add_argument("--inflight", type=int, default=None,
-                    help="frames in flight per GPU for the `frames_in_flight` extra of the single-tile workloads (each on its own HIP "
-                         "stream and context replica); default 4 for c2 / c2-bf16, 0 = skip; `value` is always one frame at a time")
+                    help="--full: frames in flight per GPU for the `frames_in_flight` extra of the single-tile workloads (each on its "
+                         "own HIP stream and context replica); default 4 for c2 / c2-bf16, 0 = skip; `value` is always one frame at a time")
     ap.add_argument("--f32-algo", default=None, choices=["split", "winograd", "direct"],
                     help="conv algorithm of the fp32 workloads (default split: f16 hi+lo operand pairs)")
     ap.add_argument("--filters", action="store_true", help="c5: also run the reference's cv2 pre / post filters (imgproc.py: NL-means + CLAHE, adaptive unsharp)")
@@ -247,16 +281,21 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
+    last = {}
+
     def timed(fn, steps, warmup):
-        """W untimed steps, then exactly `steps` steps between barrier + synchronize brackets; max over ranks (s)."""
+        """W untimed steps, then exactly `steps` steps between barrier + synchronize brackets; max over ranks (s).
+        What the last step returned is left in last["out"]."""
         for _ in range(warmup):
             fn()
         sync_all()
         t0 = time.perf_counter()
+        out = None
         for _ in range(steps):
-            fn()
+            out = fn()
         sync_all()
         el = time.perf_counter() - t0
+        last["out"] = out
         if world > 1:
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -328,8 +367,11 @@ def main():
     k_ms, k_launches, k_flops = model.kernel_time()
     model.set_kernel_timing(dev, False)
     model.check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": last.pop("out")})
+    last.clear()
     flight = None
-    if extra_inflight > 1:
+    if args.full and extra_inflight > 1:
         # the throughput extra: `extra_inflight` independent frames per step, each on its own stream with its own context replica --
         # a 512x512 frame's per-layer launches are one-round grids of 256-512 workgroups (all in their prologue, then all in their
         # epilogue, 1.3 us between dependent kernels), so a second frame's kernels fill the gaps (tools/probes/concurrent_frames.py)
@@ -411,11 +453,12 @@ def main():
                                       "note": "throughput with independent frames on their own HIP streams and context replicas (per-layer kernels); "
                                               "not the headline: `value` and `roofline` are one frame at a time"}
 
-    extras = args.workload == "c2" and not args.no_extras
+    extras = args.full and args.workload == "c2" and not args.no_extras
     yref = xc = None
     if rank == 0:
-        # host-to-host enhance() (PCIe + quantisation inclusive), reported beside the metric, never as `value`
         log(f"timed region done: {elapsed:.3f} s for {args.steps} steps")
+    if rank == 0 and args.full:
+        # host-to-host enhance() (PCIe + quantisation inclusive), reported beside the metric, never as `value`
         up.enhance(frame)                                  # warm (workspace for the u8 path)
         t1 = time.perf_counter()
         up.enhance(frame)
@@ -615,15 +658,17 @@ def bench_c5(args, wl, dev, rank, world, timed):
         trace.clear()
         last["out"] = nesr_adapter.enhance_iterations(up, img, cfg, "cuda", trace=trace, filters=args.filters)
 
-    steps = max(1, min(args.steps, 3))
-    el = timed(step, steps, min(args.warmup, 1))
+    steps = args.steps
+    el = timed(step, steps, args.warmup)
     up.model.check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"output": last["out"]})
     out_mp = last["out"].shape[0] * last["out"].shape[1] / 1e6
     flops = sum(t["net_input_px"] for t in trace) * up.model.forward_flops(1, 1, 1)      # tile overlaps included: executed, not algorithmic
     if rank == 0:
         print(json.dumps({
             "metric": "output megapixels/sec, nesr pipeline ESRGAN stage x3 iterations (x2plus tensor shapes, 12-channel 4x quirk), host uint8 in -> host uint8 out",
-            "value": round(world * steps * out_mp / el, 3), "unit": "MP/s", "n_gpus": world, "steps": steps, "warmup": min(args.warmup, 1),
+            "value": round(world * steps * out_mp / el, 3), "unit": "MP/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * el / steps, 1), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": F32_ALGOS["split"]["dtype"], "data": "synthetic (seeded frame, seeded random-init weights)",
             "config": {"workload": f"c5: {wl['desc']}",

@@ -10,6 +10,6 @@ F=$(echo $CTRS | cut -d' ' -f1)
 mkdir -p $OUT
 cd /tmp
 rm -rf $OUT/pmc_$F
-timeout -k 10 300 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/pmc_$F -- python3 $R/bench.py --steps 3 --warmup 1 --cpu-crop 0 --inflight 1 --no-extras "$@" > $OUT/pmc_$F.log 2>&1
+timeout -k 10 300 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/pmc_$F -- python3 $R/bench.py --full --steps 3 --warmup 1 --cpu-crop 0 --inflight 1 --no-extras "$@" > $OUT/pmc_$F.log 2>&1
 python3 $R/tools/pmc_summary.py $OUT/pmc_$F | tee $OUT/pmc_$F.txt
 rm -rf $OUT/pmc_$F
