@@ -67,6 +67,26 @@ enum {
 int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuffle, int num_feat,
                 int num_block, int num_grow_ch, int num_out_ch, int dtype);
 
+/* Activations of SRVGGNetCompact (upstream act_type 'prelu' | 'relu' | 'leakyrelu'; LeakyReLU's slope is 0.1). */
+enum { NESR_ACT_PRELU = 0, NESR_ACT_RELU = 1, NESR_ACT_LEAKYRELU = 2 };
+
+/*
+ * Replaces: SRVGGNetCompact.__init__ (realesrgan archs/srvgg_arch.py), the network of the realesr-general-x4v3 (and its -wdn
+ * twin), realesr-animevideov3 checkpoints the reference fetches (standalone/download-x3-model.py:77-116):
+ *     body = conv3x3(in, F), act, (conv3x3(F, F), act) x num_conv, conv3x3(F, out * s * s)
+ *     out  = pixel_shuffle(body(x), s) + nearest_upsample(x, s)
+ * State dict: body.{2i}.weight / .bias for the convs, body.{2i+1}.weight [F] for each PReLU (none for relu / leakyrelu).
+ *   num_feat 64, num_in_ch == num_out_ch == 3, upscale 2 or 4, 1 <= num_conv <= 1024, act_type one of NESR_ACT_*,
+ *   dtype NESR_DTYPE_F32_SPLIT (f32 as f16 pairs, range word as for nesr_create) or NESR_DTYPE_BF16; anything else NESR_ERR_ARG.
+ * On such a context nesr_load_weight, nesr_finalize_weights, nesr_num_tensors, nesr_forward (output [N, 3, sH, sW]),
+ * nesr_forward_u8, nesr_workspace_bytes, nesr_reserve, nesr_forward_flops, nesr_set_kernel_timing / nesr_kernel_time_ms
+ * (the num_conv body convs), nesr_check_status, nesr_check_range and nesr_destroy work as documented for nesr_create;
+ * nesr_set_size_independent and nesr_set_concurrent are accepted (the kernel choice never depends on size or batch);
+ * the RRDB-only entries (ragged, band, sharded, fused / strip switches, preferred batch) return NESR_ERR_ARG.
+ */
+int nesr_create_compact(nesr_ctx** out, int device_id, int num_in_ch, int num_out_ch, int num_feat, int num_conv, int upscale,
+                        int act_type, int dtype);
+
 /*
  * Replaces: model.load_state_dict(loadnet[keyname], strict=True) in RealESRGANer.__init__
  * (realesrgan utils.py), reached from nesr/nesr.py:220-229, standalone/direct_esrgan.py:118-127.
@@ -186,7 +206,8 @@ int nesr_set_concurrent(nesr_ctx* ctx, int concurrent);
  * that gives up raises an abort word that ends all other waits of that forward at once, nesr_check_range / nesr_check_status
  * then return NESR_ERR_HIP for it, and the context switches to per-layer launches for good (f32: the same values bit for bit;
  * bf16: the per-layer kernels' values) -- re-run the frame.  nesr_set_fused(ctx, 0 | 1) makes that choice by hand;
- * nesr_fused_state returns bit 0 = persistent launches enabled, bits 1.. = forwards that gave up so far.
+ * nesr_fused_state returns bit 0 = persistent launches enabled, bits 1.. = forwards that gave up so far; a NEGATIVE value is an
+ * error code, not a bitmask (NESR_ERR_ARG on an SRVGGNetCompact context, which has no persistent launches).
  * nesr_debug_fault is a TEST HOOK: the next persistent launch leaves out its last `drop_workgroups` workgroups (their
  * neighbours' waits must end in the abort word within the time limit).
  * Stands behind the same reference calls as nesr_forward (nesr/nesr.py:887-891, standalone/direct_esrgan.py:148).

@@ -15,11 +15,13 @@ LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT = 0, 1, 2, 3
 ROUND_TRUNC, ROUND_NEAREST = 0, 1
+ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 
 # name -> (restype, argtypes); must list every symbol include/nesr_hip.h declares
 _c = ctypes
 SIGNATURES = {
     "nesr_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_create_compact": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "nesr_load_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
     "nesr_finalize_weights": (_c.c_int, [_c.c_void_p]),
     "nesr_num_tensors": (_c.c_int, [_c.c_void_p]),

@@ -19,6 +19,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "compact_api.h"
 #include "nesr_kernels.h"
 
 using namespace nesr;
@@ -54,6 +55,8 @@ struct Layer {
 
 }  // namespace
 
+int nesr::set_error(int code, const std::string& msg) { return fail(code, msg); }
+
 // byte offsets of the feature maps inside the workspace
 struct WsLayout {
     size_t in, f, a, b, c, u1, u2, u3, sync, total;
@@ -68,6 +71,7 @@ struct FwState {
 };
 
 struct nesr_ctx {
+    nesr_compact* compact = nullptr;   // nesr_create_compact: an SRVGGNetCompact context (compact_api.cpp); no other field is used
     int device = 0, cin0 = 3, unshuffle = 0, nf = 64, nb = 23, gc = 32, nout = 3, dtype = 0;
     bool winograd = false;   // f32 feature-map convs by Winograd F(2x2,3x3) (NESR_DTYPE_F32_WINOGRAD)
     int kgroup = 8;  // K-group of the conv kernel: cin padding granule
@@ -696,9 +700,27 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     return NESR_OK;
 }
 
-int nesr_num_tensors(const nesr_ctx* c) { return c ? (int)c->layers.size() * 2 : 0; }
+int nesr_create_compact(nesr_ctx** out, int device_id, int num_in_ch, int num_out_ch, int num_feat, int num_conv, int upscale,
+                        int act_type, int dtype) {
+    if (!out) return fail(NESR_ERR_ARG, "out is null");
+    *out = nullptr;
+    nesr_compact* k = nullptr;
+    const int rc = compact_create(&k, device_id, num_in_ch, num_out_ch, num_feat, num_conv, upscale, act_type, dtype);
+    if (rc) return rc;
+    nesr_ctx* c = new nesr_ctx();
+    c->compact = k;
+    c->device = device_id;
+    *out = c;
+    return NESR_OK;
+}
+
+int nesr_num_tensors(const nesr_ctx* c) {
+    if (c && c->compact) return compact_num_tensors(c->compact);
+    return c ? (int)c->layers.size() * 2 : 0;
+}
 
 int nesr_load_weight(nesr_ctx* c, const char* key, const float* data, const int64_t* shape, int ndim) {
+    if (c && c->compact && key && data && shape) return compact_load_weight(c->compact, key, data, shape, ndim);
     if (!c || !key || !data || !shape) return fail(NESR_ERR_ARG, "null argument");
     std::string k(key);
     const size_t dot = k.rfind('.');
@@ -725,6 +747,7 @@ int nesr_load_weight(nesr_ctx* c, const char* key, const float* data, const int6
 }
 
 int nesr_finalize_weights(nesr_ctx* c) {
+    if (c && c->compact) return compact_finalize(c->compact);
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     std::string missing;
     int nmiss = 0;
@@ -853,12 +876,16 @@ int nesr_finalize_weights(nesr_ctx* c) {
 }
 
 int nesr_forward(nesr_ctx* c, const void* x_dev, int N, int C, int H, int W, void* y_dev, void* stream) {
+    if (c && c->compact && x_dev && y_dev)
+        return compact_forward(c->compact, static_cast<const float*>(x_dev), nullptr, 0, N, C, H, W, static_cast<float*>(y_dev), nullptr, 0,
+                               static_cast<hipStream_t>(stream));
     if (!c || !x_dev || !y_dev) return fail(NESR_ERR_ARG, "null argument");
     return run_forward(c, static_cast<const float*>(x_dev), nullptr, 0, N, C, H, W, static_cast<float*>(y_dev), nullptr, 0,
                        static_cast<hipStream_t>(stream));
 }
 
 int nesr_forward_ragged(nesr_ctx* c, const void* x_dev, int N, int C, int H, int W, const int* hw, void* y_dev, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_forward_ragged: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !x_dev || !y_dev || !hw) return fail(NESR_ERR_ARG, "null argument");
     if (c->dtype != NESR_DTYPE_BF16) return fail(NESR_ERR_ARG, "nesr_forward_ragged: compute dtype bf16 only (the other forms batch equal-sized images)");
     if (N < 1 || N > nesr::RAG_MAX) return fail(NESR_ERR_ARG, "nesr_forward_ragged: 1.." + std::to_string(nesr::RAG_MAX) + " images per call");
@@ -881,6 +908,7 @@ int nesr_forward_ragged(nesr_ctx* c, const void* x_dev, int N, int C, int H, int
 }
 
 int nesr_set_size_independent(nesr_ctx* c, int on) {
+    if (c && c->compact) return NESR_OK;
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->size_independent = on ? 1 : 0;
     return NESR_OK;
@@ -888,6 +916,9 @@ int nesr_set_size_independent(nesr_ctx* c, int on) {
 
 int nesr_forward_u8(nesr_ctx* c, const uint8_t* in_hwc_dev, int H, int W, uint8_t* out_hwc_dev, int flip_rgb,
                     int round_mode, void* stream) {
+    if (c && c->compact && in_hwc_dev && out_hwc_dev)
+        return compact_forward(c->compact, nullptr, in_hwc_dev, flip_rgb ? 1 : 0, 1, 3, H, W, nullptr, out_hwc_dev, round_mode,
+                               static_cast<hipStream_t>(stream));
     if (!c || !in_hwc_dev || !out_hwc_dev) return fail(NESR_ERR_ARG, "null argument");
     const int u = c->ufac();
     if (c->cin0 != 3 * u * u || c->nout != 3)
@@ -897,18 +928,21 @@ int nesr_forward_u8(nesr_ctx* c, const uint8_t* in_hwc_dev, int H, int W, uint8_
 }
 
 size_t nesr_workspace_bytes(const nesr_ctx* c, int N, int H, int W) {
+    if (c && c->compact) return compact_workspace_bytes(c->compact, N, H, W);
     if (!c || N <= 0 || H <= 0 || W <= 0) return 0;
     const int u = c->ufac();
     return ws_layout(c, N, (H + u - 1) / u, (W + u - 1) / u).total;
 }
 
 int nesr_reserve(nesr_ctx* c, int N, int H, int W) {
+    if (c && c->compact) return compact_reserve(c->compact, N, H, W);
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
     return ensure_ws(c, nesr_workspace_bytes(c, N, H, W));
 }
 
 double nesr_forward_flops(const nesr_ctx* c, int N, int H, int W) {
+    if (c && c->compact) return compact_flops(c->compact, N, H, W);
     if (!c) return 0.0;
     const int u = c->ufac();
     const double px = (double)N * (H / u) * (W / u);
@@ -924,6 +958,7 @@ double nesr_forward_flops(const nesr_ctx* c, int N, int H, int W) {
 }
 
 int nesr_preferred_batch(const nesr_ctx* c, int H, int W, int max_batch) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_preferred_batch: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || H <= 0 || W <= 0 || max_batch <= 1) return 1;
     const int u = c->ufac();
     const int h = (H + u - 1) / u, w = (W + u - 1) / u;
@@ -951,12 +986,14 @@ int nesr_preferred_batch(const nesr_ctx* c, int H, int W, int max_batch) {
 }
 
 int nesr_set_concurrent(nesr_ctx* c, int concurrent) {
+    if (c && c->compact) return NESR_OK;
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->shared_device = concurrent ? 1 : 0;
     return NESR_OK;
 }
 
 int nesr_set_fused(nesr_ctx* c, int on) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_set_fused: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->rdb_mode = on ? c->rdb_mode_init : 0;          // on: what the context was created with (NESR_RDB_FUSE / NESR_STRIP, default auto)
     c->strip_mode = on ? c->strip_mode_init : 0;
@@ -964,24 +1001,28 @@ int nesr_set_fused(nesr_ctx* c, int on) {
 }
 
 int nesr_fused_state(const nesr_ctx* c) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_fused_state: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return 0;
     const int on = c->dtype == NESR_DTYPE_BF16 ? c->strip_mode != 0 : (c->dtype == NESR_DTYPE_F32_SPLIT && c->rdb_mode != 0);
     return (on ? 1 : 0) | (c->fused_aborts << 1);
 }
 
 int nesr_debug_fault(nesr_ctx* c, int drop_workgroups) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_debug_fault: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->debug_drop = drop_workgroups > 0 ? drop_workgroups : 0;
     return NESR_OK;
 }
 
 int nesr_set_kernel_timing(nesr_ctx* c, int enable) {
+    if (c && c->compact) return compact_set_timing(c->compact, enable);
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->timing = enable != 0;
     return NESR_OK;
 }
 
 int nesr_kernel_time_ms(nesr_ctx* c, double* total_ms, int64_t* launches, double* flops) {
+    if (c && c->compact) return compact_kernel_time_ms(c->compact, total_ms, launches, flops);
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
     double ms = 0.0;
@@ -1002,6 +1043,7 @@ int nesr_kernel_time_ms(nesr_ctx* c, double* total_ms, int64_t* launches, double
 }
 
 int nesr_check_status(nesr_ctx* c) {
+    if (c && c->compact) return compact_check_status(c->compact);
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1014,6 +1056,7 @@ int nesr_check_status(nesr_ctx* c) {
 }
 
 int nesr_check_range(nesr_ctx* c, void* stream) {
+    if (c && c->compact) return compact_check_range(c->compact, static_cast<hipStream_t>(stream));
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (c->dtype != NESR_DTYPE_F32_SPLIT && !c->strip_used) return NESR_OK;   // the other forms compute in formats with f32's range
     HIP_TRY(hipSetDevice(c->device));
@@ -1068,6 +1111,11 @@ int nesr_check_range(nesr_ctx* c, void* stream) {
 }
 
 void nesr_destroy(nesr_ctx* c) {
+    if (c && c->compact) {
+        compact_destroy(c->compact);
+        delete c;
+        return;
+    }
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
@@ -1090,6 +1138,7 @@ void nesr_destroy(nesr_ctx* c) {
 // The caller runs the stages in order and refreshes the apron rows of the feature map each stage reads
 // (nesr_band_rows) with its neighbours' band rows in between; banded.py holds that protocol.
 int nesr_band_begin(nesr_ctx* c, const void* x_dev, int C, int H, int W, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_begin: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !x_dev) return fail(NESR_ERR_ARG, "null argument");
     c->band_valid = false;
     int rc = fw_setup(c, 1, C, H, W, c->band);
@@ -1100,6 +1149,7 @@ int nesr_band_begin(nesr_ctx* c, const void* x_dev, int C, int H, int W, void* s
 }
 
 int nesr_band_rdb(nesr_ctx* c, int index, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_rdb: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     if (index < 0 || index >= 3 * c->nb) return fail(NESR_ERR_ARG, "RDB index out of range");
@@ -1108,6 +1158,7 @@ int nesr_band_rdb(nesr_ctx* c, int index, void* stream) {
 }
 
 int nesr_band_rdb_phase(nesr_ctx* c, int index, int phase, int top, int bottom, int edge_rows, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_rdb_phase: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     if (index < 0 || index >= 3 * c->nb) return fail(NESR_ERR_ARG, "RDB index out of range");
@@ -1118,6 +1169,7 @@ int nesr_band_rdb_phase(nesr_ctx* c, int index, int phase, int top, int bottom, 
 }
 
 int nesr_band_pack_edges(nesr_ctx* c, int buffer, int top, int bottom, int nrows, void* top_dst, void* bottom_dst, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_pack_edges: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     const int h = c->band.h;
@@ -1129,6 +1181,7 @@ int nesr_band_pack_edges(nesr_ctx* c, int buffer, int top, int bottom, int nrows
 }
 
 int nesr_band_unpack_aprons(nesr_ctx* c, int buffer, int top, int bottom, int nrows, const void* top_src, const void* bottom_src, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_unpack_aprons: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     const int h = c->band.h;
@@ -1140,6 +1193,7 @@ int nesr_band_unpack_aprons(nesr_ctx* c, int buffer, int top, int bottom, int nr
 }
 
 int nesr_band_tail(nesr_ctx* c, void* y_dev, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_tail: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !y_dev) return fail(NESR_ERR_ARG, "null argument");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     HIP_TRY(hipSetDevice(c->device));
@@ -1147,11 +1201,16 @@ int nesr_band_tail(nesr_ctx* c, void* y_dev, void* stream) {
 }
 
 size_t nesr_band_row_bytes(const nesr_ctx* c) {
+    if (c && c->compact) {
+        fail(NESR_ERR_ARG, "nesr_band_row_bytes: RRDBNet contexts only (not an SRVGGNetCompact context)");
+        return 0;
+    }
     if (!c || !c->band_valid) return 0;
     return (size_t)c->band.w * c->nf * c->esize();
 }
 
 int nesr_band_rows(nesr_ctx* c, int buffer, int row0, int nrows, void* staging_dev, int write, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_band_rows: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !staging_dev) return fail(NESR_ERR_ARG, "null argument");
     if (!c->band_valid) return fail(NESR_ERR_STATE, "nesr_band_begin has not run (or a whole-frame forward reused the workspace)");
     const FwState& F = c->band;
@@ -1484,6 +1543,7 @@ int nesr_comm_unique_id(void* id128) {
 }
 
 int nesr_comm_init(nesr_ctx* c, int rank, int nranks, const void* id128) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_comm_init: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !id128 || nranks < 1 || rank < 0 || rank >= nranks) return fail(NESR_ERR_ARG, "nesr_comm_init: bad argument");
     int rc = rccl_load();
     if (rc) return rc;
@@ -1498,6 +1558,7 @@ int nesr_comm_init(nesr_ctx* c, int rank, int nranks, const void* id128) {
 }
 
 int nesr_comm_destroy(nesr_ctx* c) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_comm_destroy: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     if (c->comm) { RCCL_TRY(g_rccl.CommDestroy(c->comm)); c->comm = nullptr; }
     c->comm_rank = 0;
@@ -1506,6 +1567,7 @@ int nesr_comm_destroy(nesr_ctx* c) {
 }
 
 int nesr_forward_sharded_u8(nesr_ctx* c, const uint8_t* band_dev, int H, int W, int tile, int tile_pad, int through_fp16, uint8_t* out_dev, void* stream) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_forward_sharded_u8: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !band_dev) return fail(NESR_ERR_ARG, "null argument");
     const int world = c->comm ? c->comm_nranks : 1, rank = c->comm ? c->comm_rank : 0;
     const int u = c->ufac(), s = 4 / u;

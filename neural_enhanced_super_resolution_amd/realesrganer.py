@@ -23,6 +23,7 @@ import torch
 from torch.nn import functional as F
 
 from .rrdbnet import RRDBNet
+from .srvgg import SRVGGNetCompact
 
 
 # Integrity pins of the published checkpoints: the only ones the reference holds (nesr/utils/downloader.py:25-26, 33-34).
@@ -233,8 +234,8 @@ class RealESRGANer:
         for t in tiles:
             groups.setdefault((t[1] - t[0], t[3] - t[2]), []).append(t)
         order = sorted(groups.items(), key=lambda kv: -kv[0][0] * kv[0][1] * len(kv[1]))
-        hip = isinstance(self.model, RRDBNet) and img.device.type == "cuda"
-        if hip and img.shape[0] == 1 and self.model.compute_dtype == "bf16":
+        hip = self._hip_model() and img.device.type == "cuda"
+        if hip and isinstance(self.model, RRDBNet) and img.shape[0] == 1 and self.model.compute_dtype == "bf16":
             ragged = self.model.strip_kernel_active() if self.ragged_tiles is None else bool(self.ragged_tiles)
             if ragged and (len(order) > 1 or self.ragged_tiles is None):
                 return self._run_tiles_ragged(img, tiles, sink, single_stream=self.ragged_tiles is None)
@@ -382,10 +383,15 @@ class RealESRGANer:
         return self.post_process()
 
     # ------------------------------------------------------------------ enhance
+    def _hip_model(self):
+        """The network runs in libnesr_hip.so (RRDBNet or SRVGGNetCompact): the fused 8-bit, on-device and replica paths apply.
+        The RRDB-only paths (ragged batches, the strip kernel, preferred batch sizes, the declared-scale fix) test RRDBNet."""
+        return isinstance(self.model, (RRDBNet, SRVGGNetCompact))
+
     def _fused_u8_ok(self, img):
         """The fused u8 kernel path applies when the call reduces to one network evaluation of a
         plain 8-bit BGR frame: no tiling needed, no pre_pad / mod_pad, HIP-backed model."""
-        if not isinstance(self.model, RRDBNet) or self.device.type != "cuda":
+        if not self._hip_model() or self.device.type != "cuda":
             return False
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or self.pre_pad != 0:
             return False
@@ -401,7 +407,7 @@ class RealESRGANer:
         """8-bit BGR frames on the HIP backend (any tiling / padding): the uint8 frame is uploaded
         (4x fewer bytes than float), normalised, padded, tiled, clamped and quantised on the GPU with
         the same float32 operations enhance() performs in numpy, and only uint8 comes back."""
-        return (isinstance(self.model, RRDBNet) and self.device.type == "cuda" and img.dtype == np.uint8
+        return (self._hip_model() and self.device.type == "cuda" and img.dtype == np.uint8
                 and img.ndim == 3 and img.shape[2] == 3)
 
     def _u8_tiles_fused_ok(self, h, w):
@@ -459,7 +465,7 @@ class RealESRGANer:
 
     def _check_range(self, slot=None):
         """After a device-to-host copy: an out-of-range forward of the f16-pair fp32 form raises here."""
-        if isinstance(self.model, RRDBNet):
+        if self._hip_model():
             self.model.check_range(slot)
 
     @torch.no_grad()

@@ -1,0 +1,187 @@
+"""``SRVGGNetCompact`` drop-in: same constructor, state_dict key names and call signature as upstream
+``realesrgan.archs.srvgg_arch.SRVGGNetCompact``, the network of the realesr-general-x4v3 (with its -wdn twin for denoise
+strength) and realesr-animevideov3 checkpoints the reference fetches (standalone/download-x3-model.py:77-116)::
+
+    body = conv3x3(in, F), act, (conv3x3(F, F), act) x num_conv, conv3x3(F, out * s * s)
+    out  = pixel_shuffle(body(x), s) + nearest_upsample(x, s)
+
+As with :class:`RRDBNet`, the module owns ordinary torch Parameters under upstream's names (``body.{2i}.weight/bias`` for
+the convs, ``body.{2i+1}.weight`` [F] for each PReLU) and its ``forward`` is the HIP path in libnesr_hip.so
+(srvgg_compact.hip, one launch per layer).  There is no torch/CPU implementation of forward here: a non-CUDA input raises.
+"""
+from __future__ import annotations
+
+import ctypes
+from collections import OrderedDict
+
+import torch
+from torch import nn
+
+from . import _lib
+from .rrdbnet import RRDBNet, _ConvParams
+
+ACT_TYPES = {"prelu": _lib.ACT_PRELU, "relu": _lib.ACT_RELU, "leakyrelu": _lib.ACT_LEAKYRELU}
+
+
+def srvgg_state_dict_spec(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu"):
+    """Ordered {key: shape} of an SRVGGNetCompact checkpoint (101 tensors for x4v3, 53 for animevideov3)."""
+    if act_type not in ACT_TYPES:
+        raise ValueError(f"act_type {act_type!r}: expected one of {sorted(ACT_TYPES)}")
+    spec = OrderedDict()
+    i = 0
+
+    def conv(cin, cout):
+        nonlocal i
+        spec[f"body.{i}.weight"] = (cout, cin, 3, 3)
+        spec[f"body.{i}.bias"] = (cout,)
+        i += 1
+
+    def act():
+        nonlocal i
+        if act_type == "prelu":
+            spec[f"body.{i}.weight"] = (num_feat,)
+        i += 1
+
+    conv(num_in_ch, num_feat)
+    act()
+    for _ in range(num_conv):
+        conv(num_feat, num_feat)
+        act()
+    conv(num_feat, num_out_ch * upscale * upscale)
+    return spec
+
+
+class _PReLUParams(nn.Module):
+    """Parameter holder of one PReLU (``weight`` [F], torch's default 0.25).  Not callable."""
+
+    def __init__(self, num_feat):
+        super().__init__()
+        self.weight = nn.Parameter(torch.full((num_feat,), 0.25), requires_grad=False)
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("_PReLUParams holds weights only; SRVGGNetCompact.forward runs in libnesr_hip.so")
+
+
+class _NoParams(nn.Module):
+    """ReLU / LeakyReLU(0.1): no tensors, but they take a body index as upstream's modules do."""
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("SRVGGNetCompact.forward runs in libnesr_hip.so")
+
+
+class SRVGGNetCompact(nn.Module):
+    """Compact VGG-style super-resolution network (Real-ESRGAN's realesr-*-v3 models).
+
+    Args mirror upstream: num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type='prelu'.
+    Extra keyword ``compute_dtype``: "f32" (default; operands as f16 pairs, three f16 MFMAs per product, values beyond
+    +-65504 raise NesrRangeError) or "bf16" (what ``.half()`` / ``.to(torch.bfloat16)`` select, as for RRDBNet).
+    The HIP path supports num_feat 64, num_in_ch == num_out_ch == 3 and upscale 2 or 4.
+    """
+
+    def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu", compute_dtype="f32"):
+        super().__init__()
+        if act_type not in ACT_TYPES:
+            raise ValueError(f"act_type {act_type!r}: expected one of {sorted(ACT_TYPES)}")
+        self.num_in_ch = num_in_ch
+        self.num_out_ch = num_out_ch
+        self.num_feat = num_feat
+        self.num_conv = num_conv
+        self.upscale = upscale
+        self.act_type = act_type
+        self.compute_dtype = compute_dtype
+        self._dtype_code()   # a bad compute_dtype fails here, not at the first forward
+        mods = [_ConvParams(num_in_ch, num_feat), self._act()]
+        for _ in range(num_conv):
+            mods += [_ConvParams(num_feat, num_feat), self._act()]
+        mods.append(_ConvParams(num_feat, num_out_ch * upscale * upscale))
+        self.body = nn.ModuleList(mods)
+        self.calls = 0
+        self._ctx = None          # (ctypes handle, device index, dtype code): slot 0
+        self._dirty = True
+        self._extra = {}          # slot -> replica context for concurrent streams
+
+    def _act(self):
+        return _PReLUParams(self.num_feat) if self.act_type == "prelu" else _NoParams()
+
+    # the context / replica / range machinery is RRDBNet's (the C ABI is the same; only creation differs)
+    _release = RRDBNet._release
+    __del__ = RRDBNet.__del__
+    _upload = RRDBNet._upload
+    _context = RRDBNet._context
+    check_status = RRDBNet.check_status
+    check_range = RRDBNet.check_range
+    kernel_time = RRDBNet.kernel_time
+    forward_u8 = RRDBNet.forward_u8
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
+        self._dirty = True
+        return out
+
+    def half(self):
+        """Upstream's fp16 switch (RealESRGANer(half=True) calls model.half()): selects the bf16 kernels; the parameters
+        stay float32, so the bf16 weights are rounded once from the checkpoint's values."""
+        self.compute_dtype = "bf16"
+        self._dirty = True
+        return self
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._dirty = True
+        if self.body[0].weight.dtype in (torch.float16, torch.bfloat16):
+            self.compute_dtype = "bf16"
+        return out
+
+    def _dtype_code(self):
+        if self.compute_dtype in ("f32", "fp32", torch.float32, "f32-split", "split"):
+            return _lib.DTYPE_F32_SPLIT
+        if self.compute_dtype in ("bf16", torch.bfloat16, "half", torch.float16):
+            return _lib.DTYPE_BF16
+        raise ValueError(f"compute_dtype {self.compute_dtype!r}: expected 'f32' or 'bf16'")
+
+    def _create(self, index, code):
+        handle = ctypes.c_void_p()
+        _lib.check(_lib.load().nesr_create_compact(ctypes.byref(handle), index, self.num_in_ch, self.num_out_ch, self.num_feat,
+                                                   self.num_conv, self.upscale, ACT_TYPES[self.act_type], code), "nesr_create_compact")
+        return handle
+
+    # ------------------------------------------------------------------ forward
+    def out_scale(self):
+        return self.upscale
+
+    def _require_cuda(self, x):
+        if x.device.type != "cuda":
+            raise RuntimeError(
+                "SRVGGNetCompact.forward runs only on an AMD GPU through libnesr_hip.so; got a tensor on "
+                f"{x.device}. There is no CPU/PyTorch fallback for this path.")
+
+    @torch.no_grad()
+    def forward(self, x, slot: int = 0):
+        """x: [N, num_in_ch, H, W] float on a ROCm device -> [N, num_out_ch, H*s, W*s].
+        `slot` selects a context replica; work is enqueued on torch's current stream."""
+        self._require_cuda(x)
+        if x.dim() != 4:
+            raise ValueError(f"expected NCHW input, got shape {tuple(x.shape)}")
+        in_dtype = x.dtype
+        xf = x.to(torch.float32).contiguous()
+        n, c, h, w = xf.shape
+        s = self.upscale
+        self.calls += 1
+        with torch.cuda.device(xf.device):
+            ctx = self._context(xf.device, slot)
+            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xf.device)
+            stream = torch.cuda.current_stream(xf.device).cuda_stream
+            _lib.check(_lib.load().nesr_forward(ctx, ctypes.c_void_p(xf.data_ptr()), n, c, h, w,
+                                                ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(stream)), "nesr_forward")
+        return y if in_dtype == torch.float32 else y.to(in_dtype)
+
+    def forward_flops(self, n, h, w):
+        """Algorithmic FLOPs (2 x MACs) of one forward on [n, *, h, w]."""
+        f = self.num_feat
+        macs = 9 * (self.num_in_ch * f + self.num_conv * f * f + f * self.num_out_ch * self.upscale ** 2)
+        return 2.0 * macs * n * h * w
+
+    def set_kernel_timing(self, device, enable=True):
+        handles = [self._context(torch.device(device))] + [h[0] for h in self._extra.values()]
+        for ctx in handles:
+            _lib.check(_lib.load().nesr_set_kernel_timing(ctx, 1 if enable else 0), "nesr_set_kernel_timing")

@@ -58,3 +58,30 @@ def synthetic_frame(h, w, seed=0, channels=3):
     # stretch back to a wide range: box-filtered noise has std ~ 74/5
     y = (acc / 25.0 - 127.5) * 4.0 + 127.5
     return np.clip(np.rint(y), 0, 255).astype(np.uint8)
+
+
+def synthetic_compact_state_dict(seed=0, num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu",
+                                 slope_range=(0.1, 0.3), bias_std=0.02, tail_gain=0.25):
+    """Seeded weights for SRVGGNetCompact (upstream key names).  torch's default init shrinks the signal about 5x in
+    variance per PReLU layer, which would leave the tests blind to errors in a 32-layer body; here every conv is
+    kaiming-normal for its activation's negative slope (the body keeps its scale), PReLU slopes are drawn per channel in
+    `slope_range`, the weights are zero-mean (about half of every layer's pre-activations are negative, so the slope path
+    runs), and the tail is kaiming x `tail_gain` so the learned residual is clearly visible on top of the upsampled input."""
+    from .srvgg import srvgg_state_dict_spec
+    rng = np.random.default_rng(seed)
+    sd = OrderedDict()
+    spec = srvgg_state_dict_spec(num_in_ch, num_out_ch, num_feat, num_conv, upscale, act_type)
+    last = f"body.{2 * (num_conv + 1)}.weight"
+    slope = {"prelu": 0.5 * (slope_range[0] + slope_range[1]), "relu": 0.0, "leakyrelu": 0.1}[act_type]
+    for key, shape in spec.items():
+        if len(shape) == 4:
+            fan_in = shape[1] * 9
+            std = math.sqrt(2.0 / ((1.0 + slope * slope) * fan_in))
+            if key == last:
+                std = tail_gain * math.sqrt(1.0 / fan_in)
+            sd[key] = torch.from_numpy(rng.standard_normal(shape, dtype=np.float32) * np.float32(std))
+        elif key.endswith(".bias"):
+            sd[key] = torch.from_numpy(rng.standard_normal(shape, dtype=np.float32) * np.float32(bias_std))
+        else:   # PReLU slopes
+            sd[key] = torch.from_numpy(rng.uniform(slope_range[0], slope_range[1], size=shape).astype(np.float32))
+    return sd
