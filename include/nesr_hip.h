@@ -42,7 +42,15 @@ typedef struct nesr_ctx nesr_ctx;
  * condition is latched and returned (once) by the next nesr_check_range.  Callers of nesr_forward MUST call nesr_check_range
  * (or nesr_check_status) before trusting an output.
  * Whole-network max abs error vs an f64 evaluation 3e-6 on the bench weights (plain f32: 1e-6). */
-enum { NESR_DTYPE_F32 = 0, NESR_DTYPE_BF16 = 1, NESR_DTYPE_F32_WINOGRAD = 2, NESR_DTYPE_F32_SPLIT = 3 };
+/* NESR_DTYPE_F16: f16 storage and f16 MFMA operands (v_mfma_f32_{32x32x16,16x16x32}_f16), f32 accumulation and epilogue --
+ * upstream's half=True numerics; the same kernels, layouts and batching as NESR_DTYPE_BF16 (three more significand bits).
+ * Range contract, as for NESR_DTYPE_F32_SPLIT: f16 carries |x| <= 65504 only.  nesr_finalize_weights (and nesr_conv3x3)
+ * reject a weight beyond that (NESR_ERR_RANGE); an input or stored activation that is non-finite or beyond +-65504 raises the
+ * context's range word, the float output of THAT forward is NaN (an 8-bit output is invalid) and nesr_check_range /
+ * nesr_check_status return NESR_ERR_RANGE, scoped and latched per forward as above -- never a silently saturated image.
+ * The opt-in persistent trunk (NESR_TRUNK=persist) is f32 / bf16 only: an f16 context runs per-layer launches there;
+ * nesr_forward_sharded_u8 takes bf16 contexts only. */
+enum { NESR_DTYPE_F32 = 0, NESR_DTYPE_BF16 = 1, NESR_DTYPE_F32_WINOGRAD = 2, NESR_DTYPE_F32_SPLIT = 3, NESR_DTYPE_F16 = 4 };
 enum { NESR_ROUND_TRUNC = 0, NESR_ROUND_NEAREST = 1 };
 
 enum {
@@ -51,7 +59,7 @@ enum {
     NESR_ERR_HIP = -2,      /* a HIP runtime call failed */
     NESR_ERR_STATE = -3,    /* weights missing / not finalized */
     NESR_ERR_NOMEM = -4,
-    NESR_ERR_RANGE = -5     /* f16-pair fp32 form: a weight, input or activation was non-finite or beyond +-65504 */
+    NESR_ERR_RANGE = -5     /* f16-pair fp32 form or f16 form: a weight, input or activation was non-finite or beyond +-65504 */
 };
 
 /*
@@ -131,7 +139,7 @@ int nesr_forward_u8(nesr_ctx* ctx, const uint8_t* in_hwc_dev, int H, int W, uint
  * ignored) and its output in the top-left of slot i of y_dev ([N, num_out_ch, 4H/u, 4W/u]; the rest is not written).
  * Each image is evaluated as an image of its own -- its borders are the zero padding of every conv -- with the values
  * nesr_forward gives it alone (see nesr_set_size_independent).  hw: host array of N (height, width) pairs, multiples of
- * the unshuffle factor, 1 <= N <= 64.  compute dtype bf16 only (NESR_ERR_ARG otherwise: the f32 forms batch equal shapes).
+ * the unshuffle factor, 1 <= N <= 64.  compute dtype bf16 or f16 only (NESR_ERR_ARG otherwise: the f32 forms batch equal shapes).
  */
 int nesr_forward_ragged(nesr_ctx* ctx, const void* x_dev, int N, int C, int H, int W, const int* hw, void* y_dev, void* stream);
 
@@ -230,9 +238,9 @@ int nesr_kernel_time_ms(nesr_ctx* ctx, double* total_ms, int64_t* launches, doub
  * form's range flag, see nesr_check_range). */
 int nesr_check_status(nesr_ctx* ctx);
 
-/* Range / abort check of the forwards enqueued so far on `hip_stream` (NESR_DTYPE_F32_SPLIT, and contexts whose dense blocks
+/* Range / abort check of the forwards enqueued so far on `hip_stream` (NESR_DTYPE_F32_SPLIT, NESR_DTYPE_F16, and contexts whose dense blocks
  * ran as persistent launches; NESR_OK at once otherwise): waits for that stream only, returns NESR_ERR_RANGE if an input or activation did not fit the
- * (hi, lo) pair -- in the latest forward, or in an earlier one nobody asked about (the message says which; the latest output is
+ * (hi, lo) pair or the f16 value -- in the latest forward, or in an earlier one nobody asked about (the message says which; the latest output is
  * valid in the second case) -- and clears the flag.  Where the reference would hand back NaN/Inf pixels
  * (`model(img)` on diverged data, nesr/nesr.py:891) this path hands back NaN (float output) plus this error; the
  * Python wrappers call it after every device-to-host copy. */
@@ -271,7 +279,8 @@ int nesr_paste_tiles_u8(int device_id, const float* tiles_nchw_dev, int n, int H
  *                         librccl.so is loaded on the first of these calls, never before
  *   nesr_forward_sharded_u8 : band_dev = this rank's rows of the u8 HWC BGR frame (device memory); out_dev (rank 0 only) = the
  *                         [H s, W s, 3] u8 BGR result; enqueued on hip_stream.  Without nesr_comm_init it is the one-rank case.
- *                         through_fp16 as in nesr_cut_tiles_u8 / nesr_paste_tiles_u8.  bf16 contexts.
+ *                         through_fp16 as in nesr_cut_tiles_u8 / nesr_paste_tiles_u8.  bf16 contexts only (NESR_ERR_ARG for any
+ *                         other dtype, NESR_DTYPE_F16 included).
  *   nesr_shard_plan     : the plan by itself (host only, no device): tiles as 13 ints each (input window y0 y1 x0 x1, output window,
  *                         crop inside the tile's output, owner rank) and the row moves (src, dst, row lo, row hi); counts are always
  *                         returned, the arrays are filled when they are large enough.  `scale` = output / input size.
@@ -311,6 +320,8 @@ int nesr_clahe_u8(int device_id, const uint8_t* gray_dev, int H, int W, double c
  * upsample), i.e. torch.nn.Conv2d / F.leaky_relu / F.interpolate as composed in RRDBNet.forward.
  *   x_dev NCHW f32 [N,Cin,H,W];  w_host OIHW f32 [Cout,Cin,3,3];  b_host [Cout];
  *   y_dev NCHW f32 [N,Cout,H<<upsample,W<<upsample].  Synchronous.
+ *   dtype NESR_DTYPE_F16: x and w are rounded to f16 (nearest even), the output passes through f16 storage; NESR_ERR_RANGE for
+ *   a weight, input or output beyond +-65504.
  */
 int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W,
                  const float* w_host, const float* b_host, int Cout, int lrelu, int upsample,

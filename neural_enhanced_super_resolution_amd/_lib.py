@@ -13,7 +13,7 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 
-DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT = 0, 1, 2, 3
+DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT, DTYPE_F16 = 0, 1, 2, 3, 4
 ROUND_TRUNC, ROUND_NEAREST = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 
@@ -79,8 +79,8 @@ class NesrHipError(RuntimeError):
 
 
 class NesrRangeError(NesrHipError, FloatingPointError):
-    """NESR_ERR_RANGE: the f16-pair fp32 form met a weight, input or activation that is non-finite or beyond
-    +-65504 (the reference would carry it in float32; here it is an error, never a saturated image)."""
+    """NESR_ERR_RANGE: the f16-pair fp32 form or the f16 form met a weight, input or activation that is non-finite or
+    beyond +-65504 (the reference would carry it in float32; here it is an error, never a saturated image)."""
 
 
 def load():

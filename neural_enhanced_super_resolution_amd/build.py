@@ -30,7 +30,7 @@ def _stale(objs_src):
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = list(objs_src) + [os.path.join(CSRC, "nesr_kernels.h"), os.path.join(CSRC, "compact_api.h"),
+    deps = list(objs_src) + [os.path.join(CSRC, "nesr_kernels.h"), os.path.join(CSRC, "compact_api.h"), os.path.join(CSRC, "elem16.h"),
                              os.path.join(HERE, "..", "include", "nesr_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 

@@ -36,14 +36,11 @@
 
 #include <cstdlib>
 
+#include "elem16.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -66,11 +63,8 @@ struct Geo {
 
 typedef __attribute__((address_space(3))) char lds_char;
 
-__device__ inline f32x4 ld4_bf16(const uint16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                 __uint_as_float(u.y & 0xffff0000u)};
-}
+template <int K>
+__device__ inline f32x4 ld4(const uint16_t* p) { return E16<K>::unpack4(*reinterpret_cast<const uint2*>(p)); }
 // 16-byte feature-map store, write-through (sc1): see store_fm in conv3x3_wino_f32.hip
 // (in-process A/B on 6 tiles of 266x266: -1.6 % forward time).
 __device__ __forceinline__ void store16(uint16_t* p, uint4 v) {
@@ -79,11 +73,6 @@ __device__ __forceinline__ void store16(uint16_t* p, uint4 v) {
 #else
     *reinterpret_cast<uint4*>(p) = v;
 #endif
-}
-
-__device__ inline uint2 pack4_bf16(f32x4 v) {   // plain casts -> v_cvt_pk_bf16_f32 (RNE, NaN preserving)
-    const bf16x4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    return __builtin_bit_cast(uint2, b);
 }
 
 // LDS-DMA from inline asm: hipcc does not count it, so it inserts no s_waitcnt vmcnt(0) before the
@@ -104,7 +93,8 @@ __device__ __forceinline__ void glds16_asm(const char* gsrc, unsigned lds_dst) {
         : "memory");
 }
 
-template <int NT, int WAVES, int ISLOTS>
+// K: 1 bf16, 3 f16 (elem16.h)
+template <int K, int NT, int WAVES, int ISLOTS>
 __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs a) {
     typedef Geo<WAVES> G;
     constexpr int THREADS = G::THREADS, TH = G::TH;
@@ -263,9 +253,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
                     for (int t = 0; t < NT; ++t)
-                        acc[r][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[s & 1][t]),
-                                                                            __builtin_bit_cast(bf16x8, P[dx & 1][r + dy]),
-                                                                            acc[r][t], 0, 0, 0);
+                        acc[r][t] = E16<K>::mfma32(Wf[s & 1][t], P[dx & 1][r + dy], acc[r][t]);
                 // the next step's fragment reads ride between this step's MFMAs instead of in front of them
                 // (in-process A/B: -1.6 % / -1.9 % forward time on 24 / 6 tiles of 532x532)
                 {
@@ -298,6 +286,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int g = 0; g < 4; ++g) bs[t][g] = *reinterpret_cast<const f32x4*>(a.bias + t * 32 + 8 * g + 4 * hh);
+    // f16: stored activations are range-checked into the sticky word; conv_last writes NaN once it is set (elem16.h)
+    unsigned amax = 0;
+    const bool poison = E16<K>::RANGE && a.cout_real > 0 && a.status && __builtin_nontemporal_load(a.status) != 0u;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int Y = y0 + 4 * wave + r;
@@ -309,13 +300,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) r1[t][g] = ld4_bf16(res1 + at(a.res1_map, t * 32 + 8 * g + 4 * hh));
+                for (int g = 0; g < 4; ++g) r1[t][g] = ld4<K>(res1 + at(a.res1_map, t * 32 + 8 * g + 4 * hh));
         }
         if (res2) {
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) r2[t][g] = ld4_bf16(res2 + at(a.res2_map, t * 32 + 8 * g + 4 * hh));
+                for (int g = 0; g < 4; ++g) r2[t][g] = ld4<K>(res2 + at(a.res2_map, t * 32 + 8 * g + 4 * hh));
         }
         f32x4 v[NT][4];
 #pragma unroll
@@ -329,6 +320,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
                     if (res1) x = __fadd_rn(__fmul_rn(x, a.s1), r1[t][g][q]);
                     if (res2) x = __fadd_rn(__fmul_rn(x, a.s2), r2[t][g][q]);
                     v[t][g][q] = x;
+                    if constexpr (E16<K>::RANGE) amax = E16<K>::amax(amax, valid && (out || out2) ? x : 0.f);
                 }
         // 16-byte stores: for the run pair (g = 2j, 2j+1) the lower half-wave ends up with channels
         // 16j..16j+7 of its pixel (own run 2j + the upper lane's run 2j) and the upper half-wave with
@@ -339,7 +331,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
         for (int t = 0; t < NT; ++t)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const uint2 e = pack4_bf16(v[t][2 * j]), o = pack4_bf16(v[t][2 * j + 1]);
+                const uint2 e = E16<K>::pack4(v[t][2 * j]), o = E16<K>::pack4(v[t][2 * j + 1]);
                 const auto sx = __builtin_amdgcn_permlane32_swap(e.x, o.x, false, false);
                 const auto sy = __builtin_amdgcn_permlane32_swap(e.y, o.y, false, false);
                 wide[t][j] = uint4{sx[0], sy[0], sx[1], sy[1]};
@@ -364,7 +356,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (q >= a.cout_real) break;
-                    const float x = v[0][0][q];
+                    const float x = poison ? __builtin_nanf("") : v[0][0][q];
                     if (a.out_nchw) a.out_nchw[(((size_t)n * a.cout_real + q) * a.h + Y) * a.w_ + X] = x;
                     if (a.out_u8) {
                         float qv = fminf(fmaxf(x, 0.f), 1.f) * 255.0f;
@@ -376,25 +368,26 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
             }
         }
     }
+    if constexpr (E16<K>::RANGE) raise_range(a.status, amax);
+    else (void)amax;
 }
 
-template <int NT, int WAVES, int ISLOTS>
+template <int K, int NT, int WAVES, int ISLOTS>
 hipError_t launch_xl(const ConvArgs& a, hipStream_t s) {
     typedef Geo<WAVES> G;
     constexpr size_t shm = (size_t)ISLOTS * G::IN_BYTES + 2 * (size_t)(9 * 2 * 32 * NT * 16);
     static unsigned long long attr_done = 0;
     {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_bf16_xl_kernel<NT, WAVES, ISLOTS>), shm, attr_done);
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_bf16_xl_kernel<K, NT, WAVES, ISLOTS>), shm, attr_done);
         if (e != hipSuccess) return e;
     }
     const int tiles = ((a.w_ + TW - 1) / TW) * ((a.h + G::TH - 1) / G::TH) * a.n;
-    hipLaunchKernelGGL((conv3x3_bf16_xl_kernel<NT, WAVES, ISLOTS>), dim3(tiles), dim3(G::THREADS), shm, s, a);
+    hipLaunchKernelGGL((conv3x3_bf16_xl_kernel<K, NT, WAVES, ISLOTS>), dim3(tiles), dim3(G::THREADS), shm, s, a);
     return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s) {
+template <int K>
+hipError_t launch_xl_kind(const ConvArgs& a, hipStream_t s) {
     if (a.y_lo || a.y_hi) return hipErrorInvalidValue;   // row ranges: conv3x3_f16x2_kernel only
     if (a.cin % 16 || !a.zeros) return hipErrorInvalidValue;
     // the 16-byte accesses of the pair image / wide stores need pixel strides of whole 8-channel groups
@@ -404,13 +397,18 @@ hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s) {
         return e ? atoi(e) : 4;
     }();
     if (geo == 8) {
-        if (a.coutp == 64) return launch_xl<2, 8, 3>(a, s);
-        if (a.coutp == 32) return launch_xl<1, 8, 3>(a, s);
+        if (a.coutp == 64) return launch_xl<K, 2, 8, 3>(a, s);
+        if (a.coutp == 32) return launch_xl<K, 1, 8, 3>(a, s);
     } else {
-        if (a.coutp == 64) return launch_xl<2, 4, 2>(a, s);   // 2 x 19.6 + 2 x 18.4 = 76 KB -> 2 per CU
-        if (a.coutp == 32) return launch_xl<1, 4, 3>(a, s);   // 3 x 19.6 + 2 x 9.2 = 77 KB -> 2 per CU
+        if (a.coutp == 64) return launch_xl<K, 2, 4, 2>(a, s);   // 2 x 19.6 + 2 x 18.4 = 76 KB -> 2 per CU
+        if (a.coutp == 32) return launch_xl<K, 1, 4, 3>(a, s);   // 3 x 19.6 + 2 x 9.2 = 77 KB -> 2 per CU
     }
     return hipErrorInvalidValue;
 }
+
+}  // namespace
+
+hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s) { return launch_xl_kind<1>(a, s); }
+hipError_t launch_conv3x3_f16_xl(const ConvArgs& a, hipStream_t s) { return launch_xl_kind<3>(a, s); }
 
 }  // namespace nesr

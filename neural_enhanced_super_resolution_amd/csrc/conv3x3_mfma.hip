@@ -33,13 +33,13 @@
 
 #include <cstdlib>
 
+#include "elem16.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -47,39 +47,31 @@ constexpr int TH = 8, TW = 16;
 constexpr int PH = TH + 2, PW = TW + 2;
 constexpr int NPIX = PH * PW;  // 180
 
-template <bool BF>
-struct Elem;
+// K: activation layout code (PackArgs::bf16): 0 f32, 1 bf16, 3 f16 (the 16-bit forms: elem16.h)
+template <int K>
+struct Elem : E16<K> {
+    typedef uint16_t T;
+    static constexpr int KG = 16;
+    __device__ static f32x4 ld4(const T* p) { return E16<K>::unpack4(*reinterpret_cast<const uint2*>(p)); }   // 4 values (8 bytes) -> 4 f32
+    __device__ static void st4(T* p, f32x4 v) { *reinterpret_cast<uint2*>(p) = E16<K>::pack4(v); }
+};
 template <>
-struct Elem<false> {
+struct Elem<0> {
     typedef float T;
     static constexpr int KG = 8;  // channels per 32-byte chunk
+    static constexpr bool RANGE = false;
     __device__ static f32x4 ld4(const T* p) { return *reinterpret_cast<const f32x4*>(p); }
     // plain stores here: the write-through (sc1) form that helps the Winograd and bf16 XL kernels
     // measured +1.3 % (f32) / +4.5 % (bf16, 8-byte stores) slower in this kernel
     __device__ static void st4(T* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 };
-template <>
-struct Elem<true> {
-    typedef uint16_t T;
-    static constexpr int KG = 16;
-    __device__ static f32x4 ld4(const T* p) {   // 4 bf16 (8 bytes) -> 4 f32
-        const uint2 u = *reinterpret_cast<const uint2*>(p);
-        return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                     __uint_as_float(u.y & 0xffff0000u)};
-    }
-    __device__ static void st4(T* p, f32x4 v) {   // plain casts -> v_cvt_pk_bf16_f32 (RNE, NaN preserving)
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        const bf16x4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-        *reinterpret_cast<uint2*>(p) = __builtin_bit_cast(uint2, b);
-    }
-};
 
 // One output tile (8 x 16 pixels at (y0, x0) of image n) of one convolution.  Shared by the
 // per-layer kernel below and by the persistent trunk kernel (trunk_persist.hip).
-template <bool BF, int NT, int WV = 4>
+template <int K, int NT, int WV = 4>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const int y0, const int x0, char* smem) {
-    typedef typename Elem<BF>::T T;
-    constexpr int KG = Elem<BF>::KG;
+    typedef typename Elem<K>::T T;
+    constexpr int KG = Elem<K>::KG;
     // WV waves per workgroup, 2 output rows each: tile (2*WV) x 16 pixels
     constexpr int THREADS = 64 * WV;
     constexpr int NPIX = (2 * WV + 2) * PW;
@@ -175,11 +167,9 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
         for (int t = 0; t < NT; ++t) opb[sl][t] = st[b_base + tap * 2 * (32 * NT) + t * 32];
     };
     auto mfma_tap = [&](int sl) {
-        if constexpr (BF) {
+        if constexpr (K != 0) {
 #pragma unroll
-            for (int t = 0; t < NT; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, opb[sl][t]),
-                                                                 __builtin_bit_cast(bf16x8, opa[sl]), acc[t], 0, 0, 0);
+            for (int t = 0; t < NT; ++t) acc[t] = E16<K>::mfma32(opb[sl][t], opa[sl], acc[t]);
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
@@ -239,14 +229,14 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) r1[t][g] = Elem<BF>::ld4(rp + at(a.res1_map, t * 32 + 8 * g + 4 * hh));
+            for (int g = 0; g < 4; ++g) r1[t][g] = Elem<K>::ld4(rp + at(a.res1_map, t * 32 + 8 * g + 4 * hh));
     }
     if (a.res2) {
         const T* rp = static_cast<const T*>(a.res2);
 #pragma unroll
         for (int t = 0; t < NT; ++t)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) r2[t][g] = Elem<BF>::ld4(rp + at(a.res2_map, t * 32 + 8 * g + 4 * hh));
+            for (int g = 0; g < 4; ++g) r2[t][g] = Elem<K>::ld4(rp + at(a.res2_map, t * 32 + 8 * g + 4 * hh));
     }
     f32x4 v[NT][4];
 #pragma unroll
@@ -276,27 +266,42 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
 #pragma unroll
                 for (int q = 0; q < 4; ++q) v[t][g][q] = __fadd_rn(__fmul_rn(v[t][g][q], a.s2), r2[t][g][q]);
     }
+    if constexpr (Elem<K>::RANGE) {   // f16: a stored activation beyond +-65504 (or not finite) raises the range word
+        unsigned m = 0;
+        if (valid && (a.out || a.out2)) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) m = Elem<K>::amax(m, v[t][g][q]);
+        }
+        raise_range(a.status, m);
+    }
+    // conv_last, f16: a range failure anywhere upstream in this forward (the sticky word, raised by earlier launches on this
+    // stream) turns the image into NaN instead of a saturated picture
+    const bool poison = Elem<K>::RANGE && a.cout_real > 0 && a.status && __builtin_nontemporal_load(a.status) != 0u;
     if (valid) {
         if (a.out) {
             T* op = static_cast<T*>(a.out);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) Elem<BF>::st4(op + at(a.out_map, a.out_coff + t * 32 + 8 * g + 4 * hh), v[t][g]);
+                for (int g = 0; g < 4; ++g) Elem<K>::st4(op + at(a.out_map, a.out_coff + t * 32 + 8 * g + 4 * hh), v[t][g]);
         }
         if (a.out2) {
             T* op = static_cast<T*>(a.out2);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) Elem<BF>::st4(op + at(a.out2_map, t * 32 + 8 * g + 4 * hh), v[t][g]);
+                for (int g = 0; g < 4; ++g) Elem<K>::st4(op + at(a.out2_map, t * 32 + 8 * g + 4 * hh), v[t][g]);
         }
         if (a.cout_real > 0 && hh == 0) {
             // conv_last: channels 0..cout_real-1 (<= 4) live in v[0][0] of the lower half-wave
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (q >= a.cout_real) break;
-                const float x = v[0][0][q];
+                const float x = poison ? __builtin_nanf("") : v[0][0][q];
                 if (a.out_nchw) a.out_nchw[(((size_t)n * a.cout_real + q) * a.h + Y) * a.w_ + X] = x;
                 if (a.out_u8) {
                     float qv = fminf(fmaxf(x, 0.f), 1.f) * 255.0f;
@@ -309,7 +314,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
     }
 }
 
-template <bool BF, int NT, int WV>
+template <int K, int NT, int WV>
 __global__ __launch_bounds__(64 * WV) void conv3x3_mfma_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int TH_ = 2 * WV;
@@ -319,32 +324,32 @@ __global__ __launch_bounds__(64 * WV) void conv3x3_mfma_kernel(ConvArgs a) {
     const int n = bid / (tiles_x * tiles_y);
     bid -= n * tiles_x * tiles_y;
     const int ty = bid / tiles_x, tx = bid - ty * tiles_x;
-    conv_tile<BF, NT, WV>(a, n, ty * TH_, tx * TW, smem);
+    conv_tile<K, NT, WV>(a, n, ty * TH_, tx * TW, smem);
 }
 
-template <bool BF, int NT, int WV>
+template <int K, int NT, int WV>
 hipError_t launch_nt(const ConvArgs& a, hipStream_t s) {
     constexpr int TH_ = 2 * WV;
     constexpr size_t shm = 3 * (2 * (TH_ + 2) * PW + 9 * 2 * 32 * NT) * sizeof(f32x4);
     static unsigned long long attr_done = 0;
     {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_mfma_kernel<BF, NT, WV>), shm, attr_done);
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_mfma_kernel<K, NT, WV>), shm, attr_done);
         if (e != hipSuccess) return e;
     }
     const int tiles = ((a.w_ + TW - 1) / TW) * ((a.h + TH_ - 1) / TH_) * a.n;
     if (tiles <= 0) return hipSuccess;
-    hipLaunchKernelGGL((conv3x3_mfma_kernel<BF, NT, WV>), dim3(tiles), dim3(64 * WV), shm, s, a);
+    hipLaunchKernelGGL((conv3x3_mfma_kernel<K, NT, WV>), dim3(tiles), dim3(64 * WV), shm, s, a);
     return hipGetLastError();
 }
 
-template <bool BF>
+template <int K>
 hipError_t launch(const ConvArgs& a, hipStream_t s) {
-    if (a.cin % Elem<BF>::KG) return hipErrorInvalidValue;
+    if (a.cin % Elem<K>::KG) return hipErrorInvalidValue;
     // NESR_NT1_WAVES=2: Cout=32 layers in 4x16-pixel tiles, 2 waves per workgroup (4 independent
     // workgroups per CU on a 256x256 frame instead of 2) -- measured 4.5 % slower in-process, kept for A/B
     static const int nt1_waves = [] { const char* e = getenv("NESR_NT1_WAVES"); return e ? atoi(e) : 4; }();
-    if (a.coutp == 64) return launch_nt<BF, 2, 4>(a, s);
-    if (a.coutp == 32) return nt1_waves == 2 ? launch_nt<BF, 1, 2>(a, s) : launch_nt<BF, 1, 4>(a, s);
+    if (a.coutp == 64) return launch_nt<K, 2, 4>(a, s);
+    if (a.coutp == 32) return nt1_waves == 2 ? launch_nt<K, 1, 2>(a, s) : launch_nt<K, 1, 4>(a, s);
     return hipErrorInvalidValue;
 }
 
@@ -360,7 +365,7 @@ hipError_t launch(const ConvArgs& a, hipStream_t s) {
 constexpr size_t TRUNK_RING_BYTES = 3 * (2 * NPIX + 9 * 2 * 32 * 2) * sizeof(f32x4);
 constexpr size_t TRUNK_SHM = TRUNK_RING_BYTES + 16;
 
-template <bool BF>
+template <int K>
 __global__ __launch_bounds__(256, 2) void trunk_persist_kernel(TrunkArgs t) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     volatile unsigned* s_abort = reinterpret_cast<volatile unsigned*>(smem + TRUNK_RING_BYTES);
@@ -445,9 +450,9 @@ __global__ __launch_bounds__(256, 2) void trunk_persist_kernel(TrunkArgs t) {
             }
 
             if (ly.coutp == 64)
-                conv_tile<BF, 2>(a, n, ty * TH, tx * TW, smem);
+                conv_tile<K, 2>(a, n, ty * TH, tx * TW, smem);
             else
-                conv_tile<BF, 1>(a, n, ty * TH, tx * TW, smem);
+                conv_tile<K, 1>(a, n, ty * TH, tx * TW, smem);
 
             // ---- publish: this tile has completed layer L
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -461,12 +466,12 @@ __global__ __launch_bounds__(256, 2) void trunk_persist_kernel(TrunkArgs t) {
     }
 }
 
-template <bool BF>
+template <int K>
 hipError_t launch_trunk(const TrunkArgs& t, hipStream_t s) {
     static int max_blocks = -1;   // co-resident workgroups (all devices of a node are the same part)
     static unsigned long long attr_done = 0;
     {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&trunk_persist_kernel<BF>), TRUNK_SHM, attr_done);
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&trunk_persist_kernel<K>), TRUNK_SHM, attr_done);
         if (e != hipSuccess) return e;
     }
     if (max_blocks < 0) {
@@ -475,7 +480,7 @@ hipError_t launch_trunk(const TrunkArgs& t, hipStream_t s) {
         hipDeviceProp_t prop;
         if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
         if ((e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trunk_persist_kernel<BF>, 256, TRUNK_SHM);
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, trunk_persist_kernel<K>, 256, TRUNK_SHM);
         if (e != hipSuccess) return e;
         if (per_cu > 2) per_cu = 2;   // LDS admits 2; never trust the API for more (MI355X_MICROARCH.md, residency)
         if (per_cu < 1) return hipErrorLaunchOutOfResources;
@@ -487,7 +492,7 @@ hipError_t launch_trunk(const TrunkArgs& t, hipStream_t s) {
     TrunkArgs targ = t;
     void* params[] = {&targ};
     // cooperative launch: the runtime verifies that the whole grid is co-resident
-    return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&trunk_persist_kernel<BF>), dim3(grid), dim3(256), params,
+    return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&trunk_persist_kernel<K>), dim3(grid), dim3(256), params,
                                       TRUNK_SHM, s);
 }
 
@@ -516,8 +521,9 @@ void pack_weights_f32(const float* oihw, int cout, int cin, int cin_p, int coutp
             }
 }
 
-// OIHW -> [chunk = ci/16][tap][half = (ci%16)/8][n][j = ci%8] bf16 (RNE); zero padded.
-void pack_weights_bf16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst) {
+// OIHW -> [chunk = ci/16][tap][half = (ci%16)/8][n][j = ci%8] of 16-bit values (RNE); zero padded.
+template <class F>
+void pack_weights_16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst, F cvt) {
     const size_t total = packed_weight_elems_bf16(cin_p, coutp);
     for (size_t i = 0; i < total; ++i) dst[i] = 0;
     for (int o = 0; o < cout; ++o)
@@ -525,16 +531,24 @@ void pack_weights_bf16(const float* oihw, int cout, int cin, int cin_p, int cout
             for (int tap = 0; tap < 9; ++tap) {
                 const int c = ci / 16, half = (ci % 16) / 8, j = ci % 8;
                 const size_t idx = ((((size_t)c * 9 + tap) * 2 + half) * coutp + o) * 8 + j;
-                dst[idx] = host_f2bf(oihw[((size_t)o * cin + ci) * 9 + tap]);
+                dst[idx] = cvt(oihw[((size_t)o * cin + ci) * 9 + tap]);
             }
+}
+void pack_weights_bf16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst) {
+    pack_weights_16(oihw, cout, cin, cin_p, coutp, dst, host_f2bf);
+}
+// f16: |w| <= 65504 and finite (nesr_finalize_weights / nesr_conv3x3 refuse anything else); the cast rounds to nearest even,
+// as torch's .half() does
+void pack_weights_f16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst) {
+    pack_weights_16(oihw, cout, cin, cin_p, coutp, dst, [](float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); });
 }
 
 hipError_t launch_conv3x3_f32(const ConvArgs& a, hipStream_t s) {
     if (a.y_lo || a.y_hi) return hipErrorInvalidValue;   // row ranges: conv3x3_f16x2_kernel only
-    return launch<false>(a, s);
+    return launch<0>(a, s);
 }
 hipError_t launch_trunk_persist(const TrunkArgs& t, bool bf16, hipStream_t s) {
-    return bf16 ? launch_trunk<true>(t, s) : launch_trunk<false>(t, s);
+    return bf16 ? launch_trunk<1>(t, s) : launch_trunk<0>(t, s);
 }
 // bf16: frames of more than 256x256 trunk pixels take the large-tile LDS-DMA kernel (a single
 // 256x256 frame is only 64 of its tiles, too few for 256 CUs); the choice
@@ -552,7 +566,22 @@ hipError_t launch_conv3x3_bf16(const ConvArgs& a, hipStream_t s) {
         if (mode == 3 || (mode == 0 && large) || a.rag_n || a.size_independent) return launch_conv3x3_bf16_xl(a, s);
     }
     if (a.rag_n) return hipErrorInvalidValue;   // only the large-tile kernel knows about ragged batches
-    return launch<true>(a, s);
+    return launch<1>(a, s);
+}
+// f16: the same kernels and the same choice as bf16 (NESR_BF16_KERNEL applies too)
+hipError_t launch_conv3x3_f16(const ConvArgs& a, hipStream_t s) {
+    if (a.y_lo || a.y_hi) return hipErrorInvalidValue;
+    static const int mode = [] {
+        const char* e = getenv("NESR_BF16_KERNEL");
+        if (!e) return 0;
+        return e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : (e[0] == 'x' ? 3 : 0));
+    }();
+    const bool large = (long)a.h * a.w_ > 256L * 256L;
+    if (a.zeros) {
+        if (mode == 3 || (mode == 0 && large) || a.rag_n || a.size_independent) return launch_conv3x3_f16_xl(a, s);
+    }
+    if (a.rag_n) return hipErrorInvalidValue;
+    return launch<3>(a, s);
 }
 
 }  // namespace nesr

@@ -127,9 +127,15 @@ struct nesr_ctx {
     int64_t timed_launches = 0;
     double timed_flops = 0.0;
 
-    size_t esize() const { return dtype == NESR_DTYPE_BF16 ? 2 : 4; }   // bytes per stored activation value
-    // activation layout / kernel family: 0 f32 NHWC, 1 bf16 blocked, 2 f16 hi|lo blocked (PackArgs::bf16)
-    int kind() const { return dtype == NESR_DTYPE_BF16 ? 1 : (dtype == NESR_DTYPE_F32_SPLIT ? 2 : 0); }
+    size_t esize() const { return (dtype == NESR_DTYPE_BF16 || dtype == NESR_DTYPE_F16) ? 2 : 4; }   // bytes per stored activation value
+    // activation layout / kernel family: 0 f32 NHWC, 1 bf16 blocked, 2 f16 hi|lo blocked, 3 f16 blocked (PackArgs::bf16)
+    int kind() const {
+        return dtype == NESR_DTYPE_BF16 ? 1 : (dtype == NESR_DTYPE_F32_SPLIT ? 2 : (dtype == NESR_DTYPE_F16 ? 3 : 0));
+    }
+    // the forms with a range word (d_status[0]): a stored value beyond +-65504 turns the output into NaN (NESR_ERR_RANGE)
+    bool ranged() const { return dtype == NESR_DTYPE_F32_SPLIT || dtype == NESR_DTYPE_F16; }
+    // the 16-bit forms (bf16, f16): the same kernels, layouts, strip plans, leases and ragged batches
+    bool half16() const { return dtype == NESR_DTYPE_BF16 || dtype == NESR_DTYPE_F16; }
     int ct() const { return nf + 4 * gc; }  // channels of a dense-block buffer
     int ufac() const { return unshuffle > 1 ? unshuffle : 1; }
 };
@@ -182,6 +188,7 @@ int ensure_ws(nesr_ctx* c, size_t bytes) {
 
 hipError_t launch_conv(const nesr_ctx* c, const ConvArgs& a, hipStream_t s, const Layer* L = nullptr) {
     if (c->dtype == NESR_DTYPE_BF16) return launch_conv3x3_bf16(a, s);
+    if (c->dtype == NESR_DTYPE_F16) return launch_conv3x3_f16(a, s);
     if (c->dtype == NESR_DTYPE_F32_SPLIT) return launch_conv3x3_f16x2(a, s);
     if (c->winograd && L && L->d_ww && (!(a.out_nchw || a.out_u8) || (a.cout_real >= 1 && a.cout_real <= 4 && a.coutp == 32))) {
         ConvArgs w = a;
@@ -214,16 +221,16 @@ ConvArgs base_args(const nesr_ctx* c, const Layer& L, int N, int h, int w) {
         std::memcpy(a.rag_h, c->rag_h, sizeof(a.rag_h));
         std::memcpy(a.rag_w, c->rag_w, sizeof(a.rag_w));
     }
-    a.status = c->dtype == NESR_DTYPE_F32_SPLIT ? c->d_status : nullptr;
+    a.status = c->ranged() ? c->d_status : nullptr;
     return a;
 }
 
-// kind 0 (f32): NHWC (pix = channels of the buffer, chunk = 8).  kind 1 (bf16): channel-blocked
+// kind 0 (f32): NHWC (pix = channels of the buffer, chunk = 8).  kind 1 (bf16), kind 3 (f16): channel-blocked
 // [C/16][pixels][16].  kind 2 (f16 pairs): [C/16][pixels][16 hi | 16 lo], in 2-byte units.
 Map make_map(int kind, int channels, size_t pixels) {
     Map m;
     if (kind == 2) { m.pix = 32; m.chunk = (long long)pixels * 32; }
-    else if (kind == 1) { m.pix = 16; m.chunk = (long long)pixels * 16; }
+    else if (kind == 1 || kind == 3) { m.pix = 16; m.chunk = (long long)pixels * 16; }
     else { m.pix = channels; m.chunk = 8; }
     return m;
 }
@@ -319,7 +326,7 @@ int strip_plan_for(nesr_ctx* c, int N, int h, int w, const nesr_ctx::StripPlan**
 
 // does this evaluation's trunk run as persistent (lease-holding) launches?
 bool strip_wanted(const nesr_ctx* c) {
-    return c->dtype == NESR_DTYPE_BF16 && c->d_strip && c->strip_mode != 0 && c->nf == 64 && c->gc == 32;
+    return c->half16() && c->d_strip && c->strip_mode != 0 && c->nf == 64 && c->gc == 32;
 }
 
 // ---- the forward graph in stages (whole-frame forward = all of them in order; the banded multi-GPU mode
@@ -362,7 +369,7 @@ int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x
     p.dst_map = F.m_in;
     p.cp = c->layers[0].cin_p;
     p.bf16 = c->kind();
-    p.status = c->dtype == NESR_DTYPE_F32_SPLIT ? c->d_status : nullptr;
+    p.status = c->ranged() ? c->d_status : nullptr;
     if (p.status) HIP_TRY(launch_status_latch(c->d_status, s));      // the range word is per forward (nesr_check_range reports a latched one once)
     HIP_TRY(launch_pack_input(p, s));
     ConvArgs a = base_args(c, c->layers[0], F.N, F.h, F.w);
@@ -386,7 +393,7 @@ int fw_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s, int phase
     const bool ranged = phase >= 0 && c->dtype == NESR_DTYPE_F32_SPLIT && F.N == 1 && F.h >= top + bottom + 2 * edge;
     if (phase == 1 && !ranged) return NESR_OK;
     if (phase >= 0 && !ranged) phase = -1;
-    // bf16: the dense block with its working set resident in LDS (rdb_bf16_strip_kernel), whenever the context is
+    // bf16 / f16: the dense block with its working set resident in LDS (rdb_bf16_strip_kernel), whenever the context is
     // size-independent (a tiling wrapper: one arithmetic for every tile, however it is batched) or the batch fills the device
     if (phase < 0 && strip_wanted(c)) {
         const nesr_ctx::StripPlan* P = nullptr;
@@ -411,6 +418,8 @@ int fw_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s, int phase
             L.timeout_ticks = c->strip_timeout_ticks;
             L.debug_drop = c->debug_drop;
             c->debug_drop = 0;
+            L.f16 = c->dtype == NESR_DTYPE_F16 ? 1 : 0;
+            L.status = L.f16 ? c->d_status : nullptr;
             const hipError_t le = launch_rdb_bf16_strip(L, s);
             if (le == hipErrorLaunchOutOfResources) {
                 c->strip_mode = 0;      // the device does not admit the kernel's workgroups (LDS / registers): per-layer launches
@@ -575,7 +584,8 @@ int run_forward(nesr_ctx* c, const float* x_f32, const uint8_t* x_u8, int flip, 
         }
         HIP_TRY(hipEventRecord(ev0, s));
     }
-    const bool persist = c->trunk_mode == 2;   // opt-in (NESR_TRUNK=persist): measured slower at 2 tiles/CU, see DESIGN.md
+    // opt-in (NESR_TRUNK=persist): measured slower at 2 tiles/CU, see DESIGN.md.  f32 and bf16 only: f16 runs per-layer launches
+    const bool persist = c->trunk_mode == 2 && c->dtype != NESR_DTYPE_F16;
     if (persist && c->nb > 0) {
         // one cooperative launch for all 15*nb dense-block convs (tile-level dataflow sync)
         unsigned* sync = reinterpret_cast<unsigned*>(c->ws + F.L.sync);
@@ -631,8 +641,9 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     if (num_feat != 32 && num_feat != 64) return fail(NESR_ERR_ARG, "num_feat must be 32 or 64 (reference uses 64)");
     if (num_grow_ch != 32) return fail(NESR_ERR_ARG, "num_grow_ch must be 32 (reference uses 32)");
     if (num_block < 0 || num_out_ch <= 0 || num_out_ch > 32) return fail(NESR_ERR_ARG, "bad num_block / num_out_ch");
-    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F32_WINOGRAD && dtype != NESR_DTYPE_F32_SPLIT)
-        return fail(NESR_ERR_ARG, "dtype must be 0 (f32 direct), 1 (bf16), 2 (f32 Winograd) or 3 (f32 as f16 pairs)");
+    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F32_WINOGRAD && dtype != NESR_DTYPE_F32_SPLIT &&
+        dtype != NESR_DTYPE_F16)
+        return fail(NESR_ERR_ARG, "dtype must be 0 (f32 direct), 1 (bf16), 2 (f32 Winograd), 3 (f32 as f16 pairs) or 4 (f16)");
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return fail(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
@@ -658,14 +669,14 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     c->nout = num_out_ch;
     c->winograd = dtype == NESR_DTYPE_F32_WINOGRAD;
     if (const char* e = getenv("NESR_F32_ALGO")) {   // override for A/B timing: direct | winograd
-        if (dtype != NESR_DTYPE_BF16) {
+        if (dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F16) {
             c->winograd = e[0] == 'w';
             dtype = e[0] == 's' ? NESR_DTYPE_F32_SPLIT : (e[0] == 'w' ? NESR_DTYPE_F32_WINOGRAD : NESR_DTYPE_F32);
         }
     }
     if (dtype == NESR_DTYPE_F32_WINOGRAD) dtype = NESR_DTYPE_F32;
     c->dtype = dtype;
-    c->kgroup = (dtype == NESR_DTYPE_BF16 || dtype == NESR_DTYPE_F32_SPLIT) ? 16 : 8;
+    c->kgroup = (dtype == NESR_DTYPE_BF16 || dtype == NESR_DTYPE_F32_SPLIT || dtype == NESR_DTYPE_F16) ? 16 : 8;
     if (const char* e = getenv("NESR_TRUNK")) c->trunk_mode = e[0] == 'l' ? 1 : (e[0] == 'p' ? 2 : 0);
     if (const char* e = getenv("NESR_RDB_FUSE")) c->rdb_mode = atoi(e);
     if (const char* e = getenv("NESR_STRIP")) c->strip_mode = atoi(e);
@@ -756,22 +767,25 @@ int nesr_finalize_weights(nesr_ctx* c) {
         if (!L.has_b && nmiss++ < 4) missing += " " + L.name + ".bias";
     }
     if (nmiss) return fail(NESR_ERR_STATE, "Missing key(s) in state_dict (" + std::to_string(nmiss) + "):" + missing);
-    // non-finite parameters are refused for every dtype; the f16-pair form also needs |w| <= 65504 (the hi half
-    // is an f16) -- never a silently clamped weight
+    // non-finite parameters are refused for every dtype; the f16-pair form (its hi half is an f16) and the f16 form also
+    // need |w| <= 65504 -- never a silently clamped weight
     for (const Layer& L : c->layers) {
-        const float lim = c->dtype == NESR_DTYPE_F32_SPLIT ? 65504.f : INFINITY;
+        const float lim = c->ranged() ? 65504.f : INFINITY;
         for (int t = 0; t < 2; ++t) {
             const std::vector<float>& v = t ? L.b : L.w;
             const float blim = t ? INFINITY : lim;   // biases are added in f32
             for (size_t i = 0; i < v.size(); ++i)
                 if (!(std::fabs(v[i]) <= blim) || !std::isfinite(v[i]))
                     return fail(NESR_ERR_RANGE, L.name + (t ? ".bias" : ".weight") + "[" + std::to_string(i) + "] = " + std::to_string(v[i]) +
-                                                    (std::isfinite(v[i]) ? ": |w| > 65504 does not fit the f16-pair form of compute_dtype f32 "
-                                                                           "(use f32-winograd or f32-direct)" : ": non-finite parameter"));
+                                                    (!std::isfinite(v[i]) ? ": non-finite parameter"
+                                                     : c->dtype == NESR_DTYPE_F16 ? ": |w| > 65504 does not fit compute_dtype f16 (use bf16 or f32)"
+                                                                                  : ": |w| > 65504 does not fit the f16-pair form of compute_dtype f32 "
+                                                                                    "(use f32-winograd or f32-direct)"));
         }
     }
     HIP_TRY(hipSetDevice(c->device));
     const bool bf = c->dtype == NESR_DTYPE_BF16;
+    const bool hf = c->dtype == NESR_DTYPE_F16;
     const bool sp = c->dtype == NESR_DTYPE_F32_SPLIT;
     size_t total = 256;   // leading zero page
     std::vector<size_t> woff(c->layers.size()), boff(c->layers.size()), wwoff(c->layers.size(), 0);
@@ -779,9 +793,9 @@ int nesr_finalize_weights(nesr_ctx* c) {
     for (size_t i = 0; i < c->layers.size(); ++i) {
         const Layer& L = c->layers[i];
         const size_t we = sp ? packed_weight_elems_f16x2(L.cin_p, L.cout_p)
-                             : (bf ? packed_weight_elems_bf16(L.cin_p, L.cout_p) : packed_weight_elems_f32(L.cin_p, L.cout_p));
+                             : ((bf || hf) ? packed_weight_elems_bf16(L.cin_p, L.cout_p) : packed_weight_elems_f32(L.cin_p, L.cout_p));
         woff[i] = total;
-        total = align_up(total + we * ((bf || sp) ? 2 : 4), 256);
+        total = align_up(total + we * ((bf || hf || sp) ? 2 : 4), 256);
         boff[i] = total;
         total = align_up(total + (size_t)L.cout_p * 4, 256);
         (void)last;
@@ -797,6 +811,8 @@ int nesr_finalize_weights(nesr_ctx* c) {
             pack_weights_f16x2(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<uint16_t*>(host.data() + woff[i]));
         else if (bf)
             pack_weights_bf16(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<uint16_t*>(host.data() + woff[i]));
+        else if (hf)
+            pack_weights_f16(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<uint16_t*>(host.data() + woff[i]));
         else
             pack_weights_f32(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<float*>(host.data() + woff[i]));
         std::memcpy(host.data() + boff[i], L.b.data(), (size_t)L.cout * 4);
@@ -816,9 +832,9 @@ int nesr_finalize_weights(nesr_ctx* c) {
         c->layers[i].d_b = reinterpret_cast<float*>(c->d_weights + boff[i]);
         c->layers[i].d_ww = wwoff[i] ? c->d_weights + wwoff[i] : nullptr;
     }
-    // bf16: every dense block's weights once more as the LDS-resident kernel's stream (rdb_bf16_strip.hip), + its 192 biases
+    // bf16 / f16: every dense block's weights once more as the LDS-resident kernel's stream (rdb_bf16_strip.hip), + its 192 biases
     if (c->d_strip) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->d_strip)); c->d_strip = nullptr; }
-    if (bf && c->nf == 64 && c->gc == 32 && c->nb > 0) {
+    if ((bf || hf) && c->nf == 64 && c->gc == 32 && c->nb > 0) {
         c->strip_stride = align_up(strip_weight_bytes() + 192 * 4, 256);
         std::vector<char> hs((size_t)c->nb * 3 * c->strip_stride, 0);
         for (int b = 0; b < c->nb; ++b)
@@ -831,7 +847,7 @@ int nesr_finalize_weights(nesr_ctx* c) {
                     w5[k] = Ly.w.data();
                     std::memcpy(bias + 32 * k, Ly.b.data(), (size_t)Ly.cout * 4);
                 }
-                pack_strip_weights(w5, reinterpret_cast<uint16_t*>(blk));
+                pack_strip_weights(w5, reinterpret_cast<uint16_t*>(blk), hf);
             }
         HIP_TRY(hipMalloc((void**)&c->d_strip, hs.size()));
         HIP_TRY(hipMemcpy(c->d_strip, hs.data(), hs.size(), hipMemcpyHostToDevice));
@@ -887,7 +903,7 @@ int nesr_forward(nesr_ctx* c, const void* x_dev, int N, int C, int H, int W, voi
 int nesr_forward_ragged(nesr_ctx* c, const void* x_dev, int N, int C, int H, int W, const int* hw, void* y_dev, void* stream) {
     if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_forward_ragged: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c || !x_dev || !y_dev || !hw) return fail(NESR_ERR_ARG, "null argument");
-    if (c->dtype != NESR_DTYPE_BF16) return fail(NESR_ERR_ARG, "nesr_forward_ragged: compute dtype bf16 only (the other forms batch equal-sized images)");
+    if (!c->half16()) return fail(NESR_ERR_ARG, "nesr_forward_ragged: compute dtype bf16 or f16 only (the other forms batch equal-sized images)");
     if (N < 1 || N > nesr::RAG_MAX) return fail(NESR_ERR_ARG, "nesr_forward_ragged: 1.." + std::to_string(nesr::RAG_MAX) + " images per call");
     const int u = c->ufac();
     if (H % u || W % u || H / u > 16383 || W / u > 16383) return fail(NESR_ERR_ARG, "nesr_forward_ragged: slot size");
@@ -962,8 +978,8 @@ int nesr_preferred_batch(const nesr_ctx* c, int H, int W, int max_batch) {
     if (!c || H <= 0 || W <= 0 || max_batch <= 1) return 1;
     const int u = c->ufac();
     const int h = (H + u - 1) / u, w = (W + u - 1) / u;
-    // workgroups per frame of the trunk convs (the kernel choice mirrors launch_conv3x3_bf16)
-    const bool xl = c->dtype == NESR_DTYPE_BF16 && (long)h * w > 256L * 256L;
+    // workgroups per frame of the trunk convs (the kernel choice mirrors launch_conv3x3_bf16 / _f16)
+    const bool xl = c->half16() && (long)h * w > 256L * 256L;
     static const int geo = [] { const char* e = getenv("NESR_XL_GEOMETRY"); return e ? atoi(e) : 4; }();
     const int xl_th = geo == 8 ? 32 : 16;
     const bool sp = c->dtype == NESR_DTYPE_F32_SPLIT;   // 8x32-px tiles, two workgroups per CU
@@ -1003,7 +1019,7 @@ int nesr_set_fused(nesr_ctx* c, int on) {
 int nesr_fused_state(const nesr_ctx* c) {
     if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_fused_state: RRDBNet contexts only (not an SRVGGNetCompact context)");
     if (!c) return 0;
-    const int on = c->dtype == NESR_DTYPE_BF16 ? c->strip_mode != 0 : (c->dtype == NESR_DTYPE_F32_SPLIT && c->rdb_mode != 0);
+    const int on = c->half16() ? c->strip_mode != 0 : (c->dtype == NESR_DTYPE_F32_SPLIT && c->rdb_mode != 0);
     return (on ? 1 : 0) | (c->fused_aborts << 1);
 }
 
@@ -1058,7 +1074,7 @@ int nesr_check_status(nesr_ctx* c) {
 int nesr_check_range(nesr_ctx* c, void* stream) {
     if (c && c->compact) return compact_check_range(c->compact, static_cast<hipStream_t>(stream));
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
-    if (c->dtype != NESR_DTYPE_F32_SPLIT && !c->strip_used) return NESR_OK;   // the other forms compute in formats with f32's range
+    if (!c->ranged() && !c->strip_used) return NESR_OK;   // the other forms compute in formats with f32's range
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemcpyAsync(c->h_status, c->d_status, 16, hipMemcpyDeviceToHost, s));
@@ -1076,7 +1092,9 @@ int nesr_check_range(nesr_ctx* c, void* stream) {
                                   ": its workgroups were not all resident -- another process's persistent kernel shares the device?); the "
                                   "output of that forward is invalid; this context uses per-layer launches from now on (re-run the frame)");
     }
-    if (c->dtype != NESR_DTYPE_F32_SPLIT) return NESR_OK;
+    if (!c->ranged()) return NESR_OK;
+    const char* form = c->dtype == NESR_DTYPE_F16 ? "the f16 form" : "the f16-pair fp32 path";
+    const char* instead = c->dtype == NESR_DTYPE_F16 ? "use compute_dtype bf16 or f32 for such data" : "use compute_dtype f32-winograd or f32-direct for such data";
     if (c->h_status[1]) {
         const unsigned code = c->h_status[1];      // 1 | chunk whose producer was waited for << 8 | tile << 16
         HIP_TRY(hipMemsetAsync(c->d_status, 0, 8, s));
@@ -1093,9 +1111,9 @@ int nesr_check_range(nesr_ctx* c, void* stream) {
         HIP_TRY(hipMemsetAsync(c->d_status + 3, 0, 4, s));
         HIP_TRY(hipStreamSynchronize(s));
         c->h_status[3] = 0;
-        return fail(NESR_ERR_RANGE, "an EARLIER forward on this context (its result was never checked with nesr_check_range) met an input or "
-                                    "activation of the f16-pair fp32 path that was non-finite or exceeded 65504 in magnitude: that forward's "
-                                    "output was NaN / invalid; the latest forward's output is valid");
+        return fail(NESR_ERR_RANGE, std::string("an EARLIER forward on this context (its result was never checked with nesr_check_range) met an input or "
+                                                "activation of ") + form + " that was non-finite or exceeded 65504 in magnitude: that forward's "
+                                                "output was NaN / invalid; the latest forward's output is valid");
     }
     if (*c->h_status) {
         HIP_TRY(hipMemsetAsync(c->d_status, 0, 4, s));   // reported once; the next forward starts clean
@@ -1103,9 +1121,8 @@ int nesr_check_range(nesr_ctx* c, void* stream) {
         HIP_TRY(hipStreamSynchronize(s));
         *c->h_status = 0;
         c->h_status[3] = 0;
-        return fail(NESR_ERR_RANGE, "an input or activation of the f16-pair fp32 path was non-finite or exceeded 65504 in magnitude: "
-                                    "the float output of that forward is NaN, an 8-bit output is invalid (use compute_dtype "
-                                    "f32-winograd or f32-direct for such data)");
+        return fail(NESR_ERR_RANGE, std::string("an input or activation of ") + form + " was non-finite or exceeded 65504 in magnitude: "
+                                    "the float output of that forward is NaN, an 8-bit output is invalid (" + instead + ")");
     }
     return NESR_OK;
 }
@@ -1314,25 +1331,32 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
                  const float* b_host, int Cout, int lrelu, int upsample, void* y_dev, void* stream) {
     if (!x_dev || !w_host || !b_host || !y_dev) return fail(NESR_ERR_ARG, "null argument");
     if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout > 64) return fail(NESR_ERR_ARG, "bad shape (Cout <= 64)");
-    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F32_WINOGRAD && dtype != NESR_DTYPE_F32_SPLIT)
+    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F32_WINOGRAD && dtype != NESR_DTYPE_F32_SPLIT &&
+        dtype != NESR_DTYPE_F16)
         return fail(NESR_ERR_ARG, "bad dtype");
     const bool wino = dtype == NESR_DTYPE_F32_WINOGRAD;
     const bool sp = dtype == NESR_DTYPE_F32_SPLIT;
-    const int kind = sp ? 2 : (dtype == NESR_DTYPE_BF16 ? 1 : 0);
+    const bool hf = dtype == NESR_DTYPE_F16;
+    const int kind = sp ? 2 : (dtype == NESR_DTYPE_BF16 ? 1 : (hf ? 3 : 0));
+    if (hf)
+        for (size_t i = 0; i < (size_t)Cout * Cin * 9; ++i)
+            if (!(std::fabs(w_host[i]) <= 65504.f)) return fail(NESR_ERR_RANGE, "weight does not fit the f16 form (|w| > 65504 or non-finite)");
     HIP_TRY(hipSetDevice(device_id));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool bf = dtype == NESR_DTYPE_BF16;
-    const size_t es = bf ? 2 : 4;
-    const int cin_p = round_up(Cin, (bf || sp) ? 16 : 8), cout_p = round_up(Cout, 32);
+    const size_t es = (bf || hf) ? 2 : 4;
+    const int cin_p = round_up(Cin, (bf || sp || hf) ? 16 : 8), cout_p = round_up(Cout, 32);
     const int up = upsample ? 1 : 0;
     const int ho = H << up, wo = W << up;
-    const size_t we = sp ? packed_weight_elems_f16x2(cin_p, cout_p) / 2 : bf ? packed_weight_elems_bf16(cin_p, cout_p)
+    const size_t we = sp ? packed_weight_elems_f16x2(cin_p, cout_p) / 2 : (bf || hf) ? packed_weight_elems_bf16(cin_p, cout_p)
                          : (wino ? packed_weight_elems_wino_f32(cin_p, cout_p) : packed_weight_elems_f32(cin_p, cout_p));
     std::vector<char> hw(we * es);
     if (sp)
         pack_weights_f16x2(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
     else if (bf)
         pack_weights_bf16(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
+    else if (hf)
+        pack_weights_f16(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
     else if (wino)
         pack_weights_wino_f32(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<float*>(hw.data()));
     else
@@ -1365,7 +1389,7 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
     std::memset(&p, 0, sizeof(p));
     const Map mi = make_map(kind, cin_p, (size_t)N * H * W), mo = make_map(kind, cout_p, (size_t)N * ho * wo);
     p.src = x_dev; p.n = N; p.c = Cin; p.hin = H; p.win = W; p.unshuffle = 1; p.dst = d_in; p.dst_map = mi; p.cp = cin_p; p.bf16 = kind;
-    p.status = sp ? d_status : nullptr;
+    p.status = (sp || hf) ? d_status : nullptr;
     HIP_TRY(launch_pack_input(p, s));
     ConvArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1375,10 +1399,16 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
     a.out = d_out; a.out_map = mo; a.out_coff = 0;
     a.lrelu = lrelu ? 1 : 0; a.s1 = a.s2 = 1.f;
     a.zeros = d_zero;
-    a.status = sp ? d_status : nullptr;
-    HIP_TRY(sp ? launch_conv3x3_f16x2(a, s) : bf ? launch_conv3x3_bf16(a, s) : (wino ? launch_conv3x3_wino_f32(a, s) : launch_conv3x3_f32(a, s)));
+    a.status = (sp || hf) ? d_status : nullptr;
+    HIP_TRY(sp ? launch_conv3x3_f16x2(a, s) : bf ? launch_conv3x3_bf16(a, s) : hf ? launch_conv3x3_f16(a, s)
+                                                                            : (wino ? launch_conv3x3_wino_f32(a, s) : launch_conv3x3_f32(a, s)));
     HIP_TRY(launch_nhwc_to_nchw(d_out, kind, mo, N, Cout, ho, wo, static_cast<float*>(y_dev), s));
     HIP_TRY(hipStreamSynchronize(s));
+    if (hf) {
+        unsigned flag = 0;
+        HIP_TRY(hipMemcpy(&flag, d_status, 4, hipMemcpyDeviceToHost));
+        if (flag) return fail(NESR_ERR_RANGE, "input or output of the layer was non-finite or exceeded 65504 in magnitude (f16 form)");
+    }
     if (sp) {
         unsigned flag = 0;
         HIP_TRY(hipMemcpy(&flag, d_status, 4, hipMemcpyDeviceToHost));
@@ -1574,6 +1604,7 @@ int nesr_forward_sharded_u8(nesr_ctx* c, const uint8_t* band_dev, int H, int W, 
     if (c->cin0 != 3 * u * u || c->nout != 3) return fail(NESR_ERR_ARG, "nesr_forward_sharded_u8 needs a 3-channel-in / 3-channel-out network");
     if (H < 1 || W < 1 || H % u || W % u || tile < 0 || tile_pad < 0) return fail(NESR_ERR_ARG, "nesr_forward_sharded_u8: frame sides must be multiples of the unshuffle factor");
     if (rank == 0 && !out_dev) return fail(NESR_ERR_ARG, "rank 0 needs the output canvas");
+    // bf16 only: the f16 form would need the range word of every rank's ragged batches gathered with the tiles (not built)
     if (c->dtype != NESR_DTYPE_BF16) return fail(NESR_ERR_ARG, "nesr_forward_sharded_u8: compute dtype bf16 (ragged tile batches)");
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -109,6 +109,11 @@ hipError_t launch_conv3x3_bf16(const ConvArgs& a, hipStream_t s);       // picks
 hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s);    // conv3x3_bf16.hip: 32x32-px tiles, 3-deep LDS-DMA ring
 size_t packed_weight_elems_bf16(int cin_p, int coutp);
 void pack_weights_bf16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst);
+// f16 path: the same kernels instantiated on f16 (v_mfma_f32_32x32x16_f16), the same layouts; every stored activation is
+// range-checked (|x| <= 65504, finite) into ConvArgs::status, and conv_last writes NaN once that word is set
+hipError_t launch_conv3x3_f16(const ConvArgs& a, hipStream_t s);        // picks the variant as launch_conv3x3_bf16 does
+hipError_t launch_conv3x3_f16_xl(const ConvArgs& a, hipStream_t s);
+void pack_weights_f16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst);   // packed_weight_elems_bf16 elements
 
 // f32 path on the f16 matrix cores (conv3x3_f16x2.hip): operands as (hi, lo) half pairs, x = hi + lo * 2^-11,
 // three MFMAs per product, f32 accumulation.  Activations: channel-blocked [C/16][pixels][16 hi | 16 lo]
@@ -154,7 +159,7 @@ struct StripSchedule {
 // segment at most (0: chosen by the packer, < 0: images are never cut)
 StripSchedule strip_schedule(int n, const int* hw, int cus, int seg_len = 0);
 size_t strip_weight_bytes();
-void pack_strip_weights(const float* const w[5], uint16_t* dst);   // conv1..conv5 OIHW f32 of one dense block
+void pack_strip_weights(const float* const w[5], uint16_t* dst, bool f16);   // conv1..conv5 OIHW f32 of one dense block -> bf16 | f16
 struct StripLaunch {
     const void* cur; long long chunk_bytes; void* out; const void* res2;
     float s1, s2;
@@ -167,6 +172,8 @@ struct StripLaunch {
     unsigned* abort_flag;
     unsigned long long timeout_ticks;
     int debug_drop;                               // test hook: this many workgroups of the launch never start
+    int f16;                                      // 0: bf16 operands; 1: f16 operands (pack_strip_weights(..., true))
+    unsigned* status;                             // f16: the range word (ConvArgs::status); separate from abort_flag
 };
 hipError_t launch_rdb_bf16_strip(const StripLaunch& r, hipStream_t s);
 
@@ -204,8 +211,9 @@ struct PackArgs {
     void* dst;           // feature map with cp channels (zero padded), addressed through dst_map
     Map dst_map;
     int cp;
-    int bf16;            // destination layout: 0 f32 NHWC (KG = 8), 1 bf16 blocked (KG = 16), 2 f16 hi|lo blocked (KG = 16)
-    unsigned* status;    // as ConvArgs::status (layout 2 only); may be null
+    int bf16;            // destination layout: 0 f32 NHWC (KG = 8), 1 bf16 blocked (KG = 16), 2 f16 hi|lo blocked (KG = 16),
+                         // 3 f16 blocked (KG = 16)
+    unsigned* status;    // as ConvArgs::status (layouts 2 and 3); may be null
 };
 hipError_t launch_pack_input(const PackArgs& a, hipStream_t s);
 hipError_t launch_status_latch(unsigned* status, hipStream_t s);   // range word of an unchecked earlier forward: word 0 -> word 3

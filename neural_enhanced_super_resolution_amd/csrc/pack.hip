@@ -64,6 +64,9 @@ __global__ __launch_bounds__(256) void pack_input_kernel(PackArgs a) {
                 bad |= !f2hl(v, hi, lo);
                 static_cast<uint16_t*>(a.dst)[idx] = hi;
                 static_cast<uint16_t*>(a.dst)[idx + 16] = lo;
+            } else if (a.bf16 == 3) {
+                bad |= !(__builtin_fabsf(v) <= 65504.f);      // f16 cannot carry it: the range word (conv_last then writes NaN)
+                static_cast<uint16_t*>(a.dst)[idx] = __builtin_bit_cast(uint16_t, (_Float16)v);
             } else if (a.bf16)
                 static_cast<uint16_t*>(a.dst)[idx] = f2bf(v);
             else
@@ -85,6 +88,8 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const void* src, int 
         const size_t idx = (size_t)(ch / kg) * map.chunk + pix * map.pix + (ch % kg);
         if (bf16 == 2)
             dst[i] = hl2f(static_cast<const uint16_t*>(src)[idx], static_cast<const uint16_t*>(src)[idx + 16]);
+        else if (bf16 == 3)
+            dst[i] = (float)__builtin_bit_cast(_Float16, static_cast<const uint16_t*>(src)[idx]);
         else
             dst[i] = bf16 ? bf2f(static_cast<const uint16_t*>(src)[idx]) : static_cast<const float*>(src)[idx];
     }

@@ -41,13 +41,11 @@
 #include <type_traits>
 #include <vector>
 
+#include "elem16.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) char lds_char;
 typedef const __attribute__((address_space(3))) f32x4* lds_f32x4;
 
@@ -178,13 +176,6 @@ __device__ __forceinline__ uint4 load16_sc1_wait(const char* p) {
     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(v) : "v"(p) : "memory");
     return __builtin_bit_cast(uint4, v);
 }
-__device__ __forceinline__ uint2 pack4_bf16(f32x4 v) {   // plain casts -> v_cvt_pk_bf16_f32 (RNE, NaN preserving)
-    const bf16x4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    return __builtin_bit_cast(uint2, b);
-}
-__device__ __forceinline__ f32x4 unpack4_bf16(uint2 u) {
-    return f32x4{__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u)};
-}
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // max(v, 0.2 v), exact; v_max_f32 by hand: fmaxf() first canonicalises its operands (one more VALU instruction per value,
@@ -226,6 +217,7 @@ struct StripArgs {
     unsigned epoch;           // tags of this launch are epoch + position * 8 + layer
     unsigned* abort_flag;
     unsigned long long timeout_ticks;   // s_memrealtime ticks (100 MHz) a halo wait may take
+    unsigned* status;         // f16: sticky range word (ConvArgs::status), raised for a stored x1..x4 or block output beyond +-65504
 };
 
 // wave priorities (s_setprio): measured on the 4K frame, the DMA waves at 3 (as in the f32 fused kernel) cost 1.1 % against 0 or 1 --
@@ -247,6 +239,8 @@ __device__ unsigned long long g_strip_stamps[8][32][8];      // [wave][step of p
 #define SSTAMP(w, step, ev) do { } while (0)
 #endif
 
+// K: 1 bf16, 3 f16 (elem16.h)
+template <int K>
 __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(StripArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -549,10 +543,8 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                 } else {
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt) {
-                        const bf16x8 wf = __builtin_bit_cast(bf16x8, Af[cb][dy][mt]);
 #pragma unroll
-                        for (int r = 0; r < 3; ++r)
-                            acc[CG][r][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, __builtin_bit_cast(bf16x8, Bf[i][r + dy]), acc[CG][r][mt], 0, 0, 0);
+                        for (int r = 0; r < 3; ++r) acc[CG][r][mt] = E16<K>::mfma16(Af[cb][dy][mt], Bf[i][r + dy], acc[CG][r][mt]);
                     }
                 }
                 if constexpr (i < 2) load_a(cb, dy, sl2);
@@ -634,6 +626,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                     const unsigned tag = tagbase + (unsigned)m;
                     char* xdst = xch_mine + ((size_t)(pos & 1) * 4 + (m - 1)) * XCH_LAYER;
                     const int bm = base_of(wbp, m);
+                    unsigned amax = 0;                      // f16: largest |x| stored (elem16.h), raised behind the layer
 #pragma unroll
                     for (int r = 0; r < 3; ++r) {
                         const int y = yw - (m - 1) + r;
@@ -642,7 +635,12 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                         sl -= sl >= mp.R ? mp.R : 0;
 #pragma unroll
                         for (int mt = 0; mt < 2; ++mt) {
-                            uint2 pk = pack4_bf16(lrelu4(acc[0][r][mt]));
+                            const f32x4 xv = lrelu4(acc[0][r][mt]);
+                            if constexpr (E16<K>::RANGE) {
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) amax = E16<K>::amax(amax, ok ? xv[i] : 0.f);
+                            }
+                            uint2 pk = E16<K>::pack4(xv);
                             pk.x = ok ? pk.x : 0u;
                             pk.y = ok ? pk.y : 0u;
                             *reinterpret_cast<uint2*>(smem + mp.off + sl * ROWB1 + mt * CHB + lane_e) = pk;
@@ -651,6 +649,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                         }
                     }
                     if (m < 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if constexpr (E16<K>::RANGE) raise_range(a.status, amax);
                     SSTAMP(wv, sidx - 1, 3);
                 } else {
 #pragma unroll
@@ -675,7 +674,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
 #pragma unroll
                     for (int mt = 0; mt < 2; ++mt)
                     {
-                        const f32x4 u = unpack4_bf16(*reinterpret_cast<const uint2*>(smem + sl * ROWB0 + (2 * c2 + mt) * CHB + lane_e)), bz = bias4(128 + 32 * c2, mt);
+                        const f32x4 u = E16<K>::unpack4(*reinterpret_cast<const uint2*>(smem + sl * ROWB0 + (2 * c2 + mt) * CHB + lane_e)), bz = bias4(128 + 32 * c2, mt);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) acc[c2][r][mt][i] = fmaf(u[i], inv_s1, bz[i]);
                     }
@@ -717,6 +716,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                 for (int k = 0; k < 5; ++k) ba[k] = nba[k];
             }
             if (!(NESR_STRIP_ABL & 8)) {
+                unsigned amax = 0;                          // f16: largest |x| of the block output stored
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
                     const int y = yw - 4 + r;
@@ -737,14 +737,18 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                             const uint4 q = res2q[c2][r];
                             const auto sx = __builtin_amdgcn_permlane16_swap(q.x, q.z, false, false);
                             const auto sy = __builtin_amdgcn_permlane16_swap(q.y, q.w, false, false);
-                            const f32x4 q0 = unpack4_bf16(uint2{sx[0], sy[0]}), q1 = unpack4_bf16(uint2{sx[1], sy[1]});
+                            const f32x4 q0 = E16<K>::unpack4(uint2{sx[0], sy[0]}), q1 = E16<K>::unpack4(uint2{sx[1], sy[1]});
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
                                 v[0][i] = __fadd_rn(__fmul_rn(v[0][i], a.s2), q0[i]);
                                 v[1][i] = __fadd_rn(__fmul_rn(v[1][i], a.s2), q1[i]);
                             }
                         }
-                        const uint2 p0 = pack4_bf16(v[0]), p1 = pack4_bf16(v[1]);
+                        if constexpr (E16<K>::RANGE) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) amax = E16<K>::amax(E16<K>::amax(amax, valid ? v[0][i] : 0.f), valid ? v[1][i] : 0.f);
+                        }
+                        const uint2 p0 = E16<K>::pack4(v[0]), p1 = E16<K>::pack4(v[1]);
                         const auto ox = __builtin_amdgcn_permlane16_swap(p0.x, p1.x, false, false);
                         const auto oy = __builtin_amdgcn_permlane16_swap(p0.y, p1.y, false, false);
                         if (valid)
@@ -755,6 +759,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                         }
                     }
                 }
+                if constexpr (E16<K>::RANGE) raise_range(a.status, amax);
             } else {
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2)
@@ -772,6 +777,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
     }
 }
 
+inline uint16_t f2h(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }   // round-to-nearest-even (torch's .half())
 inline uint16_t f2bf(float f) {  // round-to-nearest-even, NaN stays NaN
     uint32_t u;
     __builtin_memcpy(&u, &f, 4);
@@ -791,8 +797,8 @@ size_t strip_weight_bytes() { return (size_t)WPER * WSLOT; }
 
 // The five convs of one dense block (OIHW f32, conv_k: [32 | 64][64 + 32 (k-1)][3][3]) -> the kernel's weight stream:
 // [step: layer m, chunk pair p, (conv5: cout group)][tap column in the order 1, 0, 2][dy][chunk of the pair][k half]
-// [cout % 32][8 channels] bf16.
-void pack_strip_weights(const float* const w[5], uint16_t* dst) {
+// [cout % 32][8 channels] bf16 (f16: f16).
+void pack_strip_weights(const float* const w[5], uint16_t* dst, bool f16) {
     size_t slot = 0;
     for (int m = 1; m <= 5; ++m) {
         const int cin = 64 + 32 * (m - 1), npairs = m + 1, ncg = m == 5 ? 2 : 1;
@@ -807,7 +813,7 @@ void pack_strip_weights(const float* const w[5], uint16_t* dst) {
                                 for (int o = 0; o < 32; ++o)
                                     for (int kk = 0; kk < 8; ++kk) {
                                         const int co = 32 * cg + o, ci = 32 * p + 16 * ck + 8 * kh + kk;
-                                        d[(((dy * 2 + ck) * 2 + kh) * 32 + o) * 8 + kk] = f2bf(w[m - 1][(((size_t)co * cin + ci) * 3 + dy) * 3 + dx]);
+                                        d[(((dy * 2 + ck) * 2 + kh) * 32 + o) * 8 + kk] = (f16 ? f2h : f2bf)(w[m - 1][(((size_t)co * cin + ci) * 3 + dy) * 3 + dx]);
                                     }
                 }
     }
@@ -952,12 +958,31 @@ StripSchedule strip_schedule(int n, const int* hw, int cus, int seg_len) {
     return best;
 }
 
-hipError_t launch_rdb_bf16_strip(const StripLaunch& r, hipStream_t s) {
+namespace {
+template <int K>
+hipError_t launch_strip(const StripArgs& a, int grid_all, int debug_drop, hipStream_t s) {
     static unsigned long long attr_done = 0;
     {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rdb_bf16_strip_kernel), LDSB, attr_done);
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rdb_bf16_strip_kernel<K>), LDSB, attr_done);
         if (e != hipSuccess) return e;
     }
+    static int resident = -1;      // one workgroup per CU (LDS): the schedule's grid is at most the compute-unit count
+    if (resident < 0) {
+        int per_cu = 0, dev = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rdb_bf16_strip_kernel<K>, 64 * (MW + DW), LDSB) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+            return hipErrorUnknown;
+        resident = per_cu * cus;
+    }
+    if (grid_all > resident) return hipErrorLaunchOutOfResources;
+    const int grid = grid_all - debug_drop;     // test hook (nesr_debug_fault): the last workgroups never start
+    if (grid <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rdb_bf16_strip_kernel<K>, dim3((unsigned)grid), dim3(64 * (MW + DW)), LDSB, s, a);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_rdb_bf16_strip(const StripLaunch& r, hipStream_t s) {
     if (r.grid <= 0) return hipSuccess;
     if (4 * r.chunk_bytes >= (1ll << 32)) return hipErrorInvalidValue;     // 32-bit lane offsets across the four x0 chunks
     StripArgs a;
@@ -976,19 +1001,8 @@ hipError_t launch_rdb_bf16_strip(const StripLaunch& r, hipStream_t s) {
     a.epoch = r.epoch;
     a.abort_flag = r.abort_flag;
     a.timeout_ticks = r.timeout_ticks;
-    static int resident = -1;      // one workgroup per CU (LDS): the schedule's grid is at most the compute-unit count
-    if (resident < 0) {
-        int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rdb_bf16_strip_kernel, 64 * (MW + DW), LDSB) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            return hipErrorUnknown;
-        resident = per_cu * cus;
-    }
-    if (r.grid > resident) return hipErrorLaunchOutOfResources;
-    const int grid = r.grid - r.debug_drop;     // test hook (nesr_debug_fault): the last workgroups never start
-    if (grid <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rdb_bf16_strip_kernel, dim3((unsigned)grid), dim3(64 * (MW + DW)), LDSB, s, a);
-    return hipGetLastError();
+    a.status = r.status;
+    return r.f16 ? launch_strip<3>(a, r.grid, r.debug_drop, s) : launch_strip<1>(a, r.grid, r.debug_drop, s);
 }
 
 }  // namespace nesr

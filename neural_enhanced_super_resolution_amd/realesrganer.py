@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from torch.nn import functional as F
 
-from .rrdbnet import RRDBNet
+from .rrdbnet import RAGGED_FORMS, RRDBNet
 from .srvgg import SRVGGNetCompact
 
 
@@ -84,7 +84,8 @@ class RealESRGANer:
         model (nn.Module): the network (RRDBNet).
         tile (int): tile size; 0 = no tiling.
         tile_pad (int): pad size of each tile.  pre_pad (int): reflect pad before the network.
-        half (bool): upstream's fp16 switch; here it selects the bf16 MFMA kernels.
+        half (bool): upstream's fp16 switch; here it selects the bf16 MFMA kernels, or keeps a model built with
+            RRDBNet(..., compute_dtype="f16") in f16 (upstream's fp16 numerics).
         device: 'cuda' (= the ROCm GPU), torch.device or None (-> cuda if available).
     """
 
@@ -135,7 +136,7 @@ class RealESRGANer:
         self.model = model.to(self.device)
         if self.half:
             self.model = self.model.half()
-        if isinstance(self.model, RRDBNet) and self.tile_size > 0 and self.model.compute_dtype == "bf16":
+        if isinstance(self.model, RRDBNet) and self.tile_size > 0 and self.model.compute_dtype in RAGGED_FORMS:
             # a tiling wrapper batches tiles of different shapes (ragged batches): a tile's values must not depend on how it
             # was batched, nor on whether model(tile) was called directly -- kernels are chosen by arithmetic only
             self.model.size_independent = True
@@ -235,7 +236,7 @@ class RealESRGANer:
             groups.setdefault((t[1] - t[0], t[3] - t[2]), []).append(t)
         order = sorted(groups.items(), key=lambda kv: -kv[0][0] * kv[0][1] * len(kv[1]))
         hip = self._hip_model() and img.device.type == "cuda"
-        if hip and isinstance(self.model, RRDBNet) and img.shape[0] == 1 and self.model.compute_dtype == "bf16":
+        if hip and isinstance(self.model, RRDBNet) and img.shape[0] == 1 and self.model.compute_dtype in RAGGED_FORMS:
             ragged = self.model.strip_kernel_active() if self.ragged_tiles is None else bool(self.ragged_tiles)
             if ragged and (len(order) > 1 or self.ragged_tiles is None):
                 return self._run_tiles_ragged(img, tiles, sink, single_stream=self.ragged_tiles is None)
@@ -415,7 +416,7 @@ class RealESRGANer:
         each and the float canvas of the frame never exists.  Frames that need the reflect pre-pad / mod-pad keep the general path."""
         ms = {2: 2, 1: 4}.get(self.scale, 1)
         return (self.tile_size > 0 and self.pre_pad == 0 and h % ms == 0 and w % ms == 0 and isinstance(self.model, RRDBNet)
-                and self.model.compute_dtype == "bf16" and self.model.strip_kernel_active() and self.ragged_tiles is None
+                and self.model.compute_dtype in RAGGED_FORMS and self.model.strip_kernel_active() and self.ragged_tiles is None
                 and self.model.out_scale() == self.scale)
 
     @torch.no_grad()

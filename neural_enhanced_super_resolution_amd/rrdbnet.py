@@ -73,6 +73,12 @@ class _RRDBParams(nn.Module):
         self.rdb3 = _RDBParams(nf, gc)
 
 
+# compute_dtype strings of the f16 form (opt-in: .half() and torch.float16 keep selecting bf16), and the 16-bit forms whose tiles run
+# as ragged batches through the LDS-resident strip kernel
+F16_FORMS = ("f16", "fp16")
+RAGGED_FORMS = ("bf16",) + F16_FORMS
+
+
 class RRDBNet(nn.Module):
     """Networks consisting of Residual in Residual Dense Blocks (ESRGAN / Real-ESRGAN generator).
 
@@ -85,7 +91,10 @@ class RRDBNet(nn.Module):
                       into NaN and raise NesrRangeError at the next check_range()/check_status()
       "f32-winograd"  f32 matrix cores, Winograd F(2x2,3x3) for the feature-map convs (error 2e-6)
       "f32-direct"    f32 matrix cores, direct implicit GEMM: bitwise a k-ordered fmaf chain
-      "bf16"          bf16 storage and MFMA, f32 accumulation (upstream's half=True is fp16)
+      "bf16"          bf16 storage and MFMA, f32 accumulation (what .half() / half=True select here)
+      "f16" ("fp16")  f16 storage and MFMA, f32 accumulation: upstream's half=True numerics.  Opt-in: an "f16" model
+                      stays f16 through .half(); the range contract of "f32" holds (|x| <= 65504: weights refused at
+                      upload, an activation beyond it makes the output NaN and raises NesrRangeError at check_range())
     """
 
     def __init__(self, num_in_ch, num_out_ch, scale=4, num_feat=64, num_block=23, num_grow_ch=32,
@@ -97,7 +106,7 @@ class RRDBNet(nn.Module):
         self.num_feat = num_feat
         self.num_block = num_block
         self.num_grow_ch = num_grow_ch
-        self.compute_dtype = compute_dtype
+        self.compute_dtype = "f16" if compute_dtype == "fp16" else compute_dtype
         self._build_params()
         self.calls = 0            # forward evaluations so far (callers assert on it: the reference's exception ladders
                                   # turn a dead backend into a silent bicubic resize, nesr/nesr.py:815-843)
@@ -135,8 +144,9 @@ class RRDBNet(nn.Module):
     def half(self):
         """Upstream's fp16 switch (RealESRGANer(half=True) calls model.half()).  Here it selects the bf16 MFMA
         kernels; the parameters stay float32, so the bf16 weights are rounded once from the checkpoint's values
-        (not float32 -> fp16 -> bf16)."""
-        self.compute_dtype = "bf16"
+        (not float32 -> fp16 -> bf16).  A model built with compute_dtype="f16" stays f16 (upstream's fp16 run)."""
+        if self.compute_dtype not in F16_FORMS:
+            self.compute_dtype = "bf16"
         self._dirty = True
         return self
 
@@ -144,8 +154,8 @@ class RRDBNet(nn.Module):
         out = super()._apply(fn, *a, **k)
         self._dirty = True
         p = self.conv_body.weight
-        if p.dtype in (torch.float16, torch.bfloat16):
-            self.compute_dtype = "bf16"   # .half(): upstream's fp16 switch selects the bf16 MFMA kernels here
+        if p.dtype in (torch.float16, torch.bfloat16) and self.compute_dtype not in F16_FORMS:
+            self.compute_dtype = "bf16"   # .half(): upstream's fp16 switch selects the bf16 MFMA kernels here (an "f16" model stays f16)
         return out
 
     # ------------------------------------------------------------------ HIP context
@@ -173,7 +183,9 @@ class RRDBNet(nn.Module):
             return _lib.DTYPE_F32               # direct implicit GEMM everywhere (bitwise a k-ordered fmaf chain)
         if self.compute_dtype in ("bf16", torch.bfloat16, "half", torch.float16):
             return _lib.DTYPE_BF16
-        raise ValueError(f"compute_dtype {self.compute_dtype!r}: expected 'f32' or 'bf16'")
+        if self.compute_dtype in F16_FORMS:
+            return _lib.DTYPE_F16               # f16 operands on the f16 matrix cores, range-checked (|x| <= 65504)
+        raise ValueError(f"compute_dtype {self.compute_dtype!r}: expected 'f32', 'bf16' or 'f16'")
 
     def _upload(self, handle):
         lib = _lib.load()
@@ -240,10 +252,10 @@ class RRDBNet(nn.Module):
             _lib.check(_lib.load().nesr_set_size_independent(h[0], 1 if on else 0), "nesr_set_size_independent")
 
     def strip_kernel_active(self):
-        """True when bf16 dense blocks of a size-independent model run as the LDS-resident strip kernel (rdb_bf16_strip.hip;
+        """True when bf16 / f16 dense blocks of a size-independent model run as the LDS-resident strip kernel (rdb_bf16_strip.hip;
         NESR_STRIP=0 turns it off): the tiling wrapper then hands all tiles of a frame over as one ragged batch."""
         import os
-        return (self.compute_dtype == "bf16" and self.size_independent and self.num_feat == 64 and self.num_grow_ch == 32
+        return (self.compute_dtype in RAGGED_FORMS and self.size_independent and self.num_feat == 64 and self.num_grow_ch == 32
                 and self.num_block > 0 and os.environ.get("NESR_STRIP", "-1") != "0")
 
     # ------------------------------------------------------------------ forward
@@ -287,7 +299,7 @@ class RRDBNet(nn.Module):
         x: [N, num_in_ch, H, W] float on a ROCm device, image i in the top-left sizes[i] = (h_i, w_i) pixels of slot i
         (the rest of a slot is ignored); returns [N, num_out_ch, H*s, W*s] whose slot i holds image i's output in its
         top-left h_i*s x w_i*s pixels (the rest is unspecified).  Every image gets the values forward() gives it alone
-        on a model with size_independent = True.  compute_dtype "bf16" only; N <= RAGGED_MAX."""
+        on a model with size_independent = True.  compute_dtype "bf16" or "f16" only; N <= RAGGED_MAX."""
         self._require_cuda(x)
         if x.dim() != 4 or len(sizes) != x.shape[0]:
             raise ValueError(f"expected NCHW input and one (h, w) per image, got {tuple(x.shape)} and {len(sizes)} sizes")
@@ -523,14 +535,14 @@ class RRDBNet(nn.Module):
 
     def check_range(self, slot=None):
         """Raises NesrRangeError if a forward enqueued so far (on torch's current stream) met an input or activation
-        the f16-pair fp32 form cannot carry (non-finite or beyond +-65504): its float output is NaN and an 8-bit
+        the f16-pair fp32 form or the f16 form cannot carry (non-finite or beyond +-65504): its float output is NaN and an 8-bit
         output is invalid.  Waits for the current stream only; a no-op for the other compute dtypes.  The wrappers
         call it after every device-to-host copy (the reference would have returned NaN pixels, nesr/nesr.py:891-898)."""
         handles = ([self._ctx] if self._ctx is not None else []) + list(self._extra.values()) if slot is None else \
                   [self._ctx if slot == 0 else self._extra.get(slot)]
         lib = _lib.load()
         for h in handles:
-            if h is None or h[2] not in (_lib.DTYPE_F32_SPLIT, _lib.DTYPE_BF16):     # the forms with a range word or persistent launches
+            if h is None or h[2] not in (_lib.DTYPE_F32_SPLIT, _lib.DTYPE_BF16, _lib.DTYPE_F16):   # the forms with a range word or persistent launches
                 continue
             dev = torch.device("cuda", h[1])
             with torch.cuda.device(dev):
@@ -609,7 +621,7 @@ def conv3x3(x, weight, bias, lrelu=False, upsample=False, dtype="f32"):
         stream = torch.cuda.current_stream(x.device).cuda_stream
         # "f32" is what RRDBNet(compute_dtype="f32") runs: the f16-pair kernel
         code = {"bf16": _lib.DTYPE_BF16, "f32-winograd": _lib.DTYPE_F32_WINOGRAD, "f32": _lib.DTYPE_F32_SPLIT, "f32-split": _lib.DTYPE_F32_SPLIT,
-                "f32-direct": _lib.DTYPE_F32}[dtype]
+                "f32-direct": _lib.DTYPE_F32, "f16": _lib.DTYPE_F16, "fp16": _lib.DTYPE_F16}[dtype]
         _lib.check(lib.nesr_conv3x3(index, code,
                                     ctypes.c_void_p(x.data_ptr()), n, cin, h, w, ctypes.c_void_p(wt.data_ptr()),
                                     ctypes.c_void_p(bs.data_ptr()), cout, 1 if lrelu else 0, up,

@@ -2,7 +2,7 @@
 """In-process A/B timing of two builds of libnesr_hip.so (cdna_hip_programming.md rule 24: perf
 deltas come from interleaved rounds in ONE process on ONE device).
 
-    tools/ab.py A.so B.so [--dtype direct|bf16|wino|split] [--dtype-b ...] [--hw 512] [--batch 1] [--rounds 12] [--env-b K=V,K2=V2]
+    tools/ab.py A.so B.so [--dtype direct|bf16|wino|split|f16] [--dtype-b ...] [--hw 512] [--batch 1] [--rounds 12] [--env-b K=V,K2=V2]
 """
 import argparse
 import ctypes
@@ -53,7 +53,7 @@ def main():
     ap.add_argument("--env-a", default="")
     ap.add_argument("--env-b", default="")
     args = ap.parse_args()
-    codes = {"f32": 0, "direct": 0, "bf16": 1, "wino": 2, "split": 3}
+    codes = {"f32": 0, "direct": 0, "bf16": 1, "wino": 2, "split": 3, "f16": 4}
     dts = [codes[args.dtype], codes[args.dtype_b or args.dtype]]
     sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=2)
     x = torch.rand(args.batch, 3, args.hw, args.hw, device="cuda")

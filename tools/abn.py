@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """In-process timing of N builds of libnesr_hip.so, interleaved rounds on one device (cdna_hip_programming.md rule 24).
 
-    tools/abn.py A.so B.so [C.so ...] [--dtype direct|bf16|wino|split] [--hw 512] [--batch 1] [--rounds 12]
+    tools/abn.py A.so B.so [C.so ...] [--dtype direct|bf16|wino|split|f16] [--hw 512] [--batch 1] [--rounds 12]
                  [--env "K=V,K2=V2;K=V;..."]      (one ;-separated entry per library, applied through its first forward)
+    --dtype takes one value for all libraries or a comma-separated list, one per library: `new.so new2.so --dtype bf16,f16 --c3`
+    times the two 16-bit forms of one build on the ragged 4K batch (two copies of the file: dlopen returns one handle per path).
 """
 import argparse
 import ctypes
@@ -30,12 +32,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--iters", type=int, default=3)
     ap.add_argument("--env", default="")
-    ap.add_argument("--c3", action="store_true", help="the 40 ragged tiles of a 3840x2160 frame cut 512/10 (nesr_forward_ragged, bf16)")
+    ap.add_argument("--c3", action="store_true", help="the 40 ragged tiles of a 3840x2160 frame cut 512/10 (nesr_forward_ragged, bf16 / f16)")
     ap.add_argument("--share", type=int, default=1, help="with --c3: only every share-th tile (what one of `share` ranks of a sharded frame evaluates)")
     args = ap.parse_args()
-    code = {"f32": 0, "direct": 0, "bf16": 1, "wino": 2, "split": 3}[args.dtype]
+    codes = {"f32": 0, "direct": 0, "bf16": 1, "wino": 2, "split": 3, "f16": 4}
     sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=2)
     n = len(args.libs)
+    dts = args.dtype.split(",")
+    dts = [codes[d] for d in (dts * n if len(dts) == 1 else dts)]
+    assert len(dts) == n, "--dtype: one value, or one per library"
     envs = (args.env.split(";") + [""] * n)[:n]
     x = torch.rand(args.batch, 3, args.hw, args.hw, device="cuda")
     y = [torch.empty(args.batch, 3, 2 * args.hw, 2 * args.hw, device="cuda") for _ in range(n)]
@@ -73,7 +78,7 @@ def main():
             os.environ[k] = v
         lib = load(os.path.abspath(path))
         libs.append(lib)
-        ctxs.append(make_ctx(lib, sd, code))
+        ctxs.append(make_ctx(lib, sd, dts[i]))
         run(i)
         torch.cuda.synchronize()
         for k, _ in kvs:
