@@ -16,6 +16,7 @@ evaluation goes through ``self.model``, which for this package is the HIP-backed
 from __future__ import annotations
 
 import math
+import os
 import warnings
 
 import numpy as np
@@ -73,6 +74,35 @@ def _gray2rgb(img):
     return np.repeat(img[:, :, None], 3, axis=2)
 
 
+def parse_devices(devices, count):
+    """RealESRGANer's ``devices=`` keyword -> list of CUDA device indices, or None for the one-device wrapper.  With
+    ``devices=None`` the NESR_DEVICES environment variable (comma-separated indices, e.g. "0,1,2,3") is read instead, so
+    callers that cannot pass the keyword opt in from outside; unset or empty means None.  Repeated indices are allowed
+    (several contexts on one device).  An empty list, a non-integer or an index outside [0, count) raises ValueError."""
+    source = "devices"
+    if devices is None:
+        devices = os.environ.get("NESR_DEVICES", "").strip()
+        if not devices:
+            return None
+        source = "NESR_DEVICES"
+    if isinstance(devices, str):
+        try:
+            devices = [int(v) for v in devices.split(",")]
+        except ValueError:
+            raise ValueError(f"{source}={devices!r}: expected comma-separated CUDA device indices") from None
+    out = []
+    for d in devices:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+            raise ValueError(f"{source}: {d!r} is not a CUDA device index")
+        out.append(int(d))
+    if not out:
+        raise ValueError(f"{source}: the device list is empty")
+    for d in out:
+        if d < 0 or d >= count:
+            raise ValueError(f"{source}: device {d} does not exist ({count} visible)")
+    return out
+
+
 class RealESRGANer:
     """A helper class for upsampling images with RealESRGAN (MI355X/HIP backend).
 
@@ -87,10 +117,15 @@ class RealESRGANer:
         half (bool): upstream's fp16 switch; here it selects the bf16 MFMA kernels, or keeps a model built with
             RRDBNet(..., compute_dtype="f16") in f16 (upstream's fp16 numerics).
         device: 'cuda' (= the ROCm GPU), torch.device or None (-> cuda if available).
+        devices (list[int] | None): not upstream's: CUDA device indices one wrapper spreads its work over from this process
+            (repeats put several contexts on one device).  None reads NESR_DEVICES (see parse_devices); with neither set the
+            wrapper runs on `device` alone, as upstream's does.  With two or more entries a tiled frame's tiles are split over
+            them (sharded.plan_tiles) and enhance_many deals whole frames to them; the result is bitwise the one-device result.
+            Untiled frames run on the first entry, which is also where the output is assembled and `device` points.
     """
 
     def __init__(self, scale, model_path, dni_weight=None, model=None, tile=0, tile_pad=10, pre_pad=10,
-                 half=False, device=None, gpu_id=None):
+                 half=False, device=None, gpu_id=None, devices=None):
         self.scale = scale
         self.tile_size = tile
         self.tile_pad = tile_pad
@@ -111,6 +146,9 @@ class RealESRGANer:
         else:
             self.device = torch.device("cuda" if torch.cuda.is_available() else "cpu") if device is None else device
         self.device = torch.device(self.device)
+        self.devices = parse_devices(devices, torch.cuda.device_count())
+        if self.devices is not None:
+            self.device = torch.device("cuda", self.devices[0])
 
         # where the weights came from: "verified" only for a file whose md5 is one the reference records
         self.weights_provenance = ("unverified", "in-memory state_dict (tests and benches use seeded synthetic weights: "
@@ -140,6 +178,8 @@ class RealESRGANer:
             # a tiling wrapper batches tiles of different shapes (ragged batches): a tile's values must not depend on how it
             # was batched, nor on whether model(tile) was called directly -- kernels are chosen by arithmetic only
             self.model.size_independent = True
+        if self._multi() and not self._hip_model():
+            raise ValueError("devices=: only the HIP networks (RRDBNet, SRVGGNetCompact) run on several devices at once")
 
     @staticmethod
     def _adapt_declared_scale(model, state):
@@ -224,13 +264,14 @@ class RealESRGANer:
             nb = self.model.preferred_batch(self.device, th, tw, nb)
         return nb
 
-    def run_tiles(self, img, tiles, sink):
-        """Evaluates the network on windows of `img` ([1,C,H,W] on self.device).  `tiles` is a list of
+    def run_tiles(self, img, tiles, sink, slot_base=0):
+        """Evaluates the network on windows of `img` ([1,C,H,W] on a device).  `tiles` is a list of
         (y0, y1, x0, x1, payload); `sink(payload, out)` receives each window's output [1,C,h*s,w*s] (a view
         valid on the current stream).  Equal-shaped windows are batched (batch_for); on the HIP backend
         the shape groups are spread over `tile_streams` streams with their own context replicas, so the
         small edge-tile groups -- whose 351 launches are latency-bound -- overlap the large ones.
-        Values do not depend on batching or stream assignment."""
+        Values do not depend on batching or stream assignment.  `slot_base`: the first context replica used (a lane of a
+        multi-device frame, see _tile_process_devices, takes slots slot_base, slot_base + 1, ...)."""
         groups = {}
         for t in tiles:
             groups.setdefault((t[1] - t[0], t[3] - t[2]), []).append(t)
@@ -239,7 +280,7 @@ class RealESRGANer:
         if hip and isinstance(self.model, RRDBNet) and img.shape[0] == 1 and self.model.compute_dtype in RAGGED_FORMS:
             ragged = self.model.strip_kernel_active() if self.ragged_tiles is None else bool(self.ragged_tiles)
             if ragged and (len(order) > 1 or self.ragged_tiles is None):
-                return self._run_tiles_ragged(img, tiles, sink, single_stream=self.ragged_tiles is None)
+                return self._run_tiles_ragged(img, tiles, sink, single_stream=self.ragged_tiles is None, slot_base=slot_base)
         # Batches of equal-shaped windows, one shape group per stream.  A small job (a rank's share of a sharded frame: five
         # tiles of an 8-way split 4K frame, often of one shape) is spread wider: every batch its own unit, the largest
         # halved until each of `small_job_streams` streams has one -- one stream would run 351 launches of a few hundred
@@ -273,7 +314,7 @@ class RealESRGANer:
             else:
                 inp = torch.cat([img[:, :, t[0]:t[1], t[2]:t[3]] for t in chunk], 0)
             with torch.no_grad():
-                out = self.model(inp, slot=slot) if hip else self.model(inp)
+                out = self.model(inp, slot=slot_base + slot) if hip else self.model(inp)
             for j, t in enumerate(chunk):
                 sink(t[4], out[j:j + 1] if len(chunk) > 1 else out)
 
@@ -284,9 +325,7 @@ class RealESRGANer:
                     run_batch(b, 0)
             return
         main = torch.cuda.current_stream(img.device)
-        if not hasattr(self, "_side_streams") or len(self._side_streams) < nstreams - 1:
-            self._side_streams = [torch.cuda.Stream(device=img.device) for _ in range(nstreams - 1)]
-        streams = [main] + self._side_streams[:nstreams - 1]
+        streams = [main] + self._side_streams_for(img.device, slot_base, nstreams - 1)
         for s in streams[1:]:
             s.wait_stream(main)                       # img / the output canvas were produced on the main stream
         load = [0] * nstreams
@@ -299,7 +338,21 @@ class RealESRGANer:
         for s in streams[1:]:
             main.wait_stream(s)
 
-    def _run_tiles_ragged(self, img, tiles, sink, single_stream=False):
+    def _side_streams_for(self, device, slot_base, n):
+        """The `n` side streams run_tiles spreads a call over: one list for the first device's first lane (the one-device
+        wrapper's), one per other (device, slot_base) lane of a multi-device frame."""
+        if slot_base == 0 and (not self._multi() or device.index == self.device.index):
+            if not hasattr(self, "_side_streams") or len(self._side_streams) < n:
+                self._side_streams = [torch.cuda.Stream(device=device) for _ in range(n)]
+            return self._side_streams[:n]
+        if not hasattr(self, "_lane_side_streams"):
+            self._lane_side_streams = {}
+        have = self._lane_side_streams.setdefault((device.index, slot_base), [])
+        while len(have) < n:
+            have.append(torch.cuda.Stream(device=device))
+        return have[:n]
+
+    def _run_tiles_ragged(self, img, tiles, sink, single_stream=False, slot_base=0):
         """All windows of a frame, whatever their shapes, in `tile_streams` ragged batches that run side by side: every
         window lies in the top-left corner of an equal-sized slot and the kernels take each image's own size from the
         call (nesr_forward_ragged).  Against one batch per tile shape: the small edge-tile groups were latency-bound
@@ -330,7 +383,7 @@ class RealESRGANer:
             for j, t in enumerate(chunk):
                 x[j, :, :t[1] - t[0], :t[3] - t[2]] = img[0, :, t[0]:t[1], t[2]:t[3]]
             with torch.no_grad():
-                out = self.model.forward_ragged(x, [(t[1] - t[0], t[3] - t[2]) for t in chunk], slot=slot)
+                out = self.model.forward_ragged(x, [(t[1] - t[0], t[3] - t[2]) for t in chunk], slot=slot_base + slot)
             s = out.shape[2] // H
             for j, t in enumerate(chunk):
                 sink(t[4], out[j:j + 1, :, :(t[1] - t[0]) * s, :(t[3] - t[2]) * s])
@@ -340,9 +393,7 @@ class RealESRGANer:
                 run_batch(chunk, 0)
             return
         main = torch.cuda.current_stream(img.device)
-        if not hasattr(self, "_side_streams") or len(self._side_streams) < nstreams - 1:
-            self._side_streams = [torch.cuda.Stream(device=img.device) for _ in range(nstreams - 1)]
-        streams = [main] + self._side_streams[:nstreams - 1]
+        streams = [main] + self._side_streams_for(img.device, slot_base, nstreams - 1)
         for st in streams[1:]:
             st.wait_stream(main)
         for k in range(nstreams):
@@ -356,6 +407,8 @@ class RealESRGANer:
     def tile_process(self):
         """Runs the network on overlapping tiles and pastes the un-padded centres (upstream
         semantics, tile for tile); see run_tiles for the batching / stream spreading."""
+        if self._multi():
+            return self._tile_process_devices()
         batch, channel, height, width = self.img.shape
         s = self.scale
         self.output = self.img.new_zeros((batch, channel, height * s, width * s))
@@ -366,6 +419,185 @@ class RealESRGANer:
             self.output[:, :, oy0:oy1, ox0:ox1] = out[:, :, cy0:cy1, cx0:cx1]
 
         self.run_tiles(self.img, tiles, paste)
+
+    # ------------------------------------------------------------------ several devices (devices=[...])
+    def _multi(self):
+        """Two or more entries in `devices`: tiles and frames are spread over them."""
+        return getattr(self, "devices", None) is not None and len(self.devices) > 1
+
+    def device_shares(self, height, width):
+        """(tiles, shares): upstream's tile grid of a height x width frame (the padded image the network sees) as
+        sharded.Tile records, and per entry of `devices` the indices of the tiles it computes -- sharded.plan_tiles with
+        world = len(devices): contiguous runs in row-major order, balanced by padded input area."""
+        from .sharded import plan_tiles
+        tiles, owner = plan_tiles(self, height, width, len(self.devices))
+        return tiles, [[i for i, o in enumerate(owner) if o == j] for j in range(len(self.devices))]
+
+    def _lanes(self):
+        """[(device, occurrence, stream)] per entry of `devices`: occurrence = earlier entries with the same index (it picks
+        the lane's context replicas).  The first entry runs on the caller's current stream, as the one-device wrapper does;
+        the others on streams of their own, kept across frames."""
+        if not hasattr(self, "_lane_streams"):
+            self._lane_streams = {}
+        lanes, seen = [], {}
+        for j, d in enumerate(self.devices):
+            dev = torch.device("cuda", d)
+            o = seen.get(d, 0)
+            seen[d] = o + 1
+            if j == 0:
+                st = torch.cuda.current_stream(dev)
+            else:
+                st = self._lane_streams.get(j)
+                if st is None:
+                    st = self._lane_streams[j] = torch.cuda.Stream(device=dev)
+            lanes.append((dev, o, st))
+        return lanes
+
+    def _gather_stream(self):
+        """A stream on the first device that carries the copies between devices, so they wait for no lane of that device."""
+        if getattr(self, "_gather", None) is None:
+            self._gather = torch.cuda.Stream(device=self.device)
+        return self._gather
+
+    def _send_home(self, flat, lane_stream, gather, items, dst):
+        """`flat` (contiguous, on a lane's device, written on `lane_stream`) -> one device-to-device copy to the first device
+        on `gather`, whose slices [offset, offset + numel) are then pasted into dst[index] (items: [(offset, shape, index)]).
+        Every tensor involved is used on the stream it was allocated on, so none has to outlive the call."""
+        with torch.cuda.stream(gather):
+            with torch.cuda.stream(lane_stream):
+                buf = torch.empty(flat.shape, dtype=flat.dtype, device=dst.device)
+                buf.copy_(flat, non_blocking=True)      # on the lane's stream, after its tiles; `gather` waits for it
+            for off, shape, index in items:
+                n = int(np.prod(shape))
+                dst[index] = buf[off:off + n].view(shape)
+
+    def _join_lanes(self, lanes, gather):
+        """Every device's current stream waits for the lanes on it (and the first device's for the copies home)."""
+        for dev, _, st in lanes:
+            cur = torch.cuda.current_stream(dev)
+            if st != cur:
+                cur.wait_stream(st)
+        torch.cuda.current_stream(self.device).wait_stream(gather)
+
+    @torch.no_grad()
+    def _tile_process_devices(self):
+        """tile_process with the tiles split over `devices`: every device gets the padded image (one copy from the first
+        device), runs its share through run_tiles on its lane's stream and replicas, and the un-padded centres come back to
+        self.output on the first device.  The first device's lanes paste straight into self.output."""
+        _, channel, height, width = self.img.shape
+        s = self.scale
+        dev0 = self.img.device
+        self.output = self.img.new_zeros((1, channel, height * s, width * s))
+        tiles, shares = self.device_shares(height, width)
+        lanes = self._lanes()
+        main = torch.cuda.current_stream(dev0)
+        gather = self._gather_stream()
+        gather.wait_stream(main)                        # the padded image and the output canvas
+        stride = max(1, int(self.tile_streams), int(self.small_job_streams))   # replicas one lane's run_tiles may use
+        imgs = {dev0.index: (self.img, None)}          # device index -> (the padded image there, event behind its copy)
+        for (dev, _, st), share in zip(lanes, shares):
+            if share and st != torch.cuda.current_stream(dev):
+                st.wait_stream(torch.cuda.current_stream(dev))   # the lane's replicas may still be in use there
+        for (dev, _, st), share in zip(lanes, shares):
+            if share and dev.index not in imgs:
+                with torch.cuda.stream(gather), torch.cuda.stream(st):
+                    img = self.img.to(dev, non_blocking=True)      # copied on `gather`; `st` waits for it (and so does `ev`)
+                    ev = torch.cuda.Event()
+                    ev.record(st)
+                imgs[dev.index] = (img, ev)
+        for (dev, o, st), share in zip(lanes, shares):
+            if not share:
+                continue
+            img, ev = imgs[dev.index]
+            with torch.cuda.device(dev), torch.cuda.stream(st):
+                if ev is not None:
+                    st.wait_event(ev)                   # every lane of the device, not only the one the copy was made for
+                    img.record_stream(st)               # read here after this call has returned: not freed before
+                if dev.index == dev0.index:
+                    pieces = None
+
+                    def sink(t, out):
+                        self.output[:, :, t.out[0]:t.out[1], t.out[2]:t.out[3]] = out[:, :, t.crop[0]:t.crop[1], t.crop[2]:t.crop[3]]
+                else:
+                    pieces = []
+
+                    def sink(t, out, pieces=pieces, st=st):
+                        p = out[:, :, t.crop[0]:t.crop[1], t.crop[2]:t.crop[3]].contiguous()   # on one of run_tiles' streams ...
+                        p.record_stream(st)                                                   # ... read on the lane's
+                        pieces.append((t, p))
+                self.run_tiles(img, [(t.inp[0], t.inp[1], t.inp[2], t.inp[3], t) for t in (tiles[i] for i in share)], sink,
+                               slot_base=o * stride)
+                if pieces:
+                    flat = torch.cat([p.reshape(-1) for _, p in pieces])
+                    items, off = [], 0
+                    for t, p in pieces:
+                        items.append((off, tuple(p.shape), (slice(None), slice(None), slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3]))))
+                        off += p.numel()
+                    self._send_home(flat, st, gather, items, self.output)
+        self._join_lanes(lanes, gather)
+
+    @torch.no_grad()
+    def _enhance_u8_tiles_fused_devices(self, img):
+        """_enhance_u8_tiles_fused with the tiles split over `devices`: the 8-bit frame goes to every device, each cuts, runs
+        and pastes its share (tiles_u8_on_device on its lane's stream and replica), the first device's lanes into the output
+        canvas, the others into a packed buffer that one device-to-device copy brings to the first device.  All devices are
+        enqueued before the frame is waited for; workspaces are reserved first, since growing one synchronises."""
+        h, w = img.shape[:2]
+        s = self.scale
+        dev0 = self.device
+        tiles, shares = self.device_shares(h, w)
+        lanes = self._lanes()
+        cap = max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))
+        for (dev, o, _), share in zip(lanes, shares):
+            for i in range(0, len(share), cap):
+                part = [tiles[k] for k in share[i:i + cap]]
+                self.model.reserve(dev, len(part), max(t.inp[1] - t.inp[0] for t in part), max(t.inp[3] - t.inp[2] for t in part), slot=o)
+        main = torch.cuda.current_stream(dev0)
+        gather = self._gather_stream()
+        pinned = torch.from_numpy(np.ascontiguousarray(img)).pin_memory()
+        canvas = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=dev0)
+        gather.wait_stream(main)
+        for (dev, _, st), share in zip(lanes, shares):
+            if share and st != torch.cuda.current_stream(dev):
+                st.wait_stream(torch.cuda.current_stream(dev))   # the canvas; the lane's replica may still be in use there
+        frames = {}                                     # device index -> (the frame there, event behind its upload)
+        for (dev, _, st), share in zip(lanes, shares):
+            if share and dev.index not in frames:
+                with torch.cuda.device(dev), torch.cuda.stream(st):
+                    f = pinned.to(dev, non_blocking=True)   # H2D: uint8 HWC BGR
+                    ev = torch.cuda.Event()
+                    ev.record(st)
+                frames[dev.index] = (f, ev)
+        for (dev, o, st), share in zip(lanes, shares):
+            if not share:
+                continue
+            mine = [tiles[i] for i in share]
+            windows = [(t.inp[0], t.inp[2], t.inp[1] - t.inp[0], t.inp[3] - t.inp[2]) for t in mine]
+            frame, ev = frames[dev.index]
+            with torch.cuda.device(dev), torch.cuda.stream(st):
+                st.wait_event(ev)
+                if dev.index == dev0.index:
+                    pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], (t.out[0] * w * s + t.out[2]) * 3, w * s * 3)
+                              for t in mine]
+                    self.tiles_u8_on_device(frame, windows, pastes, canvas, slot=o)
+                else:
+                    offs = [0]
+                    for t in mine:
+                        offs.append(offs[-1] + (t.out[1] - t.out[0]) * (t.out[3] - t.out[2]) * 3)
+                    packed = torch.empty((offs[-1],), dtype=torch.uint8, device=dev)
+                    pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], offs[i], (t.out[3] - t.out[2]) * 3)
+                              for i, t in enumerate(mine)]
+                    self.tiles_u8_on_device(frame, windows, pastes, packed, slot=o)
+                    items = [(offs[i], (t.out[1] - t.out[0], t.out[3] - t.out[2], 3), (slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3])))
+                             for i, t in enumerate(mine)]
+                    self._send_home(packed, st, gather, items, canvas)
+        self._join_lanes(lanes, gather)
+        host = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(canvas, non_blocking=True)
+        main.synchronize()                              # every lane and copy is behind it (_join_lanes)
+        del frames                                      # (read by every lane of their device: freed only now)
+        self._check_range()
+        return host.numpy()
 
     def post_process(self):
         if self.mod_scale is not None:
@@ -420,21 +652,23 @@ class RealESRGANer:
                 and self.model.out_scale() == self.scale)
 
     @torch.no_grad()
-    def tiles_u8_on_device(self, frame_u8, windows, pastes, dst_u8):
+    def tiles_u8_on_device(self, frame_u8, windows, pastes, dst_u8, slot=0):
         """frame_u8 [H, W, 3] uint8 on the device; windows [(y0, x0, h, w)] of the padded tiles; pastes [(crop_y, crop_x, h, w, dst byte
         offset, dst row pitch)] -> the tiles' quantised centres in dst_u8 (uint8, on the device).  Ragged batches of at most
-        RAGGED_MAX tiles: cut (nesr_cut_tiles_u8), forward_ragged, paste (nesr_paste_tiles_u8)."""
+        RAGGED_MAX tiles: cut (nesr_cut_tiles_u8), forward_ragged on context replica `slot`, paste (nesr_paste_tiles_u8)."""
         from .rrdbnet import cut_tiles_u8, paste_tiles_u8
         cap = max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))
         for i in range(0, len(windows), cap):
             win, pst = windows[i:i + cap], pastes[i:i + cap]
             hs, ws = max(v[2] for v in win), max(v[3] for v in win)
             x = cut_tiles_u8(frame_u8, win, (hs, ws), flip_rgb=True, through_fp16=bool(self.half))
-            out = self.model.forward_ragged(x, [(v[2], v[3]) for v in win])
+            out = self.model.forward_ragged(x, [(v[2], v[3]) for v in win], slot=slot)
             paste_tiles_u8(out, pst, dst_u8, flip_rgb=True, round_nearest=True, through_fp16=bool(self.half))
 
     @torch.no_grad()
     def _enhance_u8_tiles_fused(self, img):
+        if self._multi():
+            return self._enhance_u8_tiles_fused_devices(img)
         h, w = img.shape[:2]
         s = self.scale
         frame = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)          # H2D: uint8 HWC BGR
@@ -480,6 +714,8 @@ class RealESRGANer:
         that do not take the fused 8-bit path (tiling, padding, alpha, 16 bit) are processed one at a time.
         The results are identical to enhance()'s."""
         imgs = list(imgs)
+        if self._multi() and imgs and all(self._fused_u8_ok(i) for i in imgs):
+            return self._enhance_many_devices(imgs, max(1, int(inflight)))
         if inflight <= 1 or not imgs or not all(self._fused_u8_ok(i) for i in imgs):
             return [self.enhance(i) for i in imgs]
         streams = [torch.cuda.Stream(self.device) for _ in range(inflight)]
@@ -511,6 +747,76 @@ class RealESRGANer:
             finish(entry)
         for st in streams:
             caller.wait_stream(st)
+        return results
+
+    @torch.no_grad()
+    def _enhance_many_devices(self, imgs, inflight):
+        """enhance_many over `devices`: frame i to entry i % n, up to `inflight` frames in flight per entry, each on a stream of
+        its own and context replica occurrence * inflight + k of its device (k = the frame's place among the entry's in
+        flight).  Results in input order.  A frame whose persistent launch gave up is evaluated again by enhance(); after a
+        range error the frames still in flight are waited for and their contexts cleared before it is raised."""
+        from ._lib import NesrHipError, NesrRangeError
+        n = len(self.devices)
+        lanes, seen = [], {}
+        for d in self.devices:
+            dev = torch.device("cuda", d)
+            o = seen.get(d, 0)
+            seen[d] = o + 1
+            caller = torch.cuda.current_stream(dev)
+            sts = [torch.cuda.Stream(dev) for _ in range(inflight)]
+            for st in sts:
+                st.wait_stream(caller)     # the context workspaces may still be in use there
+            lanes.append((dev, o, sts))
+        results, pending = [None] * len(imgs), []
+
+        def finish(entry):
+            idx, host, ev, dev, slot, st = entry
+            ev.synchronize()
+            try:
+                with torch.cuda.device(dev), torch.cuda.stream(st):
+                    self.model.check_range(slot, device=dev)
+            except NesrRangeError:
+                raise
+            except NesrHipError as e:
+                if "gave up waiting" not in str(e):
+                    raise
+                warnings.warn(f"{e}; evaluating the frame again")
+                for other in pending:      # enhance() takes the first device's slot 0, which a frame in flight may hold
+                    other[2].synchronize()
+                results[idx] = self.enhance(imgs[idx])
+                return
+            results[idx] = (host.numpy().copy(), "RGB")
+
+        try:
+            for i, img in enumerate(imgs):
+                if len(pending) >= inflight * n:
+                    finish(pending.pop(0))
+                dev, o, sts = lanes[i % n]
+                k = (i // n) % inflight
+                st, slot = sts[k], o * inflight + k
+                with torch.cuda.device(dev), torch.cuda.stream(st):
+                    x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(dev, non_blocking=True)
+                    y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=slot)
+                    host = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True)
+                    host.copy_(y, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                pending.append((i, host, ev, dev, slot, st))
+            while pending:
+                finish(pending.pop(0))
+        except NesrHipError:
+            for entry in pending:          # the next frame starts clean on every device
+                entry[2].synchronize()
+                try:
+                    with torch.cuda.device(entry[3]), torch.cuda.stream(entry[5]):
+                        self.model.check_range(entry[4], device=entry[3])
+                except NesrHipError:
+                    pass
+            raise
+        finally:
+            for dev, _, sts in lanes:
+                for st in sts:
+                    torch.cuda.current_stream(dev).wait_stream(st)
         return results
 
     @torch.no_grad()

@@ -113,6 +113,7 @@ class RRDBNet(nn.Module):
         self._ctx = None          # (ctypes handle, device index, dtype code): slot 0
         self._dirty = True        # parameters changed since the last upload
         self._extra = {}          # slot -> (handle, device index, dtype code): replicas for concurrent streams
+        self._peers = {}          # (device index, slot) -> (handle, device index, dtype code): contexts on devices other than slot 0's
 
     # ------------------------------------------------------------------ parameters
     def _build_params(self):
@@ -163,9 +164,10 @@ class RRDBNet(nn.Module):
         if self._ctx is not None:
             _lib.load().nesr_destroy(self._ctx[0])
             self._ctx = None
-        for h in getattr(self, "_extra", {}).values():
+        for h in list(getattr(self, "_extra", {}).values()) + list(getattr(self, "_peers", {}).values()):
             _lib.load().nesr_destroy(h[0])
         self._extra = {}
+        self._peers = {}
         self._dirty = True
 
     def __del__(self):
@@ -207,17 +209,22 @@ class RRDBNet(nn.Module):
         return handle
 
     def _context(self, device: torch.device, slot: int = 0):
-        """HIP context of `slot`.  Slot 0 is the model's own; further slots are replicas (own packed
-        weights and workspace) so independent forward calls can run concurrently on different streams."""
+        """HIP context of (device, `slot`).  Slot 0 is the model's own; further slots are replicas (own packed
+        weights and workspace) so independent forward calls can run concurrently on different streams.  The device of the
+        first slot-0 context is the model's home; a call on another device gets that device's own contexts (_peer_context)
+        and leaves the home's in place, so one model can run on several devices at once."""
         lib = _lib.load()
         index = device.index if device.index is not None else torch.cuda.current_device()
         code = self._dtype_code()
-        if self._ctx is not None and (self._ctx[1] != index or self._ctx[2] != code):
+        if self._ctx is not None and self._ctx[2] != code:
             self._release()
-        if self._dirty and self._extra:
-            for h in self._extra.values():
+        if self._ctx is not None and self._ctx[1] != index:
+            return self._peer_context(index, code, slot)
+        if self._dirty and (self._extra or self._peers):
+            for h in list(self._extra.values()) + list(self._peers.values()):
                 lib.nesr_destroy(h[0])
             self._extra = {}
+            self._peers = {}
         if slot != 0:
             self._context(device, 0)   # slot 0 first: settles device / dtype / dirty state
             if slot not in self._extra:
@@ -236,6 +243,43 @@ class RRDBNet(nn.Module):
             self._dirty = False
         return self._ctx[0]
 
+    def _peer_context(self, index, code, slot):
+        """Context `slot` on device `index`, which is not the home device: created and given the weights once, then kept.
+        Several contexts on one device are marked concurrent (they exist to run beside each other), as the home's replicas are."""
+        lib = _lib.load()
+        home = torch.device("cuda", self._ctx[1])
+        with torch.cuda.device(home):
+            self._context(home, 0)      # settles dtype / dirty state: stale weights destroy the replicas and the peers
+        key = (index, slot)
+        if key not in self._peers:
+            handle = self._create(index, code)
+            self._upload(handle)
+            self._peers[key] = (handle, index, code)
+            # switches made on the model before this device was used hold here too
+            if getattr(self, "_fused_off", False):
+                _lib.check(lib.nesr_set_fused(handle, 0), "nesr_set_fused")
+            if getattr(self, "_kernel_timing", False):
+                _lib.check(lib.nesr_set_kernel_timing(handle, 1), "nesr_set_kernel_timing")
+            same = [h for k, h in self._peers.items() if k[0] == index]
+            if len(same) > 1:
+                for h in same:
+                    _lib.check(lib.nesr_set_concurrent(h[0], 1), "nesr_set_concurrent")
+        return self._peers[key][0]
+
+    def _handle(self, index, slot=0):
+        """(handle, device index, dtype code) of context (device `index`, `slot`), or None if it does not exist."""
+        if self._ctx is not None and self._ctx[1] == index:
+            return self._ctx if slot == 0 else self._extra.get(slot)
+        return self._peers.get((index, slot))
+
+    def reserve(self, device, n, h, w, slot=0):
+        """Creates context (device, `slot`) if needed and grows its workspace for a batch of n images of h x w input now
+        (nesr_reserve): a forward that has to grow it synchronises the device, which would serialise work enqueued on several."""
+        device = torch.device(device)
+        with torch.cuda.device(device):
+            ctx = self._context(device, slot)
+            _lib.check(_lib.load().nesr_reserve(ctx, int(n), int(h), int(w)), "nesr_reserve")
+
     RAGGED_MAX = 64          # images per forward_ragged call (nesr::RAG_MAX)
 
     @property
@@ -247,8 +291,7 @@ class RRDBNet(nn.Module):
     @size_independent.setter
     def size_independent(self, on):
         self._size_independent = bool(on)
-        handles = ([self._ctx] if self._ctx is not None else []) + list(self._extra.values())
-        for h in handles:
+        for h in self._handles():
             _lib.check(_lib.load().nesr_set_size_independent(h[0], 1 if on else 0), "nesr_set_size_independent")
 
     def strip_kernel_active(self):
@@ -385,9 +428,10 @@ class RRDBNet(nn.Module):
         return 2.0 * macs * px
 
     def set_kernel_timing(self, device, enable=True):
-        handles = [self._context(torch.device(device))] + [h[0] for h in self._extra.values()]
-        for ctx in handles:
-            _lib.check(_lib.load().nesr_set_kernel_timing(ctx, 1 if enable else 0), "nesr_set_kernel_timing")
+        self._context(torch.device(device))
+        self._kernel_timing = bool(enable)         # (also for contexts later created on other devices)
+        for h in self._handles():
+            _lib.check(_lib.load().nesr_set_kernel_timing(h[0], 1 if enable else 0), "nesr_set_kernel_timing")
 
     # ---- banded evaluation (banded.py: one row band of the frame per rank, SURVEY.md section 8(e) mode 2) ----
     @property
@@ -494,17 +538,20 @@ class RRDBNet(nn.Module):
             _lib.check(lib.nesr_band_rows(ctx, int(buffer), int(row0), rows.numel() // rb, ctypes.c_void_p(rows.data_ptr()), 1, stream), "nesr_band_rows")
 
     def _handles(self):
-        return ([self._ctx] if self._ctx is not None else []) + list(self._extra.values())
+        """Every context of the model: home slot 0, the home's replicas, then the other devices' contexts."""
+        return ([self._ctx] if self._ctx is not None else []) + list(self._extra.values()) + list(getattr(self, "_peers", {}).values())
 
     def set_fused(self, on: bool):
         """Persistent (fused) dense-block launches on / off for every context of this model (include/nesr_hip.h: nesr_set_fused).
-        They switch themselves off after a forward that gave up waiting (NesrHipError at check_range / check_status)."""
+        They switch themselves off after a forward that gave up waiting (NesrHipError at check_range / check_status).
+        Contexts the model later creates on another device (_peer_context) start with the same setting."""
+        self._fused_off = not on
         for h in self._handles():
             _lib.check(_lib.load().nesr_set_fused(h[0], 1 if on else 0), "nesr_set_fused")
 
-    def fused_state(self, slot=0):
-        """(persistent launches enabled, forwards that gave up so far) of a context."""
-        h = self._ctx if slot == 0 else self._extra.get(slot)
+    def fused_state(self, slot=0, device=None):
+        """(persistent launches enabled, forwards that gave up so far) of a context (`device`: None = the home device)."""
+        h = (self._ctx if slot == 0 else self._extra.get(slot)) if device is None else self._handle(torch.device(device).index, slot)
         if h is None:
             return False, 0
         v = int(_lib.load().nesr_fused_state(h[0]))
@@ -519,7 +566,7 @@ class RRDBNet(nn.Module):
         """Hint for kernel selection: forwards of this model's contexts run beside each other on several streams
         (set automatically when a context replica is created; clear it to time one forward alone)."""
         lib = _lib.load()
-        for h in ([self._ctx] if self._ctx is not None else []) + list(self._extra.values()):
+        for h in self._handles():
             _lib.check(lib.nesr_set_concurrent(h[0], 1 if concurrent else 0), "nesr_set_concurrent")
 
     def preferred_batch(self, device, h, w, max_batch):
@@ -528,25 +575,43 @@ class RRDBNet(nn.Module):
         return max(1, int(_lib.load().nesr_preferred_batch(ctx, h, w, max_batch)))
 
     def check_status(self):
-        """Synchronises the device and raises if asynchronous work of this model failed."""
-        if self._ctx is not None:
-            _lib.check(_lib.load().nesr_check_status(self._ctx[0]), "nesr_check_status")
+        """Synchronises every device the model has a context on and raises if asynchronous work of this model failed."""
+        seen = set()
+        for h in self._handles():
+            if h[1] not in seen:
+                seen.add(h[1])
+                _lib.check(_lib.load().nesr_check_status(h[0]), "nesr_check_status")
         self.check_range()
 
-    def check_range(self, slot=None):
+    def check_range(self, slot=None, device=None):
         """Raises NesrRangeError if a forward enqueued so far (on torch's current stream) met an input or activation
         the f16-pair fp32 form or the f16 form cannot carry (non-finite or beyond +-65504): its float output is NaN and an 8-bit
         output is invalid.  Waits for the current stream only; a no-op for the other compute dtypes.  The wrappers
-        call it after every device-to-host copy (the reference would have returned NaN pixels, nesr/nesr.py:891-898)."""
-        handles = ([self._ctx] if self._ctx is not None else []) + list(self._extra.values()) if slot is None else \
-                  [self._ctx if slot == 0 else self._extra.get(slot)]
+        call it after every device-to-host copy (the reference would have returned NaN pixels, nesr/nesr.py:891-898).
+        Covers every context of every device, the home device's `slot`, or with `device` that device's contexts (all, or
+        `slot`).  Every covered context is checked and cleared before the first failure is raised (a range error before a
+        persistent launch that gave up), so the next forward starts clean on all of them."""
+        if device is not None:
+            index = torch.device(device).index
+            handles = [h for h in self._handles() if h[1] == index] if slot is None else [self._handle(index, slot)]
+        elif slot is None:
+            handles = self._handles()
+        else:
+            handles = [self._ctx if slot == 0 else self._extra.get(slot)]
         lib = _lib.load()
+        first = None
         for h in handles:
             if h is None or h[2] not in (_lib.DTYPE_F32_SPLIT, _lib.DTYPE_BF16, _lib.DTYPE_F16):   # the forms with a range word or persistent launches
                 continue
             dev = torch.device("cuda", h[1])
             with torch.cuda.device(dev):
-                _lib.check(lib.nesr_check_range(h[0], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "nesr_check_range")
+                try:
+                    _lib.check(lib.nesr_check_range(h[0], ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "nesr_check_range")
+                except _lib.NesrHipError as e:
+                    if first is None or (isinstance(e, _lib.NesrRangeError) and not isinstance(first, _lib.NesrRangeError)):
+                        first = e
+        if first is not None:
+            raise first
 
     def kernel_time(self):
         """(total ms, launches, algorithmic flops) of the dense-block convs since the last call."""
@@ -555,7 +620,7 @@ class RRDBNet(nn.Module):
         tot_ms, tot_n, tot_fl = 0.0, 0, 0.0
         # replicas run on concurrent streams: their brackets overlap in wall time, so the sum of the
         # bracketed times is an upper bound of the busy time (the derived TFLOP/s a lower bound)
-        for h in [self._ctx] + list(self._extra.values()):
+        for h in self._handles():
             ms, n, fl = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
             _lib.check(_lib.load().nesr_kernel_time_ms(h[0], ctypes.byref(ms), ctypes.byref(n), ctypes.byref(fl)),
                        "nesr_kernel_time_ms")

@@ -99,6 +99,7 @@ class SRVGGNetCompact(nn.Module):
         self._ctx = None          # (ctypes handle, device index, dtype code): slot 0
         self._dirty = True
         self._extra = {}          # slot -> replica context for concurrent streams
+        self._peers = {}          # (device index, slot) -> context on a device other than slot 0's
 
     def _act(self):
         return _PReLUParams(self.num_feat) if self.act_type == "prelu" else _NoParams()
@@ -108,6 +109,10 @@ class SRVGGNetCompact(nn.Module):
     __del__ = RRDBNet.__del__
     _upload = RRDBNet._upload
     _context = RRDBNet._context
+    _peer_context = RRDBNet._peer_context
+    _handle = RRDBNet._handle
+    _handles = RRDBNet._handles
+    reserve = RRDBNet.reserve
     check_status = RRDBNet.check_status
     check_range = RRDBNet.check_range
     kernel_time = RRDBNet.kernel_time
@@ -182,6 +187,7 @@ class SRVGGNetCompact(nn.Module):
         return 2.0 * macs * n * h * w
 
     def set_kernel_timing(self, device, enable=True):
-        handles = [self._context(torch.device(device))] + [h[0] for h in self._extra.values()]
-        for ctx in handles:
-            _lib.check(_lib.load().nesr_set_kernel_timing(ctx, 1 if enable else 0), "nesr_set_kernel_timing")
+        self._context(torch.device(device))
+        self._kernel_timing = bool(enable)
+        for h in self._handles():
+            _lib.check(_lib.load().nesr_set_kernel_timing(h[0], 1 if enable else 0), "nesr_set_kernel_timing")
