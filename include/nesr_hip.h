@@ -297,9 +297,9 @@ int nesr_shard_plan(int H, int W, int scale, int tile, int tile_pad, int nranks,
  * the non-local means inside `cv2.fastNlMeansDenoisingColored(image, None, h, h, 7, 21)` of
  * SuperResolutionPipeline._preprocess_image (nesr/nesr.py:674), on [C, H, W] u8 planes taken as ONE C-channel image (C = 1: the L
  * plane, C = 2: the a and b planes).  weights_dev: int32 table over the binned ("almost", >> 6) template distance,
- * round(M exp(-d / (h^2 C))) with OpenCV's fixed-point M, 0 below M / 1000 (imgproc.nl_means_weights builds it).  The Lab
- * conversions around it stay torch operations (imgproc.py).  Parity unpinned against cv2 (absent): checked against
- * oracle/cv2_ref.py, a restatement of OpenCV's invoker.
+ * round(M exp(-d / (h^2 C))) with OpenCV's fixed-point M, 0 below M / 1000 (nesr_nl_means_weights or imgproc.nl_means_weights
+ * builds it).  The Lab conversions around it: nesr_lab_u8; the whole pre-filter: nesr_preprocess_u8.  Parity unpinned against cv2
+ * (absent): checked against oracle/cv2_ref.py, a restatement of OpenCV's invoker.
  */
 int nesr_nl_means_u8(int device_id, const uint8_t* planes_dev, int C, int H, int W, int template_size, int search_size, const int* weights_dev, int nbins,
                      uint8_t* out_dev, void* hip_stream);
@@ -313,6 +313,59 @@ int nesr_nl_means_u8(int device_id, const uint8_t* planes_dev, int C, int H, int
  */
 int nesr_clahe_u8(int device_id, const uint8_t* gray_dev, int H, int W, double clip_limit, int grid_x, int grid_y, float* lut_dev, uint8_t* out_dev,
                   void* hip_stream);
+
+/*
+ * The rest of SuperResolutionPipeline._preprocess_image (nesr/nesr.py:668-689) and all of _postprocess_image (nesr/nesr.py:1056-1084)
+ * as HIP kernels (csrc/filters.hip), for a host without torch.  Each entry is bit for bit the torch function of imgproc.py named
+ * below (tests/test_gpu_filters_hip.py); parity against cv2 is unpinned (cv2 is absent): checked against oracle/cv2_ref.py, a
+ * restatement of OpenCV's algorithms.  None of the argument checks touches a device; a bad argument returns NESR_ERR_ARG.
+ *
+ * nesr_lab_u8: cv2.cvtColor(COLOR_RGB2Lab | COLOR_Lab2RGB | COLOR_LBGR2Lab | COLOR_Lab2LBGR | ...) on u8 (L 255/100, a + 128,
+ * b + 128) -- imgproc.rgb2lab_u8 / lab2rgb_u8; the reference calls them inside fastNlMeansDenoisingColored (nesr/nesr.py:674) and
+ * around its CLAHE (nesr/nesr.py:680, 685).  mode = NESR_LAB_* bits: FROM_LAB (Lab -> RGB; else RGB -> Lab), LINEAR (no sRGB gamma),
+ * FIRST_IS_BLUE (channel 0 is blue), PLANAR (the Lab side is [3, H, W] planes; the RGB side is always HWC).  src == dst is allowed
+ * without PLANAR only.
+ */
+enum { NESR_LAB_FROM_LAB = 1, NESR_LAB_LINEAR = 2, NESR_LAB_FIRST_IS_BLUE = 4, NESR_LAB_PLANAR = 8 };
+int nesr_lab_u8(int device_id, const uint8_t* src_dev, int H, int W, int mode, uint8_t* dst_dev, void* hip_stream);
+
+/*
+ * cv2.GaussianBlur(img, (ksize, ksize) or (0, 0), sigma) on [H, W, C] u8, C = 1 or 3 -- imgproc.gaussian_blur_u8, used twice by
+ * _postprocess_image (nesr/nesr.py:1063, 1068): OpenCV's 8-bit fixed-point taps (nesr_gaussian_taps), a separable filter with int32
+ * sums, BORDER_REFLECT_101, one rounding (v + 2^15) >> 16.  ksize 0 = round(6 sigma + 1) | 1; the kernel must be odd and at most
+ * 31 taps.  src_dev != dst_dev.
+ */
+int nesr_gaussian_u8(int device_id, const uint8_t* src_dev, int H, int W, int C, double sigma, int ksize, uint8_t* dst_dev, void* hip_stream);
+
+/* Host only: the integer taps of that blur -- imgproc.gaussian_kernel_u8 (OpenCV's tabulated small kernels for sigma <= 0, else the
+ * sampled Gaussian normalised in double, x256 rounded, the centre tap making the sum 256).  *n is always set; taps[0 .. *n) is filled
+ * when cap >= *n. */
+int nesr_gaussian_taps(double sigma, int ksize, int* taps, int cap, int* n);
+
+/* Host only: the weight table of nesr_nl_means_u8 for C channels and strength h -- imgproc.nl_means_weights (OpenCV's
+ * almost_dist2weight, round(M exp(-d / (h^2 C))) with M = INT_MAX / (search^2 255), 0 below M / 1000, over bins of the template
+ * distance >> shift).  *nbins and *shift are always set; table[0 .. *nbins) is filled when cap >= *nbins. */
+int nesr_nl_means_weights(int C, double h, int template_size, int search_size, int* table, int cap, int* nbins, int* shift);
+
+/*
+ * _preprocess_image (nesr/nesr.py:668-689) on [H, W, 3] u8 RGB -- imgproc.preprocess_image: when denoise_level > 0,
+ * fastNlMeansDenoisingColored(img, None, 10 denoise_level, 10 denoise_level, 7, 21) (LBGR -> Lab planes, nesr_nl_means_u8 on L and on
+ * ab, Lab -> LBGR fused with the following RGB -> Lab); then CLAHE (clip 2.0, 8 x 8 tiles; nesr_clahe_u8) on L, Lab -> RGB.  All of it
+ * is enqueued on hip_stream with no allocation, no synchronisation and no copy, except the first call for a (device, channels, h),
+ * which builds the NL-means weight tables on the host and uploads them once (kept for the process).  scratch_dev: at least
+ * nesr_preprocess_scratch_bytes(H, W) = 2 * round_up(3 H W, 256) + 65536 bytes of device memory.  rgb_dev == out_dev is allowed.
+ */
+size_t nesr_preprocess_scratch_bytes(int H, int W);
+int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, double denoise_level, void* scratch_dev, size_t scratch_bytes,
+                       uint8_t* out_dev, void* hip_stream);
+
+/*
+ * _postprocess_image (nesr/nesr.py:1056-1084) on [H, W, 3] u8 RGB -- imgproc.postprocess_image: where the detail
+ * saturate(gray - GaussianBlur(gray, sigma 2)) exceeds 10 the pixel becomes saturate(round(1.5 x - 0.5 GaussianBlur(x, sigma 3))),
+ * elsewhere it stays; one launch.  adaptive_sharpening = 0: out = the input (a copy on hip_stream unless rgb_dev == out_dev).
+ * rgb_dev != out_dev when sharpening.
+ */
+int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int adaptive_sharpening, uint8_t* out_dev, void* hip_stream);
 
 /*
  * Single-layer entry (test hook for the per-layer parity tests): one 3x3 stride-1 zero-pad-1

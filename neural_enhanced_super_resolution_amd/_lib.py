@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT, DTYPE_F16 = 0, 1, 2, 3, 4
 ROUND_TRUNC, ROUND_NEAREST = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
+LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
 
 # name -> (restype, argtypes); must list every symbol include/nesr_hip.h declares
 _c = ctypes
@@ -61,6 +62,14 @@ SIGNATURES = {
                                    _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int)]),
     "nesr_nl_means_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_clahe_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "nesr_lab_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "nesr_gaussian_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "nesr_gaussian_taps": (_c.c_int, [_c.c_double, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_nl_means_weights": (_c.c_int, [_c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int),
+                                         _c.POINTER(_c.c_int)]),
+    "nesr_preprocess_scratch_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "nesr_preprocess_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
+    "nesr_postprocess_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_last_error": (_c.c_char_p, []),

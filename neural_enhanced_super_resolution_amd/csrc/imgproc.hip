@@ -103,13 +103,6 @@ hipError_t launch_nl_means(const uint8_t* src, int C, int H, int W, const int* l
 // half to even), so the two agree bit for bit (tests/test_gpu_filters.py).  Byte work: one read of the plane per launch, one write.
 namespace {
 
-// single-precision operations that round by themselves: hipcc contracts a * b + c into an fma also when it is spelled
-// __fadd_rn(__fmul_rn(a, b), c) (and `#pragma clang fp contract(off)` does not reach those intrinsics), the torch
-// operations this replaces are separate kernels and never do
-__device__ __forceinline__ float mul_rn(float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
-
 __global__ __launch_bounds__(256) void clahe_lut_kernel(const uint8_t* __restrict__ src, int h, int w, int th, int tw, int gx, int clip, float scale,
                                                        float* __restrict__ lut) {
     __shared__ int hist[256];

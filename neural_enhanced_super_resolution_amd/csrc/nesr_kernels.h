@@ -8,6 +8,13 @@
 
 namespace nesr {
 
+// Single-precision operations that round by themselves, for kernels that restate a chain of torch operations bit for bit
+// (imgproc.hip, filters.hip): hipcc contracts a * b + c into an fma also when it is spelled __fadd_rn(__fmul_rn(a, b), c) (and
+// `#pragma clang fp contract(off)` does not reach those intrinsics); the torch operations are separate kernels and never do.
+__device__ __forceinline__ float mul_rn(float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
 // Activation addressing.  Channels are grouped in K-groups of KG channels (8 for f32, 16 for
 // bf16 = 32 bytes, one MFMA K-chunk); element (pixel p, channel c) of a feature map lives at
 //     base + (c / KG) * chunk + p * pix + (c % KG)          (in elements)
@@ -238,6 +245,32 @@ hipError_t launch_nl_means(const uint8_t* src, int C, int H, int W, const int* l
 // scale = 255 / (th * tw), inv_th / inv_tw = 1 / th, 1 / tw as floats; lut: gx * gy * 256 floats of device scratch
 hipError_t launch_clahe(const uint8_t* src, int h, int w, int gx, int gy, int th, int tw, int clip, float scale, float inv_th, float inv_tw, float* lut,
                         uint8_t* dst, hipStream_t s);
+
+// Lab conversions (filters.hip): channel c of pixel i at src[c][i * src_step] (HWC: base + c, step 3; planar: plane c, step 1); mode0 then,
+// unless negative, mode1 on the u8 result (NESR_LAB_* bits without NESR_LAB_PLANAR)
+struct LabArgs {
+    const uint8_t* src[3];
+    uint8_t* dst[3];
+    size_t n;
+    int src_step, dst_step;
+    int mode0, mode1;
+};
+hipError_t launch_lab(const LabArgs& a, hipStream_t s);
+
+// cv2.GaussianBlur's 8-bit fixed-point path on HWC u8 (filters.hip): k[0 .. 2r] integer taps summing to 256, C = 1 or 3, dst != src
+constexpr int GAUSS_MAX_RADIUS = 15;
+struct GaussTaps {
+    int r;
+    int k[2 * GAUSS_MAX_RADIUS + 1];
+};
+hipError_t launch_gaussian(const uint8_t* src, int H, int W, int C, const GaussTaps& taps, uint8_t* dst, hipStream_t s);
+
+// the adaptive unsharp mask of _postprocess_image on HWC RGB u8 (filters.hip): taps of the sigma 2 and sigma 3 blurs, dst != src
+struct SharpenTaps {
+    int k2[13];
+    int k3[19];
+};
+hipError_t launch_postprocess(const uint8_t* src, int H, int W, const SharpenTaps& taps, uint8_t* dst, hipStream_t s);
 
 // feature map (channels [0,c)) -> planar f32 NCHW; used by the single-layer test hook
 hipError_t launch_nhwc_to_nchw(const void* src, int kind /* as PackArgs::bf16 */, Map map, int n, int c, int h, int w, float* dst, hipStream_t s);

@@ -24,6 +24,33 @@ import torch
 from torch.nn import functional as F
 
 
+def _hip_default(x):
+    """use_hip=None: the HIP kernels for a uint8 tensor on the ROCm device."""
+    return x.device.type == "cuda" and x.dtype == torch.uint8
+
+
+def _hip_require(x, layout_ok, what, layout):
+    """use_hip=True on a tensor the kernel cannot take: an error, never a launch on a wrong buffer."""
+    if x.device.type != "cuda" or x.dtype != torch.uint8 or not layout_ok:
+        raise ValueError(f"{what}: the HIP kernel takes a uint8 {layout} tensor on the ROCm device, got {x.dtype} "
+                         f"{tuple(x.shape)} on {x.device}")
+
+
+def _hip_call(x, name, *args):
+    """libnesr_hip.so entry `name`(device, *args, stream) on x's device and current stream; raises on failure."""
+    import ctypes
+    from . import _lib
+    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(getattr(_lib.load(), name)(index, *args, ctypes.c_void_p(stream)), name)
+
+
+def _ptr(t):
+    import ctypes
+    return ctypes.c_void_p(t.data_ptr())
+
+
 # ----------------------------------------------------------------------------------------------- resize
 def _lanczos4_coeffs(frac):
     """cv2 interpolateLanczos4 for a float32 tensor of fractional offsets -> [..., 8] float32 weights."""
@@ -125,10 +152,23 @@ def gaussian_kernel_u8(sigma, ksize=0):
     return q
 
 
-def gaussian_blur_u8(img, sigma, ksize=0):
+def gaussian_blur_u8(img, sigma, ksize=0, use_hip=None):
     """cv2.GaussianBlur(img, (ksize, ksize) or (0, 0), sigma) on HWC (or HW) uint8: separable fixed-point filter,
-    BORDER_REFLECT_101, one rounding at the end ((v + 2^15) >> 16)."""
+    BORDER_REFLECT_101, one rounding at the end ((v + 2^15) >> 16).  On a ROCm device one HIP kernel (csrc/filters.hip,
+    nesr_gaussian_u8: 1 or 3 channels, an odd kernel of at most 31 taps) unless use_hip=False selects the torch composition
+    below -- the two agree bit for bit."""
     squeeze = img.dim() == 2
+    if use_hip is None:
+        n = ksize if ksize > 0 else int(round(sigma * 6 + 1)) | 1
+        use_hip = _hip_default(img) and (squeeze or (img.dim() == 3 and img.shape[-1] in (1, 3))) and 1 <= n <= 31 and n % 2 == 1
+    if use_hip:
+        _hip_require(img, squeeze or (img.dim() == 3 and img.shape[-1] in (1, 3)), "gaussian_blur_u8", "[H, W], [H, W, 1] or [H, W, 3]")
+        src = img.contiguous()
+        out = torch.empty_like(src)
+        if src.numel():
+            _hip_call(src, "nesr_gaussian_u8", _ptr(src), src.shape[0], src.shape[1], 1 if squeeze else src.shape[2], float(sigma), int(ksize),
+                      _ptr(out))
+        return out
     x = (img[:, :, None] if squeeze else img).permute(2, 0, 1).unsqueeze(0)
     k = gaussian_kernel_u8(sigma, ksize).to(img.device)
     r = k.numel() // 2
@@ -167,9 +207,36 @@ def _linear_to_srgb(c):
     return torch.where(c <= 0.0031308, c * 12.92, 1.055 * torch.pow(c.clamp_min(1e-12), 1.0 / 2.4) - 0.055)
 
 
-def rgb2lab_u8(img, linear=False, first_is_blue=False):
+def _lab_hip(x, mode, planar_in):
+    """nesr_lab_u8 on an [H, W, 3] tensor (planar_in: a [3, H, W] one) -> the other layout when mode has LAB_PLANAR."""
+    from . import _lib
+    what = "lab2rgb_u8" if mode & _lib.LAB_FROM_LAB else "rgb2lab_u8"
+    if planar_in:
+        _hip_require(x, x.dim() == 3 and x.shape[0] == 3, what, "[3, H, W] (planar=True)")
+    else:
+        _hip_require(x, x.dim() == 3 and x.shape[-1] == 3, what, "[H, W, 3]")
+    src = x.contiguous()
+    h, w = src.shape[1:] if planar_in else src.shape[:2]
+    shape = (h, w, 3) if planar_in or not mode & _lib.LAB_PLANAR else (3, h, w)
+    out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    if src.numel():
+        _hip_call(src, "nesr_lab_u8", _ptr(src), h, w, mode, _ptr(out))
+    return out
+
+
+def rgb2lab_u8(img, linear=False, first_is_blue=False, use_hip=None, planar=False):
     """cv2.cvtColor(img, COLOR_RGB2Lab | COLOR_LRGB2Lab | COLOR_LBGR2Lab) on uint8 -> uint8 (L 255/100, a + 128, b + 128).
-    linear=True: no sRGB gamma (the L* variants); first_is_blue=True: channel 0 is taken as blue (the *BGR* variants)."""
+    linear=True: no sRGB gamma (the L* variants); first_is_blue=True: channel 0 is taken as blue (the *BGR* variants);
+    planar=True: an [H, W, 3] image -> [3, H, W] planes.  On a ROCm device one HIP kernel (csrc/filters.hip, nesr_lab_u8)
+    unless use_hip=False selects the torch composition below -- the two agree bit for bit."""
+    if use_hip is None:
+        use_hip = _hip_default(img) and img.dim() == 3 and img.shape[-1] == 3
+    if use_hip:
+        from . import _lib
+        return _lab_hip(img, (_lib.LAB_LINEAR if linear else 0) | (_lib.LAB_FIRST_IS_BLUE if first_is_blue else 0)
+                        | (_lib.LAB_PLANAR if planar else 0), False)
+    if planar:
+        return rgb2lab_u8(img, linear, first_is_blue, use_hip=False).permute(2, 0, 1).contiguous()
     c = img.float() / 255.0
     if not linear:
         c = _srgb_to_linear(c)
@@ -185,8 +252,17 @@ def rgb2lab_u8(img, linear=False, first_is_blue=False):
     return torch.round(out).clamp_(0, 255).to(torch.uint8)
 
 
-def lab2rgb_u8(lab, linear=False, first_is_blue=False):
-    """cv2.cvtColor(lab, COLOR_Lab2RGB | COLOR_Lab2LRGB | COLOR_Lab2LBGR) on uint8 -> uint8."""
+def lab2rgb_u8(lab, linear=False, first_is_blue=False, use_hip=None, planar=False):
+    """cv2.cvtColor(lab, COLOR_Lab2RGB | COLOR_Lab2LRGB | COLOR_Lab2LBGR) on uint8 -> uint8; planar=True: [3, H, W] Lab
+    planes -> an [H, W, 3] image.  HIP on a ROCm device (nesr_lab_u8) unless use_hip=False, as rgb2lab_u8."""
+    if use_hip is None:
+        use_hip = _hip_default(lab) and lab.dim() == 3 and lab.shape[0 if planar else -1] == 3
+    if use_hip:
+        from . import _lib
+        return _lab_hip(lab, _lib.LAB_FROM_LAB | (_lib.LAB_LINEAR if linear else 0) | (_lib.LAB_FIRST_IS_BLUE if first_is_blue else 0)
+                        | (_lib.LAB_PLANAR if planar else 0), planar)
+    if planar:
+        return lab2rgb_u8(lab.permute(1, 2, 0), linear, first_is_blue, use_hip=False)
     x = lab.float()
     L = x[..., 0] * 100.0 / 255.0
     a = x[..., 1] - 128.0
@@ -370,37 +446,61 @@ def fast_nl_means_u8(planes, h, template=7, search=21, rows_per_block=0, use_hip
     return out.clamp_(0, 255).to(torch.uint8)
 
 
-def fast_nl_means_colored_u8(img, h, h_color, template=7, search=21):
+def fast_nl_means_colored_u8(img, h, h_color, template=7, search=21, use_hip=None):
     """cv2.fastNlMeansDenoisingColored(img, None, h, hColor, template, search): COLOR_LBGR2Lab (no gamma, channel 0 taken
     as blue -- whatever order the caller's image is in: the reference hands it RGB, nesr/nesr.py:674), non-local means on
-    L with h and on (a, b) with hColor, COLOR_Lab2LBGR."""
-    lab = rgb2lab_u8(img, linear=True, first_is_blue=True)
-    p = lab.permute(2, 0, 1).contiguous()
-    L = fast_nl_means_u8(p[0:1], h, template, search)
-    ab = fast_nl_means_u8(p[1:3], h_color, template, search)
-    return lab2rgb_u8(torch.cat([L, ab], 0).permute(1, 2, 0), linear=True, first_is_blue=True)
+    L with h and on (a, b) with hColor, COLOR_Lab2LBGR.  use_hip goes to every step."""
+    p = rgb2lab_u8(img, linear=True, first_is_blue=True, use_hip=use_hip, planar=True)
+    L = fast_nl_means_u8(p[0:1], h, template, search, use_hip=use_hip)
+    ab = fast_nl_means_u8(p[1:3], h_color, template, search, use_hip=use_hip)
+    return lab2rgb_u8(torch.cat([L, ab], 0), linear=True, first_is_blue=True, use_hip=use_hip, planar=True)
 
 
 # ----------------------------------------------------------------------------------------------- the pipeline's filters
-def preprocess_image(img, denoise_level=0.5):
-    """SuperResolutionPipeline._preprocess_image (nesr/nesr.py:668-689) on an HWC uint8 RGB device tensor."""
+def preprocess_image(img, denoise_level=0.5, use_hip=None):
+    """SuperResolutionPipeline._preprocess_image (nesr/nesr.py:668-689) on an HWC uint8 RGB device tensor.  On a ROCm device
+    one C call (nesr_preprocess_u8: the Lab, NL-means and CLAHE kernels in stream order, device scratch from here) unless
+    use_hip=False selects the torch chain below, every step of it torch -- the two agree bit for bit."""
+    if use_hip is None:
+        use_hip = _hip_default(img) and img.dim() == 3 and img.shape[-1] == 3
+    if use_hip:
+        from . import _lib
+        _hip_require(img, img.dim() == 3 and img.shape[-1] == 3, "preprocess_image", "[H, W, 3]")
+        src = img.contiguous()
+        h, w = src.shape[:2]
+        out = torch.empty_like(src)
+        if src.numel():
+            nbytes = _lib.load().nesr_preprocess_scratch_bytes(h, w)
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=src.device)
+            _hip_call(src, "nesr_preprocess_u8", _ptr(src), h, w, float(denoise_level), _ptr(scratch), nbytes, _ptr(out))
+        return out
     if denoise_level > 0:
         strength = denoise_level * 10
-        img = fast_nl_means_colored_u8(img, strength, strength, 7, 21)
-    lab = rgb2lab_u8(img)                                                            # COLOR_RGB2LAB
-    L = clahe_u8(lab[..., 0].contiguous(), 2.0, (8, 8))
+        img = fast_nl_means_colored_u8(img, strength, strength, 7, 21, use_hip=False)
+    lab = rgb2lab_u8(img, use_hip=False)                                             # COLOR_RGB2LAB
+    L = clahe_u8(lab[..., 0].contiguous(), 2.0, (8, 8), use_hip=False)
     lab = torch.cat([L[..., None], lab[..., 1:]], -1)
-    return lab2rgb_u8(lab)                                                           # COLOR_LAB2RGB
+    return lab2rgb_u8(lab, use_hip=False)                                            # COLOR_LAB2RGB
 
 
-def postprocess_image(img, adaptive_sharpening=True):
+def postprocess_image(img, adaptive_sharpening=True, use_hip=None):
     """SuperResolutionPipeline._postprocess_image (nesr/nesr.py:1056-1084): unsharp (1.5 img - 0.5 blur_3) where the local
-    detail |gray - blur_2(gray)| exceeds 10, the image itself elsewhere."""
+    detail |gray - blur_2(gray)| exceeds 10, the image itself elsewhere.  On a ROCm device one fused HIP kernel
+    (csrc/filters.hip, nesr_postprocess_u8) unless use_hip=False selects the torch chain below -- the two agree bit for bit."""
     if not adaptive_sharpening:
         return img
+    if use_hip is None:
+        use_hip = _hip_default(img) and img.dim() == 3 and img.shape[-1] == 3
+    if use_hip:
+        _hip_require(img, img.dim() == 3 and img.shape[-1] == 3, "postprocess_image", "[H, W, 3]")
+        src = img.contiguous()
+        out = torch.empty_like(src)
+        if src.numel():
+            _hip_call(src, "nesr_postprocess_u8", _ptr(src), src.shape[0], src.shape[1], 1, _ptr(out))
+        return out
     gray = rgb2gray_u8(img)
-    variance = (gray.to(torch.int16) - gaussian_blur_u8(gray, 2.0).to(torch.int16)).clamp_(0, 255)   # cv2.subtract saturates; convertScaleAbs keeps it
-    blurred = gaussian_blur_u8(img, 3.0)
+    variance = (gray.to(torch.int16) - gaussian_blur_u8(gray, 2.0, use_hip=False).to(torch.int16)).clamp_(0, 255)   # cv2.subtract saturates; convertScaleAbs keeps it
+    blurred = gaussian_blur_u8(img, 3.0, use_hip=False)
     sharpened = torch.round(img.float() * 1.5 - blurred.float() * 0.5).clamp_(0, 255).to(torch.uint8)   # addWeighted: saturate_cast<uchar>
     mask = (variance > 10)[..., None]
     return torch.where(mask, sharpened, img)
