@@ -225,6 +225,36 @@ int nesr_fused_state(const nesr_ctx* ctx);
 int nesr_debug_fault(nesr_ctx* ctx, int drop_workgroups);
 
 /*
+ * conv_up1 / conv_up2 convolve a nearest-x2 upsample.  Every output parity (py, px) of such a layer reads a 2x2 neighbourhood
+ * of the low-resolution input only, so NESR_DTYPE_F32_SPLIT contexts run the layer as four 2x2-tap convolutions whose weights are
+ * the 3x3 taps summed once in nesr_finalize_weights (f32, ky then kx ascending): 2.25x fewer multiply-adds.  The sums round
+ * differently from the nine separate products, at the level of the pair format's own error (2^-22 relative per product).
+ * nesr_set_upconv(ctx, NESR_UPCONV_3X3) selects the full 3x3 form on the upsampled image instead (the values of earlier
+ * releases, for A/B runs); the environment variable NESR_UPCONV=3x3 | 2x2 sets the default of new contexts.  The choice
+ * never depends on a shape.  The other compute forms always run the 3x3 form; nesr_upconv_state returns the mode in use
+ * (negative: an error code; NESR_UPCONV_2X2 is returned only when the folded weights the launches need exist).  nesr_fold_upconv_weights is the host-side folding on its own (no device needed): OIHW f32
+ * [cout][cin][3][3] -> folded[py][px][a][b][cout][cin], the weight of low-res pixel (y + py - 1 + a, x + px - 1 + b) for
+ * output pixel (2y + py, 2x + px).
+ */
+#define NESR_UPCONV_3X3 0
+#define NESR_UPCONV_2X2 1
+int nesr_set_upconv(nesr_ctx* ctx, int mode);
+int nesr_upconv_state(const nesr_ctx* ctx);
+int nesr_fold_upconv_weights(const float* oihw, int cout, int cin, float* folded);
+
+/*
+ * conv_last has <= 4 real output channels.  NESR_DTYPE_F32_SPLIT contexts run it with one 16-channel MFMA column block per
+ * workgroup instead of the 32-channel group's two (NESR_CONV_LAST_NARROW, the default): the same products accumulated in the
+ * same order for the channels that are written, so the image is bit-identical, in both output modes; half the matrix work and
+ * weight reads of the layer.  NESR_CONV_LAST_GENERAL selects the earlier geometry (A/B runs, and the reference of the bit-equality
+ * tests); environment NESR_CONV_LAST=general | narrow sets the default of new contexts.  Other compute forms ignore it.
+ * Both NESR_UPCONV and NESR_CONV_LAST accept exactly their two values; nesr_create fails with NESR_ERR_ARG on anything else.
+ */
+#define NESR_CONV_LAST_GENERAL 0
+#define NESR_CONV_LAST_NARROW 1
+int nesr_set_conv_last(nesr_ctx* ctx, int mode);
+
+/*
  * Timing hook for bench.py's roofline leg: when enabled, forward() brackets the dominant kernel
  * family (the dense-block 3x3 convs) with hipEvents on the caller's stream; nesr_kernel_time_ms
  * returns the accumulated elapsed ms and launch count since the last call (synchronises those
@@ -379,6 +409,12 @@ int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int
 int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W,
                  const float* w_host, const float* b_host, int Cout, int lrelu, int upsample,
                  void* y_dev, void* stream);
+/* The same with the form of an upsampled NESR_DTYPE_F32_SPLIT layer chosen by hand (NESR_UPCONV_3X3 | NESR_UPCONV_2X2, see
+ * nesr_set_upconv); nesr_conv3x3 takes the default (2x2 unless NESR_UPCONV=3x3).  Ignored where the folded form does not exist
+ * (other dtypes, upsample = 0). */
+int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W,
+                    const float* w_host, const float* b_host, int Cout, int lrelu, int upsample,
+                    void* y_dev, void* stream, int upconv_mode);
 
 const char* nesr_last_error(void);
 const char* nesr_version(void);

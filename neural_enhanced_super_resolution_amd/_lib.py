@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT, DTYPE_F16 = 0, 1, 2, 3, 4
 ROUND_TRUNC, ROUND_NEAREST = 0, 1
+UPCONV_3X3, UPCONV_2X2 = 0, 1
+CONV_LAST_GENERAL, CONV_LAST_NARROW = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
 
@@ -45,6 +47,10 @@ SIGNATURES = {
     "nesr_set_concurrent": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_set_fused": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_fused_state": (_c.c_int, [_c.c_void_p]),
+    "nesr_set_upconv": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_upconv_state": (_c.c_int, [_c.c_void_p]),
+    "nesr_set_conv_last": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_fold_upconv_weights": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
     "nesr_debug_fault": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_set_kernel_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_double)]),
@@ -72,6 +78,8 @@ SIGNATURES = {
     "nesr_postprocess_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "nesr_conv3x3_up": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                   _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int]),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),
 }

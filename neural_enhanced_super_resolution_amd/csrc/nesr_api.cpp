@@ -50,6 +50,7 @@ struct Layer {
     bool has_w = false, has_b = false;
     void* d_w = nullptr;
     void* d_ww = nullptr;   // Winograd-transformed weights (f32 Winograd contexts)
+    void* d_w2 = nullptr;   // conv_up1 / conv_up2 of f16-pair contexts: the four folded 2x2-tap slabs (upconv2x2_f16x2.hip)
     float* d_b = nullptr;
 };
 
@@ -86,6 +87,8 @@ struct nesr_ctx {
     int trunk_mode = 0;              // 0 auto, 1 per-layer launches, 2 persistent kernel
     int shared_device = 0;           // nesr_set_concurrent: other contexts run on the device at the same time
     int size_independent = 0;        // nesr_set_size_independent: kernel choice must not depend on the image size
+    int last_narrow = 1;             // nesr_set_conv_last / NESR_CONV_LAST: conv_last of the f16-pair form as one 16-channel column block
+    int upconv_2x2 = 1;              // nesr_set_upconv / NESR_UPCONV: the nearest-x2 convs as four 2x2-tap convs (f16-pair form); 0: 3x3
     // the ragged batch being evaluated (nesr_forward_ragged): internal-resolution sizes of its images
     int rag_n = 0, rag_base_h = 0;
     unsigned short rag_h[nesr::RAG_MAX], rag_w[nesr::RAG_MAX];
@@ -189,7 +192,16 @@ int ensure_ws(nesr_ctx* c, size_t bytes) {
 hipError_t launch_conv(const nesr_ctx* c, const ConvArgs& a, hipStream_t s, const Layer* L = nullptr) {
     if (c->dtype == NESR_DTYPE_BF16) return launch_conv3x3_bf16(a, s);
     if (c->dtype == NESR_DTYPE_F16) return launch_conv3x3_f16(a, s);
-    if (c->dtype == NESR_DTYPE_F32_SPLIT) return launch_conv3x3_f16x2(a, s);
+    if (c->dtype == NESR_DTYPE_F32_SPLIT) {
+        // by the context's setting alone, never by the shape: one arithmetic for a tile however it is batched
+        if (a.up && c->upconv_2x2) {
+            if (!L || !L->d_w2) return hipErrorInvalidValue;   // never a silent 3x3: the folded slabs are built at finalisation
+            ConvArgs u = a;
+            u.w = L->d_w2;
+            return launch_upconv2x2_f16x2(u, s);
+        }
+        return launch_conv3x3_f16x2(a, s);
+    }
     if (c->winograd && L && L->d_ww && (!(a.out_nchw || a.out_u8) || (a.cout_real >= 1 && a.cout_real <= 4 && a.coutp == 32))) {
         ConvArgs w = a;
         w.w = L->d_ww;
@@ -559,6 +571,7 @@ int fw_tail(nesr_ctx* c, const FwState& F, float* y_f32, uint8_t* y_u8, int flip
         a.out_u8 = y_u8;
         a.u8_flip = flip;
         a.u8_round = round_mode;
+        a.narrow_last = c->last_narrow;
         HIP_TRY(launch_conv(c, a, s, &c->layers[tail + 4]));
     }
     return NESR_OK;
@@ -677,6 +690,15 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     if (dtype == NESR_DTYPE_F32_WINOGRAD) dtype = NESR_DTYPE_F32;
     c->dtype = dtype;
     c->kgroup = (dtype == NESR_DTYPE_BF16 || dtype == NESR_DTYPE_F32_SPLIT || dtype == NESR_DTYPE_F16) ? 16 : 8;
+    // A/B runs.  Exactly the documented values; anything else is refused, not read as the default
+    if (const char* e = getenv("NESR_UPCONV")) {
+        if (std::strcmp(e, "3x3") != 0 && std::strcmp(e, "2x2") != 0) { delete c; (void)hipFree(d_status); (void)hipHostFree(h_status); return fail(NESR_ERR_ARG, std::string("NESR_UPCONV must be 3x3 or 2x2, not '") + e + "'"); }
+        c->upconv_2x2 = std::strcmp(e, "2x2") == 0;
+    }
+    if (const char* e = getenv("NESR_CONV_LAST")) {
+        if (std::strcmp(e, "general") != 0 && std::strcmp(e, "narrow") != 0) { delete c; (void)hipFree(d_status); (void)hipHostFree(h_status); return fail(NESR_ERR_ARG, std::string("NESR_CONV_LAST must be general or narrow, not '") + e + "'"); }
+        c->last_narrow = std::strcmp(e, "narrow") == 0;
+    }
     if (const char* e = getenv("NESR_TRUNK")) c->trunk_mode = e[0] == 'l' ? 1 : (e[0] == 'p' ? 2 : 0);
     if (const char* e = getenv("NESR_RDB_FUSE")) c->rdb_mode = atoi(e);
     if (const char* e = getenv("NESR_STRIP")) c->strip_mode = atoi(e);
@@ -788,7 +810,9 @@ int nesr_finalize_weights(nesr_ctx* c) {
     const bool hf = c->dtype == NESR_DTYPE_F16;
     const bool sp = c->dtype == NESR_DTYPE_F32_SPLIT;
     size_t total = 256;   // leading zero page
-    std::vector<size_t> woff(c->layers.size()), boff(c->layers.size()), wwoff(c->layers.size(), 0);
+    std::vector<size_t> woff(c->layers.size()), boff(c->layers.size()), wwoff(c->layers.size(), 0), w2off(c->layers.size(), 0);
+    // f16-pair form: conv_up1 / conv_up2 also as four folded 2x2-tap slabs (the 3x3 slabs stay: nesr_set_upconv)
+    auto is_up = [&](const Layer& L) { return sp && (L.name == "conv_up1" || L.name == "conv_up2"); };
     const size_t last = c->layers.size() - 1;
     for (size_t i = 0; i < c->layers.size(); ++i) {
         const Layer& L = c->layers[i];
@@ -802,6 +826,10 @@ int nesr_finalize_weights(nesr_ctx* c) {
         if (c->winograd) {
             wwoff[i] = total;
             total = align_up(total + packed_weight_elems_wino_f32(L.cin_p, L.cout_p) * 4, 256);
+        }
+        if (is_up(L)) {
+            w2off[i] = total;
+            total = align_up(total + packed_upconv_elems_f16x2(L.cin_p, L.cout_p) * 2, 256);
         }
     }
     std::vector<char> host(total, 0);
@@ -817,6 +845,15 @@ int nesr_finalize_weights(nesr_ctx* c) {
             pack_weights_f32(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<float*>(host.data() + woff[i]));
         std::memcpy(host.data() + boff[i], L.b.data(), (size_t)L.cout * 4);
         if (wwoff[i]) pack_weights_wino_f32(L.w.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<float*>(host.data() + wwoff[i]));
+        if (w2off[i]) {
+            std::vector<float> folded((size_t)16 * L.cout * L.cin);
+            fold_upconv_weights(L.w.data(), L.cout, L.cin, folded.data());
+            for (size_t k = 0; k < folded.size(); ++k)   // a sum of up to four taps must fit the pair's hi half as every tap does
+                if (!(std::fabs(folded[k]) <= 65504.f))
+                    return fail(NESR_ERR_RANGE, L.name + ".weight: a folded 2x2 tap (sum of up to four 3x3 taps) exceeds 65504 in magnitude and "
+                                                         "does not fit the f16-pair form of compute_dtype f32 (use f32-winograd or f32-direct)");
+            pack_upconv_weights_f16x2(folded.data(), L.cout, L.cin, L.cin_p, L.cout_p, reinterpret_cast<uint16_t*>(host.data() + w2off[i]));
+        }
     }
     if (c->d_weights) {
         HIP_TRY(hipDeviceSynchronize());
@@ -831,6 +868,7 @@ int nesr_finalize_weights(nesr_ctx* c) {
         c->layers[i].d_w = c->d_weights + woff[i];
         c->layers[i].d_b = reinterpret_cast<float*>(c->d_weights + boff[i]);
         c->layers[i].d_ww = wwoff[i] ? c->d_weights + wwoff[i] : nullptr;
+        c->layers[i].d_w2 = w2off[i] ? c->d_weights + w2off[i] : nullptr;
     }
     // bf16 / f16: every dense block's weights once more as the LDS-resident kernel's stream (rdb_bf16_strip.hip), + its 192 biases
     if (c->d_strip) { HIP_TRY(hipDeviceSynchronize()); HIP_TRY(hipFree(c->d_strip)); c->d_strip = nullptr; }
@@ -1013,6 +1051,38 @@ int nesr_set_fused(nesr_ctx* c, int on) {
     if (!c) return fail(NESR_ERR_ARG, "null ctx");
     c->rdb_mode = on ? c->rdb_mode_init : 0;          // on: what the context was created with (NESR_RDB_FUSE / NESR_STRIP, default auto)
     c->strip_mode = on ? c->strip_mode_init : 0;
+    return NESR_OK;
+}
+
+int nesr_set_upconv(nesr_ctx* c, int mode) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_set_upconv: RRDBNet contexts only (not an SRVGGNetCompact context)");
+    if (!c) return fail(NESR_ERR_ARG, "null ctx");
+    if (mode != NESR_UPCONV_3X3 && mode != NESR_UPCONV_2X2) return fail(NESR_ERR_ARG, "nesr_set_upconv: mode must be NESR_UPCONV_3X3 or NESR_UPCONV_2X2");
+    c->upconv_2x2 = mode == NESR_UPCONV_2X2;
+    return NESR_OK;
+}
+
+int nesr_upconv_state(const nesr_ctx* c) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_upconv_state: RRDBNet contexts only (not an SRVGGNetCompact context)");
+    if (!c) return fail(NESR_ERR_ARG, "null ctx");
+    if (c->dtype != NESR_DTYPE_F32_SPLIT || !c->upconv_2x2) return NESR_UPCONV_3X3;
+    if (!c->finalized) return fail(NESR_ERR_STATE, "nesr_upconv_state: weights not finalised");
+    for (const Layer& L : c->layers)   // what the launches will really take: the folded slabs must be there
+        if ((L.name == "conv_up1" || L.name == "conv_up2") && !L.d_w2) return fail(NESR_ERR_STATE, "nesr_upconv_state: " + L.name + " has no folded weights");
+    return NESR_UPCONV_2X2;
+}
+
+int nesr_set_conv_last(nesr_ctx* c, int mode) {
+    if (c && c->compact) return fail(NESR_ERR_ARG, "nesr_set_conv_last: RRDBNet contexts only (not an SRVGGNetCompact context)");
+    if (!c) return fail(NESR_ERR_ARG, "null ctx");
+    if (mode != NESR_CONV_LAST_GENERAL && mode != NESR_CONV_LAST_NARROW) return fail(NESR_ERR_ARG, "nesr_set_conv_last: mode must be NESR_CONV_LAST_GENERAL or NESR_CONV_LAST_NARROW");
+    c->last_narrow = mode == NESR_CONV_LAST_NARROW;
+    return NESR_OK;
+}
+
+int nesr_fold_upconv_weights(const float* oihw, int cout, int cin, float* folded) {
+    if (!oihw || !folded || cout <= 0 || cin <= 0) return fail(NESR_ERR_ARG, "nesr_fold_upconv_weights: bad argument");
+    fold_upconv_weights(oihw, cout, cin, folded);
     return NESR_OK;
 }
 
@@ -1329,6 +1399,17 @@ int nesr_clahe_u8(int device_id, const uint8_t* gray_dev, int H, int W, double c
 
 int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W, const float* w_host,
                  const float* b_host, int Cout, int lrelu, int upsample, void* y_dev, void* stream) {
+    // the default of new contexts, read once per process
+    static const int mode = [] {
+        const char* e = getenv("NESR_UPCONV");
+        return !e ? NESR_UPCONV_2X2 : (std::strcmp(e, "3x3") == 0 ? NESR_UPCONV_3X3 : (std::strcmp(e, "2x2") == 0 ? NESR_UPCONV_2X2 : -1));
+    }();
+    if (mode < 0) return fail(NESR_ERR_ARG, "NESR_UPCONV must be 3x3 or 2x2");
+    return nesr_conv3x3_up(device_id, dtype, x_dev, N, Cin, H, W, w_host, b_host, Cout, lrelu, upsample, y_dev, stream, mode);
+}
+
+int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W, const float* w_host,
+                    const float* b_host, int Cout, int lrelu, int upsample, void* y_dev, void* stream, int upconv_mode) {
     if (!x_dev || !w_host || !b_host || !y_dev) return fail(NESR_ERR_ARG, "null argument");
     if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout > 64) return fail(NESR_ERR_ARG, "bad shape (Cout <= 64)");
     if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F32_WINOGRAD && dtype != NESR_DTYPE_F32_SPLIT &&
@@ -1337,6 +1418,8 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
     const bool wino = dtype == NESR_DTYPE_F32_WINOGRAD;
     const bool sp = dtype == NESR_DTYPE_F32_SPLIT;
     const bool hf = dtype == NESR_DTYPE_F16;
+    if (upconv_mode != NESR_UPCONV_3X3 && upconv_mode != NESR_UPCONV_2X2) return fail(NESR_ERR_ARG, "bad upconv_mode");
+    const bool up2x2 = sp && upsample && upconv_mode == NESR_UPCONV_2X2;   // the folded form exists for the f16-pair form
     const int kind = sp ? 2 : (dtype == NESR_DTYPE_BF16 ? 1 : (hf ? 3 : 0));
     if (hf)
         for (size_t i = 0; i < (size_t)Cout * Cin * 9; ++i)
@@ -1348,10 +1431,16 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
     const int cin_p = round_up(Cin, (bf || sp || hf) ? 16 : 8), cout_p = round_up(Cout, 32);
     const int up = upsample ? 1 : 0;
     const int ho = H << up, wo = W << up;
-    const size_t we = sp ? packed_weight_elems_f16x2(cin_p, cout_p) / 2 : (bf || hf) ? packed_weight_elems_bf16(cin_p, cout_p)
+    const size_t we = up2x2 ? packed_upconv_elems_f16x2(cin_p, cout_p) / 2 : sp ? packed_weight_elems_f16x2(cin_p, cout_p) / 2 : (bf || hf) ? packed_weight_elems_bf16(cin_p, cout_p)
                          : (wino ? packed_weight_elems_wino_f32(cin_p, cout_p) : packed_weight_elems_f32(cin_p, cout_p));
     std::vector<char> hw(we * es);
-    if (sp)
+    if (up2x2) {
+        std::vector<float> folded((size_t)16 * Cout * Cin);
+        fold_upconv_weights(w_host, Cout, Cin, folded.data());
+        for (size_t i = 0; i < folded.size(); ++i)
+            if (!(std::fabs(folded[i]) <= 65504.f)) return fail(NESR_ERR_RANGE, "a folded 2x2 tap does not fit the f16-pair form (|w| > 65504 or non-finite)");
+        pack_upconv_weights_f16x2(folded.data(), Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
+    } else if (sp)
         pack_weights_f16x2(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
     else if (bf)
         pack_weights_bf16(w_host, Cout, Cin, cin_p, cout_p, reinterpret_cast<uint16_t*>(hw.data()));
@@ -1400,7 +1489,7 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
     a.lrelu = lrelu ? 1 : 0; a.s1 = a.s2 = 1.f;
     a.zeros = d_zero;
     a.status = (sp || hf) ? d_status : nullptr;
-    HIP_TRY(sp ? launch_conv3x3_f16x2(a, s) : bf ? launch_conv3x3_bf16(a, s) : hf ? launch_conv3x3_f16(a, s)
+    HIP_TRY(up2x2 ? launch_upconv2x2_f16x2(a, s) : sp ? launch_conv3x3_f16x2(a, s) : bf ? launch_conv3x3_bf16(a, s) : hf ? launch_conv3x3_f16(a, s)
                                                                             : (wino ? launch_conv3x3_wino_f32(a, s) : launch_conv3x3_f32(a, s)));
     HIP_TRY(launch_nhwc_to_nchw(d_out, kind, mo, N, Cout, ho, wo, static_cast<float*>(y_dev), s));
     HIP_TRY(hipStreamSynchronize(s));

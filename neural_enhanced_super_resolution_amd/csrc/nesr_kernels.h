@@ -96,6 +96,9 @@ struct ConvArgs {
     // host-side hint: choose the kernel by arithmetic only, never by image size (nesr_set_size_independent): a tile's bits
     // must not depend on whether it was evaluated alone or inside a ragged batch
     int size_independent;
+    // host-side: conv_last of the f16-pair form (image outputs only, cout_real <= 4) computes one 16-channel MFMA column block
+    // instead of the cout group's two -- a scheduling change, bit-identical output (conv3x3_f16x2_kernel<DMAW, 1>)
+    int narrow_last;
     unsigned short rag_h[RAG_MAX], rag_w[RAG_MAX];
 };
 
@@ -128,6 +131,15 @@ void pack_weights_f16(const float* oihw, int cout, int cin, int cin_p, int coutp
 hipError_t launch_conv3x3_f16x2(const ConvArgs& a, hipStream_t s);
 size_t packed_weight_elems_f16x2(int cin_p, int coutp);   // in 2-byte units
 void pack_weights_f16x2(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst);
+
+// conv3x3(nearest_x2(x)) as four 2x2-tap convs on the stored (low-res) input, f16-pair form (upconv2x2_f16x2.hip): a.up = 1,
+// a.h = 2 a.in_h, a.w_ = 2 a.in_w, a.w = pack_upconv_weights_f16x2's image; feature-map output only, whole images.
+// fold_upconv_weights: OIHW f32 [cout][cin][3][3] -> [py][px][a][b][cout][cin] f32 (16 cout cin values), the taps that read
+// low-res pixel (y + py - 1 + a, x + px - 1 + b) at output parity (py, px) summed in f32, ky ascending, then kx.
+hipError_t launch_upconv2x2_f16x2(const ConvArgs& a, hipStream_t s);
+void fold_upconv_weights(const float* oihw, int cout, int cin, float* dst);
+size_t packed_upconv_elems_f16x2(int cin_p, int coutp);   // in 2-byte units
+void pack_upconv_weights_f16x2(const float* folded, int cout, int cin, int cin_p, int coutp, uint16_t* dst);
 
 // One residual dense block (conv1..conv5) per launch, f16-pair form, for frames whose 8x32-pixel tiles all get their
 // own resident workgroup (conv3x3_f16x2.hip, rdb_f16x2_kernel): tiles = rdb_f16x2_tiles(n, h, w) <= compute units.

@@ -258,6 +258,10 @@ class RRDBNet(nn.Module):
             # switches made on the model before this device was used hold here too
             if getattr(self, "_fused_off", False):
                 _lib.check(lib.nesr_set_fused(handle, 0), "nesr_set_fused")
+            if getattr(self, "_upconv_mode", None) is not None:
+                _lib.check(lib.nesr_set_upconv(handle, self._upconv_mode), "nesr_set_upconv")
+            if getattr(self, "_conv_last_mode", None) is not None:
+                _lib.check(lib.nesr_set_conv_last(handle, self._conv_last_mode), "nesr_set_conv_last")
             if getattr(self, "_kernel_timing", False):
                 _lib.check(lib.nesr_set_kernel_timing(handle, 1), "nesr_set_kernel_timing")
             same = [h for k, h in self._peers.items() if k[0] == index]
@@ -549,6 +553,28 @@ class RRDBNet(nn.Module):
         for h in self._handles():
             _lib.check(_lib.load().nesr_set_fused(h[0], 1 if on else 0), "nesr_set_fused")
 
+    def set_upconv(self, mode: str):
+        """"2x2" (default) | "3x3": how compute_dtype "f32" runs conv_up1 / conv_up2 (include/nesr_hip.h: nesr_set_upconv), for
+        every context of this model; contexts created later on another device start with the same setting."""
+        self._upconv_mode = {"3x3": _lib.UPCONV_3X3, "2x2": _lib.UPCONV_2X2}[mode]
+        for h in self._handles():
+            _lib.check(_lib.load().nesr_set_upconv(h[0], self._upconv_mode), "nesr_set_upconv")
+
+    def set_conv_last(self, mode: str):
+        """"narrow" (default) | "general": the launch geometry of compute_dtype "f32"'s conv_last (include/nesr_hip.h:
+        nesr_set_conv_last); the image is bit-identical either way."""
+        self._conv_last_mode = {"general": _lib.CONV_LAST_GENERAL, "narrow": _lib.CONV_LAST_NARROW}[mode]
+        for h in self._handles():
+            _lib.check(_lib.load().nesr_set_conv_last(h[0], self._conv_last_mode), "nesr_set_conv_last")
+
+    def upconv_state(self):
+        """"2x2" | "3x3": the form the home context's conv_up1 / conv_up2 run in (None before the first context exists)."""
+        if self._ctx is None:
+            return None
+        v = int(_lib.load().nesr_upconv_state(self._ctx[0]))
+        _lib.check(min(v, 0), "nesr_upconv_state")
+        return "2x2" if v == _lib.UPCONV_2X2 else "3x3"
+
     def fused_state(self, slot=0, device=None):
         """(persistent launches enabled, forwards that gave up so far) of a context (`device`: None = the home device)."""
         h = (self._ctx if slot == 0 else self._extra.get(slot)) if device is None else self._handle(torch.device(device).index, slot)
@@ -668,9 +694,21 @@ def paste_tiles_u8(tiles, descs, dst_u8, flip_rgb=True, round_nearest=True, thro
                    "nesr_paste_tiles_u8")
 
 
-def conv3x3(x, weight, bias, lrelu=False, upsample=False, dtype="f32"):
+def fold_upconv_weights(weight):
+    """OIHW float32 [cout, cin, 3, 3] -> [2, 2, 2, 2, cout, cin] = W[py][px][a][b]: the folded 2x2 taps of
+    conv3x3(nearest_x2(x)) as libnesr_hip.so builds them (nesr_fold_upconv_weights; host only, no GPU)."""
+    wt = weight.detach().to("cpu", torch.float32).contiguous()
+    cout, cin = wt.shape[0], wt.shape[1]
+    out = torch.empty((2, 2, 2, 2, cout, cin), dtype=torch.float32)
+    _lib.check(_lib.load().nesr_fold_upconv_weights(ctypes.c_void_p(wt.data_ptr()), cout, cin, ctypes.c_void_p(out.data_ptr())),
+               "nesr_fold_upconv_weights")
+    return out
+
+
+def conv3x3(x, weight, bias, lrelu=False, upsample=False, dtype="f32", upconv=None):
     """Single fused layer through the C ABI (test hook): conv3x3(pad 1) + bias [+ LeakyReLU(0.2)],
-    optionally on the nearest-x2 upsample of x.  x NCHW float32 on a ROCm device."""
+    optionally on the nearest-x2 upsample of x.  x NCHW float32 on a ROCm device.  upconv: None (the default form) | "3x3" |
+    "2x2" for an upsampled f32 layer (nesr_conv3x3_up)."""
     if x.device.type != "cuda":
         raise RuntimeError("conv3x3 runs only on an AMD GPU through libnesr_hip.so (no CPU fallback)")
     lib = _lib.load()
@@ -687,8 +725,10 @@ def conv3x3(x, weight, bias, lrelu=False, upsample=False, dtype="f32"):
         # "f32" is what RRDBNet(compute_dtype="f32") runs: the f16-pair kernel
         code = {"bf16": _lib.DTYPE_BF16, "f32-winograd": _lib.DTYPE_F32_WINOGRAD, "f32": _lib.DTYPE_F32_SPLIT, "f32-split": _lib.DTYPE_F32_SPLIT,
                 "f32-direct": _lib.DTYPE_F32, "f16": _lib.DTYPE_F16, "fp16": _lib.DTYPE_F16}[dtype]
-        _lib.check(lib.nesr_conv3x3(index, code,
-                                    ctypes.c_void_p(x.data_ptr()), n, cin, h, w, ctypes.c_void_p(wt.data_ptr()),
-                                    ctypes.c_void_p(bs.data_ptr()), cout, 1 if lrelu else 0, up,
-                                    ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(stream)), "nesr_conv3x3")
+        args = (index, code, ctypes.c_void_p(x.data_ptr()), n, cin, h, w, ctypes.c_void_p(wt.data_ptr()),
+                ctypes.c_void_p(bs.data_ptr()), cout, 1 if lrelu else 0, up, ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(stream))
+        if upconv is None:
+            _lib.check(lib.nesr_conv3x3(*args), "nesr_conv3x3")
+        else:
+            _lib.check(lib.nesr_conv3x3_up(*args, {"3x3": _lib.UPCONV_3X3, "2x2": _lib.UPCONV_2X2}[upconv]), "nesr_conv3x3_up")
     return y

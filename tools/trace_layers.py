@@ -10,7 +10,7 @@ px0 = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
 rows = list(csv.DictReader(open(f)))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 ks = [(r['Kernel_Name'], int(r['End_Timestamp']) - int(r['Start_Timestamp']), int(r['Start_Timestamp']), int(r['End_Timestamp']))
-      for r in rows if 'conv3x3' in r['Kernel_Name'] or 'pack_input' in r['Kernel_Name']]
+      for r in rows if 'conv3x3' in r['Kernel_Name'] or 'upconv2x2' in r['Kernel_Name'] or 'pack_input' in r['Kernel_Name']]
 ks = [k for k in ks] + [(r['Kernel_Name'], int(r['End_Timestamp']) - int(r['Start_Timestamp']), int(r['Start_Timestamp']), int(r['End_Timestamp']))
                         for r in rows if 'rdb_f16x2' in r['Kernel_Name']]
 ks.sort(key=lambda k: k[2])
