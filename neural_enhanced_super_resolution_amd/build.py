@@ -6,6 +6,7 @@ anything: there is no JIT fallback and no CPU fallback).
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -15,7 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_bf16.hip", "conv3x3_wino_f32.hip", "conv3x3_f16x2.hip", "upconv2x2_f16x2.hip", "rdb_bf16_strip.hip", "imgproc.hip", "pack.hip",
-           "srvgg_compact.hip", "filters.hip", "nesr_api.cpp", "compact_api.cpp", "filters_api.cpp"]
+           "srvgg_compact.hip", "filters.hip", "nesr_api.cpp", "rrdb_forward.cpp", "band_api.cpp", "shard_api.cpp", "oneshot_api.cpp", "compact_api.cpp",
+           "filters_api.cpp"]
 ARCH = "gfx950"
 
 
@@ -30,8 +32,7 @@ def _stale(objs_src):
     if not os.path.exists(LIB_PATH):
         return True
     t = os.path.getmtime(LIB_PATH)
-    deps = list(objs_src) + [os.path.join(CSRC, "nesr_kernels.h"), os.path.join(CSRC, "compact_api.h"), os.path.join(CSRC, "elem16.h"), os.path.join(CSRC, "f16x2_common.h"),
-                             os.path.join(HERE, "..", "include", "nesr_hip.h"), os.path.abspath(__file__)]
+    deps = list(objs_src) + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "nesr_hip.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,30 +1,15 @@
 // SRVGGNetCompact contexts (nesr_create_compact): strict weight loading + repacking, workspace, and the forward as one launch
 // per layer (srvgg_compact.hip).  Stands behind upstream realesrgan/archs/srvgg_arch.py SRVGGNetCompact.__init__ / forward and
 // RealESRGANer's load_state_dict for the realesr-general-x4v3 / realesr-animevideov3 checkpoints (the reference's fetcher,
-// standalone/download-x3-model.py:77-116).  The nesr_* entries of nesr_api.cpp forward a compact context's calls here.
-#include <hip/hip_runtime.h>
-
+// standalone/download-x3-model.py:77-116).  The context entries of nesr_api.cpp hand a compact context's calls on to these.
 #include <cmath>
-#include <string>
-#include <unordered_map>
-#include <utility>
-#include <vector>
 
-#include "../../include/nesr_hip.h"
+#include "api_common.h"
 #include "compact_api.h"
 
 using namespace nesr;
 
 namespace {
-
-#define CK_TRY(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess)                                                                       \
-            return set_error(NESR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
-
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct CLayer {
     int cin = 0, cout = 0, cin_p = 0, ncb = 0;
@@ -48,10 +33,7 @@ struct nesr_compact {
     size_t ws_bytes = 0;
     unsigned* d_status = nullptr;                     // [0] range word of the forward in flight, [3] latched from an unchecked earlier one
     unsigned* h_status = nullptr;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending, ev_free;
-    int64_t timed_launches = 0;
-    double timed_flops = 0.0;
+    EventTimer timer;                                 // kernel timing hook
 
     bool split() const { return dtype == NESR_DTYPE_F32_SPLIT; }
     size_t esize() const { return split() ? 4 : 2; }
@@ -65,17 +47,17 @@ CWs ws_layout(const nesr_compact* c, int N, int H, int W) {
     const size_t px = (size_t)N * H * W;
     CWs L;
     L.act0 = 0;
-    L.a = align256(px * 32 * c->esize());
-    L.b = L.a + align256(px * 64 * c->esize());
-    L.res = L.b + align256(px * 64 * c->esize());
-    L.total = L.res + align256(px * 16);
+    L.a = align_up(px * 32 * c->esize(), 256);
+    L.b = L.a + align_up(px * 64 * c->esize(), 256);
+    L.res = L.b + align_up(px * 64 * c->esize(), 256);
+    L.total = L.res + align_up(px * 16, 256);
     return L;
 }
 
 int ensure_ws(nesr_compact* c, size_t bytes) {
     if (bytes <= c->ws_bytes) return NESR_OK;
-    CK_TRY(hipDeviceSynchronize());
-    if (c->ws) CK_TRY(hipFree(c->ws));
+    NESR_TRY(hipDeviceSynchronize());
+    if (c->ws) NESR_TRY(hipFree(c->ws));
     c->ws = nullptr;
     c->ws_bytes = 0;
     if (hipMalloc((void**)&c->ws, bytes) != hipSuccess) {
@@ -102,9 +84,9 @@ int compact_create(nesr_compact** out, int device, int num_in_ch, int num_out_ch
     if (dtype != NESR_DTYPE_F32_SPLIT && dtype != NESR_DTYPE_BF16)
         return set_error(NESR_ERR_ARG, "nesr_create_compact: dtype must be NESR_DTYPE_F32_SPLIT or NESR_DTYPE_BF16");
     int ndev = 0;
-    CK_TRY(hipGetDeviceCount(&ndev));
+    NESR_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device));
-    CK_TRY(hipSetDevice(device));
+    NESR_TRY(hipSetDevice(device));
     nesr_compact* c = new nesr_compact();
     c->device = device;
     c->nin = num_in_ch;
@@ -144,8 +126,7 @@ void compact_destroy(nesr_compact* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (auto& pr : c->ev_pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (auto& pr : c->ev_free) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
+    c->timer.destroy();
     if (c->ws) (void)hipFree(c->ws);
     if (c->d_weights) (void)hipFree(c->d_weights);
     if (c->d_status) (void)hipFree(c->d_status);
@@ -213,16 +194,16 @@ int compact_finalize(nesr_compact* c) {
                     return set_error(NESR_ERR_RANGE, "body." + std::to_string(2 * i) + ".weight holds a value that is non-finite or beyond "
                                                      "+-65504: it does not fit the f16-pair fp32 form (use compute_dtype bf16)");
     }
-    CK_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipSetDevice(c->device));
     const bool sp = c->split();
     size_t bytes = 0;
     c->w_off.clear();
     c->b_off.clear();
     for (auto& L : c->conv) {
         c->w_off.push_back(bytes);
-        bytes = align256(bytes + compact_weight_bytes(L.cin_p, L.ncb, sp));
+        bytes = align_up(bytes + compact_weight_bytes(L.cin_p, L.ncb, sp), 256);
         c->b_off.push_back(bytes);
-        bytes = align256(bytes + (size_t)L.ncb * 16 * 4);
+        bytes = align_up(bytes + (size_t)L.ncb * 16 * 4, 256);
     }
     c->slope_off = bytes;
     bytes += (size_t)(c->nconv + 1) * 64 * 4;
@@ -237,11 +218,11 @@ int compact_finalize(nesr_compact* c) {
     for (int a = 0; a <= c->nconv; ++a)
         for (int ch = 0; ch < 64; ++ch)
             s[a * 64 + ch] = c->act == NESR_ACT_PRELU ? c->slope[a][ch] : (c->act == NESR_ACT_LEAKYRELU ? 0.1f : 0.f);
-    CK_TRY(hipDeviceSynchronize());
-    if (c->d_weights) CK_TRY(hipFree(c->d_weights));
+    NESR_TRY(hipDeviceSynchronize());
+    if (c->d_weights) NESR_TRY(hipFree(c->d_weights));
     c->d_weights = nullptr;
-    CK_TRY(hipMalloc((void**)&c->d_weights, bytes));
-    CK_TRY(hipMemcpy(c->d_weights, host.data(), bytes, hipMemcpyHostToDevice));
+    NESR_TRY(hipMalloc((void**)&c->d_weights, bytes));
+    NESR_TRY(hipMemcpy(c->d_weights, host.data(), bytes, hipMemcpyHostToDevice));
     c->finalized = true;
     return NESR_OK;
 }
@@ -252,7 +233,7 @@ size_t compact_workspace_bytes(const nesr_compact* c, int N, int H, int W) {
 }
 
 int compact_reserve(nesr_compact* c, int N, int H, int W) {
-    CK_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipSetDevice(c->device));
     return ensure_ws(c, compact_workspace_bytes(c, N, H, W));
 }
 
@@ -269,15 +250,15 @@ int compact_forward(nesr_compact* c, const float* x, const uint8_t* x_u8, int fl
     if (N < 1 || H < 1 || W < 1 || C != c->nin) return set_error(NESR_ERR_ARG, "forward: expected [N >= 1, " + std::to_string(c->nin) + ", H, W]");
     if ((long long)N * H * W > (1ll << 30) || (long long)H * c->up > (1 << 30) || (long long)W * c->up > (1 << 30))
         return set_error(NESR_ERR_ARG, "forward: frame too large");
-    CK_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipSetDevice(c->device));
     int rc = ensure_ws(c, ws_layout(c, N, H, W).total);
     if (rc) return rc;
     const CWs L = ws_layout(c, N, H, W);
     const bool sp = c->split();
     unsigned* status = sp ? c->d_status : nullptr;
-    if (status) CK_TRY(launch_status_latch(status, s));   // the range word is per forward (nesr_check_range reports a latched one once)
+    if (status) NESR_TRY(launch_status_latch(status, s));   // the range word is per forward (nesr_check_range reports a latched one once)
     CompactPack p{x, x_u8, flip, N, H, W, sp ? 1 : 0, c->ws + L.act0, reinterpret_cast<float*>(c->ws + L.res)};
-    CK_TRY(launch_compact_pack(p, s));
+    NESR_TRY(launch_compact_pack(p, s));
     auto conv = [&](int i, const void* in, void* out) {
         CompactConv a;
         a.in = in;
@@ -292,71 +273,46 @@ int compact_forward(nesr_compact* c, const float* x, const uint8_t* x_u8, int fl
         return a;
     };
     char* buf[2] = {c->ws + L.a, c->ws + L.b};
-    CK_TRY(launch_compact_conv(conv(0, c->ws + L.act0, buf[0]), sp, 32, c->cus, s));
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (c->timing) {
-        if (c->ev_free.empty()) {
-            CK_TRY(hipEventCreate(&ev0));
-            CK_TRY(hipEventCreate(&ev1));
-        } else {
-            ev0 = c->ev_free.back().first;
-            ev1 = c->ev_free.back().second;
-            c->ev_free.pop_back();
-        }
-        CK_TRY(hipEventRecord(ev0, s));
-    }
+    NESR_TRY(launch_compact_conv(conv(0, c->ws + L.act0, buf[0]), sp, 32, c->cus, s));
+    NESR_TRY(c->timer.begin(s));
     int cur = 0;
-    for (int i = 1; i <= c->nconv; ++i, cur ^= 1) CK_TRY(launch_compact_conv(conv(i, buf[cur], buf[cur ^ 1]), sp, 64, c->cus, s));
-    if (c->timing) {
-        CK_TRY(hipEventRecord(ev1, s));
-        c->ev_pending.emplace_back(ev0, ev1);
-        c->timed_launches += c->nconv;
-        c->timed_flops += 2.0 * 9.0 * 64 * 64 * (double)N * H * W * c->nconv;
+    for (int i = 1; i <= c->nconv; ++i, cur ^= 1) NESR_TRY(launch_compact_conv(conv(i, buf[cur], buf[cur ^ 1]), sp, 64, c->cus, s));
+    NESR_TRY(c->timer.end(s));
+    if (c->timer.on) {
+        c->timer.launches += c->nconv;
+        c->timer.flops += 2.0 * 9.0 * 64 * 64 * (double)N * H * W * c->nconv;
     }
-    CK_TRY(launch_compact_tail(conv(c->nconv + 1, buf[cur], nullptr), sp, c->up, reinterpret_cast<const float*>(c->ws + L.res), y, y_u8, flip,
+    NESR_TRY(launch_compact_tail(conv(c->nconv + 1, buf[cur], nullptr), sp, c->up, reinterpret_cast<const float*>(c->ws + L.res), y, y_u8, flip,
                                round_mode == NESR_ROUND_NEAREST ? 1 : 0, c->cus, s));
     return NESR_OK;
 }
 
 int compact_set_timing(nesr_compact* c, int enable) {
-    c->timing = enable != 0;
+    c->timer.on = enable != 0;
     return NESR_OK;
 }
 
 int compact_kernel_time_ms(nesr_compact* c, double* total_ms, int64_t* launches, double* flops) {
-    CK_TRY(hipSetDevice(c->device));
-    double ms = 0.0;
-    for (auto& pr : c->ev_pending) {
-        CK_TRY(hipEventSynchronize(pr.second));
-        float t = 0.f;
-        CK_TRY(hipEventElapsedTime(&t, pr.first, pr.second));
-        ms += t;
-        c->ev_free.push_back(pr);
-    }
-    c->ev_pending.clear();
-    if (total_ms) *total_ms = ms;
-    if (launches) *launches = c->timed_launches;
-    if (flops) *flops = c->timed_flops;
-    c->timed_launches = 0;
-    c->timed_flops = 0.0;
+    NESR_TRY(hipSetDevice(c->device));
+    NESR_TRY(c->timer.collect(total_ms, launches, flops));
     return NESR_OK;
 }
 
 int compact_check_status(nesr_compact* c) {
-    CK_TRY(hipSetDevice(c->device));
-    CK_TRY(hipDeviceSynchronize());
+    NESR_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipDeviceSynchronize());
     return compact_check_range(c, nullptr);
 }
 
 int compact_check_range(nesr_compact* c, hipStream_t s) {
     if (!c->split()) return NESR_OK;   // bf16 has f32's range
-    CK_TRY(hipSetDevice(c->device));
-    CK_TRY(hipMemcpyAsync(c->h_status, c->d_status, 16, hipMemcpyDeviceToHost, s));
-    CK_TRY(hipStreamSynchronize(s));
+    NESR_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, 16, hipMemcpyDeviceToHost, s));
+    NESR_TRY(hipStreamSynchronize(s));
     const bool now = c->h_status[0] != 0, earlier = c->h_status[3] != 0;
     if (!now && !earlier) return NESR_OK;
-    CK_TRY(hipMemsetAsync(c->d_status, 0, 16, s));   // reported once; the next forward starts clean
-    CK_TRY(hipStreamSynchronize(s));
+    NESR_TRY(hipMemsetAsync(c->d_status, 0, 16, s));   // reported once; the next forward starts clean
+    NESR_TRY(hipStreamSynchronize(s));
     c->h_status[0] = c->h_status[3] = 0;
     if (now)
         return set_error(NESR_ERR_RANGE, "an input or activation of the f16-pair fp32 path was non-finite or exceeded 65504 in magnitude: "

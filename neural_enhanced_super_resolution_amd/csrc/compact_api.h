@@ -1,19 +1,14 @@
-// Internal interface of the SRVGGNetCompact path: the C-ABI layer (nesr_api.cpp) hands a context created by
+// Internal interface of the SRVGGNetCompact path: the context entries of the C ABI (nesr_api.cpp) hand a context created by
 // nesr_create_compact to compact_api.cpp, which drives the kernels of srvgg_compact.hip.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <string>
 
 #include "nesr_kernels.h"
 
 struct nesr_compact;
 
 namespace nesr {
-
-// sets nesr_last_error() and returns `code` (nesr_api.cpp)
-int set_error(int code, const std::string& msg);
 
 // ---- kernels (srvgg_compact.hip)
 struct CompactPack {
@@ -41,7 +36,7 @@ hipError_t launch_compact_tail(const CompactConv& a, bool split, int scale, cons
 size_t compact_weight_bytes(int cin_p, int ncb, bool split);
 void pack_compact_weights(const float* oihw, int cout, int cin, int cin_p, int ncb, bool split, uint16_t* dst);
 
-// ---- context (compact_api.cpp); the nesr_* entries of nesr_api.cpp forward to these for a compact context
+// ---- context (compact_api.cpp); the context entries of nesr_api.cpp hand a compact context on to these
 int compact_create(nesr_compact** out, int device, int num_in_ch, int num_out_ch, int num_feat, int num_conv, int upscale, int act_type,
                    int dtype);
 void compact_destroy(nesr_compact* c);

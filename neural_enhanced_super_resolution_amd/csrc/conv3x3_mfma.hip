@@ -67,7 +67,7 @@ struct Elem<0> {
 };
 
 // One output tile (8 x 16 pixels at (y0, x0) of image n) of one convolution.  Shared by the
-// per-layer kernel below and by the persistent trunk kernel (trunk_persist.hip).
+// per-layer kernel below and by the persistent trunk kernel (further down in this file).
 template <int K, int NT, int WV = 4>
 __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const int y0, const int x0, char* smem) {
     typedef typename Elem<K>::T T;

@@ -2,17 +2,13 @@
 // filters.hip), nesr_preprocess_u8 (those and the NL-means / CLAHE kernels of imgproc.hip as one stream-ordered sequence), and the
 // host-side tables the reference's OpenCV calls build internally (nesr_gaussian_taps, nesr_nl_means_weights).  The tables restate
 // imgproc.gaussian_kernel_u8 and imgproc.nl_means_weights in the same double operations (tests/test_filters_host.py compares them).
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <map>
 #include <mutex>
-#include <string>
 #include <tuple>
-#include <vector>
 
-#include "../../include/nesr_hip.h"
-#include "compact_api.h"
+#include "api_common.h"
+#include "nesr_kernels.h"
 
 #pragma clang fp contract(off)      // the host tables are Python's double arithmetic, operation by operation
 
@@ -20,20 +16,11 @@ using namespace nesr;
 
 namespace {
 
-#define FT_TRY(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess)                                                                       \
-            return set_error(NESR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));    \
-    } while (0)
-
 #define FT_CALL(expr)                     \
     do {                                  \
         const int rc__ = (expr);          \
         if (rc__ != NESR_OK) return rc__; \
     } while (0)
-
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 constexpr int CLAHE_GRID = 8;
 constexpr size_t CLAHE_LUT_BYTES = (size_t)CLAHE_GRID * CLAHE_GRID * 256 * sizeof(float);
@@ -118,7 +105,7 @@ int device_weights(int device, int C, double h, const int** dev, int* nbins) {
         while (nz < n && t[nz] != 0) ++nz;                             // the weights fall monotonically to 0: a short table is enough
         const int len = nz + 1 < n ? nz + 1 : n;
         int* d = nullptr;
-        FT_TRY(hipMalloc(&d, (size_t)len * sizeof(int)));
+        NESR_TRY(hipMalloc(&d, (size_t)len * sizeof(int)));
         const hipError_t e = hipMemcpy(d, t.data(), (size_t)len * sizeof(int), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             (void)hipFree(d);
@@ -156,8 +143,8 @@ int nesr_lab_u8(int device_id, const uint8_t* src_dev, int H, int W, int mode, u
     const LabArgs a = !planar ? lab_args(src_dev, src_dev + 1, src_dev + 2, 3, dst_dev, dst_dev + 1, dst_dev + 2, 3, n, m, -1)
                       : (mode & NESR_LAB_FROM_LAB) ? lab_args(src_dev, src_dev + n, src_dev + 2 * n, 1, dst_dev, dst_dev + 1, dst_dev + 2, 3, n, m, -1)
                                                    : lab_hwc_to_planes(src_dev, dst_dev, n, m);
-    FT_TRY(hipSetDevice(device_id));
-    FT_TRY(launch_lab(a, static_cast<hipStream_t>(stream)));
+    NESR_TRY(hipSetDevice(device_id));
+    NESR_TRY(launch_lab(a, static_cast<hipStream_t>(stream)));
     return NESR_OK;
 }
 
@@ -180,8 +167,8 @@ int nesr_gaussian_u8(int device_id, const uint8_t* src_dev, int H, int W, int C,
     GaussTaps t{};
     t.r = (int)q.size() / 2;
     for (size_t i = 0; i < q.size(); ++i) t.k[i] = q[i];
-    FT_TRY(hipSetDevice(device_id));
-    FT_TRY(launch_gaussian(src_dev, H, W, C, t, dst_dev, static_cast<hipStream_t>(stream)));
+    NESR_TRY(hipSetDevice(device_id));
+    NESR_TRY(launch_gaussian(src_dev, H, W, C, t, dst_dev, static_cast<hipStream_t>(stream)));
     return NESR_OK;
 }
 
@@ -201,7 +188,7 @@ int nesr_nl_means_weights(int C, double h, int template_size, int search_size, i
 
 size_t nesr_preprocess_scratch_bytes(int H, int W) {
     if (H < 1 || W < 1) return 0;
-    return 2 * align256((size_t)3 * H * W) + CLAHE_LUT_BYTES;
+    return 2 * align_up((size_t)3 * H * W, 256) + CLAHE_LUT_BYTES;
 }
 
 int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, double denoise_level, void* scratch_dev, size_t scratch_bytes,
@@ -214,8 +201,8 @@ int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, doub
         return set_error(NESR_ERR_ARG, "nesr_preprocess_u8: scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(need) + " needed");
     const size_t n = (size_t)H * W;
     uint8_t* P = static_cast<uint8_t*>(scratch_dev);                // Lab planes [3][H][W]
-    uint8_t* Q = P + align256(3 * n);                                // second set of planes
-    float* lut = reinterpret_cast<float*>(Q + align256(3 * n));     // CLAHE tables
+    uint8_t* Q = P + align_up(3 * n, 256);                                // second set of planes
+    float* lut = reinterpret_cast<float*>(Q + align_up(3 * n, 256));     // CLAHE tables
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int lbgr = NESR_LAB_LINEAR | NESR_LAB_FIRST_IS_BLUE;
     if (denoise_level > 0) {                                         // fastNlMeansDenoisingColored(img, None, h, h, 7, 21), h = 10 denoise_level
@@ -223,19 +210,19 @@ int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, doub
         const int* wl = nullptr;
         const int* wab = nullptr;
         int nl = 0, nab = 0;
-        FT_TRY(hipSetDevice(device_id));
+        NESR_TRY(hipSetDevice(device_id));
         FT_CALL(device_weights(device_id, 1, h, &wl, &nl));
         FT_CALL(device_weights(device_id, 2, h, &wab, &nab));
-        FT_TRY(launch_lab(lab_hwc_to_planes(rgb_dev, P, n, lbgr), s));
+        NESR_TRY(launch_lab(lab_hwc_to_planes(rgb_dev, P, n, lbgr), s));
         FT_CALL(nesr_nl_means_u8(device_id, P, 1, H, W, 7, 21, wl, nl, Q, stream));
         FT_CALL(nesr_nl_means_u8(device_id, P + n, 2, H, W, 7, 21, wab, nab, Q + n, stream));
-        FT_TRY(launch_lab(lab_args(Q, Q + n, Q + 2 * n, 1, P, P + n, P + 2 * n, 1, n, NESR_LAB_FROM_LAB | lbgr, 0), s));   // Lab -> LBGR -> Lab (sRGB)
+        NESR_TRY(launch_lab(lab_args(Q, Q + n, Q + 2 * n, 1, P, P + n, P + 2 * n, 1, n, NESR_LAB_FROM_LAB | lbgr, 0), s));   // Lab -> LBGR -> Lab (sRGB)
     } else {
-        FT_TRY(hipSetDevice(device_id));
-        FT_TRY(launch_lab(lab_hwc_to_planes(rgb_dev, P, n, 0), s));
+        NESR_TRY(hipSetDevice(device_id));
+        NESR_TRY(launch_lab(lab_hwc_to_planes(rgb_dev, P, n, 0), s));
     }
     FT_CALL(nesr_clahe_u8(device_id, P, H, W, 2.0, CLAHE_GRID, CLAHE_GRID, lut, Q, stream));           // CLAHE on L -> Q[0]
-    FT_TRY(launch_lab(lab_args(Q, P + n, P + 2 * n, 1, out_dev, out_dev + 1, out_dev + 2, 3, n, NESR_LAB_FROM_LAB, -1), s));   // (L', a, b) -> RGB
+    NESR_TRY(launch_lab(lab_args(Q, P + n, P + 2 * n, 1, out_dev, out_dev + 1, out_dev + 2, 3, n, NESR_LAB_FROM_LAB, -1), s));   // (L', a, b) -> RGB
     return NESR_OK;
 }
 
@@ -245,8 +232,8 @@ int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!adaptive_sharpening) {
         if (rgb_dev == out_dev) return NESR_OK;
-        FT_TRY(hipSetDevice(device_id));
-        FT_TRY(hipMemcpyAsync(out_dev, rgb_dev, (size_t)H * W * 3, hipMemcpyDeviceToDevice, s));
+        NESR_TRY(hipSetDevice(device_id));
+        NESR_TRY(hipMemcpyAsync(out_dev, rgb_dev, (size_t)H * W * 3, hipMemcpyDeviceToDevice, s));
         return NESR_OK;
     }
     if (rgb_dev == out_dev) return set_error(NESR_ERR_ARG, "nesr_postprocess_u8: cannot sharpen in place (rgb == out)");
@@ -257,7 +244,7 @@ int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int
     if (k2.size() != 13 || k3.size() != 19) return set_error(NESR_ERR_ARG, "nesr_postprocess_u8: unexpected blur sizes");
     for (int i = 0; i < 13; ++i) t.k2[i] = k2[i];
     for (int i = 0; i < 19; ++i) t.k3[i] = k3[i];
-    FT_TRY(hipSetDevice(device_id));
-    FT_TRY(launch_postprocess(rgb_dev, H, W, t, out_dev, s));
+    NESR_TRY(hipSetDevice(device_id));
+    NESR_TRY(launch_postprocess(rgb_dev, H, W, t, out_dev, s));
     return NESR_OK;
 }

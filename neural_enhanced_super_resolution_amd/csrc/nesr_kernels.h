@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (nesr_api.cpp) and the HIP kernels.
+// Internal launcher interface between the C-ABI layer (rrdb_ctx.h: the table of compute forms and the files it lists) and the HIP kernels.
 // Not part of the public ABI (that is include/nesr_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -102,7 +102,7 @@ struct ConvArgs {
     unsigned short rag_h[RAG_MAX], rag_w[RAG_MAX];
 };
 
-// f32 path: v_mfma_f32_32x32x2_f32 implicit GEMM (conv3x3_f32.hip)
+// f32 path: v_mfma_f32_32x32x2_f32 implicit GEMM (conv3x3_mfma.hip)
 hipError_t launch_conv3x3_f32(const ConvArgs& a, hipStream_t s);
 // host-side weight repack for the f32 kernel: OIHW f32 -> [cin/8][tap][half][coutp][4]
 size_t packed_weight_elems_f32(int cin_p, int coutp);
