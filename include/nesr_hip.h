@@ -398,6 +398,49 @@ int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, doub
 int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int adaptive_sharpening, uint8_t* out_dev, void* hip_stream);
 
 /*
+ * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind
+ * RealESRGANer.enhance(outscale=...), its `cv2.resize(alpha, ..., INTER_LINEAR)` behind alpha_upsampler != "realesrgan", and the
+ * Lanczos paste of _process_with_tiling (nesr/nesr.py:437-446).  cv2's semantics as imgproc.lanczos4_resize / linear_resize_f32 and
+ * oracle/cv2_ref.py restate them: sampling position (d + 0.5) n_in / n_out - 0.5 in double, cast to float32, floor + fraction;
+ * Lanczos-4 always takes 8 taps from floor - 3 (also when shrinking), source indices clamped (BORDER_REPLICATE).  Three forms:
+ *   nesr_resize_u8   NESR_INTER_LANCZOS4, C = 1, 3, 4: OpenCV's fixed point -- coefficients short(rint(c 2048)), integer horizontal
+ *                    pass, integer vertical pass, (v + 2^21) >> 22, saturate.  Bit for bit imgproc.lanczos4_resize's torch chain.
+ *   nesr_resize_u16  NESR_INTER_LANCZOS4, C = 1, 3, 4: float32 coefficients, per pass acc = acc + w_k x_k with k ascending, product and
+ *                    sum rounded separately, rint, saturate.  Bit for bit oracle/cv2_ref.py; the torch chain sums in torch's order (+-1).
+ *   nesr_resize_f32  NESR_INTER_LINEAR, C = 1 .. 4: a (1 - f) + b f per pass, every operation rounded by itself, f = 0 at the clamped
+ *                    ends.  Bit for bit imgproc.linear_resize_f32's torch chain.
+ * Any other (type, interp) pair, a null pointer, a size below 1, another channel count, a row stride smaller than the row,
+ * src == dst, or (u16, f32) a pointer or stride that is not a multiple of the sample size: NESR_ERR_ARG, before any device is
+ * touched.  Equal sizes are legal and copy the image.
+ *
+ * Images are HWC with the pixels of a row contiguous, addressed as base pointer + row stride in BYTES: a rectangle of a frame is
+ * the pointer to its first pixel with the frame's stride -- crop, resize and paste into a rectangle of a canvas are one call.  The
+ * rectangle is its own image (the border is the rectangle's edge), and no byte of the destination outside dst_h x dst_w x C is
+ * written.  The Lanczos forms are one launch: both passes, no intermediate in device memory.
+ *
+ * The coefficient tables are built on the host (nesr_resize_taps gives the same values) and kept on the device per
+ * (device, kind, n_in, n_out): the first call for an axis pair allocates and uploads (synchronous); every later call with those
+ * sizes allocates nothing, does not synchronise, and only enqueues on hip_stream.  Any thread may call.
+ * Parity unpinned against cv2 (absent): checked against oracle/cv2_ref.py.
+ */
+enum { NESR_INTER_LINEAR = 1, NESR_INTER_LANCZOS4 = 4 };   /* cv2's values */
+int nesr_resize_u8(int device_id, const uint8_t* src_dev, int src_h, int src_w, int C, int64_t src_row_bytes, uint8_t* dst_dev, int dst_h, int dst_w,
+                   int64_t dst_row_bytes, int interp, void* hip_stream);
+int nesr_resize_u16(int device_id, const uint16_t* src_dev, int src_h, int src_w, int C, int64_t src_row_bytes, uint16_t* dst_dev, int dst_h, int dst_w,
+                    int64_t dst_row_bytes, int interp, void* hip_stream);
+int nesr_resize_f32(int device_id, const float* src_dev, int src_h, int src_w, int C, int64_t src_row_bytes, float* dst_dev, int dst_h, int dst_w,
+                    int64_t dst_row_bytes, int interp, void* hip_stream);
+
+/* Host only: the table of one axis resized n_in -> n_out.  *n_out_written = n_out always; the arrays are filled when both are given
+ * and cap (in positions) >= n_out.
+ *   NESR_INTER_LANCZOS4: first_out[d] = floor(position) - 3, the first of the 8 taps, NOT clamped (the kernels clamp every tap to
+ *     [0, n_in - 1]); coef_out[16 d .. 16 d + 8) = the float32 coefficients (the u16 form), coef_out[16 d + 8 .. 16 d + 16) = the
+ *     11-bit fixed-point coefficients short(rint(c 2048)) as floats (the u8 form; they sum to 2048 up to rounding).
+ *   NESR_INTER_LINEAR: first_out[d] = the clamped first index i0; coef_out[2 d] = f (0 at the clamped ends), coef_out[2 d + 1] =
+ *     i1 - i0 (1, or 0 at the last sample). */
+int nesr_resize_taps(int n_in, int n_out, int interp, int* first_out, float* coef_out, int cap, int* n_out_written);
+
+/*
  * Single-layer entry (test hook for the per-layer parity tests): one 3x3 stride-1 zero-pad-1
  * convolution + bias (+ LeakyReLU(0.2) if lrelu) (+ nearest x2 upsample of the input first if
  * upsample), i.e. torch.nn.Conv2d / F.leaky_relu / F.interpolate as composed in RRDBNet.forward.

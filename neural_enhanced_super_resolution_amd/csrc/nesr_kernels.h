@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <vector>
 
 namespace nesr {
@@ -283,6 +284,25 @@ struct SharpenTaps {
     int k3[19];
 };
 hipError_t launch_postprocess(const uint8_t* src, int H, int W, const SharpenTaps& taps, uint8_t* dst, hipStream_t s);
+
+// cv2.resize (resize.hip).  src / dst: base pointer + row stride in bytes, pixels of a row contiguous, C interleaved channels.
+// Lanczos-4 (u8: C = 1, 3, 4, fixed point; u16: float32): xtab / ytab = device tables of dst_w / dst_h positions, int32 first tap
+// (i0 - 3, unclamped) for every position, then 8 coefficients per position (u8: the 11-bit ints, u16: float32); a workgroup owns
+// tx x ty outputs (tx a power of two <= 256) and lds_bytes of LDS: [stage | output tile] of region0 bytes, then the horizontal sums;
+// stage_pitch / out_pitch = LDS bytes per staged source row / per output row (multiples of 4 that leave 3 bytes for the row's
+// alignment); max_rows = source rows a tile reads at most.  Linear f32 (C = 1..4): tables = i0[n], i1[n], f[n] (float bits).
+constexpr int RESIZE_LDS_BUDGET = 64 * 1024;      // per workgroup: two fit the 160 KiB of a CU
+struct ResizeArgs {
+    const unsigned char* src;
+    unsigned char* dst;
+    long long src_stride, dst_stride;
+    int src_h, src_w, dst_h, dst_w, C;
+    const int* xtab;
+    const int* ytab;
+    int tx, ty, max_rows, stage_pitch, out_pitch, region0, lds_bytes;
+};
+hipError_t launch_resize_lanczos4(const ResizeArgs& a, int elem_bytes, hipStream_t s);
+hipError_t launch_resize_linear_f32(const ResizeArgs& a, hipStream_t s);
 
 // feature map (channels [0,c)) -> planar f32 NCHW; used by the single-layer test hook
 hipError_t launch_nhwc_to_nchw(const void* src, int kind /* as PackArgs::bf16 */, Map map, int n, int c, int h, int w, float* dst, hipStream_t s);

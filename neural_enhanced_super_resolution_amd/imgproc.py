@@ -81,10 +81,81 @@ def _axis_taps(n_in, n_out, device, taps, first):
     return idx, frac, i0.long()
 
 
-def lanczos4_resize(img, out_h, out_w):
-    """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_LANCZOS4) for HWC uint8 or uint16 (int32-held) tensors.
+def _rows_ok(t, channels):
+    """[H, W, C] with the pixels of a row contiguous (any row stride that holds a row): what the resize kernels address as
+    base pointer + row stride, so frame[y0:y1, x0:x1] goes to them as it is."""
+    return (t.dim() == 3 and t.shape[2] in channels and min(t.shape) > 0 and (t.shape[2] == 1 or t.stride(2) == 1)
+            and (t.shape[1] == 1 or t.stride(1) == t.shape[2]) and (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * t.shape[2]))
+
+
+def _row_bytes(t):
+    return (t.stride(0) if t.shape[0] > 1 else t.shape[1] * t.shape[2]) * t.element_size()
+
+
+_U16 = getattr(torch, "uint16", None)
+
+
+def _lanczos4_hip(img, out_h, out_w, out):
+    """nesr_resize_u8 / nesr_resize_u16 (csrc/resize.hip) on an [H, W, C] device tensor; int32-held uint16 is narrowed once."""
+    from . import _lib
+    h, w, c = img.shape
+    if img.dtype == torch.uint8:
+        src = img if _rows_ok(img, (1, 3, 4)) else img.contiguous()
+        dst = out if out is not None else torch.empty((out_h, out_w, c), dtype=torch.uint8, device=img.device)
+        _hip_call(src, "nesr_resize_u8", _ptr(src), h, w, c, _row_bytes(src), _ptr(dst), out_h, out_w, _row_bytes(dst), _lib.INTER_LANCZOS4)
+        return dst
+    held = img.dtype == torch.int32
+    # int32-held: the low 16 bits as little-endian byte pairs, which is the uint16 image in memory
+    src = torch.stack([img & 255, (img >> 8) & 255], -1).to(torch.uint8) if held else (img if _rows_ok(img, (1, 3, 4)) else img.contiguous())
+    dst = out if out is not None and not held else torch.empty((out_h, out_w, c, 2), dtype=torch.uint8, device=img.device)
+    sb = w * c * 2 if held else _row_bytes(src)
+    db = out_w * c * 2 if dst.dtype == torch.uint8 else _row_bytes(dst)
+    _hip_call(src, "nesr_resize_u16", _ptr(src), h, w, c, sb, _ptr(dst), out_h, out_w, db, _lib.INTER_LANCZOS4)
+    if held:
+        r = dst.view(torch.int16).reshape(out_h, out_w, c).to(torch.int32) & 0xFFFF
+        if out is not None:
+            out.copy_(r)
+            return out
+        return r
+    return dst if out is not None else dst.view(_U16).reshape(out_h, out_w, c)
+
+
+def lanczos4_resize(img, out_h, out_w, use_hip=None, out=None):
+    """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_LANCZOS4) for HWC uint8 or uint16 (int32-held, or a real uint16
+    tensor on the HIP route) tensors.
     uint8: OpenCV's fixed point -- coefficients rounded to 11 bits (x2048, short), integer horizontal pass, integer vertical
-    pass, (v + 2^21) >> 22, saturate.  uint16: float32 coefficients and sums, round to nearest even, saturate."""
+    pass, (v + 2^21) >> 22, saturate.  uint16: float32 coefficients and sums, round to nearest even, saturate.
+
+    On a ROCm device one HIP kernel (csrc/resize.hip, nesr_resize_u8 / nesr_resize_u16: 1, 3 or 4 channels, both passes in one
+    launch, nothing between them in device memory) unless use_hip=False selects the torch chain below.  uint8: the two agree bit
+    for bit; uint16: the kernel sums in oracle/cv2_ref.py's order (k ascending), the chain in torch's: +-1.  A row-strided view
+    (frame[y0:y1, x0:x1]) goes to the kernel as it is, and `out` may be such a view of a canvas ([out_h, out_w, C], img's
+    dtype): crop, resize and paste are then one launch that writes nothing outside the rectangle."""
+    if img.dim() != 3:
+        raise ValueError(f"lanczos4_resize: an [H, W, C] tensor, got {tuple(img.shape)}")
+    h, w, c = img.shape
+    kinds = (torch.uint8, torch.int32) + ((_U16,) if _U16 is not None else ())
+    fits = img.device.type == "cuda" and img.dtype in kinds and c in (1, 3, 4) and h > 0 and w > 0 and out_h > 0 and out_w > 0
+    if out is not None:
+        if tuple(out.shape) != (out_h, out_w, c) or out.dtype != img.dtype or out.device != img.device:
+            raise ValueError(f"lanczos4_resize: out must be a {img.dtype} [{out_h}, {out_w}, {c}] tensor on {img.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+        fits = fits and (_rows_ok(out, (1, 3, 4)) or img.dtype == torch.int32)
+    if use_hip is None:
+        use_hip = fits
+    if use_hip:
+        if not fits:
+            raise ValueError(f"lanczos4_resize: the HIP kernel takes a uint8 or uint16 (or int32-held) [H, W, 1 | 3 | 4] tensor on the ROCm "
+                             f"device (out: rows of contiguous pixels), got {img.dtype} {tuple(img.shape)} on {img.device}")
+        return _lanczos4_hip(img, out_h, out_w, out)
+    if out is not None:
+        out.copy_(_lanczos4_chain(img, out_h, out_w))
+        return out
+    return _lanczos4_chain(img, out_h, out_w)
+
+
+def _lanczos4_chain(img, out_h, out_w):
+    """lanczos4_resize as torch operations on any device (use_hip=False)."""
     h, w, c = img.shape
     is8 = img.dtype == torch.uint8
     ix, fx, _ = _axis_taps(w, out_w, img.device, 8, -3)
@@ -104,9 +175,26 @@ def lanczos4_resize(img, out_h, out_w):
     return torch.round(out).clamp_(0, 65535).to(torch.int32).permute(1, 2, 0).contiguous()
 
 
-def linear_resize_f32(img, out_h, out_w):
-    """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_LINEAR) for float32 HW or HWC tensors."""
+def linear_resize_f32(img, out_h, out_w, use_hip=None):
+    """cv2.resize(img, (out_w, out_h), interpolation=cv2.INTER_LINEAR) for float32 HW or HWC tensors.  On a ROCm device one HIP
+    kernel (csrc/resize.hip, nesr_resize_f32: 1 to 4 channels) unless use_hip=False selects the torch chain below -- the two agree
+    bit for bit (the kernel rounds every product and sum by itself, as the chain's separate operations do)."""
     squeeze = img.dim() == 2
+    fits = (img.device.type == "cuda" and img.dtype == torch.float32 and (squeeze or (img.dim() == 3 and 1 <= img.shape[2] <= 4))
+            and img.numel() > 0 and out_h > 0 and out_w > 0)
+    if use_hip is None:
+        use_hip = fits
+    if use_hip:
+        if not fits:
+            raise ValueError(f"linear_resize_f32: the HIP kernel takes a float32 [H, W] or [H, W, 1..4] tensor on the ROCm device, got "
+                             f"{img.dtype} {tuple(img.shape)} on {img.device}")
+        from . import _lib
+        src = img[:, :, None] if squeeze else img
+        src = src if _rows_ok(src, (1, 2, 3, 4)) else src.contiguous()
+        h, w, c = src.shape
+        dst = torch.empty((out_h, out_w, c), dtype=torch.float32, device=img.device)
+        _hip_call(src, "nesr_resize_f32", _ptr(src), h, w, c, _row_bytes(src), _ptr(dst), out_h, out_w, _row_bytes(dst), _lib.INTER_LINEAR)
+        return dst[:, :, 0] if squeeze else dst
     x = (img[:, :, None] if squeeze else img).permute(2, 0, 1).float()
     h, w = x.shape[1:]
 

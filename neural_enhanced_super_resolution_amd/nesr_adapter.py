@@ -111,9 +111,12 @@ from .imgproc import lanczos4_resize as lanczos4_resize_u8   # noqa: E402  cv2.r
 
 # ----------------------------------------------------------------------------- NESR tiler + dispatcher
 @torch.no_grad()
-def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor, device, as_numpy=True):
+def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor, device, as_numpy=True, use_hip=None):
     """_process_with_tiling (nesr.py:311-475): `processor(tile_rgb_u8 ndarray|tensor) -> uint8 tensor`.
-    Returns an HWC uint8 RGB image of size int(h*uf) x int(w*uf) (ndarray, or the device tensor)."""
+    Returns an HWC uint8 RGB image of size int(h*uf) x int(w*uf) (ndarray, or the device tensor).
+    A tile's region whose size differs from its place in the canvas is resized by imgproc.lanczos4_resize: on a ROCm device the
+    HIP kernel reads the region inside the tile and writes the canvas rectangle in one launch (crop, resize and paste);
+    use_hip=False keeps slice, torch chain and copy -- the two agree bit for bit."""
     h, w, c = image_rgb.shape
     if h <= tile_size and w <= tile_size:
         out = processor(image_rgb)
@@ -153,8 +156,13 @@ def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor
             if oh <= 0 or ow <= 0:
                 continue
             region = pt[ty0:ty1, tx0:tx1]
-            if region.shape[0] != oh or region.shape[1] != ow:
-                region = lanczos4_resize_u8(region, oh, ow)     # cv2.resize(..., INTER_LANCZOS4), nesr.py:438-443
+            if region.shape[0] != oh or region.shape[1] != ow:   # cv2.resize(..., INTER_LANCZOS4), nesr.py:438-443
+                hip = use_hip if use_hip is not None else (region.device.type == "cuda" and region.dtype == torch.uint8 and c in (1, 3, 4)
+                                                           and region.device == canvas.device)
+                if hip:
+                    lanczos4_resize_u8(region, oh, ow, use_hip=True, out=canvas[oy0:oy1, ox0:ox1])
+                    continue
+                region = lanczos4_resize_u8(region, oh, ow, use_hip=False)
             canvas[oy0:oy1, ox0:ox1] = region
     return canvas.cpu().numpy() if as_numpy else canvas
 

@@ -26,6 +26,11 @@ from torch.nn import functional as F
 from .rrdbnet import RAGGED_FORMS, RRDBNet
 from .srvgg import SRVGGNetCompact
 
+# enhance(outscale=...) and the plain alpha upsampler run imgproc's HIP resize kernels (8-bit frames and the float32 alpha plane;
+# 16-bit frames keep the torch chain, see _resize_on_host_route), on the 8-bit device routes before the frame's one
+# device-to-host copy.  False: the frame goes to the host first and the resize is imgproc's torch chain (use_hip=False).
+HIP_RESIZE = True
+
 
 # Integrity pins of the published checkpoints: the only ones the reference holds (nesr/utils/downloader.py:25-26, 33-34).
 KNOWN_CHECKPOINTS = {
@@ -666,9 +671,10 @@ class RealESRGANer:
             paste_tiles_u8(out, pst, dst_u8, flip_rgb=True, round_nearest=True, through_fp16=bool(self.half))
 
     @torch.no_grad()
-    def _enhance_u8_tiles_fused(self, img):
+    def _enhance_u8_tiles_fused(self, img, resize_to=None):
         if self._multi():
-            return self._enhance_u8_tiles_fused_devices(img)
+            out = self._enhance_u8_tiles_fused_devices(img)
+            return out if resize_to is None else self._resize_on_host_route(out, resize_to)
         h, w = img.shape[:2]
         s = self.scale
         frame = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)          # H2D: uint8 HWC BGR
@@ -678,25 +684,56 @@ class RealESRGANer:
             windows.append((py0, px0, py1 - py0, px1 - px0))
             pastes.append((cy0, cx0, cy1 - cy0, cx1 - cx0, (oy0 * w * s + ox0) * 3, w * s * 3))
         self.tiles_u8_on_device(frame, windows, pastes, canvas)
+        if resize_to is not None:
+            canvas = self._resize_u8_on_device(canvas, resize_to)
         host = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)          # (the caching host allocator recycles these)
-        host.copy_(canvas, non_blocking=True)
+        self._frame_to_host(canvas, host)
         torch.cuda.current_stream(self.device).synchronize()
         self._check_range()
         return host.numpy()
 
     @torch.no_grad()
-    def _enhance_u8_on_device(self, img):
+    def _enhance_u8_on_device(self, img, resize_to=None):
+        """resize_to = (out_h, out_w): enhance(outscale=...)'s Lanczos resize, on the device before the one device-to-host copy."""
         if self._u8_tiles_fused_ok(img.shape[0], img.shape[1]) and (img.shape[0] > self.tile_size or img.shape[1] > self.tile_size):
-            return self._enhance_u8_tiles_fused(img)
+            return self._enhance_u8_tiles_fused(img, resize_to)
         x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)            # H2D: uint8 HWC BGR
         x = normalize_u8_on_device(x.permute(2, 0, 1).flip(0)).unsqueeze(0)          # BGR->RGB, /255 (f32), HWC->NCHW
         self._pad_on_device(x)
         out = self._run()                                                            # [1,3,H*s,W*s] RGB
         out = out.data.squeeze(0).float().clamp_(0, 1)
         q = (out.flip(0).permute(1, 2, 0) * 255.0).round().to(torch.uint8)           # RGB->BGR, CHW->HWC, x255, round
-        host = q.contiguous().cpu().numpy()
+        q = q.contiguous()
+        if resize_to is not None:
+            q = self._resize_u8_on_device(q, resize_to)
+        host = self._frame_to_host(q).numpy()
         self._check_range()
         return host
+
+    @staticmethod
+    def _frame_to_host(t, host=None):
+        """The device-to-host copy of a finished 8-bit frame on the enhance() routes (one per call; the tests count them here)."""
+        if host is None:
+            return t.cpu()
+        host.copy_(t, non_blocking=True)
+        return host
+
+    @staticmethod
+    def _resize_u8_on_device(frame, size):
+        from . import imgproc
+        return imgproc.lanczos4_resize(frame, size[0], size[1])
+
+    def _resize_on_host_route(self, output, size):
+        """enhance(outscale=...) for a frame that is on the host already (the float route: 16 bit, gray, alpha; several devices):
+        upload, imgproc.lanczos4_resize, download.  8-bit frames take the HIP kernel, which is bit for bit the torch chain.  16-bit
+        frames keep the torch chain: the uint16 kernel sums in oracle/cv2_ref.py's order (k ascending) and the chain in torch's, so
+        the kernel would move enhance()'s 16-bit results by one LSB where a sum lands next to a half."""
+        from . import imgproc
+        is8 = output.dtype == np.uint8
+        t = torch.from_numpy(np.ascontiguousarray(output if is8 else output.astype(np.int32))).to(self.device)
+        t = t[:, :, None] if t.dim() == 2 else t
+        r = imgproc.lanczos4_resize(t, size[0], size[1], use_hip=None if HIP_RESIZE and is8 else False).cpu().numpy().astype(output.dtype)
+        return r[:, :, 0] if output.ndim == 2 else r
 
     def _check_range(self, slot=None):
         """After a device-to-host copy: an out-of-range forward of the f16-pair fp32 form raises here."""
@@ -862,7 +899,7 @@ class RealESRGANer:
                 from . import imgproc
                 h, w = alpha.shape[0:2]
                 a = torch.from_numpy(np.ascontiguousarray(alpha)).to(self.device)
-                output_alpha = imgproc.linear_resize_f32(a, h * self.scale, w * self.scale).cpu().numpy()
+                output_alpha = imgproc.linear_resize_f32(a, h * self.scale, w * self.scale, use_hip=None if HIP_RESIZE else False).cpu().numpy()
             output_img = np.concatenate([output_img, output_alpha[:, :, None]], axis=2)
         return output_img, img_mode, max_range
 
@@ -887,29 +924,35 @@ class RealESRGANer:
     def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan"):
         h_input, w_input = img.shape[0:2]
         plain_alpha = alpha_upsampler != "realesrgan" and img.ndim == 3 and img.shape[2] == 4
+        # upstream: cv2.resize(output, (int(w_input * outscale), int(h_input * outscale)), interpolation=cv2.INTER_LANCZOS4);
+        # here OpenCV's algorithm restated on the device (imgproc.lanczos4_resize: PARITY UNPINNED, cv2 is not installed)
+        resize_to = None
+        if outscale is not None and outscale != float(self.scale):
+            resize_to = (int(h_input * outscale), int(w_input * outscale))
+        on_device = resize_to if HIP_RESIZE else None     # the 8-bit routes resize before their one device-to-host copy
 
         if self._fused_u8_ok(img) and not plain_alpha:
             # /255, BGR->RGB, network, clamp, RGB->BGR, x255, round -- all inside the HIP path
             x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
-            output = self.model.forward_u8(x, flip_rgb=True, round_nearest=True).cpu().numpy()
+            y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True)
+            if on_device is not None:
+                y = self._resize_u8_on_device(y, on_device)
+            output = self._frame_to_host(y).numpy()
             self._check_range(0)
             img_mode = "RGB"
+            done = on_device is not None
         elif self._u8_on_device_ok(img):
-            output = self._enhance_u8_on_device(img)
+            output = self._enhance_u8_on_device(img, on_device)
             img_mode = "RGB"
+            done = on_device is not None
         else:
             output_img, img_mode, max_range = self.enhance_float(img, alpha_upsampler)
             if max_range == 65535:  # 16-bit image
                 output = (output_img * 65535.0).round().astype(np.uint16)
             else:
                 output = (output_img * 255.0).round().astype(np.uint8)
+            done = False
 
-        if outscale is not None and outscale != float(self.scale):
-            # upstream: cv2.resize(output, (int(w_input * outscale), int(h_input * outscale)), interpolation=cv2.INTER_LANCZOS4);
-            # here OpenCV's algorithm restated on the device (imgproc.lanczos4_resize: PARITY UNPINNED, cv2 is not installed)
-            from . import imgproc
-            t = torch.from_numpy(np.ascontiguousarray(output if output.dtype == np.uint8 else output.astype(np.int32))).to(self.device)
-            t = t[:, :, None] if t.dim() == 2 else t
-            r = imgproc.lanczos4_resize(t, int(h_input * outscale), int(w_input * outscale)).cpu().numpy().astype(output.dtype)
-            output = r[:, :, 0] if output.ndim == 2 else r
+        if resize_to is not None and not done:
+            output = self._resize_on_host_route(output, resize_to)
         return output, img_mode
