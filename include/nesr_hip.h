@@ -441,6 +441,60 @@ int nesr_resize_f32(int device_id, const float* src_dev, int src_h, int src_w, i
 int nesr_resize_taps(int n_in, int n_out, int interp, int* first_out, float* coef_out, int cap, int* n_out_written);
 
 /*
+ * Gray, BGRA and 16-bit frames (csrc/frame_io.hip): every kind of frame RealESRGANer.enhance (realesrgan utils.py) takes besides
+ * 8-bit BGR, which has nesr_forward_u8 -- behind `upscaler.enhance(img)` of standalone/direct_esrgan.py:148 and
+ * standalone/superres_project.py:282 when the file read was a 16-bit TIFF, a gray scan or a PNG with alpha.
+ *
+ * nesr_pack_frame replaces enhance()'s host preparation: `img = img.astype(np.float32)`, `img / max_range`, for a gray frame
+ * `cv2.cvtColor(img, cv2.COLOR_GRAY2RGB)`, for colour `cv2.cvtColor(img, cv2.COLOR_BGR2RGB)`, and pre_process's HWC -> CHW.
+ *   src_dev      : [H, W] (channels 1) or [H, W, channels] (3 = BGR, 4 = BGRA) samples of `bits` bits (8: uint8, 16: uint16), the
+ *                  samples of a row contiguous, rows src_row_bytes apart
+ *   max_range    : 255 or 65535 -- what enhance() divides by (65535 when the frame's maximum exceeds 256, else 255: a uint16 frame
+ *                  that dark counts as 8-bit range and comes back as uint8); the division is correctly rounded
+ *   through_fp16 : as nesr_cut_tiles_u8 (RealESRGANer(half=True): `self.img = self.img.half()`)
+ *   image_dev    : [1, 3, H, W] f32, gray replicated, colour flipped to RGB -- what nesr_forward takes
+ *   alpha_dev    : channels 4 only, may be null (alpha is not written).  NESR_ALPHA_NETWORK: [1, 3, H, W] f32, the alpha samples
+ *                  replicated (`cv2.cvtColor(alpha, cv2.COLOR_GRAY2RGB)`), for a second nesr_forward; NESR_ALPHA_LINEAR: [H, W] f32
+ *                  (never through fp16: it does not pass the network), for nesr_resize_f32
+ *
+ * nesr_unpack_frame replaces what enhance() does with the network's output: `.float().cpu().clamp_(0, 1)`, `[[2, 1, 0]]` and
+ * CHW -> HWC, `cv2.cvtColor(output, cv2.COLOR_BGR2GRAY)` for a gray frame and for a network-upsampled alpha (0.114 b + 0.587 g +
+ * 0.299 r, each product and sum rounded to float32 by itself, left to right), the concatenation of the alpha channel, and
+ * `(output * max_range).round().astype(np.uint8 | np.uint16)` (round half to even).
+ *   image_dev    : the network's output, [3] f32 planes image_plane floats apart, rows image_row floats apart -- post_process's
+ *                  cropped view of a larger output is read in place
+ *   alpha_dev    : channels 4 only.  NESR_ALPHA_NETWORK: the alpha pass's output, planes and rows alpha_plane / alpha_row floats
+ *                  apart; NESR_ALPHA_LINEAR: one [Ho, Wo] f32 plane, rows alpha_row floats apart (clamped like the rest, not
+ *                  rounded through fp16)
+ *   dst_dev      : [Ho, Wo] (channels 1) or [Ho, Wo, channels] samples of `bits` bits, rows dst_row_bytes apart
+ * Both are one launch on hip_stream, no allocation, no synchronisation; bit for bit frame_io.py's torch chains, which are the
+ * numpy lines above.  channels not 1, 3 or 4, bits not 8 or 16, max_range not 255 or 65535, 65535 with 8 bits, a null pointer, a
+ * size below 1, a pitch smaller than a row, or a uint16 pointer or pitch that is odd: NESR_ERR_ARG, before any device is touched.
+ *
+ * nesr_enhance_frame is enhance() for one untiled frame on one context, RRDBNet or SRVGGNetCompact: nesr_pack_frame,
+ * nesr_forward, for BGRA either a second nesr_forward on the alpha planes (NESR_ALPHA_NETWORK, enhance's
+ * alpha_upsampler="realesrgan") or nesr_resize_f32 of the alpha plane (NESR_ALPHA_LINEAR: upstream's
+ * `cv2.resize(alpha, (w * scale, h * scale), interpolation=cv2.INTER_LINEAR)`, parity unpinned as everywhere), nesr_unpack_frame.
+ *   src_dev  : as nesr_pack_frame, rows contiguous;  dst_dev : the frame s times the size (s = the context's output / input size),
+ *              channels as src, uint8 when max_range is 255 and uint16 when it is 65535, rows contiguous
+ *   scratch_dev : at least nesr_frame_scratch_bytes(ctx, H, W, channels, alpha_mode) bytes of device memory, 256-byte aligned (the
+ *              float planes between the steps); 0 is returned for arguments nesr_enhance_frame would refuse
+ * H and W must be multiples of the network's unshuffle factor (RealESRGANer pads a frame that is not; a C host pads before the
+ * call), the network 3 channels in and out.  Those, every error of nesr_pack_frame, an alpha_mode that is neither constant and
+ * scratch that is null or too small: NESR_ERR_ARG before any device is touched.  Call nesr_check_range before trusting dst_dev, as
+ * after nesr_forward.
+ */
+enum { NESR_ALPHA_NETWORK = 0, NESR_ALPHA_LINEAR = 1 };
+int nesr_pack_frame(int device_id, const void* src_dev, int H, int W, int channels, int bits, int64_t src_row_bytes, int max_range, int through_fp16,
+                    float* image_dev, int alpha_mode, float* alpha_dev, void* hip_stream);
+int nesr_unpack_frame(int device_id, const float* image_dev, int Ho, int Wo, int64_t image_plane, int64_t image_row, int through_fp16, int alpha_mode,
+                      const float* alpha_dev, int64_t alpha_plane, int64_t alpha_row, int channels, int bits, int max_range, void* dst_dev,
+                      int64_t dst_row_bytes, void* hip_stream);
+size_t nesr_frame_scratch_bytes(const nesr_ctx* ctx, int H, int W, int channels, int alpha_mode);
+int nesr_enhance_frame(nesr_ctx* ctx, const void* src_dev, int H, int W, int channels, int bits, int max_range, int alpha_mode, int through_fp16,
+                       void* scratch_dev, size_t scratch_bytes, void* dst_dev, void* hip_stream);
+
+/*
  * Single-layer entry (test hook for the per-layer parity tests): one 3x3 stride-1 zero-pad-1
  * convolution + bias (+ LeakyReLU(0.2) if lrelu) (+ nearest x2 upsample of the input first if
  * upsample), i.e. torch.nn.Conv2d / F.leaky_relu / F.interpolate as composed in RRDBNet.forward.

@@ -20,6 +20,7 @@ CONV_LAST_GENERAL, CONV_LAST_NARROW = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
 INTER_LINEAR, INTER_LANCZOS4 = 1, 4
+ALPHA_NETWORK, ALPHA_LINEAR = 0, 1
 
 # name -> (restype, argtypes); must list every symbol include/nesr_hip.h declares
 _c = ctypes
@@ -84,6 +85,13 @@ SIGNATURES = {
     "nesr_resize_f32": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int,
                                    _c.c_void_p]),
     "nesr_resize_taps": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_float), _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                   _c.c_void_p]),
+    "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,
+                                     _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "nesr_frame_scratch_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_enhance_frame": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                      _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3_up": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,

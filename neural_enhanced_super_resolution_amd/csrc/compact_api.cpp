@@ -122,6 +122,8 @@ int compact_create(nesr_compact** out, int device, int num_in_ch, int num_out_ch
     return NESR_OK;
 }
 
+int compact_upscale(const nesr_compact* c) { return c->up; }
+
 void compact_destroy(nesr_compact* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);

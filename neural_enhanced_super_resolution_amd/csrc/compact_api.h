@@ -41,6 +41,7 @@ int compact_create(nesr_compact** out, int device, int num_in_ch, int num_out_ch
                    int dtype);
 void compact_destroy(nesr_compact* c);
 int compact_num_tensors(const nesr_compact* c);
+int compact_upscale(const nesr_compact* c);   // output size / input size
 int compact_load_weight(nesr_compact* c, const char* key, const float* data, const int64_t* shape, int ndim);
 int compact_finalize(nesr_compact* c);
 int compact_forward(nesr_compact* c, const float* x, const uint8_t* x_u8, int flip, int N, int C, int H, int W, float* y, uint8_t* y_u8,

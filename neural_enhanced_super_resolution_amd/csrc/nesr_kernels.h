@@ -304,6 +304,35 @@ struct ResizeArgs {
 hipError_t launch_resize_lanczos4(const ResizeArgs& a, int elem_bytes, hipStream_t s);
 hipError_t launch_resize_linear_f32(const ResizeArgs& a, hipStream_t s);
 
+// Whole frames of every kind RealESRGANer.enhance takes (frame_io.hip): u8 / u16, gray / BGR / BGRA.  alpha_form: FRAME_ALPHA_RGB =
+// three equal planes [3][H][W] (the network route, not flipped), FRAME_ALPHA_PLANE = one plane [H][W] (the linear-resize route;
+// never rounded through fp16: it does not pass the network).
+constexpr int FRAME_ALPHA_RGB = 0, FRAME_ALPHA_PLANE = 1;
+struct FramePack {
+    const unsigned char* src;   // [H][W] (C = 1) or [H][W][C] (C = 3, 4) samples of `bytes` bytes, rows src_pitch bytes apart
+    long long src_pitch;
+    int H, W, C, bytes;
+    float max_range;            // 255 or 65535: v = (float)sample / max_range, correctly rounded
+    int through_fp16;
+    float* image;               // [3][H][W]: gray replicated, colour flipped BGR -> RGB
+    float* alpha;               // C = 4: destination of the alpha samples in `alpha_form`, or null (not written)
+    int alpha_form;
+};
+struct FrameUnpack {
+    const float* image;         // [3] planes image_plane floats apart, rows image_row floats apart (a cropped view is read in place)
+    long long image_plane, image_row;
+    const float* alpha;         // C = 4: FRAME_ALPHA_RGB: three planes like `image`; FRAME_ALPHA_PLANE: one plane, rows alpha_row apart
+    long long alpha_plane, alpha_row;
+    int alpha_form;
+    int H, W, C, bytes;         // the finished frame: [H][W] (C = 1) or [H][W][C] samples of `bytes` bytes, rows dst_pitch bytes apart
+    float max_range;
+    int through_fp16;           // the network outputs pass through fp16 once before the clamp
+    unsigned char* dst;
+    long long dst_pitch;
+};
+hipError_t launch_pack_frame(const FramePack& p, hipStream_t s);
+hipError_t launch_unpack_frame(const FrameUnpack& u, hipStream_t s);
+
 // feature map (channels [0,c)) -> planar f32 NCHW; used by the single-layer test hook
 hipError_t launch_nhwc_to_nchw(const void* src, int kind /* as PackArgs::bf16 */, Map map, int n, int c, int h, int w, float* dst, hipStream_t s);
 

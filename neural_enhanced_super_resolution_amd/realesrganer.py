@@ -31,6 +31,12 @@ from .srvgg import SRVGGNetCompact
 # device-to-host copy.  False: the frame goes to the host first and the resize is imgproc's torch chain (use_hip=False).
 HIP_RESIZE = True
 
+# Gray, BGRA and 16-bit frames (everything enhance() takes besides 8-bit BGR) stay on the device from the upload of the uint8 / uint16
+# frame to the one copy home of the quantised result (_enhance_frame_on_device: frame_io.pack_frame / unpack_frame around the same
+# _pad_on_device and _run()).  False: enhance_float's host route -- numpy preparation, float32 upload, float32 canvas download, numpy
+# clamp / flip / gray / quantiser; the two give the same bits.
+DEVICE_FRAMES = True
+
 
 # Integrity pins of the published checkpoints: the only ones the reference holds (nesr/utils/downloader.py:25-26, 33-34).
 KNOWN_CHECKPOINTS = {
@@ -747,13 +753,15 @@ class RealESRGANer:
         Not part of upstream's API: a frame whose network layers are only a few hundred workgroups (512x512:
         256-512 per layer in one round, all in the same phase) leaves the GPU idle a third of the time; a second frame on its own HIP
         stream and context replica fills it (bench.py's default `value`: 134 -> 160 / 167 / 170 MP/s with 2 / 3 / 4 frames
-        in flight, no more beyond).  Frames
-        that do not take the fused 8-bit path (tiling, padding, alpha, 16 bit) are processed one at a time.
+        in flight, no more beyond).  Gray, BGRA
+        and 16-bit frames that need no tiling or padding join the frames in flight (_frame_in_flight), in any mix; a list with a
+        frame that needs tiling or padding is processed one frame at a time.
         The results are identical to enhance()'s."""
+        from .frame_io import frame_to_numpy
         imgs = list(imgs)
         if self._multi() and imgs and all(self._fused_u8_ok(i) for i in imgs):
             return self._enhance_many_devices(imgs, max(1, int(inflight)))
-        if inflight <= 1 or not imgs or not all(self._fused_u8_ok(i) for i in imgs):
+        if inflight <= 1 or not imgs or not all(self._fused_u8_ok(i) or self._frame_inflight_ok(i) for i in imgs):
             return [self.enhance(i) for i in imgs]
         streams = [torch.cuda.Stream(self.device) for _ in range(inflight)]
         caller = torch.cuda.current_stream(self.device)
@@ -762,24 +770,27 @@ class RealESRGANer:
         results, pending = [None] * len(imgs), []
 
         def finish(entry):
-            idx, host, ev = entry
+            idx, host, ev, mode = entry
             ev.synchronize()
             with torch.cuda.stream(streams[idx % inflight]):
                 self._check_range(idx % inflight)
-            results[idx] = (host.numpy().copy(), "RGB")
+            results[idx] = (frame_to_numpy(host).copy(), mode)
 
         for i, img in enumerate(imgs):
             if len(pending) >= inflight:
                 finish(pending.pop(0))
             k = i % inflight
             with torch.cuda.stream(streams[k]):
-                x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(self.device, non_blocking=True)
-                y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=k)
-                host = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True)
-                host.copy_(y, non_blocking=True)
+                if self._fused_u8_ok(img):
+                    x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(self.device, non_blocking=True)
+                    y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=k)
+                    host, mode = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True), "RGB"
+                    host.copy_(y, non_blocking=True)
+                else:
+                    host, mode = self._frame_in_flight(img, "realesrgan", k)
                 ev = torch.cuda.Event()
                 ev.record()
-            pending.append((i, host, ev))
+            pending.append((i, host, ev, mode))
         for entry in pending:
             finish(entry)
         for st in streams:
@@ -855,6 +866,88 @@ class RealESRGANer:
                 for st in sts:
                     torch.cuda.current_stream(dev).wait_stream(st)
         return results
+
+    # ------------------------------------------------------------------ gray, BGRA and 16-bit frames on the device
+    def _device_frame_ok(self, img):
+        """A frame enhance_float would take (gray, BGRA, 16 bit; 8-bit BGR has routes of its own) on a HIP model of three channels
+        in and out whose output is `scale` times its input: the frame stays on the device (_enhance_frame_on_device)."""
+        if not DEVICE_FRAMES or not self._hip_model() or self.device.type != "cuda":
+            return False
+        if not isinstance(img, np.ndarray) or img.dtype not in (np.uint8, np.uint16) or img.size == 0:
+            return False
+        if img.ndim != 2 and not (img.ndim == 3 and img.shape[2] in (3, 4)):
+            return False
+        return self.model.num_in_ch == 3 and self.model.num_out_ch == 3 and self.model.out_scale() == self.scale
+
+    @staticmethod
+    def _frame_kind(img):
+        """(max_range, img_mode) as enhance_float decides them on the host: a frame whose maximum is at most 256 counts as 8-bit
+        range whatever its dtype (a uint16 frame that dark comes back as uint8), the mode follows the shape."""
+        max_range = 65535 if np.max(img) > 256 else 255
+        return max_range, "L" if img.ndim == 2 else ("RGBA" if img.shape[2] == 4 else "RGB")
+
+    def _frame_inflight_ok(self, img):
+        """enhance_many: a frame of _device_frame_ok's kinds that is one network evaluation per plane set (no tiling, pre_pad or
+        mod-pad), so it can run on a stream and context replica of its own."""
+        if self._multi() or not self._device_frame_ok(img) or self._u8_on_device_ok(img) or self.pre_pad != 0:
+            return False
+        h, w = img.shape[:2]
+        ms = {2: 2, 1: 4}.get(self.scale, 1)
+        return not (self.tile_size > 0 and (h > self.tile_size or w > self.tile_size)) and h % ms == 0 and w % ms == 0
+
+    @torch.no_grad()
+    def _frame_in_flight(self, img, alpha_upsampler, slot):
+        """enhance() of a _frame_inflight_ok frame, enqueued on the current stream with context replica `slot`: returns (the pinned
+        host tensor the result is being copied into, img_mode).  The caller waits for the stream and calls _check_range(slot)."""
+        from . import frame_io, imgproc
+        max_range, img_mode = self._frame_kind(img)
+        plain = img_mode == "RGBA" and alpha_upsampler != "realesrgan"
+        frame = frame_io.frame_to_tensor(img).pin_memory().to(self.device, non_blocking=True)
+        x, a = frame_io.pack_frame(frame, max_range, alpha="linear" if plain else "network", through_fp16=bool(self.half))
+
+        def net(t):
+            return self.model(t.half() if self.half else t, slot=slot).float()
+
+        out = net(x)
+        if a is not None:
+            a = imgproc.linear_resize_f32(a, out.shape[2], out.shape[3], use_hip=None if HIP_RESIZE else False) if plain else net(a)
+        q = frame_io.unpack_frame(out, {"L": 1, "RGB": 3, "RGBA": 4}[img_mode], max_range, alpha=a, through_fp16=bool(self.half))
+        host = torch.empty(q.shape, dtype=q.dtype, pin_memory=True)
+        host.copy_(q, non_blocking=True)
+        return host, img_mode
+
+    @torch.no_grad()
+    def _enhance_frame_on_device(self, img, resize_to=None, alpha_upsampler="realesrgan"):
+        """enhance() for the frames enhance_float takes, without its host passes: the uint8 / uint16 frame is uploaded as it is,
+        frame_io.pack_frame normalises, replicates or flips it, _pad_on_device and _run() evaluate it as they do for every frame
+        (padding, tiles, ragged batches, devices= lanes), the alpha plane takes a second _run() or imgproc.linear_resize_f32 on the
+        device, frame_io.unpack_frame clamps, flips, takes the gray value and quantises, outscale's resize follows (resize_to), and
+        one copy brings the finished frame home.  The same float32 operations in the same order as enhance_float and enhance's
+        quantiser, so the same bits."""
+        from . import frame_io, imgproc
+        max_range, img_mode = self._frame_kind(img)
+        plain = img_mode == "RGBA" and alpha_upsampler != "realesrgan"
+        frame = frame_io.frame_to_tensor(img, self.device)                              # H2D: the frame's own bytes
+        x, a = frame_io.pack_frame(frame, max_range, alpha="linear" if plain else "network", through_fp16=bool(self.half))
+        self._pad_on_device(x)
+        out = self._run().float()                                                       # [1,3,H*s,W*s] RGB (fp16 upstream when half)
+        if a is not None:
+            if plain:   # upstream: cv2.resize(alpha, (w * scale, h * scale), interpolation=cv2.INTER_LINEAR)
+                a = imgproc.linear_resize_f32(a, img.shape[0] * self.scale, img.shape[1] * self.scale, use_hip=None if HIP_RESIZE else False)
+            else:
+                self._pad_on_device(a)
+                a = self._run().float()
+        q = frame_io.unpack_frame(out, {"L": 1, "RGB": 3, "RGBA": 4}[img_mode], max_range, alpha=a, through_fp16=bool(self.half))
+        if resize_to is not None:
+            q3 = q[:, :, None] if q.dim() == 2 else q
+            if q.dtype == torch.uint8:
+                q3 = self._resize_u8_on_device(q3, resize_to) if HIP_RESIZE else imgproc.lanczos4_resize(q3, resize_to[0], resize_to[1], use_hip=False)
+            else:       # 16 bit keeps the torch chain, for the reason given at _resize_on_host_route
+                q3 = imgproc.lanczos4_resize(q3.to(torch.int32) & 0xFFFF, resize_to[0], resize_to[1], use_hip=False).to(torch.int16)
+            q = q3[:, :, 0] if q.dim() == 2 else q3
+        host = frame_io.frame_to_numpy(self._frame_to_host(q.contiguous()))
+        self._check_range()
+        return host, img_mode
 
     @torch.no_grad()
     def enhance_float(self, img, alpha_upsampler="realesrgan"):
@@ -945,6 +1038,9 @@ class RealESRGANer:
             output = self._enhance_u8_on_device(img, on_device)
             img_mode = "RGB"
             done = on_device is not None
+        elif self._device_frame_ok(img):
+            output, img_mode = self._enhance_frame_on_device(img, resize_to, alpha_upsampler)
+            done = resize_to is not None
         else:
             output_img, img_mode, max_range = self.enhance_float(img, alpha_upsampler)
             if max_range == 65535:  # 16-bit image
