@@ -495,6 +495,67 @@ int nesr_enhance_frame(nesr_ctx* ctx, const void* src_dev, int H, int W, int cha
                        void* scratch_dev, size_t scratch_bytes, void* dst_dev, void* hip_stream);
 
 /*
+ * The ESRGAN stage of SuperResolutionPipeline.enhance_image (csrc/nesr12.hip, csrc/nesr_stage_api.cpp): the network the reference
+ * builds and calls is RRDBNet(num_in_ch=12, num_out_ch=3, scale=4) (nesr/nesr.py:216), fed with a 12-channel synthesis of the RGB
+ * frame and quantised by truncation.  With nesr_preprocess_u8 and nesr_postprocess_u8 one iteration of the pipeline is three calls on
+ * device buffers; u8 frames go in and out, no float image exists outside the context's workspace.  Every entry is bit for bit the
+ * torch statement in nesr_adapter.py named with it (tests/test_gpu_nesr_stage.py, tests/test_nesr_stage_host.py).
+ *
+ * nesr_forward_nesr_u8: _apply_esrgan_12channel (nesr/nesr.py:845-903; mode NESR_INPUT_12CH) or _apply_esrgan_3channel
+ * (nesr/nesr.py:905-945; NESR_INPUT_3CH_X4) on one window -- nesr_adapter.apply_esrgan_12channel / apply_esrgan_3channel.
+ *   rgb_dev : first pixel of an H x W window of an RGB u8 HWC frame, rows src_row_bytes apart.  The window is its own image: with
+ *             bgr = the pixel flipped (cv2.COLOR_RGB2BGR) and t = bgr / 255 (correctly rounded), the network's input channels are
+ *             t | clamp(1.1 t, 0, 1) | clamp(0.9 t, 0, 1) | cv2.GaussianBlur(bgr, (3, 3), 0) / 255 (taps [1 2 1] x [1 2 1], (S + 8) >> 4,
+ *             BORDER_REFLECT_101 at the window's edges: the reference blurs a tile after cropping it), or t four times; one launch,
+ *             written in the context's own activation layout
+ *   out_dev : u8 RGB [4H, 4W, 3], rows out_row_bytes apart: clip(255 y, 0, 255) truncated (nesr/nesr.py:894-898), BGR -> RGB
+ *             (:901), from conv_last's epilogue; rows further apart than 12 W bytes pass through the context's workspace
+ * Requires an RRDBNet context with conv_first_in_ch 12, no unshuffle, num_out_ch 3, of any NESR_DTYPE_*; H, W >= 2 (for a
+ * one-pixel side the torch statement pads by replication, not as cv2 does: not offered); strides at least a row.  Anything else,
+ * an SRVGGNetCompact context included: NESR_ERR_ARG.  Call nesr_check_range before trusting out_dev, as after nesr_forward.
+ *
+ * nesr_stage_route (host only): the dispatch of _apply_esrgan (nesr/nesr.py:761-793) as nesr_adapter.apply_esrgan states it.
+ * megapixels = H W / 1024^2; *tiled = enable_tiling and megapixels > threshold_mp (the reference's literals: 8 for cuda, 2 for cpu,
+ * 4 for mps); *mode = NESR_INPUT_3CH_X4 if force_3channel else NESR_INPUT_12CH; megapixels > large_mp (the reference's literal 16)
+ * forces tiling and NESR_INPUT_3CH_X4.
+ *
+ * nesr_stage_tile_plan (host only): the rectangles of _process_with_tiling (nesr/nesr.py:311-475) -- nesr_adapter.tile_plan.  Per
+ * tile of the ceil(H / tile) x ceil(W / tile) grid, row-major, 13 ints:
+ *     y0 y1 x0 x1      the source window, the tile grown by `padding` and clipped to the frame
+ *     ty0 ty1 tx0 tx1  the crop inside the network's output of that window (net_scale times its size): int(padding scale) off every
+ *                      side that is not a frame edge, clamped to at least one pixel
+ *     oy0 oy1 ox0 ox1  the canvas rectangle: int(window edge x upscale_factor), moved in by int(padding upscale_factor) on the same sides
+ *     skip             1: the rectangle is empty, nothing is pasted
+ * in Python's arithmetic: doubles, int() truncating toward zero.  A crop whose size differs from its rectangle is resized into it
+ * (Lanczos-4).  A frame that fits one tile (H <= tile and W <= tile) is one tile whose rectangle is the network's own output,
+ * net_scale H x net_scale W, whatever upscale_factor says (nesr/nesr.py:326-328).  *n is always set; rects[0 .. 13 *n) is filled when
+ * cap (in tiles) >= *n.
+ *
+ * nesr_apply_esrgan_u8: the stage -- nesr_adapter.apply_esrgan's two routes.  rgb_dev: u8 RGB [H, W, 3], rows contiguous.
+ *   untiled (tiled = 0), or a frame that fits one tile: one nesr_forward_nesr_u8 into out_dev, u8 RGB [4H, 4W, 3]
+ *   tiled: out_dev is the canvas, u8 RGB [int(H upscale_factor), int(W upscale_factor), 3], zeroed first; every tile of the plan
+ *          runs through the network into scratch_dev, then its crop goes to its rectangle: a 2-D copy where the sizes agree, else
+ *          nesr_resize_u8 (NESR_INTER_LANCZOS4) reading the crop in place and writing the rectangle in place
+ * mode, tiled: nesr_stage_route's, or the caller's own.  padding: the reference passes 16 (nesr/nesr.py:797).  scratch_dev: at least
+ * nesr_apply_esrgan_scratch_bytes(ctx, H, W, tiled, tile, padding) bytes (the largest tile's output; 256 where nothing is staged,
+ * scratch_dev may be null then; 0 for arguments nesr_apply_esrgan_u8 would refuse).  Everything is enqueued on hip_stream; the call
+ * allocates nothing and does not synchronise, except what nesr_forward and nesr_resize_u8 say of their first call for a size (the
+ * workspace grows, a coefficient table is uploaded: nesr_reserve and one warm-up frame take both off the path).  Every refusal
+ * (NESR_ERR_ARG: the context, a window side below 2, scratch) comes before the first launch.
+ * ONE nesr_check_range after the call covers the whole frame: the range word is scoped to one forward, and every forward first moves
+ * what the one before it left to the "earlier forward" word, which nesr_check_range reports as NESR_ERR_RANGE too -- a tile that did
+ * not fit the compute form anywhere in the frame is an error for the frame.
+ */
+enum { NESR_INPUT_12CH = 0, NESR_INPUT_3CH_X4 = 1 };
+int nesr_forward_nesr_u8(nesr_ctx* ctx, const uint8_t* rgb_dev, int64_t src_row_bytes, int H, int W, int mode, uint8_t* out_dev, int64_t out_row_bytes,
+                         void* hip_stream);
+int nesr_stage_route(int H, int W, int enable_tiling, int force_3channel, double threshold_mp, double large_mp, int* tiled, int* mode);
+int nesr_stage_tile_plan(int H, int W, int tile, int padding, double upscale_factor, int net_scale, int* rects, int cap, int* n);
+size_t nesr_apply_esrgan_scratch_bytes(const nesr_ctx* ctx, int H, int W, int tiled, int tile, int padding);
+int nesr_apply_esrgan_u8(nesr_ctx* ctx, const uint8_t* rgb_dev, int H, int W, int mode, int tiled, int tile, int padding, double upscale_factor,
+                         void* scratch_dev, size_t scratch_bytes, uint8_t* out_dev, void* hip_stream);
+
+/*
  * Single-layer entry (test hook for the per-layer parity tests): one 3x3 stride-1 zero-pad-1
  * convolution + bias (+ LeakyReLU(0.2) if lrelu) (+ nearest x2 upsample of the input first if
  * upsample), i.e. torch.nn.Conv2d / F.leaky_relu / F.interpolate as composed in RRDBNet.forward.

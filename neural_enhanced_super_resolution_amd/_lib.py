@@ -21,6 +21,8 @@ ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
 INTER_LINEAR, INTER_LANCZOS4 = 1, 4
 ALPHA_NETWORK, ALPHA_LINEAR = 0, 1
+INPUT_12CH, INPUT_3CH_X4 = 0, 1
+STAGE_RECT = 13      # ints per tile of nesr_stage_tile_plan
 
 # name -> (restype, argtypes); must list every symbol include/nesr_hip.h declares
 _c = ctypes
@@ -92,6 +94,12 @@ SIGNATURES = {
     "nesr_frame_scratch_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
     "nesr_enhance_frame": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
                                       _c.c_void_p, _c.c_void_p]),
+    "nesr_forward_nesr_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "nesr_stage_route": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "nesr_stage_tile_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_apply_esrgan_scratch_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_apply_esrgan_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t,
+                                        _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3_up": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -104,7 +112,7 @@ _lib = None
 _lock = threading.Lock()
 
 
-ERR_RANGE = -5
+ERR_ARG, ERR_RANGE = -1, -5
 
 
 class NesrHipError(RuntimeError):

@@ -238,6 +238,20 @@ struct PackArgs {
 hipError_t launch_pack_input(const PackArgs& a, hipStream_t s);
 hipError_t launch_status_latch(unsigned* status, hipStream_t s);   // range word of an unchecked earlier forward: word 0 -> word 3
 
+// the NESR pipeline's network input (nesr12.hip): a window of an RGB u8 HWC frame -> conv_first's 12 channels (+ 4 of zero padding)
+struct Pack12Args {
+    const uint8_t* src;      // the frame: [rows][pixels][3] RGB u8, rows src_stride bytes apart
+    long long src_stride;
+    int y0, x0, h, w;        // the window (h, w >= 2): the blur's border is the window's edge
+    int mode;                // NESR_INPUT_12CH | NESR_INPUT_3CH_X4
+    void* dst;               // as PackArgs: feature map with cp = 16 channels, addressed through dst_map
+    Map dst_map;
+    int cp;
+    int bf16;                // destination layout, as PackArgs::bf16
+    unsigned* status;        // as PackArgs::status
+};
+hipError_t launch_pack_nesr12(const Pack12Args& a, hipStream_t s);
+
 // all tiles of a frame at once (pack.hip): u8 HWC frame -> float NCHW tile slots (cut), float NCHW tile outputs -> u8 (paste)
 constexpr int TILE_IO_MAX = 64;
 struct TileIo {

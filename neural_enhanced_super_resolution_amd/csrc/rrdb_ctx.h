@@ -141,11 +141,14 @@ void lease_forget(const nesr_ctx* c);
 // the forward graph in stages (whole-frame forward = all of them in order; the banded multi-GPU mode runs them one at a
 // time with a row exchange in between)
 int fw_setup(nesr_ctx* c, int N, int C, int H, int W, FwState& F);
-int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x_u8, int flip, int C, int H, int W, hipStream_t s);
+int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x_u8, int flip, int C, int H, int W, hipStream_t s,
+             const Pack12Args* nesr12 = nullptr);
 int fw_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s, int phase = -1, int top = 0, int bottom = 0, int edge = 0);
 int fw_tail(nesr_ctx* c, const FwState& F, float* y_f32, uint8_t* y_u8, int flip, int round_mode, hipStream_t s);
-// The whole forward.  x -> y; exactly one of (x_f32, x_u8) and one of (y_f32, y_u8) is set.
+// The whole forward.  x -> y; exactly one of (x_f32, x_u8, nesr12) and one of (y_f32, y_u8) is set.  nesr12: the input is the
+// 12-channel synthesis of that window (nesr12.hip; its destination fields are filled here), N = 1, C = 12, H x W the window.
+// y_u8_row_bytes: bytes between the rows of y_u8 (0: contiguous rows).
 int run_forward(nesr_ctx* c, const float* x_f32, const uint8_t* x_u8, int flip, int N, int C, int H, int W,
-                float* y_f32, uint8_t* y_u8, int round_mode, hipStream_t s);
+                float* y_f32, uint8_t* y_u8, int round_mode, hipStream_t s, const Pack12Args* nesr12 = nullptr, long long y_u8_row_bytes = 0);
 
 }  // namespace nesr

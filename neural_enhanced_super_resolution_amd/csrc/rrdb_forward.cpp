@@ -343,8 +343,9 @@ int fw_setup(nesr_ctx* c, int N, int C, int H, int W, FwState& F) {
     return NESR_OK;
 }
 
-// pack (pixel_unshuffle, layout, u8 normalisation) + conv_first: IN -> P.x0 and F (feat is needed again after the trunk)
-int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x_u8, int flip, int C, int H, int W, hipStream_t s) {
+// pack (pixel_unshuffle, layout, u8 normalisation; or the NESR pipeline's 12-channel synthesis from `nesr12`'s window) + conv_first:
+// IN -> P.x0 and F (feat is needed again after the trunk)
+int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x_u8, int flip, int C, int H, int W, hipStream_t s, const Pack12Args* nesr12) {
     char* ws = c->ws;
     PackArgs p;
     std::memset(&p, 0, sizeof(p));
@@ -359,7 +360,13 @@ int fw_first(nesr_ctx* c, const FwState& F, const float* x_f32, const uint8_t* x
     p.bf16 = c->kind();
     p.status = c->ranged() ? c->d_status : nullptr;
     if (p.status) NESR_TRY(launch_status_latch(c->d_status, s));      // the range word is per forward (nesr_check_range reports a latched one once)
-    NESR_TRY(launch_pack_input(p, s));
+    if (nesr12) {
+        Pack12Args q = *nesr12;
+        q.dst = p.dst; q.dst_map = p.dst_map; q.cp = p.cp; q.bf16 = p.bf16; q.status = p.status;
+        NESR_TRY(launch_pack_nesr12(q, s));
+    } else {
+        NESR_TRY(launch_pack_input(p, s));
+    }
     ConvArgs a = base_args(c, c->layers[0], F.N, F.h, F.w);
     a.in = ws + F.L.in; a.in_map = F.m_in;
     a.out = ws + F.L.a; a.out_map = F.m_t; a.out_coff = 0;
@@ -477,12 +484,12 @@ int fw_tail(nesr_ctx* c, const FwState& F, float* y_f32, uint8_t* y_u8, int flip
 }
 
 int run_forward(nesr_ctx* c, const float* x_f32, const uint8_t* x_u8, int flip, int N, int C, int H, int W,
-                float* y_f32, uint8_t* y_u8, int round_mode, hipStream_t s) {
+                float* y_f32, uint8_t* y_u8, int round_mode, hipStream_t s, const Pack12Args* nesr12, long long y_u8_row_bytes) {
     FwState F;
     int rc = fw_setup(c, N, C, H, W, F);
     if (rc) return rc;
     c->band_valid = false;   // the workspace no longer holds a banded evaluation
-    if ((rc = fw_first(c, F, x_f32, x_u8, flip, C, H, W, s))) return rc;
+    if ((rc = fw_first(c, F, x_f32, x_u8, flip, C, H, W, s, nesr12))) return rc;
 
     NESR_TRY(c->timer.begin(s));
     // opt-in (NESR_TRUNK=persist): measured slower at 2 tiles/CU, see DESIGN.md.  f32 and bf16 only: f16 runs per-layer launches
@@ -517,6 +524,15 @@ int run_forward(nesr_ctx* c, const float* x_f32, const uint8_t* x_u8, int flip, 
         if (lease && (rc = lease_release(c, s))) return rc;
     }
     NESR_TRY(c->timer.end(s));
+    // conv_last's u8 epilogue writes whole rows.  Rows further apart than that: the image lands in the workspace's conv_up2 map
+    // (48 of its >= 2048 bytes per input pixel; nothing reads that map once conv_hr has run) and is copied out row by row
+    const long long dense = (long long)4 * F.w * c->nout;
+    if (y_u8 && y_u8_row_bytes && y_u8_row_bytes != dense) {
+        uint8_t* stage = reinterpret_cast<uint8_t*>(c->ws + F.L.u2);
+        if ((rc = fw_tail(c, F, nullptr, stage, flip, round_mode, s))) return rc;
+        NESR_TRY(hipMemcpy2DAsync(y_u8, (size_t)y_u8_row_bytes, stage, (size_t)dense, (size_t)dense, (size_t)4 * F.h, hipMemcpyDeviceToDevice, s));
+        return NESR_OK;
+    }
     return fw_tail(c, F, y_f32, y_u8, flip, round_mode, s);
 }
 

@@ -13,6 +13,11 @@ Differences, on purpose: no exception ladder (nesr.py:815-843, 448-473 turn any 
 bicubic result -- here failures raise), no MPS branches, no probe tile (nesr.py:349-357 runs the
 processor on a 256x256 corner and discards the result).
 
+On a ROCm device with the HIP RRDBNet(num_in_ch=12) the stage is one call of the C ABI, u8 frame in, u8 frame out
+(`use_hip=None`, the default: nesr_forward_nesr_u8 for one window, nesr_apply_esrgan_u8 for a frame with its tiler; csrc/nesr12.hip,
+csrc/nesr_stage_api.cpp) -- no [1,12,H,W] float input, no float output, no Python tile loop.  `use_hip=False` keeps the torch
+chains below, which are the specification, the CPU-side statement, and what the C entries equal bit for bit.
+
 cv2 is not available offline, so its two non-trivial image ops are restated, PARITY UNPINNED:
   * cv2.GaussianBlur(u8, (3,3), 0): kernel [1 2 1]/4 separable, BORDER_REFLECT_101, fixed-point with
     round-half-up -> (S + 8) >> 4 on the 16-weight integer sum.
@@ -21,12 +26,14 @@ cv2 is not available offline, so its two non-trivial image ops are restated, PAR
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
 import torch
 from torch.nn import functional as F
 
+from . import _lib
 from .realesrganer import normalize_u8_on_device
 
 
@@ -85,24 +92,58 @@ def _to_host(upscaler, t):
     return host
 
 
-@torch.no_grad()
-def apply_esrgan_12channel(upscaler, image_rgb, as_numpy=True):
-    """_apply_esrgan_12channel (nesr.py:845-903) with every step on the GPU."""
+NET_SCALE = 4            # output / input size of RRDBNet(num_in_ch=12, scale=4), nesr.py:216
+TILE_PADDING = 16        # nesr.py:797: what _apply_esrgan passes to _process_with_tiling
+
+
+def _hip_stage_refusal(upscaler, image_rgb, windows):
+    """Why the C entries of the stage cannot take this frame (None: they can): they want a uint8 [H, W, 3] frame bound for a ROCm
+    device, the HIP RRDBNet with 12 input channels (scale 4, 3 output channels), and windows (h, w) of at least 2 x 2."""
+    from .rrdbnet import RRDBNet
+    m = upscaler.model
+    if torch.device(upscaler.device).type != "cuda":
+        return f"the upscaler's device is {upscaler.device}, not a ROCm device"
+    if not (isinstance(m, RRDBNet) and m.num_in_ch == 12 and m.num_out_ch == 3 and m.scale not in (1, 2)):
+        return "upscaler.model is not the HIP RRDBNet(num_in_ch=12, num_out_ch=3, scale=4)"
+    dtype = image_rgb.dtype
+    if dtype not in (torch.uint8, np.uint8) or len(image_rgb.shape) != 3 or image_rgb.shape[2] != 3:
+        return f"the frame is {dtype} {tuple(image_rgb.shape)}, not uint8 [H, W, 3]"
+    if any(h < 2 or w < 2 for h, w in windows):
+        return "a window has a one-pixel side (the torch chain pads such a blur by replication)"
+    return None
+
+
+def _takes_hip(use_hip, upscaler, image_rgb, windows):
+    if use_hip is False:
+        return False
+    why = _hip_stage_refusal(upscaler, image_rgb, windows)
+    if use_hip and why:
+        raise ValueError(f"use_hip=True: {why}")
+    return why is None
+
+
+def _apply_one(upscaler, image_rgb, mode, as_numpy, use_hip):
     model = upscaler.model
     model.eval()
-    y = model(build_12channel(image_rgb, upscaler.device))
-    q = quantize_trunc_to_rgb(y)
+    if _takes_hip(use_hip, upscaler, image_rgb, [image_rgb.shape[:2]]):
+        q = model.forward_nesr_u8(_u8_on(image_rgb, upscaler.device), mode)
+    else:
+        build = build_12channel if mode == _lib.INPUT_12CH else build_3channel_x4
+        q = quantize_trunc_to_rgb(model(build(image_rgb, upscaler.device)))
     return _to_host(upscaler, q) if as_numpy else q
 
 
 @torch.no_grad()
-def apply_esrgan_3channel(upscaler, image_rgb, as_numpy=True):
-    """_apply_esrgan_3channel (nesr.py:905-945)."""
-    model = upscaler.model
-    model.eval()
-    y = model(build_3channel_x4(image_rgb, upscaler.device))
-    q = quantize_trunc_to_rgb(y)
-    return _to_host(upscaler, q) if as_numpy else q
+def apply_esrgan_12channel(upscaler, image_rgb, as_numpy=True, use_hip=None):
+    """_apply_esrgan_12channel (nesr.py:845-903) with every step on the GPU: one call of RRDBNet.forward_nesr_u8 where that
+    applies (module doc), else (and with use_hip=False) build_12channel, the model, quantize_trunc_to_rgb -- the same bits."""
+    return _apply_one(upscaler, image_rgb, _lib.INPUT_12CH, as_numpy, use_hip)
+
+
+@torch.no_grad()
+def apply_esrgan_3channel(upscaler, image_rgb, as_numpy=True, use_hip=None):
+    """_apply_esrgan_3channel (nesr.py:905-945); routes as apply_esrgan_12channel."""
+    return _apply_one(upscaler, image_rgb, _lib.INPUT_3CH_X4, as_numpy, use_hip)
 
 
 # ----------------------------------------------------------------------------- Lanczos-4 resize
@@ -110,26 +151,14 @@ from .imgproc import lanczos4_resize as lanczos4_resize_u8   # noqa: E402  cv2.r
 
 
 # ----------------------------------------------------------------------------- NESR tiler + dispatcher
-@torch.no_grad()
-def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor, device, as_numpy=True, use_hip=None):
-    """_process_with_tiling (nesr.py:311-475): `processor(tile_rgb_u8 ndarray|tensor) -> uint8 tensor`.
-    Returns an HWC uint8 RGB image of size int(h*uf) x int(w*uf) (ndarray, or the device tensor).
-    A tile's region whose size differs from its place in the canvas is resized by imgproc.lanczos4_resize: on a ROCm device the
-    HIP kernel reads the region inside the tile and writes the canvas rectangle in one launch (crop, resize and paste);
-    use_hip=False keeps slice, torch chain and copy -- the two agree bit for bit."""
-    h, w, c = image_rgb.shape
-    if h <= tile_size and w <= tile_size:
-        out = processor(image_rgb)
-        return out.cpu().numpy() if as_numpy else out
+def _tile_windows(h, w, tile_size, padding, upscale_factor):
+    """Per tile of _process_with_tiling's ceil grid (nesr.py:335-336), row-major: the source window y0, y1, x0, x1 (the tile grown
+    by `padding`, clipped to the frame: nesr.py:370-373) and its canvas rectangle oy0, oy1, ox0, ox1 (nesr.py:400-412)."""
     nth, ntw = math.ceil(h / tile_size), math.ceil(w / tile_size)
-    out_h, out_w = int(h * upscale_factor), int(w * upscale_factor)
-    canvas = torch.zeros((out_h, out_w, c), dtype=torch.uint8, device=device)
     for i in range(nth):
         for j in range(ntw):
             y0, y1 = max(0, i * tile_size - padding), min(h, (i + 1) * tile_size + padding)
             x0, x1 = max(0, j * tile_size - padding), min(w, (j + 1) * tile_size + padding)
-            tile = image_rgb[y0:y1, x0:x1]
-            pt = processor(tile)
             oy0, oy1 = int(y0 * upscale_factor), int(y1 * upscale_factor)
             ox0, ox1 = int(x0 * upscale_factor), int(x1 * upscale_factor)
             if padding > 0:
@@ -142,62 +171,138 @@ def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor
                     ox0 += pu
                 if x1 < w:
                     ox1 -= pu
-            th, tw = pt.shape[:2]
-            sy, sx = th / tile.shape[0], tw / tile.shape[1]
-            ty0 = 0 if y0 == 0 else int(padding * sy)
-            ty1 = th if y1 == h else int(th - padding * sy)
-            tx0 = 0 if x0 == 0 else int(padding * sx)
-            tx1 = tw if x1 == w else int(tw - padding * sx)
-            ty0 = max(0, min(ty0, th - 1))
-            ty1 = max(ty0 + 1, min(ty1, th))
-            tx0 = max(0, min(tx0, tw - 1))
-            tx1 = max(tx0 + 1, min(tx1, tw))
-            oh, ow = oy1 - oy0, ox1 - ox0
-            if oh <= 0 or ow <= 0:
+            yield y0, y1, x0, x1, oy0, oy1, ox0, ox1
+
+
+def _tile_crop(th, tw, padding, y0, y1, x0, x1, h, w):
+    """The part ty0, ty1, tx0, tx1 of a window's th x tw network output that belongs to the tile (nesr.py:414-426)."""
+    sy, sx = th / (y1 - y0), tw / (x1 - x0)
+    ty0 = 0 if y0 == 0 else int(padding * sy)
+    ty1 = th if y1 == h else int(th - padding * sy)
+    tx0 = 0 if x0 == 0 else int(padding * sx)
+    tx1 = tw if x1 == w else int(tw - padding * sx)
+    ty0 = max(0, min(ty0, th - 1))
+    ty1 = max(ty0 + 1, min(ty1, th))
+    tx0 = max(0, min(tx0, tw - 1))
+    tx1 = max(tx0 + 1, min(tx1, tw))
+    return ty0, ty1, tx0, tx1
+
+
+def tile_plan(h, w, tile_size, padding, upscale_factor, net_scale=NET_SCALE):
+    """The rectangles of process_with_tiling for a processor whose output is `net_scale` times its input, one tuple of 13 ints per
+    tile: (y0, y1, x0, x1 source window | ty0, ty1, tx0, tx1 crop inside the processor's output | oy0, oy1, ox0, ox1 canvas rectangle |
+    skip: 1 when the rectangle is empty).  A frame that fits one tile is one tile whose rectangle is the processor's whole output.
+    nesr_stage_tile_plan (include/nesr_hip.h) returns the same table."""
+    if h <= tile_size and w <= tile_size:
+        return [(0, h, 0, w, 0, net_scale * h, 0, net_scale * w, 0, net_scale * h, 0, net_scale * w, 0)]
+    rows = []
+    for y0, y1, x0, x1, oy0, oy1, ox0, ox1 in _tile_windows(h, w, tile_size, padding, upscale_factor):
+        crop = _tile_crop(net_scale * (y1 - y0), net_scale * (x1 - x0), padding, y0, y1, x0, x1, h, w)
+        rows.append((y0, y1, x0, x1) + crop + (oy0, oy1, ox0, ox1, int(oy1 - oy0 <= 0 or ox1 - ox0 <= 0)))
+    return rows
+
+
+@torch.no_grad()
+def process_with_tiling(processor, image_rgb, tile_size, padding, upscale_factor, device, as_numpy=True, use_hip=None):
+    """_process_with_tiling (nesr.py:311-475): `processor(tile_rgb_u8 ndarray|tensor) -> uint8 tensor`.
+    Returns an HWC uint8 RGB image of size int(h*uf) x int(w*uf) (ndarray, or the device tensor).
+    A tile's region whose size differs from its place in the canvas is resized by imgproc.lanczos4_resize: on a ROCm device the
+    HIP kernel reads the region inside the tile and writes the canvas rectangle in one launch (crop, resize and paste);
+    use_hip=False keeps slice, torch chain and copy -- the two agree bit for bit."""
+    h, w, c = image_rgb.shape
+    if h <= tile_size and w <= tile_size:
+        out = processor(image_rgb)
+        return out.cpu().numpy() if as_numpy else out
+    out_h, out_w = int(h * upscale_factor), int(w * upscale_factor)
+    canvas = torch.zeros((out_h, out_w, c), dtype=torch.uint8, device=device)
+    for y0, y1, x0, x1, oy0, oy1, ox0, ox1 in _tile_windows(h, w, tile_size, padding, upscale_factor):
+        tile = image_rgb[y0:y1, x0:x1]
+        pt = processor(tile)
+        ty0, ty1, tx0, tx1 = _tile_crop(pt.shape[0], pt.shape[1], padding, y0, y1, x0, x1, h, w)
+        oh, ow = oy1 - oy0, ox1 - ox0
+        if oh <= 0 or ow <= 0:
+            continue
+        region = pt[ty0:ty1, tx0:tx1]
+        if region.shape[0] != oh or region.shape[1] != ow:   # cv2.resize(..., INTER_LANCZOS4), nesr.py:438-443
+            hip = use_hip if use_hip is not None else (region.device.type == "cuda" and region.dtype == torch.uint8 and c in (1, 3, 4)
+                                                       and region.device == canvas.device)
+            if hip:
+                lanczos4_resize_u8(region, oh, ow, use_hip=True, out=canvas[oy0:oy1, ox0:ox1])
                 continue
-            region = pt[ty0:ty1, tx0:tx1]
-            if region.shape[0] != oh or region.shape[1] != ow:   # cv2.resize(..., INTER_LANCZOS4), nesr.py:438-443
-                hip = use_hip if use_hip is not None else (region.device.type == "cuda" and region.dtype == torch.uint8 and c in (1, 3, 4)
-                                                           and region.device == canvas.device)
-                if hip:
-                    lanczos4_resize_u8(region, oh, ow, use_hip=True, out=canvas[oy0:oy1, ox0:ox1])
-                    continue
-                region = lanczos4_resize_u8(region, oh, ow, use_hip=False)
-            canvas[oy0:oy1, ox0:ox1] = region
+            region = lanczos4_resize_u8(region, oh, ow, use_hip=False)
+        canvas[oy0:oy1, ox0:ox1] = region
     return canvas.cpu().numpy() if as_numpy else canvas
 
 
 LARGE_IMAGE_MP = 16      # nesr.py:787: above this many "megapixels" (px / 1024^2) tiling and 3-channel mode are forced
 
 
-def apply_esrgan(upscaler, image_rgb, config=None, device_kind="cuda", as_numpy=True, trace=None, large_mp=LARGE_IMAGE_MP):
+def stage_route(h, w, cfg, device_kind="cuda", large_mp=LARGE_IMAGE_MP):
+    """The dispatch of _apply_esrgan (nesr.py:761-793) -> (use_tiling, use_3ch); nesr_stage_route (include/nesr_hip.h) is the same."""
+    megapixels = (h * w) / (1024 * 1024)
+    use_tiling = False
+    if cfg.get("enable_tiling", True):
+        thr = {"cpu": cfg.get("cpu_megapixel_threshold", 2), "mps": cfg.get("mps_megapixel_threshold", 4)}.get(
+            device_kind, cfg.get("cuda_megapixel_threshold", 8))
+        use_tiling = megapixels > thr
+    use_3ch = cfg.get("force_3channel", False)
+    if megapixels > large_mp:
+        use_tiling, use_3ch = True, True
+    return use_tiling, use_3ch
+
+
+def _apply_esrgan_hip(upscaler, image_rgb, mode, tiled, tile_size, upscale_factor):
+    """nesr_apply_esrgan_u8 on torch's current stream: the frame's tiles, their crops and pastes in one call of the C ABI."""
+    dev = torch.device(upscaler.device)
+    x = _u8_on(image_rgb, dev).contiguous()
+    h, w, _ = x.shape
+    one = not tiled or (h <= tile_size and w <= tile_size)
+    shape = (NET_SCALE * h, NET_SCALE * w, 3) if one else (int(h * upscale_factor), int(w * upscale_factor), 3)
+    lib = _lib.load()
+    with torch.cuda.device(x.device):
+        ctx = upscaler.model._context(x.device, 0)
+        need = lib.nesr_apply_esrgan_scratch_bytes(ctx, h, w, int(tiled), int(tile_size), TILE_PADDING)
+        if not need:
+            _lib.check(_lib.ERR_ARG, "nesr_apply_esrgan_scratch_bytes")
+        scratch = torch.empty(need, dtype=torch.uint8, device=x.device)
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(lib.nesr_apply_esrgan_u8(ctx, ctypes.c_void_p(x.data_ptr()), h, w, mode, int(tiled), int(tile_size), TILE_PADDING, float(upscale_factor),
+                                            ctypes.c_void_p(scratch.data_ptr()), need, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)),
+                   "nesr_apply_esrgan_u8")
+    return out
+
+
+def apply_esrgan(upscaler, image_rgb, config=None, device_kind="cuda", as_numpy=True, trace=None, large_mp=LARGE_IMAGE_MP, use_hip=None):
     """_apply_esrgan (nesr.py:754-813): the reference's dispatch, minus its fallback ladder.
     config keys as the reference's: enable_tiling, force_3channel, max_tile_size, upscale_factor,
     cuda_megapixel_threshold (the reference's literal default for cuda is 8).  `large_mp` is the reference's
     literal 16 (a parameter only so that tests can reach that branch with small frames); `trace`, if a list,
-    receives one dict describing the route taken."""
+    receives one dict describing the route taken.  use_hip=None: the whole stage as one call of the C ABI (nesr_apply_esrgan_u8)
+    where it applies (module doc); use_hip=False: the torch chains and the Python tile loop; the same frame and trace either way."""
     cfg = {"enable_tiling": True, "force_3channel": False, "max_tile_size": 512, "upscale_factor": 2.0}
     cfg.update(config or {})
     h, w, _ = image_rgb.shape
-    megapixels = (h * w) / (1024 * 1024)
-    use_tiling = False
-    if cfg["enable_tiling"]:
-        thr = {"cpu": cfg.get("cpu_megapixel_threshold", 2), "mps": cfg.get("mps_megapixel_threshold", 4)}.get(
-            device_kind, cfg.get("cuda_megapixel_threshold", 8))
-        use_tiling = megapixels > thr
-    use_3ch = cfg["force_3channel"]
-    if megapixels > large_mp:
-        use_tiling, use_3ch = True, True
+    use_tiling, use_3ch = stage_route(h, w, cfg, device_kind, large_mp)
     model = upscaler.model
     calls0 = getattr(model, "calls", None)
     net_px = [0]
+    # the windows the network sees (the C tiler evaluates every tile of the plan, as the loop below does)
+    plan = tile_plan(h, w, cfg["max_tile_size"], TILE_PADDING, cfg["upscale_factor"]) if use_tiling else [(0, h, 0, w)]
+    windows = [(r[1] - r[0], r[3] - r[2]) for r in plan]
+    canvas_ok = len(plan) == 1 or (int(h * cfg["upscale_factor"]) >= 1 and int(w * cfg["upscale_factor"]) >= 1)
 
     def one(t):
         net_px[0] += int(t.shape[0]) * int(t.shape[1])
-        return apply_esrgan_3channel(upscaler, t, as_numpy=False) if use_3ch else apply_esrgan_12channel(upscaler, t, as_numpy=False)
+        return (apply_esrgan_3channel if use_3ch else apply_esrgan_12channel)(upscaler, t, as_numpy=False, use_hip=False)
 
-    if use_tiling:
-        out = process_with_tiling(one, image_rgb, cfg["max_tile_size"], 16, cfg["upscale_factor"], upscaler.device, as_numpy=False)
+    if canvas_ok and _takes_hip(use_hip, upscaler, image_rgb, windows):
+        model.eval()
+        out = _apply_esrgan_hip(upscaler, image_rgb, _lib.INPUT_3CH_X4 if use_3ch else _lib.INPUT_12CH, use_tiling, cfg["max_tile_size"], cfg["upscale_factor"])
+        model.calls += len(plan)
+        net_px[0] = sum(wh * ww for wh, ww in windows)
+    elif use_tiling:
+        out = process_with_tiling(one, image_rgb, cfg["max_tile_size"], TILE_PADDING, cfg["upscale_factor"], upscaler.device, as_numpy=False)
     else:
         out = one(image_rgb)
     if trace is not None:

@@ -387,6 +387,33 @@ class RRDBNet(nn.Module):
                                                    ctypes.c_void_p(stream)), "nesr_forward_u8")
         return y
 
+    @torch.no_grad()
+    def forward_nesr_u8(self, img_u8, mode, out=None, slot: int = 0):
+        """The NESR pipeline's call of its 12-channel network, u8 in, u8 out (nesr_forward_nesr_u8): RGB u8 HWC [H, W, 3] device
+        tensor -> RGB u8 HWC [4H, 4W, 3].  mode "12ch" | _lib.INPUT_12CH: _apply_esrgan_12channel (nesr/nesr.py:845-903), the
+        synthesis [t, clamp(1.1 t), clamp(0.9 t), GaussianBlur3x3 / 255] of the BGR image, the network, the truncating quantiser,
+        BGR -> RGB; "3ch" | _lib.INPUT_3CH_X4: _apply_esrgan_3channel (nesr/nesr.py:905-945), the image four times.  Bit for bit
+        nesr_adapter.apply_esrgan_12channel / _3channel(use_hip=False).  `img_u8` may be a window of a frame (frame[y0:y1, x0:x1]:
+        the blur reflects at the window's edges) and `out` a [4H, 4W, 3] window of a canvas; both need contiguous pixels in a row.
+        A model with 12 input channels, scale 4 and 3 output channels; H, W >= 2."""
+        self._require_cuda(img_u8)
+        if img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3:
+            raise ValueError("expected a uint8 [H, W, 3] tensor")
+        code = {"12ch": _lib.INPUT_12CH, "3ch": _lib.INPUT_3CH_X4}.get(mode, mode)
+        rows = lambda t: t.stride(2) == 1 and t.stride(1) == 3 and t.stride(0) >= 3 * t.shape[1]      # noqa: E731
+        x = img_u8 if rows(img_u8) else img_u8.contiguous()
+        h, w, _ = x.shape
+        if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != (4 * h, 4 * w, 3) or out.device != x.device or not rows(out)):
+            raise ValueError(f"out must be a uint8 [{4 * h}, {4 * w}, 3] tensor on {x.device} with contiguous pixels in a row")
+        self.calls += 1
+        with torch.cuda.device(x.device):
+            ctx = self._context(x.device, slot)
+            y = torch.empty((4 * h, 4 * w, 3), dtype=torch.uint8, device=x.device) if out is None else out
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(_lib.load().nesr_forward_nesr_u8(ctx, ctypes.c_void_p(x.data_ptr()), x.stride(0), h, w, int(code), ctypes.c_void_p(y.data_ptr()),
+                                                        y.stride(0), ctypes.c_void_p(stream)), "nesr_forward_nesr_u8")
+        return y
+
     # ------------------------------------------------------------------ sharded frames through the C ABI (RCCL below Python)
     def comm_init(self, device, rank, nranks, unique_id: bytes):
         """ncclCommInitRank for this model's context on `device` (include/nesr_hip.h: nesr_comm_init); `unique_id` = the 128 bytes
