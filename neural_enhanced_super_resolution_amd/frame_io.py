@@ -15,12 +15,11 @@ frame_to_numpy convert at the ends, and a torch.uint16 tensor is accepted where 
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._contexts import device_call
 
 _U16 = getattr(torch, "uint16", None)
 _LUTS = {}
@@ -79,17 +78,6 @@ def _rows_contiguous(t, inner):
     return all(t.shape[d] == 1 or t.stride(d) >= want for d in range(t.dim() - inner))
 
 
-def _call(t, name, *args):
-    index = t.device.index if t.device.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(t.device):
-        stream = torch.cuda.current_stream(t.device).cuda_stream
-        _lib.check(getattr(_lib.load(), name)(index, *args, ctypes.c_void_p(stream)), name)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
-
-
 def pack_frame(frame, max_range, alpha=None, through_fp16=False, use_hip=None):
     """frame: uint8 or 16-bit [H, W] | [H, W, 3] | [H, W, 4] tensor -> (image, alpha_out).
 
@@ -115,8 +103,8 @@ def pack_frame(frame, max_range, alpha=None, through_fp16=False, use_hip=None):
         if alpha is not None:
             out = torch.empty((1, 3, h, w) if alpha == "network" else (h, w), dtype=torch.float32, device=frame.device)
         pitch = (src.stride(0) if h > 1 else w * channels) * src.element_size()
-        _call(src, "nesr_pack_frame", _ptr(src), h, w, channels, bits, pitch, int(max_range), 1 if through_fp16 else 0, _ptr(image),
-              _lib.ALPHA_LINEAR if alpha == "linear" else _lib.ALPHA_NETWORK, _ptr(out))
+        device_call("nesr_pack_frame", src.device, src, h, w, channels, bits, pitch, int(max_range), 1 if through_fp16 else 0, image,
+                    _lib.ALPHA_LINEAR if alpha == "linear" else _lib.ALPHA_NETWORK, out)
         return image, out
     idx = frame.to(torch.int64)
     if bits == 16:
@@ -180,9 +168,9 @@ def unpack_frame(output, channels, max_range, alpha=None, through_fp16=False, us
         shape = (ho, wo) if channels == 1 else (ho, wo, channels)
         dst = torch.empty(shape, dtype=torch.uint8 if bits == 8 else torch.int16, device=x.device)
         ap, ar = (0, 0) if a is None else ((0, a.stride(0)) if plane else (a.stride(0), a.stride(1)))
-        _call(x, "nesr_unpack_frame", _ptr(x), ho, wo, x.stride(0), x.stride(1), 1 if through_fp16 else 0,
-              _lib.ALPHA_LINEAR if plane else _lib.ALPHA_NETWORK, _ptr(a), ap, ar, channels, bits, int(max_range), _ptr(dst),
-              wo * channels * (bits // 8))
+        device_call("nesr_unpack_frame", x.device, x, ho, wo, x.stride(0), x.stride(1), 1 if through_fp16 else 0,
+                    _lib.ALPHA_LINEAR if plane else _lib.ALPHA_NETWORK, a, ap, ar, channels, bits, int(max_range), dst,
+                    wo * channels * (bits // 8))
         return dst
 
     def unit(t, net=True):

@@ -38,12 +38,8 @@ def _hip_require(x, layout_ok, what, layout):
 
 def _hip_call(x, name, *args):
     """libnesr_hip.so entry `name`(device, *args, stream) on x's device and current stream; raises on failure."""
-    import ctypes
-    from . import _lib
-    index = x.device.index if x.device.index is not None else torch.cuda.current_device()
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(getattr(_lib.load(), name)(index, *args, ctypes.c_void_p(stream)), name)
+    from ._contexts import device_call
+    device_call(name, x.device, *args)
 
 
 def _ptr(t):
@@ -393,16 +389,10 @@ def clahe_u8(gray, clip_limit=2.0, grid=(8, 8), use_hip=None):
     if use_hip is None:
         use_hip = gray.device.type == "cuda" and gray.dtype == torch.uint8
     if use_hip:
-        import ctypes
-        from . import _lib
         src = gray.contiguous()
         out = torch.empty_like(src)
         lut = torch.empty((gy * gx * 256,), dtype=torch.float32, device=src.device)
-        index = src.device.index if src.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            _lib.check(_lib.load().nesr_clahe_u8(index, ctypes.c_void_p(src.data_ptr()), h, w, float(clip_limit), gx, gy, ctypes.c_void_p(lut.data_ptr()),
-                                                 ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)), "nesr_clahe_u8")
+        _hip_call(src, "nesr_clahe_u8", src, h, w, float(clip_limit), gx, gy, lut, out)
         return out
     # clahe.cpp: only when BOTH sides divide by the grid is the image used as it is; otherwise copyMakeBorder pads the bottom by
     # tilesY - h % tilesY and the right by tilesX - w % tilesX -- a side that does divide gets a whole extra tilesY / tilesX pixels
@@ -502,17 +492,11 @@ def fast_nl_means_u8(planes, h, template=7, search=21, rows_per_block=0, use_hip
     if use_hip is None:
         use_hip = planes.device.type == "cuda" and template == 7 and search == 21 and 1 <= C <= 3
     if use_hip:
-        import ctypes
-        from . import _lib
         nz = int((wt != 0).sum().item())                                             # the weights fall monotonically to 0: a short table is enough
         lut = wt[:max(nz + 1, 1)].to(torch.int32).to(planes.device)
         src = planes.contiguous()
         out = torch.empty_like(src)
-        index = src.device.index if src.device.index is not None else torch.cuda.current_device()
-        with torch.cuda.device(src.device):
-            stream = torch.cuda.current_stream(src.device).cuda_stream
-            _lib.check(_lib.load().nesr_nl_means_u8(index, ctypes.c_void_p(src.data_ptr()), C, H, W, template, search, ctypes.c_void_p(lut.data_ptr()),
-                                                    lut.numel(), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream)), "nesr_nl_means_u8")
+        _hip_call(src, "nesr_nl_means_u8", src, C, H, W, template, search, lut, lut.numel(), out)
         return out
     tr, sr = template // 2, search // 2
     border = tr + sr

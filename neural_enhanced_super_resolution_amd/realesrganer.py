@@ -444,17 +444,18 @@ class RealESRGANer:
         tiles, owner = plan_tiles(self, height, width, len(self.devices))
         return tiles, [[i for i, o in enumerate(owner) if o == j] for j in range(len(self.devices))]
 
+    def _lane_slots(self):
+        """[(device, occurrence)] per entry of `devices`: occurrence = earlier entries with the same index."""
+        return [(torch.device("cuda", d), self.devices[:j].count(d)) for j, d in enumerate(self.devices)]
+
     def _lanes(self):
         """[(device, occurrence, stream)] per entry of `devices`: occurrence = earlier entries with the same index (it picks
         the lane's context replicas).  The first entry runs on the caller's current stream, as the one-device wrapper does;
         the others on streams of their own, kept across frames."""
         if not hasattr(self, "_lane_streams"):
             self._lane_streams = {}
-        lanes, seen = [], {}
-        for j, d in enumerate(self.devices):
-            dev = torch.device("cuda", d)
-            o = seen.get(d, 0)
-            seen[d] = o + 1
+        lanes = []
+        for j, (dev, o) in enumerate(self._lane_slots()):
             if j == 0:
                 st = torch.cuda.current_stream(dev)
             else:
@@ -632,6 +633,10 @@ class RealESRGANer:
         The RRDB-only paths (ragged batches, the strip kernel, preferred batch sizes, the declared-scale fix) test RRDBNet."""
         return isinstance(self.model, (RRDBNet, SRVGGNetCompact))
 
+    def _mod_factor(self):
+        """What the sides of a frame must be multiples of to need no mod-pad (_pad_on_device: 2 for scale 2, 4 for scale 1)."""
+        return {2: 2, 1: 4}.get(self.scale, 1)
+
     def _fused_u8_ok(self, img):
         """The fused u8 kernel path applies when the call reduces to one network evaluation of a
         plain 8-bit BGR frame: no tiling needed, no pre_pad / mod_pad, HIP-backed model."""
@@ -642,7 +647,7 @@ class RealESRGANer:
         h, w = img.shape[:2]
         if self.tile_size > 0 and (h > self.tile_size or w > self.tile_size):
             return False
-        ms = {2: 2, 1: 4}.get(self.scale, 1)
+        ms = self._mod_factor()
         if h % ms or w % ms:
             return False
         return self.model.num_in_ch == 3 and self.model.num_out_ch == 3 and self.model.out_scale() == self.scale
@@ -657,7 +662,7 @@ class RealESRGANer:
     def _u8_tiles_fused_ok(self, h, w):
         """8-bit frames larger than a tile whose tiles run as ragged batches (bf16, strip kernel): cut and paste are one launch
         each and the float canvas of the frame never exists.  Frames that need the reflect pre-pad / mod-pad keep the general path."""
-        ms = {2: 2, 1: 4}.get(self.scale, 1)
+        ms = self._mod_factor()
         return (self.tile_size > 0 and self.pre_pad == 0 and h % ms == 0 and w % ms == 0 and isinstance(self.model, RRDBNet)
                 and self.model.compute_dtype in RAGGED_FORMS and self.model.strip_kernel_active() and self.ragged_tiles is None
                 and self.model.out_scale() == self.scale)
@@ -805,11 +810,8 @@ class RealESRGANer:
         range error the frames still in flight are waited for and their contexts cleared before it is raised."""
         from ._lib import NesrHipError, NesrRangeError
         n = len(self.devices)
-        lanes, seen = [], {}
-        for d in self.devices:
-            dev = torch.device("cuda", d)
-            o = seen.get(d, 0)
-            seen[d] = o + 1
+        lanes = []
+        for dev, o in self._lane_slots():
             caller = torch.cuda.current_stream(dev)
             sts = [torch.cuda.Stream(dev) for _ in range(inflight)]
             for st in sts:
@@ -892,7 +894,7 @@ class RealESRGANer:
         if self._multi() or not self._device_frame_ok(img) or self._u8_on_device_ok(img) or self.pre_pad != 0:
             return False
         h, w = img.shape[:2]
-        ms = {2: 2, 1: 4}.get(self.scale, 1)
+        ms = self._mod_factor()
         return not (self.tile_size > 0 and (h > self.tile_size or w > self.tile_size)) and h % ms == 0 and w % ms == 0
 
     @torch.no_grad()

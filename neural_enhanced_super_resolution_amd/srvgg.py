@@ -18,7 +18,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .rrdbnet import RRDBNet, _ConvParams
+from ._contexts import _HipNet
+from .rrdbnet import _ConvParams
 
 ACT_TYPES = {"prelu": _lib.ACT_PRELU, "relu": _lib.ACT_RELU, "leakyrelu": _lib.ACT_LEAKYRELU}
 
@@ -69,13 +70,14 @@ class _NoParams(nn.Module):
         raise RuntimeError("SRVGGNetCompact.forward runs in libnesr_hip.so")
 
 
-class SRVGGNetCompact(nn.Module):
+class SRVGGNetCompact(_HipNet):
     """Compact VGG-style super-resolution network (Real-ESRGAN's realesr-*-v3 models).
 
     Args mirror upstream: num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type='prelu'.
     Extra keyword ``compute_dtype``: "f32" (default; operands as f16 pairs, three f16 MFMAs per product, values beyond
     +-65504 raise NesrRangeError) or "bf16" (what ``.half()`` / ``.to(torch.bfloat16)`` select, as for RRDBNet).
     The HIP path supports num_feat 64, num_in_ch == num_out_ch == 3 and upscale 2 or 4.
+    The contexts, replicas, forward calls and range checks are _HipNet's (the C ABI is RRDBNet's; only creation differs).
     """
 
     def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu", compute_dtype="f32"):
@@ -95,47 +97,9 @@ class SRVGGNetCompact(nn.Module):
             mods += [_ConvParams(num_feat, num_feat), self._act()]
         mods.append(_ConvParams(num_feat, num_out_ch * upscale * upscale))
         self.body = nn.ModuleList(mods)
-        self.calls = 0
-        self._ctx = None          # (ctypes handle, device index, dtype code): slot 0
-        self._dirty = True
-        self._extra = {}          # slot -> replica context for concurrent streams
-        self._peers = {}          # (device index, slot) -> context on a device other than slot 0's
 
     def _act(self):
         return _PReLUParams(self.num_feat) if self.act_type == "prelu" else _NoParams()
-
-    # the context / replica / range machinery is RRDBNet's (the C ABI is the same; only creation differs)
-    _release = RRDBNet._release
-    __del__ = RRDBNet.__del__
-    _upload = RRDBNet._upload
-    _context = RRDBNet._context
-    _peer_context = RRDBNet._peer_context
-    _handle = RRDBNet._handle
-    _handles = RRDBNet._handles
-    reserve = RRDBNet.reserve
-    check_status = RRDBNet.check_status
-    check_range = RRDBNet.check_range
-    kernel_time = RRDBNet.kernel_time
-    forward_u8 = RRDBNet.forward_u8
-
-    def load_state_dict(self, state_dict, strict=True, **kw):
-        out = super().load_state_dict(state_dict, strict=strict, **kw)
-        self._dirty = True
-        return out
-
-    def half(self):
-        """Upstream's fp16 switch (RealESRGANer(half=True) calls model.half()): selects the bf16 kernels; the parameters
-        stay float32, so the bf16 weights are rounded once from the checkpoint's values."""
-        self.compute_dtype = "bf16"
-        self._dirty = True
-        return self
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._dirty = True
-        if self.body[0].weight.dtype in (torch.float16, torch.bfloat16):
-            self.compute_dtype = "bf16"
-        return out
 
     def _dtype_code(self):
         if self.compute_dtype in ("f32", "fp32", torch.float32, "f32-split", "split"):
@@ -150,44 +114,11 @@ class SRVGGNetCompact(nn.Module):
                                                    self.num_conv, self.upscale, ACT_TYPES[self.act_type], code), "nesr_create_compact")
         return handle
 
-    # ------------------------------------------------------------------ forward
     def out_scale(self):
         return self.upscale
-
-    def _require_cuda(self, x):
-        if x.device.type != "cuda":
-            raise RuntimeError(
-                "SRVGGNetCompact.forward runs only on an AMD GPU through libnesr_hip.so; got a tensor on "
-                f"{x.device}. There is no CPU/PyTorch fallback for this path.")
-
-    @torch.no_grad()
-    def forward(self, x, slot: int = 0):
-        """x: [N, num_in_ch, H, W] float on a ROCm device -> [N, num_out_ch, H*s, W*s].
-        `slot` selects a context replica; work is enqueued on torch's current stream."""
-        self._require_cuda(x)
-        if x.dim() != 4:
-            raise ValueError(f"expected NCHW input, got shape {tuple(x.shape)}")
-        in_dtype = x.dtype
-        xf = x.to(torch.float32).contiguous()
-        n, c, h, w = xf.shape
-        s = self.upscale
-        self.calls += 1
-        with torch.cuda.device(xf.device):
-            ctx = self._context(xf.device, slot)
-            y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xf.device)
-            stream = torch.cuda.current_stream(xf.device).cuda_stream
-            _lib.check(_lib.load().nesr_forward(ctx, ctypes.c_void_p(xf.data_ptr()), n, c, h, w,
-                                                ctypes.c_void_p(y.data_ptr()), ctypes.c_void_p(stream)), "nesr_forward")
-        return y if in_dtype == torch.float32 else y.to(in_dtype)
 
     def forward_flops(self, n, h, w):
         """Algorithmic FLOPs (2 x MACs) of one forward on [n, *, h, w]."""
         f = self.num_feat
         macs = 9 * (self.num_in_ch * f + self.num_conv * f * f + f * self.num_out_ch * self.upscale ** 2)
         return 2.0 * macs * n * h * w
-
-    def set_kernel_timing(self, device, enable=True):
-        self._context(torch.device(device))
-        self._kernel_timing = bool(enable)
-        for h in self._handles():
-            _lib.check(_lib.load().nesr_set_kernel_timing(h[0], 1 if enable else 0), "nesr_set_kernel_timing")
