@@ -12,17 +12,29 @@ Host logic only (padding, tile grid, cropping, colour order, quantisation); ever
 evaluation goes through ``self.model``, which for this package is the HIP-backed
 :class:`RRDBNet`.  cv2 is not needed: the colour conversions are plain numpy, and ``outscale != scale`` /
 ``alpha_upsampler != 'realesrgan'`` use imgproc.py's device-side restatement of cv2.resize (parity unpinned).
+
+The routes of a frame, in the order ``_enhance_once`` tries them (planning: _tiling.py; ``devices=`` lanes: _lanes.py):
+
+  _fused_u8_ok                      one forward_u8 call, inline in _enhance_once (enhance_many: _forward_u8_to_host)
+  _u8_on_device_ok                  _enhance_u8_on_device: _pad_on_device + _run(), quantised on the device
+    .. and _u8_tiles_fused_ok       _enhance_u8_tiles_fused (several devices: _enhance_u8_tiles_fused_devices)
+  _device_frame_ok                  _enhance_frame_on_device (enhance_many, _frame_inflight_ok: _frame_in_flight)
+  otherwise                         enhance_float on the host, then enhance's numpy quantiser
 """
 from __future__ import annotations
 
+import functools
 import math
-import os
+import types
 import warnings
 
 import numpy as np
 import torch
 from torch.nn import functional as F
 
+from . import _lanes, _tiling
+from ._lanes import parse_devices
+from ._lib import NesrHipError, NesrRangeError
 from .rrdbnet import RAGGED_FORMS, RRDBNet
 from .srvgg import SRVGGNetCompact
 
@@ -32,8 +44,8 @@ from .srvgg import SRVGGNetCompact
 HIP_RESIZE = True
 
 # Gray, BGRA and 16-bit frames (everything enhance() takes besides 8-bit BGR) stay on the device from the upload of the uint8 / uint16
-# frame to the one copy home of the quantised result (_enhance_frame_on_device: frame_io.pack_frame / unpack_frame around the same
-# _pad_on_device and _run()).  False: enhance_float's host route -- numpy preparation, float32 upload, float32 canvas download, numpy
+# frame to the one copy home of the quantised result (_enhance_frame_on_device: _frame_through's frame_io.pack_frame / unpack_frame
+# around the same _pad_on_device and _run()).  False: enhance_float's host route -- numpy preparation, float32 upload, float32 canvas download, numpy
 # clamp / flip / gray / quantiser; the two give the same bits.
 DEVICE_FRAMES = True
 
@@ -85,33 +97,30 @@ def _gray2rgb(img):
     return np.repeat(img[:, :, None], 3, axis=2)
 
 
-def parse_devices(devices, count):
-    """RealESRGANer's ``devices=`` keyword -> list of CUDA device indices, or None for the one-device wrapper.  With
-    ``devices=None`` the NESR_DEVICES environment variable (comma-separated indices, e.g. "0,1,2,3") is read instead, so
-    callers that cannot pass the keyword opt in from outside; unset or empty means None.  Repeated indices are allowed
-    (several contexts on one device).  An empty list, a non-integer or an index outside [0, count) raises ValueError."""
-    source = "devices"
-    if devices is None:
-        devices = os.environ.get("NESR_DEVICES", "").strip()
-        if not devices:
-            return None
-        source = "NESR_DEVICES"
-    if isinstance(devices, str):
-        try:
-            devices = [int(v) for v in devices.split(",")]
-        except ValueError:
-            raise ValueError(f"{source}={devices!r}: expected comma-separated CUDA device indices") from None
-    out = []
-    for d in devices:
-        if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
-            raise ValueError(f"{source}: {d!r} is not a CUDA device index")
-        out.append(int(d))
-    if not out:
-        raise ValueError(f"{source}: the device list is empty")
-    for d in out:
-        if d < 0 or d >= count:
-            raise ValueError(f"{source}: device {d} does not exist ({count} visible)")
-    return out
+def _is_gave_up(e):
+    """A persistent dense-block launch gave up waiting for its workgroups (not a range error): the frame can be evaluated again."""
+    return not isinstance(e, NesrRangeError) and "gave up waiting" in str(e)
+
+
+class _InFlight:
+    """enhance_many's frames in flight, oldest first: ``add(*entry)`` behind a frame's last enqueued work, on its stream;
+    ``collect(leave)`` waits for the oldest and calls ``finish(*entry)`` (context check, result) until `leave` are pending.
+    Errors are the caller's, and the two callers differ (as they always have; kept, not decided): enhance_many on one device lets
+    every error through -- no retry after a launch that gave up, the frames in flight not waited for; _enhance_many_devices does both."""
+
+    def __init__(self, finish):
+        self.finish, self.pending = finish, []     # pending: [(event, *entry)]
+
+    def add(self, *entry):
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append((ev,) + entry)
+
+    def collect(self, leave=0):
+        while len(self.pending) > leave:
+            ev, *entry = self.pending.pop(0)
+            ev.synchronize()
+            self.finish(*entry)
 
 
 class RealESRGANer:
@@ -283,41 +292,13 @@ class RealESRGANer:
         small edge-tile groups -- whose 351 launches are latency-bound -- overlap the large ones.
         Values do not depend on batching or stream assignment.  `slot_base`: the first context replica used (a lane of a
         multi-device frame, see _tile_process_devices, takes slots slot_base, slot_base + 1, ...)."""
-        groups = {}
-        for t in tiles:
-            groups.setdefault((t[1] - t[0], t[3] - t[2]), []).append(t)
-        order = sorted(groups.items(), key=lambda kv: -kv[0][0] * kv[0][1] * len(kv[1]))
         hip = self._hip_model() and img.device.type == "cuda"
         if hip and isinstance(self.model, RRDBNet) and img.shape[0] == 1 and self.model.compute_dtype in RAGGED_FORMS:
             ragged = self.model.strip_kernel_active() if self.ragged_tiles is None else bool(self.ragged_tiles)
-            if ragged and (len(order) > 1 or self.ragged_tiles is None):
+            if ragged and (len({(t[1] - t[0], t[3] - t[2]) for t in tiles}) > 1 or self.ragged_tiles is None):
                 return self._run_tiles_ragged(img, tiles, sink, single_stream=self.ragged_tiles is None, slot_base=slot_base)
-        # Batches of equal-shaped windows, one shape group per stream.  A small job (a rank's share of a sharded frame: five
-        # tiles of an 8-way split 4K frame, often of one shape) is spread wider: every batch its own unit, the largest
-        # halved until each of `small_job_streams` streams has one -- one stream would run 351 launches of a few hundred
-        # workgroups each, five overlap their prologues, epilogues and tails (measured on one GPU with an 8-rank share:
-        # 25.6 -> 16.9 ms for the slowest rank)
-        units = []                                    # a unit = the batches of one shape group, run in order on one stream
-        for shape, ts in order:
-            nb = self.batch_for(shape[0], shape[1], len(ts)) if img.shape[0] == 1 else 1
-            units.append([ts[i:i + nb] for i in range(0, len(ts), nb)])
-        nstreams = 1
-        if hip and len(tiles) > 1:
-            nstreams = max(1, int(self.tile_streams))
-            if len(tiles) <= self.small_job_tiles:
-                nstreams = min(max(nstreams, int(self.small_job_streams)), len(tiles))
-                units = [[b] for u in units for b in u]
-                while len(units) < nstreams:
-                    k = max(range(len(units)), key=lambda i: len(units[i][0]))
-                    b = units[k][0]
-                    if len(b) < 2:
-                        break
-                    units[k:k + 1] = [[b[:(len(b) + 1) // 2]], [b[(len(b) + 1) // 2:]]]
-            elif len(units) == 1:
-                nstreams = 1
-
-        def area(b):
-            return (b[0][1] - b[0][0]) * (b[0][3] - b[0][2]) * len(b)
+        plan = _tiling.shape_group_plan(tiles, self.batch_for if img.shape[0] == 1 else lambda *_: 1, self.tile_streams,
+                                        self.small_job_tiles, self.small_job_streams, multi=hip and len(tiles) > 1)
 
         def run_batch(chunk, slot):
             if len(chunk) == 1:
@@ -325,43 +306,40 @@ class RealESRGANer:
             else:
                 inp = torch.cat([img[:, :, t[0]:t[1], t[2]:t[3]] for t in chunk], 0)
             with torch.no_grad():
-                out = self.model(inp, slot=slot_base + slot) if hip else self.model(inp)
+                out = self.model(inp, slot=slot) if hip else self.model(inp)
             for j, t in enumerate(chunk):
                 sink(t[4], out[j:j + 1] if len(chunk) > 1 else out)
 
-        units.sort(key=lambda u: -sum(area(b) for b in u))
-        if nstreams == 1:
-            for u in units:
-                for b in u:
-                    run_batch(b, 0)
-            return
-        main = torch.cuda.current_stream(img.device)
-        streams = [main] + self._side_streams_for(img.device, slot_base, nstreams - 1)
-        for s in streams[1:]:
-            s.wait_stream(main)                       # img / the output canvas were produced on the main stream
-        load = [0] * nstreams
-        for u in units:                               # largest unit first, each to the least-loaded stream
-            k = load.index(min(load))
-            load[k] += sum(area(b) for b in u)
-            with torch.cuda.stream(streams[k]):
-                for b in u:
-                    run_batch(b, k)
-        for s in streams[1:]:
-            main.wait_stream(s)
+        self._fan_out(img.device, slot_base, plan, run_batch)
 
-    def _side_streams_for(self, device, slot_base, n):
-        """The `n` side streams run_tiles spreads a call over: one list for the first device's first lane (the one-device
-        wrapper's), one per other (device, slot_base) lane of a multi-device frame."""
-        if slot_base == 0 and (not self._multi() or device.index == self.device.index):
-            if not hasattr(self, "_side_streams") or len(self._side_streams) < n:
-                self._side_streams = [torch.cuda.Stream(device=device) for _ in range(n)]
-            return self._side_streams[:n]
-        if not hasattr(self, "_lane_side_streams"):
-            self._lane_side_streams = {}
-        have = self._lane_side_streams.setdefault((device.index, slot_base), [])
-        while len(have) < n:
-            have.append(torch.cuda.Stream(device=device))
-        return have[:n]
+    @functools.cached_property
+    def _streams(self):
+        """Streams kept across frames: side[(device index, slot_base)] _fan_out's, lane[entry of `devices`], gather (_lanes.py)."""
+        return types.SimpleNamespace(side={}, lane={}, gather=None)
+
+    def _fan_out(self, device, slot_base, plan, run_batch):
+        """Runs a _tiling plan: stream k's batches in order as ``run_batch(batch, slot_base + k)``, stream 0 being the current one;
+        the side streams first wait for it (the image and the output canvas were produced there) and it for them at the end."""
+        if len(plan) == 1:
+            for b in plan[0]:
+                run_batch(b, slot_base)
+            return
+        main = torch.cuda.current_stream(device)
+        side = self._streams.side.setdefault((device.index, slot_base), [])
+        while len(side) < len(plan) - 1:
+            side.append(torch.cuda.Stream(device=device))
+        streams = [main] + side[:len(plan) - 1]
+        for st in streams[1:]:
+            st.wait_stream(main)
+        for k, st in enumerate(streams):
+            with torch.cuda.stream(st):
+                for b in plan[k]:
+                    run_batch(b, slot_base + k)
+        for st in streams[1:]:
+            main.wait_stream(st)
+
+    def _ragged_cap(self):
+        return max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))   # tiles per ragged batch: what forward_ragged takes at most
 
     def _run_tiles_ragged(self, img, tiles, sink, single_stream=False, slot_base=0):
         """All windows of a frame, whatever their shapes, in `tile_streams` ragged batches that run side by side: every
@@ -373,19 +351,9 @@ class RealESRGANer:
         window's values are the ones model(window) gives it alone."""
         if not self.model.size_independent:
             self.model.size_independent = True
-        cap = max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))
         # (strip kernel: one batch after the other on one stream -- a persistent launch holds the whole device)
         nstreams = 1 if single_stream else max(1, min(int(self.tile_streams), len(tiles)))
-        # largest first, each to the least-loaded batch; a batch that is full opens another one on the same stream
-        ts = sorted(tiles, key=lambda t: -(t[1] - t[0]) * (t[3] - t[2]))
-        lanes = [[[]] for _ in range(nstreams)]
-        load = [0] * nstreams
-        for t in ts:
-            k = load.index(min(load))
-            load[k] += (t[1] - t[0]) * (t[3] - t[2])
-            if len(lanes[k][-1]) == cap:
-                lanes[k].append([])
-            lanes[k][-1].append(t)
+        plan = _tiling.ragged_plan(tiles, nstreams, self._ragged_cap())
 
         def run_batch(chunk, slot):
             H = max(t[1] - t[0] for t in chunk)
@@ -394,26 +362,12 @@ class RealESRGANer:
             for j, t in enumerate(chunk):
                 x[j, :, :t[1] - t[0], :t[3] - t[2]] = img[0, :, t[0]:t[1], t[2]:t[3]]
             with torch.no_grad():
-                out = self.model.forward_ragged(x, [(t[1] - t[0], t[3] - t[2]) for t in chunk], slot=slot_base + slot)
+                out = self.model.forward_ragged(x, [(t[1] - t[0], t[3] - t[2]) for t in chunk], slot=slot)
             s = out.shape[2] // H
             for j, t in enumerate(chunk):
                 sink(t[4], out[j:j + 1, :, :(t[1] - t[0]) * s, :(t[3] - t[2]) * s])
 
-        if nstreams == 1:
-            for chunk in lanes[0]:
-                run_batch(chunk, 0)
-            return
-        main = torch.cuda.current_stream(img.device)
-        streams = [main] + self._side_streams_for(img.device, slot_base, nstreams - 1)
-        for st in streams[1:]:
-            st.wait_stream(main)
-        for k in range(nstreams):
-            with torch.cuda.stream(streams[k]):
-                for chunk in lanes[k]:
-                    if chunk:
-                        run_batch(chunk, k)
-        for st in streams[1:]:
-            main.wait_stream(st)
+        self._fan_out(img.device, slot_base, plan, run_batch)
 
     def tile_process(self):
         """Runs the network on overlapping tiles and pastes the un-padded centres (upstream
@@ -444,109 +398,41 @@ class RealESRGANer:
         tiles, owner = plan_tiles(self, height, width, len(self.devices))
         return tiles, [[i for i, o in enumerate(owner) if o == j] for j in range(len(self.devices))]
 
-    def _lane_slots(self):
-        """[(device, occurrence)] per entry of `devices`: occurrence = earlier entries with the same index."""
-        return [(torch.device("cuda", d), self.devices[:j].count(d)) for j, d in enumerate(self.devices)]
-
-    def _lanes(self):
-        """[(device, occurrence, stream)] per entry of `devices`: occurrence = earlier entries with the same index (it picks
-        the lane's context replicas).  The first entry runs on the caller's current stream, as the one-device wrapper does;
-        the others on streams of their own, kept across frames."""
-        if not hasattr(self, "_lane_streams"):
-            self._lane_streams = {}
-        lanes = []
-        for j, (dev, o) in enumerate(self._lane_slots()):
-            if j == 0:
-                st = torch.cuda.current_stream(dev)
-            else:
-                st = self._lane_streams.get(j)
-                if st is None:
-                    st = self._lane_streams[j] = torch.cuda.Stream(device=dev)
-            lanes.append((dev, o, st))
-        return lanes
-
-    def _gather_stream(self):
-        """A stream on the first device that carries the copies between devices, so they wait for no lane of that device."""
-        if getattr(self, "_gather", None) is None:
-            self._gather = torch.cuda.Stream(device=self.device)
-        return self._gather
-
-    def _send_home(self, flat, lane_stream, gather, items, dst):
-        """`flat` (contiguous, on a lane's device, written on `lane_stream`) -> one device-to-device copy to the first device
-        on `gather`, whose slices [offset, offset + numel) are then pasted into dst[index] (items: [(offset, shape, index)]).
-        Every tensor involved is used on the stream it was allocated on, so none has to outlive the call."""
-        with torch.cuda.stream(gather):
-            with torch.cuda.stream(lane_stream):
-                buf = torch.empty(flat.shape, dtype=flat.dtype, device=dst.device)
-                buf.copy_(flat, non_blocking=True)      # on the lane's stream, after its tiles; `gather` waits for it
-            for off, shape, index in items:
-                n = int(np.prod(shape))
-                dst[index] = buf[off:off + n].view(shape)
-
-    def _join_lanes(self, lanes, gather):
-        """Every device's current stream waits for the lanes on it (and the first device's for the copies home)."""
-        for dev, _, st in lanes:
-            cur = torch.cuda.current_stream(dev)
-            if st != cur:
-                cur.wait_stream(st)
-        torch.cuda.current_stream(self.device).wait_stream(gather)
-
     @torch.no_grad()
     def _tile_process_devices(self):
         """tile_process with the tiles split over `devices`: every device gets the padded image (one copy from the first
         device), runs its share through run_tiles on its lane's stream and replicas, and the un-padded centres come back to
         self.output on the first device.  The first device's lanes paste straight into self.output."""
         _, channel, height, width = self.img.shape
-        s = self.scale
         dev0 = self.img.device
-        self.output = self.img.new_zeros((1, channel, height * s, width * s))
+        self.output = self.img.new_zeros((1, channel, height * self.scale, width * self.scale))
         tiles, shares = self.device_shares(height, width)
-        lanes = self._lanes()
-        main = torch.cuda.current_stream(dev0)
-        gather = self._gather_stream()
-        gather.wait_stream(main)                        # the padded image and the output canvas
+        lanes, gather = _lanes.lanes(self.devices, self._streams, self.device)
         stride = max(1, int(self.tile_streams), int(self.small_job_streams))   # replicas one lane's run_tiles may use
-        imgs = {dev0.index: (self.img, None)}          # device index -> (the padded image there, event behind its copy)
-        for (dev, _, st), share in zip(lanes, shares):
-            if share and st != torch.cuda.current_stream(dev):
-                st.wait_stream(torch.cuda.current_stream(dev))   # the lane's replicas may still be in use there
-        for (dev, _, st), share in zip(lanes, shares):
-            if share and dev.index not in imgs:
-                with torch.cuda.stream(gather), torch.cuda.stream(st):
-                    img = self.img.to(dev, non_blocking=True)      # copied on `gather`; `st` waits for it (and so does `ev`)
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                imgs[dev.index] = (img, ev)
-        for (dev, o, st), share in zip(lanes, shares):
-            if not share:
-                continue
-            img, ev = imgs[dev.index]
-            with torch.cuda.device(dev), torch.cuda.stream(st):
-                if ev is not None:
-                    st.wait_event(ev)                   # every lane of the device, not only the one the copy was made for
-                    img.record_stream(st)               # read here after this call has returned: not freed before
+
+        def copy(dev, st):
+            with torch.cuda.stream(gather), torch.cuda.stream(st):
+                return self.img.to(dev, non_blocking=True)         # copied on `gather`; `st` waits for it (and so does its event)
+        def run_share(dev, o, st, share, img):
+            if img is not self.img:
+                img.record_stream(st)                   # read here after this call has returned: not freed before
+            pieces = []
+            def sink(t, out):
+                p = out[:, :, t.crop[0]:t.crop[1], t.crop[2]:t.crop[3]]
                 if dev.index == dev0.index:
-                    pieces = None
-
-                    def sink(t, out):
-                        self.output[:, :, t.out[0]:t.out[1], t.out[2]:t.out[3]] = out[:, :, t.crop[0]:t.crop[1], t.crop[2]:t.crop[3]]
+                    self.output[:, :, t.out[0]:t.out[1], t.out[2]:t.out[3]] = p
                 else:
-                    pieces = []
+                    pieces.append((t, p.contiguous()))       # made on one of run_tiles' streams ...
+                    pieces[-1][1].record_stream(st)          # ... read on the lane's
+            self.run_tiles(img, [(t.inp[0], t.inp[1], t.inp[2], t.inp[3], t) for t in (tiles[i] for i in share)], sink,
+                           slot_base=o * stride)
+            items, off = [], 0
+            for t, p in pieces:
+                items.append((off, tuple(p.shape), (slice(None), slice(None), slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3]))))
+                off += p.numel()
+            return (torch.cat([p.reshape(-1) for _, p in pieces]), items) if pieces else None
 
-                    def sink(t, out, pieces=pieces, st=st):
-                        p = out[:, :, t.crop[0]:t.crop[1], t.crop[2]:t.crop[3]].contiguous()   # on one of run_tiles' streams ...
-                        p.record_stream(st)                                                   # ... read on the lane's
-                        pieces.append((t, p))
-                self.run_tiles(img, [(t.inp[0], t.inp[1], t.inp[2], t.inp[3], t) for t in (tiles[i] for i in share)], sink,
-                               slot_base=o * stride)
-                if pieces:
-                    flat = torch.cat([p.reshape(-1) for _, p in pieces])
-                    items, off = [], 0
-                    for t, p in pieces:
-                        items.append((off, tuple(p.shape), (slice(None), slice(None), slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3]))))
-                        off += p.numel()
-                    self._send_home(flat, st, gather, items, self.output)
-        self._join_lanes(lanes, gather)
+        _lanes.run_shares(lanes, shares, gather, self.output, {dev0.index: (self.img, None)}, copy, run_share)
 
     @torch.no_grad()
     def _enhance_u8_tiles_fused_devices(self, img):
@@ -558,55 +444,35 @@ class RealESRGANer:
         s = self.scale
         dev0 = self.device
         tiles, shares = self.device_shares(h, w)
-        lanes = self._lanes()
-        cap = max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))
+        lanes, gather = _lanes.lanes(self.devices, self._streams, self.device)
+        cap = self._ragged_cap()
         for (dev, o, _), share in zip(lanes, shares):
             for i in range(0, len(share), cap):
                 part = [tiles[k] for k in share[i:i + cap]]
                 self.model.reserve(dev, len(part), max(t.inp[1] - t.inp[0] for t in part), max(t.inp[3] - t.inp[2] for t in part), slot=o)
         main = torch.cuda.current_stream(dev0)
-        gather = self._gather_stream()
         pinned = torch.from_numpy(np.ascontiguousarray(img)).pin_memory()
         canvas = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=dev0)
-        gather.wait_stream(main)
-        for (dev, _, st), share in zip(lanes, shares):
-            if share and st != torch.cuda.current_stream(dev):
-                st.wait_stream(torch.cuda.current_stream(dev))   # the canvas; the lane's replica may still be in use there
-        frames = {}                                     # device index -> (the frame there, event behind its upload)
-        for (dev, _, st), share in zip(lanes, shares):
-            if share and dev.index not in frames:
-                with torch.cuda.device(dev), torch.cuda.stream(st):
-                    f = pinned.to(dev, non_blocking=True)   # H2D: uint8 HWC BGR
-                    ev = torch.cuda.Event()
-                    ev.record(st)
-                frames[dev.index] = (f, ev)
-        for (dev, o, st), share in zip(lanes, shares):
-            if not share:
-                continue
-            mine = [tiles[i] for i in share]
-            windows = [(t.inp[0], t.inp[2], t.inp[1] - t.inp[0], t.inp[3] - t.inp[2]) for t in mine]
-            frame, ev = frames[dev.index]
+
+        def copy(dev, st):
             with torch.cuda.device(dev), torch.cuda.stream(st):
-                st.wait_event(ev)
-                if dev.index == dev0.index:
-                    pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], (t.out[0] * w * s + t.out[2]) * 3, w * s * 3)
-                              for t in mine]
-                    self.tiles_u8_on_device(frame, windows, pastes, canvas, slot=o)
-                else:
-                    offs = [0]
-                    for t in mine:
-                        offs.append(offs[-1] + (t.out[1] - t.out[0]) * (t.out[3] - t.out[2]) * 3)
-                    packed = torch.empty((offs[-1],), dtype=torch.uint8, device=dev)
-                    pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], offs[i], (t.out[3] - t.out[2]) * 3)
-                              for i, t in enumerate(mine)]
-                    self.tiles_u8_on_device(frame, windows, pastes, packed, slot=o)
-                    items = [(offs[i], (t.out[1] - t.out[0], t.out[3] - t.out[2], 3), (slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3])))
-                             for i, t in enumerate(mine)]
-                    self._send_home(packed, st, gather, items, canvas)
-        self._join_lanes(lanes, gather)
+                return pinned.to(dev, non_blocking=True)   # H2D: uint8 HWC BGR
+        def run_share(dev, o, st, share, frame):
+            mine = [tiles[i] for i in share]
+            if dev.index == dev0.index:
+                self.tiles_u8_on_device(frame, _tiling.windows(mine), _tiling.canvas_pastes(mine, w * s), canvas, slot=o)
+                return None
+            pastes, offs = _tiling.packed_pastes(mine)
+            packed = torch.empty((offs[-1],), dtype=torch.uint8, device=dev)
+            self.tiles_u8_on_device(frame, _tiling.windows(mine), pastes, packed, slot=o)
+            return packed, [(offs[i], (t.out[1] - t.out[0], t.out[3] - t.out[2], 3), (slice(t.out[0], t.out[1]), slice(t.out[2], t.out[3])))
+                            for i, t in enumerate(mine)]
+
+        frames = {}                                     # device index -> (the frame there, the event behind its copy)
+        _lanes.run_shares(lanes, shares, gather, canvas, frames, copy, run_share)
         host = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(canvas, non_blocking=True)
-        main.synchronize()                              # every lane and copy is behind it (_join_lanes)
+        main.synchronize()                              # every lane and copy is behind it (run_shares' join)
         del frames                                      # (read by every lane of their device: freed only now)
         self._check_range()
         return host.numpy()
@@ -633,24 +499,21 @@ class RealESRGANer:
         The RRDB-only paths (ragged batches, the strip kernel, preferred batch sizes, the declared-scale fix) test RRDBNet."""
         return isinstance(self.model, (RRDBNet, SRVGGNetCompact))
 
-    def _mod_factor(self):
-        """What the sides of a frame must be multiples of to need no mod-pad (_pad_on_device: 2 for scale 2, 4 for scale 1)."""
-        return {2: 2, 1: 4}.get(self.scale, 1)
+    def _one_evaluation(self, h, w, tiled=False):
+        """A h x w frame is a single network evaluation: no tiling, pre_pad or mod-pad (`tiled`: one per tile, it may need tiling)."""
+        ms = {2: 2, 1: 4}.get(self.scale, 1)        # _pad_on_device's mod-pad: 2 for scale 2, 4 for scale 1
+        fits = not (self.tile_size > 0 and (h > self.tile_size or w > self.tile_size))
+        return (tiled or fits) and self.pre_pad == 0 and h % ms == 0 and w % ms == 0
+
+    def _three_channel_hip(self):
+        """A HIP model on cuda of three channels in and out whose output is `scale` times its input."""
+        return (self._hip_model() and self.device.type == "cuda" and self.model.num_in_ch == 3 and self.model.num_out_ch == 3
+                and self.model.out_scale() == self.scale)
 
     def _fused_u8_ok(self, img):
         """The fused u8 kernel path applies when the call reduces to one network evaluation of a
         plain 8-bit BGR frame: no tiling needed, no pre_pad / mod_pad, HIP-backed model."""
-        if not self._hip_model() or self.device.type != "cuda":
-            return False
-        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or self.pre_pad != 0:
-            return False
-        h, w = img.shape[:2]
-        if self.tile_size > 0 and (h > self.tile_size or w > self.tile_size):
-            return False
-        ms = self._mod_factor()
-        if h % ms or w % ms:
-            return False
-        return self.model.num_in_ch == 3 and self.model.num_out_ch == 3 and self.model.out_scale() == self.scale
+        return self._u8_on_device_ok(img) and self._one_evaluation(*img.shape[:2]) and self._three_channel_hip()
 
     def _u8_on_device_ok(self, img):
         """8-bit BGR frames on the HIP backend (any tiling / padding): the uint8 frame is uploaded
@@ -662,8 +525,7 @@ class RealESRGANer:
     def _u8_tiles_fused_ok(self, h, w):
         """8-bit frames larger than a tile whose tiles run as ragged batches (bf16, strip kernel): cut and paste are one launch
         each and the float canvas of the frame never exists.  Frames that need the reflect pre-pad / mod-pad keep the general path."""
-        ms = self._mod_factor()
-        return (self.tile_size > 0 and self.pre_pad == 0 and h % ms == 0 and w % ms == 0 and isinstance(self.model, RRDBNet)
+        return (self.tile_size > 0 and self._one_evaluation(h, w, tiled=True) and isinstance(self.model, RRDBNet)
                 and self.model.compute_dtype in RAGGED_FORMS and self.model.strip_kernel_active() and self.ragged_tiles is None
                 and self.model.out_scale() == self.scale)
 
@@ -673,7 +535,7 @@ class RealESRGANer:
         offset, dst row pitch)] -> the tiles' quantised centres in dst_u8 (uint8, on the device).  Ragged batches of at most
         RAGGED_MAX tiles: cut (nesr_cut_tiles_u8), forward_ragged on context replica `slot`, paste (nesr_paste_tiles_u8)."""
         from .rrdbnet import cut_tiles_u8, paste_tiles_u8
-        cap = max(1, min(self.model.RAGGED_MAX, int(self.ragged_batch)))
+        cap = self._ragged_cap()
         for i in range(0, len(windows), cap):
             win, pst = windows[i:i + cap], pastes[i:i + cap]
             hs, ws = max(v[2] for v in win), max(v[3] for v in win)
@@ -690,11 +552,8 @@ class RealESRGANer:
         s = self.scale
         frame = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)          # H2D: uint8 HWC BGR
         canvas = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=self.device)
-        windows, pastes = [], []
-        for (py0, py1, px0, px1), (oy0, oy1, ox0, ox1), (cy0, cy1, cx0, cx1) in self.tile_grid(h, w):
-            windows.append((py0, px0, py1 - py0, px1 - px0))
-            pastes.append((cy0, cx0, cy1 - cy0, cx1 - cx0, (oy0 * w * s + ox0) * 3, w * s * 3))
-        self.tiles_u8_on_device(frame, windows, pastes, canvas)
+        tiles = [_tiling.Tile(i, *g) for i, g in enumerate(self.tile_grid(h, w))]
+        self.tiles_u8_on_device(frame, _tiling.windows(tiles), _tiling.canvas_pastes(tiles, w * s), canvas)
         if resize_to is not None:
             canvas = self._resize_u8_on_device(canvas, resize_to)
         host = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)          # (the caching host allocator recycles these)
@@ -751,6 +610,15 @@ class RealESRGANer:
         if self._hip_model():
             self.model.check_range(slot)
 
+    def _forward_u8_to_host(self, img, device, slot):
+        """A frame in flight: an 8-bit BGR frame through forward_u8 on `device`'s context replica `slot`, enqueued on the current
+        stream -- pinned upload, network, copy into the pinned host tensor that is returned."""
+        x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(device, non_blocking=True)
+        y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=slot)
+        host = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(y, non_blocking=True)
+        return host
+
     @torch.no_grad()
     def enhance_many(self, imgs, inflight=4):
         """``[self.enhance(img) for img in imgs]`` with up to `inflight` frames on the GPU at once.
@@ -758,10 +626,9 @@ class RealESRGANer:
         Not part of upstream's API: a frame whose network layers are only a few hundred workgroups (512x512:
         256-512 per layer in one round, all in the same phase) leaves the GPU idle a third of the time; a second frame on its own HIP
         stream and context replica fills it (bench.py's default `value`: 134 -> 160 / 167 / 170 MP/s with 2 / 3 / 4 frames
-        in flight, no more beyond).  Gray, BGRA
-        and 16-bit frames that need no tiling or padding join the frames in flight (_frame_in_flight), in any mix; a list with a
-        frame that needs tiling or padding is processed one frame at a time.
-        The results are identical to enhance()'s."""
+        in flight, no more beyond).  Gray, BGRA and 16-bit frames that need no tiling or padding join the frames in flight
+        (_frame_in_flight), in any mix; a list with a frame that needs tiling or padding is processed one frame at a time.
+        The results are identical to enhance()'s.  Errors: see _InFlight."""
         from .frame_io import frame_to_numpy
         imgs = list(imgs)
         if self._multi() and imgs and all(self._fused_u8_ok(i) for i in imgs):
@@ -772,32 +639,24 @@ class RealESRGANer:
         caller = torch.cuda.current_stream(self.device)
         for st in streams:
             st.wait_stream(caller)     # the context workspaces (slot 0 is the caller's own) may still be in use there
-        results, pending = [None] * len(imgs), []
+        results = [None] * len(imgs)
 
-        def finish(entry):
-            idx, host, ev, mode = entry
-            ev.synchronize()
+        def finish(idx, host, mode):
             with torch.cuda.stream(streams[idx % inflight]):
                 self._check_range(idx % inflight)
             results[idx] = (frame_to_numpy(host).copy(), mode)
 
+        queue = _InFlight(finish)
         for i, img in enumerate(imgs):
-            if len(pending) >= inflight:
-                finish(pending.pop(0))
+            queue.collect(leave=inflight - 1)
             k = i % inflight
             with torch.cuda.stream(streams[k]):
                 if self._fused_u8_ok(img):
-                    x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(self.device, non_blocking=True)
-                    y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=k)
-                    host, mode = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True), "RGB"
-                    host.copy_(y, non_blocking=True)
+                    host, mode = self._forward_u8_to_host(img, self.device, k), "RGB"
                 else:
                     host, mode = self._frame_in_flight(img, "realesrgan", k)
-                ev = torch.cuda.Event()
-                ev.record()
-            pending.append((i, host, ev, mode))
-        for entry in pending:
-            finish(entry)
+                queue.add(i, host, mode)
+        queue.collect()
         for st in streams:
             caller.wait_stream(st)
         return results
@@ -808,58 +667,48 @@ class RealESRGANer:
         its own and context replica occurrence * inflight + k of its device (k = the frame's place among the entry's in
         flight).  Results in input order.  A frame whose persistent launch gave up is evaluated again by enhance(); after a
         range error the frames still in flight are waited for and their contexts cleared before it is raised."""
-        from ._lib import NesrHipError, NesrRangeError
         n = len(self.devices)
         lanes = []
-        for dev, o in self._lane_slots():
+        for dev, o in _lanes.lane_slots(self.devices):
             caller = torch.cuda.current_stream(dev)
             sts = [torch.cuda.Stream(dev) for _ in range(inflight)]
             for st in sts:
                 st.wait_stream(caller)     # the context workspaces may still be in use there
             lanes.append((dev, o, sts))
-        results, pending = [None] * len(imgs), []
+        results = [None] * len(imgs)
 
-        def finish(entry):
-            idx, host, ev, dev, slot, st = entry
-            ev.synchronize()
+        def check(dev, slot, st):
+            with torch.cuda.device(dev), torch.cuda.stream(st):
+                self.model.check_range(slot, device=dev)
+
+        def finish(idx, host, *where):
             try:
-                with torch.cuda.device(dev), torch.cuda.stream(st):
-                    self.model.check_range(slot, device=dev)
-            except NesrRangeError:
-                raise
+                check(*where)
             except NesrHipError as e:
-                if "gave up waiting" not in str(e):
+                if not _is_gave_up(e):
                     raise
                 warnings.warn(f"{e}; evaluating the frame again")
-                for other in pending:      # enhance() takes the first device's slot 0, which a frame in flight may hold
-                    other[2].synchronize()
+                for ev, *_ in queue.pending:   # enhance() takes the first device's slot 0, which a frame in flight may hold
+                    ev.synchronize()
                 results[idx] = self.enhance(imgs[idx])
                 return
             results[idx] = (host.numpy().copy(), "RGB")
 
+        queue = _InFlight(finish)
         try:
             for i, img in enumerate(imgs):
-                if len(pending) >= inflight * n:
-                    finish(pending.pop(0))
+                queue.collect(leave=inflight * n - 1)
                 dev, o, sts = lanes[i % n]
                 k = (i // n) % inflight
                 st, slot = sts[k], o * inflight + k
                 with torch.cuda.device(dev), torch.cuda.stream(st):
-                    x = torch.from_numpy(np.ascontiguousarray(img)).pin_memory().to(dev, non_blocking=True)
-                    y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True, slot=slot)
-                    host = torch.empty(y.shape, dtype=torch.uint8, pin_memory=True)
-                    host.copy_(y, non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                pending.append((i, host, ev, dev, slot, st))
-            while pending:
-                finish(pending.pop(0))
+                    queue.add(i, self._forward_u8_to_host(img, dev, slot), dev, slot, st)
+            queue.collect()
         except NesrHipError:
-            for entry in pending:          # the next frame starts clean on every device
-                entry[2].synchronize()
+            for ev, _, _, *where in queue.pending:   # the next frame starts clean on every device
+                ev.synchronize()
                 try:
-                    with torch.cuda.device(entry[3]), torch.cuda.stream(entry[5]):
-                        self.model.check_range(entry[4], device=entry[3])
+                    check(*where)
                 except NesrHipError:
                     pass
             raise
@@ -873,13 +722,8 @@ class RealESRGANer:
     def _device_frame_ok(self, img):
         """A frame enhance_float would take (gray, BGRA, 16 bit; 8-bit BGR has routes of its own) on a HIP model of three channels
         in and out whose output is `scale` times its input: the frame stays on the device (_enhance_frame_on_device)."""
-        if not DEVICE_FRAMES or not self._hip_model() or self.device.type != "cuda":
-            return False
-        if not isinstance(img, np.ndarray) or img.dtype not in (np.uint8, np.uint16) or img.size == 0:
-            return False
-        if img.ndim != 2 and not (img.ndim == 3 and img.shape[2] in (3, 4)):
-            return False
-        return self.model.num_in_ch == 3 and self.model.num_out_ch == 3 and self.model.out_scale() == self.scale
+        return (DEVICE_FRAMES and self._three_channel_hip() and isinstance(img, np.ndarray) and img.dtype in (np.uint8, np.uint16)
+                and img.size != 0 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))))
 
     @staticmethod
     def _frame_kind(img):
@@ -891,55 +735,49 @@ class RealESRGANer:
     def _frame_inflight_ok(self, img):
         """enhance_many: a frame of _device_frame_ok's kinds that is one network evaluation per plane set (no tiling, pre_pad or
         mod-pad), so it can run on a stream and context replica of its own."""
-        if self._multi() or not self._device_frame_ok(img) or self._u8_on_device_ok(img) or self.pre_pad != 0:
-            return False
-        h, w = img.shape[:2]
-        ms = self._mod_factor()
-        return not (self.tile_size > 0 and (h > self.tile_size or w > self.tile_size)) and h % ms == 0 and w % ms == 0
+        return (not self._multi() and self._device_frame_ok(img) and not self._u8_on_device_ok(img)
+                and self._one_evaluation(*img.shape[:2]))
+
+    def _frame_through(self, img, frame, alpha_upsampler, net):
+        """`frame` (img's own bytes on the device) -> (the quantised result on the device, img_mode): frame_io.pack_frame normalises,
+        replicates or flips it, `net` ([1,3,H,W] -> float32 [1,3,H*s,W*s]) evaluates the colour planes and then the alpha plane (a
+        plain alpha upsampler: imgproc.linear_resize_f32 to the colour output's size, which is img's times `scale`, _device_frame_ok
+        having out_scale() == scale), frame_io.unpack_frame clamps, flips, takes the gray value and quantises: enhance_float's bits."""
+        from . import frame_io, imgproc
+        max_range, img_mode = self._frame_kind(img)
+        plain = img_mode == "RGBA" and alpha_upsampler != "realesrgan"
+        x, a = frame_io.pack_frame(frame, max_range, alpha="linear" if plain else "network", through_fp16=bool(self.half))
+        out = net(x)
+        if a is not None:   # upstream's plain upsampler: cv2.resize(alpha, (w * scale, h * scale), interpolation=cv2.INTER_LINEAR)
+            a = imgproc.linear_resize_f32(a, out.shape[2], out.shape[3], use_hip=None if HIP_RESIZE else False) if plain else net(a)
+        q = frame_io.unpack_frame(out, {"L": 1, "RGB": 3, "RGBA": 4}[img_mode], max_range, alpha=a, through_fp16=bool(self.half))
+        return q, img_mode
 
     @torch.no_grad()
     def _frame_in_flight(self, img, alpha_upsampler, slot):
         """enhance() of a _frame_inflight_ok frame, enqueued on the current stream with context replica `slot`: returns (the pinned
         host tensor the result is being copied into, img_mode).  The caller waits for the stream and calls _check_range(slot)."""
-        from . import frame_io, imgproc
-        max_range, img_mode = self._frame_kind(img)
-        plain = img_mode == "RGBA" and alpha_upsampler != "realesrgan"
+        from . import frame_io
         frame = frame_io.frame_to_tensor(img).pin_memory().to(self.device, non_blocking=True)
-        x, a = frame_io.pack_frame(frame, max_range, alpha="linear" if plain else "network", through_fp16=bool(self.half))
-
-        def net(t):
-            return self.model(t.half() if self.half else t, slot=slot).float()
-
-        out = net(x)
-        if a is not None:
-            a = imgproc.linear_resize_f32(a, out.shape[2], out.shape[3], use_hip=None if HIP_RESIZE else False) if plain else net(a)
-        q = frame_io.unpack_frame(out, {"L": 1, "RGB": 3, "RGBA": 4}[img_mode], max_range, alpha=a, through_fp16=bool(self.half))
+        q, img_mode = self._frame_through(img, frame, alpha_upsampler,
+                                          lambda t: self.model(t.half() if self.half else t, slot=slot).float())
         host = torch.empty(q.shape, dtype=q.dtype, pin_memory=True)
         host.copy_(q, non_blocking=True)
         return host, img_mode
 
     @torch.no_grad()
     def _enhance_frame_on_device(self, img, resize_to=None, alpha_upsampler="realesrgan"):
-        """enhance() for the frames enhance_float takes, without its host passes: the uint8 / uint16 frame is uploaded as it is,
-        frame_io.pack_frame normalises, replicates or flips it, _pad_on_device and _run() evaluate it as they do for every frame
-        (padding, tiles, ragged batches, devices= lanes), the alpha plane takes a second _run() or imgproc.linear_resize_f32 on the
-        device, frame_io.unpack_frame clamps, flips, takes the gray value and quantises, outscale's resize follows (resize_to), and
-        one copy brings the finished frame home.  The same float32 operations in the same order as enhance_float and enhance's
-        quantiser, so the same bits."""
+        """enhance() for the frames enhance_float takes, without its host passes: the uint8 / uint16 frame is uploaded as it is
+        and goes through _frame_through, where _pad_on_device and _run() evaluate it as they do for every frame (padding, tiles,
+        ragged batches, devices= lanes; a second time for the alpha plane); outscale's resize follows (resize_to), and one copy
+        brings the finished frame home."""
         from . import frame_io, imgproc
-        max_range, img_mode = self._frame_kind(img)
-        plain = img_mode == "RGBA" and alpha_upsampler != "realesrgan"
-        frame = frame_io.frame_to_tensor(img, self.device)                              # H2D: the frame's own bytes
-        x, a = frame_io.pack_frame(frame, max_range, alpha="linear" if plain else "network", through_fp16=bool(self.half))
-        self._pad_on_device(x)
-        out = self._run().float()                                                       # [1,3,H*s,W*s] RGB (fp16 upstream when half)
-        if a is not None:
-            if plain:   # upstream: cv2.resize(alpha, (w * scale, h * scale), interpolation=cv2.INTER_LINEAR)
-                a = imgproc.linear_resize_f32(a, img.shape[0] * self.scale, img.shape[1] * self.scale, use_hip=None if HIP_RESIZE else False)
-            else:
-                self._pad_on_device(a)
-                a = self._run().float()
-        q = frame_io.unpack_frame(out, {"L": 1, "RGB": 3, "RGBA": 4}[img_mode], max_range, alpha=a, through_fp16=bool(self.half))
+
+        def net(t):
+            self._pad_on_device(t)
+            return self._run().float()                                                  # [1,3,H*s,W*s] RGB (fp16 upstream when half)
+
+        q, img_mode = self._frame_through(img, frame_io.frame_to_tensor(img, self.device), alpha_upsampler, net)   # H2D: the frame's own bytes
         if resize_to is not None:
             q3 = q[:, :, None] if q.dim() == 2 else q
             if q.dtype == torch.uint8:
@@ -974,22 +812,19 @@ class RealESRGANer:
             img_mode = "RGB"
             img = img[:, :, ::-1]
 
-        self.pre_process(np.ascontiguousarray(img))
-        output_img = self._run()
-        output_img = output_img.data.squeeze().float().cpu().clamp_(0, 1).numpy()
-        self._check_range()
-        output_img = np.transpose(output_img[[2, 1, 0], :, :], (1, 2, 0))
+        def through_network(planes):        # HWC float32 RGB -> the network's output as HWC float32 BGR in [0,1], on the host
+            self.pre_process(np.ascontiguousarray(planes))
+            out = self._run().data.squeeze().float().cpu().clamp_(0, 1).numpy()
+            self._check_range()
+            return np.transpose(out[[2, 1, 0], :, :], (1, 2, 0))
+
+        output_img = through_network(img)
         if img_mode == "L":
             output_img = _bgr2gray(output_img)
 
         if img_mode == "RGBA":
             if alpha_upsampler == "realesrgan":
-                self.pre_process(np.ascontiguousarray(alpha))
-                output_alpha = self._run()
-                output_alpha = output_alpha.data.squeeze().float().cpu().clamp_(0, 1).numpy()
-                self._check_range()
-                output_alpha = np.transpose(output_alpha[[2, 1, 0], :, :], (1, 2, 0))
-                output_alpha = _bgr2gray(output_alpha)
+                output_alpha = _bgr2gray(through_network(alpha))
             else:   # upstream: cv2.resize(alpha, (w * scale, h * scale), interpolation=cv2.INTER_LINEAR)
                 from . import imgproc
                 h, w = alpha.shape[0:2]
@@ -1005,13 +840,10 @@ class RealESRGANer:
         A forward whose persistent dense-block launch gave up waiting (another process's kernels kept its workgroups off the
         device: NesrHipError from the status check, never a silently wrong image) is evaluated once more: the context has
         switched to per-layer launches by then (include/nesr_hip.h, nesr_set_fused)."""
-        from ._lib import NesrHipError, NesrRangeError
         try:
             return self._enhance_once(img, outscale, alpha_upsampler)
-        except NesrRangeError:
-            raise
         except NesrHipError as e:
-            if "gave up waiting" not in str(e):
+            if not _is_gave_up(e):
                 raise
             warnings.warn(f"{e}; evaluating the frame again with per-layer launches")
             return self._enhance_once(img, outscale, alpha_upsampler)

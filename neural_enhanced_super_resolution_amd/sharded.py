@@ -16,25 +16,13 @@ The per-tile arithmetic does not depend on which rank runs it, so the N-rank res
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
-
 import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _tiling
+from ._tiling import Tile
 from .realesrganer import normalize_u8_on_device
-
-
-@dataclass(frozen=True)
-class Tile:
-    index: int
-    inp: tuple    # padded input window  (y0, y1, x0, x1) in frame coordinates
-    out: tuple    # output window        (y0, y1, x0, x1) in output coordinates
-    crop: tuple   # centre crop inside the tile's own output
-
-    @property
-    def area(self):
-        return (self.inp[1] - self.inp[0]) * (self.inp[3] - self.inp[2])
 
 
 def row_band(rank, world, height):
@@ -139,18 +127,13 @@ def enhance_sharded(up, band, frame_hw, group=None, gather=True):
     if mine and fused:
         # cut / ragged forward / paste, one launch each per batch (RealESRGANer.tiles_u8_on_device): on rank 0 straight into the
         # frame's canvas, elsewhere into one packed buffer whose slices are sent
-        windows = [(t.inp[0] - n0, t.inp[2], t.inp[1] - t.inp[0], t.inp[3] - t.inp[2]) for t in mine]
+        windows = _tiling.windows(mine, row0=n0)
         if rank == 0 and gather:
             canvas = torch.empty((H * s, W * s, 3), dtype=torch.uint8, device=dev)
-            pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], (t.out[0] * W * s + t.out[2]) * 3, W * s * 3) for t in mine]
-            up.tiles_u8_on_device(local, windows, pastes, canvas)
+            up.tiles_u8_on_device(local, windows, _tiling.canvas_pastes(mine, W * s), canvas)
         else:
-            sizes = [(t.out[1] - t.out[0]) * (t.out[3] - t.out[2]) * 3 for t in mine]
-            offs = [0]
-            for v in sizes:
-                offs.append(offs[-1] + v)
+            pastes, offs = _tiling.packed_pastes(mine)
             packed = torch.empty((offs[-1],), dtype=torch.uint8, device=dev)
-            pastes = [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], offs[i], (t.out[3] - t.out[2]) * 3) for i, t in enumerate(mine)]
             up.tiles_u8_on_device(local, windows, pastes, packed)
             results = [(t, packed[offs[i]:offs[i + 1]].view(t.out[1] - t.out[0], t.out[3] - t.out[2], 3)) for i, t in enumerate(mine)]
     elif mine:

@@ -205,3 +205,48 @@ def test_bad_device_list_is_refused(cuda_device):
     for bad in ([99], [], [0, torch.cuda.device_count()]):
         with pytest.raises(ValueError):
             _make(sd, lambda: RRDBNet(3, 3, scale=2, num_block=1), 2, devices=bad)
+
+
+@pytest.mark.parametrize("route", ["shape_groups_f32", "ragged_bf16"])
+def test_run_tiles_runs_the_plan(cuda_device, route):
+    """run_tiles executes exactly _tiling's plan: the recorded (slot, images, input H, W) sequence is the plan's, stream by
+    stream; every slot has a stream of its own; the bits are those of one stream and one tile per call.  64 x 96 at tile 32 /
+    pad 10: six tiles of two shapes, a small job (five streams) for the shape groups, two ragged batches with tile_streams=2."""
+    from neural_enhanced_super_resolution_amd import RRDBNet, _tiling
+    from neural_enhanced_super_resolution_amd.synth import synthetic_frame, synthetic_state_dict
+    sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=2, num_block=1)
+    frame = synthetic_frame(64, 96, seed=9)
+    ragged = route == "ragged_bf16"
+
+    def make(**knobs):
+        up = _make(sd, lambda: RRDBNet(3, 3, scale=2, num_block=1), 2, tile=32, tile_pad=10, half=ragged)
+        for k, v in dict(knobs, **({"ragged_tiles": True} if ragged else {})).items():
+            setattr(up, k, v)
+        return up
+
+    up = make(tile_streams=2) if ragged else make()
+    calls = []
+    for name in ("forward", "forward_ragged"):
+        def rec(x, *a, _orig=getattr(up.model, name), **k):
+            calls.append((k.get("slot", 0), x.shape[0], x.shape[2], x.shape[3], torch.cuda.current_stream(x.device).cuda_stream))
+            return _orig(x, *a, **k)
+        setattr(up.model, name, rec)
+    got, _ = up.enhance(frame)
+
+    tiles = [g[0] + (g[1:],) for g in up.tile_grid(64, 96)]
+    assert len(tiles) == 6
+    if ragged:
+        plan = _tiling.ragged_plan(tiles, 2, up._ragged_cap())
+    else:
+        plan = _tiling.shape_group_plan(tiles, up.batch_for, up.tile_streams, up.small_job_tiles, up.small_job_streams, True)
+    want = [(k, len(b), max(t[1] - t[0] for t in b), max(t[3] - t[2] for t in b)) for k, lane in enumerate(plan) for b in lane]
+    assert len(plan) == (2 if ragged else 5)
+    assert [c[:4] for c in calls] == want
+    streams = {}
+    for slot, *_, stream in calls:
+        streams.setdefault(slot, set()).add(stream)
+    assert all(len(v) == 1 for v in streams.values()), streams
+    assert len({next(iter(v)) for v in streams.values()}) == len(plan), streams
+    serial, _ = make(tile_streams=1, tile_batch=1).enhance(frame)
+    assert np.array_equal(got, serial)
+    assert got.shape == (128, 192, 3) and got.std() > 0
