@@ -416,9 +416,15 @@ __global__ __launch_bounds__(64 * (WAVES + DMAW), DMAW ? (WAVES + DMAW) / 4 : 2)
 //
 // A per-layer launch of such a frame is one round of 256-512 workgroups that all wait for their first bytes at the
 // same time, all compute, all store: ~6.6 us of every ~20 us launch is not matrix work.  Here
-// a workgroup keeps its tile through conv1..conv5 of the block: 52 K-chunk steps (4 + 6 + 8 + 10 + 2 x 12) in ONE
-// software pipeline -- the DMA waves run one step ahead straight across the layer boundaries, the LDS-DMA plan is
+// a workgroup keeps its tile through conv1..conv5 of the block: 40 K-chunk steps (4 + 6 + 8 + 10 + 12) in ONE
+// software pipeline -- the DMA waves run ahead straight across the layer boundaries, the LDS-DMA plan is
 // computed once, and a layer's stores drain while the next layer's first chunks are already being multiplied.
+// conv1..conv4 have 32 output channels: a step is one input chunk and one weight slab.  conv5 has 64: a step is one
+// input chunk and the chunk's TWO weight slabs, and every MFMA wave carries both cout groups' accumulators (64
+// registers), so the input tile is fetched and its pixel fragments are read once for all 64 channels, and conv5 has no
+// layer boundary in its middle.  The input ring has 4 slots (fetched three steps ahead); the weight ring has 4 slabs,
+// addressed in slab units: one per step in conv1..conv4 (three steps ahead), two per step in conv5 (this step's and the
+// next one's: one step ahead, each step being twice as long).
 //
 // The only thing a layer needs from other workgroups is the 1-pixel halo of the 32 channels the previous layer has
 // just produced -- and in a dense block those are the LAST two of its 6..12 input chunks.  So the wait is placed there:
@@ -496,6 +502,10 @@ __device__ unsigned long long g_rdb_arrive[12][8][2];      // [wave][step - 20][
 #endif
 
 constexpr int RSLOTS = 4;   // ring slots of the fused kernel: the DMA waves run three steps ahead, step s + 1 has landed at barrier s
+constexpr int RDB_STEP5 = 4 + 6 + 8 + 10;     // conv5's first step: its steps take two weight slabs each (all 64 output channels)
+constexpr int RDB_STEPS = RDB_STEP5 + 12;     // K-chunk steps of a dense block
+constexpr int W5_ROUNDS = 2 * W_ITEMS / (64 * 4);
+static_assert(RSLOTS == 4 && RDB_STEP5 % RSLOTS == 0 && W5_ROUNDS * 64 * 4 == 2 * W_ITEMS, "conv5's slab pairs sit at ring positions 0,1 / 2,3 and fill whole DMA rounds");
 constexpr int MW = 8;       // MFMA waves of the fused kernel: one tile row each, two per SIMD
 constexpr int DW = 4;       // DMA waves: LDS-DMA, neighbour polling, progress words
 #ifndef NESR_RDB_PAR
@@ -509,14 +519,14 @@ constexpr int EPI_STEPS = NESR_RDB_EPI_STEPS;   // a finished layer's epilogue r
 // that request polls this tile's own progress word among the nine -- which goes out EPI_STEPS steps into the layer.
 static_assert(EPI_STEPS <= 4 - (RSLOTS - 1), "the tile would wait for its own progress word");
 
-// Roles.  MFMA waves (0..7): row w of the 8x32-pixel tile, 32 couts: LDS fragment reads, MFMAs, and the epilogue of
-// the PREVIOUS (layer, cout group) -- its sums wait in 16 registers (main + cross / 2^11) and are finished (bias,
+// Roles.  MFMA waves (0..7): row w of the 8x32-pixel tile, 32 couts (conv5: 64): LDS fragment reads, MFMAs, and the epilogue of
+// the PREVIOUS layer (conv5's own follows its last step) -- its sums wait in 16 registers (main + cross / 2^11) and are finished (bias,
 // LeakyReLU / residuals, split, whole-line stores) at the start of the next layer's first step, by both waves of a SIMD
 // at the same point (NESR_RDB_PAR 0).  Measured alternatives: the epilogue in the DMA waves, or in
 // four waves of its own -- a VALU instruction of a wave that shares its SIMD with two MFMA waves gets one issue slot
 // per MFMA, ~16 cycles each: layer boundaries cost 23 % of the kernel; staggered between the two MFMA waves of a SIMD
 // (one before, one after its MFMAs) -- a VALU block beside the partner's MFMA stream crawls just the same.
-// DMA waves (8..11): one step's LDS-DMAs three steps ahead (4-slot ring), polling of the neighbours' progress words
+// DMA waves (8..11): one step's LDS-DMAs three steps ahead (4-slot ring; conv5's weight slabs one step ahead), polling of the neighbours' progress words
 // before the first chunk of each x_l, and this tile's own progress word EPI_STEPS steps into the next layer.
 __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a) {
     typedef Geo<4> G;
@@ -549,13 +559,13 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     const int y0 = ty * TH, x0 = tx * TW;
 
     const int j16 = lane & 15, g4 = lane >> 4;
-    // (layer, cout group, chunk) of the step after (l, cg, c); l == 5: past the end
-    auto advance = [](int& l, int& cg, int& c) {
-        const int nc = l == 4 ? 12 : 4 + 2 * l, ncg = l == 4 ? 2 : 1;
-        if (++c == nc) { c = 0; if (++cg == ncg) { cg = 0; ++l; } }
+    // (layer, chunk) of the step after (l, c); l == 5: past the end.  A conv5 step is one chunk of all 64 output channels.
+    auto advance = [](int& l, int& c) {
+        const int nc = l == 4 ? 12 : 4 + 2 * l;
+        if (++c == nc) { c = 0; ++l; }
     };
 
-    // The two roles run separate loops over the same 52 steps (one s_barrier per step, one more before the first):
+    // The two roles run separate loops over the same RDB_STEPS steps (one s_barrier per step, one more before the first):
     // their register sets never coexist.
     if (is_dma) {
 #ifdef NESR_RDB_DMAPRIO
@@ -572,7 +582,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         const int row0 = y0 > 0 ? y0 - 1 : 0;
         const char* in_img = static_cast<const char*>(a.cur) + ((size_t)n * a.h + row0) * a.w_ * 64;
         const unsigned* watch = nullptr;    // lanes 0..8: progress word of tile (ty + i/3 - 1, tx + i%3 - 1), if it exists
-        int kdma = 0;                       // LDS-DMA instructions this wave issues per step (vmcnt counts wave instructions)
+        int kin = 0, kw = 0;                // LDS-DMA instructions this wave issues per input chunk / per 32-cout weight slab (vmcnt counts wave instructions)
         if (lane < 9) {
             const int ny = ty + lane / 3 - 1, nx = tx + lane % 3 - 1;
             if (ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x) watch = a.progress + (n * tiles_y + ny) * tiles_x + nx;
@@ -590,7 +600,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 const bool ok = has && Y >= 0 && Y < a.h && X >= 0 && X < a.w_;
                 voff[i] = ((unsigned)(Y - row0) * (unsigned)a.w_ + (unsigned)X) * 64u + sg * 16;
                 okmask |= ok ? (1u << i) : 0u;
-                if (__builtin_amdgcn_ballot_w64(ok) != 0ull) { wavemask |= 1u << i; ++kdma; }
+                if (__builtin_amdgcn_ballot_w64(ok) != 0ull) { wavemask |= 1u << i; ++kin; }
                 if (has && !ok) {
 #pragma unroll
                     for (int sl2 = 0; sl2 < RSLOTS; ++sl2) *reinterpret_cast<f32x4*>(smem + sl2 * IN_BYTES + k * 16) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -600,24 +610,36 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 if (px >= PW) { px -= PW; py += 1; }
             }
 #pragma unroll
-            for (int j = 0; j < W_ROUNDS; ++j) kdma += (wave * 64 + THREADS * j) < W_ITEMS ? 1 : 0;
+            for (int j = 0; j < W_ROUNDS; ++j) kw += (wave * 64 + THREADS * j) < W_ITEMS ? 1 : 0;
         }
         unsigned seen = 0;     // layers of this launch known to be published by all nine tiles
         // an abort word raised earlier in this forward (or by another workgroup): nothing is waited for any more -- the forward's
         // output is invalid either way and the host turns the word into NESR_ERR_HIP (nesr_check_range)
         bool gave_up = __hip_atomic_load(a.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
-        // DMAs of one step: weight slab of (layer l, cout group cg, chunk c), then input chunk c -- after the nine tiles
-        // have published the layer that produced it (chunks 4.. hold x1..: chunk c belongs to x_((c-4)/2+1)).
-        // Exactly kdma wave instructions.
-        auto dma_step = [&](int l, int cg, int c, int slot) {
-            const int CG = l == 4 ? 2 : 1;
-            const char* wsrc = static_cast<const char*>(a.w[l]) + ((size_t)c * CG + cg) * W_BYTES;
+        // The weight ring is addressed in 32-cout slabs (RSLOTS of them).  conv1..conv4: one slab per step, slab position =
+        // step & 3, fetched three steps ahead like the input.  conv5: the chunk's two slabs ([chunk][cout group], contiguous in
+        // the packed weights and in the ring: 2 x W_ITEMS = 9 full rounds) at positions 0,1 / 2,3 -- the ring holds the
+        // current and the next step, so they are fetched one step ahead (conv5 starts at a multiple of RSLOTS steps).
+        auto dma_w = [&](int l, int c, int wpos) {
+            const char* wsrc = static_cast<const char*>(a.w[l]) + (size_t)c * W_BYTES;
 #pragma unroll
             for (int j = 0; j < W_ROUNDS; ++j) {
                 const int k = tid + THREADS * j;
-                const unsigned dst = lds_base + WRING + slot * W_BYTES + j * (THREADS * 16) + wave * 1024;
+                const unsigned dst = lds_base + WRING + wpos * W_BYTES + j * (THREADS * 16) + wave * 1024;
                 if (k < W_ITEMS && !(NESR_RDB_ABL & 64)) glds16_s(wsrc, (unsigned)k * 16u, __builtin_amdgcn_readfirstlane(dst));
             }
+        };
+        auto dma_w5 = [&](int c, int wpos) {
+            const char* wsrc = static_cast<const char*>(a.w[4]) + (size_t)c * (2 * W_BYTES);
+#pragma unroll
+            for (int j = 0; j < W5_ROUNDS; ++j) {
+                const unsigned dst = lds_base + WRING + wpos * W_BYTES + j * (THREADS * 16) + wave * 1024;
+                if (!(NESR_RDB_ABL & 64)) glds16_s(wsrc, (unsigned)(tid + THREADS * j) * 16u, __builtin_amdgcn_readfirstlane(dst));
+            }
+        };
+        // input chunk c -- after the nine tiles have published the layer that produced it (chunks 4.. hold x1..: chunk c
+        // belongs to x_((c-4)/2+1)).  Exactly kin wave instructions.
+        auto dma_in = [&](int c, int slot) {
             const unsigned need = c < 4 ? 0u : (unsigned)((c - 4) >> 1) + 1u;
             if (need > seen && !gave_up && !(NESR_RDB_ABL & 1)) {
                 const unsigned target = a.epoch + need;
@@ -660,33 +682,34 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             const int l = lane >> 3 > 4 ? 4 : lane >> 3, cgq = lane >> 3 > 4 ? 8 + (lane & 7) : (lane & 7);   // lanes 32..47: conv5's 64 biases
             *reinterpret_cast<f32x4*>(smem + BIAS + lane * 16) = *reinterpret_cast<const f32x4*>(a.bias[l] + 4 * cgq);
         }
-        int fl = 0, fcg = 0, fc = 0;      // the next step to fetch
-        dma_step(0, 0, 0, 0);
-        advance(fl, fcg, fc);
-        dma_step(fl, fcg, fc, 1);
-        advance(fl, fcg, fc);
-        dma_step(fl, fcg, fc, 2);
-        advance(fl, fcg, fc);
+        int fl = 0, fc = 0;      // the next step to fetch
+#pragma unroll
+        for (int i = 0; i < RSLOTS - 1; ++i) {
+            dma_w(0, i, i);
+            dma_in(i, i);
+            advance(fl, fc);
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zero padding is in LDS before the first barrier
         int fill = 3;
-        int cl = 0, ccg = 0, cc = 0;      // the current step
+        int cl = 0, cc = 0;      // the current step
         // chunk 0 has landed: the MFMA waves request the launch's first fragments behind this barrier
-        wait_vmcnt_le((NESR_RDB_ABL & 96) ? 0 : 2 * kdma);
+        wait_vmcnt_le((NESR_RDB_ABL & 96) ? 0 : 2 * (kw + kin));
+        int inflight = kw + kin;      // instructions of the latest issue that the next barrier does not need
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        for (int step = 0; step < 52; ++step) {
-            // this step's DMAs and the next step's have landed -- the MFMA waves read the next step's first fragments
-            // before the next barrier -- (those of step + 2, issued one step ago, may stay in flight)
+        for (int step = 0; step < RDB_STEPS; ++step) {
+            // everything the MFMA waves read before the next barrier has landed: this step and the first fragments of the next
+            // (conv5: the next step's pixels only); what was issued one step ago for later may stay in flight
             if (wave == 0) RSTAMP(1, step, 0);
 #if NESR_RDB_ABL & 256
-            if ((step == 0 || step == 51) && wave == 0 && blockIdx.x == 77 && lane == 0) {      // shader clock = d memtime / d memrealtime x 100 MHz
+            if ((step == 0 || step == RDB_STEPS - 1) && wave == 0 && blockIdx.x == 77 && lane == 0) {      // shader clock = d memtime / d memrealtime x 100 MHz
                 const unsigned long long r_ = __builtin_amdgcn_s_memrealtime(), t_ = __builtin_amdgcn_s_memtime();
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 g_rdb_stamps[1][step == 0 ? 62 : 63][0] = r_;
                 g_rdb_stamps[1][step == 0 ? 62 : 63][1] = t_;
             }
 #endif
-            wait_vmcnt_le((step >= 50 || (NESR_RDB_ABL & 96)) ? 0 : kdma);
+            wait_vmcnt_le((NESR_RDB_ABL & 96) ? 0 : inflight);
             if (wave == 0) RSTAMP(1, step, 1);
             RARRIVE(MW + wave, step, 0);
             if (!(NESR_RDB_ABL & 512)) __builtin_amdgcn_s_barrier();
@@ -695,15 +718,25 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             if (wave == 0) RSTAMP(1, step, 2);
             // layer cl - 1 of this tile is in memory: its MFMA waves stored it during steps 0 .. EPI_STEPS - 1 of layer cl
             // and waited for those stores (vmcnt(0)) before this barrier
-            if (cc == EPI_STEPS && ccg == 0 && cl >= 1 && wave == 0 && lane == 0)
+            if (cc == EPI_STEPS && cl >= 1 && wave == 0 && lane == 0)
                 __hip_atomic_store(a.progress + tile, a.epoch + (unsigned)cl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // Issue order = the order the waits count in: what the next barrier needs first.
+            inflight = 0;
+            if (step + 1 >= RDB_STEP5) {
+                // conv5's next step: both slabs into the half of the ring that step - 1 has just left; needed at the next barrier
+                if (step + 1 < RDB_STEPS) dma_w5(step + 1 - RDB_STEP5, ((step + 1) & 1) * 2);
+            } else if (fl < 4) {
+                dma_w(fl, fc, (step + RSLOTS - 1) & (RSLOTS - 1));      // conv1..conv4: three steps ahead, into the slab read one step ago
+                inflight += kw;
+            }
             if (fl < 5) {      // three steps ahead, into the slot read one step ago
-                dma_step(fl, fcg, fc, fill);
-                advance(fl, fcg, fc);
+                dma_in(fc, fill);
+                inflight += kin;
+                advance(fl, fc);
                 fill = fill == RSLOTS - 1 ? 0 : fill + 1;
             }
             if (wave == 0) RSTAMP(1, step, 3);
-            advance(cl, ccg, cc);
+            advance(cl, cc);
         }
         return;
     }
@@ -726,7 +759,8 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         }
         a16[st_] = ((((dy * 3 + dx) * 2) * 2 + kh) * 32 + j16) * 16;
     }
-    int slot = 0;       // ring slot of the current step
+    int slot = 0;       // input ring slot of the current step
+    int wpos = 0;       // weight ring slab of the current step (conv5: the first of its two)
 #if NESR_RDB_ABL & 256
     int mstep = 0;
 #endif
@@ -735,14 +769,18 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     // weight variants are immediate offsets) instead of slot base + offset per read (one v_add per ds_read).
     typedef const __attribute__((address_space(3))) f32x4* lds_f32x4;
     const unsigned lds0 = (unsigned)(size_t)(lds_char*)(smem);
-    unsigned bcur[5][2], acur[5], acur4b;
+    // Pixels: one register per tap-step (XH; XL is the other plane: address ^ 32, for the last tap ^ xl4).  Weights: the
+    // tap is an immediate offset from one of four registers -- tap-steps 0..2 (taps (un, dx)) from aw012, tap-step 3
+    // (tap (2, un)) from aw3, tap-step 4 (tap (2, 2): [w_hi | 0] and [w_hi | w_lo]) from aw4 / aw4b -- which all move on
+    // by one slab (conv5: two) at the end of a step.
+    unsigned bcur[5], aw012, aw3, aw4, aw4b;
 #pragma unroll
-    for (int t = 0; t < 5; ++t) {
-        bcur[t][0] = lds0 + (unsigned)b16[t][0];
-        bcur[t][1] = lds0 + (unsigned)(t == 4 ? (b16[4][0] ^ ((un ^ 1) << 5)) : (b16[t][0] ^ 32));
-        acur[t] = lds0 + (unsigned)(WRING + a16[t]);
-    }
-    acur4b = acur[4] + (unsigned)un * 1024u;
+    for (int t = 0; t < 5; ++t) bcur[t] = lds0 + (unsigned)b16[t][0];
+    const unsigned xl4 = (unsigned)((un ^ 1) << 5);
+    aw012 = lds0 + (unsigned)(WRING + a16[0]);
+    aw3 = lds0 + (unsigned)(WRING + a16[3]);
+    aw4 = lds0 + (unsigned)(WRING + a16[4]);
+    aw4b = aw4 + (unsigned)un * 1024u;
     // ---- the deferred epilogue
     const int par = (NESR_RDB_PAR >= 0) ? NESR_RDB_PAR : wave >> 2;                          // which end of a step this wave's epilogue half sits at
     const int cbl = (g4 & 1) * 16 + (g4 >> 1) * 8;      // a lane's 8 output channels inside a 32-cout group after the permlane16 exchange
@@ -753,7 +791,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) ep[nh][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    int ep_l = -1, ep_cg = 0;
+    int ep_l = -1;
     bool bad = false;
     auto unpack_res = [&](f32x4 rx, f32x4 rx1, f32x4& q0, f32x4& q1) {
         uint4 cx = __builtin_bit_cast(uint4, rx), cx1 = __builtin_bit_cast(uint4, rx1);
@@ -854,51 +892,86 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     auto epi_part = [&](int c) {
         if (NESR_RDB_ABL & 16) return;
         if (EPI_STEPS == 1) {
-            epi_half(ep_l, ep_cg, ep[0][0], ep[0][1], 0);
-            epi_half(ep_l, ep_cg, ep[1][0], ep[1][1], 1);
+            epi_half(ep_l, 0, ep[0][0], ep[0][1], 0);
+            epi_half(ep_l, 0, ep[1][0], ep[1][1], 1);
         } else if (c == 0) {
-            epi_half(ep_l, ep_cg, ep[0][0], ep[0][1], 0);
+            epi_half(ep_l, 0, ep[0][0], ep[0][1], 0);
         } else {
-            epi_half(ep_l, ep_cg, ep[1][0], ep[1][1], 1);
+            epi_half(ep_l, 0, ep[1][0], ep[1][1], 1);
         }
     };
-    f32x4 acc16[2][2][2];       // [pixel half][cout half][main | cross]
-    f32x4 Af[2][2][2];          // [buffer][cout half][variant]
+    f32x4 acc16[2][2][2][2];    // [cout group (conv5 only: 1)][pixel half][cout half][main | cross]
+    f32x4 Af[2][2][2];          // [buffer][cout half][variant]; in a conv5 step the buffer is the cout group
     f32x4 Bf[2][2][2];          // [buffer][pixel half][variant]
-    // fragments of tap-step s_ of the step in ring slot `sl` -> buffer `buf`; the addresses move on to slot sl + 1
-    // (the second pixel half is 16 pixels = 1024 bytes on: the slot swizzle looks at bit 2 of the column only)
-    auto load_step = [&](int sl, int s_, int buf) {
-        const bool wrap = sl == RSLOTS - 1;
-        const unsigned dB = wrap ? (unsigned)(-(RSLOTS - 1) * IN_BYTES) : (unsigned)IN_BYTES;
-        const unsigned dA = wrap ? (unsigned)(-(RSLOTS - 1) * W_BYTES) : (unsigned)W_BYTES;
+    // Weight fragments of tap-step s_ -> buffer `buf`, from the slab `off` bytes behind the address registers (conv5's second
+    // cout group: the next slab, an immediate offset).  Pixel fragments of tap-step s_ -> buffer `buf` (the second pixel
+    // half is 16 pixels = 1024 bytes on: the slot swizzle looks at bit 2 of the column only).  Each address register is
+    // moved on to where it is read next (`d` bytes) by its last read of a step.
+    auto load_a = [&](int s_, int buf, unsigned off) {
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             if (s_ < 4) {
-                Af[buf][mt][0] = *((lds_f32x4)(size_t)(acur[s_] + mt * 256));
-                Af[buf][mt][1] = *((lds_f32x4)(size_t)(acur[s_] + mt * 256 + 1024));
+                const unsigned ad = s_ < 3 ? aw012 + s_ * 2048 : aw3;
+                Af[buf][mt][0] = *((lds_f32x4)(size_t)(ad + off + mt * 256));
+                Af[buf][mt][1] = *((lds_f32x4)(size_t)(ad + off + mt * 256 + 1024));
             } else {
-                f32x4 hi = *((lds_f32x4)(size_t)(acur[4] + mt * 256));
-                Af[buf][mt][1] = *((lds_f32x4)(size_t)(acur4b + mt * 256));
+                f32x4 hi = *((lds_f32x4)(size_t)(aw4 + off + mt * 256));
+                Af[buf][mt][1] = *((lds_f32x4)(size_t)(aw4b + off + mt * 256));
                 if (un) hi = f32x4{0.f, 0.f, 0.f, 0.f};
                 Af[buf][mt][0] = hi;
             }
         }
+    };
+    auto move_a = [&](unsigned d) {
+        aw012 += d;
+        aw3 += d;
+        aw4 += d;
+        aw4b += d;
+    };
+    auto load_b = [&](int sl, int s_, int buf) {
+        const unsigned dB = sl == RSLOTS - 1 ? (unsigned)(-(RSLOTS - 1) * IN_BYTES) : (unsigned)IN_BYTES;
+        const unsigned xl = bcur[s_] ^ (s_ == 4 ? xl4 : 32u);
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh) {
-            Bf[buf][nh][0] = *((lds_f32x4)(size_t)(bcur[s_][0] + nh * 1024));
-            Bf[buf][nh][1] = *((lds_f32x4)(size_t)(bcur[s_][1] + nh * 1024));
+            Bf[buf][nh][0] = *((lds_f32x4)(size_t)(bcur[s_] + nh * 1024));
+            Bf[buf][nh][1] = *((lds_f32x4)(size_t)(xl + nh * 1024));
         }
-        acur[s_] += dA;
-        if (s_ == 4) acur4b += dA;
-        bcur[s_][0] += dB;
-        bcur[s_][1] += dB;
+        bcur[s_] += dB;
     };
-    // One step = 5 tap-steps of the chunk in ring slot `slot`; P = buffer parity of its first tap-step (5 is odd: it
-    // flips every step, and every layer has an even number of steps).  The fragments of tap-step 0 were requested in
-    // the previous step (or just below, for the launch's first step); those of the next step's tap-step 0 are requested
-    // beside this step's last MFMAs -- the next step's chunk landed before this step's barrier -- so that no wave sits
-    // behind an LDS round trip after a barrier.
-    auto step_body = [&](auto Pc, int c, bool last_of_all) {
+    // the products of one tap-step for one cout group, in the per-layer kernel's order
+    auto mfma_tap = [&](int s_, int g, int abuf, int bbuf) {
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const f16x8 a0 = __builtin_bit_cast(f16x8, Af[abuf][mt][0]), a1 = __builtin_bit_cast(f16x8, Af[abuf][mt][1]);
+#pragma unroll
+            for (int nh = 0; nh < 2; ++nh) {
+                const f16x8 x0_ = __builtin_bit_cast(f16x8, Bf[bbuf][nh][0]), x1_ = __builtin_bit_cast(f16x8, Bf[bbuf][nh][1]);
+                if (s_ < 4) {
+                    acc16[g][nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x1_, acc16[g][nh][mt][1], 0, 0, 0);
+                    acc16[g][nh][mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0_, acc16[g][nh][mt][0], 0, 0, 0);
+                    acc16[g][nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x0_, acc16[g][nh][mt][1], 0, 0, 0);
+                } else {
+                    acc16[g][nh][mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0_, acc16[g][nh][mt][0], 0, 0, 0);
+                    acc16[g][nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x1_, acc16[g][nh][mt][1], 0, 0, 0);
+                }
+            }
+        }
+    };
+    auto zero_acc = [&](int g) {
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) acc16[g][nh][mt][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    // One step of conv1..conv4 = 5 tap-steps of the chunk in input slot `slot` and weight slab `wpos`; P = buffer parity of
+    // its first tap-step (5 is odd: it flips every step, and every layer has an even number of steps).  The fragments of
+    // tap-step 0 were requested in the previous step (or just below, for the launch's first step); those of the next
+    // step's tap-step 0 are requested beside this step's last MFMAs -- the next step's chunk landed before this step's
+    // barrier -- so that no wave sits behind an LDS round trip after a barrier.  (conv4's last step requests weight
+    // fragments that are not there yet -- conv5's slabs land one barrier later -- and conv5's first step reads them again.)
+    auto step_body = [&](auto Pc, int c) {
         constexpr int P = decltype(Pc)::value;
         // the x_l stores of this wave have retired before the barrier after which the progress word goes out
         if (c == EPI_STEPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -914,6 +987,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
 #endif
         const bool epi_now = active && ep_l >= 0 && c < EPI_STEPS;
         const int nslot = slot == RSLOTS - 1 ? 0 : slot + 1;
+        const unsigned dA = wpos == RSLOTS - 1 ? (unsigned)(-(RSLOTS - 1) * W_BYTES) : (unsigned)W_BYTES;
         if (active && !(NESR_RDB_ABL & 8)) {
             if (epi_now && par == 0) {
                 epi_part(c);
@@ -929,24 +1003,14 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 tt[s_] = __builtin_amdgcn_s_memtime();      // no wait here: read at the end of the step
                 __builtin_amdgcn_sched_barrier(0);
 #endif
-                if (s_ + 1 < 5) load_step(slot, s_ + 1, buf ^ 1);
-                else if (!last_of_all) load_step(nslot, 0, buf ^ 1);
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const f16x8 a0 = __builtin_bit_cast(f16x8, Af[buf][mt][0]), a1 = __builtin_bit_cast(f16x8, Af[buf][mt][1]);
-#pragma unroll
-                    for (int nh = 0; nh < 2; ++nh) {
-                        const f16x8 x0_ = __builtin_bit_cast(f16x8, Bf[buf][nh][0]), x1_ = __builtin_bit_cast(f16x8, Bf[buf][nh][1]);
-                        if (s_ < 4) {
-                            acc16[nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x1_, acc16[nh][mt][1], 0, 0, 0);
-                            acc16[nh][mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0_, acc16[nh][mt][0], 0, 0, 0);
-                            acc16[nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x0_, acc16[nh][mt][1], 0, 0, 0);
-                        } else {
-                            acc16[nh][mt][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0_, acc16[nh][mt][0], 0, 0, 0);
-                            acc16[nh][mt][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x1_, acc16[nh][mt][1], 0, 0, 0);
-                        }
-                    }
+                if (s_ + 1 < 5) {
+                    load_a(s_ + 1, buf ^ 1, 0);
+                    load_b(slot, s_ + 1, buf ^ 1);
+                } else {
+                    load_a(0, buf ^ 1, dA);      // the next step's slab
+                    load_b(nslot, 0, buf ^ 1);
                 }
+                mfma_tap(s_, 0, buf, buf);
                 // the next tap-step's 8 fragment reads ride between this one's MFMAs
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
@@ -967,7 +1031,78 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             }
 #endif
         }
+        move_a(dA);
         slot = nslot;
+        wpos = wpos == RSLOTS - 1 ? 0 : wpos + 1;
+#if NESR_RDB_ABL & 256
+        if (wave == 1) RSTAMP(0, mstep, 2);
+        ++mstep;
+#endif
+    };
+    // One step of conv5 = 5 tap-steps of the chunk in input slot `slot` for BOTH cout groups: weight slabs wpos (group 0) and
+    // wpos + 1 (group 1).  Per tap-step the pixel fragments are read once; group 0's products run while group 1's weight
+    // fragments and the next tap-step's pixel fragments arrive, group 1's while the next tap-step's group 0 weights do --
+    // one weight fragment buffer per group, so the fragment registers are those of a 32-cout step.  Every accumulator gets
+    // the per-layer kernel's sequence of products.  The step's slabs were fetched one step ahead (4 slabs = this step and
+    // the next) and land before this step's barrier, so tap-step 0's group 0 weights are read behind the barrier; the
+    // pixel fragments of the next step's tap-step 0 are requested beside the last MFMAs as in the other layers.
+    // FIRST: conv4's deferred epilogue, then the accumulators start at zero.
+    auto step_body5 = [&](auto Pc, auto Fc, int c, bool last_of_all) {
+        constexpr int P = decltype(Pc)::value;
+        constexpr bool FIRST = decltype(Fc)::value != 0;
+        if (c == EPI_STEPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if NESR_RDB_ABL & 256
+        if (wave == 1) RSTAMP(0, mstep, 0);
+        RARRIVE(wave, mstep, 0);
+#endif
+        if (!(NESR_RDB_ABL & 512)) __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+#if NESR_RDB_ABL & 256
+        RARRIVE(wave, mstep, 1);
+        if (wave == 1) RSTAMP(0, mstep, 1);
+#endif
+        const bool epi_now = active && ep_l >= 0 && c < EPI_STEPS;
+        const int nslot = slot == RSLOTS - 1 ? 0 : slot + 1;
+        const unsigned dA = wpos == 0 ? (unsigned)(2 * W_BYTES) : (unsigned)(-2 * W_BYTES);
+        if (active && !(NESR_RDB_ABL & 8)) {
+            load_a(0, 0, 0);
+            if (epi_now && par == 0) {
+                epi_part(c);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (FIRST) { zero_acc(0); zero_acc(1); }
+#pragma unroll
+            for (int s_ = 0; s_ < 5; ++s_) {
+                const int buf = (s_ + P) & 1;
+                load_a(s_, 1, W_BYTES);
+                if (s_ + 1 < 5) load_b(slot, s_ + 1, buf ^ 1);
+                else if (!last_of_all) load_b(nslot, 0, buf ^ 1);
+                mfma_tap(s_, 0, 0, buf);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                if (s_ + 1 < 5) load_a(s_ + 1, 0, 0);
+                mfma_tap(s_, 1, 1, buf);
+                if (s_ + 1 < 5) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (epi_now && par == 1) {
+                epi_part(c);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        move_a(dA);
+        slot = nslot;
+        wpos = wpos == 0 ? 2 : 0;
 #if NESR_RDB_ABL & 256
         if (wave == 1) RSTAMP(0, mstep, 2);
         ++mstep;
@@ -976,36 +1111,49 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     // the launch's first fragments: chunk 0 is in LDS once every DMA wave has passed its first wait -- one extra barrier
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (active) load_step(0, 0, 0);
-    for (int l = 0; l < 5; ++l) {
-        const int nc = l == 4 ? 12 : 4 + 2 * l;
-        const int ncg = l == 4 ? 2 : 1;
-        for (int cg = 0; cg < ncg; ++cg) {
-#pragma unroll
-            for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) acc16[nh][mt][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            for (int c = 0; c < nc; c += 2) {
-                step_body(std::integral_constant<int, 0>{}, c, false);
-                step_body(std::integral_constant<int, 1>{}, c + 1, l == 4 && cg == 1 && c + 2 == nc);
-            }
-            // the layer's sums (main + cross / 2^11) wait for the next layer's first steps
-#pragma unroll
-            for (int nh = 0; nh < 2; ++nh)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) ep[nh][mt][i] = fmaf(acc16[nh][mt][1][i], LO_INV, acc16[nh][mt][0][i]);
-            ep_l = l;
-            ep_cg = cg;
-        }
+    if (active) {
+        load_a(0, 0, 0);
+        load_b(0, 0, 0);
     }
-    // the last cout group of conv5: nothing is left to overlap it with
+    typedef std::integral_constant<int, 0> I0;
+    typedef std::integral_constant<int, 1> I1;
+    for (int l = 0; l < 4; ++l) {
+        const int nc = 4 + 2 * l;
+        zero_acc(0);
+        for (int c = 0; c < nc; c += 2) {
+            step_body(I0{}, c);
+            step_body(I1{}, c + 1);
+        }
+        // the layer's sums (main + cross / 2^11) wait for the next layer's first steps
+#pragma unroll
+        for (int nh = 0; nh < 2; ++nh)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ep[nh][mt][i] = fmaf(acc16[0][nh][mt][1][i], LO_INV, acc16[0][nh][mt][0][i]);
+        ep_l = l;
+    }
+    // conv5: 12 steps of 64 output channels
+    step_body5(I0{}, I1{}, 0, false);
+    step_body5(I1{}, I0{}, 1, false);
+    for (int c = 2; c < 12; c += 2) {
+        step_body5(I0{}, I0{}, c, false);
+        step_body5(I1{}, I0{}, c + 1, c + 2 == 12);
+    }
+    // both cout groups of conv5: nothing is left to overlap them with
     if (active && !(NESR_RDB_ABL & 16)) {
-        epi_half(4, 1, ep[0][0], ep[0][1], 0);
-        epi_half(4, 1, ep[1][0], ep[1][1], 1);
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int nh = 0; nh < 2; ++nh) {
+                f32x4 e0, e1;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    e0[i] = fmaf(acc16[g][nh][0][1][i], LO_INV, acc16[g][nh][0][0][i]);
+                    e1[i] = fmaf(acc16[g][nh][1][1][i], LO_INV, acc16[g][nh][1][0][i]);
+                }
+                epi_half(4, g, e0, e1, nh);
+            }
     }
     if (bad && a.status) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1031,6 +1179,7 @@ hipError_t launch_split(const ConvArgs& a, hipStream_t s) {
 }  // namespace
 
 #if NESR_RDB_ABL & 256
+extern "C" int nesr_debug_rdb_steps() { return RDB_STEPS; }
 extern "C" int nesr_debug_rdb_stamps(unsigned long long* out) {
     return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_rdb_stamps), sizeof(unsigned long long) * 2 * 64 * 8);
 }

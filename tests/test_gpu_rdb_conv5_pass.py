@@ -1,0 +1,90 @@
+"""GPU: the fused dense-block kernel computes conv5's 64 output channels in one pass of 12 steps (two weight slabs per
+step in a slab-addressed ring, 64 accumulators) where it used to run two passes of 32.  Every accumulator must still
+receive the per-layer kernel's sequence of products, so the fused path (NESR_RDB_FUSE=-1) stays bit-equal to the per-layer
+launches (NESR_RDB_FUSE=0) -- checked at the smallest shapes where the new code can go wrong: x4 form (no unshuffle:
+internal size = input size), one RRDB = three dense blocks, so conv5's second residual is both absent and present.
+
+Reference semantics: the dense block of basicsr's RRDBNet (restated in oracle/rrdbnet_ref.py)."""
+import os
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+def _net(sd, num_block, fuse):
+    from neural_enhanced_super_resolution_amd import RRDBNet
+    old = os.environ.get("NESR_RDB_FUSE")
+    os.environ["NESR_RDB_FUSE"] = "-1" if fuse else "0"
+    try:
+        n = RRDBNet(3, 3, scale=4, num_block=num_block)
+        n.load_state_dict(sd)
+        n.eval().to("cuda:0")
+        n(torch.zeros(1, 3, 16, 16, device="cuda:0"))        # the context is created with the switch in force
+    finally:
+        if old is None:
+            os.environ.pop("NESR_RDB_FUSE", None)
+        else:
+            os.environ["NESR_RDB_FUSE"] = old
+    return n
+
+
+_cache = {}
+
+
+def _pair(num_block):
+    """(per-layer net, fused net) of one set of weights, built once per module run."""
+    if num_block not in _cache:
+        from neural_enhanced_super_resolution_amd.synth import synthetic_state_dict
+        sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=4, num_block=num_block)
+        _cache[num_block] = (_net(sd, num_block, False), _net(sd, num_block, True))
+    return _cache[num_block]
+
+
+def _launches(net, x):
+    net.set_kernel_timing(x.device, True)
+    net.kernel_time()                                    # clear
+    net(x)
+    torch.cuda.synchronize()
+    _, launches, _ = net.kernel_time()
+    net.set_kernel_timing(x.device, False)
+    return launches
+
+
+@pytest.mark.parametrize("n,hw", [
+    (1, (8, 32)),         # one tile, no neighbour: every halo is the zero border
+    (1, (9, 33)),         # four tiles, three partial: one with a single active row, one with a single valid column
+    (1, (24, 96)),        # 3 x 3 tiles: the centre tile polls all eight neighbours
+    (2, (16, 64)),        # two images of 2 x 2 tiles: tile -> image mapping
+])
+def test_conv5_one_pass_equals_per_layer_bitwise(cuda_device, n, hw):
+    per_layer, fused = _pair(1)
+    x = torch.rand(n, 3, *hw, generator=torch.Generator().manual_seed(5)).to(cuda_device)
+    want = per_layer(x)
+    per_layer.check_status()
+    got = fused(x)
+    fused.check_status()
+    assert got.shape == (n, 3, 4 * hw[0], 4 * hw[1])
+    assert torch.equal(got, want), (got - want).abs().max().item()
+
+
+def test_two_rrdbs_three_times_in_a_row(cuda_device):
+    """Six dense blocks per forward, three forwards: epochs advance, ring positions and address registers start over in
+    every launch."""
+    per_layer, fused = _pair(2)
+    x = torch.rand(1, 3, 17, 40, generator=torch.Generator().manual_seed(6)).to(cuda_device)      # 3 x 2 tiles, partial row and column
+    want = per_layer(x)
+    per_layer.check_status()
+    for _ in range(3):
+        got = fused(x)
+        fused.check_status()
+        assert torch.equal(got, want), (got - want).abs().max().item()
+
+
+def test_the_fused_kernel_is_what_ran(cuda_device):
+    per_layer, fused = _pair(1)
+    x = torch.rand(1, 3, 24, 96, generator=torch.Generator().manual_seed(7)).to(cuda_device)
+    n_f, n_p = _launches(fused, x), _launches(per_layer, x)
+    assert n_p - n_f == 4 * 3 * 1, (n_f, n_p)            # one launch per dense block instead of five
+    fused.check_status()

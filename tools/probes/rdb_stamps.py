@@ -21,19 +21,21 @@ buf = (ctypes.c_ulonglong * (2 * 64 * 8))()
 lib.nesr_debug_rdb_stamps.argtypes = [ctypes.c_void_p]
 assert lib.nesr_debug_rdb_stamps(buf) == 0
 S = [[[buf[(r * 64 + s) * 8 + e] for e in range(8)] for s in range(64)] for r in range(2)]
+# steps of a dense block: the kernel says (older builds: 52, conv5 as two passes of 32 output channels)
+N = lib.nesr_debug_rdb_steps() if hasattr(lib, "nesr_debug_rdb_steps") else 52
 t0 = min(S[0][0][0], S[1][0][0])
 print("step | MFMA: arrive  wait  compute | DMA: arrive(vm wait) barrier-wait  issue  epilogue | step length")
-for s in range(52):
+for s in range(N):
     m, d = S[0][s], S[1][s]
-    nm = S[0][s + 1][0] if s < 51 else m[2]
-    nd = S[1][s + 1][0] if s < 51 else d[3]
+    nm = S[0][s + 1][0] if s < N - 1 else m[2]
+    nd = S[1][s + 1][0] if s < N - 1 else d[3]
     ep = ""
     if m[3] > m[1] and m[6] > m[3]:
         ep = f"  epilogue in the MFMA wave: start +{m[3]-m[1]} exchange/bias/act {m[4]-m[3]} split/regroup {m[5]-m[4]} stores {m[6]-m[5]}"
     print(f"{s:3d} | {m[0]-t0:8d} {m[1]-m[0]:6d} {m[2]-m[1]:6d} | {d[0]-t0:8d} ({d[1]-d[0]:5d}) {d[2]-d[1]:6d} {d[3]-d[2]:6d} {nd-d[3]:6d} | {nm-m[0]:6d}{ep}")
-print("total cycles", S[0][51][2] - t0)
+print("total cycles", S[0][N - 1][2] - t0)
 dr, dt = S[1][63][0] - S[1][62][0], S[1][63][1] - S[1][62][1]
-print(f"steps 0..51: {dt} shader cycles in {dr} ticks of the 100 MHz clock = {dr / 100:.2f} us: shader clock {dt / dr * 100:.0f} MHz")
+print(f"steps 0..{N - 1}: {dt} shader cycles in {dr} ticks of the 100 MHz clock = {dr / 100:.2f} us: shader clock {dt / dr * 100:.0f} MHz")
 
 arr = (ctypes.c_ulonglong * (12 * 8 * 2))()
 lib.nesr_debug_rdb_arrive.argtypes = [ctypes.c_void_p]
