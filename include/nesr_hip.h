@@ -202,6 +202,51 @@ int nesr_band_tail(nesr_ctx* ctx, void* y_dev, void* hip_stream);
 size_t nesr_band_row_bytes(const nesr_ctx* ctx);
 int nesr_band_rows(nesr_ctx* ctx, int buffer, int row0, int nrows, void* staging_dev, int write, void* hip_stream);
 
+/*
+ * Row bands inside ONE process: an untiled frame on RealESRGANer(devices=[...]) (csrc/band_exchange.hip, csrc/band_api.cpp; DESIGN.md
+ * section 6).  The contexts of the bands know each other, a band's edge rows are written straight into its neighbours' memory, and the
+ * whole frame runs below Python.  Every entry stands behind `self.model(img)` on a whole frame (nesr/nesr.py:224, 887-891).
+ *
+ * nesr_band_link (nesr/nesr.py:224, 887-891): makes `up` the band above `ctx` and `down` the band below (either may be null: a frame
+ *   edge); both directions of a link are set, earlier links of the three contexts on those sides are dropped.  A link is WRITTEN
+ *   DIRECTLY by the push kernel when both contexts are on one device (the plain pointer) or the runtime grants peer access
+ *   (hipDeviceEnablePeerAccess, asked once here); otherwise it is STAGED: the existing pack, then hipMemcpyPeerAsync -- the same bytes.
+ *   Landing buffers are allocated when the first rows of a width are pushed.  NESR_ERR_ARG: an SRVGGNetCompact context, a neighbour of
+ *   another geometry or dtype, ctx as its own neighbour, one context on both sides.  nesr_band_unlink drops both links of ctx
+ *   (nesr_destroy does so too).  nesr_band_link_state: bit 0 / 1 = an upper / lower neighbour exists, bit 2 / 3 = that link is written
+ *   directly, bit 4 / 5 = the neighbour is on another device; negative: an error code.  nesr_band_set_staged(ctx, 1) makes every link
+ *   of ctx staged whatever the devices allow (A/B runs and tests of that route; 0: decide again).
+ * nesr_band_push_edges (nesr/nesr.py:224, 887-891): one launch of band_push_edges on `hip_stream`.  The first `edge_rows` band rows of
+ *   `buffer` (rows [top, top + edge_rows) of the band image; the rows nesr_band_pack_edges selects) go to the upper neighbour's landing
+ *   buffer of `parity` (0 | 1), the last ones to the lower neighbour's; 1 <= edge_rows <= 6.  Both neighbours must hold a band image of
+ *   the same width (nesr_band_begin).  The kernel waits for nothing: the CALLER orders it after the neighbour's nesr_band_land_aprons of
+ *   the same parity two steps earlier, and the neighbour's nesr_band_land_aprons after it (hipEventRecord / hipStreamWaitEvent).
+ * nesr_band_land_aprons (nesr/nesr.py:224, 887-891): the receiver's side: landing buffers of `parity` -> the `edge_rows` apron rows next
+ *   to the band on each linked side, of `buffer` and of every buffer whose bit is set in also_mask (8: conv_first's copy, after step 0).
+ * nesr_band_plan (nesr/nesr.py:224, 887-891; host only): the bands of `internal_rows` trunk rows over n contexts, lo_hi[2r], lo_hi[2r+1]
+ *   = [lo, hi) of band r -- banded.band_split: even boundaries, NESR_ERR_ARG when a band would be shorter than the 6-row apron
+ *   (cap: (lo, hi) pairs lo_hi holds, >= n).
+ * nesr_forward_banded_u8 (nesr/nesr.py:224, 887-891): nesr_forward_u8 of one frame as n row bands, band r on ctxs[r].  frame_u8 and out_u8
+ *   are on ctxs[0]'s device; a band's input rows (with aprons) are read in place there or copied to its device, then nesr_band_begin's
+ *   stage, 1 + 3 num_block exchange steps (phase 0, push, phase 1, land) and nesr_band_tail's stage with conv_last's own quantiser; the
+ *   band's rows without aprons are copied into out_u8.  streams: n hipStream_t, band r's work goes to streams[r]; null: streams the
+ *   contexts own.  On return everything is enqueued and the frame is complete behind streams[0] (band 0's stream); nothing is
+ *   allocated or synchronised after the first frame of a geometry.  The f32 forms only (NESR_DTYPE_F32, _F32_WINOGRAD, _F32_SPLIT):
+ *   out_u8 is byte for byte nesr_forward_u8's.  Bands never run the persistent dense-block kernel.  Call nesr_check_range on EVERY
+ *   context before trusting out_u8: the range word is per context, and a band that overflowed spoils its own rows only.
+ * nesr_forward_banded (nesr/nesr.py:224, 887-891): the float twin, nesr_forward for N = 1: x_dev [1, C, H, W], y_dev [1, num_out_ch,
+ *   4H/u, 4W/u] f32 on ctxs[0]'s device.
+ */
+int nesr_band_link(nesr_ctx* ctx, nesr_ctx* up, nesr_ctx* down);
+int nesr_band_unlink(nesr_ctx* ctx);
+int nesr_band_link_state(const nesr_ctx* ctx);
+int nesr_band_set_staged(nesr_ctx* ctx, int on);
+int nesr_band_push_edges(nesr_ctx* ctx, int buffer, int top, int bottom, int edge_rows, int parity, void* hip_stream);
+int nesr_band_land_aprons(nesr_ctx* ctx, int buffer, int also_mask, int top, int bottom, int edge_rows, int parity, void* hip_stream);
+int nesr_band_plan(int internal_rows, int n, int* lo_hi, int cap);
+int nesr_forward_banded_u8(nesr_ctx** ctxs, int n, const uint8_t* frame_u8, int H, int W, int flip_rgb, int round_mode, uint8_t* out_u8, void** streams);
+int nesr_forward_banded(nesr_ctx** ctxs, int n, const void* x_dev, int C, int H, int W, void* y_dev, void** streams);
+
 /* Hint: forwards of this context run while other contexts of the process use the same device (several frames or
  * tile groups in flight on different streams).  Changes kernel selection only, never a value. */
 int nesr_set_concurrent(nesr_ctx* ctx, int concurrent);

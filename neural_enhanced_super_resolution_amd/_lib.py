@@ -48,6 +48,16 @@ SIGNATURES = {
     "nesr_band_unpack_aprons": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "nesr_band_row_bytes": (_c.c_size_t, [_c.c_void_p]),
     "nesr_band_rows": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "nesr_band_link": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "nesr_band_unlink": (_c.c_int, [_c.c_void_p]),
+    "nesr_band_link_state": (_c.c_int, [_c.c_void_p]),
+    "nesr_band_set_staged": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_band_push_edges": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "nesr_band_land_aprons": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "nesr_band_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int]),
+    "nesr_forward_banded_u8": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                          _c.POINTER(_c.c_void_p)]),
+    "nesr_forward_banded": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.POINTER(_c.c_void_p)]),
     "nesr_set_concurrent": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_set_fused": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_fused_state": (_c.c_int, [_c.c_void_p]),

@@ -54,6 +54,21 @@ def band_split(internal_rows, world):
     return bands
 
 
+BAND_MIN_ROWS = 48   # RealESRGANer(devices=[...]): internal rows a lane gets at least.  A policy, not a measurement: 2 * APRON / 48 = 25 % extra arithmetic
+
+
+def band_lanes(internal_rows, lanes, min_rows=BAND_MIN_ROWS):
+    """The bands [(lo, hi)] of an untiled frame over at most `lanes` lanes of one process: as many lanes as get `min_rows` internal
+    rows each, down to one (then the frame is not banded), and never a band band_split refuses."""
+    n = max(1, min(int(lanes), int(internal_rows) // max(1, int(min_rows))))
+    while n > 1:
+        try:
+            return band_split(internal_rows, n)
+        except ValueError:
+            n -= 1
+    return [(0, int(internal_rows))]
+
+
 def out_buffer(i):
     """The dense-block buffer RDB i writes its result into (= the one RDB i + 1 reads): P, Q, R rotate."""
     return (i % 3 + 1) % 3

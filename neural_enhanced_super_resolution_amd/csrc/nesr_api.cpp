@@ -568,6 +568,7 @@ void nesr_destroy(nesr_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     c->timer.destroy();
+    band_release(c);
     if (c->ws) (void)hipFree(c->ws);
     if (c->d_weights) (void)hipFree(c->d_weights);
     if (c->d_trunk) (void)hipFree(c->d_trunk);

@@ -252,6 +252,18 @@ struct Pack12Args {
 };
 hipError_t launch_pack_nesr12(const Pack12Args& a, hipStream_t s);
 
+// Row bands inside one process (band_exchange.hip): the first / last edge rows of a band's feature map, gathered from the context's
+// activation layout into the packed form of nesr_band_rows and written straight into the neighbour contexts' landing buffers (plain
+// pointers on the same device, peer-mapped ones on another).  A side is `nseg` segments `seg_stride` bytes apart, each of `npieces`
+// pieces of `piece_vecs` 16-byte vectors `piece_stride` bytes apart; the destination is contiguous.  src[i] == null: nothing for side i.
+struct EdgePush {
+    const char* src[2];      // [0] the first band rows (they go to the band above), [1] the last band rows
+    char* dst[2];
+    long long seg_stride, piece_stride;
+    int nseg, npieces, piece_vecs;
+};
+hipError_t launch_band_push_edges(const EdgePush& a, hipStream_t s);
+
 // all tiles of a frame at once (pack.hip): u8 HWC frame -> float NCHW tile slots (cut), float NCHW tile outputs -> u8 (paste)
 constexpr int TILE_IO_MAX = 64;
 struct TileIo {

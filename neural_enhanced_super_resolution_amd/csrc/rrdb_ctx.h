@@ -55,6 +55,24 @@ struct FwState {
     char* buf[3] = {nullptr, nullptr, nullptr};
 };
 
+// Row bands of one frame on several contexts of ONE process (band_api.cpp): the neighbours of a context, the landing buffers
+// their band_push_edges launches write into, and what the whole-frame driver (nesr_forward_banded*) keeps between frames.
+constexpr int BAND_APRON = 6;        // banded.APRON: internal rows of each neighbour a band carries
+struct BandLink {
+    nesr_ctx* nb[2] = {nullptr, nullptr};        // [0] the band above, [1] the band below
+    bool direct[2] = {false, false};             // the link to nb[i] is written by the push kernel (same device, or peer access); false: staged copy
+    bool force_staged = false;                   // nesr_band_set_staged: every link of this context is staged
+    char* land[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [side the rows come from][step parity], BAND_APRON rows each; owned by the RECEIVER
+    size_t land_bytes = 0;                       // of each landing buffer
+    char* send[2] = {nullptr, nullptr};          // staged links: the packed rows going up / down
+    size_t send_bytes = 0;
+    hipEvent_t pushed[2] = {nullptr, nullptr};   // [step parity] behind this context's push of that step
+    hipEvent_t start = nullptr, done = nullptr;  // frame driver: behind the frame's input on the first band's stream; behind a band's output copy
+    hipStream_t stream = nullptr;                // frame driver: the band's stream when the caller gives none
+    char* io[2] = {nullptr, nullptr};            // frame driver: the band's input rows / its output image, on this context's device
+    size_t io_bytes[2] = {0, 0};
+};
+
 }  // namespace nesr
 
 struct nesr_ctx {
@@ -109,6 +127,7 @@ struct nesr_ctx {
     std::vector<StripPlan> strip_plans;
     nesr::FwState band;              // the banded evaluation in progress (nesr_band_*)
     bool band_valid = false;
+    nesr::BandLink link;             // row bands inside one process (nesr_band_link, nesr_forward_banded*)
     nesr::EventTimer timer;          // kernel timing hook
 
     size_t esize() const { return form->esize; }
@@ -132,6 +151,9 @@ int rrdb_only(const nesr_ctx* c, const char* entry);
 
 inline int layer_id(int b, int r, int k) { return 1 + (b * 3 + r) * 5 + k; }  // RDB r, conv k of RRDB b; r, k zero based
 inline double conv_flops(const Layer& L, double pixels) { return 2.0 * 9.0 * L.cin * L.cout * pixels; }
+
+// ---- band_api.cpp: nesr_destroy's part of the band links (neighbours forget `c`; buffers, events and stream are freed)
+void band_release(nesr_ctx* c);
 
 // ---- rrdb_forward.cpp
 WsLayout ws_layout(const nesr_ctx* c, int N, int h, int w);

@@ -141,8 +141,16 @@ class RealESRGANer:
             (repeats put several contexts on one device).  None reads NESR_DEVICES (see parse_devices); with neither set the
             wrapper runs on `device` alone, as upstream's does.  With two or more entries a tiled frame's tiles are split over
             them (sharded.plan_tiles) and enhance_many deals whole frames to them; the result is bitwise the one-device result.
-            Untiled frames run on the first entry, which is also where the output is assembled and `device` points.
+            An image that is ONE network evaluation (tile=0, or a frame no larger than the tile) is split into row bands, one
+            per entry, when the model is an RRDBNet in an f32 form (see _band_plan; `band_devices = False` switches that off, and
+            then, as for every other model, such a frame runs on the first entry).  The first entry is also where the output is
+            assembled and `device` points.
     """
+
+    # Row bands of an untiled frame over `devices` (class attributes: an instance that never sets them has upstream's state)
+    band_devices = True       # None | False: untiled frames run on the first entry
+    BAND_MIN_ROWS = 48        # banded.BAND_MIN_ROWS: internal rows a lane gets at least (fewer lanes below that, down to one)
+    last_bands = None         # [(lo, hi)] internal rows per lane of the last frame's (last) network evaluation; None: it was not banded
 
     def __init__(self, scale, model_path, dni_weight=None, model=None, tile=0, tile_pad=10, pre_pad=10,
                  half=False, device=None, gpu_id=None, devices=None):
@@ -256,7 +264,31 @@ class RealESRGANer:
             self.img = F.pad(self.img, (0, self.mod_pad_w, 0, self.mod_pad_h), "reflect")
 
     def process(self):
-        self.output = self.model(self.img)
+        plan = self._band_plan(self.img) if self.img.shape[0] == 1 else None
+        if plan is None:
+            self.output = self.model(self.img)
+            return
+        self.output = self.model.forward_banded(self.img, plan[0])
+        self.last_bands = plan[1]
+
+    def _band_plan(self, img):
+        """(lanes, bands) when `img`, the image the network sees ([1, 3, H, W] after pre-pad and mod-pad, or the uint8 [H, W, 3]
+        frame of the fused route), is evaluated as row bands over `devices`, else None: two or more entries, banding not switched
+        off, an RRDBNet in one of the f32 forms (their bands are bit for bit the whole frame; bf16 / f16 pick kernels by image
+        size), and at least BAND_MIN_ROWS internal rows for two lanes.  Lanes: the first len(bands) entries of `devices`."""
+        from . import _lib, banded
+        if not (self._multi() and self.band_devices and isinstance(self.model, RRDBNet) and self.device.type == "cuda"
+                and self.model._dtype_code() in (_lib.DTYPE_F32_SPLIT, _lib.DTYPE_F32_WINOGRAD, _lib.DTYPE_F32)):
+            return None
+        h, w = (img.shape[0], img.shape[1]) if img.dim() == 3 else (img.shape[2], img.shape[3])
+        u = self.model.unshuffle
+        if h % u or w % u:
+            return None
+        bands = banded.band_lanes(h // u, len(self.devices), self.BAND_MIN_ROWS)
+        if len(bands) < 2:
+            return None
+        lanes, _ = _lanes.lanes(self.devices, self._streams, self.device)
+        return lanes[:len(bands)], bands
 
     def tile_grid(self, height, width):
         """The tile windows upstream's tile_process visits, in its order.  Each entry:
@@ -487,7 +519,8 @@ class RealESRGANer:
         return self.output
 
     def _run(self):
-        if self.tile_size > 0:
+        one_tile = self.tile_size > 0 and self.img.shape[2] <= self.tile_size and self.img.shape[3] <= self.tile_size
+        if self.tile_size > 0 and not (one_tile and self.img.shape[0] == 1 and self._band_plan(self.img) is not None):
             self.tile_process()
         else:
             self.process()
@@ -849,6 +882,8 @@ class RealESRGANer:
             return self._enhance_once(img, outscale, alpha_upsampler)
 
     def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan"):
+        if self.last_bands is not None:
+            self.last_bands = None
         h_input, w_input = img.shape[0:2]
         plain_alpha = alpha_upsampler != "realesrgan" and img.ndim == 3 and img.shape[2] == 4
         # upstream: cv2.resize(output, (int(w_input * outscale), int(h_input * outscale)), interpolation=cv2.INTER_LANCZOS4);
@@ -861,11 +896,16 @@ class RealESRGANer:
         if self._fused_u8_ok(img) and not plain_alpha:
             # /255, BGR->RGB, network, clamp, RGB->BGR, x255, round -- all inside the HIP path
             x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
-            y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True)
+            plan = self._band_plan(x)
+            if plan is None:
+                y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True)
+            else:           # row bands over `devices`: byte for byte forward_u8's frame
+                y = self.model.forward_banded_u8(x, plan[0], flip_rgb=True, round_nearest=True)
+                self.last_bands = plan[1]
             if on_device is not None:
                 y = self._resize_u8_on_device(y, on_device)
             output = self._frame_to_host(y).numpy()
-            self._check_range(0)
+            self._check_range(0 if plan is None else None)     # (banded: every lane's context before the frame is used)
             img_mode = "RGB"
             done = on_device is not None
         elif self._u8_on_device_ok(img):

@@ -109,7 +109,7 @@ class RRDBNet(_HipNet):
         self.num_grow_ch = num_grow_ch
         self.compute_dtype = "f16" if compute_dtype == "fp16" else compute_dtype
         self._build_params()
-        self._band = None         # (device, internal height, internal width) of the banded evaluation band_begin started
+        self._band = None         # {(device index, slot): (internal height, internal width)} of the band images band_begin started
 
     # ------------------------------------------------------------------ parameters
     def _build_params(self):
@@ -280,74 +280,209 @@ class RRDBNet(_HipNet):
         return 3 * self.num_block
 
     @torch.no_grad()
-    def band_begin(self, x):
-        """pixel_unshuffle + conv_first on this rank's rows (band + apron): x [1, num_in_ch, H, W] float32 on a ROCm device."""
+    def band_begin(self, x, slot: int = 0):
+        """pixel_unshuffle + conv_first on this rank's rows (band + apron): x [1, num_in_ch, H, W] float32 on a ROCm device.
+        `slot`: the context replica of x's device that holds the band (several bands of one process: see band_link)."""
         self._require_cuda(x)
         if x.dim() != 4 or x.shape[0] != 1:
             raise ValueError(f"expected [1, C, H, W], got {tuple(x.shape)}")
         xf = x.to(torch.float32).contiguous()
         _, c, h, w = xf.shape
-        self._call("nesr_band_begin", xf.device, 0, xf, c, h, w)
-        self._band = (xf.device, h // self.unshuffle, w // self.unshuffle)
+        self._call("nesr_band_begin", xf.device, slot, xf, c, h, w)
+        index = xf.device.index if xf.device.index is not None else torch.cuda.current_device()
+        if self._band is None:
+            self._band = {}
+        self._band[(index, int(slot))] = (h // self.unshuffle, w // self.unshuffle)
+        self._band_last = (index, int(slot))
 
-    def _band_device(self):
-        """The device band_begin ran on; the band_* calls go to its slot 0."""
-        if self._band is None or self._handle(self._band[0].index) is None:
+    def _band_at(self, slot=None, device=None):
+        """(device, slot, internal height, internal width) of the band image of context (device, slot); None = where band_begin
+        ran last (`slot` alone: that slot of the last device)."""
+        last = getattr(self, "_band_last", None)
+        if device is not None:
+            index = torch.device(device).index
+            index = torch.cuda.current_device() if index is None else index
+        else:
+            index = last[0] if last else None
+        slot = (last[1] if last else None) if slot is None and device is None else int(slot or 0)
+        if self._band is None or (index, slot) not in self._band or self._handle(index, slot) is None:
             raise RuntimeError("band_begin has not run")
-        return self._band[0]
+        return (torch.device("cuda", index), slot) + self._band[(index, slot)]
+
+    def _band_call(self, name, slot, device, *args):
+        dev, slot, _, _ = self._band_at(slot, device)
+        self._call(name, dev, slot, *args)
 
     @torch.no_grad()
-    def band_rdb(self, index):
+    def band_rdb(self, index, slot=None, device=None):
         """The five convs of RDB `index` (0 .. num_rdb-1) on the band image."""
-        self._call("nesr_band_rdb", self._band_device(), 0, int(index))
+        self._band_call("nesr_band_rdb", slot, device, int(index))
 
     @torch.no_grad()
-    def band_rdb_phase(self, index, phase, top, bottom, edge_rows):
+    def band_rdb_phase(self, index, phase, top, bottom, edge_rows, slot=None, device=None):
         """Phase 0: conv1..conv4 of RDB `index` and conv5 on the `edge_rows` band rows next to each apron (what the
         neighbours wait for); phase 1: conv5 on the rows in between.  Same values as band_rdb."""
-        self._call("nesr_band_rdb_phase", self._band_device(), 0, int(index), int(phase), int(top), int(bottom), int(edge_rows))
+        self._band_call("nesr_band_rdb_phase", slot, device, int(index), int(phase), int(top), int(bottom), int(edge_rows))
 
-    def band_row_bytes(self):
-        return int(_lib.load().nesr_band_row_bytes(self._handle(self._band_device().index)))
+    def band_row_bytes(self, slot=None, device=None):
+        dev, slot, _, _ = self._band_at(slot, device)
+        return int(_lib.load().nesr_band_row_bytes(self._handle(dev.index, slot)))
 
     @torch.no_grad()
-    def band_pack_edges(self, buffer, top, bottom, nrows, top_dst, bottom_dst):
+    def band_pack_edges(self, buffer, top, bottom, nrows, top_dst, bottom_dst, slot=None, device=None):
         """The first / last `nrows` BAND rows (the rows the neighbours need) of `buffer` -> two preallocated uint8 tensors
         (either may be None), in one C-ABI call."""
-        self._call("nesr_band_pack_edges", self._band_device(), 0, int(buffer), int(top), int(bottom), int(nrows), top_dst, bottom_dst)
+        self._band_call("nesr_band_pack_edges", slot, device, int(buffer), int(top), int(bottom), int(nrows), top_dst, bottom_dst)
 
     @torch.no_grad()
-    def band_unpack_aprons(self, buffer, top, bottom, nrows, top_src, bottom_src):
+    def band_unpack_aprons(self, buffer, top, bottom, nrows, top_src, bottom_src, slot=None, device=None):
         """The neighbours' rows -> the `nrows` apron rows next to the band on each side (either source may be None)."""
-        self._call("nesr_band_unpack_aprons", self._band_device(), 0, int(buffer), int(top), int(bottom), int(nrows), top_src, bottom_src)
+        self._band_call("nesr_band_unpack_aprons", slot, device, int(buffer), int(top), int(bottom), int(nrows), top_src, bottom_src)
 
     @torch.no_grad()
-    def band_tail(self):
+    def band_tail(self, slot=None, device=None):
         """conv_body .. conv_last -> [1, num_out_ch, 4 h, 4 w] float32 (h, w = internal size of the band image)."""
-        dev = self._band_device()
-        _, h, w = self._band
+        dev, slot, h, w = self._band_at(slot, device)
         y = torch.empty((1, self.num_out_ch, 4 * h, 4 * w), dtype=torch.float32, device=dev)
-        self._call("nesr_band_tail", dev, 0, y)
+        self._call("nesr_band_tail", dev, slot, y)
         return y
 
     @torch.no_grad()
-    def band_rows(self, buffer, row0, nrows):
+    def band_rows(self, buffer, row0, nrows, slot=None, device=None):
         """Internal rows [row0, row0+nrows) of the num_feat-channel slice of `buffer` (0..2 dense-block buffers,
         3 = conv_first output) as an opaque uint8 tensor (the context's own element layout)."""
-        out = torch.empty(int(nrows) * self.band_row_bytes(), dtype=torch.uint8, device=self._band_device())
-        self._call("nesr_band_rows", out.device, 0, int(buffer), int(row0), int(nrows), out, 0)
+        dev, slot, _, _ = self._band_at(slot, device)
+        out = torch.empty(int(nrows) * self.band_row_bytes(slot, dev), dtype=torch.uint8, device=dev)
+        self._call("nesr_band_rows", dev, slot, int(buffer), int(row0), int(nrows), out, 0)
         return out
 
     @torch.no_grad()
-    def band_set_rows(self, buffer, row0, rows):
+    def band_set_rows(self, buffer, row0, rows, slot=None, device=None):
         """Inverse of band_rows: overwrites the rows with another rank's band_rows() bytes."""
-        rb = self.band_row_bytes()
+        dev, slot, _, _ = self._band_at(slot, device)
+        rb = self.band_row_bytes(slot, dev)
         if rb == 0:
             raise RuntimeError("band_set_rows: no banded evaluation is active (band_begin has not run, or a whole-frame forward reused the workspace)")
-        rows = rows.to(self._band_device()).contiguous()
+        rows = rows.to(dev).contiguous()
         if rows.dtype != torch.uint8 or rows.numel() % rb:
             raise ValueError("rows must be the uint8 tensor band_rows() returned on the sending rank")
-        self._call("nesr_band_rows", rows.device, 0, int(buffer), int(row0), rows.numel() // rb, rows, 1)
+        self._call("nesr_band_rows", dev, slot, int(buffer), int(row0), rows.numel() // rb, rows, 1)
+
+    # ---- row bands inside one process (include/nesr_hip.h: nesr_band_link ..., DESIGN.md section 6) ----
+    def _lane_handles(self, lanes):
+        """[(device, slot, handle)] of `lanes` = [(device, slot, ...)], contexts created where they are missing."""
+        out = []
+        for lane in lanes:
+            dev = torch.device(lane[0])
+            dev = torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+            out.append((dev, int(lane[1]), self._context(dev, int(lane[1]))))
+        return out
+
+    def band_link(self, lanes):
+        """Makes the contexts of `lanes` = [(device, slot)], top band first, neighbours of one another (nesr_band_link): their
+        band_push_edges calls then write into each other's memory.  Returns band_link_state() of every lane."""
+        hs = self._lane_handles(lanes)
+        for j, (dev, _, h) in enumerate(hs):
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().nesr_band_link(h, hs[j - 1][2] if j else None, hs[j + 1][2] if j + 1 < len(hs) else None), "nesr_band_link")
+        return [self.band_link_state(slot, dev) for dev, slot, _ in hs]
+
+    def band_unlink(self, slot=0, device=None):
+        h = self._existing(slot, device)
+        if h is not None:
+            _lib.check(_lib.load().nesr_band_unlink(h), "nesr_band_unlink")
+
+    def band_link_state(self, slot=0, device=None):
+        """{"up" | "down": None (no neighbour) | "local" (same device, the plain pointer) | "peer" (another device, written through
+        the peer mapping) | "staged" (packed, then a device-to-device copy)} of a context."""
+        h = self._existing(slot, device)
+        v = int(_lib.load().nesr_band_link_state(h)) if h is not None else 0
+        _lib.check(min(v, 0), "nesr_band_link_state")
+        kind = lambda side: None if not v >> side & 1 else ("staged" if not v >> (2 + side) & 1 else ("peer" if v >> (4 + side) & 1 else "local"))   # noqa: E731
+        return {"up": kind(0), "down": kind(1)}
+
+    def band_set_staged(self, on, slot=0, device=None):
+        """Every link of the context as a staged copy, whatever the devices allow (nesr_band_set_staged): A/B runs and tests."""
+        _lib.check(_lib.load().nesr_band_set_staged(self._existing(slot, device), 1 if on else 0), "nesr_band_set_staged")
+
+    @torch.no_grad()
+    def band_push_edges(self, buffer, top, bottom, edge_rows, parity, slot=None, device=None):
+        """This band's first / last `edge_rows` band rows of `buffer` -> the linked neighbours' landing buffers of `parity`, one
+        launch on the current stream.  Ordering against the neighbours' streams is the caller's (events)."""
+        self._band_call("nesr_band_push_edges", slot, device, int(buffer), int(top), int(bottom), int(edge_rows), int(parity))
+
+    @torch.no_grad()
+    def band_land_aprons(self, buffer, top, bottom, edge_rows, parity, also=(), slot=None, device=None):
+        """The landing buffers of `parity` -> the apron rows of `buffer` (and of the buffers in `also`) next to the band."""
+        mask = sum(1 << int(b) for b in also)
+        self._band_call("nesr_band_land_aprons", slot, device, int(buffer), mask, int(top), int(bottom), int(edge_rows), int(parity))
+
+    def _banded(self, entry, src, lanes, out, *args):
+        """nesr_forward_banded / _u8 over `lanes` = [(device, slot[, stream])], top band first; lane 0 is on src's device and runs on
+        its current stream, every other lane on its own stream (given, or kept by the model).  The streams first wait for what
+        their devices' current streams hold (the contexts may still be in use there) and those wait for them afterwards, so the
+        call is ordered like any other forward."""
+        hs = self._lane_handles(lanes)
+        if hs[0][0] != src.device:
+            raise ValueError(f"the first lane is on {hs[0][0]}, the input on {src.device}")
+        if not hasattr(self, "_band_streams"):
+            self._band_streams = {}
+        streams = []
+        for j, (dev, slot, _) in enumerate(hs):
+            cur = torch.cuda.current_stream(dev)
+            if j == 0:
+                st = cur
+            elif len(lanes[j]) > 2 and lanes[j][2] is not None:
+                st = lanes[j][2]
+            else:
+                st = self._band_streams.get((dev.index, slot))
+                if st is None:
+                    st = self._band_streams[(dev.index, slot)] = torch.cuda.Stream(device=dev)
+            if st != cur:
+                st.wait_stream(cur)
+            streams.append(st)
+        n = len(hs)
+        ctxs = (ctypes.c_void_p * n)(*[h.value if isinstance(h, ctypes.c_void_p) else h for _, _, h in hs])
+        sts = (ctypes.c_void_p * n)(*[st.cuda_stream for st in streams])
+        self.calls += 1
+        with torch.cuda.device(src.device):
+            _lib.check(getattr(_lib.load(), entry)(ctxs, n, ctypes.c_void_p(src.data_ptr()), *args, ctypes.c_void_p(out.data_ptr()), sts), entry)
+        for (dev, _, _), st in zip(hs, streams):
+            cur = torch.cuda.current_stream(dev)
+            if st != cur:
+                cur.wait_stream(st)
+        return out
+
+    @torch.no_grad()
+    def forward_banded(self, x, lanes):
+        """forward() of ONE image as row bands, one per lane, inside this process (nesr_forward_banded): x [1, num_in_ch, H, W] float
+        on the first lane's device -> [1, num_out_ch, H*s, W*s] there, for the f32 forms bit for bit forward(x).  `lanes`: see
+        _banded; len(lanes) bands of banded.band_split.  check_range() afterwards covers every lane's context."""
+        self._require_cuda(x)
+        if x.dim() != 4 or x.shape[0] != 1:
+            raise ValueError(f"expected [1, C, H, W], got {tuple(x.shape)}")
+        in_dtype = x.dtype
+        xf = x.to(torch.float32).contiguous()
+        _, c, h, w = xf.shape
+        self._check_input(h, w)
+        s = self.out_scale()
+        y = torch.empty((1, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xf.device)
+        self._banded("nesr_forward_banded", xf, lanes, y, c, h, w)
+        return y if in_dtype == torch.float32 else y.to(in_dtype)
+
+    @torch.no_grad()
+    def forward_banded_u8(self, img_hwc_u8, lanes, flip_rgb=True, round_nearest=True):
+        """forward_u8() of one frame as row bands (nesr_forward_banded_u8): byte for byte forward_u8's result for the f32 forms."""
+        self._require_cuda(img_hwc_u8)
+        if img_hwc_u8.dtype != torch.uint8 or img_hwc_u8.dim() != 3 or img_hwc_u8.shape[2] != 3:
+            raise ValueError("expected a uint8 [H, W, 3] tensor")
+        x = img_hwc_u8.contiguous()
+        h, w, _ = x.shape
+        self._check_input(h, w)
+        s = self.out_scale()
+        y = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=x.device)
+        # (the output goes last in _banded's argument list: the two switches stand before it in the C signature)
+        return self._banded("nesr_forward_banded_u8", x, lanes, y, h, w, 1 if flip_rgb else 0, _lib.ROUND_NEAREST if round_nearest else _lib.ROUND_TRUNC)
 
     # ------------------------------------------------------------------ switches (ContextPool.settings: every context, now and later)
     def set_fused(self, on: bool):
