@@ -85,7 +85,9 @@ enum { NESR_ACT_PRELU = 0, NESR_ACT_RELU = 1, NESR_ACT_LEAKYRELU = 2 };
  *     out  = pixel_shuffle(body(x), s) + nearest_upsample(x, s)
  * State dict: body.{2i}.weight / .bias for the convs, body.{2i+1}.weight [F] for each PReLU (none for relu / leakyrelu).
  *   num_feat 64, num_in_ch == num_out_ch == 3, upscale 2 or 4, 1 <= num_conv <= 1024, act_type one of NESR_ACT_*,
- *   dtype NESR_DTYPE_F32_SPLIT (f32 as f16 pairs, range word as for nesr_create) or NESR_DTYPE_BF16; anything else NESR_ERR_ARG.
+ *   dtype NESR_DTYPE_F32_SPLIT (f32 as f16 pairs, range word as for nesr_create), NESR_DTYPE_BF16 or NESR_DTYPE_F16 (bf16's kernels
+ *   on f16 elements: upstream's half=True numerics; weights rounded to nearest even and refused beyond +-65504 at
+ *   nesr_finalize_weights, the range word as for NESR_DTYPE_F32_SPLIT); anything else NESR_ERR_ARG.
  * On such a context nesr_load_weight, nesr_finalize_weights, nesr_num_tensors, nesr_forward (output [N, 3, sH, sW]),
  * nesr_forward_u8, nesr_workspace_bytes, nesr_reserve, nesr_forward_flops, nesr_set_kernel_timing / nesr_kernel_time_ms
  * (the num_conv body convs), nesr_check_status, nesr_check_range and nesr_destroy work as documented for nesr_create;

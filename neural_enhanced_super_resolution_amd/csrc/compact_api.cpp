@@ -36,7 +36,11 @@ struct nesr_compact {
     EventTimer timer;                                 // kernel timing hook
 
     bool split() const { return dtype == NESR_DTYPE_F32_SPLIT; }
+    bool f16() const { return dtype == NESR_DTYPE_F16; }
+    bool ranged() const { return split() || f16(); }     // the forms whose values end at +-65504: they keep the range word
+    int form() const { return split() ? COMPACT_SPLIT : (f16() ? COMPACT_F16 : COMPACT_BF16); }
     size_t esize() const { return split() ? 4 : 2; }
+    const char* form_name() const { return f16() ? "f16 form" : "f16-pair fp32 form"; }
 };
 
 namespace {
@@ -81,8 +85,8 @@ int compact_create(nesr_compact** out, int device, int num_in_ch, int num_out_ch
     if (num_conv < 1 || num_conv > 1024) return set_error(NESR_ERR_ARG, "nesr_create_compact: num_conv must be 1 .. 1024");
     if (act_type != NESR_ACT_PRELU && act_type != NESR_ACT_RELU && act_type != NESR_ACT_LEAKYRELU)
         return set_error(NESR_ERR_ARG, "nesr_create_compact: act_type must be NESR_ACT_PRELU, NESR_ACT_RELU or NESR_ACT_LEAKYRELU");
-    if (dtype != NESR_DTYPE_F32_SPLIT && dtype != NESR_DTYPE_BF16)
-        return set_error(NESR_ERR_ARG, "nesr_create_compact: dtype must be NESR_DTYPE_F32_SPLIT or NESR_DTYPE_BF16");
+    if (dtype != NESR_DTYPE_F32_SPLIT && dtype != NESR_DTYPE_BF16 && dtype != NESR_DTYPE_F16)
+        return set_error(NESR_ERR_ARG, "nesr_create_compact: dtype must be NESR_DTYPE_F32_SPLIT, NESR_DTYPE_BF16 or NESR_DTYPE_F16");
     int ndev = 0;
     NESR_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device));
@@ -189,21 +193,21 @@ int compact_finalize(nesr_compact* c) {
     for (size_t a = 0; a < c->slope.size(); ++a)
         if (!c->has_slope[a]) miss("body." + std::to_string(2 * a + 1) + ".weight");
     if (nmiss) return set_error(NESR_ERR_STATE, "missing keys in state_dict (" + std::to_string(nmiss) + "): " + missing);
-    if (c->split()) {   // a weight must fit the (hi, lo) pair
+    if (c->ranged()) {   // a weight must fit the (hi, lo) pair, or the f16 value
         for (size_t i = 0; i < c->conv.size(); ++i)
             for (float v : c->conv[i].w)
                 if (!(std::fabs(v) <= 65504.f))
                     return set_error(NESR_ERR_RANGE, "body." + std::to_string(2 * i) + ".weight holds a value that is non-finite or beyond "
-                                                     "+-65504: it does not fit the f16-pair fp32 form (use compute_dtype bf16)");
+                                                     "+-65504: it does not fit the " + c->form_name() + " (use compute_dtype bf16)");
     }
     NESR_TRY(hipSetDevice(c->device));
-    const bool sp = c->split();
+    const int form = c->form();
     size_t bytes = 0;
     c->w_off.clear();
     c->b_off.clear();
     for (auto& L : c->conv) {
         c->w_off.push_back(bytes);
-        bytes = align_up(bytes + compact_weight_bytes(L.cin_p, L.ncb, sp), 256);
+        bytes = align_up(bytes + compact_weight_bytes(L.cin_p, L.ncb, form), 256);
         c->b_off.push_back(bytes);
         bytes = align_up(bytes + (size_t)L.ncb * 16 * 4, 256);
     }
@@ -212,7 +216,7 @@ int compact_finalize(nesr_compact* c) {
     std::vector<char> host(bytes, 0);
     for (size_t i = 0; i < c->conv.size(); ++i) {
         const CLayer& L = c->conv[i];
-        pack_compact_weights(L.w.data(), L.cout, L.cin, L.cin_p, L.ncb, sp, reinterpret_cast<uint16_t*>(host.data() + c->w_off[i]));
+        pack_compact_weights(L.w.data(), L.cout, L.cin, L.cin_p, L.ncb, form, reinterpret_cast<uint16_t*>(host.data() + c->w_off[i]));
         float* b = reinterpret_cast<float*>(host.data() + c->b_off[i]);
         for (int o = 0; o < L.cout; ++o) b[o] = L.b[o];
     }
@@ -256,10 +260,10 @@ int compact_forward(nesr_compact* c, const float* x, const uint8_t* x_u8, int fl
     int rc = ensure_ws(c, ws_layout(c, N, H, W).total);
     if (rc) return rc;
     const CWs L = ws_layout(c, N, H, W);
-    const bool sp = c->split();
-    unsigned* status = sp ? c->d_status : nullptr;
+    const int form = c->form();
+    unsigned* status = c->ranged() ? c->d_status : nullptr;
     if (status) NESR_TRY(launch_status_latch(status, s));   // the range word is per forward (nesr_check_range reports a latched one once)
-    CompactPack p{x, x_u8, flip, N, H, W, sp ? 1 : 0, c->ws + L.act0, reinterpret_cast<float*>(c->ws + L.res)};
+    CompactPack p{x, x_u8, flip, N, H, W, form, c->ws + L.act0, reinterpret_cast<float*>(c->ws + L.res), status};
     NESR_TRY(launch_compact_pack(p, s));
     auto conv = [&](int i, const void* in, void* out) {
         CompactConv a;
@@ -275,16 +279,16 @@ int compact_forward(nesr_compact* c, const float* x, const uint8_t* x_u8, int fl
         return a;
     };
     char* buf[2] = {c->ws + L.a, c->ws + L.b};
-    NESR_TRY(launch_compact_conv(conv(0, c->ws + L.act0, buf[0]), sp, 32, c->cus, s));
+    NESR_TRY(launch_compact_conv(conv(0, c->ws + L.act0, buf[0]), form, 32, c->cus, s));
     NESR_TRY(c->timer.begin(s));
     int cur = 0;
-    for (int i = 1; i <= c->nconv; ++i, cur ^= 1) NESR_TRY(launch_compact_conv(conv(i, buf[cur], buf[cur ^ 1]), sp, 64, c->cus, s));
+    for (int i = 1; i <= c->nconv; ++i, cur ^= 1) NESR_TRY(launch_compact_conv(conv(i, buf[cur], buf[cur ^ 1]), form, 64, c->cus, s));
     NESR_TRY(c->timer.end(s));
     if (c->timer.on) {
         c->timer.launches += c->nconv;
         c->timer.flops += 2.0 * 9.0 * 64 * 64 * (double)N * H * W * c->nconv;
     }
-    NESR_TRY(launch_compact_tail(conv(c->nconv + 1, buf[cur], nullptr), sp, c->up, reinterpret_cast<const float*>(c->ws + L.res), y, y_u8, flip,
+    NESR_TRY(launch_compact_tail(conv(c->nconv + 1, buf[cur], nullptr), form, c->up, reinterpret_cast<const float*>(c->ws + L.res), y, y_u8, flip,
                                round_mode == NESR_ROUND_NEAREST ? 1 : 0, c->cus, s));
     return NESR_OK;
 }
@@ -307,7 +311,8 @@ int compact_check_status(nesr_compact* c) {
 }
 
 int compact_check_range(nesr_compact* c, hipStream_t s) {
-    if (!c->split()) return NESR_OK;   // bf16 has f32's range
+    if (!c->ranged()) return NESR_OK;   // bf16 has f32's range
+    const std::string path = c->f16() ? "f16 path" : "f16-pair fp32 path";
     NESR_TRY(hipSetDevice(c->device));
     NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, 16, hipMemcpyDeviceToHost, s));
     NESR_TRY(hipStreamSynchronize(s));
@@ -317,11 +322,11 @@ int compact_check_range(nesr_compact* c, hipStream_t s) {
     NESR_TRY(hipStreamSynchronize(s));
     c->h_status[0] = c->h_status[3] = 0;
     if (now)
-        return set_error(NESR_ERR_RANGE, "an input or activation of the f16-pair fp32 path was non-finite or exceeded 65504 in magnitude: "
+        return set_error(NESR_ERR_RANGE, "an input or activation of the " + path + " was non-finite or exceeded 65504 in magnitude: "
                                          "the float output of that forward is NaN, an 8-bit output is invalid (use compute_dtype bf16 for "
                                          "such data)");
     return set_error(NESR_ERR_RANGE, "an EARLIER forward on this context (its result was never checked with nesr_check_range) met an input or "
-                                     "activation of the f16-pair fp32 path that was non-finite or exceeded 65504 in magnitude: that forward's "
+                                     "activation of the " + path + " that was non-finite or exceeded 65504 in magnitude: that forward's "
                                      "output was NaN / invalid; the latest forward's output is valid");
 }
 

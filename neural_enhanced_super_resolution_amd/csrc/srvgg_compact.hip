@@ -11,8 +11,12 @@
 //                          64 -> out * s^2, pixel shuffle and the nearest-upsampled input added in the epilogue, every LR pixel
 //                          writing its s x s block of the NCHW f32 result or of the u8 HWC image (clamp, x255, round | trunc)
 //
-// Operand forms (SPLIT template flag):
+// Operand forms (FORM template parameter, the activation layout codes of elem16.h plus the pair form):
 //   bf16  : activations NHWC bf16, v_mfma_f32_16x16x32_bf16, f32 accumulation
+//   f16   : bf16's kernel on f16 elements (E16<3>: v_mfma_f32_16x16x32_f16, round to nearest even as torch's .half()).  f16 tops
+//           out at 65504, so the split form's range contract holds: the pack kernel checks the image it stages, every layer that
+//           stores an f16 activation keeps the largest |x| bit pattern it stored in one VGPR and raises the range word once, and
+//           the tail, which reads the word as it does for the split form, then writes NaN everywhere
 //   split : the project's f32 form: activations NHWC f32; on the way into LDS every value becomes a pair of halves
 //           x = hi + lo 2^-11 and each product is three v_mfma_f32_16x16x32_f16 (hi*hi into one accumulator, hi*lo + lo*hi into a
 //           second one scaled by 2^-11 at the end).  A value beyond +-65504 or non-finite sets the sticky range word instead
@@ -24,19 +28,19 @@
 // is the weights (16 output channels), B the pixels, so a lane's accumulator holds 4 consecutive channels of one pixel.  For
 // one horizontal tap dx a wave reads the WR + 2 input rows it needs once and uses each fragment for up to three vertical taps.
 // The (4 WR + 2) x 34 input tile sits in LDS with its 16-byte chunks XOR-swizzled by pixel (conflict-free ds_read_b128).
-//   bf16  : WR = 4 (16 x 32 tiles); the layer's weights (73.7 KB) stay resident in LDS and a grid of one workgroup per CU walks
+//   bf16, f16 : WR = 4 (16 x 32 tiles); the layer's weights (73.7 KB) stay resident in LDS and a grid of one workgroup per CU walks
 //           the tiles, so weights are read once per CU and layer
 //   split : WR = 2 (8 x 32 tiles); the f16-pair weights (147 KB) do not fit beside a tile, so the three taps of one column dx
 //           (49 KB) are streamed into LDS per dx
 #include <hip/hip_bf16.h>
 
 #include "compact_api.h"
+#include "elem16.h"
 
 namespace nesr {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -87,8 +91,9 @@ struct TailOut {
 
 // CIN: 32 (first layer, 3 channels zero padded) or 64.  NCB: output 16-channel blocks (4 for a feature layer; tail: 3 for
 // s = 4 (48 channels), 1 for s = 2 (12 of 16)).  TAIL: the epilogue of the last conv.
-template <bool SPLIT, int CIN, int NCB, bool TAIL>
+template <int FORM, int CIN, int NCB, bool TAIL>
 __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a, TailOut t) {
+    constexpr bool SPLIT = FORM == COMPACT_SPLIT, F16 = FORM == COMPACT_F16;
     typedef Form<SPLIT> G;
     constexpr int WR = G::WR, TH = G::TH, NPIX = G::NPIX;
     constexpr int PB = pix_bytes<SPLIT, CIN>();
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a,
     const int H = a.h, W = a.w;
     const int tiles_x = (W + TW - 1) / TW, tiles_y = (H + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y * a.n;
-    unsigned bad = 0;
+    unsigned bad = 0;                                   // split: a value did not fit; f16: the largest |x| bit pattern stored
 
     auto stage_w = [&](int first, int count) {          // fragments [first, first + count) -> s_w
         const uint4* src = reinterpret_cast<const uint4*>(static_cast<const char*>(a.wt) + (size_t)first * G::FRAG);
@@ -197,7 +202,14 @@ __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a,
                     for (int cb = 0; cb < NCB; ++cb) {
                         const char* f = wbase + (size_t)((dy * KC + kc) * NCB + cb) * G::FRAG + lane * 16;
                         const uint4 wh = *reinterpret_cast<const uint4*>(f);
-                        if (!SPLIT) {
+                        if (F16) {
+                            const f32x4 A = __builtin_bit_cast(f32x4, wh);
+#pragma unroll
+                            for (int o = 0; o < WR; ++o)
+#pragma unroll
+                                for (int b = 0; b < 2; ++b)
+                                    acc[o][b][cb] = E16<3>::mfma16(A, __builtin_bit_cast(f32x4, bh[o + dy][b]), acc[o][b][cb]);
+                        } else if (!SPLIT) {
                             const bf16x8 A = __builtin_bit_cast(bf16x8, wh);
 #pragma unroll
                             for (int o = 0; o < WR; ++o)
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a,
         }
 
         // ---- epilogue: lane holds channels cb*16 + 4g .. +3 of pixel (y0 + wave*WR + o, x0 + b*16 + col)
-        const bool poisoned = TAIL && SPLIT && a.status && *reinterpret_cast<volatile const unsigned*>(a.status);
+        const bool poisoned = TAIL && (SPLIT || F16) && a.status && *reinterpret_cast<volatile const unsigned*>(a.status);
 #pragma unroll
         for (int o = 0; o < WR; ++o) {
             const int y = y0 + wave * WR + o;
@@ -244,7 +256,11 @@ __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a,
                     if (!TAIL) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = v[i] < 0.f ? v[i] * a.slope[c0 + i] : v[i];
-                        if (!SPLIT) {
+                        if (F16) {
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) bad = E16<3>::amax(bad, v[i]);
+                            *reinterpret_cast<uint2*>(static_cast<uint16_t*>(a.out) + pix * NF + c0) = E16<3>::pack4(v);
+                        } else if (!SPLIT) {
                             const __bf16 q[4] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
                             *reinterpret_cast<uint2*>(static_cast<uint16_t*>(a.out) + pix * NF + c0) = __builtin_bit_cast(uint2, q);
                         } else {
@@ -279,8 +295,10 @@ __global__ __launch_bounds__(THREADS, 1) void compact_conv_kernel(CompactConv a,
         }
     }
     if (SPLIT && a.status && bad) atomicOr(a.status, 1u);
+    if (F16 && !TAIL) raise_range(a.status, bad);
 }
 
+template <int FORM>
 __global__ void compact_pack_kernel(CompactPack p) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t npix = (size_t)p.n * p.h * p.w;
@@ -293,11 +311,22 @@ __global__ void compact_pack_kernel(CompactPack p) {
         else v[c] = p.x[(n * 3 + c) * p.h * p.w + yx];
     }
     *reinterpret_cast<f32x4*>(p.res + i * 4) = f32x4{v[0], v[1], v[2], 0.f};
-    if (p.split) {
+    if (FORM == COMPACT_SPLIT) {
         f32x4* d = reinterpret_cast<f32x4*>(static_cast<float*>(p.out) + i * 32);
         d[0] = f32x4{v[0], v[1], v[2], 0.f};
 #pragma unroll
         for (int k = 1; k < 8; ++k) d[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else if (FORM == COMPACT_F16) {
+        // the first conv reads f16: what the split form checks as it stages the image is checked here
+        unsigned m = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m = E16<3>::amax(m, v[c]);
+        raise_range(p.status, m);
+        uint4* d = reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + i * 32);
+        const uint2 lo = E16<3>::pack4(f32x4{v[0], v[1], v[2], 0.f});
+        d[0] = uint4{lo.x, lo.y, 0u, 0u};
+#pragma unroll
+        for (int k = 1; k < 4; ++k) d[k] = uint4{0u, 0u, 0u, 0u};
     } else {
         uint4* d = reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + i * 32);
         const __bf16 q[8] = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
@@ -307,18 +336,19 @@ __global__ void compact_pack_kernel(CompactPack p) {
     }
 }
 
-template <bool SPLIT, int CIN, int NCB, bool TAIL>
+template <int FORM, int CIN, int NCB, bool TAIL>
 hipError_t launch_one(const CompactConv& a, const TailOut& t, int cus, hipStream_t s) {
+    constexpr bool SPLIT = FORM == COMPACT_SPLIT;
     typedef Form<SPLIT> G;
     constexpr int KC = CIN / 32;
     const size_t lds = (size_t)G::NPIX * pix_bytes<SPLIT, CIN>() + (size_t)(SPLIT ? 1 : 3) * 3 * KC * NCB * G::FRAG;
     static unsigned long long done = 0;
-    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&compact_conv_kernel<SPLIT, CIN, NCB, TAIL>), lds, done);
+    hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&compact_conv_kernel<FORM, CIN, NCB, TAIL>), lds, done);
     if (e != hipSuccess) return e;
     const long tiles = (long)a.n * ((a.h + G::TH - 1) / G::TH) * ((a.w + TW - 1) / TW);
-    // one resident workgroup per CU walks the tiles (bf16: the layer's weights are loaded once per CU)
+    // one resident workgroup per CU walks the tiles (bf16, f16: the layer's weights are loaded once per CU)
     const int grid = (int)(tiles < cus ? tiles : cus);
-    hipLaunchKernelGGL((compact_conv_kernel<SPLIT, CIN, NCB, TAIL>), dim3(grid), dim3(THREADS), lds, s, a, t);
+    hipLaunchKernelGGL((compact_conv_kernel<FORM, CIN, NCB, TAIL>), dim3(grid), dim3(THREADS), lds, s, a, t);
     return hipGetLastError();
 }
 
@@ -326,30 +356,40 @@ hipError_t launch_one(const CompactConv& a, const TailOut& t, int cus, hipStream
 
 hipError_t launch_compact_pack(const CompactPack& p, hipStream_t s) {
     const size_t npix = (size_t)p.n * p.h * p.w;
-    hipLaunchKernelGGL(compact_pack_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, p);
+    const dim3 grid((unsigned)((npix + 255) / 256));
+    if (p.form == COMPACT_SPLIT) hipLaunchKernelGGL(compact_pack_kernel<COMPACT_SPLIT>, grid, dim3(256), 0, s, p);
+    else if (p.form == COMPACT_F16) hipLaunchKernelGGL(compact_pack_kernel<COMPACT_F16>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(compact_pack_kernel<COMPACT_BF16>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
 
-hipError_t launch_compact_conv(const CompactConv& a, bool split, int cin, int cus, hipStream_t s) {
+hipError_t launch_compact_conv(const CompactConv& a, int form, int cin, int cus, hipStream_t s) {
     const TailOut t{nullptr, nullptr, nullptr, 0, 0};
-    if (split) return cin == 32 ? launch_one<true, 32, 4, false>(a, t, cus, s) : launch_one<true, 64, 4, false>(a, t, cus, s);
-    return cin == 32 ? launch_one<false, 32, 4, false>(a, t, cus, s) : launch_one<false, 64, 4, false>(a, t, cus, s);
+    if (form == COMPACT_SPLIT)
+        return cin == 32 ? launch_one<COMPACT_SPLIT, 32, 4, false>(a, t, cus, s) : launch_one<COMPACT_SPLIT, 64, 4, false>(a, t, cus, s);
+    if (form == COMPACT_F16)
+        return cin == 32 ? launch_one<COMPACT_F16, 32, 4, false>(a, t, cus, s) : launch_one<COMPACT_F16, 64, 4, false>(a, t, cus, s);
+    return cin == 32 ? launch_one<COMPACT_BF16, 32, 4, false>(a, t, cus, s) : launch_one<COMPACT_BF16, 64, 4, false>(a, t, cus, s);
 }
 
-hipError_t launch_compact_tail(const CompactConv& a, bool split, int scale, const float* res, float* y, uint8_t* y8, int flip, int round,
+hipError_t launch_compact_tail(const CompactConv& a, int form, int scale, const float* res, float* y, uint8_t* y8, int flip, int round,
                                int cus, hipStream_t s) {
     const TailOut t{res, y, y8, flip, round};
-    if (split) return scale == 4 ? launch_one<true, 64, 3, true>(a, t, cus, s) : launch_one<true, 64, 1, true>(a, t, cus, s);
-    return scale == 4 ? launch_one<false, 64, 3, true>(a, t, cus, s) : launch_one<false, 64, 1, true>(a, t, cus, s);
+    if (form == COMPACT_SPLIT)
+        return scale == 4 ? launch_one<COMPACT_SPLIT, 64, 3, true>(a, t, cus, s) : launch_one<COMPACT_SPLIT, 64, 1, true>(a, t, cus, s);
+    if (form == COMPACT_F16)
+        return scale == 4 ? launch_one<COMPACT_F16, 64, 3, true>(a, t, cus, s) : launch_one<COMPACT_F16, 64, 1, true>(a, t, cus, s);
+    return scale == 4 ? launch_one<COMPACT_BF16, 64, 3, true>(a, t, cus, s) : launch_one<COMPACT_BF16, 64, 1, true>(a, t, cus, s);
 }
 
 // OIHW f32 [cout][cin][3][3] -> fragments f = ((dx * 3 + dy) * KC + kc) * ncb + cb, each the MFMA A operand of 16 output
-// channels x 32 input channels: lane l holds W[cb*16 + (l & 15)][kc*32 + 8 (l >> 4) + i], i = 0..7 (bf16: 16 B per lane;
+// channels x 32 input channels: lane l holds W[cb*16 + (l & 15)][kc*32 + 8 (l >> 4) + i], i = 0..7 (bf16, f16: 16 B per lane;
 // split: the hi fragment, then the lo fragment, 1 KiB each).  Padded channels are zero.
-size_t compact_weight_bytes(int cin_p, int ncb, bool split) { return (size_t)9 * (cin_p / 32) * ncb * (split ? 2048 : 1024); }
+size_t compact_weight_bytes(int cin_p, int ncb, int form) { return (size_t)9 * (cin_p / 32) * ncb * (form == COMPACT_SPLIT ? 2048 : 1024); }
 
-void pack_compact_weights(const float* oihw, int cout, int cin, int cin_p, int ncb, bool split, uint16_t* dst) {
+void pack_compact_weights(const float* oihw, int cout, int cin, int cin_p, int ncb, int form, uint16_t* dst) {
     const int KC = cin_p / 32;
+    const bool split = form == COMPACT_SPLIT;
     for (int dx = 0; dx < 3; ++dx)
         for (int dy = 0; dy < 3; ++dy)
             for (int kc = 0; kc < KC; ++kc)
@@ -360,7 +400,9 @@ void pack_compact_weights(const float* oihw, int cout, int cin, int cin_p, int n
                         for (int i = 0; i < 8; ++i) {
                             const int co = cb * 16 + (l & 15), ci = kc * 32 + 8 * (l >> 4) + i;
                             const float w = (co < cout && ci < cin) ? oihw[((size_t)co * cin + ci) * 9 + dy * 3 + dx] : 0.f;
-                            if (!split) {
+                            if (form == COMPACT_F16) {
+                                d[l * 8 + i] = __builtin_bit_cast(uint16_t, (_Float16)w);   // nearest even, as torch's .half()
+                            } else if (!split) {
                                 d[l * 8 + i] = __builtin_bit_cast(uint16_t, (__bf16)w);
                             } else {
                                 const _Float16 h = (_Float16)w;

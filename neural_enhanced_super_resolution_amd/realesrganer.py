@@ -135,7 +135,7 @@ class RealESRGANer:
         tile (int): tile size; 0 = no tiling.
         tile_pad (int): pad size of each tile.  pre_pad (int): reflect pad before the network.
         half (bool): upstream's fp16 switch; here it selects the bf16 MFMA kernels, or keeps a model built with
-            RRDBNet(..., compute_dtype="f16") in f16 (upstream's fp16 numerics).
+            RRDBNet(..., compute_dtype="f16") or SRVGGNetCompact(..., compute_dtype="fp16") in f16 (upstream's fp16 numerics).
         device: 'cuda' (= the ROCm GPU), torch.device or None (-> cuda if available).
         devices (list[int] | None): not upstream's: CUDA device indices one wrapper spreads its work over from this process
             (repeats put several contexts on one device).  None reads NESR_DEVICES (see parse_devices); with neither set the

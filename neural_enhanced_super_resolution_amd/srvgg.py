@@ -75,7 +75,12 @@ class SRVGGNetCompact(_HipNet):
 
     Args mirror upstream: num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type='prelu'.
     Extra keyword ``compute_dtype``: "f32" (default; operands as f16 pairs, three f16 MFMAs per product, values beyond
-    +-65504 raise NesrRangeError) or "bf16" (what ``.half()`` / ``.to(torch.bfloat16)`` select, as for RRDBNet).
+    +-65504 raise NesrRangeError), "bf16" (what ``.half()`` / ``.to(torch.bfloat16)`` select, as for RRDBNet) or "fp16"
+    (f16 storage and MFMA operands, f32 accumulation: upstream's half=True numerics at one MFMA per product.  Opt-in: a
+    model built with it stays fp16 through ``.half()`` / ``.to(torch.float16)`` / ``RealESRGANer(half=True)``, any other
+    model keeps turning bf16 there.  The range contract of "f32" holds: a weight beyond +-65504 is refused at upload, an
+    input or activation beyond it makes the float output NaN and raises NesrRangeError at check_range()).  The spelling
+    is "fp16" only: "f16", which RRDBNet also takes, stays a ValueError here.
     The HIP path supports num_feat 64, num_in_ch == num_out_ch == 3 and upscale 2 or 4.
     The contexts, replicas, forward calls and range checks are _HipNet's (the C ABI is RRDBNet's; only creation differs).
     """
@@ -106,7 +111,14 @@ class SRVGGNetCompact(_HipNet):
             return _lib.DTYPE_F32_SPLIT
         if self.compute_dtype in ("bf16", torch.bfloat16, "half", torch.float16):
             return _lib.DTYPE_BF16
-        raise ValueError(f"compute_dtype {self.compute_dtype!r}: expected 'f32' or 'bf16'")
+        if self.compute_dtype == "fp16":
+            return _lib.DTYPE_F16               # f16 operands on the f16 matrix cores, range-checked (|x| <= 65504)
+        raise ValueError(f"compute_dtype {self.compute_dtype!r}: expected 'f32', 'bf16' or 'fp16'")
+
+    def _to_bf16(self):
+        """As _HipNet's, but a model built with compute_dtype="fp16" stays fp16 (upstream's fp16 run)."""
+        if self.compute_dtype != "fp16":
+            self.compute_dtype = "bf16"
 
     def _create(self, index, code):
         handle = ctypes.c_void_p()

@@ -3,11 +3,16 @@ RealESRGANer, per-kernel time of the body convs against their binding bound, and
 composition (F.conv2d / F.prelu / pixel_shuffle / interpolate) on the same GPU and dtype as the baseline.
 
     python tools/bench_compact.py [--steps 5] [--warmup 2] [--out profiles/compact/bench_compact.json]
-                                  [--models x4v3,animevideov3] [--dtypes f32,bf16] [--workloads 1080p,2160p-tiled] [--no-torch]
+                                  [--models x4v3,animevideov3] [--dtypes f32,bf16,fp16] [--workloads 1080p,2160p-tiled] [--no-torch]
+                                  [--alternate bf16,fp16 [--rounds 15]]
 
 Prints one JSON line per case and writes them all to --out.  Weights are seeded synthetic (synth.py).  Bounds use the
 chip-level peaks: 2.5 PFLOP/s dense bf16 / f16 MFMA (the f32 form issues three f16 MFMAs per product, so its compute bound
-is FLOPs x 3 / 2.5 PF) and 8 TB/s HBM.
+is FLOPs x 3 / 2.5 PF) and 8 TB/s HBM.  dtype fp16 is SRVGGNetCompact(compute_dtype="fp16") under half=True (upstream's fp16 run); its
+torch baseline is the composition in torch.float16.  --alternate A,B times two dtypes in ONE process, their calls taking turns
+round by round (what a ratio of a few per cent needs: two separate cases differ by more than that), and adds the medians and
+the ratio B : A to the output; the profiles/compact/bench_compact_fp16.json of the repository is
+`--dtypes bf16,fp16 --alternate bf16,fp16 --no-torch --out profiles/compact/bench_compact_fp16.json`.
 """
 from __future__ import annotations
 
@@ -64,14 +69,53 @@ def torch_net(sd, cfg, dtype, dev):
     return run
 
 
+def wrapper(cfg, sd, dtype, tile, dev):
+    """dtype "f32": half=False; "bf16": half=True with a default model; "fp16": half=True with a compute_dtype="fp16" model."""
+    model = SRVGGNetCompact(**cfg, compute_dtype="fp16") if dtype == "fp16" else SRVGGNetCompact(**cfg)
+    return RealESRGANer(scale=cfg["upscale"], model_path={"params": {k: v.clone() for k, v in sd.items()}}, model=model, tile=tile,
+                        tile_pad=10, pre_pad=0, half=dtype != "f32", device=dev)
+
+
+def alternated(model, pair, workload, rounds, warmup):
+    """Two dtypes in one process, one call each per round: device u8 -> u8 (whole frames) and host u8 -> host u8."""
+    cfg = MODELS[model]
+    H, W, tile = WORKLOADS[workload]
+    dev = torch.device("cuda:0")
+    sd = synthetic_compact_state_dict(seed=0, **cfg)
+    ups = {dt: wrapper(cfg, sd, dt, tile, dev) for dt in pair}
+    img = synthetic_frame(H, W, seed=0)
+    x_dev = torch.from_numpy(img).to(dev)
+    res = {"tool": "bench_compact", "mode": "alternated", "model": model, "pair": list(pair), "workload": workload, "rounds": rounds}
+
+    def turns(fns):
+        ts = {dt: [] for dt in pair}
+        for r in range(warmup + rounds):
+            for dt in (pair if r % 2 == 0 else pair[::-1]):          # neither is always the one that runs on a cold cache
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fns[dt]()
+                torch.cuda.synchronize()
+                if r >= warmup:
+                    ts[dt].append(time.perf_counter() - t0)
+        return {dt: {"median_ms": round(statistics.median(v) * 1e3, 3), "min_ms": round(min(v) * 1e3, 3), "max_ms": round(max(v) * 1e3, 3)}
+                for dt, v in ts.items()}
+    if not tile:
+        res["device_u8"] = turns({dt: (lambda up=ups[dt]: up.model.forward_u8(x_dev, flip_rgb=True, round_nearest=True)) for dt in pair})
+        res["device_u8"]["ratio"] = round(res["device_u8"][pair[1]]["median_ms"] / res["device_u8"][pair[0]]["median_ms"], 4)
+    res["host_to_host"] = turns({dt: (lambda up=ups[dt]: up.enhance(img)) for dt in pair})
+    res["host_to_host"]["ratio"] = round(res["host_to_host"][pair[1]]["median_ms"] / res["host_to_host"][pair[0]]["median_ms"], 4)
+    for up in ups.values():
+        up.model.check_status()
+    return res
+
+
 def case(model, dtype, workload, steps, warmup, with_torch):
     cfg = MODELS[model]
     H, W, tile = WORKLOADS[workload]
     s = cfg["upscale"]
     dev = torch.device("cuda:0")
     sd = synthetic_compact_state_dict(seed=0, **cfg)
-    up = RealESRGANer(scale=s, model_path={"params": sd}, model=SRVGGNetCompact(**cfg), tile=tile, tile_pad=10, pre_pad=0,
-                      half=dtype == "bf16", device=dev)
+    up = wrapper(cfg, sd, dtype, tile, dev)
     img = synthetic_frame(H, W, seed=0)
     sec, out = timed(lambda: up.enhance(img)[0], steps, warmup)
     out_px = H * s * W * s
@@ -105,7 +149,7 @@ def case(model, dtype, workload, steps, warmup, with_torch):
                             "binding": "mfma" if t_flop >= t_byte else "hbm", "share_of_bound": round(bound / (per * 1e-3), 3),
                             "TFLOPps": round(flops / (ms * 1e-3) / 1e12, 1)}
     if with_torch:
-        tdt = torch.float32 if dtype == "f32" else torch.bfloat16
+        tdt = {"f32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[dtype]
         net = torch_net(sd, cfg, tdt, dev)
         lut = torch.from_numpy(np.arange(256, dtype=np.float32) / 255).to(dev)
 
@@ -145,6 +189,8 @@ def main():
     ap.add_argument("--dtypes", default="f32,bf16")
     ap.add_argument("--workloads", default="1080p,2160p-tiled")
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--alternate", default="", help="two dtypes, e.g. bf16,fp16: timed in one process, their calls taking turns")
+    ap.add_argument("--rounds", type=int, default=15, help="rounds of --alternate")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     rows = []
@@ -154,10 +200,19 @@ def main():
                 r = case(m, dt, wl, a.steps, a.warmup, not a.no_torch)
                 print(json.dumps(r), flush=True)
                 rows.append(r)
+    turns = []
+    if a.alternate:
+        pair = a.alternate.split(",")
+        assert len(pair) == 2, "--alternate takes two dtypes"
+        for m in a.models.split(","):
+            for wl in a.workloads.split(","):
+                r = alternated(m, pair, wl, a.rounds, a.warmup)
+                print(json.dumps(r), flush=True)
+                turns.append(r)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
-            json.dump({"device": torch.cuda.get_device_name(0), "cases": rows}, f, indent=1)
+            json.dump({"device": torch.cuda.get_device_name(0), "cases": rows, **({"alternated": turns} if turns else {})}, f, indent=1)
 
 
 if __name__ == "__main__":
