@@ -445,6 +445,42 @@ int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, doub
 int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int adaptive_sharpening, uint8_t* out_dev, void* hip_stream);
 
 /*
+ * The image half of SuperResolutionPipeline._segment_and_enhance (nesr/nesr.py:726-747; standalone/superres_project.py:249-270) on
+ * [H, W, 3] u8 RGB -- imgproc.segment_enhance.  Everything after the segmenter's argmax: mask_dev is `(seg_map > 0).astype(np.uint8)`
+ * (nesr/nesr.py:731), [mask_h, mask_w] u8 {0, 1}, rows contiguous, at the segmenter's resolution.
+ *   launch 1: `cv2.resize(object_mask, (w, h))` (:732, cv2's default INTER_LINEAR) = nesr_resize_cv_u8(NESR_INTER_LINEAR) into
+ *             scratch_dev; skipped when the sizes are equal.  The rounded result is again {0, 1}.
+ *   launch 2: one fused stencil -- `cv2.dilate(object_mask, np.ones((3, 3)))` (:735-736: the max over the neighbours inside the
+ *             image; cv2's default border never wins a max), `cv2.GaussianBlur(enhanced, (0, 0), 3)` and
+ *             `cv2.addWeighted(enhanced, 1.5, blurred, -0.5, 0)` (:739-740: saturate(round(1.5 x - 0.5 blur)), the value and the
+ *             code of nesr_postprocess_u8), `np.where(mask == 1, sharpened, enhanced)` (:743-747).
+ * scratch_dev: at least nesr_segment_enhance_scratch_bytes(H, W) = round_up(H W, 256) bytes of device memory, always required.
+ * rgb_dev != out_dev.  Both launches are enqueued on hip_stream; no allocation and no synchronisation after the first call for a
+ * (device, mask size, frame size), which uploads the mask's resize tables (as nesr_resize_cv_u8).  A null pointer, a size below 1,
+ * rgb_dev == out_dev or a short scratch: NESR_ERR_ARG before any device is touched.
+ * The reference's branch for frames above 1024 pixels (nesr/nesr.py:703-724) resizes the class map with INTER_NEAREST first;
+ * nearest commutes with `> 0`, so a caller does it on the mask: nesr_resize_cv_u8(NESR_INTER_NEAREST) to H x W, then this entry.
+ * Bit for bit imgproc.segment_enhance's torch chain; parity unpinned against cv2 (absent): checked against tests/cv2_stages_ref.py.
+ */
+size_t nesr_segment_enhance_scratch_bytes(int H, int W);
+int nesr_segment_enhance_u8(int device_id, const uint8_t* rgb_dev, int H, int W, const uint8_t* mask_dev, int mask_h, int mask_w,
+                            void* scratch_dev, size_t scratch_bytes, uint8_t* out_dev, void* hip_stream);
+
+/*
+ * SuperResolutionPipeline._ensemble_results (nesr/nesr.py:1033-1054) on 1 <= n <= 8 u8 images of equal shape [H, W, C], rows
+ * contiguous; images_dev is a HOST array of n device pointers -- imgproc.ensemble_results after its Lanczos alignment.  The mean is
+ * the arithmetic of nesr/nesr.py:1048-1054 under NumPy 1.x, every step rounded to float32: w = float32(1 / n), acc = 0, for each
+ * image in order acc = fl32(acc + fl32(fl32(x) w)), truncated toward zero to u8 (for n <= 8, n copies of one image give it back:
+ * float32(1 / n) is exact or rounded up; a mean of different images truncates, it does not round).
+ * NumPy >= 2 would promote `img.astype(np.float32) * weights[i]` to float64 (the weight is a float64 scalar) and round once on the
+ * `+=`; this library restates the NumPy 1.x result, the one the reference was written against.  n = 1 copies (nesr/nesr.py:1035-1036).
+ * One elementwise launch on hip_stream that reads each input once, with 16-byte loads and stores when every pointer is 16-byte
+ * aligned (one byte per thread otherwise); no allocation, no synchronisation.  n outside 1..8, a null pointer, a size below 1:
+ * NESR_ERR_ARG before any device is touched.
+ */
+int nesr_ensemble_u8(int device_id, const uint8_t* const* images_dev, int n, int H, int W, int C, uint8_t* out_dev, void* hip_stream);
+
+/*
  * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind
  * RealESRGANer.enhance(outscale=...), its `cv2.resize(alpha, ..., INTER_LINEAR)` behind alpha_upsampler != "realesrgan", and the
  * Lanczos paste of _process_with_tiling (nesr/nesr.py:437-446).  cv2's semantics as imgproc.lanczos4_resize / linear_resize_f32 and
@@ -486,6 +522,39 @@ int nesr_resize_f32(int device_id, const float* src_dev, int src_h, int src_w, i
  *   NESR_INTER_LINEAR: first_out[d] = the clamped first index i0; coef_out[2 d] = f (0 at the clamped ends), coef_out[2 d + 1] =
  *     i1 - i0 (1, or 0 at the last sample). */
 int nesr_resize_taps(int n_in, int n_out, int interp, int* first_out, float* coef_out, int cap, int* n_out_written);
+
+/*
+ * 8-bit cv2.resize with cv2's other interpolations (csrc/resize.hip) -- imgproc.resize_u8: the bicubic step the loop takes when no
+ * model contributes (nesr/nesr.py:597-605; also downsample_image's default, nesr/utils/image_utils.py:119-128), the default
+ * (linear) resize of the object mask (nesr/nesr.py:732) and the nearest resize of the class map (nesr/nesr.py:720-724).  The
+ * contract is nesr_resize_u8's: C = 1, 3 or 4; base pointer + row stride in bytes, no byte outside the destination rectangle is
+ * written; equal sizes copy; every argument is checked before a device is touched (an interp that is none of the four, C = 2, a
+ * null pointer, a short stride, src == dst: NESR_ERR_ARG); tables per (device, kind, n_in, n_out), later calls only enqueue.  Each
+ * form is one launch with both passes and no intermediate in device memory.  The sampling position is nesr_resize_u8's:
+ * (d + 0.5) n_in / n_out - 0.5 in double, cast to float32, floor + fraction f.  The arithmetic is OpenCV 4.x resize.cpp's:
+ *   NESR_INTER_NEAREST   source index min(floor(d n_in / n_out), n_in - 1) per axis (the product in double); samples are copied.
+ *   NESR_INTER_LINEAR    taps (s, s + 1); f = 0 and s clamped when s < 0 or s >= n_in - 1; coefficients short(rint((1 - f) 2048)) and
+ *                        short(rint(f 2048)), 1 - f in float32; horizontal t = S[s] a0 + S[s + 1] a1 in int32; vertical
+ *                        (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2.  When BOTH axes shrink by exactly 2 cv2 takes its
+ *                        area filter instead: (a + b + c + d + 2) >> 2 over the 2 x 2 block.
+ *   NESR_INTER_CUBIC     4 taps from s - 1, indices clamped to [0, n_in - 1], f NOT zeroed at the ends; Keys weights with A = -0.75 in
+ *                        float32, evaluated left to right: w0 = ((A (f + 1) - 5 A)(f + 1) + 8 A)(f + 1) - 4 A,
+ *                        w1 = ((A + 2) f - (A + 3)) f f + 1, w2 = the same in 1 - f, w3 = 1 - w0 - w1 - w2; each short(rint(w 2048));
+ *                        integer horizontal and vertical sums, (v + 2^21) >> 22, saturated (the Lanczos kernel with 4 taps).
+ *   NESR_INTER_LANCZOS4  forwards to nesr_resize_u8: the same bytes.
+ * Bit for bit imgproc.resize_u8's torch chain; parity unpinned against cv2 (absent): checked against tests/cv2_stages_ref.py.
+ *
+ * nesr_resize_cv_taps (host only): the integer table of one axis as the kernels read it.  *n_out_written = n_out always; the arrays
+ * are filled when both are given and cap (in positions) >= n_out.  first_out[d], then per position in coef_out:
+ *   NESR_INTER_NEAREST   first = the source index;                      1 coefficient:  1
+ *   NESR_INTER_LINEAR    first = s, clamped (second tap min(s + 1, n_in - 1)); 2 coefficients: a0, a1 (they sum to 2048)
+ *   NESR_INTER_CUBIC     first = floor(position) - 1, NOT clamped;      4 coefficients: coef_out[4 d .. 4 d + 4)
+ *   NESR_INTER_LANCZOS4  first = floor(position) - 3, NOT clamped;      8 coefficients: coef_out[8 d .. 8 d + 8)
+ */
+enum { NESR_INTER_NEAREST = 0, NESR_INTER_CUBIC = 2 };   /* cv2's values, beside NESR_INTER_LINEAR and NESR_INTER_LANCZOS4 */
+int nesr_resize_cv_u8(int device_id, const uint8_t* src_dev, int src_h, int src_w, int C, int64_t src_row_bytes, uint8_t* dst_dev, int dst_h, int dst_w,
+                      int64_t dst_row_bytes, int interp, void* hip_stream);
+int nesr_resize_cv_taps(int n_in, int n_out, int interp, int* first_out, int* coef_out, int cap, int* n_out_written);
 
 /*
  * Gray, BGRA and 16-bit frames (csrc/frame_io.hip): every kind of frame RealESRGANer.enhance (realesrgan utils.py) takes besides

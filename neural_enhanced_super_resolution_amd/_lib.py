@@ -20,6 +20,8 @@ CONV_LAST_GENERAL, CONV_LAST_NARROW = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
 INTER_LINEAR, INTER_LANCZOS4 = 1, 4
+INTER_NEAREST, INTER_CUBIC = 0, 2
+ENSEMBLE_MAX = 8     # images per nesr_ensemble_u8
 ALPHA_NETWORK, ALPHA_LINEAR = 0, 1
 INPUT_12CH, INPUT_3CH_X4 = 0, 1
 STAGE_RECT = 13      # ints per tile of nesr_stage_tile_plan
@@ -97,6 +99,13 @@ SIGNATURES = {
     "nesr_resize_f32": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int,
                                    _c.c_void_p]),
     "nesr_resize_taps": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_float), _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_resize_cv_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int,
+                                     _c.c_void_p]),
+    "nesr_resize_cv_taps": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_segment_enhance_scratch_bytes": (_c.c_size_t, [_c.c_int, _c.c_int]),
+    "nesr_segment_enhance_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                           _c.c_void_p]),
+    "nesr_ensemble_u8": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
                                    _c.c_void_p]),
     "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,

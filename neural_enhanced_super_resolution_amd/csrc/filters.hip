@@ -159,11 +159,17 @@ __global__ __launch_bounds__(256) void gaussian_kernel(const uint8_t* __restrict
 // it stays.  One read and one write of the frame.
 constexpr int PT_X = 64, PT_Y = 32, R2 = 6, R3 = 9;
 
-__global__ __launch_bounds__(256) void postprocess_kernel(const uint8_t* __restrict__ src, int H, int W, SharpenTaps taps, uint8_t* __restrict__ dst) {
+//
+// MASKED = true is the image half of _segment_and_enhance (nesr/nesr.py:735-747; imgproc.segment_enhance): the same unsharp value,
+// selected where the 3 x 3 dilate of a {0, 1} mask [H][W] is 1 instead of where the detail exceeds 10 -- the dilate is the max over
+// the neighbours inside the image (cv2's default border for a dilate never wins a max); no gray plane, no sigma 2 blur.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void postprocess_kernel(const uint8_t* __restrict__ src, int H, int W, SharpenTaps taps, const uint8_t* __restrict__ mask,
+                                                          uint8_t* __restrict__ dst) {
     __shared__ uint8_t rgb[PT_Y + 2 * R3][(PT_X + 2 * R3) * 3];
-    __shared__ uint8_t gray[PT_Y + 2 * R2][PT_X + 2 * R2];
+    __shared__ uint8_t gray[MASKED ? 1 : PT_Y + 2 * R2][MASKED ? 1 : PT_X + 2 * R2];
     __shared__ uint16_t h3[PT_Y + 2 * R3][PT_X * 3];
-    __shared__ uint16_t h2[PT_Y + 2 * R2][PT_X];
+    __shared__ uint16_t h2[MASKED ? 1 : PT_Y + 2 * R2][MASKED ? 1 : PT_X];
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * PT_X, y0 = blockIdx.y * PT_Y;
     constexpr int rows = PT_Y + 2 * R3, cols = PT_X + 2 * R3;
@@ -176,10 +182,12 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const uint8_t* __restr
     }
     __syncthreads();
     constexpr int grows = PT_Y + 2 * R2, gcols = PT_X + 2 * R2, d = R3 - R2;
-    for (int i = tid; i < grows * gcols; i += 256) {      // imgproc.rgb2gray_u8 (gray of a reflected pixel = reflected gray)
-        const int ly = i / gcols, lx = i - ly * gcols;
-        const uint8_t* p = &rgb[ly + d][(lx + d) * 3];
-        gray[ly][lx] = (uint8_t)(((int)p[0] * 4899 + (int)p[1] * 9617 + (int)p[2] * 1868 + (1 << 13)) >> 14);
+    if constexpr (!MASKED) {
+        for (int i = tid; i < grows * gcols; i += 256) {      // imgproc.rgb2gray_u8 (gray of a reflected pixel = reflected gray)
+            const int ly = i / gcols, lx = i - ly * gcols;
+            const uint8_t* p = &rgb[ly + d][(lx + d) * 3];
+            gray[ly][lx] = (uint8_t)(((int)p[0] * 4899 + (int)p[1] * 9617 + (int)p[2] * 1868 + (1 << 13)) >> 14);
+        }
     }
     for (int i = tid; i < rows * PT_X * 3; i += 256) {
         const int ly = i / (PT_X * 3), j = i - ly * (PT_X * 3);
@@ -189,28 +197,38 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const uint8_t* __restr
         h3[ly][j] = (uint16_t)s;
     }
     __syncthreads();
-    for (int i = tid; i < grows * PT_X; i += 256) {
-        const int ly = i / PT_X, j = i - ly * PT_X;
-        int s = 0;
+    if constexpr (!MASKED) {
+        for (int i = tid; i < grows * PT_X; i += 256) {
+            const int ly = i / PT_X, j = i - ly * PT_X;
+            int s = 0;
 #pragma unroll
-        for (int t = 0; t < 2 * R2 + 1; ++t) s += taps.k2[t] * (int)gray[ly][j + t];
-        h2[ly][j] = (uint16_t)s;
+            for (int t = 0; t < 2 * R2 + 1; ++t) s += taps.k2[t] * (int)gray[ly][j + t];
+            h2[ly][j] = (uint16_t)s;
+        }
+        __syncthreads();
     }
-    __syncthreads();
     const int ox = tid & (PT_X - 1), x = x0 + ox;
     for (int oy = tid / PT_X; oy < PT_Y; oy += 256 / PT_X) {
         const int y = y0 + oy;
         if (y >= H || x >= W) continue;
-        int s2 = 0;
+        bool sharpen;
+        if constexpr (MASKED) {
+            int m = 0;
+            for (int yy = max(y - 1, 0); yy <= min(y + 1, H - 1); ++yy)
+                for (int xx = max(x - 1, 0); xx <= min(x + 1, W - 1); ++xx) m = max(m, (int)mask[(size_t)yy * W + xx]);
+            sharpen = m == 1;
+        } else {
+            int s2 = 0;
 #pragma unroll
-        for (int t = 0; t < 2 * R2 + 1; ++t) s2 += taps.k2[t] * (int)h2[oy + t][ox];
-        int detail = (int)gray[oy + R2][ox + R2] - round_shift16(s2);
-        detail = detail < 0 ? 0 : detail;
+            for (int t = 0; t < 2 * R2 + 1; ++t) s2 += taps.k2[t] * (int)h2[oy + t][ox];
+            const int detail = (int)gray[oy + R2][ox + R2] - round_shift16(s2);     // saturate(gray - blur): only > 10 matters
+            sharpen = detail > 10;
+        }
         uint8_t* q = dst + ((size_t)y * W + x) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int v = rgb[oy + R3][(ox + R3) * 3 + c];
-            if (detail > 10) {
+            if (sharpen) {
                 int s3 = 0;
 #pragma unroll
                 for (int t = 0; t < 2 * R3 + 1; ++t) s3 += taps.k3[t] * (int)h3[oy + t][ox * 3 + c];
@@ -222,7 +240,51 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const uint8_t* __restr
     }
 }
 
+// imgproc.ensemble_results on equal shapes: acc = fl32(acc + fl32(fl32(x) w)) over the images in order, truncated.  VEC: every
+// pointer is 16-byte aligned -- a thread takes 16 bytes of each image with one load and stores 16; the < 16 tail bytes go to the
+// threads after the last vector, one byte each.  Else one byte per thread.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ensemble_kernel(EnsembleArgs a) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t nvec = VEC ? a.total / 16 : 0;
+    if (VEC && i < nvec) {
+        float acc[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) acc[b] = 0.0f;
+        for (int k = 0; k < a.n; ++k) {
+            const uint4 v = reinterpret_cast<const uint4*>(a.img[k])[i];
+            const unsigned w4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int b = 0; b < 16; ++b) acc[b] = add_rn(acc[b], mul_rn((float)((w4[b >> 2] >> (8 * (b & 3))) & 255u), a.w));
+        }
+        unsigned o[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int b = 0; b < 16; ++b) o[b >> 2] |= ((unsigned)(int)acc[b] & 255u) << (8 * (b & 3));
+        reinterpret_cast<uint4*>(a.out)[i] = make_uint4(o[0], o[1], o[2], o[3]);
+        return;
+    }
+    const size_t j = nvec * 16 + (i - nvec);
+    if (j >= a.total) return;
+    float acc = 0.0f;
+    for (int k = 0; k < a.n; ++k) acc = add_rn(acc, mul_rn((float)a.img[k][j], a.w));
+    a.out[j] = (uint8_t)(int)acc;
+}
+
 }  // namespace
+
+hipError_t launch_ensemble(const EnsembleArgs& a, hipStream_t s) {
+    if (a.n < 1 || a.n > ENSEMBLE_MAX) return hipErrorInvalidValue;
+    if (a.total == 0) return hipSuccess;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(a.out);
+    for (int k = 0; k < a.n; ++k) bits |= reinterpret_cast<uintptr_t>(a.img[k]);
+    const bool vec = (bits & 15) == 0;
+    const size_t threads = vec ? a.total / 16 + a.total % 16 : a.total;
+    const size_t blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (vec) hipLaunchKernelGGL(ensemble_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(ensemble_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_lab(const LabArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
@@ -241,7 +303,13 @@ hipError_t launch_gaussian(const uint8_t* src, int H, int W, int C, const GaussT
 
 hipError_t launch_postprocess(const uint8_t* src, int H, int W, const SharpenTaps& taps, uint8_t* dst, hipStream_t s) {
     const dim3 grid((unsigned)((W + PT_X - 1) / PT_X), (unsigned)((H + PT_Y - 1) / PT_Y));
-    hipLaunchKernelGGL(postprocess_kernel, grid, dim3(256), 0, s, src, H, W, taps, dst);
+    hipLaunchKernelGGL(postprocess_kernel<false>, grid, dim3(256), 0, s, src, H, W, taps, static_cast<const uint8_t*>(nullptr), dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_segment_sharpen(const uint8_t* src, int H, int W, const SharpenTaps& taps, const uint8_t* mask, uint8_t* dst, hipStream_t s) {
+    const dim3 grid((unsigned)((W + PT_X - 1) / PT_X), (unsigned)((H + PT_Y - 1) / PT_Y));
+    hipLaunchKernelGGL(postprocess_kernel<true>, grid, dim3(256), 0, s, src, H, W, taps, mask, dst);
     return hipGetLastError();
 }
 

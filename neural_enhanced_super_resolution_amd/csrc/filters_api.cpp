@@ -1,5 +1,5 @@
-// C-ABI entries of the pipeline's filters (include/nesr_hip.h): nesr_lab_u8, nesr_gaussian_u8, nesr_postprocess_u8 (kernels of
-// filters.hip), nesr_preprocess_u8 (those and the NL-means / CLAHE kernels of imgproc.hip as one stream-ordered sequence), and the
+// C-ABI entries of the pipeline's filters (include/nesr_hip.h): nesr_lab_u8, nesr_gaussian_u8, nesr_postprocess_u8,
+// nesr_segment_enhance_u8, nesr_ensemble_u8 (kernels of filters.hip), nesr_preprocess_u8 (those and the NL-means / CLAHE kernels of imgproc.hip as one stream-ordered sequence), and the
 // host-side tables the reference's OpenCV calls build internally (nesr_gaussian_taps, nesr_nl_means_weights).  The tables restate
 // imgproc.gaussian_kernel_u8 and imgproc.nl_means_weights in the same double operations (tests/test_filters_host.py compares them).
 #include <cmath>
@@ -226,6 +226,69 @@ int nesr_preprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, doub
     return NESR_OK;
 }
 
+namespace {
+// the taps of _postprocess_image's two blurs; the sigma 3 one is also _segment_and_enhance's
+int sharpen_taps(SharpenTaps& t, const char* who) {
+    std::vector<int> k2, k3;
+    FT_CALL(gaussian_taps(2.0, 0, k2, who));
+    FT_CALL(gaussian_taps(3.0, 0, k3, who));
+    if (k2.size() != 13 || k3.size() != 19) return set_error(NESR_ERR_ARG, std::string(who) + ": unexpected blur sizes");
+    for (int i = 0; i < 13; ++i) t.k2[i] = k2[i];
+    for (int i = 0; i < 19; ++i) t.k3[i] = k3[i];
+    return NESR_OK;
+}
+}  // namespace
+
+size_t nesr_segment_enhance_scratch_bytes(int H, int W) {
+    if (H < 1 || W < 1) return 0;
+    return align_up((size_t)H * W, 256);
+}
+
+int nesr_segment_enhance_u8(int device_id, const uint8_t* rgb_dev, int H, int W, const uint8_t* mask_dev, int mask_h, int mask_w, void* scratch_dev,
+                            size_t scratch_bytes, uint8_t* out_dev, void* stream) {
+    if (!rgb_dev || !mask_dev || !scratch_dev || !out_dev) return set_error(NESR_ERR_ARG, "nesr_segment_enhance_u8: null argument");
+    if (H < 1 || W < 1 || mask_h < 1 || mask_w < 1) return set_error(NESR_ERR_ARG, "nesr_segment_enhance_u8: H, W, mask_h and mask_w must be at least 1");
+    if (rgb_dev == out_dev) return set_error(NESR_ERR_ARG, "nesr_segment_enhance_u8: cannot run in place (rgb == out)");
+    const size_t need = nesr_segment_enhance_scratch_bytes(H, W);
+    if (scratch_bytes < need)
+        return set_error(NESR_ERR_ARG, "nesr_segment_enhance_u8: scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(need) + " needed");
+    SharpenTaps t{};
+    FT_CALL(sharpen_taps(t, "nesr_segment_enhance_u8"));
+    const uint8_t* mask = mask_dev;
+    if (mask_h != H || mask_w != W) {          // cv2.resize(object_mask, (w, h)): the default interpolation, INTER_LINEAR
+        uint8_t* m = static_cast<uint8_t*>(scratch_dev);
+        if (m == mask_dev) return set_error(NESR_ERR_ARG, "nesr_segment_enhance_u8: the mask cannot be the scratch");
+        FT_CALL(nesr_resize_cv_u8(device_id, mask_dev, mask_h, mask_w, 1, mask_w, m, H, W, W, NESR_INTER_LINEAR, stream));
+        mask = m;
+    }
+    NESR_TRY(hipSetDevice(device_id));
+    NESR_TRY(launch_segment_sharpen(rgb_dev, H, W, t, mask, out_dev, static_cast<hipStream_t>(stream)));
+    return NESR_OK;
+}
+
+int nesr_ensemble_u8(int device_id, const uint8_t* const* images_dev, int n, int H, int W, int C, uint8_t* out_dev, void* stream) {
+    if (!images_dev || !out_dev) return set_error(NESR_ERR_ARG, "nesr_ensemble_u8: null argument");
+    if (n < 1 || n > ENSEMBLE_MAX) return set_error(NESR_ERR_ARG, "nesr_ensemble_u8: " + std::to_string(n) + " images (1 to 8)");
+    if (H < 1 || W < 1 || C < 1) return set_error(NESR_ERR_ARG, "nesr_ensemble_u8: H, W and C must be at least 1");
+    EnsembleArgs a{};
+    for (int k = 0; k < n; ++k) {
+        if (!images_dev[k]) return set_error(NESR_ERR_ARG, "nesr_ensemble_u8: null image");
+        a.img[k] = images_dev[k];
+    }
+    a.out = out_dev;
+    a.total = (size_t)H * W * C;
+    a.n = n;
+    a.w = (float)(1.0 / (double)n);            // numpy 1.x: the float64 weight takes the array's float32 (value-based casting)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    NESR_TRY(hipSetDevice(device_id));
+    if (n == 1) {                              // _ensemble_results returns the one image as it is
+        if (images_dev[0] != out_dev) NESR_TRY(hipMemcpyAsync(out_dev, images_dev[0], a.total, hipMemcpyDeviceToDevice, s));
+        return NESR_OK;
+    }
+    NESR_TRY(launch_ensemble(a, s));
+    return NESR_OK;
+}
+
 int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int adaptive_sharpening, uint8_t* out_dev, void* stream) {
     if (!rgb_dev || !out_dev) return set_error(NESR_ERR_ARG, "null argument");
     if (H < 1 || W < 1) return set_error(NESR_ERR_ARG, "nesr_postprocess_u8: H and W must be at least 1");
@@ -237,13 +300,8 @@ int nesr_postprocess_u8(int device_id, const uint8_t* rgb_dev, int H, int W, int
         return NESR_OK;
     }
     if (rgb_dev == out_dev) return set_error(NESR_ERR_ARG, "nesr_postprocess_u8: cannot sharpen in place (rgb == out)");
-    std::vector<int> k2, k3;
-    FT_CALL(gaussian_taps(2.0, 0, k2, "nesr_postprocess_u8"));
-    FT_CALL(gaussian_taps(3.0, 0, k3, "nesr_postprocess_u8"));
     SharpenTaps t{};
-    if (k2.size() != 13 || k3.size() != 19) return set_error(NESR_ERR_ARG, "nesr_postprocess_u8: unexpected blur sizes");
-    for (int i = 0; i < 13; ++i) t.k2[i] = k2[i];
-    for (int i = 0; i < 19; ++i) t.k3[i] = k3[i];
+    FT_CALL(sharpen_taps(t, "nesr_postprocess_u8"));
     NESR_TRY(hipSetDevice(device_id));
     NESR_TRY(launch_postprocess(rgb_dev, H, W, t, out_dev, s));
     return NESR_OK;

@@ -310,6 +310,19 @@ struct SharpenTaps {
     int k3[19];
 };
 hipError_t launch_postprocess(const uint8_t* src, int H, int W, const SharpenTaps& taps, uint8_t* dst, hipStream_t s);
+// the same kernel selecting by the 3 x 3 dilate of mask [H][W] u8 {0, 1} (the image half of _segment_and_enhance); k2 is not read
+hipError_t launch_segment_sharpen(const uint8_t* src, int H, int W, const SharpenTaps& taps, const uint8_t* mask, uint8_t* dst, hipStream_t s);
+
+// _ensemble_results on n <= ENSEMBLE_MAX u8 images of `total` bytes each (filters.hip): the float32 mean with weight w, truncated
+constexpr int ENSEMBLE_MAX = 8;
+struct EnsembleArgs {
+    const uint8_t* img[ENSEMBLE_MAX];
+    uint8_t* out;
+    size_t total;
+    int n;
+    float w;
+};
+hipError_t launch_ensemble(const EnsembleArgs& a, hipStream_t s);
 
 // cv2.resize (resize.hip).  src / dst: base pointer + row stride in bytes, pixels of a row contiguous, C interleaved channels.
 // Lanczos-4 (u8: C = 1, 3, 4, fixed point; u16: float32): xtab / ytab = device tables of dst_w / dst_h positions, int32 first tap
@@ -328,6 +341,13 @@ struct ResizeArgs {
     int tx, ty, max_rows, stage_pitch, out_pitch, region0, lds_bytes;
 };
 hipError_t launch_resize_lanczos4(const ResizeArgs& a, int elem_bytes, hipStream_t s);
+// the other 8-bit interpolations of nesr_resize_cv_u8 (C = 1, 3, 4).  Cubic: the Lanczos kernel with 4 taps (tables: first tap i0 - 1,
+// unclamped, then 4 11-bit coefficients per position; the tile plan counts 4 taps).  Nearest: tables = the source index per position.
+// Linear: tables = the clamped first index per position, then 2 11-bit coefficients per position; both axes shrinking by exactly 2
+// take cv2's area filter instead (no tables read).  Nearest and linear need no tile plan.
+hipError_t launch_resize_cubic_u8(const ResizeArgs& a, hipStream_t s);
+hipError_t launch_resize_nearest_u8(const ResizeArgs& a, hipStream_t s);
+hipError_t launch_resize_linear_u8(const ResizeArgs& a, hipStream_t s);
 hipError_t launch_resize_linear_f32(const ResizeArgs& a, hipStream_t s);
 
 // Whole frames of every kind RealESRGANer.enhance takes (frame_io.hip): u8 / u16, gray / BGR / BGRA.  alpha_form: FRAME_ALPHA_RGB =

@@ -1,9 +1,10 @@
 // cv2.resize as HIP kernels (nesr/nesr.py:437-446 and upstream's RealESRGANer.enhance(outscale=...,
-// alpha_upsampler=...)): INTER_LANCZOS4 on 8-bit (OpenCV's fixed point) and 16-bit (float32) images, INTER_LINEAR on float32.  Each
-// kernel restates the torch chain of imgproc.py (lanczos4_resize, linear_resize_f32) / the loops of oracle/cv2_ref.py operation by
-// operation; parity against cv2 itself is unpinned (cv2 is not installed).
+// alpha_upsampler=...)): INTER_LANCZOS4 on 8-bit (OpenCV's fixed point) and 16-bit (float32) images, INTER_LINEAR on float32; and
+// the 8-bit INTER_NEAREST, INTER_LINEAR and INTER_CUBIC of the rest of enhance_image's loop (nesr/nesr.py:597-605, 720-724, 732;
+// nesr_resize_cv_u8).  Each kernel restates the torch chain of imgproc.py (lanczos4_resize, linear_resize_f32, resize_u8) / the
+// loops of oracle/cv2_ref.py operation by operation; parity against cv2 itself is unpinned (cv2 is not installed).
 //
-// The Lanczos forms run both passes in one launch and keep nothing in HBM between them.  A workgroup owns TY output rows x TX output
+// The Lanczos forms (and the 8-bit bicubic: the same kernel with 4 taps) run both passes in one launch and keep nothing in HBM between them.  A workgroup owns TY output rows x TX output
 // columns.  It copies the source rectangle those outputs read (8 taps per axis, indices clamped = BORDER_REPLICATE) into LDS with
 // aligned 4-byte loads, runs the horizontal pass for every staged source row into LDS planes (int32 for u8, float for u16), runs
 // the vertical pass from those planes, collects the output tile in LDS and stores it as whole aligned 4-byte words (single bytes
@@ -40,7 +41,8 @@ __device__ __forceinline__ uint16_t finish(float v, uint16_t) {
     return (uint16_t)(v < 0.f ? 0.f : (v > 65535.f ? 65535.f : v));
 }
 
-template <typename T, int C>
+// NT taps per axis: 8 = Lanczos-4 (first tap floor - 3), 4 = bicubic (first tap floor - 1; u8 only)
+template <typename T, int C, int NT>
 __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
     using A = typename Acc<T>::type;
     using V = typename std::conditional<sizeof(T) == 1, long long, float>::type;      // vertical accumulator
@@ -55,8 +57,8 @@ __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
     const A* __restrict__ xcoef = reinterpret_cast<const A*>(a.xtab + a.dst_w);
     const A* __restrict__ ycoef = reinterpret_cast<const A*>(a.ytab + a.dst_h);
     // the source rectangle of this tile: first tap of the first output .. last tap of the last one, clamped (the tables are monotone)
-    const int clo = clampi(xfirst[x0], 0, a.src_w - 1), chi = clampi(xfirst[x0 + nx - 1] + 7, 0, a.src_w - 1);
-    const int rlo = clampi(yfirst[y0], 0, a.src_h - 1), rhi = clampi(yfirst[y0 + ny - 1] + 7, 0, a.src_h - 1);
+    const int clo = clampi(xfirst[x0], 0, a.src_w - 1), chi = clampi(xfirst[x0 + nx - 1] + NT - 1, 0, a.src_w - 1);
+    const int rlo = clampi(yfirst[y0], 0, a.src_h - 1), rhi = clampi(yfirst[y0 + ny - 1] + NT - 1, 0, a.src_h - 1);
     const int nr = rhi - rlo + 1;                       // <= a.max_rows
     const int seg = (chi - clo + 1) * C * S;            // bytes of a staged row segment; <= a.stage_pitch - 4
     unsigned char* stage = lds;                         // [nr][stage_pitch] source bytes, then reused as the output tile
@@ -88,12 +90,12 @@ __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
     const int lx = tid & (TX - 1), rstep = 256 / TX;
     if (lx < nx) {
         const int first = xfirst[x0 + lx];
-        int o[8];
-        A w[8];
+        int o[NT];
+        A w[NT];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < NT; ++k) {
             o[k] = (clampi(first + k, 0, a.src_w - 1) - clo) * C * S;
-            w[k] = xcoef[(size_t)(x0 + lx) * 8 + k];
+            w[k] = xcoef[(size_t)(x0 + lx) * NT + k];
         }
         for (int r = tid / TX; r < nr; r += rstep) {
             const unsigned char* row = a.src + (size_t)(rlo + r) * a.src_stride;
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
             for (int c = 0; c < C; ++c) {
                 A acc = 0;
 #pragma unroll
-                for (int k = 0; k < 8; ++k) acc = hstep(acc, w[k], (A)*reinterpret_cast<const T*>(p + o[k] + c * S));
+                for (int k = 0; k < NT; ++k) acc = hstep(acc, w[k], (A)*reinterpret_cast<const T*>(p + o[k] + c * S));
                 hbuf[((size_t)r * C + c) * TX + lx] = acc;
             }
         }
@@ -116,12 +118,12 @@ __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
     if (lx < nx) {
         for (int oy = tid / TX; oy < ny; oy += rstep) {
             const int first = yfirst[y0 + oy];
-            int rr[8];
-            A w[8];
+            int rr[NT];
+            A w[NT];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) {
+            for (int k = 0; k < NT; ++k) {
                 rr[k] = clampi(first + k, 0, a.src_h - 1) - rlo;
-                w[k] = ycoef[(size_t)(y0 + oy) * 8 + k];
+                w[k] = ycoef[(size_t)(y0 + oy) * NT + k];
             }
             const int sh = (int)((reinterpret_cast<uintptr_t>(a.dst + (size_t)(y0 + oy) * a.dst_stride) + dx0) & 3);
             T* q = reinterpret_cast<T*>(otile + (size_t)oy * a.out_pitch + sh) + lx * C;
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(256) void lanczos4_kernel(ResizeArgs a) {
             for (int c = 0; c < C; ++c) {
                 V acc = 0;
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
+                for (int k = 0; k < NT; ++k) {
                     const A h = hbuf[((size_t)rr[k] * C + c) * TX + lx];
                     if constexpr (sizeof(T) == 1) acc += (long long)w[k] * h;
                     else acc = hstep(acc, w[k], h);
@@ -180,25 +182,92 @@ __global__ __launch_bounds__(256) void linear_f32_kernel(ResizeArgs a) {
     }
 }
 
-template <typename T>
+// cv2's other 8-bit interpolations, one output pixel per thread, both passes in registers (nothing between them anywhere):
+//   PT_NEAREST  xtab / ytab = the source index of every position; the samples are copied
+//   PT_LINEAR   tables = first index s (clamped), then 2 coefficients per position (11-bit, non-negative); the second tap is
+//               min(s + 1, n - 1).  OpenCV's 8-bit form: t = S[s] a0 + S[s + 1] a1, then
+//               (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2 -- at most 255, nothing to saturate
+//   PT_AREA2    both axes shrink by exactly 2 (cv2 switches INTER_LINEAR to its area filter): (a + b + c + d + 2) >> 2, no tables
+enum { PT_NEAREST = 0, PT_LINEAR = 1, PT_AREA2 = 2 };
+
+template <int C, int MODE>
+__global__ __launch_bounds__(256) void point_u8_kernel(ResizeArgs a) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.dst_w || y >= a.dst_h) return;
+    uint8_t* q = a.dst + (size_t)y * a.dst_stride + (size_t)x * C;
+    if constexpr (MODE == PT_NEAREST) {
+        const uint8_t* p = a.src + (size_t)a.ytab[y] * a.src_stride + (size_t)a.xtab[x] * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = p[c];
+    } else if constexpr (MODE == PT_AREA2) {
+        const uint8_t* r0 = a.src + (size_t)(2 * y) * a.src_stride + (size_t)(2 * x) * C;
+        const uint8_t* r1 = r0 + a.src_stride;
+#pragma unroll
+        for (int c = 0; c < C; ++c) q[c] = (uint8_t)(((int)r0[c] + (int)r0[C + c] + (int)r1[c] + (int)r1[C + c] + 2) >> 2);
+    } else {
+        const int xa = a.xtab[x], ya = a.ytab[y];
+        const int xb = min(xa + 1, a.src_w - 1), yb = min(ya + 1, a.src_h - 1);
+        const int a0 = a.xtab[a.dst_w + 2 * x], a1 = a.xtab[a.dst_w + 2 * x + 1];
+        const int b0 = a.ytab[a.dst_h + 2 * y], b1 = a.ytab[a.dst_h + 2 * y + 1];
+        const uint8_t* r0 = a.src + (size_t)ya * a.src_stride;
+        const uint8_t* r1 = a.src + (size_t)yb * a.src_stride;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const int t0 = (int)r0[(size_t)xa * C + c] * a0 + (int)r0[(size_t)xb * C + c] * a1;
+            const int t1 = (int)r1[(size_t)xa * C + c] * a0 + (int)r1[(size_t)xb * C + c] * a1;
+            q[c] = (uint8_t)((((b0 * (t0 >> 4)) >> 16) + ((b1 * (t1 >> 4)) >> 16) + 2) >> 2);
+        }
+    }
+}
+
+template <int MODE>
+hipError_t launch_point_u8_t(const ResizeArgs& a, hipStream_t s) {
+    const dim3 grid((unsigned)((a.dst_w + 63) / 64), (unsigned)((a.dst_h + 3) / 4));
+    if (grid.y > 65535u) return hipErrorInvalidValue;
+    if (a.C == 1) hipLaunchKernelGGL((point_u8_kernel<1, MODE>), grid, dim3(256), 0, s, a);
+    else if (a.C == 3) hipLaunchKernelGGL((point_u8_kernel<3, MODE>), grid, dim3(256), 0, s, a);
+    else if (a.C == 4) hipLaunchKernelGGL((point_u8_kernel<4, MODE>), grid, dim3(256), 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+template <typename T, int NT>
 hipError_t launch_lanczos4_t(const ResizeArgs& a, hipStream_t s) {
     const dim3 grid((unsigned)((a.dst_w + a.tx - 1) / a.tx), (unsigned)((a.dst_h + a.ty - 1) / a.ty));
     const size_t lds = (size_t)a.lds_bytes;
-    if (a.C == 1) hipLaunchKernelGGL((lanczos4_kernel<T, 1>), grid, dim3(256), lds, s, a);
-    else if (a.C == 3) hipLaunchKernelGGL((lanczos4_kernel<T, 3>), grid, dim3(256), lds, s, a);
-    else if (a.C == 4) hipLaunchKernelGGL((lanczos4_kernel<T, 4>), grid, dim3(256), lds, s, a);
+    if (a.C == 1) hipLaunchKernelGGL((lanczos4_kernel<T, 1, NT>), grid, dim3(256), lds, s, a);
+    else if (a.C == 3) hipLaunchKernelGGL((lanczos4_kernel<T, 3, NT>), grid, dim3(256), lds, s, a);
+    else if (a.C == 4) hipLaunchKernelGGL((lanczos4_kernel<T, 4, NT>), grid, dim3(256), lds, s, a);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_resize_lanczos4(const ResizeArgs& a, int elem_bytes, hipStream_t s) {
+namespace {
+bool tile_plan_ok(const ResizeArgs& a) {
     if (a.tx < 1 || a.tx > 256 || (a.tx & (a.tx - 1)) || a.ty < 1 || a.lds_bytes > RESIZE_LDS_BUDGET || (a.stage_pitch & 3) || (a.out_pitch & 3) ||
         (a.region0 & 15))
-        return hipErrorInvalidValue;
-    if (a.dst_h > 65535 * a.ty) return hipErrorInvalidValue;
-    return elem_bytes == 1 ? launch_lanczos4_t<uint8_t>(a, s) : elem_bytes == 2 ? launch_lanczos4_t<uint16_t>(a, s) : hipErrorInvalidValue;
+        return false;
+    return a.dst_h <= 65535 * a.ty;
+}
+}  // namespace
+
+hipError_t launch_resize_lanczos4(const ResizeArgs& a, int elem_bytes, hipStream_t s) {
+    if (!tile_plan_ok(a)) return hipErrorInvalidValue;
+    return elem_bytes == 1 ? launch_lanczos4_t<uint8_t, 8>(a, s) : elem_bytes == 2 ? launch_lanczos4_t<uint16_t, 8>(a, s) : hipErrorInvalidValue;
+}
+
+hipError_t launch_resize_cubic_u8(const ResizeArgs& a, hipStream_t s) {
+    if (!tile_plan_ok(a)) return hipErrorInvalidValue;
+    return launch_lanczos4_t<uint8_t, 4>(a, s);
+}
+
+hipError_t launch_resize_nearest_u8(const ResizeArgs& a, hipStream_t s) { return launch_point_u8_t<PT_NEAREST>(a, s); }
+
+hipError_t launch_resize_linear_u8(const ResizeArgs& a, hipStream_t s) {
+    if (a.src_w == 2 * a.dst_w && a.src_h == 2 * a.dst_h) return launch_point_u8_t<PT_AREA2>(a, s);
+    return launch_point_u8_t<PT_LINEAR>(a, s);
 }
 
 hipError_t launch_resize_linear_f32(const ResizeArgs& a, hipStream_t s) {

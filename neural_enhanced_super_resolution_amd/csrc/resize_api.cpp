@@ -1,5 +1,5 @@
-// C-ABI entries of cv2.resize (include/nesr_hip.h): nesr_resize_u8 / _u16 / _f32 (kernels of resize.hip) and the host-side
-// coefficient tables (nesr_resize_taps).  The tables restate imgproc._axis_taps / _lanczos4_coeffs / linear_resize_f32's axis() and
+// C-ABI entries of cv2.resize (include/nesr_hip.h): nesr_resize_u8 / _u16 / _f32 / nesr_resize_cv_u8 (kernels of resize.hip) and the
+// host-side coefficient tables (nesr_resize_taps, nesr_resize_cv_taps).  The tables restate imgproc._axis_taps / _lanczos4_coeffs / linear_resize_f32's axis() and
 // oracle/cv2_ref.py's _lanczos_weights in the same double and float operations, in plain C++ (tests/test_resize_host.py compares
 // them), so a host without torch can resize.  Device copies of the tables are kept per (device, kind, n_in, n_out).
 #include <cmath>
@@ -22,7 +22,7 @@ namespace {
         if (rc__ != NESR_OK) return rc__; \
     } while (0)
 
-enum TableKind { LANCZOS_FIXED = 0, LANCZOS_FLOAT = 1, LINEAR = 2 };
+enum TableKind { LANCZOS_FIXED = 0, LANCZOS_FLOAT = 1, LINEAR = 2, CUBIC_FIXED = 3, LINEAR_FIXED = 4, NEAREST = 5 };
 
 // position d of an axis resized n_in -> n_out: cv2's sampling position (d + 0.5) n_in / n_out - 0.5 in double, cast to float
 void axis_position(int n_in, int n_out, int d, int* i0, float* frac) {
@@ -83,6 +83,33 @@ int fixed11(float c) {           // saturate_cast<short>(c * INTER_RESIZE_COEF_S
     return (int)(v < -32768.f ? -32768.f : (v > 32767.f ? 32767.f : v));
 }
 
+// cv2 interpolateCubic (A = -0.75) in float32, operation by operation (imgproc._cubic_coeffs; the fraction is NOT zeroed at the ends)
+void cubic_coeffs(float x, float co[4]) {
+    const float A = -0.75f;
+    co[0] = ((A * (x + 1.0f) - 5.0f * A) * (x + 1.0f) + 8.0f * A) * (x + 1.0f) - 4.0f * A;
+    co[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
+    co[2] = ((A + 2.0f) * (1.0f - x) - (A + 3.0f)) * (1.0f - x) * (1.0f - x) + 1.0f;
+    co[3] = 1.0f - co[0] - co[1] - co[2];
+}
+
+// INTER_NEAREST: min(floor(d scale), n_in - 1), the scale in double as axis_position takes it
+int nearest_index(int n_in, int n_out, int d) {
+    const double scale = (double)n_in / (double)n_out;
+    const int i = (int)std::floor((double)d * scale);
+    return i < n_in - 1 ? i : n_in - 1;
+}
+
+// INTER_LINEAR, 8 bit: the clamped first tap and short(rint((1 - f) 2048)), short(rint(f 2048)), f = 0 at the clamped ends
+void linear_fixed(int n_in, int n_out, int d, int* i0, int co[2]) {
+    float f;
+    axis_position(n_in, n_out, d, i0, &f);
+    const bool lo = *i0 < 0, hi = *i0 >= n_in - 1;
+    if (lo || hi) f = 0.0f;
+    *i0 = lo ? 0 : (hi ? n_in - 1 : *i0);
+    co[0] = fixed11(1.0f - f);
+    co[1] = fixed11(f);
+}
+
 // the device image of a table (nesr_kernels.h, ResizeArgs): n_out first indices, then the coefficients
 void build_table(TableKind kind, int n_in, int n_out, std::vector<int>& t) {
     union { float f; int i; } u;
@@ -99,6 +126,28 @@ void build_table(TableKind kind, int n_in, int n_out, std::vector<int>& t) {
             t[(size_t)n_out + d] = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
             u.f = f;
             t[(size_t)2 * n_out + d] = u.i;
+        }
+        return;
+    }
+    if (kind == NEAREST) {
+        t.assign((size_t)n_out, 0);
+        for (int d = 0; d < n_out; ++d) t[d] = nearest_index(n_in, n_out, d);
+        return;
+    }
+    if (kind == LINEAR_FIXED) {
+        t.assign((size_t)n_out * 3, 0);
+        for (int d = 0; d < n_out; ++d) linear_fixed(n_in, n_out, d, &t[d], &t[(size_t)n_out + (size_t)d * 2]);
+        return;
+    }
+    if (kind == CUBIC_FIXED) {
+        t.assign((size_t)n_out * 5, 0);
+        for (int d = 0; d < n_out; ++d) {
+            int i0;
+            float f, co[4];
+            axis_position(n_in, n_out, d, &i0, &f);
+            cubic_coeffs(f, co);
+            t[d] = i0 - 1;
+            for (int k = 0; k < 4; ++k) t[(size_t)n_out + (size_t)d * 4 + k] = fixed11(co[k]);
         }
         return;
     }
@@ -158,11 +207,11 @@ int device_table(int device, TableKind kind, int n_in, int n_out, const HostDev*
 }
 
 // source positions a tile of t outputs reads at most (tiles start at multiples of t; first[] is monotone)
-int max_span(const int* first, int n_out, int n_in, int t) {
+int max_span(const int* first, int n_out, int n_in, int t, int taps) {
     int m = 1;
     for (int d0 = 0; d0 < n_out; d0 += t) {
         const int d1 = d0 + t < n_out ? d0 + t : n_out;
-        const int s = first[d1 - 1] + 7 - first[d0] + 1;
+        const int s = first[d1 - 1] + taps - 1 - first[d0] + 1;
         m = s > m ? s : m;
     }
     return m < n_in ? m : n_in;
@@ -175,9 +224,9 @@ int pow2_at_least(int v, int cap) {
 }
 
 // tile shape: the widest, then the tallest power of two whose LDS need fits RESIZE_LDS_BUDGET (1 x 1 needs 8 x 8 samples: always fits)
-void plan_tile(ResizeArgs& a, int S, const int* xfirst, const int* yfirst) {
+void plan_tile(ResizeArgs& a, int S, const int* xfirst, const int* yfirst, int taps = 8) {
     auto need = [&](int tx, int ty) {
-        const int cols = max_span(xfirst, a.dst_w, a.src_w, tx), rows = max_span(yfirst, a.dst_h, a.src_h, ty);
+        const int cols = max_span(xfirst, a.dst_w, a.src_w, tx, taps), rows = max_span(yfirst, a.dst_h, a.src_h, ty, taps);
         a.tx = tx;
         a.ty = ty;
         a.max_rows = rows;
@@ -244,7 +293,62 @@ int lanczos4(int device, int S, ResizeArgs a, void* stream) {
     return NESR_OK;
 }
 
+// nesr_resize_cv_u8's nearest, linear and cubic forms: the two tables, then one launch
+int cv_resize(int device, TableKind kind, ResizeArgs a, void* stream) {
+    NESR_TRY(hipSetDevice(device));
+    std::lock_guard<std::mutex> lock(g_mu);
+    const HostDev *tx = nullptr, *ty = nullptr;
+    make_room();
+    RS_CALL(device_table(device, kind, a.src_w, a.dst_w, &tx));
+    RS_CALL(device_table(device, kind, a.src_h, a.dst_h, &ty));
+    a.xtab = tx->dev;
+    a.ytab = ty->dev;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (kind == CUBIC_FIXED) {
+        plan_tile(a, 1, tx->host.data(), ty->host.data(), 4);
+        NESR_TRY(launch_resize_cubic_u8(a, s));
+    } else if (kind == LINEAR_FIXED) {
+        NESR_TRY(launch_resize_linear_u8(a, s));
+    } else {
+        NESR_TRY(launch_resize_nearest_u8(a, s));
+    }
+    return NESR_OK;
+}
+
+bool cv_interp_known(int interp) {
+    return interp == NESR_INTER_NEAREST || interp == NESR_INTER_LINEAR || interp == NESR_INTER_CUBIC || interp == NESR_INTER_LANCZOS4;
+}
+
 }  // namespace
+
+int nesr_resize_cv_taps(int n_in, int n_out, int interp, int* first_out, int* coef_out, int cap, int* n_out_written) {
+    if (!n_out_written) return set_error(NESR_ERR_ARG, "nesr_resize_cv_taps: null argument");
+    if (n_in < 1 || n_out < 1 || n_in > (1 << 24) || n_out > (1 << 24)) return set_error(NESR_ERR_ARG, "nesr_resize_cv_taps: sizes from 1 to 2^24");
+    if (!cv_interp_known(interp))
+        return set_error(NESR_ERR_ARG, "nesr_resize_cv_taps: interp must be NESR_INTER_NEAREST, NESR_INTER_LINEAR, NESR_INTER_CUBIC or NESR_INTER_LANCZOS4");
+    *n_out_written = n_out;
+    if (!first_out || !coef_out || cap < n_out) return NESR_OK;
+    const TableKind kind = interp == NESR_INTER_NEAREST ? NEAREST : interp == NESR_INTER_LINEAR ? LINEAR_FIXED : interp == NESR_INTER_CUBIC ? CUBIC_FIXED : LANCZOS_FIXED;
+    const int per = interp == NESR_INTER_NEAREST ? 1 : interp == NESR_INTER_LINEAR ? 2 : interp == NESR_INTER_CUBIC ? 4 : 8;
+    std::vector<int> t;
+    build_table(kind, n_in, n_out, t);          // the image the kernels read
+    for (int d = 0; d < n_out; ++d) {
+        first_out[d] = t[d];
+        for (int k = 0; k < per; ++k) coef_out[(size_t)d * per + k] = kind == NEAREST ? 1 : t[(size_t)n_out + (size_t)d * per + k];
+    }
+    return NESR_OK;
+}
+
+int nesr_resize_cv_u8(int device_id, const uint8_t* src_dev, int src_h, int src_w, int C, int64_t src_row_bytes, uint8_t* dst_dev, int dst_h, int dst_w,
+                      int64_t dst_row_bytes, int interp, void* stream) {
+    if (!cv_interp_known(interp))
+        return set_error(NESR_ERR_ARG, "nesr_resize_cv_u8: interpolation " + std::to_string(interp) + " is not supported (NESR_INTER_NEAREST, NESR_INTER_LINEAR, "
+                                       "NESR_INTER_CUBIC or NESR_INTER_LANCZOS4)");
+    RS_CALL(check_args("nesr_resize_cv_u8", "u8", 1, interp, src_dev, src_h, src_w, C, src_row_bytes, dst_dev, dst_h, dst_w, dst_row_bytes, interp, false));
+    const ResizeArgs a = base_args(src_dev, src_h, src_w, C, src_row_bytes, dst_dev, dst_h, dst_w, dst_row_bytes);
+    if (interp == NESR_INTER_LANCZOS4) return lanczos4(device_id, 1, a, stream);
+    return cv_resize(device_id, interp == NESR_INTER_NEAREST ? NEAREST : interp == NESR_INTER_LINEAR ? LINEAR_FIXED : CUBIC_FIXED, a, stream);
+}
 
 int nesr_resize_taps(int n_in, int n_out, int interp, int* first_out, float* coef_out, int cap, int* n_out_written) {
     if (!n_out_written) return set_error(NESR_ERR_ARG, "nesr_resize_taps: null argument");

@@ -5,6 +5,9 @@
   RealESRGANer.enhance(alpha_upsampler=..)  cv2.resize(alpha, INTER_LINEAR)                 [UPSTREAM]
   SuperResolutionPipeline._preprocess_image cv2.fastNlMeansDenoisingColored + CLAHE on L    nesr/nesr.py:668-689
   SuperResolutionPipeline._postprocess_image variance-masked unsharp                        nesr/nesr.py:1056-1084
+  SuperResolutionPipeline._segment_and_enhance, image half: mask resize, dilate, unsharp    nesr/nesr.py:726-747
+  SuperResolutionPipeline._ensemble_results  Lanczos alignment, float32 mean, truncation    nesr/nesr.py:1033-1054
+  enhance_image's no-model step              cv2.resize(INTER_CUBIC)                         nesr/nesr.py:597-605
   (_process_with_tiling's Lanczos paste and the 12-channel builder's 3x3 blur use the same functions: nesr_adapter.py)
 
 PARITY UNPINNED, all of it: cv2 is not installed here or on the GPU box and the reference holds no output of any of
@@ -212,6 +215,117 @@ def linear_resize_f32(img, out_h, out_w, use_hip=None):
     out = rows[:, y0, :] * (1.0 - fy)[None, :, None] + rows[:, y1, :] * fy[None, :, None]
     out = out.permute(1, 2, 0)
     return out[:, :, 0].contiguous() if squeeze else out.contiguous()
+
+
+# ----------------------------------------------------------------------------------------------- 8-bit resize, cv2's other interpolations
+INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_LANCZOS4 = 0, 1, 2, 4      # cv2's values
+
+
+def _cubic_coeffs(frac):
+    """cv2 interpolateCubic (A = -0.75) for a float32 tensor of fractional offsets -> [..., 4] float32 weights, every operation in
+    float32 and in OpenCV's order (left to right)."""
+    A = -0.75
+    x = frac
+    x1 = x + 1.0
+    y = 1.0 - x
+    w0 = ((A * x1 - 5.0 * A) * x1 + 8.0 * A) * x1 - 4.0 * A
+    w1 = ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0
+    w2 = ((A + 2.0) * y - (A + 3.0)) * y * y + 1.0
+    w3 = 1.0 - w0 - w1 - w2
+    return torch.stack([w0, w1, w2, w3], -1)
+
+
+def _fixed11(w):
+    """saturate_cast<short>(w * INTER_RESIZE_COEF_SCALE): rint(w 2048) as int64."""
+    return torch.round(w * 2048.0).clamp_(-32768, 32767).to(torch.int64)
+
+
+def resize_u8_tables(n_in, n_out, interp):
+    """(first index [n_out], integer coefficients [n_out, 1 | 2 | 4 | 8]) of one axis of resize_u8, on the CPU: the tables
+    nesr_resize_cv_taps returns.  The position is cv2's, (d + 0.5) n_in / n_out - 0.5 in double, cast to float32, floor + fraction.
+      NEAREST  first = min(floor(d n_in / n_out), n_in - 1); one coefficient, 1
+      LINEAR   first = s, f = 0 and s clamped when s < 0 or s >= n_in - 1; rint((1 - f) 2048), rint(f 2048)
+      CUBIC    first = s - 1, not clamped; the Keys weights (A = -0.75, float32) x 2048, rounded
+      LANCZOS4 first = s - 3, not clamped; lanczos4_resize's 11-bit coefficients"""
+    cpu = torch.device("cpu")
+    if interp == INTER_NEAREST:
+        idx = torch.floor(torch.arange(n_out, dtype=torch.float64) * (n_in / n_out)).long().clamp_(max=n_in - 1)
+        return idx, torch.ones((n_out, 1), dtype=torch.int64)
+    _, frac, i0 = _axis_taps(n_in, n_out, cpu, 1, 0)
+    if interp == INTER_LINEAR:
+        lo, hi = i0 < 0, i0 >= n_in - 1
+        f = torch.where(lo | hi, torch.zeros_like(frac), frac)
+        i0 = torch.where(lo, torch.zeros_like(i0), torch.where(hi, torch.full_like(i0, n_in - 1), i0))
+        return i0, torch.stack([_fixed11(1.0 - f), _fixed11(f)], -1)
+    if interp == INTER_CUBIC:
+        return i0 - 1, _fixed11(_cubic_coeffs(frac))
+    if interp == INTER_LANCZOS4:
+        return i0 - 3, _fixed11(_lanczos4_coeffs(frac))
+    raise ValueError(f"resize_u8: interpolation {interp} (INTER_NEAREST 0, INTER_LINEAR 1, INTER_CUBIC 2 or INTER_LANCZOS4 4)")
+
+
+def _resize_u8_chain(img, out_h, out_w, interp):
+    """resize_u8 as torch operations on any device (use_hip=False): integer arithmetic on tables built on the CPU."""
+    h, w, c = img.shape
+    dev = img.device
+    x = img.permute(2, 0, 1).to(torch.int64)                                      # [C, H, W]
+    if interp == INTER_LINEAR and w == 2 * out_w and h == 2 * out_h:                # cv2: INTER_LINEAR becomes INTER_AREA at exactly 1/2 x 1/2
+        out = (x[:, 0::2, 0::2] + x[:, 0::2, 1::2] + x[:, 1::2, 0::2] + x[:, 1::2, 1::2] + 2) >> 2
+        return out.to(torch.uint8).permute(1, 2, 0).contiguous()
+    fx, ax = (t.to(dev) for t in resize_u8_tables(w, out_w, interp))
+    fy, ay = (t.to(dev) for t in resize_u8_tables(h, out_h, interp))
+    if interp == INTER_NEAREST:
+        return img[fy][:, fx].contiguous()
+    taps = ax.shape[1]
+    ix = (fx[:, None] + torch.arange(taps, device=dev)).clamp_(0, w - 1)            # BORDER_REPLICATE
+    iy = (fy[:, None] + torch.arange(taps, device=dev)).clamp_(0, h - 1)
+    rows = (x[:, :, ix] * ax).sum(-1)                                               # [C, H, out_w]
+    if interp == INTER_LINEAR:                                                      # OpenCV's 8-bit VResizeLinear
+        t = rows[:, iy, :] >> 4                                                     # [C, out_h, 2, out_w]
+        out = (((ay[None, :, 0, None] * t[:, :, 0]) >> 16) + ((ay[None, :, 1, None] * t[:, :, 1]) >> 16) + 2) >> 2
+    else:
+        out = ((rows[:, iy, :] * ay[None, :, :, None]).sum(2) + (1 << 21)) >> 22
+    return out.clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+
+
+def resize_u8(img, out_h, out_w, interp, use_hip=None, out=None):
+    """cv2.resize(img, (out_w, out_h), interpolation=interp) for an HWC uint8 tensor and cv2's INTER_NEAREST (0), INTER_LINEAR (1),
+    INTER_CUBIC (2) or INTER_LANCZOS4 (4) -- the reference's no-model step (nesr/nesr.py:597-605: INTER_CUBIC), the object mask's
+    default resize (:732: linear) and the class map's (:720-724: nearest).  OpenCV 4.x's 8-bit arithmetic (resize_u8_tables; the
+    linear form's vertical pass is (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2, and at exactly half size in both
+    axes cv2 takes its area filter, (a + b + c + d + 2) >> 2); PARITY UNPINNED like the rest of this module.
+
+    On a ROCm device one HIP kernel (csrc/resize.hip, nesr_resize_cv_u8: 1, 3 or 4 channels, both passes in one launch) unless
+    use_hip=False selects the torch chain, which is the specification and runs on CPU tensors too -- the two agree bit for bit.
+    Row-strided views and `out` as a view of a canvas work as in lanczos4_resize."""
+    if img.dim() != 3:
+        raise ValueError(f"resize_u8: an [H, W, C] tensor, got {tuple(img.shape)}")
+    if interp not in (INTER_NEAREST, INTER_LINEAR, INTER_CUBIC, INTER_LANCZOS4):
+        raise ValueError(f"resize_u8: interpolation {interp} (INTER_NEAREST 0, INTER_LINEAR 1, INTER_CUBIC 2 or INTER_LANCZOS4 4)")
+    if img.dtype != torch.uint8:
+        raise ValueError(f"resize_u8: a uint8 tensor, got {img.dtype}")
+    h, w, c = img.shape
+    fits = img.device.type == "cuda" and c in (1, 3, 4) and h > 0 and w > 0 and out_h > 0 and out_w > 0
+    if out is not None:
+        if tuple(out.shape) != (out_h, out_w, c) or out.dtype != img.dtype or out.device != img.device:
+            raise ValueError(f"resize_u8: out must be a {img.dtype} [{out_h}, {out_w}, {c}] tensor on {img.device}, got {out.dtype} "
+                             f"{tuple(out.shape)} on {out.device}")
+        fits = fits and _rows_ok(out, (1, 3, 4))
+    if use_hip is None:
+        use_hip = fits
+    if use_hip:
+        if not fits:
+            raise ValueError(f"resize_u8: the HIP kernel takes a uint8 [H, W, 1 | 3 | 4] tensor on the ROCm device (out: rows of contiguous "
+                             f"pixels), got {img.dtype} {tuple(img.shape)} on {img.device}")
+        src = img if _rows_ok(img, (1, 3, 4)) else img.contiguous()
+        dst = out if out is not None else torch.empty((out_h, out_w, c), dtype=torch.uint8, device=img.device)
+        _hip_call(src, "nesr_resize_cv_u8", _ptr(src), h, w, c, _row_bytes(src), _ptr(dst), out_h, out_w, _row_bytes(dst), int(interp))
+        return dst
+    res = _resize_u8_chain(img, out_h, out_w, interp)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res
 
 
 # ----------------------------------------------------------------------------------------------- Gaussian blur
@@ -576,3 +690,120 @@ def postprocess_image(img, adaptive_sharpening=True, use_hip=None):
     sharpened = torch.round(img.float() * 1.5 - blurred.float() * 0.5).clamp_(0, 255).to(torch.uint8)   # addWeighted: saturate_cast<uchar>
     mask = (variance > 10)[..., None]
     return torch.where(mask, sharpened, img)
+
+
+# ----------------------------------------------------------------------------------------------- segmentation mask stage, ensemble
+def dilate3x3_u8(mask, use_hip=None):
+    """cv2.dilate(mask, np.ones((3, 3), np.uint8), iterations=1) on an HW uint8 tensor (nesr/nesr.py:735-736): the max over the
+    neighbours that lie inside the image (cv2's default border value for a dilate never wins a max).  A torch chain only: the
+    library fuses the dilate into segment_enhance's stencil and has no entry for it alone, so use_hip=True is an error."""
+    if use_hip:
+        raise ValueError("dilate3x3_u8: the HIP kernel takes the dilate only fused into segment_enhance (nesr_segment_enhance_u8); "
+                         "there is no entry for it alone")
+    if mask.dim() != 2 or mask.dtype != torch.uint8:
+        raise ValueError(f"dilate3x3_u8: an [H, W] uint8 tensor, got {mask.dtype} {tuple(mask.shape)}")
+    p = F.pad(mask.to(torch.int16), (1, 1, 1, 1), value=-1)
+    h, w = mask.shape
+    out = p[1:h + 1, 1:w + 1]
+    for dy in range(3):
+        for dx in range(3):
+            out = torch.maximum(out, p[dy:dy + h, dx:dx + w])
+    return out.to(torch.uint8)
+
+
+SEGMENT_MAX_SIZE = 1024      # nesr/nesr.py:705: above it the segmenter sees a downscaled frame
+
+
+def segment_enhance(img, seg_map, use_hip=None):
+    """The image half of SuperResolutionPipeline._segment_and_enhance (nesr/nesr.py:726-747) on an HWC uint8 RGB tensor:
+    seg_map is the segmenter's class map (any integer dtype, a tensor or an ndarray, on the host or the device), and
+
+        object_mask = (seg_map > 0).astype(np.uint8)                        :731
+        object_mask = cv2.resize(object_mask, (w, h))                        :732   resize_u8(INTER_LINEAR); {0, 1} again
+        object_mask = cv2.dilate(object_mask, np.ones((3, 3)))               :735   dilate3x3_u8
+        sharpened = addWeighted(img, 1.5, GaussianBlur(img, (0, 0), 3), -0.5)  :739   postprocess_image's value
+        np.where(object_mask[..., None] == 1, sharpened, img)                :743
+
+    For a frame whose longer side exceeds 1024 the reference runs the segmenter on a downscaled frame and resizes the class map back
+    with INTER_NEAREST (:703-724); nearest commutes with `> 0`, so that step is done here on the mask, resize_u8(INTER_NEAREST).  In
+    the reference that branch hands an int64 array to cv2.resize, which throws, and its except clause silently skips the whole
+    stage; that throw is NOT reproduced: the stage runs.  SegFormer itself is the caller's.
+
+    On a ROCm device one C call (nesr_segment_enhance_u8: the mask's linear resize and one fused stencil, csrc/filters.hip) unless
+    use_hip=False selects the torch chain below -- the two agree bit for bit."""
+    if img.dim() != 3 or img.shape[-1] != 3 or img.dtype != torch.uint8:
+        raise ValueError(f"segment_enhance: an [H, W, 3] uint8 tensor, got {img.dtype} {tuple(img.shape)}")
+    seg = torch.as_tensor(seg_map)
+    if seg.dim() != 2 or seg.dtype.is_floating_point or seg.dtype == torch.bool or seg.numel() == 0:
+        raise ValueError(f"segment_enhance: the class map is an [h, w] integer array, got {seg.dtype} {tuple(seg.shape)}")
+    if use_hip is None:
+        use_hip = _hip_default(img)
+    if use_hip:
+        _hip_require(img, True, "segment_enhance", "[H, W, 3]")
+    h, w = img.shape[:2]
+    if img.numel() == 0:
+        return img
+    mask = (seg > 0).to(torch.uint8).to(img.device).contiguous()
+    if max(h, w) > SEGMENT_MAX_SIZE and tuple(mask.shape) != (h, w):
+        mask = resize_u8(mask[:, :, None], h, w, INTER_NEAREST, use_hip=use_hip)[:, :, 0]
+    if use_hip:
+        from . import _lib
+        src = img.contiguous()
+        out = torch.empty_like(src)
+        nbytes = _lib.load().nesr_segment_enhance_scratch_bytes(h, w)
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=src.device)
+        _hip_call(src, "nesr_segment_enhance_u8", _ptr(src), h, w, _ptr(mask), mask.shape[0], mask.shape[1], _ptr(scratch), nbytes, _ptr(out))
+        return out
+    if tuple(mask.shape) != (h, w):
+        mask = resize_u8(mask[:, :, None], h, w, INTER_LINEAR, use_hip=False)[:, :, 0]
+    mask = dilate3x3_u8(mask)
+    blurred = gaussian_blur_u8(img, 3.0, use_hip=False)
+    sharpened = torch.round(img.float() * 1.5 - blurred.float() * 0.5).clamp_(0, 255).to(torch.uint8)
+    return torch.where((mask == 1)[..., None], sharpened, img)
+
+
+def ensemble_results(images, use_hip=None):
+    """SuperResolutionPipeline._ensemble_results (nesr/nesr.py:1033-1054) on a list of HWC uint8 tensors:
+
+        if len(images) == 1: return images[0]                                             :1035   as it is
+        target_h, target_w = max([(img.shape[0], img.shape[1]) for img in images])       :1039   max over TUPLES: lexicographic
+        every other image: cv2.resize(img, (target_w, target_h), INTER_LANCZOS4)          :1044   lanczos4_resize
+        ensemble += img.astype(np.float32) * weights[i];  ensemble.astype(np.uint8)       :1052   float32 mean, truncated
+
+    The target is restated as written: Python's max of (h, w) tuples is the tallest image's size (ties: the widest of those), not
+    the per-axis maximum.  The mean is NumPy 1.x's arithmetic, every step rounded to float32: w = float32(1 / n), acc = 0, acc =
+    fl32(acc + fl32(fl32(x) w)) in order, truncated toward zero, not rounded (n <= 8 copies of one image still give it back: float32(1 / n)
+    is exact or rounded up; tests/test_stages_host.py counts it).
+    NumPy >= 2 would promote the product to float64 (the weight is a float64 scalar); the NumPy 1.x result is the one restated.
+
+    On a ROCm device one elementwise HIP kernel for up to 8 images (csrc/filters.hip, nesr_ensemble_u8) unless use_hip=False
+    selects the torch chain below -- the two agree bit for bit."""
+    images = list(images)
+    if not images:
+        raise ValueError("ensemble_results: no image")
+    if len(images) == 1:
+        return images[0]
+    for im in images:
+        if im.dim() != 3 or im.dtype != torch.uint8 or im.shape[2] != images[0].shape[2] or im.device != images[0].device:
+            raise ValueError("ensemble_results: [H, W, C] uint8 tensors with one channel count on one device")
+    th, tw = max([(int(im.shape[0]), int(im.shape[1])) for im in images])
+    fits = _hip_default(images[0]) and len(images) <= 8 and images[0].numel() > 0
+    if use_hip is None:
+        use_hip = fits
+    if use_hip and not fits:
+        raise ValueError(f"ensemble_results: the HIP kernel takes 2 to 8 uint8 [H, W, C] tensors on the ROCm device, got {len(images)} of "
+                         f"{images[0].dtype} on {images[0].device}")
+    lanczos_hip = use_hip and images[0].shape[2] in (1, 3, 4)
+    aligned = [im if (im.shape[0], im.shape[1]) == (th, tw) else lanczos4_resize(im, th, tw, use_hip=lanczos_hip) for im in images]
+    if use_hip:
+        import ctypes
+        aligned = [im.contiguous() for im in aligned]
+        out = torch.empty_like(aligned[0])
+        ptrs = (ctypes.c_void_p * len(aligned))(*[im.data_ptr() for im in aligned])
+        _hip_call(out, "nesr_ensemble_u8", ptrs, len(aligned), th, tw, int(out.shape[2]), _ptr(out))
+        return out
+    wgt = torch.tensor(1.0 / len(aligned), dtype=torch.float64).to(torch.float32).item()     # float32(1 / n), exactly representable in a Python float
+    acc = torch.zeros(aligned[0].shape, dtype=torch.float32, device=aligned[0].device)
+    for im in aligned:
+        acc = acc + im.to(torch.float32) * wgt
+    return acc.to(torch.uint8)

@@ -8,6 +8,7 @@ Reference (all in nesr/nesr.py):
   _apply_esrgan_12channel       :845-903   [img, clamp(1.1 img), clamp(0.9 img), GaussianBlur3x3(img)] -> model
   _apply_esrgan_3channel        :905-945   img repeated 4x -> model
   _process_with_tiling          :311-475   ceil grid, +-padding windows, crop, Lanczos resize to the canvas
+  enhance_image's loop          :516-633   pre-filter, mask stage, the upscalers, ensemble or bicubic step, post-filter (enhance_iterations)
 
 Differences, on purpose: no exception ladder (nesr.py:815-843, 448-473 turn any backend failure into a
 bicubic result -- here failures raise), no MPS branches, no probe tile (nesr.py:349-357 runs the
@@ -313,35 +314,96 @@ def apply_esrgan(upscaler, image_rgb, config=None, device_kind="cuda", as_numpy=
     return out
 
 
+def realesrganer_stage(up):
+    """A RealESRGANer (around an SRVGGNetCompact, say) as an `extra_upscalers` entry of enhance_iterations: RGB u8 frame -> upscaled RGB
+    u8 frame, kept on the device.  It is `up.enhance(frame[:, :, ::-1])[0][:, :, ::-1]` without the trip home: enhance()'s BGR -> RGB
+    flip and the caller's RGB -> BGR cancel, so the frame goes in as it is; /255, padding, tiles, clamp, x255, round are enhance()'s."""
+    def stage(frame_rgb):
+        up._pad_on_device(normalize_u8_on_device(_u8_on(frame_rgb, up.device).permute(2, 0, 1)).unsqueeze(0))
+        return (up._run().data.squeeze(0).float().clamp_(0, 1).permute(1, 2, 0) * 255.0).round().to(torch.uint8).contiguous()
+    stage.check_range = up._check_range
+    return stage
+
+
 def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", preprocess=None, postprocess=None,
-                       trace=None, large_mp=LARGE_IMAGE_MP, filters=False):
-    """The iteration loop of SuperResolutionPipeline.enhance_image (nesr.py:516-633) around its ESRGAN stage:
+                       trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None):
+    """The iteration loop of SuperResolutionPipeline.enhance_image (nesr.py:516-633):
 
         for iteration in range(config['iterations']):           nesr.py:516
             current = _preprocess_image(current)                 nesr.py:537   -> `preprocess` (NL-means + CLAHE; None = off)
-            esrgan_result = _apply_esrgan(current)               nesr.py:566   -> apply_esrgan above
-            current = _ensemble_results([esrgan_result])         nesr.py:596   one model: the identity (nesr.py:1035-1036)
+            current = _segment_and_enhance(current)              nesr.py:549   -> `segmenter` + imgproc.segment_enhance (None = off)
+            esrgan_result = _apply_esrgan(current)               nesr.py:566   -> apply_esrgan above (`upscaler`; None = use_esrgan off)
+            further results, Nones dropped                       nesr.py:582-584 -> `extra_upscalers`
+            current = _ensemble_results(results)                 nesr.py:596   -> imgproc.ensemble_results (one result: the identity)
+              or, with no result, cv2.resize(INTER_CUBIC)        nesr.py:597-605 -> imgproc.resize_u8
             current = _postprocess_image(current)                nesr.py:616   -> `postprocess` (adaptive unsharp; None = off)
 
-    with diffusion and segmentation off (BASELINE.json configs[4]: `--no_diffusion`; the SegFormer weights are a
-    network fetch).  `filters=True` runs the reference's cv2 pre / post filters too (NL-means + CLAHE, adaptive unsharp:
-    imgproc.py, OpenCV's algorithms restated -- parity unpinned).  Frames stay on the GPU between iterations; the final frame is returned as an HWC uint8 RGB
-    ndarray.  A backend failure raises (the reference would hand back a bicubic resize, nesr.py:835-843); `trace`
+    `segmenter` is a callable, RGB u8 frame -> class map (any integer dtype, host or device; the reference's is SegFormer, whose
+    weights are a network fetch: the caller's); `extra_upscalers` a sequence of callables, frame -> upscaled RGB u8 frame or None
+    (the reference's second model is a remote diffusion pipeline; realesrganer_stage wraps a RealESRGANer around the other network
+    family).  `upscaler=None` with no extra result is the reference's no-model configuration (use_esrgan=False, use_diffusion=False)
+    and takes its bicubic step to (int(w f), int(h f)); it is reached through that explicit configuration only, never from an
+    exception.  `filters=True` runs the reference's cv2 pre / post filters too (NL-means + CLAHE, adaptive unsharp:
+    imgproc.py, OpenCV's algorithms restated -- parity unpinned).  Frames stay on the GPU between iterations (`device`: where, when
+    there is no upscaler to say; default the frame's own device, else the ROCm device if there is one); the final frame is returned
+    as an HWC uint8 RGB ndarray.  A backend failure raises (the reference would hand back a bicubic resize, nesr.py:835-843); `trace`
     receives one dict per iteration with the route and the number of network evaluations, so a caller can assert
-    that the network really ran."""
+    that the network really ran -- and, when a segmenter, an extra upscaler or upscaler=None is in use, "segmented" and
+    "ensemble_n" (the results that were combined; 0: the bicubic step).  With those arguments left out the loop, its result and
+    its trace are what they were without them.  use_hip goes to every stage (None: the HIP kernels where they apply; False: the
+    torch chains, the same bits)."""
     cfg = {"iterations": 3, "upscale_factor": 2.0, "denoise_level": 0.5, "adaptive_sharpening": True}
     cfg.update(config or {})
+    staged = segmenter is not None or len(extra_upscalers) > 0 or upscaler is None
+    if upscaler is not None:
+        device = upscaler.device
+    elif device is None:
+        device = image_rgb.device if isinstance(image_rgb, torch.Tensor) else torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if filters:      # the reference's own pre / post filters (nesr.py:668-689, 1056-1084), on the device: imgproc.py (cv2 restated)
         from . import imgproc
-        preprocess = preprocess or (lambda im: imgproc.preprocess_image(_u8_on(im, upscaler.device), cfg["denoise_level"]))
-        postprocess = postprocess or (lambda im: imgproc.postprocess_image(_u8_on(im, upscaler.device), cfg["adaptive_sharpening"]))
+        fkw = {} if use_hip is None else {"use_hip": use_hip}
+        preprocess = preprocess or (lambda im: imgproc.preprocess_image(_u8_on(im, device), cfg["denoise_level"], **fkw))
+        postprocess = postprocess or (lambda im: imgproc.postprocess_image(_u8_on(im, device), cfg["adaptive_sharpening"], **fkw))
     current = image_rgb
     for iteration in range(int(cfg["iterations"])):
         if preprocess is not None:
             current = preprocess(current)
-        current = apply_esrgan(upscaler, current, cfg, device_kind, as_numpy=False, trace=trace, large_mp=large_mp)
+        if staged:
+            from . import imgproc
+            current = _u8_on(current, device)
+        if segmenter is not None:                                # nesr.py:540-549
+            current = imgproc.segment_enhance(current, segmenter(current), use_hip=use_hip)
+        source = current
+        results = []
+        if upscaler is not None:
+            current = apply_esrgan(upscaler, current, cfg, device_kind, as_numpy=False, trace=trace, large_mp=large_mp,
+                                   **({} if use_hip is None else {"use_hip": use_hip}))
+            results.append(current)
+        elif trace is not None:                                  # no network ran: nothing of apply_esrgan's route to report
+            trace.append({"in_shape": tuple(source.shape[:2]), "model_calls": 0, "net_input_px": 0})
         if trace is not None:
             trace[-1]["iteration"] = iteration
+        if staged:
+            for extra in extra_upscalers:                        # nesr.py:582-584: a model that gave nothing is dropped
+                r = extra(source)
+                if r is not None:
+                    results.append(_u8_on(r, device))
+            if results:
+                current = imgproc.ensemble_results(results, use_hip=use_hip)                    # nesr.py:595-596
+            else:                                                # nesr.py:597-605: the configured no-model step
+                h, w = source.shape[:2]
+                f = cfg["upscale_factor"]
+                current = imgproc.resize_u8(source, int(h * f), int(w * f), imgproc.INTER_CUBIC, use_hip=use_hip)
+            if trace is not None:
+                trace[-1].update({"segmented": segmenter is not None, "ensemble_n": len(results), "out_shape": tuple(current.shape[:2])})
         if postprocess is not None:
             current = postprocess(current)
-    return _to_host(upscaler, current) if isinstance(current, torch.Tensor) else current
+    for extra in extra_upscalers:
+        check = getattr(extra, "check_range", None)
+        if check is not None:
+            check()
+    if not isinstance(current, torch.Tensor):
+        return current
+    if upscaler is None:
+        return current.cpu().numpy()
+    return _to_host(upscaler, current)
