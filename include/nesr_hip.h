@@ -690,6 +690,17 @@ int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin,
                     const float* w_host, const float* b_host, int Cout, int lrelu, int upsample,
                     void* y_dev, void* stream, int upconv_mode);
 
+/* Debug: the kernel family that the last nesr_conv3x3 / nesr_conv3x3_up call on the calling thread launched -- the decision its
+ * launcher took, noted at the point of dispatch, not a second evaluation of the condition.  0 before any call on this thread and
+ * after a call that failed before its launch.  A per-layer test asserts with it that it ran the kernel it is named after. */
+enum { NESR_CONV_KERNEL_NONE = 0,
+       NESR_CONV_KERNEL_GENERIC = 1,     /* conv3x3_mfma_kernel: f32 direct, and bf16 / f16 frames up to the size switch */
+       NESR_CONV_KERNEL_XL = 2,          /* conv3x3_bf16_xl_kernel: the large-tile LDS-DMA kernel of bf16 / f16 */
+       NESR_CONV_KERNEL_WINOGRAD = 3,    /* f32 Winograd F(2x2,3x3) */
+       NESR_CONV_KERNEL_F16_PAIR = 4,    /* f32 as f16 pairs */
+       NESR_CONV_KERNEL_UPCONV2X2 = 5 }; /* the folded 2x2-tap form of an upsampled f16-pair layer */
+int nesr_debug_last_conv_kernel(void);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

@@ -10,7 +10,7 @@ or, with ``<repo>/dropin`` on PYTHONPATH, the reference's own import lines
 resolve to these classes unchanged.  The network forward runs in hand-written HIP kernels
 (libnesr_hip.so, C ABI in include/nesr_hip.h); there is no CPU fallback.
 """
-from .rrdbnet import RRDBNet, conv3x3, rrdbnet_state_dict_spec  # noqa: F401
+from .rrdbnet import RRDBNet, conv3x3, last_conv_kernel, rrdbnet_state_dict_spec  # noqa: F401
 from .srvgg import SRVGGNetCompact, srvgg_state_dict_spec  # noqa: F401
 from .realesrganer import RealESRGANer  # noqa: F401
 

@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_WINOGRAD, DTYPE_F32_SPLIT, DTYPE_F16 = 0, 1, 2, 3, 4
 ROUND_TRUNC, ROUND_NEAREST = 0, 1
 UPCONV_3X3, UPCONV_2X2 = 0, 1
+CONV_KERNEL_NAMES = {0: None, 1: "generic", 2: "xl", 3: "winograd", 4: "f16-pair", 5: "upconv2x2"}   # NESR_CONV_KERNEL_*
 CONV_LAST_GENERAL, CONV_LAST_NARROW = 0, 1
 ACT_PRELU, ACT_RELU, ACT_LEAKYRELU = 0, 1, 2
 LAB_FROM_LAB, LAB_LINEAR, LAB_FIRST_IS_BLUE, LAB_PLANAR = 1, 2, 4, 8
@@ -123,6 +124,7 @@ SIGNATURES = {
                                 _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_conv3x3_up": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                    _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),
 }

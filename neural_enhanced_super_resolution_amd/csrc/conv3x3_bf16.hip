@@ -7,17 +7,22 @@
 //               LDS-DMA wave-instruction (64 lanes x 16 B) copies 32 pixels = 8 whole 128-byte
 //               lines.  (With NHWC every lane touched its own line and the kernels were bound by the
 //               L1's access rate at ~20 % of the MFMA peak: profiles/r01/bf16_tcp_bound.txt.)
-//   workgroup : 512 threads = 8 waves, output tile 32 x 32 pixels x all Cout (32|64), 1 per CU
+//   workgroup : the default is 256 threads = 4 waves, output tile 16 rows x 32 cols x all Cout (32|64), two
+//               independent workgroups per CU (each one's DMA prologue and store epilogue overlap the other's
+//               MFMAs).  NESR_XL_GEOMETRY=8 opts into 512 threads = 8 waves, 32 x 32-pixel tiles, one workgroup
+//               per CU (least staged bytes per FLOP); launch_xl_kind picks, Geo<WAVES> holds the sizes.
 //   wave      : 4 output rows x 32 cols x NT 32-wide channel tiles -> 4*NT f32x16 accumulators
-//   K loop    : 16-channel chunks; the (32+2)x(32+2) halo tile and the 9x16xCout weight slab are
+//   K loop    : 16-channel chunks; the (TH+2)x(32+2) halo tile and the 9x16xCout weight slab are
 //               copied global -> LDS by LDS-DMA (global_load_lds_dwordx4 from inline asm: per-lane
-//               source, lane-linear destination, no staging registers).  3-slot input ring (two
-//               chunks ahead: HBM / Infinity-Cache latency) + 2-slot weight ring (one chunk ahead:
-//               L2 latency), a COUNTED s_waitcnt vmcnt and a raw s_barrier: one barrier per chunk,
-//               the DMA never drains inside the loop.  Out-of-image pixels read a zero page.
-//                 iteration c:  s_waitcnt vmcnt(nin)  -> this wave's w(c), in(c) have landed
+//               source, lane-linear destination, no staging registers).  Input ring of ISLOTS slots, chosen per
+//               Cout so that two workgroups fit a CU's LDS: 3 slots for Cout 32 (two chunks ahead: HBM /
+//               Infinity-Cache latency), 2 slots for Cout 64 (one chunk ahead, every wait a full drain); the
+//               8-wave geometry has 3 for both.  2-slot weight ring (one chunk ahead: L2 latency), a COUNTED
+//               s_waitcnt vmcnt and a raw s_barrier: one barrier per chunk; with 3 slots the DMA never drains
+//               inside the loop.  Out-of-image pixels read a zero page.
+//                 iteration c:  s_waitcnt vmcnt(nin)  -> this wave's w(c), in(c) have landed (3 slots; vmcnt(0) with 2)
 //                               s_barrier             -> everyone's have; all finished compute(c-1)
-//                               issue w(c+1), in(c+2) into the slots last read in iteration c-1
+//                               issue w(c+1), in(c+ISLOTS-1) into the slots last read in iteration c-1
 //                               compute(c)
 //   LDS image : input slot = [padded pixel][32 B]; the two 16-byte halves of a pixel are swapped
 //               when bit 3 of its padded column is set (applied on the DMA source address and on the

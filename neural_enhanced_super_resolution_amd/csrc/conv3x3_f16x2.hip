@@ -1275,6 +1275,7 @@ hipError_t launch_conv3x3_f16x2(const ConvArgs& a, hipStream_t s) {
     // workgroups (166 registers) keep a second kernel's workgroups off the CU (2 frames in flight: 158 -> 166 MP/s
     // without them; one frame alone: 134 -> 138 MP/s with them)
     const bool producer = dmaw >= 0 ? dmaw > 0 : (t1 <= cus && !a.shared_device);
+    note_conv_kernel(CONV_KERNEL_F16_PAIR);
     // conv_last (image outputs of <= 4 channels, no feature map): one 16-cout column block instead of two, by the caller's
     // setting alone (ConvArgs::narrow_last), never by the shape
     if (a.narrow_last && (a.out_nchw || a.out_u8) && !a.out && !a.out2 && !a.res1 && !a.res2)

@@ -32,6 +32,7 @@
 #include <hip/hip_bf16.h>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "elem16.h"
 #include "nesr_kernels.h"
@@ -545,43 +546,57 @@ void pack_weights_f16(const float* oihw, int cout, int cin, int cin_p, int coutp
 
 hipError_t launch_conv3x3_f32(const ConvArgs& a, hipStream_t s) {
     if (a.y_lo || a.y_hi) return hipErrorInvalidValue;   // row ranges: conv3x3_f16x2_kernel only
+    note_conv_kernel(CONV_KERNEL_GENERIC);
     return launch<0>(a, s);
 }
 hipError_t launch_trunk_persist(const TrunkArgs& t, bool bf16, hipStream_t s) {
     return bf16 ? launch_trunk<1>(t, s) : launch_trunk<0>(t, s);
 }
-// bf16: frames of more than 256x256 trunk pixels take the large-tile LDS-DMA kernel (a single
-// 256x256 frame is only 64 of its tiles, too few for 256 CUs); the choice
-// depends on the frame size only (never on the batch), so a tile's arithmetic is the same on every
-// rank and in every batch.  NESR_BF16_KERNEL=small|big|xl overrides (tests, A/B timing).
-hipError_t launch_conv3x3_bf16(const ConvArgs& a, hipStream_t s) {
-    if (a.y_lo || a.y_hi) return hipErrorInvalidValue;   // row ranges: conv3x3_f16x2_kernel only
+
+namespace {
+
+// NESR_BF16_KERNEL=small|xl, read once per process (tests, A/B timing): the generic kernel or the large-tile kernel for every
+// frame size.  Anything else is refused with its text where a context is created and in the single-layer hooks
+// (bad_kernel16_override), and a launcher that meets it all the same returns hipErrorInvalidValue.  Ragged and
+// size-independent launches take the large-tile kernel whatever it says.
+enum { PICK_BY_SIZE = 0, PICK_SMALL = 1, PICK_XL = 2, PICK_BAD = -1 };
+int kernel16_override() {
     static const int mode = [] {
         const char* e = getenv("NESR_BF16_KERNEL");
-        if (!e) return 0;
-        return e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : (e[0] == 'x' ? 3 : 0));
+        if (!e || !e[0]) return (int)PICK_BY_SIZE;
+        if (!strcmp(e, "small")) return (int)PICK_SMALL;
+        if (!strcmp(e, "xl")) return (int)PICK_XL;
+        return (int)PICK_BAD;
     }();
+    return mode;
+}
+
+// bf16 / f16: frames of more than 256x256 trunk pixels take the large-tile LDS-DMA kernel (a single
+// 256x256 frame is only 128 of its 16x32-pixel tiles, too few for 256 CUs); the choice
+// depends on the frame size only (never on the batch), so a tile's arithmetic is the same on every
+// rank and in every batch.
+template <int K>
+hipError_t launch16(const ConvArgs& a, hipStream_t s) {
+    if (a.y_lo || a.y_hi) return hipErrorInvalidValue;   // row ranges: conv3x3_f16x2_kernel only
+    const int mode = kernel16_override();
+    if (mode == PICK_BAD) return hipErrorInvalidValue;
     const bool large = (long)a.h * a.w_ > 256L * 256L;
     if (a.zeros) {
-        if (mode == 3 || (mode == 0 && large) || a.rag_n || a.size_independent) return launch_conv3x3_bf16_xl(a, s);
+        if (mode == PICK_XL || (mode == PICK_BY_SIZE && large) || a.rag_n || a.size_independent) {
+            note_conv_kernel(CONV_KERNEL_XL);
+            return K == 1 ? launch_conv3x3_bf16_xl(a, s) : launch_conv3x3_f16_xl(a, s);
+        }
     }
     if (a.rag_n) return hipErrorInvalidValue;   // only the large-tile kernel knows about ragged batches
-    return launch<1>(a, s);
+    note_conv_kernel(CONV_KERNEL_GENERIC);
+    return launch<K>(a, s);
 }
+
+}  // namespace
+
+const char* bad_kernel16_override() { return kernel16_override() == PICK_BAD ? getenv("NESR_BF16_KERNEL") : nullptr; }
+hipError_t launch_conv3x3_bf16(const ConvArgs& a, hipStream_t s) { return launch16<1>(a, s); }
 // f16: the same kernels and the same choice as bf16 (NESR_BF16_KERNEL applies too)
-hipError_t launch_conv3x3_f16(const ConvArgs& a, hipStream_t s) {
-    if (a.y_lo || a.y_hi) return hipErrorInvalidValue;
-    static const int mode = [] {
-        const char* e = getenv("NESR_BF16_KERNEL");
-        if (!e) return 0;
-        return e[0] == 's' ? 1 : (e[0] == 'b' ? 2 : (e[0] == 'x' ? 3 : 0));
-    }();
-    const bool large = (long)a.h * a.w_ > 256L * 256L;
-    if (a.zeros) {
-        if (mode == 3 || (mode == 0 && large) || a.rag_n || a.size_independent) return launch_conv3x3_f16_xl(a, s);
-    }
-    if (a.rag_n) return hipErrorInvalidValue;
-    return launch<3>(a, s);
-}
+hipError_t launch_conv3x3_f16(const ConvArgs& a, hipStream_t s) { return launch16<3>(a, s); }
 
 }  // namespace nesr

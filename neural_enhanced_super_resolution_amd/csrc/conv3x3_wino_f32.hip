@@ -428,6 +428,7 @@ hipError_t launch_conv3x3_wino_f32(const ConvArgs& a, hipStream_t s) {
     // (no redundant input transform between cout-group waves, but one wave per SIMD on a 256x256 frame):
     // measured 29 % slower in-process, kept for A/B
     static const bool wide = [] { const char* e = getenv("NESR_WINO_NT1"); return e && e[0] == 'w'; }();
+    if (a.coutp == 64 || a.coutp == 32) note_conv_kernel(CONV_KERNEL_WINOGRAD);
     if (a.coutp == 64) return launch_wino<2, 2, 2>(a, s);   // 2 x 38.5 KB -> two workgroups per CU
     if (a.coutp == 32) {
         if (wide && !(a.out_nchw || a.out_u8)) return launch_wino<2, 3, 1>(a, s);

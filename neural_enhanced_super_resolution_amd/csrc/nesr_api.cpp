@@ -82,6 +82,7 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
         if (std::strcmp(e, "3x3") != 0 && std::strcmp(e, "2x2") != 0) return set_error(NESR_ERR_ARG, std::string("NESR_UPCONV must be 3x3 or 2x2, not '") + e + "'");
         c->upconv_2x2 = std::strcmp(e, "2x2") == 0;
     }
+    if (const char* bad = bad_kernel16_override()) return set_error(NESR_ERR_ARG, std::string("NESR_BF16_KERNEL must be small or xl, not '") + bad + "'");
     if (const char* e = getenv("NESR_CONV_LAST")) {
         if (std::strcmp(e, "general") != 0 && std::strcmp(e, "narrow") != 0) return set_error(NESR_ERR_ARG, std::string("NESR_CONV_LAST must be general or narrow, not '") + e + "'");
         c->last_narrow = std::strcmp(e, "narrow") == 0;

@@ -103,6 +103,12 @@ struct ConvArgs {
     unsigned short rag_h[RAG_MAX], rag_w[RAG_MAX];
 };
 
+// Which kernel family a conv launcher chose (NESR_CONV_KERNEL_* of include/nesr_hip.h): every launcher below notes it at the
+// point of dispatch, per host thread; nesr_debug_last_conv_kernel reports what the single-layer hooks' launch noted
+// (oneshot_api.cpp).  A thread-local store: nothing on the device, nothing a forward waits for.
+enum { CONV_KERNEL_NONE = 0, CONV_KERNEL_GENERIC = 1, CONV_KERNEL_XL = 2, CONV_KERNEL_WINOGRAD = 3, CONV_KERNEL_F16_PAIR = 4, CONV_KERNEL_UPCONV2X2 = 5 };
+void note_conv_kernel(int family);
+
 // f32 path: v_mfma_f32_32x32x2_f32 implicit GEMM (conv3x3_mfma.hip)
 hipError_t launch_conv3x3_f32(const ConvArgs& a, hipStream_t s);
 // host-side weight repack for the f32 kernel: OIHW f32 -> [cin/8][tap][half][coutp][4]
@@ -117,7 +123,8 @@ void pack_weights_wino_f32(const float* oihw, int cout, int cin, int cin_p, int 
 
 // bf16 path: v_mfma_f32_32x32x16_bf16 implicit GEMM (conv3x3_bf16.hip)
 hipError_t launch_conv3x3_bf16(const ConvArgs& a, hipStream_t s);       // picks the variant by frame size
-hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s);    // conv3x3_bf16.hip: 32x32-px tiles, 3-deep LDS-DMA ring
+const char* bad_kernel16_override();   // the value of NESR_BF16_KERNEL if it is neither small nor xl (callers refuse it by name), else null
+hipError_t launch_conv3x3_bf16_xl(const ConvArgs& a, hipStream_t s);    // conv3x3_bf16.hip: 16x32-px tiles (NESR_XL_GEOMETRY=8: 32x32), LDS-DMA ring
 size_t packed_weight_elems_bf16(int cin_p, int coutp);
 void pack_weights_bf16(const float* oihw, int cout, int cin, int cin_p, int coutp, uint16_t* dst);
 // f16 path: the same kernels instantiated on f16 (v_mfma_f32_32x32x16_f16), the same layouts; every stored activation is

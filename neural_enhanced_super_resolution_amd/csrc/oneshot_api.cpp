@@ -9,6 +9,13 @@
 
 using namespace nesr;
 
+namespace {
+thread_local int t_noted_kernel = CONV_KERNEL_NONE;   // what the launcher running on this thread chose last
+thread_local int t_hook_kernel = CONV_KERNEL_NONE;    // ... as of the last single-layer hook call on this thread
+}  // namespace
+
+void nesr::note_conv_kernel(int family) { t_noted_kernel = family; }
+
 extern "C" {
 
 int nesr_cut_tiles_u8(int device_id, const uint8_t* frame_hwc_dev, int H, int W, int flip_rgb, int through_fp16, const int* windows, int n, int Hs, int Ws,
@@ -87,12 +94,17 @@ int nesr_conv3x3(int device_id, int dtype, const void* x_dev, int N, int Cin, in
         const char* e = getenv("NESR_UPCONV");
         return !e ? NESR_UPCONV_2X2 : (std::strcmp(e, "3x3") == 0 ? NESR_UPCONV_3X3 : (std::strcmp(e, "2x2") == 0 ? NESR_UPCONV_2X2 : -1));
     }();
-    if (mode < 0) return set_error(NESR_ERR_ARG, "NESR_UPCONV must be 3x3 or 2x2");
+    if (mode < 0) {
+        t_hook_kernel = CONV_KERNEL_NONE;
+        return set_error(NESR_ERR_ARG, "NESR_UPCONV must be 3x3 or 2x2");
+    }
     return nesr_conv3x3_up(device_id, dtype, x_dev, N, Cin, H, W, w_host, b_host, Cout, lrelu, upsample, y_dev, stream, mode);
 }
 
 int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin, int H, int W, const float* w_host,
                     const float* b_host, int Cout, int lrelu, int upsample, void* y_dev, void* stream, int upconv_mode) {
+    t_hook_kernel = t_noted_kernel = CONV_KERNEL_NONE;   // a call that fails before its launch reports no kernel
+    if (const char* bad = bad_kernel16_override()) return set_error(NESR_ERR_ARG, std::string("NESR_BF16_KERNEL must be small or xl, not '") + bad + "'");
     if (!x_dev || !w_host || !b_host || !y_dev) return set_error(NESR_ERR_ARG, "null argument");
     if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout > 64) return set_error(NESR_ERR_ARG, "bad shape (Cout <= 64)");
     const Form* form = form_of(dtype);   // F32_WINOGRAD: the Winograd slab and kernel alone
@@ -161,6 +173,7 @@ int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin,
     a.zeros = d_zero;
     a.status = form->ranged ? d_status : nullptr;
     NESR_TRY(up2x2 ? launch_upconv2x2_f16x2(a, s) : form->launch(a, s));
+    t_hook_kernel = t_noted_kernel;
     NESR_TRY(launch_nhwc_to_nchw(d_out, kind, mo, N, Cout, ho, wo, static_cast<float*>(y_dev), s));
     NESR_TRY(hipStreamSynchronize(s));
     if (hf) {
@@ -177,5 +190,7 @@ int nesr_conv3x3_up(int device_id, int dtype, const void* x_dev, int N, int Cin,
     }
     return NESR_OK;
 }
+
+int nesr_debug_last_conv_kernel(void) { return t_hook_kernel; }
 
 }  // extern "C"

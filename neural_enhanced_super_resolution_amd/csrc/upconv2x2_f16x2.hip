@@ -334,6 +334,7 @@ hipError_t launch_upconv2x2_f16x2(const ConvArgs& a, hipStream_t s) {
     const long total = (long)((a.in_w + UTW - 1) / UTW) * ((a.in_h + ULH - 1) / ULH) * a.n * (a.coutp / 32);
     if (total <= 0) return hipSuccess;
     if (total > 0x7fffffffL) return hipErrorInvalidValue;
+    note_conv_kernel(CONV_KERNEL_UPCONV2X2);
     hipLaunchKernelGGL(upconv2x2_f16x2_kernel, dim3((unsigned)total), dim3(UTHREADS), USHM, s, a);
     return hipGetLastError();
 }

@@ -594,3 +594,9 @@ def conv3x3(x, weight, bias, lrelu=False, upsample=False, dtype="f32", upconv=No
     else:   # (the stream is not this entry's last parameter: it is given here)
         device_call("nesr_conv3x3_up", x.device, *args, current_stream_ptr(x.device), {"3x3": _lib.UPCONV_3X3, "2x2": _lib.UPCONV_2X2}[upconv])
     return y
+
+
+def last_conv_kernel():
+    """The kernel family that the last conv3x3() call on this thread launched, as its launcher noted it at the point of
+    dispatch (nesr_debug_last_conv_kernel): "generic" | "xl" | "winograd" | "f16-pair" | "upconv2x2", None before any call."""
+    return _lib.CONV_KERNEL_NAMES[_lib.load().nesr_debug_last_conv_kernel()]

@@ -23,12 +23,13 @@ def _case(cin, cout, h, w, seed, n=1):
 @pytest.mark.parametrize("cin,cout", SHAPES)
 @pytest.mark.parametrize("lrelu", [False, True])
 def test_conv3x3_f32_matches_torch(cuda_device, cin, cout, lrelu):
-    from neural_enhanced_super_resolution_amd import conv3x3
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     x, w, b = _case(cin, cout, 24, 40, seed=cin * 100 + cout)
     ref = F.conv2d(x, w, b, padding=1)
     if lrelu:
         ref = F.leaky_relu(ref, 0.2)
     got = conv3x3(x.to(cuda_device), w, b, lrelu=lrelu).cpu()
+    assert last_conv_kernel() == "f16-pair"      # "f32" is what RRDBNet(compute_dtype="f32") runs
     assert got.shape == ref.shape
     assert (got - ref).abs().max().item() < F32_TOL * max(1.0, ref.abs().max().item())
 
@@ -79,23 +80,42 @@ def test_conv3x3_bf16_matches_bf16_rounded_reference(cuda_device, cin, cout):
     assert (got - ref).abs().max().item() < 2 ** -7 * scale   # output stored as bf16 (8 bits of mantissa)
 
 
-BIG = (136, 160)   # >= 128*128 trunk pixels: the bf16 path takes the large-tile LDS-DMA kernel
+@pytest.mark.parametrize("lrelu", [False, True])
+@pytest.mark.parametrize("cin,cout", SHAPES)
+def test_conv3x3_bf16_generic_kernel_rounding_pin(cuda_device, cin, cout, lrelu):
+    """The bf16 twin of test_gpu_f16.py's test_one_layer_rounding_pin for the generic kernel (tests/conv_pin.py): every value
+    within one bf16 ulp of the float64 result rounded once, nearly all of them its bits.  2 x 19 x 37: partial tiles both ways."""
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
+    from tests import conv_pin
+    x, w, b = conv_pin.make_case(cin, cout, 19, 37, "bf16", seed=cin * 7 + cout)
+    y = conv3x3(x.to(cuda_device), w, b, lrelu=lrelu, dtype="bf16").cpu()
+    assert last_conv_kernel() == "generic"
+    pre, mag = conv_pin.conv_f64(x, w, b)
+    fig = conv_pin.pin(y, pre, mag, cin, lrelu, "bf16")
+    print(f"kernel generic: bf16 cin {cin} cout {cout} lrelu {lrelu}: outside {fig['outside']}, worst {fig['worst_ulps']:.2f} ulp, not bitwise {fig['miss']:.2e}")
+    conv_pin.assert_pin(fig, "bf16", f"bf16 {cin}->{cout}")
+
+
+# A mid-size frame: below the size switch of launch_conv3x3_bf16, so the bf16 path runs the generic conv3x3_mfma_kernel on many
+# workgroups (the large-tile LDS-DMA kernel has its own per-layer tests, test_gpu_conv_xl.py).  Each test asserts which one ran.
+MID = (136, 160)
 
 
 @pytest.mark.parametrize("cin,cout", [(16, 64), (64, 32), (96, 32), (160, 32), (192, 64), (64, 64), (64, 3)])
-def test_conv3x3_bf16_xl_kernel(cuda_device, cin, cout):
-    from neural_enhanced_super_resolution_amd import conv3x3
-    x, w, b = _case(cin, cout, BIG[0], BIG[1], seed=3 * cin + cout, n=2)
+def test_conv3x3_bf16_generic_kernel_mid_size_frame(cuda_device, cin, cout):
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
+    x, w, b = _case(cin, cout, MID[0], MID[1], seed=3 * cin + cout, n=2)
     ref = F.leaky_relu(F.conv2d(x.bfloat16().float(), w.bfloat16().float(), b, padding=1), 0.2)
     got = conv3x3(x.to(cuda_device), w, b, lrelu=True, dtype="bf16").cpu()
+    assert last_conv_kernel() == "generic"
     scale = max(1.0, ref.abs().max().item())
     assert (got - ref).abs().max().item() < 2 ** -7 * scale
 
 
-def test_conv3x3_bf16_xl_one_hot_taps(cuda_device):
-    """Exact one-hot check of the large-tile kernel's tap / row-reuse / channel bookkeeping
+def test_conv3x3_bf16_generic_kernel_one_hot_taps_mid_size_frame(cuda_device):
+    """Exact one-hot check of the generic kernel's tap / channel bookkeeping over many tiles
     (small integers are exact in bf16)."""
-    from neural_enhanced_super_resolution_amd import conv3x3
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     cin, cout = 32, 64
     h, w = 130, 131
     x = ((torch.arange(cin * h * w, dtype=torch.float32).reshape(1, cin, h, w) * 7) % 61).contiguous()
@@ -106,14 +126,16 @@ def test_conv3x3_bf16_xl_one_hot_taps(cuda_device):
         b = torch.arange(cout, dtype=torch.float32)
         ref = F.conv2d(x, wt, b, padding=1)
         got = conv3x3(x.to(cuda_device), wt, b, dtype="bf16").cpu()
+        assert last_conv_kernel() == "generic"
         assert torch.equal(got, ref), f"tap {tap}"
 
 
-def test_conv3x3_bf16_xl_upsample(cuda_device):
-    from neural_enhanced_super_resolution_amd import conv3x3
+def test_conv3x3_bf16_generic_kernel_upsample_mid_size_frame(cuda_device):
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     x, wgt, b = _case(64, 64, 70, 90, seed=8)
     ref = F.conv2d(F.interpolate(x.bfloat16().float(), scale_factor=2, mode="nearest"), wgt.bfloat16().float(), b, padding=1)
     got = conv3x3(x.to(cuda_device), wgt, b, upsample=True, dtype="bf16").cpu()
+    assert last_conv_kernel() == "generic"
     assert (got - ref).abs().max().item() < 2 ** -7 * max(1.0, ref.abs().max().item())
 
 
@@ -123,10 +145,11 @@ WINO_TOL = 2e-5   # relative to max|ref|: Winograd's transforms add a few ulps t
 @pytest.mark.parametrize("cin,cout", [(16, 64), (64, 32), (96, 32), (128, 32), (160, 32), (192, 64), (64, 64)])
 @pytest.mark.parametrize("hw", [(24, 40), (9, 17), (33, 47), (1, 1), (2, 3), (7, 5)])
 def test_conv3x3_f32_winograd_matches_torch(cuda_device, cin, cout, hw):
-    from neural_enhanced_super_resolution_amd import conv3x3
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     x, w, b = _case(cin, cout, hw[0], hw[1], seed=cin * 7 + cout + hw[0], n=2)
     ref = F.leaky_relu(F.conv2d(x, w, b, padding=1), 0.2)
     got = conv3x3(x.to(cuda_device), w, b, lrelu=True, dtype="f32-winograd").cpu()
+    assert last_conv_kernel() == "winograd"
     assert got.shape == ref.shape
     assert (got - ref).abs().max().item() < WINO_TOL * max(1.0, ref.abs().max().item())
 
@@ -178,10 +201,11 @@ SPLIT_TOL = 2e-5   # relative to max|ref|: operands carry 22-23 bits, products l
 @pytest.mark.parametrize("cin,cout", SHAPES)
 @pytest.mark.parametrize("hw", [(24, 40), (1, 1), (7, 5), (9, 17), (33, 47), (16, 130)])
 def test_conv3x3_f32_split_matches_torch(cuda_device, cin, cout, hw):
-    from neural_enhanced_super_resolution_amd import conv3x3
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     x, w, b = _case(cin, cout, hw[0], hw[1], seed=cin * 11 + cout + hw[1], n=2)
     ref = F.leaky_relu(F.conv2d(x, w, b, padding=1), 0.2)
     got = conv3x3(x.to(cuda_device), w, b, lrelu=True, dtype="f32-split").cpu()
+    assert last_conv_kernel() == "f16-pair"
     assert got.shape == ref.shape
     assert (got - ref).abs().max().item() < SPLIT_TOL * max(1.0, ref.abs().max().item())
 

@@ -57,12 +57,14 @@ def test_upconv_2x2_batches_and_channel_counts(cuda_device, cin, cout, n, h, w, 
 def test_upconv_default_is_2x2_and_3x3_stays_reachable(cuda_device):
     """The 3x3 form is still there and differs from the 2x2 form only in rounding; the default entry takes the 2x2 form."""
     import os
-    from neural_enhanced_super_resolution_amd import conv3x3
+    from neural_enhanced_super_resolution_amd import conv3x3, last_conv_kernel
     x, wgt, b = _case(64, 64, 13, 21, seed=5)
     ref = _ref(x, wgt, b, True)
     xd = x.to(cuda_device)
     y3 = conv3x3(xd, wgt, b, lrelu=True, upsample=True, dtype="f32-split", upconv="3x3").cpu()
+    assert last_conv_kernel() == "f16-pair"
     y2 = conv3x3(xd, wgt, b, lrelu=True, upsample=True, dtype="f32-split", upconv="2x2").cpu()
+    assert last_conv_kernel() == "upconv2x2"
     yd = conv3x3(xd, wgt, b, lrelu=True, upsample=True, dtype="f32-split").cpu()
     tol = SPLIT_TOL * max(1.0, ref.abs().max().item())
     assert (y3 - ref).abs().max().item() < tol and (y2 - ref).abs().max().item() < tol
@@ -71,6 +73,7 @@ def test_upconv_default_is_2x2_and_3x3_stays_reachable(cuda_device):
     for dt in ("bf16", "f32-direct"):
         a = conv3x3(xd, wgt, b, upsample=True, dtype=dt, upconv="2x2").cpu()
         c = conv3x3(xd, wgt, b, upsample=True, dtype=dt, upconv="3x3").cpu()
+        assert last_conv_kernel() == "generic"
         assert torch.equal(a, c)
 
 
