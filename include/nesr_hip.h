@@ -701,6 +701,74 @@ enum { NESR_CONV_KERNEL_NONE = 0,
        NESR_CONV_KERNEL_UPCONV2X2 = 5 }; /* the folded 2x2-tap form of an upsampled f16-pair layer */
 int nesr_debug_last_conv_kernel(void);
 
+/*
+ * ---- SegFormer, the pipeline's segmenter (csrc/segformer.hip, segformer_pre.hip, segformer_api.cpp) -- segformer.SegFormer.
+ * `nvidia/segformer-b0-finetuned-ade-512-512`, which the reference's default configuration (segment_enhancement True,
+ * nesr/nesr.py:40) loads at nesr/nesr.py:285-301 and runs on every iteration of enhance_image (:691-724).  f32 throughout, every
+ * product on the f32-input MFMA; at most 80 kernel launches a frame at B0 (49 for a frame up to 1024 pixels, 51 above).
+ *
+ * nesr_segformer_create stands in for AutoModelForImageSegmentation.from_pretrained's construction (nesr/nesr.py:294-296): the
+ * arrays hold num_encoder_blocks (1..4) entries each, named as SegformerConfig's fields.  Required: hidden_sizes[i] =
+ * 32 num_attention_heads[i] (a head dimension of 32: B0; B1-B5 have 64), hidden sizes and decoder_hidden_size multiples of 32 up to
+ * 256, 1 <= num_labels <= 256, num_channels 3.  The configuration is checked first: a bad one is NESR_ERR_ARG before any device is
+ * touched.  LayerNorm eps 1e-5 (transformers builds every LayerNorm with torch's default, not config.layer_norm_eps), gelu (erf),
+ * BatchNorm eps 1e-5 with its running statistics (eval mode).
+ * nesr_segformer_load_weight stands in for its load_state_dict: a key is a transformers-5 name
+ * (segformer.stages.{i}.blocks.{j}.attention.q_proj.weight ...) or the published checkpoint's transformers-4 name
+ * (segformer.encoder.block.{i}.{j}.attention.self.query.weight ...), renamed here by the table of transformers'
+ * conversion_mapping.py, so a C host loads the checkpoint as it is; data is host f32 in torch's layout, an unexpected key or a
+ * wrong shape is NESR_ERR_ARG.
+ * decode_head.batch_norm.num_batches_tracked is accepted and ignored.  nesr_segformer_num_tensors: the tensors finalize waits for
+ * (207 at B0 with 150 labels).  nesr_segformer_finalize: a missing key is NESR_ERR_STATE; folds the BatchNorm into a scale and a
+ * shift, transposes and uploads the weights.
+ */
+typedef struct nesr_segformer nesr_segformer;
+int nesr_segformer_create(nesr_segformer** out, int device_id, int num_channels, int num_encoder_blocks, const int* depths,
+                          const int* sr_ratios, const int* hidden_sizes, const int* patch_sizes, const int* strides,
+                          const int* num_attention_heads, const int* mlp_ratios, int decoder_hidden_size, int num_labels);
+void nesr_segformer_destroy(nesr_segformer* ctx);
+int nesr_segformer_num_tensors(const nesr_segformer* ctx);
+int nesr_segformer_load_weight(nesr_segformer* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim);
+int nesr_segformer_finalize(nesr_segformer* ctx);
+/*
+ * `outputs = model(pixel_values); outputs.logits` (nesr/nesr.py:713, 716): pixel_values_dev [1, 3, H, W] f32 -> logits_dev
+ * [1, num_labels, H/4, W/4] f32, both on the context's device.  N must be 1, H and W multiples of 32 and H W <= 2^26
+ * (NESR_ERR_ARG otherwise).
+ * Enqueued on hip_stream; the workspace grows on the first call for a larger size (that call synchronises the device).
+ */
+int nesr_segformer_forward_f32(nesr_segformer* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* logits_dev,
+                               void* hip_stream);
+/*
+ * nesr/nesr.py:701-716 on an [H, W, 3] u8 RGB frame on the device: `pil_image.resize(new_size, Image.LANCZOS)` when
+ * max(W, H) > 1024 (new_size = (int(W s), int(H s)), s = 1024 / max(W, H)), the extractor's resize to 512 x 512 (PIL BILINEAR) and
+ * normalisation ((v / 255 - mean) / std, ImageNet's), the network, `logits.argmax(dim=1)` at the logits' own size: class_map_dev
+ * [128, 128] u8 (capacity: its bytes, at least 128 * 128), *out_h = *out_w = 128.  The lowest class wins a tie; the logits are never
+ * written to memory.  The map's resize back to the frame (:719-724) is the caller's, on the mask (see nesr_segment_enhance_u8).
+ * nesr_segformer_preprocess_u8: the pre-processing alone, pixel_values_dev [1, 3, 512, 512] f32 (two launches, four above 1024).
+ */
+int nesr_segformer_segment_u8(nesr_segformer* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* class_map_dev, size_t capacity,
+                              int* out_h, int* out_w, void* hip_stream);
+int nesr_segformer_preprocess_u8(nesr_segformer* ctx, const uint8_t* rgb_dev, int H, int W, float* pixel_values_dev, void* hip_stream);
+/*
+ * The launch counter and the event timing of a context.  The counter always runs; with timing on, every launch is bracketed by an
+ * event pair and summed into its group.  nesr_segformer_kernel_time_ms waits for the recorded launches, writes the first
+ * min(n_groups, NESR_SEG_GROUPS) group times (ms) and the launches since the last call, and resets both.
+ */
+enum { NESR_SEG_GROUP_PREPROCESS = 0, NESR_SEG_GROUP_PATCH_EMBED = 1, NESR_SEG_GROUP_LN_PROJ = 2, NESR_SEG_GROUP_SEQ_REDUCTION = 3,
+       NESR_SEG_GROUP_ATTENTION = 4, NESR_SEG_GROUP_MIX_FFN = 5, NESR_SEG_GROUP_DECODE_HEAD = 6, NESR_SEG_GROUPS = 7 };
+int nesr_segformer_set_timing(nesr_segformer* ctx, int enable);
+int nesr_segformer_kernel_time_ms(nesr_segformer* ctx, double* group_ms, int n_groups, int64_t* launches);
+/*
+ * PIL's `Image.resize((out_w, out_h), filter)` of an 8-bit image (nesr/nesr.py:709, and the extractor's resize behind :712) on
+ * [H, W, C] u8, C = 1..4, bit for bit: the horizontal pass, then the vertical pass, a u8 image between them, a pass that keeps its
+ * size skipped; integer coefficients with 22 fractional bits from doubles computed on the host.  filter: NESR_PIL_LANCZOS (1) or
+ * NESR_PIL_BILINEAR (2), PIL.Image's own numbers.  Allocates its tables and the intermediate image and waits for hip_stream
+ * on every route (also when the sizes are equal and the image is only copied): dst is written when it returns.
+ */
+enum { NESR_PIL_LANCZOS = 1, NESR_PIL_BILINEAR = 2 };
+int nesr_pil_resize_u8(int device_id, const uint8_t* src_dev, int H, int W, int C, uint8_t* dst_dev, int out_h, int out_w, int filter,
+                       void* hip_stream);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

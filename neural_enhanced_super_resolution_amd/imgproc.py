@@ -727,7 +727,8 @@ def segment_enhance(img, seg_map, use_hip=None):
     For a frame whose longer side exceeds 1024 the reference runs the segmenter on a downscaled frame and resizes the class map back
     with INTER_NEAREST (:703-724); nearest commutes with `> 0`, so that step is done here on the mask, resize_u8(INTER_NEAREST).  In
     the reference that branch hands an int64 array to cv2.resize, which throws, and its except clause silently skips the whole
-    stage; that throw is NOT reproduced: the stage runs.  SegFormer itself is the caller's.
+    stage; that throw is NOT reproduced: the stage runs.  The class map comes from the segmenter, segformer.SegFormer.segment on the HIP
+    path (or any callable of the caller's).
 
     On a ROCm device one C call (nesr_segment_enhance_u8: the mask's linear resize and one fused stencil, csrc/filters.hip) unless
     use_hip=False selects the torch chain below -- the two agree bit for bit."""

@@ -338,8 +338,9 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
               or, with no result, cv2.resize(INTER_CUBIC)        nesr.py:597-605 -> imgproc.resize_u8
             current = _postprocess_image(current)                nesr.py:616   -> `postprocess` (adaptive unsharp; None = off)
 
-    `segmenter` is a callable, RGB u8 frame -> class map (any integer dtype, host or device; the reference's is SegFormer, whose
-    weights are a network fetch: the caller's); `extra_upscalers` a sequence of callables, frame -> upscaled RGB u8 frame or None
+    `segmenter` is a callable, RGB u8 frame -> class map (any integer dtype, host or device).  The reference's is SegFormer-B0:
+    segformer.SegFormer.from_checkpoint(local path) runs it as HIP kernels and goes in as it is, the frame never leaves the device
+    (the reference fetches the weights from the hub; here the caller passes a local checkpoint); `extra_upscalers` a sequence of callables, frame -> upscaled RGB u8 frame or None
     (the reference's second model is a remote diffusion pipeline; realesrganer_stage wraps a RealESRGANer around the other network
     family).  `upscaler=None` with no extra result is the reference's no-model configuration (use_esrgan=False, use_diffusion=False)
     and takes its bicubic step to (int(w f), int(h f)); it is reached through that explicit configuration only, never from an

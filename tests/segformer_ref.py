@@ -1,0 +1,279 @@
+"""The specification of the SegFormer path (neural_enhanced_super_resolution_amd/segformer.py, csrc/segformer*.hip): a plain-torch
+functional restatement of ``transformers``' SegformerForSemanticSegmentation in eval mode, PIL's 8-bit resize restated in numpy,
+the pre-processing of the reference's _segment_and_enhance (nesr/nesr.py:701-712) and the seeded weights the tests use.
+
+The forward is dtype-generic: the tests run it in float64 as the reference and in float32 on the CPU to size the tolerance.
+test_segformer_host.py pins it to ``transformers`` (when that imports) and the resize to PIL (when that imports); the GPU tests
+need torch and numpy only.
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from neural_enhanced_super_resolution_amd.segformer import segformer_state_dict_spec
+
+B0 = dict(num_channels=3, num_encoder_blocks=4, depths=(2, 2, 2, 2), sr_ratios=(8, 4, 2, 1), hidden_sizes=(32, 64, 160, 256),
+          patch_sizes=(7, 3, 3, 3), strides=(4, 2, 2, 2), num_attention_heads=(1, 2, 5, 8), mlp_ratios=(4, 4, 4, 4),
+          decoder_hidden_size=256, num_labels=150)
+LN_EPS = 1e-5      # nn.LayerNorm's default: transformers builds every LayerNorm without config.layer_norm_eps (1e-6)
+BN_EPS = 1e-5
+IMAGE_MEAN = (0.485, 0.456, 0.406)
+IMAGE_STD = (0.229, 0.224, 0.225)
+SEGMENT_MAX_SIZE = 1024
+MODEL_SIZE = 512
+
+# (old checkpoint name fragment, transformers-5 fragment), the table of the issue; applied in this order, new -> old here
+_NEW_TO_OLD = [
+    ("attention.sequence_reduction.sequence_reduction", "attention.self.sr"),
+    ("attention.sequence_reduction.layer_norm", "attention.self.layer_norm"),
+    ("attention.q_proj", "attention.self.query"),
+    ("attention.k_proj", "attention.self.key"),
+    ("attention.v_proj", "attention.self.value"),
+    ("attention.o_proj", "attention.output.dense"),
+    ("mlp.fc1", "mlp.dense1"),
+    ("mlp.fc2", "mlp.dense2"),
+    ("layernorm_before", "layer_norm_1"),
+    ("layernorm_after", "layer_norm_2"),
+    ("decode_head.linear_projections", "decode_head.linear_c"),
+]
+
+
+def old_key(new):
+    """The name the published checkpoint (transformers 4) gives tensor `new` (a transformers-5 name)."""
+    k = new
+    for a, b in _NEW_TO_OLD:
+        k = k.replace(a, b)
+    parts = k.split(".")
+    if parts[:2] == ["segformer", "stages"]:
+        i, rest = parts[2], parts[3:]
+        if rest[0] == "patch_embeddings":
+            k = ".".join(["segformer", "encoder", "patch_embeddings", i] + rest[1:])
+        elif rest[0] == "blocks":
+            k = ".".join(["segformer", "encoder", "block", i] + rest[1:])
+        else:    # the stage's closing layer_norm
+            k = ".".join(["segformer", "encoder", "layer_norm", i] + rest[1:])
+    return k
+
+
+def to_old_names(sd):
+    return OrderedDict((old_key(k), v) for k, v in sd.items())
+
+
+def seeded_state_dict(seed=0, norm_noise=0.1, **cfg):
+    """Every float tensor with >= 2 dims ~ N(0, (1.5 / sqrt(fan_in))^2), biases ~ N(0, 0.1^2), norm weights 1 + norm_noise N,
+    running_mean ~ N(0, 0.1^2), running_var ~ U(0.5, 1.5), from one seeded CPU generator in the order of the spec (float32)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = OrderedDict()
+    for key, shape in segformer_state_dict_spec(**cfg).items():
+        leaf = key.rsplit(".", 1)[1]
+        if leaf == "num_batches_tracked":
+            sd[key] = torch.tensor(0, dtype=torch.int64)
+        elif leaf == "running_mean":
+            sd[key] = 0.1 * torch.randn(shape, generator=g)
+        elif leaf == "running_var":
+            sd[key] = 0.5 + torch.rand(shape, generator=g)
+        elif len(shape) >= 2:
+            fan_in = int(np.prod(shape[1:]))
+            sd[key] = (1.5 / math.sqrt(fan_in)) * torch.randn(shape, generator=g)
+        elif "norm" in key and leaf == "weight":
+            sd[key] = 1.0 + norm_noise * torch.randn(shape, generator=g)
+        else:
+            sd[key] = 0.1 * torch.randn(shape, generator=g)
+    return sd
+
+
+def seeded_input(h, w, seed=0):
+    """pixel_values-like [1, 3, h, w] float32: normalised uint8 noise."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    u8 = torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8)
+    return normalise(u8.numpy())
+
+
+def seeded_frame(h, w, seed=0):
+    """[h, w, 3] uint8 RGB ndarray: blocks of colour plus noise."""
+    g = torch.Generator().manual_seed(2000 + seed)
+    coarse = torch.rand((1, 3, (h + 15) // 16, (w + 15) // 16), generator=g)
+    img = F.interpolate(coarse, size=(h, w), mode="bilinear", align_corners=False)[0].permute(1, 2, 0)
+    img = img * 255.0 + 12.0 * torch.randn((h, w, 3), generator=g)
+    return img.round().clamp(0, 255).to(torch.uint8).numpy()
+
+
+# ------------------------------------------------------------------------------------------------ the network
+def segformer_forward(sd, x, **cfg):
+    """Logits [1, num_labels, H/4, W/4] of pixel_values x [N, 3, H, W] in x's dtype (sd: transformers-5 names, any float dtype)."""
+    c = dict(B0)
+    c.update(cfg)
+    dt = x.dtype
+    p = {k: v.to(dt) for k, v in sd.items() if v.dtype.is_floating_point}
+
+    def ln(t, name):
+        return F.layer_norm(t, (t.shape[-1],), p[name + ".weight"], p[name + ".bias"], LN_EPS)
+
+    def lin(t, name):
+        return F.linear(t, p[name + ".weight"], p[name + ".bias"])
+
+    feats = []
+    h = x
+    for i in range(c["num_encoder_blocks"]):
+        s = f"segformer.stages.{i}"
+        k = c["patch_sizes"][i]
+        h = F.conv2d(h, p[s + ".patch_embeddings.proj.weight"], p[s + ".patch_embeddings.proj.bias"], stride=c["strides"][i], padding=k // 2)
+        n, ch, hh, ww = h.shape
+        t = ln(h.flatten(2).transpose(1, 2), s + ".patch_embeddings.layer_norm")
+        heads = c["num_attention_heads"][i]
+        d = ch // heads
+        sr = c["sr_ratios"][i]
+        for j in range(c["depths"][i]):
+            b = f"{s}.blocks.{j}"
+            y = ln(t, b + ".layernorm_before")
+            q = lin(y, b + ".attention.q_proj").view(n, -1, heads, d).transpose(1, 2)
+            kv = y
+            if sr > 1:
+                r = b + ".attention.sequence_reduction"
+                kv = y.transpose(1, 2).reshape(n, ch, hh, ww)
+                kv = F.conv2d(kv, p[r + ".sequence_reduction.weight"], p[r + ".sequence_reduction.bias"], stride=sr)
+                kv = ln(kv.reshape(n, ch, -1).transpose(1, 2), r + ".layer_norm")
+            kk = lin(kv, b + ".attention.k_proj").view(n, -1, heads, d).transpose(1, 2)
+            vv = lin(kv, b + ".attention.v_proj").view(n, -1, heads, d).transpose(1, 2)
+            a = torch.softmax(torch.matmul(q, kk.transpose(2, 3)) * d ** -0.5, dim=-1)
+            a = torch.matmul(a, vv).transpose(1, 2).reshape(n, -1, ch)
+            t = t + lin(a, b + ".attention.o_proj")
+            y = lin(ln(t, b + ".layernorm_after"), b + ".mlp.fc1")
+            y = y.transpose(1, 2).reshape(n, -1, hh, ww)
+            y = F.conv2d(y, p[b + ".mlp.dwconv.dwconv.weight"], p[b + ".mlp.dwconv.dwconv.bias"], padding=1, groups=y.shape[1])
+            y = F.gelu(y.flatten(2).transpose(1, 2))
+            t = t + lin(y, b + ".mlp.fc2")
+        t = ln(t, s + ".layer_norm")
+        h = t.reshape(n, hh, ww, ch).permute(0, 3, 1, 2).contiguous()
+        feats.append(h)
+    size = feats[0].shape[2:]
+    ups = []
+    for i, f in enumerate(feats):
+        n, ch, hh, ww = f.shape
+        t = lin(f.flatten(2).transpose(1, 2), f"decode_head.linear_projections.{i}.proj")
+        t = t.transpose(1, 2).reshape(n, -1, hh, ww)
+        ups.append(F.interpolate(t, size=size, mode="bilinear", align_corners=False))
+    y = F.conv2d(torch.cat(ups[::-1], dim=1), p["decode_head.linear_fuse.weight"])
+    bn = "decode_head.batch_norm"
+    y = F.batch_norm(y, p[bn + ".running_mean"], p[bn + ".running_var"], p[bn + ".weight"], p[bn + ".bias"], False, 0.0, BN_EPS)
+    return F.conv2d(F.relu(y), p["decode_head.classifier.weight"], p["decode_head.classifier.bias"])
+
+
+def top2_margin(logits):
+    """[H, W] margin between the two largest logits of every position (logits [1, L, H, W])."""
+    top = logits[0].topk(2, dim=0).values
+    return top[0] - top[1]
+
+
+def check_class_map(got, logits64, tol, max_excluded=0.01):
+    """The class-map criterion: `got` equals the float64 argmax wherever the float64 top-2 margin is at least 2 tol; the
+    positions left out are at most max_excluded of the map.  Returns (excluded, wrong at the checked positions)."""
+    ref = logits64[0].argmax(dim=0)
+    firm = top2_margin(logits64) >= 2 * tol
+    excluded = int((~firm).sum())
+    wrong = int(((torch.as_tensor(got).to(torch.int64).cpu() != ref) & firm).sum())
+    assert excluded <= max_excluded * ref.numel(), (excluded, ref.numel())
+    return excluded, wrong
+
+
+# ------------------------------------------------------------------------------------------------ PIL's 8-bit resize
+PIL_BILINEAR, PIL_LANCZOS = 2, 1      # PIL.Image.BILINEAR / LANCZOS; the filter argument of nesr_pil_resize_u8
+PRECISION_BITS = 22
+
+
+def _bilinear(x):
+    x = abs(x)
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+def _lanczos(x):
+    return _sinc(x) * _sinc(x / 3.0) if -3.0 <= x < 3.0 else 0.0
+
+
+def pil_coeffs(in_size, out_size, flt):
+    """Per output index (xmin, integer coefficients) of PIL's ImagingResample for an 8-bit image."""
+    filt, support = (_bilinear, 1.0) if flt == PIL_BILINEAR else (_lanczos, 3.0)
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = support * fs
+    out = []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        ss = 1.0 / fs      # PIL's precompute_coeffs multiplies by the reciprocal; so do the kernel's tables
+        w = [filt((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        out.append((xmin, [int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS)) for v in w]))
+    return out
+
+
+def _pil_pass(img, out_size, flt, axis):
+    img = np.moveaxis(img, axis, 0)
+    res = np.empty((out_size,) + img.shape[1:], np.uint8)
+    for xx, (xmin, k) in enumerate(pil_coeffs(img.shape[0], out_size, flt)):
+        acc = np.full(img.shape[1:], 1 << (PRECISION_BITS - 1), np.int64)
+        for j, kj in enumerate(k):
+            acc += img[xmin + j].astype(np.int64) * kj
+        res[xx] = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
+    return np.moveaxis(res, 0, axis)
+
+
+def pil_resize(img, oh, ow, flt):
+    """PIL's Image.resize((ow, oh), flt) of an [h, w, c] uint8 array: the horizontal pass, then the vertical one, a uint8 image
+    between them; a pass that keeps its size is skipped."""
+    img = np.ascontiguousarray(img)
+    if img.shape[1] != ow:
+        img = _pil_pass(img, ow, flt, 1)
+    if img.shape[0] != oh:
+        img = _pil_pass(img, oh, flt, 0)
+    return np.ascontiguousarray(img)
+
+
+def normalise(u8):
+    """[h, w, 3] uint8 -> pixel_values [1, 3, h, w] float32: (u8 * (1 / 255) - mean) / std, each step rounded to float32."""
+    x = torch.from_numpy(np.ascontiguousarray(u8)).to(torch.float32) * torch.tensor(1.0 / 255.0, dtype=torch.float32)
+    x = (x - torch.tensor(IMAGE_MEAN, dtype=torch.float32)) / torch.tensor(IMAGE_STD, dtype=torch.float32)
+    return x.permute(2, 0, 1)[None].contiguous()
+
+
+def segment_resized(frame):
+    """The uint8 [512, 512, 3] image the network sees for an [h, w, 3] uint8 RGB frame (nesr/nesr.py:701-712)."""
+    h, w = frame.shape[:2]
+    if max(h, w) > SEGMENT_MAX_SIZE:
+        scale = SEGMENT_MAX_SIZE / max(w, h)
+        frame = pil_resize(frame, int(h * scale), int(w * scale), PIL_LANCZOS)
+    return pil_resize(frame, MODEL_SIZE, MODEL_SIZE, PIL_BILINEAR)
+
+
+def preprocess(frame):
+    return normalise(segment_resized(frame))
+
+
+# ------------------------------------------------------------------------------------------------ the cases both test files use
+# (source h, source w, result h, result w, filter): PIL sizes (w, h) 100x140, 777x1031, 600x512 (one pass only), 1300x900 -> 1024x708
+RESIZE_CASES = [(140, 100, 512, 512, PIL_BILINEAR), (1031, 777, 512, 512, PIL_BILINEAR), (512, 600, 512, 512, PIL_BILINEAR),
+                (900, 1300, 708, 1024, PIL_LANCZOS)]
+# (h, w, seed of seeded_input): 4 keys in stage 0; ragged tiles everywhere (960 / 240 / 60 / 15 tokens, 15 keys); the pipeline's
+# shape, 256 keys; 272 keys, so the attention's second key chunk (16 keys after 256) runs
+FORWARD_CASES = [(64, 64, 0), (96, 160, 1), (512, 512, 2), (512, 544, 3)]
+# (h, w, seed of seeded_frame): below and above the 1024 pixels of nesr/nesr.py:705
+FRAME_CASES = [(140, 100, 4), (900, 1300, 5)]
+WEIGHT_SEED = 0
+MAX_THIN = 0.01      # positions whose float64 top-2 margin is below twice the tolerance: at most this share of a map
