@@ -2,12 +2,14 @@
 """In-process timing of N builds of libnesr_hip.so, interleaved rounds on one device (cdna_hip_programming.md rule 24).
 
     tools/abn.py A.so B.so [C.so ...] [--dtype direct|bf16|wino|split|f16] [--hw 512] [--batch 1] [--rounds 12]
+                 [--iters 3] [--warmup 0] [--json out.json]      (--rounds 7 --iters 20 --warmup 5: the profiles' ab_c2.json)
                  [--env "K=V,K2=V2;K=V;..."]      (one ;-separated entry per library, applied through its first forward)
     --dtype takes one value for all libraries or a comma-separated list, one per library: `new.so new2.so --dtype bf16,f16 --c3`
     times the two 16-bit forms of one build on the ragged 4K batch (two copies of the file: dlopen returns one handle per path).
 """
 import argparse
 import ctypes
+import json
 import os
 import statistics
 import sys
@@ -31,6 +33,8 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--iters", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=0, help="untimed forwards in front of every timed region")
+    ap.add_argument("--json", default=None, help="write the regions' times, medians, spreads (max - min) and the output comparison here")
     ap.add_argument("--env", default="")
     ap.add_argument("--c3", action="store_true", help="the 40 ragged tiles of a 3840x2160 frame cut 512/10 (nesr_forward_ragged, bf16 / f16)")
     ap.add_argument("--share", type=int, default=1, help="with --c3: only every share-th tile (what one of `share` ranks of a sharded frame evaluates)")
@@ -91,6 +95,8 @@ def main():
         order = list(range(n))
         order = order[r % n:] + order[:r % n]
         for i in order:
+            for _ in range(args.warmup):
+                run(i)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(args.iters):
@@ -103,6 +109,20 @@ def main():
         eq = torch.equal(y[0], y[i])
         print(f"{i} {os.path.basename(name):28s} {envs[i]:24s} median {statistics.median(t):8.3f} ms  min {min(t):8.3f}  ratio {statistics.median(t) / base:.4f}  "
               f"== lib0: {eq} (max diff {float((y[0] - y[i]).abs().max()):.2e})", flush=True)
+    if args.json:
+        names = [os.path.splitext(os.path.basename(p))[0] for p in args.libs]
+        med = [statistics.median(t) for t in times]
+        out = {"frame": f"{args.batch}x3x{args.hw}x{args.hw}, synthetic weights, dtype codes {dts}", "env": envs,
+               "steps_per_region": args.iters, "warmup_per_region": args.warmup, "alternations": args.rounds,
+               "ms_per_step": {nm: [round(v, 4) for v in t] for nm, t in zip(names, times)},
+               "median": {nm: round(m, 4) for nm, m in zip(names, med)},
+               "spread_max_minus_min": {nm: round(max(t) - min(t), 4) for nm, t in zip(names, times)},
+               "bit_equal_to_" + names[0]: {nm: bool(torch.equal(y[0], y[i])) for i, nm in enumerate(names)},
+               "max_abs_diff_vs_" + names[0]: {nm: float((y[0] - y[i]).abs().max()) for i, nm in enumerate(names)},
+               "gain_ms_vs_" + names[0]: {nm: round(med[0] - m, 4) for nm, m in list(zip(names, med))[1:]},
+               "gain_pct": {nm: round(100 * (med[0] - m) / med[0], 2) for nm, m in list(zip(names, med))[1:]}}
+        with open(args.json, "w") as f:
+            json.dump(out, f, indent=1)
 
 
 if __name__ == "__main__":

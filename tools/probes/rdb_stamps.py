@@ -34,6 +34,12 @@ for s in range(N):
         ep = f"  epilogue in the MFMA wave: start +{m[3]-m[1]} exchange/bias/act {m[4]-m[3]} split/regroup {m[5]-m[4]} stores {m[6]-m[5]}"
     print(f"{s:3d} | {m[0]-t0:8d} {m[1]-m[0]:6d} {m[2]-m[1]:6d} | {d[0]-t0:8d} ({d[1]-d[0]:5d}) {d[2]-d[1]:6d} {d[3]-d[2]:6d} {nd-d[3]:6d} | {nm-m[0]:6d}{ep}")
 print("total cycles", S[0][N - 1][2] - t0)
+# outside the steps (slot 61): [role][61][0] = kernel entry of that wave, [0][61][1] = the final epilogue's last store has
+# retired (the stamp build waits for it).  The DMA wave's step-0 stamp is its first instruction behind the first barrier.
+if S[1][61][0] and S[0][61][1]:
+    print(f"entry -> first barrier: DMA wave 0 {S[1][0][0] - S[1][61][0]} cycles (MFMA wave 1 entered {S[0][61][0] - S[1][61][0]:+d} relative to it)")
+    print(f"last step -> end: {S[0][61][1] - S[0][N - 1][2]} cycles (MFMA wave 1: end of the last MFMA step to its last store retired)")
+    print(f"entry -> end: {S[0][61][1] - min(S[0][61][0], S[1][61][0])} cycles")
 dr, dt = S[1][63][0] - S[1][62][0], S[1][63][1] - S[1][62][1]
 print(f"steps 0..{N - 1}: {dt} shader cycles in {dr} ticks of the 100 MHz clock = {dr / 100:.2f} us: shader clock {dt / dr * 100:.0f} MHz")
 
