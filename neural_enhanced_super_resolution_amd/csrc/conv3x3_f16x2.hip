@@ -507,7 +507,7 @@ __device__ unsigned long long g_rdb_arrive[12][8][2];      // [wave][step - 20][
 #define RARRIVE(w, step, ev) do { } while (0)
 #endif
 
-constexpr int RSLOTS = 4;   // ring slots of the fused kernel: the DMA waves run three steps ahead, step s + 1 has landed at barrier s
+constexpr int RSLOTS = 4;   // ring slots of the fused kernel: the DMA waves run three steps ahead, step s + 1 has landed at barrier s (staggered, conv1..conv4: two ahead, step s has: namespace rdbs)
 constexpr int RDB_STEP5 = 4 + 6 + 8 + 10;     // conv5's first step: its steps take two weight slabs each (all 64 output channels)
 constexpr int RDB_STEPS = RDB_STEP5 + 12;     // K-chunk steps of a dense block
 constexpr int W5_ROUNDS = 2 * W_ITEMS / (64 * 4);
@@ -521,18 +521,158 @@ constexpr int DW = 4;       // DMA waves: LDS-DMA, neighbour polling, progress w
 #define NESR_RDB_EPI_STEPS 1
 #endif
 constexpr int EPI_STEPS = NESR_RDB_EPI_STEPS;   // a finished layer's epilogue rides in the first 1 or 2 steps of the next one
-// The DMA waves fetch RSLOTS - 1 steps ahead: the first x1 chunk of conv2 (its step 4) is requested in conv2's step 1, and
-// that request polls this tile's own progress word among the nine -- which goes out EPI_STEPS steps into the layer.
+// The DMA waves fetch at most RSLOTS - 1 steps ahead: the first x1 chunk of conv2 (its step 4) is requested in conv2's step 1
+// at the earliest, and that request polls this tile's own progress word among the nine -- which goes out EPI_STEPS steps into the layer.
 static_assert(EPI_STEPS <= 4 - (RSLOTS - 1), "the tile would wait for its own progress word");
+
+// The stagger.  MFMA waves w and w + 4 share a SIMD and run the same program: with one barrier on top of every step both
+// reach the address updates, the fragment waits, the barrier and the ramp behind it together, and the matrix pipe has
+// nothing to issue meanwhile.  NESR_RDB_LAG = L > 0 delays waves 4..7 by L tap-steps inside each of conv1..conv4: they take
+// the barrier of step s + 1 in front of tap-step 5 - L of step s, so between two barriers they run the last L tap-steps of
+// one step and the first 5 - L of the next, and their step boundary falls into the middle of their partner's MFMAs.
+// Per layer they re-converge: a layer's first step has the barrier on top as well (the deferred epilogue runs there in
+// both partners at once), its last step has none.  conv5 runs aligned.  0: no stagger (every wave as waves 0..3).
+#ifndef NESR_RDB_LAG
+#define NESR_RDB_LAG 2
+#endif
+namespace rdbs {
+constexpr int LAG = NESR_RDB_LAG;
+static_assert(LAG == 0 || LAG == 2 || LAG == 3, "NESR_RDB_LAG: 0, 2 (barrier in front of tap-step 3) or 3 (in front of tap-step 2)");
+constexpr int layer_of(int s) { return s < 4 ? 0 : s < 10 ? 1 : s < 18 ? 2 : s < RDB_STEP5 ? 3 : 4; }
+constexpr int first_of(int l) { return l == 0 ? 0 : l == 1 ? 4 : l == 2 ? 10 : l == 3 ? 18 : RDB_STEP5; }
+constexpr int steps_of(int l) { return l == 4 ? RDB_STEPS - RDB_STEP5 : 4 + 2 * l; }
+// ---- MFMA role: where a step's barriers sit and when its first fragments are requested
+enum Mode {
+    M_TOP,          // LAG 0: barrier on top; the next step's first fragments are requested beside tap-step 4
+    M_LEAD,         // waves 0..3: barrier on top; the step's first fragments are requested behind it
+    M_LAG_FIRST,    // waves 4..7, a layer's first step: as M_LEAD, and the next barrier in front of tap-step 5 - LAG
+    M_LAG_MID,      // waves 4..7: one barrier, in front of tap-step 5 - LAG
+    M_LAG_LAST,     // waves 4..7, a layer's last step: no barrier, no request for the next step
+    M_CONV5         // barrier on top; weights behind it, the next step's first pixel fragments beside tap-step 4
+};
+constexpr int mode_of(bool lagging, int s) {
+    const int l = layer_of(s), c = s - first_of(l);
+    return l == 4 ? M_CONV5 : LAG == 0 ? M_TOP : !lagging ? M_LEAD : c == 0 ? M_LAG_FIRST : c == steps_of(l) - 1 ? M_LAG_LAST : M_LAG_MID;
+}
+constexpr bool bar_top(int m) { return m != M_LAG_MID && m != M_LAG_LAST; }
+constexpr int bar_tap(int m) { return m == M_LAG_FIRST || m == M_LAG_MID ? 5 - LAG : -1; }      // the barrier in front of this tap-step
+constexpr bool req_behind(int m) { return m == M_LEAD || m == M_LAG_FIRST; }                    // tap-step 0's fragments: behind the top barrier
+constexpr bool req_early(int m) { return m == M_TOP || m == M_LAG_FIRST || m == M_LAG_MID; }    // the next step's: beside tap-step 4
+// ---- DMA role.  Input chunk and weight slab of step t go to ring position t & 3 (conv5's slab pair: 0,1 / 2,3).
+// LAG 0: three steps ahead throughout.  LAG > 0: waves 4..7 still read step s - 1 behind barrier s, so conv1..conv4 are
+// fetched TWO steps ahead (interval s = barrier s .. barrier s + 1 issues step s + 2 into the position of step s - 2);
+// conv5 needs three again (its pixel prefetch crosses the barrier): the catch-up chunk goes out in conv5's first
+// interval, when waves 4..7 have left conv4's last two slots.
+constexpr int in_end(int i) {      // input steps [0, in_end(i)) are issued by the end of interval i (-1: the prologue)
+    const int e = (LAG != 0 && i < RDB_STEP5) ? i + 3 : i + 4;
+    return e < RDB_STEPS ? e : RDB_STEPS;
+}
+constexpr int IN_LEAD = in_end(-1);
+constexpr bool w_slab(int i) { return i + 1 < RDB_STEP5 && in_end(i - 1) < RDB_STEP5; }      // interval i issues a conv1..conv4 slab (that of its input step)
+constexpr bool w_pair(int i) { return i + 1 >= RDB_STEP5 && i + 1 < RDB_STEPS; }             // interval i issues conv5's slab pair of step i + 1
+// Issue order inside an interval: weights, then the input chunks in step order -- the order the next barrier needs them
+// in.  These many of the interval's LAST issues may still be in flight at the next barrier (counted wait):
+constexpr int tail_w(int i) { return w_slab(i) ? 1 : 0;}
+constexpr int tail_in(int i) {
+    const int n = in_end(i) - in_end(i - 1);
+    return LAG != 0 && i == RDB_STEP5 - 1 ? 0       // conv5's first step prefetches step 29's pixels: nothing stays in flight
+         : LAG != 0 && i == RDB_STEP5 ? 1           // the catch-up: step 30 has landed at barrier 29, step 31 need not
+         : n;
+}
+// ---- the proof: a walk over the 40 steps with the functions above (the kernel's loops use the same ones)
+struct Walk {
+    int in_iss[RDB_STEPS] = {}, w_iss[RDB_STEPS] = {};          // interval that issues step t's input chunk / weights (-2: the prologue)
+    int in_land[RDB_STEPS] = {}, w_land[RDB_STEPS] = {};        // barrier (-1: the one in front of step 0's) whose wait covers them
+    int rd_lo[2][RDB_STEPS + 1] = {}, rd_hi[2][RDB_STEPS + 1] = {};   // [waves 0..3 | 4..7][interval + 1]: steps whose slots are read (input)
+    int wr_hi[2][RDB_STEPS + 1] = {};                                 // the same for weights (the lower end is rd_lo)
+    int bars[3] = {};                                           // s_barrier count: waves 0..3, waves 4..7, DMA waves
+    bool ok = true;
+};
+constexpr bool pos_overlap_w(int t, int u) {      // do the weights of steps t and u share a ring slab?
+    const int t0 = t < RDB_STEP5 ? (t & 3) : (t & 1) * 2, t1 = t < RDB_STEP5 ? t0 : t0 + 1;
+    const int u0 = u < RDB_STEP5 ? (u & 3) : (u & 1) * 2, u1 = u < RDB_STEP5 ? u0 : u0 + 1;
+    return t0 <= u1 && u0 <= t1;
+}
+constexpr Walk walk() {
+    Walk k;
+    // MFMA roles: which interval every tap-step (and every fragment request) falls into
+    for (int r = 0; r < 2; ++r) {
+        for (int i = 0; i <= RDB_STEPS; ++i) { k.rd_lo[r][i] = RDB_STEPS; k.rd_hi[r][i] = -1; k.wr_hi[r][i] = -1; }
+        int b = 1;      // barriers taken so far (the extra one in front of step 0's is the first): the wave is in interval b - 2
+        auto rd = [&](int t, bool pix, bool wts) {
+            if (t < k.rd_lo[r][b - 1]) k.rd_lo[r][b - 1] = t;
+            if (pix && t > k.rd_hi[r][b - 1]) k.rd_hi[r][b - 1] = t;
+            if (wts && t > k.wr_hi[r][b - 1]) k.wr_hi[r][b - 1] = t;
+        };
+        if (mode_of(r, 0) == M_TOP) rd(0, true, true);
+        for (int s = 0; s < RDB_STEPS; ++s) {
+            const int m = mode_of(r, s);
+            if (bar_top(m)) ++b;
+            for (int t = 0; t < 5; ++t) {
+                if (t == bar_tap(m)) ++b;
+                rd(s, true, true);
+                // the request for the next step: conv4's last step asks for weights that conv5's first step reads again (M_TOP)
+                if (t == 4 && req_early(m)) rd(s + 1, true, s + 1 < RDB_STEP5);
+                if (t == 4 && m == M_CONV5 && s + 1 < RDB_STEPS) rd(s + 1, true, false);
+            }
+        }
+        k.bars[r] = b;
+    }
+    // DMA role: the issue queue in order (vmcnt retires in order), and what every barrier's counted wait leaves in flight
+    int q_step[3 * RDB_STEPS] = {}, q_w[3 * RDB_STEPS] = {}, qn = 0, landed = 0;
+    auto land = [&](int upto, int b) {
+        for (; landed < upto; ++landed) (q_w[landed] ? k.w_land : k.in_land)[q_step[landed]] = b;
+    };
+    for (int t = 0; t < IN_LEAD; ++t) {
+        q_step[qn] = t; q_w[qn++] = 1; k.w_iss[t] = -2;
+        q_step[qn] = t; q_w[qn++] = 0; k.in_iss[t] = -2;
+    }
+    land(qn - 2 * (IN_LEAD - 1), -1);
+    int tail = 2;      // barrier 0: one step of the prologue may still be in flight
+    k.bars[2] = 1;
+    for (int i = 0; i < RDB_STEPS; ++i) {
+        land(qn - tail, i);
+        ++k.bars[2];
+        const int f = in_end(i - 1), e = in_end(i);
+        if (w_pair(i)) { q_step[qn] = i + 1; q_w[qn++] = 1; k.w_iss[i + 1] = i; }
+        else if (w_slab(i)) {
+            if (e - f != 1) k.ok = false;
+            q_step[qn] = f; q_w[qn++] = 1; k.w_iss[f] = i;
+        }
+        for (int t = f; t < e; ++t) { q_step[qn] = t; q_w[qn++] = 0; k.in_iss[t] = i; }
+        tail = tail_w(i) + tail_in(i);
+        if (tail_w(i) && tail_in(i) != e - f) k.ok = false;      // weights are issued first: in flight only with all that follows
+    }
+    if (qn != 2 * RDB_STEPS) k.ok = false;
+    land(qn, RDB_STEPS);
+    // every read: landed at or before the barrier that opens its interval, and nothing newer issued into its position by
+    // the end of that interval (= the position is no DMA destination while it is read)
+    for (int r = 0; r < 2; ++r)
+        for (int i = -1; i < RDB_STEPS; ++i) {
+            for (int t = k.rd_lo[r][i + 1]; t <= k.rd_hi[r][i + 1]; ++t) {
+                if (k.in_land[t] > i) k.ok = false;
+                for (int u = t + 1; u < RDB_STEPS; ++u) if ((u & 3) == (t & 3) && k.in_iss[u] <= i) k.ok = false;
+            }
+            for (int t = k.rd_lo[r][i + 1]; t <= k.wr_hi[r][i + 1]; ++t) {
+                if (k.w_land[t] > i) k.ok = false;
+                for (int u = t + 1; u < RDB_STEPS; ++u) if (pos_overlap_w(t, u) && k.w_iss[u] <= i) k.ok = false;
+            }
+        }
+    return k;
+}
+constexpr Walk WALK = walk();
+static_assert(WALK.ok, "a ring position is refilled while it is read, or read before the wait that covers it");
+static_assert(WALK.bars[0] == RDB_STEPS + 1 && WALK.bars[1] == RDB_STEPS + 1 && WALK.bars[2] == RDB_STEPS + 1, "every role takes the same number of barriers");
+}  // namespace rdbs
 
 // Roles.  MFMA waves (0..7): row w of the 8x32-pixel tile, 32 couts (conv5: 64): LDS fragment reads, MFMAs, and the epilogue of
 // the PREVIOUS layer (conv5's own follows its last step) -- its sums wait in 16 registers (main + cross / 2^11) and are finished (bias,
 // LeakyReLU / residuals, split, whole-line stores) at the start of the next layer's first step, by both waves of a SIMD
-// at the same point (NESR_RDB_PAR 0).  Measured alternatives: the epilogue in the DMA waves, or in
+// at the same point (NESR_RDB_PAR 0).  Waves 4..7 run part of a step behind waves 0..3 inside conv1..conv4 (NESR_RDB_LAG).  Measured alternatives: the epilogue in the DMA waves, or in
 // four waves of its own -- a VALU instruction of a wave that shares its SIMD with two MFMA waves gets one issue slot
 // per MFMA, ~16 cycles each: layer boundaries cost 23 % of the kernel; staggered between the two MFMA waves of a SIMD
 // (one before, one after its MFMAs) -- a VALU block beside the partner's MFMA stream crawls just the same.
-// DMA waves (8..11): one step's LDS-DMAs three steps ahead (4-slot ring; conv5's weight slabs one step ahead), polling of the neighbours' progress words
+// DMA waves (8..11): one step's LDS-DMAs three steps ahead (staggered conv1..conv4: two; 4-slot ring; conv5's weight slabs one step ahead), polling of the neighbours' progress words
 // before the first chunk of each x_l, and this tile's own progress word EPI_STEPS steps into the next layer.
 __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a) {
     typedef Geo<4> G;
@@ -688,7 +828,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         // table is filled by the MFMA waves, and the abort word is a scalar load (lgkmcnt) issued behind them.
         int fl = 0, fc = 0;      // the next step to fetch
 #pragma unroll
-        for (int i = 0; i < RSLOTS - 1; ++i) {
+        for (int i = 0; i < rdbs::IN_LEAD; ++i) {
             dma_w(0, i, i);
             dma_in(i, i);
             advance(fl, fc);
@@ -697,10 +837,10 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         // the scalar cache cannot hold a stale copy); what other workgroups raise during the launch is seen by the polls.
         gave_up = *(const __attribute__((address_space(4))) unsigned*)a.abort_flag != 0u;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zero padding is in LDS before the first barrier
-        int fill = 3;
+        int fill = rdbs::IN_LEAD;      // ring position of the next step to fetch (= that step & 3)
         int cl = 0, cc = 0;      // the current step
-        // chunk 0 has landed: the MFMA waves request the launch's first fragments behind this barrier
-        wait_vmcnt_le((NESR_RDB_ABL & 96) ? 0 : 2 * (kw + kin));
+        // chunk 0 has landed: the MFMA waves request the launch's first fragments behind this barrier (staggered: the next)
+        wait_vmcnt_le((NESR_RDB_ABL & 96) ? 0 : (rdbs::IN_LEAD - 1) * (kw + kin));
         int inflight = kw + kin;      // instructions of the latest issue that the next barrier does not need
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -728,20 +868,20 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             if (cc == EPI_STEPS && cl >= 1 && wave == 0 && lane == 0)
                 __hip_atomic_store(a.progress + tile, a.epoch + (unsigned)cl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // Issue order = the order the waits count in: what the next barrier needs first.
-            inflight = 0;
-            if (step + 1 >= RDB_STEP5) {
+            // (the schedule and its proof: namespace rdbs)
+            if (rdbs::w_pair(step)) {
                 // conv5's next step: both slabs into the half of the ring that step - 1 has just left; needed at the next barrier
-                if (step + 1 < RDB_STEPS) dma_w5(step + 1 - RDB_STEP5, ((step + 1) & 1) * 2);
-            } else if (fl < 4) {
-                dma_w(fl, fc, (step + RSLOTS - 1) & (RSLOTS - 1));      // conv1..conv4: three steps ahead, into the slab read one step ago
-                inflight += kw;
+                dma_w5(step + 1 - RDB_STEP5, ((step + 1) & 1) * 2);
+            } else if (rdbs::w_slab(step)) {
+                dma_w(fl, fc, fill);      // conv1..conv4: with the step's input chunk, into the same ring position
             }
-            if (fl < 5) {      // three steps ahead, into the slot read one step ago
+            // three steps ahead (staggered, conv1..conv4: two; two chunks in conv5's first interval), into slots no wave reads any more
+            for (int k = rdbs::in_end(step) - rdbs::in_end(step - 1); k > 0; --k) {
                 dma_in(fc, fill);
-                inflight += kin;
                 advance(fl, fc);
                 fill = fill == RSLOTS - 1 ? 0 : fill + 1;
             }
+            inflight = rdbs::tail_w(step) * kw + rdbs::tail_in(step) * kin;
             if (wave == 0) RSTAMP(1, step, 3);
             advance(cl, cc);
         }
@@ -978,24 +1118,41 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     // step's tap-step 0 are requested beside this step's last MFMAs -- the next step's chunk landed before this step's
     // barrier -- so that no wave sits behind an LDS round trip after a barrier.  (conv4's last step requests weight
     // fragments that are not there yet -- conv5's slabs land one barrier later -- and conv5's first step reads them again.)
-    auto step_body = [&](auto Pc, int c) {
-        constexpr int P = decltype(Pc)::value;
-        // the x_l stores of this wave have retired before the barrier after which the progress word goes out
-        if (c == EPI_STEPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // That is mode M_TOP, NESR_RDB_LAG 0.
+    // Staggered (NESR_RDB_LAG, namespace rdbs): the mode M says where the step's barriers sit -- on top, in front of a
+    // tap-step (waves 4..7: that one opens the NEXT step's interval; the fragments of the tap-step behind it are in
+    // registers or on their way across it), or nowhere -- and whether tap-step 0's fragments are requested behind the top
+    // barrier (the chunk has landed at that barrier, not earlier: the DMA waves run two steps ahead) or were requested
+    // beside the previous step's last MFMAs (waves 4..7 inside a layer: those MFMAs run behind the barrier).
+    auto step_body = [&](auto Pc, auto Mc, int c) {
+        constexpr int P = decltype(Pc)::value, M = decltype(Mc)::value;
+        constexpr int BT = rdbs::bar_tap(M);
+        // the barrier that opens the interval of the layer's step cb
+        auto bar = [&](int cb) {
+            // the x_l stores of this wave have retired before the barrier after which the progress word goes out
+            if (cb == EPI_STEPS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if NESR_RDB_ABL & 256
-        if (wave == 1) RSTAMP(0, mstep, 0);
-        RARRIVE(wave, mstep, 0);
+            if (wave == 1) RSTAMP(0, mstep, 0);
+            RARRIVE(wave, mstep + (cb - c), 0);
 #endif
-        if (!(NESR_RDB_ABL & 512)) __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+            if (!(NESR_RDB_ABL & 512)) __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
 #if NESR_RDB_ABL & 256
-        RARRIVE(wave, mstep, 1);
-        if (wave == 1) RSTAMP(0, mstep, 1);
+            RARRIVE(wave, mstep + (cb - c), 1);
+            if (wave == 1) RSTAMP(0, mstep, 1);
 #endif
+        };
+        if (rdbs::bar_top(M)) bar(c);
         const bool epi_now = active && ep_l >= 0 && c < EPI_STEPS;
         const int nslot = slot == RSLOTS - 1 ? 0 : slot + 1;
         const unsigned dA = wpos == RSLOTS - 1 ? (unsigned)(-(RSLOTS - 1) * W_BYTES) : (unsigned)W_BYTES;
-        if (active && !(NESR_RDB_ABL & 8)) {
+        if (!(active && !(NESR_RDB_ABL & 8))) {
+            if (BT >= 0) bar(c + 1);      // a wave without a row takes the same barriers
+        } else {
+            if (rdbs::req_behind(M)) {
+                load_a(0, P, 0);
+                load_b(slot, 0, P);
+            }
             if (epi_now && par == 0) {
                 epi_part(c);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1010,19 +1167,25 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 tt[s_] = __builtin_amdgcn_s_memtime();      // no wait here: read at the end of the step
                 __builtin_amdgcn_sched_barrier(0);
 #endif
+                if (s_ == BT) {
+                    bar(c + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 if (s_ + 1 < 5) {
                     load_a(s_ + 1, buf ^ 1, 0);
                     load_b(slot, s_ + 1, buf ^ 1);
-                } else {
+                } else if (rdbs::req_early(M)) {
                     load_a(0, buf ^ 1, dA);      // the next step's slab
                     load_b(nslot, 0, buf ^ 1);
                 }
                 mfma_tap(s_, 0, buf, buf);
                 // the next tap-step's 8 fragment reads ride between this one's MFMAs
+                if (s_ + 1 < 5 || rdbs::req_early(M)) {
 #pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+                    for (int i = 0; i < 8; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1077,6 +1240,8 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         const unsigned dA = wpos == 0 ? (unsigned)(2 * W_BYTES) : (unsigned)(-2 * W_BYTES);
         if (active && !(NESR_RDB_ABL & 8)) {
             load_a(0, 0, 0);
+            // staggered: conv4's last step could not ask for this step's first pixel fragments (step 28 lands at this barrier)
+            if (FIRST && !rdbs::req_early(rdbs::mode_of(false, RDB_STEP5 - 1))) load_b(slot, 0, P);
             if (epi_now && par == 0) {
                 epi_part(c);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1134,20 +1299,22 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     // the launch's first fragments: chunk 0 is in LDS once every DMA wave has passed its first wait -- one extra barrier
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (active) {
+    if (active && rdbs::mode_of(false, 0) == rdbs::M_TOP) {
         load_a(0, 0, 0);
         load_b(0, 0, 0);
     }
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
-    for (int l = 0; l < 4; ++l) {
-        const int nc = 4 + 2 * l;
-        zero_acc(0);
-        for (int c = 0; c < nc; c += 2) {
-            step_body(I0{}, c);
-            step_body(I1{}, c + 1);
-        }
-        // the layer's sums (main + cross / 2^11) wait for the next layer's first steps
+    typedef std::integral_constant<int, rdbs::mode_of(false, 1)> MLead;      // waves 0..3 (not staggered: every wave), any step of conv1..conv4
+    typedef std::integral_constant<int, rdbs::M_LAG_FIRST> MFirst;
+    typedef std::integral_constant<int, rdbs::M_LAG_MID> MMid;
+    typedef std::integral_constant<int, rdbs::M_LAG_LAST> MLast;
+    // waves 4..7 staggered: first step, pairs of middle steps, last step (every layer has an even number of steps >= 4)
+    static_assert(rdbs::LAG == 0 || (rdbs::mode_of(true, 4) == rdbs::M_LAG_FIRST && rdbs::mode_of(true, 5) == rdbs::M_LAG_MID &&
+                                     rdbs::mode_of(true, 8) == rdbs::M_LAG_MID && rdbs::mode_of(true, 9) == rdbs::M_LAG_LAST &&
+                                     rdbs::mode_of(false, 0) == rdbs::mode_of(false, RDB_STEP5 - 1)), "the loops below are the walk's sequence");
+    // the layer's sums (main + cross / 2^11) wait for the next layer's first steps
+    auto layer_done = [&](int l) {
 #pragma unroll
         for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
@@ -1155,6 +1322,29 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ep[nh][mt][i] = fmaf(acc16[0][nh][mt][1][i], LO_INV, acc16[0][nh][mt][0][i]);
         ep_l = l;
+    };
+    if (rdbs::LAG == 0 || wave < 4) {
+        for (int l = 0; l < 4; ++l) {
+            const int nc = 4 + 2 * l;
+            zero_acc(0);
+            for (int c = 0; c < nc; c += 2) {
+                step_body(I0{}, MLead{}, c);
+                step_body(I1{}, MLead{}, c + 1);
+            }
+            layer_done(l);
+        }
+    } else {
+        for (int l = 0; l < 4; ++l) {
+            const int nc = 4 + 2 * l;
+            zero_acc(0);
+            step_body(I0{}, MFirst{}, 0);
+            for (int c = 1; c < nc - 1; c += 2) {
+                step_body(I1{}, MMid{}, c);
+                step_body(I0{}, MMid{}, c + 1);
+            }
+            step_body(I1{}, MLast{}, nc - 1);
+            layer_done(l);
+        }
     }
     // conv5: 12 steps of 64 output channels
     step_body5(I0{}, I1{}, I0{}, 0);
