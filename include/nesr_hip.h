@@ -59,7 +59,8 @@ enum {
     NESR_ERR_HIP = -2,      /* a HIP runtime call failed */
     NESR_ERR_STATE = -3,    /* weights missing / not finalized */
     NESR_ERR_NOMEM = -4,
-    NESR_ERR_RANGE = -5     /* f16-pair fp32 form or f16 form: a weight, input or activation was non-finite or beyond +-65504 */
+    NESR_ERR_RANGE = -5,    /* f16-pair fp32 form or f16 form: a weight, input or activation was non-finite or beyond +-65504 */
+    NESR_ERR_NOFIT = -6     /* nesr_jpeg_encode_u8: the file did not fit out_cap (what a caller reports after reading the status word) */
 };
 
 /*
@@ -479,6 +480,33 @@ int nesr_segment_enhance_u8(int device_id, const uint8_t* rgb_dev, int H, int W,
  * NESR_ERR_ARG before any device is touched.
  */
 int nesr_ensemble_u8(int device_id, const uint8_t* const* images_dev, int n, int H, int W, int C, uint8_t* out_dev, void* hip_stream);
+
+/*
+ * cv2.imwrite(path, frame) for a .jpg / .jpeg path, the last call of every reference entry point (standalone/direct_esrgan.py:169,
+ * nesr/nesr.py:646), as HIP kernels (csrc/jpeg.hip): the frame stays on the device and only the file crosses to the host.  cv2's
+ * defaults: baseline JPEG, quality 95, 4:2:0 for colour, Annex K quantisation tables scaled by libjpeg's quality rule, Annex K
+ * Huffman tables, libjpeg's islow integer FDCT, no restart markers, JFIF 1.01 header.  The integer pipeline is reproducible: the
+ * bytes equal libjpeg-turbo's (pinned against Pillow's build of it in tests/test_jpeg_spec.py through tests/jpeg_ref.py, the
+ * specification the kernels are compared with byte for byte; cv2 itself is absent).
+ *
+ * src_dev: [H, W, C] u8, C = 3 (order NESR_ORDER_RGB or NESR_ORDER_BGR: which channel comes first) or C = 1 (order ignored but
+ * checked), pixels of a row contiguous, rows src_row_bytes apart; 1 <= H, W <= 65535; quality 1 .. 100.
+ * scratch_dev: at least nesr_jpeg_scratch_bytes(H, W, C) bytes (0 for a shape it rejects), 16-byte aligned: about 350 bytes per
+ * 8 x 8 block (coefficients, bit lengths, and an unstuffed stream sized for the worst case of 208 bytes per block).
+ * out_dev[0 .. out_cap): the file.  out_len_dev (8-byte aligned): [0] = the bytes the whole file needs, [1] = 0 when it fits, 1 when
+ * out_cap is smaller -- then out_dev holds the first out_cap bytes, nothing at or beyond out_cap is ever written, and a caller runs
+ * again with out_cap >= [0] (or reports NESR_ERR_NOFIT).  Everything is enqueued on hip_stream: no allocation, no synchronisation, no
+ * copy; two runs give the same bytes.  A null pointer, a size outside 1 .. 65535, C not 1 or 3, an unknown order, quality outside
+ * 1 .. 100, a stride smaller than a row, a short or misaligned scratch: NESR_ERR_ARG before any device is touched.
+ *
+ * nesr_jpeg_header (host only): the bytes up to and including SOS -- SOI, APP0, DQT x 2 (x 1 for gray), SOF0, DHT x 4 (x 2), SOS: 623
+ * bytes for colour, 328 for gray.  *n is always set; buf[0 .. *n) is filled when cap >= *n.
+ */
+enum { NESR_ORDER_RGB = 0, NESR_ORDER_BGR = 1 };
+size_t nesr_jpeg_scratch_bytes(int H, int W, int C);
+int nesr_jpeg_header(int H, int W, int C, int quality, uint8_t* buf, int cap, int* n);
+int nesr_jpeg_encode_u8(int device_id, const uint8_t* src_dev, int64_t src_row_bytes, int H, int W, int C, int order, int quality, void* scratch_dev,
+                        size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
 
 /*
  * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind

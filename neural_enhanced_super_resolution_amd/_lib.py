@@ -26,6 +26,7 @@ ENSEMBLE_MAX = 8     # images per nesr_ensemble_u8
 ALPHA_NETWORK, ALPHA_LINEAR = 0, 1
 INPUT_12CH, INPUT_3CH_X4 = 0, 1
 STAGE_RECT = 13      # ints per tile of nesr_stage_tile_plan
+ORDER_RGB, ORDER_BGR = 0, 1
 
 # name -> (restype, argtypes); must list every symbol include/nesr_hip.h declares
 _c = ctypes
@@ -107,6 +108,10 @@ SIGNATURES = {
     "nesr_segment_enhance_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                            _c.c_void_p]),
     "nesr_ensemble_u8": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "nesr_jpeg_scratch_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int]),
+    "nesr_jpeg_header": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_jpeg_encode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                       _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
     "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
                                    _c.c_void_p]),
     "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,
@@ -146,7 +151,7 @@ _lib = None
 _lock = threading.Lock()
 
 
-ERR_ARG, ERR_RANGE = -1, -5
+ERR_ARG, ERR_RANGE, ERR_NOFIT = -1, -5, -6
 
 
 class NesrHipError(RuntimeError):
@@ -156,6 +161,15 @@ class NesrHipError(RuntimeError):
 class NesrRangeError(NesrHipError, FloatingPointError):
     """NESR_ERR_RANGE: the f16-pair fp32 form or the f16 form met a weight, input or activation that is non-finite or
     beyond +-65504 (the reference would carry it in float32; here it is an error, never a saturated image)."""
+
+
+class NesrNoFitError(NesrHipError):
+    """NESR_ERR_NOFIT: the JPEG file did not fit the output buffer; `needed` is the size the device reported."""
+
+    def __init__(self, needed, cap):
+        super().__init__(f"nesr_jpeg_encode_u8 failed ({ERR_NOFIT}): the file needs {needed} bytes, the buffer holds {cap}")
+        self.needed = needed
+        self.cap = cap
 
 
 def load():

@@ -1,0 +1,509 @@
+// Baseline JPEG encoder for gfx950: libjpeg's compressor as cv2.imwrite runs it by default (quality-scaled Annex K tables, 4:2:0 for
+// colour, islow integer FDCT, Annex K Huffman tables, no restart markers), byte for byte (tests/jpeg_ref.py is the specification).
+//
+// Passes, all on one stream, nothing returns to the host between them:
+//   header     the SOI .. SOS bytes (a kernel argument) into out
+//   transform  colour conversion, edge replication, h2v2 chroma downsampling, level shift, FDCT, quantisation; zigzag int16
+//              coefficients in scan order (Y00 Y01 Y10 Y11 Cb Cr per MCU, MCUs in raster order; gray: one block per MCU)
+//   lengths    bits per block (DC difference against the previous block of the component, AC run/size symbols), bits per chunk
+//   scan       exclusive scan of the chunk sums, 64-bit (a 16384 x 16384 noise frame exceeds 2^32 bits)
+//   zero       clears the words of the unstuffed stream the scan found to be needed
+//   emit       every block writes its bits at its offset; the first and last word of a block may be shared with its neighbours and
+//              are combined with atomicOr (disjoint bits: the result does not depend on the order), the words between are stored
+//   count      0xFF bytes per 4096-byte chunk of the unstuffed stream;  scan: their exclusive scan
+//   stuff      copies each chunk behind the header with 0x00 after each 0xFF
+//   finish     FF D9, the length word and the status word
+// No pass writes out[i] for i >= out_cap.
+#include "jpeg_kernels.h"
+#include "jpeg_tables.h"
+
+namespace nesr {
+namespace jpeg {
+
+namespace {
+
+// symbol -> (code << 8 | length), canonical codes from BITS / HUFFVAL; table 0 luminance, 1 chrominance
+struct DevTables {
+    uint32_t dc[2][16];
+    uint32_t ac[2][256];
+    uint8_t inv_zigzag[64];
+};
+
+constexpr void fill_codes(uint32_t* lut, const uint8_t* bits, const uint8_t* vals, int nvals) {
+    uint32_t code = 0;
+    int k = 0;
+    for (int length = 1; length <= 16; ++length) {
+        for (int i = 0; i < bits[length - 1] && k < nvals; ++i, ++k, ++code) lut[vals[k]] = (code << 8) | (uint32_t)length;
+        code <<= 1;
+    }
+}
+
+constexpr DevTables make_tables() {
+    DevTables t{};
+    const uint8_t dcv[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+    fill_codes(t.dc[0], DC_LUMA_BITS, dcv, 12);
+    fill_codes(t.dc[1], DC_CHROMA_BITS, dcv, 12);
+    fill_codes(t.ac[0], AC_LUMA_BITS, AC_LUMA_VALS, 162);
+    fill_codes(t.ac[1], AC_CHROMA_BITS, AC_CHROMA_VALS, 162);
+    for (int i = 0; i < 64; ++i) t.inv_zigzag[i] = INV_ZIGZAG[i];
+    return t;
+}
+
+__device__ const DevTables TABLES = make_tables();
+
+constexpr int TRANSFORM_THREADS = 256;
+constexpr int STRIP_BLOCKS = 96;           // blocks per workgroup of the transform: 16 colour MCUs, or 96 gray blocks of one block row
+constexpr int WS_PITCH = 72;               // int32 per block between the FDCT passes: rows of 9 (odd: no bank conflicts either way)
+
+// ---------------------------------------------------------------------------------------------------------------- transform
+// jfdctint.c, one 8-point pass.  first: outputs 0 and 4 are << 2, the others DESCALE(., 11); second: DESCALE(., 2) and DESCALE(., 15).
+template <bool FIRST>
+__device__ __forceinline__ void fdct8(const int d[8], int o[8]) {
+    constexpr int N = FIRST ? 11 : 15;
+    constexpr int R = 1 << (N - 1);
+    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
+    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
+    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    if (FIRST) {
+        o[0] = (t10 + t11) * 4;
+        o[4] = (t10 - t11) * 4;
+    } else {
+        o[0] = (t10 + t11 + 2) >> 2;
+        o[4] = (t10 - t11 + 2) >> 2;
+    }
+    int z1 = (t12 + t13) * 4433;
+    o[2] = (z1 + t13 * 6270 + R) >> N;
+    o[6] = (z1 - t12 * 15137 + R) >> N;
+    z1 = t4 + t7;
+    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+    const int z5 = (z3 + z4) * 9633;
+    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
+    z1 = -z1 * 7373;
+    z2 = -z2 * 20995;
+    z3 = -z3 * 16069 + z5;
+    z4 = -z4 * 3196 + z5;
+    o[7] = (a4 + z1 + z3 + R) >> N;
+    o[5] = (a5 + z2 + z4 + R) >> N;
+    o[3] = (a6 + z2 + z3 + R) >> N;
+    o[1] = (a7 + z1 + z4 + R) >> N;
+}
+
+struct TransformArgs {
+    const uint8_t* src;
+    int64_t stride;
+    int H, W, bgr;
+    int mcus_x;
+    uint16_t q[2][64];
+    int16_t* coef;
+};
+
+__device__ __forceinline__ void ycc(const uint8_t* p, int bgr, int& y, int& cb, int& cr) {
+    const int r = p[bgr ? 2 : 0], g = p[1], b = p[bgr ? 0 : 2];
+    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
+    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
+    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
+}
+
+// COLOR: blockIdx.x = strip of 16 MCUs, blockIdx.y = MCU row.  Gray: blockIdx.x = strip of 96 blocks, blockIdx.y = block row.
+template <bool COLOR>
+__global__ __launch_bounds__(TRANSFORM_THREADS) void jpeg_transform(const TransformArgs a) {
+    __shared__ uint8_t smp[6144];                          // colour: Y [16][256], Cb [8][128], Cr [8][128]; gray: [8][768]
+    __shared__ int ws[STRIP_BLOCKS * WS_PITCH];
+    __shared__ __attribute__((aligned(16))) int16_t outb[STRIP_BLOCKS * 64];
+    const int tid = threadIdx.x;
+    const int strip = blockIdx.x, row = blockIdx.y;
+    const int units = COLOR ? 16 : STRIP_BLOCKS;           // MCUs of a full strip
+    const int u0 = strip * units;
+    const int nu = min(units, a.mcus_x - u0);              // MCUs of this strip
+    const int H = a.H, W = a.W;
+
+    if (COLOR) {
+        const int half_rows = (H + 1) >> 1;                // chroma rows that have source rows
+        for (int q = tid; q < 8 * 128; q += TRANSFORM_THREADS) {
+            const int qy = q >> 7, qx = q & 127;
+            const int x0 = min(u0 * 16 + 2 * qx, W - 1), x1 = min(u0 * 16 + 2 * qx + 1, W - 1);
+            const int y0 = min(row * 16 + 2 * qy, H - 1), y1 = min(row * 16 + 2 * qy + 1, H - 1);
+            const uint8_t* r0 = a.src + (int64_t)y0 * a.stride;
+            const uint8_t* r1 = a.src + (int64_t)y1 * a.stride;
+            int y[4], cb[4], cr[4];
+            ycc(r0 + (int64_t)x0 * 3, a.bgr, y[0], cb[0], cr[0]);
+            ycc(r0 + (int64_t)x1 * 3, a.bgr, y[1], cb[1], cr[1]);
+            ycc(r1 + (int64_t)x0 * 3, a.bgr, y[2], cb[2], cr[2]);
+            ycc(r1 + (int64_t)x1 * 3, a.bgr, y[3], cb[3], cr[3]);
+            smp[(2 * qy) * 256 + 2 * qx] = (uint8_t)y[0];
+            smp[(2 * qy) * 256 + 2 * qx + 1] = (uint8_t)y[1];
+            smp[(2 * qy + 1) * 256 + 2 * qx] = (uint8_t)y[2];
+            smp[(2 * qy + 1) * 256 + 2 * qx + 1] = (uint8_t)y[3];
+            // chroma rows past the last downsampled row repeat THAT row (the source is padded to even height only); this differs
+            // from the Y rows exactly when H = 8 mod 16
+            const int cy = row * 8 + qy;
+            if (cy >= half_rows) {
+                const int e0 = min(2 * (half_rows - 1), H - 1), e1 = min(2 * (half_rows - 1) + 1, H - 1);
+                const uint8_t* s0 = a.src + (int64_t)e0 * a.stride;
+                const uint8_t* s1 = a.src + (int64_t)e1 * a.stride;
+                int t;
+                ycc(s0 + (int64_t)x0 * 3, a.bgr, t, cb[0], cr[0]);
+                ycc(s0 + (int64_t)x1 * 3, a.bgr, t, cb[1], cr[1]);
+                ycc(s1 + (int64_t)x0 * 3, a.bgr, t, cb[2], cr[2]);
+                ycc(s1 + (int64_t)x1 * 3, a.bgr, t, cb[3], cr[3]);
+            }
+            const int bias = 1 + (qx & 1);                 // strips start at even chroma columns
+            smp[4096 + qy * 128 + qx] = (uint8_t)((cb[0] + cb[1] + cb[2] + cb[3] + bias) >> 2);
+            smp[5120 + qy * 128 + qx] = (uint8_t)((cr[0] + cr[1] + cr[2] + cr[3] + bias) >> 2);
+        }
+    } else {
+        for (int q = tid; q < 8 * 768; q += TRANSFORM_THREADS) {
+            const int qy = q / 768, qx = q - qy * 768;
+            const int x = min(u0 * 8 + qx, W - 1), y = min(row * 8 + qy, H - 1);
+            smp[q] = a.src[(int64_t)y * a.stride + x];
+        }
+    }
+    __syncthreads();
+
+    // row pass: task t = (block, row)
+    for (int t = tid; t < STRIP_BLOCKS * 8; t += TRANSFORM_THREADS) {
+        const int b = t >> 3, r = t & 7;
+        const uint8_t* s;
+        if (COLOR) {
+            const int m = b / 6, k = b - m * 6;
+            s = k < 4 ? smp + ((k >> 1) * 8 + r) * 256 + m * 16 + (k & 1) * 8 : smp + 4096 + (k - 4) * 1024 + r * 128 + m * 8;
+        } else {
+            s = smp + r * 768 + b * 8;
+        }
+        int d[8], o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d[i] = (int)s[i] - 128;
+        fdct8<true>(d, o);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ws[t * 9 + i] = o[i];
+    }
+    __syncthreads();
+
+    // column pass and quantisation: task t = (block, column)
+    const int blocks_w = (W + 7) >> 3, blocks_h = (H + 7) >> 3;
+    for (int t = tid; t < STRIP_BLOCKS * 8; t += TRANSFORM_THREADS) {
+        const int b = t >> 3, c = t & 7;
+        int comp = 0;
+        bool dummy = false;
+        if (COLOR) {
+            const int m = b / 6, k = b - m * 6;
+            comp = k < 4 ? 0 : 1;
+            dummy = k < 4 && ((u0 + m) * 2 + (k & 1) >= blocks_w || row * 2 + (k >> 1) >= blocks_h);
+        }
+        int d[8], o[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) d[r] = ws[b * WS_PITCH + r * 9 + c];
+        fdct8<false>(d, o);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int n = r * 8 + c;
+            const unsigned Q = a.q[comp][n];
+            const unsigned mag = ((unsigned)abs(o[r]) + 4u * Q) / (8u * Q);      // exact integer division
+            outb[b * 64 + TABLES.inv_zigzag[n]] = dummy ? (int16_t)0 : (int16_t)(o[r] < 0 ? -(int)mag : (int)mag);
+        }
+    }
+    __syncthreads();
+    if (COLOR) {
+        // dummy Y blocks: no AC, the DC of the block coded just before them in the MCU (which may itself be a dummy)
+        if (tid < 16) {
+            for (int k = 1; k < 4; ++k)
+                if ((u0 + tid) * 2 + (k & 1) >= blocks_w || row * 2 + (k >> 1) >= blocks_h) outb[(tid * 6 + k) * 64] = outb[(tid * 6 + k - 1) * 64];
+        }
+        __syncthreads();
+    }
+    const int per = COLOR ? 6 : 1;
+    const int64_t first = ((int64_t)row * a.mcus_x + u0) * per;       // first block of the strip in scan order
+    uint4* dst = reinterpret_cast<uint4*>(a.coef + first * 64);
+    const uint4* from = reinterpret_cast<const uint4*>(outb);
+    for (int i = tid; i < nu * per * 8; i += TRANSFORM_THREADS) dst[i] = from[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------------- entropy coding
+__device__ __forceinline__ int bit_length(int v) { return 32 - __clz(v); }      // v >= 0
+
+// The symbols of one block in coding order: sink(code, length) for each Huffman code and each run of extra bits.
+template <typename Sink>
+__device__ __forceinline__ void code_block(const int16_t* coef, int prev_dc, const uint32_t* dc_lut, const uint32_t* ac_lut, Sink&& sink) {
+    const uint4* p = reinterpret_cast<const uint4*>(coef);
+    int run = 0;
+#pragma unroll 1
+    for (int g = 0; g < 8; ++g) {
+        const uint4 v = p[g];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = (int)(int16_t)(w[j >> 1] >> ((j & 1) * 16));
+            if (g == 0 && j == 0) {
+                const int d = c - prev_dc;
+                const int cat = bit_length(abs(d));
+                const uint32_t e = dc_lut[cat];
+                sink(e >> 8, (int)(e & 255));
+                if (cat) sink((uint32_t)(d < 0 ? d - 1 : d) & ((1u << cat) - 1u), cat);
+                continue;
+            }
+            if (c == 0) {
+                ++run;
+                continue;
+            }
+            while (run > 15) {
+                const uint32_t e = ac_lut[0xF0];
+                sink(e >> 8, (int)(e & 255));
+                run -= 16;
+            }
+            const int size = bit_length(abs(c));
+            const uint32_t e = ac_lut[(run << 4) | size];
+            sink(e >> 8, (int)(e & 255));
+            sink((uint32_t)(c < 0 ? c - 1 : c) & ((1u << size) - 1u), size);
+            run = 0;
+        }
+    }
+    if (run) {
+        const uint32_t e = ac_lut[0];
+        sink(e >> 8, (int)(e & 255));
+    }
+}
+
+// block n of the scan: its Huffman table and the block that holds the DC predictor (-1: the predictor is 0)
+__device__ __forceinline__ void block_kind(int64_t n, bool color, int& table, int64_t& prev) {
+    if (!color) {
+        table = 0;
+        prev = n - 1;
+        return;
+    }
+    const int k = (int)(n % 6);
+    table = k < 4 ? 0 : 1;
+    prev = k == 0 ? n - 3 : (k < 4 ? n - 1 : n - 6);      // Y00 follows the last MCU's Y11; Cb and Cr their own
+}
+
+__device__ __forceinline__ void load_luts(uint32_t* dc, uint32_t* ac) {
+    for (int i = threadIdx.x; i < 32; i += blockDim.x) dc[i] = TABLES.dc[i >> 4][i & 15];
+    for (int i = threadIdx.x; i < 512; i += blockDim.x) ac[i] = TABLES.ac[i >> 8][i & 255];
+}
+
+__global__ __launch_bounds__(BLOCKS_PER_GROUP) void jpeg_lengths(const int16_t* coef, int64_t nblocks, int color, uint32_t* len, uint64_t* chunk) {
+    __shared__ uint32_t dc[32], ac[512];
+    __shared__ uint32_t total;
+    load_luts(dc, ac);
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const int64_t n = (int64_t)blockIdx.x * BLOCKS_PER_GROUP + threadIdx.x;
+    if (n < nblocks) {
+        int table;
+        int64_t prev;
+        block_kind(n, color != 0, table, prev);
+        const int prev_dc = prev >= 0 ? (int)coef[prev * 64] : 0;
+        uint32_t bits = 0;
+        code_block(coef + n * 64, prev_dc, dc + table * 16, ac + table * 256, [&](uint32_t, int l) { bits += (uint32_t)l; });
+        len[n] = bits;
+        atomicAdd(&total, bits);                           // integers: any order gives the same sum
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) chunk[blockIdx.x] = total;
+}
+
+// Exclusive scan of data[0 .. n) in place by one workgroup of 1024; n = *n_dev when n_dev is given.  *total_out = the sum.
+__global__ __launch_bounds__(1024) void jpeg_scan64(uint64_t* data, int64_t n_host, const uint64_t* n_dev, uint64_t* total_out) {
+    __shared__ uint64_t buf[2][1024];
+    const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
+    const int tid = threadIdx.x;
+    uint64_t carry = 0;
+    for (int64_t base = 0; base < n; base += 1024) {
+        const int64_t i = base + tid;
+        const uint64_t v = i < n ? data[i] : 0;
+        int cur = 0;
+        buf[0][tid] = v;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {
+            const uint64_t x = buf[cur][tid] + (tid >= d ? buf[cur][tid - d] : 0);
+            buf[cur ^ 1][tid] = x;
+            cur ^= 1;
+            __syncthreads();
+        }
+        const uint64_t incl = buf[cur][tid];
+        const uint64_t sum = buf[cur][1023];
+        if (i < n) data[i] = carry + incl - v;
+        carry += sum;
+        __syncthreads();
+    }
+    if (tid == 0) *total_out = carry;
+}
+
+// clears the words of the stream that hold total_bits (rounded up to a whole chunk of the stuffing passes, within the capacity)
+__global__ __launch_bounds__(256) void jpeg_zero(uint4* stream, const uint64_t* total_bits, int64_t cap_bytes) {
+    int64_t bytes = (int64_t)((*total_bits + 7) >> 3);
+    bytes = (bytes + STUFF_CHUNK - 1) / STUFF_CHUNK * STUFF_CHUNK;
+    if (bytes > cap_bytes) bytes = cap_bytes;
+    const int64_t n = bytes >> 4;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) stream[i] = make_uint4(0, 0, 0, 0);
+}
+
+struct BitWriter {
+    uint32_t* stream;
+    int64_t word, words;       // next word, capacity
+    uint64_t acc;              // the low `n` bits are pending
+    int n;
+    bool shared;               // the next word to leave may hold bits of the block before
+
+    __device__ __forceinline__ void put(uint32_t code, int length) {
+        acc = (acc << length) | code;
+        n += length;
+        if (n >= 32) {
+            const uint32_t w = (uint32_t)(acc >> (n - 32));
+            n -= 32;
+            acc &= (1ull << n) - 1ull;
+            if (word < words) {
+                if (shared) atomicOr(stream + word, __builtin_bswap32(w));
+                else stream[word] = __builtin_bswap32(w);
+            }
+            shared = false;
+            ++word;
+        }
+    }
+    __device__ __forceinline__ void finish() {            // the last, partial word: shared with the block after
+        if (n > 0 && word < words) atomicOr(stream + word, __builtin_bswap32((uint32_t)(acc << (32 - n))));
+    }
+};
+
+__global__ __launch_bounds__(BLOCKS_PER_GROUP) void jpeg_emit(const int16_t* coef, int64_t nblocks, int color, const uint32_t* len, const uint64_t* chunk,
+                                                               uint32_t* stream, int64_t stream_words, uint64_t* meta) {
+    __shared__ uint32_t dc[32], ac[512];
+    __shared__ uint32_t sc[2][BLOCKS_PER_GROUP];
+    load_luts(dc, ac);
+    const int tid = threadIdx.x;
+    const int64_t n = (int64_t)blockIdx.x * BLOCKS_PER_GROUP + tid;
+    const uint32_t mine = n < nblocks ? len[n] : 0;
+    int cur = 0;
+    sc[0][tid] = mine;
+    __syncthreads();
+    for (int d = 1; d < BLOCKS_PER_GROUP; d <<= 1) {
+        const uint32_t x = sc[cur][tid] + (tid >= d ? sc[cur][tid - d] : 0);
+        sc[cur ^ 1][tid] = x;
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (n >= nblocks) return;
+    const uint64_t pos = chunk[blockIdx.x] + (uint64_t)(sc[cur][tid] - mine);
+    int table;
+    int64_t prev;
+    block_kind(n, color != 0, table, prev);
+    const int prev_dc = prev >= 0 ? (int)coef[prev * 64] : 0;
+    BitWriter bw{stream, (int64_t)(pos >> 5), stream_words, 0, (int)(pos & 31), true};
+    code_block(coef + n * 64, prev_dc, dc + table * 16, ac + table * 256, [&](uint32_t c, int l) { bw.put(c, l); });
+    if (n == nblocks - 1) {                               // pad the last byte with 1-bits
+        const uint64_t end = pos + mine;
+        const int pad = (int)((8 - (end & 7)) & 7);
+        if (pad) bw.put((1u << pad) - 1u, pad);
+        const uint64_t bytes = (end + 7) >> 3;
+        meta[0] = bytes;
+        meta[1] = (bytes + STUFF_CHUNK - 1) / STUFF_CHUNK;
+    }
+    bw.finish();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- byte stuffing
+__device__ __forceinline__ int count_ff(uint32_t w) {
+    return (int)((w & 255) == 255) + (int)(((w >> 8) & 255) == 255) + (int)(((w >> 16) & 255) == 255) + (int)((w >> 24) == 255);
+}
+
+// bytes of the stream past meta[0] are zero (jpeg_zero clears whole chunks), so a chunk is counted without looking at its end
+__global__ __launch_bounds__(256) void jpeg_count_ff(const uint4* stream, const uint64_t* meta, uint64_t* ff) {
+    __shared__ uint32_t total;
+    const int64_t chunks = (int64_t)meta[1];
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        if (threadIdx.x == 0) total = 0;
+        __syncthreads();
+        const uint4 v = stream[c * (STUFF_CHUNK / 16) + threadIdx.x];
+        const int k = count_ff(v.x) + count_ff(v.y) + count_ff(v.z) + count_ff(v.w);
+        if (k) atomicAdd(&total, (uint32_t)k);
+        __syncthreads();
+        if (threadIdx.x == 0) ff[c] = total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_stuff(const uint4* stream, const uint64_t* meta, const uint64_t* ff, uint8_t* out, uint64_t out_cap, int header_bytes) {
+    __shared__ uint32_t sc[2][256];
+    __shared__ uint8_t staged[2 * STUFF_CHUNK];
+    const int tid = threadIdx.x;
+    const int64_t bytes = (int64_t)meta[0], chunks = (int64_t)meta[1];
+    for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+        const uint4 v = stream[c * (STUFF_CHUNK / 16) + tid];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const int64_t at = c * STUFF_CHUNK + tid * 16;
+        const int valid = (int)max((int64_t)0, min((int64_t)16, bytes - at));
+        const int k = count_ff(v.x) + count_ff(v.y) + count_ff(v.z) + count_ff(v.w);     // bytes past `bytes` are zero
+        int cur = 0;
+        sc[0][tid] = (uint32_t)k;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const uint32_t x = sc[cur][tid] + (tid >= d ? sc[cur][tid - d] : 0);
+            sc[cur ^ 1][tid] = x;
+            cur ^= 1;
+            __syncthreads();
+        }
+        int o = tid * 16 + (int)sc[cur][tid] - k;
+        const int chunk_out = (int)min((int64_t)STUFF_CHUNK, bytes - c * STUFF_CHUNK) + (int)sc[cur][255];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            if (j < valid) {
+                const uint8_t b = (uint8_t)(w[j >> 2] >> ((j & 3) * 8));
+                staged[o++] = b;
+                if (b == 255) staged[o++] = 0;
+            }
+        }
+        __syncthreads();
+        const uint64_t base = (uint64_t)header_bytes + (uint64_t)(c * STUFF_CHUNK) + ff[c];
+        for (int i = tid; i < chunk_out; i += 256)
+            if (base + (uint64_t)i < out_cap) out[base + i] = staged[i];
+        __syncthreads();
+    }
+}
+
+__global__ void jpeg_header(const Header h, int n, uint8_t* out, uint64_t out_cap) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (uint64_t)i < out_cap) out[i] = h.bytes[i];
+}
+
+__global__ void jpeg_finish(const uint64_t* meta, uint8_t* out, uint64_t out_cap, int header_bytes, uint64_t* out_len) {
+    const uint64_t end = (uint64_t)header_bytes + meta[0] + meta[2];
+    if (end < out_cap) out[end] = 0xFF;
+    if (end + 1 < out_cap) out[end + 1] = 0xD9;
+    out_len[0] = end + 2;
+    out_len[1] = end + 2 > out_cap ? 1 : 0;
+}
+
+}  // namespace
+
+hipError_t launch_encode(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s) {
+    hipLaunchKernelGGL(jpeg_header, dim3((a.header_bytes + 255) / 256), dim3(256), 0, s, h, a.header_bytes, a.out, a.out_cap);
+    TransformArgs t{};
+    t.src = a.src;
+    t.stride = a.src_stride;
+    t.H = p.H;
+    t.W = p.W;
+    t.bgr = a.bgr;
+    t.mcus_x = p.mcus_x;
+    for (int i = 0; i < 64; ++i) {
+        t.q[0][i] = a.q[0][i];
+        t.q[1][i] = a.q[1][i];
+    }
+    t.coef = a.coef;
+    const bool color = p.C == 3;
+    // blockIdx.y carries the MCU row: at most 65535 / 8 + 1 rows, within the grid limit
+    if (color) hipLaunchKernelGGL(jpeg_transform<true>, dim3((p.mcus_x + 15) / 16, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    else hipLaunchKernelGGL(jpeg_transform<false>, dim3((p.mcus_x + STRIP_BLOCKS - 1) / STRIP_BLOCKS, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    hipLaunchKernelGGL(jpeg_lengths, dim3((unsigned)p.nchunks), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, (int)color, a.len, a.chunk);
+    hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.chunk, p.nchunks, (const uint64_t*)nullptr, a.meta + 3);
+    const unsigned wide = (unsigned)(p.stuff_chunks < 4096 ? p.stuff_chunks : 4096);
+    hipLaunchKernelGGL(jpeg_zero, dim3(wide), dim3(256), 0, s, reinterpret_cast<uint4*>(a.stream), a.meta + 3, p.stream_bytes);
+    hipLaunchKernelGGL(jpeg_emit, dim3((unsigned)p.nchunks), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, (int)color, a.len, a.chunk, a.stream,
+                       p.stream_bytes / 4, a.meta);
+    hipLaunchKernelGGL(jpeg_count_ff, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff);
+    hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.ff, (int64_t)0, a.meta + 1, a.meta + 2);
+    hipLaunchKernelGGL(jpeg_stuff, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff, a.out, a.out_cap, a.header_bytes);
+    hipLaunchKernelGGL(jpeg_finish, dim3(1), dim3(1), 0, s, a.meta, a.out, a.out_cap, a.header_bytes, a.out_len);
+    return hipGetLastError();
+}
+
+}  // namespace jpeg
+}  // namespace nesr

@@ -8,9 +8,10 @@
   SuperResolutionPipeline._segment_and_enhance, image half: mask resize, dilate, unsharp    nesr/nesr.py:726-747
   SuperResolutionPipeline._ensemble_results  Lanczos alignment, float32 mean, truncation    nesr/nesr.py:1033-1054
   enhance_image's no-model step              cv2.resize(INTER_CUBIC)                         nesr/nesr.py:597-605
+  enhance_image's last call                  cv2.imwrite(path.jpg): baseline JPEG (PINNED)   nesr/nesr.py:639-646
   (_process_with_tiling's Lanczos paste and the 12-channel builder's 3x3 blur use the same functions: nesr_adapter.py)
 
-PARITY UNPINNED, all of it: cv2 is not installed here or on the GPU box and the reference holds no output of any of
+PARITY UNPINNED, all of it but the JPEG file (encode_jpeg_u8: libjpeg's integer pipeline, byte for byte): cv2 is not installed here or on the GPU box and the reference holds no output of any of
 these calls, so each function restates OpenCV's documented algorithm (8-bit paths in OpenCV's fixed point: 11-bit
 resize coefficients, 8-bit Gaussian kernels, integer non-local-means weights; Lab conversions in float with rounding
 where OpenCV uses lookup tables -- expect +-1 LSB there).  oracle/cv2_ref.py restates them again, independently, in numpy:
@@ -808,3 +809,70 @@ def ensemble_results(images, use_hip=None):
     for im in aligned:
         acc = acc + im.to(torch.float32) * wgt
     return acc.to(torch.uint8)
+
+
+# ----------------------------------------------------------------------------------------------- JPEG
+def _jpeg_encode_hip(frame, quality, bgr, cap):
+    """One run of nesr_jpeg_encode_u8 (csrc/jpeg.hip) into a buffer of `cap` bytes -> the file's bytes; NesrNoFitError (with the
+    size the device reported) when the file needs more.  Two transfers come back: the 16 bytes of the length and status words,
+    then exactly the file."""
+    from . import _lib
+    h, w, c = frame.shape
+    lib = _lib.load()
+    need = int(lib.nesr_jpeg_scratch_bytes(h, w, c))
+    scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
+    out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
+    words = torch.empty(2, dtype=torch.int64, device=frame.device)
+    _hip_call(frame, "nesr_jpeg_encode_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, int(quality),
+              _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+    length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
+    if status != 0:
+        raise _lib.NesrNoFitError(length, cap)
+    return out[:length].cpu().numpy().tobytes()               # D2H: the file
+
+
+def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
+    """cv2.imwrite(path.jpg, frame)'s bytes (standalone/direct_esrgan.py:169, nesr/nesr.py:646; cv2's defaults: quality 95, 4:2:0,
+    baseline, standard Huffman tables) for an [H, W, 3] (order "rgb" or "bgr": the channel that comes first), [H, W, 1] or [H, W]
+    uint8 frame -> bytes.
+
+    A uint8 tensor on the ROCm device goes through the HIP kernels (csrc/jpeg.hip, nesr_jpeg_encode_u8), a row-strided window
+    (frame[y0:y1, x0:x1]) as it is: the frame stays on the device and only the length words and the file come back.  The output
+    buffer starts at H W C // 2 + 4096 bytes; when the file does not fit, the call runs once more at the size the device reported.
+    use_hip=False, a CPU tensor or an ndarray: Pillow's libjpeg-turbo, whose bytes the kernels reproduce (tests/jpeg_ref.py is
+    pinned against both); without Pillow that raises -- there is no third route."""
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"encode_jpeg_u8: order must be 'rgb' or 'bgr', got {order!r}")
+    if not 1 <= int(quality) <= 100:
+        raise ValueError(f"encode_jpeg_u8: quality {quality} outside 1..100")
+    is_tensor = isinstance(frame, torch.Tensor)
+    if frame.ndim == 2:
+        frame = frame[:, :, None]
+    if frame.ndim != 3 or frame.shape[2] not in (1, 3) or min(frame.shape) < 1 or max(frame.shape[:2]) > 65535 or str(frame.dtype).split(".")[-1] != "uint8":
+        raise ValueError(f"encode_jpeg_u8: an [H, W, 3], [H, W, 1] or [H, W] uint8 frame of at most 65535 x 65535 pixels, got {frame.dtype} "
+                         f"{tuple(frame.shape)}")
+    fits = is_tensor and _hip_default(frame)
+    if use_hip is None:
+        use_hip = fits
+    if use_hip:
+        from . import _lib
+        if not fits:
+            raise ValueError(f"encode_jpeg_u8: the HIP kernels take a uint8 tensor on the ROCm device, got {frame.dtype} on "
+                             f"{frame.device if is_tensor else 'the host'}")
+        src = frame if _rows_ok(frame, (1, 3)) else frame.contiguous()
+        h, w, c = src.shape
+        try:
+            return _jpeg_encode_hip(src, quality, order == "bgr", h * w * c // 2 + 4096)
+        except _lib.NesrNoFitError as e:
+            return _jpeg_encode_hip(src, quality, order == "bgr", e.needed)
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("encode_jpeg_u8: the host route needs Pillow (the device route: a uint8 tensor on the ROCm device)") from e
+    import io
+    arr = frame.cpu().numpy() if is_tensor else frame
+    arr = arr[:, :, 0] if arr.shape[2] == 1 else (arr[:, :, ::-1] if order == "bgr" else arr)
+    buf = io.BytesIO()
+    import numpy as np
+    Image.fromarray(np.ascontiguousarray(arr)).save(buf, format="JPEG", quality=int(quality))
+    return buf.getvalue()

@@ -326,7 +326,8 @@ def realesrganer_stage(up):
 
 
 def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", preprocess=None, postprocess=None,
-                       trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None):
+                       trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None,
+                       encode=None):
     """The iteration loop of SuperResolutionPipeline.enhance_image (nesr.py:516-633):
 
         for iteration in range(config['iterations']):           nesr.py:516
@@ -352,7 +353,13 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     that the network really ran -- and, when a segmenter, an extra upscaler or upscaler=None is in use, "segmented" and
     "ensemble_n" (the results that were combined; 0: the bicubic step).  With those arguments left out the loop, its result and
     its trace are what they were without them.  use_hip goes to every stage (None: the HIP kernels where they apply; False: the
-    torch chains, the same bits)."""
+    torch chains, the same bits).  encode="jpeg" or ("jpeg", quality): what enhance_image writes in the end (cv2.imwrite,
+    nesr.py:639-646) -- the bytes of the final RGB frame's JPEG file (quality 95 unless given) instead of the ndarray, encoded on the
+    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home."""
+    if encode is not None:
+        kind, quality = (encode, 95) if isinstance(encode, str) else tuple(encode)
+        if kind != "jpeg":
+            raise ValueError(f"enhance_iterations: encode must be None, 'jpeg' or ('jpeg', quality), got {encode!r}")
     cfg = {"iterations": 3, "upscale_factor": 2.0, "denoise_level": 0.5, "adaptive_sharpening": True}
     cfg.update(config or {})
     staged = segmenter is not None or len(extra_upscalers) > 0 or upscaler is None
@@ -403,6 +410,13 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
         check = getattr(extra, "check_range", None)
         if check is not None:
             check()
+    if encode is not None:
+        from . import imgproc
+        data = imgproc.encode_jpeg_u8(current, quality, order="rgb")
+        check = getattr(getattr(upscaler, "model", None), "check_range", None)
+        if check is not None and isinstance(current, torch.Tensor):
+            check()
+        return data
     if not isinstance(current, torch.Tensor):
         return current
     if upscaler is None:

@@ -577,7 +577,7 @@ class RealESRGANer:
             paste_tiles_u8(out, pst, dst_u8, flip_rgb=True, round_nearest=True, through_fp16=bool(self.half))
 
     @torch.no_grad()
-    def _enhance_u8_tiles_fused(self, img, resize_to=None):
+    def _enhance_u8_tiles_fused(self, img, resize_to=None, keep=False):
         if self._multi():
             out = self._enhance_u8_tiles_fused_devices(img)
             return out if resize_to is None else self._resize_on_host_route(out, resize_to)
@@ -589,6 +589,8 @@ class RealESRGANer:
         self.tiles_u8_on_device(frame, _tiling.windows(tiles), _tiling.canvas_pastes(tiles, w * s), canvas)
         if resize_to is not None:
             canvas = self._resize_u8_on_device(canvas, resize_to)
+        if keep:
+            return canvas
         host = torch.empty(canvas.shape, dtype=torch.uint8, pin_memory=True)          # (the caching host allocator recycles these)
         self._frame_to_host(canvas, host)
         torch.cuda.current_stream(self.device).synchronize()
@@ -596,10 +598,11 @@ class RealESRGANer:
         return host.numpy()
 
     @torch.no_grad()
-    def _enhance_u8_on_device(self, img, resize_to=None):
-        """resize_to = (out_h, out_w): enhance(outscale=...)'s Lanczos resize, on the device before the one device-to-host copy."""
+    def _enhance_u8_on_device(self, img, resize_to=None, keep=False):
+        """resize_to = (out_h, out_w): enhance(outscale=...)'s Lanczos resize, on the device before the one device-to-host copy.
+        keep: the quantised frame stays on the device and is returned as a tensor (_enhance_once)."""
         if self._u8_tiles_fused_ok(img.shape[0], img.shape[1]) and (img.shape[0] > self.tile_size or img.shape[1] > self.tile_size):
-            return self._enhance_u8_tiles_fused(img, resize_to)
+            return self._enhance_u8_tiles_fused(img, resize_to, keep)
         x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)            # H2D: uint8 HWC BGR
         x = normalize_u8_on_device(x.permute(2, 0, 1).flip(0)).unsqueeze(0)          # BGR->RGB, /255 (f32), HWC->NCHW
         self._pad_on_device(x)
@@ -609,6 +612,8 @@ class RealESRGANer:
         q = q.contiguous()
         if resize_to is not None:
             q = self._resize_u8_on_device(q, resize_to)
+        if keep:
+            return q
         host = self._frame_to_host(q).numpy()
         self._check_range()
         return host
@@ -799,7 +804,7 @@ class RealESRGANer:
         return host, img_mode
 
     @torch.no_grad()
-    def _enhance_frame_on_device(self, img, resize_to=None, alpha_upsampler="realesrgan"):
+    def _enhance_frame_on_device(self, img, resize_to=None, alpha_upsampler="realesrgan", keep=False):
         """enhance() for the frames enhance_float takes, without its host passes: the uint8 / uint16 frame is uploaded as it is
         and goes through _frame_through, where _pad_on_device and _run() evaluate it as they do for every frame (padding, tiles,
         ragged batches, devices= lanes; a second time for the alpha plane); outscale's resize follows (resize_to), and one copy
@@ -818,6 +823,8 @@ class RealESRGANer:
             else:       # 16 bit keeps the torch chain, for the reason given at _resize_on_host_route
                 q3 = imgproc.lanczos4_resize(q3.to(torch.int32) & 0xFFFF, resize_to[0], resize_to[1], use_hip=False).to(torch.int16)
             q = q3[:, :, 0] if q.dim() == 2 else q3
+        if keep:
+            return q, img_mode
         host = frame_io.frame_to_numpy(self._frame_to_host(q.contiguous()))
         self._check_range()
         return host, img_mode
@@ -873,15 +880,43 @@ class RealESRGANer:
         A forward whose persistent dense-block launch gave up waiting (another process's kernels kept its workgroups off the
         device: NesrHipError from the status check, never a silently wrong image) is evaluated once more: the context has
         switched to per-layer launches by then (include/nesr_hip.h, nesr_set_fused)."""
+        return self._again_if_gave_up(lambda: self._enhance_once(img, outscale, alpha_upsampler))
+
+    @staticmethod
+    def _again_if_gave_up(evaluate):
         try:
-            return self._enhance_once(img, outscale, alpha_upsampler)
+            return evaluate()
         except NesrHipError as e:
             if not _is_gave_up(e):
                 raise
             warnings.warn(f"{e}; evaluating the frame again with per-layer launches")
-            return self._enhance_once(img, outscale, alpha_upsampler)
+            return evaluate()
 
-    def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan"):
+    @torch.no_grad()
+    def enhance_jpeg(self, img, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance() followed by cv2.imwrite(path.jpg, output) (standalone/direct_esrgan.py:163-169), the file as bytes:
+        (bytes, img_mode).  The quantised frame of enhance()'s route stays on the device and is encoded there
+        (imgproc.encode_jpeg_u8: csrc/jpeg.hip); only the file comes home.  The bytes are those of the JPEG file of enhance(img)'s
+        frame.  8-bit BGR and gray frames; a BGRA or 16-bit frame raises ValueError (cv2.imwrite would drop the alpha plane or the
+        depth without a word)."""
+        from . import imgproc
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+            kind = f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}"
+            raise ValueError(f"enhance_jpeg: an 8-bit BGR [H, W, 3] or gray [H, W] frame, got {kind} (a JPEG file holds neither alpha nor 16 bits)")
+
+        def evaluate():
+            q, img_mode = self._enhance_once(img, outscale, alpha_upsampler, keep=True)
+            if not isinstance(q, torch.Tensor):          # a route that assembles its frame on the host (several devices, no HIP model)
+                q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device)
+            data = imgproc.encode_jpeg_u8(q, quality, order="bgr")
+            self._check_range()                          # after the copy that waited for the stream, as enhance() does
+            return data, img_mode
+
+        return self._again_if_gave_up(evaluate)
+
+    def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan", keep=False):
+        """keep: the routes that hold the finished frame on the device return it there (a uint8 tensor, not yet range-checked)
+        instead of copying it home; the others return their ndarray as always."""
         if self.last_bands is not None:
             self.last_bands = None
         h_input, w_input = img.shape[0:2]
@@ -892,6 +927,7 @@ class RealESRGANer:
         if outscale is not None and outscale != float(self.scale):
             resize_to = (int(h_input * outscale), int(w_input * outscale))
         on_device = resize_to if HIP_RESIZE else None     # the 8-bit routes resize before their one device-to-host copy
+        kept = {"keep": True} if keep else {}            # (left out otherwise: the routes are called as they always were)
 
         if self._fused_u8_ok(img) and not plain_alpha:
             # /255, BGR->RGB, network, clamp, RGB->BGR, x255, round -- all inside the HIP path
@@ -904,16 +940,19 @@ class RealESRGANer:
                 self.last_bands = plan[1]
             if on_device is not None:
                 y = self._resize_u8_on_device(y, on_device)
-            output = self._frame_to_host(y).numpy()
-            self._check_range(0 if plan is None else None)     # (banded: every lane's context before the frame is used)
+            if keep:
+                output = y
+            else:
+                output = self._frame_to_host(y).numpy()
+                self._check_range(0 if plan is None else None)     # (banded: every lane's context before the frame is used)
             img_mode = "RGB"
             done = on_device is not None
         elif self._u8_on_device_ok(img):
-            output = self._enhance_u8_on_device(img, on_device)
+            output = self._enhance_u8_on_device(img, on_device, **kept)
             img_mode = "RGB"
             done = on_device is not None
         elif self._device_frame_ok(img):
-            output, img_mode = self._enhance_frame_on_device(img, resize_to, alpha_upsampler)
+            output, img_mode = self._enhance_frame_on_device(img, resize_to, alpha_upsampler, **kept)
             done = resize_to is not None
         else:
             output_img, img_mode, max_range = self.enhance_float(img, alpha_upsampler)
@@ -924,5 +963,7 @@ class RealESRGANer:
             done = False
 
         if resize_to is not None and not done:
+            if isinstance(output, torch.Tensor):
+                output = output.cpu().numpy()
             output = self._resize_on_host_route(output, resize_to)
         return output, img_mode
