@@ -60,7 +60,9 @@ enum {
     NESR_ERR_STATE = -3,    /* weights missing / not finalized */
     NESR_ERR_NOMEM = -4,
     NESR_ERR_RANGE = -5,    /* f16-pair fp32 form or f16 form: a weight, input or activation was non-finite or beyond +-65504 */
-    NESR_ERR_NOFIT = -6     /* nesr_jpeg_encode_u8: the file did not fit out_cap (what a caller reports after reading the status word) */
+    NESR_ERR_NOFIT = -6,    /* nesr_jpeg_encode_u8: the file did not fit out_cap (what a caller reports after reading the status word) */
+    NESR_ERR_UNSUPPORTED = -7, /* nesr_jpeg_parse: a valid JPEG file outside the supported list */
+    NESR_ERR_BADFILE = -8   /* nesr_jpeg_parse: malformed segments; nesr_jpeg_decode_u8: a scan the device rejected (the status word) */
 };
 
 /*
@@ -507,6 +509,60 @@ size_t nesr_jpeg_scratch_bytes(int H, int W, int C);
 int nesr_jpeg_header(int H, int W, int C, int quality, uint8_t* buf, int cap, int* n);
 int nesr_jpeg_encode_u8(int device_id, const uint8_t* src_dev, int64_t src_row_bytes, int H, int W, int C, int order, int quality, void* scratch_dev,
                         size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
+
+/*
+ * cv2.imread(path) for a .jpg / .jpeg path, the first call of every reference entry point (nesr/nesr.py:661-666,
+ * standalone/direct_esrgan.py:130), as HIP kernels (csrc/jpeg_decode.hip): the file's bytes go up, a tenth of the frame, and the
+ * frame is born on the device.  libjpeg-turbo's default decompressor (JDCT_ISLOW, fancy upsampling, no merged upsampling) pixel for
+ * pixel (tests/jpeg_decode_ref.py is the specification, pinned against Pillow's build of the library in
+ * tests/test_jpeg_decode_spec.py).  EXIF orientation is not applied: that is cv2.IMREAD_UNCHANGED's behaviour, and a gray file gives
+ * one channel as it does there.
+ *
+ * Supported: SOF0 / SOF1 Huffman, 8 bits, one interleaved scan over all components, 1 component or 3 (YCbCr), sampling 1x1 gray,
+ * 4:4:4, 4:2:2 (h2v1), 4:2:0 (h2v2), 8-bit DQT, any DHT, any DRI; APPn and COM are skipped.  A valid file outside that list
+ * (progressive, arithmetic, 12 bits, 4 components, Adobe transform 0, other sampling, several scans, 16-bit DQT) is
+ * NESR_ERR_UNSUPPORTED; malformed segments are NESR_ERR_BADFILE.
+ *
+ * nesr_jpeg_parse (host only; replaces the header half of cv2.imread): walks the marker segments of file[0 .. n) up to SOS and fills
+ * *info; it never reads the scan.  The Huffman tables are resolved per component (dc[c], ac[c] are the tables component c's scan
+ * selector names) as decode look-up tables: look[next 9 bits] = length << 8 | symbol for codes of at most 9 bits (0 otherwise), and
+ * libjpeg's maxcode / valoff / vals for the longer ones.  q[c]: component c's quantisation table in natural order.  hs, vs: the luma
+ * sampling factors (1, 1 for gray, whose scan is not interleaved).
+ *
+ * nesr_jpeg_decode_u8 (replaces the decoding half of cv2.imread): file_dev[0 .. n) is the whole file on the device, info what
+ * nesr_jpeg_parse gave for it.  dst_dev: [H, W, C] u8, rows dst_row_bytes apart, order NESR_ORDER_RGB or NESR_ORDER_BGR (C = 1:
+ * [H, W]); bytes between the rows are not written.  scratch_dev: at least nesr_jpeg_decode_scratch_bytes(info) bytes, 16-byte
+ * aligned.  status_dev (4-byte aligned): 0 when the scan decoded, otherwise bits that say why the device rejected it (a code that is
+ * not in the table, a run past coefficient 63, a stream that ends early, more blocks than the frame holds, a wrong restart marker);
+ * a caller reports NESR_ERR_BADFILE then, and dst_dev holds no defined image.  Every loop of the kernels is bounded by the stream's
+ * length and the frame's block count and every store is guarded, so a corrupt scan ends in that word.  What libjpeg would recover
+ * from such a file is not reproduced.  With a restart interval everything is enqueued on hip_stream and nothing waits; without one
+ * the self-synchronising decode launches its cross-workgroup pass until a 4-byte count it reads back is zero (at most once per
+ * workgroup of 256 x 1024 bits, usually twice).  A null pointer, an info that does not describe file[0 .. n), an unknown order, a
+ * stride smaller than a row, a short or misaligned scratch: NESR_ERR_ARG before any device is touched.
+ */
+typedef struct nesr_jpeg_huff {
+    uint16_t look[512];
+    int32_t maxcode[18]; /* [l]: the largest code of length l, -1 when there is none; [17] ends every search */
+    int32_t valoff[17];  /* vals[code + valoff[l]] */
+    uint8_t vals[256];
+} nesr_jpeg_huff;
+typedef struct nesr_jpeg_info {
+    int32_t H, W, C;
+    int32_t hs, vs;
+    int32_t restart_interval; /* MCUs, 0: none */
+    int32_t mcus_x, mcus_y;
+    int64_t scan_offset, scan_bytes; /* the entropy-coded bytes: after SOS, up to EOI when the file ends with one */
+    uint16_t q[3][64];
+    nesr_jpeg_huff dc[3], ac[3];
+} nesr_jpeg_info;
+int nesr_jpeg_parse(const uint8_t* file, size_t n, nesr_jpeg_info* info);
+size_t nesr_jpeg_decode_scratch_bytes(const nesr_jpeg_info* info);
+int nesr_jpeg_decode_u8(int device_id, const uint8_t* file_dev, size_t n, const nesr_jpeg_info* info, uint8_t* dst_dev, int64_t dst_row_bytes, int order,
+                        void* scratch_dev, size_t scratch_bytes, uint32_t* status_dev, void* hip_stream);
+/* What this thread's last nesr_jpeg_decode_u8 enqueued: launches of the cross-workgroup synchronisation pass (0 with a restart
+ * interval or a stream of one workgroup) and kernel launches in all.  For measurements (tools/bench_jpeg_decode.py). */
+int nesr_jpeg_decode_last_launches(int* sync_rounds, int* launches);
 
 /*
  * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind

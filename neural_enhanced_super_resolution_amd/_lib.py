@@ -112,6 +112,11 @@ SIGNATURES = {
     "nesr_jpeg_header": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int)]),
     "nesr_jpeg_encode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
                                        _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
+    "nesr_jpeg_parse": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_jpeg_decode_scratch_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "nesr_jpeg_decode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
+                                       _c.c_void_p]),
+    "nesr_jpeg_decode_last_launches": (_c.c_int, [_c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
                                    _c.c_void_p]),
     "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,
@@ -151,7 +156,7 @@ _lib = None
 _lock = threading.Lock()
 
 
-ERR_ARG, ERR_RANGE, ERR_NOFIT = -1, -5, -6
+ERR_ARG, ERR_RANGE, ERR_NOFIT, ERR_UNSUPPORTED, ERR_BADFILE = -1, -5, -6, -7, -8
 
 
 class NesrHipError(RuntimeError):
@@ -170,6 +175,46 @@ class NesrNoFitError(NesrHipError):
         super().__init__(f"nesr_jpeg_encode_u8 failed ({ERR_NOFIT}): the file needs {needed} bytes, the buffer holds {cap}")
         self.needed = needed
         self.cap = cap
+
+
+class NesrUnsupportedError(NesrHipError):
+    """NESR_ERR_UNSUPPORTED: a valid JPEG file outside what the device decodes (progressive, arithmetic, 12 bits, 4 components, ...)."""
+
+
+class NesrBadFileError(NesrHipError):
+    """NESR_ERR_BADFILE: malformed marker segments, or a scan the device rejected (`status`: the bits of its status word)."""
+
+    def __init__(self, msg, status=0):
+        super().__init__(msg)
+        self.status = status
+
+
+class JpegHuff(ctypes.Structure):
+    """nesr_jpeg_huff"""
+    _fields_ = [("look", _c.c_uint16 * 512), ("maxcode", _c.c_int32 * 18), ("valoff", _c.c_int32 * 17), ("vals", _c.c_uint8 * 256)]
+
+
+class JpegInfo(ctypes.Structure):
+    """nesr_jpeg_info"""
+    _fields_ = [("H", _c.c_int32), ("W", _c.c_int32), ("C", _c.c_int32), ("hs", _c.c_int32), ("vs", _c.c_int32), ("restart_interval", _c.c_int32),
+                ("mcus_x", _c.c_int32), ("mcus_y", _c.c_int32), ("scan_offset", _c.c_int64), ("scan_bytes", _c.c_int64), ("q", (_c.c_uint16 * 64) * 3),
+                ("dc", JpegHuff * 3), ("ac", JpegHuff * 3)]
+
+
+def jpeg_parse(data):
+    """nesr_jpeg_parse on the file's bytes -> JpegInfo; NesrUnsupportedError / NesrBadFileError as the parser classifies the file."""
+    data = bytes(data)
+    info = JpegInfo()
+    rc = load().nesr_jpeg_parse(data, len(data), ctypes.byref(info))
+    if rc != 0:
+        msg = load().nesr_last_error()
+        text = f"nesr_jpeg_parse failed ({rc}): {msg.decode() if msg else '?'}"
+        if rc == ERR_UNSUPPORTED:
+            raise NesrUnsupportedError(text)
+        if rc == ERR_BADFILE:
+            raise NesrBadFileError(text)
+        raise NesrHipError(text)
+    return info
 
 
 def load():

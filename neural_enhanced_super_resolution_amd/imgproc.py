@@ -876,3 +876,135 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
     import numpy as np
     Image.fromarray(np.ascontiguousarray(arr)).save(buf, format="JPEG", quality=int(quality))
     return buf.getvalue()
+
+
+def _jpeg_decode_hip(file_dev, n, info, order, out):
+    """One run of nesr_jpeg_decode_u8 (csrc/jpeg_decode.hip) on the file's bytes on the device -> the [H, W, 3] / [H, W] uint8 frame
+    (`out` when given: a window whose rows may be strided).  One word comes back, the status; NesrBadFileError when it is not 0."""
+    from . import _lib
+    lib = _lib.load()
+    import ctypes
+    h, w, c = int(info.H), int(info.W), int(info.C)
+    if out is None:
+        out = torch.empty((h, w, c), dtype=torch.uint8, device=file_dev.device)
+    view = out if out.dim() == 3 else out[:, :, None]
+    need = int(lib.nesr_jpeg_decode_scratch_bytes(ctypes.byref(info)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=file_dev.device)
+    status = torch.empty(1, dtype=torch.int32, device=file_dev.device)
+    _hip_call(file_dev, "nesr_jpeg_decode_u8", _ptr(file_dev), int(n), ctypes.byref(info), _ptr(view), _row_bytes(view), _lib.ORDER_BGR if order == "bgr" else _lib.ORDER_RGB,
+              _ptr(scratch), need, _ptr(status))
+    word = int(status.item()) & 0xFFFFFFFF                     # D2H: 4 bytes (waits for the decode)
+    if word != 0:
+        raise _lib.NesrBadFileError(f"nesr_jpeg_decode_u8 failed ({_lib.ERR_BADFILE}): the device rejected the scan, status {word:#x}", word)
+    return out[:, :, 0] if c == 1 and out.dim() == 3 else out
+
+
+def _jpeg_decode_pillow(data, order):
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("decode_jpeg_u8: the host route needs Pillow (the device route: a ROCm device)") from e
+    import io
+    import numpy as np
+    img = Image.open(io.BytesIO(bytes(data)))
+    if img.format != "JPEG":
+        raise ValueError(f"decode_jpeg_u8: a JPEG file, got {img.format}")
+    if img.mode not in ("L", "RGB"):
+        img = img.convert("RGB")
+    arr = np.asarray(img)
+    return torch.from_numpy(np.array(arr[:, :, ::-1] if arr.ndim == 3 and order == "bgr" else arr))
+
+
+def decode_jpeg_u8(data, order="rgb", device=None, use_hip=None, out=None):
+    """cv2.imread(path.jpg, cv2.IMREAD_UNCHANGED)'s pixels (the reference reads with cv2.imread, nesr/nesr.py:661-666,
+    standalone/direct_esrgan.py:130) for a JPEG file's bytes -> uint8 tensor [H, W, 3] (order "rgb" or "bgr": the channel that comes
+    first) or [H, W] for a gray file.  EXIF orientation is not applied: IMREAD_UNCHANGED and Pillow leave it alone, cv2.imread's
+    default flag would rotate a file whose orientation is not 1.
+
+    On a ROCm device (device=None: the current one when there is one) the file's bytes go up and the HIP kernels decode them
+    (csrc/jpeg_decode.hip, nesr_jpeg_parse + nesr_jpeg_decode_u8): baseline Huffman files, 8 bits, gray, 4:4:4, 4:2:2 or 4:2:0, any
+    tables, any restart interval -- pixel for pixel what libjpeg-turbo gives (tests/jpeg_decode_ref.py).  `out`: a uint8 window
+    [H, W, C] (or [H, W]) on that device to decode into; its rows may be strided and nothing outside it is written.
+    use_hip=False or a CPU device: Pillow's libjpeg-turbo; without Pillow that raises.  use_hip=None: a file the kernels do not
+    support (NesrUnsupportedError: progressive, CMYK, ...) is decoded by Pillow and copied up; a malformed file or a scan the device
+    rejects raises NesrBadFileError.  use_hip=True raises on both."""
+    from . import _lib
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"decode_jpeg_u8: order must be 'rgb' or 'bgr', got {order!r}")
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    device = torch.device(device)
+    on_gpu = device.type == "cuda"
+    if use_hip is None:
+        use_hip, fallback = on_gpu, True
+    else:
+        fallback = False
+    if use_hip and not on_gpu:
+        raise ValueError(f"decode_jpeg_u8: the HIP kernels run on the ROCm device, got {device}")
+    data = bytes(data)
+    if use_hip:
+        try:
+            info = _lib.jpeg_parse(data)
+        except _lib.NesrUnsupportedError:
+            if not fallback:
+                raise
+            info = None
+        if info is not None:
+            if out is not None:
+                shape = (info.H, info.W, 3) if info.C == 3 else (info.H, info.W)
+                ok = out.dtype == torch.uint8 and out.device.type == "cuda" and (tuple(out.shape) == shape or tuple(out.shape) == (info.H, info.W, info.C))
+                if not ok or not _rows_ok(out if out.dim() == 3 else out[:, :, None], (1, 3)):
+                    raise ValueError(f"decode_jpeg_u8: out must be a uint8 {shape} window on the ROCm device with contiguous pixels in a row, got "
+                                     f"{out.dtype} {tuple(out.shape)} on {out.device}")
+            import numpy as np
+            file_dev = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(device)         # H2D: the file
+            return _jpeg_decode_hip(file_dev, len(data), info, order, out)
+    frame = _jpeg_decode_pillow(data, order).to(device)
+    if out is not None:
+        out.copy_(frame.reshape(out.shape))
+        return out
+    return frame
+
+
+def jpeg_roundtrip_u8(frame, quality=75, order="rgb"):
+    """apply_jpeg_compression (nesr/utils/image_utils.py:130-152: cv2.imencode('.jpg', img, [IMWRITE_JPEG_QUALITY, quality]) then
+    cv2.imdecode) on a uint8 [H, W, 3], [H, W, 1] or [H, W] tensor on the ROCm device -> the decoded frame, same shape.  Neither the
+    frame nor the file leaves the device: the encoder's output buffer feeds the decoder, and only the length words are read, to size
+    the decoder's launches.  The header the decoder's parser needs is the one the host wrote for the encoder (nesr_jpeg_header)."""
+    from . import _lib
+    import ctypes
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"jpeg_roundtrip_u8: order must be 'rgb' or 'bgr', got {order!r}")
+    if not 1 <= int(quality) <= 100:
+        raise ValueError(f"jpeg_roundtrip_u8: quality {quality} outside 1..100")
+    if not isinstance(frame, torch.Tensor) or not _hip_default(frame):
+        raise ValueError("jpeg_roundtrip_u8: a uint8 tensor on the ROCm device")
+    squeeze = frame.dim() == 2
+    src = frame[:, :, None] if squeeze else frame
+    if src.dim() != 3 or src.shape[2] not in (1, 3) or min(src.shape) < 1 or max(src.shape[:2]) > 65535:
+        raise ValueError(f"jpeg_roundtrip_u8: an [H, W, 3], [H, W, 1] or [H, W] uint8 frame of at most 65535 x 65535 pixels, got {tuple(frame.shape)}")
+    if not _rows_ok(src, (1, 3)):
+        src = src.contiguous()
+    h, w, c = src.shape
+    lib = _lib.load()
+    head = (ctypes.c_uint8 * 1024)()
+    n_head = ctypes.c_int(0)
+    _lib.check(lib.nesr_jpeg_header(h, w, c, int(quality), head, 1024, ctypes.byref(n_head)), "nesr_jpeg_header")
+    info = _lib.jpeg_parse(bytes(head[:n_head.value]) + b"\0")      # the scan's length is patched in below
+    need = int(lib.nesr_jpeg_scratch_bytes(h, w, c))
+    scratch = torch.empty(need, dtype=torch.uint8, device=src.device)
+    cap = h * w * c // 2 + 4096
+    while True:
+        file_dev = torch.empty(cap, dtype=torch.uint8, device=src.device)
+        words = torch.empty(2, dtype=torch.int64, device=src.device)
+        _hip_call(src, "nesr_jpeg_encode_u8", _ptr(src), _row_bytes(src), h, w, c, _lib.ORDER_BGR if order == "bgr" else _lib.ORDER_RGB, int(quality),
+                  _ptr(scratch), need, _ptr(file_dev), cap, _ptr(words))
+        length, status = (int(v) for v in words.cpu())          # D2H: 16 bytes
+        if status == 0:
+            break
+        cap = length
+    info.scan_bytes = length - n_head.value - 2                  # the file ends with EOI
+    out = _jpeg_decode_hip(file_dev, length, info, order, None)
+    if c == 1 and not squeeze:
+        out = out[:, :, None]
+    return out

@@ -355,7 +355,8 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     its trace are what they were without them.  use_hip goes to every stage (None: the HIP kernels where they apply; False: the
     torch chains, the same bits).  encode="jpeg" or ("jpeg", quality): what enhance_image writes in the end (cv2.imwrite,
     nesr.py:639-646) -- the bytes of the final RGB frame's JPEG file (quality 95 unless given) instead of the ndarray, encoded on the
-    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home."""
+    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home.  image_rgb may be a JPEG file's bytes: they are
+    decoded on the device first (imgproc.decode_jpeg_u8), so only files cross the bus."""
     if encode is not None:
         kind, quality = (encode, 95) if isinstance(encode, str) else tuple(encode)
         if kind != "jpeg":
@@ -372,6 +373,12 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
         fkw = {} if use_hip is None else {"use_hip": use_hip}
         preprocess = preprocess or (lambda im: imgproc.preprocess_image(_u8_on(im, device), cfg["denoise_level"], **fkw))
         postprocess = postprocess or (lambda im: imgproc.postprocess_image(_u8_on(im, device), cfg["adaptive_sharpening"], **fkw))
+    if isinstance(image_rgb, (bytes, bytearray, memoryview)):
+        # enhance_image's cv2.imread + cvtColor(BGR2RGB) (nesr.py:661-666) for a JPEG file's bytes: decoded on `device`, RGB order
+        from . import imgproc
+        image_rgb = imgproc.decode_jpeg_u8(bytes(image_rgb), order="rgb", device=device)
+        if image_rgb.dim() == 2:                                # (cv2.imread's default flag gives three channels for a gray file)
+            image_rgb = image_rgb[:, :, None].expand(-1, -1, 3).contiguous()
     current = image_rgb
     for iteration in range(int(cfg["iterations"])):
         if preprocess is not None:

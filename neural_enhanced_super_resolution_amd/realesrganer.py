@@ -552,7 +552,7 @@ class RealESRGANer:
         """8-bit BGR frames on the HIP backend (any tiling / padding): the uint8 frame is uploaded
         (4x fewer bytes than float), normalised, padded, tiled, clamped and quantised on the GPU with
         the same float32 operations enhance() performs in numpy, and only uint8 comes back."""
-        return (self._hip_model() and self.device.type == "cuda" and img.dtype == np.uint8
+        return (self._hip_model() and self.device.type == "cuda" and (img.dtype == torch.uint8 if isinstance(img, torch.Tensor) else img.dtype == np.uint8)
                 and img.ndim == 3 and img.shape[2] == 3)
 
     def _u8_tiles_fused_ok(self, h, w):
@@ -583,7 +583,7 @@ class RealESRGANer:
             return out if resize_to is None else self._resize_on_host_route(out, resize_to)
         h, w = img.shape[:2]
         s = self.scale
-        frame = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)          # H2D: uint8 HWC BGR
+        frame = self._upload_u8(img)                                                 # H2D: uint8 HWC BGR
         canvas = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=self.device)
         tiles = [_tiling.Tile(i, *g) for i, g in enumerate(self.tile_grid(h, w))]
         self.tiles_u8_on_device(frame, _tiling.windows(tiles), _tiling.canvas_pastes(tiles, w * s), canvas)
@@ -603,7 +603,7 @@ class RealESRGANer:
         keep: the quantised frame stays on the device and is returned as a tensor (_enhance_once)."""
         if self._u8_tiles_fused_ok(img.shape[0], img.shape[1]) and (img.shape[0] > self.tile_size or img.shape[1] > self.tile_size):
             return self._enhance_u8_tiles_fused(img, resize_to, keep)
-        x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)            # H2D: uint8 HWC BGR
+        x = self._upload_u8(img)                                                   # H2D: uint8 HWC BGR
         x = normalize_u8_on_device(x.permute(2, 0, 1).flip(0)).unsqueeze(0)          # BGR->RGB, /255 (f32), HWC->NCHW
         self._pad_on_device(x)
         out = self._run()                                                            # [1,3,H*s,W*s] RGB
@@ -617,6 +617,13 @@ class RealESRGANer:
         host = self._frame_to_host(q).numpy()
         self._check_range()
         return host
+
+    def _upload_u8(self, img):
+        """The upload at the head of the 8-bit routes.  A frame that was born on the device (enhance_file: decoded there from the
+        file's bytes) is a uint8 tensor already and passes through."""
+        if isinstance(img, torch.Tensor):
+            return img.contiguous()
+        return torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
 
     @staticmethod
     def _frame_to_host(t, host=None):
@@ -760,6 +767,8 @@ class RealESRGANer:
     def _device_frame_ok(self, img):
         """A frame enhance_float would take (gray, BGRA, 16 bit; 8-bit BGR has routes of its own) on a HIP model of three channels
         in and out whose output is `scale` times its input: the frame stays on the device (_enhance_frame_on_device)."""
+        if isinstance(img, torch.Tensor):       # enhance_file's frame: uint8, gray or BGR, on the device
+            return DEVICE_FRAMES and self._three_channel_hip() and img.dtype == torch.uint8 and img.numel() != 0 and img.ndim in (2, 3)
         return (DEVICE_FRAMES and self._three_channel_hip() and isinstance(img, np.ndarray) and img.dtype in (np.uint8, np.uint16)
                 and img.size != 0 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))))
 
@@ -767,7 +776,7 @@ class RealESRGANer:
     def _frame_kind(img):
         """(max_range, img_mode) as enhance_float decides them on the host: a frame whose maximum is at most 256 counts as 8-bit
         range whatever its dtype (a uint16 frame that dark comes back as uint8), the mode follows the shape."""
-        max_range = 65535 if np.max(img) > 256 else 255
+        max_range = 255 if isinstance(img, torch.Tensor) else (65535 if np.max(img) > 256 else 255)     # (a tensor: enhance_file's uint8 frame)
         return max_range, "L" if img.ndim == 2 else ("RGBA" if img.shape[2] == 4 else "RGB")
 
     def _frame_inflight_ok(self, img):
@@ -815,7 +824,8 @@ class RealESRGANer:
             self._pad_on_device(t)
             return self._run().float()                                                  # [1,3,H*s,W*s] RGB (fp16 upstream when half)
 
-        q, img_mode = self._frame_through(img, frame_io.frame_to_tensor(img, self.device), alpha_upsampler, net)   # H2D: the frame's own bytes
+        frame = img.contiguous() if isinstance(img, torch.Tensor) else frame_io.frame_to_tensor(img, self.device)   # H2D: the frame's own bytes
+        q, img_mode = self._frame_through(img, frame, alpha_upsampler, net)
         if resize_to is not None:
             q3 = q[:, :, None] if q.dim() == 2 else q
             if q.dtype == torch.uint8:
@@ -899,10 +909,13 @@ class RealESRGANer:
         (imgproc.encode_jpeg_u8: csrc/jpeg.hip); only the file comes home.  The bytes are those of the JPEG file of enhance(img)'s
         frame.  8-bit BGR and gray frames; a BGRA or 16-bit frame raises ValueError (cv2.imwrite would drop the alpha plane or the
         depth without a word)."""
-        from . import imgproc
         if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             kind = f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}"
             raise ValueError(f"enhance_jpeg: an 8-bit BGR [H, W, 3] or gray [H, W] frame, got {kind} (a JPEG file holds neither alpha nor 16 bits)")
+        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler)
+
+    def _enhance_to_jpeg(self, img, quality, outscale, alpha_upsampler):
+        from . import imgproc
 
         def evaluate():
             q, img_mode = self._enhance_once(img, outscale, alpha_upsampler, keep=True)
@@ -913,6 +926,39 @@ class RealESRGANer:
             return data, img_mode
 
         return self._again_if_gave_up(evaluate)
+
+    def _read_jpeg(self, data_or_path, who):
+        """The head of enhance_file: the file's bytes (or the file at a path) -> the BGR (or gray) uint8 frame, decoded on the wrapper's
+        device (imgproc.decode_jpeg_u8: csrc/jpeg_decode.hip) and left there for the routes that start with an upload; the routes that
+        assemble their frame on the host (devices=[...], a model that is not a HIP one, a CPU device) get it copied home once."""
+        from . import imgproc
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(data_or_path)
+        else:
+            with open(data_or_path, "rb") as f:
+                data = f.read()
+        if data[:2] != b"\xff\xd8":
+            raise ValueError(f"{who}: not a JPEG file (it does not start with SOI); no other format is decoded on the device")
+        frame = imgproc.decode_jpeg_u8(data, order="bgr", device=self.device)
+        if self._multi() or not (self._u8_on_device_ok(frame) or self._device_frame_ok(frame)):
+            return frame.cpu().numpy()
+        return frame
+
+    @torch.no_grad()
+    def enhance_file(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance(cv2.imread(path, cv2.IMREAD_UNCHANGED)) for a JPEG file given as bytes or as a path (the reference reads with
+        cv2.imread, standalone/direct_esrgan.py:130): (ndarray, img_mode).  The file's bytes go up, the frame is decoded on the device
+        and handed to enhance()'s routes as a device tensor: the decoded frame never crosses the bus.  EXIF orientation is not
+        applied and a gray file stays gray (IMREAD_UNCHANGED; cv2.imread's default flag would rotate and give three channels).
+        Anything but a JPEG file raises ValueError."""
+        img = self._read_jpeg(data_or_path, "enhance_file")
+        return self._again_if_gave_up(lambda: self._enhance_once(img, outscale, alpha_upsampler))
+
+    @torch.no_grad()
+    def enhance_file_jpeg(self, data_or_path, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance_file followed by cv2.imwrite(path.jpg, output), the file as bytes: (bytes, img_mode).  File bytes in, file bytes out;
+        nothing else crosses the bus."""
+        return self._enhance_to_jpeg(self._read_jpeg(data_or_path, "enhance_file_jpeg"), quality, outscale, alpha_upsampler)
 
     def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan", keep=False):
         """keep: the routes that hold the finished frame on the device return it there (a uint8 tensor, not yet range-checked)
@@ -931,7 +977,7 @@ class RealESRGANer:
 
         if self._fused_u8_ok(img) and not plain_alpha:
             # /255, BGR->RGB, network, clamp, RGB->BGR, x255, round -- all inside the HIP path
-            x = torch.from_numpy(np.ascontiguousarray(img)).to(self.device)
+            x = self._upload_u8(img)
             plan = self._band_plan(x)
             if plan is None:
                 y = self.model.forward_u8(x, flip_rgb=True, round_nearest=True)
