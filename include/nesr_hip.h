@@ -565,6 +565,45 @@ int nesr_jpeg_decode_u8(int device_id, const uint8_t* file_dev, size_t n, const 
 int nesr_jpeg_decode_last_launches(int* sync_rounds, int* launches);
 
 /*
+ * cv2.imwrite(path, frame) for a .png path as HIP kernels (csrc/png.hip): the lossless file, which is the one the reference writes
+ * most -- standalone/superres_project.py:203-206 always names its result .png, nesr/nesr.py:619-625 saves intermediate_iter{n}.png
+ * after every iteration, and standalone/direct_esrgan.py:130,169 reads with IMREAD_UNCHANGED and writes with the input's extension,
+ * so a PNG with alpha, a gray scan or a 16-bit file comes back as PNG (the BGRA, 16-bit gray and 16-bit colour frames nesr_pack_frame
+ * takes).  The frame stays on the device and only the file crosses to the host.
+ *
+ * Lossless is the contract: a standard decoder returns the frame bit for bit.  The bytes are NOT cv2's (zlib's LZ77 output depends
+ * on its version); they are those of tests/png_ref.py, the specification the kernels are compared with byte for byte: signature,
+ * IHDR (depth 8 or 16; colour type 0, 2 or 6; no interlace), IDAT[78 01], one IDAT per deflate chunk, IDAT[Adler-32], IEND, no
+ * ancillary chunk.  Per row the cheapest of the five filter types by libpng's sum of min(v, 256 - v), each computed from raw
+ * neighbours; the filtered stream is cut into chunks of 32768 bytes, each one deflate block (stored, fixed or dynamic, the cheapest by
+ * exact bit count) with distance-1 matches only, followed by an empty stored block that re-aligns the stream (pigz's scheme).
+ *
+ * src_dev: [H, W, C] samples of `depth` bits (8: bytes; 16: little-endian 16-bit words, as nesr_unpack_frame leaves them), C = 1, 3
+ * or 4, order NESR_ORDER_RGB or NESR_ORDER_BGR (which channel comes first; the file is always R G B (A); C = 1: ignored but checked),
+ * pixels of a row contiguous, rows src_row_bytes apart; 1 <= H, W <= 65535.
+ * scratch_dev: at least nesr_png_scratch_bytes(H, W, C, depth) bytes (0 for a shape it rejects), 16-byte aligned: the filtered
+ * stream and one 32800-byte slot per chunk, about twice the frame.
+ * out_dev[0 .. out_cap): the file; nesr_png_bound(H, W, C, depth) is the exact worst case (every chunk stored: 75 bytes, the
+ * filtered stream and 22 bytes per chunk), so a buffer of that size always fits.  out_len_dev (8-byte aligned): [0] = the bytes the
+ * whole file needs, [1] = 0 when it fits, 1 when out_cap is smaller -- then out_dev holds the first out_cap bytes, nothing at or
+ * beyond out_cap is ever written, and a caller reports NESR_ERR_NOFIT.  Everything is enqueued on hip_stream: no allocation, no
+ * synchronisation, no copy; two runs give the same bytes.  A null pointer, a size outside 1 .. 65535, C not 1, 3 or 4, depth not 8 or
+ * 16, an unknown order, a stride smaller than a row, a short or misaligned scratch: NESR_ERR_ARG before any device is touched.
+ *
+ * nesr_png_head (host only): signature, IHDR and the 2-byte IDAT that holds the zlib header, 47 bytes.  *n is always set;
+ * buf[0 .. *n) is filled when cap >= *n.
+ * nesr_png_code_lengths (host only): the code-length construction the kernels run per chunk (png_ref.code_lengths), for tests: a
+ * length-limited Huffman code for counts[0 .. n), 2 <= n <= 286, n <= 2^limit, limit <= 15, counts summing to less than 2^32.  The code
+ * is always complete: with fewer than two counted symbols that symbol (or symbol 0) and the lowest other one get one bit.
+ */
+size_t nesr_png_bound(int H, int W, int C, int depth);
+size_t nesr_png_scratch_bytes(int H, int W, int C, int depth);
+int nesr_png_head(int H, int W, int C, int depth, uint8_t* buf, int cap, int* n);
+int nesr_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* lengths);
+int nesr_png_encode(int device_id, const void* src_dev, int64_t src_row_bytes, int H, int W, int C, int depth, int order, void* scratch_dev,
+                    size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
+
+/*
  * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind
  * RealESRGANer.enhance(outscale=...), its `cv2.resize(alpha, ..., INTER_LINEAR)` behind alpha_upsampler != "realesrgan", and the
  * Lanczos paste of _process_with_tiling (nesr/nesr.py:437-446).  cv2's semantics as imgproc.lanczos4_resize / linear_resize_f32 and

@@ -117,6 +117,12 @@ SIGNATURES = {
     "nesr_jpeg_decode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
                                        _c.c_void_p]),
     "nesr_jpeg_decode_last_launches": (_c.c_int, [_c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "nesr_png_bound": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_png_scratch_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_png_head": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_png_code_lengths": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
+    "nesr_png_encode": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                   _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
     "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
                                    _c.c_void_p]),
     "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,
@@ -169,10 +175,10 @@ class NesrRangeError(NesrHipError, FloatingPointError):
 
 
 class NesrNoFitError(NesrHipError):
-    """NESR_ERR_NOFIT: the JPEG file did not fit the output buffer; `needed` is the size the device reported."""
+    """NESR_ERR_NOFIT: the JPEG or PNG file did not fit the output buffer; `needed` is the size the device reported."""
 
-    def __init__(self, needed, cap):
-        super().__init__(f"nesr_jpeg_encode_u8 failed ({ERR_NOFIT}): the file needs {needed} bytes, the buffer holds {cap}")
+    def __init__(self, needed, cap, who="nesr_jpeg_encode_u8"):
+        super().__init__(f"{who} failed ({ERR_NOFIT}): the file needs {needed} bytes, the buffer holds {cap}")
         self.needed = needed
         self.cap = cap
 

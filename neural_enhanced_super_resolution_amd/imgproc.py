@@ -9,6 +9,7 @@
   SuperResolutionPipeline._ensemble_results  Lanczos alignment, float32 mean, truncation    nesr/nesr.py:1033-1054
   enhance_image's no-model step              cv2.resize(INTER_CUBIC)                         nesr/nesr.py:597-605
   enhance_image's last call                  cv2.imwrite(path.jpg): baseline JPEG (PINNED)   nesr/nesr.py:639-646
+  the iterations' and projects' .png files   cv2.imwrite(path.png): lossless (pixels PINNED) nesr/nesr.py:619-625
   (_process_with_tiling's Lanczos paste and the 12-channel builder's 3x3 blur use the same functions: nesr_adapter.py)
 
 PARITY UNPINNED, all of it but the JPEG file (encode_jpeg_u8: libjpeg's integer pipeline, byte for byte): cv2 is not installed here or on the GPU box and the reference holds no output of any of
@@ -876,6 +877,88 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
     import numpy as np
     Image.fromarray(np.ascontiguousarray(arr)).save(buf, format="JPEG", quality=int(quality))
     return buf.getvalue()
+
+
+# ----------------------------------------------------------------------------------------------- PNG
+def _png_encode_hip(frame, depth, bgr, cap=None):
+    """One run of nesr_png_encode (csrc/png.hip) on an [H, W, C] device tensor (uint8, or 16-bit samples in 2-byte elements) into a
+    buffer of `cap` bytes (default nesr_png_bound, which always fits) -> the file's bytes; NesrNoFitError when the file needs more.
+    Two transfers come back: the 16 bytes of the length and status words, then exactly the file."""
+    from . import _lib
+    h, w, c = frame.shape
+    lib = _lib.load()
+    need = int(lib.nesr_png_scratch_bytes(h, w, c, depth))
+    if cap is None:
+        cap = int(lib.nesr_png_bound(h, w, c, depth))
+    scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
+    out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
+    words = torch.empty(2, dtype=torch.int64, device=frame.device)
+    _hip_call(frame, "nesr_png_encode", _ptr(frame), _row_bytes(frame), h, w, c, depth, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB,
+              _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+    length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
+    if status != 0:
+        raise _lib.NesrNoFitError(length, cap, "nesr_png_encode")
+    return out[:length].cpu().numpy().tobytes()               # D2H: the file
+
+
+def _png_chunk(kind, payload):
+    import struct
+    import zlib
+    return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(kind + payload) & 0xFFFFFFFF)
+
+
+def encode_png(frame, order="rgb", use_hip=None):
+    """cv2.imwrite(path.png, frame) (standalone/superres_project.py:203-206, nesr/nesr.py:619-625, standalone/direct_esrgan.py:169 for a
+    PNG input) for an [H, W], [H, W, 1], [H, W, 3] or [H, W, 4] frame (order "rgb" or "bgr": the channel that comes first; alpha stays
+    last) -> the file's bytes.  8 bit: uint8.  16 bit: as frame_io holds it, an int16 tensor carrying the uint16 bit pattern, or
+    torch.uint16 / numpy uint16.  The file is lossless: a standard decoder returns the frame bit for bit (in R G B (A) order).
+
+    A tensor on the ROCm device goes through the HIP kernels (csrc/png.hip, nesr_png_encode), a row-strided window
+    (frame[y0:y1, x0:x1]) as it is: the frame stays on the device and only the length words and the file come back.  The output
+    buffer is nesr_png_bound, the exact worst case, so one run always fits.  Its bytes are those of tests/png_ref.py: adaptive row
+    filters, deflate in independent 32 KiB chunks with distance-1 matches.
+    use_hip=False, a CPU tensor or an ndarray: cv2's default settings restated with the standard library -- the Sub filter on every
+    row, zlib.compressobj(1, DEFLATED, 15, 8, Z_RLE), one IDAT.  That file holds THE SAME PIXELS as the device route's and DIFFERENT
+    BYTES (neither is cv2's own: zlib's output depends on its version)."""
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"encode_png: order must be 'rgb' or 'bgr', got {order!r}")
+    is_tensor = isinstance(frame, torch.Tensor)
+    if frame.ndim == 2:
+        frame = frame[:, :, None]
+    kind = str(frame.dtype).split(".")[-1]
+    depth = {"uint8": 8, "int16": 16, "uint16": 16}.get(kind) if is_tensor or kind != "int16" else None
+    if frame.ndim != 3 or frame.shape[2] not in (1, 3, 4) or min(frame.shape) < 1 or max(frame.shape[:2]) > 65535 or depth is None:
+        raise ValueError(f"encode_png: an [H, W], [H, W, 1], [H, W, 3] or [H, W, 4] uint8 or 16-bit frame of at most 65535 x 65535 pixels, got "
+                         f"{frame.dtype} {tuple(frame.shape)}")
+    fits = is_tensor and frame.device.type == "cuda"
+    if use_hip is None:
+        use_hip = fits
+    if use_hip:
+        if not fits:
+            raise ValueError(f"encode_png: the HIP kernels take a tensor on the ROCm device, got {frame.dtype} on "
+                             f"{frame.device if is_tensor else 'the host'}")
+        src = frame if _rows_ok(frame, (1, 3, 4)) else frame.contiguous()
+        return _png_encode_hip(src, depth, order == "bgr")
+    import struct
+    import zlib
+    import numpy as np
+    arr = frame.cpu() if is_tensor else frame
+    if is_tensor:
+        arr = (arr.view(torch.int16) if depth == 16 else arr).numpy()
+    arr = arr.view(np.uint16) if depth == 16 else arr
+    h, w, c = arr.shape
+    if order == "bgr" and c >= 3:
+        arr = np.concatenate([arr[:, :, 2::-1], arr[:, :, 3:]], axis=2)
+    bpp = c * depth // 8
+    raw = np.ascontiguousarray(arr.astype(">u2") if depth == 16 else arr).view(np.uint8).reshape(h, w * bpp)
+    rows = np.empty((h, 1 + w * bpp), np.uint8)
+    rows[:, 0] = 1                                            # Sub on every row: cv2's IMWRITE_PNG_STRATEGY default path
+    rows[:, 1:] = raw
+    rows[:, 1 + bpp:] -= raw[:, :-bpp]
+    deflate = zlib.compressobj(1, zlib.DEFLATED, 15, 8, zlib.Z_RLE)
+    stream = deflate.compress(rows.tobytes()) + deflate.flush()
+    ihdr = struct.pack(">IIBBBBB", w, h, depth, {1: 0, 3: 2, 4: 6}[c], 0, 0, 0)
+    return b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", stream) + _png_chunk(b"IEND", b"")
 
 
 def _jpeg_decode_hip(file_dev, n, info, order, out):

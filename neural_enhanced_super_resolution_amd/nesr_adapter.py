@@ -327,7 +327,7 @@ def realesrganer_stage(up):
 
 def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", preprocess=None, postprocess=None,
                        trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None,
-                       encode=None):
+                       encode=None, png=False, intermediates=None):
     """The iteration loop of SuperResolutionPipeline.enhance_image (nesr.py:516-633):
 
         for iteration in range(config['iterations']):           nesr.py:516
@@ -356,7 +356,13 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     torch chains, the same bits).  encode="jpeg" or ("jpeg", quality): what enhance_image writes in the end (cv2.imwrite,
     nesr.py:639-646) -- the bytes of the final RGB frame's JPEG file (quality 95 unless given) instead of the ndarray, encoded on the
     device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home.  image_rgb may be a JPEG file's bytes: they are
-    decoded on the device first (imgproc.decode_jpeg_u8), so only files cross the bus."""
+    decoded on the device first (imgproc.decode_jpeg_u8), so only files cross the bus.  png=True: the final RGB frame's lossless PNG
+    file instead (what standalone/superres_project.py:203-206 always writes), encoded on the device (imgproc.encode_png); together
+    with `encode` it raises ValueError, and encode="png" stays an error.  intermediates=<list>: with config["intermediate_saves"]
+    true it receives each iteration's frame as PNG bytes, the reference's intermediate_iter{n}.png (nesr.py:619-625), encoded where
+    the frame is."""
+    if png and encode is not None:
+        raise ValueError("enhance_iterations: png=True and encode are two different files; give one")
     if encode is not None:
         kind, quality = (encode, 95) if isinstance(encode, str) else tuple(encode)
         if kind != "jpeg":
@@ -413,13 +419,16 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
                 trace[-1].update({"segmented": segmenter is not None, "ensemble_n": len(results), "out_shape": tuple(current.shape[:2])})
         if postprocess is not None:
             current = postprocess(current)
+        if intermediates is not None and cfg.get("intermediate_saves"):        # nesr.py:619-625: intermediate_iter{n}.png
+            from . import imgproc
+            intermediates.append(imgproc.encode_png(current, order="rgb"))
     for extra in extra_upscalers:
         check = getattr(extra, "check_range", None)
         if check is not None:
             check()
-    if encode is not None:
+    if encode is not None or png:
         from . import imgproc
-        data = imgproc.encode_jpeg_u8(current, quality, order="rgb")
+        data = imgproc.encode_png(current, order="rgb") if png else imgproc.encode_jpeg_u8(current, quality, order="rgb")
         check = getattr(getattr(upscaler, "model", None), "check_range", None)
         if check is not None and isinstance(current, torch.Tensor):
             check()

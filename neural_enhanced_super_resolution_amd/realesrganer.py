@@ -927,6 +927,31 @@ class RealESRGANer:
 
         return self._again_if_gave_up(evaluate)
 
+    @torch.no_grad()
+    def enhance_png(self, img, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance() followed by cv2.imwrite(path.png, output) (standalone/superres_project.py:203-206; standalone/direct_esrgan.py:169
+        for a PNG input), the file as bytes: (bytes, img_mode).  Every frame kind enhance() takes -- gray, BGR, BGRA, 8 and 16 bit: the
+        ones enhance_jpeg has to refuse.  The quantised frame of enhance()'s route stays on the device and is encoded there
+        (imgproc.encode_png: csrc/png.hip); only the file comes home.  The file is lossless: it decodes to exactly enhance(img)'s
+        frame (in R G B (A) order, as every PNG file holds it)."""
+        if not isinstance(img, (np.ndarray, torch.Tensor)) or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))):
+            kind = f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}"
+            raise ValueError(f"enhance_png: a gray [H, W], BGR [H, W, 3] or BGRA [H, W, 4] frame, got {kind}")
+        return self._enhance_to_png(img, outscale, alpha_upsampler)
+
+    def _enhance_to_png(self, img, outscale, alpha_upsampler):
+        from . import frame_io, imgproc
+
+        def evaluate():
+            q, img_mode = self._enhance_once(img, outscale, alpha_upsampler, keep=True)
+            if not isinstance(q, torch.Tensor):          # a route that assembles its frame on the host (several devices, no HIP model)
+                q = frame_io.frame_to_tensor(np.ascontiguousarray(q), self.device)
+            data = imgproc.encode_png(q, order="bgr")
+            self._check_range()                          # after the copy that waited for the stream, as enhance() does
+            return data, img_mode
+
+        return self._again_if_gave_up(evaluate)
+
     def _read_jpeg(self, data_or_path, who):
         """The head of enhance_file: the file's bytes (or the file at a path) -> the BGR (or gray) uint8 frame, decoded on the wrapper's
         device (imgproc.decode_jpeg_u8: csrc/jpeg_decode.hip) and left there for the routes that start with an upload; the routes that
@@ -959,6 +984,13 @@ class RealESRGANer:
         """enhance_file followed by cv2.imwrite(path.jpg, output), the file as bytes: (bytes, img_mode).  File bytes in, file bytes out;
         nothing else crosses the bus."""
         return self._enhance_to_jpeg(self._read_jpeg(data_or_path, "enhance_file_jpeg"), quality, outscale, alpha_upsampler)
+
+    @torch.no_grad()
+    def enhance_file_png(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance_file followed by cv2.imwrite(path.png, output), the file as bytes: (bytes, img_mode).  A JPEG file's bytes in, a
+        lossless PNG file's bytes out (standalone/superres_project.py:203-206 names its result .png whatever it read); nothing else
+        crosses the bus."""
+        return self._enhance_to_png(self._read_jpeg(data_or_path, "enhance_file_png"), outscale, alpha_upsampler)
 
     def _enhance_once(self, img, outscale=None, alpha_upsampler="realesrgan", keep=False):
         """keep: the routes that hold the finished frame on the device return it there (a uint8 tensor, not yet range-checked)
