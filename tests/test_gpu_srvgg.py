@@ -1,5 +1,10 @@
 """GPU: SRVGGNetCompact (srvgg_compact.hip) against a float64 torch-CPU restatement of upstream's network (tests/srvgg_ref.py),
-alone and inside RealESRGANer against the unchanged oracle.realesrganer_ref.RealESRGANerRef."""
+alone and inside RealESRGANer against the unchanged oracle.realesrganer_ref.RealESRGANerRef.
+
+The bf16 floors and ceilings below (BF16_NET, BF16_WRAPPER, BF16_LOOP) were measured on this kernel and stay as a guard against
+drift.  What holds the bf16 form to a specification is elsewhere: test_gpu_srvgg_pin.py pins the first layer, a feature layer
+and the tail per value to the rounded float64 value (tests/srvgg_pin.py), and test_gpu_srvgg_emu16.py judges whole networks
+against the exact bf16 specification (tests/srvgg_fp16_emu.py with store=torch.bfloat16) with local conditions."""
 import ctypes
 
 import numpy as np

@@ -7,7 +7,12 @@ Two conditions carry the accuracy tests, both measured in the test itself on the
       order of the f32 accumulation separates the kernel from it, so the kernel sits closer to its specification than the
       specification sits to the exact network.  An operand of another type, a store that does not round to nearest or a
       missing rounding moves the kernel away from the emulation by about the form's whole error.
-Measured values (MI355X) are in DESIGN.md section 8."""
+Measured values (MI355X) are in DESIGN.md section 8.
+
+(b) is one image-wide mean, which a correct kernel meets by a tenth at 16 to 32 layers and which a single layer's wrong
+rounding passes at 2.  The per-value and the local checks of this form are in test_gpu_srvgg_pin.py (each layer kind pinned
+to the rounded float64 value, from 1 x 1 to 289 tiles on resident weights; tests/srvgg_pin.py) and test_gpu_srvgg_emu16.py
+(the same emulation with the maximum, per-band and mean conditions of rrdbnet_emu16.conditions)."""
 import ctypes
 
 import numpy as np
