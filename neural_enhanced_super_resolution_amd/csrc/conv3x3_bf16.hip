@@ -119,11 +119,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
     const int tiles_x = (a.w_ + TW - 1) / TW;
     const int tiles_y = (a.h + TH - 1) / TH;
     const int ntiles = tiles_x * tiles_y * a.n;
-    int tile;
-    {
-        const int bid = blockIdx.x, q = ntiles >> 3, r = ntiles & 7, xcd = bid & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    int tile = xcd_work_index(ntiles);
     const int n = tile / (tiles_x * tiles_y);
     tile -= n * tiles_x * tiles_y;
     const int ty = tile / tiles_x, tx = tile - ty * tiles_x;

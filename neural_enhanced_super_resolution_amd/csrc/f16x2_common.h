@@ -1,5 +1,6 @@
-// Shared pieces of the f16-pair kernels (conv3x3_f16x2.hip, upconv2x2_f16x2.hip): vector types, the LDS-DMA issue,
-// the (hi, scaled lo) split of an f32 value and the whole-line regrouping of the 16x16x32 epilogue.
+// Shared pieces of the f16-pair kernels (conv3x3_f16x2.hip, rdb_f16x2.hip, upconv2x2_f16x2.hip): vector types, the
+// LDS-DMA issue, the (hi, scaled lo) split of an f32 value, the whole-line regrouping of the 16x16x32 epilogue and, for
+// the two 3x3 kernels, the tile geometry, the tap address plan and a tap-step's MFMAs.
 #pragma once
 #include "nesr_kernels.h"
 
@@ -102,6 +103,74 @@ __device__ __forceinline__ void load_regrouped(const uint16_t* p, long long chun
     for (int i = 0; i < 4; ++i) {
         q0[i] = fmaf((float)l[i], LO_INV, (float)h[i]);
         q1[i] = fmaf((float)l[4 + i], LO_INV, (float)h[4 + i]);
+    }
+}
+
+// ---- the 3x3 kernels.  Per-layer (conv3x3_f16x2_kernel): 4 MFMA waves x 2 rows; fused (rdb_f16x2_kernel): Geo<4>'s
+// input tile and DMA rounds, 8 MFMA waves x 1 row.  Both: output tile 8 rows x 32 cols, 32-cout weight slabs.
+constexpr int TW = 32, PW = TW + 2;
+constexpr int WAVES = 4;   // MFMA waves per workgroup of the per-layer kernel
+constexpr int RW = 2;      // rows per MFMA wave of the per-layer kernel
+// DMAW = extra waves that only issue the LDS-DMAs (0: the MFMA waves issue them themselves)
+template <int DMAW>
+struct Geo {
+    static constexpr int LAUNCH_THREADS = 64 * (WAVES + DMAW);
+    static constexpr int THREADS = 64 * (DMAW ? DMAW : WAVES);   // lanes that share one DMA round
+    static constexpr int TH = WAVES * RW;
+    static constexpr int PH = TH + 2;
+    static constexpr int NPIX = PH * PW;
+    static constexpr int IN_ITEMS = 4 * NPIX;   // 16-byte items per input slot
+    static constexpr int IN_ROUNDS = (IN_ITEMS + THREADS - 1) / THREADS;
+    static constexpr int IN_BYTES = IN_ITEMS * 16;
+};
+constexpr int W_ITEMS = 9 * 2 * 2 * 32;   // 16-byte items of one 32-cout weight slab (per K-chunk)
+constexpr int W_BYTES = W_ITEMS * 16;
+
+// The tap address plan (the five tap-steps: conv3x3_f16x2_kernel, "operands") for lane (j16, un, kh) of a wave whose first
+// tile row is `row`: byte offset of its XH fragment of tap-step st_, pixel half nh, in an input slot / of its WH fragment
+// in a weight slab.  (The st_ / nh loops stay in the kernels: moved in here, the per-layer kernel's instructions change.)
+__device__ __forceinline__ int tap_pixel_offset(int st_, int row, int nh, int j16, int un, int kh) {
+    const int dy = st_ < 3 ? un : 2;
+    const int dx = st_ < 3 ? st_ : (st_ == 3 ? un : 2);
+    const int col = 16 * nh + j16 + dx;
+    return ((row + dy) * PW + col) * 64 + ((kh ^ (((col >> 2) & 1) << 1)) << 4);
+}
+__device__ __forceinline__ int tap_weight_offset(int st_, int j16, int un, int kh) {
+    const int dy = st_ < 3 ? un : 2;
+    const int dx = st_ < 3 ? st_ : (st_ == 3 ? un : 2);
+    return ((((dy * 3 + dx) * 2) * 2 + kh) * 32 + j16) * 16;
+}
+// One tap-step's MFMAs for one (cout half, pixel half), a0 | a1 = WH | WL, x0 | x1 = XH | XL: tap-steps 0..3
+__device__ __forceinline__ void mfma_tap3(f16x8 a0, f16x8 a1, f16x8 x0, f16x8 x1, f32x4& mn, f32x4& cr) {
+    cr = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x1, cr, 0, 0, 0);
+    mn = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0, mn, 0, 0, 0);
+    cr = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x0, cr, 0, 0, 0);
+}
+// the last tap alone (a0 = [w_hi | 0], a1 = [w_hi | w_lo], x0 = [x_hi | x_hi], x1 = [x_lo | x_hi])
+__device__ __forceinline__ void mfma_tap2(f16x8 a0, f16x8 a1, f16x8 x0, f16x8 x1, f32x4& mn, f32x4& cr) {
+    mn = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, x0, mn, 0, 0, 0);
+    cr = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, x1, cr, 0, 0, 0);
+}
+// The cout exchange.  C/D layout: lane (pixel j16, k-group g4) holds couts 16 mt + 4 g4 + i; v_permlane16_swap of the
+// mt = 0 (e) / mt = 1 (o) values leaves every lane with 8 consecutive couts of its pixel, v0 | v1 = base .. +3 | +4 .. +7,
+// base 0 / 16 / 8 / 24 for g4 = 0 / 1 / 2 / 3 (tools/probes/mfma16_layout.hip).  All 64 lanes.
+__device__ __forceinline__ void cout_exchange(f32x4 e, f32x4 o, f32x4& v0, f32x4& v1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const auto sw_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(e[i]), __float_as_uint(o[i]), false, false);
+        v0[i] = __uint_as_float(sw_[0]);
+        v1[i] = __uint_as_float(sw_[1]);
+    }
+}
+// the same from the [main | cross] accumulators of the two cout halves: value = main + cross / 2^11
+__device__ __forceinline__ void cout_exchange_acc(const f32x4 (&ae)[2], const f32x4 (&ao)[2], f32x4& v0, f32x4& v1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float e = fmaf(ae[1][i], LO_INV, ae[0][i]);
+        const float o = fmaf(ao[1][i], LO_INV, ao[0][i]);
+        const auto sw_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(e), __float_as_uint(o), false, false);
+        v0[i] = __uint_as_float(sw_[0]);
+        v1[i] = __uint_as_float(sw_[1]);
     }
 }
 

@@ -16,6 +16,14 @@ __device__ __forceinline__ float mul_rn(float a, float b) { float r; asm("v_mul_
 __device__ __forceinline__ float add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
+// XCD-aware work index of this workgroup among `total` (bijective for any count): consecutive workgroup ids go round the
+// 8 XCDs, so XCD x takes the contiguous range of work items that starts at x's share -- neighbours in the work order
+// (a tile's cout groups, adjacent tiles) share an L2.
+__device__ __forceinline__ int xcd_work_index(int total) {
+    const int bid = blockIdx.x, q = total >> 3, r = total & 7, xcd = bid & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // Activation addressing.  Channels are grouped in K-groups of KG channels (8 for f32, 16 for
 // bf16 = 32 bytes, one MFMA K-chunk); element (pixel p, channel c) of a feature map lives at
 //     base + (c / KG) * chunk + p * pix + (c % KG)          (in elements)
@@ -150,7 +158,7 @@ size_t packed_upconv_elems_f16x2(int cin_p, int coutp);   // in 2-byte units
 void pack_upconv_weights_f16x2(const float* folded, int cout, int cin, int cin_p, int coutp, uint16_t* dst);
 
 // One residual dense block (conv1..conv5) per launch, f16-pair form, for frames whose 8x32-pixel tiles all get their
-// own resident workgroup (conv3x3_f16x2.hip, rdb_f16x2_kernel): tiles = rdb_f16x2_tiles(n, h, w) <= compute units.
+// own resident workgroup (rdb_f16x2.hip, rdb_f16x2_kernel): tiles = rdb_f16x2_tiles(n, h, w) <= compute units.
 struct RdbLaunch {
     const void* cur;          // the block's 192-channel buffer (f16-pair layout: [12 chunks][pixels][64 B])
     long long chunk_bytes;

@@ -1,5 +1,6 @@
 // conv3x3(nearest_x2(x)) as four 2x2-tap convolutions on the LOW-resolution input, f16-pair form (conv3x3_f16x2.hip has
-// the arithmetic: x = hi + lo 2^-11, three v_mfma_f32_16x16x32_f16 per product, main + cross accumulators in f32).
+// the arithmetic: x = hi + lo 2^-11, three v_mfma_f32_16x16x32_f16 per product, main + cross accumulators in f32;
+// f16x2_common.h has the pieces the f16-pair kernels share).
 //
 // Output pixel (2y + py, 2x + px) of a 3x3 conv over the nearest-x2 upsample reads only the low-res pixels
 // (y + py - 1 + a, x + px - 1 + b), a, b in {0, 1}: the three kernel rows fall onto two input rows ({0 | 1,2} for py = 0,
@@ -62,11 +63,7 @@ __global__ __launch_bounds__(UTHREADS, 2) void upconv2x2_f16x2_kernel(ConvArgs a
     const int tiles_x = (lw + UTW - 1) / UTW;
     const int tiles_y = (lh + ULH - 1) / ULH;
     const int total = tiles_x * tiles_y * a.n * CG;
-    int idx;
-    {
-        const int bid = blockIdx.x, q = total >> 3, r = total & 7, xcd = bid & 7;
-        idx = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int idx = xcd_work_index(total);
     const int cg = idx % CG;
     int tile = idx / CG;
     const int n = tile / (tiles_x * tiles_y);
@@ -202,8 +199,8 @@ __global__ __launch_bounds__(UTHREADS, 2) void upconv2x2_f16x2_kernel(ConvArgs a
     }
     if (!active) return;
 
-    // ---- epilogue (conv3x3_f16x2_kernel's): lane (pixel j16, k-group g4) holds couts 16 mt + 4 g4 + i; after the permlane16
-    // exchange 8 consecutive couts of its pixel.  The two column parities of a low-res pixel are neighbours in the output
+    // ---- epilogue (conv3x3_f16x2_kernel's): lane (pixel j16, k-group g4) holds couts 16 mt + 4 g4 + i; after the cout
+    // exchange (f16x2_common.h) 8 consecutive couts of its pixel.  The two column parities of a low-res pixel are neighbours in the output
     // row: lanes exchange pieces (ds_bpermute inside their 16-lane row) so that store instruction h writes output pixels
     // 16 h .. 16 h + 15 of the 32 this (row, pixel half) produces -- 16 x 64 B = whole 128-byte lines per instruction.
     if (NESR_UABL & 4) {
@@ -225,14 +222,7 @@ __global__ __launch_bounds__(UTHREADS, 2) void upconv2x2_f16x2_kernel(ConvArgs a
 #pragma unroll
             for (int px = 0; px < 2; ++px) {
                 f32x4 v0, v1;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float e = fmaf(acc[py][px][nh][0][1][i], LO_INV, acc[py][px][nh][0][0][i]);
-                    const float o = fmaf(acc[py][px][nh][1][1][i], LO_INV, acc[py][px][nh][1][0][i]);
-                    const auto sw_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(e), __float_as_uint(o), false, false);
-                    v0[i] = __uint_as_float(sw_[0]);
-                    v1[i] = __uint_as_float(sw_[1]);
-                }
+                cout_exchange_acc(acc[py][px][nh][0], acc[py][px][nh][1], v0, v1);
                 v0 += bz0;
                 v1 += bz1;
                 if (a.lrelu) {

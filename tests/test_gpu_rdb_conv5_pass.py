@@ -5,29 +5,12 @@ launches (NESR_RDB_FUSE=0) -- checked at the smallest shapes where the new code 
 internal size = input size), one RRDB = three dense blocks, so conv5's second residual is both absent and present.
 
 Reference semantics: the dense block of basicsr's RRDBNet (restated in oracle/rrdbnet_ref.py)."""
-import os
-
 import pytest
 import torch
 
+from tests.rdb_pair import launches as _launches, net as _net
+
 pytestmark = pytest.mark.gpu
-
-
-def _net(sd, num_block, fuse):
-    from neural_enhanced_super_resolution_amd import RRDBNet
-    old = os.environ.get("NESR_RDB_FUSE")
-    os.environ["NESR_RDB_FUSE"] = "-1" if fuse else "0"
-    try:
-        n = RRDBNet(3, 3, scale=4, num_block=num_block)
-        n.load_state_dict(sd)
-        n.eval().to("cuda:0")
-        n(torch.zeros(1, 3, 16, 16, device="cuda:0"))        # the context is created with the switch in force
-    finally:
-        if old is None:
-            os.environ.pop("NESR_RDB_FUSE", None)
-        else:
-            os.environ["NESR_RDB_FUSE"] = old
-    return n
 
 
 _cache = {}
@@ -38,18 +21,8 @@ def _pair(num_block):
     if num_block not in _cache:
         from neural_enhanced_super_resolution_amd.synth import synthetic_state_dict
         sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=4, num_block=num_block)
-        _cache[num_block] = (_net(sd, num_block, False), _net(sd, num_block, True))
+        _cache[num_block] = (_net(sd, num_block, False, scale=4), _net(sd, num_block, True, scale=4))
     return _cache[num_block]
-
-
-def _launches(net, x):
-    net.set_kernel_timing(x.device, True)
-    net.kernel_time()                                    # clear
-    net(x)
-    torch.cuda.synchronize()
-    _, launches, _ = net.kernel_time()
-    net.set_kernel_timing(x.device, False)
-    return launches
 
 
 @pytest.mark.parametrize("n,hw", [

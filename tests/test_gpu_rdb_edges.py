@@ -10,10 +10,10 @@ absent, absent, present in place); repeated forwards over two RRDBs (the in-plac
 launches); and both paths against the CPU oracle within the f32-class bound of tests/test_gpu_configs.py (5e-5).
 
 Reference semantics: the dense block of basicsr's RRDBNet (restated in oracle/rrdbnet_ref.py)."""
-import os
-
 import pytest
 import torch
+
+from tests.rdb_pair import net as _net
 
 pytestmark = pytest.mark.gpu
 
@@ -25,23 +25,6 @@ SHAPES = [
     (2, (16, 64)),        # two images of 2 x 2 tiles
 ]
 F32_CLASS = 5e-5          # max abs error against the oracle (tests/test_gpu_configs.py)
-
-
-def _net(sd, num_block, fuse):
-    from neural_enhanced_super_resolution_amd import RRDBNet
-    old = os.environ.get("NESR_RDB_FUSE")
-    os.environ["NESR_RDB_FUSE"] = "-1" if fuse else "0"
-    try:
-        n = RRDBNet(3, 3, scale=4, num_block=num_block)
-        n.load_state_dict(sd)
-        n.eval().to("cuda:0")
-        n(torch.zeros(1, 3, 16, 16, device="cuda:0"))        # the context is created with the switch in force
-    finally:
-        if old is None:
-            os.environ.pop("NESR_RDB_FUSE", None)
-        else:
-            os.environ["NESR_RDB_FUSE"] = old
-    return n
 
 
 _cache = {}
@@ -56,7 +39,7 @@ def _nets(num_block):
         ref = RRDBNetRef(3, 3, scale=4, num_block=num_block)
         ref.load_state_dict(sd, strict=True)
         ref.eval()
-        _cache[num_block] = (_net(sd, num_block, False), _net(sd, num_block, True), ref)
+        _cache[num_block] = (_net(sd, num_block, False, scale=4), _net(sd, num_block, True, scale=4), ref)
     return _cache[num_block]
 
 

@@ -6,41 +6,14 @@ an epoch per launch), and the fused path must be the one that ran (its launch co
 
 Reference semantics: the dense block of basicsr's RRDBNet (un-vendored; restated in oracle/rrdbnet_ref.py), called at
 nesr/nesr.py:887-891 and through RealESRGANer.enhance at standalone/direct_esrgan.py:148."""
-import os
-
 import pytest
 import torch
+
+from tests.rdb_pair import launches as _launches, net as _net
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-3     # BASELINE.json north_star: max abs on the [0, 1] image against the CPU oracle
-
-
-def _net(sd, num_block, fuse, num_in_ch=3, scale=2):
-    from neural_enhanced_super_resolution_amd import RRDBNet
-    old = os.environ.get("NESR_RDB_FUSE")
-    os.environ["NESR_RDB_FUSE"] = "-1" if fuse else "0"
-    try:
-        n = RRDBNet(num_in_ch, 3, scale=scale, num_block=num_block)
-        n.load_state_dict(sd)
-        n.eval().to("cuda:0")
-        n(torch.zeros(1, num_in_ch, 16, 16, device="cuda:0"))        # the context is created with the switch in force
-    finally:
-        if old is None:
-            os.environ.pop("NESR_RDB_FUSE", None)
-        else:
-            os.environ["NESR_RDB_FUSE"] = old
-    return n
-
-
-def _launches(net, x):
-    net.set_kernel_timing(x.device, True)
-    net.kernel_time()                                    # clear
-    net(x)
-    torch.cuda.synchronize()
-    _, launches, _ = net.kernel_time()
-    net.set_kernel_timing(x.device, False)
-    return launches
 
 
 @pytest.mark.parametrize("num_block,hw,scale,num_in_ch", [

@@ -7,39 +7,12 @@ case, so that the epochs of the progress words advance.
 
 Reference semantics: the dense block of basicsr's RRDBNet (restated in oracle/rrdbnet_ref.py); the per-layer path is
 checked against that oracle in test_gpu_rdb_fused.py."""
-import os
-
 import pytest
 import torch
 
+from tests.rdb_pair import launches as _launches, net as _net
+
 pytestmark = pytest.mark.gpu
-
-
-def _net(sd, fuse, scale):
-    from neural_enhanced_super_resolution_amd import RRDBNet
-    old = os.environ.get("NESR_RDB_FUSE")
-    os.environ["NESR_RDB_FUSE"] = "-1" if fuse else "0"
-    try:
-        n = RRDBNet(3, 3, scale=scale, num_block=1)
-        n.load_state_dict(sd)
-        n.eval().to("cuda:0")
-        n(torch.zeros(1, 3, 16, 16, device="cuda:0"))        # the context is created with the switch in force
-    finally:
-        if old is None:
-            os.environ.pop("NESR_RDB_FUSE", None)
-        else:
-            os.environ["NESR_RDB_FUSE"] = old
-    return n
-
-
-def _launches(net, x):
-    net.set_kernel_timing(x.device, True)
-    net.kernel_time()                                    # clear
-    net(x)
-    torch.cuda.synchronize()
-    _, launches, _ = net.kernel_time()
-    net.set_kernel_timing(x.device, False)
-    return launches
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +22,7 @@ def nets(cuda_device):
     out = {}
     for scale in (2, 4):
         sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=scale, num_block=1)
-        out[scale] = (_net(sd, False, scale), _net(sd, True, scale))
+        out[scale] = (_net(sd, 1, False, scale=scale), _net(sd, 1, True, scale=scale))
     return out
 
 
