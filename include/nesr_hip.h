@@ -604,6 +604,60 @@ int nesr_png_encode(int device_id, const void* src_dev, int64_t src_row_bytes, i
                     size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
 
 /*
+ * cv2.imread(path.png, cv2.IMREAD_UNCHANGED) as HIP kernels (csrc/png_decode.hip): the way gray, BGRA and 16-bit frames arrive
+ * (standalone/direct_esrgan.py:130), and the way a run reads what the run before it wrote.  tests/png_decode_ref.py is the
+ * specification.  Supported: depth 8 or 16, colour type 0, 2 or 6, no interlace, at most 65535 x 65535 (C = 1, 3 or 4).  Palette,
+ * gray + alpha, depth 1 / 2 / 4, Adam7: NESR_ERR_UNSUPPORTED.  A malformed file, or a zlib header with CM != 8, a window above 32 KiB,
+ * FDICT set or a bad check value: NESR_ERR_BADFILE.
+ *
+ * nesr_png_parse (host only, never reads at or beyond file + n): the signature; the chunk walk with every length checked; IHDR first,
+ * its CRC checked; IDATs consecutive and at least one; ancillary chunks and PLTE skipped; IEND last.  The CRCs of the other chunks are
+ * not checked: the decoder checks the Adler-32 of the inflated stream instead.  It fills info and the segment plan: with Z the IDAT
+ * payloads joined and D = Z[2 : -4] the deflate stream, a cut is an IDAT boundary strictly inside D whose preceding four bytes of D
+ * are 00 00 FF FF (the empty stored block of a flush), and a segment is the D-bytes between two cuts -- offset: where its first byte
+ * lies in the file, bytes, first, last.  info->contiguous: no segment spans an IDAT boundary, so segment i is file[offset .. offset +
+ * bytes); only such a plan goes to nesr_png_decode.  A file of nesr_png_encode gives one segment per 32 KiB chunk.  segs[0 .. cap)
+ * receives the first cap segments (segs may be null when cap is 0); info->n_segments is set even when cap is smaller, and the call
+ * then returns NESR_ERR_NOFIT: size the table and call again.
+ *
+ * nesr_png_decode: file_dev[0 .. n) the file on the device, segs_dev the info->n_segments segments on the device (8-byte aligned).
+ * Each segment is inflated alone by one wave -- a measuring pass, a scan of the sizes, a writing pass -- then the Adler-32 is checked
+ * and the row filters are undone.  dst_dev: [H, W, C] samples (8 bit: bytes; 16 bit: little-endian words, as nesr_pack_frame takes
+ * them), order NESR_ORDER_RGB or NESR_ORDER_BGR (alpha last; C = 1: ignored but checked), rows dst_row_bytes apart, nothing between
+ * the rows is written.  scratch_dev: nesr_png_decode_scratch_bytes(info) bytes (0 for an info it rejects), 16-byte aligned, about
+ * twice the frame.  *status_dev (4-byte aligned) is 0 after a good decode, else a set of bits, and dst_dev holds no defined image:
+ *   1 a segment's input ran out   2 a code that is in no table, or symbol 286 / 287 / distance 30 / 31   4 LEN != ~NLEN
+ *   8 BTYPE 3 or a broken dynamic header   16 DEPENDENT: a distance that reaches before its segment (a Z_SYNC_FLUSH file; inflate
+ *   it on the host)   32 BFINAL before the last segment, or bytes behind the last block   64 the sizes do not add up to
+ *   H (1 + W bpp)   128 the Adler-32   256 a filter type above 4
+ * A caller reports NESR_ERR_BADFILE for every bit but 16.  No kernel loads beyond n or stores beyond what it was given, whatever the
+ * file holds; a pass that finds the word non-zero does nothing.  Everything is enqueued on hip_stream: no allocation, no
+ * synchronisation, no copy.
+ *
+ * nesr_png_unfilter: the second half alone, for a stream the host inflated (a file of one deflate stream): filtered_dev holds the
+ * H (1 + W bpp) bytes of the filtered stream; scratch_dev: nesr_png_unfilter_scratch_bytes(H, W, C, depth) bytes.  *status_dev: 0 or 256.
+ *
+ * A null pointer, an info or shape outside the list above, a plan that is not contiguous, an unknown order, a stride smaller than a
+ * row, a short or misaligned scratch: NESR_ERR_ARG before any device is touched.
+ */
+typedef struct nesr_png_segment {
+    int64_t offset, bytes;
+    int32_t first, last;
+} nesr_png_segment;
+typedef struct nesr_png_info {
+    int32_t H, W, C, depth, contiguous, n_segments;
+    int64_t stream_bytes;                  /* H (1 + W bpp) */
+    uint32_t adler;                        /* the file's Adler-32 of the filtered stream */
+} nesr_png_info;
+int nesr_png_parse(const uint8_t* file, size_t n, nesr_png_info* info, nesr_png_segment* segs, int cap);
+size_t nesr_png_decode_scratch_bytes(const nesr_png_info* info);
+int nesr_png_decode(int device_id, const uint8_t* file_dev, size_t n, const nesr_png_info* info, const nesr_png_segment* segs_dev, void* dst_dev,
+                    int64_t dst_row_bytes, int order, void* scratch_dev, size_t scratch_bytes, uint32_t* status_dev, void* hip_stream);
+size_t nesr_png_unfilter_scratch_bytes(int H, int W, int C, int depth);
+int nesr_png_unfilter(int device_id, const uint8_t* filtered_dev, int H, int W, int C, int depth, void* dst_dev, int64_t dst_row_bytes, int order,
+                      void* scratch_dev, size_t scratch_bytes, uint32_t* status_dev, void* hip_stream);
+
+/*
  * cv2.resize as HIP kernels (csrc/resize.hip), for a host without torch: upstream's `cv2.resize(output, ..., INTER_LANCZOS4)` behind
  * RealESRGANer.enhance(outscale=...), its `cv2.resize(alpha, ..., INTER_LINEAR)` behind alpha_upsampler != "realesrgan", and the
  * Lanczos paste of _process_with_tiling (nesr/nesr.py:437-446).  cv2's semantics as imgproc.lanczos4_resize / linear_resize_f32 and

@@ -123,6 +123,13 @@ SIGNATURES = {
     "nesr_png_code_lengths": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
     "nesr_png_encode": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
                                    _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
+    "nesr_png_parse": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int]),
+    "nesr_png_decode_scratch_bytes": (_c.c_size_t, [_c.c_void_p]),
+    "nesr_png_decode": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                   _c.c_void_p, _c.c_void_p]),
+    "nesr_png_unfilter_scratch_bytes": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_int]),
+    "nesr_png_unfilter": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                     _c.c_void_p, _c.c_void_p]),
     "nesr_pack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
                                    _c.c_void_p]),
     "nesr_unpack_frame": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64,
@@ -221,6 +228,44 @@ def jpeg_parse(data):
             raise NesrBadFileError(text)
         raise NesrHipError(text)
     return info
+
+
+class PngSegment(ctypes.Structure):
+    """nesr_png_segment"""
+    _fields_ = [("offset", _c.c_int64), ("bytes", _c.c_int64), ("first", _c.c_int32), ("last", _c.c_int32)]
+
+
+class PngInfo(ctypes.Structure):
+    """nesr_png_info"""
+    _fields_ = [("H", _c.c_int32), ("W", _c.c_int32), ("C", _c.c_int32), ("depth", _c.c_int32), ("contiguous", _c.c_int32), ("n_segments", _c.c_int32),
+                ("stream_bytes", _c.c_int64), ("adler", _c.c_uint32)]
+
+
+PNG_DEPENDENT = 16      # the status bit of nesr_png_decode that is no bad file: a distance that reaches before its segment
+
+
+def png_parse(data, cap=None):
+    """nesr_png_parse on the file's bytes -> (PngInfo, array of PngSegment); NesrUnsupportedError / NesrBadFileError as the parser
+    classifies the file.  cap=None: the table is sized by a first call."""
+    data = bytes(data)
+    info = PngInfo()
+    lib = load()
+    segs = (PngSegment * max(cap, 1))() if cap is not None else None
+    rc = lib.nesr_png_parse(data, len(data), ctypes.byref(info), segs, cap or 0)
+    if rc == ERR_NOFIT and cap is None:
+        segs = (PngSegment * info.n_segments)()
+        rc = lib.nesr_png_parse(data, len(data), ctypes.byref(info), segs, info.n_segments)
+    if rc != 0:
+        msg = lib.nesr_last_error()
+        text = f"nesr_png_parse failed ({rc}): {msg.decode() if msg else '?'}"
+        if rc == ERR_UNSUPPORTED:
+            raise NesrUnsupportedError(text)
+        if rc == ERR_BADFILE:
+            raise NesrBadFileError(text)
+        err = NesrHipError(text)
+        err.code, err.info = rc, info
+        raise err
+    return info, segs
 
 
 def load():

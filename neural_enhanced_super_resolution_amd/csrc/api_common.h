@@ -1,5 +1,5 @@
 // Plumbing shared by every file of the C-ABI layer (nesr_api.cpp, rrdb_forward.cpp, band_api.cpp, shard_api.cpp, oneshot_api.cpp,
-// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp): the error string, the try macro, alignment, and the kernel-timing hook of a context.
+// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, and the kernel-timing hook of a context.
 // Not part of the public ABI (that is include/nesr_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -10,6 +10,7 @@
   enhance_image's no-model step              cv2.resize(INTER_CUBIC)                         nesr/nesr.py:597-605
   enhance_image's last call                  cv2.imwrite(path.jpg): baseline JPEG (PINNED)   nesr/nesr.py:639-646
   the iterations' and projects' .png files   cv2.imwrite(path.png): lossless (pixels PINNED) nesr/nesr.py:619-625
+  a .png input (gray, alpha, 16 bit)         cv2.imread(path.png, IMREAD_UNCHANGED) (PINNED) standalone/direct_esrgan.py:130
   (_process_with_tiling's Lanczos paste and the 12-channel builder's 3x3 blur use the same functions: nesr_adapter.py)
 
 PARITY UNPINNED, all of it but the JPEG file (encode_jpeg_u8: libjpeg's integer pipeline, byte for byte): cv2 is not installed here or on the GPU box and the reference holds no output of any of
@@ -959,6 +960,237 @@ def encode_png(frame, order="rgb", use_hip=None):
     stream = deflate.compress(rows.tobytes()) + deflate.flush()
     ihdr = struct.pack(">IIBBBBB", w, h, depth, {1: 0, 3: 2, 4: 6}[c], 0, 0, 0)
     return b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", ihdr) + _png_chunk(b"IDAT", stream) + _png_chunk(b"IEND", b"")
+
+
+# ----------------------------------------------------------------------------------------------- PNG in
+# What inflate=None sends to the device inflater (profiles/png_decode/bench_png_decode.json).  A segment is walked
+# by one lane, about 1.6 us per compressed byte over both passes, and all segments run side by side; the host needs about 11 us per byte
+# of the file.  So the device wins only when the largest segment is small AND small against the file: it won at every measured file with
+# file / largest segment >= 379 (largest segment up to 28,974 bytes) and lost at every one with that ratio <= 188.
+PNG_DEVICE_SEGMENT_MAX = 33 * 1024     # compressed bytes of the largest segment: encode_png's own chunks (<= 32.8 KB) and nothing larger
+PNG_DEVICE_MIN_RATIO = 384             # file bytes / largest segment's bytes: just above the smallest ratio at which the device won
+
+
+def _png_default_on_device(info, segs, nbytes):
+    """inflate=None: True when the file goes to the device inflater (a contiguous plan of at least two segments inside the measured
+    region where that route beat the host's), False for the hybrid route"""
+    largest = max(int(s.bytes) for s in segs[:info.n_segments])
+    return bool(info.contiguous) and info.n_segments >= 2 and largest <= PNG_DEVICE_SEGMENT_MAX and nbytes >= PNG_DEVICE_MIN_RATIO * largest
+
+
+def _png_status_error(who, word):
+    from . import _lib
+    return _lib.NesrBadFileError(f"{who} failed ({_lib.ERR_BADFILE}): the device rejected the file, status {word:#x}", word)
+
+
+def _png_frame(info, device, out):
+    """The [H, W, C] tensor the kernels write (`out` when given, as a 3-d view) and what the caller gets back"""
+    h, w, c = int(info.H), int(info.W), int(info.C)
+    dtype = torch.uint8 if info.depth == 8 else torch.int16
+    if out is None:
+        out = torch.empty((h, w, c), dtype=dtype, device=device)
+    view = out if out.dim() == 3 else out[:, :, None]
+    return view, (out[:, :, 0] if c == 1 and out.dim() == 3 else out)
+
+
+def _png_decode_hip(file_dev, n, info, segs, order, out):
+    """One run of nesr_png_decode (csrc/png_decode.hip): the file and the segment table on the device -> (frame, status word).  One
+    word comes back."""
+    from . import _lib
+    import ctypes
+    import numpy as np
+    lib = _lib.load()
+    view, ret = _png_frame(info, file_dev.device, out)
+    need = int(lib.nesr_png_decode_scratch_bytes(ctypes.byref(info)))
+    scratch = torch.empty(need, dtype=torch.uint8, device=file_dev.device)
+    status = torch.empty(1, dtype=torch.int32, device=file_dev.device)
+    table = np.frombuffer(bytes(segs), np.int64).copy()
+    segs_dev = torch.from_numpy(table).to(file_dev.device)                                        # H2D: 24 bytes per segment
+    _hip_call(file_dev, "nesr_png_decode", _ptr(file_dev), int(n), ctypes.byref(info), _ptr(segs_dev), _ptr(view), _row_bytes(view),
+              _lib.ORDER_BGR if order == "bgr" else _lib.ORDER_RGB, _ptr(scratch), need, _ptr(status))
+    return ret, int(status.item()) & 0xFFFFFFFF                                                  # D2H: 4 bytes (waits for the decode)
+
+
+def _png_idat(data):
+    """The IDAT payloads of a file nesr_png_parse accepted, joined: the zlib stream"""
+    import struct
+    at, parts = 8, []
+    while at + 12 <= len(data):
+        length, kind = struct.unpack(">I4s", data[at:at + 8])
+        if kind == b"IDAT":
+            parts.append(data[at + 8:at + 8 + length])
+        at += 12 + length
+    return b"".join(parts)
+
+
+def _png_inflate_host(data, info):
+    """zlib on the host -> the filtered stream's bytes; NesrBadFileError for a stream zlib rejects or one of the wrong size (status 64)"""
+    from . import _lib
+    import zlib
+    try:
+        stream = zlib.decompress(_png_idat(data))
+    except zlib.error as e:
+        raise _lib.NesrBadFileError(f"decode_png failed ({_lib.ERR_BADFILE}): {e}") from e
+    if len(stream) != info.stream_bytes:
+        raise _png_status_error("decode_png", 64)
+    return stream
+
+
+def _png_unfilter_hip(stream, info, device, order, out):
+    """The hybrid route's device half: the filtered stream goes up, nesr_png_unfilter undoes the filters into the frame"""
+    from . import _lib
+    import numpy as np
+    lib = _lib.load()
+    filt = torch.from_numpy(np.frombuffer(stream, np.uint8).copy()).to(device)                   # H2D: the filtered stream
+    view, ret = _png_frame(info, device, out)
+    need = int(lib.nesr_png_unfilter_scratch_bytes(info.H, info.W, info.C, info.depth))
+    scratch = torch.empty(need, dtype=torch.uint8, device=device)
+    status = torch.empty(1, dtype=torch.int32, device=device)
+    _hip_call(filt, "nesr_png_unfilter", _ptr(filt), int(info.H), int(info.W), int(info.C), int(info.depth), _ptr(view), _row_bytes(view),
+              _lib.ORDER_BGR if order == "bgr" else _lib.ORDER_RGB, _ptr(scratch), need, _ptr(status))
+    word = int(status.item()) & 0xFFFFFFFF                                                       # D2H: 4 bytes
+    if word != 0:
+        raise _png_status_error("nesr_png_unfilter", word)
+    return ret
+
+
+def _png_unfilter_numpy(filt, bpp):
+    """The five PNG row filters undone on the host (numpy): whole-row operations for None / Up, a running sum for Sub, a walk over the
+    pixels for Average / Paeth"""
+    import numpy as np
+    h, n = filt.shape[0], filt.shape[1] - 1
+    raw = np.zeros((h + 1, n + bpp), np.int64)
+    for y in range(h):
+        t, line, cur, up = int(filt[y, 0]), filt[y, 1:].astype(np.int64), raw[y + 1], raw[y]
+        if t == 0:
+            cur[bpp:] = line
+        elif t == 1:
+            lanes = np.concatenate([line, np.zeros((-n) % bpp, np.int64)]).reshape(-1, bpp)
+            cur[bpp:] = (np.cumsum(lanes, axis=0) & 255).reshape(-1)[:n]
+        elif t == 2:
+            cur[bpp:] = (line + up[bpp:]) & 255
+        elif t == 3:
+            for i in range(0, n, bpp):
+                cur[i + bpp:i + 2 * bpp] = (line[i:i + bpp] + ((cur[i:i + bpp] + up[i + bpp:i + 2 * bpp]) >> 1)) & 255
+        elif t == 4:
+            for i in range(0, n, bpp):
+                a, b, c = cur[i:i + bpp], up[i + bpp:i + 2 * bpp], up[i:i + bpp]
+                p = a + b - c
+                pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+                cur[i + bpp:i + 2 * bpp] = (line[i:i + bpp] + np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))) & 255
+        else:
+            raise _png_status_error("decode_png", 256)
+    return np.ascontiguousarray(raw[1:, bpp:].astype(np.uint8))
+
+
+def _png_decode_host(data, info, order):
+    """The specification's route: stdlib zlib and a numpy unfilter -> CPU tensor"""
+    import numpy as np
+    h, w, c, depth = int(info.H), int(info.W), int(info.C), int(info.depth)
+    bpp = c * depth // 8
+    filt = np.frombuffer(_png_inflate_host(data, info), np.uint8).reshape(h, 1 + w * bpp)
+    raw = _png_unfilter_numpy(filt, bpp)
+    img = (raw.view(">u2").astype(np.uint16).view(np.int16) if depth == 16 else raw).reshape(h, w, c)
+    if order == "bgr" and c >= 3:
+        img = np.concatenate([img[:, :, 2::-1], img[:, :, 3:]], axis=2)
+    return torch.from_numpy(np.ascontiguousarray(img[:, :, 0] if c == 1 else img))
+
+
+def _png_decode_pillow(data, order):
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError("decode_png: a palette, gray + alpha, 1 / 2 / 4-bit or interlaced file needs Pillow") from e
+    import io
+    import numpy as np
+    img = Image.open(io.BytesIO(bytes(data)))
+    if img.format != "PNG":
+        raise ValueError(f"decode_png: a PNG file, got {img.format}")
+    if img.mode in ("I;16", "I;16B", "I"):
+        arr = np.asarray(img).astype(np.uint16).view(np.int16)
+    else:
+        if img.mode not in ("L", "RGB", "RGBA"):
+            img = img.convert("RGBA" if img.mode in ("LA", "PA") or "transparency" in img.info else ("L" if img.mode == "1" else "RGB"))
+        arr = np.asarray(img)
+    if arr.ndim == 3 and order == "bgr":
+        arr = np.concatenate([arr[:, :, 2::-1], arr[:, :, 3:]], axis=2)
+    return torch.from_numpy(np.array(arr))
+
+
+def decode_png(data, order="rgb", device=None, use_hip=None, inflate=None, out=None):
+    """cv2.imread(path.png, cv2.IMREAD_UNCHANGED)'s pixels (standalone/direct_esrgan.py:130) for a PNG file's bytes -> tensor [H, W]
+    (gray), [H, W, 3] or [H, W, 4] (order "rgb" or "bgr": the channel that comes first; alpha stays last); uint8, or for a 16-bit file
+    int16 carrying the uint16 bit pattern (frame_io's convention, what encode_png takes).  Non-interlaced files of depth 8 or 16 and
+    colour type 0, 2 or 6 are decoded here; the chunk CRCs are not checked, the Adler-32 of the inflated stream is.
+
+    On a ROCm device (device=None: the current one when there is one) two routes end in the same frame (csrc/png_decode.hip):
+      all-device   the file goes up; every segment between two flush points (nesr_png_parse: an IDAT boundary behind 00 00 FF FF) is
+                   inflated by its own wave, then the filters are undone.  encode_png's own files are one segment per 32 KiB chunk.
+      hybrid       stdlib zlib inflates on the host, the filtered stream goes up, nesr_png_unfilter finishes.
+    inflate=None takes the all-device route where it was measured faster than the host's (_png_default_on_device: a contiguous plan
+    of at least two segments, the largest at most PNG_DEVICE_SEGMENT_MAX compressed bytes and at most 1 / PNG_DEVICE_MIN_RATIO of the
+    file: encode_png's files from about 2160p up, not its 1024 x 1024 ones), and falls back to the hybrid route when a segment proves
+    DEPENDENT on an earlier one (Z_SYNC_FLUSH files).  inflate="device" forces the device inflater on any contiguous plan (a one-stream file is one segment, one
+    wave) and raises NesrUnsupportedError for a plan that is not contiguous or is dependent; inflate="host" forces the hybrid route.
+    `out`: a window [H, W, C] (or [H, W]) of the frame's dtype on that device; its rows may be strided, nothing outside it is written.
+    use_hip=False or a CPU device: stdlib zlib and a numpy unfilter, no Pillow needed.  use_hip=None hands a kind the kernels do not
+    take (palette, gray + alpha, 1 / 2 / 4 bit, Adam7) to Pillow and copies the frame up; use_hip=True raises NesrUnsupportedError.
+    A malformed file, and any device status but DEPENDENT, raises NesrBadFileError (`status`: the bits)."""
+    from . import _lib
+    if order not in ("rgb", "bgr"):
+        raise ValueError(f"decode_png: order must be 'rgb' or 'bgr', got {order!r}")
+    if inflate not in (None, "device", "host"):
+        raise ValueError(f"decode_png: inflate must be None, 'device' or 'host', got {inflate!r}")
+    if device is None:
+        device = out.device if out is not None else torch.device("cuda" if torch.cuda.is_available() else "cpu")
+    device = torch.device(device)
+    on_gpu = device.type == "cuda"
+    if use_hip is None:
+        use_hip, fallback = on_gpu, True
+    else:
+        fallback = False
+    if use_hip and not on_gpu:
+        raise ValueError(f"decode_png: the HIP kernels run on the ROCm device, got {device}")
+    data = bytes(data)
+    try:
+        info, segs = _lib.png_parse(data)
+    except _lib.NesrUnsupportedError:
+        if not fallback:
+            raise
+        frame = _png_decode_pillow(data, order).to(device)
+        if out is not None:
+            out.copy_(frame.reshape(out.shape))
+            return out
+        return frame
+    if not use_hip:
+        frame = _png_decode_host(data, info, order).to(device)
+        if out is not None:
+            out.copy_(frame.reshape(out.shape))
+            return out
+        return frame
+    if out is not None:
+        shape = (info.H, info.W) if info.C == 1 else (info.H, info.W, info.C)
+        dtype = torch.uint8 if info.depth == 8 else torch.int16
+        ok = out.dtype == dtype and out.device.type == "cuda" and (tuple(out.shape) == shape or tuple(out.shape) == (info.H, info.W, info.C))
+        if not ok or not _rows_ok(out if out.dim() == 3 else out[:, :, None], (1, 3, 4)):
+            raise ValueError(f"decode_png: out must be a {dtype} {shape} window on the ROCm device with contiguous pixels in a row, got "
+                             f"{out.dtype} {tuple(out.shape)} on {out.device}")
+    on_device = inflate == "device" or (inflate is None and _png_default_on_device(info, segs, len(data)))
+    if on_device:
+        if not info.contiguous:
+            raise _lib.NesrUnsupportedError(f"decode_png failed ({_lib.ERR_UNSUPPORTED}): a deflate segment spans an IDAT boundary; the device "
+                                            "inflater takes contiguous plans (inflate='host' or None)")
+        import numpy as np
+        file_dev = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(device)             # H2D: the file
+        frame, word = _png_decode_hip(file_dev, len(data), info, segs, order, out)
+        if word == 0:
+            return frame
+        if word != _lib.PNG_DEPENDENT:
+            raise _png_status_error("nesr_png_decode", word)
+        if inflate == "device":
+            raise _lib.NesrUnsupportedError(f"decode_png failed ({_lib.ERR_UNSUPPORTED}): a segment depends on the one before it (a "
+                                            "Z_SYNC_FLUSH file); inflate='host' or None")
+    return _png_unfilter_hip(_png_inflate_host(data, info), info, device, order, out)
 
 
 def _jpeg_decode_hip(file_dev, n, info, order, out):

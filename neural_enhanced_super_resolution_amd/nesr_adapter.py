@@ -355,8 +355,8 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     its trace are what they were without them.  use_hip goes to every stage (None: the HIP kernels where they apply; False: the
     torch chains, the same bits).  encode="jpeg" or ("jpeg", quality): what enhance_image writes in the end (cv2.imwrite,
     nesr.py:639-646) -- the bytes of the final RGB frame's JPEG file (quality 95 unless given) instead of the ndarray, encoded on the
-    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home.  image_rgb may be a JPEG file's bytes: they are
-    decoded on the device first (imgproc.decode_jpeg_u8), so only files cross the bus.  png=True: the final RGB frame's lossless PNG
+    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home.  image_rgb may be a JPEG or an 8-bit PNG file's bytes:
+    they are decoded on the device first (imgproc.decode_jpeg_u8 / decode_png), so only files cross the bus.  png=True: the final RGB frame's lossless PNG
     file instead (what standalone/superres_project.py:203-206 always writes), encoded on the device (imgproc.encode_png); together
     with `encode` it raises ValueError, and encode="png" stays an error.  intermediates=<list>: with config["intermediate_saves"]
     true it receives each iteration's frame as PNG bytes, the reference's intermediate_iter{n}.png (nesr.py:619-625), encoded where
@@ -382,7 +382,16 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     if isinstance(image_rgb, (bytes, bytearray, memoryview)):
         # enhance_image's cv2.imread + cvtColor(BGR2RGB) (nesr.py:661-666) for a JPEG file's bytes: decoded on `device`, RGB order
         from . import imgproc
-        image_rgb = imgproc.decode_jpeg_u8(bytes(image_rgb), order="rgb", device=device)
+        if bytes(image_rgb[:8]) == b"\x89PNG\r\n\x1a\n":
+            # a PNG file under cv2.imread's default flag: three 8-bit channels, gray expanded, alpha dropped.  cv2's 16 -> 8 bit
+            # conversion is not restated here: a 16-bit file is an error
+            image_rgb = imgproc.decode_png(bytes(image_rgb), order="rgb", device=device)
+            if image_rgb.dtype != torch.uint8:
+                raise ValueError("enhance_iterations: a 16-bit PNG file (cv2.imread's default flag would reduce it to 8 bits; decode it yourself)")
+            if image_rgb.dim() == 3:
+                image_rgb = image_rgb[:, :, :3].contiguous()
+        else:
+            image_rgb = imgproc.decode_jpeg_u8(bytes(image_rgb), order="rgb", device=device)
         if image_rgb.dim() == 2:                                # (cv2.imread's default flag gives three channels for a gray file)
             image_rgb = image_rgb[:, :, None].expand(-1, -1, 3).contiguous()
     current = image_rgb

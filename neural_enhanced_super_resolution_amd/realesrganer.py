@@ -767,8 +767,9 @@ class RealESRGANer:
     def _device_frame_ok(self, img):
         """A frame enhance_float would take (gray, BGRA, 16 bit; 8-bit BGR has routes of its own) on a HIP model of three channels
         in and out whose output is `scale` times its input: the frame stays on the device (_enhance_frame_on_device)."""
-        if isinstance(img, torch.Tensor):       # enhance_file's frame: uint8, gray or BGR, on the device
-            return DEVICE_FRAMES and self._three_channel_hip() and img.dtype == torch.uint8 and img.numel() != 0 and img.ndim in (2, 3)
+        if isinstance(img, torch.Tensor):       # enhance_file's / enhance_image_file's frame, on the device: uint8, or int16 carrying uint16
+            return (DEVICE_FRAMES and self._three_channel_hip() and img.dtype in (torch.uint8, torch.int16) and img.numel() != 0
+                    and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))))
         return (DEVICE_FRAMES and self._three_channel_hip() and isinstance(img, np.ndarray) and img.dtype in (np.uint8, np.uint16)
                 and img.size != 0 and (img.ndim == 2 or (img.ndim == 3 and img.shape[2] in (3, 4))))
 
@@ -776,7 +777,10 @@ class RealESRGANer:
     def _frame_kind(img):
         """(max_range, img_mode) as enhance_float decides them on the host: a frame whose maximum is at most 256 counts as 8-bit
         range whatever its dtype (a uint16 frame that dark comes back as uint8), the mode follows the shape."""
-        max_range = 255 if isinstance(img, torch.Tensor) else (65535 if np.max(img) > 256 else 255)     # (a tensor: enhance_file's uint8 frame)
+        if isinstance(img, torch.Tensor):       # a frame decoded on the device: the maximum is a device reduction, 4 bytes come home
+            max_range = 65535 if img.dtype == torch.int16 and int((img.to(torch.int32) & 0xFFFF).max().item()) > 256 else 255
+        else:
+            max_range = 65535 if np.max(img) > 256 else 255
         return max_range, "L" if img.ndim == 2 else ("RGBA" if img.shape[2] == 4 else "RGB")
 
     def _frame_inflight_ok(self, img):
@@ -968,6 +972,48 @@ class RealESRGANer:
         if self._multi() or not (self._u8_on_device_ok(frame) or self._device_frame_ok(frame)):
             return frame.cpu().numpy()
         return frame
+
+    def _read_image(self, data_or_path, who):
+        """_read_jpeg for a JPEG or a PNG file, told apart by signature -> (frame, "jpeg" | "png").  A PNG file gives IMREAD_UNCHANGED's
+        frame (imgproc.decode_png: csrc/png_decode.hip): gray stays [H, W], alpha is kept, 16 bit stays 16 bit -- on the device as uint8
+        or as int16 carrying the uint16 pattern, on the host (the routes that assemble there) as uint8 / uint16."""
+        from . import frame_io, imgproc
+        if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+            data = bytes(data_or_path)
+        else:
+            with open(data_or_path, "rb") as f:
+                data = f.read()
+        if data[:2] == b"\xff\xd8":
+            return self._read_jpeg(data, who), "jpeg"
+        if data[:8] != b"\x89PNG\r\n\x1a\n":
+            raise ValueError(f"{who}: neither a JPEG file (SOI) nor a PNG file (signature)")
+        frame = imgproc.decode_png(data, order="bgr", device=self.device)
+        if self._multi() or not (self._u8_on_device_ok(frame) or self._device_frame_ok(frame)):
+            return frame_io.frame_to_numpy(frame.cpu()), "png"
+        return frame, "png"
+
+    @torch.no_grad()
+    def enhance_image_file(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance(cv2.imread(path, cv2.IMREAD_UNCHANGED)) for a JPEG or a PNG file given as bytes or as a path
+        (standalone/direct_esrgan.py:130): (ndarray, img_mode), bit for bit enhance() of the host-decoded frame.  The file's bytes go
+        up (a PNG of one deflate stream: its inflated stream), the frame is born on the device and handed to enhance()'s routes as a
+        device tensor.  enhance_file* stay JPEG-only."""
+        img, _ = self._read_image(data_or_path, "enhance_image_file")
+        return self._again_if_gave_up(lambda: self._enhance_once(img, outscale, alpha_upsampler))
+
+    @torch.no_grad()
+    def enhance_image_file_to(self, data_or_path, fmt=None, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+        """enhance_image_file followed by cv2.imwrite, the file as bytes: (bytes, img_mode).  fmt=None writes the input's own format
+        (standalone/direct_esrgan.py:130,169: read unchanged, write with the input's extension); "png" or "jpeg" force one.  A JPEG
+        file of an alpha or 16-bit frame is enhance_jpeg's ValueError."""
+        if fmt not in (None, "png", "jpeg"):
+            raise ValueError(f"enhance_image_file_to: fmt must be None, 'png' or 'jpeg', got {fmt!r}")
+        img, kind = self._read_image(data_or_path, "enhance_image_file_to")
+        if (fmt or kind) == "png":
+            return self._enhance_to_png(img, outscale, alpha_upsampler)
+        if img.dtype not in (np.uint8, torch.uint8) or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
+            raise ValueError(f"enhance_image_file_to: a JPEG file holds neither alpha nor 16 bits, the frame is {img.dtype} {tuple(img.shape)}")
+        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler)
 
     @torch.no_grad()
     def enhance_file(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):
