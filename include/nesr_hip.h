@@ -909,17 +909,23 @@ int nesr_segformer_load_weight(nesr_segformer* ctx, const char* key, const float
 int nesr_segformer_finalize(nesr_segformer* ctx);
 /*
  * `outputs = model(pixel_values); outputs.logits` (nesr/nesr.py:713, 716): pixel_values_dev [1, 3, H, W] f32 -> logits_dev
- * [1, num_labels, H/4, W/4] f32, both on the context's device.  N must be 1, H and W multiples of 32 and H W <= 2^26
+ * [1, num_labels, oh, ow] f32, both on the context's device.  N must be 1, H and W multiples of 32 and H W <= 2^26
  * (NESR_ERR_ARG otherwise).
+ * The entry takes no capacity: it writes num_labels * oh * ow floats, (oh, ow) being the first stage's token grid, which
+ * nesr_segformer_output_size gives for the same patch_sizes, strides, H and W (H/4 x W/4 at B0's 7 x 7 / stride 4 patch embed;
+ * every stage is a patch_sizes[i] x patch_sizes[i] conv of stride strides[i] with patch_sizes[i] / 2 padding).  The caller
+ * sizes logits_dev by it.  nesr_segformer_output_size touches no device and needs no context.
  * Enqueued on hip_stream; the workspace grows on the first call for a larger size (that call synchronises the device).
  */
+int nesr_segformer_output_size(int num_encoder_blocks, const int* patch_sizes, const int* strides, int H, int W, int* out_h, int* out_w);
 int nesr_segformer_forward_f32(nesr_segformer* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* logits_dev,
                                void* hip_stream);
 /*
  * nesr/nesr.py:701-716 on an [H, W, 3] u8 RGB frame on the device: `pil_image.resize(new_size, Image.LANCZOS)` when
  * max(W, H) > 1024 (new_size = (int(W s), int(H s)), s = 1024 / max(W, H)), the extractor's resize to 512 x 512 (PIL BILINEAR) and
  * normalisation ((v / 255 - mean) / std, ImageNet's), the network, `logits.argmax(dim=1)` at the logits' own size: class_map_dev
- * [128, 128] u8 (capacity: its bytes, at least 128 * 128), *out_h = *out_w = 128.  The lowest class wins a tie; the logits are never
+ * [oh, ow] u8 with (oh, ow) = nesr_segformer_output_size(..., 512, 512): 128 x 128 at B0 (capacity: the bytes class_map_dev holds,
+ * at least oh * ow, NESR_ERR_ARG otherwise), *out_h = oh, *out_w = ow.  The lowest class wins a tie; the logits are never
  * written to memory.  The map's resize back to the frame (:719-724) is the caller's, on the mask (see nesr_segment_enhance_u8).
  * nesr_segformer_preprocess_u8: the pre-processing alone, pixel_values_dev [1, 3, 512, 512] f32 (two launches, four above 1024).
  */

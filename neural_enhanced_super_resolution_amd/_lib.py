@@ -153,6 +153,7 @@ SIGNATURES = {
     "nesr_segformer_num_tensors": (_c.c_int, [_c.c_void_p]),
     "nesr_segformer_load_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
     "nesr_segformer_finalize": (_c.c_int, [_c.c_void_p]),
+    "nesr_segformer_output_size": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "nesr_segformer_forward_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "nesr_segformer_segment_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
                                              _c.c_void_p]),

@@ -277,15 +277,17 @@ SegFused fused_zero() {
     return a;
 }
 
-void stage_dims(const nesr_segformer* c, int H, int W, int* sh, int* sw) {
+// the token grid of every stage: a k x k conv of stride s with k / 2 padding, as torch sizes it
+void stage_dims(int nst, const int* patch, const int* stride, int H, int W, int* sh, int* sw) {
     int h = H, w = W;
-    for (int i = 0; i < c->nst; ++i) {
-        const int k = c->patch[i], p = k / 2;
-        h = (h + 2 * p - k) / c->stride[i] + 1;
-        w = (w + 2 * p - k) / c->stride[i] + 1;
+    for (int i = 0; i < nst; ++i) {
+        const int k = patch[i], p = k / 2;
+        h = (h + 2 * p - k) / stride[i] + 1;
+        w = (w + 2 * p - k) / stride[i] + 1;
         sh[i] = h, sw[i] = w;
     }
 }
+void stage_dims(const nesr_segformer* c, int H, int W, int* sh, int* sw) { stage_dims(c->nst, c->patch, c->stride, H, W, sh, sw); }
 
 struct SegWs {
     size_t x, xn, q, kv, h1, feat, proj[SEG_MAX_STAGES], total;
@@ -705,6 +707,20 @@ int nesr_segformer_finalize(nesr_segformer* c) {
     }
     NESR_TRY(hipMemcpy(c->d_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
     c->finalized = true;
+    return NESR_OK;
+}
+
+int nesr_segformer_output_size(int num_encoder_blocks, const int* patch_sizes, const int* strides, int H, int W, int* out_h, int* out_w) {
+    if (!patch_sizes || !strides || !out_h || !out_w) return set_error(NESR_ERR_ARG, "nesr_segformer_output_size: null pointer");
+    if (num_encoder_blocks < 1 || num_encoder_blocks > SEG_MAX_STAGES)
+        return set_error(NESR_ERR_ARG, "nesr_segformer_output_size: num_encoder_blocks must be 1 .. " + std::to_string(SEG_MAX_STAGES));
+    for (int i = 0; i < num_encoder_blocks; ++i)
+        if (patch_sizes[i] < 1 || patch_sizes[i] > 15 || strides[i] < 1 || strides[i] > 8)
+            return set_error(NESR_ERR_ARG, "nesr_segformer_output_size: patch_sizes must be 1 .. 15 and strides 1 .. 8");
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 26)) return set_error(NESR_ERR_ARG, "nesr_segformer_output_size: an input of 1 .. 2^26 pixels");
+    int sh[SEG_MAX_STAGES], sw[SEG_MAX_STAGES];
+    stage_dims(num_encoder_blocks, patch_sizes, strides, H, W, sh, sw);
+    *out_h = sh[0], *out_w = sw[0];
     return NESR_OK;
 }
 

@@ -5,8 +5,8 @@ kernels behind the C ABI (csrc/segformer.hip, csrc/segformer_pre.hip, csrc/segfo
 The module owns ordinary torch Parameters and buffers under ``transformers``-5's names
 (``segformer.stages.{i}.blocks.{j}.attention.q_proj.weight`` ...), takes a state dict of either key generation (the published
 checkpoint carries the transformers-4 names) and has no torch implementation of its forward: ``forward(pixel_values)`` gives the
-logits [1, num_labels, H/4, W/4] and ``segment(frame)`` the class map of an [H, W, 3] uint8 RGB frame, both on the ROCm device;
-a tensor anywhere else raises.  ``segment`` restates the reference's pre-processing (a PIL LANCZOS resize when the longer side
+logits [1, num_labels, oh, ow] at the first stage's token grid (H/4 x W/4 at B0; ``output_size(H, W)``) and ``segment(frame)``
+the class map of an [H, W, 3] uint8 RGB frame, both on the ROCm device; a tensor anywhere else raises.  ``segment`` restates the reference's pre-processing (a PIL LANCZOS resize when the longer side
 exceeds 1024, the extractor's PIL BILINEAR resize to 512 x 512, its normalisation) and takes the argmax at the logits' own size,
 as the reference does (nesr/nesr.py:716); the logits never reach memory there.  Calling the object with a uint8 HWC frame is
 ``segment``, so it goes straight into ``enhance_iterations(segmenter=...)``.
@@ -24,6 +24,7 @@ from torch import nn
 from . import _lib
 
 PIL_LANCZOS, PIL_BILINEAR = 1, 2      # PIL.Image's filter numbers: the `filter` of nesr_pil_resize_u8
+MODEL_SIZE = 512                      # the side of the image the extractor makes of a frame (segment, pixel_values)
 
 B0 = dict(num_channels=3, num_encoder_blocks=4, depths=(2, 2, 2, 2), sr_ratios=(8, 4, 2, 1), hidden_sizes=(32, 64, 160, 256),
           patch_sizes=(7, 3, 3, 3), strides=(4, 2, 2, 2), num_attention_heads=(1, 2, 5, 8), mlp_ratios=(4, 4, 4, 4),
@@ -248,8 +249,19 @@ class SegFormer(nn.Module):
                                "(there is no CPU or PyTorch fallback)")
 
     # ------------------------------------------------------------------ forward
+    def output_size(self, h, w):
+        """(oh, ow) of the logits of an h x w input: the first stage's token grid, as the library computes it
+        (nesr_segformer_output_size; H/4 x W/4 at B0).  Needs no device."""
+        c = self.config
+        n = c["num_encoder_blocks"]
+        oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().nesr_segformer_output_size(n, (ctypes.c_int * n)(*c["patch_sizes"]), (ctypes.c_int * n)(*c["strides"]), int(h), int(w),
+                                                          ctypes.byref(oh), ctypes.byref(ow)), "nesr_segformer_output_size")
+        return oh.value, ow.value
+
     def forward(self, pixel_values):
-        """pixel_values [1, 3, H, W] float32 on the device (H, W multiples of 32) -> logits [1, num_labels, H/4, W/4]."""
+        """pixel_values [1, 3, H, W] float32 on the device (H, W multiples of 32) -> logits [1, num_labels, oh, ow],
+        (oh, ow) = output_size(H, W)."""
         if pixel_values.dtype == torch.uint8 and pixel_values.dim() == 3:
             return self.segment(pixel_values)
         x = pixel_values
@@ -260,7 +272,7 @@ class SegFormer(nn.Module):
         n, ch, h, w = x.shape
         with torch.cuda.device(x.device):
             handle = self._context(x.device)
-            out = torch.empty((1, self.config["num_labels"], max(h // 4, 1), max(w // 4, 1)), dtype=torch.float32, device=x.device)
+            out = torch.empty((1, self.config["num_labels"]) + self.output_size(h, w), dtype=torch.float32, device=x.device)
             stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
             _lib.check(_lib.load().nesr_segformer_forward_f32(handle, ctypes.c_void_p(x.data_ptr()), n, ch, h, w,
                                                               ctypes.c_void_p(out.data_ptr()), stream), "nesr_segformer_forward_f32")
@@ -268,8 +280,9 @@ class SegFormer(nn.Module):
         return out
 
     def segment(self, frame):
-        """[H, W, 3] uint8 RGB tensor on the device -> the class map, uint8 [128, 128] on the device (the argmax of the logits
-        of the 512 x 512 image the reference's extractor makes of the frame; ties take the lowest class)."""
+        """[H, W, 3] uint8 RGB tensor on the device -> the class map, uint8 [oh, ow] = output_size(512, 512) on the device
+        (128 x 128 at B0; the argmax of the logits of the 512 x 512 image the reference's extractor makes of the frame; ties
+        take the lowest class)."""
         self._require_device(frame, "segment")
         if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8 or frame.numel() == 0:
             raise ValueError(f"SegFormer.segment: an [H, W, 3] uint8 tensor, got {frame.dtype} {tuple(frame.shape)}")
@@ -277,7 +290,7 @@ class SegFormer(nn.Module):
         h, w = frame.shape[:2]
         with torch.cuda.device(frame.device):
             handle = self._context(frame.device)
-            out = torch.empty((128, 128), dtype=torch.uint8, device=frame.device)
+            out = torch.empty(self.output_size(MODEL_SIZE, MODEL_SIZE), dtype=torch.uint8, device=frame.device)
             oh, ow = ctypes.c_int(0), ctypes.c_int(0)
             stream = ctypes.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
             _lib.check(_lib.load().nesr_segformer_segment_u8(handle, ctypes.c_void_p(frame.data_ptr()), h, w, ctypes.c_void_p(out.data_ptr()),
@@ -295,7 +308,7 @@ class SegFormer(nn.Module):
         frame = frame.contiguous()
         with torch.cuda.device(frame.device):
             handle = self._context(frame.device)
-            out = torch.empty((1, 3, 512, 512), dtype=torch.float32, device=frame.device)
+            out = torch.empty((1, 3, MODEL_SIZE, MODEL_SIZE), dtype=torch.float32, device=frame.device)
             stream = ctypes.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
             _lib.check(_lib.load().nesr_segformer_preprocess_u8(handle, ctypes.c_void_p(frame.data_ptr()), frame.shape[0], frame.shape[1],
                                                                 ctypes.c_void_p(out.data_ptr()), stream), "nesr_segformer_preprocess_u8")

@@ -104,15 +104,90 @@ def seeded_frame(h, w, seed=0):
 
 
 # ------------------------------------------------------------------------------------------------ the network
-def segformer_forward(sd, x, **cfg):
-    """Logits [1, num_labels, H/4, W/4] of pixel_values x [N, 3, H, W] in x's dtype (sd: transformers-5 names, any float dtype)."""
+# One named fault at a time, each something an edit of csrc/segformer.hip or segformer_api.cpp could plausibly introduce; fault=None
+# is the pinned restatement.  tests/segformer_cases.py builds the inputs on which each of them shows.
+LN_SITES = ("patch", "before", "sr", "after", "stage")
+FAULTS = tuple("ln_eps_" + s for s in LN_SITES) + (
+    "bn_eps",                # BatchNorm folded with eps 1e-6
+    "bn_no_var",             # BatchNorm folded without its running variance
+    "gelu_tanh",             # the tanh approximation instead of erf
+    "softmax_scale_c",       # 1 / sqrt(C) instead of 1 / sqrt(head dimension 32)
+    "no_alpha_rescale",      # the running sum and accumulator not rescaled when a later 256-key chunk raises the maximum
+    "no_alpha_rescale_sum", "no_alpha_rescale_acc",               # only the running sum / only the accumulator not rescaled
+    "pad_key_zero",          # the keys that pad a chunk to a multiple of 32 score 0 instead of -inf
+    "dw_wrap",               # the depthwise 3 x 3 reads across a row end instead of zero padding
+    "patch_pad_s0", "patch_pad_s1",        # the patch conv of stage 0 (NCHW image) / a later stage (NHWC grid) padded one off
+    "patch_taps_s0", "patch_taps_s1",      # its taps read in (kx, ky) order
+    "sr_ceil",               # the sequence reduction keeps the edge that the floor drops (zero filled)
+    "up_align_corners", "up_no_clamp", "concat_first_first",      # the decode head
+)
+MAP_FAULTS = ("argmax_highest_tie", "argmax_pad_label")           # class_map's
+KEY_CHUNK = 256              # SEG_KCH
+
+
+def _attention(q, kk, vv, scale, fault, taps):
+    s = torch.matmul(q, kk.transpose(2, 3)) * scale
+    if taps is not None:
+        taps.setdefault("scores", []).append(s)
+        taps.setdefault("keys", []).append(kk)
+    if fault == "pad_key_zero":
+        npad = -s.shape[-1] % 32
+        s = torch.cat([s, s.new_zeros(s.shape[:-1] + (npad,))], dim=-1)
+        vv = torch.cat([vv, vv.new_zeros(vv.shape[:2] + (npad, vv.shape[3]))], dim=2)
+    if fault not in ("no_alpha_rescale", "no_alpha_rescale_sum", "no_alpha_rescale_acc"):
+        return torch.matmul(torch.softmax(s, dim=-1), vv)
+    # the kernel's online softmax over chunks of KEY_CHUNK keys, with the rescale by alpha left out of the sum, the accumulator or both
+    m = s.new_full(s.shape[:-1] + (1,), -math.inf)
+    total, o = torch.zeros_like(m), 0.0
+    for c0 in range(0, s.shape[-1], KEY_CHUNK):
+        sc = s[..., c0:c0 + KEY_CHUNK]
+        m_new = torch.maximum(m, sc.max(dim=-1, keepdim=True).values)
+        alpha = torch.exp(m - m_new)
+        p = torch.exp(sc - m_new)
+        total = total * (1.0 if fault != "no_alpha_rescale_acc" else alpha) + p.sum(dim=-1, keepdim=True)
+        o = o * (1.0 if fault != "no_alpha_rescale_sum" else alpha) + torch.matmul(p, vv[:, :, c0:c0 + KEY_CHUNK])
+        m = m_new
+    return o / total
+
+
+def _dwconv_wrapping(y, w, b):
+    """Depthwise 3 x 3 whose column taps run on into the neighbouring row of the row-major token grid."""
+    n, ch, hh, ww = y.shape
+    flat = F.pad(F.pad(y, (0, 0, 1, 1)).flatten(2), (1, 1))
+    out = b.view(1, -1, 1).expand(n, ch, hh * ww).clone()
+    for dy in range(3):
+        for dx in range(3):
+            at = dy * ww + dx
+            out = out + w[:, 0, dy, dx].view(1, -1, 1) * flat[:, :, at:at + hh * ww]
+    return out.reshape(n, ch, hh, ww)
+
+
+def _upsample_unclamped(t, size):
+    """Bilinear, align_corners=False, the source coordinate not clamped at 0 (the first rows and columns extrapolate)."""
+    def taps(n_in, n_out):
+        src = (n_in / n_out) * (torch.arange(n_out, dtype=t.dtype) + 0.5) - 0.5
+        i0 = src.trunc().clamp(0, n_in - 1).long()
+        return i0, (i0 + 1).clamp(max=n_in - 1), src - i0.to(t.dtype)
+    y0, y1, ly = taps(t.shape[2], size[0])
+    x0, x1, lx = taps(t.shape[3], size[1])
+    ly, lx = ly.view(-1, 1), lx.view(1, -1)
+    top = t[:, :, y0][:, :, :, x0] * (1 - lx) + t[:, :, y0][:, :, :, x1] * lx
+    bot = t[:, :, y1][:, :, :, x0] * (1 - lx) + t[:, :, y1][:, :, :, x1] * lx
+    return top * (1 - ly) + bot * ly
+
+
+def segformer_forward(sd, x, fault=None, taps=None, **cfg):
+    """Logits [N, num_labels, oh, ow] of pixel_values x [N, 3, H, W] in x's dtype (sd: transformers-5 names, any float dtype);
+    (oh, ow) is the first stage's token grid, H/4 x W/4 at B0.  fault: one of FAULTS, a deliberately wrong network (None: the pinned
+    one).  taps: a dict that receives the scaled attention scores and the keys of every block, in order, under "scores" and "keys"."""
+    assert fault is None or fault in FAULTS, fault
     c = dict(B0)
     c.update(cfg)
     dt = x.dtype
     p = {k: v.to(dt) for k, v in sd.items() if v.dtype.is_floating_point}
 
-    def ln(t, name):
-        return F.layer_norm(t, (t.shape[-1],), p[name + ".weight"], p[name + ".bias"], LN_EPS)
+    def ln(t, name, site):
+        return F.layer_norm(t, (t.shape[-1],), p[name + ".weight"], p[name + ".bias"], 1e-6 if fault == "ln_eps_" + site else LN_EPS)
 
     def lin(t, name):
         return F.linear(t, p[name + ".weight"], p[name + ".bias"])
@@ -122,33 +197,45 @@ def segformer_forward(sd, x, **cfg):
     for i in range(c["num_encoder_blocks"]):
         s = f"segformer.stages.{i}"
         k = c["patch_sizes"][i]
-        h = F.conv2d(h, p[s + ".patch_embeddings.proj.weight"], p[s + ".patch_embeddings.proj.bias"], stride=c["strides"][i], padding=k // 2)
+        wpe = p[s + ".patch_embeddings.proj.weight"]
+        at = "_s0" if i == 0 else "_s1"
+        if fault == "patch_taps" + at:
+            wpe = wpe.transpose(2, 3)
+        if fault == "patch_pad" + at:
+            h = F.conv2d(F.pad(h, (k // 2 + 1, k // 2 - 1, k // 2 + 1, k // 2 - 1)), wpe, p[s + ".patch_embeddings.proj.bias"], stride=c["strides"][i])
+        else:
+            h = F.conv2d(h, wpe, p[s + ".patch_embeddings.proj.bias"], stride=c["strides"][i], padding=k // 2)
         n, ch, hh, ww = h.shape
-        t = ln(h.flatten(2).transpose(1, 2), s + ".patch_embeddings.layer_norm")
+        t = ln(h.flatten(2).transpose(1, 2), s + ".patch_embeddings.layer_norm", "patch")
         heads = c["num_attention_heads"][i]
         d = ch // heads
         sr = c["sr_ratios"][i]
         for j in range(c["depths"][i]):
             b = f"{s}.blocks.{j}"
-            y = ln(t, b + ".layernorm_before")
+            y = ln(t, b + ".layernorm_before", "before")
             q = lin(y, b + ".attention.q_proj").view(n, -1, heads, d).transpose(1, 2)
             kv = y
             if sr > 1:
                 r = b + ".attention.sequence_reduction"
                 kv = y.transpose(1, 2).reshape(n, ch, hh, ww)
+                if fault == "sr_ceil":
+                    kv = F.pad(kv, (0, -ww % sr, 0, -hh % sr))
                 kv = F.conv2d(kv, p[r + ".sequence_reduction.weight"], p[r + ".sequence_reduction.bias"], stride=sr)
-                kv = ln(kv.reshape(n, ch, -1).transpose(1, 2), r + ".layer_norm")
+                kv = ln(kv.reshape(n, ch, -1).transpose(1, 2), r + ".layer_norm", "sr")
             kk = lin(kv, b + ".attention.k_proj").view(n, -1, heads, d).transpose(1, 2)
             vv = lin(kv, b + ".attention.v_proj").view(n, -1, heads, d).transpose(1, 2)
-            a = torch.softmax(torch.matmul(q, kk.transpose(2, 3)) * d ** -0.5, dim=-1)
-            a = torch.matmul(a, vv).transpose(1, 2).reshape(n, -1, ch)
+            a = _attention(q, kk, vv, (ch if fault == "softmax_scale_c" else d) ** -0.5, fault, taps)
+            a = a.transpose(1, 2).reshape(n, -1, ch)
             t = t + lin(a, b + ".attention.o_proj")
-            y = lin(ln(t, b + ".layernorm_after"), b + ".mlp.fc1")
+            y = lin(ln(t, b + ".layernorm_after", "after"), b + ".mlp.fc1")
             y = y.transpose(1, 2).reshape(n, -1, hh, ww)
-            y = F.conv2d(y, p[b + ".mlp.dwconv.dwconv.weight"], p[b + ".mlp.dwconv.dwconv.bias"], padding=1, groups=y.shape[1])
-            y = F.gelu(y.flatten(2).transpose(1, 2))
+            if fault == "dw_wrap":
+                y = _dwconv_wrapping(y, p[b + ".mlp.dwconv.dwconv.weight"], p[b + ".mlp.dwconv.dwconv.bias"])
+            else:
+                y = F.conv2d(y, p[b + ".mlp.dwconv.dwconv.weight"], p[b + ".mlp.dwconv.dwconv.bias"], padding=1, groups=y.shape[1])
+            y = F.gelu(y.flatten(2).transpose(1, 2), approximate="tanh" if fault == "gelu_tanh" else "none")
             t = t + lin(y, b + ".mlp.fc2")
-        t = ln(t, s + ".layer_norm")
+        t = ln(t, s + ".layer_norm", "stage")
         h = t.reshape(n, hh, ww, ch).permute(0, 3, 1, 2).contiguous()
         feats.append(h)
     size = feats[0].shape[2:]
@@ -157,11 +244,29 @@ def segformer_forward(sd, x, **cfg):
         n, ch, hh, ww = f.shape
         t = lin(f.flatten(2).transpose(1, 2), f"decode_head.linear_projections.{i}.proj")
         t = t.transpose(1, 2).reshape(n, -1, hh, ww)
-        ups.append(F.interpolate(t, size=size, mode="bilinear", align_corners=False))
-    y = F.conv2d(torch.cat(ups[::-1], dim=1), p["decode_head.linear_fuse.weight"])
+        if fault == "up_no_clamp":
+            ups.append(_upsample_unclamped(t, size))
+        else:
+            ups.append(F.interpolate(t, size=size, mode="bilinear", align_corners=fault == "up_align_corners"))
+    y = F.conv2d(torch.cat(ups if fault == "concat_first_first" else ups[::-1], dim=1), p["decode_head.linear_fuse.weight"])
     bn = "decode_head.batch_norm"
-    y = F.batch_norm(y, p[bn + ".running_mean"], p[bn + ".running_var"], p[bn + ".weight"], p[bn + ".bias"], False, 0.0, BN_EPS)
+    var = torch.ones_like(p[bn + ".running_var"]) if fault == "bn_no_var" else p[bn + ".running_var"]
+    y = F.batch_norm(y, p[bn + ".running_mean"], var, p[bn + ".weight"], p[bn + ".bias"], False, 0.0, 1e-6 if fault == "bn_eps" else BN_EPS)
     return F.conv2d(F.relu(y), p["decode_head.classifier.weight"], p["decode_head.classifier.bias"])
+
+
+def class_map(logits, fault=None):
+    """[H, W] int64 argmax over the labels of logits [1, L, H, W], the lowest index among equals (SEG_OUT_ARGMAX).  fault: one of
+    MAP_FAULTS."""
+    assert fault is None or fault in MAP_FAULTS, fault
+    lg = logits[0]
+    if fault == "argmax_pad_label":      # the classifier's columns are padded to a multiple of 32 with zero weight and zero bias
+        lg = torch.cat([lg, lg.new_zeros((-lg.shape[0] % 32,) + lg.shape[1:])], dim=0)
+    idx = torch.arange(lg.shape[0]).view(-1, 1, 1).expand_as(lg)
+    best = lg == lg.max(dim=0, keepdim=True).values
+    if fault == "argmax_highest_tie":
+        return torch.where(best, idx, torch.full_like(idx, -1)).max(dim=0).values
+    return torch.where(best, idx, torch.full_like(idx, lg.shape[0])).min(dim=0).values
 
 
 def top2_margin(logits):

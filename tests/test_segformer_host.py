@@ -13,6 +13,7 @@ os.environ.setdefault("TRANSFORMERS_OFFLINE", "1")
 
 from neural_enhanced_super_resolution_amd import SegFormer, _lib, segformer_state_dict_spec
 from neural_enhanced_super_resolution_amd.segformer import new_key
+from tests import segformer_cases as C
 from tests import segformer_ref as R
 
 RESIZE_CASES, FORWARD_CASES, FRAME_CASES, MAX_THIN = R.RESIZE_CASES, R.FORWARD_CASES, R.FRAME_CASES, R.MAX_THIN
@@ -33,6 +34,25 @@ def test_restatement_matches_transformers_f64(h, w):
     assert got.shape == want.shape == (1, 150, h // 4, w // 4)
     err = float((got - want).abs().max())
     print(f"restatement vs transformers f64 at {h}x{w}: max |logit diff| = {err:.3e}, max |logit| = {float(want.abs().max()):.2f}")
+    assert err <= 1e-10
+
+
+@pytest.mark.parametrize("name", [c.name for c in C.cases()])
+def test_restatement_matches_transformers_f64_on_the_crafted_cases(name):
+    """The non-B0 configurations of tests/segformer_cases.py, with their crafted weights and inputs."""
+    transformers = pytest.importorskip("transformers")
+    case = C.by_name(name)
+    model = transformers.SegformerForSemanticSegmentation(transformers.SegformerConfig(**{k: list(v) if isinstance(v, tuple) else v
+                                                                                         for k, v in case.cfg.items()})).eval().double()
+    assert set(model.state_dict()) == set(case.sd)
+    model.load_state_dict({k: v.double() if v.dtype.is_floating_point else v for k, v in case.sd.items()})
+    x = case.pixel_values().double()
+    with torch.no_grad():
+        want = model(pixel_values=x).logits
+    got = C.reference(case)[0]
+    assert got.shape == want.shape
+    err = float((got - want).abs().max())
+    print(f"restatement vs transformers f64, {name}: logits {tuple(want.shape)}, max |diff| = {err:.3e}, max |logit| = {float(want.abs().max()):.2f}")
     assert err <= 1e-10
 
 
