@@ -7,10 +7,11 @@
 // The two cross terms have their own f32 accumulator and are scaled once in the epilogue.  Precision of
 // the pair: hi carries 11 significant bits and lo (kept normal by the 2^11 scale) the next 11, so
 // |x - (hi + lo 2^-11)| <= 2^-22 |x| for 6.1e-5 <= |x| <= 65504; below 6.1e-5 hi is an f16 subnormal
-// (absolute step 2^-24) and the scaled lo resolves the rest to an absolute 2^-35.  Range: |x| > 65504
-// or a non-finite x does not fit; such a value is clamped AND reported -- a sticky device flag
-// (ConvArgs::status) that nesr_check_status / nesr_check_range turn into NESR_ERR_RANGE and that makes
-// conv_last write NaN instead of a saturated image (a diverged network gives NaN in the reference too).
+// (absolute step 2^-24) and the scaled lo resolves the rest to an absolute 2^-35.  Range: |x| >= 65520
+// or a non-finite x does not fit; nothing is clamped (f16x2_common.h, split2): its hi half is Inf / NaN
+// and poisons the sums it enters, and it is reported -- a sticky device flag (ConvArgs::status) that
+// nesr_check_status / nesr_check_range turn into NESR_ERR_RANGE and that makes conv_last write NaN
+// instead of a saturated image (a diverged network gives NaN in the reference too).
 //
 // v_mfma_f32_32x32x16_f16 runs at 16x the rate of the f32 MFMA, so three of them cost 3/16 of the
 // direct f32 kernel's matrix time and 27/64 of the Winograd kernel's.  Measured on the 23-block
@@ -33,7 +34,8 @@
 //   LDS image : pixel p's 16-byte slot s = 2*plane + k-half sits at p*64 + (s ^ ((col>>2)&3))*16:
 //               the 16-lane groups of ds_read_b128 (MI355X_MICROARCH.md, LDS) then cover all 16
 //               slots of a 256-byte bank row for every horizontal tap.
-//   epilogue  : bias / LeakyReLU / residuals in f32 (residuals re-joined hi + lo), split, 16-byte
+//   epilogue  : bias / LeakyReLU / residuals in f32 (residuals re-joined hi + lo; v * s + res in two
+//               roundings, scale_add_2r), split, 16-byte
 //               write-through stores of 8 channels per plane; conv_last writes planar f32 / u8.
 //
 // The fused dense block (conv1..conv5 of an RDB in one launch, the same arithmetic) is rdb_f16x2.hip; what the two share
@@ -321,13 +323,13 @@ __global__ __launch_bounds__(64 * (WAVES + DMAW), DMAW ? (WAVES + DMAW) / 4 : 2)
                 f32x4 q0, q1;
                 load_regrouped(res1 + slot(a.res1_map, 0), a.res1_map.chunk, q0, q1);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { v0[i] = __fadd_rn(__fmul_rn(v0[i], a.s1), q0[i]); v1[i] = __fadd_rn(__fmul_rn(v1[i], a.s1), q1[i]); }
+                for (int i = 0; i < 4; ++i) { v0[i] = scale_add_2r(v0[i], a.s1, q0[i]); v1[i] = scale_add_2r(v1[i], a.s1, q1[i]); }
             }
             if (res2) {
                 f32x4 q0, q1;
                 load_regrouped(res2 + slot(a.res2_map, 0), a.res2_map.chunk, q0, q1);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { v0[i] = __fadd_rn(__fmul_rn(v0[i], a.s2), q0[i]); v1[i] = __fadd_rn(__fmul_rn(v1[i], a.s2), q1[i]); }
+                for (int i = 0; i < 4; ++i) { v0[i] = scale_add_2r(v0[i], a.s2, q0[i]); v1[i] = scale_add_2r(v1[i], a.s2, q1[i]); }
             }
             if (out || out2) {
                 uint4 cx, cx1;

@@ -789,11 +789,11 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             f32x4 q0, q1;
             unpack_res(R1[p][0], R1[p][1], q0, q1);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { v0[i] = __fadd_rn(__fmul_rn(v0[i], a.s1), q0[i]); v1[i] = __fadd_rn(__fmul_rn(v1[i], a.s1), q1[i]); }
+            for (int i = 0; i < 4; ++i) { v0[i] = scale_add_2r(v0[i], a.s1, q0[i]); v1[i] = scale_add_2r(v1[i], a.s1, q1[i]); }
             if (RES2) {
                 unpack_res(R2[p][0], R2[p][1], q0, q1);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) { v0[i] = __fadd_rn(__fmul_rn(v0[i], a.s2), q0[i]); v1[i] = __fadd_rn(__fmul_rn(v1[i], a.s2), q1[i]); }
+                for (int i = 0; i < 4; ++i) { v0[i] = scale_add_2r(v0[i], a.s2, q0[i]); v1[i] = scale_add_2r(v1[i], a.s2, q1[i]); }
             }
             bool bad_here = false;
             split_regroup(v0, v1, cx[p], cx1[p], bad_here);

@@ -196,6 +196,8 @@ def test_winograd_vs_direct_random_shapes(cuda_device):
 
 # ---------------------------------------------------------------- f32 on the f16 matrix cores (f16 pairs)
 SPLIT_TOL = 2e-5   # relative to max|ref|: operands carry 22-23 bits, products lose w_lo*x_lo (2^-22)
+# (a coarse guard: a lost lo plane of one tap or one halo column passes it.  The per-value judgement of the pair form, against its
+# exact float64 specification, is test_gpu_pair_spec.py with tests/pair_spec.py.)
 
 
 @pytest.mark.parametrize("cin,cout", SHAPES)

@@ -3,6 +3,9 @@ synchronised through progress words) against the per-layer launches of the same 
 must agree bit for bit on every shape -- whole tiles, a partial tile column, tile rows that end below the image (MFMA
 waves without a row), both network scales, the 12-channel nesr form -- run after run (the progress words are never reset:
 an epoch per launch), and the fused path must be the one that ran (its launch count is a fifth of the other's).
+The two kernels share f16x2_common.h (the split, the tap plan, a tap-step's MFMAs, the cout exchange, the regrouping), so a
+mistake in a shared piece leaves them bit-equal: what both compute is held against a closed form per value in
+test_gpu_pair_spec.py (tests/pair_spec.py).
 
 Reference semantics: the dense block of basicsr's RRDBNet (un-vendored; restated in oracle/rrdbnet_ref.py), called at
 nesr/nesr.py:887-891 and through RealESRGANer.enhance at standalone/direct_esrgan.py:148."""
