@@ -318,8 +318,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv3x3_bf16_xl_kernel(ConvArgs
                 for (int q = 0; q < 4; ++q) {
                     float x = acc[r][t][4 * g + q] + bs[t][g][q];
                     if (a.lrelu) x = x > 0.f ? x : x * 0.2f;
-                    if (res1) x = __fadd_rn(__fmul_rn(x, a.s1), r1[t][g][q]);
-                    if (res2) x = __fadd_rn(__fmul_rn(x, a.s2), r2[t][g][q]);
+                    if (res1) x = scale_add_2r(x, a.s1, r1[t][g][q]);
+                    if (res2) x = scale_add_2r(x, a.s2, r2[t][g][q]);
                     v[t][g][q] = x;
                     if constexpr (E16<K>::RANGE) amax = E16<K>::amax(amax, valid && (out || out2) ? x : 0.f);
                 }

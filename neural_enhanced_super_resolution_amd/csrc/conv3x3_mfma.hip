@@ -48,6 +48,15 @@ constexpr int TH = 8, TW = 16;
 constexpr int PH = TH + 2, PW = TW + 2;
 constexpr int NPIX = PH * PW;  // 180
 
+// v * s + res of the epilogue.  The 16-bit forms round twice, as their specification does (tests/rrdbnet_emu16.py; a dense
+// block is held to it bit for bit, tests/test_gpu_rdb16_block.py).  The direct f32 form keeps what the toolchain makes of
+// __fadd_rn(__fmul_rn()), one fused multiply-add (nesr_kernels.h, scale_add_2r): nothing pins that form per value.
+template <int K>
+__device__ __forceinline__ float residual(float v, float s, float res) {
+    if constexpr (K == 0) return __fadd_rn(__fmul_rn(v, s), res);
+    else return scale_add_2r(v, s, res);
+}
+
 // K: activation layout code (PackArgs::bf16): 0 f32, 1 bf16, 3 f16 (the 16-bit forms: elem16.h)
 template <int K>
 struct Elem : E16<K> {
@@ -257,7 +266,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[t][g][q] = __fadd_rn(__fmul_rn(v[t][g][q], a.s1), r1[t][g][q]);
+                for (int q = 0; q < 4; ++q) v[t][g][q] = residual<K>(v[t][g][q], a.s1, r1[t][g][q]);
     }
     if (a.res2) {
 #pragma unroll
@@ -265,7 +274,7 @@ __device__ __forceinline__ void conv_tile(const ConvArgs& a, const int n, const 
 #pragma unroll
             for (int g = 0; g < 4; ++g)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) v[t][g][q] = __fadd_rn(__fmul_rn(v[t][g][q], a.s2), r2[t][g][q]);
+                for (int q = 0; q < 4; ++q) v[t][g][q] = residual<K>(v[t][g][q], a.s2, r2[t][g][q]);
     }
     if constexpr (Elem<K>::RANGE) {   // f16: a stored activation beyond +-65504 (or not finite) raises the range word
         unsigned m = 0;

@@ -66,15 +66,6 @@ __device__ __forceinline__ void split4(f32x4 v, uint2& hi, uint2& lo, bool& bad)
     bad |= (bits & 0x80008000u) != 0u;
 }
 
-// v * s + q in TWO roundings, as the residuals of every compute form are specified (tests/pair_spec.py holds the f16-pair
-// kernels to it per value).  __fmul_rn / __fadd_rn do not give that here: the toolchain's headers define them as plain * and +,
-// which hipcc's default -ffp-contract=fast fuses into one v_(pk_)fma_f32.  The pragma takes the contraction off these two
-// operations alone.
-__device__ __forceinline__ float scale_add_2r(float v, float s, float q) {
-#pragma clang fp contract(off)
-    const float p = v * s;
-    return p + q;
-}
 
 // ---- whole-line feature-map access for the 16x16x32 epilogue.  After the cout exchange lane (pixel j16, k-group g4)
 // holds 8 consecutive couts of ONE pixel: base 0 / 16 / 8 / 24 for g4 = 0 / 1 / 2 / 3, i.e. piece g4>>1 (8 channels)

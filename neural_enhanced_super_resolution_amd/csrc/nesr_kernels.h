@@ -16,6 +16,16 @@ __device__ __forceinline__ float mul_rn(float a, float b) { float r; asm("v_mul_
 __device__ __forceinline__ float add_rn(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float sub_rn(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
+// v * s + q in TWO roundings, as the residuals of every compute form are specified (tests/pair_spec.py holds the f16-pair
+// kernels to it per value, tests/rdb16_block.py the bf16 / f16 ones).  __fmul_rn / __fadd_rn do not give that here: the
+// toolchain's headers define them as plain * and +, which hipcc's default -ffp-contract=fast fuses into one v_(pk_)fma_f32.
+// The pragma takes the contraction off these two operations alone.
+__device__ __forceinline__ float scale_add_2r(float v, float s, float q) {
+#pragma clang fp contract(off)
+    const float p = v * s;
+    return p + q;
+}
+
 // XCD-aware work index of this workgroup among `total` (bijective for any count): consecutive workgroup ids go round the
 // 8 XCDs, so XCD x takes the contiguous range of work items that starts at x's share -- neighbours in the work order
 // (a tile's cout groups, adjacent tiles) share an L2.

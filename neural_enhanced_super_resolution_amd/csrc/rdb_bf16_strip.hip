@@ -469,7 +469,6 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
     const unsigned lane_b = lds0 + (g4 >> 1) * CHB + j16 * 32 + (g4 & 1) * 16;
     const unsigned lane_a = lds0 + WRING + (g4 >> 1) * 1024 + (g4 & 1) * 512 + j16 * 16;
     const int lane_e = (j16 + 1) * 32 + g4 * 8;     // a lane's 4 couts of its pixel inside a chunk row
-    const float inv_s1 = 1.0f / a.s1;
     int aq = 0;                                     // ring slot of the current step's first tap column
     f32x4 acc[2][3][2];                             // [cout group (conv5) | 0][row][cout half]
     f32x4 Bf[3][5], Af[2][3][2];                       // pixel fragments of tap column i (order 1, 0, 2) in buffer i; weight fragments [dy][cout half]
@@ -662,24 +661,19 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
             layer(std::integral_constant<int, 2>{});
             layer(std::integral_constant<int, 3>{});
             layer(std::integral_constant<int, 4>{});
-            // ---- conv5, its two cout groups alternating.  x5 * s1 + x0 = (x5 + x0 / s1) * s1: the first residual starts
-            // the sums, while its rows are still in the window (the next position's x0 rows overwrite them from conv5's
-            // fifth step on)
+            // ---- conv5, its two cout groups alternating.  The sums start from the bias; the first residual is applied in the
+            // epilogue as the specification has it, x5 * s1 + x0 in two roundings (folding x0 / s1 into the sums and scaling
+            // once is one rounding: an f16 ulp off where x5 * s1 cancels x0).  x0's rows have left the window by then (the next
+            // position's overwrite them from conv5's fifth step on), so x0 comes back from memory: behind conv5's last step in the
+            // registers that hold the second residual where there is one, else a row at a time in the epilogue (there are no
+            // registers for both across that step: 245 of 256 are taken).
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                int sl = base_of(wbp, 0) + 3 * wv + r + 1;      // row 12 pos - 4 + 3 wv + r
-                sl -= sl >= 18 ? 18 : 0;
+            for (int r = 0; r < 3; ++r)
 #pragma unroll
                 for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-                    {
-                        const f32x4 u = E16<K>::unpack4(*reinterpret_cast<const uint2*>(smem + sl * ROWB0 + (2 * c2 + mt) * CHB + lane_e)), bz = bias4(128 + 32 * c2, mt);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) acc[c2][r][mt][i] = fmaf(u[i], inv_s1, bz[i]);
-                    }
-            }
-            uint4 res2q[2][3];      // second residual, 16 bytes per lane in the regrouped layout of the output stores (below)
+                    for (int mt = 0; mt < 2; ++mt) acc[c2][r][mt] = bias4(128 + 32 * c2, mt);
+            uint4 resq[2][3];       // second residual, else the first: 16 bytes per lane in the regrouped layout of the output stores (below)
             for (int p = 0; p < 6; ++p) {
                 SSTAMP(wv, sidx, 0);
                 __builtin_amdgcn_s_barrier();
@@ -692,7 +686,8 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
 #endif
                 if (p < 5) baddr_of(wbp, 5, p + 1, nba);
                 else baddr_of(wbn, 1, 0, nba);                             // (past the last position: rows nobody uses)
-                if (p == 5 && a.res2) {
+                if (p == 5) {
+                    const char* early = a.res2 ? a.res2 : a.cur;
 #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
@@ -700,7 +695,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                             const int y = yw - 4 + r;
                             const bool valid = colok && y >= 0 && y < h;
                             const size_t pix = img_px + (size_t)(valid ? y : 0) * a.W + (valid ? xs + j16 : 0);
-                            res2q[c2][r] = *reinterpret_cast<const uint4*>(a.res2 + (size_t)(2 * c2 + (g4 & 1)) * a.chunk_bytes + pix * 32 + (g4 >> 1) * 16);
+                            resq[c2][r] = *reinterpret_cast<const uint4*>(early + (size_t)(2 * c2 + (g4 & 1)) * a.chunk_bytes + pix * 32 + (g4 >> 1) * 16);
                         }
                 }
                 SSTAMP(wv, sidx, 0);
@@ -724,6 +719,12 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                     // x1..x4 inputs it never computed -- the segment above stores them)
                     const bool valid = colok && y >= row_lo && y < row_hi;
                     const size_t pix = img_px + (size_t)(valid ? y : 0) * a.W + (valid ? xs + j16 : 0);
+                    uint4 x0q[2];           // first residual of this row, in the layout of the second
+#pragma unroll
+                    for (int c2 = 0; c2 < 2; ++c2) {
+                        if (a.res2) x0q[c2] = *reinterpret_cast<const uint4*>(a.cur + (size_t)(2 * c2 + (g4 & 1)) * a.chunk_bytes + pix * 32 + (g4 >> 1) * 16);
+                        else x0q[c2] = resq[c2][r];
+                    }
 #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2) {
                         // A lane holds 4 couts (8 bytes) of chunk 2 c2 and 4 of chunk 2 c2 + 1.  One v_permlane16_swap per register
@@ -732,16 +733,27 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                         // instructions per wave and position instead of 12, and the second residual arrives in 6 loads (the swap is its
                         // own inverse).  A vector-memory instruction issued by an MFMA wave beside the DMA waves' bursts costs that
                         // wave a few hundred cycles: these are the only ones it has.
-                        f32x4 v[2] = {acc[c2][r][0] * a.s1, acc[c2][r][1] * a.s1};
-                        if (a.res2) {
-                            const uint4 q = res2q[c2][r];
+                        f32x4 v[2];
+                        {
+                            const uint4 q = x0q[c2];
                             const auto sx = __builtin_amdgcn_permlane16_swap(q.x, q.z, false, false);
                             const auto sy = __builtin_amdgcn_permlane16_swap(q.y, q.w, false, false);
                             const f32x4 q0 = E16<K>::unpack4(uint2{sx[0], sy[0]}), q1 = E16<K>::unpack4(uint2{sx[1], sy[1]});
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
-                                v[0][i] = __fadd_rn(__fmul_rn(v[0][i], a.s2), q0[i]);
-                                v[1][i] = __fadd_rn(__fmul_rn(v[1][i], a.s2), q1[i]);
+                                v[0][i] = scale_add_2r(acc[c2][r][0][i], a.s1, q0[i]);
+                                v[1][i] = scale_add_2r(acc[c2][r][1][i], a.s1, q1[i]);
+                            }
+                        }
+                        if (a.res2) {
+                            const uint4 q = resq[c2][r];
+                            const auto sx = __builtin_amdgcn_permlane16_swap(q.x, q.z, false, false);
+                            const auto sy = __builtin_amdgcn_permlane16_swap(q.y, q.w, false, false);
+                            const f32x4 q0 = E16<K>::unpack4(uint2{sx[0], sy[0]}), q1 = E16<K>::unpack4(uint2{sx[1], sy[1]});
+#pragma unroll
+                            for (int i = 0; i < 4; ++i) {
+                                v[0][i] = scale_add_2r(v[0][i], a.s2, q0[i]);
+                                v[1][i] = scale_add_2r(v[1][i], a.s2, q1[i]);
                             }
                         }
                         if constexpr (E16<K>::RANGE) {

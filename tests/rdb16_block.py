@@ -1,0 +1,325 @@
+"""One bf16 / f16 dense block judged per value (helpers of test_rdb16_block_host.py and test_gpu_rdb16_block.py; no tests here).
+
+Exact cases.  With "routing" weights (a few taps per output channel, each +-1 or 2), integer biases and integer inputs, every
+partial sum of every conv of the block is a float32 value in every summation order (`exactness` proves it per case); what
+follows the sum is fixed by the kernels' text (x > 0 ? x : x * 0.2f, __fadd_rn(__fmul_rn(v, s), res), one nearest-even store),
+so the block has one right answer: RRDBNetEmu16.dense_block, bit for bit in each of its accumulation modes.
+
+Random weights, for what integers cannot show (accumulation precision on realistic values, small values): two rules against the
+float64 specification computed on the same input, `share_and_size`.
+
+The block runs through the band entries: band_begin, a chosen x0 into the block's input buffer, band_rdb(r), the output buffer
+read back.  Staging of a 16-bit context (band_api.cpp, "channel-blocked"): [chunk of 16 channels][row][column][16 elements of
+2 bytes], so a row is w * 64 * 2 bytes."""
+import os
+
+import torch
+import torch.nn.functional as F
+
+from tests import conv_pin
+from tests.rrdbnet_emu16 import RRDBNetEmu16
+
+NF, GC = 64, 32
+ROUTES = {"generic": dict(size_independent=False, strip="0", launches=5),
+          "xl": dict(size_independent=True, strip="0", launches=5),
+          "strip": dict(size_independent=True, strip="1", launches=1)}
+STANDINS = (torch.float32, "f32-chunked")
+# trunk sizes, test_gpu_strip.py's SHAPES_X4: below one strip (16 columns) and one position (12 rows), one off 16 and 12, the
+# exact multiples, one strip wide, long and thin
+SHAPES = [(1, 1), (5, 15), (11, 16), (12, 17), (13, 33), (23, 47), (24, 48), (25, 49), (100, 9), (9, 100)]
+SEG_SHAPES = [(61, 33), (130, 20)]          # 6 and 11 positions: row segments with their warm-up position
+SEGS = ["-1", "2", "0"]                     # never cut; at most 2 positions per segment; the packer's own choice
+RANDOM_CASES = [((13, 33), None), ((25, 49), None), ((61, 33), "2")]
+
+
+def threads():
+    torch.set_num_threads(max(1, min(16, torch.get_num_threads())))
+
+
+# ------------------------------------------------------------------------------------------------------------ staging
+def rows16_bytes(x, dtype):
+    """[1, C, h, w] float32 of `dtype` values, C a multiple of 16 -> the staging bytes of nesr_band_rows for rows 0..h-1 of a
+    16-bit context, as a flat uint8 tensor."""
+    _, c, h, w = x.shape
+    v = x[0].to(conv_pin.STORE[dtype]).view(c // 16, 16, h, w).permute(0, 2, 3, 1).contiguous()      # [chunk, row, column, k]
+    return v.view(torch.uint8).reshape(-1)
+
+
+def rows16_values(raw, h, w, dtype):
+    """The inverse: staging bytes -> [1, C, h, w] float32."""
+    v = raw.cpu().contiguous().view(conv_pin.STORE[dtype]).view(-1, h, w, 16).float()
+    return v.permute(0, 3, 1, 2).reshape(1, -1, h, w).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------------------ exact cases
+_sd = {}
+
+
+def taps_per_output(cin, cout):
+    """3, or as many as it takes for cout outputs to read every one of cin input channels (conv3: 4, conv4: 5)."""
+    return max(3, -(-cin // cout))
+
+
+def routing_state_dict(seed, signed, dtype):
+    """synthetic_state_dict(seed=0, num_in_ch=3, scale=4, num_block=1) with the fifteen dense-block convs of body.0 replaced by
+    routing weights: per output channel taps_per_output() taps at distinct positions, weights from {1, 2} (signed: {1, 2, -1}),
+    integer biases in 0..3 (signed: -3..3).  Over each conv every input channel and every one of the 9 tap positions is read
+    by some output channel (so conv5 reads every 16-channel chunk of x0..x4); asserted here."""
+    key = (seed, signed, dtype)
+    if key in _sd:
+        return _sd[key]
+    from neural_enhanced_super_resolution_amd.synth import synthetic_state_dict
+    sd = {k: v.clone() for k, v in synthetic_state_dict(seed=0, num_in_ch=3, scale=4, num_block=1).items()}
+    g = torch.Generator().manual_seed(1000 + seed * 2 + int(signed))
+    values = torch.tensor([1.0, 2.0, -1.0] if signed else [1.0, 2.0])
+    for r in (1, 2, 3):
+        for k in range(1, 6):
+            cin, cout = NF + GC * (k - 1), (GC if k < 5 else NF)
+            t = taps_per_output(cin, cout)
+            chans = torch.cat([torch.randperm(cin, generator=g), torch.randint(0, cin, (cout * t - cin,), generator=g)])
+            chans = chans[torch.randperm(cout * t, generator=g)].view(cout, t)
+            w = torch.zeros(cout, cin, 3, 3)
+            for o in range(cout):
+                rest = [p for p in torch.randperm(9, generator=g).tolist() if p != o % 9]
+                pos = [o % 9] + rest[:t - 1]
+                for j in range(t):
+                    w[o, chans[o, j], pos[j] // 3, pos[j] % 3] = values[torch.randint(0, len(values), (1,), generator=g)]
+            b = torch.randint(-3 if signed else 0, 4, (cout,), generator=g).float()
+            assert bool(((w != 0).sum(dim=(1, 2, 3)) == t).all()), "taps of one output channel fell on each other"
+            assert bool((w != 0).any(dim=0).any(dim=-1).any(dim=-1).all()), "an input channel is read by no output channel"
+            assert bool((w != 0).any(dim=0).any(dim=0).all()), "a tap position is used by no output channel"
+            if k == 5:
+                assert bool((w != 0).any(dim=0).any(dim=-1).any(dim=-1).view(-1, 16).any(dim=1).all()), "conv5 skips a 16-channel chunk"
+            st = conv_pin.STORE[dtype]
+            assert torch.equal(w.to(st).float(), w) and torch.equal(b.to(st).float(), b)
+            sd[f"body.0.rdb{r}.conv{k}.weight"], sd[f"body.0.rdb{r}.conv{k}.bias"] = w, b
+    _sd[key] = sd
+    return sd
+
+
+def exact_inputs(h, w, seed, signed):
+    """(x0, rrdb_in): two different tensors of integers in 0..8 (signed: -8..8), [1, 64, h, w] float32."""
+    g = torch.Generator().manual_seed(7000 + seed * 2 + int(signed) + 131 * h + w)
+    lo = -8 if signed else 0
+    x0 = torch.randint(lo, 9, (1, NF, h, w), generator=g).float()
+    rrdb_in = torch.randint(lo, 9, (1, NF, h, w), generator=g).float()
+    if torch.equal(x0, rrdb_in):          # (a 1 x 1 image could draw the same 64 values twice)
+        rrdb_in = rrdb_in.flip(1)
+    return x0, rrdb_in
+
+
+# In f16 a signed case can hold a value with two answers: a LeakyReLU'd negative that nearly cancelled (2^-20, say) summed beside
+# +300 and -300 is kept by one order and absorbed by another.  `exactness` finds such values (1 to 5 per case with the first
+# draw); the inputs of these cases are the first draw without one.  bf16 and the non-negative cases take seed 0.
+F16_SIGNED_SEED = {((5, 15), 0): 1, ((12, 17), 0): 2, ((12, 17), 1): 1, ((13, 33), 1): 2, ((13, 33), 2): 1, ((23, 47), 0): 3, ((23, 47), 1): 1,
+                   ((24, 48), 1): 4, ((24, 48), 2): 4, ((25, 49), 1): 1, ((100, 9), 0): 7, ((100, 9), 2): 2, ((9, 100), 1): 1, ((9, 100), 2): 6,
+                   ((61, 33), 0): 9, ((61, 33), 1): 2, ((61, 33), 2): 6, ((130, 20), 0): 47, ((130, 20), 1): 34, ((130, 20), 2): 1}
+
+
+def exact_case(hw, r, signed, dtype):
+    """(weights, x0, rrdb_in) of one exact case."""
+    seed = F16_SIGNED_SEED.get((tuple(hw), r), 0) if signed and dtype == "f16" else 0
+    return (routing_state_dict(0, signed, dtype),) + exact_inputs(hw[0], hw[1], seed, signed)
+
+
+RANDOM_SEED = 1      # the input draw of the random-weights part (test_rdb16_block_host.py: both stand-ins pass by each other on it)
+
+
+def random_inputs(h, w, dtype, seed=RANDOM_SEED):
+    """(x0, rrdb_in) = 0.3 randn rounded to the storage type."""
+    g = torch.Generator().manual_seed(9000 + seed + 131 * h + w)
+    st = conv_pin.STORE[dtype]
+    return tuple((0.3 * torch.randn(1, NF, h, w, generator=g)).to(st).float() for _ in range(2))
+
+
+def emu(sd, dtype, accumulate, cls=RRDBNetEmu16):
+    return cls(sd, 4, 1, conv_pin.STORE[dtype], accumulate=accumulate)
+
+
+def block(e, x0, r, rrdb_in):
+    """Dense block r (0..2) of body.0 by the emulation `e`: the third one takes the RRDB's input as its second residual."""
+    with torch.no_grad():
+        return e.dense_block(x0, f"body.0.rdb{r + 1}", rrdb_in=rrdb_in if r == 2 else None)
+
+
+def expected(sd, x0, r, rrdb_in, dtype):
+    threads()
+    return block(emu(sd, dtype, torch.float32), x0, r, rrdb_in)
+
+
+def _outward(v, up):
+    """float64 -> float32, rounded away from the interval's inside (up: toward +inf)."""
+    f = v.float()
+    wrong = (f.double() < v) if up else (f.double() > v)
+    return torch.where(wrong, torch.nextafter(f, torch.full_like(f, float("inf") if up else float("-inf"))), f)
+
+
+def exactness(sd, x0, r, rrdb_in, dtype):
+    """The proof that a case has one answer.  Per conv of the block, in float64 (where the sums are exact: `span` < 2^53):
+      span        max over the outputs of conv(|x|, |w|) + |b|, a bound of every partial sum in every order, divided by the
+                  smallest 16-bit ulp among the conv's nonzero operand products and biases.  Weights are +-2^j, so a product is a
+                  storage-type value, a multiple of its ulp, and every partial sum is a multiple of the smallest ulp: below 2^24
+                  every partial sum of the conv is a float32 value, whatever the order.
+      span_local  the same per output value, over the products that this value sums (what one accumulator sees).
+      undecided   where span_local >= 2^24 (a LeakyReLU'd negative that nearly cancels leaves values of 2^-20 and less beside
+                  sums of hundreds): a float32 sum of n <= 8 nonzero terms lies within d = 8 * 2^-24 * (conv(|x|, |w|) + |b|) of
+                  the exact one in any order, and what follows the sum (LeakyReLU, * 0.2f, + residual, the store) is monotone, so
+                  if sum - d and sum + d, rounded outward to float32, end in the same stored bits, so does every order.
+                  `undecided` counts the values for which neither argument holds; a case is exact when there are none.
+    Also: the float32 and the chunked variants' bits are equal, and whether the float64 variant's are."""
+    threads()
+    prefix, st = f"body.0.rdb{r + 1}", conv_pin.STORE[dtype]
+    e = emu(sd, dtype, torch.float64)
+    feats, span, span_local, undecided, wide, top = [x0], 0.0, 0.0, 0, 0, float(x0.abs().max())
+    big = 2.0 ** 60
+    with torch.no_grad():
+        for k in range(1, 6):
+            x = torch.cat(feats, 1).double()
+            w, b = e.w[f"{prefix}.conv{k}"].double(), e.b[f"{prefix}.conv{k}"].double()
+            taps = (w != 0).nonzero()
+            cout, t = w.shape[0], taps.shape[0] // w.shape[0]
+            assert t <= 7 and torch.equal(taps[:, 0], torch.arange(cout).repeat_interleave(t)), "not routing weights"
+            wv = w[w != 0].abs().view(cout, t, 1)
+            assert torch.equal(torch.exp2(torch.round(torch.log2(wv))), wv), "a weight that is no power of two"
+            assert torch.equal(x.to(st).double(), x)
+            acc = F.conv2d(x, w, b, padding=1)
+            mag = F.conv2d(x.abs(), w.abs(), b.abs(), padding=1)
+            # smallest ulp among the nonzero products of each output value
+            u = F.pad(torch.where(x != 0, conv_pin.ulp16(x, dtype), torch.full_like(x, big)), (1, 1, 1, 1), value=big)
+            cols = F.unfold(u, 3)[0]                                                  # [cin * 9, h * w]
+            idx = (taps[:, 1] * 9 + taps[:, 2] * 3 + taps[:, 3]).view(cout, t)
+            q = (cols[idx] * wv).min(dim=1).values.view(1, cout, *x.shape[2:])
+            q = torch.minimum(q, torch.where(b != 0, conv_pin.ulp16(b, dtype), torch.full_like(b, big)).view(1, -1, 1, 1))
+            span = max(span, float(mag.max() / q.min()))
+            span_local = max(span_local, float((mag / q).max()))
+            d = 8 * 2.0 ** -24 * mag
+            ends = []
+            for v in (_outward(acc - d, False), _outward(acc + d, True)):
+                if k < 5:
+                    ends.append(e.store(F.leaky_relu(v, 0.2)))
+                else:
+                    v = v * 0.2 + x0
+                    ends.append(e.store(v * 0.2 + rrdb_in if r == 2 else v))
+            open_ = mag / q >= 2.0 ** 24
+            wide += int(open_.sum())
+            undecided += int((open_ & (ends[0] != ends[1])).sum())
+            if k < 5:
+                feats.append(e.store(e.conv(torch.cat(feats, 1), f"{prefix}.conv{k}", lrelu=True)))
+                top = max(top, float(feats[-1].abs().max()))
+    out = {a: block(emu(sd, dtype, a), x0, r, rrdb_in) for a in (torch.float64,) + STANDINS}
+    return {"span": span, "span_local": span_local, "wide": wide, "undecided": undecided, "top": max(top, float(out[torch.float32].abs().max())),
+            "standins_equal": torch.equal(out[torch.float32], out["f32-chunked"]),
+            "f64_equal": torch.equal(out[torch.float64], out[torch.float32])}
+
+
+def describe_difference(got, want, limit=5):
+    """'<count> of <n> values differ, first at (channel, row, column): ...' for an assertion message."""
+    bad = (got != want) | (got.isnan() != want.isnan())
+    where = bad[0].nonzero()[:limit].tolist()
+    first = ", ".join(f"({c}, {y}, {x}): {float(got[0, c, y, x])!r} for {float(want[0, c, y, x])!r}" for c, y, x in where)
+    return f"{int(bad.sum())} of {bad.numel()} values differ, first at (channel, row, column): {first}"
+
+
+# ------------------------------------------------------------------------------------------------------------ random weights
+def random_state_dict():
+    from neural_enhanced_super_resolution_amd.synth import synthetic_state_dict
+    if "random" not in _sd:
+        _sd["random"] = synthetic_state_dict(seed=0, num_in_ch=3, scale=4, num_block=1)
+    return _sd["random"]
+
+
+def specs(sd, x0, r, rrdb_in, dtype):
+    """(spec64, [the float32 stand-ins]) of one block."""
+    threads()
+    return block(emu(sd, dtype, torch.float64), x0, r, rrdb_in), [block(emu(sd, dtype, a), x0, r, rrdb_in) for a in STANDINS]
+
+
+FLOOR = 20      # F of the share rule: twice the largest count one stand-in showed where the other showed none (measured in
+                # test_rdb16_block_host.py)
+
+
+def share_and_size(got, spec64, standins, dtype, floor=FLOOR):
+    """The two rules a kernel's block output must meet against the float64 specification, and their figures.
+      share  the count of values that are not spec64's bits is at most 4 max(the stand-ins' counts) + F: another summation order
+             flips a handful of roundings, each followed by a small cluster downstream, and 4 is the project's factor for
+             "another summation order"; F covers stand-ins that happen to flip nothing where a third order loses one cluster
+      size   every value lies within max(one 16-bit ulp of spec64 at that value, 4 x the larger stand-in's max |difference| over
+             the case) of spec64: correct stand-ins show clusters of several ulps where the output nearly cancels"""
+    g, s = got.double(), spec64.double()
+    counts = [int((v != spec64).sum()) for v in standins]
+    order_max = max(float((v.double() - s).abs().max()) for v in standins)
+    ulp = conv_pin.ulp16(s, dtype)
+    d = (g - s).abs()
+    fig = {"values": got.numel(), "count": int((got != spec64).sum()), "standin_counts": counts, "allowed": 4 * max(counts) + floor,
+           "worst_ulps": float((d / ulp).max()), "standin_worst_ulps": max(float(((v.double() - s).abs() / ulp).max()) for v in standins),
+           "outside": int((d > torch.maximum(ulp, torch.full_like(ulp, 4 * order_max))).sum()), "finite": bool(torch.isfinite(got).all())}
+    fig["share"] = fig["count"] <= fig["allowed"]
+    fig["size"] = fig["outside"] == 0 and fig["finite"]
+    return fig
+
+
+def describe(fig):
+    return (f"{fig['count']} of {fig['values']} not spec64's bits (stand-ins {fig['standin_counts']}, allowed {fig['allowed']}): {fig['share']} | "
+            f"worst {fig['worst_ulps']:.2f} ulps (stand-ins {fig['standin_worst_ulps']:.2f}), {fig['outside']} outside: {fig['size']}")
+
+
+# ------------------------------------------------------------------------------------------------------------ the device side
+_nets = {}
+
+
+def block_net(dtype, route, sd, seg=None):
+    """An RRDBNet (x4 form, one RRDB) whose device context is created now, under the route's NESR_STRIP and, for `seg`, under
+    NESR_STRIP_SEG (both read when the context is created); the environment is restored.  One net per (dtype, route, weights,
+    seg) for the process."""
+    key = (dtype, route, id(sd), seg)
+    if key in _nets:
+        return _nets[key][0]
+    from neural_enhanced_super_resolution_amd import RRDBNet
+    rt = ROUTES[route]
+    old = {k: os.environ.get(k) for k in ("NESR_STRIP", "NESR_STRIP_SEG")}
+    os.environ["NESR_STRIP"] = rt["strip"]
+    if seg is not None:
+        os.environ["NESR_STRIP_SEG"] = seg
+    try:
+        net = RRDBNet(3, 3, scale=4, num_block=1, compute_dtype=dtype)
+        net.load_state_dict(sd)
+        net.eval().to("cuda:0")
+        net.size_independent = rt["size_independent"]
+        net(torch.zeros(1, 3, 4, 4, device="cuda:0"))
+        net.check_status()
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    net.set_kernel_timing("cuda:0", True)
+    net.kernel_time()
+    _nets[key] = (net, sd)          # (sd is kept alive: its id is the key)
+    return net
+
+
+_faulted = []
+
+
+def run_block(net, img, x0, r, rrdb_in):
+    """band_begin(img), the chosen x0 into buffer r (for r = 2 also rrdb_in into buffer 0, the second residual, read and
+    overwritten in place), band_rdb(r), buffer (r + 1) % 3 read back.  -> (values [1, 64, h, w] float32, launches).
+    Once a call has failed on the device, later calls fail at once and start nothing more there."""
+    if _faulted:
+        raise RuntimeError(f"no further GPU work after an earlier block failed on the device: {_faulted[0]}")
+    (h, w), dtype = x0.shape[-2:], net.compute_dtype
+    try:
+        net.band_begin(img)
+        assert net.band_row_bytes() == w * NF * 2
+        if r == 2:
+            net.band_set_rows(0, 0, rows16_bytes(rrdb_in, dtype))
+        net.band_set_rows(r, 0, rows16_bytes(x0, dtype))
+        net.kernel_time()
+        net.band_rdb(r)
+        raw = net.band_rows((r + 1) % 3, 0, h).cpu()
+        net.check_status()
+    except Exception as e:
+        _faulted.append(repr(e))
+        raise
+    return rows16_values(raw, h, w, dtype), net.kernel_time()[1]

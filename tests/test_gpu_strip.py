@@ -8,7 +8,11 @@ network scales, and the third block of an RRDB (second residual).
 The checker is the CPU oracle (f32) and the per-layer bf16 path of the same library: the strip kernel rounds at the same
 points (x1..x4 and the block output to bf16, f32 accumulation) but sums in another order, so it is not the per-layer path's
 bits; its error against the f32 oracle must be the per-layer path's (PSNR within 0.5 dB) and the two must agree to bf16
-resolution.  What IS bitwise: repeatability, and independence of an image's values from its company and its slot."""
+resolution.  What IS bitwise: repeatability, and independence of an image's values from its company and its slot.
+
+These are not the only judges of the kernel: test_gpu_rdb16_block.py holds one dense block of it, on SHAPES_X4 and in row
+segments, bit for bit to the closed form of exact cases (integer inputs, routing weights), and test_gpu_rrdb_emu16.py holds the
+whole network to its 16-bit specification."""
 import os
 
 import pytest
