@@ -511,6 +511,36 @@ int nesr_jpeg_encode_u8(int device_id, const uint8_t* src_dev, int64_t src_row_b
                         size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
 
 /*
+ * The same encoder with libjpeg's other common settings -- cv2's IMWRITE_JPEG_SAMPLING_FACTOR, IMWRITE_JPEG_OPTIMIZE and
+ * IMWRITE_JPEG_RST_INTERVAL -- byte for byte again (tests/jpeg_options_ref.py is the specification, pinned against Pillow's
+ * libjpeg-turbo in tests/test_jpeg_options_spec.py).  The three entries above are these with {quality, NESR_JPEG_420, 0, 0}: the same
+ * kernels, launches and bytes as before the options existed.
+ *   sampling          NESR_JPEG_420 (cv2's default), NESR_JPEG_422 (h2v1: MCU Y0 Y1 Cb Cr, 16 x 8 pixels) or NESR_JPEG_444 (MCU
+ *                     Y Cb Cr, 8 x 8 pixels); a gray frame ignores it.  4:4:0 and 4:1:1 are not encoded.
+ *   optimize          non-zero: Huffman tables built for the frame (libjpeg's jpeg_gen_optimal_table) on the device, from
+ *                     histograms taken on the device.  The DHT segments' lengths depend on the frame, so the header's length is known
+ *                     on the device only: nesr_jpeg_header_ex refuses (NESR_ERR_ARG), the length word [0] counts it as always.
+ *                     Byte parity with libjpeg is claimed for frames of up to 500 Mpixel (22360 x 22360): libjpeg's table
+ *                     builder never picks a symbol or subtree counted more than 10^9 times, which no table of such a frame
+ *                     reaches (at most 126 chroma AC symbols per 64 pixels at 4:4:4).  A larger frame still gets a valid file
+ *                     with the true Huffman code of its counts, which libjpeg's own file then need not equal.
+ *   restart_interval  MCUs per restart interval, 0 (none) .. 65535: DRI behind the DHTs, predictors back at 0 and the stream padded
+ *                     to a byte at each interval's end, FF D0 .. FF D7 in turn between intervals.  Such a file is decoded one
+ *                     interval per lane by nesr_jpeg_decode_u8, without its synchronisation rounds.
+ * The scratch grows by 10 KiB with optimize and by 17 bytes per interval with a restart interval: nesr_jpeg_scratch_bytes_ex.
+ * Capacity, the length and status words and the argument checks are nesr_jpeg_encode_u8's; null options, a sampling outside the three
+ * or an interval outside 0 .. 65535: NESR_ERR_ARG before any device is touched.
+ */
+enum { NESR_JPEG_420 = 0, NESR_JPEG_422 = 1, NESR_JPEG_444 = 2 };
+typedef struct nesr_jpeg_opts {
+    int32_t quality, sampling, optimize, restart_interval;
+} nesr_jpeg_opts;
+size_t nesr_jpeg_scratch_bytes_ex(int H, int W, int C, const nesr_jpeg_opts* opts);
+int nesr_jpeg_header_ex(int H, int W, int C, const nesr_jpeg_opts* opts, uint8_t* buf, int cap, int* n);
+int nesr_jpeg_encode_ex_u8(int device_id, const uint8_t* src_dev, int64_t src_row_bytes, int H, int W, int C, int order, const nesr_jpeg_opts* opts,
+                           void* scratch_dev, size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* hip_stream);
+
+/*
  * cv2.imread(path) for a .jpg / .jpeg path, the first call of every reference entry point (nesr/nesr.py:661-666,
  * standalone/direct_esrgan.py:130), as HIP kernels (csrc/jpeg_decode.hip): the file's bytes go up, a tenth of the frame, and the
  * frame is born on the device.  libjpeg-turbo's default decompressor (JDCT_ISLOW, fancy upsampling, no merged upsampling) pixel for

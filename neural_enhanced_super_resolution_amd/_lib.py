@@ -112,6 +112,10 @@ SIGNATURES = {
     "nesr_jpeg_header": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int)]),
     "nesr_jpeg_encode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
                                        _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
+    "nesr_jpeg_scratch_bytes_ex": (_c.c_size_t, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "nesr_jpeg_header_ex": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int)]),
+    "nesr_jpeg_encode_ex_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                          _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
     "nesr_jpeg_parse": (_c.c_int, [_c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_jpeg_decode_scratch_bytes": (_c.c_size_t, [_c.c_void_p]),
     "nesr_jpeg_decode_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p,
@@ -201,6 +205,14 @@ class NesrBadFileError(NesrHipError):
     def __init__(self, msg, status=0):
         super().__init__(msg)
         self.status = status
+
+
+JPEG_SAMPLING = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}       # NESR_JPEG_420 | 422 | 444
+
+
+class JpegOpts(ctypes.Structure):
+    """nesr_jpeg_opts"""
+    _fields_ = [("quality", _c.c_int32), ("sampling", _c.c_int32), ("optimize", _c.c_int32), ("restart_interval", _c.c_int32)]
 
 
 class JpegHuff(ctypes.Structure):

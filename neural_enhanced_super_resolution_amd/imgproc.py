@@ -814,26 +814,36 @@ def ensemble_results(images, use_hip=None):
 
 
 # ----------------------------------------------------------------------------------------------- JPEG
-def _jpeg_encode_hip(frame, quality, bgr, cap):
+def _jpeg_encode_hip(frame, quality, bgr, cap, options=None):
     """One run of nesr_jpeg_encode_u8 (csrc/jpeg.hip) into a buffer of `cap` bytes -> the file's bytes; NesrNoFitError (with the
     size the device reported) when the file needs more.  Two transfers come back: the 16 bytes of the length and status words,
-    then exactly the file."""
+    then exactly the file.  options: (sampling, optimize, restart_interval) for nesr_jpeg_encode_ex_u8, None for the defaults."""
     from . import _lib
     h, w, c = frame.shape
     lib = _lib.load()
-    need = int(lib.nesr_jpeg_scratch_bytes(h, w, c))
-    scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
-    out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
     words = torch.empty(2, dtype=torch.int64, device=frame.device)
-    _hip_call(frame, "nesr_jpeg_encode_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, int(quality),
-              _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+    if options is None:
+        need = int(lib.nesr_jpeg_scratch_bytes(h, w, c))
+        scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
+        out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
+        _hip_call(frame, "nesr_jpeg_encode_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, int(quality),
+                  _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+    else:
+        import ctypes
+        sampling, optimize, restart_interval = options
+        opts = _lib.JpegOpts(int(quality), _lib.JPEG_SAMPLING[sampling], int(bool(optimize)), int(restart_interval))
+        need = int(lib.nesr_jpeg_scratch_bytes_ex(h, w, c, ctypes.byref(opts)))
+        scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
+        out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
+        _hip_call(frame, "nesr_jpeg_encode_ex_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, ctypes.byref(opts),
+                  _ptr(scratch), need, _ptr(out), cap, _ptr(words))
     length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
     if status != 0:
         raise _lib.NesrNoFitError(length, cap)
     return out[:length].cpu().numpy().tobytes()               # D2H: the file
 
 
-def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
+def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None, *, sampling="4:2:0", optimize=False, restart_interval=0):
     """cv2.imwrite(path.jpg, frame)'s bytes (standalone/direct_esrgan.py:169, nesr/nesr.py:646; cv2's defaults: quality 95, 4:2:0,
     baseline, standard Huffman tables) for an [H, W, 3] (order "rgb" or "bgr": the channel that comes first), [H, W, 1] or [H, W]
     uint8 frame -> bytes.
@@ -842,11 +852,20 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
     (frame[y0:y1, x0:x1]) as it is: the frame stays on the device and only the length words and the file come back.  The output
     buffer starts at H W C // 2 + 4096 bytes; when the file does not fit, the call runs once more at the size the device reported.
     use_hip=False, a CPU tensor or an ndarray: Pillow's libjpeg-turbo, whose bytes the kernels reproduce (tests/jpeg_ref.py is
-    pinned against both); without Pillow that raises -- there is no third route."""
+    pinned against both); without Pillow that raises -- there is no third route.
+
+    sampling "4:2:0" | "4:2:2" | "4:4:4" (cv2's IMWRITE_JPEG_SAMPLING_FACTOR; a gray frame ignores it), optimize (IMWRITE_JPEG_OPTIMIZE:
+    Huffman tables built for the frame, on the device) and restart_interval in MCUs, 0 .. 65535 (IMWRITE_JPEG_RST_INTERVAL) take the
+    same two routes: nesr_jpeg_encode_ex_u8, or Pillow's subsampling, optimize and restart_marker_blocks
+    (tests/jpeg_options_ref.py is pinned against both).  The defaults are the call without them."""
     if order not in ("rgb", "bgr"):
         raise ValueError(f"encode_jpeg_u8: order must be 'rgb' or 'bgr', got {order!r}")
     if not 1 <= int(quality) <= 100:
         raise ValueError(f"encode_jpeg_u8: quality {quality} outside 1..100")
+    if sampling not in ("4:2:0", "4:2:2", "4:4:4"):
+        raise ValueError(f"encode_jpeg_u8: sampling must be '4:2:0', '4:2:2' or '4:4:4', got {sampling!r} (4:4:0 and 4:1:1 are not encoded)")
+    if not 0 <= int(restart_interval) <= 65535:
+        raise ValueError(f"encode_jpeg_u8: restart_interval {restart_interval} outside 0..65535 MCUs")
     is_tensor = isinstance(frame, torch.Tensor)
     if frame.ndim == 2:
         frame = frame[:, :, None]
@@ -863,10 +882,13 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
                              f"{frame.device if is_tensor else 'the host'}")
         src = frame if _rows_ok(frame, (1, 3)) else frame.contiguous()
         h, w, c = src.shape
+        # the default options go the way they always went; anything else names its options
+        plain = (sampling == "4:2:0" or c == 1) and not optimize and not int(restart_interval)
+        options = () if plain else ((sampling, bool(optimize), int(restart_interval)),)
         try:
-            return _jpeg_encode_hip(src, quality, order == "bgr", h * w * c // 2 + 4096)
+            return _jpeg_encode_hip(src, quality, order == "bgr", h * w * c // 2 + 4096, *options)
         except _lib.NesrNoFitError as e:
-            return _jpeg_encode_hip(src, quality, order == "bgr", e.needed)
+            return _jpeg_encode_hip(src, quality, order == "bgr", e.needed, *options)
     try:
         from PIL import Image
     except ImportError as e:
@@ -876,7 +898,12 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None):
     arr = arr[:, :, 0] if arr.shape[2] == 1 else (arr[:, :, ::-1] if order == "bgr" else arr)
     buf = io.BytesIO()
     import numpy as np
-    Image.fromarray(np.ascontiguousarray(arr)).save(buf, format="JPEG", quality=int(quality))
+    extra = {"subsampling": sampling} if arr.ndim == 3 and sampling != "4:2:0" else {}
+    if optimize:
+        extra["optimize"] = True
+    if int(restart_interval):
+        extra["restart_marker_blocks"] = int(restart_interval)
+    Image.fromarray(np.ascontiguousarray(arr)).save(buf, format="JPEG", quality=int(quality), **extra)
     return buf.getvalue()
 
 

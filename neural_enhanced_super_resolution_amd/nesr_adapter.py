@@ -355,7 +355,8 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     its trace are what they were without them.  use_hip goes to every stage (None: the HIP kernels where they apply; False: the
     torch chains, the same bits).  encode="jpeg" or ("jpeg", quality): what enhance_image writes in the end (cv2.imwrite,
     nesr.py:639-646) -- the bytes of the final RGB frame's JPEG file (quality 95 unless given) instead of the ndarray, encoded on the
-    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home.  image_rgb may be a JPEG or an 8-bit PNG file's bytes:
+    device the frame is on (imgproc.encode_jpeg_u8), so only the file comes home; ("jpeg", quality, {"sampling": ..., "optimize": ...,
+    "restart_interval": ...}) passes that call's options.  image_rgb may be a JPEG or an 8-bit PNG file's bytes:
     they are decoded on the device first (imgproc.decode_jpeg_u8 / decode_png), so only files cross the bus.  png=True: the final RGB frame's lossless PNG
     file instead (what standalone/superres_project.py:203-206 always writes), encoded on the device (imgproc.encode_png); together
     with `encode` it raises ValueError, and encode="png" stays an error.  intermediates=<list>: with config["intermediate_saves"]
@@ -364,9 +365,9 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
     if png and encode is not None:
         raise ValueError("enhance_iterations: png=True and encode are two different files; give one")
     if encode is not None:
-        kind, quality = (encode, 95) if isinstance(encode, str) else tuple(encode)
-        if kind != "jpeg":
-            raise ValueError(f"enhance_iterations: encode must be None, 'jpeg' or ('jpeg', quality), got {encode!r}")
+        kind, quality, jpeg_options = (encode, 95, {}) if isinstance(encode, str) else (tuple(encode) + ({},))[:3]
+        if kind != "jpeg" or (not isinstance(encode, str) and len(encode) not in (2, 3)) or not isinstance(jpeg_options, dict):
+            raise ValueError(f"enhance_iterations: encode must be None, 'jpeg', ('jpeg', quality) or ('jpeg', quality, {{options}}), got {encode!r}")
     cfg = {"iterations": 3, "upscale_factor": 2.0, "denoise_level": 0.5, "adaptive_sharpening": True}
     cfg.update(config or {})
     staged = segmenter is not None or len(extra_upscalers) > 0 or upscaler is None
@@ -437,7 +438,7 @@ def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", pre
             check()
     if encode is not None or png:
         from . import imgproc
-        data = imgproc.encode_png(current, order="rgb") if png else imgproc.encode_jpeg_u8(current, quality, order="rgb")
+        data = imgproc.encode_png(current, order="rgb") if png else imgproc.encode_jpeg_u8(current, quality, order="rgb", **jpeg_options)
         check = getattr(getattr(upscaler, "model", None), "check_range", None)
         if check is not None and isinstance(current, torch.Tensor):
             check()

@@ -907,25 +907,26 @@ class RealESRGANer:
             return evaluate()
 
     @torch.no_grad()
-    def enhance_jpeg(self, img, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+    def enhance_jpeg(self, img, quality=95, outscale=None, alpha_upsampler="realesrgan", *, sampling="4:2:0", optimize=False, restart_interval=0):
         """enhance() followed by cv2.imwrite(path.jpg, output) (standalone/direct_esrgan.py:163-169), the file as bytes:
         (bytes, img_mode).  The quantised frame of enhance()'s route stays on the device and is encoded there
         (imgproc.encode_jpeg_u8: csrc/jpeg.hip); only the file comes home.  The bytes are those of the JPEG file of enhance(img)'s
         frame.  8-bit BGR and gray frames; a BGRA or 16-bit frame raises ValueError (cv2.imwrite would drop the alpha plane or the
-        depth without a word)."""
+        depth without a word).  sampling, optimize, restart_interval: imgproc.encode_jpeg_u8's (cv2's IMWRITE_JPEG_SAMPLING_FACTOR,
+        IMWRITE_JPEG_OPTIMIZE, IMWRITE_JPEG_RST_INTERVAL)."""
         if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             kind = f"{getattr(img, 'dtype', type(img).__name__)} {tuple(getattr(img, 'shape', ()))}"
             raise ValueError(f"enhance_jpeg: an 8-bit BGR [H, W, 3] or gray [H, W] frame, got {kind} (a JPEG file holds neither alpha nor 16 bits)")
-        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler)
+        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler, sampling=sampling, optimize=optimize, restart_interval=restart_interval)
 
-    def _enhance_to_jpeg(self, img, quality, outscale, alpha_upsampler):
+    def _enhance_to_jpeg(self, img, quality, outscale, alpha_upsampler, **options):
         from . import imgproc
 
         def evaluate():
             q, img_mode = self._enhance_once(img, outscale, alpha_upsampler, keep=True)
             if not isinstance(q, torch.Tensor):          # a route that assembles its frame on the host (several devices, no HIP model)
                 q = torch.from_numpy(np.ascontiguousarray(q)).to(self.device)
-            data = imgproc.encode_jpeg_u8(q, quality, order="bgr")
+            data = imgproc.encode_jpeg_u8(q, quality, order="bgr", **options)
             self._check_range()                          # after the copy that waited for the stream, as enhance() does
             return data, img_mode
 
@@ -1002,10 +1003,12 @@ class RealESRGANer:
         return self._again_if_gave_up(lambda: self._enhance_once(img, outscale, alpha_upsampler))
 
     @torch.no_grad()
-    def enhance_image_file_to(self, data_or_path, fmt=None, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+    def enhance_image_file_to(self, data_or_path, fmt=None, quality=95, outscale=None, alpha_upsampler="realesrgan", *, sampling="4:2:0", optimize=False,
+                              restart_interval=0):
         """enhance_image_file followed by cv2.imwrite, the file as bytes: (bytes, img_mode).  fmt=None writes the input's own format
         (standalone/direct_esrgan.py:130,169: read unchanged, write with the input's extension); "png" or "jpeg" force one.  A JPEG
-        file of an alpha or 16-bit frame is enhance_jpeg's ValueError."""
+        file of an alpha or 16-bit frame is enhance_jpeg's ValueError.  sampling, optimize, restart_interval: enhance_jpeg's, for a
+        JPEG file (a PNG file has none of them)."""
         if fmt not in (None, "png", "jpeg"):
             raise ValueError(f"enhance_image_file_to: fmt must be None, 'png' or 'jpeg', got {fmt!r}")
         img, kind = self._read_image(data_or_path, "enhance_image_file_to")
@@ -1013,7 +1016,7 @@ class RealESRGANer:
             return self._enhance_to_png(img, outscale, alpha_upsampler)
         if img.dtype not in (np.uint8, torch.uint8) or not (img.ndim == 2 or (img.ndim == 3 and img.shape[2] == 3)):
             raise ValueError(f"enhance_image_file_to: a JPEG file holds neither alpha nor 16 bits, the frame is {img.dtype} {tuple(img.shape)}")
-        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler)
+        return self._enhance_to_jpeg(img, quality, outscale, alpha_upsampler, sampling=sampling, optimize=optimize, restart_interval=restart_interval)
 
     @torch.no_grad()
     def enhance_file(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):
@@ -1026,10 +1029,11 @@ class RealESRGANer:
         return self._again_if_gave_up(lambda: self._enhance_once(img, outscale, alpha_upsampler))
 
     @torch.no_grad()
-    def enhance_file_jpeg(self, data_or_path, quality=95, outscale=None, alpha_upsampler="realesrgan"):
+    def enhance_file_jpeg(self, data_or_path, quality=95, outscale=None, alpha_upsampler="realesrgan", *, sampling="4:2:0", optimize=False, restart_interval=0):
         """enhance_file followed by cv2.imwrite(path.jpg, output), the file as bytes: (bytes, img_mode).  File bytes in, file bytes out;
-        nothing else crosses the bus."""
-        return self._enhance_to_jpeg(self._read_jpeg(data_or_path, "enhance_file_jpeg"), quality, outscale, alpha_upsampler)
+        nothing else crosses the bus.  sampling, optimize, restart_interval: enhance_jpeg's."""
+        return self._enhance_to_jpeg(self._read_jpeg(data_or_path, "enhance_file_jpeg"), quality, outscale, alpha_upsampler, sampling=sampling,
+                                     optimize=optimize, restart_interval=restart_interval)
 
     @torch.no_grad()
     def enhance_file_png(self, data_or_path, outscale=None, alpha_upsampler="realesrgan"):

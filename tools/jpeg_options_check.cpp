@@ -1,0 +1,75 @@
+// The host code of the JPEG encoder's entries (csrc/jpeg_api.cpp: the plan, the header writer, the argument checks) as a stand-alone
+// host program, for a sanitizer build: nesr_jpeg_header_ex writes into a heap buffer of exactly the size it reported, for every
+// sampling, with and without a restart interval, over the smallest and the largest shapes; nesr_jpeg_scratch_bytes_ex plans them;
+// every bad option is refused by all three entries before a device is touched.  Prints one line; exits 1 on a surprise.
+//   hipcc -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -std=c++17 -g -fsanitize=address,undefined -I include \
+//       -I neural_enhanced_super_resolution_amd/csrc tools/jpeg_options_check.cpp neural_enhanced_super_resolution_amd/csrc/jpeg_api.cpp \
+//       -L/opt/rocm/lib -lamdhip64 -o jpeg_options_check
+#include <cstdint>
+#include <cstdio>
+#include <string>
+
+#include "api_common.h"
+#include "jpeg_kernels.h"
+
+namespace nesr {
+static std::string g_error;
+int set_error(int code, const std::string& msg) {
+    g_error = msg;
+    return code;
+}
+namespace jpeg {
+hipError_t launch_encode(const Plan&, const EncodeArgs&, const Header&, hipStream_t) { return hipErrorNotSupported; }      // never reached here
+hipError_t launch_encode_ex(const Plan&, const EncodeArgs&, const Header&, hipStream_t) { return hipErrorNotSupported; }
+}  // namespace jpeg
+}  // namespace nesr
+
+#define EXPECT(cond) do { if (!(cond)) { std::fprintf(stderr, "line %d: %s (%s)\n", __LINE__, #cond, nesr::g_error.c_str()); return 1; } } while (0)
+
+int main() {
+    const int shapes[][3] = {{1, 1, 3}, {1, 1, 1}, {8, 8, 3}, {17, 9, 3}, {9, 17, 1}, {4320, 7680, 3}, {65535, 65535, 3}, {65535, 65535, 1}, {1, 65535, 3}, {65535, 1, 3}};
+    const int samplings[] = {NESR_JPEG_420, NESR_JPEG_422, NESR_JPEG_444};
+    const int intervals[] = {0, 1, 7, 65535};
+    int headers = 0;
+    for (const auto& s : shapes)
+        for (int sampling : samplings)
+            for (int ri : intervals)
+                for (int quality : {1, 50, 95, 100}) {
+                    const nesr_jpeg_opts o = {quality, sampling, 0, ri};
+                    int n = -1;
+                    EXPECT(nesr_jpeg_header_ex(s[0], s[1], s[2], &o, nullptr, 0, &n) == NESR_OK);
+                    const int want = (s[2] == 3 ? 623 : 328) + (ri ? 6 : 0);
+                    EXPECT(n == want && n <= nesr::jpeg::MAX_HEADER);
+                    uint8_t* buf = new uint8_t[n];
+                    int m = -1;
+                    EXPECT(nesr_jpeg_header_ex(s[0], s[1], s[2], &o, buf, n, &m) == NESR_OK && m == n);
+                    EXPECT(buf[0] == 0xFF && buf[1] == 0xD8 && buf[n - 3] == 0 && buf[n - 2] == 63 && buf[n - 1] == 0);
+                    EXPECT(nesr_jpeg_header_ex(s[0], s[1], s[2], &o, buf, n - 1, &m) == NESR_OK && m == n);      // too small: the size alone
+                    delete[] buf;
+                    ++headers;
+                    for (int optimize : {0, 1}) {
+                        const nesr_jpeg_opts p = {quality, sampling, optimize, ri};
+                        const size_t need = nesr_jpeg_scratch_bytes_ex(s[0], s[1], s[2], &p);
+                        EXPECT(need > 0 && need % 256 == 0);
+                        if (!optimize && !ri && sampling == NESR_JPEG_420) EXPECT(need == nesr_jpeg_scratch_bytes(s[0], s[1], s[2]));
+                    }
+                }
+    const nesr_jpeg_opts bad[] = {{95, 3, 0, 0}, {95, -1, 0, 0}, {95, 0, 0, -1}, {95, 0, 0, 65536}, {0, 0, 0, 0}, {101, 2, 1, 5}};
+    uint8_t byte = 0;
+    uint64_t words[2] = {0, 0};
+    int n = 0;
+    for (const auto& o : bad) {
+        EXPECT(nesr_jpeg_header_ex(8, 8, 3, &o, nullptr, 0, &n) == NESR_ERR_ARG);
+        EXPECT(nesr_jpeg_encode_ex_u8(0, &byte, 24, 8, 8, 3, NESR_ORDER_RGB, &o, &byte, (size_t)1 << 40, &byte, 1, words, nullptr) == NESR_ERR_ARG);
+    }
+    for (int i = 0; i < 4; ++i) EXPECT(nesr_jpeg_scratch_bytes_ex(8, 8, 3, &bad[i]) == 0);
+    const nesr_jpeg_opts optimised = {95, NESR_JPEG_444, 1, 0};
+    EXPECT(nesr_jpeg_header_ex(8, 8, 3, &optimised, nullptr, 0, &n) == NESR_ERR_ARG);
+    EXPECT(nesr_jpeg_header_ex(8, 8, 3, nullptr, nullptr, 0, &n) == NESR_ERR_ARG);
+    EXPECT(nesr_jpeg_scratch_bytes_ex(8, 8, 3, nullptr) == 0 && nesr_jpeg_scratch_bytes_ex(0, 8, 3, &optimised) == 0);
+    EXPECT(nesr_jpeg_encode_ex_u8(0, &byte, 24, 8, 8, 3, NESR_ORDER_RGB, nullptr, &byte, (size_t)1 << 40, &byte, 1, words, nullptr) == NESR_ERR_ARG);
+    EXPECT(nesr_jpeg_encode_ex_u8(0, &byte, 23, 8, 8, 3, NESR_ORDER_RGB, &optimised, &byte, (size_t)1 << 40, &byte, 1, words, nullptr) == NESR_ERR_ARG);
+    EXPECT(nesr_jpeg_encode_ex_u8(0, &byte, 24, 8, 8, 3, NESR_ORDER_RGB, &optimised, &byte, 16, &byte, 1, words, nullptr) == NESR_ERR_ARG);
+    std::printf("jpeg_options_check: %d headers written into buffers of their exact size, every bad option refused\n", headers);
+    return 0;
+}
