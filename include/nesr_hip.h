@@ -982,6 +982,49 @@ enum { NESR_PIL_LANCZOS = 1, NESR_PIL_BILINEAR = 2 };
 int nesr_pil_resize_u8(int device_id, const uint8_t* src_dev, int H, int W, int C, uint8_t* dst_dev, int out_h, int out_w, int filter,
                        void* hip_stream);
 
+/*
+ * ---- Swin2SR, a second upscaler for the ensemble (csrc/swin2sr.hip, swin2sr_api.cpp) -- swin2sr.Swin2SR.
+ * transformers' Swin2SRForImageSuperResolution in eval mode: f32 storage, every product on the f32-input MFMA.
+ *
+ * nesr_swin2sr_create takes Swin2SRConfig's fields by name; depths and num_heads hold num_stages (1..16) entries.  The
+ * configuration is checked before any device is touched.  NESR_ERR_UNSUPPORTED (the text names the field) for upsampler
+ * "pixelshuffle_aux" or any name but pixelshuffle / pixelshuffledirect / nearest+conv, resi_connection other than "1conv",
+ * use_absolute_embeddings, patch_size != 1, qkv_bias false, image_size <= window_size, num_heads that differ between stages or do
+ * not divide embed_dim, an upscale the head is not built for (pixelshuffle: 2^n or 3; nearest+conv: 4), and a window / width
+ * whose working set exceeds the 160 KiB of LDS.  Anything else out of range is NESR_ERR_ARG.
+ *
+ * nesr_swin2sr_load_weight: keys are transformers' state_dict names (one generation: conversion_mapping.py renames nothing for
+ * Swin2SR); an unknown key or a wrong shape is NESR_ERR_ARG; keys ending in relative_position_index, relative_coords_table or
+ * attn_mask are accepted and ignored.  nesr_swin2sr_finalize: a missing key is NESR_ERR_STATE; computes each layer's position bias
+ * table 16 sigmoid(MLP(table))[index] in double on the host and uploads the padded, transposed weights.
+ *
+ * nesr_swin2sr_forward_f32: pixel_values_dev [1, C, H, W] f32, H and W multiples of window_size (NESR_ERR_ARG otherwise) ->
+ * out_dev [1, num_channels_out, H s, W s] f32; capacity counts floats.  nesr_swin2sr_upscale_u8: an HWC u8 RGB frame of any size ->
+ * the HWC u8 frame [H s, W s, 3]; capacity counts bytes.  It does what Swin2SRImageProcessor and the documented post-processing
+ * do: / 255, symmetric padding right and bottom to (n / 8 + 1) * 8, the model (with its own reflect padding to the window), the
+ * crop, clamp to [0, 1], x 255, round to nearest even; the paddings, the normalisation and the quantiser run inside the first
+ * and the last convolution.  A capacity too small is NESR_ERR_ARG before any launch; the workspace grows with the frame
+ * (NESR_ERR_NOMEM when it cannot).  nesr_swin2sr_output_size touches no device and needs no context.
+ */
+typedef struct nesr_swin2sr nesr_swin2sr;
+int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int patch_size, int num_channels, int num_channels_out,
+                        int embed_dim, int num_stages, const int* depths, const int* num_heads, int window_size, double mlp_ratio,
+                        int qkv_bias, int use_absolute_embeddings, double layer_norm_eps, int upscale, double img_range,
+                        const char* resi_connection, const char* upsampler);
+void nesr_swin2sr_destroy(nesr_swin2sr* ctx);
+int nesr_swin2sr_num_tensors(const nesr_swin2sr* ctx);
+int nesr_swin2sr_load_weight(nesr_swin2sr* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim);
+int nesr_swin2sr_finalize(nesr_swin2sr* ctx);
+int nesr_swin2sr_output_size(int upscale, int H, int W, int* out_h, int* out_w);
+int nesr_swin2sr_forward_f32(nesr_swin2sr* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* out_dev, size_t capacity,
+                             void* hip_stream);
+int nesr_swin2sr_upscale_u8(nesr_swin2sr* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, size_t capacity, void* hip_stream);
+/* The launch counter and the per-group event timing, as nesr_segformer_set_timing / nesr_segformer_kernel_time_ms. */
+enum { NESR_S2_GROUP_CONV = 0, NESR_S2_GROUP_PROJ = 1, NESR_S2_GROUP_ATTENTION = 2, NESR_S2_GROUP_MLP = 3, NESR_S2_GROUP_UPSAMPLE = 4,
+       NESR_S2_GROUPS = 5 };
+int nesr_swin2sr_set_timing(nesr_swin2sr* ctx, int enable);
+int nesr_swin2sr_kernel_time_ms(nesr_swin2sr* ctx, double* group_ms, int n_groups, int64_t* launches);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

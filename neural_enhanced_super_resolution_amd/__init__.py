@@ -14,7 +14,8 @@ from .rrdbnet import RRDBNet, conv3x3, last_conv_kernel, rrdbnet_state_dict_spec
 from .srvgg import SRVGGNetCompact, srvgg_state_dict_spec  # noqa: F401
 from .realesrganer import RealESRGANer  # noqa: F401
 from .segformer import SegFormer, segformer_state_dict_spec  # noqa: F401
+from .swin2sr import Swin2SR, swin2sr_state_dict_spec  # noqa: F401
 
-__all__ = ["RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
-           "srvgg_state_dict_spec"]
+__all__ = ["RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "Swin2SR", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
+           "srvgg_state_dict_spec", "swin2sr_state_dict_spec"]
 __version__ = "0.1.0"

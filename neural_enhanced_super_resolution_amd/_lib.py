@@ -165,6 +165,18 @@ SIGNATURES = {
     "nesr_segformer_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_segformer_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_pil_resize_u8": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p]),
+    "nesr_swin2sr_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int),
+                                       _c.POINTER(_c.c_int), _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_double, _c.c_char_p,
+                                       _c.c_char_p]),
+    "nesr_swin2sr_destroy": (None, [_c.c_void_p]),
+    "nesr_swin2sr_num_tensors": (_c.c_int, [_c.c_void_p]),
+    "nesr_swin2sr_load_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "nesr_swin2sr_finalize": (_c.c_int, [_c.c_void_p]),
+    "nesr_swin2sr_output_size": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
+    "nesr_swin2sr_forward_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_swin2sr_upscale_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_swin2sr_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_swin2sr_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),

@@ -1,0 +1,648 @@
+// Swin2SR contexts (nesr_swin2sr_*): the configuration check, strict weight loading, the padded and transposed upload, the
+// continuous position bias tables (computed once on the host in double), a workspace that grows with the frame, and the forward
+// as a chain of launches of the three kernels of swin2sr.hip.  Stands behind transformers' Swin2SRForImageSuperResolution and,
+// for nesr_swin2sr_upscale_u8, its Swin2SRImageProcessor and the documented post-processing.
+#include <cmath>
+#include <cstring>
+#include <map>
+
+#include "api_common.h"
+#include "swin2sr_api.h"
+
+using namespace nesr;
+
+namespace {
+
+struct S2Tensor {
+    std::vector<int64_t> shape;
+    std::vector<float> data;
+    bool have = false;
+    size_t numel() const {
+        size_t n = 1;
+        for (int64_t d : shape) n *= (size_t)d;
+        return n;
+    }
+};
+
+struct S2ConvW {
+    size_t w = 0, b = 0;
+    int cin = 0, cinp = 0, cout = 0, coutp = 0;
+};
+struct S2LayerW {
+    size_t wqkv, bqkv, scale, bias, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
+};
+struct S2StageW {
+    std::vector<S2LayerW> layers;
+    S2ConvW conv;
+    size_t wproj, bproj;
+};
+struct S2Timed {
+    int group;
+    hipEvent_t a, b;
+};
+
+enum { UP_PIXELSHUFFLE = 0, UP_DIRECT = 1, UP_NEAREST = 2 };
+constexpr int kFeatures = 64;      // num_features of the pixelshuffle and nearest+conv heads
+constexpr int kMaxStages = 16;
+constexpr int kProcessorPad = 8;   // Swin2SRImageProcessor.size_divisor
+const float kMean[3] = {0.4488f, 0.4371f, 0.4040f};
+
+}  // namespace
+
+struct nesr_swin2sr {
+    int device = 0, nin = 3, nout = 3, C = 180, cs = 192, nst = 0, ws = 8, hidden = 360, hidp = 368, heads = 6, d = 30, dp = 32, scale = 2, up = 0;
+    int depth[kMaxStages];
+    float eps = 1e-5f, range = 1.f, mean[4] = {0.f, 0.f, 0.f, 0.f};
+    std::map<std::string, S2Tensor> t;
+    std::vector<std::string> order;
+    bool finalized = false;
+    float* d_w = nullptr;
+    S2ConvW first, after, before, up1, up2, hr, fin, direct;
+    std::vector<S2ConvW> ups;
+    size_t wpe = 0, bpe = 0, peg = 0, peb = 0, lng = 0, lnb = 0;
+    std::vector<S2StageW> stages;
+    char* ws_buf = nullptr;
+    size_t ws_bytes = 0;
+    bool timing = false;
+    int64_t launches = 0;
+    std::vector<S2Timed> pending;
+    std::vector<hipEvent_t> spare;
+};
+
+namespace {
+
+void expect(nesr_swin2sr* c, const std::string& key, std::vector<int64_t> shape) {
+    S2Tensor t;
+    t.shape = std::move(shape);
+    c->t[key] = t;
+    c->order.push_back(key);
+}
+void expect_wb(nesr_swin2sr* c, const std::string& name, std::vector<int64_t> wshape, bool bias = true) {
+    const int64_t n = wshape[0];
+    expect(c, name + ".weight", std::move(wshape));
+    if (bias) expect(c, name + ".bias", {n});
+}
+
+bool ends_with(const std::string& s, const char* tail) {
+    const size_t n = strlen(tail);
+    return s.size() >= n && s.compare(s.size() - n, n, tail) == 0;
+}
+
+int grow(char*& buf, size_t& have, size_t bytes) {
+    if (bytes <= have) return NESR_OK;
+    NESR_TRY(hipDeviceSynchronize());
+    if (buf) NESR_TRY(hipFree(buf));
+    buf = nullptr;
+    have = 0;
+    if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
+        buf = nullptr;
+        (void)hipGetLastError();
+        return set_error(NESR_ERR_NOMEM, "Swin2SR: workspace allocation of " + std::to_string(bytes) + " bytes failed (the workspace grows with the frame)");
+    }
+    have = bytes;
+    return NESR_OK;
+}
+
+hipError_t new_event(nesr_swin2sr* c, hipEvent_t* e) {
+    if (!c->spare.empty()) {
+        *e = c->spare.back();
+        c->spare.pop_back();
+        return hipSuccess;
+    }
+    return hipEventCreate(e);
+}
+
+// one launch: counted, and bracketed by an event pair of its group while timing is on
+template <class F>
+int run(nesr_swin2sr* c, int group, hipStream_t s, F&& launch) {
+    S2Timed tm{group, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    if (c->timing) {
+        e = new_event(c, &tm.a);
+        if (e == hipSuccess) e = new_event(c, &tm.b);
+        if (e == hipSuccess) e = hipEventRecord(tm.a, s);
+    }
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) ++c->launches;
+    if (e == hipSuccess && c->timing) e = hipEventRecord(tm.b, s);
+    if (e != hipSuccess) {
+        if (tm.a) c->spare.push_back(tm.a);
+        if (tm.b) c->spare.push_back(tm.b);
+        return set_error(NESR_ERR_HIP, std::string("Swin2SR launch (group ") + std::to_string(group) + "): " + hipGetErrorString(e));
+    }
+    if (c->timing) c->pending.push_back(tm);
+    return NESR_OK;
+}
+#define S2_RUN(...)                  \
+    do {                             \
+        int rc__ = run(__VA_ARGS__); \
+        if (rc__) return rc__;       \
+    } while (0)
+
+int unsupported(const std::string& field, const std::string& why) {
+    return set_error(NESR_ERR_UNSUPPORTED, "nesr_swin2sr_create: " + field + ": " + why);
+}
+
+bool is_pow2(int v) { return v >= 1 && (v & (v - 1)) == 0; }
+
+S2Attn attn_shape(const nesr_swin2sr* c) {
+    S2Attn a;
+    memset(&a, 0, sizeof(a));
+    a.ws = c->ws, a.heads = c->heads, a.d = c->d, a.dp = c->dp, a.c = c->C, a.cs = c->cs;
+    return a;
+}
+
+S2Conv conv_args(const nesr_swin2sr* c, const S2ConvW& w, const float* in, int H, int W, int cs_in, float* out, int cs_out) {
+    S2Conv a;
+    memset(&a, 0, sizeof(a));
+    a.in_mode = S2_IN_ROWS, a.in = in, a.H = H, a.W = W, a.cin = w.cin, a.cinp = w.cinp, a.cs_in = cs_in;
+    a.range = c->range;
+    for (int i = 0; i < 4; ++i) a.mean[i] = c->mean[i];
+    a.w = c->d_w + w.w, a.bias = c->d_w + w.b, a.cout = w.cout, a.coutp = w.coutp;
+    a.shuffle = 1, a.out_mode = S2_OUT_ROWS, a.out = out, a.cs_out = cs_out;
+    return a;
+}
+
+// frame: u8 HWC [fh][fw][3] (processor route) or f32 NCHW [nin][fh][fw] (model route); out: f32 NCHW or u8 HWC, cropped to fh s x fw s
+int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s) {
+    const int mh = frame_u8 ? (fh / kProcessorPad + 1) * kProcessorPad : fh, mw = frame_u8 ? (fw / kProcessorPad + 1) * kProcessorPad : fw;
+    const int H = round_up(mh, c->ws), W = round_up(mw, c->ws);
+    if (H - mh > mh - 1 || W - mw > mw - 1)
+        return set_error(NESR_ERR_ARG, "Swin2SR: the reflect padding to the window (" + std::to_string(c->ws) + ") is wider than the image allows");
+    const size_t T = (size_t)H * W, cs = c->cs, sc = c->scale;
+    const size_t act = align_up(T * cs * 4, 256), upb = c->up == UP_DIRECT ? 0 : align_up(T * sc * sc * kFeatures * 4, 256);
+    int rc = grow(c->ws_buf, c->ws_bytes, 4 * act + 2 * upb);
+    if (rc) return rc;
+    float* FIRST = reinterpret_cast<float*>(c->ws_buf);
+    float* XS = reinterpret_cast<float*>(c->ws_buf + act);
+    float* X = reinterpret_cast<float*>(c->ws_buf + 2 * act);
+    float* T1 = reinterpret_cast<float*>(c->ws_buf + 3 * act);
+    float* UA = reinterpret_cast<float*>(c->ws_buf + 4 * act);
+    float* UB = reinterpret_cast<float*>(c->ws_buf + 4 * act + upb);
+    auto wt = [&](size_t off) { return c->d_w + off; };
+    const int M = (int)T, C = c->C, CS = c->cs;
+
+    {   // first_convolution on the padded, normalised frame -> FIRST (the long residual)
+        S2Conv a = conv_args(c, c->first, nullptr, H, W, 0, FIRST, CS);
+        a.in_mode = frame_u8 ? S2_IN_FRAME_U8 : S2_IN_FRAME_F32, a.in = frame, a.fh = fh, a.fw = fw, a.mh = mh, a.mw = mw;
+        S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+    }
+    auto rows = [&](const float* in, size_t w1, size_t b1, bool ln, size_t g, size_t b, float eps, const float* res, float* o) {
+        S2Rows a;
+        memset(&a, 0, sizeof(a));
+        a.m = M, a.c = C, a.cs = CS, a.in = in;
+        if (w1 != (size_t)-1) a.w1 = wt(w1), a.b1 = wt(b1), a.n1p = CS;
+        if (ln) a.ln_g = wt(g), a.ln_b = wt(b), a.eps = eps;
+        a.res = res, a.out = o;
+        return a;
+    };
+    {   // patch embedding: 1x1 projection + LayerNorm (torch's default eps) -> XS
+        const S2Rows a = rows(FIRST, c->wpe, c->bpe, true, c->peg, c->peb, 1e-5f, nullptr, XS);
+        S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+    }
+    for (int i = 0; i < c->nst; ++i) {
+        const S2StageW& S = c->stages[i];
+        for (int j = 0; j < c->depth[i]; ++j) {
+            const S2LayerW& L = S.layers[j];
+            {
+                S2Attn a = attn_shape(c);
+                a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0;
+                a.in = j == 0 ? XS : X, a.out = X;      // the stage's input stays in XS
+                a.wqkv = wt(L.wqkv), a.bqkv = wt(L.bqkv), a.scale = wt(L.scale), a.bias = wt(L.bias), a.wo = wt(L.wo), a.bo = wt(L.bo);
+                a.ln_g = wt(L.ln1g), a.ln_b = wt(L.ln1b), a.eps = c->eps;
+                S2_RUN(c, NESR_S2_GROUP_ATTENTION, s, [&] { return launch_s2_attn(a, s); });
+            }
+            {
+                S2Rows a = rows(X, L.w1, L.b1, true, L.ln2g, L.ln2b, c->eps, X, X);
+                a.n1p = c->hidp, a.gelu = 1, a.w2 = wt(L.w2), a.b2 = wt(L.b2);
+                S2_RUN(c, NESR_S2_GROUP_MLP, s, [&] { return launch_s2_rows(a, s); });
+            }
+        }
+        {
+            const S2Conv a = conv_args(c, S.conv, X, H, W, CS, T1, CS);
+            S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+        }
+        {   // the stage's 1x1 projection + the stage's input, in place
+            const S2Rows a = rows(T1, S.wproj, S.bproj, false, 0, 0, 0.f, XS, XS);
+            S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+        }
+    }
+    {   // the encoder's LayerNorm -> X
+        const S2Rows a = rows(XS, (size_t)-1, 0, true, c->lng, c->lnb, c->eps, nullptr, X);
+        S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+    }
+    {   // conv_after_body + the long residual -> T1
+        S2Conv a = conv_args(c, c->after, X, H, W, CS, T1, CS);
+        a.res = FIRST, a.cs_res = CS;
+        S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+    }
+    auto finish = [&](S2Conv& a) {      // / img_range + mean, the crop, f32 or u8
+        a.out_mode = out_u8 ? S2_OUT_U8 : S2_OUT_F32, a.out = out, a.cs_out = 0, a.oh = fh * c->scale, a.ow = fw * c->scale;
+    };
+    const int F = kFeatures;
+    if (c->up == UP_DIRECT) {
+        S2Conv a = conv_args(c, c->direct, T1, H, W, CS, nullptr, 0);
+        a.shuffle = c->scale;
+        finish(a);
+        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+        return NESR_OK;
+    }
+    {
+        S2Conv a = conv_args(c, c->before, T1, H, W, CS, UA, F);
+        a.lrelu = 1, a.slope = 0.01f;
+        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+    }
+    float* cur = UA;
+    float* other = UB;
+    int h = H, w = W;
+    if (c->up == UP_PIXELSHUFFLE) {
+        const int r = c->scale == 3 ? 3 : 2;
+        for (const S2ConvW& u : c->ups) {
+            S2Conv a = conv_args(c, u, cur, h, w, F, other, F);
+            a.shuffle = r;
+            S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+            std::swap(cur, other);
+            h *= r, w *= r;
+        }
+    } else {
+        for (const S2ConvW* u : {&c->up1, &c->up2}) {
+            h *= 2, w *= 2;
+            S2Conv a = conv_args(c, *u, cur, h, w, F, other, F);
+            a.in_mode = S2_IN_NEAREST2, a.lrelu = 1, a.slope = 0.2f;
+            S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+            std::swap(cur, other);
+        }
+        S2Conv a = conv_args(c, c->hr, cur, h, w, F, other, F);
+        a.lrelu = 1, a.slope = 0.2f;
+        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+        std::swap(cur, other);
+    }
+    S2Conv a = conv_args(c, c->fin, cur, h, w, F, nullptr, 0);
+    finish(a);
+    S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+    return NESR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int patch_size, int num_channels, int num_channels_out, int embed_dim,
+                        int num_stages, const int* depths, const int* num_heads, int window_size, double mlp_ratio, int qkv_bias,
+                        int use_absolute_embeddings, double layer_norm_eps, int upscale, double img_range, const char* resi_connection,
+                        const char* upsampler) {
+    if (!out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: null out");
+    *out = nullptr;
+    if (!depths || !num_heads || !resi_connection || !upsampler) return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: null configuration argument");
+    if (num_stages < 1 || num_stages > kMaxStages) return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: depths must have 1 .. 16 entries");
+    if (num_channels < 1 || num_channels > 4 || num_channels_out < 1 || num_channels_out > 4)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: num_channels and num_channels_out must be 1 .. 4");
+    if (embed_dim < 1 || embed_dim > 1024 || window_size < 1 || image_size < 1 || upscale < 1 || upscale > 8 || !(mlp_ratio > 0) || !(img_range > 0) ||
+        !(layer_norm_eps >= 0))
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: a size of the configuration is not positive or out of range");
+    for (int i = 0; i < num_stages; ++i)
+        if (depths[i] < 1 || depths[i] > 64 || num_heads[i] < 1) return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: depths must be 1 .. 64 and num_heads positive");
+    const std::string up = upsampler, resi = resi_connection;
+    if (up == "pixelshuffle_aux") return unsupported("upsampler", "pixelshuffle_aux (and its bicubic branch) is not supported");
+    if (up != "pixelshuffle" && up != "pixelshuffledirect" && up != "nearest+conv")
+        return unsupported("upsampler", "'" + up + "' is not one of pixelshuffle, pixelshuffledirect, nearest+conv");
+    if (resi != "1conv") return unsupported("resi_connection", "'" + resi + "' is not supported (1conv only)");
+    if (use_absolute_embeddings) return unsupported("use_absolute_embeddings", "absolute position embeddings are not supported");
+    if (patch_size != 1) return unsupported("patch_size", "must be 1");
+    if (!qkv_bias) return unsupported("qkv_bias", "must be true");
+    if (image_size <= window_size) return unsupported("image_size", "must exceed window_size (the window and the shift are the configuration's then)");
+    for (int i = 0; i < num_stages; ++i) {
+        if (num_heads[i] != num_heads[0]) return unsupported("num_heads", "every stage must have the same number of heads");
+        if (embed_dim % num_heads[i]) return unsupported("num_heads", "embed_dim is not a multiple of the number of heads");
+    }
+    if (up == "pixelshuffle" && !(upscale == 3 || is_pow2(upscale))) return unsupported("upscale", "pixelshuffle is built for 2^n and 3");
+    if (up == "nearest+conv" && upscale != 4) return unsupported("upscale", "nearest+conv is built for 4 only");
+    if (up == "pixelshuffledirect" && upscale * upscale * num_channels_out > 1024) return unsupported("upscale", "too large");
+
+    nesr_swin2sr* c = new nesr_swin2sr();
+    c->device = device_id, c->nin = num_channels, c->nout = num_channels_out, c->C = embed_dim, c->cs = round_up(embed_dim, 16), c->nst = num_stages;
+    c->ws = window_size, c->hidden = (int)(mlp_ratio * embed_dim), c->hidp = round_up(std::max(c->hidden, 1), 16), c->heads = num_heads[0];
+    c->d = embed_dim / c->heads, c->dp = round_up(c->d, 16), c->scale = upscale;
+    c->up = up == "pixelshuffle" ? UP_PIXELSHUFFLE : (up == "pixelshuffledirect" ? UP_DIRECT : UP_NEAREST);
+    c->eps = (float)layer_norm_eps, c->range = (float)img_range;
+    for (int i = 0; i < num_stages; ++i) c->depth[i] = depths[i];
+    if (num_channels == 3 && num_channels_out == 3)
+        for (int i = 0; i < 3; ++i) c->mean[i] = kMean[i];
+    {   // what the kernels keep in LDS
+        S2Attn a = attn_shape(c);
+        S2Rows r;
+        memset(&r, 0, sizeof(r));
+        r.cs = c->cs, r.n1p = c->hidp, r.w1 = reinterpret_cast<const float*>(1);
+        S2Conv v;
+        memset(&v, 0, sizeof(v));
+        v.cinp = round_up(embed_dim, 4);
+        if (c->hidden < 1 || s2_attn_lds_bytes(a) > S2_LDS_LIMIT || s2_rows_lds_bytes(r) > S2_LDS_LIMIT || s2_conv_lds_bytes(v) > S2_LDS_LIMIT) {
+            delete c;
+            return unsupported("window_size / embed_dim / mlp_ratio", "a window's tokens, a head's q, k, v and its scores (or 32 rows of the MLP) do not fit the 160 KiB of LDS");
+        }
+    }
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || device_id < 0 || device_id >= ndev) {
+        delete c;
+        if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+        return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
+    }
+    const int64_t C = c->C, hid = c->hidden, nf = kFeatures;
+    expect_wb(c, "swin2sr.first_convolution", {C, c->nin, 3, 3});
+    expect_wb(c, "swin2sr.embeddings.patch_embeddings.projection", {C, C, 1, 1});
+    expect_wb(c, "swin2sr.embeddings.patch_embeddings.layernorm", {C});
+    for (int i = 0; i < c->nst; ++i) {
+        const std::string s = "swin2sr.encoder.stages." + std::to_string(i);
+        for (int j = 0; j < c->depth[i]; ++j) {
+            const std::string l = s + ".layers." + std::to_string(j), a = l + ".attention.self";
+            expect(c, a + ".logit_scale", {c->heads, 1, 1});
+            expect_wb(c, a + ".continuous_position_bias_mlp.0", {512, 2});
+            expect_wb(c, a + ".continuous_position_bias_mlp.2", {c->heads, 512}, false);
+            expect_wb(c, a + ".query", {C, C});
+            expect_wb(c, a + ".key", {C, C}, false);
+            expect_wb(c, a + ".value", {C, C});
+            expect_wb(c, l + ".attention.output.dense", {C, C});
+            expect_wb(c, l + ".layernorm_before", {C});
+            expect_wb(c, l + ".intermediate.dense", {hid, C});
+            expect_wb(c, l + ".output.dense", {C, hid});
+            expect_wb(c, l + ".layernorm_after", {C});
+        }
+        expect_wb(c, s + ".conv", {C, C, 3, 3});
+        expect_wb(c, s + ".patch_embed.projection", {C, C, 1, 1});
+    }
+    expect_wb(c, "swin2sr.layernorm", {C});
+    expect_wb(c, "swin2sr.conv_after_body", {C, C, 3, 3});
+    if (c->up == UP_DIRECT) {
+        expect_wb(c, "upsample.conv", {(int64_t)upscale * upscale * c->nout, C, 3, 3});
+    } else {
+        expect_wb(c, "upsample.conv_before_upsample", {nf, C, 3, 3});
+        if (c->up == UP_PIXELSHUFFLE) {
+            if (upscale == 3) {
+                expect_wb(c, "upsample.upsample.convolution", {9 * nf, nf, 3, 3});
+            } else {
+                for (int i = 0; (1 << i) < upscale; ++i) expect_wb(c, "upsample.upsample.convolution_" + std::to_string(i), {4 * nf, nf, 3, 3});
+            }
+        } else {
+            for (const char* n : {"conv_up1", "conv_up2", "conv_hr"}) expect_wb(c, std::string("upsample.") + n, {nf, nf, 3, 3});
+        }
+        expect_wb(c, "upsample.final_convolution", {c->nout, nf, 3, 3});
+    }
+    *out = c;
+    return NESR_OK;
+}
+
+void nesr_swin2sr_destroy(nesr_swin2sr* c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    for (const S2Timed& tm : c->pending) {
+        (void)hipEventDestroy(tm.a);
+        (void)hipEventDestroy(tm.b);
+    }
+    for (hipEvent_t e : c->spare) (void)hipEventDestroy(e);
+    if (c->ws_buf) (void)hipFree(c->ws_buf);
+    if (c->d_w) (void)hipFree(c->d_w);
+    delete c;
+}
+
+int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return c ? (int)c->order.size() : 0; }
+
+int nesr_swin2sr_load_weight(nesr_swin2sr* c, const char* key, const float* data, const int64_t* shape, int ndim) {
+    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_load_weight: null argument");
+    const std::string k = key;
+    // buffers older checkpoints carry: recomputed here from the configuration
+    if (ends_with(k, "relative_position_index") || ends_with(k, "relative_coords_table") || ends_with(k, "attn_mask")) return NESR_OK;
+    auto it = c->t.find(k);
+    if (it == c->t.end()) return set_error(NESR_ERR_ARG, std::string("unexpected key in state_dict: ") + key);
+    S2Tensor& t = it->second;
+    bool same = ndim == (int)t.shape.size();
+    for (int i = 0; same && i < ndim; ++i) same = shape[i] == t.shape[i];
+    if (!same) {
+        std::string want;
+        for (int64_t d : t.shape) want += (want.empty() ? "" : ",") + std::to_string(d);
+        return set_error(NESR_ERR_ARG, "size mismatch for " + k + ": expected [" + want + "]");
+    }
+    t.data.assign(data, data + t.numel());
+    t.have = true;
+    c->finalized = false;
+    return NESR_OK;
+}
+
+int nesr_swin2sr_finalize(nesr_swin2sr* c) {
+    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_finalize: null context");
+    std::string missing;
+    int nmiss = 0;
+    for (const std::string& k : c->order)
+        if (!c->t[k].have && nmiss++ < 4) missing += (missing.empty() ? "" : ", ") + k;
+    if (nmiss) return set_error(NESR_ERR_STATE, "missing keys in state_dict (" + std::to_string(nmiss) + "): " + missing);
+
+    std::vector<float> host;
+    auto reserve = [&](size_t floats) {
+        const size_t at = host.size();
+        host.resize(align_up(at + floats, 64), 0.f);
+        return at;
+    };
+    auto data = [&](const std::string& key) -> const std::vector<float>& { return c->t[key].data; };
+    // a vector, zero padded to `padded`
+    auto vec = [&](const std::string& key, int padded) {
+        const std::vector<float>& v = data(key);
+        const size_t at = reserve(std::max<size_t>(padded, v.size()));
+        std::copy(v.begin(), v.end(), host.begin() + at);
+        return at;
+    };
+    // torch's Linear / 1x1 conv weight [n][k] -> Wt[round16(k)][round16(n)]
+    auto linear = [&](const std::string& key, int n, int k) {
+        const std::vector<float>& w = data(key);
+        const int np = round_up(n, 16), kp = round_up(k, 16);
+        const size_t at = reserve((size_t)kp * np);
+        for (int o = 0; o < n; ++o)
+            for (int kk = 0; kk < k; ++kk) host[at + (size_t)kk * np + o] = w[(size_t)o * k + kk];
+        return at;
+    };
+    // conv weight [n][cin][3][3] -> Wt[(tap * cinp + ci)][coutp]
+    auto conv = [&](const std::string& name, int n, int cin) {
+        const std::vector<float>& w = data(name + ".weight");
+        S2ConvW r;
+        r.cin = cin, r.cinp = round_up(cin, 4), r.cout = n, r.coutp = round_up(n, 16);
+        r.w = reserve((size_t)9 * r.cinp * r.coutp);
+        for (int o = 0; o < n; ++o)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int t = 0; t < 9; ++t) host[r.w + ((size_t)t * r.cinp + ci) * r.coutp + o] = w[((size_t)o * cin + ci) * 9 + t];
+        r.b = vec(name + ".bias", r.coutp);
+        return r;
+    };
+    const int C = c->C, CS = c->cs, ws = c->ws, n = ws * ws, heads = c->heads, d = c->d, dp = c->dp;
+
+    // the log-spaced coordinate table (float32 as transformers makes it) and the relative position index
+    const int tw = 2 * ws - 1;
+    std::vector<float> table((size_t)tw * tw * 2);
+    auto log_coord = [&](int r) {
+        float v = (float)r;
+        if (ws > 1) v = v / (float)(ws - 1);
+        v *= 8.0f;
+        const float mag = (float)std::log2((double)(std::fabs(v) + 1.0f)) / 3.0f;
+        return v > 0 ? mag : (v < 0 ? -mag : 0.0f);
+    };
+    for (int i = 0; i < tw; ++i)
+        for (int j = 0; j < tw; ++j) table[((size_t)i * tw + j) * 2] = log_coord(i - (ws - 1)), table[((size_t)i * tw + j) * 2 + 1] = log_coord(j - (ws - 1));
+
+    c->first = conv("swin2sr.first_convolution", C, c->nin);
+    const std::string pe = "swin2sr.embeddings.patch_embeddings";
+    c->wpe = linear(pe + ".projection.weight", C, C);
+    c->bpe = vec(pe + ".projection.bias", CS);
+    c->peg = vec(pe + ".layernorm.weight", CS);
+    c->peb = vec(pe + ".layernorm.bias", CS);
+    c->stages.assign(c->nst, S2StageW());
+    for (int i = 0; i < c->nst; ++i) {
+        S2StageW& S = c->stages[i];
+        const std::string s = "swin2sr.encoder.stages." + std::to_string(i);
+        S.layers.assign(c->depth[i], S2LayerW());
+        for (int j = 0; j < c->depth[i]; ++j) {
+            S2LayerW& L = S.layers[j];
+            const std::string l = s + ".layers." + std::to_string(j), a = l + ".attention.self";
+            const int nq = heads * 3 * dp;
+            L.wqkv = reserve((size_t)CS * nq);
+            L.bqkv = reserve(nq);
+            const char* parts[3] = {".query", ".key", ".value"};
+            for (int p = 0; p < 3; ++p) {
+                const std::vector<float>& w = data(a + parts[p] + ".weight");
+                const std::vector<float>* b = p == 1 ? nullptr : &data(a + parts[p] + ".bias");
+                for (int h = 0; h < heads; ++h)
+                    for (int jd = 0; jd < d; ++jd) {
+                        const int row = h * d + jd, col = (h * 3 + p) * dp + jd;
+                        for (int k = 0; k < C; ++k) host[L.wqkv + (size_t)k * nq + col] = w[(size_t)row * C + k];
+                        if (b) host[L.bqkv + col] = (*b)[row];
+                    }
+            }
+            L.scale = reserve(heads);
+            {
+                const std::vector<float>& ls = data(a + ".logit_scale");
+                for (int h = 0; h < heads; ++h) host[L.scale + h] = (float)std::exp(std::min((double)ls[h], std::log(1.0 / 0.01)));
+            }
+            {   // 16 sigmoid(MLP(table))[index], double on the host, rounded once
+                const std::vector<float>&w0 = data(a + ".continuous_position_bias_mlp.0.weight"), &b0 = data(a + ".continuous_position_bias_mlp.0.bias"),
+                                  &w2 = data(a + ".continuous_position_bias_mlp.2.weight");
+                std::vector<double> tb((size_t)tw * tw * heads, 0.0);
+                for (int e = 0; e < tw * tw; ++e)
+                    for (int u = 0; u < 512; ++u) {
+                        const double hv = (double)w0[u * 2] * table[(size_t)e * 2] + (double)w0[u * 2 + 1] * table[(size_t)e * 2 + 1] + (double)b0[u];
+                        if (hv > 0)
+                            for (int h = 0; h < heads; ++h) tb[(size_t)e * heads + h] += hv * (double)w2[(size_t)h * 512 + u];
+                    }
+                L.bias = reserve((size_t)heads * n * n);
+                for (int h = 0; h < heads; ++h)
+                    for (int p = 0; p < n; ++p)
+                        for (int q = 0; q < n; ++q) {
+                            const int idx = (p / ws - q / ws + ws - 1) * tw + (p % ws - q % ws + ws - 1);
+                            host[L.bias + ((size_t)h * n + p) * n + q] = (float)(16.0 / (1.0 + std::exp(-tb[(size_t)idx * heads + h])));
+                        }
+            }
+            L.wo = linear(l + ".attention.output.dense.weight", C, C);
+            L.bo = vec(l + ".attention.output.dense.bias", CS);
+            L.ln1g = vec(l + ".layernorm_before.weight", CS);
+            L.ln1b = vec(l + ".layernorm_before.bias", CS);
+            L.w1 = linear(l + ".intermediate.dense.weight", c->hidden, C);
+            L.b1 = vec(l + ".intermediate.dense.bias", c->hidp);
+            L.w2 = linear(l + ".output.dense.weight", C, c->hidden);
+            L.b2 = vec(l + ".output.dense.bias", CS);
+            L.ln2g = vec(l + ".layernorm_after.weight", CS);
+            L.ln2b = vec(l + ".layernorm_after.bias", CS);
+        }
+        S.conv = conv(s + ".conv", C, C);
+        S.wproj = linear(s + ".patch_embed.projection.weight", C, C);
+        S.bproj = vec(s + ".patch_embed.projection.bias", CS);
+    }
+    c->lng = vec("swin2sr.layernorm.weight", CS);
+    c->lnb = vec("swin2sr.layernorm.bias", CS);
+    c->after = conv("swin2sr.conv_after_body", C, C);
+    c->ups.clear();
+    if (c->up == UP_DIRECT) {
+        c->direct = conv("upsample.conv", c->scale * c->scale * c->nout, C);
+    } else {
+        c->before = conv("upsample.conv_before_upsample", kFeatures, C);
+        if (c->up == UP_PIXELSHUFFLE) {
+            if (c->scale == 3) {
+                c->ups.push_back(conv("upsample.upsample.convolution", 9 * kFeatures, kFeatures));
+            } else {
+                for (int i = 0; (1 << i) < c->scale; ++i) c->ups.push_back(conv("upsample.upsample.convolution_" + std::to_string(i), 4 * kFeatures, kFeatures));
+            }
+        } else {
+            c->up1 = conv("upsample.conv_up1", kFeatures, kFeatures);
+            c->up2 = conv("upsample.conv_up2", kFeatures, kFeatures);
+            c->hr = conv("upsample.conv_hr", kFeatures, kFeatures);
+        }
+        c->fin = conv("upsample.final_convolution", c->nout, kFeatures);
+    }
+    NESR_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipDeviceSynchronize());
+    if (c->d_w) NESR_TRY(hipFree(c->d_w));
+    c->d_w = nullptr;
+    if (hipMalloc((void**)&c->d_w, host.size() * 4) != hipSuccess) {
+        c->d_w = nullptr;
+        return set_error(NESR_ERR_NOMEM, "Swin2SR: allocating the weights failed");
+    }
+    NESR_TRY(hipMemcpy(c->d_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    c->finalized = true;
+    return NESR_OK;
+}
+
+int nesr_swin2sr_output_size(int upscale, int H, int W, int* out_h, int* out_w) {
+    if (!out_h || !out_w) return set_error(NESR_ERR_ARG, "nesr_swin2sr_output_size: null pointer");
+    if (upscale < 1 || upscale > 8) return set_error(NESR_ERR_ARG, "nesr_swin2sr_output_size: upscale must be 1 .. 8");
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_output_size: a frame of 1 .. 2^24 pixels");
+    *out_h = H * upscale, *out_w = W * upscale;
+    return NESR_OK;
+}
+
+int nesr_swin2sr_forward_f32(nesr_swin2sr* c, const float* x, int N, int C, int H, int W, float* out, size_t capacity, void* stream) {
+    if (!c || !x || !out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_f32: null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, "nesr_swin2sr_forward_f32: weights not finalized (nesr_swin2sr_finalize)");
+    if (N != 1 || C != c->nin) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_f32: expected [1, " + std::to_string(c->nin) + ", H, W]");
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_f32: a frame of 1 .. 2^24 pixels");
+    if (H % c->ws || W % c->ws)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_f32: H and W must be multiples of window_size " + std::to_string(c->ws) + ", got " + std::to_string(H) +
+                                           " x " + std::to_string(W) + " (nesr_swin2sr_upscale_u8 pads a frame as the image processor does)");
+    const size_t need = (size_t)c->nout * H * c->scale * W * c->scale;
+    if (capacity < need) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_f32: the output needs " + std::to_string(need) + " floats, capacity is " + std::to_string(capacity));
+    NESR_TRY(hipSetDevice(c->device));
+    return forward(c, x, false, H, W, out, false, static_cast<hipStream_t>(stream));
+}
+
+int nesr_swin2sr_upscale_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, int W, uint8_t* out, size_t capacity, void* stream) {
+    if (!c || !rgb || !out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_u8: null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, "nesr_swin2sr_upscale_u8: weights not finalized (nesr_swin2sr_finalize)");
+    if (c->nin != 3 || c->nout != 3) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_u8: an RGB frame needs num_channels = num_channels_out = 3");
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_u8: a frame of 1 .. 2^24 pixels");
+    const size_t need = (size_t)3 * H * c->scale * W * c->scale;
+    if (capacity < need) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_u8: the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
+    NESR_TRY(hipSetDevice(c->device));
+    return forward(c, rgb, true, H, W, out, true, static_cast<hipStream_t>(stream));
+}
+
+int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) {
+    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_set_timing: null context");
+    c->timing = enable != 0;
+    return NESR_OK;
+}
+
+int nesr_swin2sr_kernel_time_ms(nesr_swin2sr* c, double* group_ms, int n_groups, int64_t* launches) {
+    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_kernel_time_ms: null context");
+    NESR_TRY(hipSetDevice(c->device));
+    double ms[NESR_S2_GROUPS] = {0};
+    for (const S2Timed& tm : c->pending) {
+        NESR_TRY(hipEventSynchronize(tm.b));
+        float t = 0.f;
+        NESR_TRY(hipEventElapsedTime(&t, tm.a, tm.b));
+        ms[tm.group] += t;
+        c->spare.push_back(tm.a);
+        c->spare.push_back(tm.b);
+    }
+    c->pending.clear();
+    for (int i = 0; group_ms && i < n_groups && i < NESR_S2_GROUPS; ++i) group_ms[i] = ms[i];
+    if (launches) *launches = c->launches;
+    c->launches = 0;
+    return NESR_OK;
+}
+
+}  // extern "C"

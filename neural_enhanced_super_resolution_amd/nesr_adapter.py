@@ -325,6 +325,18 @@ def realesrganer_stage(up):
     return stage
 
 
+def swin2sr_stage(model, device=None):
+    """A swin2sr.Swin2SR as an `extra_upscalers` entry of enhance_iterations: RGB u8 frame -> upscaled RGB u8 frame, kept on the
+    device (model.upscale: the image processor's padding, the network, the crop and the quantiser in one chain of HIP launches).
+    The slot the reference's ensemble (nesr.py:1033-1054) leaves to a second upscaler.  `device`: where a host frame goes
+    (default: the current ROCm device); a device frame stays where it is."""
+    def stage(frame_rgb):
+        if isinstance(frame_rgb, torch.Tensor) and frame_rgb.is_cuda:
+            return model.upscale(frame_rgb)
+        return model.upscale(_u8_on(frame_rgb, torch.device("cuda") if device is None else torch.device(device)))
+    return stage
+
+
 def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", preprocess=None, postprocess=None,
                        trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None,
                        encode=None, png=False, intermediates=None):

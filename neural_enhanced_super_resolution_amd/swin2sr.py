@@ -1,0 +1,296 @@
+"""``Swin2SR``: transformers' ``Swin2SRForImageSuperResolution`` (the SwinV2 window-attention super-resolution transformer) as HIP
+kernels behind the C ABI (csrc/swin2sr.hip, csrc/swin2sr_api.cpp): a second upscaler for the slot the reference's ensemble step
+averages over (nesr/nesr.py:1033-1054) and its first-generation pipeline leaves a stub (standalone/superres_project.py:80-88).
+
+The module owns ordinary torch Parameters under ``transformers``-5's names (``swin2sr.encoder.stages.{i}.layers.{j}.attention.self.
+query.weight`` ...; there is one key generation, transformers' conversion mapping renames nothing for Swin2SR) and has no torch
+implementation of its forward.  ``forward(pixel_values)`` gives the reconstruction [1, C_out, H s, W s] of a [1, C, H, W] float32
+tensor whose H and W are multiples of the window (transformers itself fails on anything else); ``upscale(frame)`` takes an
+[H, W, 3] uint8 RGB frame of any size and returns the uint8 frame [H s, W s, 3], doing what ``Swin2SRImageProcessor`` and the
+documented post-processing do (/ 255, symmetric padding to (n // 8 + 1) * 8, the model, the crop, clamp, x 255, round).  Both run
+on the ROCm device; calling the object with a uint8 HWC frame is ``upscale``.
+
+Supported: upsampler pixelshuffle (x2^n, x3), pixelshuffledirect, nearest+conv (x4); resi_connection "1conv"; patch_size 1;
+qkv_bias True; image_size > window_size; the same number of heads in every stage.  Anything else raises NesrUnsupportedError
+when the context is created, and the message names the field.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+from collections import OrderedDict
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+
+DEFAULTS = dict(image_size=64, patch_size=1, num_channels=3, num_channels_out=None, embed_dim=180, depths=(6, 6, 6, 6, 6, 6),
+                num_heads=(6, 6, 6, 6, 6, 6), window_size=8, mlp_ratio=2.0, qkv_bias=True, use_absolute_embeddings=False,
+                layer_norm_eps=1e-5, upscale=2, img_range=1.0, resi_connection="1conv", upsampler="pixelshuffle")
+NUM_FEATURES = 64                     # the width of the pixelshuffle and nearest+conv heads
+KERNEL_GROUPS = ("conv", "projection", "attention", "mlp", "upsample")      # NESR_S2_GROUP_*
+_IGNORED = ("relative_position_index", "relative_coords_table", "attn_mask")      # buffers older checkpoints carry
+
+
+def _config(cfg):
+    unknown = sorted(set(cfg) - set(DEFAULTS))
+    if unknown:
+        raise TypeError(f"Swin2SR: unknown configuration field(s) {unknown}; expected some of {sorted(DEFAULTS)}")
+    c = dict(DEFAULTS)
+    c.update(cfg)
+    c["depths"], c["num_heads"] = tuple(int(v) for v in c["depths"]), tuple(int(v) for v in c["num_heads"])
+    if len(c["depths"]) != len(c["num_heads"]) or not c["depths"]:
+        raise ValueError(f"Swin2SR: depths and num_heads must have the same, positive number of entries, got {c['depths']} and {c['num_heads']}")
+    if c["num_channels_out"] is None:
+        c["num_channels_out"] = c["num_channels"]
+    return c
+
+
+def swin2sr_state_dict_spec(**cfg):
+    """Ordered {key: shape} of a Swin2SRForImageSuperResolution checkpoint under transformers-5's names.  Keyword arguments are
+    Swin2SRConfig's fields; the defaults are the configuration class's own (classical x2: embed 180, six stages of six layers)."""
+    c = _config(cfg)
+    C, hid, nf = int(c["embed_dim"]), int(c["mlp_ratio"] * c["embed_dim"]), NUM_FEATURES
+    spec = OrderedDict()
+
+    def wb(name, wshape, bias=True):
+        spec[name + ".weight"] = tuple(wshape)
+        if bias:
+            spec[name + ".bias"] = (wshape[0],)
+
+    wb("swin2sr.first_convolution", (C, c["num_channels"], 3, 3))
+    wb("swin2sr.embeddings.patch_embeddings.projection", (C, C, 1, 1))
+    wb("swin2sr.embeddings.patch_embeddings.layernorm", (C,))
+    for i, (depth, heads) in enumerate(zip(c["depths"], c["num_heads"])):
+        s = f"swin2sr.encoder.stages.{i}"
+        for j in range(depth):
+            layer, a = f"{s}.layers.{j}", f"{s}.layers.{j}.attention.self"
+            spec[a + ".logit_scale"] = (heads, 1, 1)
+            wb(a + ".continuous_position_bias_mlp.0", (512, 2))
+            wb(a + ".continuous_position_bias_mlp.2", (heads, 512), bias=False)
+            wb(a + ".query", (C, C), bias=bool(c["qkv_bias"]))
+            wb(a + ".key", (C, C), bias=False)
+            wb(a + ".value", (C, C), bias=bool(c["qkv_bias"]))
+            wb(layer + ".attention.output.dense", (C, C))
+            wb(layer + ".layernorm_before", (C,))
+            wb(layer + ".intermediate.dense", (hid, C))
+            wb(layer + ".output.dense", (C, hid))
+            wb(layer + ".layernorm_after", (C,))
+        wb(s + ".conv", (C, C, 3, 3))
+        wb(s + ".patch_embed.projection", (C, C, 1, 1))
+    wb("swin2sr.layernorm", (C,))
+    wb("swin2sr.conv_after_body", (C, C, 3, 3))
+    up, scale, cout = c["upsampler"], int(c["upscale"]), c["num_channels_out"]
+    if up == "pixelshuffledirect":
+        wb("upsample.conv", (scale * scale * cout, C, 3, 3))
+    elif up in ("pixelshuffle", "nearest+conv"):
+        wb("upsample.conv_before_upsample", (nf, C, 3, 3))
+        if up == "nearest+conv":
+            for name in ("conv_up1", "conv_up2", "conv_hr"):
+                wb("upsample." + name, (nf, nf, 3, 3))
+        elif scale == 3:
+            wb("upsample.upsample.convolution", (9 * nf, nf, 3, 3))
+        else:
+            for i in range(int(math.log2(max(scale, 1)))):
+                wb(f"upsample.upsample.convolution_{i}", (4 * nf, nf, 3, 3))
+        wb("upsample.final_convolution", (cout, nf, 3, 3))
+    # any other head has no supported weight set: the context's creation names the field
+    return spec
+
+
+class _Holder(nn.Module):
+    """One level of the parameter tree.  Not callable."""
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("Swin2SR's sub-modules hold weights only; Swin2SR.forward runs in libnesr_hip.so")
+
+
+class Swin2SR(nn.Module):
+    """Swin2SRForImageSuperResolution in eval mode on the HIP path.  Keyword arguments are Swin2SRConfig's fields."""
+
+    def __init__(self, **cfg):
+        super().__init__()
+        self.config = _config(cfg)
+        for key, shape in swin2sr_state_dict_spec(**self.config).items():
+            *path, leaf = key.split(".")
+            mod = self
+            for name in path:
+                if name not in mod._modules:
+                    mod.add_module(name, _Holder())
+                mod = mod._modules[name]
+            if leaf == "logit_scale":
+                init = torch.full(shape, math.log(10.0))
+            else:
+                init = torch.ones(shape) if (leaf == "weight" and len(shape) == 1) else torch.zeros(shape)
+            mod.register_parameter(leaf, nn.Parameter(init, requires_grad=False))
+        self.calls = 0            # forwards so far (a caller can assert that the network really ran)
+        self._handles = {}        # device index -> context with the current weights
+        self._timing = False
+        self.eval()
+
+    # ------------------------------------------------------------------ weights
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """Strict: a missing or an unexpected key raises.  The buffers older checkpoints carry (relative_position_index,
+        relative_coords_table, attn_mask) are dropped: they follow from the configuration."""
+        sd = OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith(_IGNORED))
+        out = super().load_state_dict(sd, strict=strict, **kw)
+        self._release()
+        return out
+
+    @classmethod
+    def from_checkpoint(cls, path, **cfg):
+        """A model with the weights of a local ``model.safetensors`` or ``pytorch_model.bin`` (or of the directory that holds
+        one).  Anything that is not an existing local path raises: nothing is ever fetched."""
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            for name in ("model.safetensors", "pytorch_model.bin"):
+                if os.path.isfile(os.path.join(path, name)):
+                    path = os.path.join(path, name)
+                    break
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"Swin2SR.from_checkpoint: {path!r} is not a local checkpoint file (a hub id is not fetched: "
+                                    "pass the path of a downloaded model.safetensors or pytorch_model.bin)")
+        if path.endswith(".safetensors"):
+            from safetensors.torch import load_file
+            sd = load_file(path, device="cpu")
+        else:
+            sd = torch.load(path, map_location="cpu", weights_only=True)
+        model = cls(**cfg)
+        model.load_state_dict(sd)
+        return model
+
+    def _apply(self, fn, *a, **k):
+        out = super()._apply(fn, *a, **k)
+        self._release()
+        return out
+
+    def train(self, mode=True):
+        if mode:
+            raise RuntimeError("Swin2SR is inference only (eval mode: no dropout, no stochastic depth)")
+        return super().train(False)
+
+    # ------------------------------------------------------------------ contexts
+    def _release(self):
+        handles, self._handles = getattr(self, "_handles", {}), {}
+        for h in handles.values():
+            _lib.load().nesr_swin2sr_destroy(h)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+    def _create(self, index):
+        """A context of this configuration without weights (NesrUnsupportedError names the field the kernels do not take)."""
+        lib = _lib.load()
+        c = self.config
+        n = len(c["depths"])
+        handle = ctypes.c_void_p()
+        rc = lib.nesr_swin2sr_create(ctypes.byref(handle), index, int(c["image_size"]), int(c["patch_size"]), int(c["num_channels"]),
+                                     int(c["num_channels_out"]), int(c["embed_dim"]), n, (ctypes.c_int * n)(*c["depths"]),
+                                     (ctypes.c_int * n)(*c["num_heads"]), int(c["window_size"]), float(c["mlp_ratio"]), int(bool(c["qkv_bias"])),
+                                     int(bool(c["use_absolute_embeddings"])), float(c["layer_norm_eps"]), int(c["upscale"]), float(c["img_range"]),
+                                     str(c["resi_connection"]).encode(), str(c["upsampler"]).encode())
+        if rc == _lib.ERR_UNSUPPORTED:
+            msg = lib.nesr_last_error()
+            raise _lib.NesrUnsupportedError(f"nesr_swin2sr_create failed ({rc}): {msg.decode() if msg else '?'}")
+        _lib.check(rc, "nesr_swin2sr_create")
+        return handle
+
+    def _context(self, device):
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        if index in self._handles:
+            return self._handles[index]
+        lib = _lib.load()
+        handle = self._create(index)
+        try:
+            for key, t in self.state_dict().items():
+                t = t.detach().to("cpu", torch.float32).contiguous()
+                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
+                _lib.check(lib.nesr_swin2sr_load_weight(handle, key.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()), "nesr_swin2sr_load_weight")
+            _lib.check(lib.nesr_swin2sr_finalize(handle), "nesr_swin2sr_finalize")
+            _lib.check(lib.nesr_swin2sr_set_timing(handle, 1 if self._timing else 0), "nesr_swin2sr_set_timing")
+        except Exception:
+            lib.nesr_swin2sr_destroy(handle)
+            raise
+        self._handles[index] = handle
+        return handle
+
+    @staticmethod
+    def _require_device(t, what):
+        if not t.is_cuda:
+            raise RuntimeError(f"Swin2SR.{what}: the tensor is on {t.device}; the forward runs on the ROCm device only "
+                               "(there is no CPU or PyTorch fallback)")
+
+    # ------------------------------------------------------------------ forward
+    def output_size(self, h, w):
+        """(oh, ow) of the result for an h x w input or frame: h s x w s, as the library computes it.  Needs no device."""
+        oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().nesr_swin2sr_output_size(int(self.config["upscale"]), int(h), int(w), ctypes.byref(oh), ctypes.byref(ow)),
+                   "nesr_swin2sr_output_size")
+        return oh.value, ow.value
+
+    def forward(self, pixel_values):
+        """pixel_values [1, C, H, W] float32 on the device (H, W multiples of window_size) -> reconstruction [1, C_out, H s, W s]."""
+        if pixel_values.dtype == torch.uint8 and pixel_values.dim() == 3:
+            return self.upscale(pixel_values)
+        x = pixel_values
+        self._require_device(x, "forward")
+        if x.dim() != 4 or x.dtype != torch.float32:
+            raise ValueError(f"Swin2SR.forward: a [1, {self.config['num_channels']}, H, W] float32 tensor, got {x.dtype} {tuple(x.shape)}")
+        x = x.contiguous()
+        n, ch, h, w = x.shape
+        with torch.cuda.device(x.device):
+            handle = self._context(x.device)
+            out = torch.empty((1, self.config["num_channels_out"]) + self.output_size(h, w), dtype=torch.float32, device=x.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+            _lib.check(_lib.load().nesr_swin2sr_forward_f32(handle, ctypes.c_void_p(x.data_ptr()), n, ch, h, w, ctypes.c_void_p(out.data_ptr()),
+                                                            out.numel(), stream), "nesr_swin2sr_forward_f32")
+        self.calls += 1
+        return out
+
+    def upscale(self, frame, device=None):
+        """[H, W, 3] uint8 RGB frame -> the uint8 frame [H s, W s, 3] on the device.  `frame` is a tensor on the device, or an
+        ndarray, which is copied up once (to `device`, default the current ROCm device)."""
+        if isinstance(frame, np.ndarray):
+            frame = torch.from_numpy(np.ascontiguousarray(frame)).to(torch.device("cuda") if device is None else torch.device(device))
+        self._require_device(frame, "upscale")
+        if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8 or frame.numel() == 0:
+            raise ValueError(f"Swin2SR.upscale: an [H, W, 3] uint8 frame, got {frame.dtype} {tuple(frame.shape)}")
+        frame = frame.contiguous()
+        h, w = frame.shape[:2]
+        with torch.cuda.device(frame.device):
+            handle = self._context(frame.device)
+            out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=frame.device)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
+            _lib.check(_lib.load().nesr_swin2sr_upscale_u8(handle, ctypes.c_void_p(frame.data_ptr()), h, w, ctypes.c_void_p(out.data_ptr()),
+                                                           out.numel(), stream), "nesr_swin2sr_upscale_u8")
+        self.calls += 1
+        return out
+
+    # ------------------------------------------------------------------ timing
+    def set_kernel_timing(self, enable=True):
+        """Switches the per-group event timing of every context (kernel_time_ms reads it; the launch counter always runs)."""
+        self._timing = bool(enable)
+        for h in self._handles.values():
+            _lib.check(_lib.load().nesr_swin2sr_set_timing(h, 1 if enable else 0), "nesr_swin2sr_set_timing")
+
+    def kernel_time_ms(self, device=None):
+        """{"launches": kernel launches, "groups": {name: ms}} since the last call, summed over the forwards in between."""
+        handles = list(self._handles.items())
+        if device is not None:
+            handles = [(i, h) for i, h in handles if i == torch.device(device).index]
+        launches, groups = 0, OrderedDict((name, 0.0) for name in KERNEL_GROUPS)
+        for index, h in handles:
+            ms = (ctypes.c_double * len(KERNEL_GROUPS))()
+            n = ctypes.c_int64(0)
+            with torch.cuda.device(index):
+                _lib.check(_lib.load().nesr_swin2sr_kernel_time_ms(h, ms, len(KERNEL_GROUPS), ctypes.byref(n)), "nesr_swin2sr_kernel_time_ms")
+            launches += n.value
+            for name, v in zip(KERNEL_GROUPS, ms):
+                groups[name] += v
+        return {"launches": launches, "groups": groups}

@@ -1,0 +1,62 @@
+"""GPU: the crafted cases of tests/swin2sr_cases.py through Swin2SR(**cfg) on the HIP path (csrc/swin2sr.hip);
+test_swin2sr_cases_host.py shows on the CPU that each named fault fails a case by 10 x its tolerance.
+
+  reconstruction   max |gpu - f64| <= tol = 8 x max |f32 CPU restatement - f64|, per case (printed as err / tol)
+  bounds           the C entry runs with guard values before and after the output; the workspace is the context's own allocation,
+                   so its bounds are held by the second run: a forward repeated gives the same bits
+"""
+import ctypes
+
+import pytest
+import torch
+
+from neural_enhanced_super_resolution_amd import Swin2SR, _lib
+from tests import swin2sr_cases as C
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+NAMES = [c.name for c in C.cases()]
+GUARD = 4096
+_cache = {}
+
+
+def model(case):
+    if case.name not in _cache:
+        m = Swin2SR(**case.cfg).to(DEV)
+        m.load_state_dict(case.sd)
+        _cache[case.name] = m
+    return _cache[case.name]
+
+
+def guarded_forward(case):
+    """The reconstruction through nesr_swin2sr_forward_f32 into the middle of a buffer of sentinels: (output, guards intact)."""
+    m = model(case)
+    x = case.pixel_values().to(DEV).contiguous()
+    _, ch, h, w = x.shape
+    oh, ow = m.output_size(h, w)
+    n = 3 * oh * ow
+    buf = torch.full((GUARD + n + GUARD,), -7.0, dtype=torch.float32, device=DEV)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    _lib.check(_lib.load().nesr_swin2sr_forward_f32(m._context(x.device), ctypes.c_void_p(x.data_ptr()), 1, ch, h, w,
+                                                    ctypes.c_void_p(buf.data_ptr() + 4 * GUARD), n, stream), "nesr_swin2sr_forward_f32")
+    torch.cuda.synchronize()
+    intact = bool((buf[:GUARD] == -7.0).all()) and bool((buf[GUARD + n:] == -7.0).all())
+    return buf[GUARD:GUARD + n].view(1, 3, oh, ow).cpu(), intact
+
+
+@pytest.mark.parametrize("name", [c.name for c in C.forward_cases()])
+def test_reconstruction_against_float64(name):
+    case = C.by_name(name)
+    got, intact = guarded_forward(case)
+    y64, _, _ = C.reference(case)
+    assert got.shape == y64.shape and got.dtype == torch.float32
+    err, tol = C.error(got, case)
+    print(f"{name}: {tuple(got.shape)}, max |gpu - f64| = {err:.3e}, tol {tol:.3e}, err / tol = {err / tol:.3f}")
+    assert intact, "the entry wrote outside the extent it reports"
+    assert torch.isfinite(got).all()
+    assert err <= tol
+    again, intact = guarded_forward(case)
+    assert intact and torch.equal(got, again), "a forward repeated gives the same bits"
+    via_module = model(case)(case.x.to(DEV)).cpu()
+    assert torch.equal(via_module, got)
