@@ -1,5 +1,8 @@
 // Plumbing shared by every file of the C-ABI layer (nesr_api.cpp, rrdb_forward.cpp, band_api.cpp, shard_api.cpp, oneshot_api.cpp,
-// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, and the kernel-timing hook of a context.
+// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, segformer_api.cpp, swin2sr_api.cpp, jpeg_api.cpp,
+// jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, a workspace that grows, the upload
+// of a model's packed weights, and the kernel-timing hooks of a context (EventTimer: one bracket per forward; GroupTimer: one per
+// launch, summed per kernel group).  The host side of a strictly loaded state dict is state_dict.h.
 // Not part of the public ABI (that is include/nesr_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -87,5 +90,111 @@ struct EventTimer {
         cur = Pair{nullptr, nullptr};
     }
 };
+
+// "<what>: " in front of a message, nothing for a null `what`
+inline std::string prefix(const char* what) { return what ? std::string(what) + ": " : std::string(); }
+
+// A workspace that only grows: frees and allocates anew when `bytes` exceeds what `buf` has (the device is synchronised first,
+// launches that use the old buffer may be in flight).  A failed allocation leaves buf null and no sticky HIP error behind.
+inline int grow(char*& buf, size_t& have, size_t bytes, const char* what) {
+    if (bytes <= have) return NESR_OK;
+    NESR_TRY(hipDeviceSynchronize());
+    if (buf) NESR_TRY(hipFree(buf));
+    buf = nullptr;
+    have = 0;
+    if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
+        buf = nullptr;
+        (void)hipGetLastError();
+        return set_error(NESR_ERR_NOMEM, prefix(what) + "workspace allocation of " + std::to_string(bytes) + " bytes failed" +
+                                             (what ? " (the workspace grows with the frame)" : ""));
+    }
+    have = bytes;
+    return NESR_OK;
+}
+
+// The one weight buffer of a model: the old one is freed (after the device's work), `host` goes up in one copy.
+inline int upload_weights(int device, float*& d_w, const std::vector<float>& host, const char* what) {
+    NESR_TRY(hipSetDevice(device));
+    NESR_TRY(hipDeviceSynchronize());
+    if (d_w) NESR_TRY(hipFree(d_w));
+    d_w = nullptr;
+    if (hipMalloc((void**)&d_w, host.size() * 4) != hipSuccess) {
+        d_w = nullptr;
+        return set_error(NESR_ERR_NOMEM, prefix(what) + "allocating the weights failed");
+    }
+    NESR_TRY(hipMemcpy(d_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    return NESR_OK;
+}
+
+// Launch counter and per-group timing of a context whose forward is a chain of launches (nesr_segformer_*, nesr_swin2sr_*): every
+// launch goes through run(), which counts it and, while `on`, brackets it with an event pair of its kernel group.
+struct GroupTimer {
+    struct Timed {
+        int group;
+        hipEvent_t a, b;
+    };
+    bool on = false;
+    int64_t launches = 0;
+    std::vector<Timed> pending;
+    std::vector<hipEvent_t> spare;
+
+    hipError_t new_event(hipEvent_t* e) {
+        if (!spare.empty()) {
+            *e = spare.back();
+            spare.pop_back();
+            return hipSuccess;
+        }
+        return hipEventCreate(e);
+    }
+    // one launch (the pair goes back to the spare list when the launch or a record fails)
+    template <class F>
+    int run(const char* model, int group, hipStream_t s, F&& launch) {
+        Timed tm{group, nullptr, nullptr};
+        hipError_t e = hipSuccess;
+        if (on) {
+            e = new_event(&tm.a);
+            if (e == hipSuccess) e = new_event(&tm.b);
+            if (e == hipSuccess) e = hipEventRecord(tm.a, s);
+        }
+        if (e == hipSuccess) e = launch();
+        if (e == hipSuccess) ++launches;
+        if (e == hipSuccess && on) e = hipEventRecord(tm.b, s);
+        if (e != hipSuccess) {
+            if (tm.a) spare.push_back(tm.a);
+            if (tm.b) spare.push_back(tm.b);
+            return set_error(NESR_ERR_HIP, std::string(model) + " launch (group " + std::to_string(group) + "): " + hipGetErrorString(e));
+        }
+        if (on) pending.push_back(tm);
+        return NESR_OK;
+    }
+    // waits for the recorded launches; ms[0 .. n_groups) gets each group's sum; hands out and resets the launch count
+    int collect(double* ms, int n_groups, int64_t* n_launches) {
+        for (int i = 0; i < n_groups; ++i) ms[i] = 0.0;
+        for (const Timed& tm : pending) {
+            NESR_TRY(hipEventSynchronize(tm.b));
+            float t = 0.f;
+            NESR_TRY(hipEventElapsedTime(&t, tm.a, tm.b));
+            if (tm.group < n_groups) ms[tm.group] += t;
+        }
+        for (const Timed& tm : pending) spare.insert(spare.end(), {tm.a, tm.b});
+        pending.clear();
+        if (n_launches) *n_launches = launches;
+        launches = 0;
+        return NESR_OK;
+    }
+    void destroy() {
+        for (const Timed& tm : pending) spare.insert(spare.end(), {tm.a, tm.b});
+        for (hipEvent_t e : spare) (void)hipEventDestroy(e);
+        pending.clear();
+        spare.clear();
+    }
+};
+
+// the one way a launch of such a context is made: NESR_RUN(c->timer, "Model", group, stream, [&] { return launch_x(args, stream); })
+#define NESR_RUN(timer, ...)                    \
+    do {                                        \
+        int rc__ = (timer).run(__VA_ARGS__);    \
+        if (rc__) return rc__;                  \
+    } while (0)
 
 }  // namespace nesr

@@ -58,19 +58,7 @@ CWs ws_layout(const nesr_compact* c, int N, int H, int W) {
     return L;
 }
 
-int ensure_ws(nesr_compact* c, size_t bytes) {
-    if (bytes <= c->ws_bytes) return NESR_OK;
-    NESR_TRY(hipDeviceSynchronize());
-    if (c->ws) NESR_TRY(hipFree(c->ws));
-    c->ws = nullptr;
-    c->ws_bytes = 0;
-    if (hipMalloc((void**)&c->ws, bytes) != hipSuccess) {
-        c->ws = nullptr;
-        return set_error(NESR_ERR_NOMEM, "workspace allocation of " + std::to_string(bytes) + " bytes failed");
-    }
-    c->ws_bytes = bytes;
-    return NESR_OK;
-}
+int ensure_ws(nesr_compact* c, size_t bytes) { return grow(c->ws, c->ws_bytes, bytes, nullptr); }
 
 }  // namespace
 

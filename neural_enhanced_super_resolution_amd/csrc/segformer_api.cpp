@@ -9,21 +9,11 @@
 
 #include "api_common.h"
 #include "segformer_api.h"
+#include "state_dict.h"
 
 using namespace nesr;
 
 namespace {
-
-struct SegTensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-    bool have = false;
-    size_t numel() const {
-        size_t n = 1;
-        for (int64_t d : shape) n *= (size_t)d;
-        return n;
-    }
-};
 
 struct SegBlockW {
     size_t ln1g, ln1b, wq, bq, wsr, bsr, srg, srb, wkv, bkv, wo, bo, ln2g, ln2b, w1, b1, dww, dwb, w2, b2;
@@ -40,14 +30,10 @@ struct SegTable {
     int ksize = 0;
 };
 
-struct SegTimed {
-    int group;
-    hipEvent_t a, b;
-};
-
 const float kMean[3] = {0.485f, 0.456f, 0.406f};
 const float kStd[3] = {0.229f, 0.224f, 0.225f};
 constexpr int kModelSize = 512, kSegmentMax = 1024;
+const char* const kName = "SegFormer";      // in the texts of a failed launch or workspace allocation
 
 // ---- PIL's precompute_coeffs + normalize_coeffs_8bpc (src/libImaging/Resample.c) for one axis
 double pil_sinc(double x) {
@@ -136,8 +122,7 @@ struct nesr_segformer {
     int device = 0, nin = 3, nst = 4, dec = 256, labels = 150, labels_p = 160;
     int depth[SEG_MAX_STAGES], sr[SEG_MAX_STAGES], hid[SEG_MAX_STAGES], patch[SEG_MAX_STAGES], stride[SEG_MAX_STAGES], heads[SEG_MAX_STAGES],
         mlp[SEG_MAX_STAGES];
-    std::map<std::string, SegTensor> t;      // every expected key with its shape
-    std::vector<std::string> order;
+    StateDict sd;                            // every expected key with its shape
     bool finalized = false;
     float* d_w = nullptr;
     std::vector<SegStageW> stages;
@@ -147,76 +132,10 @@ struct nesr_segformer {
     char* pre = nullptr;                     // the pre-processing's images
     size_t pre_bytes = 0;
     std::map<std::tuple<int, int, int>, SegTable> tables;
-    bool timing = false;
-    int64_t launches = 0;
-    std::vector<SegTimed> pending;
-    std::vector<hipEvent_t> spare;
+    GroupTimer timer;
 };
 
 namespace {
-
-void expect(nesr_segformer* c, const std::string& key, std::vector<int64_t> shape) {
-    SegTensor t;
-    t.shape = std::move(shape);
-    c->t[key] = t;
-    c->order.push_back(key);
-}
-void expect_wb(nesr_segformer* c, const std::string& name, std::vector<int64_t> wshape) {
-    const int64_t n = wshape[0];
-    expect(c, name + ".weight", std::move(wshape));
-    expect(c, name + ".bias", {n});
-}
-
-int grow(char*& buf, size_t& have, size_t bytes) {
-    if (bytes <= have) return NESR_OK;
-    NESR_TRY(hipDeviceSynchronize());
-    if (buf) NESR_TRY(hipFree(buf));
-    buf = nullptr;
-    have = 0;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
-        buf = nullptr;
-        return set_error(NESR_ERR_NOMEM, "workspace allocation of " + std::to_string(bytes) + " bytes failed");
-    }
-    have = bytes;
-    return NESR_OK;
-}
-
-hipError_t new_event(nesr_segformer* c, hipEvent_t* e) {
-    if (!c->spare.empty()) {
-        *e = c->spare.back();
-        c->spare.pop_back();
-        return hipSuccess;
-    }
-    return hipEventCreate(e);
-}
-
-// one launch: counted, and bracketed by an event pair of its group while timing is on (the pair goes back to the spare list when
-// the launch or a record fails)
-template <class F>
-int run(nesr_segformer* c, int group, hipStream_t s, F&& launch) {
-    SegTimed tm{group, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    if (c->timing) {
-        e = new_event(c, &tm.a);
-        if (e == hipSuccess) e = new_event(c, &tm.b);
-        if (e == hipSuccess) e = hipEventRecord(tm.a, s);
-    }
-    if (e == hipSuccess) e = launch();
-    if (e == hipSuccess) ++c->launches;
-    if (e == hipSuccess && c->timing) e = hipEventRecord(tm.b, s);
-    if (e != hipSuccess) {
-        if (tm.a) c->spare.push_back(tm.a);
-        if (tm.b) c->spare.push_back(tm.b);
-        return set_error(NESR_ERR_HIP, std::string("SegFormer launch (group ") + std::to_string(group) + "): " + hipGetErrorString(e));
-    }
-    if (c->timing) c->pending.push_back(tm);
-    return NESR_OK;
-}
-#define SEG_RUN(...)                 \
-    do {                             \
-        int rc__ = run(__VA_ARGS__); \
-        if (rc__) return rc__;       \
-    } while (0)
 
 constexpr size_t kMaxTables = 16;      // one segment() needs at most four; a context fed many frame sizes starts over when full
 
@@ -320,7 +239,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
     int sh[SEG_MAX_STAGES], sw[SEG_MAX_STAGES];
     stage_dims(c, H, W, sh, sw);
     const SegWs L = ws_layout(c, sh, sw);
-    int rc = grow(c->ws, c->ws_bytes, L.total);
+    int rc = grow(c->ws, c->ws_bytes, L.total, kName);
     if (rc) return rc;
     auto buf = [&](size_t off) { return reinterpret_cast<float*>(c->ws + off); };
     auto wt = [&](size_t off) { return c->d_w + off; };
@@ -342,7 +261,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
             a.ksz = c->patch[i], a.stride = c->stride[i], a.pad = c->patch[i] / 2, a.out_w = sw[i];
             a.k1 = S.kpe, a.k1_real = S.kpe_real, a.n1 = C;
             a.w1 = wt(S.wpe), a.bias1 = wt(S.bpe), a.ln_g = wt(S.peg), a.ln_b = wt(S.peb), a.out1 = X;
-            SEG_RUN(c, NESR_SEG_GROUP_PATCH_EMBED, s, [&] { return launch_seg_fused(a, s); });
+            NESR_RUN(c->timer, kName, NESR_SEG_GROUP_PATCH_EMBED, s, [&] { return launch_seg_fused(a, s); });
         }
         for (const SegBlockW& B : S.blocks) {
             {   // LayerNorm + q (sr > 1: the normalised rows go on to the reduction) | LayerNorm + q, k, v
@@ -350,7 +269,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
                 a.a_mode = SEG_A_ROWS, a.m = T, a.in = X, a.n1 = C, a.ln_g = wt(B.ln1g), a.ln_b = wt(B.ln1b);
                 a.out1 = sr > 1 ? XN : nullptr;
                 a.w2 = wt(B.wq), a.bias2 = wt(B.bq), a.n2 = sr > 1 ? C : 3 * C, a.ldw2 = a.n2, a.out_mode = SEG_OUT_ROWS, a.out2 = Q, a.ld_out2 = a.n2;
-                SEG_RUN(c, NESR_SEG_GROUP_LN_PROJ, s, [&] { return launch_seg_fused(a, s); });
+                NESR_RUN(c->timer, kName, NESR_SEG_GROUP_LN_PROJ, s, [&] { return launch_seg_fused(a, s); });
             }
             int keys = T;
             if (sr > 1) {   // sr x sr / stride sr conv + bias + LayerNorm, then k | v
@@ -360,7 +279,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
                 a.ksz = sr, a.stride = sr, a.pad = 0, a.out_w = sw[i] / sr, a.k1 = a.k1_real = C * sr * sr, a.n1 = C;
                 a.w1 = wt(B.wsr), a.bias1 = wt(B.bsr), a.ln_g = wt(B.srg), a.ln_b = wt(B.srb);
                 a.w2 = wt(B.wkv), a.bias2 = wt(B.bkv), a.n2 = 2 * C, a.ldw2 = 2 * C, a.out_mode = SEG_OUT_ROWS, a.out2 = KV, a.ld_out2 = 2 * C;
-                SEG_RUN(c, NESR_SEG_GROUP_SEQ_REDUCTION, s, [&] { return launch_seg_fused(a, s); });
+                NESR_RUN(c->timer, kName, NESR_SEG_GROUP_SEQ_REDUCTION, s, [&] { return launch_seg_fused(a, s); });
             }
             {   // attention + o_proj + residual, X in place
                 SegAttn a;
@@ -369,19 +288,19 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
                 a.q = Q, a.q_ld = sr > 1 ? C : 3 * C;
                 a.k = sr > 1 ? KV : Q + C, a.v = sr > 1 ? KV + C : Q + 2 * C, a.kv_ld = sr > 1 ? 2 * C : 3 * C;
                 a.wo = wt(B.wo), a.bo = wt(B.bo), a.x = X;
-                SEG_RUN(c, NESR_SEG_GROUP_ATTENTION, s, [&] { return launch_seg_attn(a, s); });
+                NESR_RUN(c->timer, kName, NESR_SEG_GROUP_ATTENTION, s, [&] { return launch_seg_attn(a, s); });
             }
             {   // LayerNorm + fc1 -> H1
                 SegFused a = fused_zero();
                 a.a_mode = SEG_A_ROWS, a.m = T, a.in = X, a.n1 = C, a.ln_g = wt(B.ln2g), a.ln_b = wt(B.ln2b);
                 a.w2 = wt(B.w1), a.bias2 = wt(B.b1), a.n2 = hidden, a.ldw2 = hidden, a.out_mode = SEG_OUT_ROWS, a.out2 = H1, a.ld_out2 = hidden;
-                SEG_RUN(c, NESR_SEG_GROUP_LN_PROJ, s, [&] { return launch_seg_fused(a, s); });
+                NESR_RUN(c->timer, kName, NESR_SEG_GROUP_LN_PROJ, s, [&] { return launch_seg_fused(a, s); });
             }
             {   // gelu(dwconv3x3(H1)) x fc2 + bias + residual, X in place
                 SegFused a = fused_zero();
                 a.a_mode = SEG_A_DWGELU, a.m = T, a.in = H1, a.k1 = hidden, a.n1 = C, a.gh = sh[i], a.gw = sw[i];
                 a.dw_w = wt(B.dww), a.dw_b = wt(B.dwb), a.w1 = wt(B.w2), a.bias1 = wt(B.b2), a.res = X, a.out1 = X;
-                SEG_RUN(c, NESR_SEG_GROUP_MIX_FFN, s, [&] { return launch_seg_fused(a, s); });
+                NESR_RUN(c->timer, kName, NESR_SEG_GROUP_MIX_FFN, s, [&] { return launch_seg_fused(a, s); });
             }
         }
         {   // the stage's LayerNorm -> FEAT (the next stage's image), and the decode head's projection of it
@@ -389,7 +308,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
             a.a_mode = SEG_A_ROWS, a.m = T, a.in = X, a.n1 = C, a.ln_g = wt(S.lng), a.ln_b = wt(S.lnb);
             a.out1 = i + 1 < c->nst ? FEAT : nullptr;
             a.w2 = wt(S.wproj), a.bias2 = wt(S.bproj), a.n2 = c->dec, a.ldw2 = c->dec, a.out_mode = SEG_OUT_ROWS, a.out2 = buf(L.proj[i]), a.ld_out2 = c->dec;
-            SEG_RUN(c, NESR_SEG_GROUP_DECODE_HEAD, s, [&] { return launch_seg_fused(a, s); });
+            NESR_RUN(c->timer, kName, NESR_SEG_GROUP_DECODE_HEAD, s, [&] { return launch_seg_fused(a, s); });
         }
     }
     {   // upsample + concatenate + linear_fuse + BatchNorm + ReLU + classifier (+ argmax)
@@ -400,7 +319,7 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
         a.w1 = wt(c->wfuse), a.bn_scale = wt(c->bn_scale), a.bn_shift = wt(c->bn_shift);
         a.w2 = wt(c->wcls), a.bias2 = wt(c->bcls), a.n2 = c->labels, a.ldw2 = c->labels_p;
         a.out_mode = class_map ? SEG_OUT_ARGMAX : SEG_OUT_NCHW, a.out2 = logits, a.ld_out2 = a.m, a.out2_u8 = class_map;
-        SEG_RUN(c, NESR_SEG_GROUP_DECODE_HEAD, s, [&] { return launch_seg_fused(a, s); });
+        NESR_RUN(c->timer, kName, NESR_SEG_GROUP_DECODE_HEAD, s, [&] { return launch_seg_fused(a, s); });
     }
     return NESR_OK;
 }
@@ -417,7 +336,7 @@ int preprocess(nesr_segformer* c, const uint8_t* rgb, int H, int W, float* pix, 
     }
     const size_t a_bytes = big ? align_up((size_t)H * nw * 3, 256) : 0, b_bytes = big ? align_up((size_t)nh * nw * 3, 256) : 0;
     const size_t c_bytes = align_up((size_t)nh * kModelSize * 3, 256);
-    int rc = grow(c->pre, c->pre_bytes, a_bytes + b_bytes + c_bytes);
+    int rc = grow(c->pre, c->pre_bytes, a_bytes + b_bytes + c_bytes, kName);
     if (rc) return rc;
     uint8_t* ta = reinterpret_cast<uint8_t*>(c->pre);
     uint8_t* tb = ta + a_bytes;
@@ -428,25 +347,25 @@ int preprocess(nesr_segformer* c, const uint8_t* rgb, int H, int W, float* pix, 
         if (nw != w) {
             if ((rc = table_for(c, w, nw, NESR_PIL_LANCZOS, &t))) return rc;
             const SegResample a = resample_args(cur, h, w, 3, 0, nw, *t, ta, nullptr);
-            SEG_RUN(c, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
+            NESR_RUN(c->timer, kName, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
             cur = ta, w = nw;
         }
         if (nh != h) {
             if ((rc = table_for(c, h, nh, NESR_PIL_LANCZOS, &t))) return rc;
             const SegResample a = resample_args(cur, h, w, 3, 1, nh, *t, tb, nullptr);
-            SEG_RUN(c, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
+            NESR_RUN(c->timer, kName, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
             cur = tb, h = nh;
         }
     }
     if (w != kModelSize) {      // the extractor's resize to 512 x 512, PIL BILINEAR
         if ((rc = table_for(c, w, kModelSize, NESR_PIL_BILINEAR, &t))) return rc;
         const SegResample a = resample_args(cur, h, w, 3, 0, kModelSize, *t, tc, nullptr);
-        SEG_RUN(c, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
+        NESR_RUN(c->timer, kName, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
         cur = tc, w = kModelSize;
     }
     if ((rc = table_for(c, h, kModelSize, NESR_PIL_BILINEAR, &t))) return rc;      // h == 512: the one-tap table, the normalisation alone
     const SegResample a = resample_args(cur, h, w, 3, 1, kModelSize, *t, nullptr, pix);
-    SEG_RUN(c, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
+    NESR_RUN(c->timer, kName, NESR_SEG_GROUP_PREPROCESS, s, [&] { return launch_seg_resample(a, s); });
     return NESR_OK;
 }
 
@@ -496,35 +415,36 @@ int nesr_segformer_create(nesr_segformer** out, int device_id, int num_channels,
         c->depth[i] = depths[j], c->sr[i] = sr_ratios[j], c->hid[i] = hidden_sizes[j], c->patch[i] = patch_sizes[j], c->stride[i] = strides[j];
         c->heads[i] = num_attention_heads[j], c->mlp[i] = mlp_ratios[j];
     }
+    StateDict& sd = c->sd;
     int cin = c->nin;
     for (int i = 0; i < c->nst; ++i) {
         const std::string s = "segformer.stages." + std::to_string(i);
         const int64_t ch = c->hid[i], k = c->patch[i], sr = c->sr[i], hidden = ch * c->mlp[i];
-        expect_wb(c, s + ".patch_embeddings.proj", {ch, cin, k, k});
-        expect_wb(c, s + ".patch_embeddings.layer_norm", {ch});
+        sd.expect_wb(s + ".patch_embeddings.proj", {ch, cin, k, k});
+        sd.expect_wb(s + ".patch_embeddings.layer_norm", {ch});
         for (int j = 0; j < c->depth[i]; ++j) {
             const std::string b = s + ".blocks." + std::to_string(j);
-            expect_wb(c, b + ".layernorm_before", {ch});
-            for (const char* p : {"q_proj", "k_proj", "v_proj", "o_proj"}) expect_wb(c, b + ".attention." + p, {ch, ch});
+            sd.expect_wb(b + ".layernorm_before", {ch});
+            for (const char* p : {"q_proj", "k_proj", "v_proj", "o_proj"}) sd.expect_wb(b + ".attention." + p, {ch, ch});
             if (sr > 1) {
-                expect_wb(c, b + ".attention.sequence_reduction.sequence_reduction", {ch, ch, sr, sr});
-                expect_wb(c, b + ".attention.sequence_reduction.layer_norm", {ch});
+                sd.expect_wb(b + ".attention.sequence_reduction.sequence_reduction", {ch, ch, sr, sr});
+                sd.expect_wb(b + ".attention.sequence_reduction.layer_norm", {ch});
             }
-            expect_wb(c, b + ".layernorm_after", {ch});
-            expect_wb(c, b + ".mlp.fc1", {hidden, ch});
-            expect_wb(c, b + ".mlp.dwconv.dwconv", {hidden, 1, 3, 3});
-            expect_wb(c, b + ".mlp.fc2", {ch, hidden});
+            sd.expect_wb(b + ".layernorm_after", {ch});
+            sd.expect_wb(b + ".mlp.fc1", {hidden, ch});
+            sd.expect_wb(b + ".mlp.dwconv.dwconv", {hidden, 1, 3, 3});
+            sd.expect_wb(b + ".mlp.fc2", {ch, hidden});
         }
-        expect_wb(c, s + ".layer_norm", {ch});
+        sd.expect_wb(s + ".layer_norm", {ch});
         cin = (int)ch;
     }
     const int64_t d = c->dec;
-    for (int i = 0; i < c->nst; ++i) expect_wb(c, "decode_head.linear_projections." + std::to_string(i) + ".proj", {d, c->hid[i]});
-    expect(c, "decode_head.linear_fuse.weight", {d, d * c->nst, 1, 1});
-    expect_wb(c, "decode_head.batch_norm", {d});
-    expect(c, "decode_head.batch_norm.running_mean", {d});
-    expect(c, "decode_head.batch_norm.running_var", {d});
-    expect_wb(c, "decode_head.classifier", {c->labels, d, 1, 1});
+    for (int i = 0; i < c->nst; ++i) sd.expect_wb("decode_head.linear_projections." + std::to_string(i) + ".proj", {d, c->hid[i]});
+    sd.expect("decode_head.linear_fuse.weight", {d, d * c->nst, 1, 1});
+    sd.expect_wb("decode_head.batch_norm", {d});
+    sd.expect("decode_head.batch_norm.running_mean", {d});
+    sd.expect("decode_head.batch_norm.running_var", {d});
+    sd.expect_wb("decode_head.classifier", {c->labels, d, 1, 1});
     *out = c;
     return NESR_OK;
 }
@@ -533,11 +453,7 @@ void nesr_segformer_destroy(nesr_segformer* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (const SegTimed& tm : c->pending) {
-        (void)hipEventDestroy(tm.a);
-        (void)hipEventDestroy(tm.b);
-    }
-    for (hipEvent_t e : c->spare) (void)hipEventDestroy(e);
+    c->timer.destroy();
     for (auto& kv : c->tables) free_table(kv.second);
     if (c->ws) (void)hipFree(c->ws);
     if (c->pre) (void)hipFree(c->pre);
@@ -545,66 +461,28 @@ void nesr_segformer_destroy(nesr_segformer* c) {
     delete c;
 }
 
-int nesr_segformer_num_tensors(const nesr_segformer* c) { return c ? (int)c->order.size() : 0; }
+int nesr_segformer_num_tensors(const nesr_segformer* c) { return c ? (int)c->sd.size() : 0; }
 
 int nesr_segformer_load_weight(nesr_segformer* c, const char* key, const float* data, const int64_t* shape, int ndim) {
     if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_segformer_load_weight: null argument");
     const std::string k = seg_new_key(key);
     if (k == "decode_head.batch_norm.num_batches_tracked") return NESR_OK;
-    auto it = c->t.find(k);
-    if (it == c->t.end()) return set_error(NESR_ERR_ARG, std::string("unexpected key in state_dict: ") + key);
-    SegTensor& t = it->second;
-    bool same = ndim == (int)t.shape.size();
-    for (int i = 0; same && i < ndim; ++i) same = shape[i] == t.shape[i];
-    if (!same) {
-        std::string want;
-        for (int64_t d : t.shape) want += (want.empty() ? "" : ",") + std::to_string(d);
-        return set_error(NESR_ERR_ARG, "size mismatch for " + k + ": expected [" + want + "]");
-    }
-    t.data.assign(data, data + t.numel());
-    t.have = true;
-    c->finalized = false;
-    return NESR_OK;
+    const int rc = c->sd.load(k, data, shape, ndim, key);
+    if (!rc) c->finalized = false;
+    return rc;
 }
 
 int nesr_segformer_finalize(nesr_segformer* c) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_finalize: null context");
-    std::string missing;
-    int nmiss = 0;
-    for (const std::string& k : c->order)
-        if (!c->t[k].have && nmiss++ < 4) missing += (missing.empty() ? "" : ", ") + k;
-    if (nmiss) return set_error(NESR_ERR_STATE, "missing keys in state_dict (" + std::to_string(nmiss) + "): " + missing);
+    const StateDict& sd = c->sd;
+    const std::string missing = sd.missing();
+    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
 
-    std::vector<float> host;
-    auto reserve = [&](size_t floats) {
-        const size_t at = host.size();
-        host.resize(align_up(at + floats, 64), 0.f);
-        return at;
-    };
-    auto vec = [&](const std::string& key) {
-        const std::vector<float>& v = c->t[key].data;
-        const size_t at = reserve(v.size());
-        std::copy(v.begin(), v.end(), host.begin() + at);
-        return at;
-    };
-    // torch's Linear / flattened conv weight [n][k] -> host[at + kk * ld + col0 + n], kk = perm(k)
-    auto transpose_into = [&](size_t at, const std::string& key, int n, int k, int ld, int col0) {
-        const std::vector<float>& w = c->t[key].data;
-        for (int o = 0; o < n; ++o)
-            for (int kk = 0; kk < k; ++kk) host[at + (size_t)kk * ld + col0 + o] = w[(size_t)o * k + kk];
-    };
+    HostPack pk;
+    auto vec = [&](const std::string& key) { return pk.vec(sd.data(key)); };
     auto linear = [&](const std::string& name, int n, int k) {
-        const size_t at = reserve((size_t)k * n);
-        transpose_into(at, name + ".weight", n, k, n, 0);
-        return at;
-    };
-    // conv weight [n][cin][ks][ks] -> [(ky * ks + kx) * cin + c][n], the order an NHWC patch is read in
-    auto conv_nhwc = [&](const std::string& key, int n, int cin, int ks) {
-        const std::vector<float>& w = c->t[key].data;
-        const size_t at = reserve((size_t)cin * ks * ks * n);
-        for (int o = 0; o < n; ++o)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < ks * ks; ++t) host[at + ((size_t)t * cin + ci) * n + o] = w[((size_t)o * cin + ci) * ks * ks + t];
+        const size_t at = pk.reserve((size_t)k * n);
+        pk.transpose_into(at, sd.data(name + ".weight"), n, k, n, 0);
         return at;
     };
 
@@ -617,10 +495,10 @@ int nesr_segformer_finalize(nesr_segformer* c) {
         S.kpe_real = cin * ks * ks;
         S.kpe = round_up(S.kpe_real, 32);
         if (i == 0) {      // the NCHW image: torch's own (c, ky, kx) order, zero rows up to a multiple of 32
-            S.wpe = reserve((size_t)S.kpe * C);
-            transpose_into(S.wpe, s + ".patch_embeddings.proj.weight", C, S.kpe_real, C, 0);
+            S.wpe = pk.reserve((size_t)S.kpe * C);
+            pk.transpose_into(S.wpe, sd.data(s + ".patch_embeddings.proj.weight"), C, S.kpe_real, C, 0);
         } else {
-            S.wpe = conv_nhwc(s + ".patch_embeddings.proj.weight", C, cin, ks);
+            S.wpe = pk.conv_taps(sd.data(s + ".patch_embeddings.proj.weight"), C, cin, ks * ks, cin, C);      // [(ky * ks + kx) * cin + c][C]
         }
         S.bpe = vec(s + ".patch_embeddings.proj.bias");
         S.peg = vec(s + ".patch_embeddings.layer_norm.weight");
@@ -633,19 +511,19 @@ int nesr_segformer_finalize(nesr_segformer* c) {
             B.ln1b = vec(b + ".layernorm_before.bias");
             auto concat = [&](std::initializer_list<const char*> names, size_t& w_at, size_t& b_at) {
                 const int n = (int)names.size() * C;
-                w_at = reserve((size_t)C * n);
-                b_at = reserve(n);
+                w_at = pk.reserve((size_t)C * n);
+                b_at = pk.reserve(n);
                 int col = 0;
                 for (const char* p : names) {
-                    transpose_into(w_at, at + p + ".weight", C, C, n, col);
-                    const std::vector<float>& bias = c->t[at + p + ".bias"].data;
-                    std::copy(bias.begin(), bias.end(), host.begin() + b_at + col);
+                    pk.transpose_into(w_at, sd.data(at + p + ".weight"), C, C, n, col);
+                    const std::vector<float>& bias = sd.data(at + p + ".bias");
+                    std::copy(bias.begin(), bias.end(), pk.host.begin() + b_at + col);
                     col += C;
                 }
             };
             if (sr > 1) {
                 concat({"q_proj"}, B.wq, B.bq);
-                B.wsr = conv_nhwc(at + "sequence_reduction.sequence_reduction.weight", C, C, sr);
+                B.wsr = pk.conv_taps(sd.data(at + "sequence_reduction.sequence_reduction.weight"), C, C, sr * sr, C, C);
                 B.bsr = vec(at + "sequence_reduction.sequence_reduction.bias");
                 B.srg = vec(at + "sequence_reduction.layer_norm.weight");
                 B.srb = vec(at + "sequence_reduction.layer_norm.bias");
@@ -659,12 +537,7 @@ int nesr_segformer_finalize(nesr_segformer* c) {
             B.ln2b = vec(b + ".layernorm_after.bias");
             B.w1 = linear(b + ".mlp.fc1", hidden, C);
             B.b1 = vec(b + ".mlp.fc1.bias");
-            B.dww = reserve((size_t)9 * hidden);      // [hidden][1][3][3] -> [tap][hidden]
-            {
-                const std::vector<float>& w = c->t[b + ".mlp.dwconv.dwconv.weight"].data;
-                for (int ch = 0; ch < hidden; ++ch)
-                    for (int t = 0; t < 9; ++t) host[B.dww + (size_t)t * hidden + ch] = w[(size_t)ch * 9 + t];
-            }
+            B.dww = pk.conv_taps(sd.data(b + ".mlp.dwconv.dwconv.weight"), hidden, 1, 9, 1, hidden);      // [hidden][1][3][3] -> [tap][hidden]
             B.dwb = vec(b + ".mlp.dwconv.dwconv.bias");
             B.w2 = linear(b + ".mlp.fc2", C, hidden);
             B.b2 = vec(b + ".mlp.fc2.bias");
@@ -678,34 +551,22 @@ int nesr_segformer_finalize(nesr_segformer* c) {
     }
     const int D = c->dec;
     c->wfuse = linear("decode_head.linear_fuse", D, D * c->nst);
-    c->bn_scale = reserve(D);
-    c->bn_shift = reserve(D);
+    c->bn_scale = pk.reserve(D);
+    c->bn_shift = pk.reserve(D);
     {      // BatchNorm in eval mode: y = (x - mean) / sqrt(var + eps) * g + b = x * scale + shift
         const std::string bn = "decode_head.batch_norm.";
-        const std::vector<float>&g = c->t[bn + "weight"].data, &b = c->t[bn + "bias"].data, &m = c->t[bn + "running_mean"].data,
-                          &v = c->t[bn + "running_var"].data;
+        const std::vector<float>&g = sd.data(bn + "weight"), &b = sd.data(bn + "bias"), &m = sd.data(bn + "running_mean"), &v = sd.data(bn + "running_var");
         for (int i = 0; i < D; ++i) {
             const double sc = (double)g[i] / std::sqrt((double)v[i] + 1e-5);
-            host[c->bn_scale + i] = (float)sc;
-            host[c->bn_shift + i] = (float)((double)b[i] - (double)m[i] * sc);
+            pk.host[c->bn_scale + i] = (float)sc;
+            pk.host[c->bn_shift + i] = (float)((double)b[i] - (double)m[i] * sc);
         }
     }
-    c->wcls = reserve((size_t)D * c->labels_p);
-    transpose_into(c->wcls, "decode_head.classifier.weight", c->labels, D, c->labels_p, 0);
-    c->bcls = reserve(c->labels_p);
-    {
-        const std::vector<float>& b = c->t["decode_head.classifier.bias"].data;
-        std::copy(b.begin(), b.end(), host.begin() + c->bcls);
-    }
-    NESR_TRY(hipSetDevice(c->device));
-    NESR_TRY(hipDeviceSynchronize());
-    if (c->d_w) NESR_TRY(hipFree(c->d_w));
-    c->d_w = nullptr;
-    if (hipMalloc((void**)&c->d_w, host.size() * 4) != hipSuccess) {
-        c->d_w = nullptr;
-        return set_error(NESR_ERR_NOMEM, "allocating the weights failed");
-    }
-    NESR_TRY(hipMemcpy(c->d_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    c->wcls = pk.reserve((size_t)D * c->labels_p);
+    pk.transpose_into(c->wcls, sd.data("decode_head.classifier.weight"), c->labels, D, c->labels_p, 0);
+    c->bcls = pk.vec(sd.data("decode_head.classifier.bias"), c->labels_p);
+    const int rc = upload_weights(c->device, c->d_w, pk.host, nullptr);
+    if (rc) return rc;
     c->finalized = true;
     return NESR_OK;
 }
@@ -756,7 +617,7 @@ int nesr_segformer_segment_u8(nesr_segformer* c, const uint8_t* rgb, int H, int 
     // the network's input lives at the head of the network's workspace region of its own: grown here, kept by forward
     static_assert(kModelSize % 32 == 0, "the model size is a legal forward size");
     const SegWs L = ws_layout(c, sh, sw);
-    if ((rc = grow(c->ws, c->ws_bytes, L.total + pix_bytes))) return rc;
+    if ((rc = grow(c->ws, c->ws_bytes, L.total + pix_bytes, kName))) return rc;
     float* pix = reinterpret_cast<float*>(c->ws + L.total);
     if ((rc = preprocess(c, rgb, H, W, pix, s))) return rc;
     if ((rc = forward(c, pix, kModelSize, kModelSize, nullptr, class_map, s))) return rc;
@@ -767,27 +628,17 @@ int nesr_segformer_segment_u8(nesr_segformer* c, const uint8_t* rgb, int H, int 
 
 int nesr_segformer_set_timing(nesr_segformer* c, int enable) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_set_timing: null context");
-    c->timing = enable != 0;
+    c->timer.on = enable != 0;
     return NESR_OK;
 }
 
 int nesr_segformer_kernel_time_ms(nesr_segformer* c, double* group_ms, int n_groups, int64_t* launches) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_kernel_time_ms: null context");
     NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_SEG_GROUPS] = {0};
-    for (const SegTimed& tm : c->pending) {
-        NESR_TRY(hipEventSynchronize(tm.b));
-        float t = 0.f;
-        NESR_TRY(hipEventElapsedTime(&t, tm.a, tm.b));
-        ms[tm.group] += t;
-        c->spare.push_back(tm.a);
-        c->spare.push_back(tm.b);
-    }
-    c->pending.clear();
-    for (int i = 0; group_ms && i < n_groups && i < NESR_SEG_GROUPS; ++i) group_ms[i] = ms[i];
-    if (launches) *launches = c->launches;
-    c->launches = 0;
-    return NESR_OK;
+    double ms[NESR_SEG_GROUPS];
+    const int rc = c->timer.collect(ms, NESR_SEG_GROUPS, launches);
+    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_SEG_GROUPS; ++i) group_ms[i] = ms[i];
+    return rc;
 }
 
 int nesr_pil_resize_u8(int device_id, const uint8_t* src, int H, int W, int C, uint8_t* dst, int out_h, int out_w, int filter, void* stream) {

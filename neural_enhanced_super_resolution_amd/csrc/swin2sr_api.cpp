@@ -4,25 +4,14 @@
 // for nesr_swin2sr_upscale_u8, its Swin2SRImageProcessor and the documented post-processing.
 #include <cmath>
 #include <cstring>
-#include <map>
 
 #include "api_common.h"
+#include "state_dict.h"
 #include "swin2sr_api.h"
 
 using namespace nesr;
 
 namespace {
-
-struct S2Tensor {
-    std::vector<int64_t> shape;
-    std::vector<float> data;
-    bool have = false;
-    size_t numel() const {
-        size_t n = 1;
-        for (int64_t d : shape) n *= (size_t)d;
-        return n;
-    }
-};
 
 struct S2ConvW {
     size_t w = 0, b = 0;
@@ -36,16 +25,13 @@ struct S2StageW {
     S2ConvW conv;
     size_t wproj, bproj;
 };
-struct S2Timed {
-    int group;
-    hipEvent_t a, b;
-};
 
 enum { UP_PIXELSHUFFLE = 0, UP_DIRECT = 1, UP_NEAREST = 2 };
 constexpr int kFeatures = 64;      // num_features of the pixelshuffle and nearest+conv heads
 constexpr int kMaxStages = 16;
 constexpr int kProcessorPad = 8;   // Swin2SRImageProcessor.size_divisor
 const float kMean[3] = {0.4488f, 0.4371f, 0.4040f};
+const char* const kName = "Swin2SR";      // in the texts of a failed launch, workspace or weight allocation
 
 }  // namespace
 
@@ -53,8 +39,7 @@ struct nesr_swin2sr {
     int device = 0, nin = 3, nout = 3, C = 180, cs = 192, nst = 0, ws = 8, hidden = 360, hidp = 368, heads = 6, d = 30, dp = 32, scale = 2, up = 0;
     int depth[kMaxStages];
     float eps = 1e-5f, range = 1.f, mean[4] = {0.f, 0.f, 0.f, 0.f};
-    std::map<std::string, S2Tensor> t;
-    std::vector<std::string> order;
+    StateDict sd;
     bool finalized = false;
     float* d_w = nullptr;
     S2ConvW first, after, before, up1, up2, hr, fin, direct;
@@ -63,81 +48,15 @@ struct nesr_swin2sr {
     std::vector<S2StageW> stages;
     char* ws_buf = nullptr;
     size_t ws_bytes = 0;
-    bool timing = false;
-    int64_t launches = 0;
-    std::vector<S2Timed> pending;
-    std::vector<hipEvent_t> spare;
+    GroupTimer timer;
 };
 
 namespace {
-
-void expect(nesr_swin2sr* c, const std::string& key, std::vector<int64_t> shape) {
-    S2Tensor t;
-    t.shape = std::move(shape);
-    c->t[key] = t;
-    c->order.push_back(key);
-}
-void expect_wb(nesr_swin2sr* c, const std::string& name, std::vector<int64_t> wshape, bool bias = true) {
-    const int64_t n = wshape[0];
-    expect(c, name + ".weight", std::move(wshape));
-    if (bias) expect(c, name + ".bias", {n});
-}
 
 bool ends_with(const std::string& s, const char* tail) {
     const size_t n = strlen(tail);
     return s.size() >= n && s.compare(s.size() - n, n, tail) == 0;
 }
-
-int grow(char*& buf, size_t& have, size_t bytes) {
-    if (bytes <= have) return NESR_OK;
-    NESR_TRY(hipDeviceSynchronize());
-    if (buf) NESR_TRY(hipFree(buf));
-    buf = nullptr;
-    have = 0;
-    if (hipMalloc((void**)&buf, bytes) != hipSuccess) {
-        buf = nullptr;
-        (void)hipGetLastError();
-        return set_error(NESR_ERR_NOMEM, "Swin2SR: workspace allocation of " + std::to_string(bytes) + " bytes failed (the workspace grows with the frame)");
-    }
-    have = bytes;
-    return NESR_OK;
-}
-
-hipError_t new_event(nesr_swin2sr* c, hipEvent_t* e) {
-    if (!c->spare.empty()) {
-        *e = c->spare.back();
-        c->spare.pop_back();
-        return hipSuccess;
-    }
-    return hipEventCreate(e);
-}
-
-// one launch: counted, and bracketed by an event pair of its group while timing is on
-template <class F>
-int run(nesr_swin2sr* c, int group, hipStream_t s, F&& launch) {
-    S2Timed tm{group, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    if (c->timing) {
-        e = new_event(c, &tm.a);
-        if (e == hipSuccess) e = new_event(c, &tm.b);
-        if (e == hipSuccess) e = hipEventRecord(tm.a, s);
-    }
-    if (e == hipSuccess) e = launch();
-    if (e == hipSuccess) ++c->launches;
-    if (e == hipSuccess && c->timing) e = hipEventRecord(tm.b, s);
-    if (e != hipSuccess) {
-        if (tm.a) c->spare.push_back(tm.a);
-        if (tm.b) c->spare.push_back(tm.b);
-        return set_error(NESR_ERR_HIP, std::string("Swin2SR launch (group ") + std::to_string(group) + "): " + hipGetErrorString(e));
-    }
-    if (c->timing) c->pending.push_back(tm);
-    return NESR_OK;
-}
-#define S2_RUN(...)                  \
-    do {                             \
-        int rc__ = run(__VA_ARGS__); \
-        if (rc__) return rc__;       \
-    } while (0)
 
 int unsupported(const std::string& field, const std::string& why) {
     return set_error(NESR_ERR_UNSUPPORTED, "nesr_swin2sr_create: " + field + ": " + why);
@@ -171,7 +90,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         return set_error(NESR_ERR_ARG, "Swin2SR: the reflect padding to the window (" + std::to_string(c->ws) + ") is wider than the image allows");
     const size_t T = (size_t)H * W, cs = c->cs, sc = c->scale;
     const size_t act = align_up(T * cs * 4, 256), upb = c->up == UP_DIRECT ? 0 : align_up(T * sc * sc * kFeatures * 4, 256);
-    int rc = grow(c->ws_buf, c->ws_bytes, 4 * act + 2 * upb);
+    int rc = grow(c->ws_buf, c->ws_bytes, 4 * act + 2 * upb, kName);
     if (rc) return rc;
     float* FIRST = reinterpret_cast<float*>(c->ws_buf);
     float* XS = reinterpret_cast<float*>(c->ws_buf + act);
@@ -185,7 +104,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     {   // first_convolution on the padded, normalised frame -> FIRST (the long residual)
         S2Conv a = conv_args(c, c->first, nullptr, H, W, 0, FIRST, CS);
         a.in_mode = frame_u8 ? S2_IN_FRAME_U8 : S2_IN_FRAME_F32, a.in = frame, a.fh = fh, a.fw = fw, a.mh = mh, a.mw = mw;
-        S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
     auto rows = [&](const float* in, size_t w1, size_t b1, bool ln, size_t g, size_t b, float eps, const float* res, float* o) {
         S2Rows a;
@@ -198,7 +117,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     };
     {   // patch embedding: 1x1 projection + LayerNorm (torch's default eps) -> XS
         const S2Rows a = rows(FIRST, c->wpe, c->bpe, true, c->peg, c->peb, 1e-5f, nullptr, XS);
-        S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
     }
     for (int i = 0; i < c->nst; ++i) {
         const S2StageW& S = c->stages[i];
@@ -210,31 +129,31 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
                 a.in = j == 0 ? XS : X, a.out = X;      // the stage's input stays in XS
                 a.wqkv = wt(L.wqkv), a.bqkv = wt(L.bqkv), a.scale = wt(L.scale), a.bias = wt(L.bias), a.wo = wt(L.wo), a.bo = wt(L.bo);
                 a.ln_g = wt(L.ln1g), a.ln_b = wt(L.ln1b), a.eps = c->eps;
-                S2_RUN(c, NESR_S2_GROUP_ATTENTION, s, [&] { return launch_s2_attn(a, s); });
+                NESR_RUN(c->timer, kName, NESR_S2_GROUP_ATTENTION, s, [&] { return launch_s2_attn(a, s); });
             }
             {
                 S2Rows a = rows(X, L.w1, L.b1, true, L.ln2g, L.ln2b, c->eps, X, X);
                 a.n1p = c->hidp, a.gelu = 1, a.w2 = wt(L.w2), a.b2 = wt(L.b2);
-                S2_RUN(c, NESR_S2_GROUP_MLP, s, [&] { return launch_s2_rows(a, s); });
+                NESR_RUN(c->timer, kName, NESR_S2_GROUP_MLP, s, [&] { return launch_s2_rows(a, s); });
             }
         }
         {
             const S2Conv a = conv_args(c, S.conv, X, H, W, CS, T1, CS);
-            S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+            NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
         }
         {   // the stage's 1x1 projection + the stage's input, in place
             const S2Rows a = rows(T1, S.wproj, S.bproj, false, 0, 0, 0.f, XS, XS);
-            S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+            NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
         }
     }
     {   // the encoder's LayerNorm -> X
         const S2Rows a = rows(XS, (size_t)-1, 0, true, c->lng, c->lnb, c->eps, nullptr, X);
-        S2_RUN(c, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
     }
     {   // conv_after_body + the long residual -> T1
         S2Conv a = conv_args(c, c->after, X, H, W, CS, T1, CS);
         a.res = FIRST, a.cs_res = CS;
-        S2_RUN(c, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
     auto finish = [&](S2Conv& a) {      // / img_range + mean, the crop, f32 or u8
         a.out_mode = out_u8 ? S2_OUT_U8 : S2_OUT_F32, a.out = out, a.cs_out = 0, a.oh = fh * c->scale, a.ow = fw * c->scale;
@@ -244,13 +163,13 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         S2Conv a = conv_args(c, c->direct, T1, H, W, CS, nullptr, 0);
         a.shuffle = c->scale;
         finish(a);
-        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
         return NESR_OK;
     }
     {
         S2Conv a = conv_args(c, c->before, T1, H, W, CS, UA, F);
         a.lrelu = 1, a.slope = 0.01f;
-        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
     }
     float* cur = UA;
     float* other = UB;
@@ -260,7 +179,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         for (const S2ConvW& u : c->ups) {
             S2Conv a = conv_args(c, u, cur, h, w, F, other, F);
             a.shuffle = r;
-            S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+            NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
             std::swap(cur, other);
             h *= r, w *= r;
         }
@@ -269,17 +188,17 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
             h *= 2, w *= 2;
             S2Conv a = conv_args(c, *u, cur, h, w, F, other, F);
             a.in_mode = S2_IN_NEAREST2, a.lrelu = 1, a.slope = 0.2f;
-            S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+            NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
             std::swap(cur, other);
         }
         S2Conv a = conv_args(c, c->hr, cur, h, w, F, other, F);
         a.lrelu = 1, a.slope = 0.2f;
-        S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
         std::swap(cur, other);
     }
     S2Conv a = conv_args(c, c->fin, cur, h, w, F, nullptr, 0);
     finish(a);
-    S2_RUN(c, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
+    NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
     return NESR_OK;
 }
 
@@ -348,45 +267,46 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
         if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
         return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
     }
+    StateDict& sd = c->sd;
     const int64_t C = c->C, hid = c->hidden, nf = kFeatures;
-    expect_wb(c, "swin2sr.first_convolution", {C, c->nin, 3, 3});
-    expect_wb(c, "swin2sr.embeddings.patch_embeddings.projection", {C, C, 1, 1});
-    expect_wb(c, "swin2sr.embeddings.patch_embeddings.layernorm", {C});
+    sd.expect_wb("swin2sr.first_convolution", {C, c->nin, 3, 3});
+    sd.expect_wb("swin2sr.embeddings.patch_embeddings.projection", {C, C, 1, 1});
+    sd.expect_wb("swin2sr.embeddings.patch_embeddings.layernorm", {C});
     for (int i = 0; i < c->nst; ++i) {
         const std::string s = "swin2sr.encoder.stages." + std::to_string(i);
         for (int j = 0; j < c->depth[i]; ++j) {
             const std::string l = s + ".layers." + std::to_string(j), a = l + ".attention.self";
-            expect(c, a + ".logit_scale", {c->heads, 1, 1});
-            expect_wb(c, a + ".continuous_position_bias_mlp.0", {512, 2});
-            expect_wb(c, a + ".continuous_position_bias_mlp.2", {c->heads, 512}, false);
-            expect_wb(c, a + ".query", {C, C});
-            expect_wb(c, a + ".key", {C, C}, false);
-            expect_wb(c, a + ".value", {C, C});
-            expect_wb(c, l + ".attention.output.dense", {C, C});
-            expect_wb(c, l + ".layernorm_before", {C});
-            expect_wb(c, l + ".intermediate.dense", {hid, C});
-            expect_wb(c, l + ".output.dense", {C, hid});
-            expect_wb(c, l + ".layernorm_after", {C});
+            sd.expect(a + ".logit_scale", {c->heads, 1, 1});
+            sd.expect_wb(a + ".continuous_position_bias_mlp.0", {512, 2});
+            sd.expect_wb(a + ".continuous_position_bias_mlp.2", {c->heads, 512}, false);
+            sd.expect_wb(a + ".query", {C, C});
+            sd.expect_wb(a + ".key", {C, C}, false);
+            sd.expect_wb(a + ".value", {C, C});
+            sd.expect_wb(l + ".attention.output.dense", {C, C});
+            sd.expect_wb(l + ".layernorm_before", {C});
+            sd.expect_wb(l + ".intermediate.dense", {hid, C});
+            sd.expect_wb(l + ".output.dense", {C, hid});
+            sd.expect_wb(l + ".layernorm_after", {C});
         }
-        expect_wb(c, s + ".conv", {C, C, 3, 3});
-        expect_wb(c, s + ".patch_embed.projection", {C, C, 1, 1});
+        sd.expect_wb(s + ".conv", {C, C, 3, 3});
+        sd.expect_wb(s + ".patch_embed.projection", {C, C, 1, 1});
     }
-    expect_wb(c, "swin2sr.layernorm", {C});
-    expect_wb(c, "swin2sr.conv_after_body", {C, C, 3, 3});
+    sd.expect_wb("swin2sr.layernorm", {C});
+    sd.expect_wb("swin2sr.conv_after_body", {C, C, 3, 3});
     if (c->up == UP_DIRECT) {
-        expect_wb(c, "upsample.conv", {(int64_t)upscale * upscale * c->nout, C, 3, 3});
+        sd.expect_wb("upsample.conv", {(int64_t)upscale * upscale * c->nout, C, 3, 3});
     } else {
-        expect_wb(c, "upsample.conv_before_upsample", {nf, C, 3, 3});
+        sd.expect_wb("upsample.conv_before_upsample", {nf, C, 3, 3});
         if (c->up == UP_PIXELSHUFFLE) {
             if (upscale == 3) {
-                expect_wb(c, "upsample.upsample.convolution", {9 * nf, nf, 3, 3});
+                sd.expect_wb("upsample.upsample.convolution", {9 * nf, nf, 3, 3});
             } else {
-                for (int i = 0; (1 << i) < upscale; ++i) expect_wb(c, "upsample.upsample.convolution_" + std::to_string(i), {4 * nf, nf, 3, 3});
+                for (int i = 0; (1 << i) < upscale; ++i) sd.expect_wb("upsample.upsample.convolution_" + std::to_string(i), {4 * nf, nf, 3, 3});
             }
         } else {
-            for (const char* n : {"conv_up1", "conv_up2", "conv_hr"}) expect_wb(c, std::string("upsample.") + n, {nf, nf, 3, 3});
+            for (const char* n : {"conv_up1", "conv_up2", "conv_hr"}) sd.expect_wb(std::string("upsample.") + n, {nf, nf, 3, 3});
         }
-        expect_wb(c, "upsample.final_convolution", {c->nout, nf, 3, 3});
+        sd.expect_wb("upsample.final_convolution", {c->nout, nf, 3, 3});
     }
     *out = c;
     return NESR_OK;
@@ -396,79 +316,44 @@ void nesr_swin2sr_destroy(nesr_swin2sr* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    for (const S2Timed& tm : c->pending) {
-        (void)hipEventDestroy(tm.a);
-        (void)hipEventDestroy(tm.b);
-    }
-    for (hipEvent_t e : c->spare) (void)hipEventDestroy(e);
+    c->timer.destroy();
     if (c->ws_buf) (void)hipFree(c->ws_buf);
     if (c->d_w) (void)hipFree(c->d_w);
     delete c;
 }
 
-int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return c ? (int)c->order.size() : 0; }
+int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return c ? (int)c->sd.size() : 0; }
 
 int nesr_swin2sr_load_weight(nesr_swin2sr* c, const char* key, const float* data, const int64_t* shape, int ndim) {
     if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_load_weight: null argument");
     const std::string k = key;
     // buffers older checkpoints carry: recomputed here from the configuration
     if (ends_with(k, "relative_position_index") || ends_with(k, "relative_coords_table") || ends_with(k, "attn_mask")) return NESR_OK;
-    auto it = c->t.find(k);
-    if (it == c->t.end()) return set_error(NESR_ERR_ARG, std::string("unexpected key in state_dict: ") + key);
-    S2Tensor& t = it->second;
-    bool same = ndim == (int)t.shape.size();
-    for (int i = 0; same && i < ndim; ++i) same = shape[i] == t.shape[i];
-    if (!same) {
-        std::string want;
-        for (int64_t d : t.shape) want += (want.empty() ? "" : ",") + std::to_string(d);
-        return set_error(NESR_ERR_ARG, "size mismatch for " + k + ": expected [" + want + "]");
-    }
-    t.data.assign(data, data + t.numel());
-    t.have = true;
-    c->finalized = false;
-    return NESR_OK;
+    const int rc = c->sd.load(k, data, shape, ndim);
+    if (!rc) c->finalized = false;
+    return rc;
 }
 
 int nesr_swin2sr_finalize(nesr_swin2sr* c) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_finalize: null context");
-    std::string missing;
-    int nmiss = 0;
-    for (const std::string& k : c->order)
-        if (!c->t[k].have && nmiss++ < 4) missing += (missing.empty() ? "" : ", ") + k;
-    if (nmiss) return set_error(NESR_ERR_STATE, "missing keys in state_dict (" + std::to_string(nmiss) + "): " + missing);
+    const StateDict& sd = c->sd;
+    const std::string missing = sd.missing();
+    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
 
-    std::vector<float> host;
-    auto reserve = [&](size_t floats) {
-        const size_t at = host.size();
-        host.resize(align_up(at + floats, 64), 0.f);
-        return at;
-    };
-    auto data = [&](const std::string& key) -> const std::vector<float>& { return c->t[key].data; };
-    // a vector, zero padded to `padded`
-    auto vec = [&](const std::string& key, int padded) {
-        const std::vector<float>& v = data(key);
-        const size_t at = reserve(std::max<size_t>(padded, v.size()));
-        std::copy(v.begin(), v.end(), host.begin() + at);
-        return at;
-    };
+    HostPack pk;
+    auto vec = [&](const std::string& key, int padded) { return pk.vec(sd.data(key), padded); };
     // torch's Linear / 1x1 conv weight [n][k] -> Wt[round16(k)][round16(n)]
     auto linear = [&](const std::string& key, int n, int k) {
-        const std::vector<float>& w = data(key);
-        const int np = round_up(n, 16), kp = round_up(k, 16);
-        const size_t at = reserve((size_t)kp * np);
-        for (int o = 0; o < n; ++o)
-            for (int kk = 0; kk < k; ++kk) host[at + (size_t)kk * np + o] = w[(size_t)o * k + kk];
+        const int np = round_up(n, 16);
+        const size_t at = pk.reserve((size_t)round_up(k, 16) * np);
+        pk.transpose_into(at, sd.data(key), n, k, np, 0);
         return at;
     };
     // conv weight [n][cin][3][3] -> Wt[(tap * cinp + ci)][coutp]
     auto conv = [&](const std::string& name, int n, int cin) {
-        const std::vector<float>& w = data(name + ".weight");
         S2ConvW r;
         r.cin = cin, r.cinp = round_up(cin, 4), r.cout = n, r.coutp = round_up(n, 16);
-        r.w = reserve((size_t)9 * r.cinp * r.coutp);
-        for (int o = 0; o < n; ++o)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < 9; ++t) host[r.w + ((size_t)t * r.cinp + ci) * r.coutp + o] = w[((size_t)o * cin + ci) * 9 + t];
+        r.w = pk.conv_taps(sd.data(name + ".weight"), n, cin, 9, r.cinp, r.coutp);
         r.b = vec(name + ".bias", r.coutp);
         return r;
     };
@@ -502,27 +387,27 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
             S2LayerW& L = S.layers[j];
             const std::string l = s + ".layers." + std::to_string(j), a = l + ".attention.self";
             const int nq = heads * 3 * dp;
-            L.wqkv = reserve((size_t)CS * nq);
-            L.bqkv = reserve(nq);
+            L.wqkv = pk.reserve((size_t)CS * nq);
+            L.bqkv = pk.reserve(nq);
             const char* parts[3] = {".query", ".key", ".value"};
             for (int p = 0; p < 3; ++p) {
-                const std::vector<float>& w = data(a + parts[p] + ".weight");
-                const std::vector<float>* b = p == 1 ? nullptr : &data(a + parts[p] + ".bias");
+                const std::vector<float>& w = sd.data(a + parts[p] + ".weight");
+                const std::vector<float>* b = p == 1 ? nullptr : &sd.data(a + parts[p] + ".bias");
                 for (int h = 0; h < heads; ++h)
                     for (int jd = 0; jd < d; ++jd) {
                         const int row = h * d + jd, col = (h * 3 + p) * dp + jd;
-                        for (int k = 0; k < C; ++k) host[L.wqkv + (size_t)k * nq + col] = w[(size_t)row * C + k];
-                        if (b) host[L.bqkv + col] = (*b)[row];
+                        for (int k = 0; k < C; ++k) pk.host[L.wqkv + (size_t)k * nq + col] = w[(size_t)row * C + k];
+                        if (b) pk.host[L.bqkv + col] = (*b)[row];
                     }
             }
-            L.scale = reserve(heads);
+            L.scale = pk.reserve(heads);
             {
-                const std::vector<float>& ls = data(a + ".logit_scale");
-                for (int h = 0; h < heads; ++h) host[L.scale + h] = (float)std::exp(std::min((double)ls[h], std::log(1.0 / 0.01)));
+                const std::vector<float>& ls = sd.data(a + ".logit_scale");
+                for (int h = 0; h < heads; ++h) pk.host[L.scale + h] = (float)std::exp(std::min((double)ls[h], std::log(1.0 / 0.01)));
             }
             {   // 16 sigmoid(MLP(table))[index], double on the host, rounded once
-                const std::vector<float>&w0 = data(a + ".continuous_position_bias_mlp.0.weight"), &b0 = data(a + ".continuous_position_bias_mlp.0.bias"),
-                                  &w2 = data(a + ".continuous_position_bias_mlp.2.weight");
+                const std::vector<float>&w0 = sd.data(a + ".continuous_position_bias_mlp.0.weight"), &b0 = sd.data(a + ".continuous_position_bias_mlp.0.bias"),
+                                  &w2 = sd.data(a + ".continuous_position_bias_mlp.2.weight");
                 std::vector<double> tb((size_t)tw * tw * heads, 0.0);
                 for (int e = 0; e < tw * tw; ++e)
                     for (int u = 0; u < 512; ++u) {
@@ -530,12 +415,12 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
                         if (hv > 0)
                             for (int h = 0; h < heads; ++h) tb[(size_t)e * heads + h] += hv * (double)w2[(size_t)h * 512 + u];
                     }
-                L.bias = reserve((size_t)heads * n * n);
+                L.bias = pk.reserve((size_t)heads * n * n);
                 for (int h = 0; h < heads; ++h)
                     for (int p = 0; p < n; ++p)
                         for (int q = 0; q < n; ++q) {
                             const int idx = (p / ws - q / ws + ws - 1) * tw + (p % ws - q % ws + ws - 1);
-                            host[L.bias + ((size_t)h * n + p) * n + q] = (float)(16.0 / (1.0 + std::exp(-tb[(size_t)idx * heads + h])));
+                            pk.host[L.bias + ((size_t)h * n + p) * n + q] = (float)(16.0 / (1.0 + std::exp(-tb[(size_t)idx * heads + h])));
                         }
             }
             L.wo = linear(l + ".attention.output.dense.weight", C, C);
@@ -574,15 +459,8 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
         }
         c->fin = conv("upsample.final_convolution", c->nout, kFeatures);
     }
-    NESR_TRY(hipSetDevice(c->device));
-    NESR_TRY(hipDeviceSynchronize());
-    if (c->d_w) NESR_TRY(hipFree(c->d_w));
-    c->d_w = nullptr;
-    if (hipMalloc((void**)&c->d_w, host.size() * 4) != hipSuccess) {
-        c->d_w = nullptr;
-        return set_error(NESR_ERR_NOMEM, "Swin2SR: allocating the weights failed");
-    }
-    NESR_TRY(hipMemcpy(c->d_w, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+    const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
+    if (rc) return rc;
     c->finalized = true;
     return NESR_OK;
 }
@@ -622,27 +500,17 @@ int nesr_swin2sr_upscale_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, int W, u
 
 int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_set_timing: null context");
-    c->timing = enable != 0;
+    c->timer.on = enable != 0;
     return NESR_OK;
 }
 
 int nesr_swin2sr_kernel_time_ms(nesr_swin2sr* c, double* group_ms, int n_groups, int64_t* launches) {
     if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_kernel_time_ms: null context");
     NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_S2_GROUPS] = {0};
-    for (const S2Timed& tm : c->pending) {
-        NESR_TRY(hipEventSynchronize(tm.b));
-        float t = 0.f;
-        NESR_TRY(hipEventElapsedTime(&t, tm.a, tm.b));
-        ms[tm.group] += t;
-        c->spare.push_back(tm.a);
-        c->spare.push_back(tm.b);
-    }
-    c->pending.clear();
-    for (int i = 0; group_ms && i < n_groups && i < NESR_S2_GROUPS; ++i) group_ms[i] = ms[i];
-    if (launches) *launches = c->launches;
-    c->launches = 0;
-    return NESR_OK;
+    double ms[NESR_S2_GROUPS];
+    const int rc = c->timer.collect(ms, NESR_S2_GROUPS, launches);
+    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_S2_GROUPS; ++i) group_ms[i] = ms[i];
+    return rc;
 }
 
 }  // extern "C"

@@ -18,14 +18,14 @@ from __future__ import annotations
 
 import ctypes
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import _lib
+from ._contexts import _invoke
+from ._hfnet import _HFNet
 
 DEFAULTS = dict(image_size=64, patch_size=1, num_channels=3, num_channels_out=None, embed_dim=180, depths=(6, 6, 6, 6, 6, 6),
                 num_heads=(6, 6, 6, 6, 6, 6), window_size=8, mlp_ratio=2.0, qkv_bias=True, use_absolute_embeddings=False,
@@ -101,88 +101,24 @@ def swin2sr_state_dict_spec(**cfg):
     return spec
 
 
-class _Holder(nn.Module):
-    """One level of the parameter tree.  Not callable."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("Swin2SR's sub-modules hold weights only; Swin2SR.forward runs in libnesr_hip.so")
-
-
-class Swin2SR(nn.Module):
+class Swin2SR(_HFNet):
     """Swin2SRForImageSuperResolution in eval mode on the HIP path.  Keyword arguments are Swin2SRConfig's fields."""
 
-    def __init__(self, **cfg):
-        super().__init__()
-        self.config = _config(cfg)
-        for key, shape in swin2sr_state_dict_spec(**self.config).items():
-            *path, leaf = key.split(".")
-            mod = self
-            for name in path:
-                if name not in mod._modules:
-                    mod.add_module(name, _Holder())
-                mod = mod._modules[name]
-            if leaf == "logit_scale":
-                init = torch.full(shape, math.log(10.0))
-            else:
-                init = torch.ones(shape) if (leaf == "weight" and len(shape) == 1) else torch.zeros(shape)
-            mod.register_parameter(leaf, nn.Parameter(init, requires_grad=False))
-        self.calls = 0            # forwards so far (a caller can assert that the network really ran)
-        self._handles = {}        # device index -> context with the current weights
-        self._timing = False
-        self.eval()
+    PREFIX, NAME, KERNEL_GROUPS = "nesr_swin2sr", "Swin2SR", KERNEL_GROUPS
+    TRAIN_ERROR = "Swin2SR is inference only (eval mode: no dropout, no stochastic depth)"
+    _spec = staticmethod(swin2sr_state_dict_spec)
 
-    # ------------------------------------------------------------------ weights
+    def __init__(self, **cfg):
+        super().__init__(_config(cfg))
+
+    def _register_leaf(self, mod, leaf, shape, init=None):
+        super()._register_leaf(mod, leaf, shape, torch.full(shape, math.log(10.0)) if leaf == "logit_scale" else init)
+
     def load_state_dict(self, state_dict, strict=True, **kw):
         """Strict: a missing or an unexpected key raises.  The buffers older checkpoints carry (relative_position_index,
         relative_coords_table, attn_mask) are dropped: they follow from the configuration."""
         sd = OrderedDict((k, v) for k, v in state_dict.items() if not k.endswith(_IGNORED))
-        out = super().load_state_dict(sd, strict=strict, **kw)
-        self._release()
-        return out
-
-    @classmethod
-    def from_checkpoint(cls, path, **cfg):
-        """A model with the weights of a local ``model.safetensors`` or ``pytorch_model.bin`` (or of the directory that holds
-        one).  Anything that is not an existing local path raises: nothing is ever fetched."""
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            for name in ("model.safetensors", "pytorch_model.bin"):
-                if os.path.isfile(os.path.join(path, name)):
-                    path = os.path.join(path, name)
-                    break
-        if not os.path.isfile(path):
-            raise FileNotFoundError(f"Swin2SR.from_checkpoint: {path!r} is not a local checkpoint file (a hub id is not fetched: "
-                                    "pass the path of a downloaded model.safetensors or pytorch_model.bin)")
-        if path.endswith(".safetensors"):
-            from safetensors.torch import load_file
-            sd = load_file(path, device="cpu")
-        else:
-            sd = torch.load(path, map_location="cpu", weights_only=True)
-        model = cls(**cfg)
-        model.load_state_dict(sd)
-        return model
-
-    def _apply(self, fn, *a, **k):
-        out = super()._apply(fn, *a, **k)
-        self._release()
-        return out
-
-    def train(self, mode=True):
-        if mode:
-            raise RuntimeError("Swin2SR is inference only (eval mode: no dropout, no stochastic depth)")
-        return super().train(False)
-
-    # ------------------------------------------------------------------ contexts
-    def _release(self):
-        handles, self._handles = getattr(self, "_handles", {}), {}
-        for h in handles.values():
-            _lib.load().nesr_swin2sr_destroy(h)
-
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+        return super().load_state_dict(sd, strict=strict, **kw)
 
     def _create(self, index):
         """A context of this configuration without weights (NesrUnsupportedError names the field the kernels do not take)."""
@@ -201,31 +137,6 @@ class Swin2SR(nn.Module):
         _lib.check(rc, "nesr_swin2sr_create")
         return handle
 
-    def _context(self, device):
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        if index in self._handles:
-            return self._handles[index]
-        lib = _lib.load()
-        handle = self._create(index)
-        try:
-            for key, t in self.state_dict().items():
-                t = t.detach().to("cpu", torch.float32).contiguous()
-                shape = (ctypes.c_int64 * max(t.dim(), 1))(*t.shape)
-                _lib.check(lib.nesr_swin2sr_load_weight(handle, key.encode(), ctypes.c_void_p(t.data_ptr()), shape, t.dim()), "nesr_swin2sr_load_weight")
-            _lib.check(lib.nesr_swin2sr_finalize(handle), "nesr_swin2sr_finalize")
-            _lib.check(lib.nesr_swin2sr_set_timing(handle, 1 if self._timing else 0), "nesr_swin2sr_set_timing")
-        except Exception:
-            lib.nesr_swin2sr_destroy(handle)
-            raise
-        self._handles[index] = handle
-        return handle
-
-    @staticmethod
-    def _require_device(t, what):
-        if not t.is_cuda:
-            raise RuntimeError(f"Swin2SR.{what}: the tensor is on {t.device}; the forward runs on the ROCm device only "
-                               "(there is no CPU or PyTorch fallback)")
-
     # ------------------------------------------------------------------ forward
     def output_size(self, h, w):
         """(oh, ow) of the result for an h x w input or frame: h s x w s, as the library computes it.  Needs no device."""
@@ -238,18 +149,12 @@ class Swin2SR(nn.Module):
         """pixel_values [1, C, H, W] float32 on the device (H, W multiples of window_size) -> reconstruction [1, C_out, H s, W s]."""
         if pixel_values.dtype == torch.uint8 and pixel_values.dim() == 3:
             return self.upscale(pixel_values)
-        x = pixel_values
-        self._require_device(x, "forward")
-        if x.dim() != 4 or x.dtype != torch.float32:
-            raise ValueError(f"Swin2SR.forward: a [1, {self.config['num_channels']}, H, W] float32 tensor, got {x.dtype} {tuple(x.shape)}")
-        x = x.contiguous()
+        x = self._pixel_values(pixel_values)
         n, ch, h, w = x.shape
         with torch.cuda.device(x.device):
             handle = self._context(x.device)
             out = torch.empty((1, self.config["num_channels_out"]) + self.output_size(h, w), dtype=torch.float32, device=x.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-            _lib.check(_lib.load().nesr_swin2sr_forward_f32(handle, ctypes.c_void_p(x.data_ptr()), n, ch, h, w, ctypes.c_void_p(out.data_ptr()),
-                                                            out.numel(), stream), "nesr_swin2sr_forward_f32")
+            _invoke("nesr_swin2sr_forward_f32", x.device, handle, (x, n, ch, h, w, out, out.numel()))
         self.calls += 1
         return out
 
@@ -258,39 +163,11 @@ class Swin2SR(nn.Module):
         ndarray, which is copied up once (to `device`, default the current ROCm device)."""
         if isinstance(frame, np.ndarray):
             frame = torch.from_numpy(np.ascontiguousarray(frame)).to(torch.device("cuda") if device is None else torch.device(device))
-        self._require_device(frame, "upscale")
-        if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8 or frame.numel() == 0:
-            raise ValueError(f"Swin2SR.upscale: an [H, W, 3] uint8 frame, got {frame.dtype} {tuple(frame.shape)}")
-        frame = frame.contiguous()
+        frame = self._frame_u8(frame, "upscale", "frame")
         h, w = frame.shape[:2]
         with torch.cuda.device(frame.device):
             handle = self._context(frame.device)
             out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=frame.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(frame.device).cuda_stream)
-            _lib.check(_lib.load().nesr_swin2sr_upscale_u8(handle, ctypes.c_void_p(frame.data_ptr()), h, w, ctypes.c_void_p(out.data_ptr()),
-                                                           out.numel(), stream), "nesr_swin2sr_upscale_u8")
+            _invoke("nesr_swin2sr_upscale_u8", frame.device, handle, (frame, h, w, out, out.numel()))
         self.calls += 1
         return out
-
-    # ------------------------------------------------------------------ timing
-    def set_kernel_timing(self, enable=True):
-        """Switches the per-group event timing of every context (kernel_time_ms reads it; the launch counter always runs)."""
-        self._timing = bool(enable)
-        for h in self._handles.values():
-            _lib.check(_lib.load().nesr_swin2sr_set_timing(h, 1 if enable else 0), "nesr_swin2sr_set_timing")
-
-    def kernel_time_ms(self, device=None):
-        """{"launches": kernel launches, "groups": {name: ms}} since the last call, summed over the forwards in between."""
-        handles = list(self._handles.items())
-        if device is not None:
-            handles = [(i, h) for i, h in handles if i == torch.device(device).index]
-        launches, groups = 0, OrderedDict((name, 0.0) for name in KERNEL_GROUPS)
-        for index, h in handles:
-            ms = (ctypes.c_double * len(KERNEL_GROUPS))()
-            n = ctypes.c_int64(0)
-            with torch.cuda.device(index):
-                _lib.check(_lib.load().nesr_swin2sr_kernel_time_ms(h, ms, len(KERNEL_GROUPS), ctypes.byref(n)), "nesr_swin2sr_kernel_time_ms")
-            launches += n.value
-            for name, v in zip(KERNEL_GROUPS, ms):
-                groups[name] += v
-        return {"launches": launches, "groups": groups}
