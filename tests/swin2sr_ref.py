@@ -12,7 +12,7 @@ What the installed source does and a memory of SwinIR would not (modeling_swin2s
   * key has no bias; query and value have one.
 
 `fault` names one deliberate mistake (FAULTS); tests/test_swin2sr_cases_host.py shows that every one of them fails a crafted
-case.  Frame level: `process_frame` is Swin2SRImageProcessor (x / 255, symmetric pad right and bottom to (n // 8 + 1) * 8) and
+case.  The faults of FRAME_FAULTS are mistakes of the processor's padding and act in `process_frame`, not in the model.  Frame level: `process_frame` is Swin2SRImageProcessor (x / 255, symmetric pad right and bottom to (n // 8 + 1) * 8) and
 `upscale_u8` the documented post-processing (clamp, x 255, round, uint8) of the model's output cropped to H s x W s.
 """
 from __future__ import annotations
@@ -33,7 +33,9 @@ PROCESSOR_PAD = 8                    # Swin2SRImageProcessor.size_divisor
 
 FAULTS = ("no_shift", "shift_reversed", "no_mask", "regions_at_shift_only", "key_bias", "no_clamp", "bias_unsquashed",
           "index_transposed", "pre_norm", "long_residual_after_embed", "no_stage_residual", "gelu_tanh", "shuffle_order",
-          "lrelu_swapped", "symmetric_pad", "mean_not_added")
+          "lrelu_swapped", "symmetric_pad", "mean_not_added", "phantom_keys_unmasked", "shift_rounded_up", "ln_unbiased",
+          "ln_padded_width", "embed_eps_from_config", "eps_default_everywhere", "gray_mean_kept", "single_bounce_pad")
+FRAME_FAULTS = ("single_bounce_pad",)      # faults of the processor's padding: process_frame and upscale_float take them, not the model
 
 
 def config(**cfg):
@@ -188,6 +190,20 @@ def region_mask(h, w, ws, shift, dtype, fault=None):
     return torch.where(diff != 0, torch.full_like(diff, -100.0), torch.zeros_like(diff))
 
 
+def layer_norm(t, C, weight, bias, eps, fault=None):
+    """F.layer_norm over the last axis; the two faults of its statistics are written out."""
+    if fault not in ("ln_unbiased", "ln_padded_width"):
+        return F.layer_norm(t, (C,), weight, bias, eps)
+    if fault == "ln_unbiased":
+        mean = t.sum(-1, keepdim=True) / C
+        var = ((t - mean) ** 2).sum(-1, keepdim=True) / (C - 1)
+    else:                                    # the sums run over the C real columns, the divisor is the storage width
+        cp = -(-C // 16) * 16
+        mean = t.sum(-1, keepdim=True) / cp
+        var = ((t - mean) ** 2).sum(-1, keepdim=True) / cp
+    return (t - mean) / torch.sqrt(var + eps) * weight + bias
+
+
 def window_attention(p, a, xw, mask, ws, heads, fault=None, taps=None):
     """xw [windows, ws^2, C] -> the context before output.dense."""
     nw, n, C = xw.shape
@@ -204,6 +220,12 @@ def window_attention(p, a, xw, mask, ws, heads, fault=None, taps=None):
         s = (s + mask.unsqueeze(1)) + mask.unsqueeze(1)        # twice, as the source does
     if taps is not None:
         taps.setdefault("scores", []).append(s)
+    if fault == "phantom_keys_unmasked" and n % 16:
+        # the window padded to a multiple of 16 tokens with zero tokens: their keys are zero (no key bias) and score 0 where
+        # -inf belongs; their values are the value bias
+        pad = -n % 16
+        s = torch.cat([s, s.new_zeros(nw, heads, n, pad)], dim=-1)
+        v = torch.cat([v, p[a + ".value.bias"].view(1, heads, 1, d).expand(nw, heads, pad, d)], dim=2)
     return (torch.softmax(s, dim=-1) @ v).transpose(1, 2).reshape(nw, n, C)
 
 
@@ -217,8 +239,8 @@ def layer(p, l, x, h, w, ws, shift, heads, eps, fault=None, taps=None):
         img = torch.roll(img, shifts=fwd, dims=(0, 1))
     xw = img.view(h // ws, ws, w // ws, ws, C).transpose(1, 2).reshape(-1, ws * ws, C)
     mask = region_mask(h, w, ws, shift, x.dtype, fault) if (shift > 0 and fault != "no_mask") else None
-    ln1 = lambda t: F.layer_norm(t, (C,), p[l + ".layernorm_before.weight"], p[l + ".layernorm_before.bias"], eps)
-    ln2 = lambda t: F.layer_norm(t, (C,), p[l + ".layernorm_after.weight"], p[l + ".layernorm_after.bias"], eps)
+    ln1 = lambda t: layer_norm(t, C, p[l + ".layernorm_before.weight"], p[l + ".layernorm_before.bias"], eps, fault)
+    ln2 = lambda t: layer_norm(t, C, p[l + ".layernorm_after.weight"], p[l + ".layernorm_after.bias"], eps, fault)
     if fault == "pre_norm":
         xw = ln1(xw)
     ctx = window_attention(p, l + ".attention.self", xw, mask, ws, heads, fault, taps)
@@ -252,7 +274,7 @@ def swin2sr_forward(sd, pixel_values, fault=None, taps=None, **cfg):
     if c["num_channels"] == 3 and c["num_channels_out"] == 3:
         mean = torch.tensor(RGB_MEAN, dtype=torch.float32).to(dt).view(1, 3, 1, 1)      # the float32 values, as the model's buffer
     else:
-        mean = torch.zeros(1, 1, 1, 1, dtype=dt)
+        mean = torch.full((1, 1, 1, 1), RGB_MEAN[0] if fault == "gray_mean_kept" else 0.0, dtype=torch.float32).to(dt)
     ph, pw = (ws - H % ws) % ws, (ws - W % ws) % ws
     x = pixel_values
     if ph or pw:
@@ -266,18 +288,22 @@ def swin2sr_forward(sd, pixel_values, fault=None, taps=None, **cfg):
     h, w = first.shape[2:]
     pe = "swin2sr.embeddings.patch_embeddings"
     t = conv(first, pe + ".projection").flatten(2).transpose(1, 2)[0]            # [h w, C]
-    t = F.layer_norm(t, (C,), p[pe + ".layernorm.weight"], p[pe + ".layernorm.bias"], 1e-5)
+    eps_embed = eps if fault == "embed_eps_from_config" else 1e-5
+    if fault == "eps_default_everywhere":
+        eps = 1e-5
+    half = (ws + 1) // 2 if fault == "shift_rounded_up" else ws // 2
+    t = layer_norm(t, C, p[pe + ".layernorm.weight"], p[pe + ".layernorm.bias"], eps_embed, fault)
     long_res = t.t().reshape(1, C, h, w) if fault == "long_residual_after_embed" else first
     for i, (depth, heads) in enumerate(zip(c["depths"], c["num_heads"])):
         s = f"swin2sr.encoder.stages.{i}"
         res = t
         for j in range(depth):
-            t = layer(p, f"{s}.layers.{j}", t, h, w, ws, 0 if j % 2 == 0 else ws // 2, heads, eps, fault, taps)
+            t = layer(p, f"{s}.layers.{j}", t, h, w, ws, 0 if j % 2 == 0 else half, heads, eps, fault, taps)
         img = conv(t.t().reshape(1, C, h, w), s + ".conv")
         t = conv(img, s + ".patch_embed.projection").flatten(2).transpose(1, 2)[0]
         if fault != "no_stage_residual":
             t = t + res
-    t = F.layer_norm(t, (C,), p["swin2sr.layernorm.weight"], p["swin2sr.layernorm.bias"], eps)
+    t = layer_norm(t, C, p["swin2sr.layernorm.weight"], p["swin2sr.layernorm.bias"], eps, fault)
     y = conv(t.t().reshape(1, C, h, w), "swin2sr.conv_after_body") + long_res
     up = c["upsampler"]
     s_ps, s_nc = (0.2, 0.01) if fault == "lrelu_swapped" else (0.01, 0.2)
@@ -307,20 +333,24 @@ def padded_size(n):
     return (n // PROCESSOR_PAD + 1) * PROCESSOR_PAD
 
 
-def process_frame(frame, dtype=torch.float64):
+def process_frame(frame, dtype=torch.float64, fault=None):
     """Swin2SRImageProcessor: [H, W, 3] uint8 -> [1, 3, Hp, Wp], x / 255 then numpy's "symmetric" pad right and bottom."""
     a = np.asarray(frame).astype(np.float64) / 255.0
     h, w = a.shape[:2]
-    a = np.pad(a, ((0, padded_size(h) - h), (0, padded_size(w) - w), (0, 0)), mode="symmetric")
+    if fault == "single_bounce_pad":         # one reflection about the far edge, then the first sample
+        bounce = lambda n: np.array([i if i < n else max(2 * n - 1 - i, 0) for i in range(padded_size(n))])
+        a = a[bounce(h)][:, bounce(w)]
+    else:
+        a = np.pad(a, ((0, padded_size(h) - h), (0, padded_size(w) - w), (0, 0)), mode="symmetric")
     return torch.from_numpy(a).permute(2, 0, 1).unsqueeze(0).to(dtype).contiguous()
 
 
-def upscale_float(sd, frame, dtype=torch.float64, **cfg):
-    """The model's output on the processed frame, cropped to [H s, W s, 3] (before the clamp)."""
+def upscale_float(sd, frame, dtype=torch.float64, fault=None, **cfg):
+    """The model's output on the processed frame, cropped to [H s, W s, 3] (before the clamp).  `fault`: one of FRAME_FAULTS."""
     h, w = np.asarray(frame).shape[:2]
     s = config(**cfg)["upscale"]
     with torch.no_grad():
-        y = swin2sr_forward(sd, process_frame(frame, dtype), **cfg)
+        y = swin2sr_forward(sd, process_frame(frame, dtype, fault), **cfg)
     return y[0, :, :h * s, :w * s].permute(1, 2, 0).contiguous()
 
 

@@ -3,7 +3,11 @@
   upscale     every crafted configuration on a 13 x 18 frame (both paddings and the crop) and an 8 x 8 frame (a multiple of 8, which
               the processor still pads by 8): the u8 result equals the float64 route's u8 wherever the float64 value x 255 lies
               farther than 255 tol from a rounding boundary, and is off by at most 1 elsewhere; at most 2 % of the samples are
-              left out (tests/test_swin2sr_host.py holds that condition on the CPU).  Guard bytes surround the output.
+              left out (tests/test_swin2sr_host.py holds that condition on the CPU).  Guard bytes surround the output.  The same on
+              frames shorter than the processor's padding (1 x 1, 2 x 3, 3 x 17), where the symmetric extension bounces more than once
+  ties        a model whose every output sample is a rounding tie (k + 0.5 exactly in float32) or clamped: the u8 frame is
+              round-half-to-even on every sample, exactly
+  workspace   a small frame after a large one on one context gives the bits of a fresh context, and the large frame its own again
   refusals    a missing weight at finalize, an unexpected key, every unsupported field, an H that is no multiple of the window,
               a capacity too small: all rejected before any launch
   the loop    swin2sr_stage inside enhance_iterations against the same loop with the float64 restatement as the callable
@@ -23,7 +27,7 @@ from tests.test_swin2sr_host import BASE, UNSUPPORTED
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-NAMES = [c.name for c in C.cases()]
+NAMES = [c.name for c in C.frame_cases()]      # the RGB configurations; `gray` is refused (test_one_channel_model_refuses_an_rgb_frame)
 GUARD = 4096
 _cache = {}
 
@@ -37,11 +41,9 @@ def model(name):
     return _cache[name]
 
 
-@pytest.mark.parametrize("name", NAMES)
-@pytest.mark.parametrize("hw", C.FRAMES, ids=lambda hw: "%dx%d" % hw)
-def test_upscale_against_the_float64_route(name, hw):
-    m = model(name)
-    frame, y64, tol = C.frame_reference(name, hw)
+def guarded_upscale(m, frame):
+    """nesr_swin2sr_upscale_u8 into the middle of a buffer of sentinels: the u8 frame [h s, w s, 3] on the host; the guards are asserted."""
+    hw = frame.shape[:2]
     s = m.config["upscale"]
     oh, ow = hw[0] * s, hw[1] * s
     n = oh * ow * 3
@@ -51,8 +53,15 @@ def test_upscale_against_the_float64_route(name, hw):
     _lib.check(_lib.load().nesr_swin2sr_upscale_u8(m._context(src.device), ctypes.c_void_p(src.data_ptr()), hw[0], hw[1],
                                                    ctypes.c_void_p(buf.data_ptr() + GUARD), n, stream), "nesr_swin2sr_upscale_u8")
     torch.cuda.synchronize()
-    got = buf[GUARD:GUARD + n].view(oh, ow, 3).cpu()
     assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[GUARD + n:] == 0xA5).all()), "the entry wrote outside the frame it reports"
+    return buf[GUARD:GUARD + n].view(oh, ow, 3).cpu()
+
+
+def upscale_against_the_float64_route(name, hw):
+    m = model(name)
+    frame, y64, tol = C.frame_reference(name, hw)
+    src = torch.from_numpy(frame).to(DEV)
+    got = guarded_upscale(m, frame)
     excluded, wrong, total = R.u8_check(got, y64, tol)
     print(f"{name} {hw}: tol {tol:.3e}, {excluded} of {total} samples thin ({100.0 * excluded / total:.2f} %), {wrong} wrong")
     assert wrong == 0
@@ -60,6 +69,65 @@ def test_upscale_against_the_float64_route(name, hw):
     via_module = m.upscale(frame)                                   # an ndarray is copied up once
     assert via_module.is_cuda and via_module.dtype == torch.uint8 and torch.equal(via_module.cpu(), got)
     assert torch.equal(m(src).cpu(), got)                           # a u8 HWC frame through __call__ is upscale
+
+
+@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("hw", C.FRAMES, ids=lambda hw: "%dx%d" % hw)
+def test_upscale_against_the_float64_route(name, hw):
+    upscale_against_the_float64_route(name, hw)
+
+
+@pytest.mark.parametrize("name", C.SMALL_FRAME_CASES)
+@pytest.mark.parametrize("hw", C.SMALL_FRAMES, ids=lambda hw: "%dx%d" % hw)
+def test_upscale_of_frames_shorter_than_the_padding(name, hw):
+    """The symmetric extension to 8 bounces more than once (1 x 1: seven times); window 12 then reflects 8 x 8 to 12 x 12."""
+    upscale_against_the_float64_route(name, hw)
+
+
+def test_u8_rounds_ties_to_even():
+    """Exact: every sample of this model is k + 0.5 in float32 before the rounding, or outside [0, 1]; no sample is left out."""
+    case = C.rounding_ties()
+    m = Swin2SR(**case.cfg).to(DEV)
+    m.load_state_dict(case.sd)
+    got = guarded_upscale(m, case.frame)
+    want = C.ties_expected_frame(case)
+    assert got.shape == want.shape
+    bad = (got != want).nonzero()
+    assert bad.numel() == 0, (bad[:8].tolist(), got[:2, :2].tolist(), want[:2, :2].tolist())
+
+
+def test_one_channel_model_refuses_an_rgb_frame():
+    case = C.by_name("gray")
+    m = Swin2SR(**case.cfg).to(DEV)
+    m.load_state_dict(case.sd)
+    lib, h = _lib.load(), m._context(torch.device(DEV))
+    frame = torch.zeros(8, 8, 3, dtype=torch.uint8, device=DEV)
+    o8 = torch.full((16 * 16 * 3,), 0xA5, dtype=torch.uint8, device=DEV)
+    assert lib.nesr_swin2sr_upscale_u8(h, ctypes.c_void_p(frame.data_ptr()), 8, 8, ctypes.c_void_p(o8.data_ptr()), o8.numel(), None) == _lib.ERR_ARG
+    assert "an RGB frame needs num_channels = num_channels_out = 3" in lib.nesr_last_error().decode()
+    torch.cuda.synchronize()
+    assert bool((o8 == 0xA5).all())                                 # refused before any launch
+    with pytest.raises(_lib.NesrHipError, match="an RGB frame needs num_channels"):
+        m.upscale(frame)
+
+
+@pytest.mark.parametrize("name", ["small_shift", "published_width"])      # pixelshuffle (both shuffle buffers) and nearest+conv
+def test_workspace_reuse_leaves_no_trace(name):
+    """The workspace only grows, and a smaller frame carves its buffers from the same base: a read past a frame's extent would meet
+    what the larger frame left there.  Bit-equal to a context that never saw the large frame, and the large frame to itself."""
+    case = C.by_name(name)
+    used, fresh = Swin2SR(**case.cfg).to(DEV), Swin2SR(**case.cfg).to(DEV)
+    used.load_state_dict(case.sd)
+    fresh.load_state_dict(case.sd)
+    big, small = R.seeded_input(24, 24, 61).to(DEV), R.seeded_input(8, 8, 62).to(DEV)
+    y_big, y_small, y_again = used(big).cpu(), used(small).cpu(), used(big).cpu()
+    assert torch.isfinite(y_big).all() and torch.equal(y_big, y_again)
+    assert torch.equal(y_small, fresh(small).cpu())
+    fbig, fsmall = R.seeded_frame(21, 19, 63), R.seeded_frame(3, 5, 64)
+    u_big, u_small, u_again = used.upscale(fbig).cpu(), used.upscale(fsmall).cpu(), used.upscale(fbig).cpu()
+    assert torch.equal(u_big, u_again)
+    assert torch.equal(u_small, fresh.upscale(fsmall).cpu())
+    assert torch.equal(fresh(big).cpu(), y_big)                     # and growing after a small frame changes nothing either
 
 
 def test_finalize_and_load_weight_are_strict():

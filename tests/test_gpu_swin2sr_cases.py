@@ -35,14 +35,15 @@ def guarded_forward(case):
     x = case.pixel_values().to(DEV).contiguous()
     _, ch, h, w = x.shape
     oh, ow = m.output_size(h, w)
-    n = 3 * oh * ow
+    co = m.config["num_channels_out"]
+    n = co * oh * ow
     buf = torch.full((GUARD + n + GUARD,), -7.0, dtype=torch.float32, device=DEV)
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(_lib.load().nesr_swin2sr_forward_f32(m._context(x.device), ctypes.c_void_p(x.data_ptr()), 1, ch, h, w,
                                                     ctypes.c_void_p(buf.data_ptr() + 4 * GUARD), n, stream), "nesr_swin2sr_forward_f32")
     torch.cuda.synchronize()
     intact = bool((buf[:GUARD] == -7.0).all()) and bool((buf[GUARD + n:] == -7.0).all())
-    return buf[GUARD:GUARD + n].view(1, 3, oh, ow).cpu(), intact
+    return buf[GUARD:GUARD + n].view(1, co, oh, ow).cpu(), intact
 
 
 @pytest.mark.parametrize("name", [c.name for c in C.forward_cases()])

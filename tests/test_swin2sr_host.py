@@ -19,6 +19,7 @@ from tests import swin2sr_ref as R
 
 FORWARD = [c.name for c in C.forward_cases()]
 NAMES = [c.name for c in C.cases()]
+FRAME_NAMES = [c.name for c in C.frame_cases()]      # the RGB configurations: the frame-level route takes no other
 
 
 def hf_model(cfg):
@@ -67,7 +68,7 @@ def test_transformers_renames_no_swin2sr_key():
     assert "swin2sr" not in inspect.getsource(conversion_mapping).lower()
 
 
-@pytest.mark.parametrize("hw", [(13, 18), (8, 8), (5, 7)])
+@pytest.mark.parametrize("hw", [(13, 18), (8, 8), (5, 7), (1, 1), (2, 3)])
 def test_process_frame_is_the_image_processor(hw):
     pytest.importorskip("transformers")
     try:
@@ -81,7 +82,7 @@ def test_process_frame_is_the_image_processor(hw):
     assert float((got - want.float()).abs().max()) <= 1e-7
 
 
-@pytest.mark.parametrize("name", NAMES)
+@pytest.mark.parametrize("name", FRAME_NAMES)
 @pytest.mark.parametrize("hw", C.FRAMES, ids=lambda hw: "%dx%d" % hw)
 def test_thin_samples_stay_under_the_cap(name, hw):
     """The u8 criterion leaves out the samples whose float64 value x 255 lies within 255 tol of a rounding boundary; the seeds are
@@ -96,6 +97,13 @@ def test_thin_samples_stay_under_the_cap(name, hw):
     print(f"{name} {hw}: tol {tol:.3e}, {excluded} of {n} samples thin ({100.0 * excluded / n:.2f} %), {wrong} wrong (f32 CPU), {100 * inside:.0f} % inside (0, 1)")
     assert excluded <= C.MAX_THIN * n and wrong == 0
     assert inside > 0.5      # the clamp does not decide most samples
+
+
+@pytest.mark.parametrize("name", C.SMALL_FRAME_CASES)
+@pytest.mark.parametrize("hw", C.SMALL_FRAMES, ids=lambda hw: "%dx%d" % hw)
+def test_thin_samples_stay_under_the_cap_on_small_frames(name, hw):
+    """The same condition on the frames shorter than the processor's padding (a 1 x 1 frame has 12 s^2 samples: none may be thin)."""
+    test_thin_samples_stay_under_the_cap(name, hw)
 
 
 def test_output_size_needs_no_device():
