@@ -1019,6 +1019,43 @@ int nesr_swin2sr_output_size(int upscale, int H, int W, int* out_h, int* out_w);
 int nesr_swin2sr_forward_f32(nesr_swin2sr* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* out_dev, size_t capacity,
                              void* hip_stream);
 int nesr_swin2sr_upscale_u8(nesr_swin2sr* ctx, const uint8_t* rgb_dev, int H, int W, uint8_t* out_dev, size_t capacity, void* hip_stream);
+/*
+ * Tiled frames and batches.  The workspace of the entries above grows with the frame (about 1.3 GB at 512 x 512 for the classical
+ * x2 model); a large frame goes through nesr_swin2sr_upscale_tiled_u8 instead, window by window, and equal windows share launches.
+ *
+ * The plan, per axis of length n with tile = T >= 1 (the core's side, input pixels) and tile_pad = P >= 0: cores i = 0 ..
+ * ceil(n / T) - 1, [c0, c1) = [i T, min((i + 1) T, n)); every window of the axis is S = min(T + 2 P, n) long and starts at
+ * w0 = clamp(c0 - P, 0, n - S): a window at the edge slides inward instead of shrinking, so all windows of a frame have one shape
+ * win_h x win_w, and a core pixel has at least min(P, its distance to the frame's edge) pixels of true context on each side.
+ * Each window is treated exactly as a frame given to nesr_swin2sr_upscale_u8; of its output, the core's rows and columns are
+ * quantised and stored at the core's place of the H s x W s x 3 result.  A frame with H <= T + 2 P and W <= T + 2 P has one window
+ * (the frame) and gives the bits of nesr_swin2sr_upscale_u8.
+ *
+ * nesr_swin2sr_tile_plan touches no device and needs no context: the counts, the window shape and, unless `plan` is null, one row
+ * of 8 integers per tile in row-major order, {win_y, win_x (input pixels), crop_y, crop_x, crop_h, crop_w (the core inside the
+ * window's output), out_y, out_x (its place in the result)}, the last six in output pixels; capacity counts integers.
+ * nesr_swin2sr_workspace_bytes: what a forward of `batch` windows of win_h x win_w allocates.
+ *
+ * nesr_swin2sr_upscale_tiled_u8: the tiles run in row-major order in ceil(n / B) batches of B windows, the last one shorter;
+ * B = max_batch, or for max_batch <= 0 as many windows as keep the workspace within NESR_SWIN2SR_TILE_WORKSPACE_BYTES (a
+ * setting, not a measurement), in both cases at least one and at most the tiles of the frame.  The result does not depend on B.
+ * The reflect-padding limit of the model (a window no shorter than half the attention window, roughly) is checked on the
+ * window shape before any launch.  NESR_ERR_ARG, before any launch and with the argument's name in the text: tile < 1,
+ * tile_pad < 0, a capacity too small, a model whose channels are not 3 / 3.
+ *
+ * nesr_swin2sr_forward_batch_f32: pixel_values_dev [N, C, H, W] f32, N >= 1 -> out_dev [N, num_channels_out, H s, W s]; every
+ * image gets the bits nesr_swin2sr_forward_f32 gives it alone.  H or W no multiple of window_size is NESR_ERR_ARG.
+ * Every launch of a batch counts once in nesr_swin2sr_kernel_time_ms.
+ */
+#define NESR_SWIN2SR_TILE_WORKSPACE_BYTES ((size_t)2 << 30)
+#define NESR_SWIN2SR_TILED_MAX_PIXELS (1ll << 28)
+int nesr_swin2sr_tile_plan(int upscale, int H, int W, int tile, int tile_pad, int* tiles_y, int* tiles_x, int* win_h, int* win_w, int32_t* plan,
+                           size_t capacity);
+int nesr_swin2sr_workspace_bytes(nesr_swin2sr* ctx, int win_h, int win_w, int batch, size_t* bytes);
+int nesr_swin2sr_upscale_tiled_u8(nesr_swin2sr* ctx, const uint8_t* rgb_dev, int H, int W, int tile, int tile_pad, int max_batch, uint8_t* out_dev,
+                                  size_t capacity, void* hip_stream);
+int nesr_swin2sr_forward_batch_f32(nesr_swin2sr* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* out_dev, size_t capacity,
+                                   void* hip_stream);
 /* The launch counter and the per-group event timing, as nesr_segformer_set_timing / nesr_segformer_kernel_time_ms. */
 enum { NESR_S2_GROUP_CONV = 0, NESR_S2_GROUP_PROJ = 1, NESR_S2_GROUP_ATTENTION = 2, NESR_S2_GROUP_MLP = 3, NESR_S2_GROUP_UPSAMPLE = 4,
        NESR_S2_GROUPS = 5 };

@@ -88,3 +88,24 @@ def packed_pastes(tiles):
         offs.append(offs[-1] + (t.out[1] - t.out[0]) * (t.out[3] - t.out[2]) * 3)
     return [(t.crop[0], t.crop[2], t.crop[1] - t.crop[0], t.crop[3] - t.crop[2], offs[i], (t.out[3] - t.out[2]) * 3)
             for i, t in enumerate(tiles)], offs
+
+
+def slid_window_axis(n, tile, tile_pad):
+    """One axis of Swin2SR's tile plan: (S, [(w0, c0, c1)]).  Cores [c0, c1) of `tile` partition [0, n); every window is
+    S = min(tile + 2 tile_pad, n) long and starts at w0 = clamp(c0 - tile_pad, 0, n - S): a window at the edge slides inward instead
+    of shrinking, so the windows of an axis have one length."""
+    if n < 1 or tile < 1 or tile_pad < 0:
+        raise ValueError(f"slid_window_axis: n >= 1, tile >= 1, tile_pad >= 0, got {n}, {tile}, {tile_pad}")
+    side = min(tile + 2 * tile_pad, n)
+    return side, [(min(max(c0 - tile_pad, 0), n - side), c0, min(c0 + tile, n)) for c0 in range(0, n, tile)]
+
+
+def slid_window_plan(h, w, tile, tile_pad, scale):
+    """Swin2SR's tile plan of an h x w frame, what nesr_swin2sr_tile_plan computes: ((tiles_y, tiles_x), (win_h, win_w), rows), one
+    row (win_y, win_x, crop_y, crop_x, crop_h, crop_w, out_y, out_x) per tile in row-major order; the window's origin in input
+    pixels, the core inside the window's output and its place in the result in output pixels."""
+    sy, ys = slid_window_axis(h, tile, tile_pad)
+    sx, xs = slid_window_axis(w, tile, tile_pad)
+    rows = [(wy, wx, (y0 - wy) * scale, (x0 - wx) * scale, (y1 - y0) * scale, (x1 - x0) * scale, y0 * scale, x0 * scale)
+            for wy, y0, y1 in ys for wx, x0, x1 in xs]
+    return (len(ys), len(xs)), (sy, sx), rows

@@ -22,6 +22,10 @@
 // l is D[row 4 (l >> 4) + r][col l & 15].  Widths are padded to the tile with zeros (swin2sr_api.h).  No atomics, no workgroup
 // waits on another: a forward repeated gives the same bits.  Every global load and store is guarded by the token count, the
 // image extent and the real width.
+//
+// A launch takes a batch of images of one padded size (the tiles of a large frame, nesr_swin2sr_upscale_tiled_u8): the conv and the
+// attention kernel read the image from blockIdx.z and offset their bases by it; zero padding, the cyclic shift and the region mask
+// stay inside the image.  The row kernel sees batch * H * W rows.  A batch of one runs the arithmetic of a whole frame unchanged.
 #include "swin2sr_api.h"
 
 #include "nesr_kernels.h"
@@ -126,6 +130,21 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int x0 = blockIdx.x * S2_CONV_TW, y0 = blockIdx.y * S2_CONV_TH;
     const int ldp = conv_ldp(a.cinp), nq = a.cinp >> 2;
+    const size_t b = blockIdx.z, px_img = (size_t)a.H * a.W;      // the image of this workgroup; zero padding at its own border
+    // image b's window in the frame (wy, wx) and its core inside the window's output [cy0, cy1) x [cx0, cx1); a whole frame: all of it
+    int wy = 0, wx = 0, cy0 = 0, cy1 = a.oh, cx0 = 0, cx1 = a.ow;
+    if (a.tile > 0) {
+        const int ti = a.tile0 + (int)b, ty = ti / a.tiles_x, tx = ti - ty * a.tiles_x;
+        int c0, c1;
+        s2_tile_axis(a.FH, a.tile, a.tile_pad, ty, wy, c0, c1);
+        cy0 = (c0 - wy) * a.up, cy1 = (c1 - wy) * a.up;
+        s2_tile_axis(a.FW, a.tile, a.tile_pad, tx, wx, c0, c1);
+        cx0 = (c0 - wx) * a.up, cx1 = (c1 - wx) * a.up;
+    }
+    const float* in_rows = static_cast<const float*>(a.in);
+    if (a.in_mode == S2_IN_ROWS) in_rows += b * px_img * a.cs_in;
+    else if (a.in_mode == S2_IN_NEAREST2) in_rows += b * (size_t)(a.H >> 1) * (a.W >> 1) * a.cs_in;
+    else if (a.in_mode == S2_IN_FRAME_F32) in_rows += b * (size_t)a.cin * a.fh * a.fw;
 
     for (int idx = t; idx < CP_H * CP_W * nq; idx += 256) {
         const int q = idx % nq, pos = idx / nq, px = pos % CP_W, py = pos / CP_W;
@@ -133,20 +152,20 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
             if (a.in_mode == S2_IN_ROWS) {
-                v = *reinterpret_cast<const float4*>(static_cast<const float*>(a.in) + ((size_t)gy * a.W + gx) * a.cs_in + q * 4);
+                v = *reinterpret_cast<const float4*>(in_rows + ((size_t)gy * a.W + gx) * a.cs_in + q * 4);
             } else if (a.in_mode == S2_IN_NEAREST2) {
-                v = *reinterpret_cast<const float4*>(static_cast<const float*>(a.in) + ((size_t)(gy >> 1) * (a.W >> 1) + (gx >> 1)) * a.cs_in + q * 4);
+                v = *reinterpret_cast<const float4*>(in_rows + ((size_t)(gy >> 1) * (a.W >> 1) + (gx >> 1)) * a.cs_in + q * 4);
             } else if (q == 0) {
-                // reflect back into the model's input (mh x mw), then symmetric back into the frame (fh x fw)
+                // reflect back into the model's input (mh x mw), then symmetric back into the image's own window (fh x fw) of the frame
                 int my = gy < a.mh ? gy : 2 * a.mh - 2 - gy, mx = gx < a.mw ? gx : 2 * a.mw - 2 - gx;
                 const int fy = sym_index(my, a.fh), fx = sym_index(mx, a.fw);
                 float e[4] = {0.f, 0.f, 0.f, 0.f};
                 for (int ch = 0; ch < a.cin; ++ch) {
                     float p;
                     if (a.in_mode == S2_IN_FRAME_U8)
-                        p = (float)static_cast<const uint8_t*>(a.in)[((size_t)fy * a.fw + fx) * a.cin + ch] / 255.0f;
+                        p = (float)static_cast<const uint8_t*>(a.in)[((size_t)(wy + fy) * a.FW + (wx + fx)) * a.cin + ch] / 255.0f;
                     else
-                        p = static_cast<const float*>(a.in)[((size_t)ch * a.fh + fy) * a.fw + fx];
+                        p = in_rows[((size_t)ch * a.fh + fy) * a.fw + fx];
                     e[ch] = (p - a.mean[ch]) * a.range;
                 }
                 v = make_float4(e[0], e[1], e[2], e[3]);
@@ -157,6 +176,11 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
     __syncthreads();
 
     const int r2 = a.shuffle * a.shuffle, ncc = a.cout / r2;
+    const float* res = a.res ? a.res + b * px_img * a.cs_res : nullptr;
+    float* out_rows = static_cast<float*>(a.out);
+    if (a.out_mode == S2_OUT_ROWS) out_rows += b * px_img * r2 * a.cs_out;
+    else if (a.out_mode == S2_OUT_F32) out_rows += b * (size_t)ncc * a.oh * a.ow;
+    const int out_y = wy * a.up, out_x = wx * a.up, out_pitch = a.tile > 0 ? a.FW * a.up : a.ow;      // U8: the window's place in the frame
     for (int ni = wave; ni < (a.coutp >> 4); ni += 4) {
         f32x4 acc[S2_CONV_TH];
 #pragma unroll
@@ -193,25 +217,26 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
                 if (y >= a.H || x >= a.W) continue;
                 float v = acc[i][r] + bias;
                 if (a.lrelu) v = v >= 0.f ? v : v * a.slope;
-                if (a.res) v += a.res[((size_t)y * a.W + x) * a.cs_res + c];      // c < coutp <= cs_res
+                if (res) v += res[((size_t)y * a.W + x) * a.cs_res + c];      // c < coutp <= cs_res
                 if (a.out_mode == S2_OUT_ROWS && a.shuffle == 1) {
-                    static_cast<float*>(a.out)[((size_t)y * a.W + x) * a.cs_out + c] = v;      // coutp == cs_out: the zero columns too
+                    out_rows[((size_t)y * a.W + x) * a.cs_out + c] = v;      // coutp == cs_out: the zero columns too
                     continue;
                 }
                 if (c >= a.cout) continue;
                 const int cc = c / r2, rem = c - cc * r2, r1 = rem / a.shuffle;
                 const int oy = y * a.shuffle + r1, ox = x * a.shuffle + (rem - r1 * a.shuffle);
                 if (a.out_mode == S2_OUT_ROWS) {
-                    static_cast<float*>(a.out)[((size_t)oy * (a.W * a.shuffle) + ox) * a.cs_out + cc] = v;
+                    out_rows[((size_t)oy * (a.W * a.shuffle) + ox) * a.cs_out + cc] = v;
                     continue;
                 }
                 if (oy >= a.oh || ox >= a.ow) continue;
                 v = v / a.range + a.mean[cc];
                 if (a.out_mode == S2_OUT_F32) {
-                    static_cast<float*>(a.out)[((size_t)cc * a.oh + oy) * a.ow + ox] = v;
+                    out_rows[((size_t)cc * a.oh + oy) * a.ow + ox] = v;
                 } else {
+                    if (oy < cy0 || oy >= cy1 || ox < cx0 || ox >= cx1) continue;      // a tile stores its core alone
                     v = fminf(fmaxf(v, 0.f), 1.f) * 255.0f;
-                    static_cast<uint8_t*>(a.out)[((size_t)oy * a.ow + ox) * ncc + cc] = (uint8_t)rintf(v);
+                    static_cast<uint8_t*>(a.out)[((size_t)(out_y + oy) * out_pitch + (out_x + ox)) * ncc + cc] = (uint8_t)rintf(v);
                 }
             }
         }
@@ -275,6 +300,9 @@ __global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_kernel(const S2Attn a
     int* tok = reinterpret_cast<int*>(S + np * lds_s);      // [np] the token's row in memory, -1 past n
     int* reg = tok + np;                                    // [np] its region
     const int t = threadIdx.x, r8 = t >> 3, s8 = t & 7, rpp = S2_ATTN_THREADS / 8;      // row-wise work: 8 threads a row, rpp rows a pass
+    const size_t img = (size_t)blockIdx.z * a.H * a.W * a.cs;      // the window's image; tokens, the shift and the regions are its own
+    const float* in = a.in + img;
+    float* out = a.out + img;
 
     for (int i = t; i < np; i += S2_ATTN_THREADS) {
         int tk = -1, rg = -1;
@@ -289,7 +317,7 @@ __global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_kernel(const S2Attn a
     for (int i = r8; i < np; i += rpp) {
         const int tk = tok[i];
         for (int c = s8 * 4; c < a.cs; c += 32) {
-            *reinterpret_cast<float4*>(X + i * ldc + c) = tk >= 0 ? *reinterpret_cast<const float4*>(a.in + (size_t)tk * a.cs + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            *reinterpret_cast<float4*>(X + i * ldc + c) = tk >= 0 ? *reinterpret_cast<const float4*>(in + (size_t)tk * a.cs + c) : make_float4(0.f, 0.f, 0.f, 0.f);
             *reinterpret_cast<float4*>(CTX + i * ldc + c) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
@@ -362,7 +390,7 @@ __global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_kernel(const S2Attn a
         if (tk < 0) continue;
         for (int j = s8; j < a.cs; j += 8) {
             const float v = (X[i * ldc + j] - mean) * rstd * a.ln_g[j] + a.ln_b[j];      // zero past c
-            a.out[(size_t)tk * a.cs + j] = a.in[(size_t)tk * a.cs + j] + v;
+            out[(size_t)tk * a.cs + j] = in[(size_t)tk * a.cs + j] + v;
         }
     }
 }
@@ -409,8 +437,21 @@ hipError_t launch_s2_conv(const S2Conv& a, hipStream_t s) {
     } else {
         return hipErrorInvalidValue;
     }
+    if (a.batch < 1 || a.batch > 65535) return hipErrorInvalidValue;
+    const bool u8_in = a.in_mode == S2_IN_FRAME_U8, u8_out = a.out_mode == S2_OUT_U8;
+    if (a.tile > 0) {      // image b is a tile of the FH x FW frame: every window read and every core written lies inside it
+        if (!(u8_in || u8_out) || a.tile_pad < 0 || a.tile > (1 << 24) || a.tile_pad > (1 << 24) || a.FH < 1 || a.FW < 1 || a.up < 1 || a.tile0 < 0)
+            return hipErrorInvalidValue;
+        const int sy = s2_window_side(a.FH, a.tile, a.tile_pad), sx = s2_window_side(a.FW, a.tile, a.tile_pad);
+        const long long ty = (a.FH + a.tile - 1) / a.tile, tx = (a.FW + a.tile - 1) / a.tile;
+        if (a.tiles_x != tx || (long long)a.tile0 + a.batch > ty * tx) return hipErrorInvalidValue;
+        if (u8_in && (a.fh != sy || a.fw != sx)) return hipErrorInvalidValue;
+        if (u8_out && (a.oh != sy * a.up || a.ow != sx * a.up)) return hipErrorInvalidValue;
+    } else if ((u8_in || u8_out) && a.batch != 1) {
+        return hipErrorInvalidValue;      // u8 frames come one at a time, or as the tiles of one
+    }
     static unsigned long long done = 0;
-    const dim3 grid((a.W + S2_CONV_TW - 1) / S2_CONV_TW, (a.H + S2_CONV_TH - 1) / S2_CONV_TH);
+    const dim3 grid((a.W + S2_CONV_TW - 1) / S2_CONV_TW, (a.H + S2_CONV_TH - 1) / S2_CONV_TH, a.batch);
     if (grid.y > 65535u) return hipErrorInvalidValue;
     return launch_lds(&s2_conv_kernel, a, grid, 256, s2_conv_lds_bytes(a), done, s);
 }
@@ -420,6 +461,7 @@ hipError_t launch_s2_rows(const S2Rows& a, hipStream_t s) {
     if (a.w1 && (!a.b1 || a.n1p < 16 || a.n1p % 16 || (!a.w2 && a.n1p != a.cs))) return hipErrorInvalidValue;
     if (a.w2 && (!a.w1 || !a.b2)) return hipErrorInvalidValue;
     if (a.ln_g && !a.ln_b) return hipErrorInvalidValue;
+    if (a.m > S2_ROWS_MAX) return hipErrorInvalidValue;      // the row index (and m + 31) stays an int; row x cs is size_t in the kernel
     static unsigned long long done = 0;
     return launch_lds(&s2_rows_kernel, a, dim3((a.m + S2_BM - 1) / S2_BM), 256, s2_rows_lds_bytes(a), done, s);
 }
@@ -428,8 +470,9 @@ hipError_t launch_s2_attn(const S2Attn& a, hipStream_t s) {
     if (!a.in || !a.out || !a.wqkv || !a.bqkv || !a.scale || !a.bias || !a.wo || !a.bo || !a.ln_g || !a.ln_b) return hipErrorInvalidValue;
     if (a.ws < 1 || a.H < a.ws || a.W < a.ws || a.H % a.ws || a.W % a.ws || a.shift < 0 || a.shift >= a.ws) return hipErrorInvalidValue;
     if (a.heads < 1 || a.d < 1 || a.c != a.heads * a.d || a.dp % 16 || a.dp < a.d || a.cs % 16 || a.cs < a.c) return hipErrorInvalidValue;
+    if (a.batch < 1 || a.batch > 65535) return hipErrorInvalidValue;
     static unsigned long long done = 0;
-    const dim3 grid(a.W / a.ws, a.H / a.ws);
+    const dim3 grid(a.W / a.ws, a.H / a.ws, a.batch);
     if (grid.y > 65535u) return hipErrorInvalidValue;
     return launch_lds(&s2_attn_kernel, a, grid, S2_ATTN_THREADS, s2_attn_lds_bytes(a), done, s);
 }

@@ -1,6 +1,7 @@
 // Swin2SR contexts (nesr_swin2sr_*): the configuration check, strict weight loading, the padded and transposed upload, the
 // continuous position bias tables (computed once on the host in double), a workspace that grows with the frame, and the forward
-// as a chain of launches of the three kernels of swin2sr.hip.  Stands behind transformers' Swin2SRForImageSuperResolution and,
+// as a chain of launches of the three kernels of swin2sr.hip, over one frame or over a batch of images of one size: the images of
+// nesr_swin2sr_forward_batch_f32, or the windows the tile plan cuts a large frame into (nesr_swin2sr_upscale_tiled_u8).  Stands behind transformers' Swin2SRForImageSuperResolution and,
 // for nesr_swin2sr_upscale_u8, its Swin2SRImageProcessor and the documented post-processing.
 #include <cmath>
 #include <cstring>
@@ -74,7 +75,7 @@ S2Attn attn_shape(const nesr_swin2sr* c) {
 S2Conv conv_args(const nesr_swin2sr* c, const S2ConvW& w, const float* in, int H, int W, int cs_in, float* out, int cs_out) {
     S2Conv a;
     memset(&a, 0, sizeof(a));
-    a.in_mode = S2_IN_ROWS, a.in = in, a.H = H, a.W = W, a.cin = w.cin, a.cinp = w.cinp, a.cs_in = cs_in;
+    a.batch = 1, a.in_mode = S2_IN_ROWS, a.in = in, a.H = H, a.W = W, a.cin = w.cin, a.cinp = w.cinp, a.cs_in = cs_in;
     a.range = c->range;
     for (int i = 0; i < 4; ++i) a.mean[i] = c->mean[i];
     a.w = c->d_w + w.w, a.bias = c->d_w + w.b, a.cout = w.cout, a.coutp = w.coutp;
@@ -82,16 +83,49 @@ S2Conv conv_args(const nesr_swin2sr* c, const S2ConvW& w, const float* in, int H
     return a;
 }
 
-// frame: u8 HWC [fh][fw][3] (processor route) or f32 NCHW [nin][fh][fw] (model route); out: f32 NCHW or u8 HWC, cropped to fh s x fw s
-int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s) {
-    const int mh = frame_u8 ? (fh / kProcessorPad + 1) * kProcessorPad : fh, mw = frame_u8 ? (fw / kProcessorPad + 1) * kProcessorPad : fw;
-    const int H = round_up(mh, c->ws), W = round_up(mw, c->ws);
+// The images of one forward: B of them, each fh x fw.  tile = 0: they lie one after the other in `frame` and in `out` (f32), or
+// there is one (u8).  tile > 0 (u8 in and out): they are the tiles tile0 .. tile0 + B - 1 of the plan of an FH x FW frame.
+struct S2Batch {
+    int B = 1, tile = 0, tile_pad = 0, tiles_x = 1, tile0 = 0, FH = 0, FW = 0;
+};
+
+// the model's input (after the processor's symmetric padding of a u8 frame) and the conv's domain (after the reflect padding to the window)
+int padded_size(const nesr_swin2sr* c, bool frame_u8, int fh, int fw, int& mh, int& mw, int& H, int& W) {
+    mh = frame_u8 ? (fh / kProcessorPad + 1) * kProcessorPad : fh, mw = frame_u8 ? (fw / kProcessorPad + 1) * kProcessorPad : fw;
+    H = round_up(mh, c->ws), W = round_up(mw, c->ws);
     if (H - mh > mh - 1 || W - mw > mw - 1)
         return set_error(NESR_ERR_ARG, "Swin2SR: the reflect padding to the window (" + std::to_string(c->ws) + ") is wider than the image allows");
+    return NESR_OK;
+}
+
+// what forward() allocates for B images of H x W tokens: four activation buffers and the two of the upsampling head
+size_t workspace_bytes(const nesr_swin2sr* c, int H, int W, size_t B, size_t& act, size_t& upb) {
     const size_t T = (size_t)H * W, cs = c->cs, sc = c->scale;
-    const size_t act = align_up(T * cs * 4, 256), upb = c->up == UP_DIRECT ? 0 : align_up(T * sc * sc * kFeatures * 4, 256);
-    int rc = grow(c->ws_buf, c->ws_bytes, 4 * act + 2 * upb, kName);
+    act = align_up(B * T * cs * 4, 256), upb = c->up == UP_DIRECT ? 0 : align_up(B * T * sc * sc * kFeatures * 4, 256);
+    return 4 * act + 2 * upb;
+}
+
+// frame: u8 HWC [fh][fw][3] (processor route) or f32 NCHW [nin][fh][fw] (model route); out: f32 NCHW or u8 HWC, cropped to fh s x fw s
+int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt = S2Batch()) {
+    int mh, mw, H, W;
+    int rc = padded_size(c, frame_u8, fh, fw, mh, mw, H, W);
     if (rc) return rc;
+    const size_t T = (size_t)bt.B * H * W;
+    if (bt.B < 1 || bt.B > 65535 || T > (size_t)S2_ROWS_MAX)
+        return set_error(NESR_ERR_ARG, "Swin2SR: a batch of " + std::to_string(bt.B) + " images of " + std::to_string(H) + " x " + std::to_string(W) +
+                                           " tokens: at most 65535 images and 2^31 - 33 tokens go through one launch");
+    size_t act, upb;
+    rc = grow(c->ws_buf, c->ws_bytes, workspace_bytes(c, H, W, bt.B, act, upb), kName);
+    if (rc) return rc;
+    auto conv = [&](const S2ConvW& w, const float* in, int h, int wd, int cs_in, float* o, int cs_out) {
+        S2Conv a = conv_args(c, w, in, h, wd, cs_in, o, cs_out);
+        a.batch = bt.B;
+        return a;
+    };
+    auto tiled = [&](S2Conv& a) {      // where the first conv finds image b and the last one puts it
+        a.tile = bt.tile, a.tile_pad = bt.tile_pad, a.tiles_x = bt.tiles_x, a.tile0 = bt.tile0, a.up = c->scale;
+        a.FH = bt.tile > 0 ? bt.FH : fh, a.FW = bt.tile > 0 ? bt.FW : fw;
+    };
     float* FIRST = reinterpret_cast<float*>(c->ws_buf);
     float* XS = reinterpret_cast<float*>(c->ws_buf + act);
     float* X = reinterpret_cast<float*>(c->ws_buf + 2 * act);
@@ -102,8 +136,9 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     const int M = (int)T, C = c->C, CS = c->cs;
 
     {   // first_convolution on the padded, normalised frame -> FIRST (the long residual)
-        S2Conv a = conv_args(c, c->first, nullptr, H, W, 0, FIRST, CS);
+        S2Conv a = conv(c->first, nullptr, H, W, 0, FIRST, CS);
         a.in_mode = frame_u8 ? S2_IN_FRAME_U8 : S2_IN_FRAME_F32, a.in = frame, a.fh = fh, a.fw = fw, a.mh = mh, a.mw = mw;
+        tiled(a);
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
     auto rows = [&](const float* in, size_t w1, size_t b1, bool ln, size_t g, size_t b, float eps, const float* res, float* o) {
@@ -125,7 +160,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
             const S2LayerW& L = S.layers[j];
             {
                 S2Attn a = attn_shape(c);
-                a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0;
+                a.batch = bt.B, a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0;
                 a.in = j == 0 ? XS : X, a.out = X;      // the stage's input stays in XS
                 a.wqkv = wt(L.wqkv), a.bqkv = wt(L.bqkv), a.scale = wt(L.scale), a.bias = wt(L.bias), a.wo = wt(L.wo), a.bo = wt(L.bo);
                 a.ln_g = wt(L.ln1g), a.ln_b = wt(L.ln1b), a.eps = c->eps;
@@ -138,7 +173,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
             }
         }
         {
-            const S2Conv a = conv_args(c, S.conv, X, H, W, CS, T1, CS);
+            const S2Conv a = conv(S.conv, X, H, W, CS, T1, CS);
             NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
         }
         {   // the stage's 1x1 projection + the stage's input, in place
@@ -151,23 +186,24 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
     }
     {   // conv_after_body + the long residual -> T1
-        S2Conv a = conv_args(c, c->after, X, H, W, CS, T1, CS);
+        S2Conv a = conv(c->after, X, H, W, CS, T1, CS);
         a.res = FIRST, a.cs_res = CS;
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
     auto finish = [&](S2Conv& a) {      // / img_range + mean, the crop, f32 or u8
         a.out_mode = out_u8 ? S2_OUT_U8 : S2_OUT_F32, a.out = out, a.cs_out = 0, a.oh = fh * c->scale, a.ow = fw * c->scale;
+        tiled(a);
     };
     const int F = kFeatures;
     if (c->up == UP_DIRECT) {
-        S2Conv a = conv_args(c, c->direct, T1, H, W, CS, nullptr, 0);
+        S2Conv a = conv(c->direct, T1, H, W, CS, nullptr, 0);
         a.shuffle = c->scale;
         finish(a);
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
         return NESR_OK;
     }
     {
-        S2Conv a = conv_args(c, c->before, T1, H, W, CS, UA, F);
+        S2Conv a = conv(c->before, T1, H, W, CS, UA, F);
         a.lrelu = 1, a.slope = 0.01f;
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
     }
@@ -177,7 +213,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     if (c->up == UP_PIXELSHUFFLE) {
         const int r = c->scale == 3 ? 3 : 2;
         for (const S2ConvW& u : c->ups) {
-            S2Conv a = conv_args(c, u, cur, h, w, F, other, F);
+            S2Conv a = conv(u, cur, h, w, F, other, F);
             a.shuffle = r;
             NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
             std::swap(cur, other);
@@ -186,17 +222,17 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     } else {
         for (const S2ConvW* u : {&c->up1, &c->up2}) {
             h *= 2, w *= 2;
-            S2Conv a = conv_args(c, *u, cur, h, w, F, other, F);
+            S2Conv a = conv(*u, cur, h, w, F, other, F);
             a.in_mode = S2_IN_NEAREST2, a.lrelu = 1, a.slope = 0.2f;
             NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
             std::swap(cur, other);
         }
-        S2Conv a = conv_args(c, c->hr, cur, h, w, F, other, F);
+        S2Conv a = conv(c->hr, cur, h, w, F, other, F);
         a.lrelu = 1, a.slope = 0.2f;
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
         std::swap(cur, other);
     }
-    S2Conv a = conv_args(c, c->fin, cur, h, w, F, nullptr, 0);
+    S2Conv a = conv(c->fin, cur, h, w, F, nullptr, 0);
     finish(a);
     NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
     return NESR_OK;
@@ -496,6 +532,103 @@ int nesr_swin2sr_upscale_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, int W, u
     if (capacity < need) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_u8: the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
     NESR_TRY(hipSetDevice(c->device));
     return forward(c, rgb, true, H, W, out, true, static_cast<hipStream_t>(stream));
+}
+
+int nesr_swin2sr_forward_batch_f32(nesr_swin2sr* c, const float* x, int N, int C, int H, int W, float* out, size_t capacity, void* stream) {
+    if (!c || !x || !out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, "nesr_swin2sr_forward_batch_f32: weights not finalized (nesr_swin2sr_finalize)");
+    if (N < 1 || N > 65535 || C != c->nin)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: expected [N, " + std::to_string(c->nin) + ", H, W] with N in 1 .. 65535, got N = " +
+                                           std::to_string(N) + ", C = " + std::to_string(C));
+    if (H < 1 || W < 1 || (long long)H * W > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: images of 1 .. 2^24 pixels");
+    if (H % c->ws || W % c->ws)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: H and W must be multiples of window_size " + std::to_string(c->ws) + ", got " +
+                                           std::to_string(H) + " x " + std::to_string(W));
+    if ((long long)N * H * W > S2_ROWS_MAX)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: N x H x W = " + std::to_string((long long)N * H * W) + " tokens do not fit one launch (2^31 - 33)");
+    const size_t need = (size_t)N * c->nout * H * c->scale * W * c->scale;
+    if (capacity < need)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_forward_batch_f32: the output needs " + std::to_string(need) + " floats, capacity is " + std::to_string(capacity));
+    NESR_TRY(hipSetDevice(c->device));
+    S2Batch bt;
+    bt.B = N;
+    return forward(c, x, false, H, W, out, false, static_cast<hipStream_t>(stream), bt);
+}
+
+int nesr_swin2sr_tile_plan(int upscale, int H, int W, int tile, int tile_pad, int* tiles_y, int* tiles_x, int* win_h, int* win_w, int32_t* plan,
+                           size_t capacity) {
+    if (!tiles_y || !tiles_x || !win_h || !win_w) return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: null pointer");
+    if (upscale < 1 || upscale > 8) return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: upscale must be 1 .. 8");
+    if (H < 1 || W < 1 || (long long)H * W > NESR_SWIN2SR_TILED_MAX_PIXELS)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: a frame (H x W) of 1 .. 2^28 pixels");
+    if (tile < 1 || tile > (1 << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: tile must be 1 .. 2^24, got " + std::to_string(tile));
+    if (tile_pad < 0 || tile_pad > (1 << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: tile_pad must be 0 .. 2^24, got " + std::to_string(tile_pad));
+    const int ny = (H + tile - 1) / tile, nx = (W + tile - 1) / tile;
+    *tiles_y = ny, *tiles_x = nx, *win_h = s2_window_side(H, tile, tile_pad), *win_w = s2_window_side(W, tile, tile_pad);
+    if (!plan) return NESR_OK;
+    const size_t need = (size_t)ny * nx * 8;
+    if (capacity < need)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_tile_plan: the plan needs " + std::to_string(need) + " integers, capacity is " + std::to_string(capacity));
+    for (int ty = 0; ty < ny; ++ty)
+        for (int tx = 0; tx < nx; ++tx) {
+            int wy, wx, y0, y1, x0, x1;
+            s2_tile_axis(H, tile, tile_pad, ty, wy, y0, y1);
+            s2_tile_axis(W, tile, tile_pad, tx, wx, x0, x1);
+            int32_t* r = plan + ((size_t)ty * nx + tx) * 8;
+            r[0] = wy, r[1] = wx, r[2] = (y0 - wy) * upscale, r[3] = (x0 - wx) * upscale, r[4] = (y1 - y0) * upscale, r[5] = (x1 - x0) * upscale;
+            r[6] = y0 * upscale, r[7] = x0 * upscale;
+        }
+    return NESR_OK;
+}
+
+int nesr_swin2sr_workspace_bytes(nesr_swin2sr* c, int win_h, int win_w, int batch, size_t* bytes) {
+    if (!c || !bytes) return set_error(NESR_ERR_ARG, "nesr_swin2sr_workspace_bytes: null pointer");
+    if (win_h < 1 || win_w < 1 || (long long)win_h * win_w > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_workspace_bytes: a window (win_h x win_w) of 1 .. 2^24 pixels");
+    if (batch < 1 || batch > 65535) return set_error(NESR_ERR_ARG, "nesr_swin2sr_workspace_bytes: batch must be 1 .. 65535, got " + std::to_string(batch));
+    int mh, mw, H, W;
+    const int rc = padded_size(c, true, win_h, win_w, mh, mw, H, W);
+    if (rc) return rc;
+    size_t act, upb;
+    *bytes = workspace_bytes(c, H, W, batch, act, upb);
+    return NESR_OK;
+}
+
+int nesr_swin2sr_upscale_tiled_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, int W, int tile, int tile_pad, int max_batch, uint8_t* out, size_t capacity,
+                                  void* stream) {
+    if (!c || !rgb || !out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, "nesr_swin2sr_upscale_tiled_u8: weights not finalized (nesr_swin2sr_finalize)");
+    if (c->nin != 3 || c->nout != 3) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: an RGB frame needs num_channels = num_channels_out = 3");
+    if (H < 1 || W < 1 || (long long)H * W > NESR_SWIN2SR_TILED_MAX_PIXELS)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: a frame (H x W) of 1 .. 2^28 pixels");
+    if (tile < 1 || tile > (1 << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: tile must be 1 .. 2^24, got " + std::to_string(tile));
+    if (tile_pad < 0 || tile_pad > (1 << 24))
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: tile_pad must be 0 .. 2^24, got " + std::to_string(tile_pad));
+    const size_t need = (size_t)3 * H * c->scale * W * c->scale;
+    if (capacity < need)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
+    const int sy = s2_window_side(H, tile, tile_pad), sx = s2_window_side(W, tile, tile_pad);
+    if ((long long)sy * sx > (1ll << 24))
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_upscale_tiled_u8: tile + 2 tile_pad gives windows of " + std::to_string(sy) + " x " + std::to_string(sx) +
+                                           ", more than 2^24 pixels");
+    int mh, mw, HP, WP;
+    int rc = padded_size(c, true, sy, sx, mh, mw, HP, WP);      // every window has this shape: the reflect limit holds for all or none
+    if (rc) return rc;
+    const long long ny = (H + tile - 1) / tile, nx = (W + tile - 1) / tile, n = ny * nx;
+    // windows a batch: the caller's, or as many as the budget holds; one at least, and no more than a launch takes
+    size_t act, upb;
+    long long B = max_batch > 0 ? max_batch : std::max<long long>(1, (long long)(NESR_SWIN2SR_TILE_WORKSPACE_BYTES / workspace_bytes(c, HP, WP, 1, act, upb)));
+    B = std::min(B, std::min<long long>(n, 65535));
+    B = std::max<long long>(1, std::min(B, (long long)S2_ROWS_MAX / ((long long)HP * WP)));
+    while (max_batch <= 0 && B > 1 && workspace_bytes(c, HP, WP, (size_t)B, act, upb) > NESR_SWIN2SR_TILE_WORKSPACE_BYTES) --B;
+    NESR_TRY(hipSetDevice(c->device));
+    S2Batch bt;
+    bt.tile = tile, bt.tile_pad = tile_pad, bt.tiles_x = (int)nx, bt.FH = H, bt.FW = W;
+    for (long long t0 = 0; t0 < n; t0 += B) {      // row-major, ceil(n / B) batches, the last one shorter
+        bt.tile0 = (int)t0, bt.B = (int)std::min(B, n - t0);
+        rc = forward(c, rgb, true, sy, sx, out, true, static_cast<hipStream_t>(stream), bt);
+        if (rc) return rc;
+    }
+    return NESR_OK;
 }
 
 int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) {

@@ -1,10 +1,13 @@
 // Internal interface of the Swin2SR path: the nesr_swin2sr_* entries of the C ABI (swin2sr_api.cpp) drive the three kernels of
 // swin2sr.hip.  Not part of the public ABI.
 //
-// Activations are token-major f32 rows [H * W][cs], cs = the width rounded up to 16 (the MFMA tile); the columns past the real
-// width are zero in every buffer.  Every weight matrix is stored transposed and zero padded, Wt[K][N]: K and N multiples of 16
-// (a conv: K = 9 taps x the input width rounded up to 4), so a padded column meets a zero weight row and a padded output column
-// comes out zero.
+// Activations are token-major f32 rows [B][H * W][cs] (B images of one size, one after the other), cs = the width rounded up to
+// 16 (the MFMA tile); the columns past the real width are zero in every buffer.  Every weight matrix is stored transposed and
+// zero padded, Wt[K][N]: K and N multiples of 16 (a conv: K = 9 taps x the input width rounded up to 4), so a padded column
+// meets a zero weight row and a padded output column comes out zero.
+//
+// A launch takes `batch` images of one padded size H x W: the conv and the attention kernel read the image index from
+// blockIdx.z and offset every base by it in size_t; the row kernel sees batch * H * W rows.  batch = 1 is a whole frame.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,8 +16,23 @@ namespace nesr {
 
 constexpr size_t S2_LDS_LIMIT = 160 * 1024;      // LDS of one CU (gfx950); one workgroup may take all of it
 constexpr int S2_BM = 32;                        // token rows of one workgroup of the row kernel
-constexpr int S2_ATTN_THREADS = 512;              // the attention kernel's workgroup: 8 waves, two a SIMD
+constexpr int S2_ROWS_MAX = 0x7fffffff - S2_BM;  // token rows of one launch (batch * H * W): the row index is an int
+constexpr int S2_ATTN_THREADS = 512;             // the attention kernel's workgroup: 8 waves, two a SIMD
 constexpr int S2_CONV_TW = 16, S2_CONV_TH = 4;   // output pixels of one workgroup of the conv kernel: 4 rows of 16
+
+// One axis of the tile plan of a frame of n pixels with cores of T and a context of P a side (nesr_swin2sr_tile_plan, and the
+// conv kernel's frame loader and u8 epilogue, which derive image b's window from its tile index: no table on the device).
+// Every window of the axis is S = min(T + 2 P, n) long; core i is [c0, c1) and its window starts at w0 = clamp(c0 - P, 0, n - S):
+// a window at the edge slides inward instead of shrinking.
+__host__ __device__ inline int s2_window_side(int n, int T, int P) { return T + 2 * P < n ? T + 2 * P : n; }
+__host__ __device__ inline void s2_tile_axis(int n, int T, int P, int i, int& w0, int& c0, int& c1) {
+    const int S = s2_window_side(n, T, P);
+    c0 = i * T;
+    c1 = c0 + T < n ? c0 + T : n;
+    w0 = c0 - P;
+    if (w0 > n - S) w0 = n - S;
+    if (w0 < 0) w0 = 0;
+}
 
 // where the conv's input patch comes from
 enum {
@@ -31,6 +49,7 @@ enum {
 };
 
 struct S2Conv {
+    int batch;                // images in the launch; `in`, `res` and `out` hold them one after the other (but see `tile`)
     int in_mode;
     const void* in;
     int H, W;                 // the conv's domain (its output grid before any shuffle)
@@ -49,9 +68,14 @@ struct S2Conv {
     void* out;
     int cs_out;               // ROWS: row stride
     int oh, ow;               // F32, U8: the crop
+    // tile > 0 (FRAME_U8 and OUT_U8 only): image b is tile tile0 + b, in row-major order, of the plan s2_tile_axis makes of an
+    // FH x FW frame.  FRAME_U8 reads its fh x fw window at the window's origin of `in`, the whole frame (row pitch FW); OUT_U8
+    // writes the tile's core alone, at its place in `out`, the whole FH up x FW up frame.  tile = 0: a u8 frame comes alone
+    // (FH = fh, FW = fw, batch = 1).
+    int tile, tile_pad, tiles_x, tile0, FH, FW, up;
 };
 
-// rows [m][cs] -> (x w1 + b1, gelu) -> (x w2 + b2) -> LayerNorm -> + res -> out; every step optional
+// rows [m][cs] (m = batch * H * W) -> (x w1 + b1, gelu) -> (x w2 + b2) -> LayerNorm -> + res -> out; every step optional
 struct S2Rows {
     int m, c, cs;
     const float* in;
@@ -69,6 +93,7 @@ struct S2Rows {
 
 // one shifted-window attention block: out[token] = in[token] + LayerNorm(dense(attention(window of the token)))
 struct S2Attn {
+    int batch;                // images [H * W][cs] one after the other in `in` and `out`; the shift wraps inside each
     int H, W, ws, shift, heads, d, dp, c, cs;     // d = c / heads, dp = d rounded up to 16
     const float* in;
     float* out;               // may be `in`: a token is read and written by its window's workgroup alone

@@ -8,7 +8,8 @@ implementation of its forward.  ``forward(pixel_values)`` gives the reconstructi
 tensor whose H and W are multiples of the window (transformers itself fails on anything else); ``upscale(frame)`` takes an
 [H, W, 3] uint8 RGB frame of any size and returns the uint8 frame [H s, W s, 3], doing what ``Swin2SRImageProcessor`` and the
 documented post-processing do (/ 255, symmetric padding to (n // 8 + 1) * 8, the model, the crop, clamp, x 255, round).  Both run
-on the ROCm device; calling the object with a uint8 HWC frame is ``upscale``.
+on the ROCm device; calling the object with a uint8 HWC frame is ``upscale``.  ``upscale(frame, tile=T, tile_pad=P)`` cuts a large
+frame into windows of one shape that run as a batch (``tile_plan``), and ``forward_batch`` takes [N, C, H, W].
 
 Supported: upsampler pixelshuffle (x2^n, x3), pixelshuffledirect, nearest+conv (x4); resi_connection "1conv"; patch_size 1;
 qkv_bias True; image_size > window_size; the same number of heads in every stage.  Anything else raises NesrUnsupportedError
@@ -158,16 +159,61 @@ class Swin2SR(_HFNet):
         self.calls += 1
         return out
 
-    def upscale(self, frame, device=None):
+    def forward_batch(self, pixel_values):
+        """pixel_values [N, C, H, W] float32 on the device (N >= 1; H, W multiples of window_size) -> [N, C_out, H s, W s].  The N
+        images go through every launch together; each gets the bits `forward` gives it alone."""
+        x = self._pixel_values(pixel_values)
+        n, ch, h, w = x.shape
+        with torch.cuda.device(x.device):
+            handle = self._context(x.device)
+            out = torch.empty((n, self.config["num_channels_out"]) + self.output_size(h, w), dtype=torch.float32, device=x.device)
+            _invoke("nesr_swin2sr_forward_batch_f32", x.device, handle, (x, n, ch, h, w, out, out.numel()))
+        self.calls += 1
+        return out
+
+    def tile_plan(self, h, w, tile, tile_pad=16):
+        """The plan `upscale(tile=, tile_pad=)` follows on an h x w frame, as the library computes it (needs no device):
+        {"tiles": (tiles_y, tiles_x), "window": (win_h, win_w), "plan": int32 array [tiles, 8]}, a row (win_y, win_x, crop_y, crop_x,
+        crop_h, crop_w, out_y, out_x) per tile in row-major order: the window's origin in the frame, then the core inside the
+        window's output and its place in the result, in output pixels.  Every window has one shape: at the edge it slides inward."""
+        lib, args = _lib.load(), (int(self.config["upscale"]), int(h), int(w), int(tile), int(tile_pad))
+        ty, tx, wh, ww = (ctypes.c_int(0) for _ in range(4))
+        counts = (ctypes.byref(ty), ctypes.byref(tx), ctypes.byref(wh), ctypes.byref(ww))
+        _lib.check(lib.nesr_swin2sr_tile_plan(*args, *counts, None, 0), "nesr_swin2sr_tile_plan")
+        plan = np.zeros((ty.value * tx.value, 8), np.int32)
+        _lib.check(lib.nesr_swin2sr_tile_plan(*args, *counts, plan.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), plan.size), "nesr_swin2sr_tile_plan")
+        return {"tiles": (ty.value, tx.value), "window": (wh.value, ww.value), "plan": plan}
+
+    def workspace_bytes(self, win_h, win_w, batch=1, device=None):
+        """Bytes of workspace a forward of `batch` frames (or windows) of win_h x win_w allocates on the context of `device`."""
+        device = torch.device("cuda" if device is None else device)
+        n = ctypes.c_size_t(0)
+        with torch.cuda.device(device):
+            _invoke("nesr_swin2sr_workspace_bytes", None, self._context(device), (int(win_h), int(win_w), int(batch), ctypes.byref(n)))
+        return n.value
+
+    def upscale(self, frame, device=None, tile=0, tile_pad=16, max_batch=None):
         """[H, W, 3] uint8 RGB frame -> the uint8 frame [H s, W s, 3] on the device.  `frame` is a tensor on the device, or an
-        ndarray, which is copied up once (to `device`, default the current ROCm device)."""
+        ndarray, which is copied up once (to `device`, default the current ROCm device).
+
+        tile = 0: the whole frame at once; the workspace grows with it.  tile = T > 0: the frame is cut into cores of T x T input
+        pixels, each run inside a window of T + 2 tile_pad (see tile_plan), treated exactly as a frame of its own; windows share
+        launches, `max_batch` at a time (None: as many as fit the library's workspace budget).  The result does not depend on
+        max_batch; a frame no larger than T + 2 tile_pad is one window and gives the bits of tile = 0."""
         if isinstance(frame, np.ndarray):
             frame = torch.from_numpy(np.ascontiguousarray(frame)).to(torch.device("cuda") if device is None else torch.device(device))
         frame = self._frame_u8(frame, "upscale", "frame")
         h, w = frame.shape[:2]
+        tile = int(tile)
         with torch.cuda.device(frame.device):
             handle = self._context(frame.device)
-            out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=frame.device)
-            _invoke("nesr_swin2sr_upscale_u8", frame.device, handle, (frame, h, w, out, out.numel()))
+            if tile == 0:
+                out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=frame.device)
+                _invoke("nesr_swin2sr_upscale_u8", frame.device, handle, (frame, h, w, out, out.numel()))
+            else:
+                s = int(self.config["upscale"])
+                out = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=frame.device)
+                _invoke("nesr_swin2sr_upscale_tiled_u8", frame.device, handle,
+                        (frame, h, w, tile, int(tile_pad), 0 if max_batch is None else int(max_batch), out, out.numel()))
         self.calls += 1
         return out
