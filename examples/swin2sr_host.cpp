@@ -3,7 +3,9 @@
 // from a flat float32 file that holds the state dict's tensors in transformers' order, and upscales one raw H x W x 3 RGB u8
 // frame with nesr_swin2sr_upscale_u8 (the image processor's padding, the network, the crop and the quantiser on the device).
 //   hipcc -O2 --offload-arch=gfx950 -I include examples/swin2sr_host.cpp -o build/swin2sr_host -ldl
-//   build/swin2sr_host path/to/libnesr_hip.so weights.f32 in.rgb H W out.rgb
+//   build/swin2sr_host path/to/libnesr_hip.so weights.f32 in.rgb H W out.rgb [fp16]
+// A last argument "fp16" selects the fp16 compute form (nesr_swin2sr_set_dtype(ctx, NESR_DTYPE_F16) between create and finalize:
+// both operands of every GEMM rounded to f16, f32 sums; the call then returns NESR_ERR_RANGE for an activation beyond 65504).
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -26,7 +28,7 @@ struct Entry {
 
 int main(int argc, char** argv) {
     if (argc < 7) {
-        std::fprintf(stderr, "usage: %s libnesr_hip.so weights.f32 in.rgb H W out.rgb\n", argv[0]);
+        std::fprintf(stderr, "usage: %s libnesr_hip.so weights.f32 in.rgb H W out.rgb [fp16]\n", argv[0]);
         return 1;
     }
     const int H = std::atoi(argv[4]), W = std::atoi(argv[5]);
@@ -35,13 +37,14 @@ int main(int argc, char** argv) {
     if (!lib) { std::fprintf(stderr, "dlopen: %s\n", dlerror()); return 2; }
     LOAD(nesr_last_error) LOAD(nesr_version) LOAD(nesr_swin2sr_create) LOAD(nesr_swin2sr_destroy) LOAD(nesr_swin2sr_num_tensors)
     LOAD(nesr_swin2sr_load_weight) LOAD(nesr_swin2sr_finalize) LOAD(nesr_swin2sr_output_size) LOAD(nesr_swin2sr_upscale_u8)
-    LOAD(nesr_swin2sr_kernel_time_ms)
+    LOAD(nesr_swin2sr_kernel_time_ms) LOAD(nesr_swin2sr_set_dtype)
     std::printf("%s\n", p_nesr_version());
 
     const int C = 24, heads = 2, hidden = 48, scale = 2, nf = 64, depths[2] = {2, 2}, num_heads[2] = {heads, heads};
     nesr_swin2sr* ctx = nullptr;
     CHECK(p_nesr_swin2sr_create(&ctx, 0, /*image_size*/ 16, /*patch_size*/ 1, 3, 3, C, 2, depths, num_heads, /*window_size*/ 4, /*mlp_ratio*/ 2.0,
                                 /*qkv_bias*/ 1, /*use_absolute_embeddings*/ 0, /*layer_norm_eps*/ 1e-5, scale, /*img_range*/ 1.0, "1conv", "pixelshuffle"));
+    if (argc > 7 && std::string(argv[7]) == "fp16") CHECK(p_nesr_swin2sr_set_dtype(ctx, NESR_DTYPE_F16));
 
     // the state dict's keys and shapes, in transformers' order
     std::vector<Entry> spec;

@@ -1061,6 +1061,38 @@ enum { NESR_S2_GROUP_CONV = 0, NESR_S2_GROUP_PROJ = 1, NESR_S2_GROUP_ATTENTION =
        NESR_S2_GROUPS = 5 };
 int nesr_swin2sr_set_timing(nesr_swin2sr* ctx, int enable);
 int nesr_swin2sr_kernel_time_ms(nesr_swin2sr* ctx, double* group_ms, int n_groups, int64_t* launches);
+/*
+ * The fp16 compute form.  nesr_swin2sr_set_dtype, between nesr_swin2sr_create and nesr_swin2sr_finalize (NESR_ERR_STATE after it):
+ * NESR_DTYPE_F32 (the default: the path above, unchanged in launches and in bits) or NESR_DTYPE_F16; NESR_DTYPE_BF16 is
+ * NESR_ERR_UNSUPPORTED (eight significand bits cost 0.2 to 0.4 in the logits of cosine attention, whose temperature reaches 100);
+ * any other value is NESR_ERR_ARG.  The dtype is checked before the context.
+ *
+ * NESR_DTYPE_F16: storage in memory stays f32 and so do the activation layout, the workspace and the residual stream.  Every GEMM
+ * takes both operands rounded to f16 (nearest even) with f32 products and sums on v_mfma_f32_16x16x32_f16 (a K tail of 16 on
+ * v_mfma_f32_16x16x16_f16): the 3x3 convs over token rows, the 1x1 projections, q | k | v, q^ k^T (q^, k^ normalised from the f32
+ * q and k with the norm and the quotient in double, then rounded), P V (P the f32 softmax, rounded), output.dense (the context rounded), fc1 and fc2 (the GELU output rounded).
+ * Everything else is the f32 arithmetic of the default form, the frame-loading first convolution included.  The summation order
+ * inside an MFMA is the hardware's.
+ * Range: f16 carries |x| <= 65504.  A weight of one of those GEMMs beyond that (or non-finite) is NESR_ERR_RANGE at
+ * nesr_swin2sr_finalize, before any device call.  An activation that is non-finite or beyond +-65504 when it is rounded raises the
+ * context's range word; the forward entries (and nesr_swin2sr_part_f32) clear the word in front of their launches, wait for the
+ * stream behind them and return NESR_ERR_RANGE then: the output is not valid.  (The f32 form neither waits nor checks.)
+ *
+ * device_id NESR_SWIN2SR_NO_DEVICE gives nesr_swin2sr_create's context without a device: load_weight, set_dtype and finalize do
+ * their host side (the strict loading, the range check, the packing); every entry that would launch is NESR_ERR_STATE.
+ *
+ * nesr_swin2sr_part_f32 runs ONE launch of the context, in its compute form, on the caller's tokens: in_dev [N][H W][C] f32, dense
+ * and of the real width C = embed_dim, -> out_dev of the same shape (capacity counts floats); pitched copies move them into and
+ * out of the padded layout.  NESR_S2_PART_ATTENTION: the attention block of layer `layer` of stage `stage` (shifted by half a
+ * window when `layer` is odd): tokens + LayerNorm(output.dense(attention)).  NESR_S2_PART_MLP: its MLP block: tokens +
+ * LayerNorm(fc2(GELU(fc1(tokens)))).  NESR_S2_PART_STAGE_CONV: the stage's 3x3 convolution, rows to rows (`layer` is ignored).
+ * H and W are multiples of window_size.
+ */
+#define NESR_SWIN2SR_NO_DEVICE (-1)
+enum { NESR_S2_PART_ATTENTION = 0, NESR_S2_PART_MLP = 1, NESR_S2_PART_STAGE_CONV = 2 };
+int nesr_swin2sr_set_dtype(nesr_swin2sr* ctx, int dtype);
+int nesr_swin2sr_part_f32(nesr_swin2sr* ctx, int part, int stage, int layer, const float* in_dev, int N, int H, int W, float* out_dev, size_t capacity,
+                          void* hip_stream);
 
 const char* nesr_last_error(void);
 const char* nesr_version(void);

@@ -181,6 +181,9 @@ SIGNATURES = {
     "nesr_swin2sr_upscale_tiled_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_swin2sr_forward_batch_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_swin2sr_set_timing":(_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_swin2sr_set_dtype": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_swin2sr_part_f32": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                         _c.c_void_p]),
     "nesr_swin2sr_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),

@@ -26,19 +26,60 @@
 // A launch takes a batch of images of one padded size (the tiles of a large frame, nesr_swin2sr_upscale_tiled_u8): the conv and the
 // attention kernel read the image from blockIdx.z and offset their bases by it; zero padding, the cyclic shift and the region mask
 // stay inside the image.  The row kernel sees batch * H * W rows.  A batch of one runs the arithmetic of a whole frame unchanged.
+//
+// The fp16 compute form (nesr_swin2sr_set_dtype, template argument T = f16): storage in memory stays f32, every GEMM takes both
+// operands rounded to f16 (a plain cast: nearest even) and runs on v_mfma_f32_16x16x32_f16, a K tail of 16 on
+// v_mfma_f32_16x16x16_f16; products and sums are f32.  Lane l holds A[row l & 15][k = 8 (l >> 4) + j] and
+// B[k = 8 (l >> 4) + j][col l & 15], j < 8 (j < 4 and 4 (l >> 4) in the tail); the result map is the f32 one.  An A operand is
+// staged in LDS as f16 with k contiguous (one 16-byte load a fragment); the rounding and the range check (elem16.h: a value that is
+// non-finite or beyond 65504 raises the context's range word) happen at that store.  A weight is a second, f16 copy packed
+// [n][K], so a fragment is one 16-byte load as well.  Every K is a multiple of 16 (a conv's input width is padded to 16 with zeros
+// in the patch and in the weights).  Biases, temperature, bias table, mask, softmax, GELU, LayerNorm, residuals and the
+// epilogues are the f32 code (the L2 normalisation of q and k alone is evaluated in double: see s2_attn_f16_kernel); the frame-loading first conv and a row launch without a product run as T = float.
+// The LDS regions keep their f32 sizes: the 16-bit tiles lie inside them (see each kernel).
+#include <type_traits>
+
 #include "swin2sr_api.h"
 
+#include "elem16.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 __attribute__((may_alias)) f16_alias;      // halves written over the f32 values of the same LDS row
+
+template <class T>
+constexpr bool is_f16 = std::is_same<T, f16>::value;
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma4(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma4(f16x4 a, f16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+
+// f32 -> f16 (nearest even) with the range check: `am` keeps the largest |x| pattern this lane rounded
+__device__ __forceinline__ f16 round16(float v, unsigned& am) {
+    am = E16<3>::amax(am, v);
+    return (f16)v;
+}
+// Rounds value j of an LDS row of f32 in place: half j lies over float j / 2.  The row's 8 threads (one wave, in lockstep) read
+// floats 8 it .. 8 it + 7 and then write halves over floats 4 it .. 4 it + 3, which are read already; volatile keeps a thread's
+// loads and stores in program order, and LDS serves a wave's accesses in order.
+__device__ __forceinline__ float load_in_place(const float* row, int j) { return *reinterpret_cast<const volatile float*>(row + j); }
+__device__ __forceinline__ void round_in_place(float* row, int j, float v, unsigned& am) {
+    *(reinterpret_cast<volatile f16_alias*>(row) + j) = round16(v, am);
+}
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
 __device__ __forceinline__ float sum8(float v) {
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 4);
+    return v;
+}
+__device__ __forceinline__ double sum8(double v) {
     v += __shfl_xor(v, 1);
     v += __shfl_xor(v, 2);
     v += __shfl_xor(v, 4);
@@ -68,11 +109,35 @@ __device__ __forceinline__ void mma_n(const float* ap, int a_tile, const float* 
         }
     }
 }
+// The f16 form: ap and bp are the lane's A row and B column (k contiguous in both, 16-byte aligned); steps of 32, then a tail of 16.
+template <int CNT>
+__device__ __forceinline__ void mma_n(const f16* ap, int a_tile, const f16* bp, int, int K, f32x4 (&acc)[4]) {
+    const int g = (threadIdx.x & 63) >> 4;
+    int k = 0;
+    for (; k + 64 <= K; k += 64) {      // two weight fragments in flight
+        const f16x8 b0 = *reinterpret_cast<const f16x8*>(bp + k + 8 * g), b1 = *reinterpret_cast<const f16x8*>(bp + k + 32 + 8 * g);
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) acc[i] = mfma4(*reinterpret_cast<const f16x8*>(ap + i * a_tile + k + 8 * g), b0, acc[i]);
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) acc[i] = mfma4(*reinterpret_cast<const f16x8*>(ap + i * a_tile + k + 32 + 8 * g), b1, acc[i]);
+    }
+    if (k + 32 <= K) {
+        const f16x8 b = *reinterpret_cast<const f16x8*>(bp + k + 8 * g);
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) acc[i] = mfma4(*reinterpret_cast<const f16x8*>(ap + i * a_tile + k + 8 * g), b, acc[i]);
+        k += 32;
+    }
+    if (k < K) {
+        const f16x4 b = *reinterpret_cast<const f16x4*>(bp + k + 4 * g);
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) acc[i] = mfma4(*reinterpret_cast<const f16x4*>(ap + i * a_tile + k + 4 * g), b, acc[i]);
+    }
+}
 
 // D[16 mt][16 nt] = A[16 mt][K] x B[K][16 nt] by the workgroup's waves; A in LDS (row stride lda), B(k, n) = B[k sbk + n sbn] in
-// LDS or memory; K a multiple of 16.  store(row, col, value) gets every element once.
-template <class Store>
-__device__ __forceinline__ void wg_gemm(const float* A, int lda, int mt, int K, const float* B, int sbk, int sbn, int nt, Store store) {
+// LDS or memory; K a multiple of 16.  store(row, col, value) gets every element once.  T = f16: sbk is 1, lda and sbn count halves.
+template <class T, class Store>
+__device__ __forceinline__ void wg_gemm(const T* A, int lda, int mt, int K, const T* B, int sbk, int sbn, int nt, Store store) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nw = blockDim.x >> 6;
     int mch = 4;                                           // m-tiles that share a B fragment; fewer while waves would idle
@@ -84,8 +149,8 @@ __device__ __forceinline__ void wg_gemm(const float* A, int lda, int mt, int K, 
         f32x4 acc[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* ap = A + (m0 * 16 + (lane & 15)) * lda + (lane >> 4);
-        const float* bp = B + (size_t)(lane >> 4) * sbk + (size_t)(ni * 16 + (lane & 15)) * sbn;
+        const T* ap = A + (m0 * 16 + (lane & 15)) * lda + (is_f16<T> ? 0 : lane >> 4);
+        const T* bp = B + (is_f16<T> ? (size_t)0 : (size_t)(lane >> 4) * sbk) + (size_t)(ni * 16 + (lane & 15)) * sbn;
         switch (cnt) {
             case 1: mma_n<1>(ap, 16 * lda, bp, sbk, K, acc); break;
             case 2: mma_n<2>(ap, 16 * lda, bp, sbk, K, acc); break;
@@ -125,11 +190,18 @@ __device__ __forceinline__ int sym_index(int i, int n) {
     return t < n ? t : 2 * n - 1 - t;
 }
 
+// T = f16 (rows and nearest-x2 inputs only): the patch is [6 x 18][cin16 + 8] halves, cin16 = the input width rounded up to 16, and
+// the weights are a.wh [9][coutp][cin16]
+__host__ __device__ inline int conv_cin16(int cin) { return (cin + 15) & ~15; }
+
+template <class T>
 __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
     extern __shared__ float lds[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int x0 = blockIdx.x * S2_CONV_TW, y0 = blockIdx.y * S2_CONV_TH;
-    const int ldp = conv_ldp(a.cinp), nq = a.cinp >> 2;
+    const int cin16 = conv_cin16(a.cin);
+    const int ldp = is_f16<T> ? cin16 + 8 : conv_ldp(a.cinp), nq = is_f16<T> ? cin16 >> 2 : a.cinp >> 2;
+    unsigned am = 0;
     const size_t b = blockIdx.z, px_img = (size_t)a.H * a.W;      // the image of this workgroup; zero padding at its own border
     // image b's window in the frame (wy, wx) and its core inside the window's output [cy0, cy1) x [cx0, cx1); a whole frame: all of it
     int wy = 0, wx = 0, cy0 = 0, cy1 = a.oh, cx0 = 0, cx1 = a.ow;
@@ -150,7 +222,7 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
         const int q = idx % nq, pos = idx / nq, px = pos % CP_W, py = pos / CP_W;
         const int gy = y0 - 1 + py, gx = x0 - 1 + px;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+        if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W && (!is_f16<T> || q * 4 < a.cinp)) {      // f16: zeros from cinp up to cin16
             if (a.in_mode == S2_IN_ROWS) {
                 v = *reinterpret_cast<const float4*>(in_rows + ((size_t)gy * a.W + gx) * a.cs_in + q * 4);
             } else if (a.in_mode == S2_IN_NEAREST2) {
@@ -171,8 +243,14 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
                 v = make_float4(e[0], e[1], e[2], e[3]);
             }
         }
-        *reinterpret_cast<float4*>(lds + (py * CP_W + px) * ldp + q * 4) = v;
+        if constexpr (is_f16<T>) {
+            const f16x4 h = {round16(v.x, am), round16(v.y, am), round16(v.z, am), round16(v.w, am)};
+            *reinterpret_cast<f16x4*>(reinterpret_cast<f16*>(lds) + (py * CP_W + px) * ldp + q * 4) = h;
+        } else {
+            *reinterpret_cast<float4*>(lds + (py * CP_W + px) * ldp + q * 4) = v;
+        }
     }
+    if constexpr (is_f16<T>) raise_range(a.status, am);
     __syncthreads();
 
     const int r2 = a.shuffle * a.shuffle, ncc = a.cout / r2;
@@ -187,6 +265,12 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
         for (int i = 0; i < S2_CONV_TH; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int tap = 0; tap < 9; ++tap) {
             const int ky = tap / 3, kx = tap - ky * 3;
+            if constexpr (is_f16<T>) {      // one accumulator per pixel row as below; K = cin16 a tap
+                const f16* ap = reinterpret_cast<const f16*>(lds) + (ky * CP_W + (lane & 15) + kx) * ldp;
+                const f16* bp = static_cast<const f16*>(a.wh) + ((size_t)tap * a.coutp + ni * 16 + (lane & 15)) * cin16;
+                mma_n<S2_CONV_TH>(ap, CP_W * ldp, bp, 1, cin16, acc);
+                continue;
+            }
             const float* ap = lds + (ky * CP_W + (lane & 15) + kx) * ldp + (lane >> 4);
             const float* bp = a.w + (size_t)(tap * a.cinp + (lane >> 4)) * a.coutp + ni * 16 + (lane & 15);
             int c = 0;
@@ -244,6 +328,10 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- token rows
+// T = f16 (a launch with w1): the input tile is [32][cs + 8] halves at the head of A's region and, with w2, the GELU output
+// [32][n1p + 8] halves at the head of Hb's; the last product's result is f32 in its f32 place (A's tile is dead by then).  The
+// weights are a.w1h [n1p][cs] and a.w2h [cs][n1p].
+template <class T>
 __global__ __launch_bounds__(256) void s2_rows_kernel(const S2Rows a) {
     extern __shared__ float lds[];
     const int lda = a.cs + 4, ldh = a.n1p + 4;
@@ -252,12 +340,42 @@ __global__ __launch_bounds__(256) void s2_rows_kernel(const S2Rows a) {
     const int t = threadIdx.x, r8 = t >> 3, s8 = t & 7;
     const int row0 = blockIdx.x * S2_BM, grow = row0 + r8;
     const bool live = grow < a.m;
+    float* cur = A;
+    int ldcur = lda;
 
+    if constexpr (is_f16<T>) {
+        f16* Ah = reinterpret_cast<f16*>(A);
+        f16* Hh = reinterpret_cast<f16*>(Hb);
+        const int ldah = a.cs + 8, ldhh = a.n1p + 8;
+        unsigned am = 0;
+        for (int c = s8 * 4; c < a.cs; c += 32) {
+            const float4 v = live ? *reinterpret_cast<const float4*>(a.in + (size_t)grow * a.cs + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const f16x4 h = {round16(v.x, am), round16(v.y, am), round16(v.z, am), round16(v.w, am)};
+            *reinterpret_cast<f16x4*>(Ah + r8 * ldah + c) = h;
+        }
+        __syncthreads();
+        const float* b1 = a.b1;
+        const int gelu = a.gelu;
+        const bool second = a.w2 != nullptr;
+        wg_gemm(Ah, ldah, S2_BM / 16, a.cs, static_cast<const f16*>(a.w1h), 1, a.cs, a.n1p >> 4, [&](int i, int j, float v) {
+            v += b1[j];
+            if (gelu) v = gelu_erf(v);
+            if (second) Hh[i * ldhh + j] = round16(v, am);
+            else Hb[i * ldh + j] = v;
+        });
+        __syncthreads();
+        cur = Hb, ldcur = ldh;
+        if (second) {
+            const float* b2 = a.b2;
+            wg_gemm(Hh, ldhh, S2_BM / 16, a.n1p, static_cast<const f16*>(a.w2h), 1, a.n1p, a.cs >> 4, [=](int i, int j, float v) { A[i * lda + j] = v + b2[j]; });
+            __syncthreads();
+            cur = A, ldcur = lda;
+        }
+        raise_range(a.status, am);
+    } else {
     for (int c = s8 * 4; c < a.cs; c += 32)
         *reinterpret_cast<float4*>(A + r8 * lda + c) = live ? *reinterpret_cast<const float4*>(a.in + (size_t)grow * a.cs + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     __syncthreads();
-    float* cur = A;
-    int ldcur = lda;
     if (a.w1) {
         const float* b1 = a.b1;
         const int gelu = a.gelu;
@@ -273,6 +391,7 @@ __global__ __launch_bounds__(256) void s2_rows_kernel(const S2Rows a) {
             __syncthreads();
             cur = A, ldcur = lda;
         }
+    }
     }
     float* rp = cur + r8 * ldcur;
     float mean = 0.f, rstd = 1.f;
@@ -395,6 +514,137 @@ __global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_kernel(const S2Attn a
     }
 }
 
+// The fp16 form of the block above, inside the same LDS regions: X's holds the tokens [np][cs + 8] halves and, at the end,
+// output.dense's f32 result; CTX's the context [np][cs + 8] halves; QKV's one head's q | k as f32 [np][2 dp + 4], normalised
+// and rounded in place (q^ at half 0 of the row, k^ at half 2 dp), then V^T [dp][np + 8] halves; S's the f32 scores, whose softmax
+// is rounded in place (P at half 0 of the row).  The weights are a.wqkvh [heads 3 dp][cs] and a.woh [cs][cs].
+__global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_f16_kernel(const S2Attn a) {
+    extern __shared__ float lds[];
+    const int n = a.ws * a.ws, np = (n + 15) & ~15, mt = np >> 4;
+    const int ldc = a.cs + 4, ldq = 3 * a.dp + 4, lds_s = np + 4;
+    float* X = lds;
+    float* CTX = X + np * ldc;
+    float* QK = CTX + np * ldc;
+    float* S = QK + np * ldq;
+    int* tok = reinterpret_cast<int*>(S + np * lds_s);
+    int* reg = tok + np;
+    const int ldxh = a.cs + 8, ldqk = 2 * a.dp + 4, ldv = np + 8;
+    f16* Xh = reinterpret_cast<f16*>(X);
+    f16* CTXh = reinterpret_cast<f16*>(CTX);
+    f16* Vt = reinterpret_cast<f16*>(QK + np * ldqk);      // np (2 dp + 4) floats + dp (np + 8) halves <= np (3 dp + 4) floats for np >= 8
+    const f16* QKh = reinterpret_cast<const f16*>(QK);
+    const f16* Ph = reinterpret_cast<const f16*>(S);
+    const int t = threadIdx.x, r8 = t >> 3, s8 = t & 7, rpp = S2_ATTN_THREADS / 8;
+    const size_t img = (size_t)blockIdx.z * a.H * a.W * a.cs;
+    const float* in = a.in + img;
+    float* out = a.out + img;
+    unsigned am = 0;
+
+    for (int i = t; i < np; i += S2_ATTN_THREADS) {
+        int tk = -1, rg = -1;
+        if (i < n) {
+            const int iy = i / a.ws, ry = blockIdx.y * a.ws + iy, rx = blockIdx.x * a.ws + (i - iy * a.ws);
+            tk = ((ry + a.shift) % a.H) * a.W + (rx + a.shift) % a.W;
+            rg = a.shift > 0 ? region_of(ry, a.H, a.ws, a.shift) * 3 + region_of(rx, a.W, a.ws, a.shift) : 0;
+        }
+        tok[i] = tk, reg[i] = rg;
+    }
+    __syncthreads();
+    for (int i = r8; i < np; i += rpp) {
+        const int tk = tok[i];
+        for (int c = s8 * 4; c < a.cs; c += 32) {
+            const float4 v = tk >= 0 ? *reinterpret_cast<const float4*>(in + (size_t)tk * a.cs + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const f16x4 h = {round16(v.x, am), round16(v.y, am), round16(v.z, am), round16(v.w, am)};
+            *reinterpret_cast<f16x4*>(Xh + i * ldxh + c) = h;
+            *reinterpret_cast<f16x4*>(CTXh + i * ldxh + c) = f16x4{(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+        }
+    }
+    __syncthreads();
+
+    for (int h = 0; h < a.heads; ++h) {
+        {   // q | k as f32, v rounded and transposed
+            const float* bq = a.bqkv + h * 3 * a.dp;
+            const int dp2 = 2 * a.dp;
+            wg_gemm(Xh, ldxh, mt, a.cs, static_cast<const f16*>(a.wqkvh) + (size_t)h * 3 * a.dp * a.cs, 1, a.cs, (3 * a.dp) >> 4, [&](int i, int j, float v) {
+                v += bq[j];
+                if (j < dp2) QK[i * ldqk + j] = v;
+                else Vt[(j - dp2) * ldv + i] = round16(v, am);
+            });
+        }
+        __syncthreads();
+        // x / max(|x|, 1e-12) of the f32 q and k, rounded over the row's own values.  The norm and the quotient are evaluated in
+        // double, so q^ carries one rounding, not the four of the f32 chain (squares, sum, root, quotient): a q^ within those
+        // 1.5 ulp of an f16 rounding boundary would round the other way, and the temperature multiplies that f16 ulp by up to 100.
+        for (int i = r8; i < np; i += rpp) {
+            for (int part = 0; part < 2; ++part) {
+                float* p = QK + i * ldqk + part * a.dp;
+                double ss = 0.0;
+                for (int j = s8; j < a.dp; j += 8) {
+                    const double v = p[j];
+                    ss += v * v;
+                }
+                const double inv = 1.0 / fmax(sqrt(sum8(ss)), 1e-12);
+                for (int j = s8; j < a.dp; j += 8) round_in_place(p, j, (float)(load_in_place(p, j) * inv), am);
+            }
+        }
+        __syncthreads();
+        {
+            const float sc = a.scale[h];
+            const float* bias = a.bias + (size_t)h * n * n;
+            const int shift = a.shift;
+            wg_gemm(QKh, 2 * ldqk, mt, a.dp, QKh + 2 * a.dp, 1, 2 * ldqk, mt, [=](int i, int j, float v) {
+                float s = -INFINITY;
+                if (j < n) {
+                    s = v * sc;
+                    if (i < n) s += bias[i * n + j];
+                    if (shift > 0 && i < n && reg[i] != reg[j]) s = (s + -100.0f) + -100.0f;
+                }
+                S[i * lds_s + j] = s;
+            });
+        }
+        __syncthreads();
+        for (int i = r8; i < np; i += rpp) {
+            float* sp = S + i * lds_s;
+            float m = -INFINITY;
+            for (int j = s8; j < np; j += 8) m = fmaxf(m, sp[j]);
+            m = max8(m);
+            float sum = 0.f;
+            for (int j = s8; j < np; j += 8) {
+                const float p = expf(sp[j] - m);
+                sp[j] = p;
+                sum += p;
+            }
+            sum = sum8(sum);
+            for (int j = s8; j < np; j += 8) round_in_place(sp, j, load_in_place(sp, j) / sum, am);
+        }
+        __syncthreads();
+        {   // context[:, head] = P V, rounded for output.dense
+            const int d = a.d, col0 = h * a.d;
+            wg_gemm(Ph, 2 * lds_s, mt, np, Vt, 1, ldv, a.dp >> 4, [&](int i, int j, float v) {
+                if (j < d) CTXh[i * ldxh + col0 + j] = round16(v, am);
+            });
+        }
+        __syncthreads();
+    }
+
+    {   // output.dense -> X (f32; the tokens' halves are dead)
+        const float* bo = a.bo;
+        wg_gemm(CTXh, ldxh, mt, a.cs, static_cast<const f16*>(a.woh), 1, a.cs, a.cs >> 4, [=](int i, int j, float v) { X[i * ldc + j] = v + bo[j]; });
+    }
+    raise_range(a.status, am);
+    __syncthreads();
+    for (int i = r8; i < np; i += rpp) {
+        const int tk = tok[i];
+        float mean, rstd;
+        row_stats(X + i * ldc, a.c, s8, a.eps, mean, rstd);
+        if (tk < 0) continue;
+        for (int j = s8; j < a.cs; j += 8) {
+            const float v = (X[i * ldc + j] - mean) * rstd * a.ln_g[j] + a.ln_b[j];
+            out[(size_t)tk * a.cs + j] = in[(size_t)tk * a.cs + j] + v;
+        }
+    }
+}
+
 template <class K, class A>
 hipError_t launch_lds(K kernel, const A& a, dim3 grid, int threads, size_t bytes, unsigned long long& done, hipStream_t s) {
     if (bytes > S2_LDS_LIMIT) return hipErrorInvalidValue;
@@ -406,7 +656,11 @@ hipError_t launch_lds(K kernel, const A& a, dim3 grid, int threads, size_t bytes
 
 }  // namespace
 
-size_t s2_conv_lds_bytes(const S2Conv& a) { return (size_t)CP_H * CP_W * conv_ldp(a.cinp) * sizeof(float); }
+// f16: [6 x 18][cin16 + 8] halves, which is no more than the f32 patch from 20 input channels on (a few KiB below that)
+size_t s2_conv_lds_bytes(const S2Conv& a) {
+    if (a.f16) return (size_t)CP_H * CP_W * (conv_cin16(a.cin) + 8) * sizeof(f16);
+    return (size_t)CP_H * CP_W * conv_ldp(a.cinp) * sizeof(float);
+}
 
 size_t s2_rows_lds_bytes(const S2Rows& a) { return (size_t)S2_BM * ((a.cs + 4) + (a.w1 ? a.n1p + 4 : 0)) * sizeof(float); }
 
@@ -450,10 +704,14 @@ hipError_t launch_s2_conv(const S2Conv& a, hipStream_t s) {
     } else if ((u8_in || u8_out) && a.batch != 1) {
         return hipErrorInvalidValue;      // u8 frames come one at a time, or as the tiles of one
     }
-    static unsigned long long done = 0;
+    static unsigned long long done = 0, done16 = 0;
     const dim3 grid((a.W + S2_CONV_TW - 1) / S2_CONV_TW, (a.H + S2_CONV_TH - 1) / S2_CONV_TH, a.batch);
     if (grid.y > 65535u) return hipErrorInvalidValue;
-    return launch_lds(&s2_conv_kernel, a, grid, 256, s2_conv_lds_bytes(a), done, s);
+    if (a.f16) {      // token rows in, both operands rounded; a frame-loading conv is never asked for in this form
+        if (!a.wh || !a.status || (a.in_mode != S2_IN_ROWS && a.in_mode != S2_IN_NEAREST2)) return hipErrorInvalidValue;
+        return launch_lds(&s2_conv_kernel<f16>, a, grid, 256, s2_conv_lds_bytes(a), done16, s);
+    }
+    return launch_lds(&s2_conv_kernel<float>, a, grid, 256, s2_conv_lds_bytes(a), done, s);
 }
 
 hipError_t launch_s2_rows(const S2Rows& a, hipStream_t s) {
@@ -462,8 +720,12 @@ hipError_t launch_s2_rows(const S2Rows& a, hipStream_t s) {
     if (a.w2 && (!a.w1 || !a.b2)) return hipErrorInvalidValue;
     if (a.ln_g && !a.ln_b) return hipErrorInvalidValue;
     if (a.m > S2_ROWS_MAX) return hipErrorInvalidValue;      // the row index (and m + 31) stays an int; row x cs is size_t in the kernel
-    static unsigned long long done = 0;
-    return launch_lds(&s2_rows_kernel, a, dim3((a.m + S2_BM - 1) / S2_BM), 256, s2_rows_lds_bytes(a), done, s);
+    static unsigned long long done = 0, done16 = 0;
+    if (a.f16 && a.w1) {      // a launch without a product has nothing to round
+        if (!a.w1h || (a.w2 && !a.w2h) || !a.status) return hipErrorInvalidValue;
+        return launch_lds(&s2_rows_kernel<f16>, a, dim3((a.m + S2_BM - 1) / S2_BM), 256, s2_rows_lds_bytes(a), done16, s);
+    }
+    return launch_lds(&s2_rows_kernel<float>, a, dim3((a.m + S2_BM - 1) / S2_BM), 256, s2_rows_lds_bytes(a), done, s);
 }
 
 hipError_t launch_s2_attn(const S2Attn& a, hipStream_t s) {
@@ -471,9 +733,13 @@ hipError_t launch_s2_attn(const S2Attn& a, hipStream_t s) {
     if (a.ws < 1 || a.H < a.ws || a.W < a.ws || a.H % a.ws || a.W % a.ws || a.shift < 0 || a.shift >= a.ws) return hipErrorInvalidValue;
     if (a.heads < 1 || a.d < 1 || a.c != a.heads * a.d || a.dp % 16 || a.dp < a.d || a.cs % 16 || a.cs < a.c) return hipErrorInvalidValue;
     if (a.batch < 1 || a.batch > 65535) return hipErrorInvalidValue;
-    static unsigned long long done = 0;
+    static unsigned long long done = 0, done16 = 0;
     const dim3 grid(a.W / a.ws, a.H / a.ws, a.batch);
     if (grid.y > 65535u) return hipErrorInvalidValue;
+    if (a.f16) {
+        if (!a.wqkvh || !a.woh || !a.status) return hipErrorInvalidValue;
+        return launch_lds(&s2_attn_f16_kernel, a, grid, S2_ATTN_THREADS, s2_attn_lds_bytes(a), done16, s);
+    }
     return launch_lds(&s2_attn_kernel, a, grid, S2_ATTN_THREADS, s2_attn_lds_bytes(a), done, s);
 }
 

@@ -14,17 +14,19 @@ using namespace nesr;
 
 namespace {
 
+// offsets in floats into the packed f32 weights; the ...h ones in halves into the f16 copy of the fp16 form
 struct S2ConvW {
-    size_t w = 0, b = 0;
+    size_t w = 0, b = 0, wh = 0;
     int cin = 0, cinp = 0, cout = 0, coutp = 0;
 };
 struct S2LayerW {
     size_t wqkv, bqkv, scale, bias, wo, bo, ln1g, ln1b, w1, b1, w2, b2, ln2g, ln2b;
+    size_t wqkvh = 0, woh = 0, w1h = 0, w2h = 0;
 };
 struct S2StageW {
     std::vector<S2LayerW> layers;
     S2ConvW conv;
-    size_t wproj, bproj;
+    size_t wproj, bproj, wprojh = 0;
 };
 
 enum { UP_PIXELSHUFFLE = 0, UP_DIRECT = 1, UP_NEAREST = 2 };
@@ -42,10 +44,15 @@ struct nesr_swin2sr {
     float eps = 1e-5f, range = 1.f, mean[4] = {0.f, 0.f, 0.f, 0.f};
     StateDict sd;
     bool finalized = false;
+    int dtype = NESR_DTYPE_F32;      // the compute form (nesr_swin2sr_set_dtype)
+    bool packed = false;             // finalize has run: the form is fixed
     float* d_w = nullptr;
+    _Float16* d_wh = nullptr;        // the fp16 form's second copy of every GEMM weight, [n][K]
+    unsigned* d_status = nullptr;    // the fp16 form's range word
+    unsigned* h_status = nullptr;
     S2ConvW first, after, before, up1, up2, hr, fin, direct;
     std::vector<S2ConvW> ups;
-    size_t wpe = 0, bpe = 0, peg = 0, peb = 0, lng = 0, lnb = 0;
+    size_t wpe = 0, bpe = 0, peg = 0, peb = 0, lng = 0, lnb = 0, wpeh = 0;
     std::vector<S2StageW> stages;
     char* ws_buf = nullptr;
     size_t ws_bytes = 0;
@@ -80,7 +87,60 @@ S2Conv conv_args(const nesr_swin2sr* c, const S2ConvW& w, const float* in, int H
     for (int i = 0; i < 4; ++i) a.mean[i] = c->mean[i];
     a.w = c->d_w + w.w, a.bias = c->d_w + w.b, a.cout = w.cout, a.coutp = w.coutp;
     a.shuffle = 1, a.out_mode = S2_OUT_ROWS, a.out = out, a.cs_out = cs_out;
+    if (c->dtype == NESR_DTYPE_F16 && w.cin > 4) a.f16 = 1, a.wh = c->d_wh + w.wh, a.status = c->d_status;      // not the frame's conv (K = 4 a tap)
     return a;
+}
+
+bool f16_form(const nesr_swin2sr* c) { return c->dtype == NESR_DTYPE_F16; }
+
+// layer j's attention block over B images of H x W tokens
+S2Attn attn_args(const nesr_swin2sr* c, const S2LayerW& L, int j, const float* in, float* out, int B, int H, int W) {
+    S2Attn a = attn_shape(c);
+    const float* w = c->d_w;
+    a.batch = B, a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0, a.in = in, a.out = out;
+    a.wqkv = w + L.wqkv, a.bqkv = w + L.bqkv, a.scale = w + L.scale, a.bias = w + L.bias, a.wo = w + L.wo, a.bo = w + L.bo;
+    a.ln_g = w + L.ln1g, a.ln_b = w + L.ln1b, a.eps = c->eps;
+    if (f16_form(c)) a.f16 = 1, a.wqkvh = c->d_wh + L.wqkvh, a.woh = c->d_wh + L.woh, a.status = c->d_status;
+    return a;
+}
+
+// a row launch over M tokens: an optional product (w1 at offset w1, (size_t)-1 for none; its f16 copy at w1h), LayerNorm, residual
+S2Rows rows_args(const nesr_swin2sr* c, int M, const float* in, size_t w1, size_t b1, size_t w1h, bool ln, size_t g, size_t b, float eps, const float* res,
+                 float* o) {
+    S2Rows a;
+    memset(&a, 0, sizeof(a));
+    a.m = M, a.c = c->C, a.cs = c->cs, a.in = in;
+    if (w1 != (size_t)-1) {
+        a.w1 = c->d_w + w1, a.b1 = c->d_w + b1, a.n1p = c->cs;
+        if (f16_form(c)) a.f16 = 1, a.w1h = c->d_wh + w1h, a.status = c->d_status;
+    }
+    if (ln) a.ln_g = c->d_w + g, a.ln_b = c->d_w + b, a.eps = eps;
+    a.res = res, a.out = o;
+    return a;
+}
+
+// layer L's MLP block, in place on X
+S2Rows mlp_args(const nesr_swin2sr* c, const S2LayerW& L, int M, float* X) {
+    S2Rows a = rows_args(c, M, X, L.w1, L.b1, L.w1h, true, L.ln2g, L.ln2b, c->eps, X, X);
+    a.n1p = c->hidp, a.gelu = 1, a.w2 = c->d_w + L.w2, a.b2 = c->d_w + L.b2;
+    if (f16_form(c)) a.w2h = c->d_wh + L.w2h;
+    return a;
+}
+
+// The fp16 form's range word: cleared in front of a call's launches, read behind them (the stream is waited for).
+int range_begin(nesr_swin2sr* c, hipStream_t s) {
+    if (!f16_form(c)) return NESR_OK;
+    NESR_TRY(hipMemsetAsync(c->d_status, 0, sizeof(unsigned), s));
+    return NESR_OK;
+}
+int range_end(nesr_swin2sr* c, hipStream_t s, const char* entry) {
+    if (!f16_form(c)) return NESR_OK;
+    NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    NESR_TRY(hipStreamSynchronize(s));
+    if (*c->h_status)
+        return set_error(NESR_ERR_RANGE, std::string(entry) + ": an activation of the fp16 form was non-finite or exceeded 65504 in magnitude when it was "
+                                             "rounded; the output is not valid (the f32 form carries such values)");
+    return NESR_OK;
 }
 
 // The images of one forward: B of them, each fh x fw.  tile = 0: they lie one after the other in `frame` and in `out` (f32), or
@@ -106,7 +166,7 @@ size_t workspace_bytes(const nesr_swin2sr* c, int H, int W, size_t B, size_t& ac
 }
 
 // frame: u8 HWC [fh][fw][3] (processor route) or f32 NCHW [nin][fh][fw] (model route); out: f32 NCHW or u8 HWC, cropped to fh s x fw s
-int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt = S2Batch()) {
+int forward_launches(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt) {
     int mh, mw, H, W;
     int rc = padded_size(c, frame_u8, fh, fw, mh, mw, H, W);
     if (rc) return rc;
@@ -132,8 +192,7 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     float* T1 = reinterpret_cast<float*>(c->ws_buf + 3 * act);
     float* UA = reinterpret_cast<float*>(c->ws_buf + 4 * act);
     float* UB = reinterpret_cast<float*>(c->ws_buf + 4 * act + upb);
-    auto wt = [&](size_t off) { return c->d_w + off; };
-    const int M = (int)T, C = c->C, CS = c->cs;
+    const int M = (int)T, CS = c->cs;
 
     {   // first_convolution on the padded, normalised frame -> FIRST (the long residual)
         S2Conv a = conv(c->first, nullptr, H, W, 0, FIRST, CS);
@@ -141,17 +200,8 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         tiled(a);
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
-    auto rows = [&](const float* in, size_t w1, size_t b1, bool ln, size_t g, size_t b, float eps, const float* res, float* o) {
-        S2Rows a;
-        memset(&a, 0, sizeof(a));
-        a.m = M, a.c = C, a.cs = CS, a.in = in;
-        if (w1 != (size_t)-1) a.w1 = wt(w1), a.b1 = wt(b1), a.n1p = CS;
-        if (ln) a.ln_g = wt(g), a.ln_b = wt(b), a.eps = eps;
-        a.res = res, a.out = o;
-        return a;
-    };
     {   // patch embedding: 1x1 projection + LayerNorm (torch's default eps) -> XS
-        const S2Rows a = rows(FIRST, c->wpe, c->bpe, true, c->peg, c->peb, 1e-5f, nullptr, XS);
+        const S2Rows a = rows_args(c, M, FIRST, c->wpe, c->bpe, c->wpeh, true, c->peg, c->peb, 1e-5f, nullptr, XS);
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
     }
     for (int i = 0; i < c->nst; ++i) {
@@ -159,16 +209,11 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
         for (int j = 0; j < c->depth[i]; ++j) {
             const S2LayerW& L = S.layers[j];
             {
-                S2Attn a = attn_shape(c);
-                a.batch = bt.B, a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0;
-                a.in = j == 0 ? XS : X, a.out = X;      // the stage's input stays in XS
-                a.wqkv = wt(L.wqkv), a.bqkv = wt(L.bqkv), a.scale = wt(L.scale), a.bias = wt(L.bias), a.wo = wt(L.wo), a.bo = wt(L.bo);
-                a.ln_g = wt(L.ln1g), a.ln_b = wt(L.ln1b), a.eps = c->eps;
+                const S2Attn a = attn_args(c, L, j, j == 0 ? XS : X, X, bt.B, H, W);      // the stage's input stays in XS
                 NESR_RUN(c->timer, kName, NESR_S2_GROUP_ATTENTION, s, [&] { return launch_s2_attn(a, s); });
             }
             {
-                S2Rows a = rows(X, L.w1, L.b1, true, L.ln2g, L.ln2b, c->eps, X, X);
-                a.n1p = c->hidp, a.gelu = 1, a.w2 = wt(L.w2), a.b2 = wt(L.b2);
+                const S2Rows a = mlp_args(c, L, M, X);
                 NESR_RUN(c->timer, kName, NESR_S2_GROUP_MLP, s, [&] { return launch_s2_rows(a, s); });
             }
         }
@@ -177,12 +222,12 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
             NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
         }
         {   // the stage's 1x1 projection + the stage's input, in place
-            const S2Rows a = rows(T1, S.wproj, S.bproj, false, 0, 0, 0.f, XS, XS);
+            const S2Rows a = rows_args(c, M, T1, S.wproj, S.bproj, S.wprojh, false, 0, 0, 0.f, XS, XS);
             NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
         }
     }
     {   // the encoder's LayerNorm -> X
-        const S2Rows a = rows(XS, (size_t)-1, 0, true, c->lng, c->lnb, c->eps, nullptr, X);
+        const S2Rows a = rows_args(c, M, XS, (size_t)-1, 0, 0, true, c->lng, c->lnb, c->eps, nullptr, X);
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_PROJ, s, [&] { return launch_s2_rows(a, s); });
     }
     {   // conv_after_body + the long residual -> T1
@@ -236,6 +281,13 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     finish(a);
     NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_conv(a, s); });
     return NESR_OK;
+}
+
+// the launches between the range word's reset and its check (fp16 form: the call waits for the stream and may return NESR_ERR_RANGE)
+int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt = S2Batch()) {
+    int rc = range_begin(c, s);
+    if (!rc) rc = forward_launches(c, frame, frame_u8, fh, fw, out, out_u8, s, bt);
+    return rc ? rc : range_end(c, s, kName);
 }
 
 }  // namespace
@@ -297,8 +349,8 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
         }
     }
     int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || device_id < 0 || device_id >= ndev) {
+    hipError_t e = device_id == NESR_SWIN2SR_NO_DEVICE ? hipSuccess : hipGetDeviceCount(&ndev);      // no device: the host side alone
+    if (device_id != NESR_SWIN2SR_NO_DEVICE && (e != hipSuccess || device_id < 0 || device_id >= ndev)) {
         delete c;
         if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
         return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
@@ -350,12 +402,29 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
 
 void nesr_swin2sr_destroy(nesr_swin2sr* c) {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    c->timer.destroy();
-    if (c->ws_buf) (void)hipFree(c->ws_buf);
-    if (c->d_w) (void)hipFree(c->d_w);
+    if (c->device != NESR_SWIN2SR_NO_DEVICE) {
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        c->timer.destroy();
+        if (c->ws_buf) (void)hipFree(c->ws_buf);
+        if (c->d_w) (void)hipFree(c->d_w);
+        if (c->d_wh) (void)hipFree(c->d_wh);
+        if (c->d_status) (void)hipFree(c->d_status);
+        if (c->h_status) (void)hipHostFree(c->h_status);
+    }
     delete c;
+}
+
+int nesr_swin2sr_set_dtype(nesr_swin2sr* c, int dtype) {
+    if (dtype == NESR_DTYPE_BF16)
+        return set_error(NESR_ERR_UNSUPPORTED, "nesr_swin2sr_set_dtype: bf16 is not a form of Swin2SR: cosine attention multiplies a product of unit vectors by a "
+                                               "temperature of up to 100, and bf16's 8 significand bits cost 0.2 to 0.4 in the logits; NESR_DTYPE_F16 is the 16-bit form");
+    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_F16)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_set_dtype: dtype must be NESR_DTYPE_F32 or NESR_DTYPE_F16, got " + std::to_string(dtype));
+    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_set_dtype: null context");
+    if (c->packed) return set_error(NESR_ERR_STATE, "nesr_swin2sr_set_dtype: the compute form is chosen between nesr_swin2sr_create and nesr_swin2sr_finalize");
+    c->dtype = dtype;
+    return NESR_OK;
 }
 
 int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return c ? (int)c->sd.size() : 0; }
@@ -379,10 +448,31 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
     HostPack pk;
     auto vec = [&](const std::string& key, int padded) { return pk.vec(sd.data(key), padded); };
     // torch's Linear / 1x1 conv weight [n][k] -> Wt[round16(k)][round16(n)]
-    auto linear = [&](const std::string& key, int n, int k) {
+    // The fp16 form's second copy of a GEMM weight: hh[at + o * kp + kk] = f16(w[o][kk]), rows and columns zero padded; a lane's
+    // fragment (8 k of one output) is one 16-byte load.  A value f16 cannot carry is remembered by its key.
+    const bool f16 = c->dtype == NESR_DTYPE_F16;
+    std::vector<_Float16> hh;
+    std::string out_of_range;
+    auto reserve_h = [&](size_t halves) {
+        const size_t at = hh.size();
+        hh.resize((at + halves + 63) / 64 * 64, (_Float16)0.f);
+        return at;
+    };
+    auto to_h = [&](const std::string& key, float v) {
+        if (!(std::fabs(v) <= 65504.0f) && out_of_range.empty()) out_of_range = key;
+        return (_Float16)v;
+    };
+    auto linear = [&](const std::string& key, int n, int k, size_t* h) {
         const int np = round_up(n, 16);
         const size_t at = pk.reserve((size_t)round_up(k, 16) * np);
         pk.transpose_into(at, sd.data(key), n, k, np, 0);
+        if (f16) {
+            const int kp = round_up(k, 16);
+            const std::vector<float>& w = sd.data(key);
+            *h = reserve_h((size_t)np * kp);
+            for (int o = 0; o < n; ++o)
+                for (int kk = 0; kk < k; ++kk) hh[*h + (size_t)o * kp + kk] = to_h(key, w[(size_t)o * k + kk]);
+        }
         return at;
     };
     // conv weight [n][cin][3][3] -> Wt[(tap * cinp + ci)][coutp]
@@ -391,6 +481,15 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
         r.cin = cin, r.cinp = round_up(cin, 4), r.cout = n, r.coutp = round_up(n, 16);
         r.w = pk.conv_taps(sd.data(name + ".weight"), n, cin, 9, r.cinp, r.coutp);
         r.b = vec(name + ".bias", r.coutp);
+        if (f16 && cin > 4) {      // [tap][coutp][cin rounded up to 16]
+            const int c16 = round_up(cin, 16);
+            const std::string wkey = name + ".weight";
+            const std::vector<float>& w = sd.data(wkey);
+            r.wh = reserve_h((size_t)9 * r.coutp * c16);
+            for (int o = 0; o < n; ++o)
+                for (int ci = 0; ci < cin; ++ci)
+                    for (int t = 0; t < 9; ++t) hh[r.wh + ((size_t)t * r.coutp + o) * c16 + ci] = to_h(wkey, w[((size_t)o * cin + ci) * 9 + t]);
+        }
         return r;
     };
     const int C = c->C, CS = c->cs, ws = c->ws, n = ws * ws, heads = c->heads, d = c->d, dp = c->dp;
@@ -410,7 +509,7 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
 
     c->first = conv("swin2sr.first_convolution", C, c->nin);
     const std::string pe = "swin2sr.embeddings.patch_embeddings";
-    c->wpe = linear(pe + ".projection.weight", C, C);
+    c->wpe = linear(pe + ".projection.weight", C, C, &c->wpeh);
     c->bpe = vec(pe + ".projection.bias", CS);
     c->peg = vec(pe + ".layernorm.weight", CS);
     c->peb = vec(pe + ".layernorm.bias", CS);
@@ -425,14 +524,17 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
             const int nq = heads * 3 * dp;
             L.wqkv = pk.reserve((size_t)CS * nq);
             L.bqkv = pk.reserve(nq);
+            if (f16) L.wqkvh = reserve_h((size_t)nq * CS);
             const char* parts[3] = {".query", ".key", ".value"};
             for (int p = 0; p < 3; ++p) {
-                const std::vector<float>& w = sd.data(a + parts[p] + ".weight");
+                const std::string wkey = a + parts[p] + ".weight";
+                const std::vector<float>& w = sd.data(wkey);
                 const std::vector<float>* b = p == 1 ? nullptr : &sd.data(a + parts[p] + ".bias");
                 for (int h = 0; h < heads; ++h)
                     for (int jd = 0; jd < d; ++jd) {
                         const int row = h * d + jd, col = (h * 3 + p) * dp + jd;
                         for (int k = 0; k < C; ++k) pk.host[L.wqkv + (size_t)k * nq + col] = w[(size_t)row * C + k];
+                        for (int k = 0; f16 && k < C; ++k) hh[L.wqkvh + (size_t)col * CS + k] = to_h(wkey, w[(size_t)row * C + k]);
                         if (b) pk.host[L.bqkv + col] = (*b)[row];
                     }
             }
@@ -459,19 +561,19 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
                             pk.host[L.bias + ((size_t)h * n + p) * n + q] = (float)(16.0 / (1.0 + std::exp(-tb[(size_t)idx * heads + h])));
                         }
             }
-            L.wo = linear(l + ".attention.output.dense.weight", C, C);
+            L.wo = linear(l + ".attention.output.dense.weight", C, C, &L.woh);
             L.bo = vec(l + ".attention.output.dense.bias", CS);
             L.ln1g = vec(l + ".layernorm_before.weight", CS);
             L.ln1b = vec(l + ".layernorm_before.bias", CS);
-            L.w1 = linear(l + ".intermediate.dense.weight", c->hidden, C);
+            L.w1 = linear(l + ".intermediate.dense.weight", c->hidden, C, &L.w1h);
             L.b1 = vec(l + ".intermediate.dense.bias", c->hidp);
-            L.w2 = linear(l + ".output.dense.weight", C, c->hidden);
+            L.w2 = linear(l + ".output.dense.weight", C, c->hidden, &L.w2h);
             L.b2 = vec(l + ".output.dense.bias", CS);
             L.ln2g = vec(l + ".layernorm_after.weight", CS);
             L.ln2b = vec(l + ".layernorm_after.bias", CS);
         }
         S.conv = conv(s + ".conv", C, C);
-        S.wproj = linear(s + ".patch_embed.projection.weight", C, C);
+        S.wproj = linear(s + ".patch_embed.projection.weight", C, C, &S.wprojh);
         S.bproj = vec(s + ".patch_embed.projection.bias", CS);
     }
     c->lng = vec("swin2sr.layernorm.weight", CS);
@@ -495,8 +597,28 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
         }
         c->fin = conv("upsample.final_convolution", c->nout, kFeatures);
     }
+    if (!out_of_range.empty())      // before any device call
+        return set_error(NESR_ERR_RANGE, "nesr_swin2sr_finalize: " + out_of_range + " holds a value that is non-finite or beyond +-65504, which the fp16 form "
+                                             "cannot carry (NESR_DTYPE_F32 can)");
+    c->packed = true;
+    if (c->device == NESR_SWIN2SR_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no forward either
     const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
     if (rc) return rc;
+    if (f16) {
+        if (c->d_wh) NESR_TRY(hipFree(c->d_wh));
+        c->d_wh = nullptr;
+        if (hipMalloc((void**)&c->d_wh, hh.size() * sizeof(_Float16)) != hipSuccess) {
+            c->d_wh = nullptr;
+            return set_error(NESR_ERR_NOMEM, std::string(kName) + ": allocating the f16 weights failed");
+        }
+        NESR_TRY(hipMemcpy(c->d_wh, hh.data(), hh.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        if (!c->d_status) {
+            NESR_TRY(hipMalloc((void**)&c->d_status, sizeof(unsigned)));
+            NESR_TRY(hipHostMalloc((void**)&c->h_status, sizeof(unsigned), hipHostMallocDefault));
+        }
+        NESR_TRY(hipMemset(c->d_status, 0, sizeof(unsigned)));
+        *c->h_status = 0;
+    }
     c->finalized = true;
     return NESR_OK;
 }
@@ -553,6 +675,50 @@ int nesr_swin2sr_forward_batch_f32(nesr_swin2sr* c, const float* x, int N, int C
     S2Batch bt;
     bt.B = N;
     return forward(c, x, false, H, W, out, false, static_cast<hipStream_t>(stream), bt);
+}
+
+int nesr_swin2sr_part_f32(nesr_swin2sr* c, int part, int stage, int layer, const float* in, int N, int H, int W, float* out, size_t capacity, void* stream) {
+    if (!c || !in || !out) return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, "nesr_swin2sr_part_f32: weights not finalized (nesr_swin2sr_finalize)");
+    if (part != NESR_S2_PART_ATTENTION && part != NESR_S2_PART_MLP && part != NESR_S2_PART_STAGE_CONV)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: part must be one of NESR_S2_PART_*, got " + std::to_string(part));
+    if (stage < 0 || stage >= c->nst) return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: stage must be 0 .. " + std::to_string(c->nst - 1));
+    if (part != NESR_S2_PART_STAGE_CONV && (layer < 0 || layer >= c->depth[stage]))
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: layer must be 0 .. " + std::to_string(c->depth[stage] - 1));
+    if (N < 1 || N > 65535 || H < 1 || W < 1 || (long long)H * W > (1ll << 24) || (long long)N * H * W > S2_ROWS_MAX)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: tokens [N][H W][C] with N in 1 .. 65535, H W in 1 .. 2^24 and N H W below 2^31 - 33");
+    if (H % c->ws || W % c->ws)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: H and W must be multiples of window_size " + std::to_string(c->ws) + ", got " + std::to_string(H) +
+                                           " x " + std::to_string(W));
+    const size_t rows = (size_t)N * H * W, need = rows * c->C;
+    if (capacity < need) return set_error(NESR_ERR_ARG, "nesr_swin2sr_part_f32: the output needs " + std::to_string(need) + " floats, capacity is " + std::to_string(capacity));
+    NESR_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    size_t act, upb;
+    int rc = grow(c->ws_buf, c->ws_bytes, workspace_bytes(c, H, W, N, act, upb), kName);
+    if (rc) return rc;
+    float* A = reinterpret_cast<float*>(c->ws_buf + 2 * act);
+    float* B = reinterpret_cast<float*>(c->ws_buf + 3 * act);
+    const size_t pitch = (size_t)c->cs * 4, dense = (size_t)c->C * 4;
+    NESR_TRY(hipMemsetAsync(A, 0, rows * pitch, s));      // the columns past the real width are zero in every buffer
+    NESR_TRY(hipMemcpy2DAsync(A, pitch, in, dense, dense, rows, hipMemcpyDeviceToDevice, s));
+    rc = range_begin(c, s);
+    if (rc) return rc;
+    const S2StageW& S = c->stages[stage];
+    if (part == NESR_S2_PART_ATTENTION) {
+        const S2Attn a = attn_args(c, S.layers[layer], layer, A, B, N, H, W);
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_ATTENTION, s, [&] { return launch_s2_attn(a, s); });
+    } else if (part == NESR_S2_PART_MLP) {
+        S2Rows a = mlp_args(c, S.layers[layer], (int)rows, A);
+        a.out = B;
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_MLP, s, [&] { return launch_s2_rows(a, s); });
+    } else {
+        S2Conv a = conv_args(c, S.conv, A, H, W, c->cs, B, c->cs);
+        a.batch = N;
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
+    }
+    NESR_TRY(hipMemcpy2DAsync(out, dense, B, pitch, dense, rows, hipMemcpyDeviceToDevice, s));
+    return range_end(c, s, "nesr_swin2sr_part_f32");
 }
 
 int nesr_swin2sr_tile_plan(int upscale, int H, int W, int tile, int tile_pad, int* tiles_y, int* tiles_x, int* win_h, int* win_w, int32_t* plan,

@@ -73,6 +73,10 @@ struct S2Conv {
     // writes the tile's core alone, at its place in `out`, the whole FH up x FW up frame.  tile = 0: a u8 frame comes alone
     // (FH = fh, FW = fw, batch = 1).
     int tile, tile_pad, tiles_x, tile0, FH, FW, up;
+    // the fp16 form (ROWS and NEAREST2 inputs): wh [9][coutp][cin rounded up to 16] f16; status: the context's range word
+    int f16;
+    const void* wh;
+    unsigned* status;
 };
 
 // rows [m][cs] (m = batch * H * W) -> (x w1 + b1, gelu) -> (x w2 + b2) -> LayerNorm -> + res -> out; every step optional
@@ -89,6 +93,11 @@ struct S2Rows {
     float eps;
     const float* res;         // [m][cs] or null (may be `out`)
     float* out;               // [m][cs] (may be `in`)
+    // the fp16 form (launches with w1): w1h [n1p][cs], w2h [cs][n1p] f16; status: the context's range word
+    int f16;
+    const void* w1h;
+    const void* w2h;
+    unsigned* status;
 };
 
 // one shifted-window attention block: out[token] = in[token] + LayerNorm(dense(attention(window of the token)))
@@ -106,6 +115,11 @@ struct S2Attn {
     const float* ln_g;
     const float* ln_b;
     float eps;
+    // the fp16 form: wqkvh [heads * 3 * dp][cs], woh [cs][cs] f16; status: the context's range word
+    int f16;
+    const void* wqkvh;
+    const void* woh;
+    unsigned* status;
 };
 
 size_t s2_conv_lds_bytes(const S2Conv& a);

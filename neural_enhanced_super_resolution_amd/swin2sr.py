@@ -14,6 +14,13 @@ frame into windows of one shape that run as a batch (``tile_plan``), and ``forwa
 Supported: upsampler pixelshuffle (x2^n, x3), pixelshuffledirect, nearest+conv (x4); resi_connection "1conv"; patch_size 1;
 qkv_bias True; image_size > window_size; the same number of heads in every stage.  Anything else raises NesrUnsupportedError
 when the context is created, and the message names the field.
+
+``Swin2SR(compute_dtype="fp16", **cfg)`` (``SRVGGNetCompact``'s name for it) selects the fp16 compute form: storage stays float32,
+every GEMM takes both operands rounded to f16 with f32 sums on the f16 matrix cores (include/nesr_hip.h lists them).  The default
+``"f32"`` is the path above.  ``.half()`` does not select it.  f16 carries |x| <= 65504: a weight beyond that raises
+``NesrRangeError`` when the context is made, an activation beyond it when the forward returns (the fp16 form's calls wait for the
+stream).  ``part(part, stage, layer, tokens)`` runs one launch of the model (an attention block, an MLP block or a stage's 3x3
+conv) on given tokens, in the model's form.
 """
 from __future__ import annotations
 
@@ -34,6 +41,8 @@ DEFAULTS = dict(image_size=64, patch_size=1, num_channels=3, num_channels_out=No
 NUM_FEATURES = 64                     # the width of the pixelshuffle and nearest+conv heads
 KERNEL_GROUPS = ("conv", "projection", "attention", "mlp", "upsample")      # NESR_S2_GROUP_*
 _IGNORED = ("relative_position_index", "relative_coords_table", "attn_mask")      # buffers older checkpoints carry
+COMPUTE_DTYPES = {"f32": _lib.DTYPE_F32, "fp16": _lib.DTYPE_F16}
+PARTS = {"attention": 0, "mlp": 1, "stage_conv": 2}      # NESR_S2_PART_*
 
 
 def _config(cfg):
@@ -109,8 +118,12 @@ class Swin2SR(_HFNet):
     TRAIN_ERROR = "Swin2SR is inference only (eval mode: no dropout, no stochastic depth)"
     _spec = staticmethod(swin2sr_state_dict_spec)
 
-    def __init__(self, **cfg):
+    def __init__(self, compute_dtype="f32", **cfg):
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError(f"Swin2SR: compute_dtype {compute_dtype!r}: expected 'f32' or 'fp16' (bf16 is not a form of this network: its 8 "
+                             "significand bits cost 0.2 to 0.4 in the logits of cosine attention)")
         super().__init__(_config(cfg))
+        self.compute_dtype = compute_dtype
 
     def _register_leaf(self, mod, leaf, shape, init=None):
         super()._register_leaf(mod, leaf, shape, torch.full(shape, math.log(10.0)) if leaf == "logit_scale" else init)
@@ -136,6 +149,11 @@ class Swin2SR(_HFNet):
             msg = lib.nesr_last_error()
             raise _lib.NesrUnsupportedError(f"nesr_swin2sr_create failed ({rc}): {msg.decode() if msg else '?'}")
         _lib.check(rc, "nesr_swin2sr_create")
+        try:
+            _lib.check(lib.nesr_swin2sr_set_dtype(handle, COMPUTE_DTYPES[self.compute_dtype]), "nesr_swin2sr_set_dtype")
+        except Exception:
+            lib.nesr_swin2sr_destroy(handle)
+            raise
         return handle
 
     # ------------------------------------------------------------------ forward
@@ -169,6 +187,24 @@ class Swin2SR(_HFNet):
             out = torch.empty((n, self.config["num_channels_out"]) + self.output_size(h, w), dtype=torch.float32, device=x.device)
             _invoke("nesr_swin2sr_forward_batch_f32", x.device, handle, (x, n, ch, h, w, out, out.numel()))
         self.calls += 1
+        return out
+
+    def part(self, part, stage, layer, tokens):
+        """One launch of the model, in its compute form, on `tokens` [N, H, W, C] float32 on the device (C = embed_dim; H, W
+        multiples of window_size) -> the same shape.  part "attention": the attention block of layer `layer` of stage `stage`
+        (shifted when `layer` is odd), tokens + LayerNorm(output.dense(attention)); "mlp": its MLP block, tokens +
+        LayerNorm(fc2(GELU(fc1(tokens)))); "stage_conv": the stage's 3x3 convolution (`layer` is ignored)."""
+        if part not in PARTS:
+            raise ValueError(f"Swin2SR.part: part {part!r}: expected one of {sorted(PARTS)}")
+        self._require_device(tokens, "part")
+        if tokens.dim() != 4 or tokens.dtype != torch.float32 or tokens.shape[3] != self.config["embed_dim"]:
+            raise ValueError(f"Swin2SR.part: an [N, H, W, {self.config['embed_dim']}] float32 tensor, got {tokens.dtype} {tuple(tokens.shape)}")
+        x = tokens.contiguous()
+        n, h, w, _ = x.shape
+        with torch.cuda.device(x.device):
+            handle = self._context(x.device)
+            out = torch.empty_like(x)
+            _invoke("nesr_swin2sr_part_f32", x.device, handle, (PARTS[part], int(stage), int(layer), x, n, h, w, out, out.numel()))
         return out
 
     def tile_plan(self, h, w, tile, tile_pad=16):
