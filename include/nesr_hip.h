@@ -1056,6 +1056,36 @@ int nesr_swin2sr_upscale_tiled_u8(nesr_swin2sr* ctx, const uint8_t* rgb_dev, int
                                   size_t capacity, void* hip_stream);
 int nesr_swin2sr_forward_batch_f32(nesr_swin2sr* ctx, const float* pixel_values_dev, int N, int C, int H, int W, float* out_dev, size_t capacity,
                                    void* hip_stream);
+/*
+ * Overlapped tiles, averaged: the tiling of the Swin2SR / SwinIR authors' test script (--tile, --tile_overlap).  The frame is / 255
+ * and padded ONCE, by its own symmetric extension on the right and bottom, to Hp x Wp, the next multiples of window_size; there is
+ * no processor padding to (n / 8 + 1) * 8, of the frame or of a window.  The effective tile is t = min(tile, Hp, Wp).  Per axis of
+ * padded length n the tiles start at 0, t - tile_overlap, 2 (t - tile_overlap), ... below n - t, and then at n - t: the last tile
+ * slides back to end at the frame's edge and is in general not on the stride.  Every t x t window, in row-major order, goes
+ * through the network as it is (t is a multiple of window_size, so the model pads nothing); its f32 output, / img_range + mean and
+ * before any clamp, is ADDED into an f32 accumulator of the padded output, in ascending tile index; at the end every pixel is
+ * divided by the number of windows that covered it (a true f32 division), cropped to H s x W s, clamped, x 255, rounded to nearest
+ * even and stored as HWC u8.  A pixel near a tile's edge is the mean of up to four evaluations (nine when tile_overlap > t / 2).
+ *
+ * nesr_swin2sr_overlap_plan touches no device and needs no context: tiles_y, tiles_x, t, Hp, Wp and, unless `plan` is null, one row
+ * of 4 integers per window in row-major order, {win_y, win_x (input pixels of the padded frame), out_y, out_x (output pixels)};
+ * capacity counts integers.  nesr_swin2sr_overlap_workspace_bytes: the network's workspace of `batch` windows, plus their f32
+ * outputs, plus the accumulator (12 bytes per padded output pixel).
+ *
+ * nesr_swin2sr_upscale_overlapped_u8: the windows run in ceil(n / B) batches of B, in order on the stream; B = max_batch, or for
+ * max_batch <= 0 as many windows as keep the per-batch part (network workspace and outputs; the accumulator belongs to the frame)
+ * within NESR_SWIN2SR_TILE_WORKSPACE_BYTES, at least one and at most the windows of the frame.  The result does not depend on B.
+ * Both compute forms take the route (the fp16 form clears and checks its range word once a call: NESR_ERR_RANGE).  NESR_ERR_ARG,
+ * before any launch and with the output untouched: tile < 1; an effective tile that is not a multiple of window_size;
+ * tile_overlap < 0 or >= the effective tile; a capacity too small; a model whose channels are not 3 / 3.  NESR_ERR_NOMEM when the
+ * workspace cannot be allocated.  In nesr_swin2sr_kernel_time_ms the accumulation (one launch a batch) and the division (one a
+ * call) count under NESR_S2_GROUP_UPSAMPLE: launches = ceil(n / B) * (launches of one forward + 1) + 1.
+ */
+int nesr_swin2sr_overlap_plan(int upscale, int window_size, int H, int W, int tile, int tile_overlap, int* tiles_y, int* tiles_x, int* t, int* Hp,
+                              int* Wp, int32_t* plan, size_t capacity);
+int nesr_swin2sr_overlap_workspace_bytes(nesr_swin2sr* ctx, int H, int W, int tile, int tile_overlap, int batch, size_t* bytes);
+int nesr_swin2sr_upscale_overlapped_u8(nesr_swin2sr* ctx, const uint8_t* rgb_dev, int H, int W, int tile, int tile_overlap, int max_batch,
+                                       uint8_t* out_dev, size_t capacity, void* hip_stream);
 /* The launch counter and the per-group event timing, as nesr_segformer_set_timing / nesr_segformer_kernel_time_ms. */
 enum { NESR_S2_GROUP_CONV = 0, NESR_S2_GROUP_PROJ = 1, NESR_S2_GROUP_ATTENTION = 2, NESR_S2_GROUP_MLP = 3, NESR_S2_GROUP_UPSAMPLE = 4,
        NESR_S2_GROUPS = 5 };

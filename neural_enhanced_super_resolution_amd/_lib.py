@@ -179,6 +179,10 @@ SIGNATURES = {
                                           _c.POINTER(_c.c_int), _c.POINTER(_c.c_int32), _c.c_size_t]),
     "nesr_swin2sr_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "nesr_swin2sr_upscale_tiled_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_swin2sr_overlap_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                             _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int32), _c.c_size_t]),
+    "nesr_swin2sr_overlap_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "nesr_swin2sr_upscale_overlapped_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_swin2sr_forward_batch_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_swin2sr_set_timing":(_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_swin2sr_set_dtype": (_c.c_int, [_c.c_void_p, _c.c_int]),

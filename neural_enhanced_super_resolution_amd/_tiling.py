@@ -100,6 +100,31 @@ def slid_window_axis(n, tile, tile_pad):
     return side, [(min(max(c0 - tile_pad, 0), n - side), c0, min(c0 + tile, n)) for c0 in range(0, n, tile)]
 
 
+def overlap_axis(n, t, overlap):
+    """The starts of one padded axis of Swin2SR's overlapped plan: 0, t - overlap, ... below n - t, then n - t (the last tile ends
+    at n and is in general not on the stride)."""
+    if not (1 <= t <= n and 0 <= overlap < t):
+        raise ValueError(f"overlap_axis: 1 <= t <= n and 0 <= overlap < t, got n = {n}, t = {t}, overlap = {overlap}")
+    return list(range(0, n - t, t - overlap)) + [n - t]
+
+
+def overlap_plan(h, w, tile, tile_overlap, window_size, scale):
+    """Swin2SR's overlapped plan of an h x w frame, what nesr_swin2sr_overlap_plan computes: ((tiles_y, tiles_x), t, (hp, wp), rows).
+    The frame is padded once to hp x wp, multiples of the window; t = min(tile, hp, wp) must be a multiple of the window and
+    0 <= tile_overlap < t; one row (win_y, win_x, out_y, out_x) per t x t window in row-major order, the origin in input pixels of
+    the padded frame and in output pixels."""
+    if h < 1 or w < 1 or tile < 1 or window_size < 1:
+        raise ValueError(f"overlap_plan: h, w, tile and window_size must be positive, got {h}, {w}, {tile}, {window_size}")
+    hp, wp = -(-h // window_size) * window_size, -(-w // window_size) * window_size
+    t = min(tile, hp, wp)
+    if t % window_size:
+        raise ValueError(f"overlap_plan: the effective tile {t} must be a multiple of window_size {window_size}")
+    if not 0 <= tile_overlap < t:
+        raise ValueError(f"overlap_plan: tile_overlap must be 0 .. {t - 1}, got {tile_overlap}")
+    ys, xs = overlap_axis(hp, t, tile_overlap), overlap_axis(wp, t, tile_overlap)
+    return (len(ys), len(xs)), t, (hp, wp), [(y, x, y * scale, x * scale) for y in ys for x in xs]
+
+
 def slid_window_plan(h, w, tile, tile_pad, scale):
     """Swin2SR's tile plan of an h x w frame, what nesr_swin2sr_tile_plan computes: ((tiles_y, tiles_x), (win_h, win_w), rows), one
     row (win_y, win_x, crop_y, crop_x, crop_h, crop_w, out_y, out_x) per tile in row-major order; the window's origin in input

@@ -18,6 +18,9 @@
 //                    optional: the MLP block, the 1x1 projections (patch embedding with LayerNorm, a stage's end with its
 //                    residual) and the encoder's LayerNorm.
 //
+// Two small HBM-bound kernels serve the overlapped route (nesr_swin2sr_upscale_overlapped_u8): s2_overlap_add_kernel adds a batch's
+// f32 window outputs into the accumulator of the padded frame, s2_overlap_finish_kernel divides by the cover count and quantises.
+//
 // MFMA operand maps (16x16x4 f32): lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; result register r of lane
 // l is D[row 4 (l >> 4) + r][col l & 15].  Widths are padded to the tile with zeros (swin2sr_api.h).  No atomics, no workgroup
 // waits on another: a forward repeated gives the same bits.  Every global load and store is guarded by the token count, the
@@ -213,6 +216,13 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
         s2_tile_axis(a.FW, a.tile, a.tile_pad, tx, wx, c0, c1);
         cx0 = (c0 - wx) * a.up, cx1 = (c1 - wx) * a.up;
     }
+    int ovy = 0, ovx = 0;      // WINDOW_U8: image b's origin in the padded frame
+    if (a.in_mode == S2_IN_WINDOW_U8) {
+        const int ti = a.tile0 + (int)b, ty = ti / a.tiles_x, tx = ti - ty * a.tiles_x;
+        int cnt, first, last;
+        s2_overlap_axis(a.PH, a.H, a.ov_step, ty, 0, cnt, ovy, first, last);
+        s2_overlap_axis(a.PW, a.W, a.ov_step, tx, 0, cnt, ovx, first, last);
+    }
     const float* in_rows = static_cast<const float*>(a.in);
     if (a.in_mode == S2_IN_ROWS) in_rows += b * px_img * a.cs_in;
     else if (a.in_mode == S2_IN_NEAREST2) in_rows += b * (size_t)(a.H >> 1) * (a.W >> 1) * a.cs_in;
@@ -227,6 +237,13 @@ __global__ __launch_bounds__(256) void s2_conv_kernel(const S2Conv a) {
                 v = *reinterpret_cast<const float4*>(in_rows + ((size_t)gy * a.W + gx) * a.cs_in + q * 4);
             } else if (a.in_mode == S2_IN_NEAREST2) {
                 v = *reinterpret_cast<const float4*>(in_rows + ((size_t)(gy >> 1) * (a.W >> 1) + (gx >> 1)) * a.cs_in + q * 4);
+            } else if (a.in_mode == S2_IN_WINDOW_U8) {
+                if (q == 0) {      // the frame's own symmetric extension at the window's place: the index is taken against the frame
+                    const size_t at = ((size_t)sym_index(ovy + gy, a.FH) * a.FW + sym_index(ovx + gx, a.FW)) * a.cin;
+                    float e[4] = {0.f, 0.f, 0.f, 0.f};
+                    for (int ch = 0; ch < a.cin; ++ch) e[ch] = ((float)static_cast<const uint8_t*>(a.in)[at + ch] / 255.0f - a.mean[ch]) * a.range;
+                    v = make_float4(e[0], e[1], e[2], e[3]);
+                }
             } else if (q == 0) {
                 // reflect back into the model's input (mh x mw), then symmetric back into the image's own window (fh x fw) of the frame
                 int my = gy < a.mh ? gy : 2 * a.mh - 2 - gy, mx = gx < a.mw ? gx : 2 * a.mw - 2 - gx;
@@ -645,6 +662,87 @@ __global__ __launch_bounds__(S2_ATTN_THREADS) void s2_attn_f16_kernel(const S2At
     }
 }
 
+// ------------------------------------------------------------------------------------------------ overlapped tiles, averaged
+// Both kernels walk the padded output in flat pixel order, four consecutive pixels a thread (a group may run over a row's end):
+// E is planar with planes of a multiple of four floats, so a group is one aligned 16-byte access a channel and a wave's accesses
+// are contiguous.  A group belongs to one thread in every launch; nothing is shared, nothing atomic.  HBM-bound.
+
+// E[pixel] += Y[window][pixel - the window's origin] for the batch's windows that cover the pixel, in ascending tile index
+// (tile rows outer, tiles of a row inner: the row-major order of the plan).  Groups [g0, g1) are the rows the batch's tiles touch.
+__global__ __launch_bounds__(256) void s2_overlap_add_kernel(const S2Overlap a, size_t g0, size_t g1) {
+    const size_t g = g0 + (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= g1) return;
+    const int OW = a.PW * a.up, ts = a.t * a.up, t1 = a.tile0 + a.batch;
+    const size_t npx = (size_t)a.PH * a.up * OW, plane = s2_overlap_plane(a.PH, a.PW, a.up);
+    int oy[4], ox[4], fy[4], ly[4], fx[4], lx[4];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const size_t p = 4 * g + j;
+        fy[j] = 0, ly[j] = -1, fx[j] = 0, lx[j] = -1;      // past the last pixel: no tile
+        if (p >= npx) continue;
+        oy[j] = (int)(p / OW), ox[j] = (int)(p - (size_t)oy[j] * OW);
+        int cnt, st;
+        s2_overlap_axis(a.PH, a.t, a.step, 0, oy[j] / a.up, cnt, st, fy[j], ly[j]);
+        s2_overlap_axis(a.PW, a.t, a.step, 0, ox[j] / a.up, cnt, st, fx[j], lx[j]);
+        any = any || (fy[j] * a.tiles_x + fx[j] < t1 && ly[j] * a.tiles_x + lx[j] >= a.tile0);
+    }
+    if (!any) return;
+    float4* E = reinterpret_cast<float4*>(a.E) + g;
+    float e[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float4 v = E[ch * (plane / 4)];
+        e[ch][0] = v.x, e[ch][1] = v.y, e[ch][2] = v.z, e[ch][3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        for (int ty = fy[j]; ty <= ly[j]; ++ty)
+            for (int tx = fx[j]; tx <= lx[j]; ++tx) {
+                const int ti = ty * a.tiles_x + tx;
+                if (ti < a.tile0 || ti >= t1) continue;
+                int cnt, wy, wx, f, l;
+                s2_overlap_axis(a.PH, a.t, a.step, ty, 0, cnt, wy, f, l);
+                s2_overlap_axis(a.PW, a.t, a.step, tx, 0, cnt, wx, f, l);
+                const float* y = a.Y + ((size_t)(ti - a.tile0) * 3 * ts + (oy[j] - wy * a.up)) * ts + (ox[j] - wx * a.up);
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch) e[ch][j] += y[(size_t)ch * ts * ts];
+            }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) E[ch * (plane / 4)] = make_float4(e[ch][0], e[ch][1], e[ch][2], e[ch][3]);
+}
+
+// out = quantise(E / the number of tiles that covered the pixel) on the crop oh x ow: the count is cnt_y cnt_x, each the length of
+// s2_overlap_axis's covering run; a true f32 division.  Groups [0, groups) hold the crop's rows.
+__global__ __launch_bounds__(256) void s2_overlap_finish_kernel(const S2Overlap a, size_t groups) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= groups) return;
+    const int OW = a.PW * a.up;
+    const size_t plane = s2_overlap_plane(a.PH, a.PW, a.up);
+    const float4* E = reinterpret_cast<const float4*>(a.E) + g;
+    float e[3][4];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const float4 v = E[ch * (plane / 4)];
+        e[ch][0] = v.x, e[ch][1] = v.y, e[ch][2] = v.z, e[ch][3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const size_t p = 4 * g + j;
+        const int oy = (int)(p / OW), ox = (int)(p - (size_t)oy * OW);
+        if (oy >= a.oh || ox >= a.ow) continue;
+        int cnt, st, fy, ly, fx, lx;
+        s2_overlap_axis(a.PH, a.t, a.step, 0, oy / a.up, cnt, st, fy, ly);
+        s2_overlap_axis(a.PW, a.t, a.step, 0, ox / a.up, cnt, st, fx, lx);
+        const float n = (float)((ly - fy + 1) * (lx - fx + 1));
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const float v = fminf(fmaxf(e[ch][j] / n, 0.f), 1.f) * 255.0f;
+            a.out[((size_t)oy * a.ow + ox) * 3 + ch] = (uint8_t)rintf(v);
+        }
+    }
+}
+
 template <class K, class A>
 hipError_t launch_lds(K kernel, const A& a, dim3 grid, int threads, size_t bytes, unsigned long long& done, hipStream_t s) {
     if (bytes > S2_LDS_LIMIT) return hipErrorInvalidValue;
@@ -678,6 +776,14 @@ hipError_t launch_s2_conv(const S2Conv& a, hipStream_t s) {
     if (a.in_mode == S2_IN_FRAME_U8 || a.in_mode == S2_IN_FRAME_F32) {
         if (a.cin > 4 || a.cinp != 4 || a.fh < 1 || a.fw < 1 || a.mh < a.fh || a.mw < a.fw || a.H < a.mh || a.W < a.mw) return hipErrorInvalidValue;
         if (a.H - a.mh > a.mh - 1 || a.W - a.mw > a.mw - 1) return hipErrorInvalidValue;      // a reflection reaches at most n - 1
+    } else if (a.in_mode == S2_IN_WINDOW_U8) {      // every window lies inside the padded frame; sym_index takes any distance
+        if (a.cin > 4 || a.cinp != 4 || a.tile != 0 || a.H != a.W || a.ov_step < 1 || a.ov_step > a.H || a.FH < 1 || a.FW < 1 || a.PH < a.FH || a.PW < a.FW ||
+            a.H > a.PH || a.W > a.PW || a.tile0 < 0)
+            return hipErrorInvalidValue;
+        int ny, nx, v, f, l;
+        s2_overlap_axis(a.PH, a.H, a.ov_step, 0, 0, ny, v, f, l);
+        s2_overlap_axis(a.PW, a.W, a.ov_step, 0, 0, nx, v, f, l);
+        if (a.tiles_x != nx || (long long)a.tile0 + a.batch > (long long)ny * nx) return hipErrorInvalidValue;
     } else if (a.in_mode != S2_IN_ROWS && a.in_mode != S2_IN_NEAREST2) {
         return hipErrorInvalidValue;
     }
@@ -741,6 +847,36 @@ hipError_t launch_s2_attn(const S2Attn& a, hipStream_t s) {
         return launch_lds(&s2_attn_f16_kernel, a, grid, S2_ATTN_THREADS, s2_attn_lds_bytes(a), done16, s);
     }
     return launch_lds(&s2_attn_kernel, a, grid, S2_ATTN_THREADS, s2_attn_lds_bytes(a), done, s);
+}
+
+// the plan the two overlap kernels index by: E and Y are sized from it by the caller
+static bool overlap_shape_ok(const S2Overlap& a) {
+    if (!a.E || a.PH < 1 || a.PW < 1 || a.t < 1 || a.t > a.PH || a.t > a.PW || a.step < 1 || a.step > a.t || a.up < 1 || a.up > 8) return false;
+    if ((long long)a.PH * a.up * a.PW * a.up > (1ll << 36)) return false;
+    int ny, nx, v, f, l;
+    s2_overlap_axis(a.PH, a.t, a.step, 0, 0, ny, v, f, l);
+    s2_overlap_axis(a.PW, a.t, a.step, 0, 0, nx, v, f, l);
+    return a.tiles_y == ny && a.tiles_x == nx && (long long)ny * nx <= 0x7fffffff;
+}
+
+hipError_t launch_s2_overlap_add(const S2Overlap& a, hipStream_t s) {
+    if (!overlap_shape_ok(a) || !a.Y || a.tile0 < 0 || a.batch < 1 || (long long)a.tile0 + a.batch > (long long)a.tiles_y * a.tiles_x) return hipErrorInvalidValue;
+    int cnt, y0, y1, f, l;      // the output rows between the first tile row's top and the last one's bottom
+    s2_overlap_axis(a.PH, a.t, a.step, a.tile0 / a.tiles_x, 0, cnt, y0, f, l);
+    s2_overlap_axis(a.PH, a.t, a.step, (a.tile0 + a.batch - 1) / a.tiles_x, 0, cnt, y1, f, l);
+    const size_t row = (size_t)a.PW * a.up, g0 = (size_t)y0 * a.up * row / 4, g1 = ((size_t)(y1 + a.t) * a.up * row + 3) / 4;
+    const size_t blocks = (g1 - g0 + 255) / 256;
+    if (blocks < 1 || blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    s2_overlap_add_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(a, g0, g1);
+    return hipGetLastError();
+}
+
+hipError_t launch_s2_overlap_finish(const S2Overlap& a, hipStream_t s) {
+    if (!overlap_shape_ok(a) || !a.out || a.oh < 1 || a.ow < 1 || a.oh > a.PH * a.up || a.ow > a.PW * a.up) return hipErrorInvalidValue;
+    const size_t groups = ((size_t)a.oh * a.PW * a.up + 3) / 4, blocks = (groups + 255) / 256;
+    if (blocks > 0x7fffffffu) return hipErrorInvalidValue;
+    s2_overlap_finish_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(a, groups);
+    return hipGetLastError();
 }
 
 }  // namespace nesr

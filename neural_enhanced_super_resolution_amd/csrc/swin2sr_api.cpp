@@ -1,7 +1,8 @@
 // Swin2SR contexts (nesr_swin2sr_*): the configuration check, strict weight loading, the padded and transposed upload, the
 // continuous position bias tables (computed once on the host in double), a workspace that grows with the frame, and the forward
 // as a chain of launches of the three kernels of swin2sr.hip, over one frame or over a batch of images of one size: the images of
-// nesr_swin2sr_forward_batch_f32, or the windows the tile plan cuts a large frame into (nesr_swin2sr_upscale_tiled_u8).  Stands behind transformers' Swin2SRForImageSuperResolution and,
+// nesr_swin2sr_forward_batch_f32, or the windows the tile plan cuts a large frame into (nesr_swin2sr_upscale_tiled_u8), or the overlapped
+// windows whose f32 outputs are summed and averaged (nesr_swin2sr_upscale_overlapped_u8: the authors' --tile / --tile_overlap).  Stands behind transformers' Swin2SRForImageSuperResolution and,
 // for nesr_swin2sr_upscale_u8, its Swin2SRImageProcessor and the documented post-processing.
 #include <cmath>
 #include <cstring>
@@ -145,8 +146,11 @@ int range_end(nesr_swin2sr* c, hipStream_t s, const char* entry) {
 
 // The images of one forward: B of them, each fh x fw.  tile = 0: they lie one after the other in `frame` and in `out` (f32), or
 // there is one (u8).  tile > 0 (u8 in and out): they are the tiles tile0 .. tile0 + B - 1 of the plan of an FH x FW frame.
+// ov_step > 0 (u8 in, f32 out, fh = fw = t): they are the windows tile0 .. tile0 + B - 1 of the overlapped plan of the FH x FW frame
+// padded to PH x PW, read from the frame's symmetric extension without any padding of their own; `out` takes them one after the other.
 struct S2Batch {
     int B = 1, tile = 0, tile_pad = 0, tiles_x = 1, tile0 = 0, FH = 0, FW = 0;
+    int ov_step = 0, PH = 0, PW = 0;
 };
 
 // the model's input (after the processor's symmetric padding of a u8 frame) and the conv's domain (after the reflect padding to the window)
@@ -168,7 +172,7 @@ size_t workspace_bytes(const nesr_swin2sr* c, int H, int W, size_t B, size_t& ac
 // frame: u8 HWC [fh][fw][3] (processor route) or f32 NCHW [nin][fh][fw] (model route); out: f32 NCHW or u8 HWC, cropped to fh s x fw s
 int forward_launches(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt) {
     int mh, mw, H, W;
-    int rc = padded_size(c, frame_u8, fh, fw, mh, mw, H, W);
+    int rc = padded_size(c, frame_u8 && bt.ov_step == 0, fh, fw, mh, mw, H, W);
     if (rc) return rc;
     const size_t T = (size_t)bt.B * H * W;
     if (bt.B < 1 || bt.B > 65535 || T > (size_t)S2_ROWS_MAX)
@@ -198,6 +202,7 @@ int forward_launches(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, 
         S2Conv a = conv(c->first, nullptr, H, W, 0, FIRST, CS);
         a.in_mode = frame_u8 ? S2_IN_FRAME_U8 : S2_IN_FRAME_F32, a.in = frame, a.fh = fh, a.fw = fw, a.mh = mh, a.mw = mw;
         tiled(a);
+        if (bt.ov_step > 0) a.in_mode = S2_IN_WINDOW_U8, a.FH = bt.FH, a.FW = bt.FW, a.ov_step = bt.ov_step, a.PH = bt.PH, a.PW = bt.PW;
         NESR_RUN(c->timer, kName, NESR_S2_GROUP_CONV, s, [&] { return launch_s2_conv(a, s); });
     }
     {   // patch embedding: 1x1 projection + LayerNorm (torch's default eps) -> XS
@@ -289,6 +294,35 @@ int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, v
     if (!rc) rc = forward_launches(c, frame, frame_u8, fh, fw, out, out_u8, s, bt);
     return rc ? rc : range_end(c, s, kName);
 }
+
+// The overlapped plan of an H x W frame (the authors' --tile / --tile_overlap): the frame padded once to the window, the effective
+// tile t = min(tile, PH, PW), its stride and the counts of s2_overlap_axis.  The argument checks are the plan entry's, the
+// workspace query's and the upscale's alike; `entry` leads the text.
+struct S2OverlapPlan {
+    int PH = 0, PW = 0, t = 0, step = 0, ny = 0, nx = 0;
+};
+int overlap_plan(const std::string& entry, int ws, int H, int W, int tile, int tile_overlap, S2OverlapPlan& p) {
+    if (ws < 1 || ws > (1 << 12)) return set_error(NESR_ERR_ARG, entry + ": window_size must be 1 .. 4096, got " + std::to_string(ws));
+    if (H < 1 || W < 1 || (long long)H * W > NESR_SWIN2SR_TILED_MAX_PIXELS) return set_error(NESR_ERR_ARG, entry + ": a frame (H x W) of 1 .. 2^28 pixels");
+    if (tile < 1 || tile > (1 << 24)) return set_error(NESR_ERR_ARG, entry + ": tile must be 1 .. 2^24, got " + std::to_string(tile));
+    p.PH = round_up(H, ws), p.PW = round_up(W, ws);
+    p.t = std::min(tile, std::min(p.PH, p.PW));
+    if (p.t % ws)
+        return set_error(NESR_ERR_ARG, entry + ": the effective tile min(tile, padded H, padded W) = " + std::to_string(p.t) + " must be a multiple of window_size " +
+                                           std::to_string(ws) + " (no window is padded on this route)");
+    if (tile_overlap < 0 || tile_overlap >= p.t)
+        return set_error(NESR_ERR_ARG, entry + ": tile_overlap must be 0 .. " + std::to_string(p.t - 1) + " (below the effective tile), got " + std::to_string(tile_overlap));
+    p.step = p.t - tile_overlap;
+    int v, f, l;
+    s2_overlap_axis(p.PH, p.t, p.step, 0, 0, p.ny, v, f, l);
+    s2_overlap_axis(p.PW, p.t, p.step, 0, 0, p.nx, v, f, l);
+    if ((long long)p.ny * p.nx > (1ll << 26))
+        return set_error(NESR_ERR_ARG, entry + ": tile and tile_overlap give " + std::to_string((long long)p.ny * p.nx) + " windows, more than 2^26");
+    return NESR_OK;
+}
+// the staging buffer of B windows' f32 outputs, and the accumulator of the padded frame (12 bytes a padded output pixel)
+size_t overlap_y_bytes(const nesr_swin2sr* c, const S2OverlapPlan& p, size_t B) { return align_up(B * 3 * (size_t)p.t * c->scale * p.t * c->scale * 4, 256); }
+size_t overlap_e_bytes(const nesr_swin2sr* c, const S2OverlapPlan& p) { return align_up(3 * s2_overlap_plane(p.PH, p.PW, c->scale) * 4, 256); }
 
 }  // namespace
 
@@ -795,6 +829,89 @@ int nesr_swin2sr_upscale_tiled_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, in
         if (rc) return rc;
     }
     return NESR_OK;
+}
+
+int nesr_swin2sr_overlap_plan(int upscale, int window_size, int H, int W, int tile, int tile_overlap, int* tiles_y, int* tiles_x, int* t, int* Hp, int* Wp,
+                              int32_t* plan, size_t capacity) {
+    if (!tiles_y || !tiles_x || !t || !Hp || !Wp) return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_plan: null pointer");
+    if (upscale < 1 || upscale > 8) return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_plan: upscale must be 1 .. 8");
+    S2OverlapPlan p;
+    const int rc = overlap_plan("nesr_swin2sr_overlap_plan", window_size, H, W, tile, tile_overlap, p);
+    if (rc) return rc;
+    *tiles_y = p.ny, *tiles_x = p.nx, *t = p.t, *Hp = p.PH, *Wp = p.PW;
+    if (!plan) return NESR_OK;
+    const size_t need = (size_t)p.ny * p.nx * 4;
+    if (capacity < need)
+        return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_plan: the plan needs " + std::to_string(need) + " integers, capacity is " + std::to_string(capacity));
+    for (int ty = 0; ty < p.ny; ++ty)
+        for (int tx = 0; tx < p.nx; ++tx) {
+            int cnt, wy, wx, f, l;
+            s2_overlap_axis(p.PH, p.t, p.step, ty, 0, cnt, wy, f, l);
+            s2_overlap_axis(p.PW, p.t, p.step, tx, 0, cnt, wx, f, l);
+            int32_t* r = plan + ((size_t)ty * p.nx + tx) * 4;
+            r[0] = wy, r[1] = wx, r[2] = wy * upscale, r[3] = wx * upscale;
+        }
+    return NESR_OK;
+}
+
+int nesr_swin2sr_overlap_workspace_bytes(nesr_swin2sr* c, int H, int W, int tile, int tile_overlap, int batch, size_t* bytes) {
+    if (!c || !bytes) return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_workspace_bytes: null pointer");
+    if (batch < 1 || batch > 65535) return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_workspace_bytes: batch must be 1 .. 65535, got " + std::to_string(batch));
+    S2OverlapPlan p;
+    const int rc = overlap_plan("nesr_swin2sr_overlap_workspace_bytes", c->ws, H, W, tile, tile_overlap, p);
+    if (rc) return rc;
+    if ((long long)p.t * p.t > (1ll << 24)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_overlap_workspace_bytes: a tile of at most 2^24 pixels");
+    size_t act, upb;
+    *bytes = workspace_bytes(c, p.t, p.t, batch, act, upb) + overlap_y_bytes(c, p, batch) + overlap_e_bytes(c, p);
+    return NESR_OK;
+}
+
+int nesr_swin2sr_upscale_overlapped_u8(nesr_swin2sr* c, const uint8_t* rgb, int H, int W, int tile, int tile_overlap, int max_batch, uint8_t* out,
+                                       size_t capacity, void* stream) {
+    const char* const entry = "nesr_swin2sr_upscale_overlapped_u8";
+    if (!c || !rgb || !out) return set_error(NESR_ERR_ARG, std::string(entry) + ": null pointer");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, std::string(entry) + ": weights not finalized (nesr_swin2sr_finalize)");
+    if (c->nin != 3 || c->nout != 3) return set_error(NESR_ERR_ARG, std::string(entry) + ": an RGB frame needs num_channels = num_channels_out = 3");
+    S2OverlapPlan p;
+    int rc = overlap_plan(entry, c->ws, H, W, tile, tile_overlap, p);
+    if (rc) return rc;
+    if ((long long)p.t * p.t > (1ll << 24)) return set_error(NESR_ERR_ARG, std::string(entry) + ": a tile of at most 2^24 pixels");
+    const size_t need = (size_t)3 * H * c->scale * W * c->scale;
+    if (capacity < need)
+        return set_error(NESR_ERR_ARG, std::string(entry) + ": the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
+    // windows a batch: the caller's, or as many as keep the network's workspace and Y within the budget (E belongs to the frame);
+    // one at least, and no more than a launch takes
+    const long long n = (long long)p.ny * p.nx;
+    size_t act, upb;
+    auto per_batch = [&](long long b) { return workspace_bytes(c, p.t, p.t, (size_t)b, act, upb) + overlap_y_bytes(c, p, (size_t)b); };
+    long long B = max_batch > 0 ? max_batch : std::max<long long>(1, (long long)(NESR_SWIN2SR_TILE_WORKSPACE_BYTES / per_batch(1)));
+    B = std::min(B, std::min<long long>(n, 65535));
+    B = std::max<long long>(1, std::min(B, (long long)S2_ROWS_MAX / ((long long)p.t * p.t)));
+    while (max_batch <= 0 && B > 1 && per_batch(B) > NESR_SWIN2SR_TILE_WORKSPACE_BYTES) --B;
+    NESR_TRY(hipSetDevice(c->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t net = workspace_bytes(c, p.t, p.t, (size_t)B, act, upb), yb = overlap_y_bytes(c, p, (size_t)B), eb = overlap_e_bytes(c, p);
+    rc = grow(c->ws_buf, c->ws_bytes, net + yb + eb, kName);      // once: the forwards below find their part in place, E lives through them
+    if (rc) return rc;
+    S2Overlap o;
+    memset(&o, 0, sizeof(o));
+    o.PH = p.PH, o.PW = p.PW, o.t = p.t, o.step = p.step, o.up = c->scale, o.tiles_y = p.ny, o.tiles_x = p.nx;
+    o.Y = reinterpret_cast<const float*>(c->ws_buf + net), o.E = reinterpret_cast<float*>(c->ws_buf + net + yb);
+    o.out = out, o.oh = H * c->scale, o.ow = W * c->scale;
+    NESR_TRY(hipMemsetAsync(o.E, 0, eb, s));
+    rc = range_begin(c, s);
+    if (rc) return rc;
+    S2Batch bt;
+    bt.tiles_x = p.nx, bt.FH = H, bt.FW = W, bt.ov_step = p.step, bt.PH = p.PH, bt.PW = p.PW;
+    for (long long t0 = 0; t0 < n; t0 += B) {      // row-major, in order on the one stream: E sees the windows in ascending tile index
+        bt.tile0 = (int)t0, bt.B = (int)std::min(B, n - t0);
+        rc = forward_launches(c, rgb, true, p.t, p.t, const_cast<float*>(o.Y), false, s, bt);
+        if (rc) return rc;
+        o.tile0 = bt.tile0, o.batch = bt.B;
+        NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_overlap_add(o, s); });
+    }
+    NESR_RUN(c->timer, kName, NESR_S2_GROUP_UPSAMPLE, s, [&] { return launch_s2_overlap_finish(o, s); });
+    return range_end(c, s, entry);
 }
 
 int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) {

@@ -34,12 +34,25 @@ __host__ __device__ inline void s2_tile_axis(int n, int T, int P, int i, int& w0
     if (w0 < 0) w0 = 0;
 }
 
+// One axis of the overlapped plan (nesr_swin2sr_overlap_plan, the window loader and the two overlap kernels): a padded axis of n
+// pixels, tiles of t <= n whose starts step by st = t - tile_overlap >= 1: 0, st, 2 st, ... below n - t, then n - t, so the last
+// tile ends at n and is in general not on the stride.  Gives the number of starts, the start of tile i (0 <= i < count) and the
+// first and last tile that cover pixel p (0 <= p < n): the covering tiles are contiguous, first <= last.
+__host__ __device__ inline void s2_overlap_axis(int n, int t, int st, int i, int p, int& count, int& start, int& first, int& last) {
+    count = (n - t + st - 1) / st + 1;
+    start = i < count - 1 ? i * st : n - t;
+    first = p < t ? 0 : (p - t) / st + 1;      // the first regular start above p - t; past the regular ones: the last tile
+    if (first > count - 1) first = count - 1;
+    last = p >= n - t ? count - 1 : p / st;
+}
+
 // where the conv's input patch comes from
 enum {
     S2_IN_ROWS = 0,        // in[(y * W + x) * cs_in + c]
     S2_IN_NEAREST2 = 1,    // the nearest x2 upsample of an (H / 2) x (W / 2) grid of rows
     S2_IN_FRAME_U8 = 2,    // an HWC u8 frame [fh][fw][cin]: / 255, symmetric pad to mh x mw, reflect pad to H x W, (v - mean) * range
     S2_IN_FRAME_F32 = 3,   // an NCHW f32 image [cin][fh][fw]: the same without the / 255
+    S2_IN_WINDOW_U8 = 4,   // an H x W window of the symmetric extension of an HWC u8 frame [FH][FW][cin] (see ov_step): / 255, (v - mean) * range
 };
 // where the conv's result goes (after bias, LeakyReLU, residual and the PixelShuffle index map)
 enum {
@@ -73,6 +86,10 @@ struct S2Conv {
     // writes the tile's core alone, at its place in `out`, the whole FH up x FW up frame.  tile = 0: a u8 frame comes alone
     // (FH = fh, FW = fw, batch = 1).
     int tile, tile_pad, tiles_x, tile0, FH, FW, up;
+    // WINDOW_U8 (tile = 0, H = W = t): image b is tile tile0 + b, in row-major order with tiles_x a row, of the overlapped plan
+    // (s2_overlap_axis) of the FH x FW frame padded to PH x PW, stride ov_step; its pixel (y, x) is the frame's symmetric extension
+    // at (win_y + y, win_x + x).  No padding of the window itself: H and W are multiples of the attention window already.
+    int ov_step, PH, PW;
     // the fp16 form (ROWS and NEAREST2 inputs): wh [9][coutp][cin rounded up to 16] f16; status: the context's range word
     int f16;
     const void* wh;
@@ -128,5 +145,20 @@ size_t s2_attn_lds_bytes(const S2Attn& a);
 hipError_t launch_s2_conv(const S2Conv& a, hipStream_t s);
 hipError_t launch_s2_rows(const S2Rows& a, hipStream_t s);
 hipError_t launch_s2_attn(const S2Attn& a, hipStream_t s);
+
+// The overlapped route's accumulator and its two kernels.  E is f32, planar [3][plane], plane = PH up x PW up rounded up to 4
+// (a thread's four pixels are one 16-byte access a channel); Y holds a batch's window outputs [batch][3][t up][t up] f32.
+struct S2Overlap {
+    int PH, PW, t, step, up;      // the padded frame, the tile, its stride (input pixels) and the scale
+    int tiles_y, tiles_x;         // s2_overlap_axis's counts of PH and PW
+    int tile0, batch;             // add: Y holds tiles tile0 .. tile0 + batch - 1
+    const float* Y;               // add
+    float* E;
+    uint8_t* out;                 // finish: HWC u8 [oh][ow][3], the crop of the padded output
+    int oh, ow;
+};
+__host__ __device__ inline size_t s2_overlap_plane(int PH, int PW, int up) { return ((size_t)PH * up * PW * up + 3) / 4 * 4; }
+hipError_t launch_s2_overlap_add(const S2Overlap& a, hipStream_t s);
+hipError_t launch_s2_overlap_finish(const S2Overlap& a, hipStream_t s);
 
 }  // namespace nesr

@@ -325,16 +325,17 @@ def realesrganer_stage(up):
     return stage
 
 
-def swin2sr_stage(model, device=None, tile=0, tile_pad=16, max_batch=None):
+def swin2sr_stage(model, device=None, tile=0, tile_pad=16, max_batch=None, tile_overlap=None):
     """A swin2sr.Swin2SR as an `extra_upscalers` entry of enhance_iterations: RGB u8 frame -> upscaled RGB u8 frame, kept on the
     device (model.upscale: the image processor's padding, the network, the crop and the quantiser in one chain of HIP launches).
     The slot the reference's ensemble (nesr.py:1033-1054) leaves to a second upscaler.  `device`: where a host frame goes
     (default: the current ROCm device); a device frame stays where it is.  `tile`, `tile_pad`, `max_batch` are model.upscale's:
-    with tile > 0 the workspace is bounded by the window, not by the frame, so the stage runs at every iteration's size."""
+    with tile > 0 the workspace is bounded by the window, not by the frame, so the stage runs at every iteration's size.
+    `tile_overlap` (None: off) is model.upscale's as well: the authors' overlapped tiles with averaged seams."""
     def stage(frame_rgb):
         if not (isinstance(frame_rgb, torch.Tensor) and frame_rgb.is_cuda):
             frame_rgb = _u8_on(frame_rgb, torch.device("cuda") if device is None else torch.device(device))
-        return model.upscale(frame_rgb, tile=tile, tile_pad=tile_pad, max_batch=max_batch)
+        return model.upscale(frame_rgb, tile=tile, tile_pad=tile_pad, max_batch=max_batch, tile_overlap=tile_overlap)
     return stage
 
 

@@ -10,6 +10,8 @@ tensor whose H and W are multiples of the window (transformers itself fails on a
 documented post-processing do (/ 255, symmetric padding to (n // 8 + 1) * 8, the model, the crop, clamp, x 255, round).  Both run
 on the ROCm device; calling the object with a uint8 HWC frame is ``upscale``.  ``upscale(frame, tile=T, tile_pad=P)`` cuts a large
 frame into windows of one shape that run as a batch (``tile_plan``), and ``forward_batch`` takes [N, C, H, W].
+``upscale(frame, tile=T, tile_overlap=O)`` is the Swin2SR authors' tiling instead: overlapped windows of the frame padded once to the
+window, their float outputs averaged where they overlap (``overlap_plan``).
 
 Supported: upsampler pixelshuffle (x2^n, x3), pixelshuffledirect, nearest+conv (x4); resi_connection "1conv"; patch_size 1;
 qkv_bias True; image_size > window_size; the same number of heads in every stage.  Anything else raises NesrUnsupportedError
@@ -228,14 +230,46 @@ class Swin2SR(_HFNet):
             _invoke("nesr_swin2sr_workspace_bytes", None, self._context(device), (int(win_h), int(win_w), int(batch), ctypes.byref(n)))
         return n.value
 
-    def upscale(self, frame, device=None, tile=0, tile_pad=16, max_batch=None):
+    def overlap_plan(self, h, w, tile, tile_overlap):
+        """The plan `upscale(tile=, tile_overlap=)` follows on an h x w frame, as the library computes it (needs no device):
+        {"tiles": (tiles_y, tiles_x), "tile": t, "padded": (hp, wp), "plan": int32 array [windows, 4]}, a row (win_y, win_x, out_y,
+        out_x) per t x t window in row-major order: its origin in the frame padded to hp x wp (multiples of the window), in input
+        and in output pixels.  t = min(tile, hp, wp); the last window of an axis ends at the padded frame's edge."""
+        lib = _lib.load()
+        args = (int(self.config["upscale"]), int(self.config["window_size"]), int(h), int(w), int(tile), int(tile_overlap))
+        ty, tx, t, hp, wp = (ctypes.c_int(0) for _ in range(5))
+        counts = tuple(ctypes.byref(v) for v in (ty, tx, t, hp, wp))
+        _lib.check(lib.nesr_swin2sr_overlap_plan(*args, *counts, None, 0), "nesr_swin2sr_overlap_plan")
+        plan = np.zeros((ty.value * tx.value, 4), np.int32)
+        _lib.check(lib.nesr_swin2sr_overlap_plan(*args, *counts, plan.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), plan.size), "nesr_swin2sr_overlap_plan")
+        return {"tiles": (ty.value, tx.value), "tile": t.value, "padded": (hp.value, wp.value), "plan": plan}
+
+    def overlap_workspace_bytes(self, h, w, tile, tile_overlap, batch=1, device=None):
+        """Bytes `upscale(tile=, tile_overlap=)` allocates on the context of `device` for an h x w frame with `batch` windows a
+        launch: the network's workspace of the windows, their float32 outputs, and the accumulator of the padded output."""
+        device = torch.device("cuda" if device is None else device)
+        n = ctypes.c_size_t(0)
+        with torch.cuda.device(device):
+            _invoke("nesr_swin2sr_overlap_workspace_bytes", None, self._context(device),
+                    (int(h), int(w), int(tile), int(tile_overlap), int(batch), ctypes.byref(n)))
+        return n.value
+
+    def upscale(self, frame, device=None, tile=0, tile_pad=16, max_batch=None, tile_overlap=None):
         """[H, W, 3] uint8 RGB frame -> the uint8 frame [H s, W s, 3] on the device.  `frame` is a tensor on the device, or an
         ndarray, which is copied up once (to `device`, default the current ROCm device).
 
         tile = 0: the whole frame at once; the workspace grows with it.  tile = T > 0: the frame is cut into cores of T x T input
         pixels, each run inside a window of T + 2 tile_pad (see tile_plan), treated exactly as a frame of its own; windows share
         launches, `max_batch` at a time (None: as many as fit the library's workspace budget).  The result does not depend on
-        max_batch; a frame no larger than T + 2 tile_pad is one window and gives the bits of tile = 0."""
+        max_batch; a frame no larger than T + 2 tile_pad is one window and gives the bits of tile = 0.
+
+        tile_overlap = O (an integer; None, the default, is the route above) with tile = T > 0 selects the Swin2SR authors' tiling
+        instead (see overlap_plan): the frame is padded once to the window, T x T windows step by T - O, the last one of an axis
+        ends at the edge, every window's float output is added up and each pixel divided by the number of windows that covered
+        it.  No window is padded; tile_pad has no meaning there and must be left alone."""
+        if tile_overlap is not None and (int(tile) == 0 or tile_pad != 16):
+            raise ValueError(f"Swin2SR.upscale: tile_overlap={tile_overlap!r} selects the overlapped route, which needs tile > 0 and takes no "
+                             f"tile_pad (got tile={tile!r}, tile_pad={tile_pad!r}); leave tile_overlap=None for cores with a tile_pad of context")
         if isinstance(frame, np.ndarray):
             frame = torch.from_numpy(np.ascontiguousarray(frame)).to(torch.device("cuda") if device is None else torch.device(device))
         frame = self._frame_u8(frame, "upscale", "frame")
@@ -243,7 +277,12 @@ class Swin2SR(_HFNet):
         tile = int(tile)
         with torch.cuda.device(frame.device):
             handle = self._context(frame.device)
-            if tile == 0:
+            if tile_overlap is not None:
+                s = int(self.config["upscale"])
+                out = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=frame.device)
+                _invoke("nesr_swin2sr_upscale_overlapped_u8", frame.device, handle,
+                        (frame, h, w, tile, int(tile_overlap), 0 if max_batch is None else int(max_batch), out, out.numel()))
+            elif tile == 0:
                 out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=frame.device)
                 _invoke("nesr_swin2sr_upscale_u8", frame.device, handle, (frame, h, w, out, out.numel()))
             else:
