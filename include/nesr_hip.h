@@ -1124,6 +1124,52 @@ int nesr_swin2sr_set_dtype(nesr_swin2sr* ctx, int dtype);
 int nesr_swin2sr_part_f32(nesr_swin2sr* ctx, int part, int stage, int layer, const float* in_dev, int N, int H, int W, float* out_dev, size_t capacity,
                           void* hip_stream);
 
+/*
+ * ---- The x4 diffusion upscaler's VAE decoder (csrc/vae.hip, vae_api.cpp) -- vae.VaeDecoder.
+ *
+ * diffusers' AutoencoderKL.decode as StableDiffusionUpscalePipeline calls it: post_quant_conv, conv_in, the mid block (ResnetBlock,
+ * single-head attention, ResnetBlock), one UpDecoderBlock2D per entry of block_out_channels in reverse (layers_per_block + 1
+ * ResnetBlocks, then nearest x2 + 3x3 conv on every block but the last), GroupNorm, SiLU, conv_out.  f32 throughout: diffusers
+ * itself upcasts this VAE.  The output is 2^(num_blocks - 1) times the latent grid.
+ *
+ * nesr_vae_create takes the configuration's fields by name.  Supported: 2 .. 4 entries of block_out_channels, each a multiple of
+ * norm_num_groups and at most 512; layers_per_block 1 .. 4; latent_channels 1 .. 8; out_channels 1 .. 4; act_fn "silu".  Anything
+ * else is NESR_ERR_UNSUPPORTED before any device is touched, and the text names the field.  device_id NESR_VAE_NO_DEVICE gives the
+ * context without a device: load_weight, finalize and the size queries do their host side, every entry that would launch is
+ * NESR_ERR_STATE.
+ *
+ * nesr_vae_load_weight: keys are diffusers' state_dict names (post_quant_conv.weight, decoder.mid_block.attentions.0.to_q.weight,
+ * ...); the attention's legacy names query, key, value, proj_attn are the same tensors.  Strict: an unexpected key or another
+ * shape is NESR_ERR_ARG (a caller drops encoder.* and quant_conv.* first); nesr_vae_finalize: a missing key is NESR_ERR_STATE.
+ *
+ * nesr_vae_decode_f32: z_dev [1, latent_channels, h, w] f32 -> sample_dev [1, out_channels, h s, w s] f32 (capacity counts
+ * floats).  nesr_vae_decode_latents_u8 (out_channels 3): latents_dev of the same shape -> the frame [h s, w s, 3] u8 RGB:
+ * latents / scaling_factor, decode, / 2 + 0.5, clamp to [0, 1], x 255, round half to even (capacity counts bytes).  N = 1.
+ * h w may not exceed NESR_VAE_MAX_TOKENS (the attention's limit) nor h s x w s 2^24 pixels: NESR_ERR_ARG.  The workspace grows
+ * with the frame (nesr_vae_workspace_bytes says to what; NESR_ERR_NOMEM when it cannot).  No atomics anywhere: a call repeated
+ * gives the same bits.  nesr_vae_output_size touches no device and needs no context.
+ */
+#define NESR_VAE_NO_DEVICE (-1)
+#define NESR_VAE_MAX_TOKENS (1 << 16)
+typedef struct nesr_vae nesr_vae;
+int nesr_vae_create(nesr_vae** out, int device_id, int latent_channels, int out_channels, int num_blocks, const int* block_out_channels,
+                    int layers_per_block, int norm_num_groups, double scaling_factor, const char* act_fn);
+void nesr_vae_destroy(nesr_vae* ctx);
+int nesr_vae_num_tensors(const nesr_vae* ctx);
+int nesr_vae_load_weight(nesr_vae* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim);
+int nesr_vae_finalize(nesr_vae* ctx);
+int nesr_vae_output_size(int num_blocks, int h, int w, int* out_h, int* out_w);
+int nesr_vae_workspace_bytes(nesr_vae* ctx, int h, int w, size_t* bytes);
+int nesr_vae_decode_f32(nesr_vae* ctx, const float* z_dev, int N, int C, int h, int w, float* sample_dev, size_t capacity, void* hip_stream);
+int nesr_vae_decode_latents_u8(nesr_vae* ctx, const float* latents_dev, int N, int C, int h, int w, uint8_t* out_dev, size_t capacity,
+                               void* hip_stream);
+/* Kernel groups of nesr_vae_kernel_time_ms, as nesr_swin2sr_kernel_time_ms: the 3x3 convs, the GroupNorm statistics, the streamed
+ * attention, the 1x1 products (post_quant_conv, shortcuts, q | k | v, to_out, and the latents' transposition), the nearest-x2 convs. */
+enum { NESR_VAE_GROUP_CONV = 0, NESR_VAE_GROUP_NORM = 1, NESR_VAE_GROUP_ATTENTION = 2, NESR_VAE_GROUP_PROJ = 3, NESR_VAE_GROUP_UPSAMPLE = 4,
+       NESR_VAE_GROUPS = 5 };
+int nesr_vae_set_timing(nesr_vae* ctx, int enable);
+int nesr_vae_kernel_time_ms(nesr_vae* ctx, double* group_ms, int n_groups, int64_t* launches);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

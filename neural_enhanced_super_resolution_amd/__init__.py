@@ -15,7 +15,8 @@ from .srvgg import SRVGGNetCompact, srvgg_state_dict_spec  # noqa: F401
 from .realesrganer import RealESRGANer  # noqa: F401
 from .segformer import SegFormer, segformer_state_dict_spec  # noqa: F401
 from .swin2sr import Swin2SR, swin2sr_state_dict_spec  # noqa: F401
+from .vae import VaeDecoder, vae_state_dict_spec  # noqa: F401
 
-__all__ = ["RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "Swin2SR", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
-           "srvgg_state_dict_spec", "swin2sr_state_dict_spec"]
+__all__ = ["RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "Swin2SR", "VaeDecoder", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
+           "srvgg_state_dict_spec", "swin2sr_state_dict_spec", "vae_state_dict_spec"]
 __version__ = "0.1.0"

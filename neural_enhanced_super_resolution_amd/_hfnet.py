@@ -1,5 +1,5 @@
-"""``_HFNet``: what ``SegFormer`` and ``Swin2SR`` share, the two models that take a ``transformers`` checkpoint and run as a chain of
-launches behind their own entries of the C ABI (``nesr_segformer_*``, ``nesr_swin2sr_*``; their C side shares csrc/state_dict.h
+"""``_HFNet``: what ``SegFormer``, ``Swin2SR`` and ``VaeDecoder`` share, the models that take a ``transformers`` or ``diffusers``
+checkpoint and run as a chain of launches behind their own entries of the C ABI (``nesr_segformer_*``, ``nesr_swin2sr_*``, ``nesr_vae_*``; their C side shares csrc/state_dict.h
 and the GroupTimer of csrc/api_common.h in the same way).
 
 The base owns the parameter tree built from the subclass's spec, the checkpoint reader, one context per device with the current
@@ -36,6 +36,7 @@ class _Holder(nn.Module):
 class _HFNet(nn.Module):
     PREFIX = NAME = TRAIN_ERROR = _spec = None
     KERNEL_GROUPS = ()
+    CHECKPOINT_FILES = ("model.safetensors", "pytorch_model.bin")      # what from_checkpoint looks for in a directory
 
     def __init__(self, config):
         super().__init__()
@@ -78,17 +79,17 @@ class _HFNet(nn.Module):
     @classmethod
     def from_checkpoint(cls, path, **cfg):
         """A model with the weights of a local ``model.safetensors`` or ``pytorch_model.bin`` (or of the directory that holds
-        one).  Anything that is not an existing local path raises: nothing is ever fetched (the reference's
+        one; a subclass names its files in CHECKPOINT_FILES).  Anything that is not an existing local path raises: nothing is ever fetched (the reference's
         from_pretrained(hub id), nesr/nesr.py:291-296, is a network download)."""
         path = os.fspath(path)
         if os.path.isdir(path):
-            for name in ("model.safetensors", "pytorch_model.bin"):
+            for name in cls.CHECKPOINT_FILES:
                 if os.path.isfile(os.path.join(path, name)):
                     path = os.path.join(path, name)
                     break
         if not os.path.isfile(path):
             raise FileNotFoundError(f"{cls.NAME}.from_checkpoint: {path!r} is not a local checkpoint file (a hub id is not fetched: "
-                                    "pass the path of a downloaded model.safetensors or pytorch_model.bin)")
+                                    "pass the path of a downloaded " + " or ".join(cls.CHECKPOINT_FILES) + ")")
         if path.endswith(".safetensors"):
             from safetensors.torch import load_file
             sd = load_file(path, device="cpu")
