@@ -1170,6 +1170,56 @@ enum { NESR_VAE_GROUP_CONV = 0, NESR_VAE_GROUP_NORM = 1, NESR_VAE_GROUP_ATTENTIO
 int nesr_vae_set_timing(nesr_vae* ctx, int enable);
 int nesr_vae_kernel_time_ms(nesr_vae* ctx, double* group_ms, int n_groups, int64_t* launches);
 
+/*
+ * ---- The x4 diffusion upscaler's UNet (csrc/unet.hip, unet_api.cpp) -- unet.UNet2DCondition.
+ *
+ * diffusers' UNet2DConditionModel.forward as StableDiffusionUpscalePipeline calls it: the timestep's sinusoid through
+ * time_embedding plus the class row (the pipeline's noise level), conv_in, the down blocks (ResnetBlocks, each followed by a
+ * Transformer in a CrossAttnDownBlock2D, then a stride-2 conv), the mid block, the up blocks over cat(hidden, skip) (then nearest
+ * x2 + conv), GroupNorm, SiLU, conv_out.  f32 throughout.  The output has the input's grid.
+ *
+ * nesr_unet_create takes the configuration's fields by name; attention_head_dim is, as in this model family, the NUMBER of heads
+ * of every block.  Supported: 2 .. 4 levels; block types DownBlock2D, CrossAttnDownBlock2D, UpBlock2D, CrossAttnUpBlock2D and the
+ * mid block UNetMidBlock2DCrossAttn; layers_per_block 1 .. 3; widths up to 1024 that are multiples of norm_num_groups and, where
+ * the level has attention, of the heads, with a head width of 8 .. 128 that is a multiple of 8; cross_attention_dim up to 1024;
+ * in_channels and out_channels up to 16; use_linear_projection true; one transformer layer; no dual_cross_attention; act_fn "silu";
+ * flip_sin_to_cos true, freq_shift 0, downsample_padding 1; a class embedding table.  Anything else is NESR_ERR_UNSUPPORTED before
+ * any device is touched, and the text names the field.  only_cross_attention has one flag a level (down block order); up block i
+ * takes the flag and the width of level num_blocks - 1 - i.  device_id NESR_UNET_NO_DEVICE gives the context without a device.
+ *
+ * nesr_unet_load_weight: keys are diffusers' state_dict names (time_embedding.linear_1.weight, down_blocks.1.attentions.0.
+ * transformer_blocks.0.attn1.to_q.weight, ...).  Strict, as nesr_vae_load_weight.
+ *
+ * nesr_unet_forward_f32: sample_dev [n, in_channels, h, w] f32, text_states_dev [n, tokens, cross_attention_dim] f32 ->
+ * out_dev [n, out_channels, h, w] f32; out_elems must be exactly that count.  n is 1 or 2: the samples share the timestep and
+ * the class label and carry their own text states (classifier-free guidance).  h and w are multiples of 2^(num_blocks - 1),
+ * tokens is 1 .. NESR_UNET_MAX_TEXT_TOKENS, class_label indexes the table, a self-attention takes at most 65536 tokens: otherwise
+ * NESR_ERR_ARG before any launch.  The workspace holds the skip stack and grows with the frame (NESR_ERR_NOMEM when it cannot).
+ * No atomics anywhere: a call repeated gives the same bits, and a sample's result does not depend on n.
+ */
+#define NESR_UNET_NO_DEVICE (-1)
+#define NESR_UNET_MAX_TEXT_TOKENS 256
+typedef struct nesr_unet nesr_unet;
+int nesr_unet_create(nesr_unet** out, int device_id, int in_channels, int out_channels, int num_blocks, const int* block_out_channels,
+                     const char* const* down_block_types, const char* const* up_block_types, const char* mid_block_type,
+                     const int* only_cross_attention, int layers_per_block, int attention_head_dim, int cross_attention_dim,
+                     int transformer_layers_per_block, int use_linear_projection, int dual_cross_attention, int num_class_embeds,
+                     int norm_num_groups, double norm_eps, int flip_sin_to_cos, double freq_shift, int downsample_padding, const char* act_fn);
+void nesr_unet_destroy(nesr_unet* ctx);
+int nesr_unet_num_tensors(const nesr_unet* ctx);
+int nesr_unet_load_weight(nesr_unet* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim);
+int nesr_unet_finalize(nesr_unet* ctx);
+int nesr_unet_workspace_bytes(nesr_unet* ctx, int n, int h, int w, int tokens, size_t* bytes);
+int nesr_unet_forward_f32(nesr_unet* ctx, const float* sample_dev, int n, int c, int h, int w, double timestep, int class_label,
+                          const float* text_states_dev, int tokens, float* out_dev, size_t out_elems, void* hip_stream);
+/* Kernel groups of nesr_unet_kernel_time_ms: the 3x3 convs, the GroupNorm and LayerNorm statistics, the streamed attention, the
+ * projections (proj_in / proj_out, q, k | v, to_out, shortcuts, the inputs' transposition), the feed-forward's two products, the
+ * embedding path, the stride-2 and nearest-x2 convs. */
+enum { NESR_UNET_GROUP_CONV = 0, NESR_UNET_GROUP_NORM = 1, NESR_UNET_GROUP_ATTENTION = 2, NESR_UNET_GROUP_PROJ = 3, NESR_UNET_GROUP_FF = 4,
+       NESR_UNET_GROUP_EMBEDDING = 5, NESR_UNET_GROUP_RESAMPLE = 6, NESR_UNET_GROUPS = 7 };
+int nesr_unet_set_timing(nesr_unet* ctx, int enable);
+int nesr_unet_kernel_time_ms(nesr_unet* ctx, double* group_ms, int n_groups, int64_t* launches);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

@@ -1,5 +1,5 @@
-"""``_HFNet``: what ``SegFormer``, ``Swin2SR`` and ``VaeDecoder`` share, the models that take a ``transformers`` or ``diffusers``
-checkpoint and run as a chain of launches behind their own entries of the C ABI (``nesr_segformer_*``, ``nesr_swin2sr_*``, ``nesr_vae_*``; their C side shares csrc/state_dict.h
+"""``_HFNet``: what ``SegFormer``, ``Swin2SR``, ``VaeDecoder`` and ``UNet2DCondition`` share, the models that take a ``transformers`` or ``diffusers``
+checkpoint and run as a chain of launches behind their own entries of the C ABI (``nesr_segformer_*``, ``nesr_swin2sr_*``, ``nesr_vae_*``, ``nesr_unet_*``; their C side shares csrc/state_dict.h
 and the GroupTimer of csrc/api_common.h in the same way).
 
 The base owns the parameter tree built from the subclass's spec, the checkpoint reader, one context per device with the current

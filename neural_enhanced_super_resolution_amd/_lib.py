@@ -201,6 +201,18 @@ SIGNATURES = {
     "nesr_vae_decode_latents_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_vae_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_vae_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
+    "nesr_unet_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_char_p),
+                                    _c.POINTER(_c.c_char_p), _c.c_char_p, _c.POINTER(_c.c_int), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                    _c.c_int, _c.c_double, _c.c_int, _c.c_double, _c.c_int, _c.c_char_p]),
+    "nesr_unet_destroy": (None, [_c.c_void_p]),
+    "nesr_unet_num_tensors": (_c.c_int, [_c.c_void_p]),
+    "nesr_unet_load_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "nesr_unet_finalize": (_c.c_int, [_c.c_void_p]),
+    "nesr_unet_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "nesr_unet_forward_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double, _c.c_int, _c.c_void_p, _c.c_int,
+                                         _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_unet_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_unet_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),
