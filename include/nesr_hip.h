@@ -1220,6 +1220,45 @@ enum { NESR_UNET_GROUP_CONV = 0, NESR_UNET_GROUP_NORM = 1, NESR_UNET_GROUP_ATTEN
 int nesr_unet_set_timing(nesr_unet* ctx, int enable);
 int nesr_unet_kernel_time_ms(nesr_unet* ctx, double* group_ms, int n_groups, int64_t* launches);
 
+/*
+ * Single-launch entries of the UNet's kernels (test hooks for the per-launch parity tests, csrc/unet_kernel_api.cpp; not pipeline
+ * entries): each fills one launcher's arguments, field for field as csrc/unet_api.h documents them, and makes that one launch on
+ * hip_stream.  Asynchronous; no context, nothing allocated, no state changed.  Every pointer is a DEVICE pointer in the kernels'
+ * own layout, which the caller packs: activations are rows [n m][cs], cs = the width rounded up to 16 and the columns past the
+ * width zero; a weight matrix is Wt[K][N], a conv's [9 (cinp0 + cinp1)][coutp] with each source's K rounded up to 4; a norm is
+ * [n][cs] x (mean hi, mean lo, gamma rstd, beta) f32; LayerNorm statistics are [m] x (mean hi, mean lo, rstd, 0) f32.  A second
+ * source is absent when in1_dev is null.  What a launcher refuses is NESR_ERR_ARG with nothing launched (nesr_last_error names
+ * the launcher); the extents are not checked against the buffers, which are the caller's.
+ *   nesr_unet_k_in                NCHW [n][c][m] (rows = n m) or row-major [rows][c] -> rows [rows][cs]
+ *   nesr_unet_k_embedding         silu(linear_2(silu(linear_1([cos | sin](t)))) + the class row) -> out [tdp]
+ *   nesr_unet_k_temb              out[r][0 .. coutp[r]) of [count][1024] = weights[cb + c] + weights[b + c] + sum_k semb[k] weights[w + k coutp + c]
+ *                                 (the offset and coutp arrays are HOST arrays of `count` entries, offsets in floats)
+ *   nesr_unet_k_conv              3x3 / pad 1 over one or two sources, GroupNorm + SiLU in the loader where a norm is given; stride 1
+ *                                 (up: over the nearest-x2 grid of (H / 2) x (W / 2) rows) or stride 2 (the input grid is 2H x 2W);
+ *                                 H x W is the OUTPUT grid; + res; rows [n H W][coutp] or NCHW [n][cout][H][W]
+ *   nesr_unet_k_group_norm        the statistics of one or two sources side by side in `groups` groups (a partial launch per source, then
+ *                                 the finish): norm0_dev / norm1_dev are the OUTPUT, partial*_dev [n][ceil(m / 512)][cs][2] f64 scratch
+ *   nesr_unet_k_layer_norm_stats  per row of [m][cs] the mean and 1 / sqrt(var + eps) over the c real columns
+ *   nesr_unet_k_rows              rows -> prologue (0 none | 1 GroupNorm | 2 LayerNorm) -> x Wt + b -> (+ res | GEGLU) -> out [m][np]
+ *   nesr_unet_k_attention         softmax(q k^T / sqrt(d)) v per sample and head; out [samples nq][ldo], its columns past heads d zeroed
+ */
+int nesr_unet_k_in(const float* src_dev, int nchw, int c, int cs, int m, long long rows, float* out_dev, void* hip_stream);
+int nesr_unet_k_embedding(double timestep, int c0, int td, int tdp, const float* w1_dev, const float* b1_dev, const float* w2_dev, const float* b2_dev,
+                          const float* cls_dev, float* out_dev, void* hip_stream);
+int nesr_unet_k_temb(int count, int td, const float* semb_dev, const float* weights_dev, const unsigned long long* w_offset,
+                     const unsigned long long* b_offset, const unsigned long long* cb_offset, const int* coutp, float* out_dev, void* hip_stream);
+int nesr_unet_k_conv(int n, int H, int W, int stride, int up, const float* in0_dev, int c0, int cs0, const void* norm0_dev, const float* in1_dev, int c1,
+                     int cs1, const void* norm1_dev, const float* w_dev, const float* bias_dev, int cout, int coutp, const float* res_dev, int out_nchw,
+                     float* out_dev, void* hip_stream);
+int nesr_unet_k_group_norm(int n, int m, const float* in0_dev, int c0, int cs0, void* norm0_dev, double* partial0_dev, const float* in1_dev, int c1, int cs1,
+                           void* norm1_dev, double* partial1_dev, int groups, const float* gamma_dev, const float* beta_dev, float eps, void* hip_stream);
+int nesr_unet_k_layer_norm_stats(const float* in_dev, int m, int c, int cs, float eps, void* out_dev, void* hip_stream);
+int nesr_unet_k_rows(int m, int rows_per_sample, const float* in0_dev, int c0, int cs0, const void* norm0_dev, const float* in1_dev, int c1, int cs1,
+                     const void* norm1_dev, int prologue, const void* ln_dev, const float* ln_g_dev, const float* ln_b_dev, const float* w_dev,
+                     const float* b_dev, int ldw, int np, int geglu, const float* res_dev, float* out_dev, void* hip_stream);
+int nesr_unet_k_attention(int samples, int nq, int nk, int heads, int d, const float* q_dev, const float* k_dev, const float* v_dev, int ldq, int ldkv,
+                          int ldo, float* out_dev, void* hip_stream);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

@@ -213,6 +213,21 @@ SIGNATURES = {
                                          _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_unet_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_unet_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
+    "nesr_unet_k_in": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_longlong, _c.c_void_p, _c.c_void_p]),
+    "nesr_unet_k_embedding": (_c.c_int, [_c.c_double, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p]),
+    "nesr_unet_k_temb": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_ulonglong), _c.POINTER(_c.c_ulonglong),
+                                    _c.POINTER(_c.c_ulonglong), _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
+    "nesr_unet_k_conv": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                    _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "nesr_unet_k_group_norm": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                          _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p]),
+    "nesr_unet_k_layer_norm_stats": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p]),
+    "nesr_unet_k_rows": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                    _c.c_void_p]),
+    "nesr_unet_k_attention": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                         _c.c_void_p, _c.c_void_p]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),
