@@ -1259,6 +1259,32 @@ int nesr_unet_k_rows(int m, int rows_per_sample, const float* in0_dev, int c0, i
 int nesr_unet_k_attention(int samples, int nq, int nk, int heads, int d, const float* q_dev, const float* k_dev, const float* v_dev, int ldq, int ldkv,
                           int ldo, float* out_dev, void* hip_stream);
 
+/*
+ * Single-launch entries of the VAE decoder's kernels (test hooks as the nesr_unet_k_* above, csrc/vae_kernel_api.cpp): each fills
+ * one launcher's arguments, field for field as csrc/vae_api.h documents them, and makes that one launch on hip_stream.
+ * Asynchronous; no context, nothing allocated, no state changed.  Every pointer is a DEVICE pointer in the kernels' own layout:
+ * rows [H W][cs], a 3x3 weight [9 cinp][coutp] with cinp the input width rounded up to 4, a 1x1 weight [cs_in][np], a norm
+ * [cs] x (mean hi, mean lo, gamma rstd, beta) f32.  What a launcher refuses is NESR_ERR_ARG with nothing launched
+ * (nesr_last_error names the launcher); the extents are not checked against the buffers, which are the caller's.
+ *   nesr_vae_k_in          z NCHW [c][m] -> rows [m][16], each value divided by `divisor`; the columns past c zero
+ *   nesr_vae_k_conv        3x3 / pad 1 on the H x W grid; in_mode 0 rows | 1 the nearest-x2 grid of (H / 2) x (W / 2) rows; GroupNorm +
+ *                          SiLU in the loader where a norm is given; + bias + res[.][cs_res]; out_mode 0 rows [H W][cs_out = coutp] |
+ *                          1 NCHW f32 [cout][H][W] | 2 HWC u8 [H][W][cout] (v / 2 + 0.5, clamp, x 255, round to nearest even)
+ *   nesr_vae_k_group_norm  the statistics of rows [m][cs] in `groups` groups (the partial launch, then the finish): norm_dev [cs] is the
+ *                          OUTPUT, partial_dev [ceil(m / 512)][cs][2] f64 scratch
+ *   nesr_vae_k_rows        rows [m][cs_in] -> (norm, no activation) -> x Wt + b -> + res -> out [m][np]; out may be in when np == cs_in
+ *   nesr_vae_k_attention   qkv [n][3 cs] (q | k | v) -> out [n][cs] = softmax(q k^T / sqrt(c)) v, one head
+ */
+int nesr_vae_k_in(const float* z_dev, int c, int m, float divisor, float* out_dev, void* hip_stream);
+int nesr_vae_k_conv(int in_mode, const float* in_dev, int H, int W, int cin, int cinp, int cs_in, const void* norm_dev, const float* w_dev,
+                    const float* bias_dev, int cout, int coutp, const float* res_dev, int cs_res, int out_mode, void* out_dev, int cs_out,
+                    void* hip_stream);
+int nesr_vae_k_group_norm(const float* in_dev, int m, int c, int cs, int groups, double* partial_dev, const float* gamma_dev, const float* beta_dev,
+                          float eps, void* norm_dev, void* hip_stream);
+int nesr_vae_k_rows(int m, int cs_in, int np, const float* in_dev, const void* norm_dev, const float* w_dev, const float* b_dev, const float* res_dev,
+                    float* out_dev, void* hip_stream);
+int nesr_vae_k_attention(int n, int c, int cs, const float* qkv_dev, float* out_dev, void* hip_stream);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

@@ -228,6 +228,13 @@ SIGNATURES = {
                                     _c.c_void_p]),
     "nesr_unet_k_attention": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                          _c.c_void_p, _c.c_void_p]),
+    "nesr_vae_k_in": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_float, _c.c_void_p, _c.c_void_p]),
+    "nesr_vae_k_conv": (_c.c_int, [_c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                   _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "nesr_vae_k_group_norm": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p,
+                                         _c.c_void_p]),
+    "nesr_vae_k_rows": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "nesr_vae_k_attention": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),
