@@ -112,6 +112,25 @@ inline int grow(char*& buf, size_t& have, size_t bytes, const char* what) {
     return NESR_OK;
 }
 
+// A create entry's device argument: `device_id` is `no_device` (the host side alone, no HIP call is made) or names a device.
+inline int check_device(int device_id, int no_device) {
+    if (device_id == no_device) return NESR_OK;
+    int ndev = 0;
+    const hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+    if (device_id < 0 || device_id >= ndev) return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
+    return NESR_OK;
+}
+
+// What a single-launch test hook (`entry`, nesr_vae_k_* / nesr_unet_k_*) returns for its launcher's result; `header` is the file
+// that states what the launcher takes.
+inline int launch_done(hipError_t e, const char* header, const char* entry, const char* launcher) {
+    if (e == hipSuccess) return NESR_OK;
+    if (e == hipErrorInvalidValue)
+        return set_error(NESR_ERR_ARG, std::string(entry) + ": " + launcher + " refused the arguments (" + header + " states what it takes); nothing was launched");
+    return set_error(NESR_ERR_HIP, std::string(entry) + ": " + launcher + ": " + hipGetErrorString(e));
+}
+
 // The one weight buffer of a model: the old one is freed (after the device's work), `host` goes up in one copy.
 inline int upload_weights(int device, float*& d_w, const std::vector<float>& host, const char* what) {
     NESR_TRY(hipSetDevice(device));

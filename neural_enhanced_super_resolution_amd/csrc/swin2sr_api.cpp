@@ -382,12 +382,9 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
             return unsupported("window_size / embed_dim / mlp_ratio", "a window's tokens, a head's q, k, v and its scores (or 32 rows of the MLP) do not fit the 160 KiB of LDS");
         }
     }
-    int ndev = 0;
-    hipError_t e = device_id == NESR_SWIN2SR_NO_DEVICE ? hipSuccess : hipGetDeviceCount(&ndev);      // no device: the host side alone
-    if (device_id != NESR_SWIN2SR_NO_DEVICE && (e != hipSuccess || device_id < 0 || device_id >= ndev)) {
+    if (const int rc = check_device(device_id, NESR_SWIN2SR_NO_DEVICE)) {
         delete c;
-        if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-        return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
+        return rc;
     }
     StateDict& sd = c->sd;
     const int64_t C = c->C, hid = c->hidden, nf = kFeatures;

@@ -1,7 +1,13 @@
 // The UNet of the x4 diffusion upscaler (diffusers' UNet2DConditionModel.forward) for gfx950: f32 storage, every product of a
 // conv, a projection and the attention on the f32-input MFMA (v_mfma_f32_16x16x4_f32, an exact f32 fmaf chain).  tests/unet_ref.py
-// is the restatement the kernels are held to.  The layout, the operand maps and the GroupNorm scheme are those of vae.hip; the
-// kernels are this file's own because they take two samples, widths up to 1024 and inputs of two sources.
+// is the restatement the kernels are held to.  The layout, the operand maps and the GroupNorm scheme are those of vae.hip.
+//
+// Shared with vae.hip, one copy in f32_rows_device.h: the conv's patch loader and tap loop, the GroupNorm partial sums, moments and
+// VaeNorm, the attention's score tile, softmax step and P V.  They fix the order of every sum, so both files' pins hold the same bits.
+// This file's own: every kernel's prologue and epilogue, because a launch takes two samples (a sample index in the grid), a conv and
+// a GroupNorm take two sources (the loop over them, the seam in the finish's gather), the downsampler is the conv at stride 2, and
+// the attention has heads of up to 128 columns padded to 16 (its chunk loader, its static LDS, its pad columns); and whole kernels
+// with no counterpart: the K-tiled row GEMM with LayerNorm and GEGLU, the LayerNorm statistics, the embedding, the inputs.
 //
 // A workgroup is 256 threads (4 waves):
 //
@@ -13,7 +19,7 @@
 //                           the input through LDS in K chunks of 64 / S channels of the (3 + 4 S - S) x (3 + 16 S - S) patch.
 //                           S = 1 reads rows or their nearest-x2 grid; S = 2 is the downsampler.  Two sources run one after the
 //                           other through the same patch buffer: cat(hidden, skip) is never stored.  GroupNorm + SiLU in the
-//                           loader on every tap inside the image.
+//                           loader on every tap inside the image.  Loader and tap loop: conv_load_patch<S>, conv_taps<S>.
 //   unet_gn_partial_kernel  GroupNorm statistics as in vae.hip (double sums per 512 pixels and channel, then one workgroup a group
 //   unet_gn_finish_kernel   and sample in a fixed order); the finish reads two sources' partial sums, so a group may straddle the seam.
 //   unet_ln_stats_kernel    LayerNorm: one wave a row, two passes (mean, then the squared deviations), sums in double.
@@ -28,16 +34,12 @@
 // one of two.
 #include "unet_api.h"
 
+#include "f32_rows_device.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float normed(float v, const VaeNorm& n) { return ((v - n.mean_hi) - n.mean_lo) * n.a + n.beta; }
 __device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
 
 // ---------------------------------------------------------------------------------------------------------------- inputs
@@ -98,17 +100,10 @@ __global__ __launch_bounds__(256) void unet_temb_kernel(const UnetTemb a) {
 // ---------------------------------------------------------------------------------------------------------------- conv 3x3
 constexpr int CV_TW = VAE_CONV_TW, CV_TH = VAE_CONV_TH, CV_NB = VAE_CONV_NB;
 template <int S>
-struct ConvGeom {
-    static constexpr int KC = UNET_KC / S;
-    static constexpr int PW = CV_TW * S + 3 - S, PH = CV_TH * S + 3 - S;
-    static constexpr int LD = KC + 4;      // = 4 (mod 32)
-};
-
-template <int S>
 __global__ __launch_bounds__(256) void unet_conv_kernel(const UnetConv a) {
     typedef ConvGeom<S> G;
-    __shared__ float lds[G::PH * G::PW * G::LD];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    __shared__ float lds[G::FLOATS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x0 = blockIdx.x * CV_TW, y0 = blockIdx.y * CV_TH;
     const int nblk = (a.coutp + CV_NB - 1) / CV_NB, sample = blockIdx.z / nblk, blk = blockIdx.z - sample * nblk;
     const int ntiles = a.coutp >> 4, ni0 = blk * (CV_NB / 16) + wave * 2;
@@ -132,55 +127,12 @@ __global__ __launch_bounds__(256) void unet_conv_kernel(const UnetConv a) {
         const float* base = src.p + (size_t)sample * sm * src.cs;
         const VaeNorm* norm = src.norm ? src.norm + (size_t)sample * src.cs : nullptr;
         for (int c0 = 0; c0 < cseg; c0 += G::KC) {
-            const int kc = cseg - c0 < G::KC ? cseg - c0 : G::KC, nq = kc >> 2;
+            const int kc = cseg - c0 < G::KC ? cseg - c0 : G::KC;
             if (!first) __syncthreads();      // the chunk before is read
             first = false;
-            for (int idx = t; idx < G::PH * G::PW * nq; idx += 256) {
-                const int q = idx % nq, pos = idx / nq, px = pos % G::PW, py = pos / G::PW;
-                const int gy = y0 * S - 1 + py, gx = x0 * S - 1 + px;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (gy >= 0 && gy < DH && gx >= 0 && gx < DW) {
-                    const int sy = a.up ? gy >> 1 : gy, sx = a.up ? gx >> 1 : gx;
-                    const int c = c0 + q * 4;      // c + 3 < cseg <= cs
-                    v = *reinterpret_cast<const float4*>(base + ((size_t)sy * sw + sx) * src.cs + c);
-                    if (norm) {
-                        v.x = silu(normed(v.x, norm[c])), v.y = silu(normed(v.y, norm[c + 1]));
-                        v.z = silu(normed(v.z, norm[c + 2])), v.w = silu(normed(v.w, norm[c + 3]));
-                    }
-                }
-                *reinterpret_cast<float4*>(lds + pos * G::LD + q * 4) = v;
-            }
+            conv_load_patch<S>(lds, base, norm, src.cs, c0, kc, y0, x0, DH, DW, sw, a.up != 0);
             __syncthreads();
-            if (!work) continue;
-            for (int tap = 0; tap < 9; ++tap) {
-                const int ky = tap / 3, kx = tap - ky * 3;
-                const float* ap = lds + (ky * G::PW + (lane & 15) * S + kx) * G::LD + (lane >> 4);
-                const float* bp = a.w + (size_t)(tap * cinp + wrow + c0 + (lane >> 4)) * a.coutp + (lane & 15);
-                int c = 0;
-                for (; c + 16 <= kc; c += 16) {      // four weight fragments a tile in flight; the MFMAs stay in ascending c
-                    float b0[4], b1[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) b0[u] = bp[(size_t)(c + 4 * u) * a.coutp + ni0 * 16], b1[u] = bp[(size_t)(c + 4 * u) * a.coutp + ni1 * 16];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                        for (int i = 0; i < CV_TH; ++i) {
-                            const float av = ap[i * S * G::PW * G::LD + c + 4 * u];
-                            acc[0][i] = mfma4(av, b0[u], acc[0][i]);
-                            acc[1][i] = mfma4(av, b1[u], acc[1][i]);
-                        }
-                    }
-                }
-                for (; c < kc; c += 4) {
-                    const float b0 = bp[(size_t)c * a.coutp + ni0 * 16], b1 = bp[(size_t)c * a.coutp + ni1 * 16];
-#pragma unroll
-                    for (int i = 0; i < CV_TH; ++i) {
-                        const float av = ap[i * S * G::PW * G::LD + c];
-                        acc[0][i] = mfma4(av, b0, acc[0][i]);
-                        acc[1][i] = mfma4(av, b1, acc[1][i]);
-                    }
-                }
-            }
+            if (work) conv_taps<S>(lds, a.w, wrow + c0, cinp, a.coutp, kc, ni0, ni1, acc);
         }
     }
     if (!work) return;
@@ -209,39 +161,12 @@ __global__ __launch_bounds__(256) void unet_conv_kernel(const UnetConv a) {
 
 // ---------------------------------------------------------------------------------------------------------------- GroupNorm statistics
 __global__ __launch_bounds__(256) void unet_gn_partial_kernel(const UnetSrc src, int m, double* partial) {
-    __shared__ double red[256 * 8];
-    const int t = threadIdx.x, cs = src.cs, nq = cs >> 2, npl = 256 / nq;      // nq <= 256: at least one pixel lane
-    const int q4 = t % nq, pl = t / nq, sample = blockIdx.y;
-    const float* in = src.p + (size_t)sample * m * cs;
-    double* out = partial + ((size_t)sample * gridDim.x + blockIdx.x) * cs * 2;
-    const size_t p0 = (size_t)blockIdx.x * VAE_GN_PIXELS;
-    const size_t p1 = p0 + VAE_GN_PIXELS < (size_t)m ? p0 + VAE_GN_PIXELS : (size_t)m;
-    if (pl < npl) {
-        double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-        for (size_t p = p0 + pl; p < p1; p += npl) {
-            const float4 v = *reinterpret_cast<const float4*>(in + p * cs + q4 * 4);
-            const double e[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s[k] += e[k], ss[k] += e[k] * e[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            red[((size_t)pl * cs + q4 * 4 + k) * 2] = s[k];
-            red[((size_t)pl * cs + q4 * 4 + k) * 2 + 1] = ss[k];
-        }
-    }
-    __syncthreads();
-    for (int c = t; c < cs; c += 256) {
-        double s = 0.0, ss = 0.0;
-        for (int l = 0; l < npl; ++l) s += red[((size_t)l * cs + c) * 2], ss += red[((size_t)l * cs + c) * 2 + 1];
-        out[(size_t)c * 2] = s;
-        out[(size_t)c * 2 + 1] = ss;
-    }
+    const int cs = src.cs, sample = blockIdx.y;
+    gn_partial_block(src.p + (size_t)sample * m * cs, cs, m, partial + ((size_t)sample * gridDim.x + blockIdx.x) * cs * 2);
 }
 
 // block x = g < groups: group g of sample y; block `groups`: the padded channels, which normalise to zero
 __global__ __launch_bounds__(256) void unet_gn_finish_kernel(const UnetGn a, int nblocks) {
-    __shared__ double rs[256], rq[256];
     const int t = threadIdx.x, g = blockIdx.x, sample = blockIdx.y;
     const int c0 = a.in[0].c, c1 = a.in[1].p ? a.in[1].c : 0, cs0 = a.in[0].cs, cs1 = a.in[1].cs, cpg = (c0 + c1) / a.groups;
     VaeNorm* out0 = a.in[0].norm ? const_cast<VaeNorm*>(a.in[0].norm) + (size_t)sample * cs0 : nullptr;
@@ -261,21 +186,11 @@ __global__ __launch_bounds__(256) void unet_gn_finish_kernel(const UnetGn a, int
         const double* at = c < c0 ? p0 + (blk * cs0 + c) * 2 : p1 + (blk * cs1 + (c - c0)) * 2;
         s += at[0], ss += at[1];
     }
-    rs[t] = s, rq[t] = ss;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h) rs[t] += rs[t + h], rq[t] += rq[t + h];
-        __syncthreads();
-    }
-    const double n = (double)a.m * cpg, mean = rs[0] / n;
-    double var = rq[0] / n - mean * mean;      // biased; the moments are double
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    double mean, rstd;
+    gn_moments(s, ss, (double)a.m * cpg, a.eps, mean, rstd);
     for (int k = t; k < cpg; k += 256) {
         const int c = g * cpg + k;
-        VaeNorm o;
-        o.mean_hi = (float)mean, o.mean_lo = (float)(mean - (double)o.mean_hi);
-        o.a = (float)((double)a.gamma[c] * rstd), o.beta = a.beta[c];
+        const VaeNorm o = make_norm(mean, rstd, a.gamma[c], a.beta[c]);
         if (c < c0) out0[c] = o;
         else out1[c - c0] = o;
     }
@@ -414,6 +329,7 @@ __global__ __launch_bounds__(256) void unet_rows_kernel(const UnetRows a) {
 // zero filled; a chunk is 32 keys [32][dp + 4], then their values [32][dp + 16] through the same buffer; wave w owns the output
 // column tiles w and w + 4 of both 16-query halves.
 constexpr int AT_DP = UNET_MAX_HEAD, AT_S = UNET_ATTN_BK + 4;
+static_assert(AT_S == ATTN_LDS_S, "the score stride of the shared attention bodies");
 
 // rows k0 .. k0 + 31 of `src` (row stride ld_src; d real columns, zeros to dp and past row n) -> dst [32][ld_dst]
 __device__ __forceinline__ void attn_chunk(float* dst, int ld_dst, const float* src, size_t ld_src, int k0, int n, int d, int dp) {
@@ -444,70 +360,17 @@ __global__ __launch_bounds__(256) void unet_attn_kernel(const UnetAttn a) {
     const float root = sqrtf((float)a.d);
     const int row = t >> 3, sub = t & 7;       // the 8 threads of a query row: an eighth of a wave
     float m_run = -INFINITY, l_run = 0.f;      // the same in all 8
-    const int mi = wave >> 1, ni_s = wave & 1; // the wave's tile of S
 
     for (int k0 = 0; k0 < a.nk; k0 += BK) {
         __syncthreads();      // Q is there; the chunk before is done with KV, S and alpha
         attn_chunk(KV, ldc, kp, a.ldkv, k0, a.nk, a.d, dp);
         __syncthreads();
-        {
-            const float* ap = Q + (mi * 16 + (lane & 15)) * ldc + (lane >> 4);
-            const float* bp = KV + (ni_s * 16 + (lane & 15)) * ldc + (lane >> 4);
-            v4f s0 = v4f{0.f, 0.f, 0.f, 0.f}, s1 = s0;      // even and odd k steps: two chains in flight, added once
-            for (int k = 0; k < dp; k += 8) {
-                s0 = mfma4(ap[k], bp[k], s0);
-                s1 = mfma4(ap[k + 4], bp[k + 4], s1);
-            }
-            const int j = ni_s * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[(mi * 16 + (lane >> 4) * 4 + r) * AT_S + j] = k0 + j < a.nk ? (s0[r] + s1[r]) / root : -INFINITY;
-        }
+        attn_scores(S, Q, KV, ldc, dp, root, k0, a.nk);
         __syncthreads();      // the scores are there, the keys are read
-        {
-            float sv[4], mx = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sv[u] = S[row * AT_S + sub + 8 * u], mx = fmaxf(mx, sv[u]);
-#pragma unroll
-            for (int d = 1; d < 8; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-            const float m_new = fmaxf(m_run, mx);      // finite: key k0 exists
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sv[u] = expf(sv[u] - m_new), sum += sv[u];
-#pragma unroll
-            for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
-            const float al = expf(m_run - m_new);       // 0 in the first chunk
-            l_run = l_run * al + sum;
-            m_run = m_new;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) S[row * AT_S + sub + 8 * u] = sv[u];
-            if (sub == 0) alpha[row] = al;
-        }
+        attn_softmax_step(S, alpha, m_run, l_run);
         attn_chunk(KV, ldv, vp, a.ldkv, k0, a.nk, a.d, dp);
         __syncthreads();
-        float pa[2][BK / 4], al[2][4];      // this lane's A fragments of P and its rows' factors, the same for every column tile
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int u = 0; u < BK / 4; ++u) pa[i][u] = S[(i * 16 + (lane & 15)) * AT_S + 4 * u + (lane >> 4)];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) al[i][r] = alpha[i * 16 + (lane >> 4) * 4 + r];
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int ni = wave + 4 * j;
-            if (ni >= nt) break;      // the same for a wave
-            const float* bp = KV + (lane >> 4) * ldv + ni * 16 + (lane & 15);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[j][i][r] *= al[i][r];
-#pragma unroll
-            for (int u = 0; u < BK / 4; ++u) {
-                const float b = bp[4 * u * ldv];
-                acc[j][0] = mfma4(pa[0][u], b, acc[j][0]);
-                acc[j][1] = mfma4(pa[1][u], b, acc[j][1]);
-            }
-        }
+        attn_pv<2>(acc, S, alpha, KV, ldv, nt);
     }
     if (sub == 0) lsum[row] = l_run;
     __syncthreads();
@@ -537,7 +400,7 @@ bool src_ok(const UnetSrc& s, int max_cs) { return s.p && s.c >= 1 && s.cs >= 16
 }  // namespace
 
 size_t unet_conv_lds_bytes(int stride) {
-    return sizeof(float) * (stride == 2 ? ConvGeom<2>::PH * ConvGeom<2>::PW * ConvGeom<2>::LD : ConvGeom<1>::PH * ConvGeom<1>::PW * ConvGeom<1>::LD);
+    return sizeof(float) * (stride == 2 ? ConvGeom<2>::FLOATS : ConvGeom<1>::FLOATS);
 }
 size_t unet_rows_lds_bytes() { return sizeof(float) * UNET_BM * RW_LD; }
 size_t unet_attn_lds_bytes() { return sizeof(float) * (UNET_ATTN_BQ * (AT_DP + 4) + UNET_ATTN_BK * (AT_DP + 16) + UNET_ATTN_BQ * AT_S + 2 * UNET_ATTN_BQ); }

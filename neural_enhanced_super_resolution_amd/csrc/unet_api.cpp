@@ -435,12 +435,7 @@ int nesr_unet_create(nesr_unet** out, int device_id, int in_channels, int out_ch
     // checked here, not only documented: every kernel's LDS fits a CU at any configuration that passed
     for (size_t bytes : {unet_conv_lds_bytes(1), unet_conv_lds_bytes(2), unet_rows_lds_bytes(), unet_attn_lds_bytes(), unet_emb_lds_bytes()})
         if (bytes > VAE_LDS_LIMIT) return unsupported("block_out_channels", "a kernel's LDS of " + std::to_string(bytes) + " bytes exceeds 160 KB");
-    int ndev = 0;
-    hipError_t e = device_id == NESR_UNET_NO_DEVICE ? hipSuccess : hipGetDeviceCount(&ndev);
-    if (device_id != NESR_UNET_NO_DEVICE && (e != hipSuccess || device_id < 0 || device_id >= ndev)) {
-        if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-        return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
-    }
+    if (const int rc = check_device(device_id, NESR_UNET_NO_DEVICE)) return rc;
     nesr_unet* c = new nesr_unet();
     c->device = device_id, c->cin = in_channels, c->cout = out_channels, c->levels = L, c->layers = layers_per_block, c->heads = attention_head_dim;
     c->cross = cross_attention_dim, c->classes = num_class_embeds, c->groups = norm_num_groups, c->eps = (float)norm_eps;

@@ -6,8 +6,10 @@
 // Wt[K][N]; the K of a product over a concatenation is the two sources' padded widths one after the other.
 //
 // The launchers of vae_api.h take one sample and widths up to 512; this network has two samples a call, widths up to 1024 and
-// inputs of two sources (up to 2048 channels), so unet.hip has kernels of its own.  What is shared is VaeNorm, what a GroupNorm
-// leaves per channel for its consumer's loader.
+// inputs of two sources (up to 2048 channels), so unet.hip has launchers, argument structs and kernel entries of its own.  What is
+// shared: VaeNorm, what a GroupNorm leaves per channel for its consumer's loader; the tile constants of the conv, the GroupNorm and
+// the attention; and, in f32_rows_device.h, the device bodies of the conv (patch loader, tap loop), of the GroupNorm statistics and
+// of the streamed attention, which both files' kernels call with their own tile, sample and source.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -9,12 +9,7 @@ using namespace nesr;
 
 namespace {
 
-int done(hipError_t e, const char* entry, const char* launcher) {
-    if (e == hipSuccess) return NESR_OK;
-    if (e == hipErrorInvalidValue)
-        return set_error(NESR_ERR_ARG, std::string(entry) + ": " + launcher + " refused the arguments (csrc/unet_api.h states what it takes); nothing was launched");
-    return set_error(NESR_ERR_HIP, std::string(entry) + ": " + launcher + ": " + hipGetErrorString(e));
-}
+int done(hipError_t e, const char* entry, const char* launcher) { return launch_done(e, "csrc/unet_api.h", entry, launcher); }
 
 UnetSrc source(const float* p, int c, int cs, const void* norm) { return UnetSrc{p, c, cs, static_cast<const VaeNorm*>(norm)}; }
 

@@ -23,18 +23,16 @@
 // MFMA operand maps (16x16x4 f32): lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; result register r of lane
 // l is D[row 4 (l >> 4) + r][col l & 15].  Every global load and store is guarded by the pixel count, the image extent and the real
 // width; a forward repeated gives the same bits.
+//
+// The conv's patch loader and tap loop, the GroupNorm partial sums, moments and VaeNorm, and the attention's score tile, softmax step
+// and P V are in f32_rows_device.h, one copy for this file and unet.hip; the kernels here keep their prologues and epilogues.
 #include "vae_api.h"
 
+#include "f32_rows_device.h"
 #include "nesr_kernels.h"
 
 namespace nesr {
 namespace {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ v4f mfma4(float a, float b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ float silu(float v) { return v / (1.0f + expf(-v)); }
-__device__ __forceinline__ float normed(float v, const VaeNorm& n) { return ((v - n.mean_hi) - n.mean_lo) * n.a + n.beta; }
 
 // acc[i] += A[m-tile i][K] x B[K][one n-tile], i < CNT, K a multiple of 16 (swin2sr.hip's chain: ascending k, four B fragments in flight)
 template <int CNT>
@@ -81,72 +79,27 @@ __global__ __launch_bounds__(256) void vae_in_kernel(const VaeIn a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- conv 3x3
-constexpr int CP_W = VAE_CONV_TW + 2, CP_H = VAE_CONV_TH + 2;
-constexpr int CP_LD = VAE_CONV_KC + 4;      // = 4 (mod 32): a wave's 64 reads meet 64 banks
-
 __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
-    __shared__ float lds[CP_H * CP_W * CP_LD];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    typedef ConvGeom<1> G;
+    __shared__ float lds[G::FLOATS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x0 = blockIdx.x * VAE_CONV_TW, y0 = blockIdx.y * VAE_CONV_TH;
     const int ntiles = a.coutp >> 4, ni0 = blockIdx.z * (VAE_CONV_NB / 16) + wave * 2;
     const bool work = ni0 < ntiles, two = ni0 + 1 < ntiles;      // the same for a wave
     const int ni1 = two ? ni0 + 1 : ni0;                           // a tile that is not there reads the first one's weights and is dropped
-    const int sw = a.in_mode == VAE_IN_NEAREST2 ? a.W >> 1 : a.W;
+    const bool up = a.in_mode == VAE_IN_NEAREST2;
     v4f acc[2][VAE_CONV_TH];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int i = 0; i < VAE_CONV_TH; ++i) acc[j][i] = v4f{0.f, 0.f, 0.f, 0.f};
 
-    for (int c0 = 0; c0 < a.cinp; c0 += VAE_CONV_KC) {
-        const int kc = a.cinp - c0 < VAE_CONV_KC ? a.cinp - c0 : VAE_CONV_KC, nq = kc >> 2;
+    for (int c0 = 0; c0 < a.cinp; c0 += G::KC) {
+        const int kc = a.cinp - c0 < G::KC ? a.cinp - c0 : G::KC;
         if (c0 > 0) __syncthreads();      // the chunk before is read
-        for (int idx = t; idx < CP_H * CP_W * nq; idx += 256) {
-            const int q = idx % nq, pos = idx / nq, px = pos % CP_W, py = pos / CP_W;
-            const int gy = y0 - 1 + py, gx = x0 - 1 + px;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
-                const int sy = a.in_mode == VAE_IN_NEAREST2 ? gy >> 1 : gy, sx = a.in_mode == VAE_IN_NEAREST2 ? gx >> 1 : gx;
-                const int c = c0 + q * 4;      // c + 3 < cinp <= cs_in
-                v = *reinterpret_cast<const float4*>(a.in + ((size_t)sy * sw + sx) * a.cs_in + c);
-                if (a.norm) {
-                    v.x = silu(normed(v.x, a.norm[c])), v.y = silu(normed(v.y, a.norm[c + 1]));
-                    v.z = silu(normed(v.z, a.norm[c + 2])), v.w = silu(normed(v.w, a.norm[c + 3]));
-                }
-            }
-            *reinterpret_cast<float4*>(lds + pos * CP_LD + q * 4) = v;
-        }
+        conv_load_patch<1>(lds, a.in, a.norm, a.cs_in, c0, kc, y0, x0, a.H, a.W, up ? a.W >> 1 : a.W, up);
         __syncthreads();
-        if (!work) continue;
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3, kx = tap - ky * 3;
-            const float* ap = lds + (ky * CP_W + (lane & 15) + kx) * CP_LD + (lane >> 4);
-            const float* bp = a.w + (size_t)(tap * a.cinp + c0 + (lane >> 4)) * a.coutp + (lane & 15);
-            int c = 0;
-            for (; c + 16 <= kc; c += 16) {      // four weight fragments a tile in flight; the MFMAs stay in ascending c
-                float b0[4], b1[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) b0[u] = bp[(size_t)(c + 4 * u) * a.coutp + ni0 * 16], b1[u] = bp[(size_t)(c + 4 * u) * a.coutp + ni1 * 16];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                    for (int i = 0; i < VAE_CONV_TH; ++i) {
-                        const float av = ap[i * CP_W * CP_LD + c + 4 * u];
-                        acc[0][i] = mfma4(av, b0[u], acc[0][i]);
-                        acc[1][i] = mfma4(av, b1[u], acc[1][i]);
-                    }
-                }
-            }
-            for (; c < kc; c += 4) {
-                const float b0 = bp[(size_t)c * a.coutp + ni0 * 16], b1 = bp[(size_t)c * a.coutp + ni1 * 16];
-#pragma unroll
-                for (int i = 0; i < VAE_CONV_TH; ++i) {
-                    const float av = ap[i * CP_W * CP_LD + c];
-                    acc[0][i] = mfma4(av, b0, acc[0][i]);
-                    acc[1][i] = mfma4(av, b1, acc[1][i]);
-                }
-            }
-        }
+        if (work) conv_taps<1>(lds, a.w, c0, a.cinp, a.coutp, kc, ni0, ni1, acc);
     }
     if (!work) return;
 #pragma unroll
@@ -182,37 +135,11 @@ __global__ __launch_bounds__(256) void vae_conv_kernel(const VaeConv a) {
 
 // ---------------------------------------------------------------------------------------------------------------- GroupNorm statistics
 __global__ __launch_bounds__(256) void vae_stats_partial_kernel(const VaeStats a) {
-    __shared__ double red[256 * 8];
-    const int t = threadIdx.x, nq = a.cs >> 2, npl = 256 / nq;      // nq <= 128: at least two pixel lanes
-    const int q4 = t % nq, pl = t / nq;
-    const size_t p0 = (size_t)blockIdx.x * VAE_GN_PIXELS;
-    const size_t p1 = p0 + VAE_GN_PIXELS < (size_t)a.m ? p0 + VAE_GN_PIXELS : (size_t)a.m;
-    if (pl < npl) {
-        double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-        for (size_t p = p0 + pl; p < p1; p += npl) {
-            const float4 v = *reinterpret_cast<const float4*>(a.in + p * a.cs + q4 * 4);
-            const double e[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s[k] += e[k], ss[k] += e[k] * e[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            red[((size_t)pl * a.cs + q4 * 4 + k) * 2] = s[k];
-            red[((size_t)pl * a.cs + q4 * 4 + k) * 2 + 1] = ss[k];
-        }
-    }
-    __syncthreads();
-    for (int c = t; c < a.cs; c += 256) {
-        double s = 0.0, ss = 0.0;
-        for (int l = 0; l < npl; ++l) s += red[((size_t)l * a.cs + c) * 2], ss += red[((size_t)l * a.cs + c) * 2 + 1];
-        a.partial[((size_t)blockIdx.x * a.cs + c) * 2] = s;
-        a.partial[((size_t)blockIdx.x * a.cs + c) * 2 + 1] = ss;
-    }
+    gn_partial_block(a.in, a.cs, a.m, a.partial + (size_t)blockIdx.x * a.cs * 2);
 }
 
 // block g < groups: group g; block `groups`: the padded channels, which normalise to zero
 __global__ __launch_bounds__(256) void vae_stats_finish_kernel(const VaeStats a, int nblocks) {
-    __shared__ double rs[256], rq[256];
     const int t = threadIdx.x, g = blockIdx.x, cpg = a.c / a.groups;
     if (g == a.groups) {
         for (int c = a.c + t; c < a.cs; c += 256) a.out[c] = VaeNorm{0.f, 0.f, 0.f, 0.f};
@@ -224,22 +151,11 @@ __global__ __launch_bounds__(256) void vae_stats_finish_kernel(const VaeStats a,
         const size_t at = ((size_t)(it / cpg) * a.cs + g * cpg + (int)(it % cpg)) * 2;
         s += a.partial[at], ss += a.partial[at + 1];
     }
-    rs[t] = s, rq[t] = ss;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if (t < h) rs[t] += rs[t + h], rq[t] += rq[t + h];
-        __syncthreads();
-    }
-    const double n = (double)a.m * cpg, mean = rs[0] / n;
-    double var = rq[0] / n - mean * mean;      // biased; the moments are double
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)a.eps);
+    double mean, rstd;
+    gn_moments(s, ss, (double)a.m * cpg, a.eps, mean, rstd);
     for (int k = t; k < cpg; k += 256) {
         const int c = g * cpg + k;
-        VaeNorm o;
-        o.mean_hi = (float)mean, o.mean_lo = (float)(mean - (double)o.mean_hi);
-        o.a = (float)((double)a.gamma[c] * rstd), o.beta = a.beta[c];
-        a.out[c] = o;
+        a.out[c] = make_norm(mean, rstd, a.gamma[c], a.beta[c]);
     }
 }
 
@@ -304,7 +220,7 @@ __device__ __forceinline__ void load_chunk(float* dst, int ld_dst, const float* 
 
 __global__ __launch_bounds__(256) void vae_attn_kernel(const VaeAttn a) {
     extern __shared__ float lds[];
-    constexpr int BQ = VAE_ATTN_BQ, BK = VAE_ATTN_BK, LDS_S = BK + 4;
+    constexpr int BQ = VAE_ATTN_BQ, BK = VAE_ATTN_BK, LDS_S = ATTN_LDS_S;
     const int ldc = a.cs + 4, ldv = a.cs + 16, nq = a.cs >> 2, nt = a.cs >> 4;
     float* Q = lds;                   // [BQ][ldc]
     float* KV = Q + BQ * ldc;         // [BK][ldv] a chunk's keys (stride ldc), then its values (stride ldv)
@@ -324,70 +240,17 @@ __global__ __launch_bounds__(256) void vae_attn_kernel(const VaeAttn a) {
     const float root = sqrtf((float)a.c);
     const int row = t >> 3, sub = t & 7;       // the 8 threads of a query row: an eighth of a wave
     float m_run = -INFINITY, l_run = 0.f;      // the same in all 8
-    const int mi = wave >> 1, ni_s = wave & 1; // the wave's tile of S
 
     for (int k0 = 0; k0 < a.n; k0 += BK) {
         __syncthreads();      // Q is there; the chunk before is done with KV, S and alpha
         load_chunk(KV, ldc, a.qkv + a.cs, ld3, k0, a.n, nq);
         __syncthreads();
-        {
-            const float* ap = Q + (mi * 16 + (lane & 15)) * ldc + (lane >> 4);
-            const float* bp = KV + (ni_s * 16 + (lane & 15)) * ldc + (lane >> 4);
-            v4f s0 = v4f{0.f, 0.f, 0.f, 0.f}, s1 = s0;      // even and odd k steps: two chains in flight, added once
-            for (int k = 0; k < a.cs; k += 8) {
-                s0 = mfma4(ap[k], bp[k], s0);
-                s1 = mfma4(ap[k + 4], bp[k + 4], s1);
-            }
-            const int j = ni_s * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) S[(mi * 16 + (lane >> 4) * 4 + r) * LDS_S + j] = k0 + j < a.n ? (s0[r] + s1[r]) / root : -INFINITY;
-        }
+        attn_scores(S, Q, KV, ldc, a.cs, root, k0, a.n);
         __syncthreads();      // the scores are there, the keys are read
-        {
-            float sv[4], mx = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sv[u] = S[row * LDS_S + sub + 8 * u], mx = fmaxf(mx, sv[u]);
-#pragma unroll
-            for (int d = 1; d < 8; d <<= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-            const float m_new = fmaxf(m_run, mx);      // finite: key k0 exists
-            float sum = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) sv[u] = expf(sv[u] - m_new), sum += sv[u];
-#pragma unroll
-            for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
-            const float al = expf(m_run - m_new);       // 0 in the first chunk
-            l_run = l_run * al + sum;
-            m_run = m_new;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) S[row * LDS_S + sub + 8 * u] = sv[u];
-            if (sub == 0) alpha[row] = al;
-        }
+        attn_softmax_step(S, alpha, m_run, l_run);
         load_chunk(KV, ldv, a.qkv + 2 * a.cs, ld3, k0, a.n, nq);
         __syncthreads();
-        float pa[2][BK / 4], al[2][4];      // this lane's A fragments of P and its rows' factors, the same for every column tile
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int u = 0; u < BK / 4; ++u) pa[i][u] = S[(i * 16 + (lane & 15)) * LDS_S + 4 * u + (lane >> 4)];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) al[i][r] = alpha[i * 16 + (lane >> 4) * 4 + r];
-        }
-#pragma unroll
-        for (int j = 0; j < ATTN_NTW; ++j) {
-            const int ni = wave + 4 * j;
-            if (ni >= nt) break;      // the same for a wave
-            const float* bp = KV + (lane >> 4) * ldv + ni * 16 + (lane & 15);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) acc[j][i][r] *= al[i][r];
-#pragma unroll
-            for (int u = 0; u < BK / 4; ++u) {
-                const float b = bp[4 * u * ldv];
-                acc[j][0] = mfma4(pa[0][u], b, acc[j][0]);
-                acc[j][1] = mfma4(pa[1][u], b, acc[j][1]);
-            }
-        }
+        attn_pv<ATTN_NTW>(acc, S, alpha, KV, ldv, nt);
     }
     if (sub == 0) lsum[row] = l_run;
     __syncthreads();
@@ -418,7 +281,7 @@ bool width_ok(int c, int cs) { return c >= 1 && cs >= 16 && cs % 16 == 0 && cs >
 
 }  // namespace
 
-size_t vae_conv_lds_bytes() { return sizeof(float) * CP_H * CP_W * CP_LD; }
+size_t vae_conv_lds_bytes() { return sizeof(float) * ConvGeom<1>::FLOATS; }
 size_t vae_rows_lds_bytes(int cs_in) { return sizeof(float) * VAE_BM * (cs_in + 4); }
 size_t vae_attn_lds_bytes(int cs) {
     return sizeof(float) * ((size_t)VAE_ATTN_BQ * (cs + 4) + (size_t)VAE_ATTN_BK * (cs + 16) + VAE_ATTN_BQ * (VAE_ATTN_BK + 4) + 2 * VAE_ATTN_BQ);

@@ -235,12 +235,7 @@ int nesr_vae_create(nesr_vae** out, int device_id, int latent_channels, int out_
     if (out_channels < 1 || out_channels > 4) return unsupported("out_channels", "1 .. 4, got " + std::to_string(out_channels));
     if (std::string(act_fn) != "silu") return unsupported("act_fn", "'" + std::string(act_fn) + "' is not supported (silu only)");
     if (!(scaling_factor > 0) || !std::isfinite(scaling_factor)) return unsupported("scaling_factor", "must be positive and finite");
-    int ndev = 0;
-    hipError_t e = device_id == NESR_VAE_NO_DEVICE ? hipSuccess : hipGetDeviceCount(&ndev);
-    if (device_id != NESR_VAE_NO_DEVICE && (e != hipSuccess || device_id < 0 || device_id >= ndev)) {
-        if (e != hipSuccess) return set_error(NESR_ERR_HIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
-        return set_error(NESR_ERR_ARG, "no such device " + std::to_string(device_id));
-    }
+    if (const int rc = check_device(device_id, NESR_VAE_NO_DEVICE)) return rc;
     nesr_vae* c = new nesr_vae();
     c->device = device_id, c->lat = latent_channels, c->nout = out_channels, c->nb = num_blocks, c->layers = layers_per_block;
     c->groups = norm_num_groups, c->scaling = scaling_factor;
