@@ -275,6 +275,23 @@ int nesr_fused_state(const nesr_ctx* ctx);
 int nesr_debug_fault(nesr_ctx* ctx, int drop_workgroups);
 
 /*
+ * Where rdb_f16x2_kernel applies to every dense block of a whole-frame forward, the trunk goes out as ONE launch of
+ * rdb_f16x2_chain_kernel: the same block body run 3 num_block times, the block boundary a nine-neighbour wait on the progress words
+ * where it was a kernel boundary (the values are the same bit for bit).  The row-band and single-block entries (nesr_band_*) keep one
+ * launch per block.  NESR_RDB_CHAIN=0 | 1 (default 1) sets the choice for new contexts, for A/B runs; any other value is refused.
+ * nesr_rdb_chain_state: what the LAST whole-frame forward of the context sent through the fused f32 dense-block kernels: kernel
+ * launches and dense blocks -- 1 and 3 num_block chained, 3 num_block and 3 num_block with one launch per block, 0 and 0 with
+ * per-layer launches.  For the dense-block routes the launch counter of nesr_kernel_time_ms counts DENSE BLOCKS dispatched per
+ * fused route (one per block of a chained launch, as for one launch per block), five per block for per-layer launches.
+ * nesr_rdb_chain_table is host only (no device, no context): the chained launch's table for num_block RRDBs as the forward builds it,
+ * from the addresses of the three trunk buffers and of every layer's packed weights and bias (1 + 15 num_block each, indexed like the
+ * network's layers: conv_first, then body.b.rdbR.convK); table receives 3 num_block entries of 13 addresses: cur, out, res2 (0: none),
+ * w[5], bias[5].
+ */
+int nesr_rdb_chain_state(const nesr_ctx* ctx, int* kernel_launches, int* blocks);
+int nesr_rdb_chain_table(int num_block, const uint64_t* buffers, const uint64_t* layer_w, const uint64_t* layer_b, uint64_t* table);
+
+/*
  * conv_up1 / conv_up2 convolve a nearest-x2 upsample.  Every output parity (py, px) of such a layer reads a 2x2 neighbourhood
  * of the low-resolution input only, so NESR_DTYPE_F32_SPLIT contexts run the layer as four 2x2-tap convolutions whose weights are
  * the 3x3 taps summed once in nesr_finalize_weights (f32, ky then kx ascending): 2.25x fewer multiply-adds.  The sums round

@@ -89,6 +89,10 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     }
     if (const char* e = getenv("NESR_TRUNK")) c->trunk_mode = e[0] == 'l' ? 1 : (e[0] == 'p' ? 2 : 0);
     if (const char* e = getenv("NESR_RDB_FUSE")) c->rdb_mode = atoi(e);
+    if (const char* e = getenv("NESR_RDB_CHAIN")) {
+        if (std::strcmp(e, "0") != 0 && std::strcmp(e, "1") != 0) return set_error(NESR_ERR_ARG, std::string("NESR_RDB_CHAIN must be 0 or 1, not '") + e + "'");
+        c->rdb_chain = e[0] == '1';
+    }
     if (const char* e = getenv("NESR_STRIP")) c->strip_mode = atoi(e);
     c->rdb_mode_init = c->rdb_mode;
     c->strip_mode_init = c->strip_mode;
@@ -468,6 +472,32 @@ int nesr_fused_state(const nesr_ctx* c) {
     return (on ? 1 : 0) | (c->fused_aborts << 1);
 }
 
+int nesr_rdb_chain_state(const nesr_ctx* c, int* kernel_launches, int* blocks) {
+    RRDB_ONLY(c);
+    if (!c) return set_error(NESR_ERR_ARG, "null ctx");
+    if (kernel_launches) *kernel_launches = c->chain_launches;
+    if (blocks) *blocks = c->chain_blocks;
+    return NESR_OK;
+}
+
+int nesr_rdb_chain_table(int num_block, const uint64_t* buffers, const uint64_t* layer_w, const uint64_t* layer_b, uint64_t* table) {
+    if (num_block <= 0 || !buffers || !layer_w || !layer_b || !table) return set_error(NESR_ERR_ARG, "nesr_rdb_chain_table: bad argument");
+    std::vector<Layer> layers((size_t)(1 + 15 * num_block));
+    for (size_t i = 0; i < layers.size(); ++i) {
+        layers[i].d_w = reinterpret_cast<void*>(static_cast<uintptr_t>(layer_w[i]));
+        layers[i].d_b = reinterpret_cast<float*>(static_cast<uintptr_t>(layer_b[i]));
+    }
+    char* buf[3];
+    for (int i = 0; i < 3; ++i) buf[i] = reinterpret_cast<char*>(static_cast<uintptr_t>(buffers[i]));
+    static_assert(sizeof(RdbChainBlock) == 13 * sizeof(uint64_t), "13 pointers per entry");
+    for (int i = 0; i < 3 * num_block; ++i) {
+        RdbChainBlock e;
+        rdb_block_entry(buf, layers.data(), i / 3, i % 3, e);
+        std::memcpy(table + (size_t)i * 13, &e, sizeof(e));
+    }
+    return NESR_OK;
+}
+
 int nesr_debug_fault(nesr_ctx* c, int drop_workgroups) {
     RRDB_ONLY(c);
     if (!c) return set_error(NESR_ERR_ARG, "null ctx");
@@ -573,6 +603,7 @@ void nesr_destroy(nesr_ctx* c) {
     if (c->ws) (void)hipFree(c->ws);
     if (c->d_weights) (void)hipFree(c->d_weights);
     if (c->d_trunk) (void)hipFree(c->d_trunk);
+    if (c->d_chain) (void)hipFree(c->d_chain);
     if (c->d_strip) (void)hipFree(c->d_strip);
     if (c->shard_buf) (void)hipFree(c->shard_buf);
     if (c->comm) (void)nesr_comm_destroy(c);

@@ -187,6 +187,17 @@ struct RdbLaunch {
 };
 int rdb_f16x2_tiles(int n, int h, int w);
 hipError_t launch_rdb_f16x2(const RdbLaunch& r, hipStream_t s);
+// A run of consecutive dense blocks of one forward in one launch (rdb_f16x2_chain_kernel): what differs from block to block,
+// one entry per block in device memory.  r.cur / out / res2 / w / bias are not used; block k of the launch publishes
+// r.epoch + 8 k + 1 .. + 5, so the next launch's epoch is at least r.epoch + 8 nblocks.
+struct RdbChainBlock {
+    const void* cur;
+    void* out;
+    const void* res2;
+    const void* w[5];
+    const float* bias[5];
+};
+hipError_t launch_rdb_f16x2_chain(const RdbLaunch& r, const RdbChainBlock* table, int nblocks, hipStream_t s);
 
 // bf16 dense block with the working set resident in LDS (rdb_bf16_strip.hip): a workgroup owns a 16-column strip of an
 // image and sweeps it top to bottom in positions of 12 rows; x1..x4 never leave the CU except for the strips' edge columns.

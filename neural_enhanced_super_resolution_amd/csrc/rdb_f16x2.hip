@@ -168,7 +168,26 @@ constexpr int EPI_STEPS = 1;
 // (one before, one after its MFMAs) -- a VALU block beside the partner's MFMA stream crawls just the same.
 // DMA waves (8..11): one step's LDS-DMAs two steps ahead in conv1..conv4, three in conv5 (4-slot ring; conv5's weight slabs one step ahead), polling of the neighbours' progress words
 // before the first chunk of each x_l, and this tile's own progress word EPI_STEPS steps into the next layer.
-__global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a) {
+//
+// CHAIN (rdb_f16x2_chain_kernel): the same body for a run of `nblocks` consecutive dense blocks of one forward.  Block k of
+// the launch takes cur / out / res2 and its weight and bias pointers from table[k] (a.cur .. a.bias are not used) and
+// publishes epoch + 8 k + 1 .. + 5; a new level 5 means "`out` visible", published like x1..x4: write-through stores,
+// every storing wave's vmcnt(0), a workgroup barrier (the block's last, behind the final epilogue: no wave reads the
+// rings or the bias table past it), one lane's relaxed agent-scope store.  Behind that barrier the DMA waves issue the
+// next block's first IN_LEAD weight slabs, wait for level 5 of block k - 1 from all nine tiles, and issue its first
+// input chunks (conv1 reads the neighbours' `out` in its very first chunk); the MFMA waves refill the bias table.  The
+// plan, the zero padding and the geometry are per launch; the 40-step walk is per block (rdb_f16x2_schedule.h,
+// chain_reentry_ok).
+// Buffer reuse: three buffers rotate, so what block k + 1 writes (x1..x4 into its own buffer, `out` into the next one's
+// x0 slice) was last read by block k - 2, or by block k - 1 where `out` lands in the buffer block k - 1 ran in -- reads
+// of the nine tiles only.  A tile starts block k + 1 behind level 5 of block k of all nine, and a tile that has
+// published level 5 of block k has finished every read of blocks <= k (its last barrier stands behind them): no write
+// of block k + 1 can meet a read of an earlier block (rdb_f16x2_schedule.h, chain_war_ok).  Every load of bytes that
+// another workgroup wrote is an sc1 LDS-DMA and every such byte an sc1 store, in a chain as in a single block -- but a
+// chained launch does re-read lines that another workgroup has rewritten since (a rotated buffer, three blocks on): that
+// no stale copy is served there is measured ("Across blocks"), not guaranteed by the architecture.
+template <bool CHAIN>
+__device__ __forceinline__ void rdb_blocks(RdbArgs a, const RdbChainBlock* table, int nblocks) {
     typedef Geo<4> G;
     constexpr int THREADS = G::THREADS, TH = G::TH;      // THREADS = DMA lanes (256), TH = 8 rows
     constexpr int IN_ITEMS = G::IN_ITEMS, IN_ROUNDS = G::IN_ROUNDS, IN_BYTES = G::IN_BYTES;
@@ -194,7 +213,18 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     const int ty = t2 / tiles_x, tx = t2 - ty * tiles_x;
     const int y0 = ty * TH, x0 = tx * TW;
 
-    const int j16 = lane & 15, g4 = lane >> 4;
+    // CHAIN: the pointers of the block in hand are read from its table entry where they are used, through the scalar cache
+    // (the host writes the table before the launch).  The entry pointer is all a block keeps in registers: the scalar
+    // file is full too, and a changed copy of `a` indexed by a run-time layer would live in scratch.
+    typedef const __attribute__((address_space(4))) RdbChainBlock* entry_ptr;
+    entry_ptr ent = (entry_ptr)table;
+    auto cur_of = [&]() -> const void* { if constexpr (CHAIN) return ent->cur; else return a.cur; };
+    auto out_of = [&]() -> const void* { if constexpr (CHAIN) return ent->out; else return a.out; };
+    auto res2_of = [&]() -> const void* { if constexpr (CHAIN) return ent->res2; else return a.res2; };
+    auto w_of = [&](int l) -> const void* { if constexpr (CHAIN) return ent->w[l]; else return a.w[l]; };
+    auto bias_of = [&](int l) -> const float* { if constexpr (CHAIN) return ent->bias[l]; else return a.bias[l]; };
+    unsigned epoch = a.epoch;      // of the block in hand
+
     // (layer, chunk) of the step after (l, c); l == 5: past the end.  A conv5 step is one chunk of all 64 output channels.
     auto advance = [](int& l, int& c) {
         const int nc = l == 4 ? 12 : 4 + 2 * l;
@@ -211,7 +241,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         unsigned okmask = 0;       // per lane: rounds in which this lane has an in-image item
         unsigned wavemask = 0;     // wave-uniform: rounds in which any lane of the wave has one (= instructions issued)
         const int row0 = y0 > 0 ? y0 - 1 : 0;
-        const char* in_img = static_cast<const char*>(a.cur) + ((size_t)n * a.h + row0) * a.w_ * 64;
+        const char* in_img = static_cast<const char*>(cur_of()) + ((size_t)n * a.h + row0) * a.w_ * 64;
         const unsigned* watch = nullptr;    // lanes 0..8: progress word of tile (ty + i/3 - 1, tx + i%3 - 1), if it exists
         int kin = 0, kw = 0;                // LDS-DMA instructions this wave issues per input chunk / per 32-cout weight slab (vmcnt counts wave instructions)
         if (lane < 9) {
@@ -253,7 +283,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         // the packed weights and in the ring: 2 x W_ITEMS = 9 full rounds) at positions 0,1 / 2,3 -- the ring holds the
         // current and the next step, so they are fetched one step ahead (conv5 starts at a multiple of RSLOTS steps).
         auto dma_w = [&](int l, int c, int wpos) {
-            const char* wsrc = static_cast<const char*>(a.w[l]) + (size_t)c * W_BYTES;
+            const char* wsrc = static_cast<const char*>(w_of(l)) + (size_t)c * W_BYTES;
 #pragma unroll
             for (int j = 0; j < W_ROUNDS; ++j) {
                 const int k = tid + THREADS * j;
@@ -262,19 +292,16 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             }
         };
         auto dma_w5 = [&](int c, int wpos) {
-            const char* wsrc = static_cast<const char*>(a.w[4]) + (size_t)c * (2 * W_BYTES);
+            const char* wsrc = static_cast<const char*>(w_of(4)) + (size_t)c * (2 * W_BYTES);
 #pragma unroll
             for (int j = 0; j < W5_ROUNDS; ++j) {
                 const unsigned dst = lds_base + WRING + wpos * W_BYTES + j * (THREADS * 16) + wave * 1024;
                 if (!abl::no_w_dma) glds16_s(wsrc, (unsigned)(tid + THREADS * j) * 16u, __builtin_amdgcn_readfirstlane(dst));
             }
         };
-        // input chunk c -- after the nine tiles have published the layer that produced it (chunks 4.. hold x1..: chunk c
-        // belongs to x_((c-4)/2+1)).  Exactly kin wave instructions.
-        auto dma_in = [&](int c, int slot) {
-            const unsigned need = c < 4 ? 0u : (unsigned)((c - 4) >> 1) + 1u;
-            if (need > seen && !gave_up && !abl::no_poll) {
-                const unsigned target = a.epoch + need;
+        // all nine tiles have published `target`; c = the chunk that waits (goes into the abort word)
+        auto wait_nine = [&](unsigned target, int c) {
+            {
                 unsigned long long t0 = 0;
                 for (unsigned it = 0;; ++it) {
                     const unsigned v = watch ? __hip_atomic_load(watch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target;
@@ -294,6 +321,14 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                     }
                     __builtin_amdgcn_s_sleep(4);
                 }
+            }
+        };
+        // input chunk c -- after the nine tiles have published the layer that produced it (chunks 4.. hold x1..: chunk c
+        // belongs to x_((c-4)/2+1)).  Exactly kin wave instructions.
+        auto dma_in = [&](int c, int slot) {
+            const unsigned need = c < 4 ? 0u : (unsigned)((c - 4) >> 1) + 1u;
+            if (need > seen && !gave_up && !abl::no_poll) {
+                wait_nine(epoch + need, c);
                 seen = need;
             }
             const char* isrc = in_img + (long long)c * a.chunk_bytes;
@@ -310,22 +345,44 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         };
         // Nothing in front of the first LDS-DMAs waits for memory, and no full vmcnt wait stands between them: the bias
         // table is filled by the MFMA waves, and the abort word is a scalar load (lgkmcnt) issued behind them.
+      for (int blk = 0;; ++blk) {      // CHAIN: the blocks of the launch; otherwise one pass
         int fl = 0, fc = 0;      // the next step to fetch
+        int inflight;            // instructions of the latest issue that the next barrier does not need
+        if (!CHAIN || blk == 0) {
 #pragma unroll
-        for (int i = 0; i < rdbs::IN_LEAD; ++i) {
-            dma_w(0, i, i);
-            dma_in(i, i);
-            advance(fl, fc);
+            for (int i = 0; i < rdbs::IN_LEAD; ++i) {
+                dma_w(0, i, i);
+                dma_in(i, i);
+                advance(fl, fc);
+            }
+            // The word can only have been raised by an earlier launch of this forward at this point (a kernel boundary away:
+            // the scalar cache cannot hold a stale copy); what other workgroups raise during the launch is seen by the polls.
+            gave_up = *(const __attribute__((address_space(4))) unsigned*)a.abort_flag != 0u;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zero padding is in LDS before the first barrier
+            // chunk 0 has landed: the MFMA waves request the launch's first fragments behind the next barrier
+            wait_vmcnt_le(abl::no_dma ? 0 : (rdbs::IN_LEAD - 1) * (kw + kin));
+            inflight = kw + kin;
+        } else {
+            // Re-entry (behind the previous block's last barrier: no wave reads a ring position any more).  The weights do
+            // not depend on any other workgroup: all IN_LEAD slabs go out before the poll.  The input chunks are the
+            // nine tiles' `out` of the previous block: behind its level 5.  Issue order w0 w1 w2 in0 in1 in2, so the
+            // counted waits leave in1 and in2 in flight at the block's first barrier and in2 at barrier 0.
+#pragma unroll
+            for (int i = 0; i < rdbs::IN_LEAD; ++i) dma_w(0, i, i);
+            if (!gave_up && !abl::no_poll) wait_nine(epoch - 8u + 5u, 0);
+#if NESR_RDB_ABL & 256
+            if (blk + 1 == nblocks && wave == 0) RSTAMP(1, 59, 2);      // the last block: the nine tiles' level 5 seen
+#endif
+#pragma unroll
+            for (int i = 0; i < rdbs::IN_LEAD; ++i) {
+                dma_in(i, i);
+                advance(fl, fc);
+            }
+            wait_vmcnt_le(abl::no_dma ? 0 : rdbs::REENTRY_TAIL_FIRST * kin);
+            inflight = rdbs::REENTRY_TAIL_0 * kin;
         }
-        // The word can only have been raised by an earlier launch of this forward at this point (a kernel boundary away:
-        // the scalar cache cannot hold a stale copy); what other workgroups raise during the launch is seen by the polls.
-        gave_up = *(const __attribute__((address_space(4))) unsigned*)a.abort_flag != 0u;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zero padding is in LDS before the first barrier
         int fill = rdbs::IN_LEAD;      // ring position of the next step to fetch (= that step & 3)
         int cl = 0, cc = 0;      // the current step
-        // chunk 0 has landed: the MFMA waves request the launch's first fragments behind the next barrier
-        wait_vmcnt_le(abl::no_dma ? 0 : (rdbs::IN_LEAD - 1) * (kw + kin));
-        int inflight = kw + kin;      // instructions of the latest issue that the next barrier does not need
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         for (int step = 0; step < RDB_STEPS; ++step) {
@@ -343,7 +400,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             // layer cl - 1 of this tile is in memory: its MFMA waves stored it during steps 0 .. EPI_STEPS - 1 of layer cl
             // and waited for those stores (vmcnt(0)) before this barrier
             if (cc == EPI_STEPS && cl >= 1 && wave == 0 && lane == 0)
-                __hip_atomic_store(a.progress + tile, a.epoch + (unsigned)cl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.progress + tile, epoch + (unsigned)cl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // Issue order = the order the waits count in: what the next barrier needs first.
             // (the schedule and its proof: rdb_f16x2_schedule.h)
             if (rdbs::w_pair(step)) {
@@ -362,18 +419,75 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             if (wave == 0) RSTAMP(1, step, 3);
             advance(cl, cc);
         }
+        if (!CHAIN) break;
+        // Every LDS-DMA of the block has landed (barrier 39's wait is vmcnt(0)).  The next block's pointers arrive while the
+        // MFMA waves run the final epilogue; behind the block's last barrier their `out` stores have retired: level 5.
+        const bool more = blk + 1 < nblocks;
+        if (more) {
+            in_img += static_cast<const char*>(ent[1].cur) - static_cast<const char*>(ent[0].cur);
+            ent += 1;
+        }
+#if NESR_RDB_ABL & 256
+        if (blk + 2 == nblocks && wave == 0) RSTAMP(1, 59, 0);      // DMA wave 0 at the last barrier of the last block but one ...
+#endif
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+#if NESR_RDB_ABL & 256
+        if (blk + 2 == nblocks && wave == 0) RSTAMP(1, 59, 1);      // ... and released from it
+#endif
+        if (wave == 0 && lane == 0) __hip_atomic_store(a.progress + tile, epoch + 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!more) break;
+        epoch += 8u;
+        seen = 0;
+      }
         return;
     }
 
     // ---- MFMA role: operand addresses as in conv3x3_f16x2_kernel, one row per wave
     const bool active = (y0 + wave) < a.h;
     if (wave == 1) RSTAMP(0, 61, 0);
+    bool bad = false;
+    // a stored value beyond the pair format's range.  CHAIN: reported where it is found -- collected for the end of the
+    // launch, the test would be put off to there too, its operands (the split values of every epilogue) waiting in registers.
+    auto note_bad = [&](bool b) {
+        if constexpr (CHAIN) {
+            if (b && a.status) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            bad |= b;
+        }
+    };
+  for (int blk = 0;; ++blk) {      // CHAIN: the blocks of the launch; otherwise one pass
+    // CHAIN: every block derives its lane's addresses and constants anew, from a lane id the compiler cannot see through.
+    // Hoisted out of the block loop they would all stay live through the 40 steps, and the body has two registers to spare.
+    // (the lane id itself from the execution mask -- every lane of a wave is here -- so that no register carries it either)
+    int lane_blk = threadIdx.x & 63;
+    if (CHAIN) {
+        int zero = 0;
+        asm volatile("" : "+v"(zero));
+        lane_blk = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)zero)) & 63;
+    }
+    const int lane = lane_blk;
+    const int j16 = lane & 15, g4 = lane >> 4;
     // The six bias vectors of the block sit in LDS (768 B: conv1..conv4, conv5's couts 0-31 and 32-63), first read at
     // step 4: a global load inside the step loop would cost a vmcnt wait per use.  Waves 0..5 (active or not) fetch one
     // vector each through a wave-uniform pointer while the DMA waves issue the first chunks; the first barrier publishes it.
     const bool fills_bias = wave < 6 && lane < 8;
     f32x4 bias_v = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (fills_bias) bias_v = *(const __attribute__((address_space(1))) f32x4*)(a.bias[wave < 4 ? wave : 4] + (wave == 5 ? 32 : 0) + 4 * lane);
+    if (fills_bias) bias_v = *(const __attribute__((address_space(1))) f32x4*)(bias_of(wave < 4 ? wave : 4) + (wave == 5 ? 32 : 0) + 4 * lane);
+    if (CHAIN && !active) {
+        // A wave without a row: its bias vector and the block's barriers (one in front of step 0's, one per step, one behind
+        // the final epilogue).  On its own path, so that below `active` is known: registers that are written and read under
+        // `active` only would otherwise count as live around the block loop, the previous block's contents in them.
+        if (fills_bias) *reinterpret_cast<f32x4*>(smem + BIAS + wave * 128 + lane * 16) = bias_v;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int i = 0; i < rdbs::CHAIN_BARS; ++i) {
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        if (blk + 1 == nblocks) break;
+        ent += 1;
+        continue;
+    }
     const int un = g4 >> 1, kh = g4 & 1;
     int b16[5][2], a16[5];
 #pragma unroll
@@ -405,14 +519,12 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     // ---- the deferred epilogue
     const int cbl = (g4 & 1) * 16 + (g4 >> 1) * 8;      // a lane's 8 output channels inside a 32-cout group after the permlane16 exchange
     const int piece8 = ((g4 & 1) * 2 + (g4 >> 1)) * 8;  // its 16-byte piece of a 64-byte slot after regroup_pairs (2-byte units)
-    const bool res2 = a.res2 != nullptr;
     f32x4 ep[2][2];                                     // [pixel half][cout half]: sums of the finished (layer, cout group)
 #pragma unroll
     for (int nh = 0; nh < 2; ++nh)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) ep[nh][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
     int ep_l = -1;
-    bool bad = false;
     auto unpack_res = [&](f32x4 rx, f32x4 rx1, f32x4& q0, f32x4& q1) {
         uint4 cx = __builtin_bit_cast(uint4, rx), cx1 = __builtin_bit_cast(uint4, rx1);
         regroup_pairs(cx, cx1);      // -> own hi, own lo
@@ -459,11 +571,11 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         uint4 cx, cx1;
         bool bad_here = false;
         split_regroup(v0, v1, cx, cx1, bad_here);
-        bad |= bad_here && valid;
+        note_bad(bad_here && valid);
         RKEEP(__builtin_bit_cast(f32x4, cx), __builtin_bit_cast(f32x4, cx1));
         RSTAMP_M(5);
         if (valid) {
-            const char* d0 = uni(static_cast<const char*>(a.cur) + (long long)dchunk * a.chunk_bytes + row_bytes);
+            const char* d0 = uni(static_cast<const char*>(cur_of()) + (long long)dchunk * a.chunk_bytes + row_bytes);
             if (!abl::plain_stores) {
                 store16_wt_s(d0, voff, cx);
                 store16_wt_s(d0 + a.chunk_bytes, voff, cx1);
@@ -663,7 +775,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             for (int s_ = 0; s_ < 5; ++s_) {
                 const int buf = (s_ + P) & 1;
                 if (last_of_all && s_ == 4 && !abl::no_epilogue) {
-                    issue_res(a.cur, 0, R1);
+                    issue_res(cur_of(), 0, R1);
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -679,7 +791,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 __builtin_amdgcn_sched_barrier(0);
                 if (s_ + 1 < 5) load_a(s_ + 1, 0, 0);
                 else if (last_of_all && !abl::no_epilogue) {
-                    issue_res(a.cur, 1, R1);
+                    issue_res(cur_of(), 1, R1);
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -700,11 +812,6 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         RSTAMP_M(2);
         RMSTEP_NEXT();
     };
-    if (fills_bias) *reinterpret_cast<f32x4*>(smem + BIAS + wave * 128 + lane * 16) = bias_v;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the bias table is in LDS before the first barrier
-    // the launch's first fragments: chunk 0 is in LDS once every DMA wave has passed its first wait -- one extra barrier
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, rdbs::M_LEAD> MLead;      // waves 0..3, any step of conv1..conv4
@@ -725,6 +832,11 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
                 for (int i = 0; i < 4; ++i) ep[nh][mt][i] = fmaf(acc16[0][nh][mt][1][i], LO_INV, acc16[0][nh][mt][0][i]);
         ep_l = l;
     };
+    if (fills_bias) *reinterpret_cast<f32x4*>(smem + BIAS + wave * 128 + lane * 16) = bias_v;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the bias table is in LDS before the first barrier
+    // the block's first fragments: chunk 0 is in LDS once every DMA wave has passed its first wait -- one extra barrier
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
     if (wave < 4) {
         for (int l = 0; l < 4; ++l) {
             const int nc = 4 + 2 * l;
@@ -757,6 +869,11 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     }
     step_body5(I0{}, I0{}, I0{}, 10);
     step_body5(I1{}, I0{}, I1{}, 11);
+#if NESR_RDB_ABL & 256
+    // a block boundary of a chained launch: the end of the last MFMA step of the launch's last block but one (slot 59);
+    // the last block's step 0 then holds the other side
+    if (CHAIN && blk + 2 == nblocks && wave == 1) RSTAMP(0, 59, 0);
+#endif
     // Both cout groups of conv5: x5 * s1 + x0 (and * s2 + RRDB input) into `out`'s channels 32 g.  Nothing is left to
     // overlap them with, so the memory round trips are taken once for all four pieces: x0's loads are in flight since
     // tap-step 4, the RRDB input's go out here, straight behind the last MFMA; each piece waits for its own lines only
@@ -765,8 +882,8 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
     auto final_epilogue = [&](auto Rc) {
         constexpr bool RES2 = decltype(Rc)::value != 0;
         if (RES2) {
-            issue_res(a.res2, 0, R2);
-            issue_res(a.res2, 1, R2);
+            issue_res(res2_of(), 0, R2);
+            issue_res(res2_of(), 1, R2);
         }
         asm volatile("" ::: "memory");      // the loads stay here: none is moved down towards its use
         __builtin_amdgcn_sched_barrier(0);
@@ -797,14 +914,14 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
             }
             bool bad_here = false;
             split_regroup(v0, v1, cx[p], cx1[p], bad_here);
-            bad |= bad_here && lane_ok[nh];
+            note_bad(bad_here && lane_ok[nh]);
             __builtin_amdgcn_sched_barrier(0);      // piece by piece, in the order the lines were asked for: counted waits
         }
         RSTAMP_M(5);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             if (lane_ok[p & 1]) {
-                const char* d0 = uni(static_cast<const char*>(a.out) + (long long)(2 * (p >> 1)) * a.chunk_bytes + row_bytes);
+                const char* d0 = uni(static_cast<const char*>(out_of()) + (long long)(2 * (p >> 1)) * a.chunk_bytes + row_bytes);
                 // write-through like x1..x4: 16.8 MB of dirty lines less for the kernel boundary to write back (measured
                 // against plain stores: 6.185 -> 6.130 ms per frame, profiles/rdb_edges/)
                 store16_wt_s(d0, lane_off[p & 1], cx[p]);
@@ -815,11 +932,29 @@ __global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a)
         RSTAMP_RETIRED();
     };
     if (active && !abl::no_epilogue) {
-        if (res2) final_epilogue(I1{});
+        if (res2_of() != nullptr) final_epilogue(I1{});
         else final_epilogue(I0{});
     }
+    if (!CHAIN) break;
+    // The block's last barrier: this wave's `out` stores have retired in front of it (level 5 goes out behind it), and no
+    // wave reads the rings or the bias table past it.  Then the next block's pointers and its bias table; the ring
+    // positions are back at 0 (RDB_STEPS is a multiple of RSLOTS).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#if NESR_RDB_ABL & 256
+    if (blk + 2 == nblocks && wave == 1) RSTAMP(0, 59, 1);      // ... and its last store retired
+#endif
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (blk + 1 == nblocks) break;
+    ent += 1;
+  }
     if (bad && a.status) __hip_atomic_store(a.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+
+// one dense block per launch
+__global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_kernel(RdbArgs a) { rdb_blocks<false>(a, nullptr, 1); }
+// a run of consecutive dense blocks of one forward per launch
+__global__ __launch_bounds__(64 * (MW + DW), 3) void rdb_f16x2_chain_kernel(RdbArgs a, const RdbChainBlock* table, int nblocks) { rdb_blocks<true>(a, table, nblocks); }
 
 }  // namespace
 
@@ -838,12 +973,15 @@ extern "C" int nesr_debug_rdb_arrive(unsigned long long* out) {
 
 int rdb_f16x2_tiles(int n, int h, int w) { return ((w + TW - 1) / TW) * ((h + 7) / 8) * n; }
 
-hipError_t launch_rdb_f16x2(const RdbLaunch& r, hipStream_t s) {
+namespace {
+
+// One dense block (table == null) or the `nblocks` blocks of `table` (device memory; r.cur .. r.bias are not used) in one launch
+template <typename Kernel>
+hipError_t launch_rdb(Kernel kernel, unsigned long long& attr_done, int& resident, const RdbLaunch& r, const RdbChainBlock* table, int nblocks, hipStream_t s) {
     typedef Geo<4> G;
     constexpr size_t shm = (size_t)RSLOTS * (G::IN_BYTES + (size_t)W_BYTES) + 768;
-    static unsigned long long attr_done = 0;
     {
-        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&rdb_f16x2_kernel), shm, attr_done);
+        const hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), shm, attr_done);
         if (e != hipSuccess) return e;
     }
     if ((long long)r.w_ * 64 * 12 >= (1ll << 32)) return hipErrorInvalidValue;
@@ -856,10 +994,9 @@ hipError_t launch_rdb_f16x2(const RdbLaunch& r, hipStream_t s) {
     int total = rdb_f16x2_tiles(r.n, r.h, r.w_);
     if (total <= 0) return hipSuccess;
     // every tile needs its own RESIDENT workgroup: what the device admits of this kernel (registers, LDS) times its compute units
-    static int resident = -1;
     if (resident < 0) {
         int per_cu = 0, dev = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rdb_f16x2_kernel, 64 * (MW + DW), shm) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64 * (MW + DW), shm) != hipSuccess || hipGetDevice(&dev) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
             return hipErrorUnknown;
         resident = per_cu * cus;
@@ -867,8 +1004,24 @@ hipError_t launch_rdb_f16x2(const RdbLaunch& r, hipStream_t s) {
     if (total > resident) return hipErrorLaunchOutOfResources;
     total -= r.debug_drop;       // test hook (nesr_debug_fault): the last workgroups never start, their neighbours' waits must end in the abort word
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rdb_f16x2_kernel, dim3((unsigned)total), dim3(64 * (MW + DW)), shm, s, a);
+    if constexpr (std::is_same<Kernel, void (*)(RdbArgs)>::value) hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(64 * (MW + DW)), shm, s, a);
+    else hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(64 * (MW + DW)), shm, s, a, table, nblocks);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_rdb_f16x2(const RdbLaunch& r, hipStream_t s) {
+    static unsigned long long attr_done = 0;
+    static int resident = -1;
+    return launch_rdb(&rdb_f16x2_kernel, attr_done, resident, r, nullptr, 1, s);
+}
+
+hipError_t launch_rdb_f16x2_chain(const RdbLaunch& r, const RdbChainBlock* table, int nblocks, hipStream_t s) {
+    static unsigned long long attr_done = 0;
+    static int resident = -1;
+    if (!table || nblocks <= 0) return hipErrorInvalidValue;
+    return launch_rdb(&rdb_f16x2_chain_kernel, attr_done, resident, r, table, nblocks, s);
 }
 
 }  // namespace nesr

@@ -146,6 +146,59 @@ constexpr Walk walk() {
 constexpr Walk WALK = walk();
 static_assert(WALK.ok, "a ring position is refilled while it is read, or read before the wait that covers it");
 static_assert(WALK.bars[0] == RDB_STEPS + 1 && WALK.bars[1] == RDB_STEPS + 1 && WALK.bars[2] == RDB_STEPS + 1, "every role takes the same number of barriers");
+
+// ---- Chained blocks (rdb_f16x2_chain_kernel): the walk above runs once per block.  Behind a block's walk every role takes
+// one more barrier, E (behind the final epilogue), and the DMA waves then issue the next block's first IN_LEAD steps
+// in the order w[0..IN_LEAD), in[0..IN_LEAD) -- the weights in front of the poll for the previous block's `out`.
+constexpr int CHAIN_BARS = RDB_STEPS + 2;       // per block and role: the one in front of step 0's, one per step, E
+constexpr int REENTRY_TAIL_FIRST = IN_LEAD - 1; // input chunks that may be in flight at the next block's first barrier
+constexpr int REENTRY_TAIL_0 = IN_LEAD - 2;     // ... and at its barrier 0 (no weight slab in either: they were issued first)
+constexpr bool chain_reentry_ok() {
+    bool ok = true;
+    // nothing is issued into a slot or slab that a lagging wave of the previous block can still read: every read of the
+    // walk lies in an interval in front of E (the walk has no interval past RDB_STEPS - 1), every issue of the walk has
+    // landed by its last barrier, and the re-entry issues come behind E
+    for (int t = 0; t < RDB_STEPS; ++t)
+        if (WALK.in_land[t] > RDB_STEPS - 1 || WALK.w_land[t] > RDB_STEPS - 1) ok = false;
+    // the rings are back where a block starts: step t uses position t & 3, conv5's pairs 0,1 / 2,3 alternate
+    if (RDB_STEPS % 4 != 0 || RDB_STEP5 % 4 != 0 || (RDB_STEPS - RDB_STEP5) % 2 != 0) ok = false;
+    // the re-entry queue w0 .. w(L-1), in0 .. in(L-1): what the first two counted waits cover against what is read behind them
+    const int landed_first = IN_LEAD - REENTRY_TAIL_FIRST;      // input steps [0, landed_first) at the first barrier, every slab
+    const int landed_0 = IN_LEAD - REENTRY_TAIL_0;              // ... at barrier 0
+    for (int r = 0; r < 2; ++r) {
+        if (WALK.rd_hi[r][0] >= landed_first || WALK.wr_hi[r][0] >= IN_LEAD) ok = false;
+        if (WALK.rd_hi[r][1] >= landed_0 || WALK.wr_hi[r][1] >= IN_LEAD) ok = false;
+    }
+    // from interval 0 on the walk's own issues follow and its waits count them alone: barrier 1's leaves at most the
+    // issues of interval 0 in flight, so the whole re-entry queue has landed there (vmcnt retires in order)
+    if (tail_w(0) + tail_in(0) > 1 + (in_end(0) - in_end(-1))) ok = false;
+    if (WALK.bars[0] + 1 != CHAIN_BARS || WALK.bars[1] + 1 != CHAIN_BARS || WALK.bars[2] + 1 != CHAIN_BARS) ok = false;
+    return ok;
+}
+static_assert(chain_reentry_ok(), "re-entry at a block boundary: a ring position is refilled while a wave of the previous block can read it, read before it has landed, or the roles' barrier counts differ");
+
+// Buffer reuse.  Dense block r (0..2) of an RRDB runs in buffer cur(r), writes x1..x4 into it and conv5's result into the
+// x0 slice of out(r); its third block reads the RRDB's input from the x0 slice of res2(r) and lands there in place.
+constexpr int rdb_cur_buf(int r) { return r; }
+constexpr int rdb_out_buf(int r) { return r < 2 ? r + 1 : 0; }
+constexpr int rdb_res2_buf(int r) { return r < 2 ? -1 : 0; }      // -1: no second residual
+// Who can run beside whom: a tile enters block k + 1 behind level 5 of block k of all nine tiles of its neighbourhood,
+// and a tile publishes level 5 behind E, its last read and last store of the block retired.  So while a tile is inside
+// block k, each of its neighbours is inside block k too, or waits in front of block k or k + 1 holding nothing but
+// weight slabs: a write of block k + 1 never meets a read of an earlier block, whichever buffer it goes to, and what is
+// left are the hazards inside one block -- the single launch's.  Those are: x1..x4 (written into cur, read by the
+// neighbours behind levels 1..4), and `out`, which a tile stores while its neighbours may still fetch halo pixels of
+// every slice of cur: it must be another buffer.  The second residual is read from a tile's own pixels only, by the
+// lanes that then store them, loads in front of stores.
+constexpr bool chain_war_ok() {
+    for (int r = 0; r < 3; ++r) {
+        if (rdb_out_buf(r) == rdb_cur_buf(r)) return false;                                   // `out` against the neighbours' halo reads of cur
+        if (rdb_res2_buf(r) >= 0 && rdb_res2_buf(r) != rdb_out_buf(r)) return false;          // in place: own pixels, load before store
+        if (rdb_cur_buf((r + 1) % 3) != rdb_out_buf(r)) return false;                         // the next block runs where this one's result lies
+    }
+    return true;
+}
+static_assert(chain_war_ok(), "buffer rotation of chained blocks");
 }  // namespace rdbs
 
 }  // namespace nesr

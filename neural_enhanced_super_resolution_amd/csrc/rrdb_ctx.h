@@ -100,6 +100,10 @@ struct nesr_ctx {
                                      // dense-block kernel, [64..] its per-tile progress words
     unsigned rdb_epoch = 0;          // fused dense-block launches: progress values of a launch are epoch+1 .. epoch+4
     int rdb_mode = -1;               // NESR_RDB_FUSE: -1 auto (fuse when every tile gets its own CU), 0 never
+    int rdb_chain = 1;               // NESR_RDB_CHAIN: 1 the trunk's dense blocks as one chained launch where the fused kernel applies, 0 one launch per block
+    nesr::RdbChainBlock* d_chain = nullptr;       // the chained launch's per-block pointers ...
+    std::vector<nesr::RdbChainBlock> h_chain;     // ... and what they were built from (rebuilt when workspace or weights have moved)
+    int chain_launches = 0, chain_blocks = 0;     // the last forward's fused f32 dense blocks: kernel launches, blocks (nesr_rdb_chain_state)
     int cus = 256;
     unsigned* h_status = nullptr;    // pinned landing word of nesr_check_range
     // bf16 dense blocks with the working set resident in LDS (rdb_bf16_strip.hip)
@@ -156,6 +160,8 @@ inline double conv_flops(const Layer& L, double pixels) { return 2.0 * 9.0 * L.c
 void band_release(nesr_ctx* c);
 
 // ---- rrdb_forward.cpp
+// dense block r of RRDB b: the rotation of the three trunk buffers and the block's weights (the fused routes' arguments)
+void rdb_block_entry(char* const buf[3], const Layer* layers, int b, int r, RdbChainBlock& e);
 WsLayout ws_layout(const nesr_ctx* c, int N, int h, int w);
 int ensure_ws(nesr_ctx* c, size_t bytes);
 void free_strip_plans(nesr_ctx* c);

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "rdb_f16x2_schedule.h"
 #include "rrdb_ctx.h"
 
 namespace nesr {
@@ -279,33 +280,42 @@ int try_strip(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s) {
 // small frames, f16-pair form: the whole dense block in one launch (rdb_f16x2_kernel).  Every tile needs its own
 // resident workgroup, so the frame's tiles must fit the compute units and the device must be this context's
 // (frames in flight on other streams would compete for the one workgroup slot per CU).
-int try_fused_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s) {
-    if (c->dtype != NESR_DTYPE_F32_SPLIT || c->rdb_mode == 0 || c->nf != 64 || c->gc != 32 || c->shared_device) return FUSED_NA;
+bool fused_rdb_applies(const nesr_ctx* c, const FwState& F) {
+    if (c->dtype != NESR_DTYPE_F32_SPLIT || c->rdb_mode == 0 || c->nf != 64 || c->gc != 32 || c->shared_device) return false;
     const int tiles = rdb_f16x2_tiles(F.N, F.h, F.w);
-    if (tiles > c->cus || tiles > 4096) return FUSED_NA;
-    const double px = (double)F.N * F.h * F.w;
+    return tiles <= c->cus && tiles <= 4096;
+}
+
+// everything of a fused launch that does not depend on the block (the epoch is the caller's)
+RdbLaunch fused_rdb_launch(nesr_ctx* c, const FwState& F) {
     RdbLaunch L;
     std::memset(&L, 0, sizeof(L));
-    L.cur = F.buf[r];
     L.chunk_bytes = F.m_t.chunk * 2;
-    L.out = r < 2 ? F.buf[r + 1] : F.buf[0];
-    L.res2 = r < 2 ? nullptr : F.buf[0];
     L.s1 = 0.2f; L.s2 = 0.2f;
-    for (int k = 0; k < 5; ++k) {
-        const Layer& Ly = c->layers[layer_id(b, r, k)];
-        L.w[k] = Ly.d_w;
-        L.bias[k] = Ly.d_b;
-        if (c->timer.on) c->timer.flops += conv_flops(Ly, px);
-    }
     L.n = F.N; L.h = F.h; L.w_ = F.w;
     L.progress = c->d_status + 64;
-    c->rdb_epoch += 8;
-    L.epoch = c->rdb_epoch;
     L.abort_flag = c->d_status + 1;
     L.status = c->d_status;
     L.timeout_ticks = c->strip_timeout_ticks;
     L.debug_drop = c->debug_drop;
     c->debug_drop = 0;
+    return L;
+}
+
+int try_fused_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s) {
+    if (!fused_rdb_applies(c, F)) return FUSED_NA;
+    const double px = (double)F.N * F.h * F.w;
+    RdbLaunch L = fused_rdb_launch(c, F);
+    RdbChainBlock e;
+    rdb_block_entry(F.buf, c->layers.data(), b, r, e);
+    L.cur = e.cur; L.out = e.out; L.res2 = e.res2;
+    for (int k = 0; k < 5; ++k) {
+        L.w[k] = e.w[k];
+        L.bias[k] = e.bias[k];
+        if (c->timer.on) c->timer.flops += conv_flops(c->layers[layer_id(b, r, k)], px);
+    }
+    c->rdb_epoch += 8;
+    L.epoch = c->rdb_epoch;
     const hipError_t le = launch_rdb_f16x2(L, s);
     if (le == hipErrorLaunchOutOfResources) {
         c->rdb_mode = 0;        // fewer resident workgroups than tiles: per-layer launches (the same bits)
@@ -313,11 +323,63 @@ int try_fused_rdb(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s) {
     }
     NESR_TRY(le);
     c->strip_used = true;       // (the abort word of either persistent kernel is looked at by nesr_check_range)
+    c->chain_launches += 1;
+    c->chain_blocks += 1;
     if (c->timer.on) c->timer.launches += 1;
     return FUSED_LAUNCHED;
 }
 
+// The whole trunk of a forward as ONE launch of the chained kernel, where try_fused_rdb would take every block and nothing
+// sits between the blocks (run_forward's loop: no row-band phase, no single-block entry).  The device table of per-block
+// pointers is kept with the context and rewritten when the workspace or the weights have moved.
+int try_chained_rdb(nesr_ctx* c, const FwState& F, hipStream_t s) {
+    const int nblocks = 3 * c->nb;
+    if (!c->rdb_chain || nblocks <= 0 || !fused_rdb_applies(c, F)) return FUSED_NA;
+    std::vector<RdbChainBlock> table((size_t)nblocks);
+    for (int i = 0; i < nblocks; ++i) rdb_block_entry(F.buf, c->layers.data(), i / 3, i % 3, table[(size_t)i]);
+    const size_t bytes = table.size() * sizeof(RdbChainBlock);
+    if (!c->d_chain || c->h_chain.size() != table.size() || std::memcmp(c->h_chain.data(), table.data(), bytes) != 0) {
+        if (c->d_chain && c->h_chain.size() != table.size()) {
+            NESR_TRY(hipStreamSynchronize(s));
+            NESR_TRY(hipFree(c->d_chain));
+            c->d_chain = nullptr;
+        }
+        if (!c->d_chain) NESR_TRY(hipMalloc((void**)&c->d_chain, bytes));
+        c->h_chain.swap(table);       // the copy's source stays as it is until the next rebuild
+        NESR_TRY(hipMemcpyAsync(c->d_chain, c->h_chain.data(), bytes, hipMemcpyHostToDevice, s));
+    }
+    RdbLaunch L = fused_rdb_launch(c, F);
+    L.epoch = c->rdb_epoch + 8;       // block k publishes epoch + 8 k + 1 .. + 5
+    const hipError_t le = launch_rdb_f16x2_chain(L, c->d_chain, nblocks, s);
+    if (le == hipErrorLaunchOutOfResources) {
+        c->rdb_chain = 0;             // the chained kernel does not fit: one block per launch, if that kernel does
+        return FUSED_NA;
+    }
+    NESR_TRY(le);
+    c->rdb_epoch += 8u * (unsigned)nblocks;
+    c->strip_used = true;
+    c->chain_launches += 1;
+    c->chain_blocks += nblocks;
+    if (c->timer.on) {
+        const double px = (double)F.N * F.h * F.w;
+        for (int i = 0; i < nblocks * 5; ++i) c->timer.flops += conv_flops(c->layers[1 + i], px);
+        c->timer.launches += nblocks;      // dense blocks dispatched through a fused route, not kernel launches
+    }
+    return FUSED_LAUNCHED;
+}
+
 }  // namespace
+
+void rdb_block_entry(char* const buf[3], const Layer* layers, int b, int r, RdbChainBlock& e) {
+    e.cur = buf[rdbs::rdb_cur_buf(r)];
+    e.out = buf[rdbs::rdb_out_buf(r)];
+    e.res2 = rdbs::rdb_res2_buf(r) >= 0 ? buf[rdbs::rdb_res2_buf(r)] : nullptr;
+    for (int k = 0; k < 5; ++k) {
+        const Layer& Ly = layers[layer_id(b, r, k)];
+        e.w[k] = Ly.d_w;
+        e.bias[k] = Ly.d_b;
+    }
+}
 
 int fw_setup(nesr_ctx* c, int N, int C, int H, int W, FwState& F) {
     if (!c->finalized) return set_error(NESR_ERR_STATE, "weights not finalized (call nesr_finalize_weights)");
@@ -518,9 +580,13 @@ int run_forward(nesr_ctx* c, const float* x_f32, const uint8_t* x_u8, int flip, 
         // the fused dense-block kernels hold the device: serialised per device against other streams' (see DeviceLease)
         const bool lease = (strip_wanted(c) || (c->dtype == NESR_DTYPE_F32_SPLIT && c->rdb_mode != 0 && !c->shared_device)) && c->nb > 0;
         if (lease && (rc = lease_acquire(c, s))) return rc;
-        for (int b = 0; b < c->nb; ++b)
-            for (int r = 0; r < 3; ++r)
-                if ((rc = fw_rdb(c, F, b, r, s))) return rc;
+        c->chain_launches = c->chain_blocks = 0;
+        rc = try_chained_rdb(c, F, s);
+        if (rc < 0) return rc;
+        if (rc == FUSED_NA)
+            for (int b = 0; b < c->nb; ++b)
+                for (int r = 0; r < 3; ++r)
+                    if ((rc = fw_rdb(c, F, b, r, s))) return rc;
         if (lease && (rc = lease_release(c, s))) return rc;
     }
     NESR_TRY(c->timer.end(s));

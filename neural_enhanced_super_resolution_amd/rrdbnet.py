@@ -522,6 +522,17 @@ class RRDBNet(_HipNet):
         v = int(_lib.load().nesr_fused_state(h))
         return bool(v & 1), v >> 1
 
+    def chain_state(self, slot=0, device=None):
+        """(kernel launches, dense blocks) that the context's last forward sent through the fused f32 dense-block kernels
+        (nesr_rdb_chain_state): (1, 3 num_block) chained, equal numbers with one launch per block, (0, 0) with per-layer
+        launches or if the context does not exist."""
+        h = self._existing(slot, device)
+        if h is None:
+            return 0, 0
+        launches, blocks = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(_lib.load().nesr_rdb_chain_state(h, ctypes.byref(launches), ctypes.byref(blocks)), "nesr_rdb_chain_state")
+        return launches.value, blocks.value
+
     def debug_fault(self, drop_workgroups=1, slot=0):
         """TEST HOOK: the next persistent launch of the context leaves out its last workgroups (nesr_debug_fault)."""
         _lib.check(_lib.load().nesr_debug_fault(self._existing(slot, None), int(drop_workgroups)), "nesr_debug_fault")

@@ -40,6 +40,15 @@ if S[1][61][0] and S[0][61][1]:
     print(f"entry -> first barrier: DMA wave 0 {S[1][0][0] - S[1][61][0]} cycles (MFMA wave 1 entered {S[0][61][0] - S[1][61][0]:+d} relative to it)")
     print(f"last step -> end: {S[0][61][1] - S[0][N - 1][2]} cycles (MFMA wave 1: end of the last MFMA step to its last store retired)")
     print(f"entry -> end: {S[0][61][1] - min(S[0][61][0], S[1][61][0])} cycles")
+# a chained launch (rdb_f16x2_chain_kernel): the table holds the launch's last block; slot 59 = the block in front of it:
+# [0][59][0] end of its last MFMA step, [0][59][1] its last store retired, [1][59][0..1] DMA wave 0 at / behind the block's last
+# barrier, [1][59][2] the nine tiles' level 5 seen in the last block's re-entry
+if S[0][59][0]:
+    e = S[0][59][0]
+    print("block boundary of the chained launch (last block but one -> last block), cycles after the end of the last MFMA step:")
+    print(f"  last store retired {S[0][59][1] - e}, last barrier released {S[1][59][1] - e}, the nine tiles' level 5 seen {S[1][59][2] - e}, "
+          f"first barrier released (DMA wave 0's step-0 stamp) {S[1][0][0] - e}, MFMA wave 1 behind barrier 0 {S[0][0][1] - e}")
+    print(f"  last MFMA step -> first MFMAs of the next block: {S[0][0][1] - e} cycles")
 dr, dt = S[1][63][0] - S[1][62][0], S[1][63][1] - S[1][62][1]
 print(f"steps 0..{N - 1}: {dt} shader cycles in {dr} ticks of the 100 MHz clock = {dr / 100:.2f} us: shader clock {dt / dr * 100:.0f} MHz")
 

@@ -17,14 +17,14 @@ ks.sort(key=lambda k: k[2])
 idx = [i for i, k in enumerate(ks) if 'pack_input' in k[0]]
 i0 = idx[-2]
 if any('rdb_f16x2' in k[0] for k in ks[i0:idx[-1]]):
-    # fused dense blocks: pack_input, conv_first, 69 x rdb_f16x2_kernel, conv_body, up1, up2, hr, last
+    # fused dense blocks: pack_input, conv_first, 69 x rdb_f16x2_kernel or 1 x rdb_f16x2_chain_kernel, conv_body, up1, up2, hr, last
     seq = ks[i0:idx[-1]]
     tot = sum(k[1] for k in seq)
     span = seq[-1][3] - seq[0][2]
     print("forward: kernels %d, sum kernel %.3f ms, span %.3f ms, gaps %.3f ms" % (len(seq), tot / 1e6, span / 1e6, (span - tot) / 1e6))
     rdb = [k for k in seq if 'rdb_f16x2' in k[0]]
     d = [k[1] for k in rdb]
-    gaps = [rdb[i + 1][2] - rdb[i][3] for i in range(len(rdb) - 1)]
+    gaps = [rdb[i + 1][2] - rdb[i][3] for i in range(len(rdb) - 1)] or [0]      # one chained launch (rdb_f16x2_chain_kernel): no gaps
     fl = 2 * 9 * (64 * 32 + 96 * 32 + 128 * 32 + 160 * 32 + 192 * 64) * px0
     print("rdb_f16x2_kernel x%d: avg %.2f us  min %.2f  max %.2f   %.1f TFLOP/s algorithmic; gap to the next launch avg %.2f us  min %.2f  max %.2f"
           % (len(rdb), sum(d) / len(d) / 1e3, min(d) / 1e3, max(d) / 1e3, fl / (sum(d) / len(d)) / 1e3, sum(gaps) / len(gaps) / 1e3, min(gaps) / 1e3, max(gaps) / 1e3))
