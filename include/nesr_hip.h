@@ -1302,6 +1302,128 @@ int nesr_vae_k_rows(int m, int cs_in, int np, const float* in_dev, const void* n
                     float* out_dev, void* hip_stream);
 int nesr_vae_k_attention(int n, int c, int cs, const float* qkv_dev, float* out_dev, void* hip_stream);
 
+/*
+ * ---- The x4 diffusion upscaler's text encoder (csrc/clip_text.hip, clip_text_api.cpp) -- clip_text.ClipTextEncoder.
+ *
+ * transformers' CLIPTextModel(input_ids)[0] in eval mode, f32: token row + position row (positions from 0), then per layer
+ * x += out_proj(attn(layer_norm1(x))) and x += fc2(act(fc1(layer_norm2(x)))), then final_layer_norm on every position.  The
+ * attention is causal (query i sees keys 0 .. i), its heads are contiguous column blocks of q, k and v, its scores are scaled by
+ * 1 / sqrt(head width).  No attention mask is taken, as the x4 pipeline passes none: a padding id is an ordinary token.  The
+ * pooled output and text_projection are not computed.
+ *
+ * nesr_clip_text_create takes the configuration's fields by name.  Supported: hidden_size up to 1024 that is a multiple of
+ * num_attention_heads with a head width of 8 .. 128 that is a multiple of 8; intermediate_size up to 4096; any positive layer
+ * count, vocabulary and max_position_embeddings; hidden_act "gelu" (erf) or "quick_gelu" (x sigmoid(1.702 x)).  Anything else is
+ * NESR_ERR_UNSUPPORTED before any device is touched, and the text names the field.  device_id NESR_CLIP_TEXT_NO_DEVICE gives the
+ * context without a device (the host side alone: strict loading and packing; every entry that would launch is NESR_ERR_STATE).
+ *
+ * nesr_clip_text_load_weight: keys are transformers' state_dict names of either generation: embeddings.token_embedding.weight,
+ * encoder.layers.0.self_attn.k_proj.weight, ..., final_layer_norm.bias, or the same behind "text_model." as published
+ * text_encoder/ files carry them; their embeddings.position_ids buffer is accepted and ignored.  Strict, as nesr_vae_load_weight;
+ * nesr_clip_text_finalize: a missing key is NESR_ERR_STATE.
+ *
+ * nesr_clip_text_encode_f32: ids_host [n, tokens] int32 on the HOST (a tokenizer's output; read before the entry returns) ->
+ * out_dev [n, tokens, hidden_size] f32, which is what nesr_unet_forward_f32 takes as text_states_dev; out_elems must be exactly
+ * that count.  n is 1 or 2, tokens 1 .. min(max_position_embeddings, NESR_UNET_MAX_TEXT_TOKENS), every id indexes the table:
+ * otherwise NESR_ERR_ARG before any launch.  Asynchronous on hip_stream: the ids travel in a launch's arguments, nothing is copied
+ * or synchronised once the workspace has its size (nesr_clip_text_workspace_bytes; it grows with n tokens).  3 + 8 layers
+ * launches, whatever n and tokens.  No atomics anywhere: a call repeated gives the same bits, and a sample's result does not
+ * depend on n.
+ */
+#define NESR_CLIP_TEXT_NO_DEVICE (-1)
+typedef struct nesr_clip_text nesr_clip_text;
+int nesr_clip_text_create(nesr_clip_text** out, int device_id, int vocab_size, int hidden_size, int intermediate_size, int num_hidden_layers,
+                          int num_attention_heads, int max_position_embeddings, double layer_norm_eps, const char* hidden_act);
+void nesr_clip_text_destroy(nesr_clip_text* ctx);
+int nesr_clip_text_num_tensors(const nesr_clip_text* ctx);
+int nesr_clip_text_load_weight(nesr_clip_text* ctx, const char* key, const float* data_host, const int64_t* shape, int ndim);
+int nesr_clip_text_finalize(nesr_clip_text* ctx);
+int nesr_clip_text_workspace_bytes(nesr_clip_text* ctx, int n, int tokens, size_t* bytes);
+int nesr_clip_text_encode_f32(nesr_clip_text* ctx, const int32_t* ids_host, int n, int tokens, float* out_dev, size_t out_elems, void* hip_stream);
+/* Kernel groups of nesr_clip_text_kernel_time_ms: the embedding gather, the LayerNorm statistics and the final LayerNorm, the
+ * q | k | v and out_proj products, the causal attention, fc1 with its activation and fc2. */
+enum { NESR_CLIP_TEXT_GROUP_EMBEDDING = 0, NESR_CLIP_TEXT_GROUP_NORM = 1, NESR_CLIP_TEXT_GROUP_PROJ = 2, NESR_CLIP_TEXT_GROUP_ATTENTION = 3,
+       NESR_CLIP_TEXT_GROUP_FF = 4, NESR_CLIP_TEXT_GROUPS = 5 };
+int nesr_clip_text_set_timing(nesr_clip_text* ctx, int enable);
+int nesr_clip_text_kernel_time_ms(nesr_clip_text* ctx, double* group_ms, int n_groups, int64_t* launches);
+/*
+ * Single-launch entries of the text encoder's own kernels (test hooks as the nesr_unet_k_* above; csrc/clip_text_api.h documents
+ * the launchers' arguments).  Device pointers in the kernels' own layout; what a launcher refuses is NESR_ERR_ARG with nothing launched.
+ *   nesr_clip_text_k_embed      out [rows][cs] = tok [vocab][c] at ids_host[row] (a HOST array of `rows` ids) + pos [positions][c] at
+ *                               row % tokens, zero past c; an id outside the table or tokens above `positions` is refused
+ *   nesr_clip_text_k_attention  causal softmax(q k^T / sqrt(d)) v per sample and head: q, k, v [samples tokens][ld], out [samples
+ *                               tokens][ldo], its columns past heads d zeroed
+ */
+int nesr_clip_text_k_embed(const int32_t* ids_host, int rows, int tokens, const float* tok_dev, int vocab, const float* pos_dev, int positions, int c, int cs,
+                           float* out_dev, void* hip_stream);
+int nesr_clip_text_k_attention(int samples, int tokens, int heads, int d, const float* q_dev, const float* k_dev, const float* v_dev, int ldq, int ldkv, int ldo,
+                               float* out_dev, void* hip_stream);
+
+/*
+ * ---- The x4 diffusion upscaler as one call (csrc/sdx4_step.hip, sdx4_api.cpp) -- sdx4.StableDiffusionX4Upscaler.
+ *
+ * StableDiffusionUpscalePipeline's loop (nesr/nesr.py:988-1031 calls it): the prompts through the text encoder; the u8 frame as
+ * v / 127.5 - 1 with the low-res scheduler's add_noise at noise_level; `steps` times the UNet on cat(latents, noised image) with
+ * the noise level as class label, classifier-free guidance m = m_neg + g (m_prompt - m_neg), the DDIM step (eta 0); the VAE decoder
+ * and its quantiser.  The schedulers' values are recalled from diffusers, not checked against the library or a file (DESIGN
+ * section 20 lists each).  Their tables are computed on the host in double; a step reaches the device as six f32 coefficients.
+ *
+ * nesr_sdx4_create takes the three contexts (not owned: they outlive the pipeline, and nesr_sdx4_destroy leaves them) and the
+ * scheduler fields by name.  DDIM: beta_schedule "scaled_linear" (linspace(sqrt(beta_start), sqrt(beta_end), T)^2) or "linear",
+ * prediction_type "v_prediction" or "epsilon", clip_sample false, timestep_spacing "leading", steps_offset 0 or 1, eta 0; the
+ * final alpha-bar is alpha-bar[0] unless set_alpha_to_one.  Low-res: "squaredcos_cap_v2".  Anything else is NESR_ERR_UNSUPPORTED
+ * naming the field.  The contexts must fit each other, else NESR_ERR_ARG naming the mismatch: the UNet's in_channels = the VAE's
+ * latent_channels + 3 and its out_channels = latent_channels, cross_attention_dim = the text encoder's hidden_size, a class table
+ * larger than max_noise_level, a VAE of 3 out_channels, all three on one device.
+ *
+ * nesr_sdx4_upscale_u8: frame_dev [h, w, 3] u8 RGB -> out_dev [h s, w s, 3] u8 RGB, s = the VAE's scale (4); capacity counts
+ * bytes.  ids_host [n, tokens] int32 on the HOST, n = 2 in the order [negative, prompt] when guidance_scale > 1, else n = 1 (the
+ * prompt; no combination).  noise_dev [3, h, w] and latents_dev [latent_channels, h, w] f32 are the caller's unit normal draws
+ * (16-byte aligned; a C host brings its own generator).  latents_out_dev, if not null, receives the final f32 latents (one
+ * device-to-device copy queued after the last launch).  Every launch goes on hip_stream; once the workspaces have their size
+ * (nesr_sdx4_workspace_bytes is the pipeline's own: the text states, the UNet's input and output, the latents) there is no
+ * synchronisation, no copy to or from the host and no allocation between the first launch and the last.  h and w must be
+ * multiples of 2^(UNet levels - 1) and h w at most NESR_VAE_MAX_TOKENS; tokens, the ids, noise_level (0 .. max_noise_level) and
+ * steps (the first timestep must lie in the table) are checked too: NESR_ERR_ARG before any launch.
+ *
+ * nesr_sdx4_launches: the kernel launches of the last nesr_sdx4_upscale_u8: text + 1 + steps (UNet + 1) + VAE.
+ * nesr_sdx4_set_timing / nesr_sdx4_kernel_time_ms time the pipeline's own two kernels (the networks have their own timers).
+ *
+ * nesr_sdx4_schedule and nesr_sdx4_noise_coefficients need no context and no device: the tables a pipeline of these fields
+ * uses.  timesteps [steps], alpha_bars [steps][2] (at the step, at the previous step), coefficients [steps][6] (c0x, c0m, cex,
+ * cem, sp, sq: x0 = c0x x + c0m m, e = cex x + cem m, x' = sp x0 + sq e); noise coefficients (sqrt(abar_L), sqrt(1 - abar_L)).
+ * Null outputs are skipped.
+ */
+typedef struct nesr_sdx4 nesr_sdx4;
+int nesr_sdx4_create(nesr_sdx4** out, nesr_clip_text* text, nesr_unet* unet, nesr_vae* vae, int num_train_timesteps, double beta_start, double beta_end,
+                     const char* beta_schedule, const char* prediction_type, int clip_sample, int set_alpha_to_one, int steps_offset,
+                     const char* timestep_spacing, double eta, int low_res_num_train_timesteps, const char* low_res_beta_schedule, int max_noise_level);
+void nesr_sdx4_destroy(nesr_sdx4* p);
+int nesr_sdx4_workspace_bytes(nesr_sdx4* p, int n, int h, int w, int tokens, size_t* bytes);
+int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, const int32_t* ids_host, int tokens, const float* noise_dev,
+                         const float* latents_dev, int noise_level, int steps, double guidance_scale, uint8_t* out_dev, size_t capacity,
+                         float* latents_out_dev, void* hip_stream);
+int nesr_sdx4_launches(const nesr_sdx4* p, int64_t* launches);
+enum { NESR_SDX4_GROUP_PREPARE = 0, NESR_SDX4_GROUP_STEP = 1, NESR_SDX4_GROUPS = 2 };
+int nesr_sdx4_set_timing(nesr_sdx4* p, int enable);
+int nesr_sdx4_kernel_time_ms(nesr_sdx4* p, double* group_ms, int n_groups, int64_t* launches);
+int nesr_sdx4_schedule(int num_train_timesteps, double beta_start, double beta_end, const char* beta_schedule, const char* prediction_type,
+                       int set_alpha_to_one, int steps_offset, const char* timestep_spacing, int steps, int* timesteps, double* alpha_bars,
+                       float* coefficients);
+int nesr_sdx4_noise_coefficients(int num_train_timesteps, const char* beta_schedule, int noise_level, double* alpha_bar, float* coefficients);
+/*
+ * Single-launch entries of the pipeline's two kernels (test hooks as the nesr_unet_k_* above; csrc/sdx4_api.h documents the
+ * launchers' arguments).  hw is a multiple of 4, the float pointers 16-byte and the frame 4-byte aligned; n is 1 or 2.
+ *   nesr_sdx4_k_prepare  sample [n][lc + 3][hw]: channels lc .. lc + 2 = sa (frame [hw][3] u8 / 127.5 - 1) + sb noise [3][hw], channels
+ *                        0 .. lc - 1 = sigma latents [lc][hw], which also go to latents_out [lc][hw]
+ *   nesr_sdx4_k_step     model [n][lc][hw], latents [lc][hw], the guidance and six HOST coefficients -> latents_out [lc][hw] (may be
+ *                        latents) and channels 0 .. lc - 1 of every sample of sample [n][lc + 3][hw]; channels lc .. are left
+ */
+int nesr_sdx4_k_prepare(const uint8_t* frame_dev, const float* noise_dev, const float* latents_dev, int n, int hw, int lc, float sa, float sb, float sigma,
+                        float* sample_dev, float* latents_out_dev, void* hip_stream);
+int nesr_sdx4_k_step(const float* model_dev, const float* latents_dev, int n, int hw, int lc, float guidance, const float* coefficients,
+                     float* latents_out_dev, float* sample_dev, void* hip_stream);
+
 const char* nesr_last_error(void);
 const char* nesr_version(void);
 

@@ -17,7 +17,9 @@ from .segformer import SegFormer, segformer_state_dict_spec  # noqa: F401
 from .swin2sr import Swin2SR, swin2sr_state_dict_spec  # noqa: F401
 from .vae import VaeDecoder, vae_state_dict_spec  # noqa: F401
 from .unet import UNet2DCondition, unet_state_dict_spec  # noqa: F401
+from .clip_text import ClipTextEncoder, clip_text_state_dict_spec  # noqa: F401
+from .sdx4 import StableDiffusionX4Upscaler  # noqa: F401
 
-__all__ = ["RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "Swin2SR", "UNet2DCondition", "VaeDecoder", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
+__all__ = ["ClipTextEncoder", "RRDBNet", "RealESRGANer", "SRVGGNetCompact", "SegFormer", "StableDiffusionX4Upscaler", "Swin2SR", "UNet2DCondition", "VaeDecoder", "clip_text_state_dict_spec", "conv3x3", "rrdbnet_state_dict_spec", "segformer_state_dict_spec",
            "srvgg_state_dict_spec", "swin2sr_state_dict_spec", "unet_state_dict_spec", "vae_state_dict_spec"]
 __version__ = "0.1.0"

@@ -237,6 +237,36 @@ SIGNATURES = {
                                          _c.c_void_p]),
     "nesr_vae_k_rows": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "nesr_vae_k_attention": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "nesr_clip_text_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_double,
+                                         _c.c_char_p]),
+    "nesr_clip_text_destroy": (None, [_c.c_void_p]),
+    "nesr_clip_text_num_tensors": (_c.c_int, [_c.c_void_p]),
+    "nesr_clip_text_load_weight": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.POINTER(_c.c_int64), _c.c_int]),
+    "nesr_clip_text_finalize": (_c.c_int, [_c.c_void_p]),
+    "nesr_clip_text_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "nesr_clip_text_encode_f32": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_clip_text_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_clip_text_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
+    "nesr_clip_text_k_embed": (_c.c_int, [_c.POINTER(_c.c_int32), _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                          _c.c_void_p, _c.c_void_p]),
+    "nesr_clip_text_k_attention": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                              _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_double, _c.c_char_p, _c.c_char_p,
+                                    _c.c_int, _c.c_int, _c.c_int, _c.c_char_p, _c.c_double, _c.c_int, _c.c_char_p, _c.c_int]),
+    "nesr_sdx4_destroy": (None, [_c.c_void_p]),
+    "nesr_sdx4_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
+    "nesr_sdx4_upscale_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                        _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_launches": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int64)]),
+    "nesr_sdx4_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_sdx4_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
+    "nesr_sdx4_schedule": (_c.c_int, [_c.c_int, _c.c_double, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_int, _c.c_char_p, _c.c_int,
+                                      _c.POINTER(_c.c_int), _c.POINTER(_c.c_double), _c.POINTER(_c.c_float)]),
+    "nesr_sdx4_noise_coefficients": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_float)]),
+    "nesr_sdx4_k_prepare": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.c_float, _c.c_float, _c.c_void_p,
+                                       _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_k_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.POINTER(_c.c_float), _c.c_void_p, _c.c_void_p,
+                                    _c.c_void_p]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),

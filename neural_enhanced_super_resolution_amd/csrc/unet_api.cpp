@@ -686,3 +686,9 @@ int nesr_unet_kernel_time_ms(nesr_unet* c, double* group_ms, int n_groups, int64
 }
 
 }  // extern "C"
+
+// what the x4 pipeline (sdx4_api.cpp) asks of a context it does not own
+#include "sdx4_api.h"
+nesr::Sdx4UnetInfo nesr::sdx4_unet_info(const nesr_unet* c) {
+    return Sdx4UnetInfo{c->device, c->cin, c->cout, c->levels, c->cross, c->classes, c->finalized, c->timer.launches};
+}

@@ -408,3 +408,9 @@ int nesr_vae_kernel_time_ms(nesr_vae* c, double* group_ms, int n_groups, int64_t
 }
 
 }  // extern "C"
+
+// what the x4 pipeline (sdx4_api.cpp) asks of a context it does not own
+#include "sdx4_api.h"
+nesr::Sdx4VaeInfo nesr::sdx4_vae_info(const nesr_vae* c) {
+    return Sdx4VaeInfo{c->device, c->lat, c->nout, c->nb, c->finalized, c->timer.launches};
+}

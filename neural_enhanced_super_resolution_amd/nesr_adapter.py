@@ -339,6 +339,22 @@ def swin2sr_stage(model, device=None, tile=0, tile_pad=16, max_batch=None, tile_
     return stage
 
 
+def diffusion_stage(pipe, prompt="a high resolution, detailed photograph", noise_level=20, num_inference_steps=20, guidance_scale=7.5, seed=None,
+                    prompt_ids=None, negative_ids=None, device=None):
+    """A sdx4.StableDiffusionX4Upscaler as an `extra_upscalers` entry of enhance_iterations: RGB u8 frame -> the x4 RGB u8 frame,
+    kept on the device.  It is the reference's _apply_diffusion (nesr.py:988-1031) with its CUDA settings as defaults: the slot its
+    ensemble (nesr.py:570-584) gives the diffusion result.  `prompt` needs the pipeline's tokenizer; `prompt_ids` / `negative_ids`
+    replace it.  `seed`: every frame draws from a generator seeded with it (None: torch's global generator of the device).  A frame
+    over the VAE's limit of 65536 low-res pixels raises NesrUnsupportedError naming the limit; tiling is out of scope."""
+    def stage(frame_rgb):
+        if not (isinstance(frame_rgb, torch.Tensor) and frame_rgb.is_cuda):
+            frame_rgb = _u8_on(frame_rgb, torch.device("cuda") if device is None else torch.device(device))
+        generator = None if seed is None else torch.Generator(device=frame_rgb.device).manual_seed(int(seed))
+        return pipe.upscale_frame(frame_rgb, prompt=prompt, noise_level=noise_level, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
+                                  generator=generator, prompt_ids=prompt_ids, negative_ids=negative_ids)
+    return stage
+
+
 def enhance_iterations(upscaler, image_rgb, config=None, device_kind="cuda", preprocess=None, postprocess=None,
                        trace=None, large_mp=LARGE_IMAGE_MP, filters=False, segmenter=None, extra_upscalers=(), device=None, use_hip=None,
                        encode=None, png=False, intermediates=None):
