@@ -6,7 +6,8 @@
 //   hipcc -O2 --offload-arch=gfx950 -I include examples/unet_host.cpp -o build/unet_host -ldl
 //   build/unet_host path/to/libnesr_hip.so weights.f32 sample.f32 text.f32 n h w tokens timestep class_label out.f32
 //                   [widths, e.g. 16,32] [attention per level, e.g. 1,1] [only_cross_attention per level, e.g. 1,0] [norm_num_groups]
-//                   [heads] [layers_per_block] [cross_attention_dim] [num_class_embeds]
+//                   [heads] [layers_per_block] [cross_attention_dim] [num_class_embeds] [--dtype f32|fp16]
+// --dtype (anywhere on the line; default f32) picks the compute form: nesr_unet_set_dtype between create and finalize.
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -48,9 +50,18 @@ static bool read_floats(const char* path, std::vector<float>& v) {
 }
 
 int main(int argc, char** argv) {
+    int dtype = NESR_DTYPE_F32;
+    for (int i = 1; i < argc; ++i) {      // --dtype and its value leave the line; what stays is positional
+        if (std::strcmp(argv[i], "--dtype")) continue;
+        const char* v = i + 1 < argc ? argv[i + 1] : "";
+        if (!std::strcmp(v, "fp16")) dtype = NESR_DTYPE_F16;
+        else if (std::strcmp(v, "f32")) { std::fprintf(stderr, "--dtype takes f32 or fp16, got '%s'\n", v); return 1; }
+        for (int j = i; j + 2 <= argc; ++j) argv[j] = j + 2 < argc ? argv[j + 2] : nullptr;
+        argc -= 2, --i;
+    }
     if (argc < 12) {
         std::fprintf(stderr, "usage: %s libnesr_hip.so weights.f32 sample.f32 text.f32 n h w tokens timestep class_label out.f32 [widths] [attention] "
-                             "[only_cross_attention] [norm_num_groups] [heads] [layers_per_block] [cross_attention_dim] [num_class_embeds]\n", argv[0]);
+                             "[only_cross_attention] [norm_num_groups] [heads] [layers_per_block] [cross_attention_dim] [num_class_embeds] [--dtype f32|fp16]\n", argv[0]);
         return 1;
     }
     const int n = std::atoi(argv[5]), h = std::atoi(argv[6]), w = std::atoi(argv[7]), tokens = std::atoi(argv[8]), label = std::atoi(argv[10]);
@@ -64,7 +75,7 @@ int main(int argc, char** argv) {
     void* lib = dlopen(argv[1], RTLD_NOW);
     if (!lib) { std::fprintf(stderr, "dlopen: %s\n", dlerror()); return 2; }
     LOAD(nesr_last_error) LOAD(nesr_version) LOAD(nesr_unet_create) LOAD(nesr_unet_destroy) LOAD(nesr_unet_num_tensors) LOAD(nesr_unet_load_weight)
-    LOAD(nesr_unet_finalize) LOAD(nesr_unet_workspace_bytes) LOAD(nesr_unet_forward_f32) LOAD(nesr_unet_kernel_time_ms)
+    LOAD(nesr_unet_finalize) LOAD(nesr_unet_workspace_bytes) LOAD(nesr_unet_forward_f32) LOAD(nesr_unet_kernel_time_ms) LOAD(nesr_unet_set_dtype)
     std::printf("%s\n", p_nesr_version());
 
     std::vector<const char*> down(L), up(L);
@@ -72,6 +83,10 @@ int main(int argc, char** argv) {
     nesr_unet* ctx = nullptr;
     CHECK(p_nesr_unet_create(&ctx, 0, cin, cout, L, widths.data(), down.data(), up.data(), "UNetMidBlock2DCrossAttn", only_cross.data(), layers, heads, cross, 1, 1, 0,
                              classes, groups, 1e-5, 1, 0.0, 1, "silu"));
+    if (dtype != NESR_DTYPE_F32) {
+        CHECK(p_nesr_unet_set_dtype(ctx, dtype));
+        std::printf("compute form: fp16\n");
+    }
 
     // the keys and shapes, in the spec's order
     std::vector<Entry> spec;

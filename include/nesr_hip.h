@@ -1236,6 +1236,42 @@ enum { NESR_UNET_GROUP_CONV = 0, NESR_UNET_GROUP_NORM = 1, NESR_UNET_GROUP_ATTEN
        NESR_UNET_GROUP_EMBEDDING = 5, NESR_UNET_GROUP_RESAMPLE = 6, NESR_UNET_GROUPS = 7 };
 int nesr_unet_set_timing(nesr_unet* ctx, int enable);
 int nesr_unet_kernel_time_ms(nesr_unet* ctx, double* group_ms, int n_groups, int64_t* launches);
+/*
+ * The fp16 compute form.  nesr_unet_set_dtype, between nesr_unet_create and nesr_unet_finalize (NESR_ERR_STATE after it):
+ * NESR_DTYPE_F32 (the default: the path above, unchanged in launches and in bits) or NESR_DTYPE_F16; NESR_DTYPE_BF16 and every
+ * other value are NESR_ERR_UNSUPPORTED, and the text names the value.  The dtype is checked before the context.  nesr_unet_dtype
+ * reads it back.
+ *
+ * NESR_DTYPE_F16: storage in memory stays f32 in and out, and so do the layouts, the workspace, the skip stack and the residual
+ * stream; a forward makes the same number of launches, each f16 launch in the place of one f32 launch.  Both operands of every
+ * 3x3 conv (conv_in, the ResnetBlocks' convs, the downsamplers, the up-convs, conv_out) and of every row product (the 1x1
+ * shortcuts, proj_in / proj_out, q, q | k | v, the text's k | v, to_out, ff.net.0.proj, ff.net.2) are rounded to f16 (nearest
+ * even, a plain cast) with f32 products and sums on v_mfma_f32_16x16x32_f16 (a K tail of 16 on v_mfma_f32_16x16x16_f16).  The
+ * activation is rounded AFTER its prologue (GroupNorm + SiLU, GroupNorm, LayerNorm, each evaluated in f32); a padding tap is 0.
+ * Biases, residuals, GEGLU's (h + b_h) gelu(g + b_g), the norms' statistics, the streamed attention on the f32 q, k, v, the
+ * embedding and time_emb_proj stay the f32 form's arithmetic.  An operand that rounds to an f16 subnormal (below 6.1e-5 in
+ * magnitude) is KEPT by the MI355X's matrix cores, not flushed to zero.  An output element's K chain runs in one workgroup in
+ * ascending k, so a call repeated gives the same bits and a sample's result does not depend on n, as in the f32 form.
+ * The device then holds the f16 copy of those weights and NOT their f32 form: nesr_unet_weight_bytes gives what finalize uploads.
+ *
+ * Range: f16 carries |x| <= 65504.  A weight of one of those products beyond that (or non-finite) is NESR_ERR_RANGE at
+ * nesr_unet_finalize, before any device call, and the text names the key (a context of NESR_UNET_NO_DEVICE reaches this on the
+ * CPU); the embedding's and time_emb_proj's weights are not rounded and not checked.  An activation that is non-finite or beyond
+ * +-65504 when it is rounded raises the context's range word; nesr_unet_forward_f32 on such a context clears the word in front
+ * of its launches, waits for the stream behind them and returns NESR_ERR_RANGE then: the output is not valid.  So an fp16 forward
+ * is synchronous; the f32 form neither waits nor checks.
+ *
+ * nesr_unet_pack_linear_f16 / nesr_unet_pack_conv_f16: the packing finalize applies to one such weight, on the host, stateless.
+ * weight [n][k0 + k1] (torch's Linear, or a 1x1 conv over a concatenation of k0 | k1 channels; k1 = 0: one source) ->
+ * out [round16(n)][round16(k0) + round16(k1)] f16, k contiguous, source 1's k from round16(k0), zeros elsewhere; weight
+ * [n][c0 + c1][3][3] -> out [round16(n)][9 taps][round16(c0) + round16(c1)].  out_halves must be exactly that count.
+ * NESR_ERR_RANGE for a value f16 cannot carry.
+ */
+int nesr_unet_set_dtype(nesr_unet* ctx, int dtype);
+int nesr_unet_dtype(const nesr_unet* ctx);
+int nesr_unet_weight_bytes(const nesr_unet* ctx, size_t* bytes);
+int nesr_unet_pack_linear_f16(const float* weight_host, int n, int k0, int k1, uint16_t* out_host, size_t out_halves);
+int nesr_unet_pack_conv_f16(const float* weight_host, int n, int c0, int c1, uint16_t* out_host, size_t out_halves);
 
 /*
  * Single-launch entries of the UNet's kernels (test hooks for the per-launch parity tests, csrc/unet_kernel_api.cpp; not pipeline
@@ -1275,6 +1311,21 @@ int nesr_unet_k_rows(int m, int rows_per_sample, const float* in0_dev, int c0, i
                      const float* b_dev, int ldw, int np, int geglu, const float* res_dev, float* out_dev, void* hip_stream);
 int nesr_unet_k_attention(int samples, int nq, int nk, int heads, int d, const float* q_dev, const float* k_dev, const float* v_dev, int ldq, int ldkv,
                           int ldo, float* out_dev, void* hip_stream);
+/*
+ * The fp16 form's two launches (csrc/unet_f16_kernel_api.cpp): the arguments of nesr_unet_k_conv / nesr_unet_k_rows, with the
+ * weight as the DEVICE pointer w16_dev to its f16 packing, 16-byte aligned: rows W16[ldw][cs0 + cs1], conv
+ * W16[coutp][9][cs0 + cs1] (each source's K is its row width cs, not the width rounded up to 4), k contiguous.  range_dev: a
+ * DEVICE word the launch raises (stores 1) when an activation is non-finite or beyond +-65504 as it is rounded, or null.
+ * block_host: where the output columns (conv: channels) of a workgroup that the launcher picked from the shape, 128, 64 or 32,
+ * are written on the host, or null.
+ */
+int nesr_unet_k_conv_f16(int n, int H, int W, int stride, int up, const float* in0_dev, int c0, int cs0, const void* norm0_dev, const float* in1_dev,
+                         int c1, int cs1, const void* norm1_dev, const void* w16_dev, const float* bias_dev, int cout, int coutp, const float* res_dev,
+                         int out_nchw, float* out_dev, unsigned* range_dev, int* block_host, void* hip_stream);
+int nesr_unet_k_rows_f16(int m, int rows_per_sample, const float* in0_dev, int c0, int cs0, const void* norm0_dev, const float* in1_dev, int c1, int cs1,
+                         const void* norm1_dev, int prologue, const void* ln_dev, const float* ln_g_dev, const float* ln_b_dev, const void* w16_dev,
+                         const float* b_dev, int ldw, int np, int geglu, const float* res_dev, float* out_dev, unsigned* range_dev, int* block_host,
+                         void* hip_stream);
 
 /*
  * Single-launch entries of the VAE decoder's kernels (test hooks as the nesr_unet_k_* above, csrc/vae_kernel_api.cpp): each fills

@@ -215,6 +215,17 @@ SIGNATURES = {
                                          _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_unet_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_unet_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
+    "nesr_unet_set_dtype": (_c.c_int, [_c.c_void_p, _c.c_int]),
+    "nesr_unet_dtype": (_c.c_int, [_c.c_void_p]),
+    "nesr_unet_weight_bytes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_size_t)]),
+    "nesr_unet_pack_linear_f16": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t]),
+    "nesr_unet_pack_conv_f16": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t]),
+    "nesr_unet_k_conv_f16": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                        _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.POINTER(_c.c_int), _c.c_void_p]),
+    "nesr_unet_k_rows_f16": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p]),
     "nesr_unet_k_in": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_longlong, _c.c_void_p, _c.c_void_p]),
     "nesr_unet_k_embedding": (_c.c_int, [_c.c_double, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p]),

@@ -13,6 +13,7 @@
 
 #include "api_common.h"
 #include "sdx4_api.h"
+#include "unet_api.h"
 
 using namespace nesr;
 
@@ -274,6 +275,9 @@ int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, c
     const int64_t before = p->timer.launches + ti.launches + sdx4_unet_info(p->unet).launches + sdx4_vae_info(p->vae).launches;
 
     if ((rc = nesr_clip_text_encode_f32(p->text, ids_host, n, tokens, text, (size_t)n * tokens * ti.hidden, stream))) return rc;
+    // An fp16 UNet's range word is cleared once here and read once behind the last launch: the steps' forwards neither clear it nor
+    // wait, so the call still has no synchronisation inside.  With an f32 UNet both calls do nothing.
+    if ((rc = unet_range_begin(p->unet, s))) return rc;
     {
         Sdx4Prepare a;
         memset(&a, 0, sizeof(a));
@@ -289,7 +293,7 @@ int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, c
         float coef[6];
         ddim_step(p->ddim, steps, i, t, ab, pv, coef);
         // scale_model_input is the identity; the noise level is the class label
-        if ((rc = nesr_unet_forward_f32(p->unet, sample, n, cin, h, w, (double)t, noise_level, text, tokens, model, (size_t)n * p->lc * hw, stream))) return rc;
+        if ((rc = unet_forward_unchecked(p->unet, sample, n, cin, h, w, (double)t, noise_level, text, tokens, model, (size_t)n * p->lc * hw, s))) return rc;
         Sdx4Step a;
         memset(&a, 0, sizeof(a));
         a.model = model, a.latents = latents, a.n = n, a.hw = hw, a.lc = p->lc, a.g = (float)guidance_scale;
@@ -300,7 +304,7 @@ int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, c
     if ((rc = nesr_vae_decode_latents_u8(p->vae, latents, 1, p->lc, h, w, out_dev, capacity, stream))) return rc;
     if (latents_out_dev) NESR_TRY(hipMemcpyAsync(latents_out_dev, latents, (size_t)p->lc * hw * 4, hipMemcpyDeviceToDevice, s));      // for the tests; after the last launch
     p->last_launches = p->timer.launches + sdx4_text_info(p->text).launches + sdx4_unet_info(p->unet).launches + sdx4_vae_info(p->vae).launches - before;
-    return NESR_OK;
+    return unet_range_end(p->unet, s, "nesr_sdx4_upscale_u8");
 }
 
 int nesr_sdx4_launches(const nesr_sdx4* p, int64_t* launches) {

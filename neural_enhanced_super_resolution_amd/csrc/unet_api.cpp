@@ -1,5 +1,6 @@
 // UNet contexts (nesr_unet_*): the configuration check, strict weight loading, the padded and transposed upload, a workspace that
-// holds the skip stack and grows with the frame, and the forward as a chain of launches of the kernels of unet.hip.  Stands behind
+// holds the skip stack and grows with the frame, and the forward as a chain of launches of the kernels of unet.hip (in the fp16
+// compute form, nesr_unet_set_dtype, the convs and the row products are unet_f16.hip's on an f16 copy of their weights).  Stands behind
 // diffusers' UNet2DConditionModel.forward as StableDiffusionUpscalePipeline calls it: (sample, timestep, encoder_hidden_states,
 // class_labels) -> the predicted noise.
 #include <cmath>
@@ -65,6 +66,12 @@ struct nesr_unet {
     StateDict sd;
     bool finalized = false;
     float* d_w = nullptr;
+    int dtype = NESR_DTYPE_F32;      // the compute form (nesr_unet_set_dtype)
+    bool packed = false;             // finalize has run: the form is fixed
+    _Float16* d_w16 = nullptr;       // fp16 form: the GEMM weights, which d_w then does not hold
+    unsigned* d_status = nullptr;    // fp16 form: the range word
+    unsigned* h_status = nullptr;
+    size_t weight_bytes = 0;         // what finalize uploaded (or would have)
     ULinW t1, t2;
     size_t cls = 0;
     UConvW conv_in, conv_out;
@@ -78,6 +85,37 @@ struct nesr_unet {
 };
 
 namespace {
+
+// ---- the fp16 form's weight packing (unet_api.h).  Each returns whether a value was non-finite or beyond +-65504.
+inline bool f16_carries(float v) { return std::fabs(v) <= 65504.0f; }
+
+// rows [r0, r0 + n) of torch's weight [.][k0 + k1] -> rows [col0, col0 + n) of W16[.][K], K = round16(k0) + round16(k1): source
+// 1's k start at round16(k0)
+bool pack_rows_f16(_Float16* dst, const float* w, int r0, int n, int k0, int k1, int col0) {
+    const int k = k0 + k1, kp0 = round_up(k0, 16), K = kp0 + (k1 ? round_up(k1, 16) : 0);
+    bool bad = false;
+    for (int o = 0; o < n; ++o)
+        for (int kk = 0; kk < k; ++kk) {
+            const float v = w[(size_t)(r0 + o) * k + kk];
+            bad |= !f16_carries(v);
+            dst[(size_t)(col0 + o) * K + (kk < k0 ? kk : kp0 + kk - k0)] = (_Float16)v;
+        }
+    return bad;
+}
+
+// conv weight [n][c0 + c1][9] -> W16[round16(n)][9][round16(c0) + round16(c1)]
+bool pack_conv_f16(_Float16* dst, const float* w, int n, int c0, int c1) {
+    const int cin = c0 + c1, cs0 = round_up(c0, 16), ktap = cs0 + (c1 ? round_up(c1, 16) : 0);
+    bool bad = false;
+    for (int o = 0; o < n; ++o)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < 9; ++t) {
+                const float v = w[((size_t)o * cin + ci) * 9 + t];
+                bad |= !f16_carries(v);
+                dst[((size_t)o * 9 + t) * ktap + (ci < c0 ? ci : cs0 + ci - c0)] = (_Float16)v;
+            }
+    return bad;
+}
 
 int unsupported(const std::string& field, const std::string& why) {
     return set_error(NESR_ERR_UNSUPPORTED, "nesr_unet_create: " + field + ": " + why);
@@ -197,6 +235,7 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
     VaeNorm* norm[2] = {reinterpret_cast<VaeNorm*>(c->ws_buf + p.norm[0]), reinterpret_cast<VaeNorm*>(c->ws_buf + p.norm[1])};
     float4* ln = reinterpret_cast<float4*>(c->ws_buf + p.ln);
     const float* W = c->d_w;
+    const bool f16 = c->dtype == NESR_DTYPE_F16;      // a GEMM weight's offset then counts halves of d_w16
     const int L = c->levels, crossp = round_up(c->cross, 16);
     int H = h, Wd = w;
 
@@ -218,21 +257,31 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
     };
     // a conv over the current grid H x Wd (the OUTPUT grid)
     auto conv_args = [&](const UConvW& cw, const float* in0, const float* in1, bool normed, float* o) {
-        UnetConv a;
+        UnetConv16 a;
         memset(&a, 0, sizeof(a));
         a.n = n, a.H = H, a.W = Wd, a.stride = 1;
         a.in[0] = src(in0, cw.cin0, normed ? norm[0] : nullptr), a.in[1] = src(in1, cw.cin1, normed && in1 ? norm[1] : nullptr);
-        a.w = W + cw.w, a.bias = W + cw.b, a.cout = cw.cout, a.coutp = cw.coutp, a.out = o;
+        a.bias = W + cw.b, a.cout = cw.cout, a.coutp = cw.coutp, a.out = o;
+        if (f16) a.w16 = c->d_w16 + cw.w, a.status = c->d_status;
+        else a.w = W + cw.w;
         return a;
+    };
+    auto run_conv = [&](const UnetConv16& a, int group) -> int {
+        if (f16) NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_conv_f16(a, s); });
+        else NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_conv(a, s); });
+        return NESR_OK;
     };
     auto rows_args = [&](const ULinW& l, int m, const float* in0, int k0, float* o) {
-        UnetRows a;
+        UnetRows16 a;
         memset(&a, 0, sizeof(a));
-        a.m = m, a.rows_per_sample = m / n, a.in[0] = src(in0, k0, nullptr), a.w = W + l.w, a.b = W + l.b, a.ldw = l.np, a.np = l.np, a.out = o;
+        a.m = m, a.rows_per_sample = m / n, a.in[0] = src(in0, k0, nullptr), a.b = W + l.b, a.ldw = l.np, a.np = l.np, a.out = o;
+        if (f16) a.w16 = c->d_w16 + l.w, a.status = c->d_status;
+        else a.w = W + l.w;
         return a;
     };
-    auto run_rows = [&](const UnetRows& a, int group) -> int {
-        NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows(a, s); });
+    auto run_rows = [&](const UnetRows16& a, int group) -> int {
+        if (f16) NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows_f16(a, s); });
+        else NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows(a, s); });
         return NESR_OK;
     };
     auto layer_norm = [&](UnetRows& a, const UNormW& nw, const float* in, int m, int dim) -> int {
@@ -247,57 +296,56 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
     auto resnet = [&](const UResW& r, const float* in0, const float* in1, float* o) -> int {
         if ((rc = gn(r.n1, in0, r.cin0, in1, r.cin1, c->eps))) return rc;
         {
-            UnetConv a = conv_args(r.c1, in0, in1, true, t1);
+            UnetConv16 a = conv_args(r.c1, in0, in1, true, t1);
             a.bias = temb + (size_t)r.index * UNET_MAX_WIDTH;      // conv1.bias + time_emb_proj(silu(emb))
-            NESR_RUN(c->timer, kName, NESR_UNET_GROUP_CONV, s, [&] { return launch_unet_conv(a, s); });
+            if ((rc = run_conv(a, NESR_UNET_GROUP_CONV))) return rc;
         }
         if ((rc = gn(r.n2, t1, r.cout, nullptr, 0, c->eps))) return rc;
         if (r.has_sc) {
-            UnetRows a = rows_args(r.sc, n * H * Wd, in0, r.cin0, t2);
+            UnetRows16 a = rows_args(r.sc, n * H * Wd, in0, r.cin0, t2);
             a.in[1] = src(in1, r.cin1, nullptr);
             if ((rc = run_rows(a, NESR_UNET_GROUP_PROJ))) return rc;
         }
-        UnetConv a = conv_args(r.c2, t1, nullptr, true, o);
+        UnetConv16 a = conv_args(r.c2, t1, nullptr, true, o);
         a.res = r.has_sc ? t2 : in0;
-        NESR_RUN(c->timer, kName, NESR_UNET_GROUP_CONV, s, [&] { return launch_unet_conv(a, s); });
-        return NESR_OK;
+        return run_conv(a, NESR_UNET_GROUP_CONV);
     };
     auto attention = [&](const UAttnW& at, const UNormW& lnw, int dim, int m) -> int {      // hb += to_out(attn(LN(hb), context))
         const int dimp = round_up(dim, 16), tok = H * Wd;
         UnetAttn a;
         memset(&a, 0, sizeof(a));
         a.samples = n, a.nq = tok, a.heads = c->heads, a.d = dim / c->heads, a.out = ab, a.ldo = dimp;
-        UnetRows q = rows_args(at.q, m, hb, dim, qb);
+        UnetRows16 q = rows_args(at.q, m, hb, dim, qb);
         if ((rc = layer_norm(q, lnw, hb, m, dim))) return rc;
         if ((rc = run_rows(q, NESR_UNET_GROUP_PROJ))) return rc;
         if (at.self) {
             a.nk = tok, a.q = qb, a.k = qb + dimp, a.v = qb + 2 * dimp, a.ldq = a.ldkv = 3 * dimp;
         } else {
-            const UnetRows kv = rows_args(at.kv, n * tokens, textr, c->cross, kvb);
+            const UnetRows16 kv = rows_args(at.kv, n * tokens, textr, c->cross, kvb);
             if ((rc = run_rows(kv, NESR_UNET_GROUP_PROJ))) return rc;
             a.nk = tokens, a.q = qb, a.ldq = dimp, a.k = kvb, a.v = kvb + dimp, a.ldkv = 2 * dimp;
         }
         NESR_RUN(c->timer, kName, NESR_UNET_GROUP_ATTENTION, s, [&] { return launch_unet_attn(a, s); });
-        UnetRows o = rows_args(at.out, m, ab, dim, hb);
+        UnetRows16 o = rows_args(at.out, m, ab, dim, hb);
         o.res = hb;
         return run_rows(o, NESR_UNET_GROUP_PROJ);
     };
     auto transformer = [&](const UTfW& tf, float* x) -> int {      // in place
         const int dim = tf.dim, m = n * H * Wd;
         if ((rc = gn(tf.gn, x, dim, nullptr, 0, kTfNormEps))) return rc;
-        UnetRows pin = rows_args(tf.pin, m, x, dim, hb);
+        UnetRows16 pin = rows_args(tf.pin, m, x, dim, hb);
         pin.prologue = UNET_PRO_GROUPNORM, pin.in[0].norm = norm[0];
         if ((rc = run_rows(pin, NESR_UNET_GROUP_PROJ))) return rc;
         if ((rc = attention(tf.a1, tf.ln1, dim, m))) return rc;
         if ((rc = attention(tf.a2, tf.ln2, dim, m))) return rc;
-        UnetRows f0 = rows_args(tf.ff0, m, hb, dim, qb);
+        UnetRows16 f0 = rows_args(tf.ff0, m, hb, dim, qb);
         f0.geglu = 1, f0.ldw = 2 * tf.ff0.np;
         if ((rc = layer_norm(f0, tf.ln3, hb, m, dim))) return rc;
         if ((rc = run_rows(f0, NESR_UNET_GROUP_FF))) return rc;
-        UnetRows f2 = rows_args(tf.ff2, m, qb, 4 * dim, hb);
+        UnetRows16 f2 = rows_args(tf.ff2, m, qb, 4 * dim, hb);
         f2.res = hb;
         if ((rc = run_rows(f2, NESR_UNET_GROUP_FF))) return rc;
-        UnetRows po = rows_args(tf.pout, m, hb, dim, x);
+        UnetRows16 po = rows_args(tf.pout, m, hb, dim, x);
         po.res = x;
         return run_rows(po, NESR_UNET_GROUP_PROJ);
     };
@@ -331,8 +379,8 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         return b;
     };
     {
-        const UnetConv a = conv_args(c->conv_in, inr, nullptr, false, push());
-        NESR_RUN(c->timer, kName, NESR_UNET_GROUP_CONV, s, [&] { return launch_unet_conv(a, s); });
+        const UnetConv16 a = conv_args(c->conv_in, inr, nullptr, false, push());
+        if ((rc = run_conv(a, NESR_UNET_GROUP_CONV))) return rc;
         cur = skips.back();
     }
     for (int i = 0; i < L; ++i) {
@@ -345,9 +393,9 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         }
         if (b.has_samp) {
             H /= 2, Wd /= 2;
-            UnetConv a = conv_args(b.samp, cur, nullptr, false, push());
+            UnetConv16 a = conv_args(b.samp, cur, nullptr, false, push());
             a.stride = 2;
-            NESR_RUN(c->timer, kName, NESR_UNET_GROUP_RESAMPLE, s, [&] { return launch_unet_conv(a, s); });
+            if ((rc = run_conv(a, NESR_UNET_GROUP_RESAMPLE))) return rc;
             cur = skips.back();
         }
     }
@@ -366,17 +414,16 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         }
         if (b.has_samp) {
             H *= 2, Wd *= 2;
-            UnetConv a = conv_args(b.samp, cur, nullptr, false, other);
+            UnetConv16 a = conv_args(b.samp, cur, nullptr, false, other);
             a.up = 1;
-            NESR_RUN(c->timer, kName, NESR_UNET_GROUP_RESAMPLE, s, [&] { return launch_unet_conv(a, s); });
+            if ((rc = run_conv(a, NESR_UNET_GROUP_RESAMPLE))) return rc;
             std::swap(cur, other);
         }
     }
     if ((rc = gn(c->norm_out, cur, c->width[0], nullptr, 0, c->eps))) return rc;
-    UnetConv a = conv_args(c->conv_out, cur, nullptr, true, out);
+    UnetConv16 a = conv_args(c->conv_out, cur, nullptr, true, out);
     a.out_nchw = 1;
-    NESR_RUN(c->timer, kName, NESR_UNET_GROUP_CONV, s, [&] { return launch_unet_conv(a, s); });
-    return NESR_OK;
+    return run_conv(a, NESR_UNET_GROUP_CONV);
 }
 
 }  // namespace
@@ -481,11 +528,54 @@ void nesr_unet_destroy(nesr_unet* c) {
         c->timer.destroy();
         if (c->ws_buf) (void)hipFree(c->ws_buf);
         if (c->d_w) (void)hipFree(c->d_w);
+        if (c->d_w16) (void)hipFree(c->d_w16);
+        if (c->d_status) (void)hipFree(c->d_status);
+        if (c->h_status) (void)hipHostFree(c->h_status);
     }
     delete c;
 }
 
 int nesr_unet_num_tensors(const nesr_unet* c) { return c ? (int)c->sd.size() : 0; }
+
+int nesr_unet_set_dtype(nesr_unet* c, int dtype) {
+    if (dtype == NESR_DTYPE_BF16)
+        return set_error(NESR_ERR_UNSUPPORTED, "nesr_unet_set_dtype: NESR_DTYPE_BF16 (" + std::to_string(dtype) + ") is not a form of the UNet: NESR_DTYPE_F32 or NESR_DTYPE_F16");
+    if (dtype != NESR_DTYPE_F32 && dtype != NESR_DTYPE_F16)
+        return set_error(NESR_ERR_UNSUPPORTED, "nesr_unet_set_dtype: dtype " + std::to_string(dtype) + " is not a form of the UNet: NESR_DTYPE_F32 or NESR_DTYPE_F16");
+    if (!c) return set_error(NESR_ERR_ARG, "nesr_unet_set_dtype: null context");
+    if (c->packed) return set_error(NESR_ERR_STATE, "nesr_unet_set_dtype: the compute form is chosen between nesr_unet_create and nesr_unet_finalize");
+    c->dtype = dtype;
+    return NESR_OK;
+}
+
+int nesr_unet_dtype(const nesr_unet* c) { return c ? c->dtype : NESR_DTYPE_F32; }
+
+int nesr_unet_weight_bytes(const nesr_unet* c, size_t* bytes) {
+    if (!c || !bytes) return set_error(NESR_ERR_ARG, "nesr_unet_weight_bytes: null pointer");
+    if (!c->packed) return set_error(NESR_ERR_STATE, "nesr_unet_weight_bytes: weights not finalized (nesr_unet_finalize)");
+    *bytes = c->weight_bytes;
+    return NESR_OK;
+}
+
+int nesr_unet_pack_linear_f16(const float* weight, int n, int k0, int k1, uint16_t* out, size_t out_halves) {
+    if (!weight || !out || n < 1 || k0 < 1 || k1 < 0) return set_error(NESR_ERR_ARG, "nesr_unet_pack_linear_f16: a weight [n][k0 + k1] with n, k0 >= 1 and k1 >= 0");
+    const size_t need = (size_t)round_up(n, 16) * (round_up(k0, 16) + (k1 ? round_up(k1, 16) : 0));
+    if (out_halves != need) return set_error(NESR_ERR_ARG, "nesr_unet_pack_linear_f16: out_halves must be round16(n) (round16(k0) + round16(k1)) = " + std::to_string(need));
+    memset(out, 0, need * sizeof(uint16_t));
+    if (pack_rows_f16(reinterpret_cast<_Float16*>(out), weight, 0, n, k0, k1, 0))
+        return set_error(NESR_ERR_RANGE, "nesr_unet_pack_linear_f16: the weight holds a value that is non-finite or beyond +-65504");
+    return NESR_OK;
+}
+
+int nesr_unet_pack_conv_f16(const float* weight, int n, int c0, int c1, uint16_t* out, size_t out_halves) {
+    if (!weight || !out || n < 1 || c0 < 1 || c1 < 0) return set_error(NESR_ERR_ARG, "nesr_unet_pack_conv_f16: a weight [n][c0 + c1][3][3] with n, c0 >= 1 and c1 >= 0");
+    const size_t need = (size_t)round_up(n, 16) * 9 * (round_up(c0, 16) + (c1 ? round_up(c1, 16) : 0));
+    if (out_halves != need) return set_error(NESR_ERR_ARG, "nesr_unet_pack_conv_f16: out_halves must be round16(n) 9 (round16(c0) + round16(c1)) = " + std::to_string(need));
+    memset(out, 0, need * sizeof(uint16_t));
+    if (pack_conv_f16(reinterpret_cast<_Float16*>(out), weight, n, c0, c1))
+        return set_error(NESR_ERR_RANGE, "nesr_unet_pack_conv_f16: the weight holds a value that is non-finite or beyond +-65504");
+    return NESR_OK;
+}
 
 int nesr_unet_load_weight(nesr_unet* c, const char* key, const float* data, const int64_t* shape, int ndim) {
     if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_unet_load_weight: null argument");
@@ -500,6 +590,19 @@ int nesr_unet_finalize(nesr_unet* c) {
     const std::string missing = sd.missing();
     if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
     HostPack pk;
+    // The fp16 form: a GEMM weight goes into `hh` alone, packed as unet_api.h states for unet_f16.hip, and its offset counts halves;
+    // the f32 buffer then holds the biases, the norms, the class table and the M = 1 products' weights (embedding, time_emb_proj).
+    const bool f16 = c->dtype == NESR_DTYPE_F16;
+    std::vector<_Float16> hh;
+    std::string out_of_range;
+    auto reserve_h = [&](size_t halves) {
+        const size_t at = hh.size();
+        hh.resize((at + halves + 63) / 64 * 64, (_Float16)0.f);
+        return at;
+    };
+    auto note = [&](const std::string& key, bool bad) {
+        if (bad && out_of_range.empty()) out_of_range = key;
+    };
     const int L = c->levels, td = td_of(c), tdp = round_up(td, 16), cross = c->cross;
     auto norm = [&](const std::string& name, int ch) {
         UNormW n;
@@ -510,9 +613,15 @@ int nesr_unet_finalize(nesr_unet* c) {
     auto conv = [&](const std::string& name, int n, int cin0, int cin1) {
         UConvW r;
         r.cin0 = cin0, r.cin1 = cin1, r.cout = n, r.coutp = round_up(n, 16);
+        const std::vector<float>& w = sd.data(name + ".weight");
+        if (f16) {
+            r.w = reserve_h((size_t)r.coutp * 9 * (round_up(cin0, 16) + (cin1 ? round_up(cin1, 16) : 0)));
+            note(name + ".weight", pack_conv_f16(hh.data() + r.w, w.data(), n, cin0, cin1));
+            r.b = pk.vec(sd.data(name + ".bias"), r.coutp);
+            return r;
+        }
         const int cinp0 = round_up(cin0, 4), cinp = cinp0 + round_up(cin1, 4), cin = cin0 + cin1;
         r.w = pk.reserve((size_t)9 * cinp * r.coutp);
-        const std::vector<float>& w = sd.data(name + ".weight");
         for (int o = 0; o < n; ++o)
             for (int ci = 0; ci < cin; ++ci)
                 for (int t = 0; t < 9; ++t) pk.host[r.w + ((size_t)t * cinp + (ci < cin0 ? ci : cinp0 + ci - cin0)) * r.coutp + o] = w[((size_t)o * cin + ci) * 9 + t];
@@ -520,16 +629,22 @@ int nesr_unet_finalize(nesr_unet* c) {
         return r;
     };
     // rows [r0, r0 + n) of torch's weight [.][k0 + k1] -> columns [col0, col0 + n) of Wt[round16(k0) + round16(k1)][ld]
-    auto put = [&](size_t at, const std::vector<float>& w, int r0, int n, int k0, int k1, int ld, int col0) {
+    // (fp16 form, a GEMM weight: rows [col0, col0 + n) of W16[ld][K] at `at` of hh)
+    auto put = [&](size_t at, const std::string& key, int r0, int n, int k0, int k1, int ld, int col0, bool gemm = true) {
+        const std::vector<float>& w = sd.data(key);
+        if (f16 && gemm) return note(key, pack_rows_f16(hh.data() + at, w.data(), r0, n, k0, k1, col0));
         const int k = k0 + k1, kp0 = round_up(k0, 16);
         for (int o = 0; o < n; ++o)
             for (int kk = 0; kk < k; ++kk) pk.host[at + (size_t)(kk < k0 ? kk : kp0 + kk - k0) * ld + col0 + o] = w[(size_t)(r0 + o) * k + kk];
     };
-    auto linear = [&](const std::string& name, int n, int k0, int k1, bool bias) {
+    // a matrix of K rows and ld columns: where its elements go (floats of pk, or halves of hh for a GEMM weight of the fp16 form)
+    auto matrix = [&](size_t K, size_t ld, bool gemm = true) { return f16 && gemm ? reserve_h(K * ld) : pk.reserve(K * ld); };
+    // gemm false: an M = 1 product on plain FMAs (the embedding, time_emb_proj), f32 in either form
+    auto linear = [&](const std::string& name, int n, int k0, int k1, bool bias, bool gemm = true) {
         ULinW l;
         l.np = round_up(n, 16);
-        l.w = pk.reserve((size_t)(round_up(k0, 16) + (k1 ? round_up(k1, 16) : 0)) * l.np);
-        put(l.w, sd.data(name + ".weight"), 0, n, k0, k1, l.np, 0);
+        l.w = matrix(round_up(k0, 16) + (k1 ? round_up(k1, 16) : 0), l.np, gemm);
+        put(l.w, name + ".weight", 0, n, k0, k1, l.np, 0, gemm);
         l.b = bias ? pk.vec(sd.data(name + ".bias"), l.np) : pk.reserve(l.np);
         return l;
     };
@@ -538,10 +653,10 @@ int nesr_unet_finalize(nesr_unet* c) {
         ULinW l;
         const int np1 = round_up(n, 16), count = (int)parts.size();
         l.np = count * np1;
-        l.w = pk.reserve((size_t)round_up(k, 16) * l.np);
+        l.w = matrix(round_up(k, 16), l.np);
         l.b = pk.reserve(l.np);
         int i = 0;
-        for (const char* part : parts) put(l.w, sd.data(at + part + ".weight"), 0, n, k, 0, l.np, np1 * i++);
+        for (const char* part : parts) put(l.w, at + part + ".weight", 0, n, k, 0, l.np, np1 * i++);
         return l;
     };
     c->resnets.clear();
@@ -550,7 +665,7 @@ int nesr_unet_finalize(nesr_unet* c) {
         const int cin = cin0 + cin1;
         w.cin0 = cin0, w.cin1 = cin1, w.cout = cout;
         w.n1 = norm(r + ".norm1", cin), w.c1 = conv(r + ".conv1", cout, cin0, cin1), w.n2 = norm(r + ".norm2", cout), w.c2 = conv(r + ".conv2", cout, cout, 0);
-        const ULinW t = linear(r + ".time_emb_proj", cout, td, 0, true);      // Wt[td][coutp]: td = 4 width[0] is a multiple of 8, its K is not tiled
+        const ULinW t = linear(r + ".time_emb_proj", cout, td, 0, true, false);      // Wt[td][coutp]: td = 4 width[0] is a multiple of 8, its K is not tiled
         w.tw = t.w, w.tb = t.b;
         w.has_sc = cin != cout;
         if (w.has_sc) w.sc = linear(r + ".conv_shortcut", cout, cin0, cin1, true);
@@ -577,12 +692,11 @@ int nesr_unet_finalize(nesr_unet* c) {
         {   // GEGLU: value half | gate half, Wt[dimp][2 inner]
             const int inner = 4 * dim, dimp = round_up(dim, 16), np = round_up(inner, 16);
             t.ff0.np = np;
-            t.ff0.w = pk.reserve((size_t)dimp * 2 * np);
+            t.ff0.w = matrix(dimp, 2 * np);
             t.ff0.b = pk.reserve(2 * np);
-            const std::vector<float>& w = sd.data(b + ".ff.net.0.proj.weight");
             const std::vector<float>& bias = sd.data(b + ".ff.net.0.proj.bias");
             for (int half = 0; half < 2; ++half) {
-                put(t.ff0.w, w, half * inner, inner, dim, 0, 2 * np, half * np);
+                put(t.ff0.w, b + ".ff.net.0.proj.weight", half * inner, inner, dim, 0, 2 * np, half * np);
                 std::copy(bias.begin() + half * inner, bias.begin() + (half + 1) * inner, pk.host.begin() + t.ff0.b + (size_t)half * np);
             }
         }
@@ -590,8 +704,8 @@ int nesr_unet_finalize(nesr_unet* c) {
         return t;
     };
     c->conv_in = conv("conv_in", c->width[0], c->cin, 0);
-    c->t1 = linear("time_embedding.linear_1", td, c->width[0], 0, true);
-    c->t2 = linear("time_embedding.linear_2", td, td, 0, true);
+    c->t1 = linear("time_embedding.linear_1", td, c->width[0], 0, true, false);
+    c->t2 = linear("time_embedding.linear_2", td, td, 0, true, false);
     {   // the class table, rows padded to tdp
         c->cls = pk.reserve((size_t)c->classes * tdp);
         const std::vector<float>& w = sd.data("class_embedding.weight");
@@ -637,9 +751,29 @@ int nesr_unet_finalize(nesr_unet* c) {
     number(c->mid);
     for (UBlockW& b : c->up) number(b);
     if ((int)c->resnets.size() > UNET_MAX_RESNETS) return set_error(NESR_ERR_STATE, "nesr_unet_finalize: more ResnetBlocks than the embedding launch takes");
+    if (!out_of_range.empty())      // before any device call
+        return set_error(NESR_ERR_RANGE, "nesr_unet_finalize: " + out_of_range + " holds a value that is non-finite or beyond +-65504, which the fp16 form "
+                                             "cannot carry (NESR_DTYPE_F32 can)");
+    c->packed = true;
+    c->weight_bytes = pk.host.size() * sizeof(float) + hh.size() * sizeof(_Float16);
     if (c->device == NESR_UNET_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no forward either
     const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
     if (rc) return rc;
+    if (f16) {
+        if (c->d_w16) NESR_TRY(hipFree(c->d_w16));
+        c->d_w16 = nullptr;
+        if (hipMalloc((void**)&c->d_w16, hh.size() * sizeof(_Float16)) != hipSuccess) {
+            c->d_w16 = nullptr;
+            return set_error(NESR_ERR_NOMEM, std::string(kName) + ": allocating the f16 weights failed");
+        }
+        NESR_TRY(hipMemcpy(c->d_w16, hh.data(), hh.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+        if (!c->d_status) {
+            NESR_TRY(hipMalloc((void**)&c->d_status, sizeof(unsigned)));
+            NESR_TRY(hipHostMalloc((void**)&c->h_status, sizeof(unsigned), hipHostMallocDefault));
+        }
+        NESR_TRY(hipMemset(c->d_status, 0, sizeof(unsigned)));
+        *c->h_status = 0;
+    }
     c->finalized = true;
     return NESR_OK;
 }
@@ -652,8 +786,11 @@ int nesr_unet_workspace_bytes(nesr_unet* c, int n, int h, int w, int tokens, siz
     return NESR_OK;
 }
 
-int nesr_unet_forward_f32(nesr_unet* c, const float* sample, int n, int ch, int h, int w, double timestep, int class_label, const float* text_states, int tokens,
-                          float* out, size_t out_elems, void* stream) {
+}  // extern "C"
+
+// the forward behind nesr_unet_forward_f32's checks, without the fp16 form's bracket (unet_api.h)
+int unet_forward_unchecked(nesr_unet* c, const float* sample, int n, int ch, int h, int w, double timestep, int class_label, const float* text_states, int tokens,
+                           float* out, size_t out_elems, hipStream_t stream) {
     const std::string e = "nesr_unet_forward_f32";
     if (!c || !sample || !text_states || !out) return set_error(NESR_ERR_ARG, e + ": null pointer");
     if (!c->finalized) return set_error(NESR_ERR_STATE, e + ": weights not finalized (nesr_unet_finalize)");
@@ -666,7 +803,35 @@ int nesr_unet_forward_f32(nesr_unet* c, const float* sample, int n, int ch, int 
     const size_t need = (size_t)n * c->cout * h * w;
     if (out_elems != need) return set_error(NESR_ERR_ARG, e + ": out_elems must be n out_channels h w = " + std::to_string(need) + ", got " + std::to_string(out_elems));
     NESR_TRY(hipSetDevice(c->device));
-    return forward(c, sample, n, h, w, timestep, class_label, text_states, tokens, out, static_cast<hipStream_t>(stream));
+    return forward(c, sample, n, h, w, timestep, class_label, text_states, tokens, out, stream);
+}
+
+// The fp16 form's range word: cleared in front of a call's launches, read behind them (the stream is waited for).
+int unet_range_begin(nesr_unet* c, hipStream_t s) {
+    if (!c || c->dtype != NESR_DTYPE_F16 || !c->d_status) return NESR_OK;
+    NESR_TRY(hipSetDevice(c->device));
+    NESR_TRY(hipMemsetAsync(c->d_status, 0, sizeof(unsigned), s));
+    return NESR_OK;
+}
+
+int unet_range_end(nesr_unet* c, hipStream_t s, const char* entry) {
+    if (!c || c->dtype != NESR_DTYPE_F16 || !c->d_status) return NESR_OK;
+    NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    NESR_TRY(hipStreamSynchronize(s));
+    if (*c->h_status)
+        return set_error(NESR_ERR_RANGE, std::string(entry) + ": an activation of the UNet's fp16 form was non-finite or exceeded 65504 in magnitude when it was "
+                                                              "rounded to f16; the result is not valid (NESR_DTYPE_F32 carries such values)");
+    return NESR_OK;
+}
+
+extern "C" {
+
+int nesr_unet_forward_f32(nesr_unet* c, const float* sample, int n, int ch, int h, int w, double timestep, int class_label, const float* text_states, int tokens,
+                          float* out, size_t out_elems, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = unet_range_begin(c, s);
+    if (!rc) rc = unet_forward_unchecked(c, sample, n, ch, h, w, timestep, class_label, text_states, tokens, out, out_elems, s);
+    return rc ? rc : unet_range_end(c, s, "nesr_unet_forward_f32");
 }
 
 int nesr_unet_set_timing(nesr_unet* c, int enable) {

@@ -145,4 +145,46 @@ hipError_t launch_unet_attn(const UnetAttn& a, hipStream_t s);
 hipError_t launch_unet_emb(const UnetEmb& a, hipStream_t s);
 hipError_t launch_unet_temb(const UnetTemb& a, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------------------------- the fp16 compute form
+// unet_f16.hip: the products of launch_unet_conv and launch_unet_rows with both operands rounded to f16 (a plain cast: nearest even),
+// f32 products and sums on v_mfma_f32_16x16x32_f16 (a K tail of 16 on v_mfma_f32_16x16x16_f16).  Storage, prologues, biases, residuals
+// and GEGLU are the f32 form's.  The launchers take the f32 structs, whose `w` is ignored, with the weight as a second, f16 copy:
+//
+//   rows   W16[ldw][K],            K = cs0 + cs1, k contiguous: element (k, n) of Wt[K][ldw] lies at n K + k
+//   conv   W16[coutp][9][cs0 + cs1]: per output channel and tap source 0's cs0 channels, then source 1's cs1; each source's K is its
+//          row width cs (the width rounded up to 16, zeros past the real width), not the f32 form's width rounded up to 4
+//
+// so a B fragment of 8 k is one 16-byte load.  The activation is rounded after the prologue, at the store into LDS; a value that is
+// non-finite or beyond +-65504 there raises `status` (elem16.h; null: unchecked).  An f16 subnormal operand is kept, not flushed.
+//
+// An output element's K chain runs in one workgroup in ascending k (per source: steps of 32, then the tail of 16), whatever the
+// column block, so its bits do not depend on the block the launcher picks, on m or on n.  The launcher picks the widest of 128, 64
+// and 32 output columns (conv: channels) a workgroup whose grid still has UNET_F16_FILL workgroups, else 32.
+struct UnetRows16 : UnetRows {
+    const _Float16* w16;
+    unsigned* status;
+};
+struct UnetConv16 : UnetConv {
+    const _Float16* w16;
+    unsigned* status;
+};
+constexpr int UNET_F16_FILL = 256;      // one workgroup a CU of the MI355X
+int unet_rows_f16_block(int m, int np);                              // the output columns of a workgroup: 128, 64 or 32
+int unet_conv_f16_block(int n, int H, int W, int coutp);             // the output channels of a workgroup: 128, 64 or 32
+size_t unet_rows_f16_lds_bytes();
+size_t unet_conv_f16_lds_bytes(int stride);
+hipError_t launch_unet_rows_f16(const UnetRows16& a, hipStream_t s);
+hipError_t launch_unet_conv_f16(const UnetConv16& a, hipStream_t s);
+
 }  // namespace nesr
+
+// The forward of a finalized context on the caller's stream, as nesr_unet_forward_f32 makes it after its checks, without the fp16
+// form's bracket: the range word is neither cleared in front nor read behind, and nothing waits.  The x4 pipeline (sdx4_api.cpp)
+// calls it once a step between one unet_range_begin and one unet_range_end, so its call has no synchronisation inside.
+// unet_range_begin clears the word (fp16 form; f32: nothing); unet_range_end waits for the stream and returns NESR_ERR_RANGE if it
+// was raised (fp16 form; f32: nothing, no wait).
+struct nesr_unet;
+int unet_forward_unchecked(nesr_unet* c, const float* sample, int n, int ch, int h, int w, double timestep, int class_label, const float* text_states, int tokens,
+                           float* out, size_t out_elems, hipStream_t s);
+int unet_range_begin(nesr_unet* c, hipStream_t s);
+int unet_range_end(nesr_unet* c, hipStream_t s, const char* entry);

@@ -109,9 +109,11 @@ class StableDiffusionX4Upscaler:
         self._pipes = {}          # device index -> (handle, the three contexts it was made of)
 
     @classmethod
-    def from_pretrained(cls, path, **kw):
+    def from_pretrained(cls, path, unet_compute_dtype="f32", **kw):
         """The pipeline of a local directory in diffusers' layout: text_encoder/, unet/, vae/, scheduler/scheduler_config.json,
-        low_res_scheduler/scheduler_config.json and, if transformers can read it, tokenizer/.  A hub id raises: nothing is fetched."""
+        low_res_scheduler/scheduler_config.json and, if transformers can read it, tokenizer/.  A hub id raises: nothing is fetched.
+        unet_compute_dtype "fp16" loads the UNet in its fp16 compute form (UNet2DCondition(compute_dtype=)); the pipeline takes a
+        UNet of either form, and with an fp16 one `upscale` waits once behind its last launch and may raise NesrRangeError."""
         path = os.fspath(path)
         if not os.path.isdir(path):
             raise FileNotFoundError(f"StableDiffusionX4Upscaler.from_pretrained: {path!r} is not a local directory (a hub id is not fetched: "
@@ -133,7 +135,7 @@ class StableDiffusionX4Upscaler:
             tokenizer = CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer"), local_files_only=True)
         except Exception:
             tokenizer = None      # upscale(prompt_ids=...) still works; a string prompt will say so
-        return cls(ClipTextEncoder.from_checkpoint(os.path.join(path, "text_encoder")), UNet2DCondition.from_checkpoint(os.path.join(path, "unet")),
+        return cls(ClipTextEncoder.from_checkpoint(os.path.join(path, "text_encoder")), UNet2DCondition.from_checkpoint(os.path.join(path, "unet"), compute_dtype=unet_compute_dtype),
                    VaeDecoder.from_checkpoint(os.path.join(path, "vae")), scheduler=scheduler, low_res_scheduler=low_res, tokenizer=tokenizer, **kw)
 
     def to(self, device):

@@ -11,6 +11,11 @@ Supported: the configuration family of the published model.  2 to 4 levels of Do
 mirrors, the mid block UNetMidBlock2DCrossAttn, layers_per_block 1 to 3, widths up to 1024, head widths 8 to 128 in steps of 8
 (``attention_head_dim`` is the NUMBER of heads in this family), cross_attention_dim up to 1024, use_linear_projection.  Anything
 else raises NesrUnsupportedError when the context is created, and the message names the field.
+
+``compute_dtype="fp16"`` selects the fp16 compute form: storage stays float32 in and out, both operands of
+every 3x3 conv and row product are rounded to f16 and multiplied on the f16 matrix cores with f32 sums, and the device holds the f16
+copy of those weights instead of their f32 form.  A weight of those products beyond +-65504 raises NesrRangeError when the context
+is made, an activation beyond it raises NesrRangeError from ``forward``, which is synchronous in this form.
 """
 from __future__ import annotations
 
@@ -34,6 +39,7 @@ DEFAULTS = dict(in_channels=7, out_channels=4, block_out_channels=(256, 512, 512
                 norm_eps=1e-5, flip_sin_to_cos=True, freq_shift=0, downsample_padding=1, act_fn="silu", transformer_layers_per_block=1,
                 dual_cross_attention=False)
 KERNEL_GROUPS = ("conv", "norm", "attention", "projection", "feedforward", "embedding", "resample")      # NESR_UNET_GROUP_*
+COMPUTE_DTYPES = {"f32": _lib.DTYPE_F32, "fp16": _lib.DTYPE_F16}
 _TUPLES = ("block_out_channels", "down_block_types", "up_block_types", "only_cross_attention")
 
 
@@ -159,11 +165,14 @@ class UNet2DCondition(_HFNet):
     _spec = staticmethod(unet_state_dict_spec)
     CHECKPOINT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")
 
-    def __init__(self, **cfg):
+    def __init__(self, compute_dtype="f32", **cfg):
+        if compute_dtype not in COMPUTE_DTYPES:
+            raise ValueError(f"UNet2DCondition: compute_dtype {compute_dtype!r}: expected 'f32' or 'fp16'")
         super().__init__(_config(cfg))
+        self.compute_dtype = compute_dtype
 
     @classmethod
-    def from_checkpoint(cls, path, **cfg):
+    def from_checkpoint(cls, path, compute_dtype="f32", **cfg):
         """A UNet with the weights of a local ``diffusion_pytorch_model.safetensors`` / ``.bin`` (or of the ``unet/`` directory
         that holds one).  A ``config.json`` beside the weights supplies the configuration's fields; arguments override it.  Nothing
         is ever fetched."""
@@ -174,7 +183,7 @@ class UNet2DCondition(_HFNet):
             with open(config) as f:
                 found = json.load(f)
             cfg = dict({k: found[k] for k in DEFAULTS if k in found and found[k] is not None}, **cfg)
-        return super().from_checkpoint(path, **cfg)
+        return super().from_checkpoint(path, compute_dtype=compute_dtype, **cfg)
 
     def _create(self, index):
         """A context of this configuration without weights (NesrUnsupportedError names the field the kernels do not take)."""
@@ -195,7 +204,20 @@ class UNet2DCondition(_HFNet):
             msg = lib.nesr_last_error()
             raise _lib.NesrUnsupportedError(f"nesr_unet_create failed ({rc}): {msg.decode() if msg else '?'}")
         _lib.check(rc, "nesr_unet_create")
+        try:
+            _lib.check(lib.nesr_unet_set_dtype(handle, COMPUTE_DTYPES[getattr(self, "compute_dtype", "f32")]), "nesr_unet_set_dtype")
+        except Exception:
+            lib.nesr_unet_destroy(handle)
+            raise
         return handle
+
+    def weight_bytes(self, device=None):
+        """Bytes of weights the context of `device` holds on it: in the fp16 form the f16 copy of the GEMM weights and the f32 rest."""
+        device = torch.device("cuda" if device is None else device)
+        size = ctypes.c_size_t(0)
+        with torch.cuda.device(device):
+            _invoke("nesr_unet_weight_bytes", None, self._context(device), (ctypes.byref(size),))
+        return size.value
 
     # ------------------------------------------------------------------ forward
     def workspace_bytes(self, n, h, w, tokens, device=None):

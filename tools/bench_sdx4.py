@@ -2,7 +2,10 @@
 (the restatements of tests/unet_ref.py, tests/vae_ref.py and tests/sdx4_ref.py run by torch-ROCm; the text states are shared),
 alternating call by call in one process.  Writes profiles/sdx4/bench_sdx4.json.
 
-    python tools/bench_sdx4.py [--frames 64x64,128x128,256x256] [--steps 20] [--reps 5] [--warmup 1] [--out F]
+    python tools/bench_sdx4.py [--frames 64x64,128x128,256x256] [--steps 20] [--reps 5] [--warmup 1] [--unet-compute-dtype f32|fp16] [--out F]
+
+--unet-compute-dtype fp16 runs the native route with the UNet in its fp16 compute form (the eager route stays float32) and writes
+profiles/sdx4/bench_sdx4_unet_fp16.json.
 
 Configuration: the published widths as recalled (text encoder 1024 x 23 layers, UNet (256, 512, 512, 1024), VAE (128, 256, 512)),
 random weights (seeded as in the tests; no checkpoint is fetched), guidance 7.5 (n = 2), 77 ids a prompt, noise level 20.  Per size:
@@ -42,8 +45,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sdx4", "bench_sdx4.json"))
+    ap.add_argument("--unet-compute-dtype", choices=("f32", "fp16"), default="f32")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sdx4", "bench_sdx4.json" if args.unet_compute_dtype == "f32" else "bench_sdx4_unet_fp16.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_sdx4.py needs the GPU (ROCm device); there is no CPU measurement")
@@ -58,7 +64,7 @@ def main():
     sds = {"text": TR.seeded_state_dict(1), "unet": UR.seeded_state_dict(seed=7), "vae": VR.seeded_state_dict(5)}
     nets = []
     for cls, key in ((ClipTextEncoder, "text"), (UNet2DCondition, "unet"), (VaeDecoder, "vae")):
-        net = cls().to(dev)
+        net = (cls(compute_dtype=args.unet_compute_dtype) if key == "unet" else cls()).to(dev)
         net.load_state_dict(sds[key])
         nets.append(net)
     pipe = StableDiffusionX4Upscaler(*nets)
@@ -119,7 +125,7 @@ def main():
         torch.cuda.empty_cache()
         print(json.dumps(row), flush=True)
         rows.append(row)
-    out = {"device": torch.cuda.get_device_name(0),
+    out = {"device": torch.cuda.get_device_name(0), "unet_compute_dtype": args.unet_compute_dtype,
            "config": "published widths as recalled: text 1024 x 23 layers x 16 heads, UNet (256, 512, 512, 1024), VAE (128, 256, 512); random weights; n = 2, 77 ids",
            "comparison": f"the restatements of tests/ in torch {torch.__version__} eager f32 on the same device (text states shared)", "reps": args.reps, "warmup": args.warmup,
            "note": "unet_x40 counts the two samples of a step as two; it is 20 forwards of n = 2.  Random weights: the frames are noise, the u8 differences say the two routes agree.",
