@@ -1,17 +1,20 @@
-"""``_HFNet``: what ``SegFormer``, ``Swin2SR``, ``VaeDecoder`` and ``UNet2DCondition`` share, the models that take a ``transformers`` or ``diffusers``
-checkpoint and run as a chain of launches behind their own entries of the C ABI (``nesr_segformer_*``, ``nesr_swin2sr_*``, ``nesr_vae_*``, ``nesr_unet_*``; their C side shares csrc/state_dict.h
-and the GroupTimer of csrc/api_common.h in the same way).
+"""``_HFNet``: what ``SegFormer``, ``Swin2SR``, ``VaeDecoder``, ``UNet2DCondition`` and ``ClipTextEncoder`` share, the models that
+take a ``transformers`` or ``diffusers`` checkpoint and run as a chain of launches behind their own entries of the C ABI
+(``nesr_segformer_*``, ``nesr_swin2sr_*``, ``nesr_vae_*``, ``nesr_unet_*``, ``nesr_clip_text_*``; their C side shares
+csrc/net_context.h in the same way).
 
 The base owns the parameter tree built from the subclass's spec, the checkpoint reader, one context per device with the current
-weights (strictly loaded: the library refuses a key or a shape it does not expect), the argument checks of the forwards and the
-per-group kernel timing.  A subclass declares ``PREFIX`` (its entries' prefix), ``NAME`` (in messages), ``KERNEL_GROUPS``,
-``TRAIN_ERROR`` and ``_spec`` (its state-dict spec function) and gives ``_create(index)``; it may override ``_register_leaf``
-(how a leaf of the spec becomes a Parameter or a buffer) and ``_skip_upload`` (keys of the state dict the library does not take).
-Calls go through ``_contexts._invoke``: tensors as pointers, torch's current stream appended.
+weights (strictly loaded: the library refuses a key or a shape it does not expect), the argument checks of the forwards, the size
+queries and the per-group kernel timing.  A subclass declares ``PREFIX`` (its entries' prefix), ``NAME`` (in messages),
+``KERNEL_GROUPS``, ``TRAIN_ERROR`` and ``_spec`` (its state-dict spec function) and gives ``_create(index)``, usually through
+``_create_handle``; it may declare ``DEFAULTS`` (then ``from_checkpoint`` reads a ``config.json`` beside the weights) and override
+``_register_leaf`` (how a leaf of the spec becomes a Parameter or a buffer) and ``_skip_upload`` (keys of the state dict the
+library does not take).  Calls go through ``_contexts._invoke``: tensors as pointers, torch's current stream appended.
 """
 from __future__ import annotations
 
 import ctypes
+import json
 import os
 from collections import OrderedDict
 
@@ -33,8 +36,17 @@ class _Holder(nn.Module):
         raise RuntimeError(f"{self._owner}'s sub-modules hold weights only; {self._owner}.forward runs in libnesr_hip.so")
 
 
+def _merged_config(name, defaults, cfg):
+    """`defaults` overridden by `cfg`; a field that is not one of the defaults' is a TypeError.  The model's own normalisation follows."""
+    unknown = sorted(set(cfg) - set(defaults))
+    if unknown:
+        raise TypeError(f"{name}: unknown configuration field(s) {unknown}; expected some of {sorted(defaults)}")
+    return dict(defaults, **cfg)
+
+
 class _HFNet(nn.Module):
     PREFIX = NAME = TRAIN_ERROR = _spec = None
+    DEFAULTS = None           # the configuration's fields with their defaults, where a config.json beside the weights supplies them
     KERNEL_GROUPS = ()
     CHECKPOINT_FILES = ("model.safetensors", "pytorch_model.bin")      # what from_checkpoint looks for in a directory
 
@@ -66,6 +78,18 @@ class _HFNet(nn.Module):
         """A context of this configuration on device `index`, without weights."""
         raise NotImplementedError
 
+    @staticmethod
+    def _create_handle(entry, *args):
+        """The handle `entry`(&handle, *args) makes; NesrUnsupportedError names the field the kernels do not take."""
+        lib = _lib.load()
+        handle = ctypes.c_void_p()
+        rc = getattr(lib, entry)(ctypes.byref(handle), *args)
+        if rc == _lib.ERR_UNSUPPORTED:
+            msg = lib.nesr_last_error()
+            raise _lib.NesrUnsupportedError(f"{entry} failed ({rc}): {msg.decode() if msg else '?'}")
+        _lib.check(rc, entry)
+        return handle
+
     @classmethod
     def _entry(cls, name):
         return f"{cls.PREFIX}_{name}"
@@ -79,9 +103,15 @@ class _HFNet(nn.Module):
     @classmethod
     def from_checkpoint(cls, path, **cfg):
         """A model with the weights of a local ``model.safetensors`` or ``pytorch_model.bin`` (or of the directory that holds
-        one; a subclass names its files in CHECKPOINT_FILES).  Anything that is not an existing local path raises: nothing is ever fetched (the reference's
-        from_pretrained(hub id), nesr/nesr.py:291-296, is a network download)."""
+        one; a subclass names its files in CHECKPOINT_FILES).  Where the subclass declares DEFAULTS, a ``config.json`` beside the
+        weights supplies the configuration's fields; arguments override it.  Anything that is not an existing local path raises:
+        nothing is ever fetched (the reference's from_pretrained(hub id), nesr/nesr.py:291-296, is a network download)."""
         path = os.fspath(path)
+        config = os.path.join(path if os.path.isdir(path) else os.path.dirname(path), "config.json")
+        if cls.DEFAULTS is not None and os.path.isfile(config):
+            with open(config) as f:
+                found = json.load(f)
+            cfg = dict({k: found[k] for k in cls.DEFAULTS if found.get(k) is not None}, **cfg)
         if os.path.isdir(path):
             for name in cls.CHECKPOINT_FILES:
                 if os.path.isfile(os.path.join(path, name)):
@@ -141,6 +171,14 @@ class _HFNet(nn.Module):
             raise
         self._handles[index] = handle
         return handle
+
+    def _query_size(self, entry, device, *args):
+        """The size_t that `entry`(context of `device`, *args, &size) reports: a workspace's or the weights' bytes."""
+        device = torch.device("cuda" if device is None else device)
+        size = ctypes.c_size_t(0)
+        with torch.cuda.device(device):
+            _invoke(entry, None, self._context(device), (*args, ctypes.byref(size)))
+        return size.value
 
     # ------------------------------------------------------------------ the forwards' arguments
     def _require_device(self, t, what):

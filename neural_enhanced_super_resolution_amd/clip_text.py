@@ -18,15 +18,12 @@ created, and the message names the field.
 from __future__ import annotations
 
 import ctypes
-import json
-import os
 from collections import OrderedDict
 
 import torch
 
-from . import _lib
 from ._contexts import _invoke
-from ._hfnet import _HFNet
+from ._hfnet import _HFNet, _merged_config
 
 # the published x4 upscaler's values, recalled from memory: a config.json beside the weights, or the arguments, override them
 DEFAULTS = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=23, num_attention_heads=16,
@@ -37,11 +34,7 @@ POSITION_IDS = "embeddings.position_ids"
 
 
 def _config(cfg):
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown:
-        raise TypeError(f"ClipTextEncoder: unknown configuration field(s) {unknown}; expected some of {sorted(DEFAULTS)}")
-    c = dict(DEFAULTS)
-    c.update(cfg)
+    c = _merged_config("ClipTextEncoder", DEFAULTS, cfg)
     for name in ("vocab_size", "hidden_size", "intermediate_size", "num_hidden_layers", "num_attention_heads", "max_position_embeddings"):
         c[name] = int(c[name])
         if c[name] < 1:
@@ -99,7 +92,7 @@ def launches_per_forward(**cfg):
 class ClipTextEncoder(_HFNet):
     """CLIPTextModel(input_ids)[0] in eval mode on the HIP path.  Keyword arguments are the configuration's fields."""
 
-    PREFIX, NAME, KERNEL_GROUPS = "nesr_clip_text", "ClipTextEncoder", KERNEL_GROUPS
+    PREFIX, NAME, KERNEL_GROUPS, DEFAULTS = "nesr_clip_text", "ClipTextEncoder", KERNEL_GROUPS, DEFAULTS
     TRAIN_ERROR = "ClipTextEncoder is inference only"
     _spec = staticmethod(clip_text_state_dict_spec)
 
@@ -111,42 +104,17 @@ class ClipTextEncoder(_HFNet):
         (text_state_dict), so a published file and a transformers-5 state dict both load."""
         return super().load_state_dict(text_state_dict(state_dict), strict=strict, **kw)
 
-    @classmethod
-    def from_checkpoint(cls, path, **cfg):
-        """An encoder with the weights of a local ``model.safetensors`` / ``pytorch_model.bin`` (or of the ``text_encoder/``
-        directory that holds one).  A ``config.json`` beside the weights supplies the configuration's fields; arguments override
-        it.  Nothing is ever fetched."""
-        path = os.fspath(path)
-        folder = path if os.path.isdir(path) else os.path.dirname(path)
-        config = os.path.join(folder, "config.json")
-        if os.path.isfile(config):
-            with open(config) as f:
-                found = json.load(f)
-            cfg = dict({k: found[k] for k in DEFAULTS if k in found and found[k] is not None}, **cfg)
-        return super().from_checkpoint(path, **cfg)
-
     def _create(self, index):
         """A context of this configuration without weights (NesrUnsupportedError names the field the kernels do not take)."""
-        lib = _lib.load()
         c = self.config
-        handle = ctypes.c_void_p()
-        rc = lib.nesr_clip_text_create(ctypes.byref(handle), index, int(c["vocab_size"]), int(c["hidden_size"]), int(c["intermediate_size"]),
-                                       int(c["num_hidden_layers"]), int(c["num_attention_heads"]), int(c["max_position_embeddings"]),
-                                       float(c["layer_norm_eps"]), str(c["hidden_act"]).encode())
-        if rc == _lib.ERR_UNSUPPORTED:
-            msg = lib.nesr_last_error()
-            raise _lib.NesrUnsupportedError(f"nesr_clip_text_create failed ({rc}): {msg.decode() if msg else '?'}")
-        _lib.check(rc, "nesr_clip_text_create")
-        return handle
+        return self._create_handle("nesr_clip_text_create", index, int(c["vocab_size"]), int(c["hidden_size"]), int(c["intermediate_size"]),
+                                   int(c["num_hidden_layers"]), int(c["num_attention_heads"]), int(c["max_position_embeddings"]),
+                                   float(c["layer_norm_eps"]), str(c["hidden_act"]).encode())
 
     # ------------------------------------------------------------------ forward
     def workspace_bytes(self, n, tokens, device=None):
         """Bytes of workspace an encode of n samples of `tokens` ids allocates on the context of `device`."""
-        device = torch.device("cuda" if device is None else device)
-        size = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_clip_text_workspace_bytes", None, self._context(device), (int(n), int(tokens), ctypes.byref(size)))
-        return size.value
+        return self._query_size("nesr_clip_text_workspace_bytes", device, int(n), int(tokens))
 
     def forward(self, input_ids, device=None):
         """input_ids [n, tokens] integers (a tensor anywhere, an array or nested lists: the entry reads them on the host) ->

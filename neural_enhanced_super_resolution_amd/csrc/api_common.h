@@ -1,8 +1,9 @@
 // Plumbing shared by every file of the C-ABI layer (nesr_api.cpp, rrdb_forward.cpp, band_api.cpp, shard_api.cpp, oneshot_api.cpp,
-// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, segformer_api.cpp, swin2sr_api.cpp, jpeg_api.cpp,
-// jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, a workspace that grows, the upload
+// compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp,
+// unet_api.cpp, clip_text_api.cpp, sdx4_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, a workspace that grows, the upload
 // of a model's packed weights, and the kernel-timing hooks of a context (EventTimer: one bracket per forward; GroupTimer: one per
-// launch, summed per kernel group).  The host side of a strictly loaded state dict is state_dict.h.
+// launch, summed per kernel group).  The host side of a strictly loaded state dict is state_dict.h; what the five networks that
+// load one share around it (segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp, unet_api.cpp, clip_text_api.cpp) is net_context.h.
 // Not part of the public ABI (that is include/nesr_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,7 +146,7 @@ inline int upload_weights(int device, float*& d_w, const std::vector<float>& hos
     return NESR_OK;
 }
 
-// Launch counter and per-group timing of a context whose forward is a chain of launches (nesr_segformer_*, nesr_swin2sr_*): every
+// Launch counter and per-group timing of a context whose forward is a chain of launches (NetContext, net_context.h): every
 // launch goes through run(), which counts it and, while `on`, brackets it with an event pair of its kernel group.
 struct GroupTimer {
     struct Timed {

@@ -6,51 +6,34 @@
 #include <cmath>
 #include <cstring>
 
-#include "api_common.h"
 #include "clip_text_api.h"
-#include "state_dict.h"
+#include "net_context.h"
 
 using namespace nesr;
 
 namespace {
 
-struct CNormW {
-    size_t g = 0, b = 0;
-};
-struct CLinW {
-    size_t w = 0, b = 0;
-    int np = 0;      // output columns
-};
 struct CLayerW {
-    CNormW ln1, ln2;
-    CLinW qkv, out, fc1, fc2;
+    NormW ln1, ln2;
+    LinW qkv, out, fc1, fc2;
 };
 
 const char* const kName = "ClipTextEncoder";
+const char* const kCreate = "nesr_clip_text_create";
 const char* const kPrefix = "text_model.";                       // the published files' key generation
 const char* const kPositionIds = "embeddings.position_ids";      // a buffer of theirs: arange(max_position_embeddings)
 
 }  // namespace
 
-struct nesr_clip_text {
-    int device = 0, vocab = 49408, hidden = 1024, inter = 4096, layers = 23, heads = 16, positions = 77, act = CLIP_ACT_GELU;
+struct nesr_clip_text : NetContext {
+    int vocab = 49408, hidden = 1024, inter = 4096, layers = 23, heads = 16, positions = 77, act = CLIP_ACT_GELU;
     float eps = 1e-5f;
-    StateDict sd;
-    bool finalized = false;
-    float* d_w = nullptr;
     size_t tok = 0, pos = 0;
     std::vector<CLayerW> layer;
-    CNormW fin;
-    char* ws_buf = nullptr;
-    size_t ws_bytes = 0;
-    GroupTimer timer;
+    NormW fin;
 };
 
 namespace {
-
-int unsupported(const std::string& field, const std::string& why) {
-    return set_error(NESR_ERR_UNSUPPORTED, "nesr_clip_text_create: " + field + ": " + why);
-}
 
 // Where an encode's buffers lie in the workspace (bytes from its base), and its size.
 struct Plan {
@@ -91,7 +74,7 @@ int encode(nesr_clip_text* c, const int32_t* ids, int n, int tokens, float* out,
     const float* W = c->d_w;
     const int m = n * tokens, hp = round_up(c->hidden, 16), ip = round_up(c->inter, 16);
 
-    auto rows_args = [&](const CLinW& l, const float* in, int k, float* o) {
+    auto rows_args = [&](const LinW& l, const float* in, int k, float* o) {
         UnetRows a;
         memset(&a, 0, sizeof(a));
         a.m = m, a.rows_per_sample = tokens, a.in[0].p = in, a.in[0].c = k, a.in[0].cs = round_up(k, 16), a.w = W + l.w, a.b = W + l.b, a.ldw = l.np, a.np = l.np, a.out = o;
@@ -104,14 +87,14 @@ int encode(nesr_clip_text* c, const int32_t* ids, int n, int tokens, float* out,
         NESR_RUN(c->timer, kName, NESR_CLIP_TEXT_GROUP_NORM, s, [&] { return launch_unet_ln_stats(st, s); });
         return NESR_OK;
     };
-    auto normed_rows = [&](const CLinW& l, const CNormW& nw, float* o, int group) -> int {      // o = LN(x) w + b
+    auto normed_rows = [&](const LinW& l, const NormW& nw, float* o, int group) -> int {      // o = LN(x) w + b
         if ((rc = stats())) return rc;
         UnetRows a = rows_args(l, x, c->hidden, o);
         a.prologue = UNET_PRO_LAYERNORM, a.ln = ln, a.ln_g = W + nw.g, a.ln_b = W + nw.b;
         NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows(a, s); });
         return NESR_OK;
     };
-    auto residual_rows = [&](const CLinW& l, const float* in, int k, int group) -> int {      // x += in w + b
+    auto residual_rows = [&](const LinW& l, const float* in, int k, int group) -> int {      // x += in w + b
         UnetRows a = rows_args(l, in, k, x);
         a.res = x;
         NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows(a, s); });
@@ -157,22 +140,22 @@ int nesr_clip_text_create(nesr_clip_text** out, int device_id, int vocab_size, i
     *out = nullptr;
     if (!hidden_act) return set_error(NESR_ERR_ARG, "nesr_clip_text_create: null configuration argument");
     const std::string act = hidden_act;
-    if (act != "gelu" && act != "quick_gelu") return unsupported("hidden_act", "'" + act + "' is not supported (gelu, quick_gelu)");
-    if (vocab_size < 1) return unsupported("vocab_size", "must be positive");
-    if (max_position_embeddings < 1) return unsupported("max_position_embeddings", "must be positive");
-    if (num_hidden_layers < 1) return unsupported("num_hidden_layers", "must be positive");
-    if (num_attention_heads < 1) return unsupported("num_attention_heads", "must be positive");
-    if (hidden_size < 1 || hidden_size > CLIP_MAX_HIDDEN) return unsupported("hidden_size", "1 .. 1024, got " + std::to_string(hidden_size));
+    if (act != "gelu" && act != "quick_gelu") return unsupported(kCreate, "hidden_act", "'" + act + "' is not supported (gelu, quick_gelu)");
+    if (vocab_size < 1) return unsupported(kCreate, "vocab_size", "must be positive");
+    if (max_position_embeddings < 1) return unsupported(kCreate, "max_position_embeddings", "must be positive");
+    if (num_hidden_layers < 1) return unsupported(kCreate, "num_hidden_layers", "must be positive");
+    if (num_attention_heads < 1) return unsupported(kCreate, "num_attention_heads", "must be positive");
+    if (hidden_size < 1 || hidden_size > CLIP_MAX_HIDDEN) return unsupported(kCreate, "hidden_size", "1 .. 1024, got " + std::to_string(hidden_size));
     if (hidden_size % num_attention_heads)
-        return unsupported("num_attention_heads", std::to_string(hidden_size) + " (hidden_size) is no multiple of the " + std::to_string(num_attention_heads) + " heads");
+        return unsupported(kCreate, "num_attention_heads", std::to_string(hidden_size) + " (hidden_size) is no multiple of the " + std::to_string(num_attention_heads) + " heads");
     const int d = hidden_size / num_attention_heads;
     if (d < 8 || d > UNET_MAX_HEAD || d % 8)
-        return unsupported("num_attention_heads", "a head width of " + std::to_string(d) + " (hidden_size " + std::to_string(hidden_size) + " / " +
+        return unsupported(kCreate, "num_attention_heads", "a head width of " + std::to_string(d) + " (hidden_size " + std::to_string(hidden_size) + " / " +
                                                       std::to_string(num_attention_heads) + " heads): 8 .. 128 and a multiple of 8");
-    if (intermediate_size < 1 || intermediate_size > CLIP_MAX_INTER) return unsupported("intermediate_size", "1 .. 4096, got " + std::to_string(intermediate_size));
-    if (!(layer_norm_eps > 0) || !std::isfinite(layer_norm_eps)) return unsupported("layer_norm_eps", "must be positive and finite");
+    if (intermediate_size < 1 || intermediate_size > CLIP_MAX_INTER) return unsupported(kCreate, "intermediate_size", "1 .. 4096, got " + std::to_string(intermediate_size));
+    if (!(layer_norm_eps > 0) || !std::isfinite(layer_norm_eps)) return unsupported(kCreate, "layer_norm_eps", "must be positive and finite");
     for (size_t bytes : {unet_rows_lds_bytes(), clip_attn_lds_bytes()})
-        if (bytes > VAE_LDS_LIMIT) return unsupported("hidden_size", "a kernel's LDS of " + std::to_string(bytes) + " bytes exceeds 160 KB");
+        if (bytes > VAE_LDS_LIMIT) return unsupported(kCreate, "hidden_size", "a kernel's LDS of " + std::to_string(bytes) + " bytes exceeds 160 KB");
     if (const int rc = check_device(device_id, NESR_CLIP_TEXT_NO_DEVICE)) return rc;
     nesr_clip_text* c = new nesr_clip_text();
     c->device = device_id, c->vocab = vocab_size, c->hidden = hidden_size, c->inter = intermediate_size, c->layers = num_hidden_layers;
@@ -195,78 +178,36 @@ int nesr_clip_text_create(nesr_clip_text** out, int device_id, int vocab_size, i
     return NESR_OK;
 }
 
-void nesr_clip_text_destroy(nesr_clip_text* c) {
-    if (!c) return;
-    if (c->device != NESR_CLIP_TEXT_NO_DEVICE) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        c->timer.destroy();
-        if (c->ws_buf) (void)hipFree(c->ws_buf);
-        if (c->d_w) (void)hipFree(c->d_w);
-    }
-    delete c;
-}
+void nesr_clip_text_destroy(nesr_clip_text* c) { net_destroy(c); }
 
-int nesr_clip_text_num_tensors(const nesr_clip_text* c) { return c ? (int)c->sd.size() : 0; }
+int nesr_clip_text_num_tensors(const nesr_clip_text* c) { return net_num_tensors(c); }
 
 int nesr_clip_text_load_weight(nesr_clip_text* c, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_clip_text_load_weight: null argument");
-    std::string k = key;
-    if (k.compare(0, strlen(kPrefix), kPrefix) == 0) k = k.substr(strlen(kPrefix));
-    if (k == kPositionIds) return NESR_OK;      // positions count from 0 here; the buffer says nothing else
-    const int rc = c->sd.load(k, data, shape, ndim, key);
-    if (!rc) c->finalized = false;
-    return rc;
+    return net_load_weight(c, "nesr_clip_text_load_weight", key, data, shape, ndim, [](std::string& k) {
+        if (k.compare(0, strlen(kPrefix), kPrefix) == 0) k = k.substr(strlen(kPrefix));
+        return k != kPositionIds;      // positions count from 0 here; the buffer says nothing else
+    });
 }
 
 int nesr_clip_text_finalize(nesr_clip_text* c) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_clip_text_finalize: null context");
+    if (const int rc = net_begin_finalize(c, "nesr_clip_text_finalize")) return rc;
     const StateDict& sd = c->sd;
-    const std::string missing = sd.missing();
-    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
     HostPack pk;
-    const int h = c->hidden, hp = round_up(h, 16);
-    auto norm = [&](const std::string& name) {
-        CNormW n;
-        n.g = pk.vec(sd.data(name + ".weight"), hp), n.b = pk.vec(sd.data(name + ".bias"), hp);
-        return n;
-    };
-    // torch's [n][k] -> Wt[round16(k)][np], bias [np]
-    auto linear = [&](const std::string& name, int n, int k) {
-        CLinW l;
-        l.np = round_up(n, 16);
-        l.w = pk.reserve((size_t)round_up(k, 16) * l.np);
-        pk.transpose_into(l.w, sd.data(name + ".weight"), n, k, l.np, 0);
-        l.b = pk.vec(sd.data(name + ".bias"), l.np);
-        return l;
-    };
+    const int h = c->hidden;
     c->tok = pk.vec(sd.data("embeddings.token_embedding.weight"));
     c->pos = pk.vec(sd.data("embeddings.position_embedding.weight"));
     c->layer.assign(c->layers, CLayerW());
     for (int i = 0; i < c->layers; ++i) {
         const std::string l = "encoder.layers." + std::to_string(i);
         CLayerW& w = c->layer[i];
-        w.ln1 = norm(l + ".layer_norm1"), w.ln2 = norm(l + ".layer_norm2");
-        w.qkv.np = 3 * hp;      // q | k | v side by side: Wt[hp][3 hp]
-        w.qkv.w = pk.reserve((size_t)hp * 3 * hp);
-        w.qkv.b = pk.reserve(3 * hp);
-        int part = 0;
-        for (const char* name : {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj"}) {
-            pk.transpose_into(w.qkv.w, sd.data(l + name + ".weight"), h, h, 3 * hp, part * hp);
-            const std::vector<float>& b = sd.data(l + name + ".bias");
-            std::copy(b.begin(), b.end(), pk.host.begin() + w.qkv.b + (size_t)part * hp);
-            ++part;
-        }
-        w.out = linear(l + ".self_attn.out_proj", h, h);
-        w.fc1 = linear(l + ".mlp.fc1", c->inter, h);
-        w.fc2 = linear(l + ".mlp.fc2", h, c->inter);
+        w.ln1 = pk.norm(sd, l + ".layer_norm1", h), w.ln2 = pk.norm(sd, l + ".layer_norm2", h);
+        w.qkv = pk.side_by_side(sd, l, {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj"}, h, h);      // Wt[hp][3 hp]
+        w.out = pk.linear(sd, l + ".self_attn.out_proj", h, h);
+        w.fc1 = pk.linear(sd, l + ".mlp.fc1", c->inter, h);
+        w.fc2 = pk.linear(sd, l + ".mlp.fc2", h, c->inter);
     }
-    c->fin = norm("final_layer_norm");
-    if (c->device == NESR_CLIP_TEXT_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no encode either
-    const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
-    if (rc) return rc;
-    c->finalized = true;
-    return NESR_OK;
+    c->fin = pk.norm(sd, "final_layer_norm", h);
+    return net_upload(c, "nesr_clip_text_finalize", pk, nullptr, kName);
 }
 
 int nesr_clip_text_workspace_bytes(nesr_clip_text* c, int n, int tokens, size_t* bytes) {
@@ -294,20 +235,10 @@ int nesr_clip_text_encode_f32(nesr_clip_text* c, const int32_t* ids_host, int n,
     return encode(c, ids_host, n, tokens, out_dev, static_cast<hipStream_t>(stream));
 }
 
-int nesr_clip_text_set_timing(nesr_clip_text* c, int enable) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_clip_text_set_timing: null context");
-    c->timer.on = enable != 0;
-    return NESR_OK;
-}
+int nesr_clip_text_set_timing(nesr_clip_text* c, int enable) { return net_set_timing(c, "nesr_clip_text_set_timing", enable); }
 
 int nesr_clip_text_kernel_time_ms(nesr_clip_text* c, double* group_ms, int n_groups, int64_t* launches) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_clip_text_kernel_time_ms: null context");
-    if (c->device == NESR_CLIP_TEXT_NO_DEVICE) return set_error(NESR_ERR_STATE, "nesr_clip_text_kernel_time_ms: a context without a device launches nothing");
-    NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_CLIP_TEXT_GROUPS];
-    const int rc = c->timer.collect(ms, NESR_CLIP_TEXT_GROUPS, launches);
-    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_CLIP_TEXT_GROUPS; ++i) group_ms[i] = ms[i];
-    return rc;
+    return net_kernel_time_ms(c, "nesr_clip_text_kernel_time_ms", NESR_CLIP_TEXT_GROUPS, group_ms, n_groups, launches);
 }
 
 // ---- single-launch test hooks: device pointers in, the launcher's struct filled field for field, one launch, no context

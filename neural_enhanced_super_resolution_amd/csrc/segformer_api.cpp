@@ -7,9 +7,8 @@
 #include <map>
 #include <tuple>
 
-#include "api_common.h"
+#include "net_context.h"
 #include "segformer_api.h"
-#include "state_dict.h"
 
 using namespace nesr;
 
@@ -118,21 +117,15 @@ SegResample resample_args(const uint8_t* src, int h, int w, int c, int vertical,
 
 }  // namespace
 
-struct nesr_segformer {
-    int device = 0, nin = 3, nst = 4, dec = 256, labels = 150, labels_p = 160;
+struct nesr_segformer : NetContext {
+    int nin = 3, nst = 4, dec = 256, labels = 150, labels_p = 160;
     int depth[SEG_MAX_STAGES], sr[SEG_MAX_STAGES], hid[SEG_MAX_STAGES], patch[SEG_MAX_STAGES], stride[SEG_MAX_STAGES], heads[SEG_MAX_STAGES],
         mlp[SEG_MAX_STAGES];
-    StateDict sd;                            // every expected key with its shape
-    bool finalized = false;
-    float* d_w = nullptr;
     std::vector<SegStageW> stages;
     size_t wfuse = 0, bn_scale = 0, bn_shift = 0, wcls = 0, bcls = 0;
-    char* ws = nullptr;                      // the network's buffers
-    size_t ws_bytes = 0;
     char* pre = nullptr;                     // the pre-processing's images
     size_t pre_bytes = 0;
     std::map<std::tuple<int, int, int>, SegTable> tables;
-    GroupTimer timer;
 };
 
 namespace {
@@ -239,9 +232,9 @@ int forward(nesr_segformer* c, const float* x_dev, int H, int W, float* logits, 
     int sh[SEG_MAX_STAGES], sw[SEG_MAX_STAGES];
     stage_dims(c, H, W, sh, sw);
     const SegWs L = ws_layout(c, sh, sw);
-    int rc = grow(c->ws, c->ws_bytes, L.total, kName);
+    int rc = grow(c->ws_buf, c->ws_bytes, L.total, kName);
     if (rc) return rc;
-    auto buf = [&](size_t off) { return reinterpret_cast<float*>(c->ws + off); };
+    auto buf = [&](size_t off) { return reinterpret_cast<float*>(c->ws_buf + off); };
     auto wt = [&](size_t off) { return c->d_w + off; };
     float* X = buf(L.x);
     float* XN = buf(L.xn);
@@ -450,33 +443,27 @@ int nesr_segformer_create(nesr_segformer** out, int device_id, int num_channels,
 }
 
 void nesr_segformer_destroy(nesr_segformer* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    c->timer.destroy();
-    for (auto& kv : c->tables) free_table(kv.second);
-    if (c->ws) (void)hipFree(c->ws);
-    if (c->pre) (void)hipFree(c->pre);
-    if (c->d_w) (void)hipFree(c->d_w);
-    delete c;
+    if (c) {      // the tables and the pre-processing's images, once the device's work is done; the rest is the base's
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        for (auto& kv : c->tables) free_table(kv.second);
+        if (c->pre) (void)hipFree(c->pre);
+    }
+    net_destroy(c);
 }
 
-int nesr_segformer_num_tensors(const nesr_segformer* c) { return c ? (int)c->sd.size() : 0; }
+int nesr_segformer_num_tensors(const nesr_segformer* c) { return net_num_tensors(c); }
 
 int nesr_segformer_load_weight(nesr_segformer* c, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_segformer_load_weight: null argument");
-    const std::string k = seg_new_key(key);
-    if (k == "decode_head.batch_norm.num_batches_tracked") return NESR_OK;
-    const int rc = c->sd.load(k, data, shape, ndim, key);
-    if (!rc) c->finalized = false;
-    return rc;
+    return net_load_weight(c, "nesr_segformer_load_weight", key, data, shape, ndim, [](std::string& k) {
+        k = seg_new_key(k);
+        return k != "decode_head.batch_norm.num_batches_tracked";
+    });
 }
 
 int nesr_segformer_finalize(nesr_segformer* c) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_finalize: null context");
+    if (const int rc = net_begin_finalize(c, "nesr_segformer_finalize")) return rc;
     const StateDict& sd = c->sd;
-    const std::string missing = sd.missing();
-    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
 
     HostPack pk;
     auto vec = [&](const std::string& key) { return pk.vec(sd.data(key)); };
@@ -565,10 +552,7 @@ int nesr_segformer_finalize(nesr_segformer* c) {
     c->wcls = pk.reserve((size_t)D * c->labels_p);
     pk.transpose_into(c->wcls, sd.data("decode_head.classifier.weight"), c->labels, D, c->labels_p, 0);
     c->bcls = pk.vec(sd.data("decode_head.classifier.bias"), c->labels_p);
-    const int rc = upload_weights(c->device, c->d_w, pk.host, nullptr);
-    if (rc) return rc;
-    c->finalized = true;
-    return NESR_OK;
+    return net_upload(c, "nesr_segformer_finalize", pk, nullptr, nullptr);      // no model name in the allocation text
 }
 
 int nesr_segformer_output_size(int num_encoder_blocks, const int* patch_sizes, const int* strides, int H, int W, int* out_h, int* out_w) {
@@ -617,8 +601,8 @@ int nesr_segformer_segment_u8(nesr_segformer* c, const uint8_t* rgb, int H, int 
     // the network's input lives at the head of the network's workspace region of its own: grown here, kept by forward
     static_assert(kModelSize % 32 == 0, "the model size is a legal forward size");
     const SegWs L = ws_layout(c, sh, sw);
-    if ((rc = grow(c->ws, c->ws_bytes, L.total + pix_bytes, kName))) return rc;
-    float* pix = reinterpret_cast<float*>(c->ws + L.total);
+    if ((rc = grow(c->ws_buf, c->ws_bytes, L.total + pix_bytes, kName))) return rc;
+    float* pix = reinterpret_cast<float*>(c->ws_buf + L.total);
     if ((rc = preprocess(c, rgb, H, W, pix, s))) return rc;
     if ((rc = forward(c, pix, kModelSize, kModelSize, nullptr, class_map, s))) return rc;
     if (out_h) *out_h = sh[0];
@@ -626,19 +610,10 @@ int nesr_segformer_segment_u8(nesr_segformer* c, const uint8_t* rgb, int H, int 
     return NESR_OK;
 }
 
-int nesr_segformer_set_timing(nesr_segformer* c, int enable) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_set_timing: null context");
-    c->timer.on = enable != 0;
-    return NESR_OK;
-}
+int nesr_segformer_set_timing(nesr_segformer* c, int enable) { return net_set_timing(c, "nesr_segformer_set_timing", enable); }
 
 int nesr_segformer_kernel_time_ms(nesr_segformer* c, double* group_ms, int n_groups, int64_t* launches) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_segformer_kernel_time_ms: null context");
-    NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_SEG_GROUPS];
-    const int rc = c->timer.collect(ms, NESR_SEG_GROUPS, launches);
-    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_SEG_GROUPS; ++i) group_ms[i] = ms[i];
-    return rc;
+    return net_kernel_time_ms(c, "nesr_segformer_kernel_time_ms", NESR_SEG_GROUPS, group_ms, n_groups, launches);
 }
 
 int nesr_pil_resize_u8(int device_id, const uint8_t* src, int H, int W, int C, uint8_t* dst, int out_h, int out_w, int filter, void* stream) {

@@ -1,11 +1,14 @@
-// The host side of a strictly loaded checkpoint, shared by the models that take a transformers state dict (segformer_api.cpp,
-// swin2sr_api.cpp): StateDict keeps the expected keys with their shapes and the values loaded so far; HostPack is the float vector
-// the weights are repacked into before their one upload.  Host only (no HIP): tools/state_dict_check.cpp builds it alone, with its
-// own set_error.
+// The host side of a strictly loaded checkpoint, shared by the five models that take a transformers or diffusers state dict
+// (segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp, unet_api.cpp, clip_text_api.cpp; net_context.h holds the contexts' common
+// part): StateDict keeps the expected keys with their shapes and the values loaded so far; HostPack is the float vector the weights
+// are repacked into before their one upload, with the packers of a norm and of a padded Linear; HalfPack is the fp16 form's vector
+// of halves beside it.  Host only (no HIP): tools/state_dict_check.cpp builds it alone, with its own set_error.
 #pragma once
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <utility>
@@ -71,6 +74,18 @@ private:
     std::vector<std::string> order_;
 };
 
+// offsets in floats into the packed weights: a norm's gamma and beta over c channels; a product's Wt[kp][np] and bias [np]
+struct NormW {
+    size_t g = 0, b = 0;
+    int c = 0;
+};
+struct LinW {
+    size_t w = 0, b = 0;
+    int kp = 0, np = 0;      // rows and columns of Wt (side_by_side: of all parts; the UNet's GEGLU: np of one half)
+};
+
+inline int round16(int v) { return (v + 15) / 16 * 16; }
+
 // Every function returns or takes an offset in floats into `host`; each piece starts at a multiple of 64 floats and its padding is zero.
 struct HostPack {
     std::vector<float> host;
@@ -99,6 +114,64 @@ struct HostPack {
                 for (int t = 0; t < taps; ++t) host[at + ((size_t)t * cin_padded + ci) * n_padded + o] = w[((size_t)o * cin + ci) * taps + t];
         return at;
     }
+    // name.weight and name.bias of a norm over ch channels, each padded to round16(ch)
+    NormW norm(const StateDict& sd, const std::string& name, int ch) {
+        NormW n;
+        n.c = ch, n.g = vec(sd.data(name + ".weight"), round16(ch)), n.b = vec(sd.data(name + ".bias"), round16(ch));
+        return n;
+    }
+    // torch's Linear / 1x1 conv name.weight [n][k] -> Wt[round16(k)][round16(n)], name.bias padded (zeros without one)
+    LinW linear(const StateDict& sd, const std::string& name, int n, int k, bool bias = true) {
+        LinW l;
+        l.kp = round16(k), l.np = round16(n);
+        l.w = reserve((size_t)l.kp * l.np);
+        transpose_into(l.w, sd.data(name + ".weight"), n, k, l.np, 0);
+        l.b = bias ? vec(sd.data(name + ".bias"), l.np) : reserve(l.np);
+        return l;
+    }
+    // several products [n][k] of one input side by side (q | k | v): Wt[round16(k)][parts round16(n)], part i from column i round16(n)
+    LinW side_by_side(const StateDict& sd, const std::string& prefix, std::initializer_list<const char*> parts, int n, int k, bool bias = true) {
+        LinW l;
+        const int np1 = round16(n);
+        l.kp = round16(k), l.np = (int)parts.size() * np1;
+        l.w = reserve((size_t)l.kp * l.np);
+        l.b = reserve(l.np);
+        int col = 0;
+        for (const char* part : parts) {
+            transpose_into(l.w, sd.data(prefix + part + ".weight"), n, k, l.np, col);
+            if (bias) {
+                const std::vector<float>& b = sd.data(prefix + part + ".bias");
+                std::copy(b.begin(), b.end(), host.begin() + l.b + col);
+            }
+            col += np1;
+        }
+        return l;
+    }
+};
+
+// The fp16 form's copy of the GEMM weights, in halves: offsets count halves of `half`, each piece starts at a multiple of 64 and
+// its padding is zero.  The first key with a value f16 cannot carry (non-finite or beyond +-65504) is kept for finalize's refusal.
+struct HalfPack {
+    std::vector<_Float16> half;
+
+    static bool carries(float v) { return std::fabs(v) <= 65504.0f; }      // false for NaN
+    size_t reserve(size_t halves) {
+        const size_t at = half.size();
+        half.resize((at + halves + 63) / 64 * 64, (_Float16)0.f);
+        return at;
+    }
+    void note(const std::string& key, bool bad) {
+        if (bad && out_of_range_.empty()) out_of_range_ = key;
+    }
+    // `value` of tensor `key`, rounded
+    _Float16 put(const std::string& key, float value) {
+        note(key, !carries(value));
+        return (_Float16)value;
+    }
+    const std::string& out_of_range() const { return out_of_range_; }      // empty: every value so far fits
+
+private:
+    std::string out_of_range_;
 };
 
 }  // namespace nesr

@@ -7,8 +7,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "api_common.h"
-#include "state_dict.h"
+#include "net_context.h"
 #include "swin2sr_api.h"
 
 using namespace nesr;
@@ -36,28 +35,18 @@ constexpr int kMaxStages = 16;
 constexpr int kProcessorPad = 8;   // Swin2SRImageProcessor.size_divisor
 const float kMean[3] = {0.4488f, 0.4371f, 0.4040f};
 const char* const kName = "Swin2SR";      // in the texts of a failed launch, workspace or weight allocation
+const char* const kCreate = "nesr_swin2sr_create";
 
 }  // namespace
 
-struct nesr_swin2sr {
-    int device = 0, nin = 3, nout = 3, C = 180, cs = 192, nst = 0, ws = 8, hidden = 360, hidp = 368, heads = 6, d = 30, dp = 32, scale = 2, up = 0;
+struct nesr_swin2sr : NetContext {      // d_w16: the fp16 form's second copy of every GEMM weight, [n][K]
+    int nin = 3, nout = 3, C = 180, cs = 192, nst = 0, ws = 8, hidden = 360, hidp = 368, heads = 6, d = 30, dp = 32, scale = 2, up = 0;
     int depth[kMaxStages];
     float eps = 1e-5f, range = 1.f, mean[4] = {0.f, 0.f, 0.f, 0.f};
-    StateDict sd;
-    bool finalized = false;
-    int dtype = NESR_DTYPE_F32;      // the compute form (nesr_swin2sr_set_dtype)
-    bool packed = false;             // finalize has run: the form is fixed
-    float* d_w = nullptr;
-    _Float16* d_wh = nullptr;        // the fp16 form's second copy of every GEMM weight, [n][K]
-    unsigned* d_status = nullptr;    // the fp16 form's range word
-    unsigned* h_status = nullptr;
     S2ConvW first, after, before, up1, up2, hr, fin, direct;
     std::vector<S2ConvW> ups;
     size_t wpe = 0, bpe = 0, peg = 0, peb = 0, lng = 0, lnb = 0, wpeh = 0;
     std::vector<S2StageW> stages;
-    char* ws_buf = nullptr;
-    size_t ws_bytes = 0;
-    GroupTimer timer;
 };
 
 namespace {
@@ -65,10 +54,6 @@ namespace {
 bool ends_with(const std::string& s, const char* tail) {
     const size_t n = strlen(tail);
     return s.size() >= n && s.compare(s.size() - n, n, tail) == 0;
-}
-
-int unsupported(const std::string& field, const std::string& why) {
-    return set_error(NESR_ERR_UNSUPPORTED, "nesr_swin2sr_create: " + field + ": " + why);
 }
 
 bool is_pow2(int v) { return v >= 1 && (v & (v - 1)) == 0; }
@@ -88,7 +73,7 @@ S2Conv conv_args(const nesr_swin2sr* c, const S2ConvW& w, const float* in, int H
     for (int i = 0; i < 4; ++i) a.mean[i] = c->mean[i];
     a.w = c->d_w + w.w, a.bias = c->d_w + w.b, a.cout = w.cout, a.coutp = w.coutp;
     a.shuffle = 1, a.out_mode = S2_OUT_ROWS, a.out = out, a.cs_out = cs_out;
-    if (c->dtype == NESR_DTYPE_F16 && w.cin > 4) a.f16 = 1, a.wh = c->d_wh + w.wh, a.status = c->d_status;      // not the frame's conv (K = 4 a tap)
+    if (c->dtype == NESR_DTYPE_F16 && w.cin > 4) a.f16 = 1, a.wh = c->d_w16 + w.wh, a.status = c->d_status;      // not the frame's conv (K = 4 a tap)
     return a;
 }
 
@@ -101,7 +86,7 @@ S2Attn attn_args(const nesr_swin2sr* c, const S2LayerW& L, int j, const float* i
     a.batch = B, a.H = H, a.W = W, a.shift = j % 2 ? c->ws / 2 : 0, a.in = in, a.out = out;
     a.wqkv = w + L.wqkv, a.bqkv = w + L.bqkv, a.scale = w + L.scale, a.bias = w + L.bias, a.wo = w + L.wo, a.bo = w + L.bo;
     a.ln_g = w + L.ln1g, a.ln_b = w + L.ln1b, a.eps = c->eps;
-    if (f16_form(c)) a.f16 = 1, a.wqkvh = c->d_wh + L.wqkvh, a.woh = c->d_wh + L.woh, a.status = c->d_status;
+    if (f16_form(c)) a.f16 = 1, a.wqkvh = c->d_w16 + L.wqkvh, a.woh = c->d_w16 + L.woh, a.status = c->d_status;
     return a;
 }
 
@@ -113,7 +98,7 @@ S2Rows rows_args(const nesr_swin2sr* c, int M, const float* in, size_t w1, size_
     a.m = M, a.c = c->C, a.cs = c->cs, a.in = in;
     if (w1 != (size_t)-1) {
         a.w1 = c->d_w + w1, a.b1 = c->d_w + b1, a.n1p = c->cs;
-        if (f16_form(c)) a.f16 = 1, a.w1h = c->d_wh + w1h, a.status = c->d_status;
+        if (f16_form(c)) a.f16 = 1, a.w1h = c->d_w16 + w1h, a.status = c->d_status;
     }
     if (ln) a.ln_g = c->d_w + g, a.ln_b = c->d_w + b, a.eps = eps;
     a.res = res, a.out = o;
@@ -124,24 +109,14 @@ S2Rows rows_args(const nesr_swin2sr* c, int M, const float* in, size_t w1, size_
 S2Rows mlp_args(const nesr_swin2sr* c, const S2LayerW& L, int M, float* X) {
     S2Rows a = rows_args(c, M, X, L.w1, L.b1, L.w1h, true, L.ln2g, L.ln2b, c->eps, X, X);
     a.n1p = c->hidp, a.gelu = 1, a.w2 = c->d_w + L.w2, a.b2 = c->d_w + L.b2;
-    if (f16_form(c)) a.w2h = c->d_wh + L.w2h;
+    if (f16_form(c)) a.w2h = c->d_w16 + L.w2h;
     return a;
 }
 
-// The fp16 form's range word: cleared in front of a call's launches, read behind them (the stream is waited for).
-int range_begin(nesr_swin2sr* c, hipStream_t s) {
-    if (!f16_form(c)) return NESR_OK;
-    NESR_TRY(hipMemsetAsync(c->d_status, 0, sizeof(unsigned), s));
-    return NESR_OK;
-}
+// the fp16 form's range word, read behind a call's launches (net_range_begin clears it in front of them)
 int range_end(nesr_swin2sr* c, hipStream_t s, const char* entry) {
-    if (!f16_form(c)) return NESR_OK;
-    NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    NESR_TRY(hipStreamSynchronize(s));
-    if (*c->h_status)
-        return set_error(NESR_ERR_RANGE, std::string(entry) + ": an activation of the fp16 form was non-finite or exceeded 65504 in magnitude when it was "
-                                             "rounded; the output is not valid (the f32 form carries such values)");
-    return NESR_OK;
+    return net_range_end(c, s, entry, "an activation of the fp16 form was non-finite or exceeded 65504 in magnitude when it was rounded; the output is not valid "
+                                      "(the f32 form carries such values)");
 }
 
 // The images of one forward: B of them, each fh x fw.  tile = 0: they lie one after the other in `frame` and in `out` (f32), or
@@ -290,7 +265,7 @@ int forward_launches(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, 
 
 // the launches between the range word's reset and its check (fp16 form: the call waits for the stream and may return NESR_ERR_RANGE)
 int forward(nesr_swin2sr* c, const void* frame, bool frame_u8, int fh, int fw, void* out, bool out_u8, hipStream_t s, const S2Batch& bt = S2Batch()) {
-    int rc = range_begin(c, s);
+    int rc = net_range_begin(c, s);
     if (!rc) rc = forward_launches(c, frame, frame_u8, fh, fw, out, out_u8, s, bt);
     return rc ? rc : range_end(c, s, kName);
 }
@@ -344,21 +319,21 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
     for (int i = 0; i < num_stages; ++i)
         if (depths[i] < 1 || depths[i] > 64 || num_heads[i] < 1) return set_error(NESR_ERR_ARG, "nesr_swin2sr_create: depths must be 1 .. 64 and num_heads positive");
     const std::string up = upsampler, resi = resi_connection;
-    if (up == "pixelshuffle_aux") return unsupported("upsampler", "pixelshuffle_aux (and its bicubic branch) is not supported");
+    if (up == "pixelshuffle_aux") return unsupported(kCreate, "upsampler", "pixelshuffle_aux (and its bicubic branch) is not supported");
     if (up != "pixelshuffle" && up != "pixelshuffledirect" && up != "nearest+conv")
-        return unsupported("upsampler", "'" + up + "' is not one of pixelshuffle, pixelshuffledirect, nearest+conv");
-    if (resi != "1conv") return unsupported("resi_connection", "'" + resi + "' is not supported (1conv only)");
-    if (use_absolute_embeddings) return unsupported("use_absolute_embeddings", "absolute position embeddings are not supported");
-    if (patch_size != 1) return unsupported("patch_size", "must be 1");
-    if (!qkv_bias) return unsupported("qkv_bias", "must be true");
-    if (image_size <= window_size) return unsupported("image_size", "must exceed window_size (the window and the shift are the configuration's then)");
+        return unsupported(kCreate, "upsampler", "'" + up + "' is not one of pixelshuffle, pixelshuffledirect, nearest+conv");
+    if (resi != "1conv") return unsupported(kCreate, "resi_connection", "'" + resi + "' is not supported (1conv only)");
+    if (use_absolute_embeddings) return unsupported(kCreate, "use_absolute_embeddings", "absolute position embeddings are not supported");
+    if (patch_size != 1) return unsupported(kCreate, "patch_size", "must be 1");
+    if (!qkv_bias) return unsupported(kCreate, "qkv_bias", "must be true");
+    if (image_size <= window_size) return unsupported(kCreate, "image_size", "must exceed window_size (the window and the shift are the configuration's then)");
     for (int i = 0; i < num_stages; ++i) {
-        if (num_heads[i] != num_heads[0]) return unsupported("num_heads", "every stage must have the same number of heads");
-        if (embed_dim % num_heads[i]) return unsupported("num_heads", "embed_dim is not a multiple of the number of heads");
+        if (num_heads[i] != num_heads[0]) return unsupported(kCreate, "num_heads", "every stage must have the same number of heads");
+        if (embed_dim % num_heads[i]) return unsupported(kCreate, "num_heads", "embed_dim is not a multiple of the number of heads");
     }
-    if (up == "pixelshuffle" && !(upscale == 3 || is_pow2(upscale))) return unsupported("upscale", "pixelshuffle is built for 2^n and 3");
-    if (up == "nearest+conv" && upscale != 4) return unsupported("upscale", "nearest+conv is built for 4 only");
-    if (up == "pixelshuffledirect" && upscale * upscale * num_channels_out > 1024) return unsupported("upscale", "too large");
+    if (up == "pixelshuffle" && !(upscale == 3 || is_pow2(upscale))) return unsupported(kCreate, "upscale", "pixelshuffle is built for 2^n and 3");
+    if (up == "nearest+conv" && upscale != 4) return unsupported(kCreate, "upscale", "nearest+conv is built for 4 only");
+    if (up == "pixelshuffledirect" && upscale * upscale * num_channels_out > 1024) return unsupported(kCreate, "upscale", "too large");
 
     nesr_swin2sr* c = new nesr_swin2sr();
     c->device = device_id, c->nin = num_channels, c->nout = num_channels_out, c->C = embed_dim, c->cs = round_up(embed_dim, 16), c->nst = num_stages;
@@ -379,7 +354,7 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
         v.cinp = round_up(embed_dim, 4);
         if (c->hidden < 1 || s2_attn_lds_bytes(a) > S2_LDS_LIMIT || s2_rows_lds_bytes(r) > S2_LDS_LIMIT || s2_conv_lds_bytes(v) > S2_LDS_LIMIT) {
             delete c;
-            return unsupported("window_size / embed_dim / mlp_ratio", "a window's tokens, a head's q, k, v and its scores (or 32 rows of the MLP) do not fit the 160 KiB of LDS");
+            return unsupported(kCreate, "window_size / embed_dim / mlp_ratio", "a window's tokens, a head's q, k, v and its scores (or 32 rows of the MLP) do not fit the 160 KiB of LDS");
         }
     }
     if (const int rc = check_device(device_id, NESR_SWIN2SR_NO_DEVICE)) {
@@ -431,20 +406,7 @@ int nesr_swin2sr_create(nesr_swin2sr** out, int device_id, int image_size, int p
     return NESR_OK;
 }
 
-void nesr_swin2sr_destroy(nesr_swin2sr* c) {
-    if (!c) return;
-    if (c->device != NESR_SWIN2SR_NO_DEVICE) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        c->timer.destroy();
-        if (c->ws_buf) (void)hipFree(c->ws_buf);
-        if (c->d_w) (void)hipFree(c->d_w);
-        if (c->d_wh) (void)hipFree(c->d_wh);
-        if (c->d_status) (void)hipFree(c->d_status);
-        if (c->h_status) (void)hipHostFree(c->h_status);
-    }
-    delete c;
-}
+void nesr_swin2sr_destroy(nesr_swin2sr* c) { net_destroy(c); }
 
 int nesr_swin2sr_set_dtype(nesr_swin2sr* c, int dtype) {
     if (dtype == NESR_DTYPE_BF16)
@@ -458,53 +420,37 @@ int nesr_swin2sr_set_dtype(nesr_swin2sr* c, int dtype) {
     return NESR_OK;
 }
 
-int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return c ? (int)c->sd.size() : 0; }
+int nesr_swin2sr_num_tensors(const nesr_swin2sr* c) { return net_num_tensors(c); }
 
 int nesr_swin2sr_load_weight(nesr_swin2sr* c, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_swin2sr_load_weight: null argument");
-    const std::string k = key;
     // buffers older checkpoints carry: recomputed here from the configuration
-    if (ends_with(k, "relative_position_index") || ends_with(k, "relative_coords_table") || ends_with(k, "attn_mask")) return NESR_OK;
-    const int rc = c->sd.load(k, data, shape, ndim);
-    if (!rc) c->finalized = false;
-    return rc;
+    return net_load_weight(c, "nesr_swin2sr_load_weight", key, data, shape, ndim, [](std::string& k) {
+        return !(ends_with(k, "relative_position_index") || ends_with(k, "relative_coords_table") || ends_with(k, "attn_mask"));
+    });
 }
 
 int nesr_swin2sr_finalize(nesr_swin2sr* c) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_finalize: null context");
+    if (const int rc = net_begin_finalize(c, "nesr_swin2sr_finalize")) return rc;
     const StateDict& sd = c->sd;
-    const std::string missing = sd.missing();
-    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
 
     HostPack pk;
     auto vec = [&](const std::string& key, int padded) { return pk.vec(sd.data(key), padded); };
-    // torch's Linear / 1x1 conv weight [n][k] -> Wt[round16(k)][round16(n)]
     // The fp16 form's second copy of a GEMM weight: hh[at + o * kp + kk] = f16(w[o][kk]), rows and columns zero padded; a lane's
     // fragment (8 k of one output) is one 16-byte load.  A value f16 cannot carry is remembered by its key.
     const bool f16 = c->dtype == NESR_DTYPE_F16;
-    std::vector<_Float16> hh;
-    std::string out_of_range;
-    auto reserve_h = [&](size_t halves) {
-        const size_t at = hh.size();
-        hh.resize((at + halves + 63) / 64 * 64, (_Float16)0.f);
-        return at;
-    };
-    auto to_h = [&](const std::string& key, float v) {
-        if (!(std::fabs(v) <= 65504.0f) && out_of_range.empty()) out_of_range = key;
-        return (_Float16)v;
-    };
-    auto linear = [&](const std::string& key, int n, int k, size_t* h) {
-        const int np = round_up(n, 16);
-        const size_t at = pk.reserve((size_t)round_up(k, 16) * np);
-        pk.transpose_into(at, sd.data(key), n, k, np, 0);
+    HalfPack hp;
+    std::vector<_Float16>& hh = hp.half;
+    // a Linear / 1x1 conv `name`: Wt and the bias into pk (their offsets to w and b) and, in the fp16 form, the second copy (to h)
+    auto linear = [&](const std::string& name, int n, int k, size_t& w, size_t& b, size_t& h) {
+        const LinW l = pk.linear(sd, name, n, k);
+        w = l.w, b = l.b;
         if (f16) {
-            const int kp = round_up(k, 16);
-            const std::vector<float>& w = sd.data(key);
-            *h = reserve_h((size_t)np * kp);
+            const std::string key = name + ".weight";
+            const std::vector<float>& v = sd.data(key);
+            h = hp.reserve((size_t)l.np * l.kp);
             for (int o = 0; o < n; ++o)
-                for (int kk = 0; kk < k; ++kk) hh[*h + (size_t)o * kp + kk] = to_h(key, w[(size_t)o * k + kk]);
+                for (int kk = 0; kk < k; ++kk) hh[h + (size_t)o * l.kp + kk] = hp.put(key, v[(size_t)o * k + kk]);
         }
-        return at;
     };
     // conv weight [n][cin][3][3] -> Wt[(tap * cinp + ci)][coutp]
     auto conv = [&](const std::string& name, int n, int cin) {
@@ -516,10 +462,10 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
             const int c16 = round_up(cin, 16);
             const std::string wkey = name + ".weight";
             const std::vector<float>& w = sd.data(wkey);
-            r.wh = reserve_h((size_t)9 * r.coutp * c16);
+            r.wh = hp.reserve((size_t)9 * r.coutp * c16);
             for (int o = 0; o < n; ++o)
                 for (int ci = 0; ci < cin; ++ci)
-                    for (int t = 0; t < 9; ++t) hh[r.wh + ((size_t)t * r.coutp + o) * c16 + ci] = to_h(wkey, w[((size_t)o * cin + ci) * 9 + t]);
+                    for (int t = 0; t < 9; ++t) hh[r.wh + ((size_t)t * r.coutp + o) * c16 + ci] = hp.put(wkey, w[((size_t)o * cin + ci) * 9 + t]);
         }
         return r;
     };
@@ -540,8 +486,7 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
 
     c->first = conv("swin2sr.first_convolution", C, c->nin);
     const std::string pe = "swin2sr.embeddings.patch_embeddings";
-    c->wpe = linear(pe + ".projection.weight", C, C, &c->wpeh);
-    c->bpe = vec(pe + ".projection.bias", CS);
+    linear(pe + ".projection", C, C, c->wpe, c->bpe, c->wpeh);
     c->peg = vec(pe + ".layernorm.weight", CS);
     c->peb = vec(pe + ".layernorm.bias", CS);
     c->stages.assign(c->nst, S2StageW());
@@ -555,7 +500,7 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
             const int nq = heads * 3 * dp;
             L.wqkv = pk.reserve((size_t)CS * nq);
             L.bqkv = pk.reserve(nq);
-            if (f16) L.wqkvh = reserve_h((size_t)nq * CS);
+            if (f16) L.wqkvh = hp.reserve((size_t)nq * CS);
             const char* parts[3] = {".query", ".key", ".value"};
             for (int p = 0; p < 3; ++p) {
                 const std::string wkey = a + parts[p] + ".weight";
@@ -565,7 +510,7 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
                     for (int jd = 0; jd < d; ++jd) {
                         const int row = h * d + jd, col = (h * 3 + p) * dp + jd;
                         for (int k = 0; k < C; ++k) pk.host[L.wqkv + (size_t)k * nq + col] = w[(size_t)row * C + k];
-                        for (int k = 0; f16 && k < C; ++k) hh[L.wqkvh + (size_t)col * CS + k] = to_h(wkey, w[(size_t)row * C + k]);
+                        for (int k = 0; f16 && k < C; ++k) hh[L.wqkvh + (size_t)col * CS + k] = hp.put(wkey, w[(size_t)row * C + k]);
                         if (b) pk.host[L.bqkv + col] = (*b)[row];
                     }
             }
@@ -592,20 +537,16 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
                             pk.host[L.bias + ((size_t)h * n + p) * n + q] = (float)(16.0 / (1.0 + std::exp(-tb[(size_t)idx * heads + h])));
                         }
             }
-            L.wo = linear(l + ".attention.output.dense.weight", C, C, &L.woh);
-            L.bo = vec(l + ".attention.output.dense.bias", CS);
+            linear(l + ".attention.output.dense", C, C, L.wo, L.bo, L.woh);
             L.ln1g = vec(l + ".layernorm_before.weight", CS);
             L.ln1b = vec(l + ".layernorm_before.bias", CS);
-            L.w1 = linear(l + ".intermediate.dense.weight", c->hidden, C, &L.w1h);
-            L.b1 = vec(l + ".intermediate.dense.bias", c->hidp);
-            L.w2 = linear(l + ".output.dense.weight", C, c->hidden, &L.w2h);
-            L.b2 = vec(l + ".output.dense.bias", CS);
+            linear(l + ".intermediate.dense", c->hidden, C, L.w1, L.b1, L.w1h);
+            linear(l + ".output.dense", C, c->hidden, L.w2, L.b2, L.w2h);
             L.ln2g = vec(l + ".layernorm_after.weight", CS);
             L.ln2b = vec(l + ".layernorm_after.bias", CS);
         }
         S.conv = conv(s + ".conv", C, C);
-        S.wproj = linear(s + ".patch_embed.projection.weight", C, C, &S.wprojh);
-        S.bproj = vec(s + ".patch_embed.projection.bias", CS);
+        linear(s + ".patch_embed.projection", C, C, S.wproj, S.bproj, S.wprojh);
     }
     c->lng = vec("swin2sr.layernorm.weight", CS);
     c->lnb = vec("swin2sr.layernorm.bias", CS);
@@ -628,30 +569,7 @@ int nesr_swin2sr_finalize(nesr_swin2sr* c) {
         }
         c->fin = conv("upsample.final_convolution", c->nout, kFeatures);
     }
-    if (!out_of_range.empty())      // before any device call
-        return set_error(NESR_ERR_RANGE, "nesr_swin2sr_finalize: " + out_of_range + " holds a value that is non-finite or beyond +-65504, which the fp16 form "
-                                             "cannot carry (NESR_DTYPE_F32 can)");
-    c->packed = true;
-    if (c->device == NESR_SWIN2SR_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no forward either
-    const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
-    if (rc) return rc;
-    if (f16) {
-        if (c->d_wh) NESR_TRY(hipFree(c->d_wh));
-        c->d_wh = nullptr;
-        if (hipMalloc((void**)&c->d_wh, hh.size() * sizeof(_Float16)) != hipSuccess) {
-            c->d_wh = nullptr;
-            return set_error(NESR_ERR_NOMEM, std::string(kName) + ": allocating the f16 weights failed");
-        }
-        NESR_TRY(hipMemcpy(c->d_wh, hh.data(), hh.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-        if (!c->d_status) {
-            NESR_TRY(hipMalloc((void**)&c->d_status, sizeof(unsigned)));
-            NESR_TRY(hipHostMalloc((void**)&c->h_status, sizeof(unsigned), hipHostMallocDefault));
-        }
-        NESR_TRY(hipMemset(c->d_status, 0, sizeof(unsigned)));
-        *c->h_status = 0;
-    }
-    c->finalized = true;
-    return NESR_OK;
+    return net_upload(c, "nesr_swin2sr_finalize", pk, &hp, kName);
 }
 
 int nesr_swin2sr_output_size(int upscale, int H, int W, int* out_h, int* out_w) {
@@ -733,7 +651,7 @@ int nesr_swin2sr_part_f32(nesr_swin2sr* c, int part, int stage, int layer, const
     const size_t pitch = (size_t)c->cs * 4, dense = (size_t)c->C * 4;
     NESR_TRY(hipMemsetAsync(A, 0, rows * pitch, s));      // the columns past the real width are zero in every buffer
     NESR_TRY(hipMemcpy2DAsync(A, pitch, in, dense, dense, rows, hipMemcpyDeviceToDevice, s));
-    rc = range_begin(c, s);
+    rc = net_range_begin(c, s);
     if (rc) return rc;
     const S2StageW& S = c->stages[stage];
     if (part == NESR_S2_PART_ATTENTION) {
@@ -896,7 +814,7 @@ int nesr_swin2sr_upscale_overlapped_u8(nesr_swin2sr* c, const uint8_t* rgb, int 
     o.Y = reinterpret_cast<const float*>(c->ws_buf + net), o.E = reinterpret_cast<float*>(c->ws_buf + net + yb);
     o.out = out, o.oh = H * c->scale, o.ow = W * c->scale;
     NESR_TRY(hipMemsetAsync(o.E, 0, eb, s));
-    rc = range_begin(c, s);
+    rc = net_range_begin(c, s);
     if (rc) return rc;
     S2Batch bt;
     bt.tiles_x = p.nx, bt.FH = H, bt.FW = W, bt.ov_step = p.step, bt.PH = p.PH, bt.PW = p.PW;
@@ -911,19 +829,10 @@ int nesr_swin2sr_upscale_overlapped_u8(nesr_swin2sr* c, const uint8_t* rgb, int 
     return range_end(c, s, entry);
 }
 
-int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_set_timing: null context");
-    c->timer.on = enable != 0;
-    return NESR_OK;
-}
+int nesr_swin2sr_set_timing(nesr_swin2sr* c, int enable) { return net_set_timing(c, "nesr_swin2sr_set_timing", enable); }
 
 int nesr_swin2sr_kernel_time_ms(nesr_swin2sr* c, double* group_ms, int n_groups, int64_t* launches) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_swin2sr_kernel_time_ms: null context");
-    NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_S2_GROUPS];
-    const int rc = c->timer.collect(ms, NESR_S2_GROUPS, launches);
-    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_S2_GROUPS; ++i) group_ms[i] = ms[i];
-    return rc;
+    return net_kernel_time_ms(c, "nesr_swin2sr_kernel_time_ms", NESR_S2_GROUPS, group_ms, n_groups, launches);
 }
 
 }  // extern "C"

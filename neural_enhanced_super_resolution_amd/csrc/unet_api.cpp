@@ -6,8 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "api_common.h"
-#include "state_dict.h"
+#include "net_context.h"
 #include "unet_api.h"
 
 using namespace nesr;
@@ -19,30 +18,22 @@ struct UConvW {
     size_t w = 0, b = 0;
     int cin0 = 0, cin1 = 0, cout = 0, coutp = 0;      // cin1: the skip's channels of a conv over cat(hidden, skip), or 0
 };
-struct UNormW {
-    size_t g = 0, b = 0;
-    int c = 0;
-};
-struct ULinW {
-    size_t w = 0, b = 0;
-    int np = 0;      // output columns (GEGLU: of one half)
-};
 struct UResW {
-    UNormW n1, n2;
+    NormW n1, n2;
     UConvW c1, c2;
     bool has_sc = false;
-    ULinW sc;
+    LinW sc;
     size_t tw = 0, tb = 0;      // time_emb_proj
     int cin0 = 0, cin1 = 0, cout = 0, index = 0;
 };
 struct UAttnW {
     bool self = false;      // q | k | v in one product of the tokens; otherwise q of the tokens and k | v of the text states
-    ULinW q, kv, out;
+    LinW q, kv, out;
 };
 struct UTfW {
     int dim = 0;
-    UNormW gn, ln1, ln2, ln3;
-    ULinW pin, pout, ff0, ff2;
+    NormW gn, ln1, ln2, ln3;
+    LinW pin, pout, ff0, ff2;
     UAttnW a1, a2;
 };
 struct UBlockW {
@@ -55,40 +46,28 @@ struct UBlockW {
 constexpr int kMaxLevels = 4;
 constexpr float kTfNormEps = 1e-6f, kLnEps = 1e-5f;
 const char* const kName = "UNet2DCondition";
+const char* const kCreate = "nesr_unet_create";
 
 }  // namespace
 
-struct nesr_unet {
-    int device = 0, cin = 7, cout = 4, levels = 4, layers = 2, heads = 8, cross = 1024, classes = 1000, groups = 32;
+struct nesr_unet : NetContext {
+    int cin = 7, cout = 4, levels = 4, layers = 2, heads = 8, cross = 1024, classes = 1000, groups = 32;
     float eps = 1e-5f;
     int width[kMaxLevels];
     bool attn[kMaxLevels], up_attn[kMaxLevels], only_cross[kMaxLevels];
-    StateDict sd;
-    bool finalized = false;
-    float* d_w = nullptr;
-    int dtype = NESR_DTYPE_F32;      // the compute form (nesr_unet_set_dtype)
-    bool packed = false;             // finalize has run: the form is fixed
-    _Float16* d_w16 = nullptr;       // fp16 form: the GEMM weights, which d_w then does not hold
-    unsigned* d_status = nullptr;    // fp16 form: the range word
-    unsigned* h_status = nullptr;
-    size_t weight_bytes = 0;         // what finalize uploaded (or would have)
-    ULinW t1, t2;
+    size_t weight_bytes = 0;         // what finalize uploaded (or would have); fp16 form: d_w does not hold what d_w16 does
+    LinW t1, t2;
     size_t cls = 0;
     UConvW conv_in, conv_out;
-    UNormW norm_out;
+    NormW norm_out;
     std::vector<UBlockW> down, up;
     UBlockW mid;
     std::vector<const UResW*> resnets;      // in the order of their rows of the time-embedding table
-    char* ws_buf = nullptr;
-    size_t ws_bytes = 0;
-    GroupTimer timer;
 };
 
 namespace {
 
 // ---- the fp16 form's weight packing (unet_api.h).  Each returns whether a value was non-finite or beyond +-65504.
-inline bool f16_carries(float v) { return std::fabs(v) <= 65504.0f; }
-
 // rows [r0, r0 + n) of torch's weight [.][k0 + k1] -> rows [col0, col0 + n) of W16[.][K], K = round16(k0) + round16(k1): source
 // 1's k start at round16(k0)
 bool pack_rows_f16(_Float16* dst, const float* w, int r0, int n, int k0, int k1, int col0) {
@@ -97,7 +76,7 @@ bool pack_rows_f16(_Float16* dst, const float* w, int r0, int n, int k0, int k1,
     for (int o = 0; o < n; ++o)
         for (int kk = 0; kk < k; ++kk) {
             const float v = w[(size_t)(r0 + o) * k + kk];
-            bad |= !f16_carries(v);
+            bad |= !HalfPack::carries(v);
             dst[(size_t)(col0 + o) * K + (kk < k0 ? kk : kp0 + kk - k0)] = (_Float16)v;
         }
     return bad;
@@ -111,14 +90,10 @@ bool pack_conv_f16(_Float16* dst, const float* w, int n, int c0, int c1) {
         for (int ci = 0; ci < cin; ++ci)
             for (int t = 0; t < 9; ++t) {
                 const float v = w[((size_t)o * cin + ci) * 9 + t];
-                bad |= !f16_carries(v);
+                bad |= !HalfPack::carries(v);
                 dst[((size_t)o * 9 + t) * ktap + (ci < c0 ? ci : cs0 + ci - c0)] = (_Float16)v;
             }
     return bad;
-}
-
-int unsupported(const std::string& field, const std::string& why) {
-    return set_error(NESR_ERR_UNSUPPORTED, "nesr_unet_create: " + field + ": " + why);
 }
 
 int td_of(const nesr_unet* c) { return 4 * c->width[0]; }
@@ -245,7 +220,7 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         return u;
     };
     // GroupNorm statistics of in0 (| in1) into norm[0] (| norm[1])
-    auto gn = [&](const UNormW& nw, const float* in0, int c0, const float* in1, int c1, float eps) -> int {
+    auto gn = [&](const NormW& nw, const float* in0, int c0, const float* in1, int c1, float eps) -> int {
         UnetGn a;
         memset(&a, 0, sizeof(a));
         a.n = n, a.m = H * Wd, a.in[0] = src(in0, c0, norm[0]), a.in[1] = src(in1, c1, in1 ? norm[1] : nullptr);
@@ -271,7 +246,7 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         else NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_conv(a, s); });
         return NESR_OK;
     };
-    auto rows_args = [&](const ULinW& l, int m, const float* in0, int k0, float* o) {
+    auto rows_args = [&](const LinW& l, int m, const float* in0, int k0, float* o) {
         UnetRows16 a;
         memset(&a, 0, sizeof(a));
         a.m = m, a.rows_per_sample = m / n, a.in[0] = src(in0, k0, nullptr), a.b = W + l.b, a.ldw = l.np, a.np = l.np, a.out = o;
@@ -284,7 +259,7 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         else NESR_RUN(c->timer, kName, group, s, [&] { return launch_unet_rows(a, s); });
         return NESR_OK;
     };
-    auto layer_norm = [&](UnetRows& a, const UNormW& nw, const float* in, int m, int dim) -> int {
+    auto layer_norm = [&](UnetRows& a, const NormW& nw, const float* in, int m, int dim) -> int {
         UnetLnStats st;
         memset(&st, 0, sizeof(st));
         st.in = in, st.m = m, st.c = dim, st.cs = round_up(dim, 16), st.eps = kLnEps, st.out = ln;
@@ -310,7 +285,7 @@ int forward(nesr_unet* c, const float* sample, int n, int h, int w, double times
         a.res = r.has_sc ? t2 : in0;
         return run_conv(a, NESR_UNET_GROUP_CONV);
     };
-    auto attention = [&](const UAttnW& at, const UNormW& lnw, int dim, int m) -> int {      // hb += to_out(attn(LN(hb), context))
+    auto attention = [&](const UAttnW& at, const NormW& lnw, int dim, int m) -> int {      // hb += to_out(attn(LN(hb), context))
         const int dimp = round_up(dim, 16), tok = H * Wd;
         UnetAttn a;
         memset(&a, 0, sizeof(a));
@@ -440,48 +415,48 @@ int nesr_unet_create(nesr_unet** out, int device_id, int in_channels, int out_ch
     if (!block_out_channels || !down_block_types || !up_block_types || !mid_block_type || !only_cross_attention || !act_fn)
         return set_error(NESR_ERR_ARG, "nesr_unet_create: null configuration argument");
     const int L = num_blocks;
-    if (L < 2 || L > kMaxLevels) return unsupported("block_out_channels", "2 .. 4 entries, got " + std::to_string(L));
-    if (layers_per_block < 1 || layers_per_block > 3) return unsupported("layers_per_block", "1 .. 3, got " + std::to_string(layers_per_block));
-    if (norm_num_groups < 1) return unsupported("norm_num_groups", "must be positive");
-    if (attention_head_dim < 1) return unsupported("attention_head_dim", "the number of heads must be positive");
-    if (!use_linear_projection) return unsupported("use_linear_projection", "false (proj_in / proj_out as 1x1 convs around the tokens) is not supported");
-    if (transformer_layers_per_block != 1) return unsupported("transformer_layers_per_block", "one BasicTransformerBlock a Transformer, got " + std::to_string(transformer_layers_per_block));
-    if (dual_cross_attention) return unsupported("dual_cross_attention", "not supported");
-    if (std::string(act_fn) != "silu") return unsupported("act_fn", "'" + std::string(act_fn) + "' is not supported (silu only)");
-    if (!flip_sin_to_cos) return unsupported("flip_sin_to_cos", "false is not supported");
-    if (freq_shift != 0.0) return unsupported("freq_shift", "0 only");
-    if (downsample_padding != 1) return unsupported("downsample_padding", "1 only");
-    if (!(norm_eps > 0) || !std::isfinite(norm_eps)) return unsupported("norm_eps", "must be positive and finite");
-    if (std::string(mid_block_type) != "UNetMidBlock2DCrossAttn") return unsupported("mid_block_type", "'" + std::string(mid_block_type) + "' is not supported (UNetMidBlock2DCrossAttn only)");
-    if (cross_attention_dim < 1 || cross_attention_dim > UNET_MAX_WIDTH) return unsupported("cross_attention_dim", "1 .. 1024, got " + std::to_string(cross_attention_dim));
-    if (in_channels < 1 || in_channels > 16) return unsupported("in_channels", "1 .. 16, got " + std::to_string(in_channels));
-    if (out_channels < 1 || out_channels > 16) return unsupported("out_channels", "1 .. 16, got " + std::to_string(out_channels));
-    if (num_class_embeds < 1) return unsupported("num_class_embeds", "the class embedding (the pipeline's noise level) is required");
+    if (L < 2 || L > kMaxLevels) return unsupported(kCreate, "block_out_channels", "2 .. 4 entries, got " + std::to_string(L));
+    if (layers_per_block < 1 || layers_per_block > 3) return unsupported(kCreate, "layers_per_block", "1 .. 3, got " + std::to_string(layers_per_block));
+    if (norm_num_groups < 1) return unsupported(kCreate, "norm_num_groups", "must be positive");
+    if (attention_head_dim < 1) return unsupported(kCreate, "attention_head_dim", "the number of heads must be positive");
+    if (!use_linear_projection) return unsupported(kCreate, "use_linear_projection", "false (proj_in / proj_out as 1x1 convs around the tokens) is not supported");
+    if (transformer_layers_per_block != 1) return unsupported(kCreate, "transformer_layers_per_block", "one BasicTransformerBlock a Transformer, got " + std::to_string(transformer_layers_per_block));
+    if (dual_cross_attention) return unsupported(kCreate, "dual_cross_attention", "not supported");
+    if (std::string(act_fn) != "silu") return unsupported(kCreate, "act_fn", "'" + std::string(act_fn) + "' is not supported (silu only)");
+    if (!flip_sin_to_cos) return unsupported(kCreate, "flip_sin_to_cos", "false is not supported");
+    if (freq_shift != 0.0) return unsupported(kCreate, "freq_shift", "0 only");
+    if (downsample_padding != 1) return unsupported(kCreate, "downsample_padding", "1 only");
+    if (!(norm_eps > 0) || !std::isfinite(norm_eps)) return unsupported(kCreate, "norm_eps", "must be positive and finite");
+    if (std::string(mid_block_type) != "UNetMidBlock2DCrossAttn") return unsupported(kCreate, "mid_block_type", "'" + std::string(mid_block_type) + "' is not supported (UNetMidBlock2DCrossAttn only)");
+    if (cross_attention_dim < 1 || cross_attention_dim > UNET_MAX_WIDTH) return unsupported(kCreate, "cross_attention_dim", "1 .. 1024, got " + std::to_string(cross_attention_dim));
+    if (in_channels < 1 || in_channels > 16) return unsupported(kCreate, "in_channels", "1 .. 16, got " + std::to_string(in_channels));
+    if (out_channels < 1 || out_channels > 16) return unsupported(kCreate, "out_channels", "1 .. 16, got " + std::to_string(out_channels));
+    if (num_class_embeds < 1) return unsupported(kCreate, "num_class_embeds", "the class embedding (the pipeline's noise level) is required");
     bool attn[kMaxLevels], up_attn[kMaxLevels];
     for (int i = 0; i < L; ++i) {
         if (!down_block_types[i] || !up_block_types[i]) return set_error(NESR_ERR_ARG, "nesr_unet_create: null block type");
         const std::string d = down_block_types[i], u = up_block_types[i];
-        if (d != "DownBlock2D" && d != "CrossAttnDownBlock2D") return unsupported("down_block_types", "'" + d + "' is not supported (DownBlock2D, CrossAttnDownBlock2D)");
-        if (u != "UpBlock2D" && u != "CrossAttnUpBlock2D") return unsupported("up_block_types", "'" + u + "' is not supported (UpBlock2D, CrossAttnUpBlock2D)");
+        if (d != "DownBlock2D" && d != "CrossAttnDownBlock2D") return unsupported(kCreate, "down_block_types", "'" + d + "' is not supported (DownBlock2D, CrossAttnDownBlock2D)");
+        if (u != "UpBlock2D" && u != "CrossAttnUpBlock2D") return unsupported(kCreate, "up_block_types", "'" + u + "' is not supported (UpBlock2D, CrossAttnUpBlock2D)");
         attn[i] = d == "CrossAttnDownBlock2D";
         up_attn[L - 1 - i] = u == "CrossAttnUpBlock2D";      // by level
     }
     for (int i = 0; i < L; ++i) {
         const int wd = block_out_channels[i];
-        if (wd < 1 || wd > UNET_MAX_WIDTH) return unsupported("block_out_channels", "every width must be 1 .. 1024, got " + std::to_string(wd));
-        if (wd % norm_num_groups) return unsupported("block_out_channels", std::to_string(wd) + " is no multiple of norm_num_groups " + std::to_string(norm_num_groups));
-        if (i == 0 && wd % 2) return unsupported("block_out_channels", "the first width (the sinusoid's) must be even, got " + std::to_string(wd));
+        if (wd < 1 || wd > UNET_MAX_WIDTH) return unsupported(kCreate, "block_out_channels", "every width must be 1 .. 1024, got " + std::to_string(wd));
+        if (wd % norm_num_groups) return unsupported(kCreate, "block_out_channels", std::to_string(wd) + " is no multiple of norm_num_groups " + std::to_string(norm_num_groups));
+        if (i == 0 && wd % 2) return unsupported(kCreate, "block_out_channels", "the first width (the sinusoid's) must be even, got " + std::to_string(wd));
         if (attn[i] || up_attn[i] || i == L - 1) {
-            if (wd % attention_head_dim) return unsupported("attention_head_dim", std::to_string(wd) + " is no multiple of the " + std::to_string(attention_head_dim) + " heads");
+            if (wd % attention_head_dim) return unsupported(kCreate, "attention_head_dim", std::to_string(wd) + " is no multiple of the " + std::to_string(attention_head_dim) + " heads");
             const int d = wd / attention_head_dim;
             if (d < 8 || d > UNET_MAX_HEAD || d % 8)
-                return unsupported("attention_head_dim", "a head width of " + std::to_string(d) + " (width " + std::to_string(wd) + " / " + std::to_string(attention_head_dim) +
+                return unsupported(kCreate, "attention_head_dim", "a head width of " + std::to_string(d) + " (width " + std::to_string(wd) + " / " + std::to_string(attention_head_dim) +
                                                              " heads): 8 .. 128 and a multiple of 8");
         }
     }
     // checked here, not only documented: every kernel's LDS fits a CU at any configuration that passed
     for (size_t bytes : {unet_conv_lds_bytes(1), unet_conv_lds_bytes(2), unet_rows_lds_bytes(), unet_attn_lds_bytes(), unet_emb_lds_bytes()})
-        if (bytes > VAE_LDS_LIMIT) return unsupported("block_out_channels", "a kernel's LDS of " + std::to_string(bytes) + " bytes exceeds 160 KB");
+        if (bytes > VAE_LDS_LIMIT) return unsupported(kCreate, "block_out_channels", "a kernel's LDS of " + std::to_string(bytes) + " bytes exceeds 160 KB");
     if (const int rc = check_device(device_id, NESR_UNET_NO_DEVICE)) return rc;
     nesr_unet* c = new nesr_unet();
     c->device = device_id, c->cin = in_channels, c->cout = out_channels, c->levels = L, c->layers = layers_per_block, c->heads = attention_head_dim;
@@ -520,22 +495,9 @@ int nesr_unet_create(nesr_unet** out, int device_id, int in_channels, int out_ch
     return NESR_OK;
 }
 
-void nesr_unet_destroy(nesr_unet* c) {
-    if (!c) return;
-    if (c->device != NESR_UNET_NO_DEVICE) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        c->timer.destroy();
-        if (c->ws_buf) (void)hipFree(c->ws_buf);
-        if (c->d_w) (void)hipFree(c->d_w);
-        if (c->d_w16) (void)hipFree(c->d_w16);
-        if (c->d_status) (void)hipFree(c->d_status);
-        if (c->h_status) (void)hipHostFree(c->h_status);
-    }
-    delete c;
-}
+void nesr_unet_destroy(nesr_unet* c) { net_destroy(c); }
 
-int nesr_unet_num_tensors(const nesr_unet* c) { return c ? (int)c->sd.size() : 0; }
+int nesr_unet_num_tensors(const nesr_unet* c) { return net_num_tensors(c); }
 
 int nesr_unet_set_dtype(nesr_unet* c, int dtype) {
     if (dtype == NESR_DTYPE_BF16)
@@ -578,45 +540,26 @@ int nesr_unet_pack_conv_f16(const float* weight, int n, int c0, int c1, uint16_t
 }
 
 int nesr_unet_load_weight(nesr_unet* c, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_unet_load_weight: null argument");
-    const int rc = c->sd.load(key, data, shape, ndim);
-    if (!rc) c->finalized = false;
-    return rc;
+    return net_load_weight(c, "nesr_unet_load_weight", key, data, shape, ndim, [](std::string&) { return true; });
 }
 
 int nesr_unet_finalize(nesr_unet* c) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_unet_finalize: null context");
+    if (const int rc = net_begin_finalize(c, "nesr_unet_finalize")) return rc;
     const StateDict& sd = c->sd;
-    const std::string missing = sd.missing();
-    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
     HostPack pk;
-    // The fp16 form: a GEMM weight goes into `hh` alone, packed as unet_api.h states for unet_f16.hip, and its offset counts halves;
+    // The fp16 form: a GEMM weight goes into `hp` alone, packed as unet_api.h states for unet_f16.hip, and its offset counts halves;
     // the f32 buffer then holds the biases, the norms, the class table and the M = 1 products' weights (embedding, time_emb_proj).
     const bool f16 = c->dtype == NESR_DTYPE_F16;
-    std::vector<_Float16> hh;
-    std::string out_of_range;
-    auto reserve_h = [&](size_t halves) {
-        const size_t at = hh.size();
-        hh.resize((at + halves + 63) / 64 * 64, (_Float16)0.f);
-        return at;
-    };
-    auto note = [&](const std::string& key, bool bad) {
-        if (bad && out_of_range.empty()) out_of_range = key;
-    };
+    HalfPack hp;
     const int L = c->levels, td = td_of(c), tdp = round_up(td, 16), cross = c->cross;
-    auto norm = [&](const std::string& name, int ch) {
-        UNormW n;
-        n.c = ch, n.g = pk.vec(sd.data(name + ".weight"), round_up(ch, 16)), n.b = pk.vec(sd.data(name + ".bias"), round_up(ch, 16));
-        return n;
-    };
     // conv weight [n][cin0 + cin1][9] -> [(tap (cinp0 + cinp1) + the channel's place)][coutp]: the skip's channels start at cinp0
     auto conv = [&](const std::string& name, int n, int cin0, int cin1) {
         UConvW r;
         r.cin0 = cin0, r.cin1 = cin1, r.cout = n, r.coutp = round_up(n, 16);
         const std::vector<float>& w = sd.data(name + ".weight");
         if (f16) {
-            r.w = reserve_h((size_t)r.coutp * 9 * (round_up(cin0, 16) + (cin1 ? round_up(cin1, 16) : 0)));
-            note(name + ".weight", pack_conv_f16(hh.data() + r.w, w.data(), n, cin0, cin1));
+            r.w = hp.reserve((size_t)r.coutp * 9 * (round_up(cin0, 16) + (cin1 ? round_up(cin1, 16) : 0)));
+            hp.note(name + ".weight", pack_conv_f16(hp.half.data() + r.w, w.data(), n, cin0, cin1));
             r.b = pk.vec(sd.data(name + ".bias"), r.coutp);
             return r;
         }
@@ -629,19 +572,19 @@ int nesr_unet_finalize(nesr_unet* c) {
         return r;
     };
     // rows [r0, r0 + n) of torch's weight [.][k0 + k1] -> columns [col0, col0 + n) of Wt[round16(k0) + round16(k1)][ld]
-    // (fp16 form, a GEMM weight: rows [col0, col0 + n) of W16[ld][K] at `at` of hh)
+    // (fp16 form, a GEMM weight: rows [col0, col0 + n) of W16[ld][K] at `at` of hp)
     auto put = [&](size_t at, const std::string& key, int r0, int n, int k0, int k1, int ld, int col0, bool gemm = true) {
         const std::vector<float>& w = sd.data(key);
-        if (f16 && gemm) return note(key, pack_rows_f16(hh.data() + at, w.data(), r0, n, k0, k1, col0));
+        if (f16 && gemm) return hp.note(key, pack_rows_f16(hp.half.data() + at, w.data(), r0, n, k0, k1, col0));
         const int k = k0 + k1, kp0 = round_up(k0, 16);
         for (int o = 0; o < n; ++o)
             for (int kk = 0; kk < k; ++kk) pk.host[at + (size_t)(kk < k0 ? kk : kp0 + kk - k0) * ld + col0 + o] = w[(size_t)(r0 + o) * k + kk];
     };
-    // a matrix of K rows and ld columns: where its elements go (floats of pk, or halves of hh for a GEMM weight of the fp16 form)
-    auto matrix = [&](size_t K, size_t ld, bool gemm = true) { return f16 && gemm ? reserve_h(K * ld) : pk.reserve(K * ld); };
+    // a matrix of K rows and ld columns: where its elements go (floats of pk, or halves of hp for a GEMM weight of the fp16 form)
+    auto matrix = [&](size_t K, size_t ld, bool gemm = true) { return f16 && gemm ? hp.reserve(K * ld) : pk.reserve(K * ld); };
     // gemm false: an M = 1 product on plain FMAs (the embedding, time_emb_proj), f32 in either form
     auto linear = [&](const std::string& name, int n, int k0, int k1, bool bias, bool gemm = true) {
-        ULinW l;
+        LinW l;
         l.np = round_up(n, 16);
         l.w = matrix(round_up(k0, 16) + (k1 ? round_up(k1, 16) : 0), l.np, gemm);
         put(l.w, name + ".weight", 0, n, k0, k1, l.np, 0, gemm);
@@ -650,7 +593,7 @@ int nesr_unet_finalize(nesr_unet* c) {
     };
     // several products of one input side by side: Wt[round16(k)][parts np], no bias
     auto fused = [&](const std::string& at, std::initializer_list<const char*> parts, int n, int k) {
-        ULinW l;
+        LinW l;
         const int np1 = round_up(n, 16), count = (int)parts.size();
         l.np = count * np1;
         l.w = matrix(round_up(k, 16), l.np);
@@ -664,8 +607,8 @@ int nesr_unet_finalize(nesr_unet* c) {
         UResW w;
         const int cin = cin0 + cin1;
         w.cin0 = cin0, w.cin1 = cin1, w.cout = cout;
-        w.n1 = norm(r + ".norm1", cin), w.c1 = conv(r + ".conv1", cout, cin0, cin1), w.n2 = norm(r + ".norm2", cout), w.c2 = conv(r + ".conv2", cout, cout, 0);
-        const ULinW t = linear(r + ".time_emb_proj", cout, td, 0, true, false);      // Wt[td][coutp]: td = 4 width[0] is a multiple of 8, its K is not tiled
+        w.n1 = pk.norm(sd, r + ".norm1", cin), w.c1 = conv(r + ".conv1", cout, cin0, cin1), w.n2 = pk.norm(sd, r + ".norm2", cout), w.c2 = conv(r + ".conv2", cout, cout, 0);
+        const LinW t = linear(r + ".time_emb_proj", cout, td, 0, true, false);      // Wt[td][coutp]: td = 4 width[0] is a multiple of 8, its K is not tiled
         w.tw = t.w, w.tb = t.b;
         w.has_sc = cin != cout;
         if (w.has_sc) w.sc = linear(r + ".conv_shortcut", cout, cin0, cin1, true);
@@ -675,8 +618,8 @@ int nesr_unet_finalize(nesr_unet* c) {
         UTfW t;
         t.dim = dim;
         const std::string b = a + ".transformer_blocks.0";
-        t.gn = norm(a + ".norm", dim), t.pin = linear(a + ".proj_in", dim, dim, 0, true), t.pout = linear(a + ".proj_out", dim, dim, 0, true);
-        t.ln1 = norm(b + ".norm1", dim), t.ln2 = norm(b + ".norm2", dim), t.ln3 = norm(b + ".norm3", dim);
+        t.gn = pk.norm(sd, a + ".norm", dim), t.pin = linear(a + ".proj_in", dim, dim, 0, true), t.pout = linear(a + ".proj_out", dim, dim, 0, true);
+        t.ln1 = pk.norm(sd, b + ".norm1", dim), t.ln2 = pk.norm(sd, b + ".norm2", dim), t.ln3 = pk.norm(sd, b + ".norm3", dim);
         for (int i = 1; i <= 2; ++i) {
             UAttnW& at = i == 1 ? t.a1 : t.a2;
             const std::string n = b + ".attn" + std::to_string(i);
@@ -741,7 +684,7 @@ int nesr_unet_finalize(nesr_unet* c) {
         b.has_samp = i < L - 1;
         if (b.has_samp) b.samp = conv(u + ".upsamplers.0.conv", c->width[l], c->width[l], 0);
     }
-    c->norm_out = norm("conv_norm_out", c->width[0]);
+    c->norm_out = pk.norm(sd, "conv_norm_out", c->width[0]);
     c->conv_out = conv("conv_out", c->cout, c->width[0], 0);
     // the rows of the time-embedding table: the vectors above no longer move
     auto number = [&](UBlockW& b) {
@@ -751,31 +694,8 @@ int nesr_unet_finalize(nesr_unet* c) {
     number(c->mid);
     for (UBlockW& b : c->up) number(b);
     if ((int)c->resnets.size() > UNET_MAX_RESNETS) return set_error(NESR_ERR_STATE, "nesr_unet_finalize: more ResnetBlocks than the embedding launch takes");
-    if (!out_of_range.empty())      // before any device call
-        return set_error(NESR_ERR_RANGE, "nesr_unet_finalize: " + out_of_range + " holds a value that is non-finite or beyond +-65504, which the fp16 form "
-                                             "cannot carry (NESR_DTYPE_F32 can)");
-    c->packed = true;
-    c->weight_bytes = pk.host.size() * sizeof(float) + hh.size() * sizeof(_Float16);
-    if (c->device == NESR_UNET_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no forward either
-    const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
-    if (rc) return rc;
-    if (f16) {
-        if (c->d_w16) NESR_TRY(hipFree(c->d_w16));
-        c->d_w16 = nullptr;
-        if (hipMalloc((void**)&c->d_w16, hh.size() * sizeof(_Float16)) != hipSuccess) {
-            c->d_w16 = nullptr;
-            return set_error(NESR_ERR_NOMEM, std::string(kName) + ": allocating the f16 weights failed");
-        }
-        NESR_TRY(hipMemcpy(c->d_w16, hh.data(), hh.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-        if (!c->d_status) {
-            NESR_TRY(hipMalloc((void**)&c->d_status, sizeof(unsigned)));
-            NESR_TRY(hipHostMalloc((void**)&c->h_status, sizeof(unsigned), hipHostMallocDefault));
-        }
-        NESR_TRY(hipMemset(c->d_status, 0, sizeof(unsigned)));
-        *c->h_status = 0;
-    }
-    c->finalized = true;
-    return NESR_OK;
+    if (hp.out_of_range().empty()) c->weight_bytes = pk.host.size() * sizeof(float) + hp.half.size() * sizeof(_Float16);      // a refused pack leaves it
+    return net_upload(c, "nesr_unet_finalize", pk, &hp, kName);
 }
 
 int nesr_unet_workspace_bytes(nesr_unet* c, int n, int h, int w, int tokens, size_t* bytes) {
@@ -806,22 +726,12 @@ int unet_forward_unchecked(nesr_unet* c, const float* sample, int n, int ch, int
     return forward(c, sample, n, h, w, timestep, class_label, text_states, tokens, out, stream);
 }
 
-// The fp16 form's range word: cleared in front of a call's launches, read behind them (the stream is waited for).
-int unet_range_begin(nesr_unet* c, hipStream_t s) {
-    if (!c || c->dtype != NESR_DTYPE_F16 || !c->d_status) return NESR_OK;
-    NESR_TRY(hipSetDevice(c->device));
-    NESR_TRY(hipMemsetAsync(c->d_status, 0, sizeof(unsigned), s));
-    return NESR_OK;
-}
+// The fp16 form's range word around a call's launches (unet_api.h; sdx4_api.cpp brackets a whole denoising loop with them).
+int unet_range_begin(nesr_unet* c, hipStream_t s) { return net_range_begin(c, s); }
 
 int unet_range_end(nesr_unet* c, hipStream_t s, const char* entry) {
-    if (!c || c->dtype != NESR_DTYPE_F16 || !c->d_status) return NESR_OK;
-    NESR_TRY(hipMemcpyAsync(c->h_status, c->d_status, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    NESR_TRY(hipStreamSynchronize(s));
-    if (*c->h_status)
-        return set_error(NESR_ERR_RANGE, std::string(entry) + ": an activation of the UNet's fp16 form was non-finite or exceeded 65504 in magnitude when it was "
-                                                              "rounded to f16; the result is not valid (NESR_DTYPE_F32 carries such values)");
-    return NESR_OK;
+    return net_range_end(c, s, entry, "an activation of the UNet's fp16 form was non-finite or exceeded 65504 in magnitude when it was rounded to f16; the result is "
+                                      "not valid (NESR_DTYPE_F32 carries such values)");
 }
 
 extern "C" {
@@ -834,20 +744,10 @@ int nesr_unet_forward_f32(nesr_unet* c, const float* sample, int n, int ch, int 
     return rc ? rc : unet_range_end(c, s, "nesr_unet_forward_f32");
 }
 
-int nesr_unet_set_timing(nesr_unet* c, int enable) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_unet_set_timing: null context");
-    c->timer.on = enable != 0;
-    return NESR_OK;
-}
+int nesr_unet_set_timing(nesr_unet* c, int enable) { return net_set_timing(c, "nesr_unet_set_timing", enable); }
 
 int nesr_unet_kernel_time_ms(nesr_unet* c, double* group_ms, int n_groups, int64_t* launches) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_unet_kernel_time_ms: null context");
-    if (c->device == NESR_UNET_NO_DEVICE) return set_error(NESR_ERR_STATE, "nesr_unet_kernel_time_ms: a context without a device launches nothing");
-    NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_UNET_GROUPS];
-    const int rc = c->timer.collect(ms, NESR_UNET_GROUPS, launches);
-    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_UNET_GROUPS; ++i) group_ms[i] = ms[i];
-    return rc;
+    return net_kernel_time_ms(c, "nesr_unet_kernel_time_ms", NESR_UNET_GROUPS, group_ms, n_groups, launches);
 }
 
 }  // extern "C"

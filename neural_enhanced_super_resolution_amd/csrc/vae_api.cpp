@@ -5,8 +5,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "api_common.h"
-#include "state_dict.h"
+#include "net_context.h"
 #include "vae_api.h"
 
 using namespace nesr;
@@ -18,19 +17,11 @@ struct VConvW {
     size_t w = 0, b = 0;
     int cin = 0, cinp = 0, cout = 0, coutp = 0;
 };
-struct VNormW {
-    size_t g = 0, b = 0;
-    int c = 0;
-};
-struct VLinW {
-    size_t w = 0, b = 0;
-    int kp = 0, np = 0;
-};
 struct VResW {
-    VNormW n1, n2;
+    NormW n1, n2;
     VConvW c1, c2;
     bool has_sc = false;
-    VLinW sc;
+    LinW sc;
 };
 struct VUpW {
     std::vector<VResW> res;
@@ -41,32 +32,23 @@ struct VUpW {
 constexpr int kMaxBlocks = 4, kMaxWidth = 512;
 constexpr float kEps = 1e-6f;
 const char* const kName = "VaeDecoder";
+const char* const kCreate = "nesr_vae_create";
 
 }  // namespace
 
-struct nesr_vae {
-    int device = 0, lat = 4, nout = 3, nb = 3, layers = 2, groups = 32;
+struct nesr_vae : NetContext {
+    int lat = 4, nout = 3, nb = 3, layers = 2, groups = 32;
     int width[kMaxBlocks];
     double scaling = 1.0;
-    StateDict sd;
-    bool finalized = false;
-    float* d_w = nullptr;
-    VLinW pq;
+    LinW pq;
     VConvW conv_in, conv_out;
     VResW mid0, mid1;
-    VNormW attn_norm, norm_out;
-    VLinW qkv, to_out;
+    NormW attn_norm, norm_out;
+    LinW qkv, to_out;
     std::vector<VUpW> ups;
-    char* ws_buf = nullptr;
-    size_t ws_bytes = 0;
-    GroupTimer timer;
 };
 
 namespace {
-
-int unsupported(const std::string& field, const std::string& why) {
-    return set_error(NESR_ERR_UNSUPPORTED, "nesr_vae_create: " + field + ": " + why);
-}
 
 int top(const nesr_vae* c) { return c->width[c->nb - 1]; }
 
@@ -125,7 +107,7 @@ int decode(nesr_vae* c, const float* z, float divisor, int h, int w, void* out, 
     const float* W = c->d_w;
     int H = h, Wd = w;
 
-    auto stats = [&](const VNormW& n, const float* in) -> int {
+    auto stats = [&](const NormW& n, const float* in) -> int {
         VaeStats a;
         memset(&a, 0, sizeof(a));
         a.in = in, a.m = H * Wd, a.c = n.c, a.cs = round_up(n.c, 16), a.groups = c->groups, a.partial = partial;
@@ -142,7 +124,7 @@ int decode(nesr_vae* c, const float* z, float divisor, int h, int w, void* out, 
         a.out_mode = VAE_OUT_ROWS, a.out = o, a.cs_out = cw.coutp;
         return a;
     };
-    auto rows = [&](const VLinW& l, const float* in, bool normed, const float* res, float* o) -> int {
+    auto rows = [&](const LinW& l, const float* in, bool normed, const float* res, float* o) -> int {
         VaeRows a;
         memset(&a, 0, sizeof(a));
         a.m = H * Wd, a.cs_in = l.kp, a.np = l.np, a.in = in, a.norm = normed ? norm : nullptr, a.w = W + l.w, a.b = W + l.b, a.res = res, a.out = o;
@@ -223,18 +205,18 @@ int nesr_vae_create(nesr_vae** out, int device_id, int latent_channels, int out_
     if (!out) return set_error(NESR_ERR_ARG, "nesr_vae_create: null out");
     *out = nullptr;
     if (!block_out_channels || !act_fn) return set_error(NESR_ERR_ARG, "nesr_vae_create: null configuration argument");
-    if (num_blocks < 2 || num_blocks > kMaxBlocks) return unsupported("block_out_channels", "2 .. 4 entries, got " + std::to_string(num_blocks));
-    if (norm_num_groups < 1) return unsupported("norm_num_groups", "must be positive");
+    if (num_blocks < 2 || num_blocks > kMaxBlocks) return unsupported(kCreate, "block_out_channels", "2 .. 4 entries, got " + std::to_string(num_blocks));
+    if (norm_num_groups < 1) return unsupported(kCreate, "norm_num_groups", "must be positive");
     for (int i = 0; i < num_blocks; ++i) {
         const int wd = block_out_channels[i];
-        if (wd < 1 || wd > kMaxWidth) return unsupported("block_out_channels", "every width must be 1 .. 512, got " + std::to_string(wd));
-        if (wd % norm_num_groups) return unsupported("block_out_channels", std::to_string(wd) + " is no multiple of norm_num_groups " + std::to_string(norm_num_groups));
+        if (wd < 1 || wd > kMaxWidth) return unsupported(kCreate, "block_out_channels", "every width must be 1 .. 512, got " + std::to_string(wd));
+        if (wd % norm_num_groups) return unsupported(kCreate, "block_out_channels", std::to_string(wd) + " is no multiple of norm_num_groups " + std::to_string(norm_num_groups));
     }
-    if (layers_per_block < 1 || layers_per_block > 4) return unsupported("layers_per_block", "1 .. 4, got " + std::to_string(layers_per_block));
-    if (latent_channels < 1 || latent_channels > 8) return unsupported("latent_channels", "1 .. 8, got " + std::to_string(latent_channels));
-    if (out_channels < 1 || out_channels > 4) return unsupported("out_channels", "1 .. 4, got " + std::to_string(out_channels));
-    if (std::string(act_fn) != "silu") return unsupported("act_fn", "'" + std::string(act_fn) + "' is not supported (silu only)");
-    if (!(scaling_factor > 0) || !std::isfinite(scaling_factor)) return unsupported("scaling_factor", "must be positive and finite");
+    if (layers_per_block < 1 || layers_per_block > 4) return unsupported(kCreate, "layers_per_block", "1 .. 4, got " + std::to_string(layers_per_block));
+    if (latent_channels < 1 || latent_channels > 8) return unsupported(kCreate, "latent_channels", "1 .. 8, got " + std::to_string(latent_channels));
+    if (out_channels < 1 || out_channels > 4) return unsupported(kCreate, "out_channels", "1 .. 4, got " + std::to_string(out_channels));
+    if (std::string(act_fn) != "silu") return unsupported(kCreate, "act_fn", "'" + std::string(act_fn) + "' is not supported (silu only)");
+    if (!(scaling_factor > 0) || !std::isfinite(scaling_factor)) return unsupported(kCreate, "scaling_factor", "must be positive and finite");
     if (const int rc = check_device(device_id, NESR_VAE_NO_DEVICE)) return rc;
     nesr_vae* c = new nesr_vae();
     c->device = device_id, c->lat = latent_channels, c->nout = out_channels, c->nb = num_blocks, c->layers = layers_per_block;
@@ -263,38 +245,21 @@ int nesr_vae_create(nesr_vae** out, int device_id, int latent_channels, int out_
     return NESR_OK;
 }
 
-void nesr_vae_destroy(nesr_vae* c) {
-    if (!c) return;
-    if (c->device != NESR_VAE_NO_DEVICE) {
-        (void)hipSetDevice(c->device);
-        (void)hipDeviceSynchronize();
-        c->timer.destroy();
-        if (c->ws_buf) (void)hipFree(c->ws_buf);
-        if (c->d_w) (void)hipFree(c->d_w);
-    }
-    delete c;
-}
+void nesr_vae_destroy(nesr_vae* c) { net_destroy(c); }
 
-int nesr_vae_num_tensors(const nesr_vae* c) { return c ? (int)c->sd.size() : 0; }
+int nesr_vae_num_tensors(const nesr_vae* c) { return net_num_tensors(c); }
 
 int nesr_vae_load_weight(nesr_vae* c, const char* key, const float* data, const int64_t* shape, int ndim) {
-    if (!c || !key || (!data && ndim > 0) || ndim < 0 || (ndim > 0 && !shape)) return set_error(NESR_ERR_ARG, "nesr_vae_load_weight: null argument");
-    const int rc = c->sd.load(current_name(key), data, shape, ndim, key);
-    if (!rc) c->finalized = false;
-    return rc;
+    return net_load_weight(c, "nesr_vae_load_weight", key, data, shape, ndim, [](std::string& k) {
+        k = current_name(k);
+        return true;
+    });
 }
 
 int nesr_vae_finalize(nesr_vae* c) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_vae_finalize: null context");
+    if (const int rc = net_begin_finalize(c, "nesr_vae_finalize")) return rc;
     const StateDict& sd = c->sd;
-    const std::string missing = sd.missing();
-    if (!missing.empty()) return set_error(NESR_ERR_STATE, missing);
     HostPack pk;
-    auto norm = [&](const std::string& name, int ch) {
-        VNormW n;
-        n.c = ch, n.g = pk.vec(sd.data(name + ".weight"), round_up(ch, 16)), n.b = pk.vec(sd.data(name + ".bias"), round_up(ch, 16));
-        return n;
-    };
     auto conv = [&](const std::string& name, int n, int cin) {
         VConvW r;
         r.cin = cin, r.cinp = round_up(cin, 4), r.cout = n, r.coutp = round_up(n, 16);
@@ -302,41 +267,21 @@ int nesr_vae_finalize(nesr_vae* c) {
         r.b = pk.vec(sd.data(name + ".bias"), r.coutp);
         return r;
     };
-    // torch's Linear / 1x1 conv weight [n][k] -> Wt[round16(k)][round16(n)]
-    auto linear = [&](const std::string& name, int n, int k) {
-        VLinW l;
-        l.kp = round_up(k, 16), l.np = round_up(n, 16);
-        l.w = pk.reserve((size_t)l.kp * l.np);
-        pk.transpose_into(l.w, sd.data(name + ".weight"), n, k, l.np, 0);
-        l.b = pk.vec(sd.data(name + ".bias"), l.np);
-        return l;
-    };
     auto resnet = [&](const std::string& r, int cin, int cout) {
         VResW w;
-        w.n1 = norm(r + ".norm1", cin), w.c1 = conv(r + ".conv1", cout, cin), w.n2 = norm(r + ".norm2", cout), w.c2 = conv(r + ".conv2", cout, cout);
+        w.n1 = pk.norm(sd, r + ".norm1", cin), w.c1 = conv(r + ".conv1", cout, cin), w.n2 = pk.norm(sd, r + ".norm2", cout), w.c2 = conv(r + ".conv2", cout, cout);
         w.has_sc = cin != cout;
-        if (w.has_sc) w.sc = linear(r + ".conv_shortcut", cout, cin);
+        if (w.has_sc) w.sc = pk.linear(sd, r + ".conv_shortcut", cout, cin);
         return w;
     };
     const int T = top(c);
-    c->pq = linear("post_quant_conv", c->lat, c->lat);
+    c->pq = pk.linear(sd, "post_quant_conv", c->lat, c->lat);
     c->conv_in = conv("decoder.conv_in", T, c->lat);
     c->mid0 = resnet("decoder.mid_block.resnets.0", T, T);
     const std::string at = "decoder.mid_block.attentions.0";
-    c->attn_norm = norm(at + ".group_norm", T);
-    {   // q | k | v side by side: Wt[cs][3 cs]
-        const int cs = round_up(T, 16);
-        c->qkv.kp = cs, c->qkv.np = 3 * cs;
-        c->qkv.w = pk.reserve((size_t)cs * 3 * cs);
-        c->qkv.b = pk.reserve(3 * cs);
-        const char* parts[3] = {".to_q", ".to_k", ".to_v"};
-        for (int p = 0; p < 3; ++p) {
-            pk.transpose_into(c->qkv.w, sd.data(at + parts[p] + ".weight"), T, T, 3 * cs, p * cs);
-            const std::vector<float>& b = sd.data(at + parts[p] + ".bias");
-            std::copy(b.begin(), b.end(), pk.host.begin() + c->qkv.b + (size_t)p * cs);
-        }
-    }
-    c->to_out = linear(at + ".to_out.0", T, T);
+    c->attn_norm = pk.norm(sd, at + ".group_norm", T);
+    c->qkv = pk.side_by_side(sd, at, {".to_q", ".to_k", ".to_v"}, T, T);      // Wt[cs][3 cs]
+    c->to_out = pk.linear(sd, at + ".to_out.0", T, T);
     c->mid1 = resnet("decoder.mid_block.resnets.1", T, T);
     c->ups.assign(c->nb, VUpW());
     int prev = T;
@@ -348,13 +293,9 @@ int nesr_vae_finalize(nesr_vae* c) {
         if (c->ups[i].has_up) c->ups[i].up = conv(u + ".upsamplers.0.conv", wd, wd);
         prev = wd;
     }
-    c->norm_out = norm("decoder.conv_norm_out", prev);
+    c->norm_out = pk.norm(sd, "decoder.conv_norm_out", prev);
     c->conv_out = conv("decoder.conv_out", c->nout, prev);
-    if (c->device == NESR_VAE_NO_DEVICE) return NESR_OK;      // checked and packed; nothing to upload to, and no decode either
-    const int rc = upload_weights(c->device, c->d_w, pk.host, kName);
-    if (rc) return rc;
-    c->finalized = true;
-    return NESR_OK;
+    return net_upload(c, "nesr_vae_finalize", pk, nullptr, kName);
 }
 
 int nesr_vae_output_size(int num_blocks, int h, int w, int* out_h, int* out_w) {
@@ -391,20 +332,10 @@ int nesr_vae_decode_latents_u8(nesr_vae* c, const float* latents, int N, int C, 
     return decode(c, latents, (float)c->scaling, h, w, out, true, static_cast<hipStream_t>(stream));
 }
 
-int nesr_vae_set_timing(nesr_vae* c, int enable) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_vae_set_timing: null context");
-    c->timer.on = enable != 0;
-    return NESR_OK;
-}
+int nesr_vae_set_timing(nesr_vae* c, int enable) { return net_set_timing(c, "nesr_vae_set_timing", enable); }
 
 int nesr_vae_kernel_time_ms(nesr_vae* c, double* group_ms, int n_groups, int64_t* launches) {
-    if (!c) return set_error(NESR_ERR_ARG, "nesr_vae_kernel_time_ms: null context");
-    if (c->device == NESR_VAE_NO_DEVICE) return set_error(NESR_ERR_STATE, "nesr_vae_kernel_time_ms: a context without a device launches nothing");
-    NESR_TRY(hipSetDevice(c->device));
-    double ms[NESR_VAE_GROUPS];
-    const int rc = c->timer.collect(ms, NESR_VAE_GROUPS, launches);
-    for (int i = 0; !rc && group_ms && i < n_groups && i < NESR_VAE_GROUPS; ++i) group_ms[i] = ms[i];
-    return rc;
+    return net_kernel_time_ms(c, "nesr_vae_kernel_time_ms", NESR_VAE_GROUPS, group_ms, n_groups, launches);
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from ._contexts import _invoke, current_stream_ptr, device_call
-from ._hfnet import _HFNet
+from ._hfnet import _HFNet, _merged_config
 
 PIL_LANCZOS, PIL_BILINEAR = 1, 2      # PIL.Image's filter numbers: the `filter` of nesr_pil_resize_u8
 MODEL_SIZE = 512                      # the side of the image the extractor makes of a frame (segment, pixel_values)
@@ -32,11 +32,7 @@ B0 = dict(num_channels=3, num_encoder_blocks=4, depths=(2, 2, 2, 2), sr_ratios=(
 
 
 def _config(cfg):
-    unknown = sorted(set(cfg) - set(B0))
-    if unknown:
-        raise TypeError(f"SegFormer: unknown configuration field(s) {unknown}; expected some of {sorted(B0)}")
-    c = dict(B0)
-    c.update(cfg)
+    c = _merged_config("SegFormer", B0, cfg)
     n = int(c["num_encoder_blocks"])
     for name in ("depths", "sr_ratios", "hidden_sizes", "patch_sizes", "strides", "num_attention_heads", "mlp_ratios"):
         c[name] = tuple(int(v) for v in c[name])
@@ -162,11 +158,9 @@ class SegFormer(_HFNet):
         def arr(name):
             return (ctypes.c_int * n)(*c[name])
 
-        handle = ctypes.c_void_p()
-        _lib.check(_lib.load().nesr_segformer_create(ctypes.byref(handle), index, c["num_channels"], n, arr("depths"), arr("sr_ratios"),
-                                                     arr("hidden_sizes"), arr("patch_sizes"), arr("strides"), arr("num_attention_heads"),
-                                                     arr("mlp_ratios"), c["decoder_hidden_size"], c["num_labels"]), "nesr_segformer_create")
-        return handle
+        return self._create_handle("nesr_segformer_create", index, c["num_channels"], n, arr("depths"), arr("sr_ratios"), arr("hidden_sizes"),
+                                   arr("patch_sizes"), arr("strides"), arr("num_attention_heads"), arr("mlp_ratios"), c["decoder_hidden_size"],
+                                   c["num_labels"])
 
     # ------------------------------------------------------------------ forward
     def output_size(self, h, w):

@@ -35,7 +35,7 @@ import torch
 
 from . import _lib
 from ._contexts import _invoke
-from ._hfnet import _HFNet
+from ._hfnet import _HFNet, _merged_config
 
 DEFAULTS = dict(image_size=64, patch_size=1, num_channels=3, num_channels_out=None, embed_dim=180, depths=(6, 6, 6, 6, 6, 6),
                 num_heads=(6, 6, 6, 6, 6, 6), window_size=8, mlp_ratio=2.0, qkv_bias=True, use_absolute_embeddings=False,
@@ -48,11 +48,7 @@ PARTS = {"attention": 0, "mlp": 1, "stage_conv": 2}      # NESR_S2_PART_*
 
 
 def _config(cfg):
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown:
-        raise TypeError(f"Swin2SR: unknown configuration field(s) {unknown}; expected some of {sorted(DEFAULTS)}")
-    c = dict(DEFAULTS)
-    c.update(cfg)
+    c = _merged_config("Swin2SR", DEFAULTS, cfg)
     c["depths"], c["num_heads"] = tuple(int(v) for v in c["depths"]), tuple(int(v) for v in c["num_heads"])
     if len(c["depths"]) != len(c["num_heads"]) or not c["depths"]:
         raise ValueError(f"Swin2SR: depths and num_heads must have the same, positive number of entries, got {c['depths']} and {c['num_heads']}")
@@ -141,16 +137,12 @@ class Swin2SR(_HFNet):
         lib = _lib.load()
         c = self.config
         n = len(c["depths"])
-        handle = ctypes.c_void_p()
-        rc = lib.nesr_swin2sr_create(ctypes.byref(handle), index, int(c["image_size"]), int(c["patch_size"]), int(c["num_channels"]),
-                                     int(c["num_channels_out"]), int(c["embed_dim"]), n, (ctypes.c_int * n)(*c["depths"]),
-                                     (ctypes.c_int * n)(*c["num_heads"]), int(c["window_size"]), float(c["mlp_ratio"]), int(bool(c["qkv_bias"])),
-                                     int(bool(c["use_absolute_embeddings"])), float(c["layer_norm_eps"]), int(c["upscale"]), float(c["img_range"]),
-                                     str(c["resi_connection"]).encode(), str(c["upsampler"]).encode())
-        if rc == _lib.ERR_UNSUPPORTED:
-            msg = lib.nesr_last_error()
-            raise _lib.NesrUnsupportedError(f"nesr_swin2sr_create failed ({rc}): {msg.decode() if msg else '?'}")
-        _lib.check(rc, "nesr_swin2sr_create")
+        handle = self._create_handle(
+            "nesr_swin2sr_create", index, int(c["image_size"]), int(c["patch_size"]), int(c["num_channels"]),
+            int(c["num_channels_out"]), int(c["embed_dim"]), n, (ctypes.c_int * n)(*c["depths"]),
+            (ctypes.c_int * n)(*c["num_heads"]), int(c["window_size"]), float(c["mlp_ratio"]), int(bool(c["qkv_bias"])),
+            int(bool(c["use_absolute_embeddings"])), float(c["layer_norm_eps"]), int(c["upscale"]), float(c["img_range"]),
+            str(c["resi_connection"]).encode(), str(c["upsampler"]).encode())
         try:
             _lib.check(lib.nesr_swin2sr_set_dtype(handle, COMPUTE_DTYPES[self.compute_dtype]), "nesr_swin2sr_set_dtype")
         except Exception:
@@ -224,11 +216,7 @@ class Swin2SR(_HFNet):
 
     def workspace_bytes(self, win_h, win_w, batch=1, device=None):
         """Bytes of workspace a forward of `batch` frames (or windows) of win_h x win_w allocates on the context of `device`."""
-        device = torch.device("cuda" if device is None else device)
-        n = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_swin2sr_workspace_bytes", None, self._context(device), (int(win_h), int(win_w), int(batch), ctypes.byref(n)))
-        return n.value
+        return self._query_size("nesr_swin2sr_workspace_bytes", device, int(win_h), int(win_w), int(batch))
 
     def overlap_plan(self, h, w, tile, tile_overlap):
         """The plan `upscale(tile=, tile_overlap=)` follows on an h x w frame, as the library computes it (needs no device):
@@ -247,12 +235,7 @@ class Swin2SR(_HFNet):
     def overlap_workspace_bytes(self, h, w, tile, tile_overlap, batch=1, device=None):
         """Bytes `upscale(tile=, tile_overlap=)` allocates on the context of `device` for an h x w frame with `batch` windows a
         launch: the network's workspace of the windows, their float32 outputs, and the accumulator of the padded output."""
-        device = torch.device("cuda" if device is None else device)
-        n = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_swin2sr_overlap_workspace_bytes", None, self._context(device),
-                    (int(h), int(w), int(tile), int(tile_overlap), int(batch), ctypes.byref(n)))
-        return n.value
+        return self._query_size("nesr_swin2sr_overlap_workspace_bytes", device, int(h), int(w), int(tile), int(tile_overlap), int(batch))
 
     def upscale(self, frame, device=None, tile=0, tile_pad=16, max_batch=None, tile_overlap=None):
         """[H, W, 3] uint8 RGB frame -> the uint8 frame [H s, W s, 3] on the device.  `frame` is a tensor on the device, or an

@@ -20,15 +20,13 @@ is made, an activation beyond it raises NesrRangeError from ``forward``, which i
 from __future__ import annotations
 
 import ctypes
-import json
-import os
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
 from ._contexts import _invoke
-from ._hfnet import _HFNet
+from ._hfnet import _HFNet, _merged_config
 
 # the published x4 upscaler's values, recalled from memory: a config.json beside the weights, or the arguments, override them
 DEFAULTS = dict(in_channels=7, out_channels=4, block_out_channels=(256, 512, 512, 1024),
@@ -44,11 +42,7 @@ _TUPLES = ("block_out_channels", "down_block_types", "up_block_types", "only_cro
 
 
 def _config(cfg):
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown:
-        raise TypeError(f"UNet2DCondition: unknown configuration field(s) {unknown}; expected some of {sorted(DEFAULTS)}")
-    c = dict(DEFAULTS)
-    c.update(cfg)
+    c = _merged_config("UNet2DCondition", DEFAULTS, cfg)
     if not c["block_out_channels"]:
         raise ValueError("UNet2DCondition: block_out_channels is empty")
     levels = len(c["block_out_channels"])
@@ -160,7 +154,7 @@ def launches_per_forward(**cfg):
 class UNet2DCondition(_HFNet):
     """UNet2DConditionModel.forward in eval mode on the HIP path.  Keyword arguments are the configuration's fields."""
 
-    PREFIX, NAME, KERNEL_GROUPS = "nesr_unet", "UNet2DCondition", KERNEL_GROUPS
+    PREFIX, NAME, KERNEL_GROUPS, DEFAULTS = "nesr_unet", "UNet2DCondition", KERNEL_GROUPS, DEFAULTS
     TRAIN_ERROR = "UNet2DCondition is inference only"
     _spec = staticmethod(unet_state_dict_spec)
     CHECKPOINT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")
@@ -176,13 +170,6 @@ class UNet2DCondition(_HFNet):
         """A UNet with the weights of a local ``diffusion_pytorch_model.safetensors`` / ``.bin`` (or of the ``unet/`` directory
         that holds one).  A ``config.json`` beside the weights supplies the configuration's fields; arguments override it.  Nothing
         is ever fetched."""
-        path = os.fspath(path)
-        folder = path if os.path.isdir(path) else os.path.dirname(path)
-        config = os.path.join(folder, "config.json")
-        if os.path.isfile(config):
-            with open(config) as f:
-                found = json.load(f)
-            cfg = dict({k: found[k] for k in DEFAULTS if k in found and found[k] is not None}, **cfg)
         return super().from_checkpoint(path, compute_dtype=compute_dtype, **cfg)
 
     def _create(self, index):
@@ -192,18 +179,14 @@ class UNet2DCondition(_HFNet):
         widths = c["block_out_channels"]
         n = len(widths)
         strings = lambda names: (ctypes.c_char_p * n)(*[str(v).encode() for v in names])
-        handle = ctypes.c_void_p()
-        rc = lib.nesr_unet_create(ctypes.byref(handle), index, int(c["in_channels"]), int(c["out_channels"]), n, (ctypes.c_int * n)(*widths),
-                                  strings(c["down_block_types"]), strings(c["up_block_types"]), str(c["mid_block_type"]).encode(),
-                                  (ctypes.c_int * n)(*[int(v) for v in c["only_cross_attention"]]), int(c["layers_per_block"]),
-                                  int(c["attention_head_dim"]), int(c["cross_attention_dim"]), int(c["transformer_layers_per_block"]),
-                                  int(bool(c["use_linear_projection"])), int(bool(c["dual_cross_attention"])), int(c["num_class_embeds"] or 0),
-                                  int(c["norm_num_groups"]), float(c["norm_eps"]), int(bool(c["flip_sin_to_cos"])), float(c["freq_shift"]),
-                                  int(c["downsample_padding"]), str(c["act_fn"]).encode())
-        if rc == _lib.ERR_UNSUPPORTED:
-            msg = lib.nesr_last_error()
-            raise _lib.NesrUnsupportedError(f"nesr_unet_create failed ({rc}): {msg.decode() if msg else '?'}")
-        _lib.check(rc, "nesr_unet_create")
+        handle = _HFNet._create_handle(      # not through self: the refusal tests call _create with a bare configuration holder
+            "nesr_unet_create", index, int(c["in_channels"]), int(c["out_channels"]), n, (ctypes.c_int * n)(*widths),
+            strings(c["down_block_types"]), strings(c["up_block_types"]), str(c["mid_block_type"]).encode(),
+            (ctypes.c_int * n)(*[int(v) for v in c["only_cross_attention"]]), int(c["layers_per_block"]),
+            int(c["attention_head_dim"]), int(c["cross_attention_dim"]), int(c["transformer_layers_per_block"]),
+            int(bool(c["use_linear_projection"])), int(bool(c["dual_cross_attention"])), int(c["num_class_embeds"] or 0),
+            int(c["norm_num_groups"]), float(c["norm_eps"]), int(bool(c["flip_sin_to_cos"])), float(c["freq_shift"]),
+            int(c["downsample_padding"]), str(c["act_fn"]).encode())
         try:
             _lib.check(lib.nesr_unet_set_dtype(handle, COMPUTE_DTYPES[getattr(self, "compute_dtype", "f32")]), "nesr_unet_set_dtype")
         except Exception:
@@ -213,20 +196,12 @@ class UNet2DCondition(_HFNet):
 
     def weight_bytes(self, device=None):
         """Bytes of weights the context of `device` holds on it: in the fp16 form the f16 copy of the GEMM weights and the f32 rest."""
-        device = torch.device("cuda" if device is None else device)
-        size = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_unet_weight_bytes", None, self._context(device), (ctypes.byref(size),))
-        return size.value
+        return self._query_size("nesr_unet_weight_bytes", device)
 
     # ------------------------------------------------------------------ forward
     def workspace_bytes(self, n, h, w, tokens, device=None):
         """Bytes of workspace a forward of n samples of h x w latents with `tokens` text states allocates on the context of `device`."""
-        device = torch.device("cuda" if device is None else device)
-        size = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_unet_workspace_bytes", None, self._context(device), (int(n), int(h), int(w), int(tokens), ctypes.byref(size)))
-        return size.value
+        return self._query_size("nesr_unet_workspace_bytes", device, int(n), int(h), int(w), int(tokens))
 
     def forward(self, sample, timestep, encoder_hidden_states, class_labels):
         """sample [n, in_channels, h, w] and encoder_hidden_states [n, tokens, cross_attention_dim], float32 on the device; timestep

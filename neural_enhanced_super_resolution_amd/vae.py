@@ -19,15 +19,13 @@ NesrUnsupportedError when the context is created, and the message names the fiel
 from __future__ import annotations
 
 import ctypes
-import json
-import os
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
 from ._contexts import _invoke
-from ._hfnet import _HFNet
+from ._hfnet import _HFNet, _merged_config
 
 # the published x4 upscaler's values, recalled from memory: a config.json beside the weights, or the arguments, override them
 DEFAULTS = dict(latent_channels=4, out_channels=3, block_out_channels=(128, 256, 512), layers_per_block=2, norm_num_groups=32,
@@ -39,11 +37,7 @@ _DROPPED = ("encoder.", "quant_conv.")
 
 
 def _config(cfg):
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown:
-        raise TypeError(f"VaeDecoder: unknown configuration field(s) {unknown}; expected some of {sorted(DEFAULTS)}")
-    c = dict(DEFAULTS)
-    c.update(cfg)
+    c = _merged_config("VaeDecoder", DEFAULTS, cfg)
     c["block_out_channels"] = tuple(int(v) for v in c["block_out_channels"])
     if not c["block_out_channels"]:
         raise ValueError("VaeDecoder: block_out_channels is empty")
@@ -107,7 +101,7 @@ def decoder_state_dict(state_dict):
 class VaeDecoder(_HFNet):
     """AutoencoderKL.decode in eval mode on the HIP path.  Keyword arguments are the configuration's fields."""
 
-    PREFIX, NAME, KERNEL_GROUPS = "nesr_vae", "VaeDecoder", KERNEL_GROUPS
+    PREFIX, NAME, KERNEL_GROUPS, DEFAULTS = "nesr_vae", "VaeDecoder", KERNEL_GROUPS, DEFAULTS
     TRAIN_ERROR = "VaeDecoder is inference only"
     _spec = staticmethod(vae_state_dict_spec)
     CHECKPOINT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin")
@@ -120,34 +114,13 @@ class VaeDecoder(_HFNet):
         attention's legacy names renamed first (decoder_state_dict)."""
         return super().load_state_dict(decoder_state_dict(state_dict), strict=strict, **kw)
 
-    @classmethod
-    def from_checkpoint(cls, path, **cfg):
-        """A decoder with the weights of a local ``diffusion_pytorch_model.safetensors`` / ``.bin`` (or of the ``vae/`` directory
-        that holds one).  A ``config.json`` beside the weights supplies the configuration's fields; arguments override it.  Nothing
-        is ever fetched."""
-        path = os.fspath(path)
-        folder = path if os.path.isdir(path) else os.path.dirname(path)
-        config = os.path.join(folder, "config.json")
-        if os.path.isfile(config):
-            with open(config) as f:
-                found = json.load(f)
-            cfg = dict({k: found[k] for k in DEFAULTS if k in found}, **cfg)
-        return super().from_checkpoint(path, **cfg)
-
     def _create(self, index):
         """A context of this configuration without weights (NesrUnsupportedError names the field the kernels do not take)."""
-        lib = _lib.load()
         c = self.config
         widths = c["block_out_channels"]
-        handle = ctypes.c_void_p()
-        rc = lib.nesr_vae_create(ctypes.byref(handle), index, int(c["latent_channels"]), int(c["out_channels"]), len(widths),
-                                 (ctypes.c_int * len(widths))(*widths), int(c["layers_per_block"]), int(c["norm_num_groups"]),
-                                 float(c["scaling_factor"]), str(c["act_fn"]).encode())
-        if rc == _lib.ERR_UNSUPPORTED:
-            msg = lib.nesr_last_error()
-            raise _lib.NesrUnsupportedError(f"nesr_vae_create failed ({rc}): {msg.decode() if msg else '?'}")
-        _lib.check(rc, "nesr_vae_create")
-        return handle
+        return self._create_handle("nesr_vae_create", index, int(c["latent_channels"]), int(c["out_channels"]), len(widths),
+                                   (ctypes.c_int * len(widths))(*widths), int(c["layers_per_block"]), int(c["norm_num_groups"]),
+                                   float(c["scaling_factor"]), str(c["act_fn"]).encode())
 
     # ------------------------------------------------------------------ decode
     def output_size(self, h, w):
@@ -159,11 +132,7 @@ class VaeDecoder(_HFNet):
 
     def workspace_bytes(self, h, w, device=None):
         """Bytes of workspace a decode of h x w latents allocates on the context of `device`."""
-        device = torch.device("cuda" if device is None else device)
-        n = ctypes.c_size_t(0)
-        with torch.cuda.device(device):
-            _invoke("nesr_vae_workspace_bytes", None, self._context(device), (int(h), int(w), ctypes.byref(n)))
-        return n.value
+        return self._query_size("nesr_vae_workspace_bytes", device, int(h), int(w))
 
     def _latents(self, z, what):
         self._require_device(z, what)

@@ -169,6 +169,9 @@ def test_the_largest_f16_passes_and_the_form_is_fixed_at_finalize():
         assert b"between" in lib.nesr_last_error()
         # no device: nothing that would launch
         assert lib.nesr_swin2sr_part_f32(handle, 0, 0, 0, ctypes.c_void_p(64), 1, 4, 4, ctypes.c_void_p(64), 1 << 20, None) == ERR_STATE
+        n = ctypes.c_int64(7)      # nor a timing to collect: refused as the other networks' entries refuse it, before any device call
+        assert lib.nesr_swin2sr_kernel_time_ms(handle, None, 0, ctypes.byref(n)) == ERR_STATE and n.value == 7
+        assert lib.nesr_last_error() == b"nesr_swin2sr_kernel_time_ms: a context without a device launches nothing"
     finally:
         lib.nesr_swin2sr_destroy(handle)
 

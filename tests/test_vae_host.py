@@ -3,6 +3,7 @@ modules (nn.GroupNorm, nn.Conv2d, nn.Linear, F.scaled_dot_product_attention; dif
 generations of attention names, the keys that are dropped, the strictness of the loader in Python and in the library, the
 configuration checks of nesr_vae_create on a context without a device, and nesr_vae_output_size."""
 import ctypes
+import json
 
 import pytest
 import torch
@@ -10,7 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from neural_enhanced_super_resolution_amd import VaeDecoder, _lib, vae_state_dict_spec
-from neural_enhanced_super_resolution_amd.vae import decoder_state_dict
+from neural_enhanced_super_resolution_amd.vae import DEFAULTS, decoder_state_dict
 from tests import vae_cases as C
 from tests import vae_ref as R
 
@@ -189,6 +190,17 @@ def test_load_state_dict_is_strict():
         VaeDecoder.from_checkpoint("stabilityai/stable-diffusion-x4-upscaler")
     with pytest.raises(TypeError, match="unknown configuration"):
         VaeDecoder(sample_size=64)
+
+
+def test_a_null_field_of_config_json_leaves_the_default(tmp_path):
+    """from_checkpoint's config.json reader is _HFNet's: a field the file holds as null is left to the default, an argument overrides the file."""
+    case = C.by_name("two_levels")
+    torch.save(dict(case.sd), tmp_path / "diffusion_pytorch_model.bin")
+    found = dict(R.config(**case.cfg), scaling_factor=None, layers_per_block=3, _class_name="AutoencoderKL")
+    (tmp_path / "config.json").write_text(json.dumps({k: list(v) if isinstance(v, tuple) else v for k, v in found.items()}))
+    m = VaeDecoder.from_checkpoint(tmp_path, layers_per_block=case.cfg["layers_per_block"])
+    assert m.config["scaling_factor"] == DEFAULTS["scaling_factor"] and m.config["layers_per_block"] == case.cfg["layers_per_block"]
+    assert m.config["block_out_channels"] == tuple(case.cfg["block_out_channels"])
 
 
 def _load(lib, h, key, t):
