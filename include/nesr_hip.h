@@ -275,6 +275,27 @@ int nesr_fused_state(const nesr_ctx* ctx);
 int nesr_debug_fault(nesr_ctx* ctx, int drop_workgroups);
 
 /*
+ * rdb_bf16_strip_kernel: which workgroup runs which 16-column strips of which image, in which order, is a host-side packing.
+ * Read when a context is created: NESR_STRIP = -1 | 0 | 1 (auto: size-independent contexts and batches that fill the device;
+ * never; wherever the kernel applies), NESR_STRIP_SEG = n (positions of 12 rows per row segment of a strip at most; 0: the packer
+ * decides, the default; -1: images are never cut), NESR_STRIP_CUS = k (the workgroup count the packer plans for, clamped to
+ * 1 .. the device's compute units; default: all of them -- fewer workgroups put more items on each, the values do not change).
+ * The kernel applies to a batch when no image is wider than 16 k columns and none has more than 256 positions
+ * (ceil((h + 4) / 12) of its trunk height h: the edge-column tags of a launch hold position * 8 + layer below 2048).  That
+ * depends on the images alone, so a size-independent context gives an image one arithmetic in every batch.
+ * nesr_strip_schedule is host only (no device, no context): the packing of n images of hw[2i] x hw[2i+1] trunk pixels for `cus`
+ * workgroups.  items receives 8 ints per item (image | mailbox group << 16, strip, image height, image width, first position,
+ * end position, first row stored, end row), wg_first the grid + 1 list bounds; info[10] = makespan (positions; -1: no packing),
+ * grid, smax (most strips of an image), mailbox groups, items, applies (0 | 1: what the forward decides), max_wait (most
+ * positions a workgroup idles in front of its next item, by a walk of the lists; -1: the walk found a cycle), the walk's
+ * makespan, the largest end position of an item, the largest one the tag space admits; *efficiency = strip positions of work /
+ * (cus x makespan).  info and efficiency are written even where the buffers are too small (NESR_ERR_ARG): info[4] and info[1] + 1
+ * are the capacities to come back with.
+ */
+int nesr_strip_schedule(int n, const int* hw, int cus, int seg_len, int* items, int items_cap, int* wg_first, int wg_cap, int* info,
+                        double* efficiency);
+
+/*
  * Where rdb_f16x2_kernel applies to every dense block of a whole-frame forward, the trunk goes out as ONE launch of
  * rdb_f16x2_chain_kernel: the same block body run 3 num_block times, the block boundary a nine-neighbour wait on the progress words
  * where it was a kernel boundary (the values are the same bit for bit).  The row-band and single-block entries (nesr_band_*) keep one

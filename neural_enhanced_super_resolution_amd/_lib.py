@@ -67,6 +67,8 @@ SIGNATURES = {
     "nesr_fused_state": (_c.c_int, [_c.c_void_p]),
     "nesr_rdb_chain_state": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int)]),
     "nesr_rdb_chain_table": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "nesr_strip_schedule": (_c.c_int, [_c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_int, _c.POINTER(_c.c_int), _c.c_int,
+                                       _c.POINTER(_c.c_int), _c.POINTER(_c.c_double)]),
     "nesr_set_upconv": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_upconv_state": (_c.c_int, [_c.c_void_p]),
     "nesr_set_conv_last": (_c.c_int, [_c.c_void_p, _c.c_int]),

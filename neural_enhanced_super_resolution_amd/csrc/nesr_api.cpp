@@ -6,6 +6,7 @@
 // What it stands behind in the reference: basicsr RRDBNet.__init__/forward and realesrgan
 // RealESRGANer's load_state_dict, as called from nesr/nesr.py:216-229,887-891 and
 // standalone/direct_esrgan.py:104-148.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -99,6 +100,7 @@ int nesr_create(nesr_ctx** out, int device_id, int conv_first_in_ch, int unshuff
     if (const char* e = getenv("NESR_STRIP_SEG")) c->strip_seg = atoi(e);
     if (const char* e = getenv("NESR_FUSED_TIMEOUT_MS")) c->strip_timeout_ticks = (unsigned long long)atoll(e) * 100000ull;
     (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device_id);
+    if (const char* e = getenv("NESR_STRIP_CUS")) c->strip_cus = std::min(std::max(atoi(e), 1), std::max(c->cus, 1));
     auto add = [&](const std::string& name, int cin, int cout) {
         Layer L;
         L.name = name;
@@ -495,6 +497,27 @@ int nesr_rdb_chain_table(int num_block, const uint64_t* buffers, const uint64_t*
         rdb_block_entry(buf, layers.data(), i / 3, i % 3, e);
         std::memcpy(table + (size_t)i * 13, &e, sizeof(e));
     }
+    return NESR_OK;
+}
+
+int nesr_strip_schedule(int n, const int* hw, int cus, int seg_len, int* items, int items_cap, int* wg_first, int wg_cap, int* info,
+                        double* efficiency) {
+    if (n <= 0 || !hw || cus <= 0 || !info) return set_error(NESR_ERR_ARG, "nesr_strip_schedule: n and cus from 1, hw and info not null");
+    for (int i = 0; i < 2 * n; ++i)
+        if (hw[i] <= 0) return set_error(NESR_ERR_ARG, "nesr_strip_schedule: image sizes from 1");
+    const StripSchedule S = strip_schedule(n, hw, cus, seg_len);
+    const int count = (int)(S.items.size() / 8);
+    int walked = 0;
+    const int wait = S.makespan > 0 ? strip_max_wait(S, &walked) : -1;
+    info[0] = S.makespan; info[1] = S.grid; info[2] = S.smax; info[3] = S.nvimg; info[4] = count;
+    info[5] = strip_plan_applies(S) ? 1 : 0;
+    info[6] = wait; info[7] = walked;
+    info[8] = strip_largest_pos1(S); info[9] = STRIP_MAX_POS1;
+    if (efficiency) *efficiency = S.efficiency;
+    if ((count > 0 && (!items || items_cap < count)) || (!S.wg_first.empty() && (!wg_first || wg_cap < (int)S.wg_first.size())))
+        return set_error(NESR_ERR_ARG, "nesr_strip_schedule: the plan has " + std::to_string(count) + " items on " + std::to_string(S.grid) + " workgroups; buffers too small");
+    if (count > 0) std::memcpy(items, S.items.data(), S.items.size() * sizeof(int));
+    if (!S.wg_first.empty()) std::memcpy(wg_first, S.wg_first.data(), S.wg_first.size() * sizeof(int));
     return NESR_OK;
 }
 

@@ -203,6 +203,12 @@ hipError_t launch_rdb_f16x2_chain(const RdbLaunch& r, const RdbChainBlock* table
 // image and sweeps it top to bottom in positions of 12 rows; x1..x4 never leave the CU except for the strips' edge columns.
 constexpr int STRIP_BH = 12, STRIP_BW = 16;
 constexpr int STRIP_XCH_BYTES = 2 * 2 * 4 * STRIP_BH * 128;   // edge-column mailboxes of one strip
+// An edge-column granule carries the tag epoch + position * 8 + layer (layer 1..4; the position is one of the IMAGE's own grid,
+// pos0 .. pos1 - 1 of an item, not a time of the schedule), and a launch owns the tags [epoch, epoch + STRIP_EPOCH_STEP): the
+// last position of an image is at most STRIP_EPOCH_STEP / 8 - 1, so the largest end position of an item the tags can tell apart:
+constexpr unsigned STRIP_EPOCH_STEP = 2048;
+constexpr int STRIP_MAX_POS1 = (int)(STRIP_EPOCH_STEP / 8);
+static_assert((unsigned)(STRIP_MAX_POS1 - 1) * 8u + 4u < STRIP_EPOCH_STEP, "a tag of the last position runs into the next launch's");
 struct StripSchedule {
     std::vector<int> items;      // 8 ints per item: image | mailbox group << 16, strip, image height, image width, first position, end
                                  // position, first output row stored, end row (a row segment of the strip; whole images: 0, npos, 0, h)
@@ -214,6 +220,15 @@ struct StripSchedule {
 // n images of hw[2i] x hw[2i+1] internal pixels -> the packing (makespan < 0: the kernel does not apply).  seg_len: positions per row
 // segment at most (0: chosen by the packer, < 0: images are never cut)
 StripSchedule strip_schedule(int n, const int* hw, int cus, int seg_len = 0);
+// Does the kernel run this packing?  It depends on the images alone, never on their company: a packing exists (no image wider
+// than the workgroups), every item's end position fits the tag space (STRIP_MAX_POS1) and the item words hold their fields
+// (image < 65536, mailbox group < 32768).  The one answer of the forward (strip_plan_for) and of nesr_strip_schedule.
+int strip_largest_pos1(const StripSchedule& S);
+bool strip_plan_applies(const StripSchedule& S);
+// The lists walked on the host: a unit (the strips of one image segment) starts when all of its workgroups have reached it.
+// -> the largest number of positions a workgroup idles in front of its next item, the walk's makespan in *makespan; -1 if the
+// walk stops with items left (a cycle of waits: no global order of the units that every list respects)
+int strip_max_wait(const StripSchedule& S, int* makespan);
 size_t strip_weight_bytes();
 void pack_strip_weights(const float* const w[5], uint16_t* dst, bool f16);   // conv1..conv5 OIHW f32 of one dense block -> bf16 | f16
 struct StripLaunch {
@@ -224,7 +239,7 @@ struct StripLaunch {
     const void* items; const int* wg_first;       // device copies of the schedule
     int grid, smax;
     void* xch;                                    // nvimg * smax * STRIP_XCH_BYTES
-    unsigned epoch;                               // strictly increasing by >= 2048 per launch
+    unsigned epoch;                               // strictly increasing by >= STRIP_EPOCH_STEP per launch
     unsigned* abort_flag;
     unsigned long long timeout_ticks;
     int debug_drop;                               // test hook: this many workgroups of the launch never start

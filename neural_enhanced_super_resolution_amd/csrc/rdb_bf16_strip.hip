@@ -347,6 +347,7 @@ __global__ __launch_bounds__(64 * (MW + DW), 2) void rdb_bf16_strip_kernel(Strip
                     const int m_now = idx < 2 ? 0 : idx < 5 ? 1 : idx < 9 ? 2 : idx < 14 ? 3 : 4;
                     if (m_now != imp_m) { imp_m = m_now; imp_done = !has_nb; pending = false; }
                     const bool polling = d < 2 && imp_m > 0 && !imp_done && !(NESR_STRIP_ABL & 1);
+                    // (pos < STRIP_MAX_POS1, nesr_kernels.h: the launch's tags stay below the next launch's epoch -- strip_plan_applies)
                     const unsigned tag = a.epoch + (unsigned)pos * 8u + (unsigned)imp_m;
                     const unsigned long long* src = reinterpret_cast<const unsigned long long*>(
                         a.xch + ((((size_t)(slot_id + (d ? 1 : -1)) * 2 + (1 - d)) * 2 + (pos & 1)) * 4 + (imp_m > 0 ? imp_m - 1 : 0)) * XCH_LAYER) + lane;
@@ -968,6 +969,57 @@ StripSchedule strip_schedule(int n, const int* hw, int cus, int seg_len) {
     best.smax = smax;
     best.efficiency = best.makespan > 0 ? (double)work / ((double)cus * best.makespan) : 0.0;
     return best;
+}
+
+int strip_largest_pos1(const StripSchedule& S) {
+    int p = 0;
+    for (size_t i = 0; i + 8 <= S.items.size(); i += 8) p = std::max(p, S.items[i + 5]);
+    return p;
+}
+
+bool strip_plan_applies(const StripSchedule& S) {
+    // every image has a unit, so nvimg bounds the image index as well
+    return S.makespan > 0 && S.nvimg > 0 && S.nvimg < 32768 && strip_largest_pos1(S) <= STRIP_MAX_POS1;
+}
+
+int strip_max_wait(const StripSchedule& S, int* makespan) {
+    const int grid = (int)S.wg_first.size() - 1;
+    if (makespan) *makespan = 0;
+    if (grid <= 0 || S.nvimg <= 0) return -1;
+    std::vector<int> head(S.wg_first.begin(), S.wg_first.end() - 1), t((size_t)grid, 0);
+    // per unit (mailbox group): the workgroups that have it at the head of their list right now
+    std::vector<std::vector<int>> at((size_t)S.nvimg);
+    std::vector<int> ready;
+    auto arrive = [&](int g) {
+        if (head[g] >= S.wg_first[g + 1]) return;
+        const int* it = &S.items[(size_t)head[g] * 8];
+        const int v = (int)((unsigned)it[0] >> 16), ns = (it[3] + BW - 1) / BW;
+        if (v >= S.nvimg) return;
+        at[(size_t)v].push_back(g);
+        if ((int)at[(size_t)v].size() == ns) ready.push_back(v);
+    };
+    for (int g = 0; g < grid; ++g) arrive(g);
+    int wait = 0, mk = 0;
+    size_t done = 0;
+    while (!ready.empty()) {
+        const int v = ready.back();
+        ready.pop_back();
+        const std::vector<int> wgs = at[(size_t)v];
+        at[(size_t)v].clear();
+        int start = 0;
+        for (int g : wgs) start = std::max(start, t[(size_t)g]);
+        for (int g : wgs) {
+            const int* it = &S.items[(size_t)head[g] * 8];
+            wait = std::max(wait, start - t[(size_t)g]);
+            t[(size_t)g] = start + (it[5] - it[4]);
+            mk = std::max(mk, t[(size_t)g]);
+            ++head[g];
+            ++done;
+            arrive(g);
+        }
+    }
+    if (makespan) *makespan = mk;
+    return done * 8 == S.items.size() ? wait : -1;
 }
 
 namespace {

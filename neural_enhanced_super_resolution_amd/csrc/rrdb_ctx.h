@@ -115,6 +115,7 @@ struct nesr_ctx {
     unsigned long long strip_timeout_ticks = 20000000ull;   // 200 ms of s_memrealtime: what an inter-workgroup wait of a persistent kernel may take
     int rdb_mode_init = -1, strip_mode_init = -1;
     int strip_seg = 0;               // NESR_STRIP_SEG: positions per row segment of a strip at most (0: the packer decides, -1: never cut)
+    int strip_cus = 0;               // NESR_STRIP_CUS: the workgroups the packer plans for, 1 .. cus (0: cus)
     // sharded frames (nesr_comm_init / nesr_forward_sharded_u8): RCCL communicator + scratch
     void* comm = nullptr;            // ncclComm_t
     int comm_rank = 0, comm_nranks = 1;

@@ -202,9 +202,9 @@ int strip_plan_for(nesr_ctx* c, int N, int h, int w, const nesr_ctx::StripPlan**
     }
     nesr_ctx::StripPlan P;
     P.key = key;
-    const StripSchedule S = strip_schedule(N, hw.data(), c->cus, c->strip_seg);
+    const StripSchedule S = strip_schedule(N, hw.data(), c->strip_cus > 0 ? c->strip_cus : c->cus, c->strip_seg);
     P.makespan = S.makespan;
-    if (S.makespan > 0 && S.makespan < 250) {       // tags hold position * 8 + layer below 2048
+    if (strip_plan_applies(S)) {       // by the images' own positions (the tag space), not by the length of the schedule
         P.grid = S.grid; P.smax = S.smax; P.efficiency = S.efficiency;
         const size_t xb = (size_t)S.nvimg * S.smax * STRIP_XCH_BYTES;
         NESR_TRY(hipMalloc(&P.d_items, S.items.size() * 4));
@@ -253,7 +253,7 @@ int try_strip(nesr_ctx* c, const FwState& F, int b, int r, hipStream_t s) {
     L.bias = reinterpret_cast<const float*>(blk + strip_weight_bytes());
     L.H = F.h; L.W = F.w;
     L.items = P->d_items; L.wg_first = P->d_first; L.grid = P->grid; L.smax = P->smax; L.xch = P->d_xch;
-    c->strip_epoch += 2048;
+    c->strip_epoch += STRIP_EPOCH_STEP;
     L.epoch = c->strip_epoch;
     L.abort_flag = c->d_status + 2;
     L.timeout_ticks = c->strip_timeout_ticks;

@@ -29,6 +29,9 @@ STANDINS = (torch.float32, "f32-chunked")
 SHAPES = [(1, 1), (5, 15), (11, 16), (12, 17), (13, 33), (23, 47), (24, 48), (25, 49), (100, 9), (9, 100)]
 SEG_SHAPES = [(61, 33), (130, 20)]          # 6 and 11 positions: row segments with their warm-up position
 SEGS = ["-1", "2", "0"]                     # never cut; at most 2 positions per segment; the packer's own choice
+# two strips (17 columns) of 256 and of 257 positions (12 P - 4 rows are exactly P positions): the last position whose edge-column
+# tags a launch can tell from the next launch's, and the first beyond (test_gpu_strip_queue.py; non-negative cases, r = 0 and 2)
+TAG_SHAPES = [(12 * 256 - 4, 17), (12 * 257 - 4, 17)]
 RANDOM_CASES = [((13, 33), None), ((25, 49), None), ((61, 33), "2")]
 
 

@@ -128,32 +128,47 @@ def test_strip_values_do_not_depend_on_company_or_slot(cuda_device):
 
 
 def test_strip_full_ragged_batch_of_64(cuda_device):
-    """RAGGED_MAX images, several items per workgroup: every image equals its evaluation alone."""
+    """RAGGED_MAX images: every image equals its evaluation alone -- packed for the whole device (256 compute units: one item per
+    workgroup) and packed for 16 workgroups (NESR_STRIP_CUS), several items per workgroup; the packer is asked which."""
     from neural_enhanced_super_resolution_amd.synth import synthetic_state_dict
+    from tests import strip_plan
     sd = synthetic_state_dict(seed=0, num_in_ch=3, scale=2, num_block=1)
     from neural_enhanced_super_resolution_amd import RRDBNet
-    old = os.environ.get("NESR_STRIP")
+    old = {k: os.environ.get(k) for k in ("NESR_STRIP", "NESR_STRIP_CUS")}
     os.environ["NESR_STRIP"] = "1"
     try:
-        net = RRDBNet(3, 3, scale=2, num_block=1, compute_dtype="bf16")
-        net.load_state_dict(sd)
-        net.eval().to(cuda_device)
-        net.size_independent = True
         g = torch.Generator().manual_seed(9)
         shapes = [(2 * (3 + (7 * i) % 40), 2 * (5 + (11 * i) % 90)) for i in range(64)]
         imgs = [torch.rand(1, 3, h, w, generator=g) for h, w in shapes]
-        net.set_kernel_timing(cuda_device, True)
-        net.kernel_time()
-        full = _ragged(net, imgs)
-        assert net.kernel_time()[1] == 3
-        for j in (0, 13, 31, 63):
-            alone = _ragged(net, [imgs[j]])
-            assert torch.equal(alone[0], full[j]), shapes[j]
+        device_cus = torch.cuda.get_device_properties(0).multi_processor_count
+        first = None
+        for cus in (None, "16"):
+            if cus is not None:
+                os.environ["NESR_STRIP_CUS"] = cus          # read when the device context is created (first forward)
+            net = RRDBNet(3, 3, scale=2, num_block=1, compute_dtype="bf16")
+            net.load_state_dict(sd)
+            net.eval().to(cuda_device)
+            net.size_independent = True
+            net.set_kernel_timing(cuda_device, True)
+            net.kernel_time()
+            full = _ragged(net, imgs)
+            assert net.kernel_time()[1] == 3
+            for j in (0, 13, 31, 63):
+                alone = _ragged(net, [imgs[j]])
+                assert torch.equal(alone[0], full[j]), shapes[j]
+            if cus is None:
+                first = full
+            else:
+                plan = strip_plan.schedule([(h // 2, w // 2) for h, w in shapes], min(int(cus), device_cus), 0)
+                assert plan.applies and plan.most_items_per_workgroup() > 1, plan.most_items_per_workgroup()
+                for j in range(len(imgs)):
+                    assert torch.equal(full[j], first[j]), shapes[j]
     finally:
-        if old is None:
-            os.environ.pop("NESR_STRIP", None)
-        else:
-            os.environ["NESR_STRIP"] = old
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 @pytest.mark.parametrize("scale", [2, 4])

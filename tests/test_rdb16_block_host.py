@@ -59,6 +59,20 @@ def test_every_exact_case_has_one_answer(dtype, signed):
           f"largest |value| {worst['top']:.0f}, float64 variant equal everywhere: {f64_equal}")
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_the_tag_bound_cases_have_one_answer(dtype):
+    """The two tall shapes of test_gpu_strip_queue.py (256 and 257 positions, 17 columns), non-negative, r = 0 and 2: the plain
+    criterion, as for every non-negative case above."""
+    for hw in B.TAG_SHAPES:
+        for r in (0, 2):
+            sd, x0, rrdb_in = B.exact_case(hw, r, False, dtype)
+            assert not torch.equal(x0, rrdb_in)
+            fig = B.exactness(sd, x0, r, rrdb_in, dtype)
+            assert fig["span"] < 2.0 ** 24 and fig["wide"] == 0 and fig["undecided"] == 0, (hw, r, fig)
+            assert fig["f64_equal"] and fig["standins_equal"], (hw, r)
+            assert fig["top"] < 2.0 ** 11, (hw, r, fig)
+
+
 # ------------------------------------------------------------------------------------------------------------ mutants
 class LostHalo(RRDBNetEmu16):
     """The strip of columns 0..15 reads zeros for its halo column x = 16 in one of conv1..conv4."""
