@@ -1,9 +1,11 @@
 // Plumbing shared by every file of the C-ABI layer (nesr_api.cpp, rrdb_forward.cpp, band_api.cpp, shard_api.cpp, oneshot_api.cpp,
 // compact_api.cpp, filters_api.cpp, resize_api.cpp, frame_api.cpp, nesr_stage_api.cpp, segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp,
-// unet_api.cpp, clip_text_api.cpp, sdx4_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string, the try macro, alignment, a workspace that grows, the upload
-// of a model's packed weights, and the kernel-timing hooks of a context (EventTimer: one bracket per forward; GroupTimer: one per
-// launch, summed per kernel group).  The host side of a strictly loaded state dict is state_dict.h; what the five networks that
-// load one share around it (segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp, unet_api.cpp, clip_text_api.cpp) is net_context.h.
+// unet_api.cpp, clip_text_api.cpp, sdx4_api.cpp, jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp): the error string,
+// the try macro, alignment, the carver of a scratch buffer's regions, a workspace that grows, the upload of a model's packed weights,
+// and the kernel-timing hooks of a context (EventTimer: one bracket per forward; GroupTimer: one per launch, summed per kernel group).
+// The host side of a strictly loaded state dict is state_dict.h; what the five networks that load one share around it
+// (segformer_api.cpp, swin2sr_api.cpp, vae_api.cpp, unet_api.cpp, clip_text_api.cpp) is net_context.h; what the four file codecs
+// share (jpeg_api.cpp, jpeg_decode_api.cpp, png_api.cpp, png_decode_api.cpp) is codec_host.h, and on the device codec_device.h.
 // Not part of the public ABI (that is include/nesr_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +31,17 @@ int set_error(int code, const std::string& msg);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// Carves one scratch or workspace buffer into regions that each start on a 256-byte boundary: take() gives the next region's offset.
+struct ScratchCarver {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += align_up(bytes, 256);
+        return o;
+    }
+    size_t total() const { return at; }
+};
 
 // Kernel-timing hook of a context (nesr_set_kernel_timing / nesr_kernel_time_ms): one event pair around the timed part of every
 // forward, summed and recycled when the caller asks.  begin / end do nothing while the hook is off.

@@ -42,15 +42,10 @@ struct Plan {
 
 Plan plan(const nesr_clip_text* c, int n, int tokens) {
     Plan p;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
+    ScratchCarver ws;
     const size_t m = (size_t)n * tokens, hp = round_up(c->hidden, 16), ip = round_up(c->inter, 16);
-    p.x = take(m * hp * 4), p.qkv = take(m * 3 * hp * 4), p.att = take(m * hp * 4), p.fc = take(m * ip * 4), p.ln = take(m * sizeof(float4));
-    p.total = at;
+    p.x = ws.take(m * hp * 4), p.qkv = ws.take(m * 3 * hp * 4), p.att = ws.take(m * hp * 4), p.fc = ws.take(m * ip * 4), p.ln = ws.take(m * sizeof(float4));
+    p.total = ws.total();
     return p;
 }
 

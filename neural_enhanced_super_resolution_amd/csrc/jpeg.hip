@@ -16,12 +16,13 @@
 // No pass writes out[i] for i >= out_cap.
 //
 // The options (4:4:4 / 4:2:2, Huffman tables optimised for the frame, restart intervals; tests/jpeg_options_ref.py is their
-// specification) run launch_encode_ex: the same passes, with the EX = true instantiations of lengths, emit, stuff and finish, and
+// specification) run the same passes, with the EX = true instantiations of lengths, emit, stuff and finish, and
 //   transform  jpeg_transform_row for the MCUs that are one block row high (4:4:4, 4:2:2)
 //   histogram, build tables   (optimize) symbol counts, then libjpeg's jpeg_gen_optimal_table by one workgroup: BITS / HUFFVAL, the
 //              code tables, and the DHT, DRI and SOS bytes of the header, whose length is then known on the device only
 //   interval ends, bytes, scan   (restart interval) the byte each interval starts at; stuff inserts FF Dn between intervals
-// The default options run launch_encode: the EX = false instantiations, which never read the options' argument.
+// The default options run the EX = false instantiations, which never read the options' argument.
+#include "codec_device.h"
 #include "jpeg_kernels.h"
 #include "jpeg_tables.h"
 
@@ -615,27 +616,8 @@ __global__ __launch_bounds__(BLOCKS_PER_GROUP) void jpeg_lengths(const int16_t* 
 __global__ __launch_bounds__(1024) void jpeg_scan64(uint64_t* data, int64_t n_host, const uint64_t* n_dev, uint64_t* total_out) {
     __shared__ uint64_t buf[2][1024];
     const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
-    const int tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + tid;
-        const uint64_t v = i < n ? data[i] : 0;
-        int cur = 0;
-        buf[0][tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const uint64_t x = buf[cur][tid] + (tid >= d ? buf[cur][tid - d] : 0);
-            buf[cur ^ 1][tid] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const uint64_t incl = buf[cur][tid];
-        const uint64_t sum = buf[cur][1023];
-        if (i < n) data[i] = carry + incl - v;
-        carry += sum;
-        __syncthreads();
-    }
-    if (tid == 0) *total_out = carry;
+    const uint64_t total = codec::group_scan_1024<uint64_t>(n, buf, [&](int64_t i) { return data[i]; }, [&](int64_t i, uint64_t x) { data[i] = x; });
+    if (threadIdx.x == 0) *total_out = total;
 }
 
 // restart intervals: bits up to the end of each interval (len's inclusive scan at the interval's last block), whether an interval is
@@ -880,44 +862,20 @@ TransformArgs transform_args(const Plan& p, const EncodeArgs& a) {
     return t;
 }
 
-}  // namespace
-
-hipError_t launch_encode(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s) {
-    hipLaunchKernelGGL(jpeg_header, dim3((a.header_bytes + 255) / 256), dim3(256), 0, s, h, a.header_bytes, a.out, a.out_cap);
-    const TransformArgs t = transform_args(p, a);
-    const bool color = p.C == 3;
-    const ScanEx none{};
-    // blockIdx.y carries the MCU row: at most 65535 / 8 + 1 rows, within the grid limit
-    if (color) hipLaunchKernelGGL(jpeg_transform<true>, dim3((p.mcus_x + 15) / 16, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
-    else hipLaunchKernelGGL(jpeg_transform<false>, dim3((p.mcus_x + STRIP_BLOCKS - 1) / STRIP_BLOCKS, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
-    hipLaunchKernelGGL(jpeg_lengths<false>, dim3((unsigned)p.nchunks), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, (int)color, a.len, a.chunk, none);
-    hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.chunk, p.nchunks, (const uint64_t*)nullptr, a.meta + 3);
-    const unsigned wide = (unsigned)(p.stuff_chunks < 4096 ? p.stuff_chunks : 4096);
-    hipLaunchKernelGGL(jpeg_zero<false>, dim3(wide), dim3(256), 0, s, reinterpret_cast<uint4*>(a.stream), a.meta + 3, p.stream_bytes);
-    hipLaunchKernelGGL(jpeg_emit<false>, dim3((unsigned)p.nchunks), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, (int)color, a.len, a.chunk, a.stream,
-                       p.stream_bytes / 4, a.meta, none);
-    hipLaunchKernelGGL(jpeg_count_ff, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff);
-    hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.ff, (int64_t)0, a.meta + 1, a.meta + 2);
-    hipLaunchKernelGGL(jpeg_stuff<false>, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff, a.out, a.out_cap, a.header_bytes, none);
-    hipLaunchKernelGGL(jpeg_finish<false>, dim3(1), dim3(1), 0, s, a.meta, a.out, a.out_cap, a.header_bytes, a.out_len, none);
-    return hipGetLastError();
-}
-
-// The passes of launch_encode with the options' kernels.  optimize adds the histogram and the table builder between transform and
-// lengths (the header's DHTs, DRI and SOS then come from the builder, and its length from meta[5]); a restart interval adds the
-// second scan level (interval ends, their bytes, the scan of those) between the chunk scan and zero.
-hipError_t launch_encode_ex(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s) {
-    hipLaunchKernelGGL(jpeg_header, dim3((a.header_bytes + 255) / 256), dim3(256), 0, s, h, a.header_bytes, a.out, a.out_cap);
-    const TransformArgs t = transform_args(p, a);
-    if (p.C != 3) hipLaunchKernelGGL(jpeg_transform<false>, dim3((p.mcus_x + STRIP_BLOCKS - 1) / STRIP_BLOCKS, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
-    else if (p.sampling == SAMPLING_420) hipLaunchKernelGGL(jpeg_transform<true>, dim3((p.mcus_x + 15) / 16, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
-    else if (p.sampling == SAMPLING_422) hipLaunchKernelGGL(jpeg_transform_row<2>, dim3((p.mcus_x + 23) / 24, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
-    else hipLaunchKernelGGL(jpeg_transform_row<1>, dim3((p.mcus_x + 31) / 32, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+// The passes behind the transform.  EX = false is the file cv2.imwrite writes by default (4:2:0 or gray, standard tables, no restart
+// interval): the kernels without the options, an empty ScanEx.  EX = true takes the scan's layout from the plan; optimize adds the
+// histogram and the table builder in front of lengths (the header's DHTs, DRI and SOS then come from the builder, and its length from
+// meta[5]); a restart interval adds the second scan level (interval ends, their bytes, the scan of those) between the chunk scan and zero.
+template <bool EX>
+hipError_t launch_passes(const Plan& p, const EncodeArgs& a, hipStream_t s) {
+    const int color = EX ? 0 : (int)(p.C == 3);              // with EX the layout is x.per / x.ny
     ScanEx x{};
-    x.per = p.per;
-    x.ny = p.ny;
-    x.ri = p.ri;
-    x.nint = p.nint;
+    if (EX) {
+        x.per = p.per;
+        x.ny = p.ny;
+        x.ri = p.ri;
+        x.nint = p.nint;
+    }
     const unsigned groups = (unsigned)p.nchunks;
     if (p.optimize) {
         hipError_t e = hipMemsetAsync(a.hist, 0, 4 * 256 * sizeof(uint64_t), s);
@@ -929,7 +887,7 @@ hipError_t launch_encode_ex(const Plan& p, const EncodeArgs& a, const Header& h,
         x.luts = a.luts;
         x.header_dev = a.meta + 5;
     }
-    hipLaunchKernelGGL(jpeg_lengths<true>, dim3(groups), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, 0, a.len, a.chunk, x);
+    hipLaunchKernelGGL(jpeg_lengths<EX>, dim3(groups), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, color, a.len, a.chunk, x);
     hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.chunk, p.nchunks, (const uint64_t*)nullptr, a.meta + 3);
     const unsigned wide = (unsigned)(p.stuff_chunks < 4096 ? p.stuff_chunks : 4096);
     if (p.ri) {
@@ -942,12 +900,26 @@ hipError_t launch_encode_ex(const Plan& p, const EncodeArgs& a, const Header& h,
     } else {
         hipLaunchKernelGGL(jpeg_zero<false>, dim3(wide), dim3(256), 0, s, reinterpret_cast<uint4*>(a.stream), a.meta + 3, p.stream_bytes);
     }
-    hipLaunchKernelGGL(jpeg_emit<true>, dim3(groups), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, 0, a.len, a.chunk, a.stream, p.stream_bytes / 4, a.meta, x);
+    hipLaunchKernelGGL(jpeg_emit<EX>, dim3(groups), dim3(BLOCKS_PER_GROUP), 0, s, a.coef, p.nblocks, color, a.len, a.chunk, a.stream, p.stream_bytes / 4, a.meta, x);
     hipLaunchKernelGGL(jpeg_count_ff, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff);
     hipLaunchKernelGGL(jpeg_scan64, dim3(1), dim3(1024), 0, s, a.ff, (int64_t)0, a.meta + 1, a.meta + 2);
-    hipLaunchKernelGGL(jpeg_stuff<true>, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff, a.out, a.out_cap, a.header_bytes, x);
-    hipLaunchKernelGGL(jpeg_finish<true>, dim3(1), dim3(1), 0, s, a.meta, a.out, a.out_cap, a.header_bytes, a.out_len, x);
+    hipLaunchKernelGGL(jpeg_stuff<EX>, dim3(wide), dim3(256), 0, s, reinterpret_cast<const uint4*>(a.stream), a.meta, a.ff, a.out, a.out_cap, a.header_bytes, x);
+    hipLaunchKernelGGL(jpeg_finish<EX>, dim3(1), dim3(1), 0, s, a.meta, a.out, a.out_cap, a.header_bytes, a.out_len, x);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_encode(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s) {
+    hipLaunchKernelGGL(jpeg_header, dim3((a.header_bytes + 255) / 256), dim3(256), 0, s, h, a.header_bytes, a.out, a.out_cap);
+    const TransformArgs t = transform_args(p, a);
+    // blockIdx.y carries the MCU row: at most 65535 / 8 + 1 rows, within the grid limit
+    if (p.C != 3) hipLaunchKernelGGL(jpeg_transform<false>, dim3((p.mcus_x + STRIP_BLOCKS - 1) / STRIP_BLOCKS, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    else if (p.sampling == SAMPLING_420) hipLaunchKernelGGL(jpeg_transform<true>, dim3((p.mcus_x + 15) / 16, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    else if (p.sampling == SAMPLING_422) hipLaunchKernelGGL(jpeg_transform_row<2>, dim3((p.mcus_x + 23) / 24, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    else hipLaunchKernelGGL(jpeg_transform_row<1>, dim3((p.mcus_x + 31) / 32, p.mcus_y), dim3(TRANSFORM_THREADS), 0, s, t);
+    const bool defaults = p.sampling == SAMPLING_420 && !p.optimize && !p.ri;
+    return defaults ? launch_passes<false>(p, a, s) : launch_passes<true>(p, a, s);
 }
 
 }  // namespace jpeg

@@ -3,7 +3,7 @@
 // (standalone/direct_esrgan.py:169, nesr/nesr.py:646): quality 95 by default, 4:2:0, baseline, standard Huffman tables.
 // The _ex entries take a nesr_jpeg_opts (sampling, optimize, restart interval: cv2.imwrite's other JPEG flags); the three entries
 // without it forward with {quality, NESR_JPEG_420, 0, 0}, which plans the same scratch and runs the same launches as before.
-#include "api_common.h"
+#include "codec_host.h"
 #include "jpeg_kernels.h"
 #include "jpeg_tables.h"
 
@@ -48,23 +48,18 @@ bool plan(int H, int W, int C, const nesr_jpeg_opts& o, Plan* p) {
     // every restart interval but the last is rounded up to a byte: at most one more byte each (the markers are not in this stream)
     p->stream_bytes = (int64_t)align_up((size_t)p->nblocks * MAX_BLOCK_BYTES + 8 + (p->ri ? (size_t)p->nint : 0), STUFF_CHUNK);
     p->stuff_chunks = p->stream_bytes / STUFF_CHUNK;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
-    p->off_coef = take((size_t)p->nblocks * 128);
-    p->off_len = take((size_t)p->nblocks * 4);
-    p->off_chunk = take((size_t)p->nchunks * 8);
-    p->off_meta = take(256);
-    p->off_stream = take((size_t)p->stream_bytes);
-    p->off_ff = take((size_t)p->stuff_chunks * 8);
-    p->off_hist = take(p->optimize ? 4 * 256 * 8 : 0);
-    p->off_luts = take(p->optimize ? LUT_WORDS * 4 : 0);
-    p->off_ivend = take(p->ri ? (size_t)p->nint * 8 : 0);
-    p->off_ivb = take(p->ri ? (size_t)p->nint * 8 : 0);
-    p->total = at;
+    ScratchCarver ws;
+    p->off_coef = ws.take((size_t)p->nblocks * 128);
+    p->off_len = ws.take((size_t)p->nblocks * 4);
+    p->off_chunk = ws.take((size_t)p->nchunks * 8);
+    p->off_meta = ws.take(256);
+    p->off_stream = ws.take((size_t)p->stream_bytes);
+    p->off_ff = ws.take((size_t)p->stuff_chunks * 8);
+    p->off_hist = ws.take(p->optimize ? 4 * 256 * 8 : 0);
+    p->off_luts = ws.take(p->optimize ? LUT_WORDS * 4 : 0);
+    p->off_ivend = ws.take(p->ri ? (size_t)p->nint * 8 : 0);
+    p->off_ivb = ws.take(p->ri ? (size_t)p->nint * 8 : 0);
+    p->total = ws.total();
     return true;
 }
 
@@ -198,18 +193,17 @@ int nesr_jpeg_header(int H, int W, int C, int quality, uint8_t* buf, int cap, in
 int nesr_jpeg_encode_ex_u8(int device_id, const uint8_t* src_dev, int64_t src_row_bytes, int H, int W, int C, int order, const nesr_jpeg_opts* opts,
                            void* scratch_dev, size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* stream) {
     if (!src_dev || !scratch_dev || !out_dev || !out_len_dev) return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: null argument");
-    int rc = check_opts("nesr_jpeg_encode_u8", opts);
+    const char* who = "nesr_jpeg_encode_u8";
+    int rc = check_opts(who, opts);
+    if (rc == NESR_OK) rc = check_shape(who, H, W, C, opts->quality);
+    if (rc == NESR_OK) rc = codec::check_order(who, order);
+    if (rc == NESR_OK) rc = codec::check_row_stride(who, src_row_bytes, (int64_t)W * C);
     if (rc != NESR_OK) return rc;
-    rc = check_shape("nesr_jpeg_encode_u8", H, W, C, opts->quality);
-    if (rc != NESR_OK) return rc;
-    if (order != NESR_ORDER_RGB && order != NESR_ORDER_BGR) return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: order must be NESR_ORDER_RGB or NESR_ORDER_BGR");
-    if (src_row_bytes < (int64_t)W * C) return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: the row stride is smaller than a row");
     Plan p;
     plan(H, W, C, *opts, &p);
-    if (scratch_bytes < p.total)
-        return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(p.total) + " needed");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15) return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: the scratch must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out_len_dev) & 7) return set_error(NESR_ERR_ARG, "nesr_jpeg_encode_u8: out_len_dev must be 8-byte aligned");
+    rc = codec::check_scratch(who, scratch_dev, scratch_bytes, p.total);
+    if (rc == NESR_OK) rc = codec::check_word_alignment(who, "out_len_dev", out_len_dev, 8);
+    if (rc != NESR_OK) return rc;
     EncodeArgs a{};
     a.src = src_dev;
     a.src_stride = src_row_bytes;
@@ -238,9 +232,7 @@ int nesr_jpeg_encode_ex_u8(int device_id, const uint8_t* src_dev, int64_t src_ro
         a.tail_bytes = tail.n;
     }
     NESR_TRY(hipSetDevice(device_id));
-    // the default options: the kernels and launches of the file cv2.imwrite writes by default, untouched by the options
-    const bool defaults = p.sampling == SAMPLING_420 && !p.optimize && !p.ri;
-    NESR_TRY(defaults ? launch_encode(p, a, h, static_cast<hipStream_t>(stream)) : launch_encode_ex(p, a, h, static_cast<hipStream_t>(stream)));
+    NESR_TRY(launch_encode(p, a, h, static_cast<hipStream_t>(stream)));
     return NESR_OK;
 }
 

@@ -18,6 +18,7 @@
 //              YCbCr -> RGB, interleaved store, 4 pixels per lane in three 32-bit stores where the row allows
 // Every decode loop advances at least one bit per turn and ends at the stream's length; every coefficient store is guarded by the
 // frame's block count; every stream load by the stream's capacity.  A corrupt scan sets bits of the status word.
+#include "codec_device.h"
 #include "jpeg_decode_kernels.h"
 #include "jpeg_tables.h"
 
@@ -79,35 +80,9 @@ __global__ __launch_bounds__(256) void jd_count(const uint8_t* scan, int64_t n, 
     if (threadIdx.x == 0) chunk[blockIdx.x] = (uint64_t)dropped | ((uint64_t)markers << 32);
 }
 
-// Exclusive scan of data[0 .. n) in place by one workgroup of 1024; returns the sum to every lane.
-template <typename T>
-__device__ __forceinline__ T scan_in_place(T* data, int64_t n, int64_t stride, T (*buf)[1024]) {
-    const int tid = threadIdx.x;
-    T carry = 0;
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + tid;
-        const T v = i < n ? data[i * stride] : (T)0;
-        int cur = 0;
-        buf[0][tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const T x = buf[cur][tid] + (tid >= d ? buf[cur][tid - d] : (T)0);
-            buf[cur ^ 1][tid] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const T incl = buf[cur][tid];
-        const T sum = buf[cur][1023];
-        if (i < n) data[i * stride] = carry + incl - v;
-        carry += sum;
-        __syncthreads();
-    }
-    return carry;
-}
-
 __global__ __launch_bounds__(1024) void jd_scan_chunks(uint64_t* chunk, int64_t nchunks, int64_t scan_bytes, int64_t nseg, uint32_t* meta, uint32_t* status) {
     __shared__ uint64_t buf[2][1024];
-    const uint64_t total = scan_in_place<uint64_t>(chunk, nchunks, 1, buf);
+    const uint64_t total = codec::group_scan_1024<uint64_t>(nchunks, buf, [&](int64_t i) { return chunk[i]; }, [&](int64_t i, uint64_t x) { chunk[i] = x; });
     if (threadIdx.x == 0) {
         const uint32_t bytes = (uint32_t)(scan_bytes - (int64_t)(total & 0xFFFFFFFFu));
         meta[0] = bytes;
@@ -363,7 +338,7 @@ __global__ __launch_bounds__(64) void jd_sync_inter(const nesr_jpeg_huff* tables
 
 __global__ __launch_bounds__(1024) void jd_scan_counts(uint32_t* cnt, uint32_t* meta, int64_t nblocks, uint32_t* status) {
     __shared__ uint32_t buf[2][1024];
-    const uint32_t total = scan_in_place<uint32_t>(cnt, (int64_t)meta[1], 1, buf);
+    const uint32_t total = codec::group_scan_1024<uint32_t>((int64_t)meta[1], buf, [&](int64_t i) { return cnt[i]; }, [&](int64_t i, uint32_t x) { cnt[i] = x; });
     if (threadIdx.x == 0) {
         meta[2] = total;
         if ((int64_t)total < nblocks) atomicOr(status, ST_EARLY);
@@ -461,7 +436,8 @@ __global__ __launch_bounds__(DC_GROUP) void jd_dc_sums(const int16_t* coef, int6
 
 __global__ __launch_bounds__(1024) void jd_dc_scan(int32_t* dc, int64_t groups) {
     __shared__ int32_t buf[2][1024];
-    for (int c = 0; c < 3; ++c) scan_in_place<int32_t>(dc + c, groups, 3, buf);
+    for (int c = 0; c < 3; ++c)             // dc[3 g + c]: one scan per component
+        codec::group_scan_1024<int32_t>(groups, buf, [&](int64_t i) { return dc[3 * i + c]; }, [&](int64_t i, int32_t x) { dc[3 * i + c] = x; });
 }
 
 __global__ __launch_bounds__(DC_GROUP) void jd_dc_apply(int16_t* coef, int64_t nmcu, Shape sh, const int32_t* dc) {

@@ -3,7 +3,7 @@
 // (nesr/nesr.py:661-666, standalone/direct_esrgan.py:130), without the EXIF rotation: cv2.IMREAD_UNCHANGED's reading.
 #include <cstddef>
 
-#include "api_common.h"
+#include "codec_host.h"
 #include "jpeg_decode_kernels.h"
 #include "jpeg_tables.h"
 
@@ -87,25 +87,20 @@ bool plan(const nesr_jpeg_info* info, Plan* p) {
     p->yrows = p->mcus_y * info->vs * 8;
     p->cpitch = p->mcus_x * 8;
     p->crows = p->mcus_y * 8;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
-    p->off_tables = take(6 * sizeof(nesr_jpeg_huff));
-    p->off_chunk = take((size_t)p->nchunks * 8);
-    p->off_meta = take(256);
-    p->off_seg = take((size_t)p->nseg * 4);
-    p->off_stream = take((size_t)p->stream_words * 4);
-    p->off_rec = take((size_t)p->nsub * 8);
-    p->off_cnt = take((size_t)p->nsub * 4);
-    p->off_coef = take((size_t)p->nblocks * 128);
-    p->off_dc = take((size_t)p->dc_groups * 12);
-    p->off_y = take((size_t)p->ypitch * p->yrows);
-    p->off_cb = take(gray ? 0 : (size_t)p->cpitch * p->crows);
-    p->off_cr = take(gray ? 0 : (size_t)p->cpitch * p->crows);
-    p->total = at;
+    ScratchCarver ws;
+    p->off_tables = ws.take(6 * sizeof(nesr_jpeg_huff));
+    p->off_chunk = ws.take((size_t)p->nchunks * 8);
+    p->off_meta = ws.take(256);
+    p->off_seg = ws.take((size_t)p->nseg * 4);
+    p->off_stream = ws.take((size_t)p->stream_words * 4);
+    p->off_rec = ws.take((size_t)p->nsub * 8);
+    p->off_cnt = ws.take((size_t)p->nsub * 4);
+    p->off_coef = ws.take((size_t)p->nblocks * 128);
+    p->off_dc = ws.take((size_t)p->dc_groups * 12);
+    p->off_y = ws.take((size_t)p->ypitch * p->yrows);
+    p->off_cb = ws.take(gray ? 0 : (size_t)p->cpitch * p->crows);
+    p->off_cr = ws.take(gray ? 0 : (size_t)p->cpitch * p->crows);
+    p->total = ws.total();
     return true;
 }
 
@@ -251,12 +246,12 @@ int nesr_jpeg_decode_u8(int device_id, const uint8_t* file_dev, size_t n, const 
     Plan p;
     if (!plan(info, &p)) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: the info does not describe a supported frame (fill it with nesr_jpeg_parse)");
     if ((uint64_t)info->scan_offset + (uint64_t)info->scan_bytes > (uint64_t)n) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: the scan lies outside the file");
-    if (order != NESR_ORDER_RGB && order != NESR_ORDER_BGR) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: order must be NESR_ORDER_RGB or NESR_ORDER_BGR");
-    if (dst_row_bytes < (int64_t)p.W * p.C) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: the row stride is smaller than a row");
-    if (scratch_bytes < p.total)
-        return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(p.total) + " needed");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: the scratch must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(status_dev) & 3) return set_error(NESR_ERR_ARG, "nesr_jpeg_decode_u8: status_dev must be 4-byte aligned");
+    const char* who = "nesr_jpeg_decode_u8";
+    int rc = codec::check_order(who, order);
+    if (rc == NESR_OK) rc = codec::check_row_stride(who, dst_row_bytes, (int64_t)p.W * p.C);
+    if (rc == NESR_OK) rc = codec::check_scratch(who, scratch_dev, scratch_bytes, p.total);
+    if (rc == NESR_OK) rc = codec::check_word_alignment(who, "status_dev", status_dev, 4);
+    if (rc != NESR_OK) return rc;
     DecodeArgs a{};
     uint8_t* s = static_cast<uint8_t*>(scratch_dev);
     a.scan = file_dev + info->scan_offset;

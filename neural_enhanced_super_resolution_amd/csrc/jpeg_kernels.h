@@ -25,7 +25,7 @@ struct Plan {
     int64_t stream_bytes;                  // capacity of the unstuffed stream (a multiple of STUFF_CHUNK)
     int64_t stuff_chunks;                  // stream_bytes / STUFF_CHUNK
     size_t off_coef, off_len, off_chunk, off_meta, off_stream, off_ff, total;
-    // the options (nesr_jpeg_opts); with the defaults every field below is 0 / empty and launch_encode runs
+    // the options (nesr_jpeg_opts); with the defaults every field below is 0 / empty and launch_encode runs the kernels without them
     int sampling;                          // SAMPLING_420 | 422 | 444 (gray: 420)
     int per, ny;                           // blocks per MCU (1, 3, 4, 6) and how many of them are Y
     int optimize, ri;                      // Huffman tables built on the device; MCUs per restart interval (0: none)
@@ -53,7 +53,7 @@ struct EncodeArgs {
     uint64_t out_cap;
     uint64_t* out_len;                     // [0] bytes of the file  [1] 1 if it did not fit
     int header_bytes;
-    // options only (launch_encode_ex)
+    // options only
     uint64_t* hist;                        // [4][256] symbol counts: (table 0 | 1) x (DC | AC)
     uint32_t* luts;                        // [LUT_WORDS] of the optimised tables
     uint64_t* ivend;                       // [nint] bits of the scan up to each interval's end, intervals not rounded up
@@ -62,9 +62,9 @@ struct EncodeArgs {
     int tail_bytes;
 };
 
+// default options: the kernels without them; any other: the MCU shape's transform, tables and header length from device memory,
+// restart intervals
 hipError_t launch_encode(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s);
-// any other options: the MCU shape's transform, tables and header length from device memory, restart intervals
-hipError_t launch_encode_ex(const Plan& p, const EncodeArgs& a, const Header& h, hipStream_t s);
 
 }  // namespace jpeg
 }  // namespace nesr

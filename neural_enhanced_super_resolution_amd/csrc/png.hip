@@ -11,6 +11,7 @@
 //   gather   slots to `out` behind the head at their offsets, dword stores where `out` allows
 //   finish   head, Adler-32 across the chunks, the tail IDAT, IEND, the length and status words
 // No pass writes out[i] for i >= out_cap.
+#include "codec_device.h"
 #include "png_kernels.h"
 
 namespace nesr {
@@ -489,27 +490,8 @@ __global__ __launch_bounds__(THREADS) void png_chunk(const ChunkArgs a) {
 // Exclusive scan of size[0 .. n) into offs by one workgroup of 1024 with a carry; *total_out = the sum.
 __global__ __launch_bounds__(1024) void png_scan64(const uint64_t* size, uint64_t* offs, int64_t n, uint64_t* total_out) {
     __shared__ uint64_t buf[2][1024];
-    const int tid = threadIdx.x;
-    uint64_t carry = 0;
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + tid;
-        const uint64_t v = i < n ? size[i] : 0;
-        int cur = 0;
-        buf[0][tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const uint64_t x = buf[cur][tid] + (tid >= d ? buf[cur][tid - d] : 0);
-            buf[cur ^ 1][tid] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const uint64_t incl = buf[cur][tid];
-        const uint64_t sum = buf[cur][1023];
-        if (i < n) offs[i] = carry + incl - v;
-        carry += sum;
-        __syncthreads();
-    }
-    if (tid == 0) *total_out = carry;
+    const uint64_t total = codec::group_scan_1024<uint64_t>(n, buf, [&](int64_t i) { return size[i]; }, [&](int64_t i, uint64_t x) { offs[i] = x; });
+    if (threadIdx.x == 0) *total_out = total;
 }
 
 // slot c -> out[HEAD_BYTES + offs[c] ..): bytes up to the first dword boundary of `out`, dwords assembled from two of the slot's, bytes
@@ -542,33 +524,11 @@ __global__ __launch_bounds__(THREADS) void png_gather(const uint8_t* slot, const
 __global__ __launch_bounds__(THREADS) void png_finish(const Head h, const uint64_t* adler, int64_t nchunks, int64_t N, const uint64_t* meta, uint8_t* out,
                                                       uint64_t out_cap, uint64_t* out_len) {
     __shared__ uint8_t tail[TAIL_BYTES];
-    __shared__ uint32_t seg_a[THREADS], seg_b[THREADS], seg_n[THREADS];
     const int tid = threadIdx.x;
     if (tid < HEAD_BYTES && (uint64_t)tid < out_cap) out[tid] = h.bytes[tid];
-    // Adler-32 of the stream from the chunks' sums: a' = a + s1, b' = b + n a + s2 (mod 65521).  Each lane folds a run of consecutive
-    // chunks from (a, b) = (0, 0); lane 0 then chains the runs, a run of n bytes adding n a to b.  Every product stays below 2^32.
-    {
-        const int64_t per = (nchunks + THREADS - 1) / THREADS;
-        const int64_t c0 = min(nchunks, tid * per), c1 = min(nchunks, c0 + per);
-        uint32_t A = 0, B = 0;
-        for (int64_t c = c0; c < c1; ++c) {
-            const uint64_t v = adler[c];
-            const uint32_t n = (uint32_t)min((int64_t)CHUNK, N - c * CHUNK);
-            B = (B + n * A + (uint32_t)(v >> 32)) % 65521u;
-            A = (A + (uint32_t)v) % 65521u;
-        }
-        seg_a[tid] = A;
-        seg_b[tid] = B;
-        seg_n[tid] = (uint32_t)((min(N, c1 * CHUNK) - min(N, c0 * CHUNK)) % 65521);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t A = 1, B = 0;
-        for (int t = 0; t < THREADS; ++t) {
-            B = (B + (uint32_t)(((uint64_t)seg_n[t] * A) % 65521u) + seg_b[t]) % 65521u;
-            A = (A + seg_a[t]) % 65521u;
-        }
-        const uint8_t t[TAIL_BYTES] = {0, 0, 0, 4, 'I', 'D', 'A', 'T', (uint8_t)(B >> 8), (uint8_t)B, (uint8_t)(A >> 8), (uint8_t)A, 0, 0, 0, 0,
+    // the stream's Adler-32 from the chunks' sums, then the tail by lane 0
+    codec::adler_fold<CHUNK, THREADS>(adler, nchunks, N, [&](uint32_t ad) {
+        const uint8_t t[TAIL_BYTES] = {0, 0, 0, 4, 'I', 'D', 'A', 'T', (uint8_t)(ad >> 24), (uint8_t)(ad >> 16), (uint8_t)(ad >> 8), (uint8_t)ad, 0, 0, 0, 0,
                                        0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
         for (int i = 0; i < TAIL_BYTES; ++i) tail[i] = t[i];
         const uint32_t crc = crc_bytes(tail + 4, 8);
@@ -576,7 +536,7 @@ __global__ __launch_bounds__(THREADS) void png_finish(const Head h, const uint64
         tail[13] = (uint8_t)(crc >> 16);
         tail[14] = (uint8_t)(crc >> 8);
         tail[15] = (uint8_t)crc;
-    }
+    });
     __syncthreads();
     const uint64_t end = HEAD_BYTES + meta[0];
     if (tid < TAIL_BYTES && end + tid < out_cap) out[end + tid] = tail[tid];

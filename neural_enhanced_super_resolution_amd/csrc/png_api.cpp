@@ -2,11 +2,13 @@
 // nesr_png_code_lengths (host only) and nesr_png_encode (kernels of png.hip).  The lossless file a caller of the reference keeps:
 // standalone/superres_project.py:203-206 always writes .png, nesr/nesr.py:619-625 saves intermediate_iter{n}.png, and
 // standalone/direct_esrgan.py:130,169 writes a PNG input (alpha, gray, 16 bit) back as PNG.
-#include "api_common.h"
+#include "codec_host.h"
 #include "png_kernels.h"
 
 using namespace nesr;
 using namespace nesr::png;
+using codec::be32;
+using codec::crc32;
 
 namespace {
 
@@ -20,36 +22,15 @@ bool plan(int H, int W, int C, int depth, Plan* p) {
     p->row = 1 + (int64_t)W * p->bpp;
     p->N = (int64_t)H * p->row;
     p->nchunks = (p->N + CHUNK - 1) / CHUNK;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
-    p->off_filt = take((size_t)p->N);
-    p->off_slot = take((size_t)p->nchunks * SLOT);
-    p->off_size = take((size_t)p->nchunks * 8);
-    p->off_offs = take((size_t)p->nchunks * 8);
-    p->off_adler = take((size_t)p->nchunks * 8);
-    p->off_meta = take(256);
-    p->total = at;
+    ScratchCarver ws;
+    p->off_filt = ws.take((size_t)p->N);
+    p->off_slot = ws.take((size_t)p->nchunks * SLOT);
+    p->off_size = ws.take((size_t)p->nchunks * 8);
+    p->off_offs = ws.take((size_t)p->nchunks * 8);
+    p->off_adler = ws.take((size_t)p->nchunks * 8);
+    p->off_meta = ws.take(256);
+    p->total = ws.total();
     return true;
-}
-
-uint32_t crc32(const uint8_t* p, int n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (int i = 0; i < n; ++i) {
-        c ^= p[i];
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-    }
-    return ~c;
-}
-
-void be32(uint8_t* p, uint32_t v) {
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
 }
 
 // signature, IHDR, IDAT[78 01]
@@ -116,16 +97,16 @@ int nesr_png_code_lengths(const uint32_t* counts, int n, int limit, uint8_t* len
 int nesr_png_encode(int device_id, const void* src_dev, int64_t src_row_bytes, int H, int W, int C, int depth, int order, void* scratch_dev,
                     size_t scratch_bytes, uint8_t* out_dev, size_t out_cap, uint64_t* out_len_dev, void* stream) {
     if (!src_dev || !scratch_dev || !out_dev || !out_len_dev) return set_error(NESR_ERR_ARG, "nesr_png_encode: null argument");
-    const int rc = check_shape("nesr_png_encode", H, W, C, depth);
+    const char* who = "nesr_png_encode";
+    int rc = check_shape(who, H, W, C, depth);
+    if (rc == NESR_OK) rc = codec::check_order(who, order);
     if (rc != NESR_OK) return rc;
-    if (order != NESR_ORDER_RGB && order != NESR_ORDER_BGR) return set_error(NESR_ERR_ARG, "nesr_png_encode: order must be NESR_ORDER_RGB or NESR_ORDER_BGR");
     Plan p;
     plan(H, W, C, depth, &p);
-    if (src_row_bytes < (int64_t)W * p.bpp) return set_error(NESR_ERR_ARG, "nesr_png_encode: the row stride is smaller than a row");
-    if (scratch_bytes < p.total)
-        return set_error(NESR_ERR_ARG, "nesr_png_encode: scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(p.total) + " needed");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15) return set_error(NESR_ERR_ARG, "nesr_png_encode: the scratch must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out_len_dev) & 7) return set_error(NESR_ERR_ARG, "nesr_png_encode: out_len_dev must be 8-byte aligned");
+    rc = codec::check_row_stride(who, src_row_bytes, (int64_t)W * p.bpp);
+    if (rc == NESR_OK) rc = codec::check_scratch(who, scratch_dev, scratch_bytes, p.total);
+    if (rc == NESR_OK) rc = codec::check_word_alignment(who, "out_len_dev", out_len_dev, 8);
+    if (rc != NESR_OK) return rc;
     EncodeArgs a{};
     a.src = static_cast<const uint8_t*>(src_dev);
     a.src_stride = src_row_bytes;

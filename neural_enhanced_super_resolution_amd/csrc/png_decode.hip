@@ -16,6 +16,7 @@
 // before the destination, so lane i takes byte (i mod distance) of the source and an overlapped copy repeats -- and the window is
 // flushed to the stream by all lanes.  Matches therefore never read back what the wave stored to global memory: LDS operations of one
 // wave execute in order, and the barrier between lane 0's turn and the copy is a workgroup barrier of one wave.
+#include "codec_device.h"
 #include "png_decode_kernels.h"
 
 namespace nesr {
@@ -430,30 +431,17 @@ __global__ __launch_bounds__(1024) void pngd_scan(const uint64_t* size, const ui
     __shared__ uint32_t bits;
     const int tid = threadIdx.x;
     if (tid == 0) bits = 0;
-    uint64_t carry = 0;
     uint32_t mine = 0;
-    for (int64_t base = 0; base < n; base += 1024) {
-        const int64_t i = base + tid;
-        const uint64_t v = i < n ? size[i] : 0;
-        if (i < n) mine |= segst[i];
-        int cur = 0;
-        buf[0][tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            const uint64_t x = buf[cur][tid] + (tid >= d ? buf[cur][tid - d] : 0);
-            buf[cur ^ 1][tid] = x;
-            cur ^= 1;
-            __syncthreads();
-        }
-        const uint64_t incl = buf[cur][tid];
-        const uint64_t sum = buf[cur][1023];
-        if (i < n) offs[i] = carry + incl - v;
-        carry += sum;
-        __syncthreads();
-    }
+    const uint64_t total = codec::group_scan_1024<uint64_t>(
+        n, buf,
+        [&](int64_t i) {
+            mine |= segst[i];
+            return size[i];
+        },
+        [&](int64_t i, uint64_t x) { offs[i] = x; });
     if (mine) atomicOr(&bits, mine);
     __syncthreads();
-    if (tid == 0) *status = bits ? bits : (carry != (uint64_t)N ? ST_TOTAL : 0u);
+    if (tid == 0) *status = bits ? bits : (total != (uint64_t)N ? ST_TOTAL : 0u);
 }
 
 __global__ void pngd_clear(uint32_t* status) { *status = 0; }
@@ -486,30 +474,10 @@ __global__ __launch_bounds__(256) void pngd_adler(const uint8_t* filt, int64_t N
 // Adler-32 of the stream from the pieces' sums: a' = a + s1, b' = b + n a + s2 (mod 65521); each lane folds a run of pieces from
 // (0, 0), lane 0 chains the runs.  A mismatch with the file's value sets ADLER.
 __global__ __launch_bounds__(256) void pngd_adler_check(const uint64_t* adler, int64_t npieces, int64_t N, uint32_t expect, uint32_t* status) {
-    __shared__ uint32_t seg_a[256], seg_b[256], seg_n[256];
     if (*status != 0) return;
-    const int tid = threadIdx.x;
-    const int64_t per = (npieces + 255) / 256;
-    const int64_t c0 = min(npieces, tid * per), c1 = min(npieces, c0 + per);
-    uint32_t A = 0, B = 0;
-    for (int64_t c = c0; c < c1; ++c) {
-        const uint64_t v = adler[c];
-        const uint32_t n = (uint32_t)min((int64_t)ADLER_PIECE, N - c * ADLER_PIECE);
-        B = (B + n * A + (uint32_t)(v >> 32)) % 65521u;
-        A = (A + (uint32_t)v) % 65521u;
-    }
-    seg_a[tid] = A;
-    seg_b[tid] = B;
-    seg_n[tid] = (uint32_t)((min(N, c1 * ADLER_PIECE) - min(N, c0 * ADLER_PIECE)) % 65521);
-    __syncthreads();
-    if (tid == 0) {
-        A = 1, B = 0;
-        for (int t = 0; t < 256; ++t) {
-            B = (B + (uint32_t)(((uint64_t)seg_n[t] * A) % 65521u) + seg_b[t]) % 65521u;
-            A = (A + seg_a[t]) % 65521u;
-        }
-        if (((B << 16) | A) != expect) atomicOr(status, ST_ADLER);
-    }
+    codec::adler_fold<ADLER_PIECE, 256>(adler, npieces, N, [&](uint32_t got) {
+        if (got != expect) atomicOr(status, ST_ADLER);
+    });
 }
 
 // One workgroup per row; only the workgroup of a row that starts a group works (row 0, and rows of type 0 or 1: they need nothing from

@@ -2,26 +2,17 @@
 // and nesr_png_unfilter (kernels of png_decode.hip).  What a caller of the reference gets from cv2.imread(path.png,
 // cv2.IMREAD_UNCHANGED) (standalone/direct_esrgan.py:130): gray, colour or colour + alpha, 8 or 16 bit.  tests/png_decode_ref.py is
 // the specification of the parser and of the segment plan.
-#include "api_common.h"
+#include "codec_host.h"
 #include "png_decode_kernels.h"
 
 using namespace nesr;
 using namespace nesr::pngdec;
+using codec::be32;
+using codec::crc32;
 
 namespace {
 
 int bad(const char* what) { return set_error(NESR_ERR_BADFILE, std::string("nesr_png_parse: ") + what); }
-
-uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
-
-uint32_t crc32(const uint8_t* p, size_t n) {
-    uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; ++i) {
-        c ^= p[i];
-        for (int k = 0; k < 8; ++k) c = (c & 1) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-    }
-    return ~c;
-}
 
 bool is(const uint8_t* p, const char* kind) { return p[0] == (uint8_t)kind[0] && p[1] == (uint8_t)kind[1] && p[2] == (uint8_t)kind[2] && p[3] == (uint8_t)kind[3]; }
 
@@ -70,32 +61,23 @@ bool plan(const nesr_png_info* info, Plan* p) {
     if (info->n_segments < 1) return false;
     p->nseg = info->n_segments;
     p->npieces = (p->N + ADLER_PIECE - 1) / ADLER_PIECE;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
-    p->off_filt = take((size_t)p->N);
-    p->off_carry = take((size_t)info->H * (size_t)(p->row - 1));
-    p->off_size = take((size_t)p->nseg * 8);
-    p->off_offs = take((size_t)p->nseg * 8);
-    p->off_segst = take((size_t)p->nseg * 4);
-    p->off_adler = take((size_t)p->npieces * 8);
-    p->total = at;
+    ScratchCarver ws;
+    p->off_filt = ws.take((size_t)p->N);
+    p->off_carry = ws.take((size_t)info->H * (size_t)(p->row - 1));
+    p->off_size = ws.take((size_t)p->nseg * 8);
+    p->off_offs = ws.take((size_t)p->nseg * 8);
+    p->off_segst = ws.take((size_t)p->nseg * 4);
+    p->off_adler = ws.take((size_t)p->npieces * 8);
+    p->total = ws.total();
     return true;
 }
 
-int check_dst(const char* who, const Plan& p, const void* dst, int64_t dst_row_bytes, int order, const void* scratch, size_t scratch_bytes, size_t need,
-              const uint32_t* status) {
-    const std::string w(who);
-    if (order != NESR_ORDER_RGB && order != NESR_ORDER_BGR) return set_error(NESR_ERR_ARG, w + ": order must be NESR_ORDER_RGB or NESR_ORDER_BGR");
-    if (dst_row_bytes < (int64_t)p.W * p.bpp) return set_error(NESR_ERR_ARG, w + ": the row stride is smaller than a row");
-    if (scratch_bytes < need) return set_error(NESR_ERR_ARG, w + ": scratch of " + std::to_string(scratch_bytes) + " bytes, " + std::to_string(need) + " needed");
-    if (reinterpret_cast<uintptr_t>(scratch) & 15) return set_error(NESR_ERR_ARG, w + ": the scratch must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(status) & 3) return set_error(NESR_ERR_ARG, w + ": status_dev must be 4-byte aligned");
-    (void)dst;
-    return NESR_OK;
+int check_dst(const char* who, const Plan& p, int64_t dst_row_bytes, int order, const void* scratch, size_t scratch_bytes, size_t need, const uint32_t* status) {
+    int rc = codec::check_order(who, order);
+    if (rc == NESR_OK) rc = codec::check_row_stride(who, dst_row_bytes, (int64_t)p.W * p.bpp);
+    if (rc == NESR_OK) rc = codec::check_scratch(who, scratch, scratch_bytes, need);
+    if (rc == NESR_OK) rc = codec::check_word_alignment(who, "status_dev", status, 4);
+    return rc;
 }
 
 UnfilterArgs unfilter_args(const Plan& p, const uint8_t* filt, uint8_t* carry, void* dst, int64_t dst_row_bytes, int order, uint32_t* status, int gate) {
@@ -215,9 +197,9 @@ int nesr_png_decode(int device_id, const uint8_t* file_dev, size_t n, const nesr
     Plan p;
     if (!plan(info, &p)) return set_error(NESR_ERR_ARG, "nesr_png_decode: the info does not describe a supported frame (fill it with nesr_png_parse)");
     if (!info->contiguous) return set_error(NESR_ERR_ARG, "nesr_png_decode: a segment spans an IDAT boundary (inflate on the host, then nesr_png_unfilter)");
-    const int rc = check_dst("nesr_png_decode", p, dst_dev, dst_row_bytes, order, scratch_dev, scratch_bytes, p.total, status_dev);
+    int rc = check_dst("nesr_png_decode", p, dst_row_bytes, order, scratch_dev, scratch_bytes, p.total, status_dev);
+    if (rc == NESR_OK) rc = codec::check_word_alignment("nesr_png_decode", "segs_dev", segs_dev, 8);
     if (rc != NESR_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(segs_dev) & 7) return set_error(NESR_ERR_ARG, "nesr_png_decode: segs_dev must be 8-byte aligned");
     uint8_t* s = static_cast<uint8_t*>(scratch_dev);
     InflateArgs a{};
     a.file = file_dev;
@@ -252,7 +234,7 @@ int nesr_png_unfilter(int device_id, const uint8_t* filtered_dev, int H, int W, 
     Plan p;
     if (!plan(&info, &p)) return set_error(NESR_ERR_ARG, "nesr_png_unfilter: 1 .. 65535 rows and columns, 1, 3 or 4 channels, depth 8 or 16");
     const size_t need = align_up((size_t)H * (size_t)(p.row - 1), 256);
-    const int rc = check_dst("nesr_png_unfilter", p, dst_dev, dst_row_bytes, order, scratch_dev, scratch_bytes, need, status_dev);
+    const int rc = check_dst("nesr_png_unfilter", p, dst_row_bytes, order, scratch_dev, scratch_bytes, need, status_dev);
     if (rc != NESR_OK) return rc;
     NESR_TRY(hipSetDevice(device_id));
     NESR_TRY(launch_unfilter(unfilter_args(p, filtered_dev, static_cast<uint8_t*>(scratch_dev), dst_dev, dst_row_bytes, order, status_dev, 0),

@@ -118,18 +118,13 @@ struct Plan {
 
 Plan plan(const nesr_sdx4* p, int n, int h, int w, int tokens) {
     Plan pl;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
+    ScratchCarver ws;
     const size_t hw = (size_t)h * w;
-    pl.text = take((size_t)n * tokens * sdx4_text_info(p->text).hidden * 4);
-    pl.sample = take((size_t)n * (p->lc + SDX4_IMAGE_CHANNELS) * hw * 4);
-    pl.model = take((size_t)n * p->lc * hw * 4);
-    pl.latents = take((size_t)p->lc * hw * 4);
-    pl.total = at;
+    pl.text = ws.take((size_t)n * tokens * sdx4_text_info(p->text).hidden * 4);
+    pl.sample = ws.take((size_t)n * (p->lc + SDX4_IMAGE_CHANNELS) * hw * 4);
+    pl.model = ws.take((size_t)n * p->lc * hw * 4);
+    pl.latents = ws.take((size_t)p->lc * hw * 4);
+    pl.total = ws.total();
     return pl;
 }
 

@@ -146,12 +146,7 @@ struct Plan {
 Plan plan(const nesr_unet* c, int n, int h, int w, int tokens) {
     const int L = c->levels;
     Plan p;
-    size_t at = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = at;
-        at += align_up(bytes, 256);
-        return o;
-    };
+    ScratchCarver ws;
     auto px = [&](int l) { return (size_t)n * (h >> l) * (w >> l); };
     auto wp = [&](int l) { return (size_t)round_up(c->width[l], 16); };
     size_t act = 0, tf = 0, maxwp = 0, tfw = 0;
@@ -160,23 +155,23 @@ Plan plan(const nesr_unet* c, int n, int h, int w, int tokens) {
         maxwp = std::max(maxwp, wp(l));
         if (c->attn[l] || c->up_attn[l] || l == L - 1) tf = std::max(tf, px(l) * wp(l)), tfw = std::max(tfw, wp(l));
     }
-    p.x0 = take(act * 4), p.x1 = take(act * 4), p.t1 = take(act * 4), p.t2 = take(act * 4);
-    p.h = take(tf * 4), p.a = take(tf * 4), p.q = take(tf * 16);
-    p.kv = take((size_t)n * tokens * 2 * tfw * 4);
-    p.text = take((size_t)n * tokens * round_up(c->cross, 16) * 4);
-    p.in = take(px(0) * round_up(c->cin, 16) * 4);
+    p.x0 = ws.take(act * 4), p.x1 = ws.take(act * 4), p.t1 = ws.take(act * 4), p.t2 = ws.take(act * 4);
+    p.h = ws.take(tf * 4), p.a = ws.take(tf * 4), p.q = ws.take(tf * 16);
+    p.kv = ws.take((size_t)n * tokens * 2 * tfw * 4);
+    p.text = ws.take((size_t)n * tokens * round_up(c->cross, 16) * 4);
+    p.in = ws.take(px(0) * round_up(c->cin, 16) * 4);
     const size_t blocks = unet_gn_blocks((size_t)h * w);
-    for (int s = 0; s < 2; ++s) p.partial[s] = take((size_t)n * blocks * maxwp * 2 * sizeof(double));
-    for (int s = 0; s < 2; ++s) p.norm[s] = take((size_t)n * maxwp * sizeof(VaeNorm));
-    p.ln = take(px(0) * sizeof(float4));
-    p.semb = take((size_t)round_up(td_of(c), 16) * 4);
-    p.temb = take((size_t)UNET_MAX_RESNETS * UNET_MAX_WIDTH * 4);
-    p.skip.push_back(take(px(0) * wp(0) * 4));      // conv_in
+    for (int s = 0; s < 2; ++s) p.partial[s] = ws.take((size_t)n * blocks * maxwp * 2 * sizeof(double));
+    for (int s = 0; s < 2; ++s) p.norm[s] = ws.take((size_t)n * maxwp * sizeof(VaeNorm));
+    p.ln = ws.take(px(0) * sizeof(float4));
+    p.semb = ws.take((size_t)round_up(td_of(c), 16) * 4);
+    p.temb = ws.take((size_t)UNET_MAX_RESNETS * UNET_MAX_WIDTH * 4);
+    p.skip.push_back(ws.take(px(0) * wp(0) * 4));      // conv_in
     for (int i = 0; i < L; ++i) {
-        for (int j = 0; j < c->layers; ++j) p.skip.push_back(take(px(i) * wp(i) * 4));
-        if (i < L - 1) p.skip.push_back(take(px(i + 1) * wp(i) * 4));
+        for (int j = 0; j < c->layers; ++j) p.skip.push_back(ws.take(px(i) * wp(i) * 4));
+        if (i < L - 1) p.skip.push_back(ws.take(px(i + 1) * wp(i) * 4));
     }
-    p.total = at;
+    p.total = ws.total();
     return p;
 }
 

@@ -814,33 +814,36 @@ def ensemble_results(images, use_hip=None):
 
 
 # ----------------------------------------------------------------------------------------------- JPEG
+def _encode_file_hip(frame, entry, args, need, cap, who):
+    """One run of a file encoder's entry, `args` then the scratch of `need` bytes, the buffer of `cap` bytes and the two words
+    -> the file's bytes; NesrNoFitError (with the size the device reported) when the file needs more.  Two transfers come back: the
+    16 bytes of the length and status words, then exactly the file."""
+    from . import _lib
+    scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
+    out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
+    words = torch.empty(2, dtype=torch.int64, device=frame.device)
+    _hip_call(frame, entry, *args, _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+    length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
+    if status != 0:
+        raise _lib.NesrNoFitError(length, cap, who)
+    return out[:length].cpu().numpy().tobytes()               # D2H: the file
+
+
 def _jpeg_encode_hip(frame, quality, bgr, cap, options=None):
-    """One run of nesr_jpeg_encode_u8 (csrc/jpeg.hip) into a buffer of `cap` bytes -> the file's bytes; NesrNoFitError (with the
-    size the device reported) when the file needs more.  Two transfers come back: the 16 bytes of the length and status words,
-    then exactly the file.  options: (sampling, optimize, restart_interval) for nesr_jpeg_encode_ex_u8, None for the defaults."""
+    """One run of nesr_jpeg_encode_u8 (csrc/jpeg.hip) into a buffer of `cap` bytes -> the file's bytes (_encode_file_hip).
+    options: (sampling, optimize, restart_interval) for nesr_jpeg_encode_ex_u8, None for the defaults."""
     from . import _lib
     h, w, c = frame.shape
     lib = _lib.load()
-    words = torch.empty(2, dtype=torch.int64, device=frame.device)
     if options is None:
-        need = int(lib.nesr_jpeg_scratch_bytes(h, w, c))
-        scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
-        out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
-        _hip_call(frame, "nesr_jpeg_encode_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, int(quality),
-                  _ptr(scratch), need, _ptr(out), cap, _ptr(words))
+        entry, opt, need = "nesr_jpeg_encode_u8", int(quality), int(lib.nesr_jpeg_scratch_bytes(h, w, c))
     else:
         import ctypes
         sampling, optimize, restart_interval = options
         opts = _lib.JpegOpts(int(quality), _lib.JPEG_SAMPLING[sampling], int(bool(optimize)), int(restart_interval))
-        need = int(lib.nesr_jpeg_scratch_bytes_ex(h, w, c, ctypes.byref(opts)))
-        scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
-        out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
-        _hip_call(frame, "nesr_jpeg_encode_ex_u8", _ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, ctypes.byref(opts),
-                  _ptr(scratch), need, _ptr(out), cap, _ptr(words))
-    length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
-    if status != 0:
-        raise _lib.NesrNoFitError(length, cap)
-    return out[:length].cpu().numpy().tobytes()               # D2H: the file
+        entry, opt, need = "nesr_jpeg_encode_ex_u8", ctypes.byref(opts), int(lib.nesr_jpeg_scratch_bytes_ex(h, w, c, ctypes.byref(opts)))
+    args = (_ptr(frame), _row_bytes(frame), h, w, c, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB, opt)
+    return _encode_file_hip(frame, entry, args, need, cap, "nesr_jpeg_encode_u8")
 
 
 def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None, *, sampling="4:2:0", optimize=False, restart_interval=0):
@@ -910,23 +913,15 @@ def encode_jpeg_u8(frame, quality=95, order="rgb", use_hip=None, *, sampling="4:
 # ----------------------------------------------------------------------------------------------- PNG
 def _png_encode_hip(frame, depth, bgr, cap=None):
     """One run of nesr_png_encode (csrc/png.hip) on an [H, W, C] device tensor (uint8, or 16-bit samples in 2-byte elements) into a
-    buffer of `cap` bytes (default nesr_png_bound, which always fits) -> the file's bytes; NesrNoFitError when the file needs more.
-    Two transfers come back: the 16 bytes of the length and status words, then exactly the file."""
+    buffer of `cap` bytes (default nesr_png_bound, which always fits) -> the file's bytes (_encode_file_hip)."""
     from . import _lib
     h, w, c = frame.shape
     lib = _lib.load()
     need = int(lib.nesr_png_scratch_bytes(h, w, c, depth))
     if cap is None:
         cap = int(lib.nesr_png_bound(h, w, c, depth))
-    scratch = torch.empty(need, dtype=torch.uint8, device=frame.device)
-    out = torch.empty(cap, dtype=torch.uint8, device=frame.device)
-    words = torch.empty(2, dtype=torch.int64, device=frame.device)
-    _hip_call(frame, "nesr_png_encode", _ptr(frame), _row_bytes(frame), h, w, c, depth, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB,
-              _ptr(scratch), need, _ptr(out), cap, _ptr(words))
-    length, status = (int(v) for v in words.cpu())            # D2H: 16 bytes (waits for the encode)
-    if status != 0:
-        raise _lib.NesrNoFitError(length, cap, "nesr_png_encode")
-    return out[:length].cpu().numpy().tobytes()               # D2H: the file
+    args = (_ptr(frame), _row_bytes(frame), h, w, c, depth, _lib.ORDER_BGR if bgr else _lib.ORDER_RGB)
+    return _encode_file_hip(frame, "nesr_png_encode", args, need, cap, "nesr_png_encode")
 
 
 def _png_chunk(kind, payload):

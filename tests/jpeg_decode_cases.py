@@ -6,6 +6,7 @@ from __future__ import annotations
 import functools
 import io
 import os
+import re
 
 import numpy as np
 
@@ -19,6 +20,16 @@ SUBSEQ_BITS = 1024            # bits of the unstuffed stream per lane of the sel
 SUBSEQ_PER_GROUP = 256        # lanes (subsequences) per workgroup of that decode
 RECON_BLOCKS = 32             # blocks per workgroup of the reconstruction (dequantise, IDCT)
 UNSTUFF_CHUNK = 4096          # bytes of the scan per workgroup of the scan preparation
+
+
+def kernel_constant(header, name):
+    """`constexpr int NAME = value;` as csrc/<header> states it today: what a test's claim that a file reaches a path is measured by"""
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "neural_enhanced_super_resolution_amd", "csrc", header)
+    with open(path) as f:
+        return int(re.search(rf"constexpr int {name} = (\d+);", f.read()).group(1))
+
+
+SCAN_LANES = 1024             # values per step of the single-workgroup scans (csrc/codec_device.h: group_scan_1024)
 
 SHAPES = [(1, 1), (8, 8), (7, 25), (17, 33), (24, 16), (8, 16), (40, 56), (37, 53), (64, 96)]
 CONTENTS = ["noise", "impulses", "constant", jpeg_cases.CROP]
@@ -60,6 +71,31 @@ BOUNDARY = [("noise", 96, 1024, 3, 2, 95, {}), ("constant", 96, 1024, 3, 2, 95, 
 
 def cases():
     return _grid()
+
+
+def _pillow_gray(img, quality):
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(img).save(buf, format="JPEG", quality=quality)
+    data = buf.getvalue()
+    return data, np.asarray(Image.open(io.BytesIO(data)))
+
+
+# Two files beyond the grid, each the smallest that makes one of the decoder's single-workgroup scans take a second step of 1024 values
+# (test_jpeg_decode_spec.py asserts it from the header).  -> (id, bytes, Pillow's pixels: the specification is pinned to them and is
+# too slow at these sizes)
+@functools.lru_cache(maxsize=None)
+def long_scan():
+    """Gray noise 2200 x 2048 at quality 95: a scan of over 1024 unstuff chunks (jd_scan_chunks carries)"""
+    img = np.random.RandomState(2200).randint(0, 256, (2200, 2048)).astype(np.uint8)
+    return ("noise-2200x2048x1-q95-plain",) + _pillow_gray(img, 95)
+
+
+@functools.lru_cache(maxsize=None)
+def many_mcus():
+    """Gray 4104 x 4104 of 16 x 16 squares: 513 x 513 MCUs, over 1024 groups of the DC prefix sum (jd_dc_scan carries)"""
+    y, x = np.ogrid[:4104, :4104]
+    return ("squares-4104x4104x1-q50-plain",) + _pillow_gray(((y // 16 + x // 16) % 256).astype(np.uint8), 50)
 
 
 def image_rgb(kind, h, w, c):

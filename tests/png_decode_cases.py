@@ -17,6 +17,7 @@ import zlib
 import numpy as np
 
 from tests import png_cases, png_decode_ref as ref, png_ref
+from tests.jpeg_decode_cases import SCAN_LANES, kernel_constant  # noqa: F401
 
 KINDS = png_cases.KINDS
 STRATEGIES = [("l0", 0, zlib.Z_DEFAULT_STRATEGY), ("l1", 1, zlib.Z_DEFAULT_STRATEGY), ("l6", 6, zlib.Z_DEFAULT_STRATEGY), ("l9", 9, zlib.Z_DEFAULT_STRATEGY),
@@ -136,6 +137,27 @@ def far_match():
     filt = np.zeros((96, 992), np.uint8)
     filt[:, 1:] = frame
     return "96x991x1x8-period31744", make_file(96, 991, 1, 8, deflate_parts(filt.tobytes(), level=9)), frame
+
+
+# Two files beyond the grid, each the smallest that makes one loop of the all-device route take a second turn
+# (test_png_decode_spec.py asserts it from the parsed plan) -> (id, bytes, frame)
+@functools.lru_cache(maxsize=None)
+def many_segments():
+    """Gray noise 64 x 1040 with a Z_FULL_FLUSH every 64 bytes: over 1024 contiguous segments (pngd_scan carries across a step)"""
+    frame = np.random.RandomState(1040).randint(0, 256, (64, 1040)).astype(np.uint8)
+    parts = deflate_parts(filtered_cycle(frame).tobytes(), flush="full", every=64)
+    return "64x1040x1x8-noise-full64", make_file(64, 1040, 1, 8, parts), frame
+
+
+@functools.lru_cache(maxsize=None)
+def many_pieces():
+    """Gray 2049 x 4100 of 8 x 8 squares, level 1 with a Z_FULL_FLUSH every 32768 bytes: a filtered stream of 257 Adler pieces, two per
+    lane of pngd_adler_check.  Every row has filter type 0; the frame itself is what the lossless file holds."""
+    y, x = np.ogrid[:2049, :4100]
+    frame = ((y // 8 + x // 8 + 41) % 256).astype(np.uint8)
+    filt = np.zeros((2049, 4101), np.uint8)
+    filt[:, 1:] = frame
+    return "2049x4100x1x8-squares-full32768", make_file(2049, 4100, 1, 8, deflate_parts(filt.tobytes(), level=1, flush="full", every=32768)), frame
 
 
 # ------------------------------------------------------------------------------------------------ hand-made streams

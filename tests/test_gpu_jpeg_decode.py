@@ -49,6 +49,24 @@ def test_kernel_pixels_equal_the_specification(cuda_device, case):
         assert (host == 201).all(), "bytes outside the window were written"
 
 
+LONG = [dc.long_scan, dc.many_mcus]
+
+
+@pytest.mark.parametrize("build", LONG, ids=[b.__name__ for b in LONG])
+def test_long_files_take_a_second_step_of_the_scans(cuda_device, build):
+    """A scan of more than 1024 unstuff chunks (jd_scan_chunks carries) and a frame of more than 1024 DC groups (jd_dc_scan carries),
+    against Pillow's pixels (tests/test_jpeg_decode_spec.py pins the specification to them); the path is asserted from the host parser
+    so that a changed constant cannot leave it untested"""
+    from neural_enhanced_super_resolution_amd import _lib, imgproc
+    cid, data, want = build()
+    info = _lib.jpeg_parse(data)
+    nchunks = -(-info.scan_bytes // dc.kernel_constant("jpeg_decode_kernels.h", "UNSTUFF_CHUNK"))
+    dc_groups = -(-(info.mcus_x * info.mcus_y) // dc.kernel_constant("jpeg_decode_kernels.h", "DC_GROUP"))
+    assert info.restart_interval == 0 and (nchunks if build is dc.long_scan else dc_groups) > dc.SCAN_LANES
+    got = imgproc.decode_jpeg_u8(data, device=cuda_device, use_hip=True).cpu().numpy()
+    assert np.array_equal(got, want), _where(got, want)
+
+
 # ------------------------------------------------------------------------------------------------ 8: the reference's asset
 def test_reference_asset(cuda_device):
     """512 x 512, 4:2:0, DRI = 32, tables from the file: the pixels the reference's own read recorded."""

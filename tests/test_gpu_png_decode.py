@@ -68,6 +68,21 @@ def test_foreign_files_both_routes(cuda_device, case):
             imgproc.decode_png(data, order=order, device=cuda_device, inflate="device")
 
 
+LONG = [cases.many_segments, cases.many_pieces]
+
+
+@pytest.mark.parametrize("build", LONG, ids=[b.__name__ for b in LONG])
+def test_long_files_take_a_second_turn_of_the_scan_and_of_the_adler_fold(cuda_device, build):
+    """More than 1024 segments (pngd_scan carries across a step) and more than 256 Adler pieces (two per lane of pngd_adler_check),
+    all-device route; the path is asserted from the host parser so that a changed constant cannot leave it untested"""
+    from neural_enhanced_super_resolution_amd import _lib, imgproc
+    cid, data, frame = build()
+    info, _ = _lib.png_parse(data)
+    npieces = -(-info.stream_bytes // cases.kernel_constant("png_decode_kernels.h", "ADLER_PIECE"))
+    assert info.contiguous and (info.n_segments > cases.SCAN_LANES if build is cases.many_segments else npieces > 256)
+    assert _equal(imgproc.decode_png(data, device=cuda_device, inflate="device"), frame, "rgb")
+
+
 SYNC = [c for c in FOREIGN if "sync" in c[0]]
 
 

@@ -113,6 +113,20 @@ def test_the_boundary_files_cross_the_kernels_constants():
     assert many["restart_intervals"] > 2 * 64
 
 
+def test_the_long_files_reach_the_second_step_of_the_scans(lib):
+    """What tests/jpeg_decode_cases.py says of long_scan and many_mcus, from the host parser's fields and the kernels' constants
+    (the plan of csrc/jpeg_decode_api.cpp: nchunks = ceil(scan_bytes / UNSTUFF_CHUNK), dc_groups = ceil(MCUs / DC_GROUP))"""
+    pytest.importorskip("PIL")
+    from neural_enhanced_super_resolution_amd import _lib
+    chunk, group = dc.kernel_constant("jpeg_decode_kernels.h", "UNSTUFF_CHUNK"), dc.kernel_constant("jpeg_decode_kernels.h", "DC_GROUP")
+    info = _lib.jpeg_parse(dc.long_scan()[1])
+    nchunks = -(-info.scan_bytes // chunk)
+    assert info.restart_interval == 0 and nchunks > dc.SCAN_LANES                              # jd_scan_chunks carries
+    info = _lib.jpeg_parse(dc.many_mcus()[1])
+    dc_groups = -(-(info.mcus_x * info.mcus_y) // group)
+    assert info.restart_interval == 0 and dc_groups > dc.SCAN_LANES                            # jd_dc_scan carries (no DRI: the DC prefix sum runs)
+
+
 # ------------------------------------------------------------------------------------------------ 5: parser and argument checks
 def _lookup_all(h):
     """Every 16-bit window through the device's table layout (csrc/jpeg_decode.hip: step) -> length << 8 | symbol, 0 when no code matches."""

@@ -85,6 +85,20 @@ def test_segment_plans():
     assert info["contiguous"] and len(segs) == 3 and segs[0][0] == png_ref.HEAD_BYTES + 8
 
 
+def test_the_long_files_reach_the_second_turn_of_the_device_loops():
+    """What tests/png_decode_cases.py says of many_segments and many_pieces, from the parsed plan and the kernels' constants"""
+    cid, data, frame = cases.many_segments()
+    info, segs = ref.parse(data)
+    assert info["contiguous"] and info["n_segments"] == len(segs) > cases.SCAN_LANES          # pngd_scan: a second step of 1024
+    assert ref.inflate_plan(data, info, segs)[1] == 0 and np.array_equal(ref.decode(data), frame)
+    cid, data, frame = cases.many_pieces()
+    info, segs = ref.parse(data)
+    npieces = -(-info["stream_bytes"] // cases.kernel_constant("png_decode_kernels.h", "ADLER_PIECE"))
+    assert info["contiguous"] and len(segs) >= 2 and npieces > 256                              # pngd_adler_check: 256 lanes, two pieces each
+    filt = np.frombuffer(zlib.decompress(_z(data)), np.uint8).reshape(frame.shape[0], frame.shape[1] + 1)
+    assert not filt[:, 0].any() and np.array_equal(filt[:, 1:], frame)                          # filter type 0: the file holds the frame
+
+
 @pytest.mark.parametrize("cid,data,bit", cases.bad() + cases.corrupt()[:3], ids=[c[0] for c in cases.bad() + cases.corrupt()[:3]])
 def test_bad_input_gets_its_status_bit_and_a_zlib_error(cid, data, bit):
     info, segs = ref.parse(data)

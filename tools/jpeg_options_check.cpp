@@ -20,7 +20,6 @@ int set_error(int code, const std::string& msg) {
 }
 namespace jpeg {
 hipError_t launch_encode(const Plan&, const EncodeArgs&, const Header&, hipStream_t) { return hipErrorNotSupported; }      // never reached here
-hipError_t launch_encode_ex(const Plan&, const EncodeArgs&, const Header&, hipStream_t) { return hipErrorNotSupported; }
 }  // namespace jpeg
 }  // namespace nesr
 
