@@ -1,24 +1,23 @@
-// The x4 diffusion upscaler from a host with no Python and no torch in the process, through the C ABI of libnesr_hip.so
-// (include/nesr_hip.h): builds the text encoder, the UNet and the VAE decoder of a configuration, gives them weights (a flat
-// float32 file that holds the tensors in the order of clip_text_state_dict_spec, unet_state_dict_spec, vae_state_dict_spec one
-// after the other, or "seed:N": synthetic weights from a counter-based generator of this file), and runs one nesr_sdx4_upscale_u8:
-// a binary PPM frame and the prompts' ids in, the x4 frame out as a PPM.  ids [n][tokens] int32 ([negative, prompt] when guidance >
-// 1), noise [3][h][w] and latents [4][h][w] float32 come from raw files, or, for "-", from the same generator (unit normals).
-//   hipcc -O2 --offload-arch=gfx950 -I include examples/sdx4_host.cpp -o build/sdx4_host -ldl
-//   build/sdx4_host path/to/libnesr_hip.so weights.f32|seed:N frame.ppm ids.i32|- noise.f32|- latents.f32|- tokens noise_level steps guidance out.ppm
-//                   [published|crafted]
-// "published": the x4 upscaler's widths as recalled; "crafted": the small pipeline of tests/sdx4_cases.py.
+// The x4 diffusion upscaler over windows from a host with no Python and no torch in the process, through the C ABI of
+// libnesr_hip.so (include/nesr_hip.h): sdx4_host.cpp's contexts and inputs, then nesr_sdx4_tile_plan, nesr_sdx4_tiled_workspace_bytes
+// (neither needs the device) and one nesr_sdx4_upscale_tiled_u8: the denoising loop and the VAE decode over overlapping windows, so
+// the frame may exceed NESR_VAE_MAX_TOKENS low-res pixels.  Its sides must be multiples of 2^(UNet levels - 1).
+//   hipcc -O2 --offload-arch=gfx950 -I include examples/sdx4_tiled_host.cpp -o build/sdx4_tiled_host -ldl
+//   build/sdx4_tiled_host path/to/libnesr_hip.so weights.f32|seed:N frame.ppm ids.i32|- noise.f32|- latents.f32|- tokens noise_level steps guidance out.ppm
+//                         tile tile_overlap [published|crafted [vae_tile vae_overlap]]
 #include "sdx4_host_common.h"
 
 int main(int argc, char** argv) {
-    if (argc < 12) {
+    if (argc < 14) {
         std::fprintf(stderr, "usage: %s libnesr_hip.so weights.f32|seed:N frame.ppm ids.i32|- noise.f32|- latents.f32|- tokens noise_level steps guidance out.ppm "
-                             "[published|crafted]\n", argv[0]);
+                             "tile tile_overlap [published|crafted [vae_tile vae_overlap]]\n", argv[0]);
         return 1;
     }
+    const int tile = std::atoi(argv[12]), tile_overlap = std::atoi(argv[13]);
+    const int vae_tile = argc > 16 ? std::atoi(argv[15]) : 0, vae_overlap = argc > 16 ? std::atoi(argv[16]) : -1;      // 0 and -1: the loop's plan
     const int tokens = std::atoi(argv[7]), noise_level = std::atoi(argv[8]), steps = std::atoi(argv[9]);
     const double guidance = std::atof(argv[10]);
-    const bool crafted = argc > 12 && std::string(argv[12]) == "crafted";
+    const bool crafted = argc > 14 && std::string(argv[14]) == "crafted";
     const bool synthetic = std::strncmp(argv[2], "seed:", 5) == 0;
     const uint64_t seed = synthetic ? std::strtoull(argv[2] + 5, nullptr, 10) : 0;
     const int n = guidance > 1.0 ? 2 : 1, lat = 4, cin = 7;
@@ -39,7 +38,7 @@ int main(int argc, char** argv) {
     LOAD(nesr_last_error) LOAD(nesr_version) LOAD(nesr_clip_text_create) LOAD(nesr_clip_text_destroy) LOAD(nesr_clip_text_num_tensors) LOAD(nesr_clip_text_load_weight)
     LOAD(nesr_clip_text_finalize) LOAD(nesr_unet_create) LOAD(nesr_unet_destroy) LOAD(nesr_unet_num_tensors) LOAD(nesr_unet_load_weight) LOAD(nesr_unet_finalize)
     LOAD(nesr_vae_create) LOAD(nesr_vae_destroy) LOAD(nesr_vae_num_tensors) LOAD(nesr_vae_load_weight) LOAD(nesr_vae_finalize) LOAD(nesr_sdx4_create) LOAD(nesr_sdx4_destroy)
-    LOAD(nesr_sdx4_workspace_bytes) LOAD(nesr_sdx4_upscale_u8) LOAD(nesr_sdx4_launches)
+    LOAD(nesr_sdx4_tile_plan) LOAD(nesr_sdx4_tiled_workspace_bytes) LOAD(nesr_sdx4_upscale_tiled_u8) LOAD(nesr_sdx4_launches)
     std::printf("%s\n", p_nesr_version());
 
     // the configuration
@@ -100,8 +99,13 @@ int main(int argc, char** argv) {
     if (std::string(argv[6]) == "-") for (size_t i = 0; i < latents.size(); ++i) latents[i] = normal(seed, (1u << 20) + 1, i);
     else if (!read_raw(argv[6], latents)) return 1;
 
+    // the plan and the pipeline's own bytes: neither needs the device
+    int tiles_y = 0, tiles_x = 0, ty = 0, tx = 0;
+    CHECK(p_nesr_sdx4_tile_plan(h, w, 1 << (L - 1), tile, tile_overlap, &tiles_y, &tiles_x, &ty, &tx, nullptr, 0));
+    std::vector<int32_t> plan((size_t)2 * tiles_y * tiles_x);
+    CHECK(p_nesr_sdx4_tile_plan(h, w, 1 << (L - 1), tile, tile_overlap, &tiles_y, &tiles_x, &ty, &tx, plan.data(), plan.size()));
     size_t ws = 0;
-    CHECK(p_nesr_sdx4_workspace_bytes(pipe, n, h, w, tokens, &ws));
+    CHECK(p_nesr_sdx4_tiled_workspace_bytes(n, lat, hidden, 4, h, w, tokens, 1 << (L - 1), tile, tile_overlap, vae_tile, vae_overlap, &ws));
     const size_t out_bytes = (size_t)3 * 4 * h * 4 * w;
     uint8_t *d_frame, *d_out;
     float *d_noise, *d_latents;
@@ -114,7 +118,8 @@ int main(int argc, char** argv) {
     HIPCHK(hipMemcpyAsync(d_frame, frame.data(), frame.size(), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_noise, noise.data(), noise.size() * sizeof(float), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_latents, latents.data(), latents.size() * sizeof(float), hipMemcpyHostToDevice, s));
-    CHECK(p_nesr_sdx4_upscale_u8(pipe, d_frame, h, w, ids.data(), tokens, d_noise, d_latents, noise_level, steps, guidance, d_out, out_bytes, nullptr, s));
+    CHECK(p_nesr_sdx4_upscale_tiled_u8(pipe, d_frame, h, w, ids.data(), tokens, d_noise, d_latents, noise_level, steps, guidance, tile, tile_overlap, vae_tile, vae_overlap, d_out,
+                                       out_bytes, nullptr, s));
     std::vector<uint8_t> out(out_bytes);
     HIPCHK(hipMemcpyAsync(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -122,8 +127,9 @@ int main(int argc, char** argv) {
     CHECK(p_nesr_sdx4_launches(pipe, &launches));
     FILE* f = std::fopen(argv[11], "wb");
     if (!f || std::fprintf(f, "P6\n%d %d\n255\n", 4 * w, 4 * h) < 0 || std::fwrite(out.data(), 1, out.size(), f) != out.size() || std::fclose(f) != 0) { std::fprintf(stderr, "cannot write %s\n", argv[11]); return 1; }
-    std::printf("%zu + %zu + %zu tensors, %zu parameters; %d x %d -> %d x %d, %d prompt(s) of %d ids, %d steps in %lld launches, pipeline workspace %zu bytes\n", specs[0].size(),
-                specs[1].size(), specs[2].size(), total, h, w, 4 * h, 4 * w, n, tokens, steps, (long long)launches, ws);
+    std::printf("%zu + %zu + %zu tensors, %zu parameters; %d x %d -> %d x %d, %d x %d windows of %d x %d (last at %d, %d), %d prompt(s) of %d ids, %d steps in %lld launches, "
+                "pipeline workspace %zu bytes\n", specs[0].size(), specs[1].size(), specs[2].size(), total, h, w, 4 * h, 4 * w, tiles_y, tiles_x, ty, tx, plan[plan.size() - 2],
+                plan[plan.size() - 1], n, tokens, steps, (long long)launches, ws);
     HIPCHK(hipStreamDestroy(s));
     HIPCHK(hipFree(d_frame)); HIPCHK(hipFree(d_out)); HIPCHK(hipFree(d_noise)); HIPCHK(hipFree(d_latents));
     p_nesr_sdx4_destroy(pipe);

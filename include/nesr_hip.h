@@ -1186,6 +1186,14 @@ int nesr_swin2sr_part_f32(nesr_swin2sr* ctx, int part, int stage, int layer, con
  * h w may not exceed NESR_VAE_MAX_TOKENS (the attention's limit) nor h s x w s 2^24 pixels: NESR_ERR_ARG.  The workspace grows
  * with the frame (nesr_vae_workspace_bytes says to what; NESR_ERR_NOMEM when it cannot).  No atomics anywhere: a call repeated
  * gives the same bits.  nesr_vae_output_size touches no device and needs no context.
+ *
+ * nesr_vae_decode_latents_tiled_u8 lifts the token limit: the decode over overlapping windows of min(tile, h) x min(tile, w)
+ * latents, blended on the device by the plan, the weights and the kernels of nesr_sdx4_upscale_tiled_u8 below (per window a
+ * gather, the f32 decode with the scaling factor, a blend-add; one finish that normalises and quantises).  h, w, tile and
+ * tile_overlap are multiples of 2, 0 <= tile_overlap < the window's sides, a window holds at most NESR_VAE_MAX_TOKENS latents and
+ * h w at most 2^22; latents_dev is 8-byte aligned, out_dev 4-byte.  One window gives nesr_vae_decode_latents_u8's bytes.  The
+ * context's launch counter and timer see the windows' decodes; the three window kernels (one gather and one blend-add a window,
+ * one finish) are the pipeline's, and in this entry they are neither counted nor timed.
  */
 #define NESR_VAE_NO_DEVICE (-1)
 #define NESR_VAE_MAX_TOKENS (1 << 16)
@@ -1201,6 +1209,8 @@ int nesr_vae_workspace_bytes(nesr_vae* ctx, int h, int w, size_t* bytes);
 int nesr_vae_decode_f32(nesr_vae* ctx, const float* z_dev, int N, int C, int h, int w, float* sample_dev, size_t capacity, void* hip_stream);
 int nesr_vae_decode_latents_u8(nesr_vae* ctx, const float* latents_dev, int N, int C, int h, int w, uint8_t* out_dev, size_t capacity,
                                void* hip_stream);
+int nesr_vae_decode_latents_tiled_u8(nesr_vae* ctx, const float* latents_dev, int N, int C, int h, int w, int tile, int tile_overlap, uint8_t* out_dev,
+                                     size_t capacity, void* hip_stream);
 /* Kernel groups of nesr_vae_kernel_time_ms, as nesr_swin2sr_kernel_time_ms: the 3x3 convs, the GroupNorm statistics, the streamed
  * attention, the 1x1 products (post_quant_conv, shortcuts, q | k | v, to_out, and the latents' transposition), the nearest-x2 convs. */
 enum { NESR_VAE_GROUP_CONV = 0, NESR_VAE_GROUP_NORM = 1, NESR_VAE_GROUP_ATTENTION = 2, NESR_VAE_GROUP_PROJ = 3, NESR_VAE_GROUP_UPSAMPLE = 4,
@@ -1459,7 +1469,8 @@ int nesr_clip_text_k_attention(int samples, int tokens, int heads, int d, const 
  * steps (the first timestep must lie in the table) are checked too: NESR_ERR_ARG before any launch.
  *
  * nesr_sdx4_launches: the kernel launches of the last nesr_sdx4_upscale_u8: text + 1 + steps (UNet + 1) + VAE.
- * nesr_sdx4_set_timing / nesr_sdx4_kernel_time_ms time the pipeline's own two kernels (the networks have their own timers).
+ * nesr_sdx4_set_timing / nesr_sdx4_kernel_time_ms time the pipeline's own kernels (the networks have their own timers): the two of
+ * the untiled call and, in groups 2 .. 6, the five of the tiled one.
  *
  * nesr_sdx4_schedule and nesr_sdx4_noise_coefficients need no context and no device: the tables a pipeline of these fields
  * uses.  timesteps [steps], alpha_bars [steps][2] (at the step, at the previous step), coefficients [steps][6] (c0x, c0m, cex,
@@ -1476,7 +1487,44 @@ int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, c
                          const float* latents_dev, int noise_level, int steps, double guidance_scale, uint8_t* out_dev, size_t capacity,
                          float* latents_out_dev, void* hip_stream);
 int nesr_sdx4_launches(const nesr_sdx4* p, int64_t* launches);
-enum { NESR_SDX4_GROUP_PREPARE = 0, NESR_SDX4_GROUP_STEP = 1, NESR_SDX4_GROUPS = 2 };
+/*
+ * Frames above NESR_VAE_MAX_TOKENS low-res pixels: the denoising loop and the VAE decode over overlapping windows of one shape
+ * (csrc/sdx4_tiled.hip).  The specification is this project's own (MultiDiffusion-style: one shared latent
+ * frame); how diffusers tiles is recalled, not checked, and its enable_vae_tiling blend is not reproduced.
+ *
+ * The plan, per axis of the low-res frame (sides that are multiples of `multiple` = 2^(UNet levels - 1), which must be even): a
+ * window is t = min(tile, n) long; the windows start at 0, t - overlap, ... below n - t, then at n - t (the last one ends at the
+ * edge and is in general not on the stride).  tile and tile_overlap are multiples of `multiple`, 0 <= tile_overlap < t on both
+ * axes, and a window holds at most NESR_VAE_MAX_TOKENS pixels.  Windows run in row-major order and all have the shape ty x tx.  A
+ * window [a, a + t) weighs pixel i of its axis by min(left, right), left = (a > 0 && R > 0) ? min(i - a + 1, R) / R : 1, right =
+ * (a + t < n && R > 0) ? min(a + t - i, R) / R : 1, R = tile_overlap: the sides on the frame's edge are not ramped.  w(y, x) =
+ * w_y(y) w_x(x); a pixel's normaliser is S(y, x) = Sy(y) Sx(x), each the sum of the axis weights of the windows that cover it, in
+ * ascending order.  At the output resolution the same rule holds with origin, length and ramp times the VAE's scale.
+ *
+ * nesr_sdx4_tile_plan needs no device and no context: tiles_y, tiles_x, ty, tx and, unless `plan` is null, one row (y, x) per
+ * window in row-major order (capacity counts integers).  nesr_sdx4_tiled_workspace_bytes needs neither: the pipeline's own bytes
+ * of a tiled call (text states, the full-frame buffer [lc + 3][h w], the accumulator [lc][h w], one window's UNet input and
+ * output, one VAE window's latents and f32 sample, the f32 frame [h s][w s][3]); the networks report their own for the window.
+ *
+ * nesr_sdx4_upscale_tiled_u8: the arguments of nesr_sdx4_upscale_u8 and the two plans; vae_tile 0 stands for tile, vae_overlap
+ * below 0 for tile_overlap.  noise_dev and latents_dev are full-frame draws.  Per step and window: a gather of the window's
+ * UNet input, the UNet forward, an accumulate of w times the guided output; per step one kernel divides by S and takes the DDIM
+ * step.  Then per VAE window: a gather, the f32 decode, a blend-add; one finish kernel divides by S and quantises.  Windows run
+ * one after the other on hip_stream, so there are no atomics and a repeated call gives the same bits; with one window the call
+ * returns nesr_sdx4_upscale_u8's bits.  Checked before any launch (NESR_ERR_ARG naming the value): the multiples, the overlap's
+ * range, the window's token limit, capacity, alignment (noise and latents 16 bytes, frame and output 4), h w at most 2^22.  Once
+ * the workspaces have their size there is no synchronisation, host copy or allocation between the first launch and the last; an
+ * fp16 UNet's range word is cleared once in front and read once behind, as in nesr_sdx4_upscale_u8.
+ * nesr_sdx4_launches after it: text + 1 + steps (windows (1 + UNet + 1) + 1) + vae_windows (1 + VAE + 1) + 1.
+ */
+int nesr_sdx4_tile_plan(int h, int w, int multiple, int tile, int tile_overlap, int* tiles_y, int* tiles_x, int* ty, int* tx, int32_t* plan, size_t capacity);
+int nesr_sdx4_tiled_workspace_bytes(int n, int latent_channels, int text_hidden, int vae_scale, int h, int w, int tokens, int multiple, int tile, int tile_overlap,
+                                    int vae_tile, int vae_overlap, size_t* bytes);
+int nesr_sdx4_upscale_tiled_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, const int32_t* ids_host, int tokens, const float* noise_dev,
+                               const float* latents_dev, int noise_level, int steps, double guidance_scale, int tile, int tile_overlap, int vae_tile,
+                               int vae_overlap, uint8_t* out_dev, size_t capacity, float* latents_out_dev, void* hip_stream);
+enum { NESR_SDX4_GROUP_PREPARE = 0, NESR_SDX4_GROUP_STEP = 1, NESR_SDX4_GROUP_GATHER = 2, NESR_SDX4_GROUP_ACCUMULATE = 3, NESR_SDX4_GROUP_TILED_STEP = 4,
+       NESR_SDX4_GROUP_BLEND_ADD = 5, NESR_SDX4_GROUP_BLEND_FINISH = 6, NESR_SDX4_GROUPS = 7 };
 int nesr_sdx4_set_timing(nesr_sdx4* p, int enable);
 int nesr_sdx4_kernel_time_ms(nesr_sdx4* p, double* group_ms, int n_groups, int64_t* launches);
 int nesr_sdx4_schedule(int num_train_timesteps, double beta_start, double beta_end, const char* beta_schedule, const char* prediction_type,
@@ -1495,6 +1543,22 @@ int nesr_sdx4_k_prepare(const uint8_t* frame_dev, const float* noise_dev, const 
                         float* sample_dev, float* latents_out_dev, void* hip_stream);
 int nesr_sdx4_k_step(const float* model_dev, const float* latents_dev, int n, int hw, int lc, float guidance, const float* coefficients,
                      float* latents_out_dev, float* sample_dev, void* hip_stream);
+/*
+ * Single-launch entries of the five window kernels (csrc/sdx4_api.h documents the launchers' arguments).  `axes`: eight HOST
+ * integers, (n, t, r, a) of the y axis, then of the x axis: the frame's length, the window's, the ramp and the window's origin
+ * (the two kernels that normalise ignore a); the blend kernels take them at the output resolution.  Every n, t and a is even, r
+ * is below t, the float pointers are 8-byte aligned (blend_finish: 16, and x.n a multiple of 4).
+ *   nesr_sdx4_k_window_gather  src [channels][y.n][x.n] -> dst [n][channels][y.t][x.t], every sample the same
+ *   nesr_sdx4_k_accumulate     acc [lc][y.n][x.n] += w (model[0] + g (model[1] - model[0])) (n = 2; n = 1: model[0]) of model [n][lc][y.t][x.t]
+ *   nesr_sdx4_k_tiled_step     m = acc / S, the DDIM step of nesr_sdx4_k_step on channels 0 .. lc - 1 of frame [lc + 3][y.n][x.n], acc <- 0
+ *   nesr_sdx4_k_blend_add      acc [y.n][x.n][3] += w sample [3][y.t][x.t]
+ *   nesr_sdx4_k_blend_finish   out [y.n][x.n][3] u8 = rint(clamp(acc / S / 2 + 0.5, 0, 1) 255)
+ */
+int nesr_sdx4_k_window_gather(const float* src_dev, int n, int channels, const int* axes, float* dst_dev, void* hip_stream);
+int nesr_sdx4_k_accumulate(const float* model_dev, int n, int lc, const int* axes, float guidance, float* acc_dev, void* hip_stream);
+int nesr_sdx4_k_tiled_step(float* acc_dev, float* frame_dev, int lc, const int* axes, const float* coefficients, void* hip_stream);
+int nesr_sdx4_k_blend_add(const float* sample_dev, const int* axes, float* acc_dev, void* hip_stream);
+int nesr_sdx4_k_blend_finish(const float* acc_dev, const int* axes, uint8_t* out_dev, void* hip_stream);
 
 const char* nesr_last_error(void);
 const char* nesr_version(void);

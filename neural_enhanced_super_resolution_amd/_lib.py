@@ -203,6 +203,8 @@ SIGNATURES = {
     "nesr_vae_workspace_bytes": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_size_t)]),
     "nesr_vae_decode_f32": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "nesr_vae_decode_latents_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "nesr_vae_decode_latents_tiled_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t,
+                                                    _c.c_void_p]),
     "nesr_vae_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_vae_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_unet_create": (_c.c_int, [_c.POINTER(_c.c_void_p), _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_char_p),
@@ -271,6 +273,11 @@ SIGNATURES = {
     "nesr_sdx4_upscale_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
                                         _c.c_int, _c.c_double, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
     "nesr_sdx4_launches": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int64)]),
+    "nesr_sdx4_tile_plan": (_c.c_int, [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_int), _c.POINTER(_c.c_int),
+                                       _c.POINTER(_c.c_int), _c.POINTER(_c.c_int32), _c.c_size_t]),
+    "nesr_sdx4_tiled_workspace_bytes": (_c.c_int, [_c.c_int] * 12 + [_c.POINTER(_c.c_size_t)]),
+    "nesr_sdx4_upscale_tiled_u8": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int32), _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                              _c.c_int, _c.c_double, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_size_t, _c.c_void_p, _c.c_void_p]),
     "nesr_sdx4_set_timing": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "nesr_sdx4_kernel_time_ms": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_double), _c.c_int, _c.POINTER(_c.c_int64)]),
     "nesr_sdx4_schedule": (_c.c_int, [_c.c_int, _c.c_double, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_int, _c.c_char_p, _c.c_int,
@@ -280,6 +287,11 @@ SIGNATURES = {
                                        _c.c_void_p, _c.c_void_p]),
     "nesr_sdx4_k_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_float, _c.POINTER(_c.c_float), _c.c_void_p, _c.c_void_p,
                                     _c.c_void_p]),
+    "nesr_sdx4_k_window_gather": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_k_accumulate": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.POINTER(_c.c_int), _c.c_float, _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_k_tiled_step": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int), _c.POINTER(_c.c_float), _c.c_void_p]),
+    "nesr_sdx4_k_blend_add": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
+    "nesr_sdx4_k_blend_finish": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int), _c.c_void_p, _c.c_void_p]),
     "nesr_debug_last_conv_kernel": (_c.c_int, []),
     "nesr_last_error": (_c.c_char_p, []),
     "nesr_version": (_c.c_char_p, []),

@@ -101,11 +101,36 @@ def slid_window_axis(n, tile, tile_pad):
 
 
 def overlap_axis(n, t, overlap):
-    """The starts of one padded axis of Swin2SR's overlapped plan: 0, t - overlap, ... below n - t, then n - t (the last tile ends
-    at n and is in general not on the stride)."""
+    """The starts of one padded axis of Swin2SR's overlapped plan and of the x4 diffusion stage's window plan: 0, t - overlap, ...
+    below n - t, then n - t (the last tile ends at n and is in general not on the stride)."""
     if not (1 <= t <= n and 0 <= overlap < t):
         raise ValueError(f"overlap_axis: 1 <= t <= n and 0 <= overlap < t, got n = {n}, t = {t}, overlap = {overlap}")
     return list(range(0, n - t, t - overlap)) + [n - t]
+
+
+def blend_axis_weight(i, a, t, n, ramp):
+    """The weight window [a, a + t) of an axis of n gives pixel i under the x4 diffusion stage's blend (nesr_sdx4_tile_plan): a ramp
+    of `ramp` pixels on every side that is not on the frame's edge.  A fraction's numerator and denominator: (k, ramp) or (1, 1)."""
+    left = min(i - a + 1, ramp) if a > 0 and ramp > 0 else ramp or 1
+    right = min(a + t - i, ramp) if a + t < n and ramp > 0 else ramp or 1
+    return min(left, right), ramp or 1
+
+
+def sdx4_tile_plan(h, w, multiple, tile, tile_overlap, max_window=1 << 16):
+    """The x4 diffusion stage's window plan of an h x w low-res frame, what nesr_sdx4_tile_plan computes: ((tiles_y, tiles_x), (ty,
+    tx), [(y, x)] in row-major order).  h, w, tile and tile_overlap are multiples of `multiple` (the UNet's frame multiple, even);
+    ty = min(tile, h), tx = min(tile, w); 0 <= tile_overlap < min(ty, tx); a window holds at most `max_window` pixels."""
+    if multiple < 2 or multiple % 2 or h < 1 or w < 1 or h % multiple or w % multiple:
+        raise ValueError(f"sdx4_tile_plan: h and w must be positive multiples of an even frame multiple, got {h} x {w}, multiple {multiple}")
+    if tile < 1 or tile % multiple:
+        raise ValueError(f"sdx4_tile_plan: tile must be a positive multiple of {multiple}, got {tile}")
+    ty, tx = min(tile, h), min(tile, w)
+    if not 0 <= tile_overlap < min(ty, tx) or tile_overlap % multiple:
+        raise ValueError(f"sdx4_tile_plan: tile_overlap must be a multiple of {multiple} in 0 .. {min(ty, tx) - 1}, got {tile_overlap}")
+    if ty * tx > max_window:
+        raise ValueError(f"sdx4_tile_plan: a window of {ty} x {tx} exceeds {max_window} pixels")
+    ys, xs = overlap_axis(h, ty, tile_overlap), overlap_axis(w, tx, tile_overlap)
+    return (len(ys), len(xs)), (ty, tx), [(y, x) for y in ys for x in xs]
 
 
 def overlap_plan(h, w, tile, tile_overlap, window_size, scale):

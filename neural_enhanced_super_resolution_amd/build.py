@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.path.join(HERE, "libnesr_hip.so")
 SOURCES = ["conv3x3_mfma.hip", "conv3x3_bf16.hip", "conv3x3_wino_f32.hip", "conv3x3_f16x2.hip", "rdb_f16x2.hip", "upconv2x2_f16x2.hip", "rdb_bf16_strip.hip", "imgproc.hip", "pack.hip", "nesr12.hip",
-           "srvgg_compact.hip", "segformer.hip", "segformer_pre.hip", "swin2sr.hip", "vae.hip", "unet.hip", "unet_f16.hip", "clip_text.hip", "sdx4_step.hip", "filters.hip", "resize.hip", "frame_io.hip", "band_exchange.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "nesr_api.cpp", "rrdb_forward.cpp", "band_api.cpp", "shard_api.cpp", "oneshot_api.cpp", "compact_api.cpp",
+           "srvgg_compact.hip", "segformer.hip", "segformer_pre.hip", "swin2sr.hip", "vae.hip", "unet.hip", "unet_f16.hip", "clip_text.hip", "sdx4_step.hip", "sdx4_tiled.hip", "filters.hip", "resize.hip", "frame_io.hip", "band_exchange.hip", "jpeg.hip", "jpeg_decode.hip", "png.hip", "png_decode.hip", "nesr_api.cpp", "rrdb_forward.cpp", "band_api.cpp", "shard_api.cpp", "oneshot_api.cpp", "compact_api.cpp",
            "filters_api.cpp", "resize_api.cpp", "frame_api.cpp", "nesr_stage_api.cpp", "segformer_api.cpp", "swin2sr_api.cpp", "vae_api.cpp", "vae_kernel_api.cpp", "unet_api.cpp", "unet_kernel_api.cpp", "unet_f16_kernel_api.cpp", "clip_text_api.cpp", "sdx4_api.cpp", "jpeg_api.cpp", "jpeg_decode_api.cpp", "png_api.cpp", "png_decode_api.cpp"]
 ARCH = "gfx950"
 

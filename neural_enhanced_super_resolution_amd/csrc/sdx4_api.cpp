@@ -1,6 +1,7 @@
 // The x4 diffusion upscaler as one call (nesr_sdx4_*): StableDiffusionUpscalePipeline's loop over the three networks' own entries
 // (nesr_clip_text_encode_f32, nesr_unet_forward_f32, nesr_vae_decode_latents_u8) with the two kernels of sdx4_step.hip between
-// them.  The schedulers' tables are computed here, on the host, in double, and reach the device as a handful of f32 coefficients
+// them; nesr_sdx4_upscale_tiled_u8 runs the same loop and the decode over overlapping windows with the five kernels of
+// sdx4_tiled.hip.  The schedulers' tables are computed here, on the host, in double, and reach the device as a handful of f32 coefficients
 // in a launch's arguments: once the workspaces have their size, nothing is copied, allocated or synchronised between the first
 // launch of a call and the last.  At the end: the single-launch test hooks nesr_sdx4_k_*.
 //
@@ -97,6 +98,22 @@ int make_low_res(const char* entry, std::vector<double>& abar, int T, const char
 
 }  // namespace
 
+// The window plan's rules for one pair (tile, overlap) on an h x w frame whose sides are multiples of `multiple`: ty = min(tile, h),
+// tx = min(tile, w); the message names the value.  `what` is "tile" or "vae_tile".
+int nesr::sdx4_check_windows(const char* entry, const char* what, int h, int w, int multiple, int tile, int overlap, int* ty, int* tx) {
+    const std::string e = std::string(entry) + ": " + what;
+    if (tile < 1 || tile % multiple) return set_error(NESR_ERR_ARG, e + " must be a positive multiple of " + std::to_string(multiple) + ", got " + std::to_string(tile));
+    *ty = std::min(tile, h), *tx = std::min(tile, w);
+    const int t = std::min(*ty, *tx);
+    if (overlap < 0 || overlap >= t || overlap % multiple)
+        return set_error(NESR_ERR_ARG, e + "_overlap must be a multiple of " + std::to_string(multiple) + " in 0 .. " + std::to_string(t - 1) + " (below the window of " +
+                                           std::to_string(*ty) + " x " + std::to_string(*tx) + "), got " + std::to_string(overlap));
+    if ((long long)*ty * *tx > NESR_VAE_MAX_TOKENS)
+        return set_error(NESR_ERR_ARG, e + ": a window of " + std::to_string(*ty) + " x " + std::to_string(*tx) + " exceeds NESR_VAE_MAX_TOKENS = " + std::to_string(NESR_VAE_MAX_TOKENS) +
+                                           " pixels");
+    return NESR_OK;
+}
+
 struct nesr_sdx4 {
     nesr_clip_text* text = nullptr;
     nesr_unet* unet = nullptr;
@@ -107,7 +124,7 @@ struct nesr_sdx4 {
     char* ws_buf = nullptr;
     size_t ws_bytes = 0;
     int64_t last_launches = 0;
-    GroupTimer timer;      // the pipeline's own two kernels
+    GroupTimer timer;      // the pipeline's own kernels
 };
 
 namespace {
@@ -144,9 +161,82 @@ int check_call(nesr_sdx4* p, const char* entry, int n, int h, int w, int tokens)
     return rc;
 }
 
+// the windows of a tiled call, both plans resolved
+struct Windows {
+    int ty, tx, r;          // the denoising loop's
+    int vty, vtx, vr;       // the VAE decode's
+};
+
+struct TiledPlan {
+    size_t text, frame, acc, window, model, vae, total;
+};
+
+// the pipeline's own bytes of a tiled call: the text states, the full-frame buffer [lc + 3][hw], the accumulator [lc][hw], a
+// window's UNet input and output, and the tiled decode's buffers (a window's latents and sample, the f32 frame)
+TiledPlan tiled_plan(int n, int lc, int hidden, int scale, int h, int w, int tokens, const Windows& wd) {
+    TiledPlan pl;
+    ScratchCarver ws;
+    const size_t hw = (size_t)h * w, win = (size_t)wd.ty * wd.tx;
+    pl.text = ws.take((size_t)n * tokens * hidden * 4);
+    pl.frame = ws.take((lc + SDX4_IMAGE_CHANNELS) * hw * 4);
+    pl.acc = ws.take(lc * hw * 4);
+    pl.window = ws.take((size_t)n * (lc + SDX4_IMAGE_CHANNELS) * win * 4);
+    pl.model = ws.take((size_t)n * lc * win * 4);
+    pl.vae = ws.take(sdx4_vae_tiled_plan(lc, scale, h, w, wd.vty, wd.vtx).total);
+    pl.total = ws.total();
+    return pl;
+}
+
+// the frame and both window plans; vae_tile 0 and vae_overlap < 0 stand for tile and tile_overlap
+int check_windows(const char* entry, int h, int w, int multiple, int tile, int tile_overlap, int vae_tile, int vae_overlap, Windows& wd) {
+    const std::string e = entry;
+    if (multiple < 2 || multiple % 2) return set_error(NESR_ERR_ARG, e + ": the frame multiple must be even (a UNet of at least two levels), got " + std::to_string(multiple));
+    if (h < 1 || w < 1 || h % multiple || w % multiple)
+        return set_error(NESR_ERR_ARG, e + ": h and w must be positive multiples of " + std::to_string(multiple) + " (2^(UNet levels - 1)), got " + std::to_string(h) + " x " + std::to_string(w));
+    if ((long long)h * w > SDX4_MAX_FRAME_PIXELS)
+        return set_error(NESR_ERR_ARG, e + ": a frame of " + std::to_string(h) + " x " + std::to_string(w) + " exceeds 2^22 low-res pixels");
+    int rc = sdx4_check_windows(entry, "tile", h, w, multiple, tile, tile_overlap, &wd.ty, &wd.tx);
+    if (rc) return rc;
+    wd.r = tile_overlap;
+    wd.vr = vae_overlap < 0 ? tile_overlap : vae_overlap;
+    return sdx4_check_windows(entry, "vae_tile", h, w, multiple, vae_tile == 0 ? tile : vae_tile, wd.vr, &wd.vty, &wd.vtx);
+}
+
 }  // namespace
 
 extern "C" {
+
+int nesr_sdx4_tile_plan(int h, int w, int multiple, int tile, int tile_overlap, int* tiles_y, int* tiles_x, int* ty, int* tx, int32_t* plan, size_t capacity) {
+    const char* e = "nesr_sdx4_tile_plan";
+    if (!tiles_y || !tiles_x || !ty || !tx) return set_error(NESR_ERR_ARG, "nesr_sdx4_tile_plan: null pointer");
+    Windows wd;
+    const int rc = check_windows(e, h, w, multiple, tile, tile_overlap, 0, -1, wd);
+    if (rc) return rc;
+    const int ky = sdx4_axis_windows(h, wd.ty, wd.r), kx = sdx4_axis_windows(w, wd.tx, wd.r);
+    *tiles_y = ky, *tiles_x = kx, *ty = wd.ty, *tx = wd.tx;
+    if (!plan) return NESR_OK;
+    const size_t need = (size_t)2 * ky * kx;
+    if (capacity < need) return set_error(NESR_ERR_ARG, "nesr_sdx4_tile_plan: the plan needs " + std::to_string(need) + " integers, capacity is " + std::to_string(capacity));
+    for (int iy = 0; iy < ky; ++iy)
+        for (int ix = 0; ix < kx; ++ix) {
+            plan[2 * (iy * kx + ix)] = sdx4_axis_origin(h, wd.ty, wd.r, iy);
+            plan[2 * (iy * kx + ix) + 1] = sdx4_axis_origin(w, wd.tx, wd.r, ix);
+        }
+    return NESR_OK;
+}
+
+int nesr_sdx4_tiled_workspace_bytes(int n, int latent_channels, int text_hidden, int vae_scale, int h, int w, int tokens, int multiple, int tile, int tile_overlap, int vae_tile,
+                                    int vae_overlap, size_t* bytes) {
+    const char* e = "nesr_sdx4_tiled_workspace_bytes";
+    if (!bytes) return set_error(NESR_ERR_ARG, "nesr_sdx4_tiled_workspace_bytes: null pointer");
+    if (n < 1 || n > 2 || latent_channels < 1 || latent_channels > SDX4_MAX_LATENT_CHANNELS || text_hidden < 1 || tokens < 1 || vae_scale < 2 || vae_scale > 8 || vae_scale % 2)
+        return set_error(NESR_ERR_ARG, "nesr_sdx4_tiled_workspace_bytes: n 1 or 2, latent_channels 1 .. 8, text_hidden and tokens positive, vae_scale 2, 4 or 8");
+    Windows wd;
+    const int rc = check_windows(e, h, w, multiple, tile, tile_overlap, vae_tile, vae_overlap, wd);
+    if (rc) return rc;
+    *bytes = tiled_plan(n, latent_channels, text_hidden, vae_scale, h, w, tokens, wd).total;
+    return NESR_OK;
+}
 
 int nesr_sdx4_schedule(int num_train_timesteps, double beta_start, double beta_end, const char* beta_schedule, const char* prediction_type, int set_alpha_to_one,
                        int steps_offset, const char* timestep_spacing, int steps, int* timesteps, double* alpha_bars, float* coefficients) {
@@ -302,6 +392,96 @@ int nesr_sdx4_upscale_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, c
     return unet_range_end(p->unet, s, "nesr_sdx4_upscale_u8");
 }
 
+int nesr_sdx4_upscale_tiled_u8(nesr_sdx4* p, const uint8_t* frame_dev, int h, int w, const int32_t* ids_host, int tokens, const float* noise_dev, const float* latents_dev,
+                               int noise_level, int steps, double guidance_scale, int tile, int tile_overlap, int vae_tile, int vae_overlap, uint8_t* out_dev, size_t capacity,
+                               float* latents_out_dev, void* stream) {
+    const std::string e = "nesr_sdx4_upscale_tiled_u8";
+    if (!p || !frame_dev || !ids_host || !noise_dev || !latents_dev || !out_dev) return set_error(NESR_ERR_ARG, e + ": null pointer");
+    if (!std::isfinite(guidance_scale)) return set_error(NESR_ERR_ARG, e + ": guidance_scale must be finite");
+    const int n = guidance_scale > 1.0 ? 2 : 1;      // [negative, prompt], or the prompt alone
+    Windows wd;
+    int rc = check_windows(e.c_str(), h, w, 1 << (p->levels - 1), tile, tile_overlap, vae_tile, vae_overlap, wd);
+    if (rc) return rc;
+    {   // the three contexts' own rules, on the shapes they will see
+        size_t bytes = 0;
+        rc = nesr_clip_text_workspace_bytes(p->text, n, tokens, &bytes);
+        if (!rc) rc = nesr_unet_workspace_bytes(p->unet, n, wd.ty, wd.tx, tokens, &bytes);
+        if (!rc) rc = nesr_vae_workspace_bytes(p->vae, wd.vty, wd.vtx, &bytes);
+        if (rc) return rc;
+    }
+    if (noise_level < 0 || noise_level > p->max_noise_level)
+        return set_error(NESR_ERR_ARG, e + ": noise_level must be 0 .. " + std::to_string(p->max_noise_level) + " (max_noise_level), got " + std::to_string(noise_level));
+    if ((rc = check_steps(e.c_str(), p->ddim, steps))) return rc;
+    const Sdx4TextInfo ti = sdx4_text_info(p->text);
+    if (!ti.finalized || !sdx4_unet_info(p->unet).finalized || !sdx4_vae_info(p->vae).finalized) return set_error(NESR_ERR_STATE, e + ": a context's weights are not finalized");
+    for (int i = 0; i < n * tokens; ++i)
+        if (ids_host[i] < 0 || ids_host[i] >= ti.vocab)
+            return set_error(NESR_ERR_ARG, e + ": id " + std::to_string(ids_host[i]) + " at position " + std::to_string(i % tokens) + " of sample " + std::to_string(i / tokens) +
+                                               " is outside the table of " + std::to_string(ti.vocab) + " (vocab_size)");
+    const size_t need = (size_t)3 * h * p->scale * w * p->scale;
+    if (capacity < need) return set_error(NESR_ERR_ARG, e + ": the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
+    for (const void* ptr : {(const void*)noise_dev, (const void*)latents_dev, (const void*)latents_out_dev})
+        if (reinterpret_cast<uintptr_t>(ptr) & 15) return set_error(NESR_ERR_ARG, e + ": the noise and latents pointers must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(frame_dev) & 3) || (reinterpret_cast<uintptr_t>(out_dev) & 3)) return set_error(NESR_ERR_ARG, e + ": the frame and output pointers must be 4-byte aligned");
+    NESR_TRY(hipSetDevice(p->device));
+    const TiledPlan pl = tiled_plan(n, p->lc, ti.hidden, p->scale, h, w, tokens, wd);
+    if ((rc = grow(p->ws_buf, p->ws_bytes, pl.total, kName))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float* text = reinterpret_cast<float*>(p->ws_buf + pl.text);
+    float* frame = reinterpret_cast<float*>(p->ws_buf + pl.frame);
+    float* acc = reinterpret_cast<float*>(p->ws_buf + pl.acc);
+    float* window = reinterpret_cast<float*>(p->ws_buf + pl.window);
+    float* model = reinterpret_cast<float*>(p->ws_buf + pl.model);
+    const int hw = h * w, cin = p->lc + SDX4_IMAGE_CHANNELS;
+    const int ky = sdx4_axis_windows(h, wd.ty, wd.r), kx = sdx4_axis_windows(w, wd.tx, wd.r);
+    const int64_t before = p->timer.launches + ti.launches + sdx4_unet_info(p->unet).launches + sdx4_vae_info(p->vae).launches;
+
+    if ((rc = nesr_clip_text_encode_f32(p->text, ids_host, n, tokens, text, (size_t)n * tokens * ti.hidden, stream))) return rc;
+    if ((rc = unet_range_begin(p->unet, s))) return rc;      // as in nesr_sdx4_upscale_u8: one bracket around every window's forward
+    {   // the full-frame buffer is sdx4_prepare_kernel's sample with n = 1; its second copy of the latents lands in the accumulator,
+        // which is cleared behind it and then kept zero by the step kernel
+        Sdx4Prepare a;
+        memset(&a, 0, sizeof(a));
+        const double ab = p->low_abar[noise_level];
+        a.frame = frame_dev, a.noise = noise_dev, a.latents = latents_dev, a.n = 1, a.hw = hw, a.lc = p->lc;
+        a.sa = (float)std::sqrt(ab), a.sb = (float)std::sqrt(1.0 - ab), a.sigma = 1.0f;
+        a.sample = frame, a.lat_out = acc;
+        NESR_RUN(p->timer, kName, NESR_SDX4_GROUP_PREPARE, s, [&] { return launch_sdx4_prepare(a, s); });
+        NESR_TRY(hipMemsetAsync(acc, 0, (size_t)p->lc * hw * 4, s));
+    }
+    for (int i = 0; i < steps; ++i) {
+        int t;
+        double ab, pv;
+        float coef[6];
+        ddim_step(p->ddim, steps, i, t, ab, pv, coef);
+        for (int iy = 0; iy < ky; ++iy)
+            for (int ix = 0; ix < kx; ++ix) {
+                const Sdx4Axis ay = sdx4_axis(h, wd.ty, wd.r, sdx4_axis_origin(h, wd.ty, wd.r, iy)), ax = sdx4_axis(w, wd.tx, wd.r, sdx4_axis_origin(w, wd.tx, wd.r, ix));
+                Sdx4Gather g;
+                memset(&g, 0, sizeof(g));
+                g.src = frame, g.n = n, g.channels = cin, g.y = ay, g.x = ax, g.dst = window;
+                NESR_RUN(p->timer, kName, NESR_SDX4_GROUP_GATHER, s, [&] { return launch_sdx4_gather(g, s); });
+                if ((rc = unet_forward_unchecked(p->unet, window, n, cin, wd.ty, wd.tx, (double)t, noise_level, text, tokens, model, (size_t)n * p->lc * wd.ty * wd.tx, s))) return rc;
+                Sdx4Accumulate a;
+                memset(&a, 0, sizeof(a));
+                a.model = model, a.n = n, a.lc = p->lc, a.y = ay, a.x = ax, a.g = (float)guidance_scale, a.acc = acc;
+                NESR_RUN(p->timer, kName, NESR_SDX4_GROUP_ACCUMULATE, s, [&] { return launch_sdx4_accumulate(a, s); });
+            }
+        Sdx4TiledStep a;
+        memset(&a, 0, sizeof(a));
+        a.acc = acc, a.frame = frame, a.lc = p->lc, a.y = sdx4_axis(h, wd.ty, wd.r, 0), a.x = sdx4_axis(w, wd.tx, wd.r, 0);
+        a.c0x = coef[0], a.c0m = coef[1], a.cex = coef[2], a.cem = coef[3], a.sp = coef[4], a.sq = coef[5];
+        NESR_RUN(p->timer, kName, NESR_SDX4_GROUP_TILED_STEP, s, [&] { return launch_sdx4_tiled_step(a, s); });
+    }
+    // the final latents are channels 0 .. lc - 1 of the full-frame buffer
+    if ((rc = sdx4_vae_decode_tiled(p->vae, frame, h, w, wd.vty, wd.vtx, wd.vr, p->ws_buf + pl.vae, out_dev, &p->timer, kName,
+                                    Sdx4TileGroups{NESR_SDX4_GROUP_GATHER, NESR_SDX4_GROUP_BLEND_ADD, NESR_SDX4_GROUP_BLEND_FINISH}, s)))
+        return rc;
+    if (latents_out_dev) NESR_TRY(hipMemcpyAsync(latents_out_dev, frame, (size_t)p->lc * hw * 4, hipMemcpyDeviceToDevice, s));      // for the tests; after the last launch
+    p->last_launches = p->timer.launches + sdx4_text_info(p->text).launches + sdx4_unet_info(p->unet).launches + sdx4_vae_info(p->vae).launches - before;
+    return unet_range_end(p->unet, s, "nesr_sdx4_upscale_tiled_u8");
+}
+
 int nesr_sdx4_launches(const nesr_sdx4* p, int64_t* launches) {
     if (!p || !launches) return set_error(NESR_ERR_ARG, "nesr_sdx4_launches: null pointer");
     *launches = p->last_launches;
@@ -342,6 +522,53 @@ int nesr_sdx4_k_step(const float* model_dev, const float* latents_dev, int n, in
     a.c0x = coefficients[0], a.c0m = coefficients[1], a.cex = coefficients[2], a.cem = coefficients[3], a.sp = coefficients[4], a.sq = coefficients[5];
     a.lat_out = latents_out_dev, a.sample = sample_dev;
     return launch_done(launch_sdx4_step(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_step", "launch_sdx4_step");
+}
+
+// the window kernels (sdx4_tiled.hip): an axis is four integers (n, t, r, a) on the host, y first
+namespace {
+Sdx4Axis axis_of(const int* v) { return Sdx4Axis{v[0], v[1], v[2], v[3]}; }
+const char* const kAxes = ": the axes are two rows of (n, t, r, a) on the host; nothing was launched";
+}  // namespace
+
+int nesr_sdx4_k_window_gather(const float* src_dev, int n, int channels, const int* axes, float* dst_dev, void* stream) {
+    if (!axes) return set_error(NESR_ERR_ARG, std::string("nesr_sdx4_k_window_gather") + kAxes);
+    Sdx4Gather a;
+    memset(&a, 0, sizeof(a));
+    a.src = src_dev, a.n = n, a.channels = channels, a.y = axis_of(axes), a.x = axis_of(axes + 4), a.dst = dst_dev;
+    return launch_done(launch_sdx4_gather(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_window_gather", "launch_sdx4_gather");
+}
+
+int nesr_sdx4_k_accumulate(const float* model_dev, int n, int lc, const int* axes, float guidance, float* acc_dev, void* stream) {
+    if (!axes) return set_error(NESR_ERR_ARG, std::string("nesr_sdx4_k_accumulate") + kAxes);
+    Sdx4Accumulate a;
+    memset(&a, 0, sizeof(a));
+    a.model = model_dev, a.n = n, a.lc = lc, a.y = axis_of(axes), a.x = axis_of(axes + 4), a.g = guidance, a.acc = acc_dev;
+    return launch_done(launch_sdx4_accumulate(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_accumulate", "launch_sdx4_accumulate");
+}
+
+int nesr_sdx4_k_tiled_step(float* acc_dev, float* frame_dev, int lc, const int* axes, const float* coefficients, void* stream) {
+    if (!axes || !coefficients) return set_error(NESR_ERR_ARG, std::string("nesr_sdx4_k_tiled_step") + kAxes);
+    Sdx4TiledStep a;
+    memset(&a, 0, sizeof(a));
+    a.acc = acc_dev, a.frame = frame_dev, a.lc = lc, a.y = axis_of(axes), a.x = axis_of(axes + 4);
+    a.c0x = coefficients[0], a.c0m = coefficients[1], a.cex = coefficients[2], a.cem = coefficients[3], a.sp = coefficients[4], a.sq = coefficients[5];
+    return launch_done(launch_sdx4_tiled_step(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_tiled_step", "launch_sdx4_tiled_step");
+}
+
+int nesr_sdx4_k_blend_add(const float* sample_dev, const int* axes, float* acc_dev, void* stream) {
+    if (!axes) return set_error(NESR_ERR_ARG, std::string("nesr_sdx4_k_blend_add") + kAxes);
+    Sdx4BlendAdd a;
+    memset(&a, 0, sizeof(a));
+    a.sample = sample_dev, a.y = axis_of(axes), a.x = axis_of(axes + 4), a.acc = acc_dev;
+    return launch_done(launch_sdx4_blend_add(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_blend_add", "launch_sdx4_blend_add");
+}
+
+int nesr_sdx4_k_blend_finish(const float* acc_dev, const int* axes, uint8_t* out_dev, void* stream) {
+    if (!axes) return set_error(NESR_ERR_ARG, std::string("nesr_sdx4_k_blend_finish") + kAxes);
+    Sdx4BlendFinish a;
+    memset(&a, 0, sizeof(a));
+    a.acc = acc_dev, a.y = axis_of(axes), a.x = axis_of(axes + 4), a.out = out_dev;
+    return launch_done(launch_sdx4_blend_finish(a, (hipStream_t)stream), "csrc/sdx4_api.h", "nesr_sdx4_k_blend_finish", "launch_sdx4_blend_finish");
 }
 
 }  // extern "C"

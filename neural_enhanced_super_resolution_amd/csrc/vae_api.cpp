@@ -8,6 +8,8 @@
 #include "net_context.h"
 #include "vae_api.h"
 
+#include "sdx4_api.h"
+
 using namespace nesr;
 
 namespace {
@@ -46,6 +48,8 @@ struct nesr_vae : NetContext {
     NormW attn_norm, norm_out;
     LinW qkv, to_out;
     std::vector<VUpW> ups;
+    char* tile_buf = nullptr;      // nesr_vae_decode_latents_tiled_u8: a window's latents and sample, the f32 frame
+    size_t tile_bytes = 0;
 };
 
 namespace {
@@ -245,7 +249,14 @@ int nesr_vae_create(nesr_vae** out, int device_id, int latent_channels, int out_
     return NESR_OK;
 }
 
-void nesr_vae_destroy(nesr_vae* c) { net_destroy(c); }
+void nesr_vae_destroy(nesr_vae* c) {
+    if (c && c->tile_buf && c->device != NET_NO_DEVICE) {
+        (void)hipSetDevice(c->device);
+        (void)hipDeviceSynchronize();
+        (void)hipFree(c->tile_buf);
+    }
+    net_destroy(c);
+}
 
 int nesr_vae_num_tensors(const nesr_vae* c) { return net_num_tensors(c); }
 
@@ -332,6 +343,27 @@ int nesr_vae_decode_latents_u8(nesr_vae* c, const float* latents, int N, int C, 
     return decode(c, latents, (float)c->scaling, h, w, out, true, static_cast<hipStream_t>(stream));
 }
 
+int nesr_vae_decode_latents_tiled_u8(nesr_vae* c, const float* latents, int N, int C, int h, int w, int tile, int tile_overlap, uint8_t* out, size_t capacity, void* stream) {
+    const std::string e = "nesr_vae_decode_latents_tiled_u8";
+    if (!c || !latents || !out) return set_error(NESR_ERR_ARG, e + ": null pointer");
+    if (c->nout != 3) return set_error(NESR_ERR_ARG, e + ": an RGB frame needs out_channels = 3");
+    if (!c->finalized) return set_error(NESR_ERR_STATE, e + ": weights not finalized (nesr_vae_finalize)");
+    if (N != 1 || C != c->lat) return set_error(NESR_ERR_ARG, e + ": expected [1, " + std::to_string(c->lat) + ", h, w]");
+    if (h < 2 || w < 2 || h % 2 || w % 2 || (long long)h * w > SDX4_MAX_FRAME_PIXELS)
+        return set_error(NESR_ERR_ARG, e + ": h and w must be positive multiples of 2 and h w at most 2^22, got " + std::to_string(h) + " x " + std::to_string(w));
+    int ty = 0, tx = 0;
+    const int rc = sdx4_check_windows(e.c_str(), "tile", h, w, 2, tile, tile_overlap, &ty, &tx);
+    if (rc) return rc;
+    const size_t sc = (size_t)1 << (c->nb - 1), need = 3 * h * sc * w * sc;
+    if (capacity < need) return set_error(NESR_ERR_ARG, e + ": the output needs " + std::to_string(need) + " bytes, capacity is " + std::to_string(capacity));
+    if ((reinterpret_cast<uintptr_t>(latents) & 7) || (reinterpret_cast<uintptr_t>(out) & 3))
+        return set_error(NESR_ERR_ARG, e + ": the latents pointer must be 8-byte aligned, the output 4-byte");
+    NESR_TRY(hipSetDevice(c->device));
+    const int grc = grow(c->tile_buf, c->tile_bytes, sdx4_vae_tiled_plan(c->lat, (int)sc, h, w, ty, tx).total, kName);
+    if (grc) return grc;
+    return sdx4_vae_decode_tiled(c, latents, h, w, ty, tx, tile_overlap, c->tile_buf, out, nullptr, kName, Sdx4TileGroups{0, 0, 0}, static_cast<hipStream_t>(stream));
+}
+
 int nesr_vae_set_timing(nesr_vae* c, int enable) { return net_set_timing(c, "nesr_vae_set_timing", enable); }
 
 int nesr_vae_kernel_time_ms(nesr_vae* c, double* group_ms, int n_groups, int64_t* launches) {
@@ -341,7 +373,59 @@ int nesr_vae_kernel_time_ms(nesr_vae* c, double* group_ms, int n_groups, int64_t
 }  // extern "C"
 
 // what the x4 pipeline (sdx4_api.cpp) asks of a context it does not own
-#include "sdx4_api.h"
 nesr::Sdx4VaeInfo nesr::sdx4_vae_info(const nesr_vae* c) {
     return Sdx4VaeInfo{c->device, c->lat, c->nout, c->nb, c->finalized, c->timer.launches};
+}
+
+// The decode over windows (sdx4_api.h): shared by nesr_vae_decode_latents_tiled_u8 above and nesr_sdx4_upscale_tiled_u8, which
+// brings its own buffer and timer.
+nesr::Sdx4VaeTiledPlan nesr::sdx4_vae_tiled_plan(int lc, int scale, int h, int w, int ty, int tx) {
+    Sdx4VaeTiledPlan pl;
+    ScratchCarver ws;
+    const size_t sc = (size_t)scale;
+    pl.window = ws.take((size_t)lc * ty * tx * 4);
+    pl.sample = ws.take(3 * ty * sc * tx * sc * 4);
+    pl.acc = ws.take(3 * h * sc * w * sc * 4);
+    pl.total = ws.total();
+    return pl;
+}
+
+int nesr::sdx4_vae_decode_tiled(nesr_vae* c, const float* latents, int h, int w, int ty, int tx, int r, char* buf, uint8_t* out, GroupTimer* timer, const char* model,
+                                Sdx4TileGroups groups, hipStream_t s) {
+    const int sc = 1 << (c->nb - 1);
+    const Sdx4VaeTiledPlan pl = sdx4_vae_tiled_plan(c->lat, sc, h, w, ty, tx);
+    float* window = reinterpret_cast<float*>(buf + pl.window);
+    float* sample = reinterpret_cast<float*>(buf + pl.sample);
+    float* acc = reinterpret_cast<float*>(buf + pl.acc);
+    {   // the decode's own workspace has its size before the first launch
+        size_t act, part;
+        const int rc = grow(c->ws_buf, c->ws_bytes, workspace_bytes(c, ty, tx, act, part), kName);
+        if (rc) return rc;
+    }
+    // one window kernel: through the caller's timer, or as it is
+    auto run = [&](int group, auto&& launch) -> int {
+        if (timer) return timer->run(model, group, s, launch);
+        const hipError_t e = launch();
+        return e == hipSuccess ? NESR_OK : set_error(NESR_ERR_HIP, std::string(model) + " launch (window kernel): " + hipGetErrorString(e));
+    };
+    int rc;
+    NESR_TRY(hipMemsetAsync(acc, 0, (size_t)3 * h * sc * w * sc * 4, s));
+    const int ky = sdx4_axis_windows(h, ty, r), kx = sdx4_axis_windows(w, tx, r);
+    for (int iy = 0; iy < ky; ++iy)
+        for (int ix = 0; ix < kx; ++ix) {
+            const int ay = sdx4_axis_origin(h, ty, r, iy), ax = sdx4_axis_origin(w, tx, r, ix);
+            Sdx4Gather g;
+            memset(&g, 0, sizeof(g));
+            g.src = latents, g.n = 1, g.channels = c->lat, g.y = sdx4_axis(h, ty, r, ay), g.x = sdx4_axis(w, tx, r, ax), g.dst = window;
+            if ((rc = run(groups.gather, [&] { return launch_sdx4_gather(g, s); }))) return rc;
+            if ((rc = decode(c, window, (float)c->scaling, ty, tx, sample, false, s))) return rc;
+            Sdx4BlendAdd b;
+            memset(&b, 0, sizeof(b));
+            b.sample = sample, b.y = sdx4_axis(h, ty, r, ay, sc), b.x = sdx4_axis(w, tx, r, ax, sc), b.acc = acc;
+            if ((rc = run(groups.add, [&] { return launch_sdx4_blend_add(b, s); }))) return rc;
+        }
+    Sdx4BlendFinish f;
+    memset(&f, 0, sizeof(f));
+    f.acc = acc, f.y = sdx4_axis(h, ty, r, 0, sc), f.x = sdx4_axis(w, tx, r, 0, sc), f.out = out;
+    return run(groups.finish, [&] { return launch_sdx4_blend_finish(f, s); });
 }

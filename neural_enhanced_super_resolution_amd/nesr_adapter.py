@@ -340,18 +340,20 @@ def swin2sr_stage(model, device=None, tile=0, tile_pad=16, max_batch=None, tile_
 
 
 def diffusion_stage(pipe, prompt="a high resolution, detailed photograph", noise_level=20, num_inference_steps=20, guidance_scale=7.5, seed=None,
-                    prompt_ids=None, negative_ids=None, device=None):
+                    prompt_ids=None, negative_ids=None, device=None, tile=None, tile_overlap=0, vae_tile=None, vae_overlap=None):
     """A sdx4.StableDiffusionX4Upscaler as an `extra_upscalers` entry of enhance_iterations: RGB u8 frame -> the x4 RGB u8 frame,
     kept on the device.  It is the reference's _apply_diffusion (nesr.py:988-1031) with its CUDA settings as defaults: the slot its
     ensemble (nesr.py:570-584) gives the diffusion result.  `prompt` needs the pipeline's tokenizer; `prompt_ids` / `negative_ids`
     replace it.  `seed`: every frame draws from a generator seeded with it (None: torch's global generator of the device).  A frame
-    over the VAE's limit of 65536 low-res pixels raises NesrUnsupportedError naming the limit; tiling is out of scope."""
+    over the VAE's limit of 65536 low-res pixels raises NesrUnsupportedError naming the limit unless `tile` is given: then the loop and
+    the decode run over overlapping windows (upscale_frame's tile, tile_overlap, vae_tile, vae_overlap)."""
     def stage(frame_rgb):
         if not (isinstance(frame_rgb, torch.Tensor) and frame_rgb.is_cuda):
             frame_rgb = _u8_on(frame_rgb, torch.device("cuda") if device is None else torch.device(device))
         generator = None if seed is None else torch.Generator(device=frame_rgb.device).manual_seed(int(seed))
         return pipe.upscale_frame(frame_rgb, prompt=prompt, noise_level=noise_level, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                  generator=generator, prompt_ids=prompt_ids, negative_ids=negative_ids)
+                                  generator=generator, prompt_ids=prompt_ids, negative_ids=negative_ids, tile=tile, tile_overlap=tile_overlap, vae_tile=vae_tile,
+                                  vae_overlap=vae_overlap)
     return stage
 
 

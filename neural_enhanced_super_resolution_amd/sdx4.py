@@ -2,13 +2,15 @@
 reference's second upscaler (nesr/nesr.py:243-283 loads it, :988-1031 calls it, :570-584 puts its result into the ensemble), as one
 C call: ``nesr_sdx4_upscale_u8`` (csrc/sdx4_api.cpp) chains ``ClipTextEncoder``, ``UNet2DCondition`` and ``VaeDecoder`` with the two
 kernels of csrc/sdx4_step.hip, which are the schedulers and the guidance.  A prompt's ids and a u8 frame in, the x4 u8 frame out,
-with no host round trip inside the denoising loop.
+with no host round trip inside the denoising loop.  With ``tile=`` the loop and the decode run over overlapping windows of one
+shape, blended on the device (``nesr_sdx4_upscale_tiled_u8``, csrc/sdx4_tiled.hip): that is how a frame above the VAE's limit runs.
 
 diffusers is not a dependency and nothing is fetched: the schedulers and the loop are written from memory of the library, and
 DESIGN section 20 says "recalled" about each such value.  Departures on purpose: frames whose sides are no multiple of 8 are padded
 up by edge replication and the x4 result is cropped (diffusers resizes, as recalled); random numbers come from this process's
 torch generator on the ROCm device, so a CUDA run's draws are not reproduced; eta is 0, one image a prompt, no callbacks, no
-watermarker, no fp16 form, and a frame above 65536 low-res pixels is refused (tiling is out of scope).
+watermarker, no fp16 form, and a frame above 65536 low-res pixels is refused unless ``tile`` is given.  The tiling is this project's
+own specification (one shared latent frame, ramped seams: DESIGN section 22); how diffusers tiles is recalled, not checked.
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ import torch
 
 from . import _lib
 from ._contexts import _invoke
+from ._tiling import sdx4_tile_plan
 from .clip_text import ClipTextEncoder
 from .unet import UNet2DCondition
 from .vae import VaeDecoder
@@ -32,7 +35,7 @@ DDIM_DEFAULTS = dict(num_train_timesteps=1000, beta_start=1e-4, beta_end=0.02, b
 LOW_RES_DEFAULTS = dict(num_train_timesteps=1000, beta_schedule="squaredcos_cap_v2")
 SCHEDULER_CLASS, LOW_RES_CLASS = "DDIMScheduler", "DDPMScheduler"
 MAX_NOISE_LEVEL = 350
-KERNEL_GROUPS = ("prepare", "step")      # NESR_SDX4_GROUP_*
+KERNEL_GROUPS = ("prepare", "step", "window_gather", "accumulate", "tiled_step", "blend_add", "blend_finish")      # NESR_SDX4_GROUP_*
 FRAME_MULTIPLE = 8                       # __call__ pads to it: 2^(levels - 1) of the published UNet
 MAX_LOW_RES_PIXELS = 1 << 16             # NESR_VAE_MAX_TOKENS
 
@@ -184,7 +187,7 @@ class StableDiffusionX4Upscaler:
             m.set_kernel_timing(enable)
 
     def kernel_time_ms(self):
-        """{"launches", "groups": {"prepare", "step"}} of the pipeline's own kernels since the last call."""
+        """{"launches", "groups": {name of KERNEL_GROUPS: ms}} of the pipeline's own kernels since the last call."""
         launches, groups = 0, dict.fromkeys(KERNEL_GROUPS, 0.0)
         for index, (handle, _) in self._pipes.items():
             ms, n = (ctypes.c_double * len(KERNEL_GROUPS))(), ctypes.c_int64(0)
@@ -196,15 +199,40 @@ class StableDiffusionX4Upscaler:
         return {"launches": launches, "groups": groups}
 
     def last_launches(self, device=None):
-        """Kernel launches of the last upscale on `device`: text + 1 + steps (UNet + 1) + VAE."""
+        """Kernel launches of the last upscale on `device`: text + 1 + steps (UNet + 1) + VAE; of a tiled one: text + 1 + steps
+        (windows (1 + UNet + 1) + 1) + vae_windows (1 + VAE + 1) + 1."""
         device = torch.device("cuda" if device is None else device)
         n = ctypes.c_int64(0)
         with torch.cuda.device(device):
             _invoke("nesr_sdx4_launches", None, self._pipeline(device), (ctypes.byref(n),))
         return n.value
 
-    def workspace_bytes(self, n, h, w, tokens, device=None):
-        """Bytes the pipeline itself allocates for n samples of an h x w frame (the networks report their own)."""
+    def frame_multiple(self):
+        """2^(levels - 1) of this UNet: what a frame's sides, `tile` and `tile_overlap` are multiples of."""
+        return 2 ** (len(self.unet.config["block_out_channels"]) - 1)
+
+    def tile_plan(self, h, w, tile, tile_overlap=0):
+        """((tiles_y, tiles_x), (ty, tx), [(y, x)]) of an h x w low-res frame as the library computes it (nesr_sdx4_tile_plan): the
+        windows of `upscale(tile=, tile_overlap=)` in the order they run.  Needs no device."""
+        counts = [ctypes.c_int(0) for _ in range(4)]
+        args = (int(h), int(w), self.frame_multiple(), int(tile), int(tile_overlap))
+        lib = _lib.load()
+        _check(lib.nesr_sdx4_tile_plan(*args, *counts, None, 0), "nesr_sdx4_tile_plan")
+        ky, kx, ty, tx = (c.value for c in counts)
+        plan = (ctypes.c_int32 * (2 * ky * kx))()
+        _check(lib.nesr_sdx4_tile_plan(*args, *counts, plan, len(plan)), "nesr_sdx4_tile_plan")
+        return (ky, kx), (ty, tx), [(plan[2 * i], plan[2 * i + 1]) for i in range(ky * kx)]
+
+    def workspace_bytes(self, n, h, w, tokens, device=None, tile=None, tile_overlap=0, vae_tile=None, vae_overlap=None):
+        """Bytes the pipeline itself allocates for n samples of an h x w frame (the networks report their own); with `tile`, of the
+        tiled call (no device needed)."""
+        if tile is not None:
+            size = ctypes.c_size_t(0)
+            _check(_lib.load().nesr_sdx4_tiled_workspace_bytes(int(n), int(self.vae.config["latent_channels"]), int(self.text_encoder.config["hidden_size"]),
+                                                               2 ** (len(self.vae.config["block_out_channels"]) - 1), int(h), int(w), int(tokens), self.frame_multiple(),
+                                                               int(tile), int(tile_overlap), 0 if vae_tile is None else int(vae_tile),
+                                                               -1 if vae_overlap is None else int(vae_overlap), ctypes.byref(size)), "nesr_sdx4_tiled_workspace_bytes")
+            return size.value
         device = torch.device("cuda" if device is None else device)
         size = ctypes.c_size_t(0)
         with torch.cuda.device(device):
@@ -220,17 +248,26 @@ class StableDiffusionX4Upscaler:
         return ids
 
     def upscale(self, frame, prompt_ids=None, negative_ids=None, noise_level=20, num_inference_steps=20, guidance_scale=7.5, generator=None, noise=None,
-                latents=None, return_latents=False):
+                latents=None, return_latents=False, tile=None, tile_overlap=0, vae_tile=None, vae_overlap=None):
         """frame [h, w, 3] uint8 RGB on the device -> the x4 frame [4h, 4w, 3] uint8 on the device (and, return_latents, the final
         float32 latents [1, 4, h, w]).  prompt_ids / negative_ids: one row of token ids each, of the same length (negative_ids is
         needed when guidance_scale > 1).  noise [3, h, w] and latents [4, h, w]: unit normal float32 on the device; what is not given
-        is drawn with torch.randn(generator=generator) on the frame's device, the low-res noise first, then the latents."""
+        is drawn with torch.randn(generator=generator) on the frame's device, the low-res noise first, then the latents.
+        tile (low-res pixels; None: the untiled call, unchanged): the denoising loop runs over overlapping windows of min(tile, h) x
+        min(tile, w) on one shared latent frame, seams ramped over tile_overlap pixels, and the VAE decodes over windows of vae_tile
+        / vae_overlap (None: tile / tile_overlap); tile_plan() gives the windows.  noise and latents stay full-frame draws."""
         if not (torch.is_tensor(frame) and frame.is_cuda):
             raise RuntimeError("StableDiffusionX4Upscaler.upscale: the frame is not on the ROCm device (there is no CPU or PyTorch fallback)")
         if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8 or frame.numel() == 0:
             raise ValueError(f"StableDiffusionX4Upscaler.upscale: an [h, w, 3] uint8 tensor, got {frame.dtype} {tuple(frame.shape)}")
         if prompt_ids is None:
             raise ValueError("StableDiffusionX4Upscaler.upscale: prompt_ids is required (a tokenizer's input_ids of the prompt)")
+        if tile is None and (tile_overlap or vae_tile is not None or vae_overlap is not None):
+            raise ValueError("StableDiffusionX4Upscaler.upscale: tile_overlap, vae_tile and vae_overlap need tile")
+        if vae_tile is not None and int(vae_tile) < 1:      # the C entry reads 0 as "tile" and a negative overlap as "tile_overlap": None says that here
+            raise ValueError(f"StableDiffusionX4Upscaler.upscale: vae_tile must be positive (None: tile), got {vae_tile}")
+        if vae_overlap is not None and int(vae_overlap) < 0:
+            raise ValueError(f"StableDiffusionX4Upscaler.upscale: vae_overlap must not be negative (None: tile_overlap), got {vae_overlap}")
         frame = frame.contiguous()
         h, w = int(frame.shape[0]), int(frame.shape[1])
         device = frame.device
@@ -262,10 +299,20 @@ class StableDiffusionX4Upscaler:
             scale = 2 ** (len(self.vae.config["block_out_channels"]) - 1)
             out = torch.empty((h * scale, w * scale, 3), dtype=torch.uint8, device=device)
             final = torch.empty((1, lc, h, w), dtype=torch.float32, device=device) if return_latents else None
-            _invoke("nesr_sdx4_upscale_u8", device, handle, (frame, h, w, host, tokens, noise, latents, int(noise_level), int(num_inference_steps),
-                                                            ctypes.c_double(float(guidance_scale)), out, out.numel(), final))
+            if tile is None:
+                _invoke("nesr_sdx4_upscale_u8", device, handle, (frame, h, w, host, tokens, noise, latents, int(noise_level), int(num_inference_steps),
+                                                                ctypes.c_double(float(guidance_scale)), out, out.numel(), final))
+                windows = vae_windows = 1
+            else:
+                vt, vo = (0 if vae_tile is None else int(vae_tile)), (-1 if vae_overlap is None else int(vae_overlap))
+                _invoke("nesr_sdx4_upscale_tiled_u8", device, handle, (frame, h, w, host, tokens, noise, latents, int(noise_level), int(num_inference_steps),
+                                                                      ctypes.c_double(float(guidance_scale)), int(tile), int(tile_overlap), vt, vo, out, out.numel(), final))
+                m = self.frame_multiple()
+                (ky, kx), _, _ = sdx4_tile_plan(h, w, m, int(tile), int(tile_overlap))
+                (vy, vx), _, _ = sdx4_tile_plan(h, w, m, int(tile) if vae_tile is None else int(vae_tile), int(tile_overlap) if vae_overlap is None else int(vae_overlap))
+                windows, vae_windows = ky * kx, vy * vx
         self.calls += 1
-        for m, count in ((self.text_encoder, 1), (self.unet, int(num_inference_steps)), (self.vae, 1)):
+        for m, count in ((self.text_encoder, 1), (self.unet, int(num_inference_steps) * windows), (self.vae, vae_windows)):
             m.calls += count
         return (out, final) if return_latents else out
 
@@ -279,10 +326,11 @@ class StableDiffusionX4Upscaler:
         return list(self.tokenizer(prompt, padding="max_length", max_length=length, truncation=True)["input_ids"])
 
     def upscale_frame(self, image, prompt=None, noise_level=20, num_inference_steps=20, guidance_scale=7.5, negative_prompt=None, generator=None,
-                      prompt_ids=None, negative_ids=None, device=None):
+                      prompt_ids=None, negative_ids=None, device=None, tile=None, tile_overlap=0, vae_tile=None, vae_overlap=None):
         """`__call__` without the trip home: image (a PIL image, an [H, W, 3] uint8 ndarray or a device tensor) -> the device uint8
         [4H, 4W, 3] frame.  Sides that are no multiple of 8 are padded up by edge replication and the result is cropped (diffusers
-        resizes instead, as recalled).  A frame above the VAE's limit raises NesrUnsupportedError naming it."""
+        resizes instead, as recalled).  A frame above the VAE's limit raises NesrUnsupportedError naming it, unless `tile` is given:
+        then it runs over windows (upscale's tile, tile_overlap, vae_tile, vae_overlap)."""
         if image is None:
             raise ValueError("StableDiffusionX4Upscaler: image is required")
         if prompt_ids is None:
@@ -296,7 +344,7 @@ class StableDiffusionX4Upscaler:
             raise ValueError(f"StableDiffusionX4Upscaler: image is RGB uint8 [H, W, 3], got {frame.dtype} {tuple(frame.shape)}")
         H, W = int(frame.shape[0]), int(frame.shape[1])
         ph, pw = -H % FRAME_MULTIPLE, -W % FRAME_MULTIPLE
-        if (H + ph) * (W + pw) > MAX_LOW_RES_PIXELS:
+        if tile is None and (H + ph) * (W + pw) > MAX_LOW_RES_PIXELS:
             raise _lib.NesrUnsupportedError(f"StableDiffusionX4Upscaler: a frame of {H} x {W} exceeds the VAE's limit of {MAX_LOW_RES_PIXELS} low-res pixels "
                                             "(NESR_VAE_MAX_TOKENS; tiling is out of scope)")
         if not frame.is_cuda:
@@ -306,17 +354,19 @@ class StableDiffusionX4Upscaler:
             cols = torch.cat([torch.arange(W), torch.full((pw,), W - 1, dtype=torch.int64)]).to(frame.device)
             frame = frame[rows][:, cols]
         out = self.upscale(frame, prompt_ids=prompt_ids, negative_ids=negative_ids, noise_level=noise_level, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale, generator=generator)
+                           guidance_scale=guidance_scale, generator=generator, tile=tile, tile_overlap=tile_overlap, vae_tile=vae_tile, vae_overlap=vae_overlap)
         scale = out.shape[0] // frame.shape[0]
         return out[:H * scale, :W * scale].contiguous() if (ph or pw) else out
 
     def __call__(self, prompt=None, image=None, noise_level=20, num_inference_steps=20, guidance_scale=7.5, negative_prompt=None, generator=None,
-                 prompt_ids=None, negative_ids=None, eta=0.0, num_images_per_prompt=1, device=None, **unsupported):
+                 prompt_ids=None, negative_ids=None, eta=0.0, num_images_per_prompt=1, device=None, tile=None, tile_overlap=0, vae_tile=None, vae_overlap=None,
+                 **unsupported):
         """The reference's call (nesr/nesr.py:1001-1025): returns an object whose .images[0] is the host uint8 [4H, 4W, 3] array."""
         if unsupported:
             raise _lib.NesrUnsupportedError(f"StableDiffusionX4Upscaler: argument(s) {sorted(unsupported)} are not supported")
         if eta != 0.0 or num_images_per_prompt != 1:
             raise _lib.NesrUnsupportedError("StableDiffusionX4Upscaler: eta 0 and num_images_per_prompt 1 only")
         out = self.upscale_frame(image, prompt=prompt, noise_level=noise_level, num_inference_steps=num_inference_steps, guidance_scale=guidance_scale,
-                                 negative_prompt=negative_prompt, generator=generator, prompt_ids=prompt_ids, negative_ids=negative_ids, device=device)
+                                 negative_prompt=negative_prompt, generator=generator, prompt_ids=prompt_ids, negative_ids=negative_ids, device=device,
+                                 tile=tile, tile_overlap=tile_overlap, vae_tile=vae_tile, vae_overlap=vae_overlap)
         return UpscaleOutput([out.cpu().numpy()])

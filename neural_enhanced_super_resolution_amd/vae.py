@@ -26,6 +26,7 @@ import torch
 from . import _lib
 from ._contexts import _invoke
 from ._hfnet import _HFNet, _merged_config
+from ._tiling import sdx4_tile_plan
 
 # the published x4 upscaler's values, recalled from memory: a config.json beside the weights, or the arguments, override them
 DEFAULTS = dict(latent_channels=4, out_channels=3, block_out_channels=(128, 256, 512), layers_per_block=2, norm_num_groups=32,
@@ -153,14 +154,24 @@ class VaeDecoder(_HFNet):
 
     forward = decode
 
-    def decode_latents_u8(self, latents):
+    def decode_latents_u8(self, latents, tile=None, tile_overlap=0):
         """latents [1, latent_channels, h, w] float32 on the device, as the denoising loop leaves them -> the uint8 RGB frame
-        [h s, w s, 3] on the device: / scaling_factor, decode, / 2 + 0.5, clamp, x 255, round half to even."""
+        [h s, w s, 3] on the device: / scaling_factor, decode, / 2 + 0.5, clamp, x 255, round half to even.
+        `tile` (latent pixels): the decode runs over overlapping windows of min(tile, h) x min(tile, w) whose seams are blended on
+        the device with ramps of `tile_overlap` (nesr_vae_decode_latents_tiled_u8), which lifts the limit of 65536 latents; h, w,
+        tile and tile_overlap are even.  One window gives the untiled bytes.  `calls` rises by the number of windows."""
         z = self._latents(latents, "decode_latents_u8")
         n, ch, h, w = z.shape
         with torch.cuda.device(z.device):
             handle = self._context(z.device)
-            out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=z.device)
-            _invoke("nesr_vae_decode_latents_u8", z.device, handle, (z, n, ch, h, w, out, out.numel()))
-        self.calls += 1
+            if tile is None:
+                out = torch.empty(self.output_size(h, w) + (3,), dtype=torch.uint8, device=z.device)
+                _invoke("nesr_vae_decode_latents_u8", z.device, handle, (z, n, ch, h, w, out, out.numel()))
+                self.calls += 1
+                return out
+            s = 2 ** (len(self.config["block_out_channels"]) - 1)
+            out = torch.empty((h * s, w * s, 3), dtype=torch.uint8, device=z.device)
+            _invoke("nesr_vae_decode_latents_tiled_u8", z.device, handle, (z, n, ch, h, w, int(tile), int(tile_overlap), out, out.numel()))
+        (ky, kx), _, _ = sdx4_tile_plan(h, w, 2, int(tile), int(tile_overlap))
+        self.calls += ky * kx
         return out
